@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — captions/sec of the ExpansionNet v2 hot path on N MI355X (one process per GPU).
 
-    python bench.py --gpus N --steps K --warmup W [--workload e2e16|features48|coco5k]
+    python bench.py --gpus N --steps K --warmup W [--workload e2e16|features48|coco5k] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; `--full` adds the extra measurements and
+checks listed below.  `--dump-outputs DIR` writes what the timed path returned for its last step (rank 0's captions) as
+DIR/captions.npy (float64 token ids [n, T], padded with -1) and DIR/caption_lengths.npy (float64 [n]); the inputs and
+weights are seeded, so two builds can be compared output for output.
 
 With N > 1 and no torchrun environment the script launches its own N ranks (fresh child processes, one per
 GPU, started before this process makes any GPU call); under `python -m torch.distributed.run` it is one of
@@ -17,7 +22,7 @@ Workloads (`config.workload` in the output line):
 Synthetic xavier weights never emit EOS, so every caption runs its full decode length.  Inputs are resident
 in HBM when the timed region starts.  Weak scaling: every rank processes its own batch / shard.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries extra objects:
   roofline      dominant kernel family (by time) of the step, HIP events on the launch stream around every
                 C-ABI call in one instrumented eager pass (torch.cuda.Event on the current stream = the stream
                 the kernels are launched on); `kernels` lists every family
@@ -81,6 +86,10 @@ def parse():
     ap.add_argument("--max-len", type=int, default=None)
     ap.add_argument("--shard", type=int, default=None, help="coco5k: images per rank per step")
     ap.add_argument("--precision", default=None, choices=["bf16", "fp32", "fp8", "x3"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity checks, roofline pass, x3 / fp32 mode timings and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the captions of the last timed step as DIR/*.npy")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -109,6 +118,8 @@ def parse():
         a.max_len = w["max_len"]
     if a.shard is None:
         a.shard = w.get("shard", 0)
+    if not a.full:                     # a plain run measures the headline figure only
+        a.no_parity = a.no_roofline = a.no_exact = a.no_fp32 = a.no_cpu_baseline = True
     return a
 
 
@@ -365,6 +376,18 @@ def cpu_baseline(sd, g, runs, beam, max_len, end_to_end=True):
                       f"{detail}; torch default threads {default_threads}, os.cpu_count()={os.cpu_count()}"}
 
 
+def dump_outputs(path, caps, width):
+    """The captions of the last timed step (token-id lists) as float64 arrays: captions.npy [n, width] padded
+    with -1, caption_lengths.npy [n]."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    toks = np.full((len(caps), width), -1.0, dtype=np.float64)
+    for i, c in enumerate(caps):
+        toks[i, :len(c)] = c
+    np.save(os.path.join(path, "captions.npy"), toks)
+    np.save(os.path.join(path, "caption_lengths.npy"), np.array([len(c) for c in caps], dtype=np.float64))
+
+
 # =================================================================================================
 def selftest_rank(a, world, rank):
     """Rank plumbing without a GPU: gloo group, barrier, MAX-reduced time, rank 0 prints the line."""
@@ -483,6 +506,8 @@ def main():
     per_step = a.shard if a.workload == "coco5k" else a.batch
 
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, caps, pipe.T)
         out = {
             "metric": "captions/sec end-to-end (Swin-L 384, beam=3) at 1/2/4/8 MI355X" if a.workload in ("e2e16", "fp8b64")
                       else f"captions/sec ({a.workload})",

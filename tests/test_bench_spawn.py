@@ -75,3 +75,30 @@ def test_gpu_count_comes_from_sysfs_not_from_hip(tmp_path, monkeypatch):
     src = open(BENCH).read()
     body = src[src.index("def spawn_ranks"):src.index("# model / pipeline")]
     assert "import torch" not in body and "device_count" not in body
+
+
+def test_plain_run_is_lean_and_full_keeps_the_extras(monkeypatch):
+    """A plain run does only the timed steps; --full brings back the parity checks, roofline pass, x3 / fp32 timings
+    and CPU baseline, and the --no-* switches still apply under --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    extras = ("no_parity", "no_roofline", "no_exact", "no_fp32", "no_cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-fp32"])
+    a = bench.parse()
+    assert a.full and a.no_fp32 and not any(getattr(a, k) for k in extras if k != "no_fp32")
+
+
+def test_dump_outputs_writes_padded_float_captions(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.dump_outputs(str(tmp_path / "out"), [[79, 5, 6], [79, 8]], 4)
+    toks = np.load(tmp_path / "out" / "captions.npy")
+    lens = np.load(tmp_path / "out" / "caption_lengths.npy")
+    assert toks.dtype == np.float64 and lens.dtype == np.float64
+    np.testing.assert_array_equal(toks, [[79, 5, 6, -1], [79, 8, -1, -1]])
+    np.testing.assert_array_equal(lens, [3, 2])

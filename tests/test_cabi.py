@@ -113,18 +113,34 @@ def test_reference_api_surface():
         E2E_ExpansionNet_Captioner({"sos_idx": 1, "eos_idx": 2}, split_encoder=True)
 
 
-def test_preprocess_matches_recorded_checksums():
+def test_preprocess_matches_recorded_checksums(tmp_path):
+    """The two small demo JPEGs are stored in tests/golden/demo_material and checked against the checksums recorded
+    from them.  The two large ones (3456x4608 and 3394x4134, several MB) are not stored: their downscale factors are
+    covered by seeded synthetic JPEGs of the same sizes, compared with the oracle's preprocessing exactly."""
     import json
-    ref_dir = "/root/reference/demo_material"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("demo JPEGs live in the reference tree (build container only)")
+    import numpy as np
+    from PIL import Image
     from on_device_image_captioning_amd.image_utils import preprocess_image
+    from oracle import expansionnet_ref as R
+    img_dir = os.path.join(ROOT, "tests", "golden", "demo_material")
     helper = json.load(open(os.path.join(ROOT, "tests", "golden", "helpers.json")))
-    for fn, want in helper["preprocess_pil_checksums"].items():
-        t = preprocess_image(os.path.join(ref_dir, fn), 384)
+    stored = sorted(os.listdir(img_dir))
+    assert stored == ["micheal.jpg", "tatin.jpg"]
+    for fn in stored:
+        want = helper["preprocess_pil_checksums"][fn]
+        t = preprocess_image(os.path.join(img_dir, fn), 384)
         assert tuple(t.shape) == (1, 3, 384, 384) and t.dtype == torch.float32
         assert abs(float(t.double().sum()) - want["sum"]) < 1e-2
         assert abs(float(t.double().abs().sum()) - want["abssum"]) < 1e-2
+    rng = np.random.default_rng(0)
+    for w, h in ((3456, 4608), (3394, 4134)):
+        yy, xx = np.mgrid[0:h, 0:w]
+        a = np.stack([xx * 255 // w, yy * 255 // h, (xx + yy) % 256], -1) + rng.integers(-20, 21, size=(h, w, 3))
+        path = str(tmp_path / f"synth_{w}x{h}.jpg")
+        Image.fromarray(np.clip(a, 0, 255).astype(np.uint8), "RGB").save(path, quality=90)
+        t = preprocess_image(path, 384)
+        assert tuple(t.shape) == (1, 3, 384, 384) and t.dtype == torch.float32
+        assert torch.equal(t, R.preprocess_image(path, 384))
 
 
 def test_preprocess_non_rgb_becomes_a_black_canvas(tmp_path):
