@@ -28,6 +28,7 @@
 #ifndef ODIC_HIP_H
 #define ODIC_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -50,7 +51,7 @@ extern "C" {
 #define ODIC_EUNSUPPORTED (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define ODIC_ABI_VERSION 15
+#define ODIC_ABI_VERSION 16
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -179,6 +180,64 @@ int odic_resize_bilinear_normalize(const uint8_t* src_rgb, int32_t H, int32_t W,
                                    const int32_t* bounds_y, const int32_t* coef_y, int32_t ksize_y,
                                    uint8_t* tmp, float* dst, int32_t out_size, const float* mean3,
                                    const float* std3, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched baseline JPEG decode on the device (utils/image_utils.py:7, PIL_Image.open), bit-exact with
+ * np.asarray(PIL.Image.open(f)) on Pillow's libjpeg-turbo default path (ISLOW IDCT, fancy upsampling,
+ * fixed-point YCbCr→RGB).  The host parser (on_device_image_captioning_amd/jpeg.py) walks the markers up to
+ * SOS and fills one odic_jpeg_header per image; only its `device` kind is passed here: 8-bit SOF0/SOF1
+ * Huffman, one interleaved scan of 3 YCbCr components, luma sampling 1x1 / 2x1 / 2x2 with 1x1 chroma,
+ * restart interval present or absent.  All offsets are set by that parser.
+ *   data_off / data_end  byte range in `data` from the first entropy-coded byte to the end of the file,
+ *                        at most 2^27 bytes (bit positions are int32)
+ *   out_off              byte offset of the image's H×W×3 uint8 RGB output in `out`
+ *   scan_off / coef_off / plane_off / int_off / unit_off   the image's slices of the workspace regions:
+ *                        compacted scan bytes (4-aligned, round_up(data_end - data_off, 4) + 16 reserved),
+ *                        coefficient blocks, component planes (bytes, 16-aligned), intervals (n_intervals
+ *                        + 1 slots), units (n_units slots)
+ *   restart              MCUs per restart interval (all MCUs without DRI); n_intervals = ceil(MCUs / restart)
+ *   n_units              ceil(8 (data_end - data_off) / subseq_bits) + n_intervals
+ *   qt                   quantisation table of each component, natural order
+ *   lut/maxcode/valoff/huffval  tables 0-2: DC of components 0-2, 3-5: their AC.  lut[peek9] = (len << 8) |
+ *                        symbol for codes of at most 9 bits, else 0; longer codes: the first length l with
+ *                        code(l) <= maxcode[l] gives huffval[code + valoff[l]]
+ * ------------------------------------------------------------------------------------------- */
+typedef struct odic_jpeg_header {
+  int64_t data_off, data_end, out_off, scan_off, coef_off, plane_off;
+  int32_t int_off, unit_off, width, height;
+  int32_t sampling;              /* 0: 4:4:4, 1: 4:2:2 (h2v1), 2: 4:2:0 (h2v2) */
+  int32_t mcus_x, mcus_y, restart, n_intervals, n_units;
+  uint16_t qt[3][64];
+  uint16_t lut[6][512];
+  int32_t maxcode[6][18];
+  int32_t valoff[6][18];
+  uint8_t huffval[6][256];
+} odic_jpeg_header;
+
+/* One decode call.  headers, data, out, status are DEVICE pointers; status int32 [n_images] receives 0 for a
+ * decoded image and 1 for one whose entropy data did not decode (invalid code, unexpected marker, restart
+ * markers out of sequence, an interval whose MCUs need bits past its end, no EOI) or whose coefficients leave
+ * the range where libjpeg-turbo's SIMD and C IDCTs agree (a dequantised coefficient or pass-1 value beyond
+ * ±8191, a result beyond [-512, 511], a DC beyond int16): the caller decodes those again on the host.  subseq_bits (32..4096): bits per speculative unit; max_sync_passes (0..64): synchronisation
+ * passes before the intervals that have not converged are decoded serially (0: all of them).  The max_* and
+ * total_* fields are the maxima / sums of the headers' sizes (widths, heights, units, intervals + 1 per image,
+ * blocks, reserved scan bytes, plane bytes) that size the grids and the workspace. */
+typedef struct odic_jpeg_batch {
+  const void* headers;           /* odic_jpeg_header [n_images] */
+  const uint8_t* data;
+  uint8_t* out;
+  int32_t* status;
+  int32_t n_images, subseq_bits, max_sync_passes, max_units, max_intervals, max_width, max_height, pad;
+  int64_t max_blocks, max_scan_bytes, total_scan_bytes, total_intervals, total_units, total_blocks,
+      total_plane_bytes;
+} odic_jpeg_batch;
+
+/* Workspace bytes odic_jpeg_decode needs for this batch (host-side query, reads no device memory); 0 for an
+ * invalid descriptor. */
+size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* batch);
+
+/* Decode the batch on `stream` (one pass of launches, no host synchronisation, capturable). */
+int odic_jpeg_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core  (WindowAttention.forward swin_transformer_mod.py:193-211

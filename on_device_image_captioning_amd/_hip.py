@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libodic_hip.so")
 
 F32, BF16, FP8, F16, H2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _ERR = {-1: "ODIC_EINVAL (bad shape / alignment / enum)", -2: "ODIC_ENULL (required pointer is NULL)",
         -3: "ODIC_EUNSUPPORTED"}
@@ -46,6 +46,17 @@ class EmbedArgs(C.Structure):
     """odic_embed_args: the next position's input embedding as the tail of the launch that chooses the words."""
     _fields_ = [("embed", C.c_void_p), ("pos_table", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int64),
                 ("d", C.c_int32), ("scale", C.c_float), ("pos_rows", C.c_int32)]
+
+
+class JpegBatch(C.Structure):
+    """odic_jpeg_batch: one batched JPEG decode (headers from on_device_image_captioning_amd.jpeg.pack_headers)."""
+    _fields_ = [("headers", C.c_void_p), ("data", C.c_void_p), ("out", C.c_void_p), ("status", C.c_void_p),
+                ("n_images", C.c_int32), ("subseq_bits", C.c_int32), ("max_sync_passes", C.c_int32),
+                ("max_units", C.c_int32), ("max_intervals", C.c_int32), ("max_width", C.c_int32),
+                ("max_height", C.c_int32), ("pad", C.c_int32),
+                ("max_blocks", C.c_int64), ("max_scan_bytes", C.c_int64), ("total_scan_bytes", C.c_int64),
+                ("total_intervals", C.c_int64), ("total_units", C.c_int64), ("total_blocks", C.c_int64),
+                ("total_plane_bytes", C.c_int64)]
 
 
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -80,6 +91,8 @@ _SIGNATURES = {
     "odic_beam_finalize": (C.c_int, [C.POINTER(BeamState), _P, _P, _I32, _I32, _P]),
     "odic_beam_finalize_best": (C.c_int, [C.POINTER(BeamState), _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "odic_beam_reset": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),
+    "odic_jpeg_workspace_bytes": (C.c_size_t, [C.POINTER(JpegBatch)]),
+    "odic_jpeg_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
 }
 
 #: every symbol include/odic_hip.h declares

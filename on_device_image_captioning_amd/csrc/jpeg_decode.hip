@@ -1,0 +1,814 @@
+// Batched baseline JPEG decode, bit-exact with np.asarray(PIL.Image.open(f)) — Pillow on
+// libjpeg-turbo's default path: ISLOW IDCT, "fancy" triangle upsampling, table-driven YCbCr→RGB.
+//
+// The host parser (on_device_image_captioning_amd/jpeg.py) walks the markers up to SOS and packs one
+// odic_jpeg_header per image: quantisation tables in natural order, Huffman tables in a lookup form, the
+// restart interval and the workspace offsets.  Everything after SOS is decoded here, the whole batch in one
+// pass of launches on the caller's stream:
+//
+//   segment     one workgroup per image: classify every byte of the scan (data, stuffed 0x00, RSTn, EOI, any
+//               other marker → error), compact the data bytes with a prefix sum, record the start bit of each
+//               restart interval (without DRI the whole scan is one interval) and split every interval into
+//               units of subseq_bits bits.
+//   speculate   one lane per unit: decode from the unit's first bit with a guessed state (bit position,
+//               block in MCU, zig-zag index) = (start, 0, 0) until the unit's end; record the end state and the
+//               number of blocks begun.  The first unit of an interval starts from the exact state.
+//   sync × P    Jacobi passes of the self-synchronising scheme of Weißenberger & Schmidt (ICPP 2018): unit u
+//               decodes again from the end state of unit u-1 of the previous pass.  A pass in which no unit
+//               of an interval changes its end state proves that interval's states exact; once a whole pass
+//               changes nothing, the remaining passes return at once (device flag).
+//   serial      one wave per interval that did not converge (all of them with max_sync_passes = 0): walk its
+//               units from the exact start, decoding again every unit whose last start state was wrong.
+//   scan        per image: exclusive prefix of the blocks begun per unit.
+//   write-out   one lane per unit: decode again from the synchronised start state and write int16
+//               coefficients in natural order (DC as a difference) at the unit's block indices.
+//   dc          per image and component: DC prediction, a scan that resets at each restart interval.
+//   idct        jidctint.c jpeg_idct_islow with dequantisation and the masked post-IDCT range limit
+//               (range_limit[x & 1023]), writing uint8 planes padded to whole MCUs.
+//   color       h2v1 / h2v2 fancy upsampling + jdcolor.c ycc_rgb_convert, cropped H×W×3 into the caller's
+//               buffer, and the per-image status.
+//
+// An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
+// or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
+// whose coefficients leave the range where libjpeg-turbo's SIMD and C IDCTs agree (kIdctLimit), gets status 1:
+// the caller decodes it again on the host.  Entropy data that does decode yields libjpeg's coefficients exactly.
+#include "odic_common.h"
+
+static_assert(sizeof(odic_jpeg_header) == 9016 && offsetof(odic_jpeg_header, qt) == 88 &&
+                  offsetof(odic_jpeg_header, huffval) == 7480,
+              "odic_jpeg_header layout is mirrored by jpeg.HEADER_DTYPE");
+
+namespace {
+
+constexpr int kInvalidPos = 0x7fffffff;
+constexpr int kLutBits = 9;
+constexpr int kStateWords = 8;            // per image: [0] error bits, [1] intervals finished
+constexpr int kErrSegment = 1, kErrDecode = 2, kErrRange = 4;
+// Pillow's libjpeg-turbo runs the SIMD ISLOW IDCT: 16-bit dequantisation products, 16-bit sums of up to four inputs,
+// pass-1 results packed to 16 bits, and a saturating final clamp where the C code masks (x & 1023).  The two agree,
+// and this file's int32 arithmetic is exact, while every dequantised coefficient and every pass-1 value stays within
+// ±kIdctLimit and every final value within [-512, 511].  Legitimate 8-bit images stay far inside (the extreme cases
+// tried — 1-pixel checkerboards and binary noise at quality 100 — reach 838, 3702 and [-134, 131]); anything else gets
+// kErrRange and is decoded by the host.  A DC value that leaves int16 (JCOEF) gets it too.
+constexpr int kIdctLimit = 8191;
+
+__device__ const unsigned char kNatural[64] = {
+    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+    28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
+    54, 47, 55, 62, 63};
+
+struct Ws {                                // workspace regions (host-computed from the batch totals)
+  int* state;                              // [n_images][kStateWords]
+  int* flags;                              // [0] last sync pass that ran, [1 + p] pass p changed something
+  int* last_change;                        // per interval: last pass that changed one of its units
+  unsigned char* scan;                     // compacted entropy data
+  int* int_bits;                           // per image n_intervals + 1 interval boundaries (bits)
+  int* unit_start;                         // per image n_intervals + 1 first unit of each interval
+  int4* est[2];                            // per unit end state {pos, blk, k, blocks begun}, two pass buffers
+  int* unit_first;                         // per unit: blocks begun in the image before it
+  short* coef;                             // [blocks][64]
+  unsigned char* planes;
+};
+
+struct Layout {
+  size_t state, flags, last_change, scan, int_bits, unit_start, est0, est1, unit_first, coef, planes, total;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+Layout layout(const odic_jpeg_batch& b) {
+  Layout L;
+  size_t o = 0;
+  L.state = o; o = align256(o + sizeof(int) * kStateWords * (size_t)b.n_images);
+  L.flags = o; o = align256(o + sizeof(int) * (2 + (size_t)b.max_sync_passes));
+  L.last_change = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
+  L.scan = o; o = align256(o + (size_t)b.total_scan_bytes);
+  L.int_bits = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
+  L.unit_start = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
+  L.est0 = o; o = align256(o + sizeof(int4) * (size_t)b.total_units);
+  L.est1 = o; o = align256(o + sizeof(int4) * (size_t)b.total_units);
+  L.unit_first = o; o = align256(o + sizeof(int) * (size_t)b.total_units);
+  L.coef = o; o = align256(o + 128 * (size_t)b.total_blocks);
+  L.planes = o; o = align256(o + (size_t)b.total_plane_bytes);
+  L.total = o;
+  return L;
+}
+
+__device__ __forceinline__ int blocks_per_mcu(int sampling) { return sampling == 0 ? 3 : (sampling == 1 ? 4 : 6); }
+__device__ __forceinline__ int luma_blocks(int sampling) { return sampling == 0 ? 1 : (sampling == 1 ? 2 : 4); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// segment: one workgroup of 256 lanes per image, 16 bytes per lane per 4 KiB tile
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ T block_exclusive_scan(T v, T* lds, T& total) {   // 256 lanes; lds holds 256 T
+  const int t = threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const T x = t >= off ? lds[t - off] : T(0);
+    __syncthreads();
+    lds[t] += x;
+    __syncthreads();
+  }
+  total = lds[255];
+  const T incl = lds[t];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ __launch_bounds__(256) void jpeg_segment_kernel(const odic_jpeg_header* __restrict__ hdrs,
+                                                           const unsigned char* __restrict__ data, Ws ws,
+                                                           int subseq_bits) {
+  const odic_jpeg_header& h = hdrs[blockIdx.x];
+  const int t = threadIdx.x;
+  const unsigned char* src = data + h.data_off;
+  const long len = h.data_end - h.data_off;
+  unsigned char* dst = ws.scan + h.scan_off;
+  int* ib = ws.int_bits + h.int_off;
+  int* us = ws.unit_start + h.int_off;
+  int* state = ws.state + kStateWords * blockIdx.x;
+  const int nint = h.n_intervals;
+  __shared__ int sh_scan[256];
+  __shared__ long sh_stop;
+  __shared__ int sh_err;
+  long carry_data = 0;
+  int carry_marks = 0, err = 0;
+  bool eoi = false;
+  if (t == 0) sh_err = 0;
+  for (long base = 0; base < len; base += 4096) {
+    if (t == 0) sh_stop = len;
+    __syncthreads();
+    const long i0 = base + 16L * t;
+    unsigned char bb[18];                                    // bytes i0 - 1 .. i0 + 16, 0 outside the scan
+#pragma unroll
+    for (int j = 0; j < 18; ++j) {
+      const long i = i0 - 1 + j;
+      bb[j] = (i >= 0 && i < len) ? src[i] : 0;
+    }
+    // the first stop (EOI or error) of the tile; a byte after 0xFF is the second byte of a pair
+    for (int j = 0; j < 16; ++j) {
+      const long i = i0 + j;
+      if (i >= len) break;
+      if (bb[j + 1] != 0xFF || bb[j] == 0xFF) continue;
+      const int nx = i + 1 < len ? bb[j + 2] : -1;
+      if (nx == 0 || (nx >= 0xD0 && nx <= 0xD7)) continue;
+      atomicMin((unsigned long long*)&sh_stop, (unsigned long long)i);
+      break;
+    }
+    __syncthreads();
+    const long stop = sh_stop;
+    int nd = 0, nm = 0;
+    for (int j = 0; j < 16; ++j) {
+      if (i0 + j >= stop) break;
+      if (bb[j] == 0xFF) continue;
+      if (bb[j + 1] != 0xFF || bb[j + 2] == 0) ++nd; else ++nm;
+    }
+    int tot_d, tot_m;
+    int ed = block_exclusive_scan(nd, sh_scan, tot_d);
+    int em = block_exclusive_scan(nm, sh_scan, tot_m);
+    long d = carry_data + ed;
+    int m = carry_marks + em;
+    for (int j = 0; j < 16; ++j) {
+      if (i0 + j >= stop) break;
+      if (bb[j] == 0xFF) continue;
+      if (bb[j + 1] != 0xFF || bb[j + 2] == 0) {
+        dst[d++] = bb[j + 1];
+      } else {                                               // RSTn ends interval m
+        if (m + 1 >= nint || (bb[j + 2] & 7) != (m & 7)) sh_err = 1;   // too many, or out of sequence
+        if (m + 1 < nint) ib[m + 1] = (int)(d * 8);
+        ++m;
+      }
+    }
+    carry_data += tot_d;
+    carry_marks += tot_m;
+    if (stop < len) {
+      eoi = stop + 1 < len && src[stop + 1] == 0xD9;
+      break;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  err = sh_err;
+  if (!eoi || carry_marks != nint - 1) err = 1;
+  if (t == 0) {
+    if (err) state[0] |= kErrSegment;
+    ib[0] = 0;
+  }
+  const int endbits = (int)(carry_data * 8);
+  for (int k = min(carry_marks, nint - 1) + 1 + t; k <= nint; k += 256) ib[k] = endbits;   // end; missing: empty
+  if (t < 16) dst[carry_data + t] = 0;
+  __syncthreads();
+  // units: interval k gets max(1, ceil(bits / subseq_bits)) of them
+  int carry_u = 0;
+  for (int k0 = 0; k0 < nint; k0 += 256) {
+    const int k = k0 + t;
+    int n = 0;
+    if (k < nint) {
+      const int bits = ib[k + 1] - ib[k];
+      n = bits > 0 ? (bits + subseq_bits - 1) / subseq_bits : 1;
+    }
+    int tot;
+    const int e = block_exclusive_scan(n, sh_scan, tot);
+    if (k < nint) us[k] = carry_u + e;
+    carry_u += tot;
+  }
+  if (t == 0) us[nint] = min(carry_u, h.n_units);                 // never more than the slots reserved
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Huffman decoding, shared by the speculative, sync, write-out and serial kernels
+// ---------------------------------------------------------------------------------------------------------------
+struct Tabs {
+  unsigned short lut[6 * 512];
+  int lim[6 * 8];                  // [l - 9]: one past the last code of length <= l, left-justified to 16 bits
+  int maxcode[6 * 18];
+  int valoff[6 * 18];
+  unsigned char huffval[6 * 256];
+  unsigned char natural[64];
+};
+
+__device__ void load_tabs(const odic_jpeg_header& h, Tabs& T) {
+  const int t = threadIdx.x;
+  for (int i = t; i < 6 * 512; i += blockDim.x) T.lut[i] = (&h.lut[0][0])[i];
+  for (int i = t; i < 6 * 18; i += blockDim.x) {
+    T.maxcode[i] = (&h.maxcode[0][0])[i];
+    T.valoff[i] = (&h.valoff[0][0])[i];
+  }
+  for (int i = t; i < 6 * 256; i += blockDim.x) T.huffval[i] = (&h.huffval[0][0])[i];
+  for (int i = t; i < 64; i += blockDim.x) T.natural[i] = kNatural[i];
+  if (t < 6) {                     // canonical codes: the codes of length l, left-justified, end where those of l+1 begin
+    int last = 0;
+    for (int l = 1; l <= 16; ++l) {
+      const int mc = (&h.maxcode[0][0])[t * 18 + l];
+      if (mc >= 0) last = (mc + 1) << (16 - l);
+      if (l >= 9) T.lim[t * 8 + l - 9] = last;
+    }
+  }
+  __syncthreads();
+}
+
+struct St {
+  int pos, blk, k;                 // next bit; block within the MCU; 0: next symbol is a DC, else the AC index
+};
+
+// Bit reader: the 64-bit window [32 wi, 32 wi + 64) in registers plus two prefetched words, so a symbol costs no
+// memory access and a word is read 64 bits before it is needed.  w[i - off] holds compacted word i (the unit kernels
+// stage their words in LDS, the serial walk reads global memory with off = 0).  Reads stop 16 bytes past the
+// compacted data, inside the 16 bytes reserved behind every image's scan.
+struct Bits {
+  const unsigned* __restrict__ w;
+  int off;
+  int wi;
+  unsigned w0, w1, w2, w3;
+};
+
+__device__ __forceinline__ void bits_seek(Bits& b, int pos) {
+  b.wi = pos >> 5;
+  const unsigned* p = b.w + (b.wi - b.off);
+  b.w0 = __builtin_bswap32(p[0]);
+  b.w1 = __builtin_bswap32(p[1]);
+  b.w2 = __builtin_bswap32(p[2]);
+  b.w3 = __builtin_bswap32(p[3]);
+}
+
+__device__ __forceinline__ unsigned bits_peek(Bits& b, int pos) {      // the 32 bits from `pos` (pos never decreases)
+  while ((pos >> 5) > b.wi) {
+    ++b.wi;
+    b.w0 = b.w1;
+    b.w1 = b.w2;
+    b.w2 = b.w3;
+    b.w3 = __builtin_bswap32(b.w[b.wi - b.off + 3]);
+  }
+  const unsigned long long x = ((unsigned long long)b.w0 << 32) | b.w1;
+  return (unsigned)(x >> (32 - (pos & 31)));
+}
+
+__device__ __forceinline__ int huff(const Tabs& T, int tab, unsigned win, int& len) {
+  const unsigned e = T.lut[tab * 512 + (win >> (32 - kLutBits))];
+  if (e) {
+    len = e >> 8;
+    return e & 255;
+  }
+  // longer codes: the length is one more than the number of limits the 16-bit peek reaches (independent LDS reads
+  // instead of a dependent loop that every lane of the wave would wait for)
+  const int p16 = (int)(win >> 16);
+  int l = kLutBits + 1;
+#pragma unroll
+  for (int i = 1; i <= 7; ++i) l += p16 >= T.lim[tab * 8 + i];
+  if (l > 16) return -1;
+  len = l;
+  return T.huffval[tab * 256 + (((p16 >> (16 - l)) + T.valoff[tab * 18 + l]) & 255)];
+}
+
+__device__ __forceinline__ int extend(unsigned bits, int s) {    // HUFF_EXTEND
+  return (int)bits < (1 << (s - 1)) ? (int)bits - (1 << s) + 1 : (int)bits;
+}
+
+// One symbol at s.pos.  zz = zig-zag index written (-1: none), val its value.  Returns false on an invalid code.
+__device__ __forceinline__ bool step(const Tabs& T, Bits& br, St& s, int nY, int bpm, int& zz, int& val) {
+  const unsigned win = bits_peek(br, s.pos);
+  const int comp = s.blk < nY ? 0 : s.blk - nY + 1;
+  int len;
+  if (s.k == 0) {
+    const int cat = huff(T, comp, win, len);
+    if (cat < 0) return false;
+    val = cat ? extend((win << len) >> (32 - cat), cat) : 0;
+    s.pos += len + cat;
+    zz = 0;
+    s.k = 1;
+    return true;
+  }
+  const int rs = huff(T, 3 + comp, win, len);
+  if (rs < 0) return false;
+  const int r = rs >> 4, c = rs & 15;
+  if (c) {
+    s.k += r;
+    zz = s.k;
+    val = extend((win << len) >> (32 - c), c);
+    s.pos += len + c;
+    s.k += 1;
+  } else {
+    zz = -1;
+    s.pos += len;
+    s.k = r == 15 ? s.k + 16 : 64;
+  }
+  if (s.k >= 64) {
+    s.k = 0;
+    s.blk = s.blk + 1 == bpm ? 0 : s.blk + 1;
+  }
+  return true;
+}
+
+// decode [s.pos, end) counting the blocks begun; an invalid code ends the span with pos = kInvalidPos
+__device__ int4 decode_span(const Tabs& T, const unsigned* __restrict__ w, int off, St s, int end, int nY, int bpm) {
+  int count = 0;
+  Bits br{w, off};
+  if (s.pos < end) bits_seek(br, s.pos);
+  while (s.pos < end) {
+    count += s.k == 0;
+    int zz, val;
+    if (!step(T, br, s, nY, bpm, zz, val)) {
+      s = St{kInvalidPos, 0, 0};
+      break;
+    }
+  }
+  return make_int4(s.pos, s.blk, s.k, count);
+}
+
+struct Unit {
+  int k, u, first, start, end, int_end;
+};
+
+// unit u of an image → its interval (binary search in unit_start) and bit range; false past the last unit
+__device__ __forceinline__ bool locate(const int* __restrict__ us, const int* __restrict__ ib, int nint, int S, int u,
+                                       Unit& U) {
+  if (u >= us[nint]) return false;
+  int lo = 0, hi = nint - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (us[mid] <= u) lo = mid; else hi = mid - 1;
+  }
+  U.k = lo;
+  U.u = u;
+  U.first = us[lo];
+  U.int_end = ib[lo + 1];
+  U.start = ib[lo] + (u - us[lo]) * S;
+  U.end = min(U.start + S, U.int_end);
+  return true;
+}
+
+constexpr int kUnitLanes = 64;                  // unit kernels: one wave per workgroup spreads a batch over more CUs
+constexpr int kMaxSubseqBits = 4096;            // a workgroup's units are staged in LDS: 64 * 4096 bits = 32 KiB
+// bit positions are int32: with at most 2^27 scan bytes every position, unit end (+ subseq_bits) and end state
+// (+ 31 bits) stays below 2^30 + 2^13, far from kInvalidPos
+constexpr long kMaxScanBytes = 1L << 27;
+
+__host__ __device__ constexpr int stage_words(int S) { return kUnitLanes * S / 32 + 8; }
+
+// Copy the compacted words the workgroup's units read (bits [lo, hi) plus the reader's 3 words of look-ahead) to
+// LDS; returns the index of the first word staged.  Units are contiguous, so hi - lo <= 64 S.
+__device__ int stage_units(const unsigned* __restrict__ gw, unsigned* sdata, bool valid, int start, int end) {
+  __shared__ int sh_lo, sh_hi;
+  if (threadIdx.x == 0) {
+    sh_lo = 0x7fffffff;
+    sh_hi = 0;
+  }
+  __syncthreads();
+  if (valid) {
+    atomicMin(&sh_lo, start);
+    atomicMax(&sh_hi, end);
+  }
+  __syncthreads();
+  const int lo = sh_lo, hi = sh_hi;
+  if (lo > hi) return 0;                                          // no valid unit in this workgroup
+  const int w_lo = lo >> 5, n = ((hi > 0 ? hi - 1 : 0) >> 5) + 3 - w_lo + 1;
+  for (int i = threadIdx.x; i < n; i += kUnitLanes) sdata[i] = gw[w_lo + i];
+  __syncthreads();
+  return w_lo;
+}
+
+__global__ __launch_bounds__(kUnitLanes) void jpeg_sync_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws, int S,
+                                                        int pass) {
+  if (pass >= 2 && ws.flags[pass] == 0) return;                // pass - 1 changed nothing: converged
+  __shared__ Tabs T;
+  const int img = blockIdx.y;
+  const odic_jpeg_header& h = hdrs[img];
+  if (blockIdx.x * kUnitLanes >= h.n_units) return;
+  if (pass >= 1 && threadIdx.x == 0) atomicMax(&ws.flags[0], pass);
+  load_tabs(h, T);
+  const int* us = ws.unit_start + h.int_off;
+  const int* ib = ws.int_bits + h.int_off;
+  Unit U{};
+  const bool valid = locate(us, ib, h.n_intervals, S, blockIdx.x * kUnitLanes + threadIdx.x, U);
+  extern __shared__ unsigned sdata[];
+  const int off = stage_units((const unsigned*)(ws.scan + h.scan_off), sdata, valid, U.start, U.end);
+  if (!valid) return;
+  const int sampling = h.sampling, nY = luma_blocks(sampling), bpm = blocks_per_mcu(sampling);
+  int4* out = ws.est[pass & 1] + h.unit_off;
+  St s{U.start, 0, 0};
+  if (pass >= 1 && U.u != U.first) {
+    const int4 p = ws.est[(pass - 1) & 1][h.unit_off + U.u - 1];
+    s = St{p.x, p.y, p.z};
+  }
+  const int4 e = decode_span(T, sdata, off, s, U.end, nY, bpm);
+  if (pass >= 1) {
+    const int4 old = ws.est[(pass - 1) & 1][h.unit_off + U.u];
+    if (old.x != e.x || old.y != e.y || old.z != e.z || old.w != e.w) {
+      ws.flags[1 + pass] = 1;
+      atomicMax(&ws.last_change[h.int_off + U.k], pass);
+    }
+  }
+  out[U.u] = e;
+}
+
+// an interval's end states are exact once a pass changed none of them, or after jpeg_serial_kernel walked it (-1)
+__device__ __forceinline__ bool converged(const Ws& ws, const odic_jpeg_header& h, int k) {
+  const int ran = ws.flags[0], last = ws.last_change[h.int_off + k];
+  return last < 0 || (ran >= 1 && last < ran);
+}
+
+// per image: exclusive prefix of the blocks begun per unit (final pass buffer)
+__global__ __launch_bounds__(256) void jpeg_block_scan_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
+  const odic_jpeg_header& h = hdrs[blockIdx.x];
+  __shared__ int sh[256];
+  const int n = ws.unit_start[h.int_off + h.n_intervals];
+  const int4* e = ws.est[ws.flags[0] & 1] + h.unit_off;
+  int carry = 0;
+  for (int u0 = 0; u0 < n; u0 += 256) {
+    const int u = u0 + threadIdx.x;
+    const int v = u < n ? e[u].w : 0;
+    int tot;
+    const int x = block_exclusive_scan(v, sh, tot);
+    if (u < n) ws.unit_first[h.unit_off + u] = carry + x;
+    carry += tot;
+  }
+}
+
+// decode from s to `end` (or the interval's last block) writing coefficients; bcur = block in progress (local)
+__device__ void write_span(const Tabs& T, const unsigned* __restrict__ w, int off, St s, int bcur, int end,
+                           int int_end, int nblk, short* __restrict__ coef, int nY, int bpm, int* state) {
+  Bits br{w, off};
+  if (s.pos < end) bits_seek(br, s.pos);
+  while (s.pos < end) {
+    const int nb = s.k == 0 ? bcur + 1 : bcur;
+    if (nb >= nblk) return;                                   // past the interval's last block: padding
+    int zz, val;
+    if (nb < 0 || !step(T, br, s, nY, bpm, zz, val) || zz > 63) {   // zz > 63: libjpeg would clobber coef 63
+      atomicOr(&state[0], kErrDecode);
+      return;
+    }
+    bcur = nb;
+    if (zz >= 0) coef[(long)bcur * 64 + T.natural[zz]] = (short)val;
+    if (s.k == 0 && bcur == nblk - 1) {                       // the interval's last block is complete
+      if (s.pos > int_end) atomicOr(&state[0], kErrDecode);   // its MCUs needed bits past the interval
+      else atomicAdd(&state[1], 1);
+      return;
+    }
+  }
+  // the unit's bits are used up; the interval's completion is counted by the unit that finishes it
+}
+
+__device__ __forceinline__ int interval_blocks(const odic_jpeg_header& h, int k, int bpm) {
+  const int nmcu = h.mcus_x * h.mcus_y;
+  return min(h.restart, nmcu - k * h.restart) * bpm;
+}
+
+__global__ __launch_bounds__(kUnitLanes) void jpeg_writeout_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws, int S) {
+  __shared__ Tabs T;
+  const int img = blockIdx.y;
+  const odic_jpeg_header& h = hdrs[img];
+  if (blockIdx.x * kUnitLanes >= h.n_units) return;
+  load_tabs(h, T);
+  const int* us = ws.unit_start + h.int_off;
+  const int* ib = ws.int_bits + h.int_off;
+  Unit U{};
+  const bool valid = locate(us, ib, h.n_intervals, S, blockIdx.x * kUnitLanes + threadIdx.x, U);
+  extern __shared__ unsigned sdata[];
+  const int off = stage_units((const unsigned*)(ws.scan + h.scan_off), sdata, valid, U.start, U.end);
+  if (!valid) return;
+  const int sampling = h.sampling, nY = luma_blocks(sampling), bpm = blocks_per_mcu(sampling);
+  St s{U.start, 0, 0};
+  if (U.u != U.first) {
+    const int4 p = ws.est[ws.flags[0] & 1][h.unit_off + U.u - 1];
+    s = St{p.x, p.y, p.z};
+  }
+  const int* uf = ws.unit_first + h.unit_off;
+  const int bcur = uf[U.u] - uf[U.first] - 1;
+  short* coef = ws.coef + (h.coef_off + (long)U.k * h.restart * bpm) * 64;
+  write_span(T, sdata, off, s, bcur, U.end, U.int_end, interval_blocks(h, U.k, bpm), coef, nY, bpm,
+             ws.state + kStateWords * img);
+}
+
+// One wave per interval that did not converge: walk its units in order from the interval's exact start.  A unit whose
+// start state in the last pass equals the walker's state kept a correct end state and is stepped over; any other unit
+// is decoded again from the walker's state.  The wave loads 64 units' states at a time and broadcasts them; all lanes
+// decode redundantly (same state, same addresses).  With max_sync_passes = 0 this is a serial decode of each interval.
+__global__ __launch_bounds__(64) void jpeg_serial_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws, int S) {
+  __shared__ Tabs T;
+  const int img = blockIdx.y, k = blockIdx.x;
+  const odic_jpeg_header& h = hdrs[img];
+  if (k >= h.n_intervals || converged(ws, h, k)) return;
+  load_tabs(h, T);
+  const int* ib = ws.int_bits + h.int_off;
+  const int* us = ws.unit_start + h.int_off;
+  const int ran = ws.flags[0];
+  int4* cur = ws.est[ran & 1] + h.unit_off;
+  const int4* prev = ws.est[(ran - 1) & 1] + h.unit_off;
+  const unsigned* w = (const unsigned*)(ws.scan + h.scan_off);
+  const int sampling = h.sampling, nY = luma_blocks(sampling), bpm = blocks_per_mcu(sampling);
+  const int lane = threadIdx.x, u_end = us[k + 1];
+  St s{ib[k], 0, 0};
+  for (int u0 = us[k]; u0 < u_end; u0 += 64) {
+    const int u = u0 + lane;
+    int4 rec = make_int4(ib[k] + (u - us[k]) * S, 0, 0, 0), e = make_int4(0, 0, 0, 0);   // start unit u was decoded from
+    if (u < u_end) {
+      if (ran >= 1 && u != us[k]) rec = prev[u - 1];
+      e = cur[u];
+    }
+    for (int j = 0; j < 64 && u0 + j < u_end; ++j) {
+      const int rp = __shfl(rec.x, j), rb = __shfl(rec.y, j), rk = __shfl(rec.z, j);
+      const int ep = __shfl(e.x, j), eb = __shfl(e.y, j), ek = __shfl(e.z, j);
+      if (rp == s.pos && rb == s.blk && rk == s.k) {
+        s = St{ep, eb, ek};
+      } else {
+        const int start = ib[k] + (u0 + j - us[k]) * S;
+        const int4 d = decode_span(T, w, 0, s, min(start + S, ib[k + 1]), nY, bpm);
+        if (lane == 0) cur[u0 + j] = d;
+        s = St{d.x, d.y, d.z};
+      }
+    }
+  }
+  if (lane == 0) ws.last_change[h.int_off + k] = -1;        // its end states are now exact
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// DC prediction: per image, one lane per MCU, a segmented scan of the three components' differences
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jpeg_dc_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
+  const odic_jpeg_header& h = hdrs[blockIdx.x];
+  const int t = threadIdx.x;
+  const int nY = luma_blocks(h.sampling), bpm = nY + 2;
+  const int nmcu = h.mcus_x * h.mcus_y, R = h.restart;
+  short* coef = ws.coef + h.coef_off * 64;
+  __shared__ int sv[3][256];
+  __shared__ int sf[256];
+  int carry[3] = {0, 0, 0};
+  for (int m0 = 0; m0 < nmcu; m0 += 256) {
+    const int m = m0 + t;
+    int own[3] = {0, 0, 0};
+    if (m < nmcu) {
+      for (int j = 0; j < bpm; ++j) own[j < nY ? 0 : j - nY + 1] += coef[((long)m * bpm + j) * 64];
+    }
+    int f = m % R == 0;
+    int v[3];
+    for (int c = 0; c < 3; ++c) v[c] = own[c] + (t == 0 && !f ? carry[c] : 0);
+    for (int off = 1; off < 256; off <<= 1) {
+      for (int c = 0; c < 3; ++c) sv[c][t] = v[c];
+      sf[t] = f;
+      __syncthreads();
+      if (t >= off && !f) {
+        for (int c = 0; c < 3; ++c) v[c] += sv[c][t - off];
+        f = sf[t - off];
+      }
+      __syncthreads();
+    }
+    if (m < nmcu) {
+      int run[3];
+      for (int c = 0; c < 3; ++c) run[c] = v[c] - own[c];
+      for (int j = 0; j < bpm; ++j) {
+        const int c = j < nY ? 0 : j - nY + 1;
+        short* p = &coef[((long)m * bpm + j) * 64];
+        run[c] += *p;
+        if (run[c] < -32768 || run[c] > 32767) atomicOr(&ws.state[kStateWords * blockIdx.x], kErrRange);
+        *p = (short)run[c];                                  // JCOEF is a short
+      }
+    }
+    for (int c = 0; c < 3; ++c) sv[c][t] = v[c];
+    __syncthreads();
+    for (int c = 0; c < 3; ++c) carry[c] = sv[c][255];
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// ISLOW IDCT (jidctint.c): 8 lanes per block, column pass → LDS → row pass
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
+              FIX_0_899976223 = 7373, FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137,
+              FIX_1_961570560 = 16069, FIX_2_053119869 = 16819, FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+
+__device__ __forceinline__ void idct_1d(const int* in, int* out, int shift) {
+  int z2 = in[2], z3 = in[6];
+  int z1 = (z2 + z3) * FIX_0_541196100;
+  const int tmp2 = z1 - z3 * FIX_1_847759065;
+  const int tmp3 = z1 + z2 * FIX_0_765366865;
+  const int tmp0 = (in[0] + in[4]) * (1 << 13);
+  const int tmp1 = (in[0] - in[4]) * (1 << 13);
+  const int t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+  int t0 = in[7], t1 = in[5], t2 = in[3], t3 = in[1];
+  z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
+  int z4 = t1 + t3;
+  const int z5 = (z3 + z4) * FIX_1_175875602;
+  t0 *= FIX_0_298631336; t1 *= FIX_2_053119869; t2 *= FIX_3_072711026; t3 *= FIX_1_501321110;
+  z1 *= -FIX_0_899976223; z2 *= -FIX_2_562915447;
+  z3 = z3 * -FIX_1_961570560 + z5;
+  z4 = z4 * -FIX_0_390180644 + z5;
+  t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+  const int r = 1 << (shift - 1);
+  out[0] = (t10 + t3 + r) >> shift; out[7] = (t10 - t3 + r) >> shift;
+  out[1] = (t11 + t2 + r) >> shift; out[6] = (t11 - t2 + r) >> shift;
+  out[2] = (t12 + t1 + r) >> shift; out[5] = (t12 - t1 + r) >> shift;
+  out[3] = (t13 + t0 + r) >> shift; out[4] = (t13 - t0 + r) >> shift;
+}
+
+__device__ __forceinline__ unsigned range_limit(int x) {   // IDCT_range_limit[x & RANGE_MASK] (jdmaster.c table)
+  const int s = ((x + 512) & 1023) - 512 + 128;
+  return (unsigned)(s < 0 ? 0 : (s > 255 ? 255 : s));
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
+  const odic_jpeg_header& h = hdrs[blockIdx.y];
+  const int nY = luma_blocks(h.sampling), bpm = nY + 2;
+  const long nblocks = (long)h.mcus_x * h.mcus_y * bpm;
+  const long b = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
+  const int lane = threadIdx.x & 7, slot = threadIdx.x >> 3;
+  __shared__ int ws8[32][8][9];
+  if ((long)blockIdx.x * 32 >= nblocks) return;
+  const bool live = b < nblocks;
+  const int j = (int)(live ? b % bpm : 0);
+  const int comp = j < nY ? 0 : j - nY + 1;
+  bool outside = false;                                       // a value where libjpeg-turbo's SIMD and C IDCTs part
+  if (live) {                                                 // column `lane`
+    const short* c = ws.coef + (h.coef_off + b) * 64;
+    int in[8], out[8];
+    for (int r = 0; r < 8; ++r) {
+      in[r] = (int)c[r * 8 + lane] * (int)h.qt[comp][r * 8 + lane];
+      if (in[r] < -kIdctLimit || in[r] > kIdctLimit) {
+        outside = true;
+        in[r] = 0;                                            // keeps the int32 arithmetic in range; image is redone
+      }
+    }
+    idct_1d(in, out, 13 - 2);
+    for (int r = 0; r < 8; ++r) {
+      if (out[r] < -kIdctLimit || out[r] > kIdctLimit) {
+        outside = true;
+        out[r] = 0;
+      }
+      ws8[slot][r][lane] = out[r];
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  int in[8], out[8];                                          // row `lane`
+  for (int x = 0; x < 8; ++x) in[x] = ws8[slot][lane][x];
+  idct_1d(in, out, 13 + 2 + 3);
+  for (int x = 0; x < 8; ++x) outside |= out[x] < -512 || out[x] > 511;
+  if (outside) atomicOr(&ws.state[kStateWords * blockIdx.y], kErrRange);
+  const long mcu = b / bpm;
+  const int mx = (int)(mcu % h.mcus_x), my = (int)(mcu / h.mcus_x);
+  const int hy = h.sampling == 0 ? 1 : 2, vy = h.sampling == 2 ? 2 : 1;
+  int bx = mx, by = my, pw = h.mcus_x * 8;
+  unsigned char* plane = ws.planes + h.plane_off;
+  const long ysz = (long)h.mcus_x * 8 * hy * h.mcus_y * 8 * vy, csz = (long)h.mcus_x * 8 * h.mcus_y * 8;
+  if (comp == 0) {
+    bx = mx * hy + j % hy;
+    by = my * vy + j / hy;
+    pw *= hy;
+  } else {
+    plane += ysz + (comp - 1) * csz;
+  }
+  uint2 v;
+  v.x = range_limit(out[0]) | range_limit(out[1]) << 8 | range_limit(out[2]) << 16 | range_limit(out[3]) << 24;
+  v.y = range_limit(out[4]) | range_limit(out[5]) << 8 | range_limit(out[6]) << 16 | range_limit(out[7]) << 24;
+  *(uint2*)(plane + (long)(by * 8 + lane) * pw + bx * 8) = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// fancy upsampling + YCbCr→RGB (jdsample.c h2v1/h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert) + status
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kCrR = 91881, kCbB = 116130, kCrG = 46802, kCbG = 22554;   // FIX(1.402), FIX(1.772), FIX(.71414), FIX(.34414)
+
+__device__ __forceinline__ unsigned char clamp255(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws,
+                                                         unsigned char* __restrict__ out, int* __restrict__ status) {
+  const int img = blockIdx.z;
+  const odic_jpeg_header& h = hdrs[img];
+  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+  if (x == 0 && y == 0) {
+    const int* st = ws.state + kStateWords * img;
+    status[img] = (st[0] == 0 && st[1] == h.n_intervals) ? 0 : 1;
+  }
+  const int W = h.width, H = h.height;
+  if (x >= W || y >= H) return;
+  const int sampling = h.sampling, hy = sampling == 0 ? 1 : 2, vy = sampling == 2 ? 2 : 1;
+  const int yw = h.mcus_x * 8 * hy, cw = h.mcus_x * 8;
+  const unsigned char* Y = ws.planes + h.plane_off;
+  const unsigned char* Cb = Y + (long)yw * h.mcus_y * 8 * vy;
+  const unsigned char* Cr = Cb + (long)cw * h.mcus_y * 8;
+  const int yv = Y[(long)y * yw + x];
+  int cb, cr;
+  if (sampling == 0) {
+    cb = Cb[(long)y * cw + x];
+    cr = Cr[(long)y * cw + x];
+  } else {
+    const int dw = (W + 1) >> 1;
+    const int c = x >> 1, odd = x & 1;
+    const int cn = odd ? min(c + 1, dw - 1) : max(c - 1, 0);
+    if (sampling == 1) {
+      const long r = (long)y * cw;
+      cb = (3 * Cb[r + c] + Cb[r + cn] + 1 + odd) >> 2;
+      cr = (3 * Cr[r + c] + Cr[r + cn] + 1 + odd) >> 2;
+    } else {
+      const int dh = (H + 1) >> 1;
+      const int rr = y >> 1;
+      const int rn = (y & 1) ? min(rr + 1, dh - 1) : max(rr - 1, 0);
+      const long r0 = (long)rr * cw, r1 = (long)rn * cw;
+      const int cbs0 = 3 * Cb[r0 + c] + Cb[r1 + c], cbs1 = 3 * Cb[r0 + cn] + Cb[r1 + cn];
+      const int crs0 = 3 * Cr[r0 + c] + Cr[r1 + c], crs1 = 3 * Cr[r0 + cn] + Cr[r1 + cn];
+      cb = (3 * cbs0 + cbs1 + 8 - odd) >> 4;
+      cr = (3 * crs0 + crs1 + 8 - odd) >> 4;
+    }
+  }
+  cb -= 128;
+  cr -= 128;
+  unsigned char* o = out + h.out_off + ((long)y * W + x) * 3;
+  o[0] = clamp255(yv + ((kCrR * cr + 32768) >> 16));
+  o[1] = clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
+  o[2] = clamp255(yv + ((kCbB * cb + 32768) >> 16));
+}
+
+}  // namespace
+
+extern "C" size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* b) {
+  if (!b || b->n_images <= 0 || b->max_sync_passes < 0 || b->total_scan_bytes < 0 || b->total_intervals < 0 ||
+      b->total_units < 0 || b->total_blocks < 0 || b->total_plane_bytes < 0)
+    return 0;
+  return layout(*b).total;
+}
+
+extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
+  if (!b || !b->headers || !b->data || !b->out || !b->status || !workspace) return ODIC_ENULL;
+  if (b->n_images <= 0 || b->n_images > 65535 || b->subseq_bits < 32 || b->subseq_bits > kMaxSubseqBits ||
+      b->max_sync_passes < 0 || b->max_sync_passes > 64 || b->max_units <= 0 || b->max_intervals <= 0 ||
+      b->max_width <= 0 || b->max_width > 65535 || b->max_height <= 0 || b->max_height > 65535 ||
+      b->max_blocks <= 0 || b->max_scan_bytes <= 0 || b->max_scan_bytes > kMaxScanBytes || b->total_scan_bytes <= 0 ||
+      b->total_intervals <= 0 || b->total_units <= 0 || b->total_blocks <= 0 || b->total_plane_bytes <= 0)
+    return ODIC_EINVAL;
+  const size_t need = odic_jpeg_workspace_bytes(b);
+  if (need == 0 || ws_bytes < need) return ODIC_EINVAL;
+  const Layout L = layout(*b);
+  unsigned char* base = (unsigned char*)workspace;
+  Ws ws;
+  ws.state = (int*)(base + L.state);
+  ws.flags = (int*)(base + L.flags);
+  ws.last_change = (int*)(base + L.last_change);
+  ws.scan = base + L.scan;
+  ws.int_bits = (int*)(base + L.int_bits);
+  ws.unit_start = (int*)(base + L.unit_start);
+  ws.est[0] = (int4*)(base + L.est0);
+  ws.est[1] = (int4*)(base + L.est1);
+  ws.unit_first = (int*)(base + L.unit_first);
+  ws.coef = (short*)(base + L.coef);
+  ws.planes = base + L.planes;
+  hipStream_t s = (hipStream_t)stream;
+  const auto* hdrs = (const odic_jpeg_header*)b->headers;
+  const int n = b->n_images, S = b->subseq_bits;
+  hipError_t e = hipMemsetAsync(base, 0, L.scan, s);                      // state, flags, last_change
+  if (e == hipSuccess) e = hipMemsetAsync(ws.coef, 0, L.planes - L.coef, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(jpeg_segment_kernel, dim3(n), dim3(256), 0, s, hdrs, b->data, ws, S);
+  const dim3 ugrid((b->max_units + kUnitLanes - 1) / kUnitLanes, n);
+  const size_t lds = sizeof(unsigned) * stage_words(S);
+  for (int p = 0; p <= b->max_sync_passes; ++p)                          // pass 0: speculative
+    hipLaunchKernelGGL(jpeg_sync_kernel, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S, p);
+  hipLaunchKernelGGL(jpeg_serial_kernel, dim3(b->max_intervals, n), dim3(64), 0, s, hdrs, ws, S);
+  hipLaunchKernelGGL(jpeg_block_scan_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
+  hipLaunchKernelGGL(jpeg_writeout_kernel, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
+  hipLaunchKernelGGL(jpeg_dc_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs, ws);
+  hipLaunchKernelGGL(jpeg_color_kernel, dim3((b->max_width + 63) / 64, (b->max_height + 3) / 4, n), dim3(64, 4), 0, s,
+                     hdrs, ws, b->out, b->status);
+  return odic_launch_status();
+}

@@ -7,6 +7,9 @@ the reference does (it calls PIL_Image.new, image_utils.py:18-19).
 """
 from __future__ import annotations
 
+import ctypes
+import io
+
 import numpy as np
 import torch
 from PIL import Image
@@ -29,7 +32,10 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # =================================================================================================
 # Device-side pipeline: resize + ToTensor + Normalize on the GPU, bit-exact with the
 # PIL / torch path above; pinned double-buffered uploads so the copy of image i+1 overlaps the
-# kernels of image i.  JPEG decoding stays on the host (PIL) — there is no decoder to bind to.
+# kernels of image i.  Baseline JPEGs can also be decoded on the GPU (odic_jpeg_decode, csrc/jpeg_decode.hip),
+# bit-exact with PIL: `from_jpeg_bytes` / `from_files(..., decode="device")`.  Files the device decoder does not
+# take (progressive, non-JPEG, ...) and images whose entropy data fails to decode are decoded by PIL in the same
+# call, so the result and the exceptions are those of the host path.
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -81,7 +87,10 @@ class DevicePreprocessor:
         self.ev = [torch.cuda.Event() for _ in range(2)]
         self.stream = torch.cuda.Stream(device=self.device)
         self._coef_cache = {}
-        import ctypes
+        # device JPEG decode: grow-only pinned staging / device copies of the compressed batch, workspace
+        self._jpeg_ev = torch.cuda.Event()
+        self._jpeg_pinned = self._jpeg_dev = self._jpeg_ws = self._jpeg_status = None
+        self._jpeg_tmp = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._mean = (ctypes.c_float * 3)(*_MEAN)
         self._std = (ctypes.c_float * 3)(*_STD)
 
@@ -124,8 +133,17 @@ class DevicePreprocessor:
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
 
-    def from_files(self, paths) -> torch.Tensor:
-        """Host JPEG/PNG decode (PIL; non-RGB files become a black canvas as in the reference) + device pipeline."""
+    def from_files(self, paths, decode: str = "host") -> torch.Tensor:
+        """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
+        the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result)."""
+        if decode == "device":
+            blobs = []
+            for p in paths:
+                with open(p, "rb") as f:
+                    blobs.append(f.read())
+            return self.from_jpeg_bytes(blobs)
+        if decode != "host":
+            raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
         imgs = []
         for p in paths:
             pil = Image.open(p)
@@ -133,3 +151,122 @@ class DevicePreprocessor:
                 pil = Image.new("RGB", pil.size)
             imgs.append(np.asarray(pil, dtype=np.uint8))
         return self(imgs)
+
+    # ---------------------------------------------------------------------------------------------------------
+    # device JPEG decode
+    # ---------------------------------------------------------------------------------------------------------
+    def _check_size(self, H: int, W: int) -> None:
+        if H * W * 3 > self.max_bytes:
+            raise RuntimeError(f"image {H}x{W} exceeds the staging buffers ({self.max_bytes} bytes)")
+
+    def _host_rgb(self, blob) -> np.ndarray:
+        """The host path for one file: PIL decode (black canvas for non-RGB modes) → uint8 (H,W,3) array."""
+        pil = Image.open(io.BytesIO(blob))
+        if pil.mode != "RGB":
+            pil = Image.new("RGB", pil.size)
+        return np.asarray(pil, dtype=np.uint8)
+
+    @staticmethod
+    def _grow(buf, nbytes, **kw):
+        if buf is not None and buf.numel() >= nbytes:
+            return buf
+        return torch.empty(max(nbytes, 2 * (buf.numel() if buf is not None else 0)), dtype=torch.uint8, **kw)
+
+    def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4):
+        """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
+        np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path).  Baseline JPEGs are
+        decoded by odic_jpeg_decode in one batched call (one host-to-device copy, one status read-back); the rest,
+        and images the device rejects, by PIL.  Exceptions are the host path's, in its order: PIL's, file by file,
+        then the size check of `__call__`.  Ordered after the work on the CURRENT stream."""
+        from . import jpeg as J
+        blobs = [bytes(b) for b in blobs]
+        hdrs = [J.parse(b) for b in blobs]
+        out = [None] * len(blobs)
+        # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
+        dev = [i for i, h in enumerate(hdrs)
+               if h.kind == J.DEVICE and h.width * h.height * 3 <= self.max_bytes]
+        if dev:
+            status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in dev], [blobs[i] for i in dev],
+                                                           subseq_bits, max_sync_passes)
+            for k, i in enumerate(dev):
+                h = hdrs[i]
+                if status[k] == 0:
+                    n = h.width * h.height * 3
+                    out[i] = rgb[out_offs[k]:out_offs[k] + n].view(h.height, h.width, 3)
+        for i, h in enumerate(hdrs):                                     # input order, as the host path
+            if h.kind != J.BLACK and out[i] is None:
+                out[i] = self._host_rgb(blobs[i])
+        for i, h in enumerate(hdrs):
+            if h.kind == J.BLACK:
+                self._check_size(h.height, h.width)
+                out[i] = torch.zeros(h.height, h.width, 3, dtype=torch.uint8, device=self.device)
+            else:
+                self._check_size(out[i].shape[0], out[i].shape[1])
+                if isinstance(out[i], np.ndarray):
+                    out[i] = torch.from_numpy(out[i].copy()).to(self.device)
+        return out
+
+    def _decode_on_device(self, hdrs, blobs, subseq_bits, max_sync_passes):
+        """One odic_jpeg_decode call → (per-image status numpy int32, uint8 RGB buffer, byte offset per image)."""
+        from . import jpeg as J
+        hdr_bytes = (len(hdrs) * J.HEADER_DTYPE.itemsize + 255) // 256 * 256
+        offs, ends, pos = [], [], 0
+        for h, blob in zip(hdrs, blobs):
+            offs.append(pos + h.data_offset)
+            pos += len(blob)
+            ends.append(pos)
+        rec, tot, out_offs, out_bytes = J.pack_headers(hdrs, offs, ends, subseq_bits)
+        total = hdr_bytes + pos
+        self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
+        self._jpeg_pinned = self._grow(self._jpeg_pinned, total, pin_memory=True)
+        self._jpeg_status = self._grow(self._jpeg_status, 4 * len(hdrs), pin_memory=True)
+        host = self._jpeg_pinned.numpy()
+        host[:rec.nbytes] = np.frombuffer(rec.tobytes(), np.uint8)
+        p = hdr_bytes
+        for blob in blobs:
+            host[p:p + len(blob)] = np.frombuffer(blob, np.uint8)
+            p += len(blob)
+        rgb = torch.empty(max(out_bytes, 1), dtype=torch.uint8, device=self.device)
+        status = torch.empty(len(hdrs), dtype=torch.int32, device=self.device)
+        b = self._hip.JpegBatch()
+        b.n_images, b.subseq_bits, b.max_sync_passes = len(hdrs), subseq_bits, max_sync_passes
+        for k, v in tot.items():
+            setattr(b, k, v)
+        need = self.lib.odic_jpeg_workspace_bytes(ctypes.byref(b))
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self._jpeg_dev = self._grow(self._jpeg_dev, total, device=self.device)
+            self._jpeg_ws = self._grow(self._jpeg_ws, need, device=self.device)
+            self._jpeg_dev[:total].copy_(self._jpeg_pinned[:total], non_blocking=True)
+            self._jpeg_ev.record(self.stream)
+            base = self._jpeg_dev.data_ptr()
+            b.headers, b.data, b.out, b.status = base, base + hdr_bytes, rgb.data_ptr(), status.data_ptr()
+            self._hip.check(self.lib.odic_jpeg_decode(ctypes.byref(b), self._jpeg_ws.data_ptr(), need,
+                                                      self.stream.cuda_stream), "odic_jpeg_decode")
+            st = self._jpeg_status[:4 * len(hdrs)].view(torch.int32)
+            st.copy_(status, non_blocking=True)
+        self.stream.synchronize()                                        # the one host synchronisation
+        torch.cuda.current_stream().wait_stream(self.stream)
+        return st.numpy().copy(), rgb, out_offs
+
+    def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4) -> torch.Tensor:
+        """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
+        torch.equal to `from_files` on the same files."""
+        imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes)
+        S = self.S
+        out = torch.empty(len(imgs), 3, S, S, dtype=torch.float32, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            for i, img in enumerate(imgs):
+                H, W, _ = img.shape
+                self._check_size(H, W)
+                if self._jpeg_tmp.numel() < H * S * 3:
+                    self._jpeg_tmp = torch.empty(H * S * 3, dtype=torch.uint8, device=self.device)
+                bx, kx, ksx = self._coeffs(W)
+                by, ky, ksy = self._coeffs(H)
+                self._hip.check(self.lib.odic_resize_bilinear_normalize(
+                    img.data_ptr(), H, W, 3 * W, bx.data_ptr(), kx.data_ptr(), ksx, by.data_ptr(), ky.data_ptr(), ksy,
+                    self._jpeg_tmp.data_ptr(), out[i].data_ptr(), S, self._mean, self._std, self.stream.cuda_stream),
+                    "odic_resize_bilinear_normalize")
+        torch.cuda.current_stream().wait_stream(self.stream)
+        return out

@@ -1,0 +1,335 @@
+"""Host side of the device JPEG decoder: a marker parser that sorts every input into
+`device` / `black` / `host` and packs the header records that csrc/jpeg_decode.hip reads.
+
+The parser walks the markers up to SOS only.  It never scans the entropy-coded data: finding restart
+markers and removing 0xFF00 stuffing is device work.  The rule behind the three kinds is that a device
+decode must reproduce `np.asarray(PIL.Image.open(f))` (Pillow with libjpeg-turbo: ISLOW IDCT, fancy
+upsampling, table-driven YCbCr→RGB) bit for bit, and that anything the parser does not fully understand
+goes to PIL, which then raises or decodes exactly as the host path does:
+
+    device  8-bit SOF0/SOF1 Huffman, one interleaved scan of 3 YCbCr components (JFIF, Adobe transform 1,
+            or component ids 1/2/3 — libjpeg's colour-space rules), luma sampling 1x1 / 2x1 / 2x2 with
+            1x1 chroma, DRI present or absent
+    black   1- or 4-component JPEGs (PIL mode L / CMYK): the host path never decodes them, it substitutes
+            an all-black RGB canvas of the same size
+    host    everything else (progressive, arithmetic, 12-bit, lossless, Adobe RGB, multi-scan, DNL,
+            non-JPEG data, malformed or truncated headers, more than MAX_SCAN_BYTES after SOS)
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+
+DEVICE, BLACK, HOST = "device", "black", "host"
+
+#: zig-zag index → natural (row-major) index
+NATURAL_ORDER = np.array([
+    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+    28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
+    54, 47, 55, 62, 63], dtype=np.int32)
+
+MAX_SCAN_BYTES = 1 << 27           # kMaxScanBytes of csrc/jpeg_decode.hip: bit positions stay int32
+LUT_BITS = 9                       # codes up to this length decode with one table lookup on the device
+SAMPLING = {(1, 1): 0, (2, 1): 1, (2, 2): 2}          # luma (h, v) → 0: 4:4:4, 1: 4:2:2 (h2v1), 2: 4:2:0 (h2v2)
+BLOCKS_PER_MCU = (3, 4, 6)
+
+# odic_jpeg_header (include/odic_hip.h), field for field
+HEADER_DTYPE = np.dtype([
+    ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
+    ("plane_off", "<i8"),
+    ("int_off", "<i4"), ("unit_off", "<i4"), ("width", "<i4"), ("height", "<i4"), ("sampling", "<i4"),
+    ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart", "<i4"), ("n_intervals", "<i4"), ("n_units", "<i4"),
+    ("qt", "<u2", (3, 64)), ("lut", "<u2", (6, 512)), ("maxcode", "<i4", (6, 18)), ("valoff", "<i4", (6, 18)),
+    ("huffval", "u1", (6, 256)),
+], align=True)
+
+
+@dataclass
+class HuffTable:
+    bits: list            # number of codes of each length 1..16
+    vals: bytes           # symbols in code order
+
+
+@dataclass
+class JpegHeader:
+    kind: str
+    width: int = 0
+    height: int = 0
+    ncomp: int = 0
+    sampling: int = -1                                   # index into SAMPLING values (device kind only)
+    comp_ids: list = field(default_factory=list)
+    comp_hv: list = field(default_factory=list)          # [(h, v)] per frame component
+    qtables: list = field(default_factory=list)          # per component: int32[64] natural order
+    dc_tables: list = field(default_factory=list)        # per component HuffTable
+    ac_tables: list = field(default_factory=list)
+    restart_interval: int = 0                            # DRI value (0: none)
+    data_offset: int = 0                                 # first byte of the entropy-coded data
+    reason: str = ""
+
+    @property
+    def mcus_x(self):
+        return -(-self.width // (8 * self.comp_hv[0][0]))
+
+    @property
+    def mcus_y(self):
+        return -(-self.height // (8 * self.comp_hv[0][1]))
+
+
+class _Bad(Exception):
+    pass
+
+
+def _u16(b, i):
+    if i + 2 > len(b):
+        raise _Bad("truncated")
+    return (b[i] << 8) | b[i + 1]
+
+
+def parse(blob) -> JpegHeader:
+    """Walk the markers of one file up to SOS → JpegHeader with its kind; never raises."""
+    try:
+        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob)
+    except _Bad as e:
+        return JpegHeader(HOST, reason=str(e))
+    except (IndexError, ValueError) as e:
+        return JpegHeader(HOST, reason=f"malformed: {e}")
+
+
+def _parse(b) -> JpegHeader:
+    n = len(b)
+    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        raise _Bad("not a JPEG")
+    i = 2
+    qt = {}
+    dht = {}                                      # (class, id) → HuffTable
+    jfif = adobe = False
+    adobe_transform = None
+    sof = None
+    dri = 0
+    while True:
+        if i + 2 > n:
+            raise _Bad("truncated")
+        if b[i] != 0xFF:
+            raise _Bad("junk between markers")
+        m = b[i + 1]
+        if m == 0xFF:                              # fill byte
+            i += 1
+            continue
+        if m in (0xD8, 0x01) or 0xD0 <= m <= 0xD7 or m == 0xD9:
+            raise _Bad(f"unexpected marker {m:02X} before SOS")
+        seg_len = _u16(b, i + 2)
+        if seg_len < 2 or i + 2 + seg_len > n:
+            raise _Bad("truncated segment")
+        s = bytes(b[i + 4:i + 2 + seg_len])
+        i += 2 + seg_len
+        if m == 0xE0:
+            if len(s) >= 14 and s[:5] == b"JFIF\x00":          # libjpeg: APP0_DATA_LEN
+                jfif = True
+        elif m == 0xEE:
+            if len(s) >= 12 and s[:5] == b"Adobe":             # libjpeg: APP14_DATA_LEN
+                adobe, adobe_transform = True, s[11]
+        elif m == 0xDB:
+            j = 0
+            while j < len(s):
+                pq, tq = s[j] >> 4, s[j] & 15
+                if pq > 1 or tq > 3:
+                    raise _Bad("bad DQT")
+                size = 64 * (pq + 1)
+                if j + 1 + size > len(s):
+                    raise _Bad("bad DQT length")
+                raw = np.frombuffer(s, dtype=">u2" if pq else "u1", count=64, offset=j + 1).astype(np.int32)
+                nat = np.zeros(64, np.int32)
+                nat[NATURAL_ORDER] = raw
+                qt[tq] = nat
+                j += 1 + size
+        elif m == 0xC4:
+            j = 0
+            while j < len(s):
+                tc, th = s[j] >> 4, s[j] & 15
+                if tc > 1 or th > 3 or j + 17 > len(s):
+                    raise _Bad("bad DHT")
+                bits = list(s[j + 1:j + 17])
+                cnt = sum(bits)
+                if cnt > 256 or j + 17 + cnt > len(s):
+                    raise _Bad("bad DHT length")
+                vals = s[j + 17:j + 17 + cnt]
+                code = 0
+                for length in range(1, 17):                   # libjpeg jpeg_make_d_derived_tbl checks
+                    code += bits[length - 1]
+                    if code >= (1 << length):
+                        raise _Bad("bad Huffman table")
+                    code <<= 1
+                if tc == 0 and any(v > 15 for v in vals):
+                    raise _Bad("bad DC symbol")
+                dht[(tc, th)] = HuffTable(bits, vals)
+                j += 17 + cnt
+        elif m == 0xDD:
+            if len(s) != 2:
+                raise _Bad("bad DRI")
+            dri = (s[0] << 8) | s[1]
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            if sof is not None:
+                raise _Bad("second SOF")
+            if len(s) < 6:
+                raise _Bad("short SOF")
+            nc = s[5]
+            if len(s) != 6 + 3 * nc:
+                raise _Bad("bad SOF length")
+            sof = (m, s[0], _u16(s, 1), _u16(s, 3), nc,
+                   [(s[6 + 3 * k], s[7 + 3 * k] >> 4, s[7 + 3 * k] & 15, s[8 + 3 * k]) for k in range(nc)])
+        elif m == 0xDA:
+            break
+        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
+            raise _Bad(f"marker {m:02X}")
+        # APPn and COM segments are skipped
+    if sof is None:
+        raise _Bad("SOS before SOF")
+    m, prec, height, width, nc, comps = sof
+    if prec != 8:
+        raise _Bad(f"{prec}-bit")
+    if nc not in (1, 3, 4):
+        raise _Bad(f"{nc} components")
+    if nc in (1, 4) and m in (0xC0, 0xC1, 0xC2):
+        # PIL opens these as mode L / CMYK and the host path substitutes a black RGB canvas without decoding
+        if width == 0 or height == 0:
+            raise _Bad("empty frame")
+        return JpegHeader(BLACK, width=width, height=height, ncomp=nc)
+    if m not in (0xC0, 0xC1):
+        raise _Bad(f"SOF{m - 0xC0}")
+    if width == 0 or height == 0:
+        raise _Bad("DNL / empty frame")
+    ids = [c[0] for c in comps]
+    if jfif:
+        ycc = True
+    elif adobe:
+        ycc = adobe_transform == 1
+    else:
+        ycc = ids == [1, 2, 3]
+    if not ycc:
+        raise _Bad("not YCbCr")
+    hv = [(c[1], c[2]) for c in comps]
+    if hv[1] != (1, 1) or hv[2] != (1, 1) or hv[0] not in SAMPLING:
+        raise _Bad(f"sampling {hv}")
+    # SOS: one interleaved baseline scan of all three components, in frame order
+    ns = s[0] if len(s) >= 1 else 0
+    if ns != 3 or len(s) != 1 + 2 * ns + 3:
+        raise _Bad("not one interleaved scan")
+    sel = [(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(3)]
+    if [x[0] for x in sel] != ids:
+        raise _Bad("scan component order")
+    ss, se, ah_al = s[7], s[8], s[9]
+    if ss != 0 or se != 63 or ah_al != 0:
+        raise _Bad("bad spectral selection")
+    qts, dcs, acs = [], [], []
+    for k in range(3):
+        tq = comps[k][3]
+        if tq not in qt:
+            raise _Bad("missing DQT")
+        qts.append(qt[tq])
+        td, ta = sel[k][1], sel[k][2]
+        if (0, td) not in dht or (1, ta) not in dht:
+            raise _Bad("missing DHT")                   # libjpeg-turbo would substitute the standard tables
+        dcs.append(dht[(0, td)])
+        acs.append(dht[(1, ta)])
+    if i >= n:
+        raise _Bad("no scan data")
+    if n - i > MAX_SCAN_BYTES:
+        raise _Bad("scan longer than the device decoder's bit positions allow")
+    return JpegHeader(DEVICE, width=width, height=height, ncomp=3, sampling=SAMPLING[hv[0]], comp_ids=ids,
+                      comp_hv=hv, qtables=qts, dc_tables=dcs, ac_tables=acs, restart_interval=dri, data_offset=i)
+
+
+_TABLE_CACHE: dict = {}
+
+
+def device_tables(t: HuffTable):
+    """One Huffman table in the device lookup form: (lut uint16[512] = (len << 8) | symbol for codes of at most
+    LUT_BITS bits, 0 elsewhere; maxcode int32[18] (largest code of each length, -1 if none); valoff int32[18]
+    (index into huffval minus the first code of that length); huffval uint8[256]).  Files of one encoder share
+    their tables, so the expanded form is cached by content."""
+    key = (bytes(t.bits), bytes(t.vals))
+    hit = _TABLE_CACHE.get(key)
+    if hit is None:
+        if len(_TABLE_CACHE) >= 1024:
+            _TABLE_CACHE.clear()
+        hit = _TABLE_CACHE[key] = _expand_table(t)
+    return hit
+
+
+def _expand_table(t: HuffTable):
+    lut = np.zeros(1 << LUT_BITS, np.uint16)
+    maxcode = np.full(18, -1, np.int32)
+    valoff = np.zeros(18, np.int32)
+    huffval = np.zeros(256, np.uint8)
+    huffval[:len(t.vals)] = np.frombuffer(bytes(t.vals), np.uint8)
+    code, p = 0, 0
+    for length in range(1, 17):
+        cnt = t.bits[length - 1]
+        if cnt:
+            valoff[length] = p - code
+            for c in range(code, code + cnt):
+                if length <= LUT_BITS:
+                    sh = LUT_BITS - length
+                    lut[c << sh:(c + 1) << sh] = (length << 8) | t.vals[p + c - code]
+            code += cnt
+            p += cnt
+            maxcode[length] = code - 1
+        code <<= 1
+    return lut, maxcode, valoff, huffval
+
+
+def n_intervals(h: JpegHeader) -> int:
+    total = h.mcus_x * h.mcus_y
+    r = h.restart_interval or total
+    return -(-total // r)
+
+
+def pack_headers(hdrs, data_offs, data_ends, subseq_bits):
+    """Header records + workspace totals for a batch of device-kind headers.
+    data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
+    buffer.  → (np array HEADER_DTYPE [n], dict of batch totals / maxima, list of output byte offsets)."""
+    n = len(hdrs)
+    rec = np.zeros(n, HEADER_DTYPE)
+    tot = dict(total_scan_bytes=0, total_intervals=0, total_units=0, total_blocks=0, total_plane_bytes=0,
+               max_units=1, max_intervals=1, max_width=1, max_height=1, max_blocks=1, max_scan_bytes=1)
+    out_offs, out_bytes = [], 0
+    for k, h in enumerate(hdrs):
+        r = rec[k]
+        scan = data_ends[k] - data_offs[k]
+        nint = n_intervals(h)
+        units = -(-scan * 8 // subseq_bits) + nint
+        bpm = BLOCKS_PER_MCU[h.sampling]
+        nmcu = h.mcus_x * h.mcus_y
+        hy, vy = h.comp_hv[0]
+        plane = nmcu * 64 * (hy * vy + 2)
+        r["data_off"], r["data_end"], r["out_off"] = data_offs[k], data_ends[k], out_bytes
+        r["scan_off"], r["coef_off"], r["plane_off"] = tot["total_scan_bytes"], tot["total_blocks"], \
+            tot["total_plane_bytes"]
+        r["int_off"], r["unit_off"] = tot["total_intervals"], tot["total_units"]
+        r["width"], r["height"], r["sampling"] = h.width, h.height, h.sampling
+        r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
+        r["restart"] = h.restart_interval or nmcu
+        r["n_intervals"], r["n_units"] = nint, units
+        for c in range(3):
+            r["qt"][c] = h.qtables[c]
+            for t, tab in ((c, h.dc_tables[c]), (3 + c, h.ac_tables[c])):
+                lut, mc, vo, hv = device_tables(tab)
+                r["lut"][t], r["maxcode"][t], r["valoff"][t], r["huffval"][t] = lut, mc, vo, hv
+        out_offs.append(out_bytes)
+        out_bytes += h.width * h.height * 3
+        tot["total_scan_bytes"] += (scan + 3) // 4 * 4 + 16
+        tot["total_intervals"] += nint + 1
+        tot["total_units"] += units
+        tot["total_blocks"] += nmcu * bpm
+        tot["total_plane_bytes"] += (plane + 15) // 16 * 16
+        tot["max_units"] = max(tot["max_units"], units)
+        tot["max_intervals"] = max(tot["max_intervals"], nint)
+        tot["max_width"] = max(tot["max_width"], h.width)
+        tot["max_height"] = max(tot["max_height"], h.height)
+        tot["max_blocks"] = max(tot["max_blocks"], nmcu * bpm)
+        tot["max_scan_bytes"] = max(tot["max_scan_bytes"], scan)
+    if (tot["total_intervals"] >= 2 ** 31 or tot["total_units"] >= 2 ** 31
+            or tot["max_scan_bytes"] > MAX_SCAN_BYTES):
+        raise RuntimeError("JPEG batch too large for one decode call")
+    return rec, tot, out_offs, out_bytes
