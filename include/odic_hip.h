@@ -63,6 +63,13 @@ const char* odic_build_info(void);
  *   bias: fp32, NULL or length N (bias_axis 0, per column) / length M (bias_axis 1, per row)
  *   residual: fp32 [M,N] (ldr) or NULL; out: `out_dtype` [M,N] (ldc)
  *   batch > 1: operands advance by the given element strides (0 = shared operand).
+ *   Containment (every family, every tile configuration; pinned by tests/test_containment_gpu.py): `out` columns [N, ldc) of
+ *   every row, rows >= M and the elements between batches (strideC > M·ldc) are LEFT UNTOUCHED — a caller may keep zeros
+ *   there and read them as the K padding of a later product.  Nothing is read from A / a_ln / W columns [K, ld), rows
+ *   >= M / >= N, residual columns [N, ldr), or past the N (M) entries of bias / col_scale / ln_colsum
+ *   (test_gemm_f32_folded_layernorm_reads_exactly_n_column_sums): those bytes may hold anything, NaN included.  A refused
+ *   launch writes nothing.  (`out16` / `stats_out` exist in -DODIC_EXPERIMENTAL_GEMM builds only; their padding is pinned by
+ *   no test of the default build.)
  * Replaces every nn.Linear on the path: swin_transformer_mod.py:190,212 (qkv/proj), :94-97
  * (Mlp fc1/fc2), :396 (PatchMerging.reduction), layers.py:49-51,99,154-161,274-276,293,306-307,
  * End_ExpansionNet_v2.py:82,97,134,137.
@@ -134,6 +141,8 @@ int odic_gemm(const odic_gemm_args* args, void* stream);
  * LayerNorm over the last dim (eps inside sqrt, biased variance — torch.nn.LayerNorm).
  *   x fp32 [M,C] (ldx) → out `out_dtype` [M,C] contiguous (ODIC_F32 / ODIC_BF16 / ODIC_FP8 / ODIC_H2; an fp8 consumer's
  *   quantisation scale is folded into gamma / beta by the caller).   C % 4 == 0 (ODIC_H2: % 8), C <= 8192.
+ *   `out` has no leading dimension: exactly M·C elements are written, nothing in front or behind; x columns [C, ldx) are
+ *   not read (test_layernorm_reads_ldx_and_writes_compact_rows).
  * Replaces swin_transformer_mod.py:309,338 (norm1/norm2), :639 (final norm), layers.py:119,121,
  * 225,228,232 and the reduce norms End_ExpansionNet_v2.py:99,135.
  * ------------------------------------------------------------------------------------------- */
@@ -141,11 +150,13 @@ int odic_layernorm(const float* x, int64_t ldx, const float* gamma, const float*
                    int32_t M, int32_t C, float eps, int32_t out_dtype, void* stream);
 
 /* Device-to-device copy of nbytes (a multiple of 16; both pointers 16-byte aligned) by a kernel of this library:
- * the pipeline's K/V hand-off from the encode stream's staging buffer to a decode lane. */
+ * the pipeline's K/V hand-off from the encode stream's staging buffer to a decode lane.  Exactly nbytes of dst are written
+ * (test_copy_exact_extent). */
 int odic_copy(const void* src, void* dst, int64_t nbytes, void* stream);
 
 /* Row-strided fp32 → bf16 conversion (feeds fp32 residual streams / caller tensors to the bf16 MFMA
- * GEMM).  x fp32 [M,C] (ldx) → out bf16 [M,C] (ldo); C, ldx, ldo multiples of 4. */
+ * GEMM).  x fp32 [M,C] (ldx) → out bf16 [M,C] (ldo); C, ldx, ldo multiples of 4.  out columns [C, ldo) are left untouched,
+ * x columns [C, ldx) are not read (test_casts_respect_ldx_and_ldo; the same for the split-fp16 form below). */
 int odic_cast_f32_to_bf16(const float* x, int64_t ldx, void* out, int64_t ldo, int32_t M, int32_t C,
                           void* stream);
 /* The same into split fp16 (ODIC_H2): C % 8 == 0, ldo % 8 == 0 (elements of 4 bytes), out 32-byte aligned. */
@@ -153,14 +164,16 @@ int odic_cast_f32_to_h2(const float* x, int64_t ldx, void* out, int64_t ldo, int
 
 /* PatchMerging gather + LayerNorm(4C)  (swin_transformer_mod.py:386-395):
  *   x fp32 [B, res*res, C] → out `out_dtype` (ODIC_F32 / ODIC_BF16 / ODIC_H2) [B, (res/2)², 4C]; channel blocks in
- *   the order (0,0),(1,0),(0,1),(1,1) of the 2x2 neighbourhood (row offset, col offset). */
+ *   the order (0,0),(1,0),(0,1),(1,1) of the 2x2 neighbourhood (row offset, col offset).  `out` is compact: exactly
+ *   B·(res/2)²·4C elements are written, nothing in front or behind (test_patch_merge_layernorm_compact_output). */
 int odic_patch_merge_layernorm(const float* x, const float* gamma, const float* beta, void* out,
                                int32_t B, int32_t res, int32_t C, float eps, int32_t out_dtype,
                                void* stream);
 
 /* PatchEmbed: Conv2d(in_chans→C, k=s=patch) + flatten + LayerNorm(C)
  * (swin_transformer_mod.py:511-519).  img fp32 [B,in_chans,H,W]; w fp32 [C,in_chans*patch*patch];
- * out fp32 [B,(H/patch)*(W/patch),C].  patch == 4, C in {64,96,128,192,256}, in_chans*16 <= 64. */
+ * out fp32 [B,(H/patch)*(W/patch),C].  patch == 4, C in {64,96,128,192,256}, in_chans*16 <= 64.  `out` is compact: exactly
+ * that many elements are written (test_patch_embed_compact_output). */
 int odic_patch_embed(const float* img, const float* w, const float* b, const float* gamma,
                      const float* beta, float* out, int32_t B, int32_t in_chans, int32_t H,
                      int32_t W, int32_t patch, int32_t C, float eps, void* stream);
@@ -236,7 +249,9 @@ typedef struct odic_jpeg_batch {
  * invalid descriptor. */
 size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* batch);
 
-/* Decode the batch on `stream` (one pass of launches, no host synchronisation, capturable). */
+/* Decode the batch on `stream` (one pass of launches, no host synchronisation, capturable).  At most ws_bytes =
+ * odic_jpeg_workspace_bytes(batch) of `workspace` are touched, `data` is only read, and exactly the images' H·W·3 bytes of
+ * `out` and n_images entries of `status` are written (test_jpeg_decode_stays_inside_its_workspace). */
 int odic_jpeg_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -253,7 +268,9 @@ int odic_jpeg_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_by
  *        The fast kernel keeps the 9 KiB in LDS, loads the bias as the accumulator init of the q·kᵀ MFMA and
  *        applies scale·log2(e) afterwards (base-2 softmax).  NULL → the table is used (slower kernel).
  *   out  `dtype` [B*res*res, C]    softmax(q·kᵀ·scale + bias + mask)·v, heads concatenated,
- *        written back at the un-shifted token positions (ready for the proj Linear).
+ *        written back at the un-shifted token positions (ready for the proj Linear).  Compact: exactly B·res²·C elements
+ *        are written and nothing outside qkv's B·res²·3C is read, for every dtype, B and shift
+ *        (test_window_attention_front_and_back_guards).
  * head_dim is 32 (every Swin-L stage), ws*ws <= 144, res % ws == 0, 0 <= shift < ws.
  * dtype ODIC_H2 (near-exact fast mode; needs bias_shifted_prescaled, ws = 12): qkv and out are split-fp16 tensors,
  *        q·kᵀ and P·v run as three fp16 MFMAs each, the softmax between them in fp32.
@@ -269,7 +286,8 @@ int odic_window_attention(const void* qkv, const float* bias_table, const float*
  *   w_qkv_folded bf16 [3C, C], b_qkv_folded fp32 [3C]:  W·diag(gamma) and bias + W·beta of norm1 → qkv (the caller folds the
  *            LayerNorm's affine part at pack time; the kernel computes (x − mean)/sqrt(var + ln_eps) in registers)
  *   bias_shifted_prescaled fp32 [heads, 4, 576]   as for odic_window_attention
- *   out      bf16 [B*res*res, C]   attention output at the un-shifted token positions (ready for the proj Linear)
+ *   out      bf16 [B*res*res, C]   attention output at the un-shifted token positions (ready for the proj Linear); compact:
+ *            exactly B·res²·C elements are written; x columns [C, ldx) are not read (test_swin_qkv_attention_ldx_and_guards)
  * One block per window keeps its 144 normalised rows as MFMA fragments in registers; q / k / v of a head never leave the
  * chip.  Results are bit-identical to odic_gemm(a_ln = x, …) followed by odic_window_attention (bf16).
  * ------------------------------------------------------------------------------------------- */
@@ -285,7 +303,8 @@ int odic_swin_qkv_attention(const float* x, int64_t ldx, const void* w_qkv_folde
  *        (layers.py:56-61) → pos_fw, neg_fw `out_dtype` [B, nq, ld_fw].  enc_len[b] = #valid keys.
  *   bw:  relu(±zᵀ), each of the `ngroups` column groups L1-normalised separately (layers.py:67-79)
  *        and pre-divided by ngroups (:84-85) → pos_bw, neg_bw `out_dtype` [B, S, ld_bw].
- *   ld_fw >= S and ld_bw >= nq: the padding columns are written as zeros, so the outputs can be the
+ *   ld_fw >= S and ld_bw >= nq: the padding columns [S, ld_fw) / [nq, ld_bw) are ZERO-FILLED (the opposite of odic_gemm's
+ *        outputs; nothing beyond the last row is written — test_stcexp_normalize_zero_fills_its_padding), so the outputs can be the
  *        K-padded operands of odic_gemm (bf16 needs K % 64 == 0, ODIC_H2 K % 32 == 0); out_dtype ODIC_F32 / ODIC_BF16 /
  *        ODIC_H2.
  *   group_meta: device int32 [ngroups+1+nq] = exclusive prefix sums of the group sizes (last = nq)
@@ -301,7 +320,8 @@ int odic_stcexp_normalize(const float* z, const int32_t* enc_len, const int32_t*
                           int32_t S, float eps, float scale_fw, float scale_bw, int32_t out_dtype, void* stream);
 
 /* out = x + sigmoid(sel_pre)·a + (1-sigmoid(sel_pre))·b     (layers.py:99-100 + the residual add of
- * EncoderLayer :120); all fp32 [M, d] with row strides. */
+ * EncoderLayer :120); all fp32 [M, d] with row strides.  out columns [d, ldo) are left untouched and the inputs' columns
+ * beyond d are not read, so out may be a column block of the buffer x lives in (test_selector_mix_leading_dimensions). */
 int odic_selector_mix(const float* x, int64_t ldx, const float* sel_pre, int64_t lds,
                       const float* a, int64_t lda, const float* b, int64_t ldb, float* out,
                       int64_t ldo, int32_t M, int32_t d, void* stream);
@@ -315,7 +335,8 @@ int odic_selector_mix(const float* x, int64_t ldx, const float* sel_pre, int64_t
 
 /* y[n,:] = embed[tok[n]]·sqrt(d) + pos_table[pos]   (layers.py:16-17, End_ExpansionNet_v2.py:118-121).
  * pos_rows = rows of pos_table (pos_encoder = nn.Embedding(max_seq_len, d), End_ExpansionNet_v2.py:105): *pos is device
- * memory, so the bound is checked ON the device — a launch with *pos outside [0, pos_rows) writes nothing. */
+ * memory, so the bound is checked ON the device — a launch with *pos outside [0, pos_rows) writes nothing.  y columns
+ * [d, ldy) are left untouched (test_dec_embed_ldy). */
 int odic_dec_embed(const int64_t* tokens, const float* embed, const float* pos_table,
                    const int32_t* pos, float* y, int64_t ldy, int32_t N, int32_t d, int32_t pos_rows,
                    float scale, void* stream);
@@ -338,6 +359,9 @@ int odic_dec_embed(const int64_t* tokens, const float* embed, const float* pos_t
  *   y_in fp32 [N,d] (ldy_in) → y fp32 [N,d] (ldy):  y = y_in + sel·A' + (1-sel)·B'  (may alias).
  *   T <= 128, E in {4, 8, 16, 32}, d a multiple of 64; one launch (one 1024-thread block per sequence).
  *   A launch with *pos outside [0, T) changes nothing (the caches hold T positions; checked on the device).
+ *   y columns [d, ldy) are left untouched; lin columns beyond 5d and y_in columns beyond d are not read; the caches are
+ *   compact, written only at position *pos, and no entry is read that an earlier position did not write — they need no
+ *   clearing (test_dynexp_step_leading_dimensions_and_caches).
  */
 int odic_dynexp_step(const float* lin, int64_t ldlin, const float* qexp, const float* bexp,
                      float* cond_c, float* key_c, float* va_c, float* vb_c, float* wfa_c,
@@ -351,7 +375,10 @@ int odic_dynexp_step(const float* lin, int64_t ldlin, const float* qexp, const f
  *   kv fp32 [n_img, S, ldkv]: projected keys at column koff, values at column voff;
  *   enc_len int32 [n_img]; beams = N / n_img; row_valid as above (0 → all scores masked to -1e4,
  *   i.e. a uniform average over all S positions, exactly what masked_fill + softmax gives).
- *   out fp32 [N, d] (ldo) = softmax(q·kᵀ/sqrt(d/heads))·v, heads concatenated.  d/heads in {16,32,64}. */
+ *   out fp32 [N, d] (ldo) = softmax(q·kᵀ/sqrt(d/heads))·v, heads concatenated.  d/heads in {16,32,64}.
+ *   ldq, ldkv and koff are multiples of 4 and q / kv 16-byte aligned (ODIC_EINVAL otherwise, before any launch).  Every
+ *   out row is written, row_valid = 0 rows included; out columns [d, ldo) are left untouched; q / kv columns beyond their
+ *   widths are not read (test_cross_attn_step_leading_dimensions). */
 int odic_cross_attn_step(const float* q, int64_t ldq, const float* kv, int64_t ldkv, int32_t koff,
                          int32_t voff, const int32_t* enc_len, const int32_t* row_valid, float* out,
                          int64_t ldo, int32_t N, int32_t n_img, int32_t S, int32_t d, int32_t heads,
@@ -359,7 +386,8 @@ int odic_cross_attn_step(const float* q, int64_t ldq, const float* kv, int64_t l
 
 /* log_softmax over V + top-k (captioning_model.py:126-127,162-170).  logits fp32 [N, V] (ldl);
  * writes logp_out fp32 [N, V] (ldp) if non-NULL, top_val fp32 [N,k] / top_idx int32 [N,k] sorted
- * descending (ties: lower index first).  k <= 16. */
+ * descending (ties: lower index first).  k <= 16.  logp_out columns [V, ldp) are left untouched, top_val / top_idx are compact,
+ * logits columns [V, ldl) are not read (test_logsoftmax_topk_leading_dimensions). */
 int odic_logsoftmax_topk(const float* logits, int64_t ldl, float* logp_out, int64_t ldp,
                          float* top_val, int32_t* top_idx, int32_t N, int32_t V, int32_t k,
                          void* stream);
@@ -368,17 +396,21 @@ int odic_logsoftmax_topk(const float* logits, int64_t ldl, float* logp_out, int6
  * replacement=False); :59-109 ancestral sampling with k = 1): k words drawn WITHOUT replacement from
  * softmax(logits[n]) on the device (Gumbel-top-k), top_idx int32 [N,k] in draw order, top_val fp32 [N,k] =
  * their log-probabilities; logp_out as in odic_logsoftmax_topk.  Noise = Philox4x32-10(seed; row, word/4,
- * *pos): `pos` (device int32 scalar, may be NULL = 0) separates the steps of a captured graph. */
+ * *pos): `pos` (device int32 scalar, may be NULL = 0) separates the steps of a captured graph.  Padding as for
+ * odic_logsoftmax_topk: logp_out columns [V, ldp) left untouched, top_val / top_idx compact
+ * (test_logsoftmax_sample_leading_dimensions). */
 int odic_logsoftmax_sample(const float* logits, int64_t ldl, float* logp_out, int64_t ldp, float* top_val,
                            int32_t* top_idx, int32_t N, int32_t V, int32_t k, uint64_t seed,
                            const int32_t* pos, void* stream);
 
 /* Ensemble step distribution (ensemble_captioning_model.py:66-83): `logits` is a HOST array of M (<= 8)
- * device pointers to fp32 [N, V] logits (row pitch ldl); out[n][v] = log(mean_m softmax(logits_m[n])[v]). */
+ * device pointers to fp32 [N, V] logits (row pitch ldl); out[n][v] = log(mean_m softmax(logits_m[n])[v]).  out columns
+ * [V, ldo) are left untouched, logits columns [V, ldl) are not read. */
 int odic_ensemble_logprobs(const float* const* logits, int32_t M, int64_t ldl, float* out, int64_t ldo,
                            int32_t N, int32_t V, void* stream);
 /* k largest entries of every row (ties → lower index), values taken as they are (rows already hold
- * log-probabilities, e.g. the output of odic_ensemble_logprobs): top_val fp32 [N,k], top_idx int32 [N,k]. */
+ * log-probabilities, e.g. the output of odic_ensemble_logprobs): top_val fp32 [N,k], top_idx int32 [N,k], both compact;
+ * logp columns [V, ldl) are not read (test_ensemble_logprobs_and_topk_rows_leading_dimensions, also for the one above). */
 int odic_topk_rows(const float* logp, int64_t ldl, float* top_val, int32_t* top_idx, int32_t N, int32_t V,
                    int32_t k, void* stream);
 
@@ -391,6 +423,9 @@ int odic_topk_rows(const float* logp, int64_t ldl, float* top_val, int32_t* top_
  *   row_valid int32 [N] (output: 1 while the beam was still growing), next_tok int64 [N] (output:
  *   token to feed at the next step), pos int32 scalar (incremented at the end),
  *   done int32 scalar (set to 1 when every beam has stopped growing, :222).
+ * All of these are compact arrays without leading dimensions.  The search-level test
+ * test_pipeline_search_is_independent_of_the_previous_search pins that a search reads nothing a previous search left in them;
+ * no guarded-buffer test covers the beam kernels' stores yet.
  */
 typedef struct odic_beam_state {
   int64_t* tokens; float* logprobs; int32_t* anc;

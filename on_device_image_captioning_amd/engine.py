@@ -423,6 +423,9 @@ class CaptionerEngine:
         # K-padded operands.  odic_stcexp_normalize writes its four outputs out to their leading dimension (zeros in the
         # padding), so they need no clearing; the three GEMM outputs whose padding columns no launch ever writes are kept
         # per (shape, stream) and zeroed ONCE — clearing them inside every captured encode pass was seven fill launches
+        # (both halves of this contract are pinned by tests/test_containment_gpu.py: odic_gemm leaves columns [N, ldc) untouched
+        # for every tile configuration — test_gemm_engine_padded_products_verbatim — and the result of a call does not depend
+        # on the call before it — test_encode_is_independent_of_the_previous_call)
         ec = lambda *s: torch.empty(*s, dtype=cdt, device=dv)               # noqa: E731
         pf, nf = ec(B, nq, Sp), ec(B, nq, Sp)
         pb, nb = ec(B, S, nqp), ec(B, S, nqp)

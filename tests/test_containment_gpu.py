@@ -1,0 +1,1125 @@
+"""Containment: a launch writes nothing outside its output operand and its result does not depend on anything outside its
+input operands.
+
+Every operand lives in a guarded buffer (tests/guards.py): poison bytes (0xFF = NaN) in front, behind, in the columns between
+the operand's width and its leading dimension and between batches.  Each case asserts three things:
+  * values against the fp64 reference of the operation's existing test, with that test's bound (named where it is used);
+  * every guard byte intact (bitwise);
+  * the operand's bytes identical to the same call on compact, exactly-sized, unpoisoned operands — layout must not
+    change arithmetic, and a stray READ of padding would have turned the result into NaN.
+
+Nothing here provokes a fault: the guards sit inside one live allocation, a breach is a changed byte.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import guards
+from guards import H2, guarded, poisoned_input
+from test_hip_ops import assert_close, rnd
+from test_x3_gpu import rel_err
+
+from conftest import cached_state_dict
+from on_device_image_captioning_amd import weights as W
+
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+DEV = "cuda"
+F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
+FP8 = torch.float8_e4m3fn
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from on_device_image_captioning_amd import _hip, ops as o
+    _hip.load()
+    return o
+
+
+def _lib():
+    from on_device_image_captioning_amd import _hip
+    return _hip, _hip.load()
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ============================================================================================== a + b. GEMM stores and loads
+from containment_cases import (APANEL, BM, FAMILIES, KDEF, KPAD, ODTS, Case, cases as _cases, panel_candidates, panel_cases,
+                               tiled_tiles as _tiled_tiles)
+
+#: (family, tile) -> tags of the cases that RAN ("raggedM", "raggedN", "ldc") or that the library REFUSED with its documented
+#: error ("refused:raggedM", ...), and the families whose sweep ran in this session (test_gemm_coverage_every_selectable_tile)
+COVER, NCASES, SWEPT = {}, {}, set()
+
+
+def _operand(ops, fam, x32):
+    """fp32 values (CPU) -> (device operand of the family's input dtype, the values it really carries as float64, dtype marker)."""
+    if fam == "bf16":
+        t = x32.bfloat16()
+        return t.to(DEV), t.double(), BF16
+    if fam == "x3":
+        return ops.h2_from_f32(x32).to(DEV), x32.double(), H2           # (22 significand bits: the mode's bound covers it)
+    if fam == "fp8":
+        t = x32.clamp(-448, 448).to(FP8)
+        return t.to(DEV), t.float().double(), FP8
+    if fam == "fp16":
+        t = x32.half()
+        return t.to(DEV), t.double(), F16
+    return x32.to(DEV), x32.double(), F32
+
+
+def _act64(v, act):
+    return [lambda t: t, torch.nn.functional.gelu, torch.relu, torch.sigmoid][act](v)
+
+
+def _bound(fam, odt, act):
+    """The value bound of the family's EXISTING test (relative to the output scale, tests/test_hip_ops.py::assert_close).
+    None: the output type has a per-element check instead (_assert_values)."""
+    if fam == "f32":      # test_gemm_f32_*: 2e-5 (a bf16 output: per element, see _assert_values)
+        return 2e-5
+    if fam == "bf16":     # test_gemm_bf16_random / _every_tile_config: 2e-4 into fp32, 6e-3 into bf16
+        return 2e-4 if odt == F32 else 6e-3
+    if fam == "x3":       # test_gemm_x3_random_against_fp64: 1e-6; with an activation test_gemm_x3_epilogues: 2e-6
+        return 1e-6 if act == 0 else 2e-6
+    if odt == FP8:        # test_gemm_fp8_identity_and_random: per element, half an e4m3 ulp
+        return None
+    if odt == F16:        # test_gemm_fp8_identity_and_random: 1e-3 into fp16 (the fp16-operand kernel shares that epilogue)
+        return 1e-3
+    return 1e-4 if fam == "fp8" else 2e-5      # test_gemm_fp8_identity_and_random: 1e-4 into fp32; test_gemm_f16: 2e-5
+
+
+def _assert_values(got, want, fam, odt, act, what):
+    """The existing bound of the family (relative to the output scale), plus, where the kernel evaluates GELU by its
+    polynomial (bf16 / fp8 / fp16 operands), the 6e-5 ABSOLUTE error test_gelu_poly_accuracy allows it — the existing GEMM
+    bounds were set on products without an activation.  e4m3 outputs: the per-element form of test_gemm_fp8_identity_and_random
+    (half an ulp of 3 mantissa bits, 2^-9 below the normal range).  bf16 outputs of the fp32 kernel (no existing test): the
+    same per-element form with bf16's 8 significand bits (2^-8 of the element, test_hip_ops' docstring) on top of the fp32
+    kernel's 2e-5 of the scale."""
+    got, want = got.double(), want.double()
+    err = (got - want).abs()
+    if odt == FP8:
+        wc = want.clamp(-448, 448)
+        err = (got - wc).abs()
+        worst = float((err - wc.abs() * 2 ** -4).max())
+        assert worst <= 2 ** -9 + 1e-6, f"{what}: {worst:.3e} beyond half an e4m3 ulp"
+        return
+    scale = float(want.abs().max()) + 1e-12
+    extra = 6e-5 if (act == 1 and fam in ("bf16", "fp8", "fp16")) else 0.0
+    if fam == "f32" and odt == BF16:
+        worst = float((err - want.abs() * 2 ** -8).max())
+        assert worst <= 2e-5 * scale, f"{what}: {worst:.3e} beyond bf16 rounding + 2e-5 of scale {scale:.3e}"
+        return
+    rtol = _bound(fam, odt, act)
+    assert float(err.max()) <= rtol * scale + extra, f"{what}: max err {float(err.max()):.3e} vs scale {scale:.3e} (rtol {rtol}, +{extra})"
+
+
+def _torch_odt(ops, odt):
+    return ops.H2_DTYPE if odt == H2 else odt
+
+
+def _run_gemm(ops, fam, tile, odt, c, K=None, seed=0, poison_inputs=True, ldr_step=5):
+    """One case: the guarded / poisoned launch, the compact launch, the fp64 reference.  Returns the guarded output."""
+    K = K or KDEF[fam]
+    M, N, Bn = c.M, c.N, c.batch
+    a32, w32 = rnd(M, K, seed=seed + 1), rnd(Bn, N, K, seed=seed + 2, scale=0.05)
+    wsc = ops.pow2_scale_for_h2(w32) if fam == "x3" else 1.0
+    A, a64, idt = _operand(ops, fam, a32)
+    Wt, w64, _ = _operand(ops, fam, w32 * wsc)
+    w64 = w64 / wsc
+    alpha = c.alpha / wsc
+    bias32 = None if c.bias is None else rnd(N if c.bias == "col" else M, seed=seed + 3)
+    r32 = rnd(Bn, M, N, seed=seed + 4) if c.residual else None
+    col_scale32 = (0.5 + torch.rand(N, generator=torch.Generator().manual_seed(seed + 5))) if fam in ("fp8", "fp16") else None
+    want = torch.einsum("mk,bnk->bmn", a64, w64) * c.alpha
+    if col_scale32 is not None:
+        want = want * col_scale32.double()
+    if bias32 is not None:
+        want = want + (bias32.double()[None, None, :] if c.bias == "col" else bias32.double()[None, :, None])
+    want = _act64(want, c.act)
+    if r32 is not None:
+        want = want + r32.double()
+    todt = _torch_odt(ops, odt)
+
+    def launch(out_t, ldc, strideC, A_t, lda, W_t, ldw, strideW, bias_t, res_t, ldr, strideR, cs_t):
+        ops.gemm(A_t, W_t, bias_t, res_t, out=out_t, act=c.act, alpha=alpha, bias_axis=1 if c.bias == "row" else 0,
+                 M=M, N=N, K=K, lda=lda, ldw=ldw, ldr=ldr, ldc=ldc, batch=Bn, strideA=0, strideW=strideW, strideR=strideR,
+                 strideC=strideC, tile_cfg=tile, col_scale=cs_t)
+
+    # ---- compact, exactly-sized, unpoisoned operands (split-fp16 rows are whole groups of 8)
+    ldc0 = -(-N // 8) * 8 if odt == H2 else N
+    o0 = guarded(M, N, ldc0, odt, DEV, batch=Bn, stride=M * ldc0)
+    res0 = None
+    if c.inplace:
+        o0.t3[:, :, :N].copy_(r32.to(DEV))
+        res0, ldr0, sr0 = o0.t, ldc0, M * ldc0
+    elif r32 is not None:
+        res0, ldr0, sr0 = r32.to(DEV), N, M * N
+    else:
+        ldr0, sr0 = None, 0
+    launch(o0.t.view(todt) if odt == H2 else o0.t, ldc0, M * ldc0, A, K, Wt, K, N * K,
+           None if bias32 is None else bias32.to(DEV), res0, ldr0, sr0, None if col_scale32 is None else col_scale32.to(DEV))
+
+    # ---- the same call on guarded output and poisoned inputs: lda / ldw / ldr above the width, NaN rows behind M and N
+    strideC = M * c.ldc + c.gap
+    o1 = guarded(M, N, c.ldc, odt, DEV, batch=Bn, stride=strideC)
+    ins = []
+    if poison_inputs:
+        lda = ldw = K + KPAD[fam]
+        gA = poisoned_input(A, M, K, lda, dtype=idt)
+        gW = poisoned_input(Wt, N, K, ldw, batch=Bn, stride=N * ldw + 16, dtype=idt)
+        ins += [gA, gW]
+        A1, W1, sW = gA.t, gW.t, N * ldw + 16
+        b1 = cs1 = None
+        if bias32 is not None:                  # exactly N (M) long inside a poisoned buffer
+            gb = poisoned_input(bias32, 1, bias32.numel(), bias32.numel(), device=DEV)
+            ins.append(gb)
+            b1 = gb.t
+        if col_scale32 is not None:
+            gc = poisoned_input(col_scale32, 1, N, N, device=DEV)
+            ins.append(gc)
+            cs1 = gc.t
+    else:
+        A1, lda, W1, ldw, sW = A, K, Wt, K, N * K
+        b1 = None if bias32 is None else bias32.to(DEV)
+        cs1 = None if col_scale32 is None else col_scale32.to(DEV)
+    res1, ldr1, sr1 = None, None, 0
+    if c.inplace:
+        o1.t3[:, :, :N].copy_(r32.to(DEV))
+        res1, ldr1, sr1 = o1.t, c.ldc, strideC
+    elif r32 is not None:
+        ldr1 = N + ldr_step                     # ldr > N, NaN pad columns (an odd ldr: the element-wise residual path)
+        gR = poisoned_input(r32, M, N, ldr1, batch=Bn, stride=M * ldr1 + 3, device=DEV)
+        ins.append(gR)
+        res1, sr1 = gR.t, M * ldr1 + 3
+    launch(o1.t.view(todt) if odt == H2 else o1.t, c.ldc, strideC, A1, lda, W1, ldw, sW, b1, res1, ldr1, sr1, cs1)
+    torch.cuda.synchronize()
+
+    what = f"{fam} tile {tile} -> {odt} [{c.name}] {M}x{N}x{K}"
+    o1.assert_untouched(what=what)
+    o0.assert_untouched(what=what + " (compact)")
+    for g in ins:
+        g.assert_untouched(what=what + " (an INPUT was written)")
+    got = o1.values()
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output — padding of an input was read into the result"
+    assert torch.equal(o1.data_bytes(), o0.data_bytes()), \
+        f"{what}: differs from the compact call (max diff {float((got - o0.values()).abs().max()):.3e})"
+    if odt == H2:      # as test_gemm_x3_random_against_fp64: the same values as the fp32 output, split again
+        return o1, want, what
+    _assert_values(got, want, fam, odt, c.act, what)
+    return o1, want, what
+
+
+def _h2_bytes_of(ops, vals32, N):
+    """Owned bytes of h2_from_f32(vals32) for rows of N columns (padded to whole groups of 8)."""
+    N8 = -(-N // 8) * 8
+    pad = torch.zeros(*vals32.shape[:-1], N8)
+    pad[..., :N] = vals32
+    by = ops.h2_from_f32(pad).contiguous().view(torch.uint8).reshape(*vals32.shape[:-1], N8 * 4).numpy()
+    return torch.from_numpy(np.ascontiguousarray(by[..., guards.owned_bytes(N, N8, H2)]))
+
+
+def _count(fam, tile, tags, n=1):
+    COVER.setdefault((fam, tile), set()).update(tags)
+    NCASES[fam] = NCASES.get(fam, 0) + n
+
+
+@pytest.mark.parametrize("fam", ["bf16", "x3", "fp8", "fp16", "f32"])
+def test_gemm_stores_and_loads_every_tile(ops, fam):
+    SWEPT.add(("tiled", fam))
+    for tile in _tiled_tiles(ops, fam):
+        bm = BM[fam][tile]
+        f32_vals = {}
+        for odt in ODTS[fam]:
+            for c in _cases(fam, bm, odt):
+                o1, want, what = _run_gemm(ops, fam, tile, odt, c)
+                if odt == F32:
+                    f32_vals[c.name] = o1.values().float()
+                if odt == H2:
+                    ref32 = f32_vals[c.name]
+                    assert rel_err(ref32, want) <= _bound("x3", F32, c.act), what
+                    assert torch.equal(o1.data_bytes(), _h2_bytes_of(ops, ref32, c.N)), f"{what}: not the split of the fp32 output"
+                _count(fam, tile, c.tags)
+
+
+@pytest.mark.parametrize("fam", ["bf16", "x3"])
+def test_gemm_a_resident_tiles_whole_tiles_only(ops, fam):
+    """tile_cfg 50-53 / 20, 21 take whole tiles only: ragged M and ragged N are REFUSED by the library (its documented error),
+    so for them containment means ldc > N, the residual forms and the LayerNorm-while-reading form (a_ln rows poisoned)."""
+    _hip, lib = _lib()
+    SWEPT.add(("panel", fam))
+    for tile, (bm, bnc, K) in APANEL[fam].items():
+        M, N = 2 * bm, 3 * bnc
+        for odt in ODTS[fam]:
+            for c in panel_cases(fam, tile, odt):
+                # (the A-resident kernels read the residual in 16-byte pieces: ldr % 4 == 0, refused otherwise before any launch)
+                o1, want, what = _run_gemm(ops, fam, tile, odt, c, K=K, ldr_step=4)
+                if odt == H2:
+                    assert rel_err(o1.values(), want) <= _bound("x3", F32, c.act) + 2.0 ** -22, what   # (+ the output's own split)
+                _count(fam, tile, c.tags)
+        for tag, (Mr, Nr) in (("raggedM", (M + 1, N)), ("raggedN", (M, N + 1))):
+            with pytest.raises(RuntimeError):
+                ops.gemm(_operand(ops, fam, torch.zeros(Mr, K))[0], _operand(ops, fam, torch.zeros(Nr, K))[0],
+                         out_dtype=F32, tile_cfg=tile)
+            _count(fam, tile, ("refused:" + tag,), 0)
+        # LayerNorm while reading: a_ln fp32 rows with ld_aln > K (NaN pad columns, NaN rows behind M), guarded output
+        x32 = rnd(M, K, seed=7, scale=2.0) + 0.5
+        w32, b32 = rnd(N, K, seed=8, scale=0.05), rnd(N, seed=9)
+        wsc = ops.pow2_scale_for_h2(w32) if fam == "x3" else 1.0
+        Wt, w64, _ = _operand(ops, fam, w32 * wsc)
+        want = torch.nn.functional.layer_norm(x32.double(), (K,), None, None, 1e-5) @ (w64 / wsc).T + b32.double()
+        for odt in ODTS[fam]:
+            outs = []
+            for ld_aln, ldc in ((K, -(-N // 8) * 8), (K + 4, N + 8)):
+                gx = poisoned_input(x32, M, K, ld_aln, device=DEV)
+                gb = poisoned_input(b32, 1, N, N, device=DEV)
+                o = guarded(M, N, ldc, odt, DEV)
+                a = _hip.GemmArgs()
+                a.W, a.bias, a.out, a.M, a.N, a.K = Wt.data_ptr(), gb.data_ptr(), o.data_ptr(), M, N, K
+                a.lda, a.ldw, a.ldc, a.batch, a.alpha, a.ln_eps = K, K, ldc, 1, 1.0 / wsc, 1e-5
+                a.in_dtype = ops.dtype_code(Wt.dtype)
+                a.out_dtype = ops.dtype_code(_torch_odt(ops, odt))
+                a.tile_cfg, a.a_ln, a.ld_aln = tile, gx.data_ptr(), ld_aln
+                _hip.check(lib.odic_gemm(C.byref(a), _stream()), "odic_gemm")
+                torch.cuda.synchronize()
+                what = f"{fam} tile {tile} a_ln -> {odt} ld_aln={ld_aln} ldc={ldc}"
+                o.assert_untouched(what=what)
+                gx.assert_untouched(what=what + " (a_ln was written)")
+                assert bool(torch.isfinite(o.values()).all()), what
+                outs.append(o)
+            assert torch.equal(outs[0].data_bytes(), outs[1].data_bytes()), f"{fam} tile {tile} a_ln -> {odt}: layout changed the result"
+            # bounds of test_gemm_bf16_layernorm_while_reading (bf16 out 1.2e-2, fp32 out 8e-3) / the x3 test (4e-6)
+            if fam == "bf16":
+                assert_close(outs[1].values()[0], want, 1.2e-2 if odt == BF16 else 8e-3, "a_ln vs fp64")
+            else:
+                assert rel_err(outs[1].values()[0], want) <= 4e-6
+            _count(fam, tile, ("ldc",))
+
+
+@pytest.mark.parametrize("fam", ["bf16", "x3", "fp8", "fp16", "f32"])
+def test_gemm_large_multi_tile(ops, fam):
+    """One 2304 x 1536-class case per family (many tiles, every XCD partition): ragged M, ldc > N, poisoned inputs."""
+    for odt in ODTS[fam][:2]:
+        c = Case("2303x1536 bias+relu ldc=1600", 2303, 1536, 1600, act=2, bias="col", tags=("raggedM", "ldc"))
+        o1, want, what = _run_gemm(ops, fam, -1, odt, c, K=192 if fam != "fp8" else 256)
+        if odt == H2:
+            assert rel_err(o1.values(), want) <= _bound("x3", F32, 2) + 2.0 ** -22, what
+        _count(fam, -1, c.tags)
+
+
+@pytest.mark.parametrize("K", [3, 37, 52])
+@pytest.mark.parametrize("shape", [-1, 0, 1, 2, 3])
+def test_gemm_f32_ragged_K_loads(ops, K, shape):
+    """The fp32 kernel takes any K: lda = ldw = K + 1 (element-wise loads) and K + 4 (the 16-byte loads over a ragged K), NaN
+    behind column K and behind rows M / N, both the 64 x 64 kernel (M = 300) and the skinny-M kernel's shapes (M = 41)."""
+    for M, N in ((300, 190), (41, 130)):
+        a32, w32, b32 = rnd(M, K, seed=1), rnd(N, K, seed=2), rnd(N, seed=3)
+        want = a32.double() @ w32.double().T + b32.double()
+        ref = ops.gemm(a32.to(DEV), w32.to(DEV), b32.to(DEV), tile_cfg=shape)
+        for step in (1, 4):
+            gA, gW = poisoned_input(a32, M, K, K + step, device=DEV), poisoned_input(w32, N, K, K + step, device=DEV)
+            gb = poisoned_input(b32, 1, N, N, device=DEV)
+            o = guarded(M, N, N + 1, F32, DEV)
+            ops.gemm(gA.t, gW.t, gb.t, out=o.t, M=M, N=N, K=K, lda=K + step, ldw=K + step, ldc=N + 1, tile_cfg=shape)
+            torch.cuda.synchronize()
+            what = f"f32 shape {shape} {M}x{N}x{K} lda=K+{step}"
+            o.assert_untouched(what=what)
+            got = o.t[:, :N]
+            assert bool(torch.isfinite(got).all()), what
+            assert_close(got, want, 2e-5, what)                         # test_gemm_f32_shapes
+            assert torch.equal(got, ref), what
+            _count("f32", shape, ("raggedM", "raggedN", "ldc"))
+
+
+@pytest.mark.parametrize("fam,Ks", [("bf16", (64, 320)), ("x3", (32, 160)), ("fp8", (64, 192)), ("fp16", (32, 160))])
+def test_gemm_k_granularity_smallest_and_mid(ops, fam, Ks):
+    """The K % 64 / K % 32 families at their smallest K and one mid K that is not a multiple of the next granularity."""
+    for K in Ks:
+        tiles = [-1] + ([0, 1, 2] if fam != "bf16" else [0, 1, 42])
+        for tile in tiles:
+            c = Case(f"K={K} bias ldc=N+8", 130, 72, 80, bias="col", tags=("raggedM", "raggedN", "ldc"))
+            _run_gemm(ops, fam, tile, F32, c, K=K)
+            _count(fam, tile, c.tags)
+
+
+@pytest.mark.parametrize("prec", ["bf16", "x3"])
+@pytest.mark.parametrize("B", [1, 3])
+def test_gemm_engine_padded_products_verbatim(ops, prec, B):
+    """The five K-padded products of CaptionerEngine.encode at the FULL geometry, with the engine's M, N, K, lda, ldw, ldr,
+    ldc, batch and strides: outputs AT / BT (ldc = nqp) and vabT (ldc = Sp) keep their padding columns untouched — the engine
+    zeroes them ONCE and reads them as the K padding of the next product in every later call."""
+    g = W.FULL
+    d, S, nq = g.d_model, 144, sum(g.num_exp_enc_list)
+    pad = 64 if prec == "bf16" else 32
+    Sp, nqp = -(-S // pad) * pad, -(-nq // pad) * pad
+    fam = prec
+    cdt = BF16 if prec == "bf16" else H2
+    tcdt = _torch_odt(ops, cdt)
+    # split fp16: the engine writes the normalised tables times a power of two (lo halves stay fp16 normals) and packs
+    # weights with pow2_scale_for_h2, both undone in alpha — the same here
+    fw_sc, bw_sc = (256.0, 4096.0) if prec == "x3" else (1.0, 1.0)
+
+    def operand(x32, rows, cols, ld, batch):
+        """values [batch, rows, cols] -> K-padded operand [batch, rows, ld] with ZERO padding (the contract: K padding finite)."""
+        full = torch.zeros(batch, rows, ld)
+        full[:, :, :cols] = x32
+        t, v64, idt = _operand(ops, fam, full)
+        return poisoned_input(t, rows, ld, ld, batch=batch, dtype=idt), v64[:, :, :cols]
+
+    tiles = _tiled_tiles(ops, fam)
+    for tile in tiles:
+        # (class_a | class_b) projections, transposed: [B, 2d, S] = W·x2ᵀ + b(row)
+        w32 = rnd(1, 2 * d, d, seed=1, scale=0.05)
+        wsc = ops.pow2_scale_for_h2(w32) if prec == "x3" else 1.0
+        gw, w64 = operand(w32 * wsc, 2 * d, d, d, 1)
+        gx, x64 = operand(rnd(B, S, d, seed=2), S, d, d, B)
+        bias = rnd(2 * d, seed=3)
+        vabT = guarded(2 * d, S, Sp, cdt, DEV, batch=B, stride=2 * d * Sp)
+        ops.gemm(gw.t, gx.t, bias.to(DEV), out=vabT.t.view(tcdt), bias_axis=1, M=2 * d, N=S, K=d, lda=d, ldw=d, ldc=Sp, batch=B,
+                 strideA=0, strideW=S * d, strideC=2 * d * Sp, alpha=1.0 / wsc, tile_cfg=tile)
+        want = torch.einsum("mk,bnk->bmn", w64[0], x64) / wsc + bias.double()[None, :, None]
+        _check_engine_product(vabT, want, prec, f"vabT tile {tile} B {B}")
+        # class_aT [d, nq] = VaT·pos_fwT + BvT, and class_b from the rows d.. of vabT
+        gv, v64 = operand(rnd(B, 2 * d, S, seed=4), 2 * d, S, Sp, B)
+        gp, p64 = operand(rnd(B, nq, S, seed=5).abs() / S * fw_sc, nq, S, Sp, B)
+        bvT = rnd(d, nq, seed=6)
+        for name, off in (("AT", 0), ("BT", d)):
+            o = guarded(d, nq, nqp, cdt, DEV, batch=B, stride=d * nqp)
+            ops.gemm(gv.t3[:, off:] if B > 1 else gv.t[off:], gp.t, residual=bvT.to(DEV), out=o.t.view(tcdt), M=d, N=nq, K=Sp,
+                     lda=Sp, ldw=Sp, ldr=nq, ldc=nqp, batch=B, strideA=2 * d * Sp, strideW=nq * Sp, strideR=0,
+                     strideC=d * nqp, alpha=1.0 / fw_sc, tile_cfg=tile)
+            want = torch.einsum("bmk,bnk->bmn", v64[:, off:off + d], p64) / fw_sc + bvT.double()[None]
+            _check_engine_product(o, want, prec, f"{name} tile {tile} B {B}")
+        # backward: [S, nq]·[nq, d] -> fp32 [B, S, d]
+        gpb, pb64 = operand(rnd(B, S, nq, seed=7).abs() / nq * bw_sc, S, nq, nqp, B)
+        gat, at64 = operand(rnd(B, d, nq, seed=8), d, nq, nqp, B)
+        for name in ("A2", "B2"):
+            o = guarded(S, d, d, F32, DEV, batch=B, stride=S * d)
+            ops.gemm(gpb.t, gat.t, out=o.t, M=S, N=d, K=nqp, lda=nqp, ldw=nqp, ldc=d, batch=B, strideA=S * nqp, strideW=d * nqp,
+                     strideC=S * d, alpha=1.0 / bw_sc, tile_cfg=tile)
+            want = torch.einsum("bmk,bnk->bmn", pb64, at64) / bw_sc
+            _check_engine_product(o, want, prec, f"{name} tile {tile} B {B}", f32=True)
+        for gi in (gw, gx, gv, gp, gpb, gat):
+            gi.assert_untouched(what=f"engine products tile {tile}: an input was written")
+        _count(fam, tile, ("ldc",), 5)
+
+
+def _check_engine_product(o, want, prec, what, f32=False):
+    torch.cuda.synchronize()
+    o.assert_untouched(what=what)
+    got = o.values()
+    assert bool(torch.isfinite(got).all()), what
+    if prec == "bf16":
+        assert_close(got, want, 2e-4 if f32 else 6e-3, what)
+    else:      # fp32 output: the mode's 1e-6; a split-fp16 output carries its own 2^-22 split on top
+        assert rel_err(got, want) <= (1e-6 if f32 else 1e-6 + 2.0 ** -22), (what, rel_err(got, want))
+
+
+def test_gemm_folded_layernorm_secondary_outputs_are_refused_or_contained(ops):
+    """The producer's out16 / stats_out secondary outputs exist in -DODIC_EXPERIMENTAL_GEMM builds only; the default build
+    refuses them before any launch (test_gemm_bf16_default_build_rejects_compiled_out_configurations), and nothing is written."""
+    _hip, lib = _lib()
+    M, N, K = 129, 96, 64
+    A, Wt = rnd(M, K, seed=1).bfloat16().to(DEV), rnd(N, K, seed=2, scale=0.05).bfloat16().to(DEV)
+    o, o16, st = guarded(M, N, N + 8, F32, DEV), guarded(M, N, N + 8, BF16, DEV), guarded(M, 2 * (N // 32), 2 * (N // 32), F32, DEV)
+    if b"experimental-gemm" not in lib.odic_build_info():
+        with pytest.raises(RuntimeError):
+            ops.gemm(A, Wt, out=o.t, M=M, N=N, K=K, lda=K, ldw=K, ldc=N + 8, out16=o16.t, stats_out=st.t)
+        torch.cuda.synchronize()
+        for gbuf in (o, o16, st):
+            gbuf.assert_all_poison("refused launch")
+        return
+    ops.gemm(A, Wt, out=o.t, M=M, N=N, K=K, lda=K, ldw=K, ldc=N + 8, out16=o16.t, stats_out=st.t, tile_cfg=0)
+    torch.cuda.synchronize()
+    for gbuf in (o, o16, st):
+        gbuf.assert_untouched(what="folded-LayerNorm producer")
+    assert_close(o.values()[0], A.double().cpu() @ Wt.double().cpu().T, 2e-4, "producer")
+
+
+def test_gemm_coverage_every_selectable_tile(ops):
+    """No silent skipping: every tile id of each default candidate list (and the built-in choice, -1) EXECUTED at least one
+    ragged-M, one ragged-N and one ldc > N case; the A-resident tiles, which take whole tiles only, executed ldc > N and had the
+    ragged shapes refused by the library.  Independent of test selection and order: a family whose sweep has not run in this
+    session is run here.  (The plan itself — shapes against the dispatch constraints — is checked without a GPU in
+    tests/test_guards.py.)"""
+    for fam in FAMILIES:
+        if ("tiled", fam) not in SWEPT:
+            test_gemm_stores_and_loads_every_tile(ops, fam)
+    for fam in ("bf16", "x3"):
+        if ("panel", fam) not in SWEPT:
+            test_gemm_a_resident_tiles_whole_tiles_only(ops, fam)
+    need = {"raggedM", "raggedN", "ldc"}
+    missing = []
+    for fam in FAMILIES:
+        for tile in _tiled_tiles(ops, fam):
+            got = COVER.get((fam, tile), set())
+            if not need <= got:
+                missing.append((fam, tile, sorted(need - got)))
+    for fam in ("bf16", "x3"):
+        for tile in panel_candidates(ops, fam):
+            got = COVER.get((fam, tile), set())
+            want = {"ldc", "refused:raggedM", "refused:raggedN"}
+            if not want <= got:
+                missing.append((fam, tile, sorted(want - got)))
+    print("GEMM containment cases per family:", NCASES)
+    assert not missing, missing
+
+
+def test_gemm_f32_folded_layernorm_reads_exactly_n_column_sums(ops):
+    """ln_colsum (the fp32 skinny-M fold): exactly N entries inside a poisoned buffer, A a strided slice with NaN around it,
+    guarded output — test_gemm_f32_folded_layernorm's reference and bound (3e-5)."""
+    for shape in (-1, 0, 1, 2):
+        M, N, K = 48, 200, 512
+        a32, Wt, b = rnd(M, K, seed=1, scale=2.0) + 0.3, rnd(N, K, seed=2, scale=0.1), rnd(N, seed=3)
+        g, be = 1 + 0.1 * rnd(K, seed=4), 0.1 * rnd(K, seed=5)
+        want = torch.nn.functional.layer_norm(a32.double(), (K,), g.double(), be.double(), 1e-5) @ Wt.double().T + b.double()
+        Wf, bf, cs = ops.fold_layernorm(Wt.to(DEV), b.to(DEV), g.to(DEV), be.to(DEV))
+        ref = ops.gemm(a32.to(DEV), Wf, bf, ln_fold=(cs, 1e-5), tile_cfg=shape)
+        gA, gW = poisoned_input(a32, M, K, K + 4, device=DEV), poisoned_input(Wf, N, K, K + 4)
+        gb, gc = poisoned_input(bf, 1, N, N), poisoned_input(cs, 1, N, N)
+        o = guarded(M, N, N + 1, F32, DEV)
+        ops.gemm(gA.t, gW.t, gb.t, out=o.t, M=M, N=N, K=K, lda=K + 4, ldw=K + 4, ldc=N + 1, ln_fold=(gc.t, 1e-5), tile_cfg=shape)
+        torch.cuda.synchronize()
+        o.assert_untouched(what=f"folded LN shape {shape}")
+        assert_close(o.t[:, :N], want, 3e-5, "folded LN gemm")
+        assert torch.equal(o.t[:, :N], ref)
+
+
+# ============================================================================================== c. row and step kernels
+LN_C = [96, 192, 512, 768, 1536, 3072, 6144]              # test_layernorm's list
+
+
+@pytest.mark.parametrize("odt,bound", [(F32, 2e-5), (BF16, 5e-3), (H2, None), (FP8, None)])
+def test_layernorm_reads_ldx_and_writes_compact_rows(ops, odt, bound):
+    """odic_layernorm: x with ldx > C (NaN pad columns, NaN rows behind M); the output has no leading dimension (compact
+    rows), so only the bands in front and behind apply."""
+    _hip, lib = _lib()
+    M = 37
+    for Cw in LN_C:
+        x, g, b = rnd(M, Cw, seed=1, scale=3.0) + 0.7, 1 + 0.1 * rnd(Cw, seed=2), 0.1 * rnd(Cw, seed=3)
+        want = torch.nn.functional.layer_norm(x.double(), (Cw,), g.double(), b.double(), 1e-5)
+        gx = poisoned_input(x, M, Cw, Cw + 4, device=DEV)
+        gg, gb = poisoned_input(g, 1, Cw, Cw, device=DEV), poisoned_input(b, 1, Cw, Cw, device=DEV)
+        o = guarded(M, Cw, Cw, odt, DEV)
+        _hip.check(lib.odic_layernorm(gx.data_ptr(), Cw + 4, gg.data_ptr(), gb.data_ptr(), o.data_ptr(), M, Cw, 1e-5,
+                                      ops.dtype_code(_torch_odt(ops, odt)), _stream()), "odic_layernorm")
+        ref = ops.layernorm(x.to(DEV), g.to(DEV), b.to(DEV), out_dtype=_torch_odt(ops, odt))
+        torch.cuda.synchronize()
+        what = f"layernorm C={Cw} -> {odt}"
+        o.assert_untouched(what=what)
+        gx.assert_untouched(what=what + " (input written)")
+        assert torch.equal(o.data_bytes()[0], ref.contiguous().view(torch.uint8).reshape(M, -1).cpu()), what
+        if bound is not None:
+            assert_close(o.values()[0], want, bound, what)               # test_layernorm
+        elif odt == H2:        # 22 significand bits of fp32-class values: the fp32 bound of test_layernorm; at the width of
+            assert_close(o.values()[0], want, 2e-5, what)                # test_layernorm_and_patch_merge_write_h2 also its
+            if Cw == 768:                                                 # bitwise check (the fp32 kernel's values, split)
+                r32 = ops.layernorm(x.to(DEV), g.to(DEV), b.to(DEV)).cpu()
+                assert torch.equal(o.data_bytes()[0], _h2_bytes_of(ops, r32, Cw)), what
+        else:                  # test_layernorm_fp8_output: per element, half an e4m3 ulp
+            _assert_values(o.values()[0], want, "fp8", FP8, 0, what)
+
+
+def test_casts_respect_ldx_and_ldo(ops):
+    """odic_cast_f32_to_bf16 (C, ldx, ldo multiples of 4) and odic_cast_f32_to_h2 (C, ldo multiples of 8)."""
+    _hip, lib = _lib()
+    M, Cw = 37, 96
+    x = rnd(M, Cw, seed=8, scale=3.0)
+    gx = poisoned_input(x, M, Cw, Cw + 4, device=DEV)
+    for ldo in (Cw + 4, Cw + 8, 128):
+        o = guarded(M, Cw, ldo, BF16, DEV)
+        _hip.check(lib.odic_cast_f32_to_bf16(gx.data_ptr(), Cw + 4, o.data_ptr(), ldo, M, Cw, _stream()), "cast")
+        torch.cuda.synchronize()
+        o.assert_untouched(what=f"cast_bf16 ldo={ldo}")
+        assert torch.equal(o.t[:, :Cw].cpu(), x.bfloat16())               # test_stcexp_normalize_and_mix: exact
+    for ldo in (Cw + 8, 128):
+        o = guarded(M, Cw, ldo, H2, DEV)
+        _hip.check(lib.odic_cast_f32_to_h2(gx.data_ptr(), Cw + 4, o.data_ptr(), ldo, M, Cw, _stream()), "cast")
+        torch.cuda.synchronize()
+        o.assert_untouched(what=f"cast_h2 ldo={ldo}")
+        assert torch.equal(o.data_bytes()[0], _h2_bytes_of(ops, x, Cw))   # test_h2_pack_roundtrip_and_device_cast: same bytes
+    gx.assert_untouched(what="cast input")
+
+
+@pytest.mark.parametrize("layout", ["five-lds", "xcat"])
+def test_selector_mix_leading_dimensions(ops, layout):
+    M, dm = 50, 128
+    x, s, a, b = (rnd(M, dm, seed=i) for i in range(4))
+    sg = torch.sigmoid(s.double())
+    want = x.double() + sg * a.double() + (1 - sg) * b.double()
+    ref = torch.empty(M, dm, device=DEV)
+    ops.selector_mix(x.to(DEV), dm, s.to(DEV), dm, a.to(DEV), dm, b.to(DEV), dm, ref, dm, M, dm)
+    if layout == "five-lds":
+        lds = (dm + 1, dm + 4, dm + 7, dm + 64, dm + 3)
+        gs = [poisoned_input(t, M, dm, ld, device=DEV) for t, ld in zip((x, s, a, b), lds)]
+        o = guarded(M, dm, lds[4], F32, DEV)
+        ops.selector_mix(gs[0].t, lds[0], gs[1].t, lds[1], gs[2].t, lds[2], gs[3].t, lds[3], o.t, lds[4], M, dm)
+        torch.cuda.synchronize()
+        o.assert_untouched(what="selector_mix")
+        got = o.t[:, :dm]
+    else:      # the engine's layout: x = xcat[:, (i-1)d:], out = xcat[:, i·d:], ld = L·d — the other layers' columns stay put
+        L = 3
+        xc = guarded(M, L * dm, L * dm, F32, DEV)
+        xc.t[:, :dm].copy_(x.to(DEV))
+        gs = [poisoned_input(t, M, dm, dm, device=DEV) for t in (s, a, b)]
+        ops.selector_mix(xc.t, L * dm, gs[0].t, dm, gs[1].t, dm, gs[2].t, dm, xc.t[:, dm:], L * dm, M, dm)
+        torch.cuda.synchronize()
+        xc.assert_untouched(written_cols=2 * dm, what="selector_mix in xcat")
+        assert torch.equal(xc.t[:, :dm].cpu(), x), "the input columns of xcat changed"
+        got = xc.t[:, dm:2 * dm]
+    for gi in gs:
+        gi.assert_untouched(what="selector_mix input")
+    assert_close(got, want, 2e-5, "selector_mix")                         # test_stcexp_normalize_and_mix
+    assert torch.equal(got, ref)
+
+
+@pytest.mark.parametrize("beams,S,d,heads", [(3, 143, 512, 8), (5, 37, 128, 4), (1, 144, 512, 8)])
+def test_cross_attn_step_leading_dimensions(ops, beams, S, d, heads):
+    """ldq, ldkv, ldo above the widths, S not a multiple of anything, ragged enc_len, row_valid = 0 rows (header: a uniform
+    average over all S positions — their output rows ARE written)."""
+    n_img = 3
+    N = n_img * beams
+    q, kv = rnd(N, d, seed=1), rnd(n_img, S, 3 * d, seed=2)
+    koff, voff = d, 2 * d
+    lens = torch.tensor([S, max(1, S // 2 + 1), max(1, S - 4)], dtype=torch.int32)
+    valid = torch.ones(N, dtype=torch.int32)
+    valid[min(3, N - 1)] = 0
+    ref = torch.empty(N, d, device=DEV)
+    ops.cross_attn_step(q.to(DEV), d, kv.to(DEV), 3 * d, koff, voff, lens.to(DEV), valid.to(DEV), ref, d, N, n_img, S, d, heads)
+    ldq, ldkv, ldo = d + 4, 3 * d + 4, d + 1      # (ldq, ldkv, koff: multiples of 4 — validated before the launch, see below)
+    gq = poisoned_input(q, N, d, ldq, device=DEV)
+    gkv = poisoned_input(kv, S, 3 * d, ldkv, batch=n_img, stride=S * ldkv, device=DEV)
+    gl, gv = poisoned_input(lens, 1, n_img, n_img, device=DEV), poisoned_input(valid, 1, N, N, device=DEV)
+    o = guarded(N, d, ldo, F32, DEV)
+    ops.cross_attn_step(gq.t, ldq, gkv.t, ldkv, koff, voff, gl.t, gv.t, o.t, ldo, N, n_img, S, d, heads)
+    torch.cuda.synchronize()
+    o.assert_untouched(what="cross_attn_step")
+    for gi in (gq, gkv, gl, gv):
+        gi.assert_untouched(what="cross_attn_step input")
+    dk = d // heads
+    want = torch.empty(N, d, dtype=torch.float64)
+    for n in range(N):
+        i = n // beams
+        Kk = kv[i, :, koff:koff + d].double().view(S, heads, dk)
+        Vv = kv[i, :, voff:voff + d].double().view(S, heads, dk)
+        sc = torch.einsum("hc,shc->hs", q[n].double().view(heads, dk), Kk) / math.sqrt(dk)
+        allow = (torch.arange(S) < lens[i]) & bool(valid[n])
+        want[n] = torch.einsum("hs,shc->hc", torch.softmax(sc.masked_fill(~allow[None, :], -1e4), -1), Vv).reshape(d)
+    assert_close(o.t[:, :d], want, 2e-5, "cross_attn_step")               # test_cross_attn_step
+    assert torch.equal(o.t[:, :d], ref)
+    o2 = guarded(N, d, ldo, F32, DEV)
+    with pytest.raises(RuntimeError):             # an odd ldq is refused, and nothing is written
+        ops.cross_attn_step(gq.t, d + 3, gkv.t, ldkv, koff, voff, gl.t, gv.t, o2.t, ldo, N, n_img, S, d, heads)
+    torch.cuda.synchronize()
+    o2.assert_all_poison("refused cross_attn_step")
+
+
+@pytest.mark.parametrize("V", [37, 513, 10000])
+def test_logsoftmax_topk_leading_dimensions(ops, V):
+    N, k = 7, 5
+    x = rnd(N, V, seed=1, scale=3.0)
+    want = torch.log_softmax(x.double(), -1)
+    wv, wi = torch.topk(want, k, -1)
+    ldl, ldp = V + 3, V + 1
+    gx = poisoned_input(x, N, V, ldl, device=DEV)
+    lp, tv, ti = guarded(N, V, ldp, F32, DEV), guarded(N, k, k, F32, DEV), guarded(N, k, k, torch.int32, DEV)
+    ops.logsoftmax_topk(gx.t, ldl, lp.t, ldp, tv.t, ti.t, N, V, k)
+    torch.cuda.synchronize()
+    for gi, nm in ((lp, "logp_out"), (tv, "top_val"), (ti, "top_idx"), (gx, "logits (input)")):
+        gi.assert_untouched(what=f"logsoftmax_topk V={V} {nm}")
+    assert_close(lp.t[:, :V], want, 2e-6, "log_softmax")                  # test_logsoftmax_topk
+    assert torch.equal(ti.t.cpu().long(), wi)
+    assert_close(tv.t, wv, 2e-6, "topk values")
+    rl, rv, ri = torch.empty(N, V, device=DEV), torch.empty(N, k, device=DEV), torch.empty(N, k, dtype=torch.int32, device=DEV)
+    ops.logsoftmax_topk(x.to(DEV), V, rl, V, rv, ri, N, V, k)
+    assert torch.equal(lp.t[:, :V], rl) and torch.equal(tv.t, rv) and torch.equal(ti.t, ri)
+
+
+def test_dec_embed_ldy(ops):
+    N, d, V, T = 6, 64, 50, 9
+    embed, table = rnd(V, d, seed=1), rnd(T, d, seed=2)
+    tok = torch.tensor([3, 49, 0, 7, 7, 21], dtype=torch.int64)
+    pos = torch.tensor([4], dtype=torch.int32)
+    ge, gt = poisoned_input(embed, V, d, d, device=DEV), poisoned_input(table, T, d, d, device=DEV)
+    gk = poisoned_input(tok, 1, N, N, device=DEV)
+    y = guarded(N, d, d + 5, F32, DEV)
+    ops.dec_embed(gk.t, ge.t, gt.t, pos.to(DEV), y.t, d + 5, N, d, 8.0)
+    torch.cuda.synchronize()
+    y.assert_untouched(what="dec_embed")
+    want = embed[tok].double() * 8.0 + table[4].double()
+    assert_close(y.t[:, :d], want, 2e-5, "dec_embed")                     # the fp32 kernels' bound (test_hip_ops' docstring)
+    yc = torch.empty(N, d, device=DEV)
+    ops.dec_embed(tok.to(DEV), embed.to(DEV), table.to(DEV), torch.tensor([4], dtype=torch.int32, device=DEV), yc, d, N, d, 8.0)
+    assert torch.equal(y.t[:, :d], yc), "dec_embed: ldy changed the result"
+    pos.fill_(T)                                                          # header: *pos outside [0, pos_rows) writes nothing
+    y2 = guarded(N, d, d + 5, F32, DEV)
+    ops.dec_embed(gk.t, ge.t, gt.t, pos.to(DEV), y2.t, d + 5, N, d, 8.0)
+    torch.cuda.synchronize()
+    y2.assert_all_poison("dec_embed with *pos out of range")
+
+
+@pytest.mark.parametrize("nbytes", [16, 48, 4096 + 16, 16 * 65537])
+def test_copy_exact_extent(ops, nbytes):
+    """odic_copy's contract: multiples of 16 bytes, 16-byte aligned pointers."""
+    src = torch.randint(0, 255, (nbytes,), dtype=torch.uint8, generator=torch.Generator().manual_seed(nbytes))
+    gs = poisoned_input(src, 1, nbytes, nbytes, device=DEV)
+    o = guarded(1, nbytes, nbytes, torch.uint8, DEV)
+    ops.copy(gs.t.view(-1), o.t.view(-1))
+    torch.cuda.synchronize()
+    o.assert_untouched(what=f"copy {nbytes}")
+    gs.assert_untouched(what="copy source")
+    assert torch.equal(o.t.view(-1).cpu(), src)
+
+
+def _compact_out(ops, M, Cw, odt):
+    return guarded(M, Cw, Cw, odt, DEV)
+
+
+@pytest.mark.parametrize("odt", [F32, BF16, H2])
+def test_patch_merge_layernorm_compact_output(ops, odt):
+    """odic_patch_merge_layernorm has no leading dimensions: bands in front and behind input and output."""
+    from oracle import expansionnet_ref as R
+    _hip, lib = _lib()
+    B, res, Cw = 3, 24, 96
+    x = rnd(B, res * res, Cw, seed=5)
+    g, b = 1 + 0.1 * rnd(4 * Cw, seed=2), 0.1 * rnd(4 * Cw, seed=3)
+    sd = {"m.norm.weight": g, "m.norm.bias": b, "m.reduction.weight": torch.eye(4 * Cw)}
+    want = R.patch_merging(sd, "m", x, res).reshape(-1, 4 * Cw)         # test_patch_merge_layernorm's reference
+    gx = poisoned_input(x.reshape(-1, Cw), B * res * res, Cw, Cw, device=DEV)
+    gg, gb = poisoned_input(g, 1, 4 * Cw, 4 * Cw, device=DEV), poisoned_input(b, 1, 4 * Cw, 4 * Cw, device=DEV)
+    rows = B * (res // 2) ** 2
+    o = _compact_out(ops, rows, 4 * Cw, odt)
+    tdt = _torch_odt(ops, odt)
+    _hip.check(lib.odic_patch_merge_layernorm(gx.data_ptr(), gg.data_ptr(), gb.data_ptr(), o.data_ptr(), B, res, Cw, 1e-5,
+                                              ops.dtype_code(tdt), _stream()), "odic_patch_merge_layernorm")
+    ref = ops.patch_merge_layernorm(x.to(DEV), g.to(DEV), b.to(DEV), B, res, Cw, out_dtype=tdt)
+    torch.cuda.synchronize()
+    o.assert_untouched(what=f"patch_merge_layernorm -> {odt}")
+    gx.assert_untouched(what="patch_merge input")
+    assert torch.equal(o.data_bytes()[0], ref.reshape(rows, -1).contiguous().view(torch.uint8).reshape(rows, -1).cpu())
+    # fp32: test_patch_merge_layernorm (2e-5); bf16: test_layernorm's bf16 bound (5e-3, the same LayerNorm rounding);
+    # split fp16: 22 bits of the fp32 values (test_layernorm_and_patch_merge_write_h2 asserts the exact split of them)
+    assert_close(o.values()[0], want, 5e-3 if odt == BF16 else 2e-5, f"patch_merge_ln {odt}")
+    if odt == H2:
+        r32 = ops.patch_merge_layernorm(x.to(DEV), g.to(DEV), b.to(DEV), B, res, Cw).reshape(rows, -1).cpu()
+        assert torch.equal(o.data_bytes()[0], _h2_bytes_of(ops, r32, 4 * Cw))
+
+
+def test_patch_embed_compact_output(ops):
+    from oracle import expansionnet_ref as R
+    _hip, lib = _lib()
+    g = W.TINY
+    sd = {k: W.synth_tensor(k, s_, kind, g) for k, s_, kind in W.state_dict_spec(g) if "patch_embed" in k}
+    Bn = 3
+    img = W.synth_images(Bn, g)
+    want = R.patch_embed(sd, g, img)                                      # test_patch_embed's reference
+    P = "swin_transf.patch_embed"
+    Cw = g.swin_embed_dim
+    w2 = sd[P + ".proj.weight"].reshape(Cw, -1).contiguous()
+    ins = [poisoned_input(t.reshape(1, -1), 1, t.numel(), t.numel(), device=DEV)
+           for t in (img, w2, sd[P + ".proj.bias"], sd[P + ".norm.weight"], sd[P + ".norm.bias"])]
+    H = img.shape[-1]
+    rows = Bn * (H // 4) ** 2
+    o = guarded(rows, Cw, Cw, F32, DEV)
+    _hip.check(lib.odic_patch_embed(*[t.data_ptr() for t in ins], o.data_ptr(), Bn, img.shape[1], H, H, 4, Cw, 1e-5, _stream()),
+               "odic_patch_embed")
+    ref = ops.patch_embed(img.to(DEV), w2.to(DEV), sd[P + ".proj.bias"].to(DEV), sd[P + ".norm.weight"].to(DEV),
+                          sd[P + ".norm.bias"].to(DEV), 4)
+    torch.cuda.synchronize()
+    o.assert_untouched(what="patch_embed")
+    for gi in ins:
+        gi.assert_untouched(what="patch_embed input")
+    assert_close(o.t.view(Bn, -1, Cw), want, 2e-5, "patch_embed")
+    assert torch.equal(o.t.view(Bn, -1, Cw), ref)
+
+
+def test_dynexp_step_leading_dimensions_and_caches(ops):
+    """test_dynexp_step_matches_full_recompute with ldlin, ldy_in, ldy above the widths, every cache in a guarded buffer that
+    starts as poison (a read of a cache entry no earlier step wrote would surface as NaN), against the oracle's full-prefix
+    block (5e-5) and bit for bit against the compact call."""
+    from oracle import expansionnet_ref as R
+    N, T, d, E = 3, 9, 128, 4
+    names = ["cond_embed", "key_linear", "class_a_embed", "class_b_embed", "selector_embed"]
+    sd = {}
+    for i, nm in enumerate(names):
+        sd[f"p.{nm}.weight"] = rnd(d, d, seed=10 + i, scale=d ** -0.5)
+        sd[f"p.{nm}.bias"] = rnd(d, seed=20 + i, scale=0.1)
+    sd["p.query_exp_vectors.weight"] = rnd(E, d, seed=30, scale=0.3)
+    sd["p.bias_exp_vectors.weight"] = rnd(E, d, seed=31, scale=0.3)
+    x = rnd(N, T, d, seed=40)
+    pads = [0, 2, 4]
+    t = torch.arange(T)
+    ok = t[None, :] < (T - torch.tensor(pads))[:, None]
+    causal = ((t[None, :, None] >= t[None, None, :]) & ok[:, :, None] & ok[:, None, :]).float()
+    want = R.dynamic_expansion(sd, "p", x, E, causal)
+    Wcat = torch.cat([sd[f"p.{nm}.weight"] for nm in names], 0).to(DEV)
+    bcat = torch.cat([sd[f"p.{nm}.bias"] for nm in names], 0).to(DEV)
+    qe, be = sd["p.query_exp_vectors.weight"], sd["p.bias_exp_vectors.weight"]
+    plain = [torch.zeros(T, N, d, device=DEV) for _ in range(4)] + [torch.zeros(T, N, T, E, device=DEV) for _ in range(2)]
+    qk = torch.zeros(T, N, E, device=DEV)
+    gc = [guarded(T * N, d, d, F32, DEV) for _ in range(4)] + [guarded(T * N, T * E, T * E, F32, DEV) for _ in range(2)]
+    gqk = guarded(T * N, E, E, F32, DEV)
+    gqe, gbe = poisoned_input(qe, E, d, d, device=DEV), poisoned_input(be, E, d, d, device=DEV)
+    anc = torch.arange(N, dtype=torch.int32)[:, None].repeat(1, T).contiguous()
+    ganc = poisoned_input(anc, N, T, T, device=DEV)
+    pos = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ldlin, ldy = 5 * d + 4, d + 4
+    got = torch.empty(N, T, d)
+    for step in range(T):
+        pos.fill_(step)
+        lin = ops.gemm(x[:, step].contiguous().to(DEV), Wcat, bcat)
+        valid = ok[:, step].to(torch.int32)
+        y = torch.zeros(N, d, device=DEV)
+        ops.dynexp_step(lin, 5 * d, qe.to(DEV), be.to(DEV), *plain, qk, anc.to(DEV), valid.to(DEV), pos, y, d, y, d, N, T, d, E)
+        glin = poisoned_input(lin, N, 5 * d, ldlin)
+        gyin = poisoned_input(torch.zeros(N, d), N, d, ldy, device=DEV)
+        gy = guarded(N, d, ldy, F32, DEV)
+        gv = poisoned_input(valid, 1, N, N, device=DEV)
+        ops.dynexp_step(glin.t, ldlin, gqe.t, gbe.t, *[c.t for c in gc], gqk.t, ganc.t, gv.t, pos, gyin.t, ldy, gy.t, ldy,
+                        N, T, d, E)
+        torch.cuda.synchronize()
+        gy.assert_untouched(what=f"dynexp_step y, step {step}")
+        for c in gc + [gqk, glin, gyin, ganc]:
+            c.assert_untouched(what=f"dynexp_step step {step}")
+        assert torch.equal(gy.t[:, :d], y), f"dynexp_step step {step}: layout changed the result"
+        got[:, step] = gy.t[:, :d].cpu()
+    assert bool(torch.isfinite(got).all())
+    assert_close(got, want, 5e-5, "dynexp_step")
+
+
+@pytest.mark.parametrize("V", [37, 513, 10000])
+def test_logsoftmax_sample_leading_dimensions(ops, V):
+    N, k = 7, 3
+    x = rnd(N, V, seed=2, scale=2.0)
+    want = torch.log_softmax(x.double(), -1)
+    pos = torch.full((1,), 2, dtype=torch.int32, device=DEV)
+    rl, rv, ri = torch.empty(N, V, device=DEV), torch.empty(N, k, device=DEV), torch.empty(N, k, dtype=torch.int32, device=DEV)
+    ops.logsoftmax_sample(x.to(DEV), V, rl, V, rv, ri, N, V, k, 77, pos)
+    ldl, ldp = V + 3, V + 1
+    gx = poisoned_input(x, N, V, ldl, device=DEV)
+    lp, tv, ti = guarded(N, V, ldp, F32, DEV), guarded(N, k, k, F32, DEV), guarded(N, k, k, torch.int32, DEV)
+    ops.logsoftmax_sample(gx.t, ldl, lp.t, ldp, tv.t, ti.t, N, V, k, 77, pos)
+    torch.cuda.synchronize()
+    for gi, nm in ((lp, "logp_out"), (tv, "top_val"), (ti, "top_idx"), (gx, "logits (input)")):
+        gi.assert_untouched(what=f"logsoftmax_sample V={V} {nm}")
+    assert torch.equal(lp.t[:, :V], rl) and torch.equal(tv.t, rv) and torch.equal(ti.t, ri)
+    assert_close(lp.t[:, :V], want, 2e-6, "logp_out")                     # test_logsoftmax_sample_draws_follow_the_distribution
+    I = ti.t.cpu().long()
+    assert bool((I >= 0).all()) and bool((I < V).all())
+    assert_close(tv.t, torch.gather(want, 1, I).float(), 2e-6, "log-probs of the drawn words")
+    assert all(len(set(r.tolist())) == k for r in I)
+
+
+@pytest.mark.parametrize("V", [37, 513, 10000])
+def test_ensemble_logprobs_and_topk_rows_leading_dimensions(ops, V):
+    N, Mm, k = 7, 3, 5
+    logits = [rnd(N, V, seed=10 + m, scale=3.0) for m in range(Mm)]
+    want = torch.stack([torch.softmax(l.double(), -1) for l in logits]).mean(0).log()
+    ref = torch.empty(N, V, device=DEV)
+    ops.ensemble_logprobs([l.to(DEV) for l in logits], ref)
+    gl = [poisoned_input(l, N, V, V + 3, device=DEV) for l in logits]
+    o = guarded(N, V, V + 1, F32, DEV)
+    ops.ensemble_logprobs([g_.t[:, :V] for g_ in gl], o.t[:, :V])       # (the wrapper passes the views' row strides as ldl / ldo)
+    torch.cuda.synchronize()
+    o.assert_untouched(what=f"ensemble_logprobs V={V}")
+    for g_ in gl:
+        g_.assert_untouched(what="ensemble logits (input)")
+    assert_close(o.t[:, :V], want, 2e-6, "ensemble_logprobs")             # test_ensemble_logprobs_and_topk_rows
+    assert torch.equal(o.t[:, :V], ref)
+    tv, ti = guarded(N, k, k, F32, DEV), guarded(N, k, k, torch.int32, DEV)
+    ops.topk_rows(o.t[:, :V], tv.t, ti.t, k)                               # rows with ldl = V + 1, NaN behind every row
+    rv, ri = torch.empty(N, k, device=DEV), torch.empty(N, k, dtype=torch.int32, device=DEV)
+    ops.topk_rows(ref, rv, ri, k)
+    torch.cuda.synchronize()
+    tv.assert_untouched(what="topk_rows top_val"); ti.assert_untouched(what="topk_rows top_idx")
+    o.assert_untouched(what="topk_rows input")
+    ref_v, ref_i = torch.topk(ref.cpu(), k, dim=-1)
+    assert torch.equal(tv.t.cpu(), ref_v) and torch.equal(ti.t.cpu().long(), ref_i)
+    assert torch.equal(tv.t, rv) and torch.equal(ti.t, ri)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("dt", [F32, BF16, F16, H2], ids=str)
+@pytest.mark.parametrize("res,heads,shift", [(24, 12, 6), (12, 48, 0)])
+def test_window_attention_front_and_back_guards(ops, dt, B, res, heads, shift):
+    """odic_window_attention takes no leading dimensions; its loads and stores are index maps (roll, partition, reverse) over
+    the whole [B·res², ...] tensors — a wrong map at the first / last window lands in the bands.  B = 1 and an odd B."""
+    from test_hip_ops import _win_ref
+    ws = 12
+    Cw = heads * 32
+    rows = B * res * res
+    q32 = rnd(rows, 3 * Cw, seed=res + shift, scale=1.5)
+    table = rnd(529, heads, seed=9, scale=0.5)
+    dense = ops.shifted_bias_prescaled(table.to(DEV), ws, 32 ** -0.5)
+    if dt == H2:
+        qkv, q64 = ops.h2_from_f32(q32).to(DEV), q32
+    else:
+        qkv = q32.to(dt).to(DEV)
+        q64 = q32.to(dt).float()
+    want = _win_ref(q64, table, B, res, Cw, heads, ws, shift)
+    gq = poisoned_input(qkv, rows, 3 * Cw, 3 * Cw, dtype=dt)
+    gt = poisoned_input(table, 529, heads, heads, device=DEV)
+    tdt = _torch_odt(ops, dt)
+    # bounds: test_window_attention (fp32 2e-5, bf16 1.2e-2, both bf16 kernels), test_window_attention_fp16 (2.5e-3),
+    # test_window_attention_x3 (4e-6)
+    variants = [(None, {F32: 2e-5, BF16: 1.2e-2}.get(dt))] if dt in (F32, BF16) else []
+    if dt != F32:
+        variants.append((dense, {BF16: 1.2e-2, F16: 2.5e-3, H2: 4e-6}[dt]))
+    for bsp, bound in variants:
+        o = guarded(rows, Cw, Cw, dt, DEV)
+        ops.window_attention(gq.t.view(tdt) if dt == H2 else gq.t, gt.t, B, res, Cw, heads, ws, shift,
+                             out=o.t.view(tdt) if dt == H2 else o.t, bias_shifted_prescaled=bsp)
+        ref = ops.window_attention(qkv, table.to(DEV), B, res, Cw, heads, ws, shift, bias_shifted_prescaled=bsp)
+        torch.cuda.synchronize()
+        what = f"window_attention {dt} B={B} res={res} shift={shift} fast={bsp is not None}"
+        o.assert_untouched(what=what)
+        gq.assert_untouched(what=what + " (qkv written)")
+        assert torch.equal(o.data_bytes()[0], ref.contiguous().view(torch.uint8).reshape(rows, -1).cpu()), what
+        if dt == H2:
+            assert rel_err(o.values()[0], want) <= bound, what
+        else:
+            assert_close(o.values()[0], want, bound, what)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("shift", [0, 6])
+def test_swin_qkv_attention_ldx_and_guards(ops, B, shift):
+    """odic_swin_qkv_attention with ldx > C (NaN pad columns and NaN rows around x), guarded bf16 output: bit for bit the compact
+    call, and bit for bit the two launches it replaces (test_swin_qkv_attention_fused's reference)."""
+    _hip, lib = _lib()
+    res, Cw, heads, ws = 48, 192, 6, 12            # (B·res² whole 128-row panels: the two-launch reference needs them)
+    rows = B * res * res
+    gen = torch.Generator().manual_seed(11 + shift)
+    x = torch.randn(rows, Cw, generator=gen) * 1.5 + torch.randn(rows, 1, generator=gen) * 3.0
+    Wq, bq = torch.randn(3 * Cw, Cw, generator=gen) * 0.06, torch.randn(3 * Cw, generator=gen) * 0.2
+    gamma, beta = 1.0 + 0.2 * torch.randn(Cw, generator=gen), 0.1 * torch.randn(Cw, generator=gen)
+    table = torch.randn((2 * ws - 1) ** 2, heads, generator=gen) * 0.3
+    Wf, bf, _ = ops.fold_layernorm_bf16(Wq.to(DEV), bq.to(DEV), gamma.to(DEV), beta.to(DEV))
+    dense = ops.shifted_bias_prescaled(table.to(DEV), ws, 32 ** -0.5)
+    ref = ops.swin_qkv_attention(x.to(DEV), Wf, bf, dense, B, res, Cw, heads, ws, shift)
+    qkv = ops.gemm(None, Wf, bf, a_ln=x.to(DEV), out_dtype=BF16)
+    two = ops.window_attention(qkv, table.to(DEV), B, res, Cw, heads, ws, shift, bias_shifted_prescaled=dense)
+    ldx = Cw + 4
+    gx = poisoned_input(x, rows, Cw, ldx, device=DEV)
+    gw, gb = poisoned_input(Wf, 3 * Cw, Cw, Cw), poisoned_input(bf, 1, 3 * Cw, 3 * Cw)
+    o = guarded(rows, Cw, Cw, BF16, DEV)
+    _hip.check(lib.odic_swin_qkv_attention(gx.data_ptr(), ldx, gw.data_ptr(), gb.data_ptr(), dense.data_ptr(), o.data_ptr(), B, res,
+                                           Cw, heads, ws, shift, (Cw // heads) ** -0.5, 1e-5, _stream()), "odic_swin_qkv_attention")
+    torch.cuda.synchronize()
+    o.assert_untouched(what=f"swin_qkv_attention B={B} shift={shift}")
+    for gi in (gx, gw, gb):
+        gi.assert_untouched(what="swin_qkv_attention input")
+    assert bool(torch.isfinite(o.t.float()).all())
+    assert torch.equal(o.t, ref), "ldx changed the result"
+    assert torch.equal(o.t, two), float((o.t.float() - two.float()).abs().max())
+
+
+# ============================================================================================== d. stcexp_normalize
+@pytest.mark.parametrize("odt", [BF16, H2])
+@pytest.mark.parametrize("S", [1, 20, 144, 64])
+def test_stcexp_normalize_zero_fills_its_padding(ops, odt, S):
+    """The opposite contract: the four outputs are written OUT TO their leading dimension with zeros in the padding (the engine
+    allocates them with torch.empty), and nothing beyond.  S = 64 with bf16 (pad 64) / S = 64 with split fp16 (pad 32): no
+    padding at all on the forward tables."""
+    B, groups = 3, (8, 16, 24)
+    nq = sum(groups)
+    pad = 64 if odt == BF16 else 32
+    Sp, nqp = -(-S // pad) * pad, -(-nq // pad) * pad
+    sfw, sbw = (1.0, 1.0) if odt == BF16 else (256.0, 4096.0)
+    z = rnd(B, nq, S, seed=3)
+    lens = torch.tensor([S, max(1, (2 * S) // 3), max(1, S - 3)], dtype=torch.int32)
+    valid = (torch.arange(S)[None, :] < lens[:, None]).double()[:, None, :]
+    zd = z.double()
+    pf, nf = torch.relu(zd) * valid, torch.relu(-zd) * valid
+    pf, nf = pf / (pf.sum(-1, keepdim=True) + 1e-9), nf / (nf.sum(-1, keepdim=True) + 1e-9)
+    meta = ops.stcexp_group_meta(groups, DEV)
+    gz = poisoned_input(z, nq, S, S, batch=B, device=DEV)
+    glen = poisoned_input(lens, 1, B, B, device=DEV)
+    ws = guarded(1, B * len(groups) * 2 * S, B * len(groups) * 2 * S, F32, DEV)
+    tdt = _torch_odt(ops, odt)
+    # outputs as the engine lays them out: [B, nq, Sp] / [B, S, nqp], all columns out to ld written
+    outs = [guarded(nq, Sp, Sp, odt, DEV, batch=B, stride=nq * Sp) for _ in range(2)] + \
+           [guarded(S, nqp, nqp, odt, DEV, batch=B, stride=S * nqp) for _ in range(2)]
+    ops.stcexp_normalize(gz.t, glen.t, meta, len(groups), *[o.t.view(tdt) for o in outs], ws.t.view(-1), scale_fw=sfw, scale_bw=sbw)
+    # fp32 reference run of the same kernel on plain buffers (test_stcexp_normalize_h2_outputs_with_scales compares with it)
+    o32 = [torch.empty(B, nq, S, device=DEV) for _ in range(2)] + [torch.empty(B, S, nq, device=DEV) for _ in range(2)]
+    ops.stcexp_normalize(z.to(DEV), lens.to(DEV), meta, len(groups), *o32, torch.empty(B * len(groups) * 2 * S, device=DEV))
+    torch.cuda.synchronize()
+    for i, (o, n, sc) in enumerate(zip(outs, (S, S, nq, nq), (sfw, sfw, sbw, sbw))):
+        what = f"stcexp {odt} S={S} output {i}"
+        o.assert_untouched(what=what)                      # bands (and, with batch > 1 and stride = rows·ld, nothing else)
+        full = o.values(cols=o.ld)                         # every column out to ld
+        assert bool(torch.isfinite(full).all()), f"{what}: poison left inside [0, ld) — the padding was not written"
+        by = o._rows_u8()
+        padmask = ~guards.owned_bytes(n, o.ld, odt)
+        assert not by[:, :, padmask].any(), f"{what}: padding columns [{n}, {o.ld}) are not bitwise zero"
+        got = full[..., :n] / sc
+        if odt == BF16:
+            assert_close(got, o32[i].double().cpu(), 5e-3, what)          # test_stcexp_normalize_and_mix (bf16 outputs)
+        else:
+            assert rel_err(got, o32[i]) <= 3e-7, what                     # test_stcexp_normalize_h2_outputs_with_scales
+    assert_close(o32[0], pf, 2e-5, "pos_fw"); assert_close(o32[1], nf, 2e-5, "neg_fw")
+    # the backward tables of test_stcexp_normalize_and_mix: relu(+-z^T), every column group L1-normalised, divided by ngroups.
+    # The kernel masks nothing there: rows s >= enc_len[b] hold the same formula (the consumer's forward weights are zero at
+    # those keys), which is what the header's formula says and what this reference restates.
+    zt = zd.transpose(1, 2)
+    pb, nb = torch.relu(zt).clone(), torch.relu(-zt).clone()
+    lo_ = 0
+    for n_ in groups:
+        pb[..., lo_:lo_ + n_] = pb[..., lo_:lo_ + n_] / (pb[..., lo_:lo_ + n_].sum(-1, keepdim=True) + 1e-9)
+        nb[..., lo_:lo_ + n_] = nb[..., lo_:lo_ + n_] / (nb[..., lo_:lo_ + n_].sum(-1, keepdim=True) + 1e-9)
+        lo_ += n_
+    assert_close(o32[2], pb / len(groups), 2e-5, "pos_bw"); assert_close(o32[3], nb / len(groups), 2e-5, "neg_bw")
+    # rows of images with enc_len < S: the forward tables hold exact zeros at the masked keys (pos = relu(z)·valid)
+    fw = outs[0].values(cols=S)
+    for b in range(B):
+        assert float(fw[b, :, int(lens[b]):].abs().max() if int(lens[b]) < S else 0.0) == 0.0
+    gz.assert_untouched(what="stcexp z (input)")
+    ws.assert_untouched(what="stcexp colsum workspace")
+
+
+# ============================================================================================== e. engine: previous call
+def _engine(prec, geom):
+    from on_device_image_captioning_amd import engine as E
+    g = getattr(W, geom)
+    sd = cached_state_dict(geom, "xavier", end_to_end=False, img_feature_dim=g.final_swin_dim)
+    return E.CaptionerEngine(sd, g, torch.device("cuda:0"), prec), g
+
+
+def _batch(g, B, seed, lens):
+    x = rnd(B, 144, g.final_swin_dim, seed=seed).to("cuda:0")
+    return x, torch.tensor(lens, dtype=torch.int32, device="cuda:0")
+
+
+def _pad_cols_zero(eng, g, prec):
+    nq, pad = sum(g.num_exp_enc_list), (64 if prec == "bf16" else 32)
+    for (B, S, _), bufs in eng._pad_ws.items():
+        for t, n in zip(bufs, (nq, nq, S)):
+            dt = BF16 if prec == "bf16" else H2
+            by = t.contiguous().view(torch.uint8).reshape(-1, t.shape[-1] * t.element_size()).cpu().numpy()
+            m = ~guards.owned_bytes(n, t.shape[-1], dt)
+            assert not by[:, m].any(), f"_pad_ws[{B},{S}] padding columns [{n}, {t.shape[-1]}) are not bitwise zero"
+
+
+@pytest.mark.parametrize("geom", ["TINY", "FULL"])
+@pytest.mark.parametrize("prec", ["bf16", "x3"])
+def test_encode_is_independent_of_the_previous_call(prec, geom):
+    """CaptionerEngine.encode keeps ONE set of buffers across calls: the three K-padded GEMM outputs AT, BT, vabT in
+    `_pad_ws` (per (B, S, stream); zeroed once).  Everything else encode uses is allocated per call."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    eng, g = _engine(prec, geom)
+    X, lx = _batch(g, 3, 11, [144, 100, 131])
+    Y, ly = _batch(g, 3, 12, [144, 144, 140])          # longer, different
+    fresh = eng.encode(X, lx).clone()
+    assert bool(torch.isfinite(fresh).all())
+    _pad_cols_zero(eng, g, prec)
+    eng.encode(Y, ly)
+    _pad_cols_zero(eng, g, prec)
+    after_y = eng.encode(X, lx).clone()
+    assert torch.equal(after_y, fresh), "encode(X) depends on the batch encoded before it"
+    # poison the DATA columns of every cached buffer between two calls: fully rewritten before they are read
+    nq = sum(g.num_exp_enc_list)
+    for (B, S, _), bufs in eng._pad_ws.items():
+        for t, n in zip(bufs, (nq, nq, S)):
+            t.view(torch.int16 if prec == "bf16" else torch.int32)[..., :n] = -1
+    poisoned = eng.encode(X, lx).clone()
+    assert torch.equal(poisoned, fresh), "encode reads a cached buffer's data columns before rewriting them"
+    _pad_cols_zero(eng, g, prec)
+    # a fresh engine, fresh buffers
+    eng2, _ = _engine(prec, geom)
+    assert torch.equal(eng2.encode(X, lx), fresh)
+
+
+@pytest.mark.parametrize("beam", [3, 5])
+@pytest.mark.parametrize("prec", ["bf16", "x3"])
+def test_pipeline_search_is_independent_of_the_previous_search(prec, beam):
+    """One full CaptionPipeline beam search (encode graph, K/V hand-off, beam state, step graphs) on X returns the same token
+    ids and per-token log-probs, bit for bit, on a fresh pipeline and on one that has just searched a different batch Y with
+    longer encoder lengths: the buffers a pipeline keeps across batches (input ring, xcat and the K-padded operands inside the
+    captured encode, K/V staging, decode-lane caches, beam state) carry nothing from one batch into the next."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from on_device_image_captioning_amd.pipeline import CaptionPipeline
+    from test_e2e_gpu import TEOS, TSOS, _features_model
+    g, fd = W.TINY64, 1024                           # features-only model: the form that takes ragged encoder lengths
+    m = _features_model(g, cached_state_dict("TINY64", "xavier", end_to_end=False, img_feature_dim=fd), fd, prec)
+    X = W.synth_features(3, 144, fd, seed=42).to("cuda:0")
+    Y = W.synth_features(3, 144, fd, seed=7).to("cuda:0")
+    padx = [0, 40, 13]
+
+    def search(pipe):
+        pipe.submit(X, padx)
+        return pipe.collect_scored()
+
+    fresh = CaptionPipeline(m, 3, beam, 12, TSOS, TEOS, keep_scores=True)
+    toks0, lps0 = search(fresh)
+    used = CaptionPipeline(m, 3, beam, 12, TSOS, TEOS, keep_scores=True)
+    for _ in range(3):                               # every decode lane and ring slot has held Y
+        used.submit(Y, None)
+        used.collect_scored()
+    for rnd_ in range(3):
+        toks1, lps1 = search(used)
+        assert toks1 == toks0, (rnd_, toks1, toks0)
+        assert all(torch.equal(a, b) for a, b in zip(lps1, lps0)), rnd_
+    assert all(len(t_) >= 2 for t_ in toks0) and all(bool(torch.isfinite(l).all()) for l in lps0)
+
+
+# ============================================================================================== f. JPEG decode workspace
+def test_jpeg_decode_stays_inside_its_workspace(monkeypatch):
+    """DevicePreprocessor._grow over-allocates (grow-only, 2x), which would hide an overrun of odic_jpeg_workspace_bytes: here
+    every device buffer the decode path allocates is EXACTLY the requested bytes inside a poisoned allocation — the workspace
+    and the compressed-data copy (through `_grow`), and the RGB output and `status` (the module's torch.empty calls).
+    What this pins: no WRITE outside any of the four.  It does not pin over-READS of the compressed data: 0xFF is a legal JPEG
+    fill byte, so a decoder reading a few poison bytes past the end need not change a pixel."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from on_device_image_captioning_amd import image_utils
+    from on_device_image_captioning_amd.image_utils import DevicePreprocessor
+    from test_jpeg_gpu import check
+    from test_jpeg_host import encode, matrix_blobs, smooth_rgb
+    made = []
+    orig = DevicePreprocessor._grow
+
+    def exact(buf, nbytes, **kw):
+        if "device" not in kw:
+            return orig(buf, nbytes, **kw)
+        g = guarded(1, max(nbytes, 1), max(nbytes, 1), torch.uint8, kw["device"])
+        made.append(g)
+        return g.t.view(-1)
+
+    class TorchWithGuardedEmpty:
+        """`torch` as image_utils sees it, with device-side 1-D uint8 / int32 torch.empty (the RGB output, `status`) guarded."""
+        def __getattr__(self, name):
+            return getattr(torch, name)
+
+        @staticmethod
+        def empty(*size, **kw):
+            if kw.get("device") is not None and not kw.get("pin_memory") and len(size) == 1 and isinstance(size[0], int) \
+                    and kw.get("dtype") in (torch.uint8, torch.int32) and torch.device(kw["device"]).type == "cuda":
+                g = guarded(1, size[0], size[0], kw["dtype"], kw["device"])
+                made.append(g)
+                return g.t.view(-1)
+            return torch.empty(*size, **kw)
+
+    monkeypatch.setattr(DevicePreprocessor, "_grow", staticmethod(exact))
+    pre = DevicePreprocessor(384, "cuda:0")
+    monkeypatch.setattr(image_utils, "torch", TorchWithGuardedEmpty())
+    small = encode(smooth_rgb(8, 8, seed=1), quality=90)
+    big = encode(smooth_rgb(480, 640, seed=2), quality=90)
+    kinds = set()
+    for batch in (matrix_blobs(), [small], [big, big, small], [small]):      # ... and a large-then-small sequence
+        check(pre, batch)
+        torch.cuda.synchronize()
+        assert len(made) >= 4, "workspace, data copy, RGB output and status are all guarded"
+        for g in made:
+            g.assert_untouched(what=f"jpeg decode, {g.dtype} buffer of {g.cols} elements")
+            kinds.add(g.dtype)
+        made.clear()
+    assert kinds == {torch.uint8, torch.int32}
