@@ -51,7 +51,7 @@ extern "C" {
 #define ODIC_EUNSUPPORTED (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define ODIC_ABI_VERSION 16
+#define ODIC_ABI_VERSION 17
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -368,6 +368,49 @@ int odic_dynexp_step(const float* lin, int64_t ldlin, const float* qexp, const f
                      float* wfb_c, float* qk_c, const int32_t* anc, const int32_t* row_valid,
                      const int32_t* pos, const float* y_in, int64_t ldy_in, float* y, int64_t ldy,
                      int32_t N, int32_t T, int32_t d, int32_t E, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Whole-sequence (teacher-forced) decoder pass: every token is known up front, so all T positions of all N sequences
+ * are processed at once — rows are sequence-major, row = n·T + t, and the linear layers are odic_gemm with M = N·T.
+ * (The reference's evaluation loss, test.py:84-138: model(enc_x, dec_x = y[:, :-1]) → LabelSmoothingLoss.)  Nothing is
+ * cached in global memory and the launch count does not depend on T.  csrc/decoder_seq.hip.
+ * ------------------------------------------------------------------------------------------- */
+
+/* y[n·T + t, :] = embed[tokens[n][t]]·scale + pos_table[t]   (layers.py:16-17, End_ExpansionNet_v2.py:118-121).
+ *   tokens int64 [N, T] compact; embed fp32 [vocab, d]; pos_table fp32 [pos_rows, d]; T <= pos_rows (ODIC_EINVAL otherwise,
+ *   checked on the host).  A token outside [0, vocab) embeds as the zero vector: nothing is read out of bounds.
+ *   row_valid (optional, with dec_len int32 [N]): int32 [N·T] receives 1 where t < dec_len[n], else 0 — the row mask
+ *   odic_cross_attn_step takes.  y columns [d, ldy) are left untouched; row_valid is compact. */
+int odic_dec_embed_seq(const int64_t* tokens, const float* embed, const float* pos_table, const int32_t* dec_len,
+                       int32_t* row_valid, float* y, int64_t ldy, int32_t N, int32_t T, int32_t d, int32_t vocab,
+                       int32_t pos_rows, float scale, void* stream);
+
+/* Dynamic expansion (layers.py:152-204) for all positions of every sequence in one launch.
+ *   lin fp32 [N·T, >=5d] (ldlin): cond | key | class_a | class_b | selector pre-activation of LN1(y), the layout
+ *        odic_dynexp_step reads; qexp, bexp fp32 [E, d]; dec_len int32 [N] (clamped to [0, T]).
+ *   y_in fp32 [N·T, d] (ldy_in) → y fp32 [N·T, d] (ldy):  y = y_in + sel·A' + (1-sel)·B'  (may alias).
+ *   Masking as the reference: causal in position, rows and columns at t >= dec_len[n] masked.  A padded row gets
+ *   y = y_in (its weights are 0/(0+eps)), exactly what the step kernel gives with row_valid = 0.
+ *   z[(i,e), j] = (qexp[e]·key_j + cond_i·key_j)/sqrt(d) splits into an E x T and a T x T product per sequence; both,
+ *   the normalisers of the forward and backward weights and 16 rows at a time of the re-associated backward sum
+ *   (odic_dynexp_step above) stay in LDS; fp32 accumulation throughout.  One 1024-thread block per sequence.
+ *   T <= 128, E in {4, 8, 16, 32}, d a multiple of 64, ldlin a multiple of 4, lin / qexp 16-byte aligned: ODIC_EINVAL
+ *   before any launch otherwise.
+ *   y columns [d, ldy) are left untouched; lin columns beyond 5d and y_in columns beyond d are not read. */
+int odic_dynexp_seq(const float* lin, int64_t ldlin, const float* qexp, const float* bexp, const int32_t* dec_len,
+                    const float* y_in, int64_t ldy_in, float* y, int64_t ldy, int32_t N, int32_t T, int32_t d,
+                    int32_t E, float eps, void* stream);
+
+/* The scoring tail (log_softmax + gather of test.py:119-131 / losses/loss.py:15-39), one pass per logits row, no
+ * [R, V] log-prob tensor:   logits fp32 [R, V] (ldl); target int64 [R] or NULL.
+ *   logp_target fp32 [R]  logits[r][target[r]] − logsumexp(logits[r])       (written only with target)
+ *   sum_logp    fp32 [R]  Σ_v logits[r][v] − V·logsumexp  (the label-smoothing term; summed in fp64)
+ *   argmax     int32 [R]  (ties → lower index, as odic_logsoftmax_topk);  max_logp fp32 [R] its log-probability
+ *   status     int32 scalar, required with target: bit 0 is OR-ed in when some target lies outside [0, V); that row's
+ *              logp_target is 0 and nothing is read out of bounds.  The caller clears it.
+ * All outputs are compact; logits columns [V, ldl) are not read. */
+int odic_token_stats(const float* logits, int64_t ldl, const int64_t* target, float* logp_target, float* sum_logp,
+                     int32_t* argmax, float* max_logp, int32_t* status, int32_t R, int32_t V, void* stream);
 
 /* Cross attention of one query row per sequence against per-IMAGE cached K/V (layers.py:266-295;
  * the reference re-projects K/V of the 144 encoder tokens every step for every beam copy).

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libodic_hip.so")
 
 F32, BF16, FP8, F16, H2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _ERR = {-1: "ODIC_EINVAL (bad shape / alignment / enum)", -2: "ODIC_ENULL (required pointer is NULL)",
         -3: "ODIC_EUNSUPPORTED"}
@@ -79,6 +79,9 @@ _SIGNATURES = {
     "odic_selector_mix": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _P]),
     "odic_copy": (C.c_int, [_P, _P, _I64, _P]),
     "odic_dec_embed": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _P]),
+    "odic_dec_embed_seq": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64] + [_I32] * 5 + [_F, _P]),
+    "odic_dynexp_seq": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64] + [_I32] * 4 + [_F, _P]),
+    "odic_token_stats": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _P]),
     "odic_dynexp_step": (C.c_int, [_P, _I64, _P, _P] + [_P] * 7 + [_P, _P, _P, _P, _I64, _P, _I64] + [_I32] * 4 + [_F, _P]),
     "odic_cross_attn_step": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _I64] + [_I32] * 5 + [_P]),
     "odic_logsoftmax_topk": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _P]),

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import engine as _engine
 from . import ops
+from . import scoring as _scoring
 
 _DONE_POLL = 4      # host looks at the device `done` flag every this many steps
 
@@ -159,6 +160,85 @@ class CaptioningModel(nn.Module):
             else:
                 out[:, t].copy_(st.logits)
         return out
+
+    # ------------------------------------------------------------------ scoring given captions
+    def _sequence_stats(self, enc_x, enc_x_num_pads, n_img: int, dec: torch.Tensor, dec_len: torch.Tensor,
+                        targets: torch.Tensor, row_chunk: Optional[int] = None) -> dict:
+        """Encoder once per image + one whole-sequence decoder pass → per-position statistics [N, T] on the device
+        (CaptionerEngine.decode_sequence).  The ensemble overrides this."""
+        eng = self._captioner_engine()
+        dv = eng.device
+        mem = self.forward_enc(enc_x, enc_x_num_pads)
+        S = mem.shape[1]
+        return eng.decode_sequence(dec.to(dv), dec_len.to(dv), eng.project_kv(mem), self._enc_lens(n_img, S, enc_x_num_pads),
+                                   n_img, targets=targets.to(dv), row_chunk=row_chunk)
+
+    def _vocab_size(self) -> int:
+        return self.geometry.vocab_size          # (the module's own geometry: argument checks need no GPU)
+
+    def _max_seq_len(self) -> int:
+        return self.geometry.max_seq_len
+
+    def score_captions(self, enc_x, captions, enc_x_num_pads=None, *, captions_per_image: int = 1, pad_idx=None,
+                       dec_x_num_pads=None, row_chunk: Optional[int] = None) -> "_scoring.CaptionScores":
+        """Log-probability of given captions under the model, in one whole-sequence decoder pass (what test.py:84-138
+        does with forward + log_softmax + gather).  `captions`: token-id lists (SOS … EOS, ragged), or a padded int64
+        tensor with `dec_x_num_pads` (or `pad_idx` to measure trailing pads).  With `captions_per_image = R` the rows
+        are image-major — captions[i·R : (i+1)·R] belong to image i — and the encoder runs once per image.
+        Returns scoring.CaptionScores: logprobs[n, t] = log p(token t+1 | tokens 0..t), 0 behind the caption's end."""
+        n_img = enc_x.shape[0]
+        toks, lens = _scoring.pack_captions(captions, dec_x_num_pads, pad_idx=pad_idx, max_seq_len=self._max_seq_len())
+        N, Tm = toks.shape
+        if captions_per_image < 1 or N != n_img * captions_per_image:
+            raise ValueError(f"{N} captions for {n_img} inputs x {captions_per_image} captions per image")
+        V = self._vocab_size()
+        if int(toks.min()) < 0 or int(toks.max()) >= V:
+            raise ValueError(f"token ids must lie in [0, {V})")
+        if enc_x_num_pads is None:
+            enc_x_num_pads = [0] * n_img
+        dec_len = torch.tensor([n - 1 for n in lens], dtype=torch.int32)
+        st = self._sequence_stats(enc_x, enc_x_num_pads, n_img, toks[:, :-1].contiguous(), dec_len,
+                                  toks[:, 1:].contiguous(), row_chunk)
+        dv = st["logp"].device
+        real = torch.arange(Tm - 1, device=dv)[None, :] < dec_len.to(dv)[:, None]
+        lp = torch.where(real, st["logp"], torch.zeros_like(st["logp"]))
+        lengths = dec_len.to(dv, torch.int64)
+        tot = lp.sum(-1)
+        out_dv = enc_x.device if isinstance(enc_x, torch.Tensor) else dv
+        res = _scoring.CaptionScores(
+            logprobs=lp, lengths=lengths, sum=tot, mean=tot / lengths.to(torch.float32),
+            argmax=torch.where(real, st["argmax"], torch.full_like(st["argmax"], -1)),
+            sum_logp_vocab=torch.where(real, st["sum_logp"], torch.zeros_like(st["sum_logp"])))
+        for k in ("logprobs", "lengths", "sum", "mean", "argmax", "sum_logp_vocab"):
+            setattr(res, k, getattr(res, k).to(out_dv))
+        return res
+
+    def caption_loss(self, enc_x, dec_y, enc_x_num_pads, dec_y_num_pads, ignore_index, smoothing: float = 0.0,
+                     divide_by_non_zeros: bool = False) -> torch.Tensor:
+        """The evaluation loss of test.py:119-131: LabelSmoothingLoss(smoothing)(forward(enc_x, dec_y[:, :-1]),
+        dec_y[:, 1:], ignore_index, divide_by_non_zeros) — computed from the per-position statistics of one
+        whole-sequence pass in closed form (scoring.label_smoothing_loss); no [N, T, V] tensor exists."""
+        dec_y = dec_y.detach().to("cpu", torch.int64)
+        if dec_y.dim() != 2:
+            raise ValueError("dec_y must be [N, Ty]")
+        N, Ty = dec_y.shape
+        if enc_x.shape[0] != N:
+            raise ValueError(f"{N} target rows for {enc_x.shape[0]} inputs")
+        if Ty < 2:
+            raise ValueError("dec_y needs at least two columns")
+        pads = _as_list(dec_y_num_pads, N)
+        V = self._vocab_size()
+        dec = dec_y[:, :-1].contiguous()
+        tgt = dec_y[:, 1:].contiguous()
+        ignored = tgt == ignore_index
+        if int(dec.min()) < 0 or int(dec.max()) >= V or bool(((tgt < 0) | (tgt >= V))[~ignored].any()):
+            raise ValueError(f"token ids must lie in [0, {V})")
+        # as the reference, the decoder sees Ty - 1 positions with the pad counts of the Ty-long rows (test.py:121-123)
+        dec_len = torch.tensor([max(0, Ty - 1 - p) for p in pads], dtype=torch.int32)
+        st = self._sequence_stats(enc_x, enc_x_num_pads, N, dec, dec_len, tgt.masked_fill(ignored, 0))
+        loss = _scoring.label_smoothing_loss(st["logp"].cpu(), st["sum_logp"].cpu(), ignored, V, smoothing,
+                                             divide_by_non_zeros)
+        return loss.to(enc_x.device) if isinstance(enc_x, torch.Tensor) else loss
 
     def forward(self, enc_x, dec_x=None, enc_x_num_pads=[0], dec_x_num_pads=[0], apply_log_softmax=False,
                 mode="forward", **kwargs):
@@ -349,3 +429,9 @@ class Captioner:
 
     def beam_search(self, *a, **k):
         return self.model.beam_search(*a, **k)
+
+    def score_captions(self, *a, **k):
+        return self.model.score_captions(*a, **k)
+
+    def caption_loss(self, *a, **k):
+        return self.model.caption_loss(*a, **k)

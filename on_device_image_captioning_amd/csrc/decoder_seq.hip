@@ -1,0 +1,364 @@
+// Whole-sequence (teacher-forced) decoder kernels for gfx950 (fp32): every position of every sequence in one launch.
+//
+// The search path (decoder_ops.hip) processes ONE new position per launch against per-position caches in global memory,
+// because the next token is not known yet.  Scoring a caption that already exists knows every token up front, so the
+// N·T rows go through the linear layers as one M = N·T product each (odic_gemm) and the kernels here do the parts that
+// couple the positions of a sequence:
+//
+//   dec_embed_seq_kernel   y[n·T + t] = embed[tok[n][t]]·sqrt(d) + pos_table[t]  (+ the [N·T] row-validity flags)
+//   dynexp_seq_kernel      DynamicExpansionBlock (layers.py:152-204) for all positions of a sequence, nothing cached
+//                          in global memory
+//   token_stats_kernel     the scoring tail: per logits row the target's log-prob, Σ_v log-prob, arg-max and its
+//                          log-prob — one number per quantity instead of an [R, V] log-prob tensor
+#include "odic_common.h"
+
+namespace {
+
+constexpr int SEQ_MAX_T = 128;
+constexpr int SEQ_NT = 1024;      // threads per sequence
+constexpr int SEQ_TR = 16;        // output rows per phase-2 tile
+
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dec_embed_seq_kernel(const long long* __restrict__ tokens,
+                                                            const float* __restrict__ embed,
+                                                            const float* __restrict__ pos_table,
+                                                            const int* __restrict__ dec_len, int* __restrict__ row_valid,
+                                                            float* __restrict__ y, long ldy, int T, int d, int vocab,
+                                                            float scale) {
+  const long row = blockIdx.x;            // n·T + t
+  const int n = (int)(row / T), t = (int)(row - (long)n * T);
+  const long tok = tokens[row];
+  const bool ok = tok >= 0 && tok < vocab;      // an id outside the table embeds as zero: nothing is read out of bounds
+  const float* er = embed + (ok ? tok : 0) * (long)d;
+  const float sc = ok ? scale : 0.f;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) y[row * ldy + c] = er[c] * sc + pos_table[(long)t * d + c];
+  if (row_valid && threadIdx.x == 0) row_valid[row] = t < dec_len[n] ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Dynamic expansion of a whole sequence.  With s = 1/sqrt(d), L = dec_len[n] and, for positions i, j, t < L,
+//   QK[e][j] = qexp[e]·key_j          CK[i][j] = cond_i·key_j                 (an E x L and an L x L product)
+//   forward   zf(j,e,i) = (QK[e][i] + CK[j][i])·s,  i <= j     nfa[e][j] = 1/(Σ_{i<=j} relu(zf) + eps)   (nfb: relu(-zf))
+//   backward  zb(t,j,e) = (QK[e][t] + CK[j][t])·s,  j <= t     nba[t]   = 1/(Σ_{j<=t,e} relu(zb) + eps)  (nbb: relu(-zb))
+// the reference's output row t is  Σ_{j<=t,e} wba(t,j,e)·(Σ_{i<=j} wfa(j,e,i)·va_i + bexp[e] + cond_j); re-associated as in
+// dynexp_step_kernel (include/odic_hip.h) it is
+//   out_a[t] = Σ_{i<=t} ca[t][i]·va_i + Σ_{j<=t} wja[t][j]·cond_j + Σ_e wea[t][e]·bexp[e]
+//   ca[t][i] = nba[t]·Σ_{j=i..t} Σ_e relu(zb(t,j,e))·relu(zf(j,e,i))·nfa[e][j]
+//   wja[t][j] = nba[t]·Σ_e relu(zb(t,j,e))          wea[t][e] = nba[t]·Σ_{j<=t} relu(zb(t,j,e))
+// and the same with relu(-z) for out_b;  y[t] = y_in[t] + σ(sel_t)·out_a[t] + (1-σ(sel_t))·out_b[t].
+// Causality and the padding mask are the loop bounds: a position t >= L adds nothing (its weights are 0/(0+eps)) and no
+// valid position ever looks at one.
+//
+// One 1024-thread block per sequence.  QK, CK and the normalisers live in LDS for the whole block (the forward weights
+// themselves — L·E·L values — would not fit and are recomputed from QK / CK where they are used: two adds, two max and
+// a multiply); the coefficient rows ca | cb | wja | wjb exist for SEQ_TR = 16 output rows at a time.
+//   LDS words: E·TS + T·TS + 2·E·TS + 2·T + 4·TR·T + 2·TR·E   with TS = T rounded up to 1 mod 4
+//     T = 73, E = 16 (COCO evaluation length, the shipped decoder): 57 KB;  T = 128, E = 32 (the limits): 153 KB of the
+//     CU's 160 KB.  Occupancy is ONE block per CU at every T, and registers set it, not LDS: 90 VGPRs allocate 96, that
+//     is 5 waves per SIMD = 20 per CU, and a block is 16 waves.
+//   phase 1  (L+E) x L dot products of length d as 4 x 4 register tiles, float4 loads from the lin rows
+//   phase 2  per row tile: coefficients (one thread per (t, i), consecutive lanes = consecutive i: QK / nf rows are read
+//            at consecutive addresses, CK rows with an odd stride), then thread = (channel, 8 rows) accumulates the three
+//            sums over i with coalesced loads of va_i | vb_i | cond_i and one 16-byte LDS read per (row, i).
+// ---------------------------------------------------------------------------------------------
+struct DynSeqParams {
+  const float* lin; long ldlin; const float* qexp; const float* bexp; const int* dec_len;
+  const float* y_in; long ldyi; float* y; long ldy;
+  int N, T, d, E, TS; float eps;
+};
+
+__global__ __launch_bounds__(SEQ_NT) void dynexp_seq_kernel(DynSeqParams p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int d = p.d, E = p.E, T = p.T, TS = p.TS, n = blockIdx.x, tid = threadIdx.x;
+  constexpr int TR = SEQ_TR;
+  float4* coef = (float4*)sm;                       // [T][TR] {ca, cb, wja, wjb}
+  float* we = sm + 4 * TR * T;                      // [TR][E][2]
+  float* QK = we + 2 * TR * E;                      // [E][TS]
+  float* CK = QK + E * TS;                          // [T][TS]
+  float* nfa = CK + T * TS;                         // [E][TS]
+  float* nfb = nfa + E * TS;                        // [E][TS]
+  float* nba = nfb + E * TS;                        // [T]
+  float* nbb = nba + T;                             // [T]
+
+  const int L = max(0, min(p.dec_len[n], T));
+  const float* lin = p.lin + (long)n * T * p.ldlin;
+  const float* yin = p.y_in + (long)n * T * p.ldyi;
+  float* yout = p.y + (long)n * T * p.ldy;
+  const float s = rsqrtf((float)d);
+
+  // rows [L, T): nothing is added
+  for (long q = tid; q < (long)(T - L) * d; q += SEQ_NT) {
+    const int t = L + (int)(q / d), c = (int)(q % d);
+    yout[(long)t * p.ldy + c] = yin[(long)t * p.ldyi + c];
+  }
+  if (L == 0) return;
+
+  // ---- phase 1: rows a < L are cond_a, rows L..L+E-1 are qexp; columns are key_b
+  {
+    const int na = (L + E + 3) >> 2, nb = (L + 3) >> 2;
+    for (int it = tid; it < na * nb; it += SEQ_NT) {
+      const int a0 = (it / nb) * 4, b0 = (it % nb) * 4;
+      const float* ar[4]; const float* br[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int a = min(a0 + u, L + E - 1), b = min(b0 + u, L - 1);
+        ar[u] = a < L ? lin + (long)a * p.ldlin : p.qexp + (long)(a - L) * d;
+        br[u] = lin + (long)b * p.ldlin + d;
+      }
+      float acc[4][4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[u][v] = 0.f;
+      for (int c = 0; c < d; c += 4) {
+        float4 av[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { av[u] = *(const float4*)(ar[u] + c); bv[u] = *(const float4*)(br[u] + c); }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            float r = acc[u][v];
+            r = fmaf(av[u].x, bv[v].x, r); r = fmaf(av[u].y, bv[v].y, r);
+            r = fmaf(av[u].z, bv[v].z, r); r = fmaf(av[u].w, bv[v].w, r);
+            asm volatile("" : "+v"(r));     // scalar FMAs: hipcc's SLP pass pairs neighbouring accumulators into packed fp32
+                                            // ops with `op_sel` source selection otherwise (tests/test_isa_lint.py)
+            acc[u][v] = r;
+          }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int a = a0 + u, b = b0 + v;
+          if (a < L + E && b < L) {
+            if (a < L) CK[a * TS + b] = acc[u][v];
+            else QK[(a - L) * TS + b] = acc[u][v];
+          }
+        }
+    }
+  }
+  __syncthreads();
+
+  // ---- normalisers.  forward: one thread per (e, j); backward: 16 lanes per t, fixed shuffle order
+  for (int it = tid; it < E * L; it += SEQ_NT) {
+    const int e = it / L, j = it - e * L;
+    float sp = 0.f, sn = 0.f;
+    for (int i = 0; i <= j; ++i) {
+      const float z = (QK[e * TS + i] + CK[j * TS + i]) * s;
+      sp += fmaxf(z, 0.f); sn += fmaxf(-z, 0.f);
+    }
+    nfa[e * TS + j] = 1.0f / (sp + p.eps);
+    nfb[e * TS + j] = 1.0f / (sn + p.eps);
+  }
+  {
+    const int grp = tid >> 4, gl = tid & 15;
+    for (int t = grp; t < ((L + SEQ_NT / 16 - 1) / (SEQ_NT / 16)) * (SEQ_NT / 16); t += SEQ_NT / 16) {
+      float sp = 0.f, sn = 0.f;
+      if (t < L)
+        for (int q = gl; q < (t + 1) * E; q += 16) {
+          const int j = q / E, e = q - j * E;
+          const float z = (QK[e * TS + t] + CK[j * TS + t]) * s;
+          sp += fmaxf(z, 0.f); sn += fmaxf(-z, 0.f);
+        }
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sn += __shfl_xor(sn, o, 64); }
+      if (gl == 0 && t < L) { nba[t] = 1.0f / (sp + p.eps); nbb[t] = 1.0f / (sn + p.eps); }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2, SEQ_TR output rows at a time
+  for (int t0 = 0; t0 < L; t0 += TR) {
+    const int rows = min(TR, L - t0);            // valid rows of this tile
+    const int tmax = t0 + rows - 1;              // last position any of them looks at
+    // coefficients; entries with i > t are zero so that the channel loop below needs no per-row bound
+    for (int it = tid; it < TR * (tmax + 1); it += SEQ_NT) {
+      const int r = it / (tmax + 1), i = it - r * (tmax + 1);
+      const int t = t0 + r;
+      float sa = 0.f, sb = 0.f, ja = 0.f, jb = 0.f;
+      if (r < rows && i <= t) {
+        for (int j = i; j <= t; ++j) {
+          const float ckt = CK[j * TS + t], cki = CK[j * TS + i];
+          for (int e = 0; e < E; ++e) {
+            const float zb = (QK[e * TS + t] + ckt) * s;
+            const float zf = (QK[e * TS + i] + cki) * s;
+            sa = fmaf(fmaxf(zb, 0.f) * fmaxf(zf, 0.f), nfa[e * TS + j], sa);
+            sb = fmaf(fmaxf(-zb, 0.f) * fmaxf(-zf, 0.f), nfb[e * TS + j], sb);
+          }
+        }
+        const float cit = CK[i * TS + t];        // wja[t][i]: the backward weights of position i summed over e
+        for (int e = 0; e < E; ++e) {
+          const float zb = (QK[e * TS + t] + cit) * s;
+          ja += fmaxf(zb, 0.f); jb += fmaxf(-zb, 0.f);
+        }
+        const float na = nba[t], nb = nbb[t];
+        sa *= na; ja *= na; sb *= nb; jb *= nb;
+      }
+      coef[i * TR + r] = make_float4(sa, sb, ja, jb);
+    }
+    for (int it = tid; it < TR * E; it += SEQ_NT) {
+      const int r = it / E, e = it - r * E;
+      const int t = t0 + r;
+      float ea = 0.f, eb = 0.f;
+      if (r < rows) {
+        const float qt = QK[e * TS + t];
+        for (int j = 0; j <= t; ++j) {
+          const float zb = (qt + CK[j * TS + t]) * s;
+          ea += fmaxf(zb, 0.f); eb += fmaxf(-zb, 0.f);
+        }
+        ea *= nba[t]; eb *= nbb[t];
+      }
+      we[2 * it] = ea; we[2 * it + 1] = eb;
+    }
+    __syncthreads();
+    // channel sums: thread = (channel c, 8 rows of the tile)
+    constexpr int RG = 8;
+    for (int it = tid; it < d * (TR / RG); it += SEQ_NT) {
+      const int c = it % d, r0 = (it / d) * RG;
+      if (r0 >= rows) continue;
+      float oa[RG], ob[RG];
+#pragma unroll
+      for (int r = 0; r < RG; ++r) { oa[r] = 0.f; ob[r] = 0.f; }
+      const int iend = min(tmax, t0 + r0 + RG - 1);
+      for (int i = 0; i <= iend; ++i) {
+        const float* li = lin + (long)i * p.ldlin + c;
+        const float cj = li[0], va = li[2 * d], vb = li[3 * d];
+        const float4* cf = coef + i * TR + r0;
+#pragma unroll
+        for (int r = 0; r < RG; ++r) {
+          const float4 w = cf[r];
+          oa[r] = fmaf(w.x, va, oa[r]); oa[r] = fmaf(w.z, cj, oa[r]);
+          ob[r] = fmaf(w.y, vb, ob[r]); ob[r] = fmaf(w.w, cj, ob[r]);
+          asm volatile("" : "+v"(oa[r]), "+v"(ob[r]));      // (kept scalar, as above)
+        }
+      }
+      for (int e = 0; e < E; ++e) {
+        const float be = p.bexp[(long)e * d + c];
+#pragma unroll
+        for (int r = 0; r < RG; ++r) {
+          oa[r] = fmaf(we[2 * ((r0 + r) * E + e)], be, oa[r]);
+          ob[r] = fmaf(we[2 * ((r0 + r) * E + e) + 1], be, ob[r]);
+          asm volatile("" : "+v"(oa[r]), "+v"(ob[r]));
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < RG; ++r) {
+        const int t = t0 + r0 + r;
+        if (r0 + r < rows) {
+          const float sg = 1.0f / (1.0f + expf(-lin[(long)t * p.ldlin + 4 * d + c]));
+          yout[(long)t * p.ldy + c] = yin[(long)t * p.ldyi + c] + sg * oa[r] + (1.0f - sg) * ob[r];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Scoring tail: one 256-thread block per logits row, two passes over the row (the second one hits the cache).
+//   pass 1: maximum with its lowest index, pass 2: Σ exp(x - max) in fp32 and Σ (x - max) in fp64 (V terms of
+//   magnitude ~10: an fp32 sum would carry an error of the size of one term's last bits times V)
+// ---------------------------------------------------------------------------------------------
+constexpr int TS_NT = 256;
+
+__global__ __launch_bounds__(TS_NT) void token_stats_kernel(const float* __restrict__ logits, long ldl,
+                                                            const long long* __restrict__ target,
+                                                            float* __restrict__ logp_target, float* __restrict__ sum_logp,
+                                                            int* __restrict__ argmax, float* __restrict__ max_logp,
+                                                            int* __restrict__ status, int V) {
+  __shared__ float s_v[TS_NT / 64];
+  __shared__ int s_i[TS_NT / 64];
+  __shared__ double s_d[TS_NT / 64];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ldl;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float m = -INFINITY; int mi = 0x7fffffff;
+  for (int i = tid; i < V; i += TS_NT) {
+    const float v = x[i];
+    if (v > m || mi == 0x7fffffff) { m = v; mi = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64); const int oi = __shfl_xor(mi, o, 64);
+    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+  }
+  if (lane == 0) { s_v[wave] = m; s_i[wave] = mi; }
+  __syncthreads();
+  m = s_v[0]; mi = s_i[0];
+#pragma unroll
+  for (int w = 1; w < TS_NT / 64; ++w)
+    if (s_v[w] > m || (s_v[w] == m && s_i[w] < mi)) { m = s_v[w]; mi = s_i[w]; }
+  __syncthreads();
+  float se = 0.f; double sx = 0.0;
+  for (int i = tid; i < V; i += TS_NT) {
+    const float dv = x[i] - m;
+    se += expf(dv); sx += (double)dv;
+  }
+  se = wave_sum(se);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+  if (lane == 0) { s_v[wave] = se; s_d[wave] = sx; }
+  __syncthreads();
+  if (tid == 0) {
+    float e = 0.f; double dsum = 0.0;
+    for (int w = 0; w < TS_NT / 64; ++w) { e += s_v[w]; dsum += s_d[w]; }
+    const float lg = logf(e);                 // logsumexp = m + lg
+    sum_logp[row] = (float)(dsum - (double)V * (double)lg);
+    argmax[row] = mi;
+    max_logp[row] = -lg;
+    if (target) {
+      const long long tg = target[row];
+      if (tg >= 0 && tg < V) logp_target[row] = (x[tg] - m) - lg;
+      else { logp_target[row] = 0.f; atomicOr(status, 1); }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int odic_dec_embed_seq(const int64_t* tokens, const float* embed, const float* pos_table,
+                                  const int32_t* dec_len, int32_t* row_valid, float* y, int64_t ldy, int32_t N,
+                                  int32_t T, int32_t d, int32_t vocab, int32_t pos_rows, float scale, void* stream) {
+  if (!tokens || !embed || !pos_table || !y) return ODIC_ENULL;
+  if (row_valid && !dec_len) return ODIC_ENULL;
+  if (N <= 0 || T <= 0 || d <= 0 || vocab <= 0 || pos_rows <= 0 || T > pos_rows || ldy < d) return ODIC_EINVAL;
+  if ((int64_t)N * T > 0x7fffffff) return ODIC_EINVAL;
+  hipLaunchKernelGGL(dec_embed_seq_kernel, dim3((unsigned)(N * T)), dim3(256), 0, (hipStream_t)stream,
+                     (const long long*)tokens, embed, pos_table, dec_len, row_valid, y, (long)ldy, T, d, vocab, scale);
+  return odic_launch_status();
+}
+
+extern "C" int odic_dynexp_seq(const float* lin, int64_t ldlin, const float* qexp, const float* bexp,
+                               const int32_t* dec_len, const float* y_in, int64_t ldy_in, float* y, int64_t ldy,
+                               int32_t N, int32_t T, int32_t d, int32_t E, float eps, void* stream) {
+  if (!lin || !qexp || !bexp || !dec_len || !y_in || !y) return ODIC_ENULL;
+  if (N <= 0 || T <= 0 || T > SEQ_MAX_T || d <= 0 || d % 64) return ODIC_EINVAL;
+  if (E != 4 && E != 8 && E != 16 && E != 32) return ODIC_EINVAL;
+  if (ldlin < 5 * (int64_t)d || (ldlin & 3) || ldy_in < d || ldy < d || ((uintptr_t)lin & 15) || ((uintptr_t)qexp & 15))
+    return ODIC_EINVAL;
+  DynSeqParams p;
+  p.lin = lin; p.ldlin = ldlin; p.qexp = qexp; p.bexp = bexp; p.dec_len = dec_len; p.y_in = y_in; p.ldyi = ldy_in;
+  p.y = y; p.ldy = ldy; p.N = N; p.T = T; p.d = d; p.E = E; p.eps = eps;
+  p.TS = T + ((5 - (T & 3)) & 3);           // T rounded up to 1 mod 4: odd row stride, 2-way conflicts at worst
+  const size_t shmem = ((size_t)4 * SEQ_TR * T + 2 * SEQ_TR * E + (size_t)(3 * E + T) * p.TS + 2 * T) * sizeof(float);
+  if (shmem > 160 * 1024) return ODIC_EINVAL;
+  static bool raised = false;               // the first call is never inside a capture
+  if (!raised) {
+    (void)hipFuncSetAttribute((const void*)dynexp_seq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    raised = true;
+  }
+  hipLaunchKernelGGL(dynexp_seq_kernel, dim3(N), dim3(SEQ_NT), shmem, (hipStream_t)stream, p);
+  return odic_launch_status();
+}
+
+extern "C" int odic_token_stats(const float* logits, int64_t ldl, const int64_t* target, float* logp_target,
+                                float* sum_logp, int32_t* argmax, float* max_logp, int32_t* status, int32_t R,
+                                int32_t V, void* stream) {
+  if (!logits || !sum_logp || !argmax || !max_logp) return ODIC_ENULL;
+  if (target && (!logp_target || !status)) return ODIC_ENULL;
+  if (R <= 0 || V <= 0 || ldl < V) return ODIC_EINVAL;
+  hipLaunchKernelGGL(token_stats_kernel, dim3(R), dim3(TS_NT), 0, (hipStream_t)stream, logits, (long)ldl,
+                     (const long long*)target, logp_target, sum_logp, argmax, max_logp, status, V);
+  return odic_launch_status();
+}

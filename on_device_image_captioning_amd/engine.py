@@ -564,3 +564,92 @@ class CaptionerEngine:
             return
         ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx, emb=st.emb)
+
+    # ------------------------------------------------------------------------------------------
+    # whole-sequence (teacher-forced) pass: every token is known, so the N·T rows go through each layer at once
+    def vocab_row_chunk(self) -> int:
+        """Rows per vocabulary product of decode_sequence: the logits workspace stays below 100 MB (2496 rows at
+        V = 10000)."""
+        return max(64, (100_000_000 // (4 * self.g.vocab_size)) // 64 * 64)
+
+    def decode_sequence(self, tokens: torch.Tensor, dec_len: torch.Tensor, kv: torch.Tensor, enc_len: torch.Tensor,
+                        n_img: int, targets: Optional[torch.Tensor] = None, want_logits: bool = False,
+                        row_chunk: Optional[int] = None):
+        """Teacher-forced decoder over whole sequences (End_ExpansionNet_v2.py:103-138 in one pass).
+        tokens int64 [N, T], rows image-major (N / n_img captions per image, sharing that image's K/V); dec_len int32 [N]
+        real tokens per row; kv = project_kv(mem) [n_img, S, 2·N_dec·d]; enc_len int32 [n_img].
+        want_logits: returns the logits fp32 [N, T, V] (padded rows hold what the reference's masked rows hold).
+        Otherwise returns a dict of per-position statistics, each [N, T]: 'logp' (log-prob of targets[n, t]; only with
+        `targets` int64 [N, T]), 'sum_logp' (Σ_v log-prob), 'argmax' (int32), 'max_logp', and 'status' (int32 scalar,
+        non-zero when a target was outside the vocabulary).  The vocabulary product and the statistics run over
+        `row_chunk` rows at a time; the chunking changes no result bit (every product here is the 64 x 64 tile kernel,
+        whose rows are independent of M).  The number of launches does not depend on T."""
+        g, dv = self.g, self.device
+        d, L, V, E = g.d_model, g.N_dec, g.vocab_size, g.num_exp_dec
+        N, T = tokens.shape
+        if T > 128:
+            raise RuntimeError("more than 128 decode positions are not supported by odic_dynexp_seq")
+        if T > self.pos_table.shape[0]:
+            raise RuntimeError(f"{T} decode positions exceed the pos_encoder table ({self.pos_table.shape[0]})")
+        if N % n_img or kv.shape[0] != n_img or enc_len.numel() != n_img or dec_len.numel() != N:
+            raise RuntimeError("decode_sequence: rows must be image-major with N a multiple of n_img")
+        if tokens.dtype != torch.int64 or dec_len.dtype != torch.int32 or enc_len.dtype != torch.int32:
+            raise RuntimeError("decode_sequence wants int64 tokens and int32 lengths")
+        tokens = tokens.contiguous()
+        M, ld, S = N * T, L * d, kv.shape[1]
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dv)      # noqa: E731
+        TC = 3                                   # odic_gemm tile_cfg: the 64 x 64 tile kernel whatever M is
+        ycat, row_valid = f(M, ld), torch.empty(M, dtype=torch.int32, device=dv)
+        ops.dec_embed_seq(tokens, self.embed, self.pos_table, ycat, ld, N, T, d, math.sqrt(d), dec_len, row_valid)
+        xn, lin, q, att, h = f(M, d), f(M, 5 * d), f(M, d), f(M, d), f(M, g.ff)
+        for i, w in enumerate(self.dec):
+            xin = ycat if i == 0 else ycat[:, (i - 1) * d:]
+            xo = ycat[:, i * d:]
+            ops.layernorm(xin, w["n1w"], w["n1b"], M=M, C_=d, ldx=ld, out=xn)
+            ops.gemm(xn, w["dyn_w"], w["dyn_b"], out=lin, tile_cfg=TC)                                   # [M,5d]
+            ops.dynexp_seq(lin, 5 * d, w["qexp"], w["bexp"], dec_len, xin, ld, xo, ld, N, T, d, E)
+            ops.layernorm(xo, w["n2w"], w["n2b"], M=M, C_=d, ldx=ld, out=xn)
+            ops.gemm(xn, w["wq"], w["bq"], out=q, tile_cfg=TC)
+            # the step kernel's row → image map is row / (rows / n_img): the sequence-major rows of an image are contiguous
+            ops.cross_attn_step(q, d, kv, kv.shape[2], 2 * i * d, (2 * i + 1) * d, enc_len, row_valid, att, d, M,
+                                n_img, S, d, g.num_heads)
+            ops.gemm(att, w["wo"], w["bo"], residual=xo, out=xo, M=M, N=d, K=d, lda=d, ldw=d, ldr=ld, ldc=ld,
+                     tile_cfg=TC)
+            ops.layernorm(xo, w["n3w"], w["n3b"], M=M, C_=d, ldx=ld, out=xn)
+            ops.gemm(xn, w["f1w"], w["f1b"], out=h, act=ops.ACT_RELU, tile_cfg=TC)
+            ops.gemm(h, w["f2w"], w["f2b"], residual=xo, out=xo, M=M, N=d, K=g.ff, lda=g.ff, ldw=g.ff, ldr=ld,
+                     ldc=ld, tile_cfg=TC)
+        pre = f(M, d)
+        ops.gemm(ycat, self.dr_w, self.dr_b, residual=ycat[:, (L - 1) * d:], out=pre, M=M, N=d, K=ld, lda=ld,
+                 ldw=ld, ldr=ld, ldc=d, tile_cfg=TC)
+        ops.layernorm(pre, self.drn_w, self.drn_b, out=xn)
+        rc = int(row_chunk) if row_chunk else self.vocab_row_chunk()
+        if rc <= 0:
+            raise ValueError("row_chunk must be positive")
+        if want_logits:
+            out = f(N, T, V)
+            o2 = out.view(M, V)
+            for r0 in range(0, M, rc):
+                r1 = min(M, r0 + rc)
+                ops.gemm(xn[r0:r1], self.voc_w, self.voc_b, out=o2[r0:r1], tile_cfg=TC)
+            return out
+        tg = None
+        if targets is not None:
+            if targets.dtype != torch.int64 or tuple(targets.shape) != (N, T):
+                raise RuntimeError("targets must be int64 [N, T]")
+            tg = targets.contiguous().view(M)
+        logp = f(M) if tg is not None else None
+        sum_logp, max_logp = f(M), f(M)
+        argmax = torch.empty(M, dtype=torch.int32, device=dv)
+        status = torch.zeros(1, dtype=torch.int32, device=dv)
+        ws = f(min(rc, M), V)
+        for r0 in range(0, M, rc):
+            r1 = min(M, r0 + rc)
+            ops.gemm(xn[r0:r1], self.voc_w, self.voc_b, out=ws[:r1 - r0], tile_cfg=TC)
+            ops.token_stats(ws, V, None if tg is None else tg[r0:r1], None if logp is None else logp[r0:r1],
+                            sum_logp[r0:r1], argmax[r0:r1], max_logp[r0:r1], None if tg is None else status, r1 - r0, V)
+        res = {"sum_logp": sum_logp.view(N, T), "argmax": argmax.view(N, T), "max_logp": max_logp.view(N, T),
+               "status": status}
+        if logp is not None:
+            res["logp"] = logp.view(N, T)
+        return res

@@ -42,13 +42,61 @@ class EsembleCaptioningModel(CaptioningModel):
     def forward_enc(self, enc_input, enc_input_num_pads):
         return [m.forward_enc(enc_input, enc_input_num_pads) for m in self.models_list]
 
+    # ------------------------------------------------------------------ scoring (CaptioningModel.score_captions)
+    def _vocab_size(self) -> int:
+        sizes = {m._vocab_size() for m in self.models_list}
+        if len(sizes) != 1:
+            raise ValueError(f"the members of an ensemble must share one vocabulary (sizes {sorted(sizes)})")
+        return sizes.pop()
+
+    def _max_seq_len(self) -> int:
+        return min(m._max_seq_len() for m in self.models_list)
+
+    def _sequence_stats(self, enc_x, enc_x_num_pads, n_img, dec, dec_len, targets, row_chunk=None) -> dict:
+        """Per member the whole-sequence logits of a row chunk, averaged as the search averages a step
+        (odic_ensemble_logprobs), then the same odic_token_stats as the single model: its log-sum-exp of an already
+        normalised row is ~0, and there is one code path.
+        `row_chunk` here bounds the logits rows held at once over ALL members (each member's [rows, V] tensor plus the
+        average): the captions are processed in groups of whole images of about row_chunk / (members + 1) rows, each group
+        one decode_sequence(want_logits=True) call per member (whose own vocabulary product then fits one chunk)."""
+        V = self._vocab_size()
+        engs = [m._captioner_engine() for m in self.models_list]
+        dv = engs[0].device
+        N, T = dec.shape
+        dec, dec_len, tg = dec.to(dv), dec_len.to(dv), targets.to(dv).contiguous().view(-1)
+        per_img = N // n_img
+        # whole captions-of-an-image groups per chunk, so that every chunk is a decode_sequence call of its own
+        imgs_per_chunk = max(1, (row_chunk or engs[0].vocab_row_chunk()) // (per_img * T * (len(engs) + 1)))
+        kvs, lens = [], []
+        for m, eng, mem in zip(self.models_list, engs, self.forward_enc(enc_x, enc_x_num_pads)):
+            kvs.append(eng.project_kv(mem))
+            lens.append(m._enc_lens(n_img, mem.shape[1], enc_x_num_pads))
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dv)      # noqa: E731
+        logp, sum_logp, max_logp = f(N * T), f(N * T), f(N * T)
+        argmax = torch.empty(N * T, dtype=torch.int32, device=dv)
+        status = torch.zeros(1, dtype=torch.int32, device=dv)
+        for i0 in range(0, n_img, imgs_per_chunk):
+            i1 = min(n_img, i0 + imgs_per_chunk)
+            r0, r1 = i0 * per_img, i1 * per_img
+            lg = [eng.decode_sequence(dec[r0:r1], dec_len[r0:r1], kv[i0:i1], ln[i0:i1], i1 - i0, want_logits=True)
+                  .view(-1, V) for eng, kv, ln in zip(engs, kvs, lens)]
+            avg = f((r1 - r0) * T, V)
+            ops.ensemble_logprobs(lg, avg)
+            a, b = r0 * T, r1 * T
+            ops.token_stats(avg, V, tg[a:b], logp[a:b], sum_logp[a:b], argmax[a:b], max_logp[a:b], status, b - a, V)
+        return {"logp": logp.view(N, T), "sum_logp": sum_logp.view(N, T), "argmax": argmax.view(N, T),
+                "max_logp": max_logp.view(N, T), "status": status}
+
     def ensemble_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                              max_seq_len=20, sample_or_max="max") -> Tuple[List[List[List[int]]], torch.Tensor]:
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
-        if sample_or_max != "max":
-            raise NotImplementedError("the ensemble search is built for sample_or_max='max'")
+        sample = sample_or_max == "sample"
+        # 'sample' (reference models/ensemble_captioning_model.py:123-130,174-183): the k candidates of every beam are drawn
+        # without replacement from the averaged distribution — odic_logsoftmax_sample on rows that already are
+        # log-probabilities (its normalisation is then the identity up to rounding), keyed by the lead member's seed
+        seed = self.models_list[0]._next_sampling_seed() if sample else 0
         mems = self.forward_enc(enc_input, enc_input_num_pads)
         engs = [m._captioner_engine() for m in self.models_list]
         dv = engs[0].device
@@ -72,7 +120,10 @@ class EsembleCaptioningModel(CaptioningModel):
             for eng, st in zip(engs, states):
                 eng.step_logits(st)                              # reads the shared next_tok / pos / ancestor table
             ops.ensemble_logprobs([st.logits for st in states], avg)
-            ops.topk_rows(avg, lead.cand_val, lead.cand_idx, k)
+            if sample:
+                ops.logsoftmax_sample(avg, V, None, 0, lead.cand_val, lead.cand_idx, lead.N, V, k, seed, lead.pos)
+            else:
+                ops.topk_rows(avg, lead.cand_val, lead.cand_idx, k)
             ops.beam_step(lead.cand_val, lead.cand_idx, lead.beam_state, lead.n_img, lead.beams, lead.T, eos_idx)
             if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(lead.done.item()):
                 break

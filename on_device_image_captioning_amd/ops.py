@@ -559,6 +559,36 @@ def dynexp_step(lin, ldlin, qexp, bexp, cond_c, key_c, va_c, vb_c, wfa_c, wfb_c,
                    "odic_dynexp_step")
 
 
+# ----------------------------------------------------------------------------------------------
+# whole-sequence (teacher-forced) decoder pass — csrc/decoder_seq.hip
+def dec_embed_seq(tokens, embed, pos_table, y, ldy, N, T, d, scale, dec_len=None, row_valid=None) -> None:
+    """y[n·T + t] = embed[tokens[n, t]]·scale + pos_table[t]; with dec_len / row_valid also the [N·T] row mask."""
+    _need_cuda(tokens, embed, pos_table, y, dec_len, row_valid)
+    with _timed("dec_embed", 2.0 * N * T * d, N * T * (8.0 + 2 * d * 4) + T * d * 4):
+        _hip.check(_hip.load().odic_dec_embed_seq(_p(tokens), _p(embed), _p(pos_table), _p(dec_len), _p(row_valid),
+                                                  _p(y), ldy, N, T, d, embed.shape[0], pos_table.shape[0], scale,
+                                                  _stream()), "odic_dec_embed_seq")
+
+
+def dynexp_seq(lin, ldlin, qexp, bexp, dec_len, y_in, ldy_in, y, ldy, N, T, d, E, eps=1e-9) -> None:
+    """Dynamic expansion of all T positions of N sequences (layers.py:152-204) in one launch."""
+    _need_cuda(lin, qexp, bexp, dec_len, y_in, y)
+    # lin rows in, y in / out;  (T+E)·T dot products of length d, the T³E/6 coefficient sums (5 flops each, x2),
+    # 4 FMAs per (t, i <= t, channel)
+    flops = N * (2.0 * (T + E) * T * d + 10.0 * T * T * T * E / 6 + 4.0 * T * T * d)
+    with _timed("dynexp_seq", flops, N * T * (5 * d + 2 * d) * 4.0):
+        _hip.check(_hip.load().odic_dynexp_seq(_p(lin), ldlin, _p(qexp), _p(bexp), _p(dec_len), _p(y_in), ldy_in,
+                                               _p(y), ldy, N, T, d, E, eps, _stream()), "odic_dynexp_seq")
+
+
+def token_stats(logits, ldl, target, logp_target, sum_logp, argmax, max_logp, status, R, V) -> None:
+    """Per logits row: log-prob of the target, Σ_v log-prob, arg-max (ties → lower index) and its log-prob."""
+    _need_cuda(logits, target, logp_target, sum_logp, argmax, max_logp, status)
+    with _timed("token_stats", 4.0 * R * V, R * V * 4.0 + R * 24.0):
+        _hip.check(_hip.load().odic_token_stats(_p(logits), ldl, _p(target), _p(logp_target), _p(sum_logp), _p(argmax),
+                                                _p(max_logp), _p(status), R, V, _stream()), "odic_token_stats")
+
+
 def cross_attn_step(q, ldq, kv, ldkv, koff, voff, enc_len, row_valid, out, ldo, N, n_img, S, d, heads) -> None:
     _need_cuda(q, kv, enc_len, row_valid, out)
     # q and out rows per sequence, K and V of the S encoder tokens ONCE per image (shared by its beams)

@@ -1,0 +1,514 @@
+"""Caption scoring on the GPU (`-m gpu`): the whole-sequence kernels against the oracle, decode_sequence / score_captions /
+caption_loss against the fixtures recorded from the reference and against the existing step-replay path, the exact
+invariances (row chunking, captions per image, call order) and containment of the three new kernels.
+
+Bounds are the ones the project already uses for the same quantities: logits / log-probs against the reference 2e-4
+(xavier) / 1e-3 (eos) as test_tiny_teacher_forced_logits, FULL log-probs 1e-3 as test_e2e_gpu, dynexp 5e-5 of the output
+scale as test_dynexp_step_matches_full_recompute, log-softmax 2e-6 as test_logsoftmax_topk."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import guards
+from conftest import GOLDEN, cached_state_dict
+from on_device_image_captioning_amd import weights as W
+
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+DEV = "cuda:0"
+TSOS, TEOS = 3, 2
+LP_BOUND = {"xavier": 2e-4, "eos": 1e-3}
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from on_device_image_captioning_amd import _hip, ops as o
+    _hip.load()
+    return o
+
+
+def rnd(*shape, seed=0, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g) * scale
+
+
+def assert_close(got, want, rtol, name=""):
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    assert got.shape == want.shape, (name, got.shape, want.shape)
+    scale = want.abs().max().item() + 1e-12
+    err = (got - want).abs().max().item()
+    print(f"{name}: max err {err:.3e}, scale {scale:.3e}")
+    assert err <= rtol * scale, f"{name}: max err {err:.3e} vs scale {scale:.3e} (rtol {rtol})"
+
+
+_MODELS = {}
+
+
+def build_model(geom, variant, precision="fp32"):
+    from on_device_image_captioning_amd.End_ExpansionNet_v2 import End_ExpansionNet_v2, make_drop_args
+    key = (geom, variant)
+    if key not in _MODELS:
+        g = getattr(W, geom)
+        m = End_ExpansionNet_v2(**g.model_kwargs(), output_word2idx={i: i for i in range(g.vocab_size)},
+                                output_idx2word=list(range(g.vocab_size)), drop_args=make_drop_args(), rank=DEV)
+        m.load_state_dict(cached_state_dict(geom, variant), strict=True)
+        _MODELS[key] = m.to(DEV).eval()
+    return _MODELS[key].set_precision(precision)
+
+
+def fixture_set(variant, name):
+    fx = np.load(os.path.join(GOLDEN, "tiny_scoring.npz"))
+    k = f"{variant}.{name}."
+    y = torch.from_numpy(fx[k + "tokens"]).long()
+    pads = [int(p) for p in fx[k + "pads"]]
+    caps = [y[i, :y.shape[1] - p].tolist() for i, p in enumerate(pads)]
+    return fx, k, y, pads, caps, int(fx[k + "per_image"])
+
+
+# ------------------------------------------------------------------------------------------------- 1. kernels
+def dynexp_case(N, T, d, E, lens, seed):
+    from oracle import expansionnet_ref as R
+    names = ["cond_embed", "key_linear", "class_a_embed", "class_b_embed", "selector_embed"]
+    sd = {}
+    for i, nm in enumerate(names):
+        sd[f"p.{nm}.weight"] = rnd(d, d, seed=seed + 10 + i, scale=d ** -0.5)
+        sd[f"p.{nm}.bias"] = rnd(d, seed=seed + 20 + i, scale=0.1)
+    sd["p.query_exp_vectors.weight"] = rnd(E, d, seed=seed + 30, scale=0.3)
+    sd["p.bias_exp_vectors.weight"] = rnd(E, d, seed=seed + 31, scale=0.3)
+    x = rnd(N, T, d, seed=seed + 40)
+    t = torch.arange(T)
+    ok = t[None, :] < torch.tensor(lens)[:, None]
+    causal = ((t[None, :, None] >= t[None, None, :]) & ok[:, :, None] & ok[:, None, :]).double()
+    sd64 = {k: v.double() for k, v in sd.items()}
+    want = R.dynamic_expansion(sd64, "p", x.double(), E, causal)                     # (N,T,d) fp64
+    Wcat = torch.cat([sd[f"p.{nm}.weight"] for nm in names], 0)
+    bcat = torch.cat([sd[f"p.{nm}.bias"] for nm in names], 0)
+    return sd, x, want, Wcat, bcat
+
+
+@pytest.mark.parametrize("N,T,d,E,lens", [
+    (4, 24, 128, 4, [24, 1, 9, 17]),                     # TINY decoder geometry, the whole pos_encoder table
+    (3, 74, 512, 16, [74, 1, 40]),                       # FULL decoder geometry, the whole pos_encoder table
+    (2, 33, 64, 8, [33, 16]), (2, 20, 192, 32, [5, 20]), (1, 128, 64, 4, [128]), (2, 16, 64, 4, [0, 16])])
+def test_dynexp_seq_matches_the_oracle(ops, N, T, d, E, lens):
+    sd, x, want, Wcat, bcat = dynexp_case(N, T, d, E, lens, seed=N + T)
+    lin = ops.gemm(x.view(N * T, d).to(DEV), Wcat.to(DEV), bcat.to(DEV), tile_cfg=3)
+    y_in = rnd(N * T, d, seed=99).to(DEV)
+    y = torch.empty_like(y_in)
+    ops.dynexp_seq(lin, 5 * d, sd["p.query_exp_vectors.weight"].to(DEV), sd["p.bias_exp_vectors.weight"].to(DEV),
+                   torch.tensor(lens, dtype=torch.int32, device=DEV), y_in, d, y, d, N, T, d, E)
+    got = (y.double() - y_in.double()).view(N, T, d)
+    assert_close(got, want, 5e-5, f"dynexp_seq T={T} d={d} E={E}")
+    t = torch.arange(T)
+    padded = t[None, :] >= torch.tensor(lens)[:, None]
+    assert torch.equal(y.view(N, T, d).cpu()[padded], y_in.view(N, T, d).cpu()[padded])     # a padded row adds exactly 0
+    # in place (y aliases y_in), as the engine's first layer calls it: the same bits
+    y2 = y_in.clone()
+    ops.dynexp_seq(lin, 5 * d, sd["p.query_exp_vectors.weight"].to(DEV), sd["p.bias_exp_vectors.weight"].to(DEV),
+                   torch.tensor(lens, dtype=torch.int32, device=DEV), y2, d, y2, d, N, T, d, E)
+    assert torch.equal(y2, y)
+
+
+def test_token_stats(ops):
+    R_, V = 9, 10000
+    x = rnd(R_, V, seed=1, scale=3.0)
+    x[2, 17] = x[2, 4000] = x[2].max() + 1.0              # an exact tie: the lower index wins
+    x[5] = 0.25                                           # an all-equal row → index 0
+    tgt = torch.randint(0, V, (R_,), generator=torch.Generator().manual_seed(2))
+    tgt[3], tgt[7] = V, -1                                # outside the vocabulary: flagged, log-prob 0
+    want = torch.log_softmax(x.double(), -1)
+    f = lambda: torch.empty(R_, device=DEV)               # noqa: E731
+    lp, sl, ml = f(), f(), f()
+    am = torch.empty(R_, dtype=torch.int32, device=DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ops.token_stats(x.to(DEV), V, tgt.to(DEV), lp, sl, am, ml, status, R_, V)
+    okr = [r for r in range(R_) if r not in (3, 7)]
+    scale = want.abs().max().item()
+    got_lp = lp.cpu().double()
+    assert float((got_lp[okr] - want[okr, tgt[okr]]).abs().max()) <= 2e-6 * scale
+    assert got_lp[3] == 0 and got_lp[7] == 0 and int(status) == 1
+    assert float((sl.cpu().double() - want.sum(-1)).abs().max()) <= 2e-6 * want.sum(-1).abs().max().item()
+    assert float((ml.cpu().double() - want.max(-1).values).abs().max()) <= 2e-6 * scale
+    order = torch.argsort(x.double(), dim=-1, descending=True, stable=True)[:, 0]
+    assert torch.equal(am.cpu().long(), order) and int(am[2]) == 17 and int(am[5]) == 0
+    # without targets: no status, the same statistics
+    sl2, ml2 = f(), f()
+    am2 = torch.empty_like(am)
+    ops.token_stats(x.to(DEV), V, None, None, sl2, am2, ml2, None, R_, V)
+    assert torch.equal(sl2, sl) and torch.equal(am2, am) and torch.equal(ml2, ml)
+    status.zero_()
+    tgt[3], tgt[7] = 0, 1
+    ops.token_stats(x.to(DEV), V, tgt.to(DEV), lp, sl, am, ml, status, R_, V)
+    assert int(status) == 0
+
+
+def test_dec_embed_seq(ops):
+    N, T, d, V = 3, 7, 128, 50
+    emb, pos = rnd(V, d, seed=1), rnd(T + 2, d, seed=2)
+    tok = torch.randint(0, V, (N, T), generator=torch.Generator().manual_seed(3))
+    tok[1, 2] = V + 5                                     # outside the table: embeds as zero
+    lens = torch.tensor([7, 1, 4], dtype=torch.int32)
+    y = torch.empty(N * T, d, device=DEV)
+    rv = torch.empty(N * T, dtype=torch.int32, device=DEV)
+    ops.dec_embed_seq(tok.to(DEV), emb.to(DEV), pos.to(DEV), y, d, N, T, d, 3.0, lens.to(DEV), rv)
+    e = emb[tok.clamp(0, V - 1)] * 3.0
+    e[1, 2] = 0
+    want = e + pos[:T][None]
+    assert_close(y.view(N, T, d), want, 1e-6, "dec_embed_seq")
+    assert torch.equal(rv.view(N, T).cpu(), (torch.arange(T)[None, :] < lens[:, None]).int())
+
+
+# ------------------------------------------------------------------------------------------------- 2. decode_sequence
+def _check_sample(store, name, t, atol, rtol=1e-4):
+    meta = store[name + ".meta"]
+    stride = int(meta[0])
+    assert list(t.shape) == [int(v) for v in meta[3:]], (name, t.shape)
+    f = t.detach().reshape(-1).double().cpu()
+    want = store[name + ".sample"]
+    err = np.abs(f[::stride].float().numpy() - want).max()
+    print(f"{name}: max err {err:.3e} (bound {atol + rtol * np.abs(want).max():.3e})")
+    assert err <= atol + rtol * np.abs(want).max(), f"{name}: max err {err:.3e}"
+    assert abs(float(f.abs().sum()) - meta[2]) <= 1e-3 * meta[2], name
+
+
+def _decode_logits(m, img, dec, pads, **kw):
+    eng = m._captioner_engine()
+    mem = m.forward_enc(img, [0] * img.shape[0])
+    N, T = dec.shape
+    dec_len = torch.tensor([T - p for p in pads], dtype=torch.int32, device=DEV)
+    return eng.decode_sequence(dec.to(DEV), dec_len, eng.project_kv(mem), m._enc_lens(img.shape[0], mem.shape[1], None),
+                               img.shape[0], **kw)
+
+
+@pytest.mark.parametrize("geom,variant", [("TINY", "xavier"), ("TINY", "eos"), ("FULL", "xavier")])
+def test_decode_sequence_logits_match_the_reference(geom, variant):
+    """tiny_*.npz record the reference's teacher-forced logits (ragged pads, padded rows included), full_xavier.npz its
+    log-probs with pads [0, 3] (full_eos.npz has no teacher-forced record)."""
+    g = getattr(W, geom)
+    store = np.load(os.path.join(GOLDEN, f"{geom.lower()}_{variant}.npz"))
+    m = build_model(geom, variant)
+    dec = torch.from_numpy(store["teacher.tokens"]).long()
+    pads = store["teacher.pads"].tolist() if geom == "TINY" else [0, 3]      # (the FULL record: test_e2e_gpu.py:205)
+    img = W.synth_images(dec.shape[0], g).to(DEV)
+    lg = _decode_logits(m, img, dec, pads, want_logits=True)
+    if geom == "TINY":
+        _check_sample(store, "teacher.logits", lg, 1e-3 if variant == "eos" else 2e-4)
+    else:
+        _check_sample(store, "teacher.logprobs", torch.log_softmax(lg, -1), 1e-3)
+
+
+# ------------------------------------------------------------------------------------------------- 3. score_captions
+@pytest.mark.parametrize("variant", ["xavier", "eos"])
+@pytest.mark.parametrize("name", ["teacher", "fresh"])
+def test_score_captions_matches_the_reference_fixture(variant, name):
+    fx, k, y, pads, caps, per = fixture_set(variant, name)
+    m = build_model("TINY", variant)
+    img = W.synth_images(3, W.TINY).to(DEV)
+    sc = m.score_captions(img, caps, captions_per_image=per)
+    Ty = y.shape[1]
+    lens = torch.tensor([Ty - 1 - p for p in pads])
+    real = torch.arange(Ty - 1)[None, :] < lens[:, None]
+    want = torch.from_numpy(fx[k + "logp_target"])
+    got = sc.logprobs.cpu()
+    err = float((got - want)[real].abs().max())
+    print(f"{variant}/{name}: log-prob max err {err:.3e}")
+    assert err <= LP_BOUND[variant]
+    assert torch.equal(got[~real], torch.zeros_like(got[~real]))
+    assert torch.equal(sc.lengths.cpu(), lens)
+    assert float((sc.sum.cpu() - torch.where(real, want, torch.zeros(())).sum(-1)).abs().max()) <= LP_BOUND[variant] * Ty
+    assert torch.allclose(sc.mean.cpu(), sc.sum.cpu() / lens.float())
+    sure = real & (torch.from_numpy(fx[k + "margin"]) > 2 * LP_BOUND[variant])
+    assert float((real & ~sure).sum()) <= 0.01 * float(real.sum())          # the cap on what the margin rule may exclude
+    assert torch.equal(sc.argmax.cpu().long()[sure], torch.from_numpy(fx[k + "argmax"]).long()[sure])
+    assert bool((sc.argmax.cpu()[~real] == -1).all())
+    # the same captions as a padded tensor with pad counts, and through the Captioner front end
+    from on_device_image_captioning_amd.End_ExpansionNet_v2 import E2E_ExpansionNet_Captioner
+    sc2 = m.score_captions(img, y, captions_per_image=per, dec_x_num_pads=pads)
+    assert torch.equal(sc2.logprobs, sc.logprobs) and torch.equal(sc2.argmax, sc.argmax)
+    cap = E2E_ExpansionNet_Captioner({"sos_idx": TSOS, "eos_idx": TEOS}, model=m)
+    assert torch.equal(cap.score_captions(img, caps, captions_per_image=per).logprobs, sc.logprobs)
+
+
+def test_score_captions_matches_the_oracle_on_fresh_full_captions():
+    """FULL decoder geometry, 2 images x 3 captions with ragged lengths (2 tokens … max_seq_len), against the CPU oracle."""
+    from oracle import expansionnet_ref as R
+    g = W.FULL
+    m = build_model("FULL", "eos")
+    sd = cached_state_dict("FULL", "eos")
+    img = W.synth_images(2, g)
+    rng = np.random.Generator(np.random.Philox(key=5))
+    lens = [2, g.max_seq_len, 12, 30, 9, 20]
+    caps = [[79] + rng.integers(4, g.vocab_size, size=n - 2).tolist() + [77] for n in lens]
+    sc = m.score_captions(img.to(DEV), caps, captions_per_image=3)
+    mem = R.forward_enc(sd, g, img, [0, 0])
+    Ty = max(lens)
+    y = torch.zeros(6, Ty, dtype=torch.long)
+    for i, c in enumerate(caps):
+        y[i, :len(c)] = torch.tensor(c)
+    lp = R.decoder_forward(sd, g, mem.repeat_interleave(3, 0), [0] * 6, y[:, :-1], [Ty - n for n in lens], True)
+    real = torch.arange(Ty - 1)[None, :] < (torch.tensor(lens) - 1)[:, None]
+    want = lp.gather(-1, y[:, 1:, None])[..., 0]
+    err = float((sc.logprobs.cpu() - want)[real].abs().max())
+    print(f"FULL fresh captions: log-prob max err {err:.3e}")
+    assert err <= 1e-3
+    top2 = lp.topk(2, -1).values
+    sure = real & ((top2[..., 0] - top2[..., 1]) > 2e-3)
+    assert float((real & ~sure).sum()) <= 0.01 * float(real.sum())
+    assert torch.equal(sc.argmax.cpu().long()[sure], lp.argmax(-1)[sure])
+
+
+# ------------------------------------------------------------------------------------------------- 4. the existing path
+@pytest.mark.parametrize("variant", ["xavier", "eos"])
+def test_score_captions_agrees_with_the_step_replay_path(variant):
+    fx, k, y, pads, caps, per = fixture_set(variant, "fresh")
+    m = build_model("TINY", variant)
+    img = W.synth_images(3, W.TINY).to(DEV)
+    sc = m.score_captions(img, caps, captions_per_image=per)
+    lp = m(enc_x=img.repeat_interleave(per, 0), dec_x=y[:, :-1].to(DEV), enc_x_num_pads=[0] * len(caps), dec_x_num_pads=pads,
+           apply_log_softmax=True, mode="forward")
+    want = lp.gather(-1, y[:, 1:, None].to(DEV))[..., 0].cpu()
+    real = torch.arange(y.shape[1] - 1)[None, :] < (y.shape[1] - 1 - torch.tensor(pads))[:, None]
+    err = float((sc.logprobs.cpu() - want)[real].abs().max())
+    print(f"{variant}: whole-sequence vs step replay, max diff {err:.3e}")
+    assert err <= 2 * LP_BOUND[variant]             # each path is within LP_BOUND of the reference
+    # padded rows of the full logits hold what the step path's hold (want_logits), to the same bound
+    lg_step = m(enc_x=img.repeat_interleave(per, 0), dec_x=y[:, :-1].to(DEV), enc_x_num_pads=[0] * len(caps),
+                dec_x_num_pads=pads, apply_log_softmax=False, mode="forward")
+    lg_seq = _decode_logits(m, img, y[:, :-1], pads, want_logits=True)
+    assert float((lg_seq - lg_step).abs().max()) <= 2 * LP_BOUND[variant] * max(1.0, float(lg_step.abs().max()))
+
+
+# ------------------------------------------------------------------------------------------------- 5. invariances, exact
+def test_scoring_invariances_are_exact():
+    fx, k, y, pads, caps, per = fixture_set("eos", "fresh")
+    m = build_model("TINY", "eos")
+    img = W.synth_images(3, W.TINY).to(DEV)
+    base = m.score_captions(img, caps, captions_per_image=per)
+    # row chunking: one 64-row block at a time / a chunk that is no multiple of anything / everything at once
+    for rc in (64, 23, 1 << 20):
+        sc = m.score_captions(img, caps, captions_per_image=per, row_chunk=rc)
+        for f in ("logprobs", "argmax", "sum_logp_vocab", "sum"):
+            assert torch.equal(getattr(sc, f), getattr(base, f)), (rc, f)
+    # captions_per_image = 2 against the same captions with one image copy each
+    one = m.score_captions(img.repeat_interleave(per, 0), caps)
+    assert torch.equal(one.logprobs, base.logprobs) and torch.equal(one.argmax, base.argmax)
+    # no state carried over: a different batch (other images, other lengths) in between
+    other = m.score_captions(img[:1], [[TSOS, 9, 10, 11, TEOS]])
+    again = m.score_captions(img, caps, captions_per_image=per)
+    assert torch.equal(again.logprobs, base.logprobs) and torch.equal(again.argmax, base.argmax)
+    assert other.logprobs.shape == (1, 4)
+    # want_logits chunked = unchunked
+    a = _decode_logits(m, img, y[:2, :-1].repeat(3, 1)[:3], [0, 0, 0], want_logits=True)
+    b = _decode_logits(m, img, y[:2, :-1].repeat(3, 1)[:3], [0, 0, 0], want_logits=True, row_chunk=7)
+    assert torch.equal(a, b)
+
+
+def test_launch_count_does_not_depend_on_the_length(ops):
+    m = build_model("TINY", "eos")
+    img = W.synth_images(2, W.TINY).to(DEV)
+    counts = []
+    for n in (5, 24):
+        caps = [[TSOS] + [7] * (n - 2) + [TEOS]] * 2
+        m.score_captions(img, caps)
+        with ops.profile() as recs:
+            m._captioner_engine()            # (engines exist already: only the decoder pass is counted below)
+            eng = m._captioner_engine()
+            mem = m.forward_enc(img, [0, 0])
+            n0 = len(recs)
+            dec = torch.tensor(caps)[:, :-1].to(DEV)
+            eng.decode_sequence(dec, torch.full((2,), n - 1, dtype=torch.int32, device=DEV), eng.project_kv(mem),
+                                m._enc_lens(2, mem.shape[1], None), 2, targets=torch.tensor(caps)[:, 1:].to(DEV))
+            counts.append(len(recs) - n0)
+    print("launches per decode_sequence call:", counts)
+    assert counts[0] == counts[1] and counts[0] <= 16 * W.TINY.N_dec + 8
+
+
+# ------------------------------------------------------------------------------------------------- 6. caption_loss
+@pytest.mark.parametrize("variant", ["xavier", "eos"])
+@pytest.mark.parametrize("name", ["teacher", "fresh"])
+def test_caption_loss_matches_the_reference(variant, name):
+    fx, k, y, pads, caps, per = fixture_set(variant, name)
+    m = build_model("TINY", variant)
+    img = W.synth_images(3, W.TINY).to(DEV).repeat_interleave(per, 0)
+    for tag, ign in (("pad", 0), ("none", -1)):
+        rec = fx[k + f"loss_ignore_{tag}"]
+        n_keep = int((y[:, 1:] != ign).sum())                         # the positions that enter the loss
+        for si, s in enumerate(fx["smoothings"].tolist()):
+            for di, divide in enumerate((False, True)):
+                got = float(m.caption_loss(img, y, [0] * y.shape[0], pads, ign, smoothing=s, divide_by_non_zeros=divide))
+                want = float(rec[si, di])
+                # a sum over the n_keep kept positions, each c·lp_t + u·Σ_v lp_v with c + (V-1)·u = 1: every log-prob within
+                # LP_BOUND; the mean divides by n_keep
+                bound = LP_BOUND[variant] * (1 if divide else n_keep) + 1e-5 * abs(want)
+                print(f"{variant}/{name} ignore={tag} s={s} divide={divide}: {got:.6f} vs {want:.6f}")
+                assert abs(got - want) <= bound, (tag, s, divide, got, want)
+
+
+# ------------------------------------------------------------------------------------------------- 7. other models / modes
+def test_features_only_model_with_ragged_encoder_pads():
+    from oracle import expansionnet_ref as R
+    from on_device_image_captioning_amd.End_ExpansionNet_v2 import make_drop_args
+    from on_device_image_captioning_amd.ExpansionNet_v2 import ExpansionNet_v2
+    g, fd = W.TINY, 64
+    sd = cached_state_dict("TINY", "eos", end_to_end=False, img_feature_dim=fd)
+    m = ExpansionNet_v2(d_model=g.d_model, N_enc=g.N_enc, N_dec=g.N_dec, ff=g.ff, num_heads=g.num_heads,
+                        num_exp_enc_list=list(g.num_exp_enc_list), num_exp_dec=g.num_exp_dec,
+                        output_word2idx={i: i for i in range(g.vocab_size)}, output_idx2word=list(range(g.vocab_size)),
+                        max_seq_len=g.max_seq_len, drop_args=make_drop_args(), img_feature_dim=fd, rank=DEV)
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    feats = W.synth_features(4, 20, fd)
+    epads = [0, 3, 7, 1]
+    rng = np.random.Generator(np.random.Philox(key=9))
+    lens = [6, 2, 24, 11, 3, 8, 15, 5]
+    caps = [[TSOS] + rng.integers(4, g.vocab_size, size=n - 2).tolist() + [TEOS] for n in lens]
+    sc = m.score_captions(feats.to(DEV), caps, epads, captions_per_image=2)
+    Ty = max(lens)
+    y = torch.zeros(8, Ty, dtype=torch.long)
+    for i, c in enumerate(caps):
+        y[i, :len(c)] = torch.tensor(c)
+    ep2 = [p for p in epads for _ in range(2)]
+    lp = R.forward_teacher(sd, g, feats.repeat_interleave(2, 0), y[:, :-1], ep2, [Ty - n for n in lens], log_softmax=True,
+                           end_to_end=False)
+    real = torch.arange(Ty - 1)[None, :] < (torch.tensor(lens) - 1)[:, None]
+    err = float((sc.logprobs.cpu() - lp.gather(-1, y[:, 1:, None])[..., 0])[real].abs().max())
+    print(f"features-only: log-prob max err {err:.3e}")
+    assert err <= 1e-3
+
+
+@pytest.mark.parametrize("precision", ["bf16", "x3"])
+def test_low_precision_encoders_give_finite_scores(precision):
+    """bf16: finite scores.  x3: scores and the encoder memory they are computed from within the x3 feature bound of
+    tests/test_x3_gpu.py (relative 2e-5 of the largest magnitude) of the fp32 mode."""
+    fx, k, y, pads, caps, per = fixture_set("eos", "fresh")
+    geom = "TINY64" if precision == "bf16" else "TINY"          # the bf16 MFMA products need K % 64 == 0 (Swin width 128)
+    m = build_model(geom, "eos")
+    img = W.synth_images(3, getattr(W, geom)).to(DEV)
+    base = m.score_captions(img, caps, captions_per_image=per)
+    try:
+        sc = build_model(geom, "eos", precision).score_captions(img, caps, captions_per_image=per)
+    finally:
+        build_model(geom, "eos", "fp32")
+    assert bool(torch.isfinite(sc.logprobs).all()) and bool(torch.isfinite(sc.sum_logp_vocab).all())
+    real = base.logprobs != 0
+    rel = float((sc.logprobs - base.logprobs)[real].abs().max() / base.logprobs[real].abs().max())
+    try:
+        mem32 = m.forward_enc(img, [0] * 3)
+        memlp = build_model(geom, "eos", precision).forward_enc(img, [0] * 3)
+    finally:
+        build_model(geom, "eos", "fp32")
+    rel_mem = float((memlp - mem32).abs().max() / mem32.abs().max())
+    print(f"{precision}: log-probs relative to fp32 {rel:.3e}, encoder memory relative to fp32 {rel_mem:.3e}")
+    if precision == "x3":
+        # the bound test_full_x3_feature_error_is_fp32_class holds the split-fp16 features to: max error / max magnitude < 2e-5
+        assert rel < 2e-5, rel
+        assert rel_mem < 2e-5, rel_mem
+
+
+# ------------------------------------------------------------------------------------------------- 8. ensemble
+def _ensemble(n):
+    from on_device_image_captioning_amd.End_ExpansionNet_v2 import End_ExpansionNet_v2, make_drop_args
+    from on_device_image_captioning_amd.ensemble_captioning_model import EsembleCaptioningModel
+    g = W.TINY
+    sds, models = [], []
+    for i in range(n):
+        sd = W.synth_state_dict(g, seed=i, variant="eos", eos_idx=TEOS)
+        mm = End_ExpansionNet_v2(**g.model_kwargs(), output_word2idx={j: j for j in range(g.vocab_size)},
+                                 output_idx2word=list(range(g.vocab_size)), drop_args=make_drop_args(), rank=DEV)
+        mm.load_state_dict(sd, strict=True)
+        sds.append(sd)
+        models.append(mm.to(DEV).eval())
+    return EsembleCaptioningModel(models, rank=DEV).to(DEV), sds
+
+
+@pytest.mark.parametrize("members", [2, 3])
+def test_ensemble_score_captions_matches_the_oracle(members):
+    from oracle import expansionnet_ref as R
+    g = W.TINY
+    ens, sds = _ensemble(members)
+    fx, k, y, pads, caps, per = fixture_set("eos", "fresh")
+    img = W.synth_images(3, g)
+    sc = ens.score_captions(img.to(DEV), caps, captions_per_image=per)
+    enc = img.repeat_interleave(per, 0)
+    probs = [torch.softmax(R.forward_teacher(sd, g, enc, y[:, :-1], [0] * len(caps), pads), -1) for sd in sds]
+    lp = torch.stack(probs).mean(0).log()
+    real = torch.arange(y.shape[1] - 1)[None, :] < (y.shape[1] - 1 - torch.tensor(pads))[:, None]
+    err = float((sc.logprobs.cpu() - lp.gather(-1, y[:, 1:, None])[..., 0])[real].abs().max())
+    print(f"ensemble of {members}: log-prob max err {err:.3e}")
+    assert err <= 1e-3
+
+
+def test_ensemble_sampled_search_scores_equal_score_captions():
+    g = W.TINY
+    ens, _ = _ensemble(2)
+    img = W.synth_images(8, g).to(DEV)
+    kw = dict(enc_x=img, enc_x_num_pads=[0] * 8, mode="beam_search", beam_size=3, how_many_outputs=2, beam_max_seq_len=12,
+              sample_or_max="sample", sos_idx=TSOS, eos_idx=TEOS)
+    lead = ens.models_list[0]
+    lead.sampling_seed, lead._sampling_calls = 5, 0
+    toks, lps = ens(**kw)
+    assert len(toks) == 8 and all(len(per) == 2 for per in toks)
+    caps = [c for per in toks for c in per]
+    sc = ens.score_captions(img, caps, captions_per_image=2)
+    for n, c in enumerate(caps):
+        got = lps.view(16, -1)[n, 1:len(c)].cpu()
+        assert float((got - sc.logprobs[n, :len(c) - 1].cpu()).abs().max()) <= 2e-3, n
+    lead.sampling_seed, lead._sampling_calls = 5, 0
+    toks2, _ = ens(**kw)
+    assert toks2 == toks                                   # same seed → same captions
+    lead.sampling_seed, lead._sampling_calls = 6, 0
+    toks3, _ = ens(**kw)
+    assert toks3 != toks                                   # a different seed → at least one different caption
+    with pytest.raises(AssertionError):
+        ens(**dict(kw, how_many_outputs=4))
+
+
+# ------------------------------------------------------------------------------------------------- 9. containment
+def test_sequence_kernels_stay_inside_their_operands(ops):
+    N, T, d, E, V = 3, 11, 64, 4, 300
+    lens = torch.tensor([11, 1, 6], dtype=torch.int32, device=DEV)
+    # dec_embed_seq: y with a padded leading dimension
+    emb, pos = rnd(V, d, seed=1).to(DEV), rnd(T, d, seed=2).to(DEV)
+    tok = torch.randint(0, V, (N, T), generator=torch.Generator().manual_seed(3)).to(DEV)
+    y_c = torch.empty(N * T, d, device=DEV)
+    rv_c = torch.empty(N * T, dtype=torch.int32, device=DEV)
+    ops.dec_embed_seq(tok, emb, pos, y_c, d, N, T, d, 2.0, lens, rv_c)
+    y_g = guards.guarded(N * T, d, d + 24, torch.float32, DEV)
+    rv_g = guards.guarded(1, N * T, N * T, torch.int32, DEV)
+    ops.dec_embed_seq(tok, emb, pos, y_g.t, d + 24, N, T, d, 2.0, lens, rv_g.t)
+    y_g.assert_untouched(what="dec_embed_seq y")
+    rv_g.assert_untouched(what="dec_embed_seq row_valid")
+    assert torch.equal(y_g.t[:, :d], y_c) and torch.equal(rv_g.t.view(-1), rv_c)
+    # dynexp_seq: poisoned lin / y_in padding, guarded y
+    lin = rnd(N * T, 5 * d, seed=4)
+    qe, be = rnd(E, d, seed=5, scale=0.3).to(DEV), rnd(E, d, seed=6, scale=0.3).to(DEV)
+    yin = rnd(N * T, d, seed=7)
+    out_c = torch.empty(N * T, d, device=DEV)
+    ops.dynexp_seq(lin.to(DEV), 5 * d, qe, be, lens, yin.to(DEV), d, out_c, d, N, T, d, E)
+    lin_g = guards.poisoned_input(lin, N * T, 5 * d, 5 * d + 8, device=DEV)
+    yin_g = guards.poisoned_input(yin, N * T, d, d + 12, device=DEV)
+    out_g = guards.guarded(N * T, d, d + 20, torch.float32, DEV)
+    ops.dynexp_seq(lin_g.t, 5 * d + 8, qe, be, lens, yin_g.t, d + 12, out_g.t, d + 20, N, T, d, E)
+    out_g.assert_untouched(what="dynexp_seq y")
+    assert bool(torch.isfinite(out_g.t[:, :d]).all()) and torch.equal(out_g.t[:, :d], out_c)
+    # token_stats: poisoned logits padding, guarded compact outputs
+    R_ = 13
+    x = rnd(R_, V, seed=8, scale=2.0)
+    tg = torch.randint(0, V, (R_,), generator=torch.Generator().manual_seed(9)).to(DEV)
+    outs_c = [torch.empty(R_, device=DEV) for _ in range(3)]
+    am_c = torch.empty(R_, dtype=torch.int32, device=DEV)
+    st = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ops.token_stats(x.to(DEV), V, tg, outs_c[0], outs_c[1], am_c, outs_c[2], st, R_, V)
+    x_g = guards.poisoned_input(x, R_, V, V + 9, device=DEV)
+    outs_g = [guards.guarded(1, R_, R_, torch.float32, DEV) for _ in range(3)]
+    am_g = guards.guarded(1, R_, R_, torch.int32, DEV)
+    ops.token_stats(x_g.t, V + 9, tg, outs_g[0].t, outs_g[1].t, am_g.t, outs_g[2].t, st, R_, V)
+    for gbuf, c, nm in zip(outs_g + [am_g], outs_c + [am_c], ("logp_target", "sum_logp", "max_logp", "argmax")):
+        gbuf.assert_untouched(what="token_stats " + nm)
+        assert torch.equal(gbuf.t.view(-1), c), nm
+    assert int(st) == 0
