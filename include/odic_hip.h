@@ -68,8 +68,7 @@ const char* odic_build_info(void);
  *   there and read them as the K padding of a later product.  Nothing is read from A / a_ln / W columns [K, ld), rows
  *   >= M / >= N, residual columns [N, ldr), or past the N (M) entries of bias / col_scale / ln_colsum
  *   (test_gemm_f32_folded_layernorm_reads_exactly_n_column_sums): those bytes may hold anything, NaN included.  A refused
- *   launch writes nothing.  (`out16` / `stats_out` exist in -DODIC_EXPERIMENTAL_GEMM builds only; their padding is pinned by
- *   no test of the default build.)
+ *   launch writes nothing.
  * Replaces every nn.Linear on the path: swin_transformer_mod.py:190,212 (qkv/proj), :94-97
  * (Mlp fc1/fc2), :396 (PatchMerging.reduction), layers.py:49-51,99,154-161,274-276,293,306-307,
  * End_ExpansionNet_v2.py:82,97,134,137.
@@ -96,8 +95,7 @@ typedef struct odic_gemm_args {
   int32_t out_dtype;  /* dtype of out */
   int32_t tile_cfg;   /* tile configuration, -1 = built-in choice.  bf16 (csrc/gemm_bf16.hip): 0, 1, 2, 7, 10 power-of-two tiles,
                        * 40..47 tiles of 48 x 96 wave patches (144 / 288 rows), 48 / 49 64 x 64, 50..53 the A-resident streaming
-                       * kernels for K = 192 / 384 (whole tiles only; the only ones that take `a_ln`); 3..33 further variants in
-                       * -DODIC_EXPERIMENTAL_GEMM builds (16 + c = config c as a persistent launch: needs `workspace`, batch == 1).
+                       * kernels for K = 192 / 384 (whole tiles only; the only ones that take `a_ln`); every other value is refused.
                        * fp8 / fp16 (gemm_lowp.hip): 0..4, 5..9 = the same on the block-scaled fp8 MFMA.  split fp16 (gemm_x3.hip):
                        * 0..9, 20 / 21 the A-resident kernels for K = 192.  An unsupported (shape, configuration) pair is refused. */
   /* Optional LayerNorm of the A operand, folded (fp32 skinny-M path only: M <= 192, K % 16 == 0,
@@ -109,21 +107,13 @@ typedef struct odic_gemm_args {
    * Replaces the separate norm_1/2/3 + dec_reduce_norm launches of the decoder step
    * (layers.py:225,228,232; End_ExpansionNet_v2.py:135).  NULL = plain GEMM. */
   const float* ln_colsum; float ln_eps;
-  /* bf16 persistent tile configurations only: 16 int32 of device memory, all zero when the launch starts;
-   * the kernel leaves them zero again, so ONE buffer serves every launch of a stream (launches of different
-   * streams that may overlap need their own).  NULL otherwise. */
+  /* Reserved (kept for the layout): pass NULL.  Ignored. */
   int32_t* workspace;
   /* fp8 / fp16 inputs only: per-output-column dequantisation factor (fp32 [N], NULL = 1) and the factor applied
    * before the output cast (0 = 1; 1/scale of the consumer's fp8 operand). */
   const float* col_scale; float out_scale;
-  /* LayerNorm folded across two bf16 products (one-block-per-tile tile configurations 0..11, batch == 1) — removes
-   * the separate norm1 / norm2 launches of a Swin block (swin_transformer_mod.py:309,338) and their fp32 re-read
-   * of the residual stream:
-   *   producer (out_dtype ODIC_F32, e.g. the proj / fc2 product with the residual added): out16 (bf16 [M,N], ld16)
-   *     receives the rounded copy of `out`; stats_out (fp32 [M, N/32, 2]) receives, per row and 32-column group, the
-   *     mean and the centred sum of squares of those bf16 values.  N % 32 == 0.
-   *   consumer (A = that bf16 copy): ln_stats = the producer's stats_out (K/32 groups per row), ln_colsum and the
-   *     packed W / bias as for the fp32 form above; out = act(rstd·(alpha·A·W'ᵀ − mean·ln_colsum) + bias') + residual. */
+  /* Reserved (kept for the layout): pass NULL / 0.  A non-NULL out16, stats_out or ln_stats is refused with
+   * ODIC_EUNSUPPORTED before anything is launched. */
   void* out16; int64_t ld16; float* stats_out;
   const float* ln_stats;
   /* LayerNorm of the A operand computed while A is read (A-resident tile configurations only: bf16 50-53, split fp16 20 / 21 — the

@@ -10,15 +10,12 @@ int odic_gemm_x3_launch(const odic_gemm_args* a, hipStream_t stream);
 extern "C" int odic_abi_version(void) { return ODIC_ABI_VERSION; }
 
 extern "C" const char* odic_build_info(void) {
-#ifdef ODIC_EXPERIMENTAL_GEMM
-  return "libodic_hip gfx950 (CDNA4) experimental-gemm " __DATE__ " " __TIME__ " hipcc " __clang_version__;
-#else
   return "libodic_hip gfx950 (CDNA4) " __DATE__ " " __TIME__ " hipcc " __clang_version__;
-#endif
 }
 
 extern "C" int odic_gemm(const odic_gemm_args* a, void* stream) {
   if (!a || !a->W || !a->out) return ODIC_ENULL;
+  if (a->out16 || a->stats_out || a->ln_stats) return ODIC_EUNSUPPORTED;   // reserved fields: no kernel family takes them
   if (a->a_ln) {                           // LayerNorm-while-reading form: bf16 W, no A, whole fp32 rows of K elements
     if (a->A || (a->in_dtype != ODIC_BF16 && a->in_dtype != ODIC_H2) || a->ld_aln < a->K || a->batch != 1) return ODIC_EINVAL;
   } else if (!a->A) {

@@ -40,16 +40,7 @@ struct Params {
   float alpha; int act; int bias_axis;
   int tiles_m, tiles_n;
   int pm, pn;          // XCD partition of the tile grid, pm * pn == 8
-  int* ws;             // persistent kernels: 8 per-partition tile counters + 1 exit counter (all zero at launch)
-  // LayerNorm folded across two products (one-block-per-tile kernel only):
-  //   producer (fp32 out): also writes the bf16 copy of its output rows and, per row and 32-column group, the
-  //                        mean and centred sum of squares of those bf16 values;
-  //   consumer: A is that bf16 copy; row moments are combined from the K/32 groups and the epilogue computes
-  //             rstd·(A·W'ᵀ − mean·colsum) + bias' = LayerNorm(A)·Wᵀ + bias (W', colsum, bias' packed by the caller).
-  bf16_raw* out16; long ld16; float* stats_out;
-  const float* ln_stats; const float* ln_colsum; float ln_eps;
-  int skew_from, skew_to, skew_sleeps;   // blocks [skew_from, skew_to) start skew_sleeps x 64·127 clocks late
-  const float* a_ln; long ld_aln;        // A-resident kernels: fp32 rows whose LayerNorm (no affine) is the A operand
+  const float* a_ln; long ld_aln; float ln_eps;   // A-resident kernels: fp32 rows whose LayerNorm (no affine) is the A operand
 };
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -70,8 +61,6 @@ __device__ __forceinline__ int wperm(int r) {
   return (r & ~31) + 8 * ((r & 15) >> 2) + 4 * ((r >> 4) & 1) + (r & 3);
 }
 
-// LNF: 0 plain, 1 producer of a folded LayerNorm (fp32 out + bf16 copy + row-group moments), 2 consumer
-// (separate instantiations: the extra registers of the fold must not cost the plain products their occupancy)
 // (second launch bound: the 4-wave blocks with 128 accumulator registers per lane must stay within 256 registers
 //  so that two of them share a CU — left alone hipcc takes 158 + 128)
 // KS = 2: TWO groups of NWM x NWN waves share the tile and its LDS stages; group g takes the 32-deep half g of every 64-deep
@@ -79,9 +68,9 @@ __device__ __forceinline__ int wperm(int r) {
 // additions: deterministic, but not the summation order of the KS = 1 form).  For the tiles whose wave count does not fill
 // four SIMDs evenly — 144 x 192 is six waves, the exact-round tile of the 9216 x 768 products — this gives every SIMD three
 // waves.  Only group 0 stages (its vmcnt waits precede the barrier both groups meet at) and only group 0 stores.
-template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK, typename OutT, int LNF = 0, int KS = 1>
+template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK, typename OutT, int KS = 1>
 __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * NI == 32) ? 2 : 1) void gemm_bf16_nt_kernel(Params p) {
-  static_assert(KS == 1 || (KS == 2 && BK == 64 && LNF == 0), "the K-split form is two groups on 64-deep K-tiles");
+  static_assert(KS == 1 || (KS == 2 && BK == 64), "the K-split form is two groups on 64-deep K-tiles");
   constexpr int NW = NWM * NWN;
   constexpr int ROWB = BK * 2;                 // bytes per LDS row
   constexpr int RPI = 1024 / ROWB;             // rows per 1-KiB DMA instruction
@@ -100,9 +89,6 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
   const int wave = KS == 1 ? (tid >> 6) : __builtin_amdgcn_readfirstlane((tid >> 6) % NW);
   const int wm = wave / NWN, wn = wave % NWN;
   ODIC_ENCODE_PRIO();
-  if ((int)blockIdx.x >= p.skew_from && (int)blockIdx.x < p.skew_to)
-    for (int i = 0; i < p.skew_sleeps; ++i) __builtin_amdgcn_s_sleep(127);
-
 
   // XCD x = blockIdx % 8 owns tile rows [r0,r1) x cols [c0,c1); inside the rectangle tiles run N-fastest
   int tm, tn;
@@ -166,38 +152,6 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
   for (int t = 0; t < D; ++t)
     if (t < nk) stage(t, t);
 
-  // folded LayerNorm, consumer side: (mean, rstd) of this tile's BM rows of A from the per-32-column-group
-  // moments its producer left (Chan's combination of equal-sized groups) → LDS tail, read in the epilogue.
-  // Four lanes per row, each with a quarter of the K/32 groups in registers (all loads issued before the first
-  // use: a dependent load per group would cost more than the tile's whole K-loop).
-  float2* s_stat = (float2*)(lds + NSTAGE * STAGE);
-  if constexpr (LNF == 2) {
-    const int ng = p.K >> 5;                                      // groups per row (<= 48); lane q takes q, q+4, ...
-    for (int t = tid; t < 4 * BM; t += 64 * NW) {
-      const int r = t >> 2, q = t & 3;
-      const int row = min(m0 + r, p.M - 1);
-      const float2* st = (const float2*)p.ln_stats + (long)row * ng + q;
-      float2 gv[12];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) gv[i] = q + 4 * i < ng ? st[4 * i] : make_float2(0.f, 0.f);
-      float msum = 0.f;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) msum += gv[i].x;
-      msum += __shfl_xor(msum, 1, 64);
-      msum += __shfl_xor(msum, 2, 64);
-      const float mean = msum / (float)ng;
-      float m2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        const float d = gv[i].x - mean;
-        m2 += q + 4 * i < ng ? gv[i].y + 32.0f * d * d : 0.f;
-      }
-      m2 += __shfl_xor(m2, 1, 64);
-      m2 += __shfl_xor(m2, 2, 64);
-      if (q == 0) s_stat[r] = make_float2(mean, rsqrtf(m2 / (float)p.K + p.ln_eps));
-    }
-  }
-
   for (int kt = 0; kt < nk; ++kt) {
     const int ahead = min(D - 1, nk - 1 - kt);
     if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
@@ -251,7 +205,7 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
   OutT* out = (OutT*)p.out + bz * p.strideC;
   const bool ld_ok = ((p.ldc & 7) == 0) && (!resid || (p.ldr & 3) == 0) &&
                      ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  if constexpr (sizeof(OutT) == 2 && LNF == 0 && NI % 4 == 0) {
+  if constexpr (sizeof(OutT) == 2 && NI % 4 == 0) {
     // bf16 output in WHOLE 128-byte lines.  A lane's 8 columns are 16 bytes, the four fq lanes of a row 64 contiguous
     // bytes: half a line per row and store instruction, and half-line stores run at 4 TB/s where whole lines run at
     // 6.8 (tools/smallk_probe.py).  The line's other half is the same lanes' NEXT column group: the two groups are
@@ -311,7 +265,7 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
       return;
     }
   }
-  if constexpr (LNF == 0 && !(sizeof(OutT) == 2 && NI % 4 == 0)) {   // (bf16 with NI % 4 == 0: whole-line path above, or the plain loop below)
+  if constexpr (!(sizeof(OutT) == 2 && NI % 4 == 0)) {   // (bf16 with NI % 4 == 0: whole-line path above, or the plain loop below)
     // The general vector path.  vmcnt retires in order and counts stores, so ANY load between two groups of stores
     // waits for every store before it: a bias or residual load per column group turned the epilogue into a chain of
     // memory round trips (9 per 144 x 192 tile; the "+16-20 us for the fp32 residual form" of DESIGN.md §4.1).  Here
@@ -416,27 +370,18 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
   for (int nq = 0; nq < NI / 2; ++nq) {
     const int col = n0 + wn * NI * 16 + nq * 32 + fq * 8;
     if (col >= p.N) continue;
-    float bc[8], cs[8];
+    float bc[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      bc[e] = (bias && !p.bias_axis && col + e < p.N) ? bias[col + e] : 0.f;
-      cs[e] = (LNF == 2 && col + e < p.N) ? p.ln_colsum[col + e] : 0.f;
-    }
+    for (int e = 0; e < 8; ++e) bc[e] = (bias && !p.bias_axis && col + e < p.N) ? bias[col + e] : 0.f;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      const int rloc = (wm * MI + mi) * 16 + frow;
-      const int row = m0 + rloc;
+      const int row = m0 + (wm * MI + mi) * 16 + frow;
       if (row >= p.M) continue;
       const float brow = (bias && p.bias_axis) ? bias[row] : 0.f;
-      float2 mr = make_float2(0.f, 1.f);
-      if constexpr (LNF == 2) mr = s_stat[rloc];
       f32x4_t v[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        f32x4_t lin = acc[mi][2 * nq + h] * p.alpha;
-        if constexpr (LNF == 2)
-          lin = (lin - f32x4_t{cs[4 * h], cs[4 * h + 1], cs[4 * h + 2], cs[4 * h + 3]} * mr.x) * mr.y;
-        f32x4_t pre = lin + f32x4_t{bc[4 * h], bc[4 * h + 1], bc[4 * h + 2], bc[4 * h + 3]} + brow;
+        f32x4_t pre = acc[mi][2 * nq + h] * p.alpha + f32x4_t{bc[4 * h], bc[4 * h + 1], bc[4 * h + 2], bc[4 * h + 3]} + brow;
         if (p.act == ODIC_ACT_GELU) {
           pre = gelu_poly4(pre);
         } else if (p.act != ODIC_ACT_NONE) {
@@ -453,29 +398,6 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
         OutT* dst = out + (long)row * p.ldc + col;
         if constexpr (sizeof(OutT) == 4) {
           ((f32x4_t*)dst)[0] = v[0]; ((f32x4_t*)dst)[1] = v[1];
-          if constexpr (LNF == 1) {
-            // folded LayerNorm, producer side: the bf16 copy the next product reads as its A operand, and the
-            // moments of THOSE bf16 values over this row's 32-column group (the 4 fq lanes of a row hold it)
-            bf16x8_t pk;
-            float a8[8], sum = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const bf16_raw hb = f32_to_bf16(v[e >> 2][e & 3]);
-              pk[e] = (short)hb;
-              a8[e] = bf16_to_f32(hb);
-              sum += a8[e];
-            }
-            *(bf16x8_t*)(p.out16 + (long)row * p.ld16 + col) = pk;
-            sum += __shfl_xor(sum, 16, 64);
-            sum += __shfl_xor(sum, 32, 64);
-            const float gmean = sum * (1.0f / 32.0f);
-            float m2 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float d = a8[e] - gmean; m2 += d * d; }
-            m2 += __shfl_xor(m2, 16, 64);
-            m2 += __shfl_xor(m2, 32, 64);
-            if (fq == 0) ((float2*)p.stats_out)[(long)row * (p.N >> 5) + (col >> 5)] = make_float2(gmean, m2);
-          }
         } else {
           bf16x8_t pk;
 #pragma unroll
@@ -495,512 +417,6 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
     }
   }
 }
-
-
-
-#ifdef ODIC_EXPERIMENTAL_GEMM   // persistent and 256x256 phase-pipelined kernels: measured, never selected
-// One K-tile of LDS-DMA for the persistent kernel: `buffer_load ... lds` with the tile origins in scalar resource
-// descriptors, per-lane 32-bit offsets and the K advance as the scalar offset.  (A free function: a local of the
-// buffer-resource type inside a lambda of a __global__ template suppresses the kernel's host stub on ROCm 7.2.)
-template <int A_INSTR, int W_INSTR, int NW>
-__device__ __forceinline__ void persist_stage(char* la, int a_bytes, const bf16_raw* a_base, const bf16_raw* w_base,
-                                              const int* voff_a, const int* voff_w, int wave, int koff) {
-  char* lw = la + a_bytes;
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-  for (int i = 0; i < A_INSTR; ++i)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lptr_t)(la + (i * NW + wave) * 1024), 16, voff_a[i], koff, 0, 0);
-#pragma unroll
-  for (int i = 0; i < W_INSTR; ++i)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lptr_t)(lw + (i * NW + wave) * 1024), 16, voff_w[i], koff, 0, 0);
-}
-
-// =================================================================================================
-// Persistent, dynamically scheduled form of the generic kernel (tile_cfg 16 + c runs tile config c this way).
-//
-// Why: a Swin-L product is 100..1700 tiles on 256 CUs x (1..3 resident blocks), i.e. 1-3 "rounds" with a ragged
-// last one, and beside the decoder-step kernels of the other HIP streams some CUs are slower than others — with
-// one block per tile the launch ends with its slowest CU (the straggler effect).  Here a launch is
-// only as many blocks as fit the chip; every block pulls tiles from per-XCD-partition atomic counters until the
-// product is done, so a slowed CU simply takes fewer tiles, and a partition that runs dry steals from the next.
-//   * tile order inside a partition is unchanged (N-fastest inside the XCD's rectangle → its W sub-panel stays in
-//     the XCD's L2 and an A panel is consumed by all its column tiles while resident);
-//   * the NEXT tile's ticket is drawn (one returning atomic by one lane) right after the current tile's first
-//     K-tiles have been requested and is only looked at after the K-loop, so its latency costs nothing;
-//     (vmcnt retires in order and counts stores, so a tile's first K-tile cannot be consumed before the previous
-//     epilogue's stores are acknowledged: requesting it ahead of the epilogue buys nothing inside one wave —
-//     prologue and store tail overlap across the 2-3 resident blocks of a CU instead);
-//   * LDS-DMA as `buffer_load ... lds`: the tile's base sits in a scalar resource descriptor, the per-lane part
-//     is a 32-bit offset computed once per tile and the K advance is the scalar offset — no 64-bit address
-//     arithmetic per issue.
-// Workspace protocol: ws[0..7] tile counters, ws[8] exit counter; the caller hands zeros, the last block to
-// leave zeroes them again (kernel boundary = release), so one workspace serves all launches of a stream.
-// Blocks never wait for each other: no residency requirement, nothing can hang.
-// =================================================================================================
-template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK, typename OutT>
-__global__ __launch_bounds__(64 * NWM * NWN) void gemm_bf16_nt_persist_kernel(Params p) {
-  constexpr int NW = NWM * NWN;
-  constexpr int ROWB = BK * 2;
-  constexpr int RPI = 1024 / ROWB;
-  constexpr int CPR = ROWB / 16;
-  constexpr int BM = NWM * MI * 16, BN = NWN * NI * 16;
-  constexpr int A_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2, STAGE = A_BYTES + W_BYTES;
-  constexpr int A_INSTR = BM / RPI / NW, W_INSTR = BN / RPI / NW;
-  static_assert(BM % (RPI * NW) == 0 && BN % (RPI * NW) == 0, "tile rows must split evenly over the waves");
-  constexpr int G = A_INSTR + W_INSTR;
-  static_assert(NI % 2 == 0, "the epilogue pairs MFMA column tiles");
-  constexpr int D = NSTAGE - 1;
-  extern __shared__ __attribute__((aligned(16))) char lds[];          // stages | int slot[2] (next-tile mailbox)
-  typedef __attribute__((address_space(3))) int lds_int;
-  lds_int* slot = (lds_int*)(lds + NSTAGE * STAGE);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / NWN, wn = wave % NWN;
-  ODIC_ENCODE_PRIO();
-
-  // ---- tile source.  Partition `part` of the tile grid (the XCD rectangles of the one-block-per-tile kernel)
-  //      has its own counter; a block starts on partition blockIdx % 8 and moves on when that one runs dry.
-  const int xcd = blockIdx.x & 7;
-  int dry = 0;                                                        // partitions this block has seen exhausted
-  int p_r0 = 0, p_c0 = 0, p_w = 1, p_size = 0;                        // rectangle of the current partition
-  auto load_part = [&]() {
-    const int part = (xcd + dry) & 7;
-    const int xm = part / p.pn, xn = part - xm * p.pn;
-    const int r1 = (xm + 1) * p.tiles_m / p.pm, c1 = (xn + 1) * p.tiles_n / p.pn;
-    p_r0 = xm * p.tiles_m / p.pm; p_c0 = xn * p.tiles_n / p.pn;
-    p_w = c1 - p_c0; p_size = (r1 - p_r0) * p_w;
-  };
-  auto decode = [&](int idx) -> int {
-    const int lr = idx / p_w;
-    return ((p_r0 + lr) << 16) | (p_c0 + idx - lr * p_w);
-  };
-  auto draw = [&]() -> int {                                          // returning atomic, result not waited for here
-    return __hip_atomic_fetch_add(p.ws + ((xcd + dry) & 7), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  // ticket → tile; run by ALL lanes of wave 0 with the ticket in lane 0.  When the partition is dry, lanes 0..7 read
-  // the eight counters in ONE wave instruction (past the L1) and the partition with the most tiles left is taken;
-  // nothing left anywhere → -1.  (Eight dependent loads by one lane cost more than the tile itself.)
-  auto resolve = [&](int ticket_lane0) -> int {
-    int idx = __builtin_amdgcn_readfirstlane(ticket_lane0);
-    while (idx >= p_size) {
-      const int i = lane & 7;
-      const int xm = i / p.pn, xn = i - xm * p.pn;
-      const int sz = ((xm + 1) * p.tiles_m / p.pm - xm * p.tiles_m / p.pm) *
-                     ((xn + 1) * p.tiles_n / p.pn - xn * p.tiles_n / p.pn);
-      int key = ((sz - __hip_atomic_load(p.ws + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) << 3) | i;
-#pragma unroll
-      for (int o = 4; o > 0; o >>= 1) key = max(key, __shfl_xor(key, o, 64));      // lanes 0..7 hold the 8 partitions
-      key = __builtin_amdgcn_readfirstlane(key);
-      if ((key >> 3) <= 0) return -1;
-      dry = ((key & 7) - xcd) & 7;
-      load_part();
-      int t = 0;
-      if (lane == 0) t = draw();
-      idx = __builtin_amdgcn_readfirstlane(t);
-    }
-    return decode(idx);
-  };
-  load_part();
-
-  const int srow = lane / CPR;
-  const int schunk = swz<BK>(lane % CPR, srow);
-  const int frow = lane & 15, fq = lane >> 4;
-  const int nk = p.K / BK;
-  const bf16_raw* A = p.A;
-  const bf16_raw* W = p.W;
-
-  int m0 = 0, n0 = 0;
-  const bf16_raw* a_base = A;                                          // tile origins (wave-uniform)
-  const bf16_raw* w_base = W;
-  int voff_a[A_INSTR], voff_w[W_INSTR];
-  auto setup = [&](int tile) {                                         // tile is wave-uniform (SGPR)
-    m0 = (tile >> 16) * BM; n0 = (tile & 0xffff) * BN;
-    a_base = A + (long)m0 * p.lda;
-    w_base = W + (long)n0 * p.ldw;
-#pragma unroll
-    for (int i = 0; i < A_INSTR; ++i) {
-      const int row = (i * NW + wave) * RPI + srow;
-      voff_a[i] = (min(m0 + row, p.M - 1) - m0) * (int)p.lda * 2 + schunk * 16;
-    }
-#pragma unroll
-    for (int i = 0; i < W_INSTR; ++i) {
-      const int row = (i * NW + wave) * RPI + srow;
-      voff_w[i] = (min(n0 + wperm(row), p.N - 1) - n0) * (int)p.ldw * 2 + schunk * 16;
-    }
-  };
-  auto stage = [&](int buf, int kt) {
-    persist_stage<A_INSTR, W_INSTR, NW>(lds + buf * STAGE, A_BYTES, a_base, w_base, voff_a, voff_w, wave, kt * ROWB);
-  };
-
-  // ---- first tile
-  if (wave == 0) {
-    int t = 0;
-    if (lane == 0) t = draw();
-    const int first = resolve(t);
-    if (lane == 0) slot[0] = first;
-  }
-  __syncthreads();
-  int tile = __builtin_amdgcn_readfirstlane(slot[0]);
-  const float* bias = p.bias;
-  const float* resid = p.residual;
-  OutT* out = (OutT*)p.out;
-  const bool ld_ok = ((p.ldc & 7) == 0) && (!resid || (p.ldr & 3) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-
-  for (int it = 0; tile >= 0; ++it) {
-    setup(tile);
-#pragma unroll
-    for (int t = 0; t < D; ++t)
-      if (t < nk) stage(t, t);
-    // ticket for the NEXT tile: issued now, looked at after the K-loop (its latency hides behind the whole tile;
-    // it is younger than this tile's first DMA groups, so the counted waits below at most over-wait by one)
-    int ticket = 0;
-    if (tid == 0) ticket = draw();
-
-    f32x4_t acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    for (int kt = 0; kt < nk; ++kt) {
-      // (the previous tile's epilogue stores are OLDER than this tile's DMA: a counted wait covers them too)
-      const int ahead = min(D - 1, nk - 1 - kt);
-      if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
-      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (kt + D < nk) stage((kt + D) % NSTAGE, kt + D);
-
-      const int cur = kt % NSTAGE;
-      const char* la = lds + cur * STAGE + (wm * MI * 16 + frow) * ROWB;
-      const char* lw = lds + cur * STAGE + A_BYTES + (wn * NI * 16 + frow) * ROWB;
-#pragma unroll
-      for (int kk = 0; kk < BK / 32; ++kk) {
-        bf16x8_t af[MI], wf[NI];
-        const int chunk = swz<BK>(kk * 4 + fq, frow) << 4;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) af[mi] = *(const bf16x8_t*)(la + mi * 16 * ROWB + chunk);
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) wf[ni] = *(const bf16x8_t*)(lw + ni * 16 * ROWB + chunk);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni], af[mi], acc[mi][ni], 0, 0, 0);
-      }
-    }
-    // next tile: resolve the ticket (steals only at the very end of a launch), hand it to the other waves.
-    // slot[] alternates, so a fast wave 0 cannot overwrite a value a slow wave has not read yet.
-    if (wave == 0) {
-      const int nx = resolve(ticket);
-      if (lane == 0) slot[(it + 1) & 1] = nx;
-    }
-
-    // ---- epilogue (lane → 8 adjacent output columns, as in the generic kernel)
-#pragma unroll
-    for (int nq = 0; nq < NI / 2; ++nq) {
-      const int col = n0 + wn * NI * 16 + nq * 32 + fq * 8;
-      if (col >= p.N) continue;
-      float bc[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) bc[e] = (bias && !p.bias_axis && col + e < p.N) ? bias[col + e] : 0.f;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        const int row = m0 + (wm * MI + mi) * 16 + frow;
-        if (row >= p.M) continue;
-        const float brow = (bias && p.bias_axis) ? bias[row] : 0.f;
-        f32x4_t v[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          f32x4_t pre = acc[mi][2 * nq + h] * p.alpha + f32x4_t{bc[4 * h], bc[4 * h + 1], bc[4 * h + 2], bc[4 * h + 3]} + brow;
-          if (p.act == ODIC_ACT_GELU) {
-            pre = gelu_poly4(pre);
-          } else if (p.act != ODIC_ACT_NONE) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pre[e] = apply_act<true>(pre[e], p.act);
-          }
-          v[h] = pre;
-        }
-        if (ld_ok && col + 7 < p.N) {
-          if (resid) {
-            const f32x4_t* rp = (const f32x4_t*)(resid + (long)row * p.ldr + col);
-            v[0] += rp[0]; v[1] += rp[1];
-          }
-          OutT* dst = out + (long)row * p.ldc + col;
-          if constexpr (sizeof(OutT) == 4) {
-            ((f32x4_t*)dst)[0] = v[0]; ((f32x4_t*)dst)[1] = v[1];
-          } else {
-            bf16x8_t pk;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { pk[e] = (short)f32_to_bf16(v[0][e]); pk[4 + e] = (short)f32_to_bf16(v[1][e]); }
-            *(bf16x8_t*)dst = pk;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            if (col + e < p.N) {
-              float x = v[e >> 2][e & 3];
-              if (resid) x += resid[(long)row * p.ldr + col + e];
-              store_from_f32<OutT>(out + (long)row * p.ldc + col + e, x);
-            }
-          }
-        }
-      }
-    }
-    // every wave has finished reading this tile's LDS stages (its last ds_reads fed the MFMAs above) and wave
-    // 0's mailbox write has landed: one barrier, then the stages may be refilled.  (A raw barrier: __syncthreads()
-    // would also wait for the acknowledgement of the epilogue's stores.)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    tile = __builtin_amdgcn_readfirstlane(slot[(it + 1) & 1]);
-  }
-  // ---- leave: the last block re-arms the workspace for the next launch on this stream
-  if (tid == 0) {
-    const int prev = __hip_atomic_fetch_add(p.ws + 8, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == (int)gridDim.x - 1) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) __hip_atomic_store(p.ws + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// =================================================================================================
-// 256 x 256 x 64 tile, one block of 8 waves per CU, four phases per K-tile (config 12).
-//
-// The generic kernel above fills LDS at ~half of what a CU can take from L2 and keeps the matrix pipe
-// ~30 % busy: per K-tile it is one wait + one barrier + a compiler-scheduled blob.  This one follows
-// the phase structure of cdna_hip_programming.md §5 ("256² 8-phase"): the 256 x 256 accumulator is
-// cut into four 128 x 128 QUADRANTS (A half i x W half j); a phase = every wave's 64 x 32 patch of
-// one quadrant over the whole K-tile (16 MFMAs) and the LDS-DMA of ONE 16-KiB half-tile (2 per wave):
-//
-//   phase  quadrant   LDS fragment reads           stages (dest. = LDS parity of that K-tile)
-//     1    (A0, W0)   W0: 4, A0: 8 ds_read_b128    A1 of K-tile c+1
-//     2    (A0, W1)   W1: 4 (A0 stays in regs)     W0 of K-tile c+1
-//     3    (A1, W1)   A1: 8 (W1 stays)             A0 of K-tile c+2   (A0 of c: last read in phase 1)
-//     4    (A1, W0)   none (W0 kept from phase 1)  W1 of K-tile c+2   (W1 of c: last read in phase 2)
-//
-// so every half-tile buffer is restaged two phases after its last read (WAR) and is read no earlier
-// than the phase after the counted wait + barrier that retires it (RAW): the
-// only vmcnt is in phase 4, vmcnt(4) = the two half-tiles of K-tile c+2 just issued stay in flight,
-// everything of K-tile c+1 has landed.  128 KiB of LDS (2 parities x 4 halves), 128 accumulator
-// registers per lane, operands swapped / W rows permuted exactly as in the generic kernel.
-// Requires K % 128 == 0 (K-tiles are processed in pairs so that LDS parities are compile-time).
-// =================================================================================================
-template <typename OutT>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_256sq_kernel(Params p) {
-  constexpr int HALF = 128 * 128;               // bytes of one half-tile: 128 rows x 64 bf16
-  extern __shared__ __attribute__((aligned(16))) char lds[];   // [parity 2][A0, A1, W0, W1][128][128 B]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  ODIC_ENCODE_PRIO();
-
-  int tm, tn;
-  {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int xm = xcd / p.pn, xn = xcd - xm * p.pn;
-    const int r0 = xm * p.tiles_m / p.pm, r1 = (xm + 1) * p.tiles_m / p.pm;
-    const int c0 = xn * p.tiles_n / p.pn, c1 = (xn + 1) * p.tiles_n / p.pn;
-    const int w = c1 - c0;
-    if (idx >= (r1 - r0) * w) return;
-    const int lr = idx / w;
-    tm = r0 + lr; tn = c0 + (idx - lr * w);
-  }
-  const int m0 = tm * 256, n0 = tn * 256;
-  const long bz = blockIdx.z;
-  const bf16_raw* A = p.A + bz * p.strideA;
-  const bf16_raw* W = p.W + bz * p.strideW;
-
-  // ---- LDS-DMA sources: a half-tile is 16 pieces of 1 KiB (8 rows x 128 B); wave w moves pieces 2w, 2w+1.
-  //      buffer_load ... lds with the tile's base in a scalar resource descriptor, a 32-bit per-lane byte
-  //      offset and the K-tile advance as the scalar offset: no per-issue 64-bit address arithmetic, and the
-  //      LDS-DMA issues cheaper than the flat-address form (it is the long pole of a phase's load segment).
-  const int srow = lane >> 3, schunk = (lane & 7) ^ srow;          // swizzle: chunk ^ (row & 7)
-  const __amdgpu_buffer_rsrc_t rsrc_a =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(A + (long)m0 * p.lda), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(W + (long)n0 * p.ldw), 0, 0x7fffffff, 0x00020000);
-  int voff[4][2];                                                  // [A0, A1, W0, W1][piece] byte offsets
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = (wave * 2 + i) * 8 + srow;                     // row inside the half-tile
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      voff[h][i] = (min(m0 + h * 128 + row, p.M - 1) - m0) * (int)p.lda * 2 + schunk * 16;
-      voff[2 + h][i] = (min(n0 + h * 128 + wperm(row), p.N - 1) - n0) * (int)p.ldw * 2 + schunk * 16;
-    }
-  }
-  auto stage = [&](int parity, int h, int kt) {
-    char* dst = lds + (parity * 4 + h) * HALF + wave * 2048;
-    const __amdgpu_buffer_rsrc_t r = h < 2 ? rsrc_a : rsrc_w;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lptr_t)dst, 16, voff[h][0], kt * 128, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lptr_t)(dst + 1024), 16, voff[h][1], kt * 128, 0, 0);
-  };
-
-  f32x4_t acc[2][2][4][2];                                         // [A half][W half][mi][ni]
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[i][j][mi][ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = p.K / 64;
-  const int frow = lane & 15, fq = lane >> 4;
-  const int a_off = (wr * 64 + frow) * 128, w_off = (wc * 32 + frow) * 128;
-  const int c0 = ((0 + fq) ^ (frow & 7)) << 4, c1 = ((4 + fq) ^ (frow & 7)) << 4;   // kk = 0 / 1 chunks
-
-  bf16x8_t af[4][2], wf[2][2][2];                                  // [mi][kk], [W half][ni][kk]: both W halves stay live
-  auto read_a = [&](int parity, int h) {
-    const char* b = lds + (parity * 4 + h) * HALF + a_off;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      af[mi][0] = *(const bf16x8_t*)(b + mi * 16 * 128 + c0);
-      af[mi][1] = *(const bf16x8_t*)(b + mi * 16 * 128 + c1);
-    }
-  };
-  auto read_w = [&](int parity, int h) {
-    const char* b = lds + (parity * 4 + 2 + h) * HALF + w_off;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      wf[h][ni][0] = *(const bf16x8_t*)(b + ni * 16 * 128 + c0);
-      wf[h][ni][1] = *(const bf16x8_t*)(b + ni * 16 * 128 + c1);
-    }
-  };
-  auto mma = [&](int i, int j) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[i][j][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][ni][kk], af[mi][kk], acc[i][j][mi][ni], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  // prologue: all of K-tile 0, plus A0 / W1 of K-tile 1 (its A1 / W0 follow in phases 1 and 2)
-  stage(0, 0, 0); stage(0, 2, 0); stage(0, 3, 0); stage(0, 1, 0);
-  if (nk > 1) {
-    stage(1, 0, 1); stage(1, 3, 1);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-
-  // The two wave rows run half a phase apart (one extra barrier for row 1 here, one for row 0 after the
-  // loop): a SIMD holds one wave of each row, so while one of them issues its 16 MFMAs the other is in
-  // its load segment (fragment reads, LDS-DMA issue, counted wait) — the matrix pipe never waits for LDS.
-  // Every segment ends in a block-wide barrier.  Hazards with the half-phase skew: a buffer is restaged
-  // two phases (four segments) after its last read, the later row finishes that read two segments after
-  // the earlier one started it; a retired K-tile is first read two segments after the earlier row's wait,
-  // i.e. one segment after the later row's wait + barrier.
-  auto ktile = [&](int c, int parity) {           // parity is a literal at both call sites
-    // ---- phase 1: quadrant (A0, W0)
-    read_w(parity, 0); read_a(parity, 0);
-    if (c + 1 < nk) stage(parity ^ 1, 1, c + 1);
-    __builtin_amdgcn_s_barrier();
-    mma(0, 0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 2: quadrant (A0, W1)
-    read_w(parity, 1);
-    if (c + 1 < nk) stage(parity ^ 1, 2, c + 1);
-    __builtin_amdgcn_s_barrier();
-    mma(0, 1);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 3: quadrant (A1, W1)
-    read_a(parity, 1);
-    if (c + 2 < nk) stage(parity, 0, c + 2);
-    __builtin_amdgcn_s_barrier();
-    mma(1, 1);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 4: quadrant (A1, W0) — W0 fragments are still in registers from phase 1; the counted wait
-    //      retires every half-tile of K-tile c+1
-    if (c + 2 < nk) {
-      stage(parity, 3, c + 2);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    mma(1, 0);
-    __builtin_amdgcn_s_barrier();
-  };
-  if (wr == 1) __builtin_amdgcn_s_barrier();
-  for (int c = 0; c < nk; c += 2) {
-    ktile(c, 0);
-    ktile(c + 1, 1);
-  }
-  if (wr == 0) __builtin_amdgcn_s_barrier();
-
-  // ---- epilogue (same lane → 8 adjacent output columns mapping as the generic kernel)
-  const float* bias = p.bias ? p.bias + bz * p.strideBias : nullptr;
-  const float* resid = p.residual ? p.residual + bz * p.strideR : nullptr;
-  OutT* out = (OutT*)p.out + bz * p.strideC;
-  const bool ld_ok = ((p.ldc & 7) == 0) && (!resid || (p.ldr & 3) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = n0 + j * 128 + wc * 32 + fq * 8;
-    if (col >= p.N) continue;
-    float bc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bc[e] = (bias && !p.bias_axis && col + e < p.N) ? bias[col + e] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        const int row = m0 + i * 128 + wr * 64 + mi * 16 + frow;
-        if (row >= p.M) continue;
-        const float brow = (bias && p.bias_axis) ? bias[row] : 0.f;
-        f32x4_t v[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          f32x4_t pre = acc[i][j][mi][h] * p.alpha + f32x4_t{bc[4 * h], bc[4 * h + 1], bc[4 * h + 2], bc[4 * h + 3]} + brow;
-          if (p.act == ODIC_ACT_GELU) {
-            pre = gelu_poly4(pre);
-          } else if (p.act != ODIC_ACT_NONE) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pre[e] = apply_act<true>(pre[e], p.act);
-          }
-          v[h] = pre;
-        }
-        if (ld_ok && col + 7 < p.N) {
-          if (resid) {
-            const f32x4_t* rp = (const f32x4_t*)(resid + (long)row * p.ldr + col);
-            v[0] += rp[0]; v[1] += rp[1];
-          }
-          OutT* dst = out + (long)row * p.ldc + col;
-          if constexpr (sizeof(OutT) == 4) {
-            ((f32x4_t*)dst)[0] = v[0]; ((f32x4_t*)dst)[1] = v[1];
-          } else {
-            bf16x8_t pk;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { pk[e] = (short)f32_to_bf16(v[0][e]); pk[4 + e] = (short)f32_to_bf16(v[1][e]); }
-            *(bf16x8_t*)dst = pk;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            if (col + e < p.N) {
-              float x = v[e >> 2][e & 3];
-              if (resid) x += resid[(long)row * p.ldr + col + e];
-              store_from_f32<OutT>(out + (long)row * p.ldc + col + e, x);
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-#endif  // ODIC_EXPERIMENTAL_GEMM
 
 // =================================================================================================
 // A-resident streaming form for the K = 192 / 384 products of Swin stages 0-1 (tile_cfg 50-53).
@@ -1273,7 +689,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_apanel_kernel(Params p, int 
 template <int MI, int NI, int KT, int KH = 1>
 int launch_apanel(Params& p, int out_dtype, int batch, hipStream_t stream) {
   constexpr int BM = 4 * MI * 16, BNC = NI * 16;
-  if (batch != 1 || p.K != KT * 64 || p.M % BM != 0 || p.N % BNC != 0 || p.bias_axis != 0 || p.out16 || p.ln_stats)
+  if (batch != 1 || p.K != KT * 64 || p.M % BM != 0 || p.N % BNC != 0 || p.bias_axis != 0)
     return ODIC_EUNSUPPORTED;
   if ((long)BNC * p.ldw >= (1L << 30) || (p.residual && MI > 2))       // (the residual form of the 64-row waves would spill)
     return ODIC_EUNSUPPORTED;
@@ -1307,10 +723,13 @@ int launch_apanel(Params& p, int out_dtype, int batch, hipStream_t stream) {
   return odic_launch_status();
 }
 
-template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK = 64, bool FOLD = false, int KS = 1>
+template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK = 64, int KS = 1>
 int launch_cfg(Params& p, int out_dtype, int batch, hipStream_t stream) {
   constexpr int BM = NWM * MI * 16, BN = NWN * NI * 16;
-  constexpr int SH_STAGES = NSTAGE * (BM + BN) * BK * 2 + BM * 8;      // + (mean, rstd) per row of the tile
+  // (+ BM * 8: a tail no kernel reads any more — it held a row's (mean, rstd) for the retired LayerNorm fold.  It stays
+  //  because it is part of the footprint every tile was measured and tuned with: without it a fifth 64 x 64 x 2-stage
+  //  block fits a CU's 160 KiB of LDS, and a change of residency is one to measure, not to slip in.)
+  constexpr int SH_STAGES = NSTAGE * (BM + BN) * BK * 2 + BM * 8;
   constexpr int SH_RED = KS == 2 ? NWM * NWN * MI * NI * 1024 : 0;     // K-split: one group's accumulators
   constexpr int SHMEM = SH_STAGES > SH_RED ? SH_STAGES : SH_RED;
   if (p.K % BK != 0) return ODIC_EINVAL;
@@ -1326,8 +745,8 @@ int launch_cfg(Params& p, int out_dtype, int batch, hipStream_t stream) {
       if (r > max_rect) max_rect = r;
     }
   dim3 grid(8 * max_rect, 1, batch), block(64 * NWM * NWN * KS);
-  auto kb = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, bf16_raw, 0, KS>;
-  auto kf = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, float, 0, KS>;
+  auto kb = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, bf16_raw, KS>;
+  auto kf = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, float, KS>;
   if (SHMEM > 64 * 1024) {
     static bool done = false;       // idempotent; racing first calls set the same value
     if (!done) {
@@ -1336,155 +755,34 @@ int launch_cfg(Params& p, int out_dtype, int batch, hipStream_t stream) {
       done = true;
     }
   }
-  if constexpr (FOLD) {             // folded-LayerNorm forms exist for the tile configurations the tuner picks from
-    auto kprod = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, float, 1>;
-    auto kcons = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, bf16_raw, 2>;
-    if (SHMEM > 64 * 1024) {
-      static bool done2 = false;
-      if (!done2) {
-        (void)hipFuncSetAttribute((const void*)kprod, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-        (void)hipFuncSetAttribute((const void*)kcons, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-        done2 = true;
-      }
-    }
-    if (p.out16) { hipLaunchKernelGGL(kprod, grid, block, SHMEM, stream, p); return odic_launch_status(); }
-    if (p.ln_stats) {
-      if (out_dtype != ODIC_BF16 || (p.K >> 5) > 48) return ODIC_EUNSUPPORTED;
-      hipLaunchKernelGGL(kcons, grid, block, SHMEM, stream, p);
-      return odic_launch_status();
-    }
-  } else {
-    if (p.out16 || p.ln_stats) return ODIC_EUNSUPPORTED;
-  }
   if (out_dtype == ODIC_BF16) hipLaunchKernelGGL(kb, grid, block, SHMEM, stream, p);
   else hipLaunchKernelGGL(kf, grid, block, SHMEM, stream, p);
   return odic_launch_status();
 }
 
-
-#ifdef ODIC_EXPERIMENTAL_GEMM
-template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK = 64>
-int launch_persist(Params& p, int out_dtype, int batch, hipStream_t stream) {
-  constexpr int BM = NWM * MI * 16, BN = NWN * NI * 16;
-  constexpr int SHMEM = NSTAGE * (BM + BN) * BK * 2 + 16;
-  if (p.K % BK != 0 || batch != 1 || !p.ws) return ODIC_EINVAL;
-  if ((long)(BM - 1) * p.lda * 2 + 2L * p.K >= 0x7fffffffL || (long)(BN - 1) * p.ldw * 2 + 2L * p.K >= 0x7fffffffL)
-    return ODIC_EINVAL;                        // 32-bit byte offsets inside a tile's buffer resource
-  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
-  if (p.tiles_m > 65535 || p.tiles_n > 65535) return ODIC_EINVAL;
-  int pn = 1;
-  while (pn < 8 && pn * 2 <= p.tiles_n && (double)p.N / pn * p.K * 2.0 > 2.5 * 1024 * 1024) pn *= 2;
-  int pm = 8 / pn;
-  while (pm > p.tiles_m && pm > 1) { pm /= 2; pn *= 2; }
-  if (pn > p.tiles_n) { pn = 1; pm = 8; while (pm > p.tiles_m && pm > 1) pm /= 2; pn = 8 / pm; }
-  p.pm = pm; p.pn = pn;
-  auto kb = gemm_bf16_nt_persist_kernel<NWM, NWN, MI, NI, NSTAGE, BK, bf16_raw>;
-  auto kf = gemm_bf16_nt_persist_kernel<NWM, NWN, MI, NI, NSTAGE, BK, float>;
-  static int per_cu = 0;                       // resident blocks per CU of this instantiation (code-object property)
-  if (!per_cu) {
-    if (SHMEM > 64 * 1024) {
-      (void)hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    }
-    // resident blocks per CU from the code object's own numbers (LDS, registers, wave slots); blocks never wait
-    // for each other, so an estimate that is one too high or too low only costs a little speed
-    int nb = (160 * 1024) / SHMEM;
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)kb) == hipSuccess && fa.numRegs > 0) {
-      const int alloc = (fa.numRegs + 7) / 8 * 8;
-      const int waves_per_simd = 512 / alloc < 8 ? 512 / alloc : 8;
-      const int by_regs = waves_per_simd * 4 / (NWM * NWN);
-      if (by_regs < nb) nb = by_regs;
-    }
-    if (32 / (NWM * NWN) < nb) nb = 32 / (NWM * NWN);
-    per_cu = nb < 1 ? 1 : nb;
-    if (getenv("ODIC_GEMM_DEBUG"))
-      fprintf(stderr, "[odic_gemm] persistent %dx%dx%d stages %d: %d B LDS, %d regs -> %d blocks/CU\n", BM, BN, BK, NSTAGE,
-              SHMEM, fa.numRegs, per_cu);
-  }
-  const long tiles = (long)p.tiles_m * p.tiles_n;
-  const long slots = 256L * per_cu;
-  dim3 grid((unsigned)(tiles < slots ? tiles : slots)), block(64 * NWM * NWN);
-  if (out_dtype == ODIC_BF16) hipLaunchKernelGGL(kb, grid, block, SHMEM, stream, p);
-  else hipLaunchKernelGGL(kf, grid, block, SHMEM, stream, p);
-  return odic_launch_status();
-}
-
-int launch_256sq(Params& p, int out_dtype, int batch, hipStream_t stream) {
-  constexpr int SHMEM = 128 * 1024;
-  if (p.K % 128 != 0) return ODIC_EINVAL;
-  if (256L * p.lda * 2 + 2L * p.K >= 0x7fffffffL || 256L * p.ldw * 2 + 2L * p.K >= 0x7fffffffL)
-    return ODIC_EINVAL;                        // 32-bit byte offsets inside a tile's buffer resource
-  p.tiles_m = (p.M + 255) / 256; p.tiles_n = (p.N + 255) / 256;
-  int pn = 1;
-  while (pn < 8 && pn * 2 <= p.tiles_n && (double)p.N / pn * p.K * 2.0 > 2.5 * 1024 * 1024) pn *= 2;
-  int pm = 8 / pn;
-  while (pm > p.tiles_m && pm > 1) { pm /= 2; pn *= 2; }
-  if (pn > p.tiles_n) { pn = 1; pm = 8; while (pm > p.tiles_m && pm > 1) pm /= 2; pn = 8 / pm; }
-  p.pm = pm; p.pn = pn;
-  int max_rect = 0;
-  for (int xm = 0; xm < pm; ++xm)
-    for (int xn = 0; xn < pn; ++xn) {
-      const int r = ((xm + 1) * p.tiles_m / pm - xm * p.tiles_m / pm) * ((xn + 1) * p.tiles_n / pn - xn * p.tiles_n / pn);
-      if (r > max_rect) max_rect = r;
-    }
-  dim3 grid(8 * max_rect, 1, batch), block(512);
-  auto kb = gemm_bf16_256sq_kernel<bf16_raw>;
-  auto kf = gemm_bf16_256sq_kernel<float>;
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    done = true;
-  }
-  if (out_dtype == ODIC_BF16) hipLaunchKernelGGL(kb, grid, block, SHMEM, stream, p);
-  else hipLaunchKernelGGL(kf, grid, block, SHMEM, stream, p);
-  return odic_launch_status();
-}
-
-#endif  // ODIC_EXPERIMENTAL_GEMM
-
-// The default build carries the five tile configurations the host's tuner chooses from (0, 1, 7, 10) or the built-in
-// model falls back to (2).  Everything else that was built and measured on the way — more stages, 16-wave and 4-wave
-// 256-wide tiles, out-of-phase residents, the persistent and the 256x256 phase-pipelined kernels, the LayerNorm fold
-// across two products — compiles only with -DODIC_EXPERIMENTAL_GEMM (make EXTRA=-DODIC_EXPERIMENTAL_GEMM): none of it
-// is ever selected, and the folded-LayerNorm consumer is the one place where hipcc emits v_pk_fma_f32 with op_sel
-// source selection, the instruction form behind the round-2 wrong-row incident.
-#ifdef ODIC_EXPERIMENTAL_GEMM
-constexpr bool kFold = true;
-#else
-constexpr bool kFold = false;
-#endif
+// This file carries the tile configurations the host's tuner chooses from (0, 1, 7, 10, 40-42, 50-53), the one the
+// built-in model falls back to (2) and the variants kept beside them (43-49).  Everything else that was built and
+// measured on the way — more stages, 16-wave and 4-wave 256-wide tiles, out-of-phase residents, the persistent and
+// the 256x256 phase-pipelined kernels, the LayerNorm fold across two products — lost every comparison and is gone;
+// DESIGN.md §4.1 / §4.4 / §5 keep the measurements and name the last commit that has the code.
 
 }  // namespace
 
 int odic_gemm_bf16_launch(const odic_gemm_args* a, hipStream_t stream) {
-  if (a->ln_colsum && !a->ln_stats) return ODIC_EUNSUPPORTED;          // (the in-kernel moments form is fp32 skinny only)
+  if (a->ln_colsum) return ODIC_EUNSUPPORTED;                          // (the in-kernel moments form is fp32 skinny only)
   if (a->K % 64 != 0 || (a->A && a->lda % 8 != 0) || a->ldw % 8 != 0) return ODIC_EINVAL;
   if (((uintptr_t)a->A & 15) || ((uintptr_t)a->W & 15)) return ODIC_EINVAL;
   if (a->a_ln && (a->tile_cfg < 50 || a->tile_cfg > 53)) return ODIC_EUNSUPPORTED;   // (A-resident kernels only)
   if (!a->a_ln && !a->A) return ODIC_EINVAL;
   if ((a->strideA % 8) || (a->strideW % 8)) return ODIC_EINVAL;
   Params p;
-  p.skew_from = 0; p.skew_to = 0; p.skew_sleeps = 0;
   p.A = (const bf16_raw*)a->A; p.W = (const bf16_raw*)a->W; p.bias = a->bias; p.residual = a->residual;
   p.out = a->out; p.M = a->M; p.N = a->N; p.K = a->K;
   p.lda = a->lda; p.ldw = a->ldw; p.ldr = a->ldr; p.ldc = a->ldc;
   p.strideA = a->strideA; p.strideW = a->strideW; p.strideBias = a->strideBias;
   p.strideR = a->strideR; p.strideC = a->strideC;
   p.alpha = a->alpha; p.act = a->act; p.bias_axis = a->bias_axis;
-  p.ws = a->workspace;
-  p.out16 = (bf16_raw*)a->out16; p.ld16 = a->ld16; p.stats_out = a->stats_out;
-  p.ln_stats = a->ln_stats; p.ln_colsum = a->ln_colsum; p.ln_eps = a->ln_eps;
-  p.a_ln = a->a_ln; p.ld_aln = a->ld_aln;
-  if (p.out16) {          // producer of a folded LayerNorm: whole 32-column groups, vector stores, fp32 output
-    if (!p.stats_out || a->out_dtype != ODIC_F32 || a->batch != 1 || (a->N & 31) || (a->ldc & 7) || (a->ld16 & 7) ||
-        ((uintptr_t)a->out16 & 15) || ((uintptr_t)a->out & 15) || (a->residual && (a->ldr & 3)))
-      return ODIC_EINVAL;
-  }
-  if (p.ln_stats) {       // consumer: A's row moments come in K/32 groups (a multiple of 4, at most 48)
-    if (!p.ln_colsum || a->batch != 1 || (a->K & 31) || a->K > 1536 || a->bias_axis != 0) return ODIC_EINVAL;
-  }
+  p.a_ln = a->a_ln; p.ld_aln = a->ld_aln; p.ln_eps = a->ln_eps;
   // Tile choice = fewest "rounds x per-tile cost": a launch runs in ceil(tiles / resident slots)
   // rounds (256 CUs x 3 / 2 / 1 blocks for the 128x64 / 128x128 / 256x256 tiles, set by their LDS
   // footprints); relative per-tile costs 1 : 1.38 : 2.6 were measured on MI355X over the Swin-L
@@ -1496,15 +794,15 @@ int odic_gemm_bf16_launch(const odic_gemm_args* a, hipStream_t stream) {
       return (double)((t + slots - 1) / slots);
     };
     const double c0 = rounds(128, 64, 768) * 1.0, c1 = rounds(128, 128, 512) * 1.38;
-    const double c2 = (a->N % 256 == 0 && !p.out16 && !p.ln_stats) ? rounds(256, 256, 256) * 2.6 : 1e30;   // (no folded-LN form)
+    const double c2 = a->N % 256 == 0 ? rounds(256, 256, 256) * 2.6 : 1e30;
     cfg = (c0 <= c1 && c0 <= c2) ? 0 : (c1 <= c2 ? 1 : 2);
   }
   switch (cfg) {
-    case 0: return launch_cfg<2, 2, 4, 2, 2, 64, kFold>(p, a->out_dtype, a->batch, stream);     // 128 x 64, 2 stages
-    case 1: return launch_cfg<2, 2, 4, 4, 2, 64, kFold>(p, a->out_dtype, a->batch, stream);     // 128 x 128
+    case 0: return launch_cfg<2, 2, 4, 2, 2>(p, a->out_dtype, a->batch, stream);     // 128 x 64, 2 stages
+    case 1: return launch_cfg<2, 2, 4, 4, 2>(p, a->out_dtype, a->batch, stream);     // 128 x 128
     case 2: return launch_cfg<2, 4, 8, 4, 2>(p, a->out_dtype, a->batch, stream);     // 256 x 256
-    case 7: return launch_cfg<4, 2, 4, 4, 2, 32, kFold>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 32 (48 KiB)
-    case 10: return launch_cfg<4, 2, 4, 4, 3, 32, kFold>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 32, 3 stages (72 KiB)
+    case 7: return launch_cfg<4, 2, 4, 4, 2, 32>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 32 (48 KiB)
+    case 10: return launch_cfg<4, 2, 4, 4, 3, 32>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 32, 3 stages (72 KiB)
     // 144- / 288-row tiles of 48 x 96 wave patches (MI = 3, NI = 6): the Swin-L token counts carry factors of 9
     // (9216 = 32·288, 2304 = 16·144), so these tile grids are exact multiples of the 256 compute units where the
     // power-of-two tiles leave a ragged last round (9216 x 3072: 512 tiles of 288 x 192 = two full rounds of one
@@ -1517,7 +815,7 @@ int odic_gemm_bf16_launch(const odic_gemm_args* a, hipStream_t stream) {
     case 44: return launch_cfg<3, 1, 3, 6, 2, 64>(p, a->out_dtype, a->batch, stream);  // 144 x 96,   3 waves, 2 stages (60 KiB)
     case 45: return launch_cfg<3, 3, 3, 6, 3, 32>(p, a->out_dtype, a->batch, stream);  // 144 x 288 x 32, 9 waves, 3 stages (81 KiB)
     case 46: return launch_cfg<3, 1, 3, 6, 3, 64>(p, a->out_dtype, a->batch, stream);  // 144 x 96,   3 waves, 3 stages (90 KiB)
-    case 47: return launch_cfg<3, 2, 3, 6, 2, 64, false, 2>(p, a->out_dtype, a->batch, stream);  // 144 x 192, TWO K groups of 6 waves (108 KiB)
+    case 47: return launch_cfg<3, 2, 3, 6, 2, 64, 2>(p, a->out_dtype, a->batch, stream);  // 144 x 192, TWO K groups of 6 waves (108 KiB)
     // 64 x 64 tiles (4 waves of 32 x 32): the expansion encoder's products are 2304 rows (or 16 batches of 144) by 512 columns —
     // 72 tiles of 128 x 128 leave 184 of the 256 CUs idle while each tile walks a K of 512 ... 2048 alone
     case 48: return launch_cfg<2, 2, 2, 2, 3, 64>(p, a->out_dtype, a->batch, stream);  // 64 x 64, 3 stages (48 KiB)
@@ -1527,53 +825,6 @@ int odic_gemm_bf16_launch(const odic_gemm_args* a, hipStream_t stream) {
     case 51: return launch_apanel<2, 2, 6>(p, a->out_dtype, a->batch, stream);  // K = 384: 128-row panels, 32-column chunks
     case 52: return launch_apanel<2, 4, 3>(p, a->out_dtype, a->batch, stream);  // K = 192: 128-row panels, 64-column chunks
     case 53: return launch_apanel<2, 4, 6, 2>(p, a->out_dtype, a->batch, stream);  // K = 384: 128-row panels, 64-column chunks in two K pieces
-#ifdef ODIC_EXPERIMENTAL_GEMM
-    case 3: return launch_cfg<2, 2, 4, 2, 3>(p, a->out_dtype, a->batch, stream);     // 128 x 64, 3 stages
-    case 4: return launch_cfg<2, 2, 4, 4, 3>(p, a->out_dtype, a->batch, stream);     // 128 x 128, 3 stages
-    case 5: return launch_cfg<4, 2, 4, 4, 3>(p, a->out_dtype, a->batch, stream);     // 256 x 128, 3 stages (144 KiB)
-    case 6: return launch_cfg<2, 2, 4, 2, 4>(p, a->out_dtype, a->batch, stream);     // 128 x 64, 4 stages
-    case 8: return launch_cfg<2, 2, 4, 4, 2, 32>(p, a->out_dtype, a->batch, stream); // 128 x 128 x 32 (32 KiB)
-    case 9: return launch_cfg<2, 4, 8, 4, 2, 32>(p, a->out_dtype, a->batch, stream); // 256 x 256 x 32 (64 KiB)
-    case 11: return launch_cfg<2, 4, 8, 4, 3, 32>(p, a->out_dtype, a->batch, stream); // 256 x 256 x 32, 3 stages (96 KiB)
-    case 13: return launch_cfg<4, 4, 4, 4, 3, 32>(p, a->out_dtype, a->batch, stream); // 256 x 256 x 32, 16 waves of 64 x 64, 3 stages (96 KiB)
-    case 14: return launch_cfg<4, 4, 4, 4, 2, 64>(p, a->out_dtype, a->batch, stream); // 256 x 256 x 64, 16 waves of 64 x 64, 2 stages (128 KiB)
-    case 15: return launch_cfg<4, 4, 4, 4, 4, 32>(p, a->out_dtype, a->batch, stream); // 256 x 256 x 32, 16 waves, 4 stages (128 KiB)
-    // 4 waves of 128 x 64 (64 x 128): 12 KiB of LDS reads per 32 MFMAs instead of 8 KiB per 16, two blocks per CU
-    case 28: return launch_cfg<2, 2, 8, 4, 3, 32>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 32, 3 stages (72 KiB)
-    case 29: return launch_cfg<2, 2, 4, 8, 3, 32>(p, a->out_dtype, a->batch, stream); // 128 x 256 x 32, 3 stages (72 KiB)
-    case 30: return launch_cfg<2, 2, 8, 4, 2, 32>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 32, 2 stages (48 KiB)
-    case 31: return launch_cfg<2, 2, 8, 4, 2, 64>(p, a->out_dtype, a->batch, stream); // 256 x 128 x 64, 2 stages (96 KiB)
-    // 32 / 33: config 10 with the blocks that become the SECOND resident block of a CU (ids 256..511) started 8 / 12 us
-    // late, so that the two blocks of a CU are out of phase — one's pipeline fill and store tail under the other's
-    // K-loop — instead of running prologue, loop and epilogue in lockstep (fc1 / fc2 of stage 2: -5 %)
-    case 32: p.skew_from = 256; p.skew_to = 512; p.skew_sleeps = 2;
-             return launch_cfg<4, 2, 4, 4, 3, 32, kFold>(p, a->out_dtype, a->batch, stream);
-    case 33: p.skew_from = 256; p.skew_to = 512; p.skew_sleeps = 3;
-             return launch_cfg<4, 2, 4, 4, 3, 32, kFold>(p, a->out_dtype, a->batch, stream);
-    case 12: if (p.out16 || p.ln_stats) return ODIC_EUNSUPPORTED;
-             return launch_256sq(p, a->out_dtype, a->batch, stream);                 // 256 x 256 x 64, 4 phases per K-tile (128 KiB)
-    // 16 + c: tile config c as a persistent, dynamically scheduled launch (needs args->workspace, batch == 1)
-    case 16: case 17: case 18: case 19: case 20: case 21: case 23: case 24: case 25: case 26: case 27:
-      if (p.out16 || p.ln_stats) return ODIC_EUNSUPPORTED;
-      break;
-    default: break;
-  }
-  switch (cfg) {
-    case 16: return launch_persist<2, 2, 4, 2, 2>(p, a->out_dtype, a->batch, stream);
-    case 17: return launch_persist<2, 2, 4, 4, 2>(p, a->out_dtype, a->batch, stream);
-    case 18: return launch_persist<2, 4, 8, 4, 2>(p, a->out_dtype, a->batch, stream);
-    case 19: return launch_persist<2, 2, 4, 2, 3>(p, a->out_dtype, a->batch, stream);
-    case 20: return launch_persist<2, 2, 4, 4, 3>(p, a->out_dtype, a->batch, stream);
-    case 21: return launch_persist<4, 2, 4, 4, 3>(p, a->out_dtype, a->batch, stream);
-    case 23: return launch_persist<4, 2, 4, 4, 2, 32>(p, a->out_dtype, a->batch, stream);
-    case 24: return launch_persist<2, 2, 4, 4, 2, 32>(p, a->out_dtype, a->batch, stream);
-    case 25: return launch_persist<2, 4, 8, 4, 2, 32>(p, a->out_dtype, a->batch, stream);
-    case 26: return launch_persist<4, 2, 4, 4, 3, 32>(p, a->out_dtype, a->batch, stream);
-    case 27: return launch_persist<2, 4, 8, 4, 3, 32>(p, a->out_dtype, a->batch, stream);
     default: return ODIC_EINVAL;
   }
-#else
-    default: return ODIC_EINVAL;             // (tile configurations 3-6, 8, 9, 11-33: -DODIC_EXPERIMENTAL_GEMM builds only)
-  }
-#endif
 }

@@ -508,7 +508,7 @@ int launch(Params& p, int out_dtype, int batch, hipStream_t stream) {
 }  // namespace
 
 int odic_gemm_x3_launch(const odic_gemm_args* a, hipStream_t stream) {
-  if (a->ln_colsum || a->col_scale || a->out16 || a->ln_stats) return ODIC_EUNSUPPORTED;
+  if (a->ln_colsum || a->col_scale) return ODIC_EUNSUPPORTED;
   if (a->out_dtype != ODIC_F32 && a->out_dtype != ODIC_H2) return ODIC_EINVAL;
   // h2 rows are whole [8 hi | 8 lo] groups and K-tiles are four of them
   if (a->K % 32 != 0 || (a->A && a->lda % 8 != 0) || a->ldw % 8 != 0 || (a->strideA % 8) || (a->strideW % 8)) return ODIC_EINVAL;

@@ -95,23 +95,6 @@ class SwinEngine:
             self.stages.append((blocks, down))
         self.fn_w, self.fn_b = f32(f"{P}.norm.weight"), f32(f"{P}.norm.bias")
         self.stage_chunks = [int(v) for v in os.environ.get("ODIC_SWIN_CHUNKS", "1").split(",")]
-        # Optional (ODIC_FOLD_BACKBONE_LN=1, bf16 mode): norm2 and the norm1 of every block but a stage's first folded
-        # across the products around them (ops.gemm producer / consumer form): the proj / fc2 product leaves a bf16
-        # copy of the residual stream plus row-group moments, the fc1 / next qkv product normalises in its epilogue.
-        # Equally accurate (tools/fold_diag.py) and 44 launches fewer, but measured 1.5 % SLOWER end to end: the
-        # LayerNorm kernels already run at 5 TB/s, and the producer's extra stores + the consumer's moment combine
-        # cost the four products of a block 20 µs against the 16 µs of the two launches they replace.
-        # (the fold's GEMM forms are compiled only into -DODIC_EXPERIMENTAL_GEMM builds of the library)
-        self.fold_ln = precision == "bf16" and os.environ.get("ODIC_FOLD_BACKBONE_LN", "0") == "1" and \
-            all(g.stage_dim(s) % 64 == 0 for s in range(len(g.swin_depths)))
-        if self.fold_ln and b"experimental-gemm" not in _hip.load().odic_build_info():
-            raise RuntimeError("ODIC_FOLD_BACKBONE_LN=1 needs a library built with make EXTRA=-DODIC_EXPERIMENTAL_GEMM")
-        if self.fold_ln:
-            for s, (blocks, _) in enumerate(self.stages):
-                for b, w in enumerate(blocks):
-                    p = f"{P}.layers.{s}.blocks.{b}"
-                    w["qkv_f"] = ops.fold_layernorm_bf16(f32(p + ".attn.qkv.weight"), w["qkv_b"], w["n1w"], w["n1b"])
-                    w["fc1_f"] = ops.fold_layernorm_bf16(f32(p + ".mlp.fc1.weight"), w["fc1_b"], w["n2w"], w["n2b"])
         # bf16 mode, the stage of width 192 (Swin-L stage 0): norm1 → qkv and norm2 → fc1 are ONE launch each — the A-resident
         # GEMM kernel normalises the fp32 rows while it reads them (odic_gemm_args.a_ln; gamma / beta folded into the
         # weights): 96 → 85 and 130 → 105 µs per pair at B = 16.  Not at width 384: there the fused form needs the registers
@@ -121,7 +104,7 @@ class SwinEngine:
         #  gamma into the weights changes WHICH near-ties of the xavier checkpoint round the other way: 255 / 256 captions equal
         #  to fp32 instead of 256 / 256 — the mode exists for that equality, so it is opt-in there: ODIC_FUSE_BACKBONE_LN_READ=x3)
         lr = os.environ.get("ODIC_FUSE_BACKBONE_LN_READ", "1")
-        self.ln_read = not self.fold_ln and ((precision == "bf16" and lr != "0") or (precision == "x3" and lr == "x3"))
+        self.ln_read = (precision == "bf16" and lr != "0") or (precision == "x3" and lr == "x3")
         self.fuse_qkv_attn = precision == "bf16" and os.environ.get("ODIC_FUSE_QKV_ATTENTION", "1") == "1"
         if self.ln_read:
             for s, (blocks, _) in enumerate(self.stages):
@@ -209,7 +192,7 @@ class SwinEngine:
             # writes (qkv, the MLP hidden, the residual stream) is still in the 256 MB Infinity Cache when the
             # next launch reads it — the stage-0/1 launches are HBM-bound
             n_ch = self.stage_chunks[s] if s < len(self.stage_chunks) else 1
-            if taps is not None or _amax is not None or self.fold_ln or n_ch < 1 or B % n_ch:
+            if taps is not None or _amax is not None or n_ch < 1 or B % n_ch:
                 n_ch = 1
             x_all, B_all = x, B
             B = B_all // n_ch
@@ -227,24 +210,6 @@ class SwinEngine:
                     h = ops.gemm(xn, w["fc1_w8"], w["fc1_b"], act=ops.ACT_GELU, col_scale=w["fc1_cs"],
                                  out_scale=w["hid_inv"], out_dtype=ops.FP8_DTYPE)
                     ops.gemm(h, w["fc2_w8"], w["fc2_b"], residual=x, out=x, col_scale=w["fc2_cs"])
-                elif self.fold_ln and _amax is None:
-                    if bi == 0:                                  # x comes from patch embed / patch merge: plain norm1
-                        x16 = torch.empty(x.shape, dtype=cdt, device=x.device)
-                        stats = torch.empty(x.shape[0], C_ // 32, 2, dtype=torch.float32, device=x.device)
-                        xn = ops.layernorm(x, w["n1w"], w["n1b"], out_dtype=cdt)
-                        qkv = ops.gemm(xn, w["qkv_w"], w["qkv_b"])
-                    else:                                        # norm1 folded: A = bf16 copy left by the previous fc2
-                        Wf, bf, cs = w["qkv_f"]
-                        qkv = ops.gemm(x16, Wf, bf, ln_fold=(cs, 1e-5), ln_stats=stats)
-                    att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
-                                               bias_shifted_prescaled=w["dense"])
-                    ops.gemm(att, w["proj_w"], w["proj_b"], residual=x, out=x, out16=x16, stats_out=stats)
-                    Wf, bf, cs = w["fc1_f"]
-                    h = ops.gemm(x16, Wf, bf, act=ops.ACT_GELU, ln_fold=(cs, 1e-5), ln_stats=stats)
-                    if bi + 1 < len(blocks):
-                        ops.gemm(h, w["fc2_w"], w["fc2_b"], residual=x, out=x, out16=x16, stats_out=stats)
-                    else:
-                        ops.gemm(h, w["fc2_w"], w["fc2_b"], residual=x, out=x)
                 elif "qkv_lnr" in w and _amax is None and ops.a_ln_supported(x.shape[0], 3 * C_, C_, cdt):
                     if self.fuse_qkv_attn and ws == 12 and w["dense"] is not None:
                         # norm1 → qkv → attention core: one launch, q / k / v never leave the chip

@@ -123,18 +123,6 @@ def _load_tile_cache() -> dict:
 _TILE_CACHE: dict = _load_tile_cache()
 _TILE_CANDIDATES = tuple(int(c) for c in os.environ.get("ODIC_TILE_CANDIDATES", "0,1,7,10,40,41,42,50,51,52,53").split(","))
 
-# persistent tile configurations (16 + c) draw tiles from atomic counters in a 16-int workspace that is zero at
-# launch and left zero by the kernel: launches of one stream are ordered, so one buffer per stream suffices
-_GEMM_WS: dict = {}
-
-
-def _gemm_workspace(device: torch.device) -> torch.Tensor:
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _GEMM_WS.get(key)
-    if ws is None:
-        ws = _GEMM_WS[key] = torch.zeros(16, dtype=torch.int32, device=device)
-    return ws
-
 
 class autotune:
     def __enter__(self):
@@ -193,23 +181,18 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
          ldc: Optional[int] = None, batch: int = 1, strideA: int = 0, strideW: int = 0, strideBias: int = 0,
          strideR: int = 0, strideC: int = 0, ln_fold: Optional[tuple] = None, tile_cfg: int = -1,
          col_scale: Optional[torch.Tensor] = None, out_scale: float = 1.0,
-         out16: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None,
-         ln_stats: Optional[torch.Tensor] = None, a_ln: Optional[torch.Tensor] = None, ln_eps: float = 1e-5
-         ) -> torch.Tensor:
+         a_ln: Optional[torch.Tensor] = None, ln_eps: float = 1e-5) -> torch.Tensor:
     """out = act(alpha·A·Wᵀ + bias) + residual.  With no explicit dims, A is [..., K] (flattened to
     [M,K]) and W is [N,K], both contiguous.  Explicit dims / leading dimensions / batch strides allow
     strided sub-matrices (elements).  ln_fold = (colsum, eps): W and bias come from fold_layernorm() and
     the rows of A are LayerNorm-ed inside the product (fp32 skinny-M path only).  fp8 / fp16 operands (the
     low-precision backbone mode): `col_scale` fp32 [N] multiplies column n of A·Wᵀ (activation scale x weight channel
     scale) and `out_scale` the result before an fp8 / fp16 output cast.
-    LayerNorm folded across two bf16 products: the PRODUCER (fp32 output) is given `out16` (bf16 [M,N]) and
-    `stats_out` (fp32 [M, N/32, 2]); the CONSUMER reads that copy as A with `ln_stats=stats_out` and
-    `ln_fold=(colsum, eps)` from fold_layernorm_bf16().
     LayerNorm while reading (A = None, `a_ln` = the fp32 rows [M,K], W / bias from fold_layernorm_bf16()): the bf16
     A-resident kernels normalise each row in registers — one launch for norm → linear (K = 192 / 384, whole tiles)."""
     if a_ln is not None:
         return _gemm_a_ln(a_ln, W, bias, out, act=act, alpha=alpha, out_dtype=out_dtype, ln_eps=ln_eps, tile_cfg=tile_cfg)
-    _need_cuda(A, W, bias, residual, out, col_scale, out16, stats_out, ln_stats)
+    _need_cuda(A, W, bias, residual, out, col_scale)
     if A.dtype != W.dtype:
         raise RuntimeError("A and W must share a dtype")
     if M is None:
@@ -238,12 +221,9 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
                       strideA, strideW, strideBias, strideR, strideC, alpha, act, bias_axis,
                       dtype_code(A.dtype), dtype_code(out.dtype), tile_cfg,
                       _p(ln_fold[0]) if ln_fold else None, float(ln_fold[1]) if ln_fold else 0.0, None,
-                      _p(col_scale), float(out_scale), _p(out16), out16.stride(0) if out16 is not None else 0,
-                      _p(stats_out), _p(ln_stats))
+                      _p(col_scale), float(out_scale), None, 0, None, None)
     if A.dtype in (torch.bfloat16, torch.float16, FP8_DTYPE, H2_DTYPE):
-        if batch == 1 and A.dtype == torch.bfloat16:
-            a.workspace = _gemm_workspace(A.device).data_ptr()
-        key = (A.dtype, M, N, K, batch, out.dtype, act, residual is not None, out16 is not None, ln_stats is not None)
+        key = (A.dtype, M, N, K, batch, out.dtype, act, residual is not None)
         cfg = _TILE_CHOICE.get(key) if tile_cfg < 0 else tile_cfg
         if cfg is None and tile_cfg < 0 and _TILE_CACHE:
             cfg = _TILE_CACHE.get(_cache_key(key))

@@ -67,7 +67,7 @@ def test_argument_validation_needs_no_gpu(lib):
     assert lib.odic_copy(16, 32, 24, None) == -1 and lib.odic_copy(None, 32, 32, None) == -2
     assert lib.odic_beam_finalize_best(ctypes.byref(st), 16, 16, None, 16, 4, 3, 20, 77, None) == -2
     assert lib.odic_logsoftmax_sample(16, 8, None, 0, 16, 16, 4, 8, 9, 0, None, None) == -1           # k > V
-    # persistent bf16 tile configurations need the caller's workspace
+    # a bf16 tile configuration the library does not carry (17: a retired persistent form) is refused by the dispatch
     a = _hip.GemmArgs()
     a.A, a.W, a.out = 16, 16, 16
     a.M, a.N, a.K, a.batch, a.lda, a.ldw, a.ldc = 256, 256, 64, 1, 64, 64, 256

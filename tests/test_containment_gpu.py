@@ -422,24 +422,25 @@ def _check_engine_product(o, want, prec, what, f32=False):
 
 
 def test_gemm_folded_layernorm_secondary_outputs_are_refused_or_contained(ops):
-    """The producer's out16 / stats_out secondary outputs exist in -DODIC_EXPERIMENTAL_GEMM builds only; the default build
-    refuses them before any launch (test_gemm_bf16_default_build_rejects_compiled_out_configurations), and nothing is written."""
+    """out16 / stats_out / ln_stats of odic_gemm_args are reserved: the library refuses them with ODIC_EUNSUPPORTED before any
+    launch (test_gemm_bf16_default_build_rejects_compiled_out_configurations), and nothing is written."""
     _hip, lib = _lib()
     M, N, K = 129, 96, 64
     A, Wt = rnd(M, K, seed=1).bfloat16().to(DEV), rnd(N, K, seed=2, scale=0.05).bfloat16().to(DEV)
     o, o16, st = guarded(M, N, N + 8, F32, DEV), guarded(M, N, N + 8, BF16, DEV), guarded(M, 2 * (N // 32), 2 * (N // 32), F32, DEV)
-    if b"experimental-gemm" not in lib.odic_build_info():
-        with pytest.raises(RuntimeError):
-            ops.gemm(A, Wt, out=o.t, M=M, N=N, K=K, lda=K, ldw=K, ldc=N + 8, out16=o16.t, stats_out=st.t)
+    for fields in (("out16", "stats_out"), ("ln_stats",)):
+        a = _hip.GemmArgs()
+        a.A, a.W, a.out, a.M, a.N, a.K = A.data_ptr(), Wt.data_ptr(), o.data_ptr(), M, N, K
+        a.lda, a.ldw, a.ldc, a.batch, a.alpha = K, K, N + 8, 1, 1.0
+        a.in_dtype, a.out_dtype, a.tile_cfg = _hip.BF16, _hip.F32, -1
+        if "out16" in fields:
+            a.out16, a.ld16, a.stats_out = o16.data_ptr(), N + 8, st.data_ptr()
+        else:
+            a.ln_stats = st.data_ptr()
+        assert lib.odic_gemm(C.byref(a), _stream()) == -3, fields                # ODIC_EUNSUPPORTED
         torch.cuda.synchronize()
         for gbuf in (o, o16, st):
-            gbuf.assert_all_poison("refused launch")
-        return
-    ops.gemm(A, Wt, out=o.t, M=M, N=N, K=K, lda=K, ldw=K, ldc=N + 8, out16=o16.t, stats_out=st.t, tile_cfg=0)
-    torch.cuda.synchronize()
-    for gbuf in (o, o16, st):
-        gbuf.assert_untouched(what="folded-LayerNorm producer")
-    assert_close(o.values()[0], A.double().cpu() @ Wt.double().cpu().T, 2e-4, "producer")
+            gbuf.assert_all_poison("refused launch: " + " / ".join(fields))
 
 
 def test_gemm_coverage_every_selectable_tile(ops):

@@ -3,7 +3,7 @@
 fill, epilogue, store tail).  For one output shape (M x N) the product is timed at several K and with each
 epilogue; T(K) = fixed + slope·K is fitted per (tile config, epilogue).  Variants interleaved in one process.
 
-    python tools/gemm_fixed_cost.py [--M 9216] [--N 3072] [--cfgs 10,12]
+    python tools/gemm_fixed_cost.py [--M 9216] [--N 3072] [--cfgs 10,40]
 """
 import argparse
 import os
@@ -17,7 +17,7 @@ from on_device_image_captioning_amd import ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--M", type=int, default=9216)
 ap.add_argument("--N", type=int, default=3072)
-ap.add_argument("--cfgs", default="1,10,12")
+ap.add_argument("--cfgs", default="1,10,40")
 ap.add_argument("--ks", default="256,768,1536,3072")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--inner", type=int, default=10)

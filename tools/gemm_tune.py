@@ -4,7 +4,7 @@ epilogue the product path uses.  Variants are interleaved round by round in ONE 
 §5.4 rule 24) on random data; the median over rounds is printed.  `--vendor` adds torch.mm (hipBLASLt; plain GEMM,
 calibration only — never on the product path).
 
-    python tools/gemm_tune.py [--batch 16] [--cfgs 0,1,7,10,16,17,23,26] [--stages 2,3] [--rounds 7] [--vendor]
+    python tools/gemm_tune.py [--batch 16] [--cfgs 0,1,7,10,40,41,42] [--stages 2,3] [--rounds 7] [--vendor]
 """
 import argparse
 import os
@@ -17,7 +17,7 @@ from on_device_image_captioning_amd import ops
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=16)
-ap.add_argument("--cfgs", default="0,1,7,10,16,17,23,26")
+ap.add_argument("--cfgs", default="0,1,7,10,40,41,42")
 ap.add_argument("--stages", default="0,1,2,3")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--inner", type=int, default=10)
