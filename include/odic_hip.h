@@ -51,7 +51,7 @@ extern "C" {
 #define ODIC_EUNSUPPORTED (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define ODIC_ABI_VERSION 17
+#define ODIC_ABI_VERSION 18
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -185,7 +185,7 @@ int odic_resize_bilinear_normalize(const uint8_t* src_rgb, int32_t H, int32_t W,
                                    const float* std3, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Batched baseline JPEG decode on the device (utils/image_utils.py:7, PIL_Image.open), bit-exact with
+ * Batched JPEG decode on the device, baseline files here and progressive ones below (utils/image_utils.py:7, PIL_Image.open), bit-exact with
  * np.asarray(PIL.Image.open(f)) on Pillow's libjpeg-turbo default path (ISLOW IDCT, fancy upsampling,
  * fixed-point YCbCr→RGB).  The host parser (on_device_image_captioning_amd/jpeg.py) walks the markers up to
  * SOS and fills one odic_jpeg_header per image; only its `device` kind is passed here: 8-bit SOF0/SOF1
@@ -243,6 +243,75 @@ size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* batch);
  * odic_jpeg_workspace_bytes(batch) of `workspace` are touched, `data` is only read, and exactly the images' H·W·3 bytes of
  * `out` and n_images entries of `status` are written (test_jpeg_decode_stays_inside_its_workspace). */
 int odic_jpeg_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Progressive files (8-bit SOF2 Huffman, 3 YCbCr components, the samplings above), bit-exact with Pillow as well.
+ * The host parser (jpeg.parse_progressive) reads the whole scan script and accepts what libjpeg accepts without a
+ * warning and what leaves every coefficient at full precision by EOI; it packs one odic_jpeg_prog_header per image,
+ * one odic_jpeg_scan per scan and one odic_jpeg_table per distinct Huffman table of the batch.
+ *   header   out_off / coef_off / plane_off as above; n_intervals = the sum of its scans' n_intervals
+ *   scan     data_off / data_end: the scan's entropy-coded bytes in `data`, from the byte behind the SOS header to the
+ *            marker that closes the scan (exclusive); scan_off: its compacted bytes in the workspace (4-aligned,
+ *            round_up(data_end - data_off, 4) + 16 reserved); int_off: its n_intervals + 1 interval slots;
+ *            n_units: what the scan walks — the frame's MCUs for an interleaved scan, else the blocks of the component's
+ *            own raster, ceil(ceil(W·h/hmax)/8) (= blocks_w) by ceil(ceil(H·v/vmax)/8); restart: units per restart
+ *            interval (n_units without DRI), n_intervals = ceil(n_units / restart); comp_mask: bit c = frame component c
+ *            takes part; ss / se / ah / al: the SOS parameters; level: 1 + the highest level of an earlier scan of the
+ *            image that shares a component and overlaps the band (an AC scan also follows its component's first DC scan);
+ *            table: indices into `tables` — the DC table of each participating component in order (first DC pass) or the
+ *            AC table in [0] (AC scans); -1 where none is needed
+ *   scans are sorted by level: level l (0-based) is scans [level_first[l], level_first[l + 1]), at most 65535 of them, and
+ *   level_intervals[l] is the largest n_intervals among them.  One launch per level decodes all its scans concurrently.
+ * ------------------------------------------------------------------------------------------- */
+#define ODIC_JPEG_MAX_SCANS 64   /* scans per image, and so levels per batch; files with more go to the host */
+
+typedef struct odic_jpeg_table {
+  uint16_t lut[512];
+  int32_t maxcode[18];
+  int32_t valoff[18];
+  uint8_t huffval[256];
+} odic_jpeg_table;
+
+typedef struct odic_jpeg_prog_header {
+  int64_t out_off, coef_off, plane_off;
+  int32_t width, height, sampling, mcus_x, mcus_y, n_intervals;
+  uint16_t qt[3][64];
+} odic_jpeg_prog_header;
+
+typedef struct odic_jpeg_scan {
+  int64_t data_off, data_end, scan_off;
+  int32_t image, int_off, n_intervals, restart, n_units, blocks_w, comp_mask, ss, se, ah, al, level;
+  int32_t table[3];
+  int32_t pad;
+} odic_jpeg_scan;
+
+typedef struct odic_jpeg_prog_batch {
+  const void* headers;           /* odic_jpeg_prog_header [n_images] */
+  const void* scans;             /* odic_jpeg_scan [n_scans], sorted by level */
+  const void* tables;            /* odic_jpeg_table [n_tables] */
+  const uint8_t* data;
+  uint8_t* out;
+  int32_t* status;
+  int32_t n_images, n_scans, n_tables, n_levels, max_width, max_height, pad0, pad1;
+  int64_t max_blocks, total_scan_bytes, total_intervals, total_blocks, total_plane_bytes;
+  int32_t level_first[ODIC_JPEG_MAX_SCANS + 1];
+  int32_t level_intervals[ODIC_JPEG_MAX_SCANS];
+  int32_t pad2;
+} odic_jpeg_prog_batch;
+
+/* Workspace bytes odic_jpeg_decode_progressive needs (host-side query); 0 for an invalid descriptor. */
+size_t odic_jpeg_progressive_workspace_bytes(const odic_jpeg_prog_batch* batch);
+
+/* Diagnostic: byte offset inside that workspace of the int16 coefficient blocks ([total_blocks][64], natural order,
+ * image i at block coef_off, MCU by MCU), valid after a decode until the workspace is reused; 0 for an invalid descriptor. */
+size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* batch);
+
+/* Decode the batch on `stream`: same contract as odic_jpeg_decode (all launches on the stream, no allocation, no host
+ * synchronisation, capturable; only `workspace`, `out` and `status` are written —
+ * test_jpeg_progressive_decode_stays_inside_its_workspace).  status 1: a marker other than RSTn inside a scan, too few or too
+ * many intervals, an invalid code, an EOB run or coefficient index past the band, bits needed past an interval's end, or
+ * coefficients outside the IDCT's range as above.  The parser vouches for the script and the closing EOI. */
+int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core  (WindowAttention.forward swin_transformer_mod.py:193-211

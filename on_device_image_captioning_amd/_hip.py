@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libodic_hip.so")
 
 F32, BF16, FP8, F16, H2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _ERR = {-1: "ODIC_EINVAL (bad shape / alignment / enum)", -2: "ODIC_ENULL (required pointer is NULL)",
         -3: "ODIC_EUNSUPPORTED"}
@@ -59,6 +59,21 @@ class JpegBatch(C.Structure):
                 ("total_plane_bytes", C.c_int64)]
 
 
+JPEG_MAX_SCANS = 64                                       # ODIC_JPEG_MAX_SCANS
+
+
+class JpegProgBatch(C.Structure):
+    """odic_jpeg_prog_batch: one batched progressive JPEG decode (records from jpeg.pack_progressive)."""
+    _fields_ = [("headers", C.c_void_p), ("scans", C.c_void_p), ("tables", C.c_void_p), ("data", C.c_void_p),
+                ("out", C.c_void_p), ("status", C.c_void_p),
+                ("n_images", C.c_int32), ("n_scans", C.c_int32), ("n_tables", C.c_int32), ("n_levels", C.c_int32),
+                ("max_width", C.c_int32), ("max_height", C.c_int32), ("pad0", C.c_int32), ("pad1", C.c_int32),
+                ("max_blocks", C.c_int64), ("total_scan_bytes", C.c_int64), ("total_intervals", C.c_int64),
+                ("total_blocks", C.c_int64), ("total_plane_bytes", C.c_int64),
+                ("level_first", C.c_int32 * (JPEG_MAX_SCANS + 1)), ("level_intervals", C.c_int32 * JPEG_MAX_SCANS),
+                ("pad2", C.c_int32)]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 _SIGNATURES = {
@@ -96,6 +111,9 @@ _SIGNATURES = {
     "odic_beam_reset": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),
     "odic_jpeg_workspace_bytes": (C.c_size_t, [C.POINTER(JpegBatch)]),
     "odic_jpeg_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
+    "odic_jpeg_progressive_workspace_bytes": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
+    "odic_jpeg_progressive_coef_offset": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
+    "odic_jpeg_decode_progressive": (C.c_int, [C.POINTER(JpegProgBatch), _P, C.c_size_t, _P]),
 }
 
 #: every symbol include/odic_hip.h declares

@@ -117,24 +117,21 @@ __device__ T block_exclusive_scan(T v, T* lds, T& total) {   // 256 lanes; lds h
   return incl - v;
 }
 
-__global__ __launch_bounds__(256) void jpeg_segment_kernel(const odic_jpeg_header* __restrict__ hdrs,
-                                                           const unsigned char* __restrict__ data, Ws ws,
-                                                           int subseq_bits) {
-  const odic_jpeg_header& h = hdrs[blockIdx.x];
+// Classify and compact the bytes [src, src + len) of one scan into dst and record the start bit of every restart
+// interval in ib[0 .. nint] (256 lanes).  want_eoi: the data must end with EOI inside the range (a baseline file is
+// passed up to its last byte); otherwise the host parser has already cut the range at the scan's closing marker, and
+// any marker other than RSTn inside it is an error.  Returns nonzero on an error; carry_data = compacted bytes.
+__device__ int segment_bytes(const unsigned char* __restrict__ src, const long len, unsigned char* __restrict__ dst,
+                             int* __restrict__ ib, const int nint, const bool want_eoi, long& carry_data,
+                             int& carry_marks) {
   const int t = threadIdx.x;
-  const unsigned char* src = data + h.data_off;
-  const long len = h.data_end - h.data_off;
-  unsigned char* dst = ws.scan + h.scan_off;
-  int* ib = ws.int_bits + h.int_off;
-  int* us = ws.unit_start + h.int_off;
-  int* state = ws.state + kStateWords * blockIdx.x;
-  const int nint = h.n_intervals;
   __shared__ int sh_scan[256];
   __shared__ long sh_stop;
   __shared__ int sh_err;
-  long carry_data = 0;
-  int carry_marks = 0, err = 0;
-  bool eoi = false;
+  carry_data = 0;
+  carry_marks = 0;
+  int err = 0;
+  bool eoi = false, stopped = false;
   if (t == 0) sh_err = 0;
   for (long base = 0; base < len; base += 4096) {
     if (t == 0) sh_stop = len;
@@ -184,21 +181,37 @@ __global__ __launch_bounds__(256) void jpeg_segment_kernel(const odic_jpeg_heade
     carry_marks += tot_m;
     if (stop < len) {
       eoi = stop + 1 < len && src[stop + 1] == 0xD9;
+      stopped = true;
       break;
     }
     __syncthreads();
   }
   __syncthreads();
   err = sh_err;
-  if (!eoi || carry_marks != nint - 1) err = 1;
-  if (t == 0) {
-    if (err) state[0] |= kErrSegment;
-    ib[0] = 0;
-  }
+  if ((want_eoi ? !eoi : stopped) || carry_marks != nint - 1) err = 1;
+  if (t == 0) ib[0] = 0;
   const int endbits = (int)(carry_data * 8);
   for (int k = min(carry_marks, nint - 1) + 1 + t; k <= nint; k += 256) ib[k] = endbits;   // end; missing: empty
   if (t < 16) dst[carry_data + t] = 0;
   __syncthreads();
+  return err;
+}
+
+__global__ __launch_bounds__(256) void jpeg_segment_kernel(const odic_jpeg_header* __restrict__ hdrs,
+                                                           const unsigned char* __restrict__ data, Ws ws,
+                                                           int subseq_bits) {
+  const odic_jpeg_header& h = hdrs[blockIdx.x];
+  const int t = threadIdx.x;
+  int* ib = ws.int_bits + h.int_off;
+  int* us = ws.unit_start + h.int_off;
+  int* state = ws.state + kStateWords * blockIdx.x;
+  const int nint = h.n_intervals;
+  __shared__ int sh_scan[256];
+  long carry_data;
+  int carry_marks;
+  const int err = segment_bytes(data + h.data_off, h.data_end - h.data_off, ws.scan + h.scan_off, ib, nint, true,
+                                carry_data, carry_marks);
+  if (t == 0 && err) state[0] |= kErrSegment;
   // units: interval k gets max(1, ceil(bits / subseq_bits)) of them
   int carry_u = 0;
   for (int k0 = 0; k0 < nint; k0 += 256) {
@@ -647,8 +660,9 @@ __device__ __forceinline__ unsigned range_limit(int x) {   // IDCT_range_limit[x
   return (unsigned)(s < 0 ? 0 : (s > 255 ? 255 : s));
 }
 
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
-  const odic_jpeg_header& h = hdrs[blockIdx.y];
+template <typename Header>                                      // odic_jpeg_header or odic_jpeg_prog_header
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const Header* __restrict__ hdrs, Ws ws) {
+  const Header& h = hdrs[blockIdx.y];
   const int nY = luma_blocks(h.sampling), bpm = nY + 2;
   const long nblocks = (long)h.mcus_x * h.mcus_y * bpm;
   const long b = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
@@ -711,10 +725,11 @@ constexpr int kCrR = 91881, kCbB = 116130, kCrG = 46802, kCbG = 22554;   // FIX(
 
 __device__ __forceinline__ unsigned char clamp255(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-__global__ __launch_bounds__(256) void jpeg_color_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws,
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const Header* __restrict__ hdrs, Ws ws,
                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
   const int img = blockIdx.z;
-  const odic_jpeg_header& h = hdrs[img];
+  const Header& h = hdrs[img];
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
   if (x == 0 && y == 0) {
     const int* st = ws.state + kStateWords * img;
@@ -757,6 +772,378 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const odic_jpeg_header*
   o[0] = clamp255(yv + ((kCrR * cr + 32768) >> 16));
   o[1] = clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
   o[2] = clamp255(yv + ((kCbB * cb + 32768) >> 16));
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------
+// Progressive files (SOF2).  The host parser (jpeg.parse_progressive) reads the whole scan script and packs one
+// odic_jpeg_prog_header per image, one odic_jpeg_scan per scan (sorted by dependency level) and the batch's distinct
+// Huffman tables.  Launches:
+//
+//   segment   one workgroup per scan: the byte classification and compaction of the baseline path on the scan's own
+//             byte range (the parser cut it at the closing marker), restart-interval start bits.
+//   decode    one launch per dependency level, one wave per (scan, restart interval): the four coding procedures of
+//             ITU T.81 G.1 / jdphuff.c, serial inside the interval.  Scans of one level touch disjoint coefficients
+//             of an image, so all of them, for all images, run concurrently.  DC scans apply the prediction while
+//             they decode (it resets at every interval), so the coefficient array holds libjpeg's values directly
+//             and the baseline path's DC kernel is not needed.
+//   idct / color   the baseline path's kernels on the same int16 natural-order coefficient array.
+//
+// Every lane of the wave runs the serial decode redundantly (uniform control flow, broadcast loads); what is
+// parallel is per coefficient.  AC refinement holds zig-zag coefficient `lane` of the block in lane `lane`: the mask
+// of already-nonzero coefficients is one ballot, a run of r zeros is r lowest-bit clears on the inverted mask, the
+// correction bit of a nonzero coefficient passed over sits at (bit position of the step) + (nonzero coefficients
+// passed before it), a popcount, and is fetched by that lane after the block's symbols are decoded.
+//
+// Bounds by construction, whatever the entropy data holds: a block ordinal is below the scan's n_units and its block
+// index is checked against the image's block count; a zig-zag index is checked against Se <= 63 before it is used;
+// the bit reader only advances while pos <= the interval's end, which keeps its look-ahead inside the 16 bytes reserved
+// behind every compacted scan, and correction bits are fetched only after pos <= end was checked for the whole block.
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(odic_jpeg_prog_header) == 432 && offsetof(odic_jpeg_prog_header, qt) == 48 &&
+                  sizeof(odic_jpeg_scan) == 88 && offsetof(odic_jpeg_scan, table) == 72 &&
+                  sizeof(odic_jpeg_table) == 1424 && offsetof(odic_jpeg_table, huffval) == 1168,
+              "the progressive records are mirrored by jpeg.PROG_HEADER_DTYPE / SCAN_DTYPE / TABLE_DTYPE");
+
+struct PTab {                      // one Huffman table in LDS
+  unsigned short lut[512];
+  int lim[8];                      // as Tabs::lim
+  int valoff[18];
+  unsigned char huffval[256];
+};
+
+__device__ void load_ptab(const odic_jpeg_table& g, PTab& T) {          // one wave
+  const int t = threadIdx.x;
+  for (int i = t; i < 512; i += 64) T.lut[i] = g.lut[i];
+  for (int i = t; i < 256; i += 64) T.huffval[i] = g.huffval[i];
+  if (t < 18) T.valoff[t] = g.valoff[t];
+  if (t == 0) {
+    int last = 0;
+    for (int l = 1; l <= 16; ++l) {
+      const int mc = g.maxcode[l];
+      if (mc >= 0) last = (mc + 1) << (16 - l);
+      if (l >= 9) T.lim[l - 9] = last;
+    }
+  }
+}
+
+__device__ __forceinline__ int huff1(const PTab& T, unsigned win, int& len) {      // as huff(), one table
+  const unsigned e = T.lut[win >> (32 - kLutBits)];
+  if (e) {
+    len = e >> 8;
+    return e & 255;
+  }
+  const int p16 = (int)(win >> 16);
+  int l = kLutBits + 1;
+#pragma unroll
+  for (int i = 1; i <= 7; ++i) l += p16 >= T.lim[i];
+  if (l > 16) return -1;
+  len = l;
+  return T.huffval[((p16 >> (16 - l)) + T.valoff[l]) & 255];
+}
+
+struct ScanCtx {
+  const unsigned* w;               // the scan's compacted words
+  short* coef;                     // the image's coefficient blocks
+  long nblocks;                    // ... and how many there are
+  int mcus_x, nY, bpm, hy, vy;
+  int u0, nu;                      // the interval's units (MCUs of an interleaved scan, else blocks of the component)
+  int pos, end;                    // its bit range
+  int mask, ss, se, al, bw;
+  int* state;
+};
+
+// block `n` of component c's own raster (bw blocks per row) → its block index in the MCU-ordered coefficient array
+__device__ __forceinline__ long raster_block(const ScanCtx& x, int c, int n) {
+  const int bx = n % x.bw, by = n / x.bw;
+  const int hh = c == 0 ? x.hy : 1, vv = c == 0 ? x.vy : 1;
+  const long mcu = (long)(by / vv) * x.mcus_x + bx / hh;
+  return mcu * x.bpm + (c == 0 ? 0 : x.nY + c - 1) + (by % vv) * hh + bx % hh;
+}
+
+__device__ __forceinline__ unsigned bit_at(const unsigned* __restrict__ w, int pos) {
+  return (__builtin_bswap32(w[pos >> 5]) >> (31 - (pos & 31))) & 1u;
+}
+
+// DC, first pass (G.1.2.1): difference coding, prediction reset at the interval's start, value << Al
+__device__ bool prog_dc_first(ScanCtx& x, const PTab* T) {
+  int pred[3] = {0, 0, 0};
+  Bits br{x.w, 0};
+  bits_seek(br, x.pos);
+  const bool single = (x.mask & (x.mask - 1)) == 0;
+  for (int u = x.u0; u < x.u0 + x.nu; ++u) {
+    int q = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (!((x.mask >> c) & 1)) continue;
+      const int nb = (c == 0 && !single) ? x.nY : 1;
+      for (int j = 0; j < nb; ++j) {
+        if (x.pos > x.end) return false;
+        const unsigned win = bits_peek(br, x.pos);
+        int len;
+        const int cat = huff1(T[q], win, len);
+        if (cat < 0 || cat > 15) return false;
+        const int diff = cat ? extend((win << len) >> (32 - cat), cat) : 0;
+        x.pos += len + cat;
+        pred[c] += diff;
+        const int v = pred[c] * (1 << x.al);
+        if (v < -32768 || v > 32767) atomicOr(&x.state[0], kErrRange);
+        const long b = single ? raster_block(x, c, u) : (long)u * x.bpm + (c == 0 ? 0 : x.nY + c - 1) + j;
+        if (b < 0 || b >= x.nblocks) return false;
+        if (threadIdx.x == 0) x.coef[b * 64] = (short)v;
+      }
+      ++q;
+    }
+  }
+  return x.pos <= x.end;
+}
+
+// DC, refinement (G.1.2.1): one raw bit per block, 64 blocks per step
+__device__ bool prog_dc_refine(ScanCtx& x) {
+  const bool single = (x.mask & (x.mask - 1)) == 0;
+  const int bps = single ? 1 : ((x.mask & 1) ? x.nY : 0) + ((x.mask >> 1) & 1) + ((x.mask >> 2) & 1);
+  const long nb = (long)x.nu * bps;
+  if (x.pos + nb > x.end) return false;
+  bool ok = true;
+  for (long i = threadIdx.x; i < nb; i += 64) {
+    long b;
+    if (single) {
+      b = raster_block(x, __builtin_ctz(x.mask), x.u0 + (int)i);
+    } else {
+      int idx = (int)(i % bps), j = 0;
+      for (int c = 0; c < 3; ++c) {
+        if (!((x.mask >> c) & 1)) continue;
+        const int n = c == 0 ? x.nY : 1;
+        if (idx < n) {
+          j = (c == 0 ? 0 : x.nY + c - 1) + idx;
+          break;
+        }
+        idx -= n;
+      }
+      b = (long)(x.u0 + i / bps) * x.bpm + j;
+    }
+    if (b < 0 || b >= x.nblocks) {
+      ok = false;
+      continue;
+    }
+    if (bit_at(x.w, x.pos + (int)i)) x.coef[b * 64] |= (short)(1 << x.al);
+  }
+  x.pos += (int)nb;
+  return __all(ok);
+}
+
+// AC, first pass (G.1.2.2): run/size symbols, ZRL, EOB runs carried across blocks (reset at the interval's start)
+__device__ bool prog_ac_first(ScanCtx& x, const PTab& T) {
+  const int c = __builtin_ctz(x.mask);
+  Bits br{x.w, 0};
+  bits_seek(br, x.pos);
+  int eobrun = 0;
+  const int nend = x.u0 + x.nu;
+  for (int n = x.u0; n < nend; ++n) {
+    if (eobrun > 0) {                                   // these blocks get nothing in this scan
+      const int skip = min(eobrun, nend - n);
+      eobrun -= skip;
+      n += skip - 1;
+      continue;
+    }
+    const long b = raster_block(x, c, n);
+    if (b < 0 || b >= x.nblocks) return false;
+    for (int k = x.ss; k <= x.se; ++k) {
+      if (x.pos > x.end) return false;
+      const unsigned win = bits_peek(br, x.pos);
+      int len;
+      const int rs = huff1(T, win, len);
+      if (rs < 0) return false;
+      const int r = rs >> 4, s = rs & 15;
+      if (s) {
+        k += r;
+        if (k > x.se) return false;                     // libjpeg would write outside the band
+        const int v = extend((win << len) >> (32 - s), s);
+        x.pos += len + s;
+        if (threadIdx.x == 0) x.coef[b * 64 + kNatural[k]] = (short)(v * (1 << x.al));
+      } else if (r == 15) {
+        k += 15;
+        x.pos += len;
+      } else {
+        eobrun = 1 << r;
+        if (r) eobrun += (int)((win << len) >> (32 - r));
+        x.pos += len + r;
+        --eobrun;                                       // this block is the run's first
+        break;
+      }
+    }
+  }
+  return x.pos <= x.end;
+}
+
+// AC, refinement (G.1.2.3).  Lane i holds zig-zag coefficient i of the block.
+__device__ bool prog_ac_refine(ScanCtx& x, const PTab& T) {
+  const int c = __builtin_ctz(x.mask);
+  const int lane = threadIdx.x;
+  const int nat = kNatural[lane];
+  const int p1 = 1 << x.al, m1 = -p1;
+  const unsigned long long band = (x.se == 63 ? ~0ull : (1ull << (x.se + 1)) - 1) & ~((1ull << x.ss) - 1);
+  const unsigned long long below = (1ull << lane) - 1;
+  Bits br{x.w, 0};
+  bits_seek(br, x.pos);
+  int eobrun = 0;
+  const int nend = x.u0 + x.nu;
+  long b = raster_block(x, c, x.u0);
+  if (b < 0 || b >= x.nblocks) return false;
+  int v = x.coef[b * 64 + nat];
+  for (int n = x.u0; n < nend; ++n) {
+    long bn = b;
+    int vn = 0;
+    if (n + 1 < nend) {                                 // the next block's coefficients are on their way meanwhile
+      bn = raster_block(x, c, n + 1);
+      if (bn < 0 || bn >= x.nblocks) return false;
+      vn = x.coef[bn * 64 + nat];
+    }
+    const unsigned long long nz = __ballot(v != 0) & band;
+    int cpos = -1, newv = 0;                            // this lane's correction bit / newly nonzero value
+    int k = x.ss;
+    if (eobrun == 0) {
+      while (k <= x.se) {
+        if (x.pos > x.end) return false;
+        const unsigned win = bits_peek(br, x.pos);
+        int len;
+        const int rs = huff1(T, win, len);
+        if (rs < 0) return false;
+        const int r = rs >> 4, s = rs & 15;
+        x.pos += len;
+        int sval = 0;
+        if (s) {
+          if (s != 1) return false;                     // libjpeg warns and carries on: the host's business
+          sval = ((win << len) >> 31) ? p1 : m1;
+          x.pos += 1;
+        } else if (r != 15) {
+          eobrun = 1 << r;
+          if (r) eobrun += (int)((win << len) >> (32 - r));
+          x.pos += r;
+          break;                                        // the rest of the block is the run's first block
+        }
+        const unsigned long long from = ~0ull << k;
+        unsigned long long z = ~nz & band & from;       // still-zero coefficients from k on
+        for (int q = 0; q < r; ++q) z &= z - 1;         // r of them are skipped
+        const int t = z ? __builtin_ctzll(z) : x.se + 1;
+        const unsigned long long passed = nz & from & (t >= 64 ? ~0ull : (1ull << t) - 1);
+        if ((passed >> lane) & 1) cpos = x.pos + __popcll(passed & below);
+        x.pos += __popcll(passed);
+        if (s) {
+          if (t > x.se) return false;                   // libjpeg would write outside the band
+          if (lane == t) newv = sval;
+        }
+        k = t + 1;
+      }
+    }
+    if (eobrun > 0) {                                   // only correction bits for the rest of the band
+      const unsigned long long passed = k <= 63 ? nz & (~0ull << k) : 0ull;
+      if ((passed >> lane) & 1) cpos = x.pos + __popcll(passed & below);
+      x.pos += __popcll(passed);
+      --eobrun;
+    }
+    if (x.pos > x.end) return false;                    // every cpos < pos <= end
+    if (cpos >= 0) {
+      if (bit_at(x.w, cpos) && (v & p1) == 0) x.coef[b * 64 + nat] = (short)(v + (v >= 0 ? p1 : m1));
+    } else if (newv) {
+      x.coef[b * 64 + nat] = (short)newv;
+    }
+    b = bn;
+    v = vn;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(256) void jpeg_prog_segment_kernel(const odic_jpeg_scan* __restrict__ scans,
+                                                                const unsigned char* __restrict__ data, Ws ws,
+                                                                int n_images) {
+  const odic_jpeg_scan& sc = scans[blockIdx.x];
+  if ((unsigned)sc.image >= (unsigned)n_images) return;
+  long carry_data;
+  int carry_marks;
+  const int err = segment_bytes(data + sc.data_off, sc.data_end - sc.data_off, ws.scan + sc.scan_off,
+                                ws.int_bits + sc.int_off, sc.n_intervals, false, carry_data, carry_marks);
+  if (threadIdx.x == 0 && err) atomicOr(&ws.state[kStateWords * sc.image], kErrSegment);
+}
+
+__global__ __launch_bounds__(64) void jpeg_prog_decode_kernel(const odic_jpeg_prog_header* __restrict__ hdrs,
+                                                              const odic_jpeg_scan* __restrict__ scans,
+                                                              const odic_jpeg_table* __restrict__ tables, Ws ws,
+                                                              int first, int n_images, int n_tables) {
+  const odic_jpeg_scan& sc = scans[first + blockIdx.y];
+  const int k = blockIdx.x;
+  if (k >= sc.n_intervals || (unsigned)sc.image >= (unsigned)n_images) return;
+  const odic_jpeg_prog_header& h = hdrs[sc.image];
+  int* state = ws.state + kStateWords * sc.image;
+  __shared__ PTab T[3];
+  const bool dc = sc.ss == 0, first_pass = sc.ah == 0;
+  const int ntab = dc ? (first_pass ? __popc(sc.comp_mask & 7) : 0) : 1;
+  bool ok = sc.restart > 0 && sc.n_units > 0 && (sc.comp_mask & 7) != 0 && sc.ss >= 0 && sc.ss <= sc.se &&
+            sc.se <= 63 && sc.al >= 0 && sc.al <= 13 && (dc || ((sc.comp_mask & (sc.comp_mask - 1)) == 0 && sc.blocks_w > 0));
+  for (int q = 0; q < ntab && ok; ++q) {
+    if ((unsigned)sc.table[q] >= (unsigned)n_tables) ok = false;
+    else load_ptab(tables[sc.table[q]], T[q]);
+  }
+  __syncthreads();
+  if (ok) {
+    const int* ib = ws.int_bits + sc.int_off;
+    ScanCtx x;
+    x.w = (const unsigned*)(ws.scan + sc.scan_off);
+    x.coef = ws.coef + h.coef_off * 64;
+    x.nY = luma_blocks(h.sampling);
+    x.bpm = x.nY + 2;
+    x.nblocks = (long)h.mcus_x * h.mcus_y * x.bpm;
+    x.mcus_x = h.mcus_x;
+    x.hy = h.sampling == 0 ? 1 : 2;
+    x.vy = h.sampling == 2 ? 2 : 1;
+    x.u0 = k * sc.restart;
+    x.nu = min(sc.restart, sc.n_units - x.u0);
+    x.pos = ib[k];
+    x.end = ib[k + 1];
+    x.mask = sc.comp_mask & 7;
+    x.ss = sc.ss;
+    x.se = sc.se;
+    x.al = sc.al;
+    x.bw = max(sc.blocks_w, 1);
+    x.state = state;
+    if (dc) ok = first_pass ? prog_dc_first(x, T) : prog_dc_refine(x);
+    else ok = first_pass ? prog_ac_first(x, T[0]) : prog_ac_refine(x, T[0]);
+  }
+  if (threadIdx.x == 0) {
+    if (ok) atomicAdd(&state[1], 1);
+    else atomicOr(&state[0], kErrDecode);
+  }
+}
+
+struct PLayout {
+  size_t state, scan, int_bits, coef, planes, total;
+};
+
+PLayout prog_layout(const odic_jpeg_prog_batch& b) {
+  PLayout L;
+  size_t o = 0;
+  L.state = o; o = align256(o + sizeof(int) * kStateWords * (size_t)b.n_images);
+  L.scan = o; o = align256(o + (size_t)b.total_scan_bytes);
+  L.int_bits = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
+  L.coef = o; o = align256(o + 128 * (size_t)b.total_blocks);
+  L.planes = o; o = align256(o + (size_t)b.total_plane_bytes);
+  L.total = o;
+  return L;
+}
+
+bool prog_batch_ok(const odic_jpeg_prog_batch* b) {
+  if (b->n_images <= 0 || b->n_images > 65535 || b->n_scans < b->n_images ||
+      (long)b->n_scans > (long)b->n_images * ODIC_JPEG_MAX_SCANS || b->n_tables <= 0 || b->n_levels <= 0 ||
+      b->n_levels > ODIC_JPEG_MAX_SCANS || b->max_width <= 0 || b->max_width > 65535 || b->max_height <= 0 ||
+      b->max_height > 65535 || b->max_blocks <= 0 || b->total_scan_bytes <= 0 || b->total_intervals <= 0 ||
+      b->total_intervals > 0x7fffffffL || b->total_blocks <= 0 || b->total_plane_bytes <= 0)
+    return false;
+  if (b->level_first[0] != 0 || b->level_first[b->n_levels] != b->n_scans) return false;
+  for (int l = 0; l < b->n_levels; ++l) {
+    const int n = b->level_first[l + 1] - b->level_first[l];
+    if (n <= 0 || n > 65535 || b->level_intervals[l] <= 0) return false;
+  }
+  return true;
 }
 
 }  // namespace
@@ -807,8 +1194,51 @@ extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_
   hipLaunchKernelGGL(jpeg_block_scan_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
   hipLaunchKernelGGL(jpeg_writeout_kernel, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
   hipLaunchKernelGGL(jpeg_dc_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs, ws);
-  hipLaunchKernelGGL(jpeg_color_kernel, dim3((b->max_width + 63) / 64, (b->max_height + 3) / 4, n), dim3(64, 4), 0, s,
+  hipLaunchKernelGGL(jpeg_idct_kernel<odic_jpeg_header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs, ws);
+  hipLaunchKernelGGL(jpeg_color_kernel<odic_jpeg_header>, dim3((b->max_width + 63) / 64, (b->max_height + 3) / 4, n), dim3(64, 4), 0, s,
                      hdrs, ws, b->out, b->status);
+  return odic_launch_status();
+}
+
+extern "C" size_t odic_jpeg_progressive_workspace_bytes(const odic_jpeg_prog_batch* b) {
+  if (!b || !prog_batch_ok(b)) return 0;
+  return prog_layout(*b).total;
+}
+
+extern "C" size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* b) {
+  if (!b || !prog_batch_ok(b)) return 0;
+  return prog_layout(*b).coef;
+}
+
+extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
+                                            void* stream) {
+  if (!b || !b->headers || !b->scans || !b->tables || !b->data || !b->out || !b->status || !workspace)
+    return ODIC_ENULL;
+  if (!prog_batch_ok(b)) return ODIC_EINVAL;
+  const PLayout L = prog_layout(*b);
+  if (ws_bytes < L.total) return ODIC_EINVAL;
+  unsigned char* base = (unsigned char*)workspace;
+  Ws ws{};
+  ws.state = (int*)(base + L.state);
+  ws.scan = base + L.scan;
+  ws.int_bits = (int*)(base + L.int_bits);
+  ws.coef = (short*)(base + L.coef);
+  ws.planes = base + L.planes;
+  hipStream_t s = (hipStream_t)stream;
+  const auto* hdrs = (const odic_jpeg_prog_header*)b->headers;
+  const auto* scans = (const odic_jpeg_scan*)b->scans;
+  const auto* tables = (const odic_jpeg_table*)b->tables;
+  const int n = b->n_images;
+  hipError_t e = hipMemsetAsync(base, 0, L.scan, s);                      // state
+  if (e == hipSuccess) e = hipMemsetAsync(ws.coef, 0, L.planes - L.coef, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(jpeg_prog_segment_kernel, dim3(b->n_scans), dim3(256), 0, s, scans, b->data, ws, n);
+  for (int l = 0; l < b->n_levels; ++l)
+    hipLaunchKernelGGL(jpeg_prog_decode_kernel, dim3(b->level_intervals[l], b->level_first[l + 1] - b->level_first[l]),
+                       dim3(64), 0, s, hdrs, scans, tables, ws, b->level_first[l], n, b->n_tables);
+  hipLaunchKernelGGL(jpeg_idct_kernel<odic_jpeg_prog_header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256),
+                     0, s, hdrs, ws);
+  hipLaunchKernelGGL(jpeg_color_kernel<odic_jpeg_prog_header>, dim3((b->max_width + 63) / 64, (b->max_height + 3) / 4, n),
+                     dim3(64, 4), 0, s, hdrs, ws, b->out, b->status);
   return odic_launch_status();
 }

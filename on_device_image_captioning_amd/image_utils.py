@@ -32,10 +32,11 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # =================================================================================================
 # Device-side pipeline: resize + ToTensor + Normalize on the GPU, bit-exact with the
 # PIL / torch path above; pinned double-buffered uploads so the copy of image i+1 overlaps the
-# kernels of image i.  Baseline JPEGs can also be decoded on the GPU (odic_jpeg_decode, csrc/jpeg_decode.hip),
-# bit-exact with PIL: `from_jpeg_bytes` / `from_files(..., decode="device")`.  Files the device decoder does not
-# take (progressive, non-JPEG, ...) and images whose entropy data fails to decode are decoded by PIL in the same
-# call, so the result and the exceptions are those of the host path.
+# kernels of image i.  Baseline and progressive JPEGs can also be decoded on the GPU (odic_jpeg_decode /
+# odic_jpeg_decode_progressive, csrc/jpeg_decode.hip), bit-exact with PIL: `from_jpeg_bytes` /
+# `from_files(..., decode="device")`.  Files the device decoder does not take (arithmetic coding, non-JPEG, ...)
+# and images whose entropy data fails to decode are decoded by PIL in the same call, so the result and the
+# exceptions are those of the host path.
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -91,6 +92,7 @@ class DevicePreprocessor:
         self._jpeg_ev = torch.cuda.Event()
         self._jpeg_pinned = self._jpeg_dev = self._jpeg_ws = self._jpeg_status = None
         self._jpeg_tmp = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._jpeg_routes, self._jpeg_prog_coef = [], None
         self._mean = (ctypes.c_float * 3)(*_MEAN)
         self._std = (ctypes.c_float * 3)(*_STD)
 
@@ -172,27 +174,58 @@ class DevicePreprocessor:
             return buf
         return torch.empty(max(nbytes, 2 * (buf.numel() if buf is not None else 0)), dtype=torch.uint8, **kw)
 
-    def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4):
+    @property
+    def last_routes(self):
+        """How each file of the last `decode_jpeg` / `from_jpeg_bytes` call was decoded, in input order: "device" (baseline,
+        odic_jpeg_decode), "device-progressive" (odic_jpeg_decode_progressive), "host" (PIL: a kind the device does not
+        take), "host-after-status" (the device reported status 1 and PIL decoded the file again) or "black"."""
+        return tuple(self._jpeg_routes)
+
+    def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host"):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
         np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path).  Baseline JPEGs are
-        decoded by odic_jpeg_decode in one batched call (one host-to-device copy, one status read-back); the rest,
-        and images the device rejects, by PIL.  Exceptions are the host path's, in its order: PIL's, file by file,
-        then the size check of `__call__`.  Ordered after the work on the CURRENT stream."""
+        decoded by odic_jpeg_decode and, with progressive="device", progressive ones by odic_jpeg_decode_progressive
+        (the default "host" sends them to PIL until the device route is measured faster), each kind in one batched call, with one host-to-device copy and one status read-back
+        for both; the rest, and images the device rejects, by PIL.  Exceptions are the host path's, in its order: PIL's,
+        file by file, then the size check of `__call__`.  Ordered after the work on the CURRENT stream."""
         from . import jpeg as J
+        if progressive not in ("device", "host"):
+            raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
         blobs = [bytes(b) for b in blobs]
         hdrs = [J.parse(b) for b in blobs]
+        if progressive == "device":
+            for i, h in enumerate(hdrs):
+                if h.kind == J.HOST and h.reason == "SOF2":
+                    ph = J.parse_progressive(blobs[i])
+                    if ph.kind == J.DEVICE:
+                        hdrs[i] = ph
         out = [None] * len(blobs)
+        routes = [h.kind for h in hdrs]
         # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
         dev = [i for i, h in enumerate(hdrs)
                if h.kind == J.DEVICE and h.width * h.height * 3 <= self.max_bytes]
+        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader)]
+        prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader)]
+        for i, h in enumerate(hdrs):
+            if h.kind == J.DEVICE:
+                routes[i] = "host"                                       # oversized
+        for i in prog:
+            routes[i] = "device-progressive"
+        for i in base:
+            routes[i] = "device"
         if dev:
-            status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in dev], [blobs[i] for i in dev],
+            order = base + prog
+            status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
+                                                           [hdrs[i] for i in prog], [blobs[i] for i in prog],
                                                            subseq_bits, max_sync_passes)
-            for k, i in enumerate(dev):
+            for k, i in enumerate(order):
                 h = hdrs[i]
                 if status[k] == 0:
                     n = h.width * h.height * 3
                     out[i] = rgb[out_offs[k]:out_offs[k] + n].view(h.height, h.width, 3)
+                else:
+                    routes[i] = "host-after-status"
+        self._jpeg_routes = routes
         for i, h in enumerate(hdrs):                                     # input order, as the host path
             if h.kind != J.BLACK and out[i] is None:
                 out[i] = self._host_rgb(blobs[i])
@@ -206,33 +239,74 @@ class DevicePreprocessor:
                     out[i] = torch.from_numpy(out[i].copy()).to(self.device)
         return out
 
-    def _decode_on_device(self, hdrs, blobs, subseq_bits, max_sync_passes):
-        """One odic_jpeg_decode call → (per-image status numpy int32, uint8 RGB buffer, byte offset per image)."""
+    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes):
+        """One odic_jpeg_decode call for the baseline files and one odic_jpeg_decode_progressive call for the progressive
+        ones, sharing one upload, one output buffer, one workspace and one status read-back → (status numpy int32 —
+        baseline files first —, uint8 RGB buffer, byte offset per image)."""
         from . import jpeg as J
-        hdr_bytes = (len(hdrs) * J.HEADER_DTYPE.itemsize + 255) // 256 * 256
-        offs, ends, pos = [], [], 0
+
+        def pad(n):
+            return (n + 255) // 256 * 256
+
+        nb, npg = len(hdrs), len(phdrs)
+        offs, ends, poffs = [], [], []
+        sections, pos = [], 0                                            # (staging offset, record array)
+        if nb:
+            pos = pad(nb * J.HEADER_DTYPE.itemsize)
+        if npg:
+            prec, srec, trec, ptot, pout_offs, pout_bytes = J.pack_progressive(phdrs, [0] * npg)   # sizes only, for now
+            prog_off = (pos, pos + pad(prec.nbytes), pos + pad(prec.nbytes) + pad(srec.nbytes))
+            pos = prog_off[2] + pad(trec.nbytes)
+        data_off = pos
+        pos = 0
         for h, blob in zip(hdrs, blobs):
             offs.append(pos + h.data_offset)
             pos += len(blob)
             ends.append(pos)
-        rec, tot, out_offs, out_bytes = J.pack_headers(hdrs, offs, ends, subseq_bits)
-        total = hdr_bytes + pos
+        for blob in pblobs:
+            poffs.append(pos)
+            pos += len(blob)
+        total = data_off + pos
+        out_offs, out_bytes = [], 0
+        if nb:
+            rec, tot, out_offs, out_bytes = J.pack_headers(hdrs, offs, ends, subseq_bits)
+            sections.append((0, rec))
+        if npg:
+            srec["data_off"] += np.asarray(poffs, np.int64)[srec["image"]]
+            srec["data_end"] += np.asarray(poffs, np.int64)[srec["image"]]
+            sections += list(zip(prog_off, (prec, srec, trec)))
+            out_offs = out_offs + [out_bytes + o for o in pout_offs]
         self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
         self._jpeg_pinned = self._grow(self._jpeg_pinned, total, pin_memory=True)
-        self._jpeg_status = self._grow(self._jpeg_status, 4 * len(hdrs), pin_memory=True)
+        self._jpeg_status = self._grow(self._jpeg_status, 4 * (nb + npg), pin_memory=True)
         host = self._jpeg_pinned.numpy()
-        host[:rec.nbytes] = np.frombuffer(rec.tobytes(), np.uint8)
-        p = hdr_bytes
-        for blob in blobs:
+        for o, r in sections:
+            host[o:o + r.nbytes] = np.frombuffer(r.tobytes(), np.uint8)
+        p = data_off
+        for blob in list(blobs) + list(pblobs):
             host[p:p + len(blob)] = np.frombuffer(blob, np.uint8)
             p += len(blob)
-        rgb = torch.empty(max(out_bytes, 1), dtype=torch.uint8, device=self.device)
-        status = torch.empty(len(hdrs), dtype=torch.int32, device=self.device)
-        b = self._hip.JpegBatch()
-        b.n_images, b.subseq_bits, b.max_sync_passes = len(hdrs), subseq_bits, max_sync_passes
-        for k, v in tot.items():
-            setattr(b, k, v)
-        need = self.lib.odic_jpeg_workspace_bytes(ctypes.byref(b))
+        rgb = torch.empty(max(out_bytes + (pout_bytes if npg else 0), 1), dtype=torch.uint8, device=self.device)
+        status = torch.empty(nb + npg, dtype=torch.int32, device=self.device)
+        need = 0
+        if nb:
+            b = self._hip.JpegBatch()
+            b.n_images, b.subseq_bits, b.max_sync_passes = nb, subseq_bits, max_sync_passes
+            for k, v in tot.items():
+                setattr(b, k, v)
+            need = need_b = self.lib.odic_jpeg_workspace_bytes(ctypes.byref(b))
+        if npg:
+            pb = self._hip.JpegProgBatch()
+            pb.n_images = npg
+            for k, v in ptot.items():
+                if isinstance(v, list):
+                    getattr(pb, k)[:len(v)] = v
+                else:
+                    setattr(pb, k, v)
+            need_p = self.lib.odic_jpeg_progressive_workspace_bytes(ctypes.byref(pb))
+            if need_p == 0:
+                raise RuntimeError("JPEG batch too large for one progressive decode call")
+            need = max(need, need_p)
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             self._jpeg_dev = self._grow(self._jpeg_dev, total, device=self.device)
@@ -240,19 +314,36 @@ class DevicePreprocessor:
             self._jpeg_dev[:total].copy_(self._jpeg_pinned[:total], non_blocking=True)
             self._jpeg_ev.record(self.stream)
             base = self._jpeg_dev.data_ptr()
-            b.headers, b.data, b.out, b.status = base, base + hdr_bytes, rgb.data_ptr(), status.data_ptr()
-            self._hip.check(self.lib.odic_jpeg_decode(ctypes.byref(b), self._jpeg_ws.data_ptr(), need,
-                                                      self.stream.cuda_stream), "odic_jpeg_decode")
-            st = self._jpeg_status[:4 * len(hdrs)].view(torch.int32)
+            if nb:
+                b.headers, b.data, b.out, b.status = base, base + data_off, rgb.data_ptr(), status.data_ptr()
+                self._hip.check(self.lib.odic_jpeg_decode(ctypes.byref(b), self._jpeg_ws.data_ptr(), need_b,
+                                                          self.stream.cuda_stream), "odic_jpeg_decode")
+            if npg:                                                      # second: its coefficients stay in the workspace
+                pb.headers, pb.scans, pb.tables = (base + o for o in prog_off)
+                pb.data, pb.out, pb.status = base + data_off, rgb.data_ptr() + out_bytes, status.data_ptr() + 4 * nb
+                self._hip.check(self.lib.odic_jpeg_decode_progressive(ctypes.byref(pb), self._jpeg_ws.data_ptr(), need_p,
+                                                                      self.stream.cuda_stream),
+                                "odic_jpeg_decode_progressive")
+                self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(pb)),
+                                        [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])])
+            st = self._jpeg_status[:4 * (nb + npg)].view(torch.int32)
             st.copy_(status, non_blocking=True)
         self.stream.synchronize()                                        # the one host synchronisation
         torch.cuda.current_stream().wait_stream(self.stream)
         return st.numpy().copy(), rgb, out_offs
 
-    def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4) -> torch.Tensor:
+    def progressive_coefficients(self, k: int) -> torch.Tensor:
+        """Diagnostic: the int16 [blocks, 64] natural-order coefficients (MCU by MCU, DC as its value) of the k-th file
+        routed "device-progressive" in the last call, read from the workspace; valid until the next call."""
+        byte_off, blocks = self._jpeg_prog_coef
+        lo, hi = byte_off + 128 * blocks[k], byte_off + 128 * blocks[k + 1]
+        return self._jpeg_ws[lo:hi].view(torch.int16).view(-1, 64).clone()
+
+    def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
+                        progressive: str = "host") -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
         torch.equal to `from_files` on the same files."""
-        imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes)
+        imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive)
         S = self.S
         out = torch.empty(len(imgs), 3, S, S, dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream())

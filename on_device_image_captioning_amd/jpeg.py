@@ -14,6 +14,9 @@ goes to PIL, which then raises or decodes exactly as the host path does:
             an all-black RGB canvas of the same size
     host    everything else (progressive, arithmetic, 12-bit, lossless, Adobe RGB, multi-scan, DNL,
             non-JPEG data, malformed or truncated headers, more than MAX_SCAN_BYTES after SOS)
+
+`parse` keeps that sorting.  For the files it turns away with reason "SOF2", `parse_progressive` (below) reads the whole
+scan script, locating every scan's end in the file, and packs the records odic_jpeg_decode_progressive reads.
 """
 from __future__ import annotations
 
@@ -96,6 +99,47 @@ def parse(blob) -> JpegHeader:
         return JpegHeader(HOST, reason=f"malformed: {e}")
 
 
+def _read_dqt(s, qt):
+    """One DQT segment → qt[id] = int32[64] in natural order."""
+    j = 0
+    while j < len(s):
+        pq, tq = s[j] >> 4, s[j] & 15
+        if pq > 1 or tq > 3:
+            raise _Bad("bad DQT")
+        size = 64 * (pq + 1)
+        if j + 1 + size > len(s):
+            raise _Bad("bad DQT length")
+        raw = np.frombuffer(s, dtype=">u2" if pq else "u1", count=64, offset=j + 1).astype(np.int32)
+        nat = np.zeros(64, np.int32)
+        nat[NATURAL_ORDER] = raw
+        qt[tq] = nat
+        j += 1 + size
+
+
+def _read_dht(s, dht):
+    """One DHT segment → dht[(class, id)] = HuffTable."""
+    j = 0
+    while j < len(s):
+        tc, th = s[j] >> 4, s[j] & 15
+        if tc > 1 or th > 3 or j + 17 > len(s):
+            raise _Bad("bad DHT")
+        bits = list(s[j + 1:j + 17])
+        cnt = sum(bits)
+        if cnt > 256 or j + 17 + cnt > len(s):
+            raise _Bad("bad DHT length")
+        vals = s[j + 17:j + 17 + cnt]
+        code = 0
+        for length in range(1, 17):                   # libjpeg jpeg_make_d_derived_tbl checks
+            code += bits[length - 1]
+            if code >= (1 << length):
+                raise _Bad("bad Huffman table")
+            code <<= 1
+        if tc == 0 and any(v > 15 for v in vals):
+            raise _Bad("bad DC symbol")
+        dht[(tc, th)] = HuffTable(bits, vals)
+        j += 17 + cnt
+
+
 def _parse(b) -> JpegHeader:
     n = len(b)
     if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
@@ -130,40 +174,9 @@ def _parse(b) -> JpegHeader:
             if len(s) >= 12 and s[:5] == b"Adobe":             # libjpeg: APP14_DATA_LEN
                 adobe, adobe_transform = True, s[11]
         elif m == 0xDB:
-            j = 0
-            while j < len(s):
-                pq, tq = s[j] >> 4, s[j] & 15
-                if pq > 1 or tq > 3:
-                    raise _Bad("bad DQT")
-                size = 64 * (pq + 1)
-                if j + 1 + size > len(s):
-                    raise _Bad("bad DQT length")
-                raw = np.frombuffer(s, dtype=">u2" if pq else "u1", count=64, offset=j + 1).astype(np.int32)
-                nat = np.zeros(64, np.int32)
-                nat[NATURAL_ORDER] = raw
-                qt[tq] = nat
-                j += 1 + size
+            _read_dqt(s, qt)
         elif m == 0xC4:
-            j = 0
-            while j < len(s):
-                tc, th = s[j] >> 4, s[j] & 15
-                if tc > 1 or th > 3 or j + 17 > len(s):
-                    raise _Bad("bad DHT")
-                bits = list(s[j + 1:j + 17])
-                cnt = sum(bits)
-                if cnt > 256 or j + 17 + cnt > len(s):
-                    raise _Bad("bad DHT length")
-                vals = s[j + 17:j + 17 + cnt]
-                code = 0
-                for length in range(1, 17):                   # libjpeg jpeg_make_d_derived_tbl checks
-                    code += bits[length - 1]
-                    if code >= (1 << length):
-                        raise _Bad("bad Huffman table")
-                    code <<= 1
-                if tc == 0 and any(v > 15 for v in vals):
-                    raise _Bad("bad DC symbol")
-                dht[(tc, th)] = HuffTable(bits, vals)
-                j += 17 + cnt
+            _read_dht(s, dht)
         elif m == 0xDD:
             if len(s) != 2:
                 raise _Bad("bad DRI")
@@ -333,3 +346,343 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits):
             or tot["max_scan_bytes"] > MAX_SCAN_BYTES):
         raise RuntimeError("JPEG batch too large for one decode call")
     return rec, tot, out_offs, out_bytes
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Progressive files (SOF2): `parse` turns them away with reason "SOF2"; `parse_progressive` reads the whole scan
+# script and either understands it completely or says "host" with a reason.
+#
+# device  8-bit SOF2 Huffman, three YCbCr components under the rules of `parse`, any scan script libjpeg accepts
+#         without a warning and that leaves every coefficient of every component at full precision by EOI
+#         (libjpeg's inter-block smoothing only runs for incomplete scripts), DHT / DRI redefined between scans,
+#         at most MAX_SCANS scans
+# host    everything else: bogus progressions, AC before DC, an incomplete script, DQT or any other marker
+#         between scans, DNL, a scan cut short or a missing EOI, more than MAX_SCANS scans
+# ---------------------------------------------------------------------------------------------------------------
+MAX_SCANS = 64                     # ODIC_JPEG_MAX_SCANS: libjpeg's standard script has 10; arbitrary ones rarely more
+
+# odic_jpeg_prog_header / odic_jpeg_scan / odic_jpeg_table (include/odic_hip.h), field for field
+PROG_HEADER_DTYPE = np.dtype([
+    ("out_off", "<i8"), ("coef_off", "<i8"), ("plane_off", "<i8"),
+    ("width", "<i4"), ("height", "<i4"), ("sampling", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"),
+    ("n_intervals", "<i4"), ("qt", "<u2", (3, 64)),
+], align=True)
+SCAN_DTYPE = np.dtype([
+    ("data_off", "<i8"), ("data_end", "<i8"), ("scan_off", "<i8"),
+    ("image", "<i4"), ("int_off", "<i4"), ("n_intervals", "<i4"), ("restart", "<i4"), ("n_units", "<i4"),
+    ("blocks_w", "<i4"), ("comp_mask", "<i4"), ("ss", "<i4"), ("se", "<i4"), ("ah", "<i4"), ("al", "<i4"),
+    ("level", "<i4"), ("table", "<i4", (3,)), ("pad", "<i4"),
+], align=True)
+TABLE_DTYPE = np.dtype([
+    ("lut", "<u2", (512,)), ("maxcode", "<i4", (18,)), ("valoff", "<i4", (18,)), ("huffval", "u1", (256,)),
+], align=True)
+
+
+@dataclass
+class ProgScan:
+    comps: list                    # frame component indices, in frame order
+    ss: int
+    se: int
+    ah: int
+    al: int
+    restart_interval: int          # DRI in effect for this scan (0: none)
+    dc_tables: list                # HuffTable per component of a first DC scan, else None
+    ac_table: object               # HuffTable of an AC scan, else None
+    data_offset: int               # entropy-coded bytes [data_offset, data_end) of the file;
+    data_end: int                  # data_end is the first marker that is neither stuffing nor RSTn
+    level: int = 1                 # dependency level (1-based)
+    n_units: int = 0               # what the scan walks: MCUs (interleaved) or the component's own blocks
+    blocks_w: int = 0              # blocks per row of that component's raster (single-component scans)
+
+    @property
+    def n_intervals(self):
+        return -(-self.n_units // (self.restart_interval or self.n_units))
+
+
+@dataclass
+class ProgHeader(JpegHeader):
+    scans: list = field(default_factory=list)
+
+    @property
+    def n_levels(self):
+        return max((s.level for s in self.scans), default=0)
+
+
+def marker_positions(blob) -> np.ndarray:
+    """Offsets of every 0xFF that is followed by something other than 0x00 (stuffing), RSTn or another 0xFF: inside
+    entropy-coded data these are exactly the markers that end a scan.  Vectorised over the whole file."""
+    a = np.frombuffer(blob, np.uint8)
+    ff = np.flatnonzero(a[:-1] == 0xFF)                  # few: one byte in some hundreds
+    nx = a[ff + 1]
+    return ff[(nx != 0) & (nx != 0xFF) & ((nx & 0xF8) != 0xD0)]
+
+
+def parse_progressive(blob) -> ProgHeader:
+    """The whole scan script of a progressive file → ProgHeader of kind DEVICE, or HOST with a reason (BLACK for
+    one and four components, as `parse`); never raises."""
+    try:
+        return _parse_progressive(bytes(blob))
+    except _Bad as e:
+        return ProgHeader(HOST, reason=str(e))
+    except (IndexError, ValueError) as e:
+        return ProgHeader(HOST, reason=f"malformed: {e}")
+
+
+def _parse_progressive(b) -> ProgHeader:
+    n = len(b)
+    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        raise _Bad("not a JPEG")
+    i = 2
+    qt, dht = {}, {}
+    jfif = adobe = False
+    adobe_transform = None
+    sof = None
+    dri = 0
+    hd = None                                      # set at the first SOS
+    coef_bits = None                               # [3][64] current Al of every coefficient, -1: not yet sent (lists)
+    marks = None
+    while True:
+        if i + 2 > n:
+            raise _Bad("truncated")
+        if b[i] != 0xFF:
+            raise _Bad("junk between markers")
+        m = b[i + 1]
+        if m == 0xFF:
+            i += 1
+            continue
+        if m == 0xD9:
+            if hd is None:
+                raise _Bad("EOI before SOS")
+            break
+        if m in (0xD8, 0x01) or 0xD0 <= m <= 0xD7:
+            raise _Bad(f"unexpected marker {m:02X}")
+        seg_len = _u16(b, i + 2)
+        if seg_len < 2 or i + 2 + seg_len > n:
+            raise _Bad("truncated segment")
+        s = b[i + 4:i + 2 + seg_len]
+        i += 2 + seg_len
+        if m == 0xC4:
+            _read_dht(s, dht)
+        elif m == 0xDD:
+            if len(s) != 2:
+                raise _Bad("bad DRI")
+            dri = (s[0] << 8) | s[1]
+        elif 0xE0 <= m <= 0xEF or m == 0xFE:
+            if hd is None and m == 0xE0 and len(s) >= 14 and s[:5] == b"JFIF\x00":
+                jfif = True
+            elif hd is None and m == 0xEE and len(s) >= 12 and s[:5] == b"Adobe":
+                adobe, adobe_transform = True, s[11]
+        elif hd is not None and m != 0xDA:
+            raise _Bad(f"marker {m:02X} between scans")      # DQT (latched per component by libjpeg), DNL, ...
+        elif m == 0xDB:
+            _read_dqt(s, qt)
+        elif 0xC0 <= m <= 0xCF and m not in (0xC8, 0xCC):
+            if sof is not None:
+                raise _Bad("second SOF")
+            if len(s) < 6:
+                raise _Bad("short SOF")
+            nc = s[5]
+            if len(s) != 6 + 3 * nc:
+                raise _Bad("bad SOF length")
+            sof = (m, s[0], _u16(s, 1), _u16(s, 3), nc,
+                   [(s[6 + 3 * k], s[7 + 3 * k] >> 4, s[7 + 3 * k] & 15, s[8 + 3 * k]) for k in range(nc)])
+        elif m == 0xDA:
+            if hd is None:
+                hd = _progressive_frame(sof, jfif, adobe, adobe_transform, qt)
+                if hd.kind != DEVICE:
+                    return hd
+                coef_bits = [[-1] * 64 for _ in range(3)]
+                marks = marker_positions(b)
+            if len(hd.scans) >= MAX_SCANS:
+                raise _Bad(f"more than {MAX_SCANS} scans")
+            sc = _progressive_scan(hd, s, dht, dri, coef_bits)
+            k = int(np.searchsorted(marks, i))
+            if k >= len(marks):
+                raise _Bad("truncated scan")
+            sc.data_offset, sc.data_end = i, int(marks[k])
+            if sc.data_end - sc.data_offset > MAX_SCAN_BYTES:
+                raise _Bad("scan longer than the device decoder's bit positions allow")
+            hd.scans.append(sc)
+            i = sc.data_end
+        else:
+            raise _Bad(f"marker {m:02X}")
+    if any(any(row) for row in coef_bits):
+        raise _Bad("incomplete scan script")             # libjpeg smooths across blocks: not a plain decode
+    _dependency_levels(hd.scans)
+    return hd
+
+
+def _progressive_frame(sof, jfif, adobe, adobe_transform, qt) -> ProgHeader:
+    if sof is None:
+        raise _Bad("SOS before SOF")
+    m, prec, height, width, nc, comps = sof
+    if prec != 8:
+        raise _Bad(f"{prec}-bit")
+    if nc not in (1, 3, 4):
+        raise _Bad(f"{nc} components")
+    if nc in (1, 4) and m in (0xC0, 0xC1, 0xC2):
+        if width == 0 or height == 0:
+            raise _Bad("empty frame")
+        return ProgHeader(BLACK, width=width, height=height, ncomp=nc)
+    if m != 0xC2:
+        raise _Bad(f"SOF{m - 0xC0}")
+    if width == 0 or height == 0:
+        raise _Bad("DNL / empty frame")
+    ids = [c[0] for c in comps]
+    if jfif:
+        ycc = True
+    elif adobe:
+        ycc = adobe_transform == 1
+    else:
+        ycc = ids == [1, 2, 3]
+    if not ycc:
+        raise _Bad("not YCbCr")
+    if len(set(ids)) != 3:
+        raise _Bad("duplicate component ids")
+    hv = [(c[1], c[2]) for c in comps]
+    if hv[1] != (1, 1) or hv[2] != (1, 1) or hv[0] not in SAMPLING:
+        raise _Bad(f"sampling {hv}")
+    qts = []
+    for c in comps:
+        if c[3] not in qt:
+            raise _Bad("missing DQT")
+        qts.append(qt[c[3]])
+    return ProgHeader(DEVICE, width=width, height=height, ncomp=3, sampling=SAMPLING[hv[0]], comp_ids=ids,
+                      comp_hv=hv, qtables=qts)
+
+
+def _progressive_scan(hd, s, dht, dri, coef_bits) -> ProgScan:
+    """One SOS header under libjpeg's rules (jdmarker.c get_sos, jdphuff.c start_pass_phuff_decoder): whatever
+    makes libjpeg warn goes to the host."""
+    ns = s[0] if len(s) >= 1 else 0
+    if ns < 1 or ns > 3 or len(s) != 1 + 2 * ns + 3:
+        raise _Bad("bad SOS")
+    sel = [(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(ns)]
+    try:
+        comps = [hd.comp_ids.index(x[0]) for x in sel]
+    except ValueError:
+        raise _Bad("scan names an unknown component") from None
+    if comps != sorted(set(comps)):
+        raise _Bad("scan component order")
+    ss, se, ah, al = s[1 + 2 * ns], s[2 + 2 * ns], s[3 + 2 * ns] >> 4, s[3 + 2 * ns] & 15
+    if ss == 0:
+        if se != 0:
+            raise _Bad("bogus progression: DC scan with Se > 0")
+    elif se < ss or se > 63 or ns != 1:
+        raise _Bad("bogus progression: AC band")
+    if al > 13 or (ah != 0 and al != ah - 1):
+        raise _Bad("bogus progression: successive approximation")
+    for c in comps:
+        if ss != 0 and coef_bits[c][0] < 0:
+            raise _Bad("AC scan before DC")
+        have = coef_bits[c][ss:se + 1]
+        if have.count(ah if ah else -1) + (0 if ah else have.count(0)) != len(have):
+            raise _Bad("bogus progression: Ah does not continue the previous scan")
+        coef_bits[c][ss:se + 1] = [al] * len(have)
+    dcs, ac = [None] * ns, None
+    if ss == 0 and ah == 0:
+        for k in range(ns):
+            if (0, sel[k][1]) not in dht:
+                raise _Bad("missing DHT")
+            dcs[k] = dht[(0, sel[k][1])]
+    elif ss != 0:
+        if (1, sel[0][2]) not in dht:
+            raise _Bad("missing DHT")
+        ac = dht[(1, sel[0][2])]
+    sc = ProgScan(comps, ss, se, ah, al, dri, dcs, ac, 0, 0)
+    if ns > 1:
+        sc.n_units = hd.mcus_x * hd.mcus_y
+    else:
+        h, v = hd.comp_hv[comps[0]]
+        hmax, vmax = hd.comp_hv[0]
+        sc.blocks_w = -(-(-(-hd.width * h // hmax)) // 8)
+        sc.n_units = sc.blocks_w * -(-(-(-hd.height * v // vmax)) // 8)
+    return sc
+
+
+def _dependency_levels(scans):
+    """level = 1 + the highest level of an earlier scan that shares a component and overlaps its band (DC scans are
+    band 0).  An AC scan also waits for the first DC scan of its component, the order libjpeg insists on.  Scans of
+    one level touch disjoint coefficients and decode concurrently."""
+    for k, sc in enumerate(scans):
+        lvl = 0
+        for prev in scans[:k]:
+            if not set(prev.comps) & set(sc.comps):
+                continue
+            if (prev.ss <= sc.se and sc.ss <= prev.se) or (sc.ss > 0 and prev.ss == 0 and prev.ah == 0):
+                lvl = max(lvl, prev.level)
+        sc.level = lvl + 1
+
+
+def pack_progressive(hdrs, blob_offs):
+    """Header, scan and table records + batch totals for progressive headers whose files start at blob_offs inside
+    the batch's data buffer.  Scans are sorted by level (stable), which is how odic_jpeg_decode_progressive walks
+    them.  → (headers PROG_HEADER_DTYPE [n], scans SCAN_DTYPE [m], tables TABLE_DTYPE [t], totals dict with
+    level_first / level_intervals lists, output byte offsets, output bytes)."""
+    n = len(hdrs)
+    rec = np.zeros(n, PROG_HEADER_DTYPE)
+    tot = dict(total_scan_bytes=0, total_intervals=0, total_blocks=0, total_plane_bytes=0, max_width=1, max_height=1,
+               max_blocks=1)
+    tables, table_ix, flat = [], {}, []
+    out_offs, out_bytes = [], 0
+
+    def table(t):
+        key = (bytes(t.bits), bytes(t.vals))
+        if key not in table_ix:
+            table_ix[key] = len(tables)
+            tables.append(device_tables(t))
+        return table_ix[key]
+
+    for k, h in enumerate(hdrs):
+        r = rec[k]
+        nmcu = h.mcus_x * h.mcus_y
+        hy, vy = h.comp_hv[0]
+        bpm = hy * vy + 2
+        plane = nmcu * 64 * bpm
+        r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
+        r["width"], r["height"], r["sampling"], r["mcus_x"], r["mcus_y"] = h.width, h.height, h.sampling, h.mcus_x, \
+            h.mcus_y
+        r["n_intervals"] = sum(s.n_intervals for s in h.scans)
+        for c in range(3):
+            r["qt"][c] = h.qtables[c]
+        flat += [(s.level, k, s) for s in h.scans]
+        out_offs.append(out_bytes)
+        out_bytes += h.width * h.height * 3
+        tot["total_blocks"] += nmcu * bpm
+        tot["total_plane_bytes"] += (plane + 15) // 16 * 16
+        tot["max_width"] = max(tot["max_width"], h.width)
+        tot["max_height"] = max(tot["max_height"], h.height)
+        tot["max_blocks"] = max(tot["max_blocks"], nmcu * bpm)
+    flat.sort(key=lambda x: x[0])
+    srec = np.zeros(len(flat), SCAN_DTYPE)
+    n_levels = flat[-1][0] if flat else 0
+    level_first, level_intervals = [0] * (n_levels + 1), [1] * n_levels
+    for j, (lvl, k, s) in enumerate(flat):
+        r = srec[j]
+        nbytes = s.data_end - s.data_offset
+        r["data_off"], r["data_end"] = blob_offs[k] + s.data_offset, blob_offs[k] + s.data_end
+        r["scan_off"], r["int_off"] = tot["total_scan_bytes"], tot["total_intervals"]
+        r["image"], r["n_intervals"], r["restart"] = k, s.n_intervals, s.restart_interval or s.n_units
+        r["n_units"], r["blocks_w"] = s.n_units, s.blocks_w
+        r["comp_mask"] = sum(1 << c for c in s.comps)
+        r["ss"], r["se"], r["ah"], r["al"], r["level"] = s.ss, s.se, s.ah, s.al, lvl
+        r["table"] = -1
+        for q, t in enumerate(s.dc_tables):
+            if t is not None:
+                r["table"][q] = table(t)
+        if s.ac_table is not None:
+            r["table"][0] = table(s.ac_table)
+        tot["total_scan_bytes"] += (nbytes + 3) // 4 * 4 + 16
+        tot["total_intervals"] += s.n_intervals + 1
+        level_first[lvl] = j + 1
+        level_intervals[lvl - 1] = max(level_intervals[lvl - 1], s.n_intervals)
+    for l in range(1, n_levels + 1):                     # levels without a scan cannot occur, but keep it monotonic
+        level_first[l] = max(level_first[l], level_first[l - 1])
+    trec = np.zeros(max(len(tables), 1), TABLE_DTYPE)
+    for q, (lut, mc, vo, hv) in enumerate(tables):
+        trec[q]["lut"], trec[q]["maxcode"], trec[q]["valoff"], trec[q]["huffval"] = lut, mc, vo, hv
+    if tot["total_intervals"] >= 2 ** 31 or n_levels > MAX_SCANS:
+        raise RuntimeError("JPEG batch too large for one decode call")
+    tot.update(n_scans=len(flat), n_tables=len(tables), n_levels=n_levels, level_first=level_first,
+               level_intervals=level_intervals)
+    return rec, srec, trec, tot, out_offs, out_bytes

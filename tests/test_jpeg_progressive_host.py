@@ -1,0 +1,619 @@
+"""CPU side of the progressive device JPEG decoder: `jpeg.parse_progressive` against an independent marker walk and
+against hand-edited scan scripts, a pure-Python model of the four progressive coding procedures (ITU T.81 G.1 /
+jdphuff.c) whose coefficients, pushed through the baseline model's DC prediction, IDCT, planes and colour stages, equal
+`np.asarray(Image.open(f))` bit for bit, the IDCT range check that lets the GPU test demand status 0, the packed
+records against the C structs, and the argument checks of the new entry points."""
+import ctypes
+import functools
+import io
+import os
+
+import numpy as np
+import pytest
+from PIL import Image
+
+import test_jpeg_host as H
+from on_device_image_captioning_amd import jpeg as J
+from test_jpeg_host import DEMO, smooth_rgb
+
+
+def noisy_rgb(h, w, seed=0):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def flat_rgb(h, w, seed=0):
+    img = np.empty((h, w, 3), np.uint8)
+    img[:] = [(90 + 40 * seed) % 256, 160, 30]
+    return img
+
+
+def encode_progressive(img, **kw):
+    buf = io.BytesIO()
+    Image.fromarray(img).save(buf, format="JPEG", progressive=True, **kw)
+    return buf.getvalue()
+
+
+# the file matrix: (content, (w, h), save kwargs); restart_marker_blocks counts MCUs
+MATRIX = [(smooth_rgb, (40, 24), dict(subsampling=s, quality=q, **r))
+          for s in (0, 1, 2) for r in (dict(), dict(restart_marker_blocks=1), dict(restart_marker_blocks=3))
+          for q in (30, 75, 95)] + [
+    (smooth_rgb, (1, 1), dict(subsampling=2, quality=75)),
+    (smooth_rgb, (7, 9), dict(subsampling=2, quality=75)),
+    (smooth_rgb, (7, 9), dict(subsampling=1, quality=95, restart_marker_blocks=1)),
+    (smooth_rgb, (67, 93), dict(subsampling=2, quality=75)),
+    (smooth_rgb, (67, 93), dict(subsampling=1, quality=30, restart_marker_blocks=3)),
+    (smooth_rgb, (67, 93), dict(subsampling=0, quality=95)),
+    (smooth_rgb, (64, 48), dict(subsampling=2, quality=75)),
+    (smooth_rgb, (640, 480), dict(subsampling=2, quality=75)),
+    (noisy_rgb, (67, 93), dict(subsampling=0, quality=95)),
+    (noisy_rgb, (50, 34), dict(subsampling=2, quality=75, restart_marker_blocks=3)),
+    (noisy_rgb, (33, 17), dict(subsampling=1, quality=30)),
+    (flat_rgb, (67, 93), dict(subsampling=2, quality=75)),
+    (flat_rgb, (40, 24), dict(subsampling=0, quality=95, restart_marker_blocks=1)),
+    (flat_rgb, (31, 50), dict(subsampling=1, quality=30)),
+]
+N_FILES = len(MATRIX) + 1                                    # ... and tatin.jpg
+
+
+@functools.lru_cache(maxsize=None)
+def matrix_blob(k):
+    if k == len(MATRIX):
+        with open(os.path.join(DEMO, "tatin.jpg"), "rb") as f:
+            return f.read()
+    make, (w, h), kw = MATRIX[k]
+    return encode_progressive(make(h, w, seed=k % 5), **kw)
+
+
+def matrix_blobs():
+    return [matrix_blob(k) for k in range(N_FILES)]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# an independent marker walk: byte by byte, no numpy, nothing shared with the parser
+# ------------------------------------------------------------------------------------------------------------
+def walk_entropy(blob, i):
+    """Destuffed entropy data from offset i split at the restart markers → (intervals, offset of the closing marker)."""
+    segs, cur = [], bytearray()
+    while True:
+        b = blob[i]
+        if b != 0xFF:
+            cur.append(b)
+            i += 1
+            continue
+        m = blob[i + 1]
+        if m == 0:
+            cur.append(0xFF)
+        elif 0xD0 <= m <= 0xD7:
+            assert m - 0xD0 == len(segs) % 8
+            segs.append(bytes(cur))
+            cur = bytearray()
+        elif m == 0xFF:
+            i += 1
+            continue
+        else:
+            segs.append(bytes(cur))
+            return segs, i
+        i += 2
+
+
+def walk(blob):
+    """→ list of scans: dict(marker offset of the SOS, ids, tsel, ss, se, ah, al, dri, dht snapshot, data start / end,
+    intervals) and the offset of EOI."""
+    assert blob[:2] == b"\xff\xd8"
+    i, dht, dri, scans = 2, {}, 0, []
+    while True:
+        assert blob[i] == 0xFF
+        m = blob[i + 1]
+        if m == 0xD9:
+            return scans, i
+        n = (blob[i + 2] << 8) | blob[i + 3]
+        s = blob[i + 4:i + 2 + n]
+        if m == 0xC4:
+            j = 0
+            while j < len(s):
+                cnt = sum(s[j + 1:j + 17])
+                dht[(s[j] >> 4, s[j] & 15)] = (list(s[j + 1:j + 17]), bytes(s[j + 17:j + 17 + cnt]))
+                j += 17 + cnt
+        elif m == 0xDD:
+            dri = (s[0] << 8) | s[1]
+        if m != 0xDA:
+            i += 2 + n
+            continue
+        ns = s[0]
+        segs, end = walk_entropy(blob, i + 2 + n)
+        scans.append(dict(sos=i, ids=[s[1 + 2 * k] for k in range(ns)],
+                          tsel=[(s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(ns)],
+                          ss=s[1 + 2 * ns], se=s[2 + 2 * ns], ah=s[3 + 2 * ns] >> 4, al=s[3 + 2 * ns] & 15, dri=dri,
+                          dht=dict(dht), start=i + 2 + n, end=end, segs=segs))
+        i = end
+
+
+@pytest.mark.parametrize("k", range(N_FILES))
+def test_parser_accepts_the_matrix_and_agrees_with_the_marker_walk(k):
+    blob = matrix_blob(k)
+    hd = J.parse_progressive(blob)
+    assert hd.kind == J.DEVICE, hd.reason
+    base = J.parse(blob)
+    assert base.kind == J.HOST and base.reason == "SOF2"
+    im = Image.open(io.BytesIO(blob))
+    assert (hd.width, hd.height) == im.size
+    for c in range(3):
+        assert list(hd.qtables[c]) == list(im.quantization[im.layer[c][3]])
+    scans, eoi = walk(blob)
+    assert len(hd.scans) == len(scans)
+    for sc, w in zip(hd.scans, scans):
+        assert [hd.comp_ids[c] for c in sc.comps] == w["ids"]
+        assert (sc.ss, sc.se, sc.ah, sc.al) == (w["ss"], w["se"], w["ah"], w["al"])
+        assert sc.restart_interval == w["dri"]
+        assert (sc.data_offset, sc.data_end) == (w["start"], w["end"])
+        assert sc.n_intervals == len(w["segs"])
+        for q, (td, ta) in enumerate(w["tsel"]):                       # which tables are live
+            if sc.ss == 0 and sc.ah == 0:
+                assert (sc.dc_tables[q].bits, bytes(sc.dc_tables[q].vals)) == w["dht"][(0, td)]
+            else:
+                assert sc.dc_tables[q] is None
+        if sc.ss:
+            assert (sc.ac_table.bits, bytes(sc.ac_table.vals)) == w["dht"][(1, w["tsel"][0][1])]
+        else:
+            assert sc.ac_table is None
+    assert hd.scans[-1].data_end == eoi
+
+
+def test_dependency_levels_of_the_standard_script_are_four():
+    for k in (0, len(MATRIX) - 1, len(MATRIX)):
+        hd = J.parse_progressive(matrix_blob(k))
+        assert len(hd.scans) == 10
+        assert [s.level for s in hd.scans] == [1, 2, 2, 2, 2, 3, 2, 3, 3, 4]
+        assert hd.n_levels == 4
+
+
+def test_component_rasters_of_single_component_scans():
+    hd = J.parse_progressive(encode_progressive(smooth_rgb(93, 67), subsampling=2, quality=75))
+    assert (hd.mcus_x, hd.mcus_y) == (5, 6)
+    luma = [s for s in hd.scans if s.comps == [0] and s.ss]
+    chroma = [s for s in hd.scans if s.comps == [1] and s.ss]
+    assert all((s.blocks_w, s.n_units) == (9, 9 * 12) for s in luma)          # not the MCU-padded 10 x 12
+    assert all((s.blocks_w, s.n_units) == (5, 5 * 6) for s in chroma)
+    assert all(s.n_units == 30 for s in hd.scans if len(s.comps) == 3)
+
+
+def edited_files():
+    """Hand-edited scripts: (name, bytes) that must go to the host."""
+    blob = matrix_blob(3)                                              # 4:4:4 with DRI 1
+    scans, eoi = walk(blob)
+    out = []
+    last = scans[-1]
+    seg = blob.rfind(b"\xff\xc4", scans[-2]["end"], last["sos"])       # the DHT in front of the last scan, if any
+    cut = seg if seg >= 0 else last["sos"]
+    out.append(("refinement removed", blob[:cut] + blob[eoi:]))
+    b = bytearray(blob)
+    ref = next(s for s in scans if s["ah"])
+    b[ref["start"] - 1] = (3 << 4) | ref["al"]
+    out.append(("Ah inconsistent", bytes(b)))
+    b = bytearray(blob)
+    b[ref["start"] - 1] = (ref["ah"] << 4) | ref["ah"]
+    out.append(("Al inconsistent", bytes(b)))
+    out.append(("AC before DC", blob[:scans[0]["sos"]] + blob[scans[0]["end"]:]))
+    for n, s in enumerate(scans):
+        out.append((f"cut at the end of scan {n}", blob[:s["end"]]))
+        out.append((f"cut inside scan {n}", blob[:(s["start"] + s["end"]) // 2]))
+    out.append(("cut inside a header", blob[:scans[1]["sos"] + 5]))
+    return out
+
+
+def test_edited_scripts_go_to_the_host_with_a_reason():
+    names = set()
+    for name, blob in edited_files():
+        hd = J.parse_progressive(blob)
+        assert hd.kind == J.HOST and hd.reason, name
+        assert J.parse(blob).kind == J.HOST, name
+        names.add(hd.reason)
+    assert {"incomplete scan script", "AC scan before DC"} <= names
+    assert any(r.startswith("bogus progression") for r in names) and any("truncated" in r for r in names)
+
+
+def test_other_kinds():
+    g = io.BytesIO()
+    Image.fromarray(smooth_rgb(8, 8)[:, :, 0]).save(g, format="JPEG", progressive=True)
+    assert J.parse_progressive(g.getvalue()).kind == J.BLACK and J.parse(g.getvalue()).kind == J.BLACK
+    base = H.encode(smooth_rgb(16, 16), quality=90)
+    assert J.parse_progressive(base).kind == J.HOST                    # SOF0: `parse` takes those
+    assert J.parse_progressive(b"").kind == J.HOST
+    assert J.parse_progressive(b"\x89PNG\r\n\x1a\n" + bytes(40)).kind == J.HOST
+    blob = matrix_blob(0)
+    scans, _ = walk(blob)
+    extra = blob[:scans[0]["end"]] + blob[scans[0]["sos"]:scans[0]["end"]] * J.MAX_SCANS + blob[scans[0]["end"]:]
+    assert J.parse_progressive(extra).kind == J.HOST                   # repeated DC scans: bogus, and too many
+
+
+def test_marker_search_is_vectorised_and_exact():
+    blob = matrix_blob(len(MATRIX))
+    scans, eoi = walk(blob)
+    marks = J.marker_positions(blob)
+    for s in scans:
+        assert int(marks[np.searchsorted(marks, s["start"])]) == s["end"]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the model: jdphuff.c's four procedures, coefficient by coefficient
+# ------------------------------------------------------------------------------------------------------------
+class BitReader:
+    def __init__(self, data):
+        self.d, self.pos, self.n = data + bytes(8), 0, 8 * len(data)
+
+    def peek(self, n):
+        i = self.pos >> 3
+        return (int.from_bytes(self.d[i:i + 4], "big") >> (32 - (self.pos & 7) - n)) & ((1 << n) - 1)
+
+    def get(self, n):
+        v = self.peek(n) if n else 0
+        self.pos += n
+        return v
+
+    def symbol(self, tab):
+        ln, s = H._lookup(*tab, self.peek(16))
+        self.pos += ln
+        return s
+
+
+def extend(v, s):
+    return v - (1 << s) + 1 if s and v < (1 << (s - 1)) else v
+
+
+def block_index(hd, c, n, bw):
+    """Block n of component c's own raster → index into the MCU-ordered block array."""
+    hy, vy = hd.comp_hv[0]
+    nY = hy * vy
+    hh, vv = (hy, vy) if c == 0 else (1, 1)
+    bx, by = n % bw, n // bw
+    return ((by // vv) * hd.mcus_x + bx // hh) * (nY + 2) + (0 if c == 0 else nY + c - 1) + (by % vv) * hh + bx % hh
+
+
+def model_progressive_coefficients(blob, hd):
+    """→ int32 [blocks, 64], natural order, MCU by MCU, DC as its value (libjpeg's coefficient arrays)."""
+    hy, vy = hd.comp_hv[0]
+    nY = hy * vy
+    bpm = nY + 2
+    coef = np.zeros((hd.mcus_x * hd.mcus_y * bpm, 64), np.int32)
+    nat = [int(x) for x in J.NATURAL_ORDER]
+    for sc in hd.scans:
+        segs, end = walk_entropy(blob, sc.data_offset)
+        assert end == sc.data_end and len(segs) == sc.n_intervals
+        R = sc.restart_interval or sc.n_units
+        p1, m1 = 1 << sc.al, -(1 << sc.al)
+        for k, seg in enumerate(segs):
+            br = BitReader(seg)
+            units = range(k * R, min((k + 1) * R, sc.n_units))
+            if sc.ss == 0:
+                blocks = []                                            # (block index, slot in the scan)
+                for u in units:
+                    if len(sc.comps) == 1:
+                        blocks.append((block_index(hd, sc.comps[0], u, sc.blocks_w), 0))
+                    else:
+                        for q, c in enumerate(sc.comps):
+                            for j in range(nY if c == 0 else 1):
+                                blocks.append((u * bpm + (0 if c == 0 else nY + c - 1) + j, q))
+                if sc.ah == 0:
+                    tabs = [J.device_tables(t) for t in sc.dc_tables]
+                    pred = [0] * len(sc.comps)
+                    for b, q in blocks:
+                        s = br.symbol(tabs[q])
+                        pred[q] += extend(br.get(s), s)
+                        coef[b, 0] = pred[q] << sc.al
+                else:
+                    for b, q in blocks:
+                        if br.get(1):
+                            coef[b, 0] |= p1
+            elif sc.ah == 0:
+                tab = J.device_tables(sc.ac_table)
+                eobrun = 0
+                for u in units:
+                    if eobrun:
+                        eobrun -= 1
+                        continue
+                    row = coef[block_index(hd, sc.comps[0], u, sc.blocks_w)]
+                    kk = sc.ss
+                    while kk <= sc.se:
+                        rs = br.symbol(tab)
+                        r, s = rs >> 4, rs & 15
+                        if s:
+                            kk += r
+                            assert kk <= sc.se
+                            row[nat[kk]] = extend(br.get(s), s) << sc.al
+                        elif r == 15:
+                            kk += 15
+                        else:
+                            eobrun = (1 << r) + br.get(r) - 1
+                            break
+                        kk += 1
+            else:
+                tab = J.device_tables(sc.ac_table)
+                eobrun = 0
+                for u in units:
+                    row = coef[block_index(hd, sc.comps[0], u, sc.blocks_w)]
+                    kk = sc.ss
+                    if eobrun == 0:
+                        while kk <= sc.se:
+                            rs = br.symbol(tab)
+                            r, s = rs >> 4, rs & 15
+                            if s:
+                                assert s == 1
+                                s = p1 if br.get(1) else m1
+                            elif r != 15:
+                                eobrun = (1 << r) + br.get(r)
+                                break
+                            while kk <= sc.se:
+                                x = row[nat[kk]]
+                                if x:
+                                    if br.get(1) and not (x & p1):
+                                        row[nat[kk]] = x + (p1 if x >= 0 else m1)
+                                else:
+                                    r -= 1
+                                    if r < 0:
+                                        break
+                                kk += 1
+                            if s:
+                                assert kk <= sc.se
+                                row[nat[kk]] = s
+                            kk += 1
+                    if eobrun:
+                        while kk <= sc.se:
+                            x = row[nat[kk]]
+                            if x and br.get(1) and not (x & p1):
+                                row[nat[kk]] = x + (p1 if x >= 0 else m1)
+                            kk += 1
+                        eobrun -= 1
+            assert br.pos <= br.n
+    return coef
+
+
+def as_baseline(hd, coef):
+    """The header and DC differences the baseline model takes: `model_dc_prediction` turns them back into `coef`."""
+    nY = hd.comp_hv[0][0] * hd.comp_hv[0][1]
+    comp = np.array([0] * nY + [1, 2])
+    d = coef.reshape(-1, nY + 2, 64).copy()
+    for c in range(3):
+        cols = np.nonzero(comp == c)[0]
+        dc = d[:, cols, 0].reshape(-1)
+        d[:, cols, 0] = np.diff(dc, prepend=0).reshape(-1, len(cols))
+    base = J.JpegHeader(J.DEVICE, width=hd.width, height=hd.height, ncomp=3, sampling=hd.sampling,
+                        comp_ids=hd.comp_ids, comp_hv=hd.comp_hv, qtables=hd.qtables, restart_interval=0)
+    return base, d.reshape(-1, 64)
+
+
+@functools.lru_cache(maxsize=None)
+def model_of(k):
+    """(coefficients, RGB or the Rejected the IDCT range check raised) of matrix file k."""
+    blob = matrix_blob(k)
+    hd = J.parse_progressive(blob)
+    assert hd.kind == J.DEVICE, hd.reason
+    coef = model_progressive_coefficients(blob, hd)
+    base, diffs = as_baseline(hd, coef)
+    assert np.array_equal(H.model_dc_prediction(diffs, base), coef)
+    mp = pytest.MonkeyPatch()
+    try:                                   # model_rgb = parse + model_coefficients + the stages under test here
+        mp.setattr(J, "parse", lambda b: base)
+        mp.setattr(H, "model_coefficients", lambda b, h: diffs)
+        try:
+            rgb = H.model_rgb(blob)
+        except H.Rejected as e:
+            rgb = e
+    finally:
+        mp.undo()
+    return coef, rgb
+
+
+@pytest.mark.parametrize("k", range(N_FILES))
+def test_model_is_bit_exact_with_pillow(k):
+    want = np.asarray(Image.open(io.BytesIO(matrix_blob(k))))
+    _, got = model_of(k)
+    assert not isinstance(got, Exception), got
+    assert got.shape == want.shape
+    assert np.array_equal(got, want), np.abs(got.astype(int) - want).max()
+
+
+def test_every_matrix_file_stays_inside_the_idct_range():
+    """model_idct raises Rejected where the device sets its range error; none of the matrix does, so the GPU test may
+    demand status 0 (route `device-progressive`) for every file."""
+    for k in range(N_FILES):
+        _, got = model_of(k)
+        assert not isinstance(got, H.Rejected), k
+
+
+# ------------------------------------------------------------------------------------------------------------
+# records and entry points
+# ------------------------------------------------------------------------------------------------------------
+class CTable(ctypes.Structure):
+    _fields_ = [("lut", ctypes.c_uint16 * 512), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18),
+                ("huffval", ctypes.c_uint8 * 256)]
+
+
+class CProgHeader(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("out_off", "coef_off", "plane_off")] + \
+               [(n, ctypes.c_int32) for n in ("width", "height", "sampling", "mcus_x", "mcus_y", "n_intervals")] + \
+               [("qt", ctypes.c_uint16 * 64 * 3)]
+
+
+class CScan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("data_off", "data_end", "scan_off")] + \
+               [(n, ctypes.c_int32) for n in ("image", "int_off", "n_intervals", "restart", "n_units", "blocks_w",
+                                              "comp_mask", "ss", "se", "ah", "al", "level")] + \
+               [("table", ctypes.c_int32 * 3), ("pad", ctypes.c_int32)]
+
+
+def test_records_match_the_c_structs():
+    """The same declarations as include/odic_hip.h (whose sizes and key offsets csrc/jpeg_decode.hip static_asserts)."""
+    for dt, cs, size in ((J.PROG_HEADER_DTYPE, CProgHeader, 432), (J.SCAN_DTYPE, CScan, 88), (J.TABLE_DTYPE, CTable, 1424)):
+        assert dt.itemsize == ctypes.sizeof(cs) == size
+        assert list(dt.names) == [f[0] for f in cs._fields_]
+        for name in dt.names:
+            assert dt.fields[name][1] == getattr(cs, name).offset, name
+            assert dt.fields[name][0].itemsize == getattr(cs, name).size, name
+    from on_device_image_captioning_amd import _hip
+    assert ctypes.sizeof(_hip.JpegProgBatch) == 640 and _hip.JpegProgBatch.level_first.offset == 120
+    assert _hip.JPEG_MAX_SCANS == J.MAX_SCANS == 64
+
+
+def test_packed_records_describe_the_batch():
+    hdrs = [J.parse_progressive(matrix_blob(k)) for k in (0, 4, len(MATRIX) - 1)]
+    offs = [0, 1000, 5000]
+    rec, srec, trec, tot, out_offs, out_bytes = J.pack_progressive(hdrs, offs)
+    assert len(rec) == 3 and len(srec) == 30 and tot["n_scans"] == 30 and tot["n_levels"] == 4
+    assert list(srec["level"]) == sorted(srec["level"])
+    assert tot["level_first"] == [0, 3, 18, 27, 30]
+    assert out_bytes == sum(h.width * h.height * 3 for h in hdrs)
+    for k, h in enumerate(hdrs):
+        mine = srec[srec["image"] == k]
+        assert rec[k]["n_intervals"] == mine["n_intervals"].sum() == sum(s.n_intervals for s in h.scans)
+        assert sorted(mine["data_off"] - offs[k]) == sorted(s.data_offset for s in h.scans)
+    assert (np.diff(srec["scan_off"]) >= srec["data_end"][:-1] - srec["data_off"][:-1] + 16).all()
+    assert (srec["table"] < tot["n_tables"]).all() and tot["n_tables"] == len(trec)
+    assert tot["level_intervals"][0] == max(s.n_intervals for h in hdrs for s in h.scans if s.level == 1)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from on_device_image_captioning_amd import _hip
+    if not os.path.exists(_hip.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    return _hip.load()
+
+
+def test_c_entry_points_reject_bad_arguments(lib):
+    from on_device_image_captioning_amd import _hip
+    assert lib.odic_jpeg_decode_progressive(None, None, 0, None) == -2
+    assert lib.odic_jpeg_progressive_workspace_bytes(None) == 0
+    b = _hip.JpegProgBatch()
+    assert lib.odic_jpeg_decode_progressive(ctypes.byref(b), None, 0, None) == -2
+    b.headers = b.scans = b.tables = b.data = b.out = b.status = 16
+    b.n_images, b.n_scans, b.n_tables, b.n_levels = 1, 2, 1, 2
+    b.max_width = b.max_height = 8
+    b.max_blocks = b.total_blocks = 3
+    b.total_scan_bytes, b.total_intervals, b.total_plane_bytes = 40, 4, 192
+    b.level_first[1], b.level_first[2] = 1, 2
+    b.level_intervals[0] = b.level_intervals[1] = 1
+    need = lib.odic_jpeg_progressive_workspace_bytes(ctypes.byref(b))
+    assert need > 0
+    assert 0 < lib.odic_jpeg_progressive_coef_offset(ctypes.byref(b)) < need
+    assert lib.odic_jpeg_decode_progressive(ctypes.byref(b), None, need, None) == -2       # no workspace
+    assert lib.odic_jpeg_decode_progressive(ctypes.byref(b), 16, need - 1, None) == -1     # workspace too small
+    for fld, bad in (("n_images", 0), ("n_scans", 0), ("n_scans", 3), ("n_tables", 0), ("n_levels", 0),
+                     ("n_levels", 65), ("n_levels", 1), ("max_width", 0), ("max_height", 70000), ("total_blocks", 0),
+                     ("total_intervals", 0), ("total_scan_bytes", 0)):
+        old = getattr(b, fld)
+        setattr(b, fld, bad)
+        assert lib.odic_jpeg_decode_progressive(ctypes.byref(b), 16, need, None) == -1, fld
+        assert lib.odic_jpeg_progressive_workspace_bytes(ctypes.byref(b)) == 0, fld
+        setattr(b, fld, old)
+    b.level_first[1] = 2                                                                   # an empty level
+    assert lib.odic_jpeg_decode_progressive(ctypes.byref(b), 16, need, None) == -1
+    b.level_first[1] = 1
+    b.level_intervals[1] = 0
+    assert lib.odic_jpeg_decode_progressive(ctypes.byref(b), 16, need, None) == -1
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the device's formulation of AC refinement (prog_ac_refine of csrc/jpeg_decode.hip): masks instead of a walk
+# ------------------------------------------------------------------------------------------------------------
+def refine_block_with_masks(row_zz, br, tab, ss, se, al, eobrun):
+    """One block, coefficients in zig-zag order, updated in place → the EOB run left.  The nonzero coefficients are a
+    64-bit mask; a run of r zeros clears r lowest bits of the inverted mask; the correction bit of a nonzero coefficient
+    passed over sits popcount(nonzero coefficients passed before it) bits behind the step's position and is fetched
+    after the block's symbols, as each lane of the wave does."""
+    p1, m1 = 1 << al, -(1 << al)
+    full = (1 << 64) - 1
+    band = ((1 << (se + 1)) - 1) & ~((1 << ss) - 1)
+    nz = sum(1 << i for i in range(64) if row_zz[i]) & band
+    cpos, newv = {}, {}
+    k = ss
+
+    def passed_over(passed):
+        for i in range(64):
+            if (passed >> i) & 1:
+                cpos[i] = br.pos + bin(passed & ((1 << i) - 1)).count("1")
+        br.pos += bin(passed).count("1")
+
+    if eobrun == 0:
+        while k <= se:
+            rs = br.symbol(tab)
+            r, s = rs >> 4, rs & 15
+            sval = 0
+            if s:
+                assert s == 1
+                sval = p1 if br.get(1) else m1
+            elif r != 15:
+                eobrun = (1 << r) + br.get(r)
+                break
+            frm = (full << k) & full
+            z = ~nz & band & frm
+            for _ in range(r):
+                z &= z - 1
+            t = (z & -z).bit_length() - 1 if z else se + 1
+            passed_over(nz & frm & ((1 << t) - 1))
+            if s:
+                assert t <= se
+                newv[t] = sval
+            k = t + 1
+    if eobrun > 0:
+        passed_over(nz & (full << k) & full if k <= 63 else 0)
+        eobrun -= 1
+    for i, pos in cpos.items():
+        bit = (br.d[pos >> 3] >> (7 - (pos & 7))) & 1
+        if bit and not (row_zz[i] & p1):
+            row_zz[i] += p1 if row_zz[i] >= 0 else m1
+    for i, v in newv.items():
+        assert i not in cpos
+        row_zz[i] = v
+    return eobrun
+
+
+@pytest.mark.parametrize("k", [1, 5, 13, 26, 27 + 3, 27 + 8, 27 + 9, 27 + 11])
+def test_mask_formulation_of_ac_refinement_equals_the_walk(k):
+    """Decode the file with the model, but its AC refinement scans with the device's formulation: same coefficients."""
+    blob = matrix_blob(k)
+    hd = J.parse_progressive(blob)
+    nat = J.NATURAL_ORDER
+    first = J.ProgHeader(J.DEVICE, width=hd.width, height=hd.height, ncomp=3, sampling=hd.sampling, comp_ids=hd.comp_ids,
+                         comp_hv=hd.comp_hv, qtables=hd.qtables)
+    n_refined = 0
+    coef = None
+    for n, sc in enumerate(hd.scans):
+        if not (sc.ss and sc.ah):
+            continue
+        first.scans = hd.scans[:n]                                # everything before this scan, by the walk
+        coef = model_progressive_coefficients(blob, first)
+        segs, _ = walk_entropy(blob, sc.data_offset)
+        R = sc.restart_interval or sc.n_units
+        tab = J.device_tables(sc.ac_table)
+        for i, seg in enumerate(segs):
+            br, eobrun = BitReader(seg), 0
+            for u in range(i * R, min((i + 1) * R, sc.n_units)):
+                b = block_index(hd, sc.comps[0], u, sc.blocks_w)
+                zz = [int(x) for x in coef[b, nat]]
+                eobrun = refine_block_with_masks(zz, br, tab, sc.ss, sc.se, sc.al, eobrun)
+                coef[b, nat] = zz
+            assert br.pos <= br.n
+        first.scans = hd.scans[:n + 1]
+        assert np.array_equal(coef, model_progressive_coefficients(blob, first)), n
+        n_refined += 1
+    assert n_refined >= 4 and np.array_equal(coef, model_of(k)[0])
+
+
+def test_packed_matrix_batch_passes_the_descriptor_checks(lib):
+    """The totals `pack_progressive` computes for the whole matrix, set field by field as DevicePreprocessor does, are a
+    descriptor the library accepts; the coefficient region lies inside the workspace."""
+    from on_device_image_captioning_amd import _hip
+    hdrs = [J.parse_progressive(b) for b in matrix_blobs()]
+    rec, srec, trec, tot, _, _ = J.pack_progressive(hdrs, [0] * len(hdrs))
+    b = _hip.JpegProgBatch()
+    b.n_images = len(hdrs)
+    for k, v in tot.items():
+        if isinstance(v, list):
+            getattr(b, k)[:len(v)] = v
+        else:
+            setattr(b, k, v)
+    need = lib.odic_jpeg_progressive_workspace_bytes(ctypes.byref(b))
+    off = lib.odic_jpeg_progressive_coef_offset(ctypes.byref(b))
+    assert need > 0 and 0 < off and off + 128 * tot["total_blocks"] <= need
+    assert need >= tot["total_scan_bytes"] + 4 * tot["total_intervals"] + 128 * tot["total_blocks"] + tot["total_plane_bytes"]
