@@ -50,8 +50,9 @@ extern "C" {
 #define ODIC_ENULL (-2)    /* required pointer is NULL */
 #define ODIC_EUNSUPPORTED (-3)
 
-/* ABI version of this header; bumped on any signature change. */
-#define ODIC_ABI_VERSION 18
+/* ABI version of this header; bumped on any signature change.
+ *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step). */
+#define ODIC_ABI_VERSION 19
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -549,13 +550,6 @@ typedef struct odic_embed_args {
 int odic_beam_step(const float* cand_val, const int32_t* cand_idx, const odic_beam_state* st,
                    const odic_embed_args* emb, int32_t n_img, int32_t beams, int32_t T, int64_t eos_idx,
                    void* stream);
-
-/* The tail of a single-model search step in ONE launch (captioning_model.py:150-223): log_softmax of the step's
- * logits rows (fp32 [n_img·beams, V], ldl), their `beams` best words (ties → lower index), odic_beam_step on those
- * candidates (which never leave LDS) and, with emb, the next position's input.  Same limits as odic_beam_step. */
-int odic_beam_search_step(const float* logits, int64_t ldl, int32_t V, const odic_beam_state* st,
-                          const odic_embed_args* emb, int32_t n_img, int32_t beams, int32_t T, int64_t eos_idx,
-                          void* stream);
 
 /* Initial state of a search (captioning_model.py:117-125): tokens[:, :, 0] = sos, logprobs[:, :, 0] = 0,
  * next_tok = sos, row_valid = 1, *pos = *done = *ctr = 0; with emb, also the input of position 0 (the embedded

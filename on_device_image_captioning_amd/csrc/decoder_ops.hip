@@ -302,13 +302,7 @@ __global__ __launch_bounds__(DYN_NT) void dynexp_step_kernel(DynParams p) {
 //            NB accumulators; key groups combined through LDS.
 // kv: [n_img, S, ldkv], K at koff, V at voff.
 // ---------------------------------------------------------------------------------------------
-// PF (diagnostic builds only, -DODIC_XATTN_VARIANTS, tools/xattn_ab.py): the software-pipelined P·V loop of round 2 —
-// the first batch of V rows requested before the score phase, the next batch under the current batch's FMAs — whose
-// results differed from this kernel's 30 times in 96,000 captions beside the encode graph.
-//   PF = 1 as round 2 wrote it; 2..4 = the same with ONE change each, to locate the mechanism on the hardware:
-//   2: `s_nop 7` after every group of P·V FMAs; 3: the FMAs kept scalar (no v_pk_fma_f32); 4: all of a key's
-//   probabilities read and waited for (lgkmcnt(0)) before the first FMA.
-template <int NB, int PF = 0>
+template <int NB>
 __global__ __launch_bounds__(256) void cross_attn_step_kernel(const float* __restrict__ q, long ldq,
                                                               const float* __restrict__ kv, long ldkv, int koff,
                                                               int voff, const int* __restrict__ enc_len,
@@ -342,13 +336,6 @@ __global__ __launch_bounds__(256) void cross_attn_step_kernel(const float* __res
 #pragma unroll
   for (int b = 0; b < NB; ++b) valid[b] = row_valid[n0 + min(b, nb - 1)];
 
-  float vpre[12];
-  if constexpr (PF) {       // V rows of the first P·V batch requested now: their latency passes under scores + softmax
-    const int c_ = tid % dk, g_ = tid / dk, ng_ = 256 / dk;
-    const float* vp_ = kvb + voff + h * dk + c_;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) vpre[i] = vp_[(long)min(g_ + i * ng_, S - 1) * ldkv];
-  }
   // ---- scores: wave w takes sweeps w, w+4, ...; up to 3 sweeps of K loads in flight
   const int nsweep = (S + kps - 1) / kps;
   for (int sw0 = wave; sw0 < nsweep; sw0 += 12) {
@@ -401,36 +388,14 @@ __global__ __launch_bounds__(256) void cross_attn_step_kernel(const float* __res
   const float* vp = kvb + voff + h * dk + c;
   for (int s0 = g; s0 < S; s0 += 12 * ng) {
     float v[12];
-    if constexpr (PF) {
 #pragma unroll
-      for (int i = 0; i < 12; ++i) v[i] = vpre[i];
-      if (s0 + 12 * ng < S) {                        // next batch in flight under this one's FMAs
-#pragma unroll
-        for (int i = 0; i < 12; ++i) vpre[i] = vp[(long)min(s0 + 12 * ng + i * ng, S - 1) * ldkv];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) v[i] = vp[(long)min(s0 + i * ng, S - 1) * ldkv];
-    }
+    for (int i = 0; i < 12; ++i) v[i] = vp[(long)min(s0 + i * ng, S - 1) * ldkv];
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
       const int s = s0 + i * ng;
       if (s < S) {
-        if constexpr (PF == 4) {
-          float pb[NB];
 #pragma unroll
-          for (int b = 0; b < NB; ++b) pb[b] = sc[(b < nb ? b : 0) * S + s];
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pb[0]) :: "memory");
-#pragma unroll
-          for (int b = 0; b < NB; ++b) acc[b] = fmaf(pb[b], v[i], acc[b]);
-        } else {
-#pragma unroll
-          for (int b = 0; b < NB; ++b) {
-            acc[b] = fmaf(sc[(b < nb ? b : 0) * S + s], v[i], acc[b]);
-            if constexpr (PF == 3) asm volatile("" : "+v"(acc[b]));
-          }
-          if constexpr (PF == 2) asm volatile("s_nop 7" ::: "memory");
-        }
+        for (int b = 0; b < NB; ++b) acc[b] = fmaf(sc[(b < nb ? b : 0) * S + s], v[i], acc[b]);
       }
     }
   }
@@ -446,21 +411,24 @@ __global__ __launch_bounds__(256) void cross_attn_step_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------
-// log-softmax + exact top-k (ties → lower index) of up to NR rows AT ONCE by one 512-thread block (the fused search
-// step: the k logits rows of one image; the stand-alone kernel: NR = 1).  A thread holds a 20-value slice of every
-// row in registers (V <= 10240; longer rows stream).  Selection by threshold instead of sorting:
-//   1. wave maxima of every row → LDS (their maximum is the row maximum the log-sum-exp needs anyway);
+// log-softmax + exact top-k (ties → lower index) of one row by one 512-thread block.  A thread holds a 20-value slice
+// of the row in registers (V <= 10240; longer rows stream).  Selection by threshold instead of sorting:
+//   1. wave maxima → LDS (their maximum is the row maximum the log-sum-exp needs anyway);
 //   2. tau = the k-th largest of the 8 wave maxima: at least k elements are >= tau, so the k best all are;
 //   3. in the Σexp pass every element >= tau (k .. a dozen of them) is appended to a candidate list in LDS;
-//   4. wave r picks the k best of row r's candidates: k rounds of a wave arg-max over (value, lower index).
-// Per row that is ~60 VALU operations per thread and k+1 shuffle chains, against ~1000 for per-thread sorted lists
-// (which made a block that owns several rows ALU-bound).  Rows whose candidate list would overflow (k > 8 wave
-// maxima, or hundreds of equal values) take k rounds of a block-wide arg-max instead — exact, just slower.
-// `top_val` / `top_idx` ([row][k]) may point to global memory or LDS; logp0 (optional): the full log-prob rows.
+//   4. wave 0 picks the k best of the candidates: k rounds of a wave arg-max over (value, lower index).
+// That is ~60 VALU operations per thread and k+1 shuffle chains, against ~1000 for per-thread sorted lists.  A row
+// whose candidate list would overflow (k > 8 wave maxima, or hundreds of equal values) takes k rounds of a block-wide
+// arg-max instead — exact, just slower.
+// `top_val` / `top_idx` ([k]); logp (optional): the full log-prob row.
+// The three one-trip `for (once …)` loops and the first and last barrier do no work.  They are what is left of the
+// multi-row form this kernel was measured in (commit d9f7de9): with them hipcc emits that commit's instruction stream
+// for both instantiations; without a loop it lays the blocks out differently (a few instructions, one SGPR), without
+// the barriers the stream is shorter.  Take them out together with an end-to-end measurement of the search step.
 // ---------------------------------------------------------------------------------------------
-constexpr int TOPK_CAP = 128;          // candidates per row (two per lane of the selecting wave)
-template <int NR> struct TopkSharedN {
-  float red[NR][16]; float red2[NR][16]; int cnt[NR]; float cv[NR][TOPK_CAP]; int ci[NR][TOPK_CAP];
+constexpr int TOPK_CAP = 128;          // candidates (two per lane of the selecting wave)
+struct TopkShared {
+  float red[16]; float red2[16]; int cnt; float cv[TOPK_CAP]; int ci[TOPK_CAP];
   float bv[16]; int bi[16];
 };
 
@@ -473,162 +441,122 @@ __device__ __forceinline__ void wave_argmax(float& best, int& besti) {        //
   }
 }
 
-template <int NR, int NTH, bool NORM>
-__device__ __forceinline__ void rows_logsoftmax_topk(const float* __restrict__ x0, long ldl, int nr,
-                                                     float* __restrict__ logp0, long ldp, float* top_val,
-                                                     int* top_idx, int V, int k, TopkSharedN<NR>& sh) {
+template <int NTH, bool NORM>
+__device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x, float* __restrict__ logp,
+                                                    float* top_val, int* top_idx, int V, int k, TopkShared& sh) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NPT = 10240 / NTH, NWV = NTH / 64;
   const bool small = V <= NPT * NTH;
-  float xv[NR][NPT];
-  float tm[NR];
-  if (small) {                                       // every row's loads are in flight before the first use
+  float xv[NPT];
+  float tm = -INFINITY;
+  if (small) {                                       // all loads are in flight before the first use
 #pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      const float* x = x0 + (long)min(r, nr - 1) * ldl;
+    for (int u = 0; u < NPT; ++u) { const int i = tid + u * NTH; xv[u] = i < V ? x[i] : -INFINITY; }
+  }
+  for (int once = 0; once < 1; ++once) {             // (pins hipcc's block layout, see above)
+    if (small) {
 #pragma unroll
-      for (int u = 0; u < NPT; ++u) { const int i = tid + u * NTH; xv[r][u] = i < V ? x[i] : -INFINITY; }
+      for (int u = 0; u < NPT; ++u) tm = fmaxf(tm, xv[u]);
+    } else {
+      for (int i = tid; i < V; i += NTH) tm = fmaxf(tm, x[i]);
     }
   }
-#pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    tm[r] = -INFINITY;
-    if (r < nr) {
-      if (small) {
-#pragma unroll
-        for (int u = 0; u < NPT; ++u) tm[r] = fmaxf(tm[r], xv[r][u]);
-      } else {
-        const float* x = x0 + (long)r * ldl;
-        for (int i = tid; i < V; i += NTH) tm[r] = fmaxf(tm[r], x[i]);
-      }
-    }
+  __syncthreads();                                   // (no work: see above)
+  for (int once = 0; once < 1; ++once) {             // (pins hipcc's block layout)
+    const float m = wave_max(tm);
+    if (lane == 0) sh.red[wave] = m;
   }
-  __syncthreads();                                   // (the previous call's readers of sh are done)
-#pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    const float m = wave_max(tm[r]);
-    if (lane == 0) sh.red[r][wave] = m;
-  }
-  if (tid < NR) sh.cnt[tid] = 0;
+  if (tid == 0) sh.cnt = 0;
   __syncthreads();
-  float mx[NR], tau[NR];
+  float wm[NWV];
 #pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    float wm[NWV];
+  for (int i = 0; i < NWV; ++i) wm[i] = sh.red[i];
+  float mx = wm[0];
 #pragma unroll
-    for (int i = 0; i < NWV; ++i) wm[i] = sh.red[r][i];
-    float t = wm[0];
+  for (int i = 1; i < NWV; ++i) mx = fmaxf(mx, wm[i]);
+  float tau = -INFINITY;                             // k > NWV: every element is a candidate → the overflow path
+  if (k <= NWV) {
 #pragma unroll
-    for (int i = 1; i < NWV; ++i) t = fmaxf(t, wm[i]);
-    mx[r] = t;
-    tau[r] = -INFINITY;                              // k > NWV: every element is a candidate → the overflow path
-    if (k <= NWV) {
+    for (int i = 0; i < NWV; ++i) {                  // the element with exactly k-1 others ranked above it
+      int above = 0;
 #pragma unroll
-      for (int i = 0; i < NWV; ++i) {                // the element with exactly k-1 others ranked above it
-        int above = 0;
-#pragma unroll
-        for (int j = 0; j < NWV; ++j) above += (wm[j] > wm[i] || (wm[j] == wm[i] && j < i)) ? 1 : 0;
-        if (above == k - 1) tau[r] = wm[i];
-      }
+      for (int j = 0; j < NWV; ++j) above += (wm[j] > wm[i] || (wm[j] == wm[i] && j < i)) ? 1 : 0;
+      if (above == k - 1) tau = wm[i];
     }
   }
   // Σ exp(x - max) and the candidates
-  float sm[NR];
+  float sacc = 0.f;
+  if (small) {
 #pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    float sacc = 0.f;
-    if (r < nr) {
-      const float* x = x0 + (long)r * ldl;
-      if (small) {
-#pragma unroll
-        for (int u = 0; u < NPT; ++u) {
-          const float v = xv[r][u];
-          if constexpr (NORM) sacc += expf(v - mx[r]);
-          if (v >= tau[r] && tid + u * NTH < V) {
-            const int pos = atomicAdd(&sh.cnt[r], 1);
-            if (pos < TOPK_CAP) { sh.cv[r][pos] = v; sh.ci[r][pos] = tid + u * NTH; }
-          }
-        }
-      } else {
-        for (int i = tid; i < V; i += NTH) {
-          const float v = x[i];
-          if constexpr (NORM) sacc += expf(v - mx[r]);
-          if (v >= tau[r]) {
-            const int pos = atomicAdd(&sh.cnt[r], 1);
-            if (pos < TOPK_CAP) { sh.cv[r][pos] = v; sh.ci[r][pos] = i; }
-          }
-        }
+    for (int u = 0; u < NPT; ++u) {
+      const float v = xv[u];
+      if constexpr (NORM) sacc += expf(v - mx);
+      if (v >= tau && tid + u * NTH < V) {
+        const int pos = atomicAdd(&sh.cnt, 1);
+        if (pos < TOPK_CAP) { sh.cv[pos] = v; sh.ci[pos] = tid + u * NTH; }
       }
     }
-    sm[r] = wave_sum(sacc);
-  }
-#pragma unroll
-  for (int r = 0; r < NR; ++r)
-    if (lane == 0) sh.red2[r][wave] = sm[r];
-  __syncthreads();
-  float lse[NR];
-#pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    lse[r] = 0.f;                                    // NORM = false: rows are log-probs already
-    if constexpr (NORM) {
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < NWV; ++i) t += sh.red2[r][i];
-      lse[r] = mx[r] + logf(t);
+  } else {
+    for (int i = tid; i < V; i += NTH) {
+      const float v = x[i];
+      if constexpr (NORM) sacc += expf(v - mx);
+      if (v >= tau) {
+        const int pos = atomicAdd(&sh.cnt, 1);
+        if (pos < TOPK_CAP) { sh.cv[pos] = v; sh.ci[pos] = i; }
+      }
     }
   }
-  if (logp0) {
+  const float sm = wave_sum(sacc);
+  if (lane == 0) sh.red2[wave] = sm;
+  __syncthreads();
+  float lse = 0.f;                                   // NORM = false: the row holds log-probs already
+  if constexpr (NORM) {
+    float t = 0.f;
 #pragma unroll
-    for (int r = 0; r < NR; ++r)
-      if (r < nr)
-        for (int i = tid; i < V; i += NTH) logp0[(long)r * ldp + i] = x0[(long)r * ldl + i] - lse[r];
+    for (int i = 0; i < NWV; ++i) t += sh.red2[i];
+    lse = mx + logf(t);
   }
-  // selection: wave r takes row r
-  if (wave < nr) {
-    const int r = wave, n = sh.cnt[r];
+  if (logp)
+    for (int i = tid; i < V; i += NTH) logp[i] = x[i] - lse;
+  // selection: wave 0
+  if (wave == 0) {
+    const int n = sh.cnt;
     if (n <= TOPK_CAP) {
-      float l = lse[0];
-#pragma unroll
-      for (int q = 1; q < NR; ++q) if (r == q) l = lse[q];
       float c0 = -INFINITY, c1 = -INFINITY; int i0 = 0x7fffffff, i1 = 0x7fffffff;
-      if (lane < n) { c0 = sh.cv[r][lane]; i0 = sh.ci[r][lane]; }
-      if (lane + 64 < n) { c1 = sh.cv[r][lane + 64]; i1 = sh.ci[r][lane + 64]; }
+      if (lane < n) { c0 = sh.cv[lane]; i0 = sh.ci[lane]; }
+      if (lane + 64 < n) { c1 = sh.cv[lane + 64]; i1 = sh.ci[lane + 64]; }
       for (int rd = 0; rd < k; ++rd) {
         const bool first = c0 > c1 || (c0 == c1 && i0 < i1);
         float best = first ? c0 : c1; int besti = first ? i0 : i1;
         wave_argmax(best, besti);
-        if (lane == 0) { top_val[r * k + rd] = best - l; top_idx[r * k + rd] = besti; }
+        if (lane == 0) { top_val[rd] = best - lse; top_idx[rd] = besti; }
         if (i0 == besti) { c0 = -INFINITY; i0 = 0x7fffffff; }
         if (i1 == besti) { c1 = -INFINITY; i1 = 0x7fffffff; }
       }
     }
   }
-  // overflowed rows (block-uniform): k rounds of a block-wide arg-max over the elements ranked below the last winner
-#pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    if (r < nr && sh.cnt[r] > TOPK_CAP) {
-      const float* x = x0 + (long)r * ldl;
-      float pv = INFINITY; int pi = -1;              // last winner: later rounds take (value, index) ranked after it
-      for (int rd = 0; rd < k; ++rd) {
-        float best = -INFINITY; int besti = 0x7fffffff;
-        for (int i = tid; i < V; i += NTH) {
-          const float v = x[i];
-          const bool after = v < pv || (v == pv && i > pi);
-          if (after && (v > best || (v == best && i < besti))) { best = v; besti = i; }
-        }
-        wave_argmax(best, besti);
-        __syncthreads();
-        if (lane == 0) { sh.bv[wave] = best; sh.bi[wave] = besti; }
-        __syncthreads();
-        best = sh.bv[0]; besti = sh.bi[0];
-        for (int w = 1; w < NWV; ++w)
-          if (sh.bv[w] > best || (sh.bv[w] == best && sh.bi[w] < besti)) { best = sh.bv[w]; besti = sh.bi[w]; }
-        if (tid == 0) { top_val[r * k + rd] = best - lse[r]; top_idx[r * k + rd] = besti; }
-        pv = best; pi = besti;
+  // overflowed row (block-uniform): k rounds of a block-wide arg-max over the elements ranked below the last winner
+  for (int once = 0; once < 1; ++once) if (sh.cnt > TOPK_CAP) {            // (loop: pins hipcc's block layout)
+    float pv = INFINITY; int pi = -1;                // last winner: later rounds take (value, index) ranked after it
+    for (int rd = 0; rd < k; ++rd) {
+      float best = -INFINITY; int besti = 0x7fffffff;
+      for (int i = tid; i < V; i += NTH) {
+        const float v = x[i];
+        const bool after = v < pv || (v == pv && i > pi);
+        if (after && (v > best || (v == best && i < besti))) { best = v; besti = i; }
       }
+      wave_argmax(best, besti);
+      __syncthreads();
+      if (lane == 0) { sh.bv[wave] = best; sh.bi[wave] = besti; }
+      __syncthreads();
+      best = sh.bv[0]; besti = sh.bi[0];
+      for (int w = 1; w < NWV; ++w)
+        if (sh.bv[w] > best || (sh.bv[w] == best && sh.bi[w] < besti)) { best = sh.bv[w]; besti = sh.bi[w]; }
+      if (tid == 0) { top_val[rd] = best - lse; top_idx[rd] = besti; }
+      pv = best; pi = besti;
     }
   }
-  __syncthreads();
+  __syncthreads();                                   // (no work: see above)
 }
 
 template <bool NORM = true>
@@ -636,10 +564,10 @@ __global__ __launch_bounds__(512) void logsoftmax_topk_kernel(const float* __res
                                                               float* __restrict__ logp_out, long ldp,
                                                               float* __restrict__ top_val, int* __restrict__ top_idx,
                                                               int V, int k) {
-  __shared__ TopkSharedN<1> sh;
+  __shared__ TopkShared sh;
   const int n = blockIdx.x;
-  rows_logsoftmax_topk<1, 512, NORM>(logits + (long)n * ldl, ldl, 1, logp_out ? logp_out + (long)n * ldp : nullptr, ldp,
-                                     top_val + (long)n * k, top_idx + (long)n * k, V, k, sh);
+  row_logsoftmax_topk<512, NORM>(logits + (long)n * ldl, logp_out ? logp_out + (long)n * ldp : nullptr,
+                                 top_val + (long)n * k, top_idx + (long)n * k, V, k, sh);
 }
 
 
@@ -768,8 +696,8 @@ struct BeamShared {
 };
 
 // s.cv / s.ci hold the k x k candidates (written by this block; a barrier follows inside)
-template <int NT>
 __device__ __forceinline__ void beam_update(const BeamParams& p, const EmbedArgs& e, BeamShared& s, int b, int t) {
+  constexpr int NT = 256;                              // threads of beam_step_kernel
   const int tid = threadIdx.x, k = p.k, T = p.T;
   for (int r = tid; r < k; r += NT) {
     s.eos[r] = p.has_eos[b * k + r]; s.ne[r] = p.n_elem[b * k + r]; s.cu[r] = p.cumul[b * k + r];
@@ -825,49 +753,28 @@ __device__ __forceinline__ void beam_update(const BeamParams& p, const EmbedArgs
     s.cumul[tid] = cs + s.lp[tid];
   }
   const long base = (long)b * k * T;
-  if constexpr (NT >= 256) {
-    // one (row, column) element per thread and pass: all reads of the old rows, a barrier, then the writes
-    constexpr int EPT = (MAX_K * MAX_T + NT - 1) / NT;
-    long long tv[EPT]; float lv[EPT]; int av[EPT];
-    const int cols = t + 1;
+  // one (row, column) element per thread and pass: all reads of the old rows, a barrier, then the writes
+  constexpr int EPT = (MAX_K * MAX_T + NT - 1) / NT;
+  long long tv[EPT]; float lv[EPT]; int av[EPT];
+  const int cols = t + 1;
 #pragma unroll
-    for (int u = 0; u < EPT; ++u) {
-      const int i = tid + u * NT;
-      if (i < k * cols) {
-        const int r = i / cols, j = i - r * cols;
-        const long src = base + (long)s.parent[r] * T + j;
-        tv[u] = p.tok[src]; lv[u] = p.lp[src];
-        av[u] = j < t ? p.anc[src] : b * k + s.parent[r];
-      }
+  for (int u = 0; u < EPT; ++u) {
+    const int i = tid + u * NT;
+    if (i < k * cols) {
+      const int r = i / cols, j = i - r * cols;
+      const long src = base + (long)s.parent[r] * T + j;
+      tv[u] = p.tok[src]; lv[u] = p.lp[src];
+      av[u] = j < t ? p.anc[src] : b * k + s.parent[r];
     }
-    __syncthreads();
+  }
+  __syncthreads();
 #pragma unroll
-    for (int u = 0; u < EPT; ++u) {
-      const int i = tid + u * NT;
-      if (i < k * cols) {
-        const int r = i / cols, j = i - r * cols;
-        const long dst = base + (long)r * T + j;
-        p.tok[dst] = tv[u]; p.lp[dst] = lv[u]; p.anc[dst] = av[u];
-      }
-    }
-  } else {
-    for (int j = tid; j <= t; j += NT) {                // a thread owns whole columns
-      long long tv[MAX_K]; float lv[MAX_K]; int av[MAX_K];
-#pragma unroll
-      for (int r = 0; r < MAX_K; ++r) {
-        if (r < k) {
-          const long src = base + (long)s.parent[r] * T + j;
-          tv[r] = p.tok[src]; lv[r] = p.lp[src];
-          av[r] = j < t ? p.anc[src] : b * k + s.parent[r];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < MAX_K; ++r) {
-        if (r < k) {
-          const long dst = base + (long)r * T + j;
-          p.tok[dst] = tv[r]; p.lp[dst] = lv[r]; p.anc[dst] = av[r];
-        }
-      }
+  for (int u = 0; u < EPT; ++u) {
+    const int i = tid + u * NT;
+    if (i < k * cols) {
+      const int r = i / cols, j = i - r * cols;
+      const long dst = base + (long)r * T + j;
+      p.tok[dst] = tv[u]; p.lp[dst] = lv[u]; p.anc[dst] = av[u];
     }
   }
   if (e.embed && t + 2 < T && t + 1 < e.pos_rows) {     // input of the next position for the k chosen words (the
@@ -917,24 +824,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p, EmbedArgs 
     s.cv[i] = p.cand_val[(long)b * k * k + i];
     s.ci[i] = p.cand_idx[(long)b * k * k + i];
   }
-  beam_update<256>(p, e, s, b, t);       // (four waves: the k·d embedding rows and the prefix re-gather are the bulk)
-}
-
-// The whole tail of a search step in one launch: log-softmax + top-k of the image's k logits rows, NR rows per pass
-// (the candidates stay in LDS), the beam update above and the next position's input embedding.
-template <int NR>
-__global__ __launch_bounds__(512) void beam_search_step_kernel(const float* __restrict__ logits, long ldl, int V,
-                                                                BeamParams p, EmbedArgs e) {
-  __shared__ BeamShared s;
-  __shared__ TopkSharedN<NR> sh;
-  const int b = blockIdx.x, k = p.k;
-  const int t = *p.pos;
-  if (t + 1 >= p.T) return;
-  const int nrows = t == 0 ? 1 : k;     // at the first position only beam 0 seeds the search
-  for (int r0 = 0; r0 < nrows; r0 += NR)
-    rows_logsoftmax_topk<NR, 512, true>(logits + (long)(b * k + r0) * ldl, ldl, min(NR, nrows - r0), nullptr, 0, s.cv + r0 * k,
-                                 s.ci + r0 * k, V, k, sh);
-  beam_update<512>(p, e, s, b, t);
+  beam_update(p, e, s, b, t);            // (four waves: the k·d embedding rows and the prefix re-gather are the bulk)
 }
 
 __global__ void beam_finalize_kernel(const float* cumul, const int* n_elem, int* order, float* score, int n_img,
@@ -1142,22 +1032,6 @@ extern "C" int odic_beam_step(const float* cand_val, const int32_t* cand_idx, co
   return odic_launch_status();
 }
 
-extern "C" int odic_beam_search_step(const float* logits, int64_t ldl, int32_t V, const odic_beam_state* st,
-                                     const odic_embed_args* emb, int32_t n_img, int32_t beams, int32_t T,
-                                     int64_t eos_idx, void* stream) {
-  if (!logits) return ODIC_ENULL;
-  BeamParams p; EmbedArgs e;
-  const int rc = beam_params(p, e, st, emb, n_img, beams, T, eos_idx);
-  if (rc != 0) return rc;
-  if (V <= 0 || beams > V) return ODIC_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  // rows per pass: a thread's 20-value slice of every row of the pass lives in registers
-  if (beams <= 3) hipLaunchKernelGGL(beam_search_step_kernel<3>, dim3(n_img), dim3(512), 0, s, logits, (long)ldl, V, p, e);
-  else if (beams <= 5) hipLaunchKernelGGL(beam_search_step_kernel<5>, dim3(n_img), dim3(512), 0, s, logits, (long)ldl, V, p, e);
-  else hipLaunchKernelGGL(beam_search_step_kernel<6>, dim3(n_img), dim3(512), 0, s, logits, (long)ldl, V, p, e);
-  return odic_launch_status();
-}
-
 extern "C" int odic_beam_finalize(const odic_beam_state* st, int32_t* order, float* score, int32_t n_img,
                                   int32_t beams, void* stream) {
   if (!st || !order || !score) return ODIC_ENULL;
@@ -1210,91 +1084,3 @@ extern "C" int odic_logsoftmax_sample(const float* logits, int64_t ldl, float* l
   else hipLaunchKernelGGL(logsoftmax_sample_kernel<16>, dim3(N), dim3(1024), 0, s, logits, (long)ldl, logp_out, (long)ldp, top_val, top_idx, V, k, (unsigned long long)seed, pos);
   return odic_launch_status();
 }
-
-#ifdef ODIC_XATTN_VARIANTS
-// =================================================================================================
-// Diagnostic build only (tools/xattn_ab.py → tools/_build/libodic_dbg.so; never part of libodic_hip.so): the two forms
-// of the cross-attention step side by side on the SAME inputs inside the real pipeline, every output element compared
-// on the device, and the operands of the first mismatch kept for the post-mortem.
-// =================================================================================================
-namespace {
-struct DbgState { int count; int first_site; int row; int col; int snapped; int launches; int per_variant[10]; };
-
-__global__ __launch_bounds__(256) void dbg_compare_kernel(const float* __restrict__ a, const float* __restrict__ b, int n,
-                                                          int ld, int d, int site, DbgState* st, int variant) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0 && variant == 1) atomicAdd(&st->launches, 1);
-  if (i >= n) return;
-  const int r = i / d, c = i - r * d;
-  const unsigned x = __float_as_uint(a[(long)r * ld + c]), y = __float_as_uint(b[(long)r * ld + c]);
-  if (x != y) {
-    atomicAdd(&st->per_variant[variant], 1);
-    if (variant == 1) {
-      atomicAdd(&st->count, 1);
-      if (atomicCAS(&st->first_site, -1, site) == -1) { st->row = r; st->col = c; }
-    }
-  }
-}
-// one block: if this site holds the first mismatch and nothing was kept yet, keep q / both outputs of the image's beams
-// and the K / V columns [koff, koff + d) / [voff, voff + d) of the image
-__global__ __launch_bounds__(256) void dbg_snapshot_kernel(const float* q, long ldq, const float* kv, long ldkv, int koff,
-                                                           int voff, const float* a, const float* b, long ldo, int beams,
-                                                           int S, int d, int site, DbgState* st, float* snap) {
-  if (st->first_site != site || st->snapped) return;
-  __syncthreads();
-  const int img = st->row / beams;
-  float* sq = snap; float* sa = sq + beams * d; float* sb = sa + beams * d; float* sk = sb + beams * d; float* sv = sk + (long)S * d;
-  for (int i = threadIdx.x; i < beams * d; i += 256) {
-    const int r = i / d, c = i - r * d;
-    sq[i] = q[(long)(img * beams + r) * ldq + c];
-    sa[i] = a[(long)(img * beams + r) * ldo + c];
-    sb[i] = b[(long)(img * beams + r) * ldo + c];
-  }
-  for (int i = threadIdx.x; i < S * d; i += 256) {
-    const int s_ = i / d, c = i - s_ * d;
-    sk[i] = kv[((long)img * S + s_) * ldkv + koff + c];
-    sv[i] = kv[((long)img * S + s_) * ldkv + voff + c];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) st->snapped = 1;
-}
-}  // namespace
-
-// variant 0 = the shipped kernel, 1 = the round-2 software-pipelined form
-extern "C" int odic_dbg_cross_attn_step(int variant, const float* q, int64_t ldq, const float* kv, int64_t ldkv, int32_t koff,
-                                        int32_t voff, const int32_t* enc_len, const int32_t* row_valid, float* out,
-                                        int64_t ldo, int32_t N, int32_t n_img, int32_t S, int32_t d, int32_t heads,
-                                        void* stream) {
-  const int beams = N / n_img;
-  if (beams != 3 || d / heads != 64) return ODIC_EUNSUPPORTED;
-  const size_t sh = (size_t)(3 * S + 256 * 3 + 3) * sizeof(float);
-#define ODIC_DBG_X(V)                                                                                                  \
-  hipLaunchKernelGGL((cross_attn_step_kernel<3, V>), dim3(n_img, heads, 1), dim3(256), sh, (hipStream_t)stream, q,       \
-                     (long)ldq, kv, (long)ldkv, koff, voff, enc_len, row_valid, out, (long)ldo, beams, S, d, heads)
-  switch (variant) {
-    case 0: ODIC_DBG_X(0); break;
-    case 1: ODIC_DBG_X(1); break;
-    case 2: ODIC_DBG_X(2); break;
-    case 3: ODIC_DBG_X(3); break;
-    case 4: ODIC_DBG_X(4); break;
-    default: return ODIC_EINVAL;
-  }
-#undef ODIC_DBG_X
-  return odic_launch_status();
-}
-// state: int32[16] from the caller ({count, first_site = -1, row, col, snapped, launches, per_variant[10]});
-// snap: fp32 [3·beams·d + 2·S·d]; variant = which form `b` came from (the snapshot is taken for variant 1 only)
-extern "C" int odic_dbg_compare_snapshot(const float* a, const float* b, int64_t ldo, const float* q, int64_t ldq,
-                                         const float* kv, int64_t ldkv, int32_t koff, int32_t voff, int32_t N, int32_t n_img,
-                                         int32_t S, int32_t d, int32_t site, void* state, float* snap, int32_t variant,
-                                         void* stream) {
-  const int n = N * d;
-  if (variant < 1 || variant > 9) return ODIC_EINVAL;
-  hipLaunchKernelGGL(dbg_compare_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, b, n, (int)ldo, d,
-                     site, (DbgState*)state, variant);
-  if (variant == 1)
-    hipLaunchKernelGGL(dbg_snapshot_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, q, (long)ldq, kv, (long)ldkv, koff,
-                       voff, a, b, (long)ldo, N / n_img, S, d, site, (DbgState*)state, snap);
-  return odic_launch_status();
-}
-#endif  // ODIC_XATTN_VARIANTS

@@ -472,7 +472,7 @@ class CaptionerEngine:
 
     def step_logits(self, st: DecodeState, embed: bool = True) -> None:
         """Process position *st.pos for every sequence: next_tok → st.logits [N,V].  embed=False: the input row of
-        this position is already in st.ycat (written by the launch that chose the word: beam_reset / beam_search_step
+        this position is already in st.ycat (written by the launch that chose the word: beam_reset / beam_step
         with st.emb)."""
         g = self.g
         d, L, N = g.d_model, g.N_dec, st.N
@@ -519,14 +519,10 @@ class CaptionerEngine:
     def beam_step(self, st: DecodeState, eos_idx: int) -> None:
         """One full search step: decoder → log-softmax / top-k (one block per row) → beam bookkeeping + the next
         position's input rows (one block per image).  The state must have been armed with
-        ops.beam_reset(st.beam_state, ..., emb=st.emb).  (odic_beam_search_step does the two launches in one, but a
-        block per image then works through its k rows alone: 20 / 30 us against 14 / 16 at beam 3 / 5,
-        tools/topk_bench.py.)"""
+        ops.beam_reset(st.beam_state, ..., emb=st.emb).  (Both launches in one were slower, DESIGN.md §4.6: a block
+        per image then works through its k rows alone.)"""
         self.step_logits(st, embed=False)
         V = self.g.vocab_size
-        if os.environ.get("ODIC_FUSED_SEARCH_STEP", "0") == "1":
-            ops.beam_search_step(st.logits, V, V, st.beam_state, st.n_img, st.beams, st.T, eos_idx, emb=st.emb)
-            return
         ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx, emb=st.emb)
 

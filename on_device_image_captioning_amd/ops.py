@@ -615,7 +615,7 @@ def topk_rows(logp: torch.Tensor, top_val: torch.Tensor, top_idx: torch.Tensor, 
 
 
 def embed_args(embed, pos_table, y, ldy, d, scale) -> "_hip.EmbedArgs":
-    """odic_embed_args for beam_step / beam_search_step / beam_reset (the caller keeps the tensors alive)."""
+    """odic_embed_args for beam_step / beam_reset (the caller keeps the tensors alive)."""
     _need_cuda(embed, pos_table, y)
     return _hip.EmbedArgs(_p(embed), _p(pos_table), _p(y), ldy, d, scale, pos_table.shape[0])
 
@@ -635,14 +635,6 @@ def beam_step(cand_val, cand_idx, state: "_hip.BeamState", n_img, beams, T, eos_
     with _timed("beam_step", 0.0, n_img * beams * beams * 8.0 + _beam_bytes(n_img, beams, T, emb)):
         _hip.check(_hip.load().odic_beam_step(_p(cand_val), _p(cand_idx), C.byref(state), _emb_ref(emb), n_img, beams,
                                               T, eos_idx, _stream()), "odic_beam_step")
-
-
-def beam_search_step(logits, ldl, V, state: "_hip.BeamState", n_img, beams, T, eos_idx, emb=None) -> None:
-    """log-softmax + top-k of the step's logits rows, the beam update and (emb) the next input, in one launch."""
-    _need_cuda(logits)
-    with _timed("beam_search_step", 4.0 * n_img * beams * V, n_img * beams * V * 4.0 + _beam_bytes(n_img, beams, T, emb)):
-        _hip.check(_hip.load().odic_beam_search_step(_p(logits), ldl, V, C.byref(state), _emb_ref(emb), n_img, beams, T,
-                                                     eos_idx, _stream()), "odic_beam_search_step")
 
 
 def beam_finalize(state: "_hip.BeamState", order, score, n_img, beams) -> None:

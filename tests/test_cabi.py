@@ -59,8 +59,12 @@ def test_argument_validation_needs_no_gpu(lib):
     assert lib.odic_beam_step(16, 16, ctypes.byref(st), None, 4, 3, 129, 77, None) == -1
     assert lib.odic_beam_step(16, 16, ctypes.byref(st), None, 32768, 3, 20, 77, None) == -1
     assert lib.odic_beam_step(16, 16, ctypes.byref(st), None, 4, 17, 20, 77, None) == -1
-    assert lib.odic_beam_search_step(16, 100, 100, ctypes.byref(st), None, 4, 3, 129, 77, None) == -1
-    assert lib.odic_beam_search_step(None, 100, 100, ctypes.byref(st), None, 4, 3, 20, 77, None) == -2
+    # the retired one-launch search step and the diagnostic entry points are gone from the library and the binding
+    # (the names appear nowhere in the file, so not in its dynamic symbol table either)
+    with open(_hip.LIB_PATH, "rb") as f:
+        blob = f.read()
+    assert not [n for n in (b"odic_beam_search_step", b"odic_dbg_") if n in blob] and \
+        not [n for n in _hip.EXPORTED_SYMBOLS if n == "odic_beam_search_step" or n.startswith("odic_dbg_")]
     emb = _hip.EmbedArgs(16, 16, None, 512, 512, 1.0, 20)             # embedding tail asked for without an output
     assert lib.odic_beam_step(16, 16, ctypes.byref(st), ctypes.byref(emb), 4, 3, 20, 77, None) == -2
     assert lib.odic_beam_reset(None, None, 4, 3, 20, 79, None) == -2

@@ -626,10 +626,10 @@ def _beam_state(ops, n_img, k, T):
 
 
 @pytest.mark.parametrize("k,V", [(3, 1000), (5, 10000), (2, 12000), (9, 3000)])
-def test_beam_search_step_fused_equals_the_three_launches(ops, k, V):
-    """odic_beam_search_step (log-softmax + top-k + beam update + next input embedding in one launch) against
-    odic_logsoftmax_topk → odic_beam_step → odic_dec_embed on the same logits, bit for bit, over a whole search with
-    beams finishing on the way; a second search re-uses both states (counter re-armed, idempotent past the end)."""
+def test_beam_launches_with_embedding_tail_equal_separate_dec_embed(ops, k, V):
+    """The embedding tail of the beam launches — odic_beam_reset(emb) then odic_logsoftmax_topk → odic_beam_step(emb) —
+    against odic_logsoftmax_topk → odic_beam_step → odic_dec_embed on the same logits, bit for bit, over a whole search
+    with beams finishing on the way; a second search re-uses both states (counter re-armed, idempotent past the end)."""
     n_img, T, sos, eos, d = 5, 11, 3, 4, 64
     N = n_img * k
     g = torch.Generator().manual_seed(11)
@@ -639,7 +639,8 @@ def test_beam_search_step_fused_equals_the_three_launches(ops, k, V):
     tb, sb = _beam_state(ops, n_img, k, T)
     ya, yb = torch.zeros(N, 2 * d, device="cuda"), torch.zeros(N, 2 * d, device="cuda")
     emb = ops.embed_args(embed, pos_table, yb, 2 * d, d, 8.0)
-    cv, ci = torch.zeros(N, k, device="cuda"), torch.zeros(N, k, dtype=torch.int32, device="cuda")
+    cva, cia = torch.zeros(N, k, device="cuda"), torch.zeros(N, k, dtype=torch.int32, device="cuda")
+    cvb, cib = torch.zeros(N, k, device="cuda"), torch.zeros(N, k, dtype=torch.int32, device="cuda")
     for search in range(2):
         ops.beam_reset(sa, n_img, k, T, sos)
         ops.dec_embed(ta["next_tok"], embed, pos_table, ta["pos"], ya, 2 * d, N, d, 8.0)
@@ -650,14 +651,21 @@ def test_beam_search_step_fused_equals_the_three_launches(ops, k, V):
             if step >= 2:
                 logits[torch.rand(N, generator=g) < 0.4, eos] = 12.0
             lg = dev(logits)
-            ops.logsoftmax_topk(lg, V, None, 0, cv, ci, N, V, k)
-            ops.beam_step(cv, ci, sa, n_img, k, T, eos)
+            before = {name: t.clone() for name, t in tb.items()}, yb.clone()
+            ops.logsoftmax_topk(lg, V, None, 0, cva, cia, N, V, k)
+            ops.beam_step(cva, cia, sa, n_img, k, T, eos)
             if step < T - 2:                           # (position T-1 is never an input)
                 ops.dec_embed(ta["next_tok"], embed, pos_table, ta["pos"], ya, 2 * d, N, d, 8.0)
-            ops.beam_search_step(lg, V, V, sb, n_img, k, T, eos, emb=emb)
+            ops.logsoftmax_topk(lg, V, None, 0, cvb, cib, N, V, k)
+            ops.beam_step(cvb, cib, sb, n_img, k, T, eos, emb=emb)
             for name in ta:
                 assert torch.equal(ta[name], tb[name]), f"search {search} step {step}: {name}"
             assert torch.equal(ya, yb), f"search {search} step {step}: next input rows"
+            assert int(tb["ctr"].item()) == 0, f"search {search} step {step}: arrival counter not re-armed"
+            if step >= T - 1:
+                for name in tb:
+                    assert torch.equal(before[0][name], tb[name]), f"search {search} step {step} past the end: {name}"
+                assert torch.equal(before[1], yb), f"search {search} step {step} past the end: next input rows"
         assert int(ta["pos"].item()) == T - 1 and int(ta["has_eos"].sum().item()) > 0
 
 

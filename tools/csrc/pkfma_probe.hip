@@ -1,8 +1,8 @@
-// Minimal hardware probe for the round-2 cross-attention incident (tools/xattn_ab.py located it on
-// `v_pk_fma_f32 ... op_sel:[0,1,0]` with vector-memory loads in flight).  Every lane computes the same sum of products
-// four ways — two packed forms whose source selection differs only in HOW the same operand dword is named, and a scalar
-// form — while global loads that nothing waits for keep returning into other registers.  Any lane where the results
-// differ is a hardware / code-generation fault, independent of this library's kernels.
+// Minimal hardware probe for the round-2 cross-attention incident (the in-pipeline A/B harness of commit
+// d9f7de9 located it on `v_pk_fma_f32 ... op_sel:[0,1,0]` with vector-memory loads in flight).  Every lane computes the
+// same sum of products four ways — two packed forms whose source selection differs only in HOW the same operand dword
+// is named, and a scalar form — while global loads that nothing waits for keep returning into other registers.  Any
+// lane where the results differ is a hardware / code-generation fault, independent of this library's kernels.
 //
 //   form A   v_pk_fma_f32 acc, a, b,  acc op_sel:[0,1,0]        low = a.lo·b.HI + acc.lo   high = a.hi·b.HI + acc.hi
 //   form B   v_pk_fma_f32 acc, a, b', acc op_sel_hi:[1,0,1]     b' = (b.hi, junk):  low = a.lo·b'.lo, high = a.hi·b'.lo

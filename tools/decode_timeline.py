@@ -67,7 +67,7 @@ def report(path):
           f"{total - busy:.1f} us of gaps ({(total - busy) / max(1, len(chain) - 1):.2f} us per boundary)")
     gaps = sorted(((chain[i][0] - chain[i - 1][1]) / 1e3, i) for i in range(1, len(chain)))[-5:]
     print("largest gaps (us, launch index): " + ", ".join(f"{g:.1f} @ {i}" for g, i in reversed(gaps)))
-    steps = [i + 1 for i, k in enumerate(chain[:-1]) if "beam_search_step" in k[2] or "beam_step_kernel" in k[2]]
+    steps = [i + 1 for i, k in enumerate(chain[:-1]) if "beam_step_kernel" in k[2]]
     steps = [1] + steps                                # (launch 0 is the reset; a step ends with the beam update)
     which = min(int(os.environ.get("ODIC_STEP", len(steps) // 2)), len(steps) - 2)
     mid = steps[which]

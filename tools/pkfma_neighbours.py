@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Which co-resident kernel makes `v_pk_fma_f32 ... op_sel:[0,1,0]` return a wrong low half in lanes 48-63?
-(tools/csrc/pkfma_probe.hip mode 0: registers only, no memory traffic in the probe itself.)"""
+(tools/csrc/pkfma_probe.hip mode 0: registers only, no memory traffic in the probe itself.)
+Loads tools/_build/libpkfma_probe.so; the hipcc line that builds it is in tools/pkfma_probe.py's docstring."""
 import ctypes as C
 import json
 import os

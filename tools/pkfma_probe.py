@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Drives tools/csrc/pkfma_probe.hip: does `v_pk_fma_f32 ... op_sel:[0,1,0]` compute the same sums as its
 `op_sel_hi:[1,0,1]` twin and as scalar FMAs — alone, with global loads in flight, and beside a GEMM stream?
-Prints one line per (mode, background) with the number of lanes x iterations whose four results disagreed."""
+Prints one line per (mode, background) with the number of lanes x iterations whose four results disagreed.
+Build the probe first, from the repository root (tools/_build/ is ignored by git):
+    mkdir -p tools/_build
+    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -shared tools/csrc/pkfma_probe.hip -o tools/_build/libpkfma_probe.so"""
 import ctypes as C
 import json
 import os

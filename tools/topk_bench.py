@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""odic_logsoftmax_topk / odic_beam_search_step timing against k (beams), N (rows) and V, back to back inside one
-hipGraph (the search-step kernel re-armed by odic_beam_reset before every call)."""
+"""Timing of the tail of a search step — odic_logsoftmax_topk and odic_beam_step (with the embedding tail) — against k
+(beams) and V, back to back inside one hipGraph (the beam state re-armed by odic_beam_reset before every step pair)."""
 import os
 import sys
 
@@ -54,29 +54,16 @@ def main():
             t, st = beam_state(n_img, k, T)
             embed, ptab, y = torch.randn(V, d, device="cuda"), torch.randn(T, d, device="cuda"), torch.zeros(N, d, device="cuda")
             emb = ops.embed_args(embed, ptab, y, d, d, 1.0)
-            t_reset = graph_time(lambda: ops.beam_reset(st, n_img, k, T, 3, emb=emb))
 
-            def two_steps():        # reset, step at pos 0 (one row per image), step at pos 1 (k rows per image)
+            def steps(n):           # reset, then n steps: position 0 (one row per image seeds), position 1 (k rows per image)
                 ops.beam_reset(st, n_img, k, T, 3, emb=emb)
-                ops.beam_search_step(lg, V, V, st, n_img, k, T, 4, emb=emb)
-                ops.beam_search_step(lg, V, V, st, n_img, k, T, 4, emb=emb)
+                for _ in range(n):
+                    ops.logsoftmax_topk(lg, V, None, 0, cv, ci, N, V, k)
+                    ops.beam_step(cv, ci, st, n_img, k, T, 4, emb=emb)
 
-            def one_step():
-                ops.beam_reset(st, n_img, k, T, 3, emb=emb)
-                ops.beam_search_step(lg, V, V, st, n_img, k, T, 4, emb=emb)
-
-            t1, t2 = graph_time(one_step), graph_time(two_steps)
-
-            def unfused():
-                ops.beam_reset(st, n_img, k, T, 3)
-                ops.logsoftmax_topk(lg, V, None, 0, cv, ci, N, V, k)
-                ops.beam_step(cv, ci, st, n_img, k, T, 4)
-                ops.logsoftmax_topk(lg, V, None, 0, cv, ci, N, V, k)
-                ops.beam_step(cv, ci, st, n_img, k, T, 4)
-            t_un = graph_time(unfused)
-            print(f"V={V:5d} k={k}: logsoftmax_topk ({N} rows) {t_topk:6.2f} us | reset {t_reset:5.2f} | fused step at pos 0 "
-                  f"{t1 - t_reset:6.2f}, at pos 1 {t2 - t1:6.2f} | unfused topk+beam_step at pos 1 "
-                  f"{t_un - t_reset - (t_topk + 0) - 0:6.2f} (minus one topk: two launches + a step-0 beam_step)", flush=True)
+            t0, t1, t2 = (graph_time(lambda n=n: steps(n)) for n in (0, 1, 2))
+            print(f"V={V:5d} k={k}: logsoftmax_topk ({N} rows) {t_topk:6.2f} us | reset {t0:5.2f} | topk + beam_step at pos 0 "
+                  f"{t1 - t0:6.2f}, at pos 1 {t2 - t1:6.2f}", flush=True)
 
 
 if __name__ == "__main__":
