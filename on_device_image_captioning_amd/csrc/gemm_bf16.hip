@@ -24,13 +24,14 @@
 //     owns a PM x PN rectangle of the tile grid chosen so that its W sub-panel stays L2-resident
 //     while its A panels stream through once (PMC: L2 hit rate 70 % → see profiles/).
 //   * rows/cols beyond M/N are clamped on load (valid memory, discarded on store).
-#include "odic_common.h"
+// The swizzle, the W row permutation, the tile grid and the host's launch helpers are gemm_tile.h's, shared with
+// gemm_x3.hip and gemm_lowp.hip (which repeat this kernel's rectangle walk, staging and counted wait as text).
+#include "gemm_tile.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
 
 struct Params {
   const bf16_raw* A; const bf16_raw* W; const float* bias; const float* residual; void* out;
@@ -38,28 +39,9 @@ struct Params {
   long lda, ldw, ldr, ldc;
   long strideA, strideW, strideBias, strideR, strideC;
   float alpha; int act; int bias_axis;
-  int tiles_m, tiles_n;
-  int pm, pn;          // XCD partition of the tile grid, pm * pn == 8
+  TileGrid grid;       // tile counts and XCD partition (gemm_tile.h)
   const float* a_ln; long ld_aln; float ln_eps;   // A-resident kernels: fp32 rows whose LayerNorm (no affine) is the A operand
 };
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// 16-byte-chunk swizzle inside an LDS row.  BK = 64 (128-byte rows, 8 chunks): chunk ^ (row & 7).
-// BK = 32 (64-byte rows, 4 chunks; 4 rows share a 256-byte bank row): chunk ^ f((row >> 2) & 3) with
-// f = {0, 2, 3, 1}, which makes every 16-lane service group of ds_read_b128 hit 16 distinct slots.
-template <int BK> __device__ __forceinline__ int swz(int chunk, int row) {
-  if constexpr (BK == 64) return chunk ^ (row & 7);
-  else return chunk ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3);
-}
-
-// LDS row r of the W tile holds tile-local output column wperm(r): inside each 32-row group the two
-// 16-row MFMA tiles interleave in runs of 4, so that MFMA slot 4·fq + j of tile h is column
-// 8·fq + 4·h + j and a lane's registers across the tile pair are 8 adjacent output columns.
-__device__ __forceinline__ int wperm(int r) {
-  return (r & ~31) + 8 * ((r & 15) >> 2) + 4 * ((r >> 4) & 1) + (r & 3);
-}
 
 // (second launch bound: the 4-wave blocks with 128 accumulator registers per lane must stay within 256 registers
 //  so that two of them share a CU — left alone hipcc takes 158 + 128)
@@ -94,9 +76,9 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
   int tm, tn;
   {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int xm = xcd / p.pn, xn = xcd - xm * p.pn;
-    const int r0 = xm * p.tiles_m / p.pm, r1 = (xm + 1) * p.tiles_m / p.pm;
-    const int c0 = xn * p.tiles_n / p.pn, c1 = (xn + 1) * p.tiles_n / p.pn;
+    const int xm = xcd / p.grid.pn, xn = xcd - xm * p.grid.pn;
+    const int r0 = xm * p.grid.tiles_m / p.grid.pm, r1 = (xm + 1) * p.grid.tiles_m / p.grid.pm;
+    const int c0 = xn * p.grid.tiles_n / p.grid.pn, c1 = (xn + 1) * p.grid.tiles_n / p.grid.pn;
     const int w = c1 - c0;
     if (idx >= (r1 - r0) * w) return;             // rectangles differ by at most one row/col of tiles
     const int lr = idx / w;
@@ -109,7 +91,7 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
 
   // ---- LDS-DMA source addresses: instruction i of this wave fills rows (i*NW+wave)*RPI .. +RPI-1
   const int srow = lane / CPR;
-  const int schunk = swz<BK>(lane % CPR, srow);  // logical 16-byte chunk this lane must fetch
+  const int schunk = swz<ROWB>(lane % CPR, srow);  // logical 16-byte chunk this lane must fetch
   const bf16_raw* a_src[A_INSTR];
   const bf16_raw* w_src[W_INSTR];
 #pragma unroll
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(64 * NWM * NWN * KS, (NWM * NWN * KS == 4 && MI * N
     for (int kq = 0; kq < BK / 32 / KS; ++kq) {
       const int kk = KS == 1 ? kq : kg;
       bf16x8_t af[MI], wf[NI];
-      const int chunk = swz<BK>(kk * 4 + fq, frow) << 4;
+      const int chunk = swz<ROWB>(kk * 4 + fq, frow) << 4;
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) af[mi] = *(const bf16x8_t*)(la + mi * 16 * ROWB + chunk);
 #pragma unroll
@@ -554,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_apanel_kernel(Params p, int 
   for (int i = 0; i < INSTR; ++i) {
     const int j = i * NW + wave, kt = j / RG, rg = j - kt * RG;
     const int srow = lane >> 3, r = rg * 8 + srow;
-    w_off[i] = wperm(r) * (int)p.ldw + kt * 64 + swz<64>(lane & 7, srow) * 8;
+    w_off[i] = wperm(r) * (int)p.ldw + kt * 64 + swz<128>(lane & 7, srow) * 8;
   }
   auto issue = [&](int c, int h, int buf) {
     const bf16_raw* wb = p.W + (long)c * BNC * p.ldw + h * KTS * 64;
@@ -598,7 +580,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_apanel_kernel(Params p, int 
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
           bf16x8_t wf[NI];
-          const int chunk = swz<64>(kk * 4 + fq, frow) << 4;
+          const int chunk = swz<128>(kk * 4 + fq, frow) << 4;
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni) wf[ni] = *(const bf16x8_t*)(lw + kt * SUB + ni * 16 * 128 + chunk);
 #pragma unroll
@@ -699,9 +681,7 @@ int launch_apanel(Params& p, int out_dtype, int batch, hipStream_t stream) {
   // column ranges per panel: the smallest divisor of the chunk count that gives the chip >= `want` blocks (3 rounds of 2
   // per CU) — a block should keep its A rows for as many chunks as the grid size allows
   static const int want = getenv("ODIC_APANEL_BLOCKS") ? atoi(getenv("ODIC_APANEL_BLOCKS")) : 1536;
-  int nsplit = nchunks;
-  for (int d = 1; d <= nchunks; ++d)
-    if (nchunks % d == 0 && (long)panels * d >= want) { nsplit = d; break; }
+  const int nsplit = panel_split(panels, nchunks, want);
   dim3 grid(8 * ((panels + 7) / 8) * nsplit), block(256);
   const int SHMEM = 2 * (KT / KH) * BNC * 128 + (nchunks + nsplit - 1) / nsplit * BNC * 4;     // W buffers + the block's bias values
   if (SHMEM > 64 * 1024) return ODIC_EUNSUPPORTED;
@@ -733,28 +713,12 @@ int launch_cfg(Params& p, int out_dtype, int batch, hipStream_t stream) {
   constexpr int SH_RED = KS == 2 ? NWM * NWN * MI * NI * 1024 : 0;     // K-split: one group's accumulators
   constexpr int SHMEM = SH_STAGES > SH_RED ? SH_STAGES : SH_RED;
   if (p.K % BK != 0) return ODIC_EINVAL;
-  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
-  int pm, pn;                                 // XCD partition: the split with the least fabric traffic (odic_common.h)
-  odic_xcd_partition(p.tiles_m, p.tiles_n, (double)p.M * p.K * 2.0, (double)p.N * p.K * 2.0,
-                     32 * (NWM * NWN * KS <= 4 ? 2 : 1), &pm, &pn);
-  p.pm = pm; p.pn = pn;
-  int max_rect = 0;
-  for (int xm = 0; xm < pm; ++xm)
-    for (int xn = 0; xn < pn; ++xn) {
-      const int r = ((xm + 1) * p.tiles_m / pm - xm * p.tiles_m / pm) * ((xn + 1) * p.tiles_n / pn - xn * p.tiles_n / pn);
-      if (r > max_rect) max_rect = r;
-    }
+  const int max_rect = tile_grid(p.grid, p.M, p.N, BM, BN, (double)p.M * p.K * 2.0, (double)p.N * p.K * 2.0,
+                                 32 * (NWM * NWN * KS <= 4 ? 2 : 1));
   dim3 grid(8 * max_rect, 1, batch), block(64 * NWM * NWN * KS);
-  auto kb = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, bf16_raw, KS>;
-  auto kf = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, float, KS>;
-  if (SHMEM > 64 * 1024) {
-    static bool done = false;       // idempotent; racing first calls set the same value
-    if (!done) {
-      (void)hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      done = true;
-    }
-  }
+  constexpr auto kb = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, bf16_raw, KS>;
+  constexpr auto kf = gemm_bf16_nt_kernel<NWM, NWN, MI, NI, NSTAGE, BK, float, KS>;
+  tile_allow_lds<SHMEM, kb, kf>();
   if (out_dtype == ODIC_BF16) hipLaunchKernelGGL(kb, grid, block, SHMEM, stream, p);
   else hipLaunchKernelGGL(kf, grid, block, SHMEM, stream, p);
   return odic_launch_status();
@@ -789,12 +753,9 @@ int odic_gemm_bf16_launch(const odic_gemm_args* a, hipStream_t stream) {
   // shapes (tools/gemm_tune.py; profiles/r01_gemm_tile_sweep.txt).
   int cfg = a->tile_cfg;
   if (cfg < 0) {
-    auto rounds = [&](int bm, int bn, int slots) {
-      const long t = (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn) * a->batch;
-      return (double)((t + slots - 1) / slots);
-    };
-    const double c0 = rounds(128, 64, 768) * 1.0, c1 = rounds(128, 128, 512) * 1.38;
-    const double c2 = a->N % 256 == 0 ? rounds(256, 256, 256) * 2.6 : 1e30;
+    const double c0 = tile_rounds(a->M, a->N, a->batch, 128, 64, 768) * 1.0;
+    const double c1 = tile_rounds(a->M, a->N, a->batch, 128, 128, 512) * 1.38;
+    const double c2 = a->N % 256 == 0 ? tile_rounds(a->M, a->N, a->batch, 256, 256, 256) * 2.6 : 1e30;
     cfg = (c0 <= c1 && c0 <= c2) ? 0 : (c1 <= c2 ? 1 : 2);
   }
   switch (cfg) {

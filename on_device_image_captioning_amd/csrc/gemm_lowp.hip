@@ -10,43 +10,27 @@
 //                       dequantisation is ONE per-column factor col_scale[n] = sa·sw[n] in the epilogue.
 //   in_dtype ODIC_F16   the attention-output projection (A = fp16 attention output, W fp16); v_mfma_f32_16x16x32_f16.
 //
-// Same structure as gemm_bf16.hip's one-block-per-tile kernel (LDS-DMA staging with the XOR chunk swizzle on the
-// source address and on the fragment read, counted vmcnt + raw barrier, operands swapped so a lane owns 8 adjacent
-// output columns of a row, W rows staged permuted, XCD-aware tile partition); what differs:
+// Same one-block-per-tile structure as gemm_bf16.hip (its header describes it).  The swizzle, the W row permutation,
+// the tile grid and the host's launch helpers are gemm_tile.h's, shared with gemm_bf16.hip and gemm_x3.hip; what differs:
 //   * an LDS row is ROWB = 128 bytes = 128 fp8 K-elements (or 64 fp16): half the staging bytes per FLOP of bf16 —
 //     the generic tiles are L2→LDS-fill-bound, so this is where fp8 pays even at the bf16 MFMA rate
 //     of the non-scaled fp8 instruction;
 //   * a 16-byte ds_read_b128 fragment feeds TWO fp8 MFMAs (its low and high 8 bytes are the K-slots of two
 //     consecutive 32-deep steps; A and W use the same assignment, and a dot product does not care about K order).
-#include "odic_common.h"
+#include "gemm_tile.h"
 #include <type_traits>
 
 namespace {
 
 typedef unsigned char fp8_raw;
-typedef _Float16 f16_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct Params {
   const char* A; const char* W; const float* bias; const float* residual; const float* col_scale; void* out;
   int M, N, K;                // K in ELEMENTS
   long lda, ldw, ldr, ldc;    // elements
   float alpha, out_scale; int act; int bias_axis;
-  int tiles_m, tiles_n, pm, pn;
+  TileGrid grid;
 };
-
-// 16-byte-chunk swizzle inside an LDS row (as gemm_bf16.hip): 128-byte rows: chunk ^ (row & 7); 64-byte rows (4 rows share
-// a 256-byte bank row): chunk ^ f((row >> 2) & 3), f = {0, 2, 3, 1}.
-template <int ROWB> __device__ __forceinline__ int swz(int chunk, int row) {
-  if constexpr (ROWB == 128) return chunk ^ (row & 7);
-  else return chunk ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3);
-}
-
-__device__ __forceinline__ int wperm(int r) {
-  return (r & ~31) + 8 * ((r & 15) >> 2) + 4 * ((r >> 4) & 1) + (r & 3);
-}
 
 __device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) { return f32x4_to_fp8(a, b, c, d); }
 
@@ -81,9 +65,9 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_lowp_nt_kernel(Params p) 
   int tm, tn;
   {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int xm = xcd / p.pn, xn = xcd - xm * p.pn;
-    const int r0 = xm * p.tiles_m / p.pm, r1 = (xm + 1) * p.tiles_m / p.pm;
-    const int c0 = xn * p.tiles_n / p.pn, c1 = (xn + 1) * p.tiles_n / p.pn;
+    const int xm = xcd / p.grid.pn, xn = xcd - xm * p.grid.pn;
+    const int r0 = xm * p.grid.tiles_m / p.grid.pm, r1 = (xm + 1) * p.grid.tiles_m / p.grid.pm;
+    const int c0 = xn * p.grid.tiles_n / p.grid.pn, c1 = (xn + 1) * p.grid.tiles_n / p.grid.pn;
     const int w = c1 - c0;
     if (idx >= (r1 - r0) * w) return;
     const int lr = idx / w;
@@ -421,29 +405,12 @@ template <int NWM, int NWN, int MI, int NI, int NSTAGE, int ROWB, int EB, bool M
 int launch(Params& p, int out_dtype, hipStream_t stream) {
   constexpr int BM = NWM * MI * 16, BN = NWN * NI * 16;
   constexpr int SHMEM = NSTAGE * (BM + BN) * ROWB;
-  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
-  int pm, pn;                                 // XCD partition: the split with the least fabric traffic (odic_common.h)
-  odic_xcd_partition(p.tiles_m, p.tiles_n, (double)p.M * p.K * EB, (double)p.N * p.K * EB, 32 * (NWM * NWN <= 4 ? 2 : 1), &pm, &pn);
-  p.pm = pm; p.pn = pn;
-  int max_rect = 0;
-  for (int xm = 0; xm < pm; ++xm)
-    for (int xn = 0; xn < pn; ++xn) {
-      const int r = ((xm + 1) * p.tiles_m / pm - xm * p.tiles_m / pm) * ((xn + 1) * p.tiles_n / pn - xn * p.tiles_n / pn);
-      if (r > max_rect) max_rect = r;
-    }
+  const int max_rect = tile_grid(p.grid, p.M, p.N, BM, BN, (double)p.M * p.K * EB, (double)p.N * p.K * EB, 32 * (NWM * NWN <= 4 ? 2 : 1));
   dim3 grid(8 * max_rect), block(64 * NWM * NWN);
-  auto k32 = gemm_lowp_nt_kernel<NWM, NWN, MI, NI, NSTAGE, ROWB, EB, float, MX>;
-  auto k16 = gemm_lowp_nt_kernel<NWM, NWN, MI, NI, NSTAGE, ROWB, EB, f16_t, MX>;
-  auto k8 = gemm_lowp_nt_kernel<NWM, NWN, MI, NI, NSTAGE, ROWB, EB, fp8_raw, MX>;
-  if (SHMEM > 64 * 1024) {
-    static bool done = false;       // code-object attribute; idempotent
-    if (!done) {
-      (void)hipFuncSetAttribute((const void*)k32, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      (void)hipFuncSetAttribute((const void*)k16, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      (void)hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      done = true;
-    }
-  }
+  constexpr auto k32 = gemm_lowp_nt_kernel<NWM, NWN, MI, NI, NSTAGE, ROWB, EB, float, MX>;
+  constexpr auto k16 = gemm_lowp_nt_kernel<NWM, NWN, MI, NI, NSTAGE, ROWB, EB, f16_t, MX>;
+  constexpr auto k8 = gemm_lowp_nt_kernel<NWM, NWN, MI, NI, NSTAGE, ROWB, EB, fp8_raw, MX>;
+  tile_allow_lds<SHMEM, k32, k16, k8>();
   if (out_dtype == ODIC_F32) hipLaunchKernelGGL(k32, grid, block, SHMEM, stream, p);
   else if (out_dtype == ODIC_F16) hipLaunchKernelGGL(k16, grid, block, SHMEM, stream, p);
   else if (out_dtype == ODIC_FP8) hipLaunchKernelGGL(k8, grid, block, SHMEM, stream, p);
@@ -455,11 +422,9 @@ template <int EB>
 int dispatch(Params& p, const odic_gemm_args* a, hipStream_t stream) {
   int cfg = a->tile_cfg;
   if (cfg < 0) {
-    auto rounds = [&](int bm, int bn, int slots) {
-      const long t = (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn);
-      return (double)((t + slots - 1) / slots);
-    };
-    const double c0 = rounds(128, 64, 768) * 1.0, c1 = rounds(128, 128, 512) * 1.38, c2 = rounds(256, 128, 512) * 2.2;
+    const double c0 = tile_rounds(a->M, a->N, 1, 128, 64, 768) * 1.0;
+    const double c1 = tile_rounds(a->M, a->N, 1, 128, 128, 512) * 1.38;
+    const double c2 = tile_rounds(a->M, a->N, 1, 256, 128, 512) * 2.2;
     cfg = (c0 <= c1 && c0 <= c2) ? 0 : (c1 <= c2 ? 1 : 2);
   }
   if constexpr (EB == 1) {

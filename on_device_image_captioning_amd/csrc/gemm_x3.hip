@@ -9,22 +9,18 @@
 // is a 5x higher matrix-pipe ceiling at fp32-class accuracy; against the bf16 kernel the LDS image carries twice
 // the bytes per K but feeds 1.5x the MFMAs per staged byte, which is what these L2→LDS-fill-bound tiles want.
 //
-// Same structure as gemm_bf16.hip's one-block-per-tile kernel (LDS-DMA staging, XOR chunk swizzle on the source
-// address and on the fragment read, counted vmcnt + raw barrier, operands swapped so a lane owns 8 adjacent
-// output columns of a row, W rows staged permuted, XCD-aware tile partition).  What differs:
+// Same one-block-per-tile structure as gemm_bf16.hip (its header describes it).  The swizzle, the W row permutation,
+// the tile grid and the host's launch helpers are gemm_tile.h's, shared with gemm_bf16.hip and gemm_lowp.hip.  What differs:
 //   * a K-tile is 32 elements = one 128-byte LDS row per matrix row, staged PLANAR: LDS chunks 0..3 hold the hi
 //     fragments of k-groups 0..3, chunks 4..7 their lo fragments (the per-lane DMA source address does the
 //     de-interleave for free), so the hi / lo fragment of lane (row, fq) is chunk fq / 4 + fq — the conflict-free
 //     ds_read_b128 pattern of the bf16 kernel, twice;
 //   * out_dtype ODIC_H2: the lane's 8 adjacent columns are exactly one h2 group → 32 contiguous bytes (hi | lo).
 //   * GELU is the exact erf form: this mode exists to reproduce the fp32 reference's captions.
-#include "odic_common.h"
+#include "gemm_tile.h"
 #include <type_traits>
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct Params {
   const char* A; const char* W; const float* bias; const float* residual; void* out;
@@ -32,15 +28,10 @@ struct Params {
   long lda, ldw, ldr, ldc;    // elements (4 bytes each for h2 operands)
   long strideA, strideW, strideBias, strideR, strideC;
   float alpha; int act; int bias_axis;
-  int tiles_m, tiles_n, pm, pn;
+  TileGrid grid;
 };
 
 constexpr int ROWB = 128;      // bytes per LDS row = 32 h2 elements
-
-__device__ __forceinline__ int swz(int chunk, int row) { return chunk ^ (row & 7); }
-__device__ __forceinline__ int wperm(int r) {
-  return (r & ~31) + 8 * ((r & 15) >> 2) + 4 * ((r >> 4) & 1) + (r & 3);
-}
 
 template <int NWM, int NWN, int MI, int NI, int NSTAGE, typename OutT>
 __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_nt_kernel(Params p) {
@@ -63,9 +54,9 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_nt_kernel(Params p) {
   int tm, tn;
   {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int xm = xcd / p.pn, xn = xcd - xm * p.pn;
-    const int r0 = xm * p.tiles_m / p.pm, r1 = (xm + 1) * p.tiles_m / p.pm;
-    const int c0 = xn * p.tiles_n / p.pn, c1 = (xn + 1) * p.tiles_n / p.pn;
+    const int xm = xcd / p.grid.pn, xn = xcd - xm * p.grid.pn;
+    const int r0 = xm * p.grid.tiles_m / p.grid.pm, r1 = (xm + 1) * p.grid.tiles_m / p.grid.pm;
+    const int c0 = xn * p.grid.tiles_n / p.grid.pn, c1 = (xn + 1) * p.grid.tiles_n / p.grid.pn;
     const int w = c1 - c0;
     if (idx >= (r1 - r0) * w) return;
     const int lr = idx / w;
@@ -76,10 +67,10 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_nt_kernel(Params p) {
   const char* A = p.A + bz * p.strideA * 4;
   const char* W = p.W + bz * p.strideW * 4;
 
-  // LDS-DMA source: LDS slot `pos` (0..7) of a row holds logical image chunk c = swz(pos): c < 4 → hi fragment of
+  // LDS-DMA source: LDS slot `pos` (0..7) of a row holds logical image chunk c = swz<ROWB>(pos): c < 4 → hi fragment of
   // k-group c (memory chunk 2c of the 128-byte K-tile), c >= 4 → lo fragment of k-group c-4 (memory chunk 2(c-4)+1)
   const int srow = lane >> 3;
-  const int simg = swz(lane & 7, srow);
+  const int simg = swz<ROWB>(lane & 7, srow);
   const int smem_chunk = simg < 4 ? 2 * simg : 2 * (simg - 4) + 1;
   const char* a_src[A_INSTR];
   const char* w_src[W_INSTR];
@@ -116,7 +107,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_nt_kernel(Params p) {
   for (int t = 0; t < D; ++t)
     if (t < nk) stage(t, t);
 
-  const int ch_hi = swz(fq, frow) << 4, ch_lo = swz(4 + fq, frow) << 4;
+  const int ch_hi = swz<ROWB>(fq, frow) << 4, ch_lo = swz<ROWB>(4 + fq, frow) << 4;
   for (int kt = 0; kt < nk; ++kt) {
     const int ahead = min(D - 1, nk - 1 - kt);
     if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
@@ -374,7 +365,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_apanel_kernel(PanelParams p, i
   for (int i = 0; i < INSTR; ++i) {
     const int j = i * NW + wave, kt = j / RG, rg = j - kt * RG;
     const int srow = lane >> 3, r = rg * 8 + srow;
-    const int simg = swz(lane & 7, srow);
+    const int simg = swz<ROWB>(lane & 7, srow);
     const int smem_chunk = simg < 4 ? 2 * simg : 2 * (simg - 4) + 1;
     w_off[i] = wperm(r) * (int)p.ldw * 4 + kt * ROWB + smem_chunk * 16;
   }
@@ -390,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_apanel_kernel(PanelParams p, i
   float* sbias = (float*)(lds + 2 * CHUNK);
   for (int t = tid; t < (c1 - c0) * BNC; t += 256) sbias[t] = p.bias ? p.bias[c0 * BNC + t] : 0.f;
   __builtin_amdgcn_s_waitcnt(0x0070);                                  // vmcnt(0) lgkmcnt(0) (the builtin: hipcc must see it)
-  const int ch_hi = swz(fq, frow) << 4, ch_lo = swz(4 + fq, frow) << 4;
+  const int ch_hi = swz<ROWB>(fq, frow) << 4, ch_lo = swz<ROWB>(4 + fq, frow) << 4;
   for (int c = c0; c < c1; ++c) {
     if (c != c0) __builtin_amdgcn_s_waitcnt(0x0F70 | (NST & 15) | ((NST >> 4) << 14));      // vmcnt(NST)
     __builtin_amdgcn_s_barrier();
@@ -458,9 +449,7 @@ int launch_panel(const odic_gemm_args* a, hipStream_t stream) {
   p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ld_aln = a->ld_aln; p.ldw = a->ldw; p.ldc = a->ldc;
   p.alpha = a->alpha; p.ln_eps = a->ln_eps; p.act = a->act;
   const int panels = a->M / BM, nchunks = a->N / BNC;
-  int nsplit = nchunks;
-  for (int d = 1; d <= nchunks; ++d)
-    if (nchunks % d == 0 && (long)panels * d >= 1536) { nsplit = d; break; }
+  const int nsplit = panel_split(panels, nchunks, 1536);
   dim3 grid(8 * ((panels + 7) / 8) * nsplit), block(256);
   const int SHMEM = 2 * KT * BNC * ROWB + (nchunks + nsplit - 1) / nsplit * BNC * 4;
   if (SHMEM > 64 * 1024) return ODIC_EUNSUPPORTED;
@@ -479,27 +468,11 @@ template <int NWM, int NWN, int MI, int NI, int NSTAGE>
 int launch(Params& p, int out_dtype, int batch, hipStream_t stream) {
   constexpr int BM = NWM * MI * 16, BN = NWN * NI * 16;
   constexpr int SHMEM = NSTAGE * (BM + BN) * ROWB;
-  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
-  int pm, pn;                                 // XCD partition: the split with the least fabric traffic (odic_common.h)
-  odic_xcd_partition(p.tiles_m, p.tiles_n, (double)p.M * p.K * 4.0, (double)p.N * p.K * 4.0, 32 * (NWM * NWN <= 4 ? 2 : 1), &pm, &pn);
-  p.pm = pm; p.pn = pn;
-  int max_rect = 0;
-  for (int xm = 0; xm < pm; ++xm)
-    for (int xn = 0; xn < pn; ++xn) {
-      const int r = ((xm + 1) * p.tiles_m / pm - xm * p.tiles_m / pm) * ((xn + 1) * p.tiles_n / pn - xn * p.tiles_n / pn);
-      if (r > max_rect) max_rect = r;
-    }
+  const int max_rect = tile_grid(p.grid, p.M, p.N, BM, BN, (double)p.M * p.K * 4.0, (double)p.N * p.K * 4.0, 32 * (NWM * NWN <= 4 ? 2 : 1));
   dim3 grid(8 * max_rect, 1, batch), block(64 * NWM * NWN);
-  auto k32 = gemm_x3_nt_kernel<NWM, NWN, MI, NI, NSTAGE, float>;
-  auto kh2 = gemm_x3_nt_kernel<NWM, NWN, MI, NI, NSTAGE, h2_t>;
-  if (SHMEM > 64 * 1024) {
-    static bool done = false;       // code-object attribute; idempotent
-    if (!done) {
-      (void)hipFuncSetAttribute((const void*)k32, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      (void)hipFuncSetAttribute((const void*)kh2, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-      done = true;
-    }
-  }
+  constexpr auto k32 = gemm_x3_nt_kernel<NWM, NWN, MI, NI, NSTAGE, float>;
+  constexpr auto kh2 = gemm_x3_nt_kernel<NWM, NWN, MI, NI, NSTAGE, h2_t>;
+  tile_allow_lds<SHMEM, k32, kh2>();
   if (out_dtype == ODIC_F32) hipLaunchKernelGGL(k32, grid, block, SHMEM, stream, p);
   else hipLaunchKernelGGL(kh2, grid, block, SHMEM, stream, p);
   return odic_launch_status();
@@ -526,11 +499,9 @@ int odic_gemm_x3_launch(const odic_gemm_args* a, hipStream_t stream) {
   p.alpha = a->alpha; p.act = a->act; p.bias_axis = a->bias_axis;
   int cfg = a->tile_cfg;
   if (cfg < 0) {
-    auto rounds = [&](int bm, int bn, int slots) {
-      const long t = (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn) * a->batch;
-      return (double)((t + slots - 1) / slots);
-    };
-    const double c0 = rounds(128, 64, 768) * 1.0, c1 = rounds(128, 128, 512) * 1.5, c2 = rounds(256, 128, 256) * 2.6;
+    const double c0 = tile_rounds(a->M, a->N, a->batch, 128, 64, 768) * 1.0;
+    const double c1 = tile_rounds(a->M, a->N, a->batch, 128, 128, 512) * 1.5;
+    const double c2 = tile_rounds(a->M, a->N, a->batch, 256, 128, 256) * 2.6;
     cfg = (c0 <= c1 && c0 <= c2) ? 0 : (c1 <= c2 ? 1 : 2);
   }
   switch (cfg) {
@@ -545,7 +516,6 @@ int odic_gemm_x3_launch(const odic_gemm_args* a, hipStream_t stream) {
     case 6: return launch<6, 2, 3, 6, 2>(p, a->out_dtype, a->batch, stream);      // 288 x 192, 12 waves (120 KiB)
     case 7: return launch<3, 3, 3, 6, 2>(p, a->out_dtype, a->batch, stream);      // 144 x 288,  9 waves (108 KiB)
     case 8: return launch<3, 2, 3, 6, 2>(p, a->out_dtype, a->batch, stream);      // 144 x 192,  6 waves (84 KiB)
-    case 9: return launch<4, 2, 4, 4, 3>(p, a->out_dtype, a->batch, stream);      // 256 x 128, 3 stages (144 KiB) [as 4]
     default: return ODIC_EINVAL;
   }
 }

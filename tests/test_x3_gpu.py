@@ -71,7 +71,7 @@ def test_layernorm_and_patch_merge_write_h2(ops):
 
 
 # ------------------------------------------------------------------------------------------ GEMM
-@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5])
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5, 6, 7, 8])
 def test_gemm_x3_identity_asymmetric(ops, cfg):
     """A = I with an ASYMMETRIC integer W (values whose hi AND lo halves are non-zero: |w| up to 40000 needs more than
     fp16's 11 bits): the output must equal Wᵀ exactly — catches any fragment, plane-order, swizzle or C-layout slip."""
@@ -84,8 +84,12 @@ def test_gemm_x3_identity_asymmetric(ops, cfg):
     assert torch.equal(got2.cpu(), Wt)
 
 
-@pytest.mark.parametrize("cfg", [-1, 0, 1, 2, 3])
-@pytest.mark.parametrize("M,N,K", [(128, 128, 32), (300, 192, 192), (144, 576, 160), (2304, 1536, 1536), (517, 264, 992)])
+_X3_RANDOM_SHAPES = [(128, 128, 32), (300, 192, 192), (144, 576, 160), (2304, 1536, 1536), (517, 264, 992)]
+
+
+# (the 288x192 / 144x288 / 144x192 tiles 6-8: one ragged shape, smaller than a tile along N)
+@pytest.mark.parametrize("M,N,K,cfg", [(M, N, K, cfg) for (M, N, K) in _X3_RANDOM_SHAPES for cfg in (-1, 0, 1, 2, 3)] +
+                         [(300, 192, 192, cfg) for cfg in (6, 7, 8)])
 def test_gemm_x3_random_against_fp64(ops, M, N, K, cfg):
     A, Wt = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.05)
     b, r = rnd(N, seed=3), rnd(M, N, seed=4)
@@ -198,6 +202,13 @@ def test_gemm_x3_rejects_what_it_cannot_do(ops):
     a = torch.zeros(64, 64, dtype=ops.H2_DTYPE, device="cuda")
     with pytest.raises(RuntimeError):                                 # bf16 outputs do not exist in this mode
         ops.gemm(a, a.clone(), out_dtype=torch.bfloat16)
+    for cfg in (9, 10):                                               # no such tile: refused, and nothing is written
+        for odt in (torch.float32, ops.H2_DTYPE):
+            out = torch.full((64, 64), 7, dtype=odt, device="cuda")
+            with pytest.raises(RuntimeError):
+                ops.gemm(a, a.clone(), out=out, tile_cfg=cfg)
+            torch.cuda.synchronize()
+            assert bool((out == 7).all()), f"cfg{cfg}: a refused launch wrote to its output"
 
 
 # ------------------------------------------------------------------------------------------ window attention
