@@ -11,42 +11,66 @@
 // Roofline: per (window, head) 2,654,208 FLOP against 36,864 B (bf16) / 73,728 B (fp32) of
 // compulsory q,k,v,out traffic → AI 72 / 36 FLOP/B, far left of the ridge: HBM-bound.
 //
-//   bf16 kernel  3 waves; wave w owns query tiles 3w..3w+2 (48 queries).  Sᵀ = K·Qᵀ by
-//                v_mfma_f32_16x16x32_bf16 (head dim 32 = exactly one MFMA per 16x16 score tile),
-//                so each lane holds, for ITS query (lane&15), keys 16kt+4(lane>>4)+{0..3} of all 9
-//                key tiles: the row softmax is 36 in-register values + 2 shuffle steps.  Those
-//                registers are already the B operand of Oᵀ = Vᵀ·Pᵀ (K index = key, permuted
-//                consistently on both operands), so P never touches LDS.  K is staged row-major,
-//                V transposed ([d][key], zero-padded to 160 keys) in LDS; Q goes straight from
-//                global memory into MFMA fragments.
-//   fp32 kernel  parity path: one thread per query row, K/V fp32 in LDS (broadcast reads), scores
-//                recomputed in two passes (max, then exp/sum/PV) — plain fp32 FMA chains.
-#include "odic_common.h"
+// All MFMA kernels: 3 waves per (window, head) (the fused one: 9 per window); a wave owns 16-query tiles.
+// Sᵀ = K·Qᵀ by v_mfma_f32_16x16x32 (head dim 32 = exactly one MFMA per 16x16 score tile), so each
+// lane holds, for ITS query (lane&15), keys 16kt+4(lane>>4)+{0..3} of all 9 key tiles: the row
+// softmax is 36 in-register values + 2 shuffle steps.  Those registers are already the B operand
+// of Oᵀ = Vᵀ·Pᵀ (K index = key, permuted consistently on both operands), so P never touches LDS.
+//
+// Five kernels:
+//   window_attention_f32_kernel       parity path: one thread per query row, K/V fp32 in LDS (broadcast reads),
+//                                     scores recomputed in two passes (max, then exp/sum/PV) — plain fp32 FMA chains.
+//   window_attention_bf16_kernel      bf16, bias from the (2ws-1)² table (what a NULL packed bias selects): K row-major,
+//                                     V transposed by the staging stores, Q straight into MFMA fragments.
+//   window_attention_bf16_v3_kernel   bf16 / fp16 with the packed bias: the tuned core ("the v3 core" below).
+//   swin_qkv_attention_kernel         norm1 → qkv → core in one launch for the width-192 stage.
+//   window_attention_h2_kernel        split-fp16 (hi + lo) activations, three MFMAs per contraction.
+// The last three run the same core ("the v3 core"): K row-major and chunk-swizzled, V row-major, zero-padded to 160 keys
+// and read through ds_read_b64_tr_b16.  Shared helpers: window geometry, the slot → token map, the rows[] / rids[] fill,
+// the zeroed padding keys, the bias-initialised accumulators, the score MFMAs, the row max and the output store.  Block
+// map, bias staging, key-quad offsets, bias origin, V-fragment offset, mask, softmax and P·V are still text in each of the
+// three: as helpers each compiles to another instruction stream (profiles/r09_window_attention_core_bench.txt).
+#include "gemm_tile.h"        // gptr_t / lptr_t, wperm
 
 namespace {
 
 constexpr int HD = 32;        // head dim of every Swin-L stage
 constexpr int MAXN = 144;     // ws*ws upper bound
 
-struct WinParams {
-  const void* qkv; const float* table; const float* bias_shifted; void* out;
+struct WinGeom {
   int B, res, C, heads, ws, shift, nwin_side;
   float scale;
 };
+struct WinParams {
+  const void* qkv; const float* table; const float* bias_shifted; void* out;
+  WinGeom g;
+};
 
-// token index (row of the [B*L, *] buffers) of slot n of window (wy, wx) in image b, and the region
-// id of that slot on the shifted grid (0..8; all equal when shift == 0)
-__device__ __forceinline__ void slot_to_token(const WinParams& p, int b, int wy, int wx, int n, long& row,
-                                              int& rid) {
-  const int ny = n / p.ws, nx = n - ny * p.ws;
-  const int sy = wy * p.ws + ny, sx = wx * p.ws + nx;          // coords on the shifted grid
-  int y = sy + p.shift, x = sx + p.shift;                     // roll(-shift): shifted[p] = x[p+shift]
-  if (y >= p.res) y -= p.res;
-  if (x >= p.res) x -= p.res;
-  row = ((long)b * p.res + y) * p.res + x;
-  if (p.shift > 0) {
-    const int ey = sy < p.res - p.ws ? 0 : (sy < p.res - p.shift ? 1 : 2);
-    const int ex = sx < p.res - p.ws ? 0 : (sx < p.res - p.shift ? 1 : 2);
+// window `win` of the launch: image b, window (wy, wx) of its grid
+struct Window { int b, wy, wx; };
+__device__ __forceinline__ Window window_of(const WinGeom& g, int win) {
+  const int wpi = g.nwin_side * g.nwin_side;
+  const int b = win / wpi, wrem = win - b * wpi;
+  const int wy = wrem / g.nwin_side, wx = wrem - wy * g.nwin_side;
+  return {b, wy, wx};
+}
+// the window touches the seam of the shifted grid: some of its key / query pairs lie in different regions
+__device__ __forceinline__ bool on_shift_seam(const WinGeom& g, const Window& w) {
+  return g.shift > 0 && (w.wy == g.nwin_side - 1 || w.wx == g.nwin_side - 1);
+}
+
+// token index (row of the [B*L, *] buffers) of slot n of window w, and the region id of that slot on
+// the shifted grid (0..8; all equal when shift == 0)
+__device__ __forceinline__ void slot_to_token(const WinGeom& g, const Window& w, int n, long& row, int& rid) {
+  const int ny = n / g.ws, nx = n - ny * g.ws;
+  const int sy = w.wy * g.ws + ny, sx = w.wx * g.ws + nx;      // coords on the shifted grid
+  int y = sy + g.shift, x = sx + g.shift;                     // roll(-shift): shifted[p] = x[p+shift]
+  if (y >= g.res) y -= g.res;
+  if (x >= g.res) x -= g.res;
+  row = ((long)w.b * g.res + y) * g.res + x;
+  if (g.shift > 0) {
+    const int ey = sy < g.res - g.ws ? 0 : (sy < g.res - g.shift ? 1 : 2);
+    const int ex = sx < g.res - g.ws ? 0 : (sx < g.res - g.shift ? 1 : 2);
     rid = ey * 3 + ex;
   } else {
     rid = 0;
@@ -63,21 +87,18 @@ __global__ __launch_bounds__(192) void window_attention_f32_kernel(WinParams p) 
   __shared__ int rids[MAXN];
   __shared__ long rows[MAXN];
 
-  const int N = p.ws * p.ws;
+  const int N = p.g.ws * p.g.ws;
   const int head = blockIdx.y;
-  const int win = blockIdx.x;
-  const int wpi = p.nwin_side * p.nwin_side;
-  const int b = win / wpi, wrem = win - b * wpi;
-  const int wy = wrem / p.nwin_side, wx = wrem - wy * p.nwin_side;
+  const Window w = window_of(p.g, blockIdx.x);
   const int tid = threadIdx.x;
   const float* qkv = (const float*)p.qkv;
-  const int ld = 3 * p.C;
-  const int ntab = (2 * p.ws - 1) * (2 * p.ws - 1);
+  const int ld = 3 * p.g.C;
+  const int ntab = (2 * p.g.ws - 1) * (2 * p.g.ws - 1);
 
-  for (int i = tid; i < ntab; i += blockDim.x) tab[i] = p.table[(long)i * p.heads + head];
+  for (int i = tid; i < ntab; i += blockDim.x) tab[i] = p.table[(long)i * p.g.heads + head];
   if (tid < N) {
     long r; int rid;
-    slot_to_token(p, b, wy, wx, tid, r, rid);
+    slot_to_token(p.g, w, tid, r, rid);
     rows[tid] = r; rids[tid] = rid;
   }
   __syncthreads();
@@ -85,8 +106,8 @@ __global__ __launch_bounds__(192) void window_attention_f32_kernel(WinParams p) 
   for (int i = tid; i < N * 8; i += blockDim.x) {
     const int n = i >> 3, c = (i & 7) * 4;
     const float* src = qkv + rows[n] * ld + head * HD + c;
-    *(float4*)&Ks[n][c] = *(const float4*)(src + p.C);
-    *(float4*)&Vs[n][c] = *(const float4*)(src + 2 * p.C);
+    *(float4*)&Ks[n][c] = *(const float4*)(src + p.g.C);
+    *(float4*)&Vs[n][c] = *(const float4*)(src + 2 * p.g.C);
   }
   __syncthreads();
   if (tid >= N) return;
@@ -97,13 +118,13 @@ __global__ __launch_bounds__(192) void window_attention_f32_kernel(WinParams p) 
 #pragma unroll
     for (int c = 0; c < HD; c += 4) {
       const float4 t = *(const float4*)(src + c);
-      q[c] = t.x * p.scale; q[c + 1] = t.y * p.scale; q[c + 2] = t.z * p.scale; q[c + 3] = t.w * p.scale;
+      q[c] = t.x * p.g.scale; q[c + 1] = t.y * p.g.scale; q[c + 2] = t.z * p.g.scale; q[c + 3] = t.w * p.g.scale;
     }
   }
-  const int iy = tid / p.ws, ix = tid - iy * p.ws;
+  const int iy = tid / p.g.ws, ix = tid - iy * p.g.ws;
   const int my_rid = rids[tid];
-  const int tw = 2 * p.ws - 1;
-  const int ibase = (iy + p.ws - 1) * tw + (ix + p.ws - 1);
+  const int tw = 2 * p.g.ws - 1;
+  const int ibase = (iy + p.g.ws - 1) * tw + (ix + p.g.ws - 1);
 
   auto score = [&](int j, int jy, int jx) -> float {
     float s = 0.f;
@@ -117,7 +138,7 @@ __global__ __launch_bounds__(192) void window_attention_f32_kernel(WinParams p) 
   float m = -INFINITY;
   for (int j = 0, jy = 0, jx = 0; j < N; ++j) {
     m = fmaxf(m, score(j, jy, jx));
-    if (++jx == p.ws) { jx = 0; ++jy; }
+    if (++jx == p.g.ws) { jx = 0; ++jy; }
   }
   float l = 0.f, o[HD];
 #pragma unroll
@@ -127,10 +148,10 @@ __global__ __launch_bounds__(192) void window_attention_f32_kernel(WinParams p) 
     l += pj;
 #pragma unroll
     for (int c = 0; c < HD; ++c) o[c] = fmaf(pj, Vs[j][c], o[c]);
-    if (++jx == p.ws) { jx = 0; ++jy; }
+    if (++jx == p.g.ws) { jx = 0; ++jy; }
   }
   const float inv = 1.0f / l;
-  float* dst = (float*)p.out + rows[tid] * p.C + head * HD;
+  float* dst = (float*)p.out + rows[tid] * p.g.C + head * HD;
 #pragma unroll
   for (int c = 0; c < HD; c += 4)
     *(float4*)(dst + c) = make_float4(o[c] * inv, o[c + 1] * inv, o[c + 2] * inv, o[c + 3] * inv);
@@ -149,18 +170,15 @@ __global__ __launch_bounds__(192, 2) void window_attention_bf16_kernel(WinParams
   __shared__ long rows[MAXN];
 
   const int head = blockIdx.y;
-  const int win = blockIdx.x;
-  const int wpi = p.nwin_side * p.nwin_side;
-  const int b = win / wpi, wrem = win - b * wpi;
-  const int wy = wrem / p.nwin_side, wx = wrem - wy * p.nwin_side;
+  const Window w = window_of(p.g, blockIdx.x);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bf16_raw* qkv = (const bf16_raw*)p.qkv;
-  const int ld = 3 * p.C;
+  const int ld = 3 * p.g.C;
 
-  for (int i = tid; i < 23 * 23; i += 192) tab[i] = p.table[(long)i * p.heads + head];
+  for (int i = tid; i < 23 * 23; i += 192) tab[i] = p.table[(long)i * p.g.heads + head];
   if (tid < MAXN) {
     long r; int rid;
-    slot_to_token(p, b, wy, wx, tid, r, rid);
+    slot_to_token(p.g, w, tid, r, rid);
     rows[tid] = r; rids[tid] = rid;
   }
   // zero the padded key columns 144..163 of Vᵀ (they meet P = 0, but 0·NaN garbage would poison O)
@@ -174,8 +192,8 @@ __global__ __launch_bounds__(192, 2) void window_attention_bf16_kernel(WinParams
   for (int i = tid; i < MAXN * 4; i += 192) {
     const int n = i >> 2, c = (i & 3) * 8;
     const bf16_raw* src = qkv + rows[n] * ld + head * HD + c;
-    *(bf16x8_t*)&Ks[n][c] = *(const bf16x8_t*)(src + p.C);
-    const bf16x8_t v = *(const bf16x8_t*)(src + 2 * p.C);
+    *(bf16x8_t*)&Ks[n][c] = *(const bf16x8_t*)(src + p.g.C);
+    const bf16x8_t v = *(const bf16x8_t*)(src + 2 * p.g.C);
 #pragma unroll
     for (int e = 0; e < 8; ++e) Vt[c + e][n] = (bf16_raw)v[e];
   }
@@ -216,7 +234,7 @@ __global__ __launch_bounds__(192, 2) void window_attention_bf16_kernel(WinParams
       for (int j = 0; j < 4; ++j) {
         const int key = kt * 16 + fq * 4 + j;
         const int jy = key / 12, jx = key - jy * 12;
-        float s = sc[qt][kt][j] * p.scale + tab[ibase - jy * tw - jx];
+        float s = sc[qt][kt][j] * p.g.scale + tab[ibase - jy * tw - jx];
         if (rids[key] != my_rid) s += -100.0f;
         sc[qt][kt][j] = s;
         m = fmaxf(m, s);
@@ -276,7 +294,7 @@ __global__ __launch_bounds__(192, 2) void window_attention_bf16_kernel(WinParams
 #pragma unroll
   for (int qt = 0; qt < 3; ++qt) {
     const int qn = (wave * 3 + qt) * 16 + fr;
-    bf16_raw* dst = out + rows[qn] * p.C + head * HD + fq * 4;
+    bf16_raw* dst = out + rows[qn] * p.g.C + head * HD + fq * 4;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       ushort4 pk;
@@ -316,8 +334,6 @@ __global__ __launch_bounds__(192, 2) void window_attention_bf16_kernel(WinParams
 // =================================================================================================
 typedef __attribute__((ext_vector_type(4))) short v4s_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int BS_COPY = 576;          // floats per shifted bias copy (23 rows x 24 + slack; 4 copies = 9 x 1 KiB)
 
@@ -329,7 +345,6 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {      // inpu
 
 // 16-bit element flavour of the fast kernel: bf16 (the default backbone mode) or IEEE fp16 (the low-precision mode's
 // activations, BASELINE.json configs[4]); same MFMA shape, same fragment layouts, same LDS image.
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 template <bool F16> __device__ __forceinline__ f32x4_t mfma16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
   if constexpr (F16)
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
@@ -339,6 +354,78 @@ template <bool F16> __device__ __forceinline__ f32x4_t mfma16(bf16x8_t a, bf16x8
 template <bool F16> __device__ __forceinline__ unsigned short cvt16(float f) {
   if constexpr (F16) { const _Float16 h = (_Float16)f; return __builtin_bit_cast(unsigned short, h); }
   else return f32_to_bf16(f);
+}
+
+// ------------------------------------------------------------------------------------------------- the v3 core
+// Pieces of the core shared by window_attention_bf16_v3_kernel<F16>, swin_qkv_attention_kernel and
+// window_attention_h2_kernel.  Lane (fr, fq) = (lane & 15, lane >> 4) holds, for query fr of its tile, keys
+// 16kt + 4fq + {0..3} of the nine key tiles in sc[9].  Only helpers that leave every kernel's instruction stream as it was
+// are here.  The block map, bias staging, key-quad offsets, bias origin, V-fragment offset, mask, softmax and P·V were each
+// shown to change it and stay as text in each kernel until they are timed on the device
+// (profiles/r09_window_attention_core_bench.txt).
+
+// token rows and packed region ids of the window's 144 slots (one thread each)
+__device__ __forceinline__ void stage_rows(const WinGeom& g, const Window& w, int tid, int* rows, unsigned char* rids) {
+  if (tid < MAXN) {
+    long r; int rid;
+    slot_to_token(g, w, tid, r, rid);
+    rows[tid] = (int)r; rids[tid] = (unsigned char)rid;
+  }
+}
+
+// rows 144..159 of a [160][32] V image: the padding keys of the fifth P·V step meet P = 0, but must not be NaN garbage
+__device__ __forceinline__ void zero_padding_keys(void* V, int tid) {
+  if (tid < 128) ((unsigned long long*)((char*)V + MAXN * HD * 2))[tid] = 0ull;      // 16 x 64 B
+}
+
+// The K / V / bias fragment addresses are made opaque once per tile: otherwise hipcc hoists the loop-invariant LDS
+// reads out of the tile loop and parks dozens of registers on them.
+__device__ __forceinline__ void opaque_offsets(int& k, int& v, int& b) { asm volatile("" : "+v"(k), "+v"(v), "+v"(b)); }
+
+// the relative-position bias (pre-divided by scale) as the accumulator init of the score MFMAs
+__device__ __forceinline__ void load_bias36(const char* bbase, const int (&koffs)[9], f32x4_t (&sc)[9]) {
+#pragma unroll
+  for (int kt = 0; kt < 9; ++kt) sc[kt] = *(const f32x4_t*)(bbase + koffs[kt]);
+}
+
+// Sᵀ = K·Qᵀ on top of the bias: kbase = this lane's fragment of key row fr in the chunk-swizzled [144][32] K image
+template <bool F16> __device__ __forceinline__ void scores16(const char* kbase, bf16x8_t q, f32x4_t (&sc)[9]) {
+#pragma unroll
+  for (int kt = 0; kt < 9; ++kt) {
+    const bf16x8_t kf = *(const bf16x8_t*)(kbase + kt * 16 * HD * 2);
+    sc[kt] = mfma16<F16>(kf, q, sc[kt]);
+  }
+}
+
+// row max of the query's 144 raw scores: 18 v_max3_f32 over the lane's 36, two shuffles across the fq groups
+__device__ __forceinline__ float row_max36(const f32x4_t (&sc)[9]) {
+  float m = max3f(sc[0][0], sc[0][1], sc[0][2]);
+  m = max3f(m, sc[0][3], sc[1][0]);
+  m = max3f(m, sc[1][1], sc[1][2]);
+#pragma unroll
+  for (int kt = 2; kt < 9; kt += 2) {                                  // (sc[kt-1][3], sc[kt][0..3], sc[kt+1][0..2]) pairs
+    m = max3f(m, sc[kt - 1][3], sc[kt][0]);
+    m = max3f(m, sc[kt][1], sc[kt][2]);
+    if (kt + 1 < 9) {
+      m = max3f(m, sc[kt][3], sc[kt + 1][0]);
+      m = max3f(m, sc[kt + 1][1], sc[kt + 1][2]);
+    } else {
+      m = fmaxf(m, sc[kt][3]);
+    }
+  }
+  m = fmaxf(m, __shfl_xor(m, 16, 64));
+  return fmaxf(m, __shfl_xor(m, 32, 64));
+}
+
+// lane holds O[query = fr][d = 16nt + 4fq + {0..3}] → two 8-byte stores; dst = the query's row + head·32 + 4fq
+template <bool F16> __device__ __forceinline__ void store_o16(bf16_raw* dst, const f32x4_t (&oacc)[2], float inv_l) {
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) {
+    ushort4 o4;
+    o4.x = cvt16<F16>(oacc[nt][0] * inv_l); o4.y = cvt16<F16>(oacc[nt][1] * inv_l);
+    o4.z = cvt16<F16>(oacc[nt][2] * inv_l); o4.w = cvt16<F16>(oacc[nt][3] * inv_l);
+    *(ushort4*)(dst + nt * 16) = o4;
+  }
 }
 
 template <bool F16>
@@ -354,16 +441,14 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
   // line — are requested back-to-back from the same L2 and every HBM line is fetched once.
   ODIC_ENCODE_PRIO();
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int head = idx % p.heads;
-  const int win = (idx / p.heads) * 8 + xcd;
-  const int wpi = p.nwin_side * p.nwin_side;
-  if (win >= p.B * wpi) return;
-  const int b = win / wpi, wrem = win - b * wpi;
-  const int wy = wrem / p.nwin_side, wx = wrem - wy * p.nwin_side;
+  const int head = idx % p.g.heads;
+  const int win = (idx / p.g.heads) * 8 + xcd;
+  if (win >= p.g.B * (p.g.nwin_side * p.g.nwin_side)) return;
+  const Window w = window_of(p.g, win);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bf16_raw* qkv = (const bf16_raw*)p.qkv;
-  const long ld = 3 * p.C;
-  const bool masked = p.shift > 0 && (wy == p.nwin_side - 1 || wx == p.nwin_side - 1);
+  const long ld = 3 * p.g.C;
+  const bool masked = on_shift_seam(p.g, w);
 
   // bias copies of this head: 9 x 1 KiB of LDS-DMA, 3 per wave (independent of the token rows)
   {
@@ -374,12 +459,8 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
       __builtin_amdgcn_global_load_lds((gptr_t)(bsrc + blk * 256), (lptr_t)((char*)&Bs[0] + blk * 1024), 16, 0, 0);
     }
   }
-  if (tid < MAXN) {
-    long r; int rid;
-    slot_to_token(p, b, wy, wx, tid, r, rid);
-    rows[tid] = (int)r; rids[tid] = (unsigned char)rid;
-  }
-  if (tid < 128) ((unsigned long long*)&Vs[MAXN][0])[tid] = 0ull;       // 16 x 64 B of padding keys
+  stage_rows(p.g, w, tid, rows, rids);
+  zero_padding_keys(Vs, tid);
   __syncthreads();
 
   // ---- LDS-DMA gather: instruction i covers window slots 16i .. 16i+15 (16 rows x 64 B = 1 KiB)
@@ -390,13 +471,13 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
     for (int i = 0; i < 3; ++i) {
       const int blk = wave * 3 + i;                                       // 0..8
       const bf16_raw* src = qkv + (long)rows[blk * 16 + r_in] * ld + head * HD;
-      __builtin_amdgcn_global_load_lds((gptr_t)(src + p.C + chk * 8), (lptr_t)((char*)&Ks[0][0] + blk * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)(src + 2 * p.C + ch * 8), (lptr_t)((char*)&Vs[0][0] + blk * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(src + p.g.C + chk * 8), (lptr_t)((char*)&Ks[0][0] + blk * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(src + 2 * p.g.C + ch * 8), (lptr_t)((char*)&Vs[0][0] + blk * 1024), 16, 0, 0);
     }
   }
   const int fr = lane & 15, fq = lane >> 4;
-  const float scale2 = p.scale * 1.4426950408889634f;
-  const float mask_acc = 100.0f / p.scale;                              // -100 in accumulator units
+  const float scale2 = p.g.scale * 1.4426950408889634f;
+  const float mask_acc = 100.0f / p.g.scale;                              // -100 in accumulator units
   bf16_raw* out = (bf16_raw*)p.out;
   // transposed-read addresses of V: lane (fr = 4q+p) of 16-lane group fq supplies row r0+q, cols 4p..4p+3
   const int voff = ((4 * fq + (fr >> 2)) * HD + 4 * (fr & 3)) * 2;
@@ -423,21 +504,14 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
   for (int qt = 0; qt < 3; ++qt) {
     const int qn = (wave * 3 + qt) * 16 + fr;
     const int orow = rows[qn];
-    // (the K / V / bias fragment addresses are made opaque once per tile: otherwise hipcc hoists the
-    //  loop-invariant LDS reads out of the tile loop and parks dozens of registers on them)
     int koff = (fr * HD + ((fq ^ ((fr >> 2) & 3)) * 8)) * 2, vo = voff, bb = bias_base(qn);
-    asm volatile("" : "+v"(koff), "+v"(vo), "+v"(bb));
+    opaque_offsets(koff, vo, bb);
     const char* kbase = (const char*)&Ks[0][0] + koff;
     const char* vbase = (const char*)&Vs[0][0] + vo;
     const char* bbase = (const char*)&Bs[0] + bb;
     f32x4_t sc[9];
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) sc[kt] = *(const f32x4_t*)(bbase + koffs[kt]);
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) {
-      const bf16x8_t kf = *(const bf16x8_t*)(kbase + kt * 16 * HD * 2);
-      sc[kt] = mfma16<F16>(kf, q, sc[kt]);
-    }
+    load_bias36(bbase, koffs, sc);
+    scores16<F16>(kbase, q, sc);
     if (masked) {
       const unsigned my = rids[qn];
 #pragma unroll
@@ -448,22 +522,7 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
           if (((kr >> (8 * j)) & 0xff) != my) sc[kt][j] -= mask_acc;
       }
     }
-    float m = max3f(sc[0][0], sc[0][1], sc[0][2]);
-    m = max3f(m, sc[0][3], sc[1][0]);
-    m = max3f(m, sc[1][1], sc[1][2]);
-#pragma unroll
-    for (int kt = 2; kt < 9; kt += 2) {                                  // (sc[kt-1][3], sc[kt][0..3], sc[kt+1][0..2]) pairs
-      m = max3f(m, sc[kt - 1][3], sc[kt][0]);
-      m = max3f(m, sc[kt][1], sc[kt][2]);
-      if (kt + 1 < 9) {
-        m = max3f(m, sc[kt][3], sc[kt + 1][0]);
-        m = max3f(m, sc[kt + 1][1], sc[kt + 1][2]);
-      } else {
-        m = fmaxf(m, sc[kt][3]);
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float m = row_max36(sc);
     const f32x2_t s2 = {scale2, scale2};
     const f32x2_t c2 = {-m * scale2, -m * scale2};
     f32x2_t lsum = {0.f, 0.f};
@@ -503,14 +562,7 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
         oacc[nt] = mfma16<F16>(vf, pf, oacc[nt]);
       }
     }
-    bf16_raw* dst = out + (long)orow * p.C + head * HD + fq * 4;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      ushort4 o4;
-      o4.x = cvt16<F16>(oacc[nt][0] * inv_l); o4.y = cvt16<F16>(oacc[nt][1] * inv_l);
-      o4.z = cvt16<F16>(oacc[nt][2] * inv_l); o4.w = cvt16<F16>(oacc[nt][3] * inv_l);
-      *(ushort4*)(dst + nt * 16) = o4;
-    }
+    store_o16<F16>(out + (long)orow * p.g.C + head * HD + fq * 4, oacc, inv_l);
   }
 }
 
@@ -537,13 +589,9 @@ __global__ __launch_bounds__(192, 4) void window_attention_bf16_v3_kernel(WinPar
 // =================================================================================================
 struct FusedParams {
   const float* x; long ldx; const bf16_raw* W; const float* bqkv; const float* bias_shifted; bf16_raw* out;
-  int B, res, C, heads, ws, shift, nwin_side;
-  float scale, eps;
+  WinGeom g;
+  float eps;
 };
-
-__device__ __forceinline__ int wperm32(int r) {            // gemm_bf16.hip's W row permutation inside a 32-row group
-  return 8 * ((r & 15) >> 2) + 4 * ((r >> 4) & 1) + (r & 3);
-}
 
 template <int KT>
 __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams p) {
@@ -566,19 +614,10 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fq = lane >> 4;
-  const int win = blockIdx.x;
-  const int wpi = p.nwin_side * p.nwin_side;
-  const int b = win / wpi, wrem = win - b * wpi;
-  const int wy = wrem / p.nwin_side, wx = wrem - wy * p.nwin_side;
-  const bool masked = p.shift > 0 && (wy == p.nwin_side - 1 || wx == p.nwin_side - 1);
-  if (tid < MAXN) {
-    WinParams wp;
-    wp.ws = p.ws; wp.shift = p.shift; wp.res = p.res;
-    long r; int rid;
-    slot_to_token(wp, b, wy, wx, tid, r, rid);
-    rows[tid] = (int)r; rids[tid] = (unsigned char)rid;
-  }
-  if (tid < 128) ((unsigned long long*)(Vp + MAXN * HD * 2))[tid] = 0ull;             // 16 x 64 B of padding keys
+  const Window w = window_of(p.g, blockIdx.x);
+  const bool masked = on_shift_seam(p.g, w);
+  stage_rows(p.g, w, tid, rows, rids);
+  zero_padding_keys(Vp, tid);
   for (int t = tid; t < 3 * C; t += 64 * NWV) sbq[t] = p.bqkv[t];
 
   // ---- per-head DMA: W rows (part, 32-row group permuted) as KT swizzled sub-tiles, then the head's bias copies
@@ -587,7 +626,7 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
   for (int i = 0; i < WI; ++i) {
     const int j = i * NWV + wave, kt = j / 12, rg = j - kt * 12;
     const int srow = lane >> 3, r = rg * 8 + srow;
-    w_off[i] = ((r >> 5) * C + wperm32(r & 31)) * C + kt * 64 + ((lane & 7) ^ srow) * 8;
+    w_off[i] = ((r >> 5) * C + wperm(r & 31)) * C + kt * 64 + ((lane & 7) ^ srow) * 8;
   }
   auto issue = [&](int h, int buf) {
     const bf16_raw* wb = p.W + (long)h * HD * C;
@@ -635,8 +674,8 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
     }
   }
 
-  const float scale2 = p.scale * 1.4426950408889634f;
-  const float mask_acc = 100.0f / p.scale;
+  const float scale2 = p.g.scale * 1.4426950408889634f;
+  const float mask_acc = 100.0f / p.g.scale;
   const int voff = ((4 * fq + (fr >> 2)) * HD + 4 * (fr & 3)) * 2;
   int koffs[9];
 #pragma unroll
@@ -654,11 +693,11 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
   const unsigned my_rid = rids[slot];
 
   __builtin_amdgcn_s_waitcnt(0x0070);                       // vmcnt(0) lgkmcnt(0): x rows and head 0's DMA
-  for (int h = 0; h < p.heads; ++h) {
+  for (int h = 0; h < p.g.heads; ++h) {
     const int buf = h & 1;
     if (h) __builtin_amdgcn_s_waitcnt(0x0F72);              // vmcnt(2): this head's DMA landed, last head's stores may fly
     __builtin_amdgcn_s_barrier();                           // ... for every wave; everyone is done with K / V / the other buffers
-    if (h + 1 < p.heads) issue(h + 1, buf ^ 1);
+    if (h + 1 < p.g.heads) issue(h + 1, buf ^ 1);
 
     // ---- q, k, v of this wave's tokens for head h: [96 channels] x [16 tokens], K = C
     f32x4_t acc[6];
@@ -693,18 +732,13 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
 
     // ---- the v3 core on this wave's query tile
     int koff = (fr * HD + ((fq ^ ((fr >> 2) & 3)) * 8)) * 2, vo = voff, bb = bias_org;
-    asm volatile("" : "+v"(koff), "+v"(vo), "+v"(bb));
+    opaque_offsets(koff, vo, bb);
     const char* kbase = Kp + koff;
     const char* vbase = Vp + vo;
     const char* bbase = Bp + buf * 4 * BS_COPY * 4 + bb;
     f32x4_t sc[9];
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) sc[kt] = *(const f32x4_t*)(bbase + koffs[kt]);
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) {
-      const bf16x8_t kf = *(const bf16x8_t*)(kbase + kt * 16 * HD * 2);
-      sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, q, sc[kt], 0, 0, 0);
-    }
+    load_bias36(bbase, koffs, sc);
+    scores16<false>(kbase, q, sc);
     if (masked) {
 #pragma unroll
       for (int kt = 0; kt < 9; ++kt) {
@@ -714,22 +748,7 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
           if (((kr >> (8 * j)) & 0xff) != my_rid) sc[kt][j] -= mask_acc;
       }
     }
-    float m = max3f(sc[0][0], sc[0][1], sc[0][2]);
-    m = max3f(m, sc[0][3], sc[1][0]);
-    m = max3f(m, sc[1][1], sc[1][2]);
-#pragma unroll
-    for (int kt = 2; kt < 9; kt += 2) {
-      m = max3f(m, sc[kt - 1][3], sc[kt][0]);
-      m = max3f(m, sc[kt][1], sc[kt][2]);
-      if (kt + 1 < 9) {
-        m = max3f(m, sc[kt][3], sc[kt + 1][0]);
-        m = max3f(m, sc[kt + 1][1], sc[kt + 1][2]);
-      } else {
-        m = fmaxf(m, sc[kt][3]);
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float m = row_max36(sc);
     const f32x2_t s2 = {scale2, scale2};
     const f32x2_t c2 = {-m * scale2, -m * scale2};
     f32x2_t lsum = {0.f, 0.f};
@@ -765,14 +784,7 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
         oacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[nt], 0, 0, 0);
       }
     }
-    bf16_raw* dst = p.out + (long)orow * C + h * HD + fq * 4;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      ushort4 o4;
-      o4.x = f32_to_bf16(oacc[nt][0] * inv_l); o4.y = f32_to_bf16(oacc[nt][1] * inv_l);
-      o4.z = f32_to_bf16(oacc[nt][2] * inv_l); o4.w = f32_to_bf16(oacc[nt][3] * inv_l);
-      *(ushort4*)(dst + nt * 16) = o4;
-    }
+    store_o16<false>(p.out + (long)orow * C + h * HD + fq * 4, oacc, inv_l);
   }
 }
 
@@ -799,17 +811,15 @@ __global__ __launch_bounds__(192, 3) void window_attention_h2_kernel(WinParams p
 
   ODIC_ENCODE_PRIO();
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int head = idx % p.heads;
-  const int win = (idx / p.heads) * 8 + xcd;
-  const int wpi = p.nwin_side * p.nwin_side;
-  if (win >= p.B * wpi) return;
-  const int b = win / wpi, wrem = win - b * wpi;
-  const int wy = wrem / p.nwin_side, wx = wrem - wy * p.nwin_side;
+  const int head = idx % p.g.heads;
+  const int win = (idx / p.g.heads) * 8 + xcd;
+  if (win >= p.g.B * (p.g.nwin_side * p.g.nwin_side)) return;
+  const Window w = window_of(p.g, win);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const char* qkv = (const char*)p.qkv;
-  const long ldb = 12L * p.C;                                           // bytes per token row of [*, 3C] h2
-  const long kbyte = 4L * p.C, vbyte = 8L * p.C;                        // byte offsets of the k / v column blocks
-  const bool masked = p.shift > 0 && (wy == p.nwin_side - 1 || wx == p.nwin_side - 1);
+  const long ldb = 12L * p.g.C;                                           // bytes per token row of [*, 3C] h2
+  const long kbyte = 4L * p.g.C, vbyte = 8L * p.g.C;                        // byte offsets of the k / v column blocks
+  const bool masked = on_shift_seam(p.g, w);
 
   {
     const float* bsrc = p.bias_shifted + (long)head * 4 * BS_COPY + lane * 4;
@@ -819,12 +829,9 @@ __global__ __launch_bounds__(192, 3) void window_attention_h2_kernel(WinParams p
       __builtin_amdgcn_global_load_lds((gptr_t)(bsrc + blk * 256), (lptr_t)((char*)&Bs[0] + blk * 1024), 16, 0, 0);
     }
   }
-  if (tid < MAXN) {
-    long r; int rid;
-    slot_to_token(p, b, wy, wx, tid, r, rid);
-    rows[tid] = (int)r; rids[tid] = (unsigned char)rid;
-  }
-  if (tid < 128) { ((unsigned long long*)&Vh[MAXN][0])[tid] = 0ull; ((unsigned long long*)&Vl[MAXN][0])[tid] = 0ull; }
+  stage_rows(p.g, w, tid, rows, rids);
+  zero_padding_keys(Vh, tid);
+  zero_padding_keys(Vl, tid);
   __syncthreads();
 
   // ---- LDS-DMA gather.  K: instruction j covers window slots 8j .. 8j+7 (8 rows x 128 B); V: slots 16i .. 16i+15
@@ -849,8 +856,8 @@ __global__ __launch_bounds__(192, 3) void window_attention_h2_kernel(WinParams p
     }
   }
   const int fr = lane & 15, fq = lane >> 4;
-  const float scale2 = p.scale * 1.4426950408889634f;
-  const float mask_acc = 100.0f / p.scale;
+  const float scale2 = p.g.scale * 1.4426950408889634f;
+  const float mask_acc = 100.0f / p.g.scale;
   const int voff = ((4 * fq + (fr >> 2)) * HD + 4 * (fr & 3)) * 2;
   int koffs[9];
 #pragma unroll
@@ -876,12 +883,11 @@ __global__ __launch_bounds__(192, 3) void window_attention_h2_kernel(WinParams p
     const int qn = (wave * 3 + qt) * 16 + fr;
     const int orow = rows[qn];
     int koh = fr * 128 + ((fq ^ (fr & 7)) << 4), vo = voff, bb = bias_base(qn);
-    asm volatile("" : "+v"(koh), "+v"(vo), "+v"(bb));
+    opaque_offsets(koh, vo, bb);
     const char* kbase = Kx + koh;                                        // hi fragment; lo = slot ^ 4 → byte ^ 64
     const char* bbase = (const char*)&Bs[0] + bb;
     f32x4_t sc[9];
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) sc[kt] = *(const f32x4_t*)(bbase + koffs[kt]);
+    load_bias36(bbase, koffs, sc);
 #pragma unroll
     for (int kt = 0; kt < 9; ++kt) {
       const f16x8_t kh = *(const f16x8_t*)(kbase + kt * 16 * 128);
@@ -900,22 +906,7 @@ __global__ __launch_bounds__(192, 3) void window_attention_h2_kernel(WinParams p
           if (((kr >> (8 * j)) & 0xff) != my) sc[kt][j] -= mask_acc;
       }
     }
-    float m = max3f(sc[0][0], sc[0][1], sc[0][2]);
-    m = max3f(m, sc[0][3], sc[1][0]);
-    m = max3f(m, sc[1][1], sc[1][2]);
-#pragma unroll
-    for (int kt = 2; kt < 9; kt += 2) {
-      m = max3f(m, sc[kt - 1][3], sc[kt][0]);
-      m = max3f(m, sc[kt][1], sc[kt][2]);
-      if (kt + 1 < 9) {
-        m = max3f(m, sc[kt][3], sc[kt + 1][0]);
-        m = max3f(m, sc[kt + 1][1], sc[kt + 1][2]);
-      } else {
-        m = fmaxf(m, sc[kt][3]);
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float m = row_max36(sc);
     const float c2 = 12.0f - m * scale2;                                 // P carries a factor 2^12
     float lsum = 0.f;
     f16x4_t ph[9], pl[9];
@@ -962,7 +953,7 @@ __global__ __launch_bounds__(192, 3) void window_attention_h2_kernel(WinParams p
         oacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pfh, oacc[nt], 0, 0, 0);
       }
     }
-    h2_t* drow = (h2_t*)p.out + (long)orow * p.C + head * HD;
+    h2_t* drow = (h2_t*)p.out + (long)orow * p.g.C + head * HD;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
       h2_store4(drow, nt * 16 + fq * 4, oacc[nt][0] * inv_l, oacc[nt][1] * inv_l, oacc[nt][2] * inv_l, oacc[nt][3] * inv_l);
@@ -978,35 +969,29 @@ extern "C" int odic_window_attention(const void* qkv, const float* bias_table, c
   if (B <= 0 || ws <= 0 || ws * ws > MAXN || res % ws || heads * HD != C || shift < 0 || shift >= ws)
     return ODIC_EINVAL;
   if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return ODIC_EINVAL;
-  WinParams p;
-  p.qkv = qkv; p.table = bias_table; p.bias_shifted = bias_shifted_prescaled; p.out = out; p.B = B; p.res = res; p.C = C; p.heads = heads;
-  p.ws = ws; p.shift = shift; p.nwin_side = res / ws; p.scale = scale;
-  dim3 grid(B * p.nwin_side * p.nwin_side, heads), block(192);
+  const WinParams p = {qkv, bias_table, bias_shifted_prescaled, out, {B, res, C, heads, ws, shift, res / ws, scale}};
+  const int nwin = B * p.g.nwin_side * p.g.nwin_side;
+  const dim3 grid(nwin, heads), block(192);
+  // the packed-bias kernels: 32-bit token rows, 16-byte DMA of the bias; one round of eight blocks per 8 windows and head
+  const bool packed = bias_shifted_prescaled && (long)B * res * res < 2147483647L && !(((uintptr_t)bias_shifted_prescaled) & 15);
+  const dim3 xgrid(((nwin + 7) / 8) * 8 * heads);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == ODIC_F32) {
     hipLaunchKernelGGL(window_attention_f32_kernel, grid, block, 0, s, p);
   } else if (dtype == ODIC_BF16) {
     if (ws != 12) return ODIC_EUNSUPPORTED;      // MFMA tiling is specialised for N = 144
-    if (bias_shifted_prescaled && (long)B * res * res < 2147483647L && !(((uintptr_t)bias_shifted_prescaled) & 15)) {
-      // (a persistent, double-buffered variant — one head x several windows per block — measured
-      //  slower at every stage: with ~0.5 us of work per window a prefetch distance of one window does
-      //  not cover the gather latency, and six independent 3-wave blocks per CU keep more bytes in flight)
-      const int nwin = B * p.nwin_side * p.nwin_side;
-      hipLaunchKernelGGL(window_attention_bf16_v3_kernel<false>, dim3(((nwin + 7) / 8) * 8 * heads), block, 0, s, p);
-    }
-    else
-      hipLaunchKernelGGL(window_attention_bf16_kernel, grid, block, 0, s, p);
+    // (a persistent, double-buffered variant — one head x several windows per block — measured
+    //  slower at every stage: with ~0.5 us of work per window a prefetch distance of one window does
+    //  not cover the gather latency, and six independent 3-wave blocks per CU keep more bytes in flight)
+    if (packed) hipLaunchKernelGGL(window_attention_bf16_v3_kernel<false>, xgrid, block, 0, s, p);
+    else hipLaunchKernelGGL(window_attention_bf16_kernel, grid, block, 0, s, p);
   } else if (dtype == ODIC_F16) {
-    if (ws != 12 || !bias_shifted_prescaled || (long)B * res * res >= 2147483647L || (((uintptr_t)bias_shifted_prescaled) & 15))
-      return ODIC_EUNSUPPORTED;                  // fp16 activations: packed-bias MFMA kernel only
-    const int nwin = B * p.nwin_side * p.nwin_side;
-    hipLaunchKernelGGL(window_attention_bf16_v3_kernel<true>, dim3(((nwin + 7) / 8) * 8 * heads), block, 0, s, p);
+    if (ws != 12 || !packed) return ODIC_EUNSUPPORTED;      // fp16 activations: packed-bias MFMA kernel only
+    hipLaunchKernelGGL(window_attention_bf16_v3_kernel<true>, xgrid, block, 0, s, p);
   } else if (dtype == ODIC_H2) {
-    if (ws != 12 || !bias_shifted_prescaled || (long)B * res * res >= 2147483647L || (((uintptr_t)bias_shifted_prescaled) & 15) ||
-        ((uintptr_t)qkv & 31) || ((uintptr_t)out & 31))
+    if (ws != 12 || !packed || ((uintptr_t)qkv & 31) || ((uintptr_t)out & 31))
       return ODIC_EUNSUPPORTED;                  // split-fp16 activations: packed-bias MFMA kernel only
-    const int nwin = B * p.nwin_side * p.nwin_side;
-    hipLaunchKernelGGL(window_attention_h2_kernel, dim3(((nwin + 7) / 8) * 8 * heads), block, 0, s, p);
+    hipLaunchKernelGGL(window_attention_h2_kernel, xgrid, block, 0, s, p);
   } else {
     return ODIC_EINVAL;
   }
@@ -1023,14 +1008,12 @@ extern "C" int odic_swin_qkv_attention(const float* x, int64_t ldx, const void* 
   if (((uintptr_t)x & 15) || (ldx & 3) || ((uintptr_t)w_qkv_folded & 15) || ((uintptr_t)out & 7) ||
       ((uintptr_t)bias_shifted_prescaled & 15) || ((uintptr_t)b_qkv_folded & 3) || (long)B * res * res >= 2147483647L)
     return ODIC_EINVAL;
-  FusedParams p;
-  p.x = x; p.ldx = ldx; p.W = (const bf16_raw*)w_qkv_folded; p.bqkv = b_qkv_folded; p.bias_shifted = bias_shifted_prescaled;
-  p.out = (bf16_raw*)out; p.B = B; p.res = res; p.C = C; p.heads = heads; p.ws = ws; p.shift = shift;
-  p.nwin_side = res / ws; p.scale = scale; p.eps = ln_eps;
+  const FusedParams p = {x, ldx, (const bf16_raw*)w_qkv_folded, b_qkv_folded, bias_shifted_prescaled, (bf16_raw*)out,
+                         {B, res, C, heads, ws, shift, res / ws, scale}, ln_eps};
   constexpr int SHMEM = 2 * 3 * 96 * 128 + MAXN * HD * 2 + (MAXN + 16) * HD * 2 + 2 * 4 * BS_COPY * 4 + 3 * 192 * 4 + MAXN * 4 + MAXN;
   auto k = swin_qkv_attention_kernel<3>;
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM); done = true; }
-  hipLaunchKernelGGL(k, dim3(B * p.nwin_side * p.nwin_side), dim3(576), SHMEM, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k, dim3(B * p.g.nwin_side * p.g.nwin_side), dim3(576), SHMEM, (hipStream_t)stream, p);
   return odic_launch_status();
 }

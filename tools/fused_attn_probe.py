@@ -1,15 +1,25 @@
 #!/usr/bin/env python3
 """norm1 -> qkv -> attention core of a width-192 Swin block at batch B: LayerNorm-while-reading product + window
-attention (two launches) against odic_swin_qkv_attention (one), isolated, interleaved.   python tools/fused_attn_probe.py [16]"""
+attention (two launches) against odic_swin_qkv_attention (one), isolated, interleaved.
+python tools/fused_attn_probe.py [16] [--lib other/libodic_hip.so]"""
+import argparse
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+from on_device_image_captioning_amd import _hip
+
+ap = argparse.ArgumentParser()
+ap.add_argument("B", nargs="?", type=int, default=16)
+ap.add_argument("--lib", help="time this build of the library instead of the tree's")
+a = ap.parse_args()
+if a.lib:
+    _hip.LIB_PATH = os.path.abspath(a.lib)
 from on_device_image_captioning_amd import ops
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+B = a.B
 res, C, heads, ws = 96, 192, 6, 12
 torch.manual_seed(0)
 x = torch.randn(B * res * res, C, device="cuda")
