@@ -52,7 +52,7 @@ extern "C" {
 
 /* ABI version of this header; bumped on any signature change.
  *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step). */
-#define ODIC_ABI_VERSION 19
+#define ODIC_ABI_VERSION 20
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -486,6 +486,29 @@ int odic_cross_attn_step(const float* q, int64_t ldq, const float* kv, int64_t l
                          int32_t voff, const int32_t* enc_len, const int32_t* row_valid, float* out,
                          int64_t ldo, int32_t N, int32_t n_img, int32_t S, int32_t d, int32_t heads,
                          void* stream);
+
+/* The cross-attention probabilities themselves — where the model looked for each word — instead of the attention output:
+ * what odic_cross_attn_step computes in LDS, uses for P·V and discards.  q, kv, koff, enc_len, row_valid and the row →
+ * image map (row n belongs to image n / (N / n_img)) are those of odic_cross_attn_step; with the [N·T] rows of the
+ * whole-sequence pass, one launch covers every position of every caption.
+ *   p_h[n, s] = softmax_s(q_h[n]·k_h[s]/sqrt(d/heads)), a score set to exactly -1e4 where s >= enc_len[img] or
+ *   row_valid[n] == 0 (layers.py:247-250): a masked key of a valid row gets exactly 0, a row_valid = 0 row and every row
+ *   of an image with enc_len = 0 get exactly 1/S everywhere.  fp32 throughout, base e.
+ *   per_head = 0: out fp32 [N, S] (ldo)        = scale·Σ_h p_h[n, s]  (heads summed in the block, in head order)
+ *   per_head = 1: out fp32 [N, heads·S] (ldo)  = scale·p_h[n, s] at column h·S + s
+ *   accumulate = 1 adds that to what out holds, 0 overwrites: the mean over L layers and the heads is L calls with
+ *   scale = 1/(L·heads) into one [N, S] buffer.  scale·x and out + x are separate roundings (no FMA), so an accumulated
+ *   call adds exactly what an overwriting call would have stored.
+ *   One thread writes each element, there are no atomics and the result does not depend on the grid.
+ *   d/heads in {16,32,64}, S >= 1, N >= 1 a multiple of n_img, ldq, ldkv and koff multiples of 4, q / kv 16-byte aligned,
+ *   ldo >= S (per_head: heads·S), and an S whose score and sum rows fit the block's 64 KB of LDS (S <= 8159 at d/heads = 64;
+ *   the shipped decoder has S = 144): ODIC_EINVAL otherwise, before any launch.
+ *   Every out row is written, row_valid = 0 rows included; out columns [S, ldo) (per_head: [heads·S, ldo)) are left
+ *   untouched; q / kv columns beyond their widths are not read (test_cross_attn_probs_containment). */
+int odic_cross_attn_probs(const float* q, int64_t ldq, const float* kv, int64_t ldkv, int32_t koff,
+                          const int32_t* enc_len, const int32_t* row_valid, float* out, int64_t ldo,
+                          int32_t N, int32_t n_img, int32_t S, int32_t d, int32_t heads,
+                          int32_t per_head, int32_t accumulate, float scale, void* stream);
 
 /* log_softmax over V + top-k (captioning_model.py:126-127,162-170).  logits fp32 [N, V] (ldl);
  * writes logp_out fp32 [N, V] (ldp) if non-NULL, top_val fp32 [N,k] / top_idx int32 [N,k] sorted

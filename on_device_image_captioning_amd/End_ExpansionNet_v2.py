@@ -8,6 +8,7 @@ arithmetic runs in hand-written HIP kernels on an MI355X.
 """
 from __future__ import annotations
 
+import math
 from argparse import Namespace
 
 import torch
@@ -90,6 +91,11 @@ class End_ExpansionNet_v2(CaptioningModel):
     def _enc_lens(self, n, S, enc_input_num_pads):
         # end-to-end: the encoder never has padding (End_ExpansionNet_v2.py:107)
         return torch.full((n,), S, dtype=torch.int32, device=self._device())
+
+    def _attention_grid(self, S):
+        # the last Swin stage's square token grid, row-major (SwinEngine.forward): 12 x 12 at 384 x 384
+        r = math.isqrt(S)
+        return (r, r) if r * r == S else None
 
     # ------------------------------------------------------------------ reference API
     def forward_enc(self, enc_input, enc_input_num_pads):

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import engine as _engine
 from . import ops
+from . import grounding as _grounding
 from . import scoring as _scoring
 
 _DONE_POLL = 4      # host looks at the device `done` flag every this many steps
@@ -212,6 +213,63 @@ class CaptioningModel(nn.Module):
         for k in ("logprobs", "lengths", "sum", "mean", "argmax", "sum_logp_vocab"):
             setattr(res, k, getattr(res, k).to(out_dv))
         return res
+
+    # ------------------------------------------------------------------ where the model looked for each word
+    def _attention_grid(self, S: int) -> Optional[Tuple[int, int]]:
+        """The (rows, columns) the S encoder positions lie on in the image, or None when the model cannot know."""
+        return None
+
+    def word_attention(self, enc_x, captions=None, enc_x_num_pads=None, *, captions_per_image: int = 1, pad_idx=None,
+                       dec_x_num_pads=None, layers="mean", heads="mean", sos_idx=None, eos_idx=None, beam_size: int = 3,
+                       max_seq_len: int = 20) -> "_grounding.WordAttention":
+        """Per-word cross-attention maps: for every word of a caption, how the decoder's cross attention spread over the
+        S encoder positions when it predicted that word — in one whole-sequence decoder pass (the softmax of
+        layers.py:244-250 kept instead of discarded; odic_cross_attn_probs).  `captions`, `captions_per_image`, `pad_idx`
+        and `dec_x_num_pads` are those of score_captions, with the same errors.  With `captions=None` the best caption
+        of every input is generated first (`beam_search(..., how_many_outputs=1)` with `sos_idx`, `eos_idx`, `beam_size`,
+        `max_seq_len`) and then grounded: the encoder then runs twice, once for the search and once for the maps.
+        layers: "mean" (the mean over the decoder layers), "all", an int or a list of ints (negative = from the end);
+        heads: "mean" or "all".  Returns grounding.WordAttention: maps[n, …, t, :] belongs to the step that predicted
+        token t+1 of caption n and sums to 1 over the S positions; rows behind a caption's end are 0.  The decoder is
+        fp32 in every precision mode, so the method works in all of them."""
+        a_layers, a_reduce = _grounding.parse_layers(layers, self.geometry.N_dec)
+        a_heads = _grounding.parse_heads(heads)
+        n_img = enc_x.shape[0]
+        if enc_x_num_pads is None:
+            enc_x_num_pads = [0] * n_img
+        if captions is None:
+            if sos_idx is None or eos_idx is None:
+                raise ValueError("word_attention without captions generates them and needs sos_idx and eos_idx")
+            if captions_per_image != 1:
+                raise ValueError("word_attention without captions grounds one generated caption per input")
+            best, _ = self.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx, beam_size=beam_size,
+                                       how_many_outputs=1, max_seq_len=max_seq_len)
+            captions, pad_idx, dec_x_num_pads = [per[0] for per in best], None, None
+        toks, lens = _scoring.pack_captions(captions, dec_x_num_pads, pad_idx=pad_idx, max_seq_len=self._max_seq_len())
+        N, Tm = toks.shape
+        if captions_per_image < 1 or N != n_img * captions_per_image:
+            raise ValueError(f"{N} captions for {n_img} inputs x {captions_per_image} captions per image")
+        V = self._vocab_size()
+        if int(toks.min()) < 0 or int(toks.max()) >= V:
+            raise ValueError(f"token ids must lie in [0, {V})")
+        dec_len = torch.tensor([n - 1 for n in lens], dtype=torch.int32)
+        eng = self._captioner_engine()
+        dv = eng.device
+        mem = self.forward_enc(enc_x, enc_x_num_pads)
+        S = mem.shape[1]
+        enc_len = self._enc_lens(n_img, S, enc_x_num_pads)
+        st = eng.decode_sequence(toks[:, :-1].contiguous().to(dv), dec_len.to(dv), eng.project_kv(mem), enc_len, n_img,
+                                 attn={"layers": a_layers, "per_head": a_heads, "reduce_layers": a_reduce})
+        maps = st["attn"]                                                       # [N, (L',) (H,) Tm-1, S]
+        real = torch.arange(Tm - 1, device=dv)[None, :] < dec_len.to(dv)[:, None]
+        real = real.view([N] + [1] * (maps.dim() - 3) + [Tm - 1, 1])
+        maps = torch.where(real, maps, torch.zeros_like(maps))
+        out_dv = enc_x.device if isinstance(enc_x, torch.Tensor) else dv
+        return _grounding.WordAttention(
+            tokens=[toks[i, :n].tolist() for i, n in enumerate(lens)], maps=maps.to(out_dv),
+            lengths=dec_len.to(out_dv, torch.int64),
+            enc_lengths=enc_len.to(out_dv, torch.int64).repeat_interleave(captions_per_image),
+            grid=self._attention_grid(S))
 
     def caption_loss(self, enc_x, dec_y, enc_x_num_pads, dec_y_num_pads, ignore_index, smoothing: float = 0.0,
                      divide_by_non_zeros: bool = False) -> torch.Tensor:
@@ -435,3 +493,13 @@ class Captioner:
 
     def caption_loss(self, *a, **k):
         return self.model.caption_loss(*a, **k)
+
+    def word_attention(self, enc_x, captions=None, *a, **k):
+        """CaptioningModel.word_attention; the generated-caption form (`captions=None`) searches with this object's
+        `beam_search_args` (sos_idx, eos_idx, beam_size, beam_max_seq_len) unless the call names its own."""
+        b = self.beam_search_args
+        for arg, key in (("sos_idx", "sos_idx"), ("eos_idx", "eos_idx"), ("beam_size", "beam_size"),
+                         ("max_seq_len", "beam_max_seq_len")):
+            if key in b:
+                k.setdefault(arg, b[key])
+        return self.model.word_attention(enc_x, captions, *a, **k)

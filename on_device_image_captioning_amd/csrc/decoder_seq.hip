@@ -10,6 +10,8 @@
 //                          in global memory
 //   token_stats_kernel     the scoring tail: per logits row the target's log-prob, Σ_v log-prob, arg-max and its
 //                          log-prob — one number per quantity instead of an [R, V] log-prob tensor
+//   cross_attn_probs_kernel  the softmax probabilities of the cross attention themselves (where the model looked for
+//                          each word): what cross_attn_step_kernel computes in LDS, uses for P·V and discards
 #include "odic_common.h"
 
 namespace {
@@ -315,6 +317,100 @@ __global__ __launch_bounds__(TS_NT) void token_stats_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Cross-attention probabilities: one 256-thread block per (image, chunk of R query rows of that image), looping over the
+// heads.  Per head
+//   q       the nr x dk slice of the chunk's query rows → LDS
+//   scores  thread = key: its dk-float K row is read ONCE (float4, as cross_attn_step_kernel reads it) into registers
+//           and used for all nr rows (the q row comes from LDS as a broadcast); masked exactly as the step kernel
+//   softmax wave w normalises rows w, w + 4, ...; lane l owns keys l, l + 64, ... of a row in every head, so the
+//           head sum (acc[r][s], fixed head order) and the final store are by ONE thread per element: no atomics,
+//           and nothing depends on the grid or on R
+// LDS words: R·dk + 2·R·S + R;  R = 16 rows at S = 144, dk = 64 (the shipped decoder): 22.6 KB, so registers, not LDS,
+// bound the blocks per CU; the host halves R until the block fits 64 KB (S = 576: R = 8, 39 KB — two blocks a CU).
+// Products and sums that reach `out` are __fmul_rn / __fadd_rn: never contracted into an FMA, so accumulate = 1 adds
+// exactly what accumulate = 0 would have stored.
+// ---------------------------------------------------------------------------------------------
+constexpr int AP_NT = 256;
+constexpr int AP_MAX_R = 16;
+constexpr size_t AP_MAX_LDS = 64 * 1024;
+
+template <int DK>
+__global__ __launch_bounds__(AP_NT) void cross_attn_probs_kernel(const float* __restrict__ q, long ldq,
+                                                                 const float* __restrict__ kv, long ldkv, int koff,
+                                                                 const int* __restrict__ enc_len,
+                                                                 const int* __restrict__ row_valid, float* out,
+                                                                 long ldo, int rows, int S, int heads, int R,
+                                                                 int per_head, int accumulate, float scale) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* qs = sm;                                  // [R][DK]
+  float* sc = qs + R * DK;                         // [R][S]  scores → exp of the current head
+  float* acc = sc + R * S;                         // [R][S]  Σ_h p_h   (per_head = 0)
+  int* vld = (int*)(acc + R * S);                  // [R]
+  const int img = blockIdx.x, r0 = blockIdx.y * R;
+  const int nr = min(R, rows - r0);                // rows handled here
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long n0 = (long)img * rows + r0;           // first query row of this block
+  const int len = enc_len[img];
+  const float inv = rsqrtf((float)DK);
+  const float* kvb = kv + (long)img * S * ldkv + koff;
+  if (tid < nr) vld[tid] = row_valid[n0 + tid];
+
+  for (int h = 0; h < heads; ++h) {
+    for (int e = tid; e < nr * DK; e += AP_NT) {
+      const int r = e / DK, c = e - r * DK;
+      qs[e] = q[(n0 + r) * ldq + h * DK + c];
+    }
+    __syncthreads();       // q (and vld) visible; every wave is through the previous head's softmax: sc may be rewritten
+    for (int s = tid; s < S; s += AP_NT) {
+      float4 k4[DK / 4];
+      const float* kr = kvb + (long)s * ldkv + h * DK;
+#pragma unroll
+      for (int i = 0; i < DK / 4; ++i) k4[i] = *(const float4*)(kr + 4 * i);
+      for (int r = 0; r < nr; ++r) {
+        const float4* qr = (const float4*)(qs + r * DK);
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < DK / 4; ++i) {
+          const float4 qq = qr[i];
+          a = fmaf(qq.x, k4[i].x, a); a = fmaf(qq.y, k4[i].y, a);
+          a = fmaf(qq.z, k4[i].z, a); a = fmaf(qq.w, k4[i].w, a);
+        }
+        float v = a * inv;
+        if (!vld[r] || s >= len) v = -1e4f;        // masked_fill(mask == 0, -1e4), layers.py:286
+        sc[r * S + s] = v;
+      }
+    }
+    __syncthreads();
+    for (int r = wave; r < nr; r += AP_NT / 64) {
+      float* row = sc + r * S;
+      float m = -INFINITY;
+      for (int s = lane; s < S; s += 64) m = fmaxf(m, row[s]);
+      m = wave_max(m);
+      float l = 0.f;
+      for (int s = lane; s < S; s += 64) { const float e = expf(row[s] - m); row[s] = e; l += e; }
+      l = wave_sum(l);
+      for (int s = lane; s < S; s += 64) {
+        const float p = row[s] / l;
+        if (per_head) {
+          float* o = out + (n0 + r) * ldo + (long)h * S + s;
+          const float v = __fmul_rn(scale, p);
+          *o = accumulate ? __fadd_rn(*o, v) : v;
+        } else {
+          acc[r * S + s] = h == 0 ? p : __fadd_rn(acc[r * S + s], p);
+        }
+      }
+    }
+  }
+  if (!per_head)                                   // the thread that summed an element stores it
+    for (int r = wave; r < nr; r += AP_NT / 64)
+      for (int s = lane; s < S; s += 64) {
+        float* o = out + (n0 + r) * ldo + s;
+        const float v = __fmul_rn(scale, acc[r * S + s]);
+        *o = accumulate ? __fadd_rn(*o, v) : v;
+      }
+}
+
 }  // namespace
 
 extern "C" int odic_dec_embed_seq(const int64_t* tokens, const float* embed, const float* pos_table,
@@ -360,5 +456,34 @@ extern "C" int odic_token_stats(const float* logits, int64_t ldl, const int64_t*
   if (R <= 0 || V <= 0 || ldl < V) return ODIC_EINVAL;
   hipLaunchKernelGGL(token_stats_kernel, dim3(R), dim3(TS_NT), 0, (hipStream_t)stream, logits, (long)ldl,
                      (const long long*)target, logp_target, sum_logp, argmax, max_logp, status, V);
+  return odic_launch_status();
+}
+
+extern "C" int odic_cross_attn_probs(const float* q, int64_t ldq, const float* kv, int64_t ldkv, int32_t koff,
+                                     const int32_t* enc_len, const int32_t* row_valid, float* out, int64_t ldo,
+                                     int32_t N, int32_t n_img, int32_t S, int32_t d, int32_t heads, int32_t per_head,
+                                     int32_t accumulate, float scale, void* stream) {
+  if (!q || !kv || !enc_len || !row_valid || !out) return ODIC_ENULL;
+  if (N < 1 || n_img < 1 || N % n_img || S < 1 || d < 1 || heads < 1 || d % heads) return ODIC_EINVAL;
+  const int dk = d / heads;
+  if (dk != 16 && dk != 32 && dk != 64) return ODIC_EINVAL;
+  if ((ldq & 3) || (ldkv & 3) || (koff & 3) || koff < 0 || ((uintptr_t)q & 15) || ((uintptr_t)kv & 15)) return ODIC_EINVAL;
+  if (ldq < d || ldkv < (int64_t)koff + d) return ODIC_EINVAL;
+  if (ldo < (per_head ? (int64_t)heads * S : (int64_t)S)) return ODIC_EINVAL;
+  const int rows = N / n_img;
+  int R = rows < AP_MAX_R ? rows : AP_MAX_R;
+  auto lds = [&](int r) { return ((size_t)r * dk + 2 * (size_t)r * S + r) * sizeof(float); };
+  while (R > 1 && lds(R) > AP_MAX_LDS) R = (R + 1) / 2;
+  if (lds(R) > AP_MAX_LDS) return ODIC_EINVAL;      // one row of scores + sums does not fit: S > 8159 at dk = 64
+  const int chunks = (rows + R - 1) / R;
+  if (chunks > 65535) return ODIC_EINVAL;
+#define ODIC_APROBS(DK)                                                                                              \
+  hipLaunchKernelGGL(cross_attn_probs_kernel<DK>, dim3(n_img, chunks), dim3(AP_NT), lds(R), (hipStream_t)stream, q,  \
+                     (long)ldq, kv, (long)ldkv, koff, enc_len, row_valid, out, (long)ldo, rows, S, heads, R,         \
+                     per_head ? 1 : 0, accumulate ? 1 : 0, scale)
+  if (dk == 16) ODIC_APROBS(16);
+  else if (dk == 32) ODIC_APROBS(32);
+  else ODIC_APROBS(64);
+#undef ODIC_APROBS
   return odic_launch_status();
 }

@@ -535,7 +535,7 @@ class CaptionerEngine:
 
     def decode_sequence(self, tokens: torch.Tensor, dec_len: torch.Tensor, kv: torch.Tensor, enc_len: torch.Tensor,
                         n_img: int, targets: Optional[torch.Tensor] = None, want_logits: bool = False,
-                        row_chunk: Optional[int] = None):
+                        row_chunk: Optional[int] = None, attn: Optional[dict] = None):
         """Teacher-forced decoder over whole sequences (End_ExpansionNet_v2.py:103-138 in one pass).
         tokens int64 [N, T], rows image-major (N / n_img captions per image, sharing that image's K/V); dec_len int32 [N]
         real tokens per row; kv = project_kv(mem) [n_img, S, 2·N_dec·d]; enc_len int32 [n_img].
@@ -544,7 +544,13 @@ class CaptionerEngine:
         `targets` int64 [N, T]), 'sum_logp' (Σ_v log-prob), 'argmax' (int32), 'max_logp', and 'status' (int32 scalar,
         non-zero when a target was outside the vocabulary).  The vocabulary product and the statistics run over
         `row_chunk` rows at a time; the chunking changes no result bit (every product here is the 64 x 64 tile kernel,
-        whose rows are independent of M).  The number of launches does not depend on T."""
+        whose rows are independent of M).  The number of launches does not depend on T.
+        attn = {"layers": [i, …], "per_head": bool, "reduce_layers": bool}: the statistics gain 'attn', the cross-attention
+        probabilities of the listed decoder layers (odic_cross_attn_probs on the q, kv, enc_len and row mask the layer's
+        attention runs on; one more launch per listed layer): fp32 [N, T, S] with reduce_layers (the mean over the listed
+        layers), [N, L', T, S] without, the mean over the heads either way; with per_head a heads axis in front of T.
+        Padded rows hold the uniform 1/S of a masked row.  Without `attn` nothing is allocated or launched for it, and
+        every other result keeps its bits either way."""
         g, dv = self.g, self.device
         d, L, V, E = g.d_model, g.N_dec, g.vocab_size, g.num_exp_dec
         N, T = tokens.shape
@@ -563,6 +569,18 @@ class CaptionerEngine:
         ycat, row_valid = f(M, ld), torch.empty(M, dtype=torch.int32, device=dv)
         ops.dec_embed_seq(tokens, self.embed, self.pos_table, ycat, ld, N, T, d, math.sqrt(d), dec_len, row_valid)
         xn, lin, q, att, h = f(M, d), f(M, 5 * d), f(M, d), f(M, d), f(M, g.ff)
+        amap = None
+        if attn is not None:
+            if want_logits:
+                raise RuntimeError("decode_sequence: attn comes with the statistics, not with want_logits")
+            a_layers = [int(i) for i in attn["layers"]]
+            if not a_layers or len(set(a_layers)) != len(a_layers) or min(a_layers) < 0 or max(a_layers) >= L:
+                raise ValueError(f"attn layers must be distinct indices in [0, {L})")
+            a_heads, a_reduce = bool(attn.get("per_head", False)), bool(attn.get("reduce_layers", False))
+            H = g.num_heads
+            a_w = H * S if a_heads else S
+            amap = f(1 if a_reduce else len(a_layers), M, a_w)
+            a_scale = (1.0 if a_heads else 1.0 / H) / (len(a_layers) if a_reduce else 1)
         for i, w in enumerate(self.dec):
             xin = ycat if i == 0 else ycat[:, (i - 1) * d:]
             xo = ycat[:, i * d:]
@@ -574,6 +592,11 @@ class CaptionerEngine:
             # the step kernel's row → image map is row / (rows / n_img): the sequence-major rows of an image are contiguous
             ops.cross_attn_step(q, d, kv, kv.shape[2], 2 * i * d, (2 * i + 1) * d, enc_len, row_valid, att, d, M,
                                 n_img, S, d, g.num_heads)
+            if amap is not None and i in a_layers:
+                j = a_layers.index(i)
+                ops.cross_attn_probs(q, d, kv, kv.shape[2], 2 * i * d, enc_len, row_valid, amap[0 if a_reduce else j], a_w,
+                                     M, n_img, S, d, g.num_heads, per_head=a_heads, accumulate=a_reduce and i != min(a_layers),
+                                     scale=a_scale)
             ops.gemm(att, w["wo"], w["bo"], residual=xo, out=xo, M=M, N=d, K=d, lda=d, ldw=d, ldr=ld, ldc=ld,
                      tile_cfg=TC)
             ops.layernorm(xo, w["n3w"], w["n3b"], M=M, C_=d, ldx=ld, out=xn)
@@ -613,4 +636,8 @@ class CaptionerEngine:
                "status": status}
         if logp is not None:
             res["logp"] = logp.view(N, T)
+        if amap is not None:
+            a = amap.view(amap.shape[0], N, T, H, S).permute(1, 0, 3, 2, 4) if a_heads else \
+                amap.view(amap.shape[0], N, T, S).transpose(0, 1)                  # [N, L', (H,) T, S]
+            res["attn"] = (a[:, 0] if a_reduce else a).contiguous()
         return res

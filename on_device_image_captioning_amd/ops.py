@@ -578,6 +578,18 @@ def cross_attn_step(q, ldq, kv, ldkv, koff, voff, enc_len, row_valid, out, ldo, 
                    "odic_cross_attn_step")
 
 
+def cross_attn_probs(q, ldq, kv, ldkv, koff, enc_len, row_valid, out, ldo, N, n_img, S, d, heads, per_head=False,
+                     accumulate=False, scale=1.0) -> None:
+    """The cross-attention probabilities of N query rows (odic_cross_attn_step's q, kv, enc_len, row_valid):
+    out [N, S] = scale·Σ_h p_h, or with per_head out [N, heads·S] = scale·p_h at column h·S + s; accumulate adds to out."""
+    _need_cuda(q, kv, enc_len, row_valid, out)
+    with _timed("cross_attn_probs", 2.0 * N * S * d, (N * d + n_img * S * d + N * S * (heads if per_head else 1)) * 4.0):
+        _hip.check(_hip.load().odic_cross_attn_probs(_p(q), ldq, _p(kv), ldkv, koff, _p(enc_len), _p(row_valid), _p(out),
+                                                     ldo, N, n_img, S, d, heads, int(bool(per_head)),
+                                                     int(bool(accumulate)), scale, _stream()),
+                   "odic_cross_attn_probs")
+
+
 def logsoftmax_topk(logits, ldl, logp_out, ldp, top_val, top_idx, N, V, k) -> None:
     _need_cuda(logits, logp_out, top_val, top_idx)
     with _timed("logsoftmax_topk", 4.0 * N * V, N * V * 4.0 * (2 if logp_out is not None else 1) + N * k * 8.0):
