@@ -4,7 +4,9 @@
 // The host parser (on_device_image_captioning_amd/jpeg.py) walks the markers up to SOS and packs one
 // odic_jpeg_header per image: quantisation tables in natural order, Huffman tables in a lookup form, the
 // restart interval and the workspace offsets.  Everything after SOS is decoded here, the whole batch in one
-// pass of launches on the caller's stream:
+// pass of launches on the caller's stream.  Progressive files (second half of the file) take their own segment
+// and decode kernels and then the same IDCT and colour kernels; both paths share one workspace layout (layout(),
+// bind()), the bit reader and the Huffman lookup (huff(), fill_lim()).  The baseline launches:
 //
 //   segment     one workgroup per image: classify every byte of the scan (data, stuffed 0x00, RSTn, EOI, any
 //               other marker → error), compact the data bytes with a prefix sum, record the start bit of each
@@ -76,22 +78,61 @@ struct Layout {
 
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-Layout layout(const odic_jpeg_batch& b) {
+// The one workspace layout.  The baseline path passes sync_intervals = intervals; the progressive path, which has no
+// synchronisation stage, passes 0 for flag_words, sync_intervals and units: a region of size 0 takes no room (every
+// offset is a multiple of 256), so its five live regions lie exactly where they would with those regions left out.
+Layout layout(size_t n_images, size_t flag_words, size_t sync_intervals, size_t scan_bytes, size_t intervals,
+              size_t units, size_t blocks, size_t plane_bytes) {
   Layout L;
   size_t o = 0;
-  L.state = o; o = align256(o + sizeof(int) * kStateWords * (size_t)b.n_images);
-  L.flags = o; o = align256(o + sizeof(int) * (2 + (size_t)b.max_sync_passes));
-  L.last_change = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
-  L.scan = o; o = align256(o + (size_t)b.total_scan_bytes);
-  L.int_bits = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
-  L.unit_start = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
-  L.est0 = o; o = align256(o + sizeof(int4) * (size_t)b.total_units);
-  L.est1 = o; o = align256(o + sizeof(int4) * (size_t)b.total_units);
-  L.unit_first = o; o = align256(o + sizeof(int) * (size_t)b.total_units);
-  L.coef = o; o = align256(o + 128 * (size_t)b.total_blocks);
-  L.planes = o; o = align256(o + (size_t)b.total_plane_bytes);
+  L.state = o; o = align256(o + sizeof(int) * kStateWords * n_images);
+  L.flags = o; o = align256(o + sizeof(int) * flag_words);
+  L.last_change = o; o = align256(o + sizeof(int) * sync_intervals);
+  L.scan = o; o = align256(o + scan_bytes);
+  L.int_bits = o; o = align256(o + sizeof(int) * intervals);
+  L.unit_start = o; o = align256(o + sizeof(int) * sync_intervals);
+  L.est0 = o; o = align256(o + sizeof(int4) * units);
+  L.est1 = o; o = align256(o + sizeof(int4) * units);
+  L.unit_first = o; o = align256(o + sizeof(int) * units);
+  L.coef = o; o = align256(o + 128 * blocks);
+  L.planes = o; o = align256(o + plane_bytes);
   L.total = o;
   return L;
+}
+
+Layout layout(const odic_jpeg_batch& b) {
+  return layout(b.n_images, 2 + (size_t)b.max_sync_passes, b.total_intervals, b.total_scan_bytes, b.total_intervals,
+                b.total_units, b.total_blocks, b.total_plane_bytes);
+}
+
+Layout layout(const odic_jpeg_prog_batch& b) {
+  return layout(b.n_images, 0, 0, b.total_scan_bytes, b.total_intervals, 0, b.total_blocks, b.total_plane_bytes);
+}
+
+// A region of size 0 gets the address of the region behind it; no kernel of the path that passed 0 reads it.
+Ws bind(void* workspace, const Layout& L) {
+  unsigned char* base = (unsigned char*)workspace;
+  Ws ws;
+  ws.state = (int*)(base + L.state);
+  ws.flags = (int*)(base + L.flags);
+  ws.last_change = (int*)(base + L.last_change);
+  ws.scan = base + L.scan;
+  ws.int_bits = (int*)(base + L.int_bits);
+  ws.unit_start = (int*)(base + L.unit_start);
+  ws.est[0] = (int4*)(base + L.est0);
+  ws.est[1] = (int4*)(base + L.est1);
+  ws.unit_first = (int*)(base + L.unit_first);
+  ws.coef = (short*)(base + L.coef);
+  ws.planes = base + L.planes;
+  return ws;
+}
+
+// The limits both batch descriptors share: grid dimensions that fit 16 bits, and something in every live region.
+template <typename Batch>
+bool batch_dims_ok(const Batch& b) {
+  return b.n_images > 0 && b.n_images <= 65535 && b.max_width > 0 && b.max_width <= 65535 && b.max_height > 0 &&
+         b.max_height <= 65535 && b.max_blocks > 0 && b.total_scan_bytes > 0 && b.total_intervals > 0 &&
+         b.total_blocks > 0 && b.total_plane_bytes > 0;
 }
 
 __device__ __forceinline__ int blocks_per_mcu(int sampling) { return sampling == 0 ? 3 : (sampling == 1 ? 4 : 6); }
@@ -241,6 +282,17 @@ struct Tabs {
   unsigned char natural[64];
 };
 
+// canonical codes: the codes of length l, left-justified, end where those of l + 1 begin → lim[] of table `tab` (Tabs:
+// one of six; PTab: tab = 0)
+__device__ __forceinline__ void fill_lim(const int* maxcode, int* lim, int tab) {
+  int last = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int mc = maxcode[tab * 18 + l];
+    if (mc >= 0) last = (mc + 1) << (16 - l);
+    if (l >= 9) lim[tab * 8 + l - 9] = last;
+  }
+}
+
 __device__ void load_tabs(const odic_jpeg_header& h, Tabs& T) {
   const int t = threadIdx.x;
   for (int i = t; i < 6 * 512; i += blockDim.x) T.lut[i] = (&h.lut[0][0])[i];
@@ -250,14 +302,7 @@ __device__ void load_tabs(const odic_jpeg_header& h, Tabs& T) {
   }
   for (int i = t; i < 6 * 256; i += blockDim.x) T.huffval[i] = (&h.huffval[0][0])[i];
   for (int i = t; i < 64; i += blockDim.x) T.natural[i] = kNatural[i];
-  if (t < 6) {                     // canonical codes: the codes of length l, left-justified, end where those of l+1 begin
-    int last = 0;
-    for (int l = 1; l <= 16; ++l) {
-      const int mc = (&h.maxcode[0][0])[t * 18 + l];
-      if (mc >= 0) last = (mc + 1) << (16 - l);
-      if (l >= 9) T.lim[t * 8 + l - 9] = last;
-    }
-  }
+  if (t < 6) fill_lim(&h.maxcode[0][0], T.lim, t);
   __syncthreads();
 }
 
@@ -297,7 +342,8 @@ __device__ __forceinline__ unsigned bits_peek(Bits& b, int pos) {      // the 32
   return (unsigned)(x >> (32 - (pos & 31)));
 }
 
-__device__ __forceinline__ int huff(const Tabs& T, int tab, unsigned win, int& len) {
+template <typename Tab>          // Tabs: six tables, `tab` picks one; PTab (the progressive path): one table, tab = 0
+__device__ __forceinline__ int huff(const Tab& T, int tab, unsigned win, int& len) {
   const unsigned e = T.lut[tab * 512 + (win >> (32 - kLutBits))];
   if (e) {
     len = e >> 8;
@@ -817,29 +863,7 @@ __device__ void load_ptab(const odic_jpeg_table& g, PTab& T) {          // one w
   for (int i = t; i < 512; i += 64) T.lut[i] = g.lut[i];
   for (int i = t; i < 256; i += 64) T.huffval[i] = g.huffval[i];
   if (t < 18) T.valoff[t] = g.valoff[t];
-  if (t == 0) {
-    int last = 0;
-    for (int l = 1; l <= 16; ++l) {
-      const int mc = g.maxcode[l];
-      if (mc >= 0) last = (mc + 1) << (16 - l);
-      if (l >= 9) T.lim[l - 9] = last;
-    }
-  }
-}
-
-__device__ __forceinline__ int huff1(const PTab& T, unsigned win, int& len) {      // as huff(), one table
-  const unsigned e = T.lut[win >> (32 - kLutBits)];
-  if (e) {
-    len = e >> 8;
-    return e & 255;
-  }
-  const int p16 = (int)(win >> 16);
-  int l = kLutBits + 1;
-#pragma unroll
-  for (int i = 1; i <= 7; ++i) l += p16 >= T.lim[i];
-  if (l > 16) return -1;
-  len = l;
-  return T.huffval[((p16 >> (16 - l)) + T.valoff[l]) & 255];
+  if (t == 0) fill_lim(g.maxcode, T.lim, 0);
 }
 
 struct ScanCtx {
@@ -881,7 +905,7 @@ __device__ bool prog_dc_first(ScanCtx& x, const PTab* T) {
         if (x.pos > x.end) return false;
         const unsigned win = bits_peek(br, x.pos);
         int len;
-        const int cat = huff1(T[q], win, len);
+        const int cat = huff(T[q], 0, win, len);
         if (cat < 0 || cat > 15) return false;
         const int diff = cat ? extend((win << len) >> (32 - cat), cat) : 0;
         x.pos += len + cat;
@@ -952,7 +976,7 @@ __device__ bool prog_ac_first(ScanCtx& x, const PTab& T) {
       if (x.pos > x.end) return false;
       const unsigned win = bits_peek(br, x.pos);
       int len;
-      const int rs = huff1(T, win, len);
+      const int rs = huff(T, 0, win, len);
       if (rs < 0) return false;
       const int r = rs >> 4, s = rs & 15;
       if (s) {
@@ -1007,7 +1031,7 @@ __device__ bool prog_ac_refine(ScanCtx& x, const PTab& T) {
         if (x.pos > x.end) return false;
         const unsigned win = bits_peek(br, x.pos);
         int len;
-        const int rs = huff1(T, win, len);
+        const int rs = huff(T, 0, win, len);
         if (rs < 0) return false;
         const int r = rs >> 4, s = rs & 15;
         x.pos += len;
@@ -1115,28 +1139,9 @@ __global__ __launch_bounds__(64) void jpeg_prog_decode_kernel(const odic_jpeg_pr
   }
 }
 
-struct PLayout {
-  size_t state, scan, int_bits, coef, planes, total;
-};
-
-PLayout prog_layout(const odic_jpeg_prog_batch& b) {
-  PLayout L;
-  size_t o = 0;
-  L.state = o; o = align256(o + sizeof(int) * kStateWords * (size_t)b.n_images);
-  L.scan = o; o = align256(o + (size_t)b.total_scan_bytes);
-  L.int_bits = o; o = align256(o + sizeof(int) * (size_t)b.total_intervals);
-  L.coef = o; o = align256(o + 128 * (size_t)b.total_blocks);
-  L.planes = o; o = align256(o + (size_t)b.total_plane_bytes);
-  L.total = o;
-  return L;
-}
-
 bool prog_batch_ok(const odic_jpeg_prog_batch* b) {
-  if (b->n_images <= 0 || b->n_images > 65535 || b->n_scans < b->n_images ||
-      (long)b->n_scans > (long)b->n_images * ODIC_JPEG_MAX_SCANS || b->n_tables <= 0 || b->n_levels <= 0 ||
-      b->n_levels > ODIC_JPEG_MAX_SCANS || b->max_width <= 0 || b->max_width > 65535 || b->max_height <= 0 ||
-      b->max_height > 65535 || b->max_blocks <= 0 || b->total_scan_bytes <= 0 || b->total_intervals <= 0 ||
-      b->total_intervals > 0x7fffffffL || b->total_blocks <= 0 || b->total_plane_bytes <= 0)
+  if (!batch_dims_ok(*b) || b->n_scans < b->n_images || (long)b->n_scans > (long)b->n_images * ODIC_JPEG_MAX_SCANS ||
+      b->n_tables <= 0 || b->n_levels <= 0 || b->n_levels > ODIC_JPEG_MAX_SCANS || b->total_intervals > 0x7fffffffL)
     return false;
   if (b->level_first[0] != 0 || b->level_first[b->n_levels] != b->n_scans) return false;
   for (int l = 0; l < b->n_levels; ++l) {
@@ -1157,32 +1162,18 @@ extern "C" size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* b) {
 
 extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
   if (!b || !b->headers || !b->data || !b->out || !b->status || !workspace) return ODIC_ENULL;
-  if (b->n_images <= 0 || b->n_images > 65535 || b->subseq_bits < 32 || b->subseq_bits > kMaxSubseqBits ||
-      b->max_sync_passes < 0 || b->max_sync_passes > 64 || b->max_units <= 0 || b->max_intervals <= 0 ||
-      b->max_width <= 0 || b->max_width > 65535 || b->max_height <= 0 || b->max_height > 65535 ||
-      b->max_blocks <= 0 || b->max_scan_bytes <= 0 || b->max_scan_bytes > kMaxScanBytes || b->total_scan_bytes <= 0 ||
-      b->total_intervals <= 0 || b->total_units <= 0 || b->total_blocks <= 0 || b->total_plane_bytes <= 0)
+  if (!batch_dims_ok(*b) || b->subseq_bits < 32 || b->subseq_bits > kMaxSubseqBits || b->max_sync_passes < 0 ||
+      b->max_sync_passes > 64 || b->max_units <= 0 || b->max_intervals <= 0 || b->max_scan_bytes <= 0 ||
+      b->max_scan_bytes > kMaxScanBytes || b->total_units <= 0)
     return ODIC_EINVAL;
   const size_t need = odic_jpeg_workspace_bytes(b);
   if (need == 0 || ws_bytes < need) return ODIC_EINVAL;
   const Layout L = layout(*b);
-  unsigned char* base = (unsigned char*)workspace;
-  Ws ws;
-  ws.state = (int*)(base + L.state);
-  ws.flags = (int*)(base + L.flags);
-  ws.last_change = (int*)(base + L.last_change);
-  ws.scan = base + L.scan;
-  ws.int_bits = (int*)(base + L.int_bits);
-  ws.unit_start = (int*)(base + L.unit_start);
-  ws.est[0] = (int4*)(base + L.est0);
-  ws.est[1] = (int4*)(base + L.est1);
-  ws.unit_first = (int*)(base + L.unit_first);
-  ws.coef = (short*)(base + L.coef);
-  ws.planes = base + L.planes;
+  const Ws ws = bind(workspace, L);
   hipStream_t s = (hipStream_t)stream;
   const auto* hdrs = (const odic_jpeg_header*)b->headers;
   const int n = b->n_images, S = b->subseq_bits;
-  hipError_t e = hipMemsetAsync(base, 0, L.scan, s);                      // state, flags, last_change
+  hipError_t e = hipMemsetAsync(workspace, 0, L.scan, s);                 // state, flags, last_change
   if (e == hipSuccess) e = hipMemsetAsync(ws.coef, 0, L.planes - L.coef, s);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(jpeg_segment_kernel, dim3(n), dim3(256), 0, s, hdrs, b->data, ws, S);
@@ -1202,12 +1193,12 @@ extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_
 
 extern "C" size_t odic_jpeg_progressive_workspace_bytes(const odic_jpeg_prog_batch* b) {
   if (!b || !prog_batch_ok(b)) return 0;
-  return prog_layout(*b).total;
+  return layout(*b).total;
 }
 
 extern "C" size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* b) {
   if (!b || !prog_batch_ok(b)) return 0;
-  return prog_layout(*b).coef;
+  return layout(*b).coef;
 }
 
 extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
@@ -1215,21 +1206,15 @@ extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void*
   if (!b || !b->headers || !b->scans || !b->tables || !b->data || !b->out || !b->status || !workspace)
     return ODIC_ENULL;
   if (!prog_batch_ok(b)) return ODIC_EINVAL;
-  const PLayout L = prog_layout(*b);
+  const Layout L = layout(*b);
   if (ws_bytes < L.total) return ODIC_EINVAL;
-  unsigned char* base = (unsigned char*)workspace;
-  Ws ws{};
-  ws.state = (int*)(base + L.state);
-  ws.scan = base + L.scan;
-  ws.int_bits = (int*)(base + L.int_bits);
-  ws.coef = (short*)(base + L.coef);
-  ws.planes = base + L.planes;
+  const Ws ws = bind(workspace, L);
   hipStream_t s = (hipStream_t)stream;
   const auto* hdrs = (const odic_jpeg_prog_header*)b->headers;
   const auto* scans = (const odic_jpeg_scan*)b->scans;
   const auto* tables = (const odic_jpeg_table*)b->tables;
   const int n = b->n_images;
-  hipError_t e = hipMemsetAsync(base, 0, L.scan, s);                      // state
+  hipError_t e = hipMemsetAsync(workspace, 0, L.scan, s);                 // state
   if (e == hipSuccess) e = hipMemsetAsync(ws.coef, 0, L.planes - L.coef, s);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(jpeg_prog_segment_kernel, dim3(b->n_scans), dim3(256), 0, s, scans, b->data, ws, n);

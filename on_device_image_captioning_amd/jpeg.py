@@ -1,11 +1,14 @@
 """Host side of the device JPEG decoder: a marker parser that sorts every input into
 `device` / `black` / `host` and packs the header records that csrc/jpeg_decode.hip reads.
 
-The parser walks the markers up to SOS only.  It never scans the entropy-coded data: finding restart
-markers and removing 0xFF00 stuffing is device work.  The rule behind the three kinds is that a device
-decode must reproduce `np.asarray(PIL.Image.open(f))` (Pillow with libjpeg-turbo: ISLOW IDCT, fancy
-upsampling, table-driven YCbCr→RGB) bit for bit, and that anything the parser does not fully understand
-goes to PIL, which then raises or decodes exactly as the host path does:
+One marker walker (`_Walker`) reads every file: fill bytes, segment lengths, DQT / DHT / DRI, the SOF and the
+JFIF / Adobe latches, up to each SOS.  One frame rule set (`_frame`) decides what the SOF admits.  `parse` drives
+the walker to the first SOS; `parse_progressive` drives it through the whole scan script to EOI.  Neither scans
+the entropy-coded data of a baseline file: finding restart markers and removing 0xFF00 stuffing is device work.
+
+The rule behind the three kinds is that a device decode must reproduce `np.asarray(PIL.Image.open(f))` (Pillow
+with libjpeg-turbo: ISLOW IDCT, fancy upsampling, table-driven YCbCr→RGB) bit for bit, and that anything the
+parser does not fully understand goes to PIL, which then raises or decodes exactly as the host path does:
 
     device  8-bit SOF0/SOF1 Huffman, one interleaved scan of 3 YCbCr components (JFIF, Adobe transform 1,
             or component ids 1/2/3 — libjpeg's colour-space rules), luma sampling 1x1 / 2x1 / 2x2 with
@@ -140,65 +143,84 @@ def _read_dht(s, dht):
         j += 17 + cnt
 
 
-def _parse(b) -> JpegHeader:
-    n = len(b)
-    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
-        raise _Bad("not a JPEG")
-    i = 2
-    qt = {}
-    dht = {}                                      # (class, id) → HuffTable
-    jfif = adobe = False
-    adobe_transform = None
-    sof = None
-    dri = 0
-    while True:
-        if i + 2 > n:
-            raise _Bad("truncated")
-        if b[i] != 0xFF:
-            raise _Bad("junk between markers")
-        m = b[i + 1]
-        if m == 0xFF:                              # fill byte
-            i += 1
-            continue
-        if m in (0xD8, 0x01) or 0xD0 <= m <= 0xD7 or m == 0xD9:
-            raise _Bad(f"unexpected marker {m:02X} before SOS")
-        seg_len = _u16(b, i + 2)
-        if seg_len < 2 or i + 2 + seg_len > n:
-            raise _Bad("truncated segment")
-        s = bytes(b[i + 4:i + 2 + seg_len])
-        i += 2 + seg_len
-        if m == 0xE0:
-            if len(s) >= 14 and s[:5] == b"JFIF\x00":          # libjpeg: APP0_DATA_LEN
-                jfif = True
-        elif m == 0xEE:
-            if len(s) >= 12 and s[:5] == b"Adobe":             # libjpeg: APP14_DATA_LEN
-                adobe, adobe_transform = True, s[11]
-        elif m == 0xDB:
-            _read_dqt(s, qt)
-        elif m == 0xC4:
-            _read_dht(s, dht)
-        elif m == 0xDD:
-            if len(s) != 2:
-                raise _Bad("bad DRI")
-            dri = (s[0] << 8) | s[1]
-        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
-            if sof is not None:
-                raise _Bad("second SOF")
-            if len(s) < 6:
-                raise _Bad("short SOF")
-            nc = s[5]
-            if len(s) != 6 + 3 * nc:
-                raise _Bad("bad SOF length")
-            sof = (m, s[0], _u16(s, 1), _u16(s, 3), nc,
-                   [(s[6 + 3 * k], s[7 + 3 * k] >> 4, s[7 + 3 * k] & 15, s[8 + 3 * k]) for k in range(nc)])
-        elif m == 0xDA:
-            break
-        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
-            raise _Bad(f"marker {m:02X}")
-        # APPn and COM segments are skipped
-    if sof is None:
+class _Walker:
+    """The marker walk behind both parsers (libjpeg's jdmarker.c rules): what the segments ahead of a scan define."""
+
+    def __init__(self, b):
+        if len(b) < 4 or b[0] != 0xFF or b[1] != 0xD8:
+            raise _Bad("not a JPEG")
+        self.b, self.i = b, 2                         # i: where the walk goes on after an SOS; the caller moves it past
+                                                      # the scan's data
+        self.qt, self.dht = {}, {}                    # id → int32[64]; (class, id) → HuffTable
+        self.dri, self.sof = 0, None                  # sof: (marker, precision, height, width, nc, [(id, h, v, tq)])
+        self.jfif = self.adobe = False
+        self.adobe_transform = None
+
+    def scans(self, script):
+        """Generator of the payload of every SOS segment, self.i behind it.  script=False (`parse`): the caller
+        stops at the first SOS.  script=True (`parse_progressive`): the caller sets self.i to the end of the scan's
+        data and goes on; the walk ends at EOI."""
+        b, n, i = self.b, len(self.b), self.i
+        before = True                                 # no SOS yet
+        while True:
+            if i + 2 > n:
+                raise _Bad("truncated")
+            if b[i] != 0xFF:
+                raise _Bad("junk between markers")
+            m = b[i + 1]
+            if m == 0xFF:                             # fill byte
+                i += 1
+                continue
+            if m == 0xD9 and script:                  # a scan script ends at EOI, and says so when it comes too early;
+                if before:                            # to `parse` an EOI is one more unexpected marker, below
+                    raise _Bad("EOI before SOS")
+                return
+            if m in (0xD8, 0x01) or 0xD0 <= m <= 0xD7 or m == 0xD9:      # SOI, TEM, RSTn: no segment, and no place here
+                raise _Bad(f"unexpected marker {m:02X} before SOS" if before else f"unexpected marker {m:02X}")
+            seg_len = _u16(b, i + 2)
+            if seg_len < 2 or i + 2 + seg_len > n:
+                raise _Bad("truncated segment")
+            s = bytes(b[i + 4:i + 2 + seg_len])
+            i += 2 + seg_len
+            if m == 0xC4:
+                _read_dht(s, self.dht)
+            elif m == 0xDD:
+                if len(s) != 2:
+                    raise _Bad("bad DRI")
+                self.dri = (s[0] << 8) | s[1]
+            elif 0xE0 <= m <= 0xEF or m == 0xFE:      # APPn / COM: skipped, but for libjpeg's two colour-space latches
+                if before and m == 0xE0 and len(s) >= 14 and s[:5] == b"JFIF\x00":        # APP0_DATA_LEN
+                    self.jfif = True
+                elif before and m == 0xEE and len(s) >= 12 and s[:5] == b"Adobe":         # APP14_DATA_LEN
+                    self.adobe, self.adobe_transform = True, s[11]
+            elif m == 0xDA:
+                before, self.i = False, i
+                yield s
+                i = self.i
+            elif not before:                          # between scans only DHT, DRI, APPn / COM and SOS
+                raise _Bad(f"marker {m:02X} between scans")      # DQT (latched per component by libjpeg), DNL, ...
+            elif m == 0xDB:
+                _read_dqt(s, self.qt)
+            elif 0xC0 <= m <= 0xCF and m not in (0xC8, 0xCC):    # every SOF; C4 is DHT, above
+                if self.sof is not None:
+                    raise _Bad("second SOF")
+                if len(s) < 6:
+                    raise _Bad("short SOF")
+                nc = s[5]
+                if len(s) != 6 + 3 * nc:
+                    raise _Bad("bad SOF length")
+                self.sof = (m, s[0], _u16(s, 1), _u16(s, 3), nc,
+                            [(s[6 + 3 * k], s[7 + 3 * k] >> 4, s[7 + 3 * k] & 15, s[8 + 3 * k]) for k in range(nc)])
+            else:
+                raise _Bad(f"marker {m:02X}")
+
+
+def _frame(w, header, sof_kinds, distinct_ids):
+    """What the frame admits, by libjpeg's rules, at the first SOS → header(BLACK) or header(DEVICE) with the frame
+    fields; anything else raises.  sof_kinds: {C0, C1} for `parse`, {C2} for `parse_progressive`."""
+    if w.sof is None:
         raise _Bad("SOS before SOF")
-    m, prec, height, width, nc, comps = sof
+    m, prec, height, width, nc, comps = w.sof
     if prec != 8:
         raise _Bad(f"{prec}-bit")
     if nc not in (1, 3, 4):
@@ -207,50 +229,59 @@ def _parse(b) -> JpegHeader:
         # PIL opens these as mode L / CMYK and the host path substitutes a black RGB canvas without decoding
         if width == 0 or height == 0:
             raise _Bad("empty frame")
-        return JpegHeader(BLACK, width=width, height=height, ncomp=nc)
-    if m not in (0xC0, 0xC1):
+        return header(BLACK, width=width, height=height, ncomp=nc)
+    if m not in sof_kinds:
         raise _Bad(f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
         raise _Bad("DNL / empty frame")
     ids = [c[0] for c in comps]
-    if jfif:
+    if w.jfif:
         ycc = True
-    elif adobe:
-        ycc = adobe_transform == 1
+    elif w.adobe:
+        ycc = w.adobe_transform == 1
     else:
         ycc = ids == [1, 2, 3]
     if not ycc:
         raise _Bad("not YCbCr")
+    if distinct_ids and len(set(ids)) != 3:           # progressive only: its scans name components by id
+        raise _Bad("duplicate component ids")
     hv = [(c[1], c[2]) for c in comps]
     if hv[1] != (1, 1) or hv[2] != (1, 1) or hv[0] not in SAMPLING:
         raise _Bad(f"sampling {hv}")
+    for c in comps:
+        if c[3] not in w.qt:
+            raise _Bad("missing DQT")
+    return header(DEVICE, width=width, height=height, ncomp=3, sampling=SAMPLING[hv[0]], comp_ids=ids, comp_hv=hv,
+                  qtables=[w.qt[c[3]] for c in comps])
+
+
+def _parse(b) -> JpegHeader:
+    w = _Walker(b)
+    s = next(w.scans(script=False))                   # the first SOS; whatever keeps the walk from it raises
+    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False)
+    if hd.kind != DEVICE:
+        return hd
     # SOS: one interleaved baseline scan of all three components, in frame order
     ns = s[0] if len(s) >= 1 else 0
     if ns != 3 or len(s) != 1 + 2 * ns + 3:
         raise _Bad("not one interleaved scan")
     sel = [(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(3)]
-    if [x[0] for x in sel] != ids:
+    if [x[0] for x in sel] != hd.comp_ids:
         raise _Bad("scan component order")
     ss, se, ah_al = s[7], s[8], s[9]
     if ss != 0 or se != 63 or ah_al != 0:
         raise _Bad("bad spectral selection")
-    qts, dcs, acs = [], [], []
-    for k in range(3):
-        tq = comps[k][3]
-        if tq not in qt:
-            raise _Bad("missing DQT")
-        qts.append(qt[tq])
-        td, ta = sel[k][1], sel[k][2]
-        if (0, td) not in dht or (1, ta) not in dht:
+    for _, td, ta in sel:
+        if (0, td) not in w.dht or (1, ta) not in w.dht:
             raise _Bad("missing DHT")                   # libjpeg-turbo would substitute the standard tables
-        dcs.append(dht[(0, td)])
-        acs.append(dht[(1, ta)])
-    if i >= n:
+        hd.dc_tables.append(w.dht[(0, td)])
+        hd.ac_tables.append(w.dht[(1, ta)])
+    if w.i >= len(b):
         raise _Bad("no scan data")
-    if n - i > MAX_SCAN_BYTES:
+    if len(b) - w.i > MAX_SCAN_BYTES:
         raise _Bad("scan longer than the device decoder's bit positions allow")
-    return JpegHeader(DEVICE, width=width, height=height, ncomp=3, sampling=SAMPLING[hv[0]], comp_ids=ids,
-                      comp_hv=hv, qtables=qts, dc_tables=dcs, ac_tables=acs, restart_interval=dri, data_offset=i)
+    hd.restart_interval, hd.data_offset = w.dri, w.i
+    return hd
 
 
 _TABLE_CACHE: dict = {}
@@ -298,6 +329,25 @@ def n_intervals(h: JpegHeader) -> int:
     return -(-total // r)
 
 
+def _place_image(r, h, tot, out_offs, out_bytes):
+    """The per-image part of both packers: geometry, quantisation tables and the output / coefficient / plane offsets
+    into record r, the running totals and maxima into tot → (MCUs, output bytes after this image)."""
+    nmcu = h.mcus_x * h.mcus_y
+    blocks = nmcu * BLOCKS_PER_MCU[h.sampling]
+    r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
+    r["width"], r["height"], r["sampling"] = h.width, h.height, h.sampling
+    r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
+    for c in range(3):
+        r["qt"][c] = h.qtables[c]
+    out_offs.append(out_bytes)
+    tot["total_blocks"] += blocks
+    tot["total_plane_bytes"] += (blocks * 64 + 15) // 16 * 16
+    tot["max_width"] = max(tot["max_width"], h.width)
+    tot["max_height"] = max(tot["max_height"], h.height)
+    tot["max_blocks"] = max(tot["max_blocks"], blocks)
+    return nmcu, out_bytes + h.width * h.height * 3
+
+
 def pack_headers(hdrs, data_offs, data_ends, subseq_bits):
     """Header records + workspace totals for a batch of device-kind headers.
     data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
@@ -312,35 +362,20 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits):
         scan = data_ends[k] - data_offs[k]
         nint = n_intervals(h)
         units = -(-scan * 8 // subseq_bits) + nint
-        bpm = BLOCKS_PER_MCU[h.sampling]
-        nmcu = h.mcus_x * h.mcus_y
-        hy, vy = h.comp_hv[0]
-        plane = nmcu * 64 * (hy * vy + 2)
-        r["data_off"], r["data_end"], r["out_off"] = data_offs[k], data_ends[k], out_bytes
-        r["scan_off"], r["coef_off"], r["plane_off"] = tot["total_scan_bytes"], tot["total_blocks"], \
-            tot["total_plane_bytes"]
+        nmcu, out_bytes = _place_image(r, h, tot, out_offs, out_bytes)
+        r["data_off"], r["data_end"], r["scan_off"] = data_offs[k], data_ends[k], tot["total_scan_bytes"]
         r["int_off"], r["unit_off"] = tot["total_intervals"], tot["total_units"]
-        r["width"], r["height"], r["sampling"] = h.width, h.height, h.sampling
-        r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
         r["restart"] = h.restart_interval or nmcu
         r["n_intervals"], r["n_units"] = nint, units
         for c in range(3):
-            r["qt"][c] = h.qtables[c]
             for t, tab in ((c, h.dc_tables[c]), (3 + c, h.ac_tables[c])):
                 lut, mc, vo, hv = device_tables(tab)
                 r["lut"][t], r["maxcode"][t], r["valoff"][t], r["huffval"][t] = lut, mc, vo, hv
-        out_offs.append(out_bytes)
-        out_bytes += h.width * h.height * 3
         tot["total_scan_bytes"] += (scan + 3) // 4 * 4 + 16
         tot["total_intervals"] += nint + 1
         tot["total_units"] += units
-        tot["total_blocks"] += nmcu * bpm
-        tot["total_plane_bytes"] += (plane + 15) // 16 * 16
         tot["max_units"] = max(tot["max_units"], units)
         tot["max_intervals"] = max(tot["max_intervals"], nint)
-        tot["max_width"] = max(tot["max_width"], h.width)
-        tot["max_height"] = max(tot["max_height"], h.height)
-        tot["max_blocks"] = max(tot["max_blocks"], nmcu * bpm)
         tot["max_scan_bytes"] = max(tot["max_scan_bytes"], scan)
     if (tot["total_intervals"] >= 2 ** 31 or tot["total_units"] >= 2 ** 31
             or tot["max_scan_bytes"] > MAX_SCAN_BYTES):
@@ -429,126 +464,30 @@ def parse_progressive(blob) -> ProgHeader:
 
 
 def _parse_progressive(b) -> ProgHeader:
-    n = len(b)
-    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
-        raise _Bad("not a JPEG")
-    i = 2
-    qt, dht = {}, {}
-    jfif = adobe = False
-    adobe_transform = None
-    sof = None
-    dri = 0
-    hd = None                                      # set at the first SOS
-    coef_bits = None                               # [3][64] current Al of every coefficient, -1: not yet sent (lists)
-    marks = None
-    while True:
-        if i + 2 > n:
-            raise _Bad("truncated")
-        if b[i] != 0xFF:
-            raise _Bad("junk between markers")
-        m = b[i + 1]
-        if m == 0xFF:
-            i += 1
-            continue
-        if m == 0xD9:
-            if hd is None:
-                raise _Bad("EOI before SOS")
-            break
-        if m in (0xD8, 0x01) or 0xD0 <= m <= 0xD7:
-            raise _Bad(f"unexpected marker {m:02X}")
-        seg_len = _u16(b, i + 2)
-        if seg_len < 2 or i + 2 + seg_len > n:
-            raise _Bad("truncated segment")
-        s = b[i + 4:i + 2 + seg_len]
-        i += 2 + seg_len
-        if m == 0xC4:
-            _read_dht(s, dht)
-        elif m == 0xDD:
-            if len(s) != 2:
-                raise _Bad("bad DRI")
-            dri = (s[0] << 8) | s[1]
-        elif 0xE0 <= m <= 0xEF or m == 0xFE:
-            if hd is None and m == 0xE0 and len(s) >= 14 and s[:5] == b"JFIF\x00":
-                jfif = True
-            elif hd is None and m == 0xEE and len(s) >= 12 and s[:5] == b"Adobe":
-                adobe, adobe_transform = True, s[11]
-        elif hd is not None and m != 0xDA:
-            raise _Bad(f"marker {m:02X} between scans")      # DQT (latched per component by libjpeg), DNL, ...
-        elif m == 0xDB:
-            _read_dqt(s, qt)
-        elif 0xC0 <= m <= 0xCF and m not in (0xC8, 0xCC):
-            if sof is not None:
-                raise _Bad("second SOF")
-            if len(s) < 6:
-                raise _Bad("short SOF")
-            nc = s[5]
-            if len(s) != 6 + 3 * nc:
-                raise _Bad("bad SOF length")
-            sof = (m, s[0], _u16(s, 1), _u16(s, 3), nc,
-                   [(s[6 + 3 * k], s[7 + 3 * k] >> 4, s[7 + 3 * k] & 15, s[8 + 3 * k]) for k in range(nc)])
-        elif m == 0xDA:
-            if hd is None:
-                hd = _progressive_frame(sof, jfif, adobe, adobe_transform, qt)
-                if hd.kind != DEVICE:
-                    return hd
-                coef_bits = [[-1] * 64 for _ in range(3)]
-                marks = marker_positions(b)
-            if len(hd.scans) >= MAX_SCANS:
-                raise _Bad(f"more than {MAX_SCANS} scans")
-            sc = _progressive_scan(hd, s, dht, dri, coef_bits)
-            k = int(np.searchsorted(marks, i))
-            if k >= len(marks):
-                raise _Bad("truncated scan")
-            sc.data_offset, sc.data_end = i, int(marks[k])
-            if sc.data_end - sc.data_offset > MAX_SCAN_BYTES:
-                raise _Bad("scan longer than the device decoder's bit positions allow")
-            hd.scans.append(sc)
-            i = sc.data_end
-        else:
-            raise _Bad(f"marker {m:02X}")
+    w = _Walker(b)
+    hd = coef_bits = marks = None                  # set at the first SOS; coef_bits: [3][64] current Al of every
+    for s in w.scans(script=True):                 # coefficient, -1: not yet sent (lists)
+        if hd is None:
+            hd = _frame(w, ProgHeader, (0xC2,), distinct_ids=True)
+            if hd.kind != DEVICE:
+                return hd
+            coef_bits = [[-1] * 64 for _ in range(3)]
+            marks = marker_positions(b)
+        if len(hd.scans) >= MAX_SCANS:
+            raise _Bad(f"more than {MAX_SCANS} scans")
+        sc = _progressive_scan(hd, s, w.dht, w.dri, coef_bits)
+        k = int(np.searchsorted(marks, w.i))
+        if k >= len(marks):
+            raise _Bad("truncated scan")
+        sc.data_offset, sc.data_end = w.i, int(marks[k])
+        if sc.data_end - sc.data_offset > MAX_SCAN_BYTES:
+            raise _Bad("scan longer than the device decoder's bit positions allow")
+        hd.scans.append(sc)
+        w.i = sc.data_end                          # the walk goes on at the marker that closed the scan
     if any(any(row) for row in coef_bits):
         raise _Bad("incomplete scan script")             # libjpeg smooths across blocks: not a plain decode
     _dependency_levels(hd.scans)
     return hd
-
-
-def _progressive_frame(sof, jfif, adobe, adobe_transform, qt) -> ProgHeader:
-    if sof is None:
-        raise _Bad("SOS before SOF")
-    m, prec, height, width, nc, comps = sof
-    if prec != 8:
-        raise _Bad(f"{prec}-bit")
-    if nc not in (1, 3, 4):
-        raise _Bad(f"{nc} components")
-    if nc in (1, 4) and m in (0xC0, 0xC1, 0xC2):
-        if width == 0 or height == 0:
-            raise _Bad("empty frame")
-        return ProgHeader(BLACK, width=width, height=height, ncomp=nc)
-    if m != 0xC2:
-        raise _Bad(f"SOF{m - 0xC0}")
-    if width == 0 or height == 0:
-        raise _Bad("DNL / empty frame")
-    ids = [c[0] for c in comps]
-    if jfif:
-        ycc = True
-    elif adobe:
-        ycc = adobe_transform == 1
-    else:
-        ycc = ids == [1, 2, 3]
-    if not ycc:
-        raise _Bad("not YCbCr")
-    if len(set(ids)) != 3:
-        raise _Bad("duplicate component ids")
-    hv = [(c[1], c[2]) for c in comps]
-    if hv[1] != (1, 1) or hv[2] != (1, 1) or hv[0] not in SAMPLING:
-        raise _Bad(f"sampling {hv}")
-    qts = []
-    for c in comps:
-        if c[3] not in qt:
-            raise _Bad("missing DQT")
-        qts.append(qt[c[3]])
-    return ProgHeader(DEVICE, width=width, height=height, ncomp=3, sampling=SAMPLING[hv[0]], comp_ids=ids,
-                      comp_hv=hv, qtables=qts)
 
 
 def _progressive_scan(hd, s, dht, dri, coef_bits) -> ProgScan:
@@ -634,25 +573,9 @@ def pack_progressive(hdrs, blob_offs):
         return table_ix[key]
 
     for k, h in enumerate(hdrs):
-        r = rec[k]
-        nmcu = h.mcus_x * h.mcus_y
-        hy, vy = h.comp_hv[0]
-        bpm = hy * vy + 2
-        plane = nmcu * 64 * bpm
-        r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
-        r["width"], r["height"], r["sampling"], r["mcus_x"], r["mcus_y"] = h.width, h.height, h.sampling, h.mcus_x, \
-            h.mcus_y
-        r["n_intervals"] = sum(s.n_intervals for s in h.scans)
-        for c in range(3):
-            r["qt"][c] = h.qtables[c]
+        _, out_bytes = _place_image(rec[k], h, tot, out_offs, out_bytes)
+        rec[k]["n_intervals"] = sum(s.n_intervals for s in h.scans)
         flat += [(s.level, k, s) for s in h.scans]
-        out_offs.append(out_bytes)
-        out_bytes += h.width * h.height * 3
-        tot["total_blocks"] += nmcu * bpm
-        tot["total_plane_bytes"] += (plane + 15) // 16 * 16
-        tot["max_width"] = max(tot["max_width"], h.width)
-        tot["max_height"] = max(tot["max_height"], h.height)
-        tot["max_blocks"] = max(tot["max_blocks"], nmcu * bpm)
     flat.sort(key=lambda x: x[0])
     srec = np.zeros(len(flat), SCAN_DTYPE)
     n_levels = flat[-1][0] if flat else 0

@@ -115,6 +115,35 @@ def test_kinds():
     assert J.parse(p.getvalue()).kind == J.HOST
 
 
+def random_rgb():
+    """The 24x40 image of the prefix sweeps (here and in test_jpeg_progressive_host.py)."""
+    return np.random.default_rng(7).integers(0, 256, (40, 24, 3), dtype=np.uint8)
+
+
+def header_fields(hd):
+    """Every field of a header but `reason`, in a form that compares with == (tables as lists / bytes)."""
+    return [(f, [list(map(int, q)) for q in v] if f == "qtables" else
+             [(t.bits, bytes(t.vals)) for t in v] if f in ("dc_tables", "ac_tables") else v)
+            for f, v in vars(hd).items() if f != "reason"]
+
+
+@pytest.mark.parametrize("kw", [dict(subsampling=2), dict(subsampling=0, restart_marker_blocks=2)], ids=["420", "444-dri"])
+def test_every_prefix_of_a_baseline_file_is_sorted_without_raising(kw):
+    """Neither parser raises on any prefix; `parse` needs the whole header and one byte of scan data, and from
+    there on returns the full file's header (it never looks at the entropy-coded data)."""
+    blob = encode(random_rgb(), quality=50, **kw)
+    full = J.parse(blob)
+    assert full.kind == J.DEVICE and (full.restart_interval > 0) == ("restart_marker_blocks" in kw)
+    want = header_fields(full)
+    for n in range(len(blob)):
+        hd = J.parse(blob[:n])
+        assert J.parse_progressive(blob[:n]).kind == J.HOST, n                # SOF0, or cut before it
+        if n <= full.data_offset:
+            assert hd.kind == J.HOST and hd.reason, n
+        else:
+            assert header_fields(hd) == want, n
+
+
 def test_device_tables_decode_every_code():
     hd = J.parse(encode(smooth_rgb(24, 24), quality=90, optimize=True))
     for t in hd.dc_tables + hd.ac_tables:

@@ -226,6 +226,34 @@ def test_other_kinds():
     assert J.parse_progressive(extra).kind == J.HOST                   # repeated DC scans: bogus, and too many
 
 
+@pytest.mark.parametrize("subsampling", [2, 0], ids=["420", "444"])
+def test_every_prefix_of_a_progressive_file_goes_to_the_host_without_raising(subsampling):
+    """Neither parser raises on any prefix, and a progressive file missing any of its bytes (EOI at the least) is
+    never a device kind."""
+    blob = encode_progressive(H.random_rgb(), quality=50, subsampling=subsampling)
+    assert J.parse_progressive(blob).kind == J.DEVICE
+    for n in range(len(blob)):
+        hd = J.parse_progressive(blob[:n])
+        assert hd.kind == J.HOST and hd.reason, n
+        base = J.parse(blob[:n])
+        assert base.kind == J.HOST and base.reason, n
+
+
+@pytest.mark.parametrize("subsampling", [0, 1, 2])
+def test_both_parsers_read_the_same_frame(subsampling):
+    """One image, one quality and subsampling, saved baseline and progressive: the frame fields of `parse` on the first
+    equal those of `parse_progressive` on the second."""
+    img = H.random_rgb()
+    a = J.parse(H.encode(img, quality=80, subsampling=subsampling))
+    b = J.parse_progressive(encode_progressive(img, quality=80, subsampling=subsampling))
+    assert a.kind == b.kind == J.DEVICE
+    for f in ("width", "height", "sampling", "comp_ids", "comp_hv"):
+        assert getattr(a, f) == getattr(b, f), f
+    assert len(a.qtables) == len(b.qtables) == 3
+    for qa, qb in zip(a.qtables, b.qtables):
+        assert list(qa) == list(qb)
+
+
 def test_marker_search_is_vectorised_and_exact():
     blob = matrix_blob(len(MATRIX))
     scans, eoi = walk(blob)
