@@ -51,8 +51,9 @@ extern "C" {
 #define ODIC_EUNSUPPORTED (-3)
 
 /* ABI version of this header; bumped on any signature change.
- *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step). */
-#define ODIC_ABI_VERSION 20
+ *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step).
+ *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale). */
+#define ODIC_ABI_VERSION 21
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -245,6 +246,18 @@ size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* batch);
  * `out` and n_images entries of `status` are written (test_jpeg_decode_stays_inside_its_workspace). */
 int odic_jpeg_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
+/* The same decode at 1/1, 1/2, 1/4 or 1/8 of each frame's size, bit-exact with Pillow's Image.draft (libjpeg's
+ * scale_denom): scale_log2 is a DEVICE pointer to int32 [n_images], each 0..3 (jpeg.draft_scale picks it as Pillow
+ * does).  Image i yields ceil(W / s) × ceil(H / s)
+ * × 3 bytes at its out_off, s = 1 << scale_log2[i]; out_off, and the batch's max_width / max_height, are those of the
+ * scaled sizes, while width, height, mcus_x and mcus_y stay the frame's own.  Everything up to the coefficients runs
+ * as in odic_jpeg_decode; the inverse transforms are libjpeg's reduced ones (8 / s samples per luma block side;
+ * 4:2:0 chroma takes twice that and needs no upsampling, 4:2:2 chroma is upsampled horizontally).  Workspace query,
+ * workspace layout, status rule (the ±8191 / [-512, 511] limits apply to what the reduced transform reads and makes) and
+ * containment are those of odic_jpeg_decode.  ODIC_ENULL for a null scale_log2. */
+int odic_jpeg_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace, size_t ws_bytes,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Progressive files (8-bit SOF2 Huffman, 3 YCbCr components, the samplings above), bit-exact with Pillow as well.
  * The host parser (jpeg.parse_progressive) reads the whole scan script and accepts what libjpeg accepts without a
@@ -313,6 +326,10 @@ size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* batch);
  * many intervals, an invalid code, an EOB run or coefficient index past the band, bits needed past an interval's end, or
  * coefficients outside the IDCT's range as above.  The parser vouches for the script and the closing EOI. */
 int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* batch, void* workspace, size_t ws_bytes, void* stream);
+
+/* odic_jpeg_decode_scaled for progressive files: scale_log2 as there, everything else as odic_jpeg_decode_progressive. */
+int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* batch, const int32_t* scale_log2, void* workspace,
+                                        size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core  (WindowAttention.forward swin_transformer_mod.py:193-211

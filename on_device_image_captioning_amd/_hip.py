@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libodic_hip.so")
 
 F32, BF16, FP8, F16, H2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _ERR = {-1: "ODIC_EINVAL (bad shape / alignment / enum)", -2: "ODIC_ENULL (required pointer is NULL)",
         -3: "ODIC_EUNSUPPORTED"}
@@ -113,6 +113,8 @@ _SIGNATURES = {
     "odic_jpeg_progressive_workspace_bytes": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
     "odic_jpeg_progressive_coef_offset": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
     "odic_jpeg_decode_progressive": (C.c_int, [C.POINTER(JpegProgBatch), _P, C.c_size_t, _P]),
+    "odic_jpeg_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
+    "odic_jpeg_decode_progressive_scaled": (C.c_int, [C.POINTER(JpegProgBatch), _P, _P, C.c_size_t, _P]),
 }
 
 #: every symbol include/odic_hip.h declares

@@ -30,6 +30,10 @@
 //   color       h2v1 / h2v2 fancy upsampling + jdcolor.c ycc_rgb_convert, cropped H×W×3 into the caller's
 //               buffer, and the per-image status.
 //
+// odic_jpeg_decode_scaled / odic_jpeg_decode_progressive_scaled (Pillow's Image.draft) run the same launches up to the
+// coefficients and then the scaled forms of the last two: reduced 4x4 / 2x2 / 1x1 inverse transforms per component
+// (idct_blocks) and a colour pass over ceil(W / s) × ceil(H / s) pixels (color_pixel), s = 1, 2, 4, 8 per image.
+//
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
 // whose coefficients leave the range where libjpeg-turbo's SIMD and C IDCTs agree (kIdctLimit), gets status 1:
@@ -706,31 +710,76 @@ __device__ __forceinline__ unsigned range_limit(int x) {   // IDCT_range_limit[x
   return (unsigned)(s < 0 ? 0 : (s > 255 ? 255 : s));
 }
 
-template <typename Header>                                      // odic_jpeg_header or odic_jpeg_prog_header
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(const Header* __restrict__ hdrs, Ws ws) {
-  const Header& h = hdrs[blockIdx.y];
+// The reduced transforms of a scaled decode (jidctred.c jpeg_idct_4x4 / jpeg_idct_2x2; libjpeg's scale_denom 2, 4, 8):
+// the same two passes on fewer inputs.  4x4 never reads column 4 or row 4; 2x2 reads columns and rows 0, 1, 3, 5, 7.
+__device__ __forceinline__ void idct4_1d(const int* in, int* out, int shift) {
+  const int t0 = in[0] * (1 << 14);
+  const int t2 = in[2] * FIX_1_847759065 - in[6] * FIX_0_765366865;
+  const int t10 = t0 + t2, t12 = t0 - t2;
+  const int z1 = in[7], z2 = in[5], z3 = in[3], z4 = in[1];
+  const int o0 = -z1 * 1730 + z2 * 11893 - z3 * 17799 + z4 * 8697;
+  const int o2 = -z1 * 4176 - z2 * 4926 + z3 * FIX_0_899976223 + z4 * FIX_2_562915447;
+  const int r = 1 << (shift - 1);
+  out[0] = (t10 + o2 + r) >> shift; out[3] = (t10 - o2 + r) >> shift;
+  out[1] = (t12 + o0 + r) >> shift; out[2] = (t12 - o0 + r) >> shift;
+}
+
+__device__ __forceinline__ void idct2_1d(const int* in, int* out, int shift) {
+  const int t10 = in[0] * (1 << 15);
+  const int t0 = -in[7] * 5906 + in[5] * 6967 - in[3] * 10426 + in[1] * 29692;
+  const int r = 1 << (shift - 1);
+  out[0] = (t10 + t0 + r) >> shift;
+  out[1] = (t10 - t0 + r) >> shift;
+}
+
+// Transform size of the luma (ny) and chroma (nc) blocks at scale 1 / 2^lg (jdmaster.c: every component starts at
+// 8 >> lg and doubles while that keeps it on the luma grid in both directions).  Only 4:2:0 chroma doubles: it then
+// shares the luma's grid and is not upsampled; 4:2:2 chroma fails the vertical test and stays.
+__device__ __forceinline__ void scaled_sizes(int sampling, int lg, int& ny, int& nc) {
+  ny = 8 >> lg;
+  nc = (sampling == 2 && lg > 0) ? 2 * ny : ny;
+}
+
+// row / column i is an input of the n-point transform
+__device__ __forceinline__ bool idct_reads(int n, int i) {
+  return n == 8 || (n == 4 ? i != 4 : (n == 2 ? (i < 2 || (i & 1)) : i == 0));
+}
+
+// One block per 8 lanes: column pass → LDS → row pass, n×n samples into the component's plane.  kScaled = false is
+// the full-size decode (lg = 0, n = 8 throughout, the branches below fold away).  A scaled image's planes keep the
+// full-size order (Y, Cb, Cr from plane_off) with every block n wide and high.  The range rule of kIdctLimit holds for
+// the reduced transforms as it stands: on the inputs a transform reads, its pass-1 values and its results (1x1 has
+// only the input and the result).  libjpeg-turbo's SIMD 4x4 / 2x2 keep the same 16-bit intermediates as its 8x8.
+template <bool kScaled, typename Header>
+__device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int img, int lg, int (*ws8)[8][9]) {
   const int nY = luma_blocks(h.sampling), bpm = nY + 2;
   const long nblocks = (long)h.mcus_x * h.mcus_y * bpm;
   const long b = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
   const int lane = threadIdx.x & 7, slot = threadIdx.x >> 3;
-  __shared__ int ws8[32][8][9];
   if ((long)blockIdx.x * 32 >= nblocks) return;
   const bool live = b < nblocks;
   const int j = (int)(live ? b % bpm : 0);
   const int comp = j < nY ? 0 : j - nY + 1;
+  int ny = 8, nc = 8;
+  if (kScaled) scaled_sizes(h.sampling, lg, ny, nc);
+  const int n = comp == 0 ? ny : nc;
   bool outside = false;                                       // a value where libjpeg-turbo's SIMD and C IDCTs part
-  if (live) {                                                 // column `lane`
+  if (live && idct_reads(n, lane)) {                          // column `lane`
     const short* c = ws.coef + (h.coef_off + b) * 64;
     int in[8], out[8];
     for (int r = 0; r < 8; ++r) {
-      in[r] = (int)c[r * 8 + lane] * (int)h.qt[comp][r * 8 + lane];
+      in[r] = idct_reads(n, r) ? (int)c[r * 8 + lane] * (int)h.qt[comp][r * 8 + lane] : 0;
       if (in[r] < -kIdctLimit || in[r] > kIdctLimit) {
         outside = true;
         in[r] = 0;                                            // keeps the int32 arithmetic in range; image is redone
       }
     }
-    idct_1d(in, out, 13 - 2);
+    if (n == 8) idct_1d(in, out, 13 - 2);
+    else if (n == 4) idct4_1d(in, out, 13 - 2 + 1);
+    else if (n == 2) idct2_1d(in, out, 13 - 2 + 2);
+    else out[0] = in[0];                                      // 1x1: DESCALE(in0, 3) below, no pass 1
     for (int r = 0; r < 8; ++r) {
+      if (r >= n) break;
       if (out[r] < -kIdctLimit || out[r] > kIdctLimit) {
         outside = true;
         out[r] = 0;
@@ -741,27 +790,60 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const Header* __restrict
   __syncthreads();
   if (!live) return;
   int in[8], out[8];                                          // row `lane`
-  for (int x = 0; x < 8; ++x) in[x] = ws8[slot][lane][x];
-  idct_1d(in, out, 13 + 2 + 3);
-  for (int x = 0; x < 8; ++x) outside |= out[x] < -512 || out[x] > 511;
-  if (outside) atomicOr(&ws.state[kStateWords * blockIdx.y], kErrRange);
+  if (lane < n) {
+    for (int x = 0; x < 8; ++x) in[x] = idct_reads(n, x) ? ws8[slot][lane][x] : 0;
+    if (n == 8) idct_1d(in, out, 13 + 2 + 3);
+    else if (n == 4) idct4_1d(in, out, 13 + 2 + 3 + 1);
+    else if (n == 2) idct2_1d(in, out, 13 + 2 + 3 + 2);
+    else out[0] = (in[0] + 4) >> 3;
+    for (int x = 0; x < 8; ++x) outside |= x < n && (out[x] < -512 || out[x] > 511);
+  }
+  if (outside) atomicOr(&ws.state[kStateWords * img], kErrRange);
+  if (lane >= n) return;
   const long mcu = b / bpm;
   const int mx = (int)(mcu % h.mcus_x), my = (int)(mcu / h.mcus_x);
   const int hy = h.sampling == 0 ? 1 : 2, vy = h.sampling == 2 ? 2 : 1;
-  int bx = mx, by = my, pw = h.mcus_x * 8;
+  int bx = mx, by = my, pw = h.mcus_x * nc;
   unsigned char* plane = ws.planes + h.plane_off;
-  const long ysz = (long)h.mcus_x * 8 * hy * h.mcus_y * 8 * vy, csz = (long)h.mcus_x * 8 * h.mcus_y * 8;
+  const long ysz = (long)h.mcus_x * ny * hy * h.mcus_y * ny * vy, csz = (long)h.mcus_x * nc * h.mcus_y * nc;
   if (comp == 0) {
     bx = mx * hy + j % hy;
     by = my * vy + j / hy;
-    pw *= hy;
+    pw = h.mcus_x * ny * hy;
   } else {
     plane += ysz + (comp - 1) * csz;
   }
-  uint2 v;
-  v.x = range_limit(out[0]) | range_limit(out[1]) << 8 | range_limit(out[2]) << 16 | range_limit(out[3]) << 24;
-  v.y = range_limit(out[4]) | range_limit(out[5]) << 8 | range_limit(out[6]) << 16 | range_limit(out[7]) << 24;
-  *(uint2*)(plane + (long)(by * 8 + lane) * pw + bx * 8) = v;
+  unsigned char* row = plane + (long)(by * n + lane) * pw + bx * n;
+  if (n == 8) {
+    uint2 v;
+    v.x = range_limit(out[0]) | range_limit(out[1]) << 8 | range_limit(out[2]) << 16 | range_limit(out[3]) << 24;
+    v.y = range_limit(out[4]) | range_limit(out[5]) << 8 | range_limit(out[6]) << 16 | range_limit(out[7]) << 24;
+    *(uint2*)row = v;
+  } else if (n == 4) {                                        // every row of an n-wide block is n-aligned: plane sizes and
+    *(unsigned*)row =                                         // row pitches are multiples of 16 n / 4, plane_off of 16
+        range_limit(out[0]) | range_limit(out[1]) << 8 | range_limit(out[2]) << 16 | range_limit(out[3]) << 24;
+  } else if (n == 2) {
+    *(unsigned short*)row = (unsigned short)(range_limit(out[0]) | range_limit(out[1]) << 8);
+  } else {
+    row[0] = (unsigned char)range_limit(out[0]);
+  }
+}
+
+template <typename Header>                                      // odic_jpeg_header or odic_jpeg_prog_header
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const Header* __restrict__ hdrs, Ws ws) {
+  __shared__ int ws8[32][8][9];
+  idct_blocks<false>(hdrs[blockIdx.y], ws, blockIdx.y, 0, ws8);
+}
+
+// scale_log2[image] = 0..3: decode at 1 / 2 / 4 / 8 of the frame's size.  The caller vouches for the range; a value
+// outside it is kept away from the shifts and the plane geometry (the image is left undecoded, with status 1).
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_idct_scaled_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                               const int* __restrict__ scale_log2) {
+  __shared__ int ws8[32][8][9];
+  const int lg = scale_log2[blockIdx.y];
+  if ((unsigned)lg > 3u) return;
+  idct_blocks<true>(hdrs[blockIdx.y], ws, blockIdx.y, lg, ws8);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -771,36 +853,46 @@ constexpr int kCrR = 91881, kCbB = 116130, kCrG = 46802, kCbG = 22554;   // FIX(
 
 __device__ __forceinline__ unsigned char clamp255(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-template <typename Header>
-__global__ __launch_bounds__(256) void jpeg_color_kernel(const Header* __restrict__ hdrs, Ws ws,
-                                                         unsigned char* __restrict__ out, int* __restrict__ status) {
-  const int img = blockIdx.z;
-  const Header& h = hdrs[img];
+// One output pixel.  kScaled = false is the full-size decode (lg = 0).  At scale 1 / 2^lg the output is
+// ceil(W / 2^lg) × ceil(H / 2^lg) and the planes hold the transform sizes of scaled_sizes(): 4:4:4 and, for lg > 0,
+// 4:2:0 read chroma on the luma grid; 4:2:2 upsamples horizontally (jdsample.c): fancy while the chroma transform is
+// larger than 1x1 and the component's downsampled width ceil(W·nc / 16) is above 2, else by replication.
+template <bool kScaled, typename Header>
+__device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int img, int lg,
+                                            unsigned char* __restrict__ out, int* __restrict__ status) {
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
   if (x == 0 && y == 0) {
     const int* st = ws.state + kStateWords * img;
     status[img] = (st[0] == 0 && st[1] == h.n_intervals) ? 0 : 1;
   }
-  const int W = h.width, H = h.height;
+  const int round = (1 << lg) - 1;
+  const int W = kScaled ? (h.width + round) >> lg : h.width, H = kScaled ? (h.height + round) >> lg : h.height;
   if (x >= W || y >= H) return;
   const int sampling = h.sampling, hy = sampling == 0 ? 1 : 2, vy = sampling == 2 ? 2 : 1;
-  const int yw = h.mcus_x * 8 * hy, cw = h.mcus_x * 8;
+  int ny = 8, nc = 8;
+  if (kScaled) scaled_sizes(sampling, lg, ny, nc);
+  const int yw = h.mcus_x * ny * hy, cw = h.mcus_x * nc;
   const unsigned char* Y = ws.planes + h.plane_off;
-  const unsigned char* Cb = Y + (long)yw * h.mcus_y * 8 * vy;
-  const unsigned char* Cr = Cb + (long)cw * h.mcus_y * 8;
+  const unsigned char* Cb = Y + (long)yw * h.mcus_y * ny * vy;
+  const unsigned char* Cr = Cb + (long)cw * h.mcus_y * nc;
   const int yv = Y[(long)y * yw + x];
   int cb, cr;
-  if (sampling == 0) {
+  if (sampling == 0 || (kScaled && sampling == 2 && lg > 0)) {
     cb = Cb[(long)y * cw + x];
     cr = Cr[(long)y * cw + x];
   } else {
-    const int dw = (W + 1) >> 1;
+    const int dw = kScaled ? (h.width * nc + 15) >> 4 : (W + 1) >> 1;      // the same number at lg = 0
     const int c = x >> 1, odd = x & 1;
     const int cn = odd ? min(c + 1, dw - 1) : max(c - 1, 0);
     if (sampling == 1) {
       const long r = (long)y * cw;
-      cb = (3 * Cb[r + c] + Cb[r + cn] + 1 + odd) >> 2;
-      cr = (3 * Cr[r + c] + Cr[r + cn] + 1 + odd) >> 2;
+      if (kScaled && lg > 0 && (nc == 1 || dw <= 2)) {
+        cb = Cb[r + c];
+        cr = Cr[r + c];
+      } else {
+        cb = (3 * Cb[r + c] + Cb[r + cn] + 1 + odd) >> 2;
+        cr = (3 * Cr[r + c] + Cr[r + cn] + 1 + odd) >> 2;
+      }
     } else {
       const int dh = (H + 1) >> 1;
       const int rr = y >> 1;
@@ -818,6 +910,25 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const Header* __restric
   o[0] = clamp255(yv + ((kCrR * cr + 32768) >> 16));
   o[1] = clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
   o[2] = clamp255(yv + ((kCbB * cb + 32768) >> 16));
+}
+
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                         unsigned char* __restrict__ out, int* __restrict__ status) {
+  color_pixel<false>(hdrs[blockIdx.z], ws, blockIdx.z, 0, out, status);
+}
+
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_color_scaled_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                                const int* __restrict__ scale_log2,
+                                                                unsigned char* __restrict__ out,
+                                                                int* __restrict__ status) {
+  const int img = blockIdx.z, lg = scale_log2[img];
+  if ((unsigned)lg > 3u) {                                    // not a scale: nothing was decoded, nothing is written
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) status[img] = 1;
+    return;
+  }
+  color_pixel<true>(hdrs[img], ws, img, lg, out, status);
 }
 
 
@@ -1160,7 +1271,26 @@ extern "C" size_t odic_jpeg_workspace_bytes(const odic_jpeg_batch* b) {
   return layout(*b).total;
 }
 
-extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
+namespace {
+
+// The IDCT and colour launches both entry points of a file kind end with: full-size (scale_log2 == nullptr, the
+// kernels of odic_jpeg_decode / odic_jpeg_decode_progressive) or per-image scales.
+template <typename Header, typename Batch>
+void launch_idct_color(const Batch* b, const Header* hdrs, const Ws& ws, const int32_t* scale_log2, hipStream_t s) {
+  const dim3 igrid((unsigned)((b->max_blocks + 31) / 32), b->n_images);
+  const dim3 cgrid((b->max_width + 63) / 64, (b->max_height + 3) / 4, b->n_images);
+  if (scale_log2) {
+    hipLaunchKernelGGL(jpeg_idct_scaled_kernel<Header>, igrid, dim3(256), 0, s, hdrs, ws, scale_log2);
+    hipLaunchKernelGGL(jpeg_color_scaled_kernel<Header>, cgrid, dim3(64, 4), 0, s, hdrs, ws, scale_log2, b->out,
+                       b->status);
+  } else {
+    hipLaunchKernelGGL(jpeg_idct_kernel<Header>, igrid, dim3(256), 0, s, hdrs, ws);
+    hipLaunchKernelGGL(jpeg_color_kernel<Header>, cgrid, dim3(64, 4), 0, s, hdrs, ws, b->out, b->status);
+  }
+}
+
+int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream,
+                    const int32_t* scale_log2) {
   if (!b || !b->headers || !b->data || !b->out || !b->status || !workspace) return ODIC_ENULL;
   if (!batch_dims_ok(*b) || b->subseq_bits < 32 || b->subseq_bits > kMaxSubseqBits || b->max_sync_passes < 0 ||
       b->max_sync_passes > 64 || b->max_units <= 0 || b->max_intervals <= 0 || b->max_scan_bytes <= 0 ||
@@ -1185,24 +1315,12 @@ extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_
   hipLaunchKernelGGL(jpeg_block_scan_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
   hipLaunchKernelGGL(jpeg_writeout_kernel, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
   hipLaunchKernelGGL(jpeg_dc_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
-  hipLaunchKernelGGL(jpeg_idct_kernel<odic_jpeg_header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs, ws);
-  hipLaunchKernelGGL(jpeg_color_kernel<odic_jpeg_header>, dim3((b->max_width + 63) / 64, (b->max_height + 3) / 4, n), dim3(64, 4), 0, s,
-                     hdrs, ws, b->out, b->status);
+  launch_idct_color(b, hdrs, ws, scale_log2, s);
   return odic_launch_status();
 }
 
-extern "C" size_t odic_jpeg_progressive_workspace_bytes(const odic_jpeg_prog_batch* b) {
-  if (!b || !prog_batch_ok(b)) return 0;
-  return layout(*b).total;
-}
-
-extern "C" size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* b) {
-  if (!b || !prog_batch_ok(b)) return 0;
-  return layout(*b).coef;
-}
-
-extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
-                                            void* stream) {
+int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes, void* stream,
+                       const int32_t* scale_log2) {
   if (!b || !b->headers || !b->scans || !b->tables || !b->data || !b->out || !b->status || !workspace)
     return ODIC_ENULL;
   if (!prog_batch_ok(b)) return ODIC_EINVAL;
@@ -1221,9 +1339,39 @@ extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void*
   for (int l = 0; l < b->n_levels; ++l)
     hipLaunchKernelGGL(jpeg_prog_decode_kernel, dim3(b->level_intervals[l], b->level_first[l + 1] - b->level_first[l]),
                        dim3(64), 0, s, hdrs, scans, tables, ws, b->level_first[l], n, b->n_tables);
-  hipLaunchKernelGGL(jpeg_idct_kernel<odic_jpeg_prog_header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256),
-                     0, s, hdrs, ws);
-  hipLaunchKernelGGL(jpeg_color_kernel<odic_jpeg_prog_header>, dim3((b->max_width + 63) / 64, (b->max_height + 3) / 4, n),
-                     dim3(64, 4), 0, s, hdrs, ws, b->out, b->status);
+  launch_idct_color(b, hdrs, ws, scale_log2, s);
   return odic_launch_status();
+}
+
+}  // namespace
+
+extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
+  return decode_baseline(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" int odic_jpeg_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
+                                       size_t ws_bytes, void* stream) {
+  if (!scale_log2) return ODIC_ENULL;
+  return decode_baseline(b, workspace, ws_bytes, stream, scale_log2);
+}
+
+extern "C" size_t odic_jpeg_progressive_workspace_bytes(const odic_jpeg_prog_batch* b) {
+  if (!b || !prog_batch_ok(b)) return 0;
+  return layout(*b).total;
+}
+
+extern "C" size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* b) {
+  if (!b || !prog_batch_ok(b)) return 0;
+  return layout(*b).coef;
+}
+
+extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
+                                            void* stream) {
+  return decode_progressive(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* b, const int32_t* scale_log2,
+                                                   void* workspace, size_t ws_bytes, void* stream) {
+  if (!scale_log2) return ODIC_ENULL;
+  return decode_progressive(b, workspace, ws_bytes, stream, scale_log2);
 }

@@ -36,7 +36,8 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # odic_jpeg_decode_progressive, csrc/jpeg_decode.hip), bit-exact with PIL: `from_jpeg_bytes` /
 # `from_files(..., decode="device")`.  Files the device decoder does not take (arithmetic coding, non-JPEG, ...)
 # and images whose entropy data fails to decode are decoded by PIL in the same call, so the result and the
-# exceptions are those of the host path.
+# exceptions are those of the host path.  With a draft request (`draft=`) the files are decoded at 1/2, 1/4 or 1/8 scale
+# in the DCT domain, as `PIL.Image.draft` does, on either path and bit-exact between them.
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -135,24 +136,31 @@ class DevicePreprocessor:
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
 
-    def from_files(self, paths, decode: str = "host") -> torch.Tensor:
+    def from_files(self, paths, decode: str = "host", draft: bool = False) -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
-        the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result)."""
+        the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
+        draft=True: JPEGs are decoded at the scale `Image.draft("RGB", (S, S))` picks (1/2, 1/4 or 1/8 while both sides
+        stay at least S) and resized from there; the tensor differs slightly from the undrafted one, identically for
+        both values of `decode`."""
         if decode == "device":
             blobs = []
             for p in paths:
                 with open(p, "rb") as f:
                     blobs.append(f.read())
-            return self.from_jpeg_bytes(blobs)
+            return self.from_jpeg_bytes(blobs, draft=draft)
         if decode != "host":
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
-        imgs = []
-        for p in paths:
-            pil = Image.open(p)
-            if pil.mode != "RGB":
-                pil = Image.new("RGB", pil.size)
-            imgs.append(np.asarray(pil, dtype=np.uint8))
-        return self(imgs)
+        return self([self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None) for p in paths])
+
+    @staticmethod
+    def _pil_rgb(pil, draft=None) -> np.ndarray:
+        """The host decode of one opened file: the draft request if there is one, a black canvas for non-RGB modes
+        (of the size the draft left) → uint8 (H,W,3) array."""
+        if draft is not None:
+            pil.draft("RGB", draft)
+        if pil.mode != "RGB":
+            pil = Image.new("RGB", pil.size)
+        return np.asarray(pil, dtype=np.uint8)
 
     # ---------------------------------------------------------------------------------------------------------
     # device JPEG decode
@@ -161,12 +169,10 @@ class DevicePreprocessor:
         if H * W * 3 > self.max_bytes:
             raise RuntimeError(f"image {H}x{W} exceeds the staging buffers ({self.max_bytes} bytes)")
 
-    def _host_rgb(self, blob) -> np.ndarray:
-        """The host path for one file: PIL decode (black canvas for non-RGB modes) → uint8 (H,W,3) array."""
-        pil = Image.open(io.BytesIO(blob))
-        if pil.mode != "RGB":
-            pil = Image.new("RGB", pil.size)
-        return np.asarray(pil, dtype=np.uint8)
+    def _host_rgb(self, blob, draft=None) -> np.ndarray:
+        """The host path for one file: PIL decode, after `im.draft("RGB", draft)` if there is a draft request (black
+        canvas for non-RGB modes, of the drafted size) → uint8 (H,W,3) array."""
+        return self._pil_rgb(Image.open(io.BytesIO(blob)), draft)
 
     @staticmethod
     def _grow(buf, nbytes, **kw):
@@ -181,16 +187,25 @@ class DevicePreprocessor:
         take), "host-after-status" (the device reported status 1 and PIL decoded the file again) or "black"."""
         return tuple(self._jpeg_routes)
 
-    def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host"):
+    def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host",
+                    draft=None):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
         np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path).  Baseline JPEGs are
         decoded by odic_jpeg_decode and, with progressive="device", progressive ones by odic_jpeg_decode_progressive
         (the default "host" sends them to PIL until the device route is measured faster), each kind in one batched call, with one host-to-device copy and one status read-back
         for both; the rest, and images the device rejects, by PIL.  Exceptions are the host path's, in its order: PIL's,
-        file by file, then the size check of `__call__`.  Ordered after the work on the CURRENT stream."""
+        file by file, then the size check of `__call__`.  Ordered after the work on the CURRENT stream.
+        draft=(width, height): every file is decoded as after `im.draft("RGB", draft)`, at 1/2, 1/4 or 1/8 of its size
+        while both sides stay at least the requested ones (`jpeg.draft_scale`), by odic_jpeg_decode_scaled /
+        odic_jpeg_decode_progressive_scaled or by PIL with the same request; sizes, black canvases and the size check
+        are those of the drafted image."""
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
+        if draft is not None:
+            draft = (int(draft[0]), int(draft[1]))
+            if draft[0] <= 0 or draft[1] <= 0:
+                raise ValueError(f"draft wants a positive (width, height), not {draft!r}")
         blobs = [bytes(b) for b in blobs]
         hdrs = [J.parse(b) for b in blobs]
         if progressive == "device":
@@ -201,9 +216,12 @@ class DevicePreprocessor:
                         hdrs[i] = ph
         out = [None] * len(blobs)
         routes = [h.kind for h in hdrs]
+        scales = [J.draft_scale((h.width, h.height), draft) if draft is not None and h.kind != J.HOST else 1
+                  for h in hdrs]
+        sizes = [J.scaled_size((h.width, h.height), s) for h, s in zip(hdrs, scales)]        # (width, height)
         # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
         dev = [i for i, h in enumerate(hdrs)
-               if h.kind == J.DEVICE and h.width * h.height * 3 <= self.max_bytes]
+               if h.kind == J.DEVICE and sizes[i][0] * sizes[i][1] * 3 <= self.max_bytes]
         base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader)]
         prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader)]
         for i, h in enumerate(hdrs):
@@ -217,46 +235,53 @@ class DevicePreprocessor:
             order = base + prog
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
                                                            [hdrs[i] for i in prog], [blobs[i] for i in prog],
-                                                           subseq_bits, max_sync_passes)
+                                                           subseq_bits, max_sync_passes, [scales[i] for i in order])
             for k, i in enumerate(order):
-                h = hdrs[i]
                 if status[k] == 0:
-                    n = h.width * h.height * 3
-                    out[i] = rgb[out_offs[k]:out_offs[k] + n].view(h.height, h.width, 3)
+                    w, h = sizes[i]
+                    out[i] = rgb[out_offs[k]:out_offs[k] + w * h * 3].view(h, w, 3)
                 else:
                     routes[i] = "host-after-status"
         self._jpeg_routes = routes
         for i, h in enumerate(hdrs):                                     # input order, as the host path
             if h.kind != J.BLACK and out[i] is None:
-                out[i] = self._host_rgb(blobs[i])
+                out[i] = self._host_rgb(blobs[i], draft)
         for i, h in enumerate(hdrs):
             if h.kind == J.BLACK:
-                self._check_size(h.height, h.width)
-                out[i] = torch.zeros(h.height, h.width, 3, dtype=torch.uint8, device=self.device)
+                self._check_size(sizes[i][1], sizes[i][0])
+                out[i] = torch.zeros(sizes[i][1], sizes[i][0], 3, dtype=torch.uint8, device=self.device)
             else:
                 self._check_size(out[i].shape[0], out[i].shape[1])
                 if isinstance(out[i], np.ndarray):
                     out[i] = torch.from_numpy(out[i].copy()).to(self.device)
         return out
 
-    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes):
+    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales=None):
         """One odic_jpeg_decode call for the baseline files and one odic_jpeg_decode_progressive call for the progressive
         ones, sharing one upload, one output buffer, one workspace and one status read-back → (status numpy int32 —
-        baseline files first —, uint8 RGB buffer, byte offset per image)."""
+        baseline files first —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
+        baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales
+        uploaded beside the headers."""
         from . import jpeg as J
 
         def pad(n):
             return (n + 255) // 256 * 256
 
         nb, npg = len(hdrs), len(phdrs)
+        scales = list(scales) if scales else [1] * (nb + npg)
+        scaled_b, scaled_p = any(s > 1 for s in scales[:nb]), any(s > 1 for s in scales[nb:])
         offs, ends, poffs = [], [], []
         sections, pos = [], 0                                            # (staging offset, record array)
         if nb:
             pos = pad(nb * J.HEADER_DTYPE.itemsize)
         if npg:
-            prec, srec, trec, ptot, pout_offs, pout_bytes = J.pack_progressive(phdrs, [0] * npg)   # sizes only, for now
+            prec, srec, trec, ptot, pout_offs, pout_bytes = J.pack_progressive(phdrs, [0] * npg, scales[nb:])   # sizes only, for now
             prog_off = (pos, pos + pad(prec.nbytes), pos + pad(prec.nbytes) + pad(srec.nbytes))
             pos = prog_off[2] + pad(trec.nbytes)
+        if scaled_b or scaled_p:                                         # int32 scale_log2 [nb + npg]
+            scale_off = pos
+            sections.append((pos, np.asarray([s.bit_length() - 1 for s in scales], np.int32)))
+            pos += pad(4 * (nb + npg))
         data_off = pos
         pos = 0
         for h, blob in zip(hdrs, blobs):
@@ -269,7 +294,7 @@ class DevicePreprocessor:
         total = data_off + pos
         out_offs, out_bytes = [], 0
         if nb:
-            rec, tot, out_offs, out_bytes = J.pack_headers(hdrs, offs, ends, subseq_bits)
+            rec, tot, out_offs, out_bytes = J.pack_headers(hdrs, offs, ends, subseq_bits, scales[:nb])
             sections.append((0, rec))
         if npg:
             srec["data_off"] += np.asarray(poffs, np.int64)[srec["image"]]
@@ -316,14 +341,24 @@ class DevicePreprocessor:
             base = self._jpeg_dev.data_ptr()
             if nb:
                 b.headers, b.data, b.out, b.status = base, base + data_off, rgb.data_ptr(), status.data_ptr()
-                self._hip.check(self.lib.odic_jpeg_decode(ctypes.byref(b), self._jpeg_ws.data_ptr(), need_b,
-                                                          self.stream.cuda_stream), "odic_jpeg_decode")
+                if scaled_b:
+                    self._hip.check(self.lib.odic_jpeg_decode_scaled(
+                        ctypes.byref(b), base + scale_off, self._jpeg_ws.data_ptr(), need_b, self.stream.cuda_stream),
+                        "odic_jpeg_decode_scaled")
+                else:
+                    self._hip.check(self.lib.odic_jpeg_decode(ctypes.byref(b), self._jpeg_ws.data_ptr(), need_b,
+                                                              self.stream.cuda_stream), "odic_jpeg_decode")
             if npg:                                                      # second: its coefficients stay in the workspace
                 pb.headers, pb.scans, pb.tables = (base + o for o in prog_off)
                 pb.data, pb.out, pb.status = base + data_off, rgb.data_ptr() + out_bytes, status.data_ptr() + 4 * nb
-                self._hip.check(self.lib.odic_jpeg_decode_progressive(ctypes.byref(pb), self._jpeg_ws.data_ptr(), need_p,
-                                                                      self.stream.cuda_stream),
-                                "odic_jpeg_decode_progressive")
+                if scaled_p:
+                    self._hip.check(self.lib.odic_jpeg_decode_progressive_scaled(
+                        ctypes.byref(pb), base + scale_off + 4 * nb, self._jpeg_ws.data_ptr(), need_p,
+                        self.stream.cuda_stream), "odic_jpeg_decode_progressive_scaled")
+                else:
+                    self._hip.check(self.lib.odic_jpeg_decode_progressive(
+                        ctypes.byref(pb), self._jpeg_ws.data_ptr(), need_p, self.stream.cuda_stream),
+                        "odic_jpeg_decode_progressive")
                 self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(pb)),
                                         [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])])
             st = self._jpeg_status[:4 * (nb + npg)].view(torch.int32)
@@ -340,10 +375,11 @@ class DevicePreprocessor:
         return self._jpeg_ws[lo:hi].view(torch.int16).view(-1, 64).clone()
 
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
-                        progressive: str = "host") -> torch.Tensor:
+                        progressive: str = "host", draft: bool = False) -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
-        torch.equal to `from_files` on the same files."""
-        imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive)
+        torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`)."""
+        imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
+                                draft=(self.S, self.S) if draft else None)
         S = self.S
         out = torch.empty(len(imgs), 3, S, S, dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream())

@@ -329,9 +329,26 @@ def n_intervals(h: JpegHeader) -> int:
     return -(-total // r)
 
 
-def _place_image(r, h, tot, out_offs, out_bytes):
+def draft_scale(size, requested) -> int:
+    """The scale Pillow's `Image.draft(mode, requested)` picks for a JPEG of `size` (both (width, height)):
+    the largest of 8, 4, 2, 1 that does not exceed min(width // req_w, height // req_h)."""
+    scale = min(size[0] // requested[0], size[1] // requested[1])
+    return next((s for s in (8, 4, 2) if scale >= s), 1)
+
+
+def scaled_size(size, scale):
+    """(width, height) a frame of `size` decodes to at 1 / scale: what `im.size` becomes after the draft."""
+    return (size[0] + scale - 1) // scale, (size[1] + scale - 1) // scale
+
+
+def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     """The per-image part of both packers: geometry, quantisation tables and the output / coefficient / plane offsets
-    into record r, the running totals and maxima into tot → (MCUs, output bytes after this image)."""
+    into record r, the running totals and maxima into tot → (MCUs, output bytes after this image).  The record keeps
+    the frame's own geometry, which the entropy decoders need; the output bytes and the maxima that size the colour
+    launch are those of the frame decoded at 1 / scale (odic_jpeg_decode_scaled)."""
+    if scale not in (1, 2, 4, 8):
+        raise ValueError(f"scale must be 1, 2, 4 or 8, not {scale!r}")
+    width, height = scaled_size((h.width, h.height), scale)
     nmcu = h.mcus_x * h.mcus_y
     blocks = nmcu * BLOCKS_PER_MCU[h.sampling]
     r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
@@ -342,16 +359,17 @@ def _place_image(r, h, tot, out_offs, out_bytes):
     out_offs.append(out_bytes)
     tot["total_blocks"] += blocks
     tot["total_plane_bytes"] += (blocks * 64 + 15) // 16 * 16
-    tot["max_width"] = max(tot["max_width"], h.width)
-    tot["max_height"] = max(tot["max_height"], h.height)
+    tot["max_width"] = max(tot["max_width"], width)
+    tot["max_height"] = max(tot["max_height"], height)
     tot["max_blocks"] = max(tot["max_blocks"], blocks)
-    return nmcu, out_bytes + h.width * h.height * 3
+    return nmcu, out_bytes + width * height * 3
 
 
-def pack_headers(hdrs, data_offs, data_ends, subseq_bits):
+def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None):
     """Header records + workspace totals for a batch of device-kind headers.
     data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
-    buffer.  → (np array HEADER_DTYPE [n], dict of batch totals / maxima, list of output byte offsets)."""
+    buffer.  scales: 1, 2, 4 or 8 per image (None: all 1), the draft scale its output is placed for.
+    → (np array HEADER_DTYPE [n], dict of batch totals / maxima, list of output byte offsets, output bytes)."""
     n = len(hdrs)
     rec = np.zeros(n, HEADER_DTYPE)
     tot = dict(total_scan_bytes=0, total_intervals=0, total_units=0, total_blocks=0, total_plane_bytes=0,
@@ -362,7 +380,7 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits):
         scan = data_ends[k] - data_offs[k]
         nint = n_intervals(h)
         units = -(-scan * 8 // subseq_bits) + nint
-        nmcu, out_bytes = _place_image(r, h, tot, out_offs, out_bytes)
+        nmcu, out_bytes = _place_image(r, h, tot, out_offs, out_bytes, scales[k] if scales else 1)
         r["data_off"], r["data_end"], r["scan_off"] = data_offs[k], data_ends[k], tot["total_scan_bytes"]
         r["int_off"], r["unit_off"] = tot["total_intervals"], tot["total_units"]
         r["restart"] = h.restart_interval or nmcu
@@ -553,10 +571,10 @@ def _dependency_levels(scans):
         sc.level = lvl + 1
 
 
-def pack_progressive(hdrs, blob_offs):
+def pack_progressive(hdrs, blob_offs, scales=None):
     """Header, scan and table records + batch totals for progressive headers whose files start at blob_offs inside
     the batch's data buffer.  Scans are sorted by level (stable), which is how odic_jpeg_decode_progressive walks
-    them.  → (headers PROG_HEADER_DTYPE [n], scans SCAN_DTYPE [m], tables TABLE_DTYPE [t], totals dict with
+    them.  scales: as `pack_headers`.  → (headers PROG_HEADER_DTYPE [n], scans SCAN_DTYPE [m], tables TABLE_DTYPE [t], totals dict with
     level_first / level_intervals lists, output byte offsets, output bytes)."""
     n = len(hdrs)
     rec = np.zeros(n, PROG_HEADER_DTYPE)
@@ -573,7 +591,7 @@ def pack_progressive(hdrs, blob_offs):
         return table_ix[key]
 
     for k, h in enumerate(hdrs):
-        _, out_bytes = _place_image(rec[k], h, tot, out_offs, out_bytes)
+        _, out_bytes = _place_image(rec[k], h, tot, out_offs, out_bytes, scales[k] if scales else 1)
         rec[k]["n_intervals"] = sum(s.n_intervals for s in h.scans)
         flat += [(s.level, k, s) for s in h.scans]
     flat.sort(key=lambda x: x[0])

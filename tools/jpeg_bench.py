@@ -14,10 +14,22 @@ size; the two results are checked torch.equal first.  One JSON line per batch si
 --progressive: the same crops saved with progressive=True (libjpeg's standard ten-scan script), for which the host
 path is what every progressive file took before odic_jpeg_decode_progressive; then tatin.jpg itself (1280x960), alone
 and as a batch of copies; and the cost of jpeg.parse_progressive per file.
+
+--draft: what decoding at the scale `Image.draft("RGB", (S, S))` picks saves.  Seeded synthetic JPEGs,
+3456x4608 (drafts at 1/8) and 640x480 (drafts at 1/1: the control), 4:2:0 and 4:4:4, baseline and progressive; per
+case `decode_jpeg` alone and `from_jpeg_bytes` (decode + resize), draft off and on alternating in the same process,
+median / quartiles / min over --iters.  The drafted pixels are checked against Pillow's first.  The per-kernel split
+comes from a profiler run of its own (tools/jpeg_sync_stats.py is a CPU model of the synchronisation and times no
+kernel), in which the scaled kernels carry their own names; profiles/r11_jpeg_draft_kernel_stats.txt is its table:
+
+    python tools/jpeg_bench.py --draft --iters 15 --warmup 3 --out profiles/r11_jpeg_draft_bench.json
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/jpeg_bench.py --draft --device-only --draft-cases large \
+        --iters 4 --warmup 1
 """
 from __future__ import annotations
 
 import argparse
+import functools
 import io
 import json
 import os
@@ -48,6 +60,86 @@ def make_inputs(n: int, seed: int = 0, progressive: bool = False):
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def synthetic_rgb(h: int, w: int, seed: int) -> np.ndarray:
+    """A seeded image with a photograph's spectrum, roughly: smooth fields at three scales plus sensor-like noise."""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    img = np.zeros((h, w, 3), np.float32)
+    for div, amp in ((64, 70.0), (16, 30.0), (4, 12.0)):
+        small = rng.normal(0, 1, (max(h // div, 2), max(w // div, 2), 3)).astype(np.float32)
+        for c in range(3):
+            img[:, :, c] += amp * np.asarray(Image.fromarray(small[:, :, c]).resize((w, h), Image.BICUBIC))
+    img += 128 + rng.normal(0, 3, img.shape).astype(np.float32)
+    return np.clip(img, 0, 255).astype(np.uint8)
+
+
+DRAFT_CASES = [(size, batch, sub, prog) for size, batch in (((3456, 4608), 4), ((640, 480), 16))
+               for sub in (2, 0) for prog in (False, True)]
+
+
+def draft_bench(args):
+    """Draft off against draft on: the same build, the same files, alternating."""
+    import torch
+    from PIL import Image
+    from on_device_image_captioning_amd import jpeg as J
+    from on_device_image_captioning_amd.image_utils import DevicePreprocessor
+    assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
+    S = args.size
+    pre = DevicePreprocessor(S, "cuda:0")
+    lines = []
+    for (w, h), B, sub, prog in DRAFT_CASES:
+        if args.draft_cases == "large" and w < 1000:
+            continue
+        blobs = []
+        for k in range(B):
+            buf = io.BytesIO()
+            Image.fromarray(synthetic_rgb(h, w, seed=k)).save(buf, format="JPEG", quality=90, subsampling=sub,
+                                                              progressive=prog)
+            blobs.append(buf.getvalue())
+        route = "device" if prog else "host"
+        fns = {"decode": lambda d: pre.decode_jpeg(blobs, progressive=route, draft=(S, S) if d else None),
+               "decode_resize": lambda d: pre.from_jpeg_bytes(blobs, progressive=route, draft=d)}
+        if args.device_only:
+            for _ in range(args.warmup + args.iters):
+                for d in (False, True):
+                    fns["decode_resize"](d)
+            torch.cuda.synchronize()
+            continue
+        scale = J.draft_scale((w, h), (S, S))
+        im = Image.open(io.BytesIO(blobs[0]))
+        im.draft("RGB", (S, S))
+        got = fns["decode"](True)[0]
+        assert pre.last_routes == ("device-progressive" if prog else "device",) * B, pre.last_routes
+        assert torch.equal(got.cpu(), torch.from_numpy(np.asarray(im).copy())), "drafted decode differs from Pillow"
+        line = {"width": w, "height": h, "batch": B, "quality": 90, "subsampling": {2: "4:2:0", 0: "4:4:4"}[sub],
+                "progressive": prog, "draft_scale": scale, "drafted_size": list(J.scaled_size((w, h), scale)),
+                "mean_jpeg_bytes": int(np.mean([len(b) for b in blobs])), "iters": args.iters,
+                "gpu": torch.cuda.get_device_name(0)}
+        for name, fn in fns.items():
+            for _ in range(args.warmup):
+                fn(False)
+                fn(True)
+            torch.cuda.synchronize()
+            t = {False: [], True: []}
+            for _ in range(args.iters):
+                for d in (False, True):
+                    t0 = time.perf_counter()
+                    fn(d)
+                    torch.cuda.synchronize()
+                    t[d].append(1e3 * (time.perf_counter() - t0))
+            for d, key in ((False, "full"), (True, "draft")):
+                q1, med, q3 = (float(x) for x in np.percentile(t[d], [25, 50, 75]))
+                line[f"{name}_{key}_ms"] = {"median": med, "q1": q1, "q3": q3, "min": float(min(t[d]))}
+            line[f"{name}_full_over_draft"] = line[f"{name}_full_ms"]["median"] / line[f"{name}_draft_ms"]["median"]
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.out and lines:
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 64])
@@ -57,8 +149,12 @@ def main():
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--sweep", action="store_true", help="also time the device path at other subseq_bits / passes")
     ap.add_argument("--progressive", action="store_true", help="progressive re-saves of the crops, and tatin.jpg")
+    ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
+    ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.draft:
+        return draft_bench(args)
 
     import torch
     from PIL import Image
