@@ -52,8 +52,9 @@ extern "C" {
 
 /* ABI version of this header; bumped on any signature change.
  *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step).
- *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale). */
-#define ODIC_ABI_VERSION 21
+ *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale).
+ *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)). */
+#define ODIC_ABI_VERSION 22
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -185,6 +186,44 @@ int odic_resize_bilinear_normalize(const uint8_t* src_rgb, int32_t H, int32_t W,
                                    const int32_t* bounds_y, const int32_t* coef_y, int32_t ksize_y,
                                    uint8_t* tmp, float* dst, int32_t out_size, const float* mean3,
                                    const float* std3, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same resize + normalise for N regions of any of several images in one call, bit-exact with
+ * PIL.Image.resize((S, S), BILINEAR, box=(l, t, r, b)) (float boxes) followed by the same fp32 arithmetic.  One job per
+ * region, packed by on_device_image_captioning_amd.image_utils.pack_resize_jobs, which also validates the geometry: the
+ * records live in device memory and are not checked here.  The tap tables of an axis are those of
+ * image_utils.pil_bilinear_coeffs_box(in_size, in0, in1, S): windows clipped to the IMAGE, not to the box, so the pixels
+ * just outside a box contribute at its edges, as in Pillow.
+ *   src_off             byte offset of the source image (its pixel (0, 0)) from src_base: images decoded by one
+ *                       odic_jpeg_decode call share one RGB buffer, other sets are gathered into one first
+ *   src_pitch           bytes from one source row to the next (>= 3 W)
+ *   tmp_off             byte offset of the job's n_rows x S x 3 slice of tmp (the horizontally resampled rows)
+ *   H, W                size of the source image
+ *   row_first, n_rows   the source rows the vertical taps of the box touch, [row_first, row_first + n_rows): the first
+ *                       tap of output row 0 to the last tap of output row S - 1; only these are resampled horizontally
+ *   bounds_x, bounds_y  int32 index in bounds_pool of the axis's [S, 2] (first tap, tap count) table; the y table holds
+ *                       source rows of the image (the kernel subtracts row_first), so a table can serve several jobs
+ *   coef_x, coef_y      int32 index in coef_pool of the axis's [S, ksize] fixed-point (2^22) weights
+ *   ksize_x, ksize_y    row length of those weight tables
+ * ------------------------------------------------------------------------------------------- */
+typedef struct odic_resize_job {
+  int64_t src_off, src_pitch, tmp_off;
+  int32_t H, W, row_first, n_rows;
+  int32_t bounds_x, coef_x, bounds_y, coef_y;
+  int32_t ksize_x, ksize_y;
+} odic_resize_job;
+
+/* jobs, src_base, bounds_pool, coef_pool, tmp, dst are DEVICE pointers; mean3 / std3 HOST pointers to 3 floats.  Job j
+ * writes dst[j] = fp32 [3, S, S] (S = out_size).  Two launches for any n_jobs, on `stream`, no allocation, no host
+ * synchronisation, capturable: the horizontal pass on a grid of (ceil(S / 256), max_rows, n_jobs) blocks (max_rows: the
+ * largest n_rows of the jobs; rows at or beyond a job's n_rows exit) and the vertical pass + normalise on
+ * (ceil(S / 256), S, n_jobs).  Exactly n_jobs·3·S·S floats of dst are written and at most tmp_bytes of tmp: a job whose
+ * tmp slice would end behind tmp_bytes is skipped (test_resize_boxes_containment).  ODIC_ENULL for a null pointer;
+ * ODIC_EINVAL for n_jobs outside 1..65535, out_size or max_rows outside 1..65535, or tmp_bytes below one row (3·S). */
+int odic_resize_boxes_normalize(const odic_resize_job* jobs, int32_t n_jobs, const uint8_t* src_base,
+                                const int32_t* bounds_pool, const int32_t* coef_pool, uint8_t* tmp, size_t tmp_bytes,
+                                float* dst, int32_t out_size, int32_t max_rows, const float* mean3, const float* std3,
+                                void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched JPEG decode on the device, baseline files here and progressive ones below (utils/image_utils.py:7, PIL_Image.open), bit-exact with

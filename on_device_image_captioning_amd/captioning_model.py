@@ -503,3 +503,20 @@ class Captioner:
             if key in b:
                 k.setdefault(arg, b[key])
         return self.model.word_attention(enc_x, captions, *a, **k)
+
+    def caption_regions(self, preprocessor, images, regions):
+        """Captions of parts of pictures that live on the device: `preprocessor.resize_regions(images, regions)` (a
+        DevicePreprocessor of the model's input size; images: uint8 (H,W,3) device tensors as its `decode_jpeg` returns
+        them; regions: sequence of (image index, (l, t, r, b)), the box as PIL's `resize(..., box=)` takes it), then
+        this object's encode and search on that batch (`__call__`).  Returns one list per input image,
+        holding a grounding.RegionCaption for each of its regions in the order they were given; an image without a
+        region gets an empty list."""
+        regions = [(int(i), tuple(float(v) for v in box)) for i, box in regions]
+        per_image = [[] for _ in images]
+        if not regions:
+            return per_image
+        batch = preprocessor.resize_regions(images, regions)
+        toks, lps = self(batch, enc_x_num_pads=[0] * len(regions))
+        for n, (i, box) in enumerate(regions):
+            per_image[i].append(_grounding.RegionCaption(region=n, box=box, tokens=toks[n], logprobs=lps[n]))
+        return per_image

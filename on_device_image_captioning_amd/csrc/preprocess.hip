@@ -60,6 +60,62 @@ __global__ __launch_bounds__(256) void resize_v_norm_kernel(const unsigned char*
   dst[2 * plane + o] = (__fdiv_rn((float)clip8(a2), 255.0f) - m2) / s2;
 }
 
+// The two passes above over a job list (odic_resize_job, one per region): blockIdx.z is the job, the horizontal pass runs
+// over the job's n_rows source rows from row_first only, the vertical one reads tmp rows relative to row_first.  A job
+// whose tmp slice would end behind tmp_bytes is skipped by both passes.
+__device__ __forceinline__ bool job_fits(const odic_resize_job& j, int out, unsigned long tmp_bytes) {
+  return j.tmp_off >= 0 && (unsigned long)j.tmp_off + (unsigned long)j.n_rows * out * 3 <= tmp_bytes;
+}
+
+__global__ __launch_bounds__(256) void resize_boxes_h_kernel(const odic_resize_job* __restrict__ jobs,
+                                                             const unsigned char* __restrict__ src_base,
+                                                             const int* __restrict__ bounds_pool,
+                                                             const int* __restrict__ coef_pool,
+                                                             unsigned char* __restrict__ tmp_base,
+                                                             unsigned long tmp_bytes, int out) {
+  const odic_resize_job j = jobs[blockIdx.z];
+  const int xx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (xx >= out || y >= j.n_rows || !job_fits(j, out, tmp_bytes)) return;
+  const int* bounds = bounds_pool + j.bounds_x;
+  const int x0 = bounds[2 * xx], n = bounds[2 * xx + 1];
+  const int* k = coef_pool + j.coef_x + (long)xx * j.ksize_x;
+  const unsigned char* p = src_base + j.src_off + (long)(j.row_first + y) * j.src_pitch + 3L * x0;
+  int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+  for (int i = 0; i < n; ++i) {
+    const int w = k[i];
+    a0 += p[3 * i] * w; a1 += p[3 * i + 1] * w; a2 += p[3 * i + 2] * w;
+  }
+  unsigned char* q = tmp_base + j.tmp_off + ((long)y * out + xx) * 3;
+  q[0] = clip8(a0); q[1] = clip8(a1); q[2] = clip8(a2);
+}
+
+__global__ __launch_bounds__(256) void resize_boxes_v_norm_kernel(const odic_resize_job* __restrict__ jobs,
+                                                                  const int* __restrict__ bounds_pool,
+                                                                  const int* __restrict__ coef_pool,
+                                                                  const unsigned char* __restrict__ tmp_base,
+                                                                  unsigned long tmp_bytes, float* __restrict__ dst_base,
+                                                                  int out, float m0, float m1, float m2, float s0,
+                                                                  float s1, float s2) {
+  const odic_resize_job j = jobs[blockIdx.z];
+  const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
+  if (xx >= out || !job_fits(j, out, tmp_bytes)) return;
+  const int* bounds = bounds_pool + j.bounds_y;
+  const int y0 = bounds[2 * yy] - j.row_first, n = bounds[2 * yy + 1];
+  const int* k = coef_pool + j.coef_y + (long)yy * j.ksize_y;
+  const unsigned char* p = tmp_base + j.tmp_off + ((long)y0 * out + xx) * 3;
+  int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+  for (int i = 0; i < n; ++i) {
+    const int w = k[i];
+    const unsigned char* r = p + (long)i * out * 3;
+    a0 += r[0] * w; a1 += r[1] * w; a2 += r[2] * w;
+  }
+  const long plane = (long)out * out, o = (long)yy * out + xx;
+  float* dst = dst_base + 3 * plane * blockIdx.z;
+  dst[o] = (__fdiv_rn((float)clip8(a0), 255.0f) - m0) / s0;
+  dst[plane + o] = (__fdiv_rn((float)clip8(a1), 255.0f) - m1) / s1;
+  dst[2 * plane + o] = (__fdiv_rn((float)clip8(a2), 255.0f) - m2) / s2;
+}
+
 }  // namespace
 
 extern "C" int odic_resize_bilinear_normalize(const uint8_t* src_rgb, int32_t H, int32_t W, int64_t src_stride_bytes,
@@ -77,5 +133,25 @@ extern "C" int odic_resize_bilinear_normalize(const uint8_t* src_rgb, int32_t H,
                      bounds_x, coef_x, ksize_x, tmp, out_size);
   hipLaunchKernelGGL(resize_v_norm_kernel, dim3((out_size + 255) / 256, out_size), block, 0, s, tmp, bounds_y, coef_y,
                      ksize_y, dst, out_size, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  return odic_launch_status();
+}
+
+static_assert(sizeof(odic_resize_job) == 64, "odic_resize_job is packed by image_utils.RESIZE_JOB_DTYPE");
+
+extern "C" int odic_resize_boxes_normalize(const odic_resize_job* jobs, int32_t n_jobs, const uint8_t* src_base,
+                                           const int32_t* bounds_pool, const int32_t* coef_pool, uint8_t* tmp,
+                                           size_t tmp_bytes, float* dst, int32_t out_size, int32_t max_rows,
+                                           const float* mean3, const float* std3, void* stream) {
+  if (!jobs || !src_base || !bounds_pool || !coef_pool || !tmp || !dst || !mean3 || !std3) return ODIC_ENULL;
+  if (n_jobs <= 0 || n_jobs > 65535 || out_size <= 0 || out_size > 65535 || max_rows <= 0 || max_rows > 65535 ||
+      tmp_bytes < 3UL * out_size)
+    return ODIC_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 block(256);
+  hipLaunchKernelGGL(resize_boxes_h_kernel, dim3((out_size + 255) / 256, max_rows, n_jobs), block, 0, s, jobs, src_base,
+                     bounds_pool, coef_pool, tmp, (unsigned long)tmp_bytes, out_size);
+  hipLaunchKernelGGL(resize_boxes_v_norm_kernel, dim3((out_size + 255) / 256, out_size, n_jobs), block, 0, s, jobs,
+                     bounds_pool, coef_pool, tmp, (unsigned long)tmp_bytes, dst, out_size, mean3[0], mean3[1], mean3[2],
+                     std3[0], std3[1], std3[2]);
   return odic_launch_status();
 }

@@ -1,5 +1,6 @@
 """Host-side pieces of word grounding: the result object of `word_attention` (per-word cross-attention maps over the
-encoder positions) and the parsing of its `layers` / `heads` arguments.
+encoder positions), the parsing of its `layers` / `heads` arguments, and the way back from a grid cell to a box of the
+source image (`source_box`) for `Captioner.caption_regions`.
 
 Nothing here touches the GPU; the probabilities come from CaptionerEngine.decode_sequence(attn=...)
 (odic_cross_attn_probs).
@@ -47,6 +48,36 @@ def parse_heads(heads) -> bool:
     if isinstance(heads, str) and heads in ("mean", "all"):
         return heads == "all"
     raise ValueError(f"heads must be 'mean' or 'all', not {heads!r}")
+
+
+def source_box(box, from_size: Union[int, Tuple[int, int]],
+               image_size: Union[int, Tuple[int, int]]) -> Tuple[float, float, float, float]:
+    """A (x0, y0, x1, y1) box in an image of `from_size` — what `WordAttention.cell_box(idx, from_size)` returns for the
+    model's input size — as the float (l, t, r, b) box of the same area in the source image of `image_size` (sizes are an
+    int, or (height, width)): the box `DevicePreprocessor.resize_regions` and `Captioner.caption_regions` take.
+    "Caption what word t of caption n looked at", for `images = pre.decode_jpeg(blobs)` and their batch
+    `x = pre.from_jpeg_bytes(blobs)`:
+
+        wa = captioner.word_attention(x)
+        box = source_box(wa.cell_box(wa.peak_cells()[n, t], pre.S), pre.S, images[n].shape[:2])
+        tokens = captioner.caption_regions(pre, images, [(n, box)])[n][0].tokens
+    """
+    fh, fw = (from_size, from_size) if isinstance(from_size, int) else (int(from_size[0]), int(from_size[1]))
+    H, W = (image_size, image_size) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
+    x0, y0, x1, y1 = (float(v) for v in box)
+    if fh <= 0 or fw <= 0 or H <= 0 or W <= 0 or not (0 <= x0 < x1 <= fw and 0 <= y0 < y1 <= fh):
+        raise ValueError(f"box {tuple(box)!r} does not lie in a {fw} x {fh} image")
+    return (x0 * W / fw, y0 * H / fh, x1 * W / fw, y1 * H / fh)
+
+
+@dataclass
+class RegionCaption:
+    """One region of `Captioner.caption_regions`: its position in the `regions` argument, its box, the captions the
+    search returned for it (best first) and their per-token log-probabilities [how_many_outputs, Tmax]."""
+    region: int
+    box: Tuple[float, float, float, float]
+    tokens: List[List[int]]
+    logprobs: torch.Tensor
 
 
 @dataclass

@@ -46,12 +46,24 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
     """Tap windows and fixed-point weights of PIL's BILINEAR resampler for one axis, computed exactly as
     libImaging/Resample.c::precompute_coeffs + normalize_coeffs_8bpc do (double arithmetic, taps summed in
     order): → (bounds int32 [out, 2] = first tap / tap count, coeffs int32 [out, ksize], ksize)."""
-    scale = in_size / out_size
+    return pil_bilinear_coeffs_box(in_size, 0, in_size, out_size)
+
+
+def pil_bilinear_coeffs_box(in_size: int, in0: float, in1: float, out_size: int):
+    """The same for the span [in0, in1) of an axis of in_size pixels: one axis of `Image.resize(size, BILINEAR, box=)`.
+    Pillow carries the box as C floats: both ends are rounded to float32 and their difference is taken in float32,
+    everything after that is double.  The tap windows are clipped to the image, not to the box, so pixels just outside
+    the box contribute at its edges.  ValueError unless 0 <= in0 < in1 <= in_size (after the rounding)."""
+    in_size, out_size = int(in_size), int(out_size)
+    f0, f1 = np.float32(in0), np.float32(in1)
+    if not (0 <= f0 < f1 <= in_size) or out_size <= 0:
+        raise ValueError(f"box span [{in0}, {in1}) must satisfy 0 <= start < end <= {in_size}")
+    scale = float(f1 - f0) / out_size
     filterscale = max(scale, 1.0)
     support = 1.0 * filterscale                              # bilinear filter support = 1
     ksize = int(np.ceil(support)) * 2 + 1
     xx = np.arange(out_size, dtype=np.float64)
-    center = (xx + 0.5) * scale
+    center = float(f0) + (xx + 0.5) * scale
     xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # C (int) cast: truncation, values >= -0.5
     xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
     n = xmax - xmin
@@ -68,6 +80,66 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
     fixed = np.where(taps < n[:, None], fixed, 0).astype(np.int32)
     bounds = np.stack([xmin, n], axis=1).astype(np.int32)
     return bounds, fixed, ksize
+
+
+#: odic_resize_job (include/odic_hip.h), field for field
+RESIZE_JOB_DTYPE = np.dtype([("src_off", "<i8"), ("src_pitch", "<i8"), ("tmp_off", "<i8"), ("H", "<i4"), ("W", "<i4"),
+                             ("row_first", "<i4"), ("n_rows", "<i4"), ("bounds_x", "<i4"), ("coef_x", "<i4"),
+                             ("bounds_y", "<i4"), ("coef_y", "<i4"), ("ksize_x", "<i4"), ("ksize_y", "<i4")])
+MAX_RESIZE_JOBS = 65535                                       # one grid z index per job
+
+
+def pack_resize_jobs(jobs, out_size: int):
+    """jobs: sequence of (src_off, H, W, src_pitch, (l, t, r, b)) — the byte offset of an RGB8 image in one buffer, its
+    size and row pitch in bytes, and a box as `Image.resize` takes it → (records RESIZE_JOB_DTYPE [N], bounds pool
+    int32, coefficient pool int32, tmp_bytes, max_rows) for odic_resize_boxes_normalize.  Axes with the same
+    (in_size, in0, in1) after the float32 rounding share one table in the pools.  This is where the geometry is
+    validated (the kernel trusts the records): ValueError for a box outside 0 <= l < r <= W, 0 <= t < b <= H, a pitch
+    below 3 W or a negative offset."""
+    S = int(out_size)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"out_size must lie in 1..65535, not {out_size}")
+    if len(jobs) > MAX_RESIZE_JOBS:
+        raise ValueError(f"at most {MAX_RESIZE_JOBS} regions per call, not {len(jobs)}")
+    rec = np.zeros(len(jobs), RESIZE_JOB_DTYPE)
+    axes, bounds, coefs = {}, [], []
+    n_bounds = n_coefs = 0
+
+    def axis(in_size, in0, in1):
+        nonlocal n_bounds, n_coefs
+        key = (in_size, float(np.float32(in0)), float(np.float32(in1)))
+        if key not in axes:
+            b, k, ks = pil_bilinear_coeffs_box(in_size, in0, in1, S)
+            axes[key] = (n_bounds, n_coefs, ks, int(b[0, 0]), int(b[-1, 0] + b[-1, 1]))
+            bounds.append(b.reshape(-1))
+            coefs.append(k.reshape(-1))
+            n_bounds += b.size
+            n_coefs += k.size
+        return axes[key]
+
+    tmp_bytes = max_rows = 0
+    for r, (src_off, H, W, pitch, box) in zip(rec, jobs):
+        src_off, H, W, pitch = int(src_off), int(H), int(W), int(pitch)
+        if len(box) != 4:
+            raise ValueError(f"a box is (left, top, right, bottom), not {box!r}")
+        if H <= 0 or W <= 0 or H > 65535 or pitch < 3 * W or src_off < 0:
+            raise ValueError(f"bad source image: {H} x {W}, pitch {pitch}, offset {src_off}")
+        try:
+            bx, kx, ksx, _, _ = axis(W, box[0], box[2])
+            by, ky, ksy, first, last = axis(H, box[1], box[3])
+        except ValueError:
+            raise ValueError(f"box {tuple(box)!r} does not fit a {W} x {H} image: 0 <= left < right <= width and "
+                             "0 <= top < bottom <= height are required") from None
+        r["src_off"], r["src_pitch"], r["tmp_off"], r["H"], r["W"] = src_off, pitch, tmp_bytes, H, W
+        r["row_first"], r["n_rows"] = first, last - first
+        r["bounds_x"], r["coef_x"], r["ksize_x"] = bx, kx, ksx
+        r["bounds_y"], r["coef_y"], r["ksize_y"] = by, ky, ksy
+        tmp_bytes += (last - first) * S * 3
+        max_rows = max(max_rows, last - first)
+    if n_bounds >= 2 ** 31 or n_coefs >= 2 ** 31:
+        raise ValueError("too many distinct boxes for one call: the coefficient pool is indexed with int32")
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int32)
+    return rec, cat(bounds), cat(coefs), tmp_bytes, max_rows
 
 
 class DevicePreprocessor:
@@ -94,6 +166,8 @@ class DevicePreprocessor:
         self._jpeg_pinned = self._jpeg_dev = self._jpeg_ws = self._jpeg_status = None
         self._jpeg_tmp = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._jpeg_routes, self._jpeg_prog_coef = [], None
+        # region resize: grow-only gather buffer for images that do not share one storage, and the horizontal pass's rows
+        self._region_src = self._region_tmp = None
         self._mean = (ctypes.c_float * 3)(*_MEAN)
         self._std = (ctypes.c_float * 3)(*_STD)
 
@@ -136,21 +210,29 @@ class DevicePreprocessor:
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
 
-    def from_files(self, paths, decode: str = "host", draft: bool = False) -> torch.Tensor:
+    def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None) -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
         the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
         draft=True: JPEGs are decoded at the scale `Image.draft("RGB", (S, S))` picks (1/2, 1/4 or 1/8 while both sides
         stay at least S) and resized from there; the tensor differs slightly from the undrafted one, identically for
-        both values of `decode`."""
+        both values of `decode`.
+        regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` instead
+        of the whole-image batch, for either value of `decode` (torch.equal between them); with draft=True the boxes
+        are in the coordinates of the drafted image."""
         if decode == "device":
             blobs = []
             for p in paths:
                 with open(p, "rb") as f:
                     blobs.append(f.read())
-            return self.from_jpeg_bytes(blobs, draft=draft)
+            return self.from_jpeg_bytes(blobs, draft=draft, regions=regions)
         if decode != "host":
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
-        return self([self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None) for p in paths])
+        arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None) for p in paths]
+        if regions is None:
+            return self(arrays)
+        for a in arrays:
+            self._check_size(a.shape[0], a.shape[1])
+        return self.resize_regions([torch.from_numpy(a.copy()).to(self.device) for a in arrays], regions)
 
     @staticmethod
     def _pil_rgb(pil, draft=None) -> np.ndarray:
@@ -375,11 +457,15 @@ class DevicePreprocessor:
         return self._jpeg_ws[lo:hi].view(torch.int16).view(-1, 64).clone()
 
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
-                        progressive: str = "host", draft: bool = False) -> torch.Tensor:
+                        progressive: str = "host", draft: bool = False, regions=None) -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
-        torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`)."""
+        torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`).
+        regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` on the
+        decoded images instead; with draft=True the boxes are in the coordinates of the drafted image."""
         imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
                                 draft=(self.S, self.S) if draft else None)
+        if regions is not None:
+            return self.resize_regions(imgs, regions)
         S = self.S
         out = torch.empty(len(imgs), 3, S, S, dtype=torch.float32, device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream())
@@ -397,3 +483,79 @@ class DevicePreprocessor:
                     "odic_resize_bilinear_normalize")
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
+
+    # ---------------------------------------------------------------------------------------------------------
+    # regions: PIL's resize(..., box=) for N boxes of images on the device, in one launch pair
+    # ---------------------------------------------------------------------------------------------------------
+    def resize_regions(self, images, regions) -> torch.Tensor:
+        """images: list of uint8 (H,W,3) RGB tensors on the device, as `decode_jpeg` returns them (contiguous, or views
+        into one buffer whose pixels are 3 contiguous bytes); regions: sequence of (image index, (l, t, r, b)) with float
+        boxes in pixels → normalised fp32 [N,3,S,S] in region order, row n equal to
+        `normalise(PIL.Image.resize((S, S), BILINEAR, box=box))` of its image (not crop-then-resize: the filter reads the
+        pixels just outside the box, as Pillow's does).  One odic_resize_boxes_normalize call; images that do not share
+        one storage are first copied into one buffer.  ValueError for an index or a box outside its image
+        (0 <= l < r <= W, 0 <= t < b <= H).  Ordered after the work on the CURRENT stream."""
+        S = self.S
+        regions = [(int(i), tuple(box)) for i, box in regions]
+        out = torch.empty(len(regions), 3, S, S, dtype=torch.float32, device=self.device)
+        if not regions:
+            return out
+        used = sorted({i for i, _ in regions})
+        if used[0] < 0 or used[-1] >= len(images):
+            raise ValueError(f"region of image {used[0] if used[0] < 0 else used[-1]}: there are {len(images)} images")
+        for i in used:
+            im = images[i]
+            if not (isinstance(im, torch.Tensor) and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3
+                    and im.device == out.device and im.numel() > 0 and im.stride(2) == 1 and im.stride(1) == 3
+                    and im.stride(0) >= 3 * im.shape[1]):
+                raise RuntimeError(f"resize_regions wants uint8 (H,W,3) RGB tensors on {self.device} (image {i})")
+        shared = len({images[i].untyped_storage().data_ptr() for i in used}) == 1
+        if shared:
+            src_base = min(images[i].data_ptr() for i in used)
+            place = {i: (images[i].data_ptr() - src_base, images[i].stride(0)) for i in used}
+        else:                                                            # one 256-aligned slot per image, rows packed
+            place, pos = {}, 0
+            for i in used:
+                place[i] = (pos, 3 * images[i].shape[1])
+                pos += (images[i].numel() + 255) // 256 * 256
+            gather_bytes = pos
+        rec, bounds, coefs, tmp_bytes, max_rows = pack_resize_jobs(
+            [(place[i][0], images[i].shape[0], images[i].shape[1], place[i][1], box) for i, box in regions], S)
+
+        def pad(n):
+            return (n + 255) // 256 * 256
+
+        off_b = pad(rec.nbytes)
+        off_k = off_b + pad(bounds.nbytes)
+        tables = np.zeros(off_k + coefs.nbytes, np.uint8)
+        for o, a in ((0, rec), (off_b, bounds), (off_k, coefs)):
+            tables[o:o + a.nbytes] = np.frombuffer(a.tobytes(), np.uint8)
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            if not shared:
+                self._region_src = self._grow(self._region_src, gather_bytes, device=self.device)
+                src_base = self._region_src.data_ptr()
+                for i in used:
+                    self._gather(images[i], self._region_src[place[i][0]:place[i][0] + images[i].numel()])
+            self._region_tmp = self._grow(self._region_tmp, tmp_bytes, device=self.device)
+            dev = torch.from_numpy(tables).to(self.device)
+            self._hip.check(self.lib.odic_resize_boxes_normalize(
+                dev.data_ptr(), len(regions), src_base, dev.data_ptr() + off_b, dev.data_ptr() + off_k,
+                self._region_tmp.data_ptr(), tmp_bytes, out.data_ptr(), S, max_rows, self._mean, self._std,
+                self.stream.cuda_stream), "odic_resize_boxes_normalize")
+        torch.cuda.current_stream().wait_stream(self.stream)
+        return out
+
+    def _gather(self, img: torch.Tensor, dst: torch.Tensor) -> None:
+        """img (H,W,3) → the flat uint8 `dst` of as many bytes, on self.stream: odic_copy for the whole 16-byte words of a
+        contiguous, 16-byte aligned image (dst slots are 256-aligned), a strided copy for its last bytes or for a view
+        with a row pitch."""
+        n = img.numel()
+        n16 = n & ~15 if img.is_contiguous() and img.data_ptr() % 16 == 0 else 0
+        if n16:
+            self._hip.check(self.lib.odic_copy(img.data_ptr(), dst.data_ptr(), n16, self.stream.cuda_stream), "odic_copy")
+        if n16 < n:
+            if n16:
+                dst[n16:].copy_(img.view(-1)[n16:])
+            else:
+                dst.view(img.shape).copy_(img)
