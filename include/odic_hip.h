@@ -54,7 +54,7 @@ extern "C" {
  *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step).
  *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale).
  *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)). */
-#define ODIC_ABI_VERSION 22
+#define ODIC_ABI_VERSION 23
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -410,6 +410,26 @@ int odic_window_attention(const void* qkv, const float* bias_table, const float*
 int odic_swin_qkv_attention(const float* x, int64_t ldx, const void* w_qkv_folded, const float* b_qkv_folded,
                             const float* bias_shifted_prescaled, void* out, int32_t B, int32_t res, int32_t C,
                             int32_t heads, int32_t ws, int32_t shift, float scale, float ln_eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The MLP half of one Swin block in ONE launch (swin_transformer_mod.py:338: x + mlp(norm2(x))),
+ * for the stage of width C = 192:
+ *   x        fp32 [M, C] (ldx)           the residual stream after the attention half
+ *   w1_folded bf16 [4C, C], b1_folded fp32 [4C]:  W·diag(gamma) and bias + W·beta of norm2 → fc1 (the caller folds the
+ *            LayerNorm's affine part at pack time; the kernel computes (x − mean)/sqrt(var + ln_eps) in registers)
+ *   w2       bf16 [C, 4C], b2 fp32 [C], alpha2:  fc2; the product is scaled by alpha2 before the bias is added
+ *   out      fp32 [M, C] (ldo)           x + alpha2·GELU(LN0(x)·w1ᵀ + b1)·w2ᵀ + b2.  May be x itself (ldo = ldx): every row
+ *            panel is read and written by one block only.  Any other overlap of out and x is not supported.
+ * The bf16 hidden activations [M, 4C] never leave the registers: a wave's finished fc1 accumulators are, after GELU and
+ * rounding, its fc2 operand fragments.  Results are bit-identical to odic_gemm(a_ln = x, GELU, bf16 out) followed by
+ * odic_gemm(hidden, w2, residual = x, fp32 out).  Exactly M·C elements are written (columns [C, ldo) are untouched) and
+ * x columns [C, ldx) are not read.
+ * C = 192, M a positive multiple of 128, ldx and ldo multiples of 4 and >= C, x / out / w1_folded / w2 16-byte aligned:
+ * ODIC_EINVAL otherwise, ODIC_ENULL for a null operand, both before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int odic_swin_mlp(const float* x, int64_t ldx, const void* w1_folded, const float* b1_folded, const void* w2,
+                  const float* b2, float alpha2, float* out, int64_t ldo, int32_t M, int32_t C, float ln_eps,
+                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Static expansion (encoder) helpers — layers.py:45-102.  The contractions run through

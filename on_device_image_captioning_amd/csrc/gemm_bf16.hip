@@ -703,6 +703,230 @@ int launch_apanel(Params& p, int out_dtype, int batch, hipStream_t stream) {
   return odic_launch_status();
 }
 
+// =================================================================================================
+// The MLP of a Swin block of width C = 64·KT in ONE launch:  out = x + fc2(GELU(fc1(LN0(x))))  (odic_swin_mlp).
+//
+// As two launches (the LNA form above, then the tiled kernel) the bf16 hidden tensor [M, 4C] is written once and read
+// once — 2 x 226 MB per stage-0 block at B = 16, two thirds of the pair's traffic — and nothing else reads it.  Here it
+// never leaves the registers.  What makes that free is the swapped-operand accumulator layout: a lane's finished pair
+// (2q, 2q+1) of fc1 tiles is row frow, hidden columns 32q + 8·fq .. +7 (the epilogue note of the tiled kernel), which is
+// the B-operand fragment of v_mfma_f32_16x16x32_bf16 for the 32-deep K step q.  After bias, GELU and rounding to bf16 a
+// wave's 64-column fc1 chunk IS its fc2 activation fragment pair: no LDS, no shuffle, no store.
+//   * a wave keeps its 16·MI rows as LayerNorm-ed fragments over the whole K = C (the LNA prologue, the same bits) and
+//     MI x C/16 fp32 output accumulators for the whole launch;
+//   * the block walks the hidden dimension in chunks of 64: phase A = fc1 of the chunk (W1 rows 64c .. +63, 24 KiB at
+//     C = 192) → hidden fragments; phase B = two 32-deep K steps of fc2 (W2 columns 64c .. +63 of all C rows, through
+//     wperm, 24 KiB) into the output accumulators;
+//   * one LDS buffer per operand: W2(c) is requested after the barrier in front of phase A, W1(c+1) after the barrier in
+//     front of phase B, so each phase computes under the other operand's DMA; two barriers per chunk.  The DMA group is
+//     the only outstanding vector-memory operation inside the loop, so its wait is vmcnt(0);
+//   * epilogue once per block: alpha2, bias, the residual rows re-read from x (L2 / Infinity Cache hits), float4 pairs.
+// Every output element is one accumulator chain over ascending 32-deep steps, as in the tiled kernel, and both epilogue
+// expressions are the ones of the kernels this replaces: the result is bit-identical to the two launches.
+// `out` may be `x` itself: a lane re-reads exactly the elements it then writes, and a row belongs to one wave.
+// =================================================================================================
+struct MlpParams {
+  const float* x; float* out; const bf16_raw* W1; const float* b1; const bf16_raw* W2; const float* b2;
+  long ldx, ldo; int M;
+  float alpha1, alpha2, ln_eps;
+};
+
+template <int MI, int KT>
+__global__ __launch_bounds__(256, 2) void swin_mlp_kernel(MlpParams p) {
+  constexpr int NW = 4;
+  constexpr int C = KT * 64, H = 4 * C, BM = NW * MI * 16;
+  constexpr int NO = C / 16;                             // fc2 output tiles per 16 rows
+  constexpr int SUB = 64 * 128;                          // one 64-deep sub-tile of the W1 chunk: 64 rows x 128 B
+  constexpr int W1B = KT * SUB, W2B = C * 128;           // bytes per buffer (equal: 64·C bf16 each)
+  constexpr int I1 = W1B / 1024 / NW, I2 = W2B / 1024 / NW;            // 1-KiB LDS-DMA instructions per wave per chunk
+  static_assert(W1B % (1024 * NW) == 0 && W2B % (1024 * NW) == 0, "a chunk must split into whole DMA instructions per wave");
+  extern __shared__ __attribute__((aligned(16))) char lds[];          // W1 chunk | W2 chunk | fc1 bias [H] | fc2 bias [C]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  ODIC_ENCODE_PRIO();
+  const int m0 = blockIdx.x * BM;                        // (blocks b, b + 8, ... share an XCD: consecutive panels spread over all eight)
+  // (the two alphas live in VGPRs: a packed multiply by one scalar of an SGPR pair is the `op_sel` source-selection form
+  //  the ISA lint forbids — DESIGN.md §5)
+  float alpha1_v = p.alpha1, alpha2_v = p.alpha2;
+  asm volatile("" : "+v"(alpha1_v), "+v"(alpha2_v));
+  const int frow = lane & 15, fq = lane >> 4;
+
+  // ---- W chunk DMA (element offsets inside a chunk).  W1: sub-tile kt, rows 8·rg .. +7 as in the A-resident kernel;
+  //      W2: C rows of 128 B, rows 8·j .. +7
+  int w1_off[I1], w2_off[I2];
+  {
+    const int srow = lane >> 3, sch = swz<128>(lane & 7, srow) * 8;
+#pragma unroll
+    for (int i = 0; i < I1; ++i) {
+      const int j = i * NW + wave, kt = j / 8, rg = j - kt * 8;
+      w1_off[i] = wperm(rg * 8 + srow) * C + kt * 64 + sch;
+    }
+#pragma unroll
+    for (int i = 0; i < I2; ++i) w2_off[i] = wperm((i * NW + wave) * 8 + srow) * H + sch;
+  }
+  char* const l1 = lds;
+  char* const l2 = lds + W1B;
+  auto issue1 = [&](int c) {
+    const bf16_raw* wb = p.W1 + (long)c * 64 * C;
+#pragma unroll
+    for (int i = 0; i < I1; ++i)
+      __builtin_amdgcn_global_load_lds((gptr_t)(wb + w1_off[i]), (lptr_t)(l1 + (i * NW + wave) * 1024), 16, 0, 0);
+  };
+  auto issue2 = [&](int c) {
+    const bf16_raw* wb = p.W2 + c * 64;
+#pragma unroll
+    for (int i = 0; i < I2; ++i)
+      __builtin_amdgcn_global_load_lds((gptr_t)(wb + w2_off[i]), (lptr_t)(l2 + (i * NW + wave) * 1024), 16, 0, 0);
+  };
+  issue1(0);
+  float* sb1 = (float*)(lds + W1B + W2B);
+  float* sb2 = sb1 + H;
+  for (int t = tid; t < H; t += 256) sb1[t] = p.b1[t];
+  for (int t = tid; t < C; t += 256) sb2[t] = p.b2[t];
+
+  // ---- this wave's rows, LayerNorm-ed while read, as MFMA B-operand fragments (gemm_bf16_apanel_kernel's LNA prologue,
+  //      KT <= 3 form, statement for statement: the fragments are the same bits)
+  bf16x8_t af[2 * KT][MI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const float* xr = p.x + (long)(m0 + (wave * MI + mi) * 16 + frow) * p.ldx + fq * 8;
+    f32x4_t xv[2 * KT][2];
+#pragma unroll
+    for (int k = 0; k < 2 * KT; ++k) { xv[k][0] = *(const f32x4_t*)(xr + k * 32); xv[k][1] = *(const f32x4_t*)(xr + k * 32 + 4); }
+    f32x4_t s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 2 * KT; ++k) s4 += xv[k][0] + xv[k][1];
+    float sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float mean = sum / (float)(64 * KT);       // (a true division: a constant row then normalises to exactly 0)
+    f32x4_t q4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 2 * KT; ++k) {
+      xv[k][0] -= mean; xv[k][1] -= mean;
+      q4 += xv[k][0] * xv[k][0] + xv[k][1] * xv[k][1];
+    }
+    float ssq = (q4[0] + q4[1]) + (q4[2] + q4[3]);
+    ssq += __shfl_xor(ssq, 16, 64);
+    ssq += __shfl_xor(ssq, 32, 64);
+    const float rstd = rsqrtf(ssq / (float)(64 * KT) + p.ln_eps);
+#pragma unroll
+    for (int k = 0; k < 2 * KT; ++k) {
+      bf16x8_t f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        f[e] = (short)f32_to_bf16(xv[k][0][e] * rstd);
+        f[4 + e] = (short)f32_to_bf16(xv[k][1][e] * rstd);
+      }
+      af[k][mi] = f;
+    }
+  }
+
+  f32x4_t acc2[MI][NO];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NO; ++j) acc2[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  // rows, first W1 chunk and bias staging complete (the builtin: hipcc's wait insertion must see the rows arrive)
+  __builtin_amdgcn_s_waitcnt(0x0070);                                  // vmcnt(0) lgkmcnt(0)
+  const char* lw1 = l1 + frow * 128;
+  const char* lw2 = l2 + frow * 128;
+  for (int c = 0; c < H / 64; ++c) {
+    // W1(c) has landed for every wave, and every wave is done with W2(c-1)
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                // vmcnt(0)
+    __builtin_amdgcn_s_barrier();
+    issue2(c);
+    // ---- phase A: 64 hidden columns of fc1
+    f32x4_t acc1[MI][4];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc1[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        bf16x8_t wf[4];
+        const int chunk = swz<128>(kk * 4 + fq, frow) << 4;
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) wf[ni] = *(const bf16x8_t*)(lw1 + kt * SUB + ni * 16 * 128 + chunk);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni)
+            acc1[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni], af[2 * kt + kk][mi], acc1[mi][ni], 0, 0, 0);
+      }
+    }
+    // the chunk's epilogue as the A-resident kernel writes it (alpha, bias, GELU, bf16): pair q → fragment of K step q
+    bf16x8_t hf[2][MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const f32x4_t* sb = (const f32x4_t*)(sb1 + c * 64 + q * 32 + fq * 8);
+        bf16x8_t f;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          f32x4_t pre = acc1[mi][2 * q + h] * alpha1_v + sb[h];
+          pre = gelu_poly4(pre);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) f[4 * h + e] = (short)f32_to_bf16(pre[e]);
+        }
+        hf[q][mi] = f;
+      }
+    }
+    // W2(c) has landed for every wave, and every wave is done with W1(c)
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                // vmcnt(0)
+    __builtin_amdgcn_s_barrier();
+    if (c + 1 < H / 64) issue1(c + 1);
+    // ---- phase B: two 32-deep K steps of fc2, four output tiles at a time
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int chunk = swz<128>(kk * 4 + fq, frow) << 4;
+#pragma unroll
+      for (int n4 = 0; n4 < NO / 4; ++n4) {
+        bf16x8_t wf[4];
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) wf[ni] = *(const bf16x8_t*)(lw2 + (n4 * 4 + ni) * 16 * 128 + chunk);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni)
+            acc2[mi][n4 * 4 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni], hf[kk][mi], acc2[mi][n4 * 4 + ni], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- epilogue (the tiled kernel's fp32 vector path with a residual: the rows of column group q + 1 are requested
+  //      before the stores of group q; no bounds: whole panels only)
+  constexpr int NG = NO / 2;
+  const float brow = 0.f;                                // (the tiled kernel's row-bias term, absent here, kept in the expression)
+  f32x4_t rv[2][MI][2];
+  auto loadg = [&](int q, int slot) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const f32x4_t* rp = (const f32x4_t*)(p.x + (long)(m0 + (wave * MI + mi) * 16 + frow) * p.ldx + q * 32 + fq * 8);
+      rv[slot][mi][0] = rp[0]; rv[slot][mi][1] = rp[1];
+    }
+  };
+  loadg(0, 0);
+#pragma unroll
+  for (int q = 0; q < NG; ++q) {
+    if (q + 1 < NG) loadg(q + 1, (q + 1) & 1);
+    const f32x4_t* sb = (const f32x4_t*)(sb2 + q * 32 + fq * 8);
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      f32x4_t v[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) v[h] = acc2[mi][2 * q + h] * alpha2_v + sb[h] + brow;
+      v[0] += rv[q & 1][mi][0]; v[1] += rv[q & 1][mi][1];
+      float* dst = p.out + (long)(m0 + (wave * MI + mi) * 16 + frow) * p.ldo + q * 32 + fq * 8;
+      ((f32x4_t*)dst)[0] = v[0]; ((f32x4_t*)dst)[1] = v[1];
+    }
+  }
+}
+
 template <int NWM, int NWN, int MI, int NI, int NSTAGE, int BK = 64, int KS = 1>
 int launch_cfg(Params& p, int out_dtype, int batch, hipStream_t stream) {
   constexpr int BM = NWM * MI * 16, BN = NWN * NI * 16;
@@ -788,4 +1012,22 @@ int odic_gemm_bf16_launch(const odic_gemm_args* a, hipStream_t stream) {
     case 53: return launch_apanel<2, 4, 6, 2>(p, a->out_dtype, a->batch, stream);  // K = 384: 128-row panels, 64-column chunks in two K pieces
     default: return ODIC_EINVAL;
   }
+}
+
+/* x + fc2(GELU(fc1(LN0(x)))) of one Swin block in one launch (stage width 192; see swin_mlp_kernel). */
+extern "C" int odic_swin_mlp(const float* x, int64_t ldx, const void* w1_folded, const float* b1_folded, const void* w2,
+                             const float* b2, float alpha2, float* out, int64_t ldo, int32_t M, int32_t C, float ln_eps,
+                             void* stream) {
+  if (!x || !w1_folded || !b1_folded || !w2 || !b2 || !out) return ODIC_ENULL;
+  constexpr int MI = 2, BM = 4 * MI * 16;
+  if (C != 192 || M <= 0 || M % BM != 0) return ODIC_EINVAL;
+  if (ldx < C || ldo < C || (ldx & 3) || (ldo & 3)) return ODIC_EINVAL;
+  if (((uintptr_t)x & 15) || ((uintptr_t)out & 15) || ((uintptr_t)w1_folded & 15) || ((uintptr_t)w2 & 15)) return ODIC_EINVAL;
+  MlpParams p;
+  p.x = x; p.out = out; p.W1 = (const bf16_raw*)w1_folded; p.b1 = b1_folded; p.W2 = (const bf16_raw*)w2; p.b2 = b2;
+  p.ldx = ldx; p.ldo = ldo; p.M = M;
+  p.alpha1 = 1.0f; p.alpha2 = alpha2; p.ln_eps = ln_eps;
+  const int SHMEM = 2 * 64 * C * 2 + 5 * C * 4;          // W1 chunk + W2 chunk + the two bias vectors
+  hipLaunchKernelGGL((swin_mlp_kernel<MI, 3>), dim3(M / BM), dim3(256), SHMEM, (hipStream_t)stream, p);
+  return odic_launch_status();
 }

@@ -106,6 +106,9 @@ class SwinEngine:
         lr = os.environ.get("ODIC_FUSE_BACKBONE_LN_READ", "1")
         self.ln_read = (precision == "bf16" and lr != "0") or (precision == "x3" and lr == "x3")
         self.fuse_qkv_attn = precision == "bf16" and os.environ.get("ODIC_FUSE_QKV_ATTENTION", "1") == "1"
+        # bf16 mode, width 192: norm2 → fc1 → GELU → fc2 + residual as ONE launch (odic_swin_mlp); it
+        # uses the folded fc1 weights of the LayerNorm-while-reading form.  ODIC_FUSE_MLP=0 keeps the two launches.
+        self.fuse_mlp = precision == "bf16" and os.environ.get("ODIC_FUSE_MLP", "1") == "1"
         if self.ln_read:
             for s, (blocks, _) in enumerate(self.stages):
                 if g.stage_dim(s) != 192:
@@ -220,9 +223,13 @@ class SwinEngine:
                         att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
                                                    bias_shifted_prescaled=w["dense"])
                     ops.gemm(att, w["proj_w"], w["proj_b"], residual=x, out=x, alpha=w["proj_a"])
-                    h = ops.gemm(None, w["fc1_lnr"][0], w["fc1_lnr"][1], a_ln=x, act=ops.ACT_GELU, out_dtype=cdt,
-                                 alpha=w["fc1_lnr"][2])
-                    ops.gemm(h, w["fc2_w"], w["fc2_b"], residual=x, out=x, alpha=w["fc2_a"])
+                    if self.fuse_mlp and ops.swin_mlp_supported(x.shape[0], C_, cdt):
+                        # norm2 → fc1 → GELU → fc2 + residual: one launch, the hidden activations never leave the chip
+                        ops.swin_mlp(x, w["fc1_lnr"][0], w["fc1_lnr"][1], w["fc2_w"], w["fc2_b"], w["fc2_a"], out=x)
+                    else:
+                        h = ops.gemm(None, w["fc1_lnr"][0], w["fc1_lnr"][1], a_ln=x, act=ops.ACT_GELU, out_dtype=cdt,
+                                     alpha=w["fc1_lnr"][2])
+                        ops.gemm(h, w["fc2_w"], w["fc2_b"], residual=x, out=x, alpha=w["fc2_a"])
                 else:
                     xn = ops.layernorm(x, w["n1w"], w["n1b"], out_dtype=cdt)
                     if _amax is not None:

@@ -455,6 +455,37 @@ def swin_qkv_attention(x: torch.Tensor, w_folded: torch.Tensor, b_folded: torch.
     return out
 
 
+def swin_mlp_supported(M: int, C_: int, dtype=torch.bfloat16) -> bool:
+    """Shapes odic_swin_mlp takes: bf16 weights, width 192, whole 128-row panels.  (One tile form, chosen by this rule
+    and not by a timed run: the call is legal inside a stream capture at a shape never run before.)"""
+    return dtype == torch.bfloat16 and C_ == 192 and M > 0 and M % 128 == 0
+
+
+def swin_mlp(x: torch.Tensor, w1_folded: torch.Tensor, b1_folded: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+             alpha2: float = 1.0, out: Optional[torch.Tensor] = None, ln_eps: float = 1e-5) -> torch.Tensor:
+    """x + fc2(GELU(fc1(LN0(x)))) in one launch (odic_swin_mlp; width 192): the bf16 hidden activations stay in registers.
+    x fp32 [M, C] contiguous, (w1_folded, b1_folded) from fold_layernorm_bf16(fc1.weight, fc1.bias, norm2.weight,
+    norm2.bias), w2 bf16 [C, 4C] with its fp32 bias and alpha.  `out` may be x itself (in place).  Bit-identical to
+    gemm(None, w1_folded, b1_folded, a_ln=x, act=ACT_GELU) followed by gemm(h, w2, b2, residual=x, alpha=alpha2)."""
+    _need_cuda(x, w1_folded, b1_folded, w2, b2, out)
+    if x.dtype != torch.float32 or w1_folded.dtype != torch.bfloat16 or w2.dtype != torch.bfloat16 or \
+            not (x.is_contiguous() and w1_folded.is_contiguous() and w2.is_contiguous()):
+        raise RuntimeError("swin_mlp: contiguous fp32 rows and contiguous bf16 weights")
+    C_ = x.shape[-1]
+    M = x.numel() // C_
+    if tuple(w1_folded.shape) != (4 * C_, C_) or tuple(w2.shape) != (C_, 4 * C_) or b1_folded.numel() != 4 * C_ or \
+            b2.numel() != C_ or b1_folded.dtype != torch.float32 or b2.dtype != torch.float32:
+        raise RuntimeError("swin_mlp: fc1 is [4C, C] with an fp32 bias [4C], fc2 [C, 4C] with an fp32 bias [C]")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous():
+        raise RuntimeError("swin_mlp: out is a contiguous fp32 tensor of x's shape")
+    with _timed("swin_mlp", 2.0 * M * C_ * 4 * C_ * 2, 2.0 * M * C_ * 4 + 2 * 4 * C_ * C_ * 2, f"{M}x{C_}"):
+        _hip.check(_hip.load().odic_swin_mlp(_p(x), C_, _p(w1_folded), _p(b1_folded), _p(w2), _p(b2), float(alpha2), _p(out),
+                                             C_, M, C_, float(ln_eps), _stream()), "odic_swin_mlp")
+    return out
+
+
 def window_attention(qkv: torch.Tensor, bias_table: torch.Tensor, B: int, res: int, C_: int, heads: int, ws: int,
                      shift: int, *, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
                      bias_shifted_prescaled: Optional[torch.Tensor] = None) -> torch.Tensor:
