@@ -7,7 +7,9 @@
 // window [xmin, xmin+n) of taps with coefficients round(w·2^22) (computed on the host exactly as
 // precompute_coeffs / normalize_coeffs_8bpc do, ops.pil_bilinear_coeffs), accumulator = 2^21 + Σ pix·k,
 // result = clip8(acc >> 22); horizontal pass first into an 8-bit intermediate, then the vertical one.
-// Both passes here are one thread per output pixel (3 channels), coalesced along x.
+// Both passes here are one thread per output pixel (3 channels), coalesced along x.  Each pass is written once, as a
+// __device__ body; the whole-image kernels (odic_resize_bilinear_normalize) and the job-list kernels
+// (odic_resize_boxes_normalize) only resolve its operands, so both entry points run the same statements.
 #include "odic_common.h"
 
 namespace {
@@ -19,32 +21,28 @@ __device__ __forceinline__ unsigned char clip8(int v) {
   return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// tmp[y][xx][c] = clip8(2^21 + Σ_i src[y][xmin+i][c]·kx[xx][i])
-__global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __restrict__ src, long sstride, int H,
-                                                       const int* __restrict__ bounds, const int* __restrict__ kk,
-                                                       int ksize, unsigned char* __restrict__ tmp, int out) {
-  const int xx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (xx >= out) return;
+// Horizontal: q[c] = clip8(2^21 + Σ_i row[xmin+i][c]·kx[xx][i]); row: the source row, q: the 8-bit intermediate's pixel.
+__device__ __forceinline__ void resize_h_pixel(const unsigned char* __restrict__ row, const int* __restrict__ bounds,
+                                               const int* __restrict__ kk, int ksize, int xx,
+                                               unsigned char* __restrict__ q) {
   const int x0 = bounds[2 * xx], n = bounds[2 * xx + 1];
   const int* k = kk + (long)xx * ksize;
-  const unsigned char* p = src + (long)y * sstride + 3L * x0;
+  const unsigned char* p = row + 3L * x0;
   int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
   for (int i = 0; i < n; ++i) {
     const int w = k[i];
     a0 += p[3 * i] * w; a1 += p[3 * i + 1] * w; a2 += p[3 * i + 2] * w;
   }
-  unsigned char* q = tmp + ((long)y * out + xx) * 3;
   q[0] = clip8(a0); q[1] = clip8(a1); q[2] = clip8(a2);
 }
 
-// dst[c][yy][xx] = (clip8(2^21 + Σ_i tmp[ymin+i][xx][c]·ky[yy][i]) / 255 - mean[c]) / std[c]
-__global__ __launch_bounds__(256) void resize_v_norm_kernel(const unsigned char* __restrict__ tmp,
-                                                            const int* __restrict__ bounds, const int* __restrict__ kk,
-                                                            int ksize, float* __restrict__ dst, int out, float m0,
-                                                            float m1, float m2, float s0, float s1, float s2) {
-  const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
-  if (xx >= out) return;
-  const int y0 = bounds[2 * yy], n = bounds[2 * yy + 1];
+// Vertical + normalise: dst[c][yy][xx] = (clip8(2^21 + Σ_i tmp[ymin+i][xx][c]·ky[yy][i]) / 255 - mean[c]) / std[c];
+// tmp: the intermediate's rows from source row `row_first` on, `out` pixels each; dst: the image's [3, out, out].
+__device__ __forceinline__ void resize_v_norm_pixel(const unsigned char* __restrict__ tmp, int row_first,
+                                                    const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                    int ksize, int xx, int yy, float* __restrict__ dst, int out,
+                                                    float m0, float m1, float m2, float s0, float s1, float s2) {
+  const int y0 = bounds[2 * yy] - row_first, n = bounds[2 * yy + 1];
   const int* k = kk + (long)yy * ksize;
   const unsigned char* p = tmp + ((long)y0 * out + xx) * 3;
   int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
@@ -60,9 +58,26 @@ __global__ __launch_bounds__(256) void resize_v_norm_kernel(const unsigned char*
   dst[2 * plane + o] = (__fdiv_rn((float)clip8(a2), 255.0f) - m2) / s2;
 }
 
-// The two passes above over a job list (odic_resize_job, one per region): blockIdx.z is the job, the horizontal pass runs
-// over the job's n_rows source rows from row_first only, the vertical one reads tmp rows relative to row_first.  A job
-// whose tmp slice would end behind tmp_bytes is skipped by both passes.
+__global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __restrict__ src, long sstride, int H,
+                                                       const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                       int ksize, unsigned char* __restrict__ tmp, int out) {
+  const int xx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (xx >= out) return;
+  resize_h_pixel(src + (long)y * sstride, bounds, kk, ksize, xx, tmp + ((long)y * out + xx) * 3);
+}
+
+__global__ __launch_bounds__(256) void resize_v_norm_kernel(const unsigned char* __restrict__ tmp,
+                                                            const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                            int ksize, float* __restrict__ dst, int out, float m0,
+                                                            float m1, float m2, float s0, float s1, float s2) {
+  const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
+  if (xx >= out) return;
+  resize_v_norm_pixel(tmp, 0, bounds, kk, ksize, xx, yy, dst, out, m0, m1, m2, s0, s1, s2);
+}
+
+// A job list (odic_resize_job, one per region): blockIdx.z is the job, the horizontal pass runs over the job's n_rows
+// source rows from row_first only, the vertical one reads tmp rows relative to row_first.  A job whose tmp slice would
+// end behind tmp_bytes is skipped by both passes.
 __device__ __forceinline__ bool job_fits(const odic_resize_job& j, int out, unsigned long tmp_bytes) {
   return j.tmp_off >= 0 && (unsigned long)j.tmp_off + (unsigned long)j.n_rows * out * 3 <= tmp_bytes;
 }
@@ -76,17 +91,8 @@ __global__ __launch_bounds__(256) void resize_boxes_h_kernel(const odic_resize_j
   const odic_resize_job j = jobs[blockIdx.z];
   const int xx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (xx >= out || y >= j.n_rows || !job_fits(j, out, tmp_bytes)) return;
-  const int* bounds = bounds_pool + j.bounds_x;
-  const int x0 = bounds[2 * xx], n = bounds[2 * xx + 1];
-  const int* k = coef_pool + j.coef_x + (long)xx * j.ksize_x;
-  const unsigned char* p = src_base + j.src_off + (long)(j.row_first + y) * j.src_pitch + 3L * x0;
-  int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-  for (int i = 0; i < n; ++i) {
-    const int w = k[i];
-    a0 += p[3 * i] * w; a1 += p[3 * i + 1] * w; a2 += p[3 * i + 2] * w;
-  }
-  unsigned char* q = tmp_base + j.tmp_off + ((long)y * out + xx) * 3;
-  q[0] = clip8(a0); q[1] = clip8(a1); q[2] = clip8(a2);
+  resize_h_pixel(src_base + j.src_off + (long)(j.row_first + y) * j.src_pitch, bounds_pool + j.bounds_x,
+                 coef_pool + j.coef_x, j.ksize_x, xx, tmp_base + j.tmp_off + ((long)y * out + xx) * 3);
 }
 
 __global__ __launch_bounds__(256) void resize_boxes_v_norm_kernel(const odic_resize_job* __restrict__ jobs,
@@ -99,21 +105,8 @@ __global__ __launch_bounds__(256) void resize_boxes_v_norm_kernel(const odic_res
   const odic_resize_job j = jobs[blockIdx.z];
   const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
   if (xx >= out || !job_fits(j, out, tmp_bytes)) return;
-  const int* bounds = bounds_pool + j.bounds_y;
-  const int y0 = bounds[2 * yy] - j.row_first, n = bounds[2 * yy + 1];
-  const int* k = coef_pool + j.coef_y + (long)yy * j.ksize_y;
-  const unsigned char* p = tmp_base + j.tmp_off + ((long)y0 * out + xx) * 3;
-  int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-  for (int i = 0; i < n; ++i) {
-    const int w = k[i];
-    const unsigned char* r = p + (long)i * out * 3;
-    a0 += r[0] * w; a1 += r[1] * w; a2 += r[2] * w;
-  }
-  const long plane = (long)out * out, o = (long)yy * out + xx;
-  float* dst = dst_base + 3 * plane * blockIdx.z;
-  dst[o] = (__fdiv_rn((float)clip8(a0), 255.0f) - m0) / s0;
-  dst[plane + o] = (__fdiv_rn((float)clip8(a1), 255.0f) - m1) / s1;
-  dst[2 * plane + o] = (__fdiv_rn((float)clip8(a2), 255.0f) - m2) / s2;
+  resize_v_norm_pixel(tmp_base + j.tmp_off, j.row_first, bounds_pool + j.bounds_y, coef_pool + j.coef_y, j.ksize_y, xx,
+                      yy, dst_base + 3L * out * out * blockIdx.z, out, m0, m1, m2, s0, s1, s2);
 }
 
 }  // namespace

@@ -14,6 +14,8 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .jpeg import pad256 as _pad256
+
 _MEAN = (0.485, 0.456, 0.406)
 _STD = (0.229, 0.224, 0.225)
 
@@ -179,6 +181,22 @@ class DevicePreprocessor:
             self._coef_cache[n] = c
         return c
 
+    def _check_size(self, H: int, W: int) -> None:
+        if H * W * 3 > self.max_bytes:
+            raise RuntimeError(f"image {H}x{W} exceeds the staging buffers ({self.max_bytes} bytes)")
+
+    def _resize_whole(self, src_ptr: int, H: int, W: int, tmp: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+        """Resize + normalise the packed RGB8 image of H x W at device address src_ptr into dst fp32 [3,S,S], on
+        self.stream.  tmp holds the horizontal pass's H x S pixels: → tmp, or a larger buffer that replaces it."""
+        if tmp.numel() < H * self.S * 3:
+            tmp = torch.empty(H * self.S * 3, dtype=torch.uint8, device=self.device)
+        bx, kx, ksx = self._coeffs(W)
+        by, ky, ksy = self._coeffs(H)
+        self._hip.check(self.lib.odic_resize_bilinear_normalize(
+            src_ptr, H, W, 3 * W, bx.data_ptr(), kx.data_ptr(), ksx, by.data_ptr(), ky.data_ptr(), ksy, tmp.data_ptr(),
+            dst.data_ptr(), self.S, self._mean, self._std, self.stream.cuda_stream), "odic_resize_bilinear_normalize")
+        return tmp
+
     def __call__(self, images) -> torch.Tensor:
         """images: sequence of HWC uint8 RGB numpy arrays (any sizes) → normalised fp32 [B,3,S,S] on the device,
         ordered after the work on the CURRENT stream."""
@@ -191,21 +209,13 @@ class DevicePreprocessor:
                 if img.ndim != 3 or img.shape[2] != 3:
                     raise RuntimeError("DevicePreprocessor wants HWC RGB uint8 arrays")
                 H, W, _ = img.shape
+                self._check_size(H, W)
                 nbytes = H * W * 3
-                if nbytes > self.max_bytes:
-                    raise RuntimeError(f"image {H}x{W} exceeds the staging buffers ({self.max_bytes} bytes)")
                 slot = i & 1
                 self.ev[slot].synchronize()                                   # the kernels that read this slot are done
                 self.host[slot][:nbytes].copy_(torch.from_numpy(img).reshape(-1))
                 self.dev[slot][:nbytes].copy_(self.host[slot][:nbytes], non_blocking=True)
-                if self.tmp[slot].numel() < H * S * 3:
-                    self.tmp[slot] = torch.empty(H * S * 3, dtype=torch.uint8, device=self.device)
-                bx, kx, ksx = self._coeffs(W)
-                by, ky, ksy = self._coeffs(H)
-                self._hip.check(self.lib.odic_resize_bilinear_normalize(
-                    self.dev[slot].data_ptr(), H, W, 3 * W, bx.data_ptr(), kx.data_ptr(), ksx, by.data_ptr(),
-                    ky.data_ptr(), ksy, self.tmp[slot].data_ptr(), out[i].data_ptr(), S, self._mean, self._std,
-                    self.stream.cuda_stream), "odic_resize_bilinear_normalize")
+                self.tmp[slot] = self._resize_whole(self.dev[slot].data_ptr(), H, W, self.tmp[slot], out[i])
                 self.ev[slot].record(self.stream)
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
@@ -247,10 +257,6 @@ class DevicePreprocessor:
     # ---------------------------------------------------------------------------------------------------------
     # device JPEG decode
     # ---------------------------------------------------------------------------------------------------------
-    def _check_size(self, H: int, W: int) -> None:
-        if H * W * 3 > self.max_bytes:
-            raise RuntimeError(f"image {H}x{W} exceeds the staging buffers ({self.max_bytes} bytes)")
-
     def _host_rgb(self, blob, draft=None) -> np.ndarray:
         """The host path for one file: PIL decode, after `im.draft("RGB", draft)` if there is a draft request (black
         canvas for non-RGB modes, of the drafted size) → uint8 (H,W,3) array."""
@@ -261,6 +267,14 @@ class DevicePreprocessor:
         if buf is not None and buf.numel() >= nbytes:
             return buf
         return torch.empty(max(nbytes, 2 * (buf.numel() if buf is not None else 0)), dtype=torch.uint8, **kw)
+
+    @staticmethod
+    def _set_fields(struct, totals):
+        for k, v in totals.items():
+            if isinstance(v, list):
+                getattr(struct, k)[:len(v)] = v
+            else:
+                setattr(struct, k, v)
 
     @property
     def last_routes(self):
@@ -297,7 +311,6 @@ class DevicePreprocessor:
                     if ph.kind == J.DEVICE:
                         hdrs[i] = ph
         out = [None] * len(blobs)
-        routes = [h.kind for h in hdrs]
         scales = [J.draft_scale((h.width, h.height), draft) if draft is not None and h.kind != J.HOST else 1
                   for h in hdrs]
         sizes = [J.scaled_size((h.width, h.height), s) for h, s in zip(hdrs, scales)]        # (width, height)
@@ -306,13 +319,9 @@ class DevicePreprocessor:
                if h.kind == J.DEVICE and sizes[i][0] * sizes[i][1] * 3 <= self.max_bytes]
         base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader)]
         prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader)]
-        for i, h in enumerate(hdrs):
-            if h.kind == J.DEVICE:
-                routes[i] = "host"                                       # oversized
-        for i in prog:
-            routes[i] = "device-progressive"
-        for i in base:
-            routes[i] = "device"
+        routes = ["host" if h.kind == J.DEVICE else h.kind for h in hdrs]        # a device kind left so is oversized
+        for i in dev:
+            routes[i] = "device-progressive" if isinstance(hdrs[i], J.ProgHeader) else "device"
         if dev:
             order = base + prog
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
@@ -338,116 +347,63 @@ class DevicePreprocessor:
                     out[i] = torch.from_numpy(out[i].copy()).to(self.device)
         return out
 
-    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales=None):
+    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales):
         """One odic_jpeg_decode call for the baseline files and one odic_jpeg_decode_progressive call for the progressive
         ones, sharing one upload, one output buffer, one workspace and one status read-back → (status numpy int32 —
         baseline files first —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
-        baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales
-        uploaded beside the headers."""
+        baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales uploaded
+        beside the headers.  This is the GPU half: `jpeg.plan_device_batch` lays the upload and the output out."""
         from . import jpeg as J
-
-        def pad(n):
-            return (n + 255) // 256 * 256
-
         nb, npg = len(hdrs), len(phdrs)
-        scales = list(scales) if scales else [1] * (nb + npg)
-        scaled_b, scaled_p = any(s > 1 for s in scales[:nb]), any(s > 1 for s in scales[nb:])
-        offs, ends, poffs = [], [], []
-        sections, pos = [], 0                                            # (staging offset, record array)
-        if nb:
-            pos = pad(nb * J.HEADER_DTYPE.itemsize)
-        if npg:
-            prec, srec, trec, ptot, pout_offs, pout_bytes = J.pack_progressive(phdrs, [0] * npg, scales[nb:])   # sizes only, for now
-            prog_off = (pos, pos + pad(prec.nbytes), pos + pad(prec.nbytes) + pad(srec.nbytes))
-            pos = prog_off[2] + pad(trec.nbytes)
-        if scaled_b or scaled_p:                                         # int32 scale_log2 [nb + npg]
-            scale_off = pos
-            sections.append((pos, np.asarray([s.bit_length() - 1 for s in scales], np.int32)))
-            pos += pad(4 * (nb + npg))
-        data_off = pos
-        pos = 0
-        for h, blob in zip(hdrs, blobs):
-            offs.append(pos + h.data_offset)
-            pos += len(blob)
-            ends.append(pos)
-        for blob in pblobs:
-            poffs.append(pos)
-            pos += len(blob)
-        total = data_off + pos
-        out_offs, out_bytes = [], 0
-        if nb:
-            rec, tot, out_offs, out_bytes = J.pack_headers(hdrs, offs, ends, subseq_bits, scales[:nb])
-            sections.append((0, rec))
-        if npg:
-            srec["data_off"] += np.asarray(poffs, np.int64)[srec["image"]]
-            srec["data_end"] += np.asarray(poffs, np.int64)[srec["image"]]
-            sections += list(zip(prog_off, (prec, srec, trec)))
-            out_offs = out_offs + [out_bytes + o for o in pout_offs]
+        plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales)
         self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
-        self._jpeg_pinned = self._grow(self._jpeg_pinned, total, pin_memory=True)
+        self._jpeg_pinned = self._grow(self._jpeg_pinned, plan.total, pin_memory=True)
         self._jpeg_status = self._grow(self._jpeg_status, 4 * (nb + npg), pin_memory=True)
-        host = self._jpeg_pinned.numpy()
-        for o, r in sections:
-            host[o:o + r.nbytes] = np.frombuffer(r.tobytes(), np.uint8)
-        p = data_off
-        for blob in list(blobs) + list(pblobs):
-            host[p:p + len(blob)] = np.frombuffer(blob, np.uint8)
-            p += len(blob)
-        rgb = torch.empty(max(out_bytes + (pout_bytes if npg else 0), 1), dtype=torch.uint8, device=self.device)
+        plan.fill(self._jpeg_pinned.numpy())
+        rgb = torch.empty(max(plan.out_bytes + plan.pout_bytes, 1), dtype=torch.uint8, device=self.device)
         status = torch.empty(nb + npg, dtype=torch.int32, device=self.device)
-        need = 0
+        need_b = need_p = 0
         if nb:
             b = self._hip.JpegBatch()
             b.n_images, b.subseq_bits, b.max_sync_passes = nb, subseq_bits, max_sync_passes
-            for k, v in tot.items():
-                setattr(b, k, v)
-            need = need_b = self.lib.odic_jpeg_workspace_bytes(ctypes.byref(b))
+            self._set_fields(b, plan.tot)
+            need_b = self.lib.odic_jpeg_workspace_bytes(ctypes.byref(b))
         if npg:
             pb = self._hip.JpegProgBatch()
             pb.n_images = npg
-            for k, v in ptot.items():
-                if isinstance(v, list):
-                    getattr(pb, k)[:len(v)] = v
-                else:
-                    setattr(pb, k, v)
+            self._set_fields(pb, plan.ptot)
             need_p = self.lib.odic_jpeg_progressive_workspace_bytes(ctypes.byref(pb))
             if need_p == 0:
                 raise RuntimeError("JPEG batch too large for one progressive decode call")
-            need = max(need, need_p)
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
-            self._jpeg_dev = self._grow(self._jpeg_dev, total, device=self.device)
-            self._jpeg_ws = self._grow(self._jpeg_ws, need, device=self.device)
-            self._jpeg_dev[:total].copy_(self._jpeg_pinned[:total], non_blocking=True)
+            self._jpeg_dev = self._grow(self._jpeg_dev, plan.total, device=self.device)
+            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p), device=self.device)
+            self._jpeg_dev[:plan.total].copy_(self._jpeg_pinned[:plan.total], non_blocking=True)
             self._jpeg_ev.record(self.stream)
             base = self._jpeg_dev.data_ptr()
+
+            def decode(name, batch, need, first):                        # `first`: the kind's first image in `scales`
+                args = [ctypes.byref(batch), self._jpeg_ws.data_ptr(), need, self.stream.cuda_stream]
+                if any(s > 1 for s in scales[first:first + batch.n_images]):
+                    name += "_scaled"
+                    args.insert(1, base + plan.scale_off + 4 * first)
+                self._hip.check(getattr(self.lib, name)(*args), name)
+
             if nb:
-                b.headers, b.data, b.out, b.status = base, base + data_off, rgb.data_ptr(), status.data_ptr()
-                if scaled_b:
-                    self._hip.check(self.lib.odic_jpeg_decode_scaled(
-                        ctypes.byref(b), base + scale_off, self._jpeg_ws.data_ptr(), need_b, self.stream.cuda_stream),
-                        "odic_jpeg_decode_scaled")
-                else:
-                    self._hip.check(self.lib.odic_jpeg_decode(ctypes.byref(b), self._jpeg_ws.data_ptr(), need_b,
-                                                              self.stream.cuda_stream), "odic_jpeg_decode")
+                b.headers, b.data, b.out, b.status = base, base + plan.data_off, rgb.data_ptr(), status.data_ptr()
+                decode("odic_jpeg_decode", b, need_b, 0)
             if npg:                                                      # second: its coefficients stay in the workspace
-                pb.headers, pb.scans, pb.tables = (base + o for o in prog_off)
-                pb.data, pb.out, pb.status = base + data_off, rgb.data_ptr() + out_bytes, status.data_ptr() + 4 * nb
-                if scaled_p:
-                    self._hip.check(self.lib.odic_jpeg_decode_progressive_scaled(
-                        ctypes.byref(pb), base + scale_off + 4 * nb, self._jpeg_ws.data_ptr(), need_p,
-                        self.stream.cuda_stream), "odic_jpeg_decode_progressive_scaled")
-                else:
-                    self._hip.check(self.lib.odic_jpeg_decode_progressive(
-                        ctypes.byref(pb), self._jpeg_ws.data_ptr(), need_p, self.stream.cuda_stream),
-                        "odic_jpeg_decode_progressive")
-                self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(pb)),
-                                        [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])])
+                pb.headers, pb.scans, pb.tables = (base + o for o in plan.prog_off)
+                pb.data, pb.out = base + plan.data_off, rgb.data_ptr() + plan.out_bytes
+                pb.status = status.data_ptr() + 4 * nb
+                decode("odic_jpeg_decode_progressive", pb, need_p, nb)
+                self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(pb)), plan.coef_off)
             st = self._jpeg_status[:4 * (nb + npg)].view(torch.int32)
             st.copy_(status, non_blocking=True)
         self.stream.synchronize()                                        # the one host synchronisation
         torch.cuda.current_stream().wait_stream(self.stream)
-        return st.numpy().copy(), rgb, out_offs
+        return st.numpy().copy(), rgb, plan.out_offs
 
     def progressive_coefficients(self, k: int) -> torch.Tensor:
         """Diagnostic: the int16 [blocks, 64] natural-order coefficients (MCU by MCU, DC as its value) of the k-th file
@@ -473,14 +429,7 @@ class DevicePreprocessor:
             for i, img in enumerate(imgs):
                 H, W, _ = img.shape
                 self._check_size(H, W)
-                if self._jpeg_tmp.numel() < H * S * 3:
-                    self._jpeg_tmp = torch.empty(H * S * 3, dtype=torch.uint8, device=self.device)
-                bx, kx, ksx = self._coeffs(W)
-                by, ky, ksy = self._coeffs(H)
-                self._hip.check(self.lib.odic_resize_bilinear_normalize(
-                    img.data_ptr(), H, W, 3 * W, bx.data_ptr(), kx.data_ptr(), ksx, by.data_ptr(), ky.data_ptr(), ksy,
-                    self._jpeg_tmp.data_ptr(), out[i].data_ptr(), S, self._mean, self._std, self.stream.cuda_stream),
-                    "odic_resize_bilinear_normalize")
+                self._jpeg_tmp = self._resize_whole(img.data_ptr(), H, W, self._jpeg_tmp, out[i])
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
 
@@ -517,16 +466,12 @@ class DevicePreprocessor:
             place, pos = {}, 0
             for i in used:
                 place[i] = (pos, 3 * images[i].shape[1])
-                pos += (images[i].numel() + 255) // 256 * 256
+                pos += _pad256(images[i].numel())
             gather_bytes = pos
         rec, bounds, coefs, tmp_bytes, max_rows = pack_resize_jobs(
             [(place[i][0], images[i].shape[0], images[i].shape[1], place[i][1], box) for i, box in regions], S)
-
-        def pad(n):
-            return (n + 255) // 256 * 256
-
-        off_b = pad(rec.nbytes)
-        off_k = off_b + pad(bounds.nbytes)
+        off_b = _pad256(rec.nbytes)
+        off_k = off_b + _pad256(bounds.nbytes)
         tables = np.zeros(off_k + coefs.nbytes, np.uint8)
         for o, a in ((0, rec), (off_b, bounds), (off_k, coefs)):
             tables[o:o + a.nbytes] = np.frombuffer(a.tobytes(), np.uint8)

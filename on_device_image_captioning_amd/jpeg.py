@@ -627,3 +627,64 @@ def pack_progressive(hdrs, blob_offs, scales=None):
     tot.update(n_scans=len(flat), n_tables=len(tables), n_levels=n_levels, level_first=level_first,
                level_intervals=level_intervals)
     return rec, srec, trec, tot, out_offs, out_bytes
+
+
+def pad256(n: int) -> int:
+    return (n + 255) // 256 * 256
+
+
+@dataclass
+class BatchPlan:
+    """One decode batch in the staging buffer that is uploaded in one copy (256-aligned record sections in the order
+    baseline headers, progressive headers / scans / tables, scales; then the files, baseline first) and in the output."""
+    sections: list                 # [(staging offset, record array)], by offset
+    data_off: int                  # the data area: what the records' data_off / data_end count from
+    blobs: list                    # [(staging offset, uint8 array)] of every file, baseline first
+    total: int                     # staging bytes
+    tot: dict                      # odic_jpeg_batch totals (`pack_headers`); None without baseline files
+    ptot: dict                     # odic_jpeg_prog_batch totals (`pack_progressive`); None without progressive files
+    prog_off: tuple                # staging offsets of the progressive headers, scans, tables; None without them
+    scale_off: int                 # staging offset of int32 scale_log2 [images]; None when every scale is 1
+    out_offs: list                 # byte offset of every image in the RGB output, baseline first
+    out_bytes: int                 # RGB bytes of the baseline files: the progressive output starts here
+    pout_bytes: int                # RGB bytes of the progressive files
+    coef_off: list                 # first coefficient block of every progressive file, then their total
+
+    def fill(self, host):
+        """Write the sections and the files into the uint8 array `host` of at least `total` bytes."""
+        for o, a in self.sections + self.blobs:
+            host[o:o + a.nbytes] = a.view(np.uint8)
+
+
+def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales) -> BatchPlan:
+    """The layout of one device decode of the baseline files (hdrs, blobs: DEVICE-kind `parse` results and their bytes)
+    and the progressive ones (phdrs, pblobs: `parse_progressive`).  scales: the draft scale of every image, baseline
+    first.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload."""
+    nb, npg = len(hdrs), len(phdrs)
+    sections, pos = [], pad256(nb * HEADER_DTYPE.itemsize)
+    ptot = prog_off = scale_off = None
+    if npg:                                              # sizes only, for now: the files' offsets follow from them
+        prec, srec, trec, ptot, pout_offs, pout_bytes = pack_progressive(phdrs, [0] * npg, scales[nb:])
+        prog_off = (pos, pos + pad256(prec.nbytes), pos + pad256(prec.nbytes) + pad256(srec.nbytes))
+        sections = list(zip(prog_off, (prec, srec, trec)))
+        pos = prog_off[2] + pad256(trec.nbytes)
+    if any(s > 1 for s in scales):
+        scale_off = pos
+        sections.append((pos, np.asarray([s.bit_length() - 1 for s in scales], np.int32)))
+        pos += pad256(4 * (nb + npg))
+    data_off = pos
+    starts = np.cumsum([0] + [len(b) for b in list(blobs) + list(pblobs)]).tolist()     # inside the data area
+    tot, out_offs, out_bytes = None, [], 0
+    if nb:
+        rec, tot, out_offs, out_bytes = pack_headers(hdrs, [o + h.data_offset for o, h in zip(starts, hdrs)],
+                                                     starts[1:nb + 1], subseq_bits, scales[:nb])
+        sections.insert(0, (0, rec))
+    if npg:
+        shift = np.asarray(starts[nb:-1], np.int64)[srec["image"]]
+        srec["data_off"] += shift
+        srec["data_end"] += shift
+        out_offs = out_offs + [out_bytes + o for o in pout_offs]
+    files = [(data_off + o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, list(blobs) + list(pblobs))]
+    coef_off = [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])] if npg else []
+    return BatchPlan(sections, data_off, files, data_off + starts[-1], tot, ptot, prog_off, scale_off, out_offs,
+                     out_bytes, pout_bytes if npg else 0, coef_off)
