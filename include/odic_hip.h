@@ -54,7 +54,7 @@ extern "C" {
  *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step).
  *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale).
  *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)). */
-#define ODIC_ABI_VERSION 23
+#define ODIC_ABI_VERSION 24
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -410,6 +410,25 @@ int odic_window_attention(const void* qkv, const float* bias_table, const float*
 int odic_swin_qkv_attention(const float* x, int64_t ldx, const void* w_qkv_folded, const float* b_qkv_folded,
                             const float* bias_shifted_prescaled, void* out, int32_t B, int32_t res, int32_t C,
                             int32_t heads, int32_t ws, int32_t shift, float scale, float ln_eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * qkv Linear → window attention core of one Swin block in ONE launch for the wide stages (WindowAttention.forward
+ * swin_transformer_mod.py:222-263 up to, not including, the proj Linear, with the shift / partition / reverse of :312-334):
+ *   xn       bf16 [B*res*res, C] compact   the norm1 output (token-major, un-shifted, un-partitioned)
+ *   w_qkv    bf16 [3C, C] compact, b_qkv fp32 [3C]   the qkv Linear, unpacked
+ *   bias_shifted_prescaled fp32 [heads, 4, 576]   as for odic_window_attention (required)
+ *   out      bf16 [B*res*res, C]   attention output at the un-shifted token positions (ready for the proj Linear); compact:
+ *            exactly B·res²·C elements are written
+ * One block is the tiled GEMM's 144 x 288 tile read as (window, three heads): q / k / v of a head never leave the chip.
+ * Results are bit-identical to odic_gemm(tile_cfg = 41, bf16 out) followed by odic_window_attention (bf16, packed bias).
+ * The tile is chosen by rule: the call is legal inside a stream capture at a shape never run before.
+ * ws = 12, head dim 32 (heads·32 = C), heads % 3 == 0, C % 64 == 0: ODIC_EUNSUPPORTED otherwise.  res % ws == 0,
+ * 0 <= shift < ws, xn / w_qkv / b_qkv / bias_shifted_prescaled 16-byte and out 8-byte aligned: ODIC_EINVAL otherwise.
+ * ODIC_ENULL for a null operand.  All before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int odic_swin_qkv_attention_tiled(const void* xn, const void* w_qkv, const float* b_qkv,
+                                  const float* bias_shifted_prescaled, void* out, int32_t B, int32_t res, int32_t C,
+                                  int32_t heads, int32_t ws, int32_t shift, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The MLP half of one Swin block in ONE launch (swin_transformer_mod.py:338: x + mlp(norm2(x))),

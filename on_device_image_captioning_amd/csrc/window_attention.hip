@@ -17,19 +17,20 @@
 // softmax is 36 in-register values + 2 shuffle steps.  Those registers are already the B operand
 // of Oᵀ = Vᵀ·Pᵀ (K index = key, permuted consistently on both operands), so P never touches LDS.
 //
-// Five kernels:
+// Six kernels:
 //   window_attention_f32_kernel       parity path: one thread per query row, K/V fp32 in LDS (broadcast reads),
 //                                     scores recomputed in two passes (max, then exp/sum/PV) — plain fp32 FMA chains.
 //   window_attention_bf16_kernel      bf16, bias from the (2ws-1)² table (what a NULL packed bias selects): K row-major,
 //                                     V transposed by the staging stores, Q straight into MFMA fragments.
 //   window_attention_bf16_v3_kernel   bf16 / fp16 with the packed bias: the tuned core ("the v3 core" below).
 //   swin_qkv_attention_kernel         norm1 → qkv → core in one launch for the width-192 stage.
+//   swin_qkv_attention_tiled_kernel   qkv → core in one launch for the wider stages: the tiled GEMM's 144 x 288 tile as (window, 3 heads).
 //   window_attention_h2_kernel        split-fp16 (hi + lo) activations, three MFMAs per contraction.
-// The last three run the same core ("the v3 core"): K row-major and chunk-swizzled, V row-major, zero-padded to 160 keys
+// All but the first two run the same core ("the v3 core"): K row-major and chunk-swizzled, V row-major, zero-padded to 160 keys
 // and read through ds_read_b64_tr_b16.  Shared helpers: window geometry, the slot → token map, the rows[] / rids[] fill,
 // the zeroed padding keys, the bias-initialised accumulators, the score MFMAs, the row max and the output store.  Block
-// map, bias staging, key-quad offsets, bias origin, V-fragment offset, mask, softmax and P·V are still text in each of the
-// three: as helpers each compiles to another instruction stream (profiles/r09_window_attention_core_bench.txt).
+// map, bias staging, key-quad offsets, bias origin, V-fragment offset, mask, softmax and P·V are still text in each of
+// them: as helpers each compiles to another instruction stream (profiles/r09_window_attention_core_bench.txt).
 #include "gemm_tile.h"        // gptr_t / lptr_t, wperm
 
 namespace {
@@ -357,8 +358,8 @@ template <bool F16> __device__ __forceinline__ unsigned short cvt16(float f) {
 }
 
 // ------------------------------------------------------------------------------------------------- the v3 core
-// Pieces of the core shared by window_attention_bf16_v3_kernel<F16>, swin_qkv_attention_kernel and
-// window_attention_h2_kernel.  Lane (fr, fq) = (lane & 15, lane >> 4) holds, for query fr of its tile, keys
+// Pieces of the core shared by window_attention_bf16_v3_kernel<F16>, swin_qkv_attention_kernel,
+// swin_qkv_attention_tiled_kernel and window_attention_h2_kernel.  Lane (fr, fq) = (lane & 15, lane >> 4) holds, for query fr of its tile, keys
 // 16kt + 4fq + {0..3} of the nine key tiles in sc[9].  Only helpers that leave every kernel's instruction stream as it was
 // are here.  The block map, bias staging, key-quad offsets, bias origin, V-fragment offset, mask, softmax and P·V were each
 // shown to change it and stay as text in each kernel until they are timed on the device
@@ -790,6 +791,265 @@ __global__ __launch_bounds__(576, 1) void swin_qkv_attention_kernel(FusedParams 
 
 
 // =================================================================================================
+// qkv product → attention core in ONE launch for the wide stages (C = 384 / 768 / 1536): the bf16 qkv tensor [B·L, 3C] —
+// 42.5 MB at stage 2, B = 16 — is never written and never gathered back.
+//
+// The tile is the tiled GEMM's configuration 41 (gemm_bf16_nt_kernel<3,3,3,6,2,64>: 144 x 288, nine waves, two 54-KiB
+// stages) read as a window: its 144 rows are the 144 tokens of ONE 12 x 12 window (the LDS-DMA source rows come from
+// slot_to_token, cyclic shift included — nothing is permuted in memory), its 288 columns are q | k | v (32 channels each) of
+// THREE heads.  Tile column j = LDS row j of the W image is wave column j / 96, part u = (j % 96) / 32, channel j % 32:
+// source row u·C + (3·tn + wn)·32 + wperm(channel) of the unpacked qkv weight.  Wave (wm, wn) of the 3 x 3 grid leaves the
+// K loop with q, k, v of head 3·tn + wn for the window's slots 48·wm .. 48·wm + 47, and with the swapped-operand layout a
+// lane's accumulator pair (2u, 2u + 1) of row tile mi is slot 48·wm + 16·mi + frow, channels 8·fq .. 8·fq + 7 of part u:
+// pair 0 IS the Q fragment of the score MFMA, pairs 1 and 2 are 16 bytes of the head's K and V images.
+//   * the K loop is configuration 41's, statement for statement (two stages, BK = 64, vmcnt + raw s_barrier, the same
+//     fragment reads and MFMA order): every accumulator is the chain the tiled GEMM computes for that element;
+//   * under the LAST K-tile the three heads' packed bias copies (3 x 9 KiB) arrive by LDS-DMA in the stage buffer the loop
+//     has finished with;
+//   * after the loop: acc + bias rounded to bf16 (the tiled epilogue's acc·alpha + bias with alpha = 1: the bits of the
+//     stored qkv tensor), barrier, K (chunk-swizzled) and V (+ zeroed padding keys) written over the stage buffers, barrier;
+//   * each wave runs the v3 core on its three query tiles against its head's 144 keys.
+// LDS after the loop: free stage = bias 3 x 9216 | K 3 x 9216 (= 55296, exactly one stage), other stage = V 3 x 10240;
+// rows[] / rids[] live in the tail behind the stages (config 41's footprint, 111744 B, is kept).
+// Grid: config 41's XCD rectangle walk with tile row = window, tile column = head group.
+// Bit-identical to odic_gemm(tile_cfg 41) + odic_window_attention (bf16, packed bias):
+// tests/test_swin_qkv_attention_tiled_gpu.py.
+// =================================================================================================
+struct TiledParams {
+  const bf16_raw* A; const bf16_raw* W; const float* bqkv; const float* bias_shifted; bf16_raw* out;
+  WinGeom g;
+  TileGrid grid;
+};
+
+constexpr int QT_ROWB = 128, QT_A_BYTES = 144 * QT_ROWB, QT_W_BYTES = 288 * QT_ROWB, QT_STAGE = QT_A_BYTES + QT_W_BYTES;
+constexpr int QT_KIMG = MAXN * HD * 2, QT_VIMG = (MAXN + 16) * HD * 2, QT_BIMG = 4 * BS_COPY * 4;
+constexpr int QT_SHMEM = 2 * QT_STAGE + 144 * 8;             // configuration 41's footprint; the tail holds rows[] / rids[]
+static_assert(3 * QT_BIMG + 3 * QT_KIMG <= QT_STAGE && 3 * QT_VIMG <= QT_STAGE, "the core's images reuse the two stages");
+static_assert(MAXN * 4 + MAXN <= 144 * 8, "rows[] and rids[] fit the tail");
+
+__global__ __launch_bounds__(576, 1) void swin_qkv_attention_tiled_kernel(TiledParams p) {
+  constexpr int NW = 9, NWN = 3, MI = 3, NI = 6, BK = 64;
+  constexpr int ROWB = QT_ROWB, A_BYTES = QT_A_BYTES, STAGE = QT_STAGE;
+  constexpr int A_INSTR = 2, W_INSTR = 4;                    // 1-KiB DMA instructions per wave and K-tile (8 rows each)
+  extern __shared__ __attribute__((aligned(16))) char lds[];          // stage0 {A,W} | stage1 {A,W} | rows[144] | rids[144]
+  int* rows = (int*)(lds + 2 * STAGE);
+  unsigned char* rids = (unsigned char*)(rows + MAXN);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / NWN, wn = wave % NWN;
+  ODIC_ENCODE_PRIO();
+
+  // XCD x = blockIdx % 8 owns tile rows [r0,r1) x cols [c0,c1); inside the rectangle tiles run N-fastest
+  int tm, tn;
+  {
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    const int xm = xcd / p.grid.pn, xn = xcd - xm * p.grid.pn;
+    const int r0 = xm * p.grid.tiles_m / p.grid.pm, r1 = (xm + 1) * p.grid.tiles_m / p.grid.pm;
+    const int c0 = xn * p.grid.tiles_n / p.grid.pn, c1 = (xn + 1) * p.grid.tiles_n / p.grid.pn;
+    const int w = c1 - c0;
+    if (idx >= (r1 - r0) * w) return;
+    const int lr = idx / w;
+    tm = r0 + lr; tn = c0 + (idx - lr * w);
+  }
+  const int C = p.g.C;
+  const Window w = window_of(p.g, tm);
+  const bool masked = on_shift_seam(p.g, w);
+  const int head = 3 * tn + wn;
+  stage_rows(p.g, w, tid, rows, rids);                      // read after the loop: its barriers order the writes
+
+  // ---- LDS-DMA source addresses: instruction i of this wave fills rows (i*NW+wave)*8 .. +7
+  const int srow = lane >> 3;
+  const int schunk = swz<ROWB>(lane & 7, srow);
+  const bf16_raw* a_src[A_INSTR];
+  const bf16_raw* w_src[W_INSTR];
+#pragma unroll
+  for (int i = 0; i < A_INSTR; ++i) {
+    long r; int rid;
+    slot_to_token(p.g, w, (i * NW + wave) * 8 + srow, r, rid);
+    a_src[i] = p.A + r * C + schunk * 8;
+  }
+#pragma unroll
+  for (int i = 0; i < W_INSTR; ++i) {
+    const int row = (i * NW + wave) * 8 + srow;              // tile column: wave column row / 96, part, channel
+    const int wc = row / 96, rem = row - wc * 96;
+    w_src[i] = p.W + (long)((rem >> 5) * C + (3 * tn + wc) * HD + wperm(rem & 31)) * C + schunk * 8;
+  }
+
+  auto stage = [&](int buf, int kt) {
+    char* la = lds + buf * STAGE;
+    char* lw = la + A_BYTES;
+#pragma unroll
+    for (int i = 0; i < A_INSTR; ++i)
+      __builtin_amdgcn_global_load_lds((gptr_t)(a_src[i] + (long)kt * BK), (lptr_t)(la + (i * NW + wave) * 1024), 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < W_INSTR; ++i)
+      __builtin_amdgcn_global_load_lds((gptr_t)(w_src[i] + (long)kt * BK), (lptr_t)(lw + (i * NW + wave) * 1024), 16, 0, 0);
+  };
+
+  f32x4_t acc[MI][NI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = C / BK;
+  const int frow = lane & 15, fq = lane >> 4;
+  // after the loop: the stage tile nk-1 does not use holds bias | K, the other one V
+  char* Bp = lds + (nk & 1) * STAGE;
+  char* Kp = Bp + 3 * QT_BIMG;
+  char* Vp = lds + ((nk & 1) ^ 1) * STAGE;
+
+  stage(0, 0);
+  for (int kt = 0; kt < nk; ++kt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (kt + 1 < nk) {
+      stage((kt + 1) & 1, kt + 1);
+    } else {
+      // last K-tile: the other stage is free — the three heads' bias copies, 27 x 1 KiB, three per wave
+      const float* bsrc = p.bias_shifted + (long)(3 * tn) * 4 * BS_COPY + lane * 4;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        __builtin_amdgcn_global_load_lds((gptr_t)(bsrc + (i * NW + wave) * 256), (lptr_t)(Bp + (i * NW + wave) * 1024), 16, 0, 0);
+    }
+
+    const int cur = kt & 1;
+    const char* la = lds + cur * STAGE + (wm * MI * 16 + frow) * ROWB;
+    const char* lw = lds + cur * STAGE + A_BYTES + (wn * NI * 16 + frow) * ROWB;
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+      bf16x8_t af[MI], wf[NI];
+      const int chunk = swz<ROWB>(kk * 4 + fq, frow) << 4;
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) af[mi] = *(const bf16x8_t*)(la + mi * 16 * ROWB + chunk);
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) wf[ni] = *(const bf16x8_t*)(lw + ni * 16 * ROWB + chunk);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni], af[mi], acc[mi][ni], 0, 0, 0);
+    }
+  }
+
+  // ---- q, k, v of this wave's 48 slots, head `head`: acc + bias → bf16 (the stored qkv tensor's bits)
+  bf16x8_t qf[MI], kf8[MI], vf8[MI];
+  {
+    f32x4_t bc[3][2];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const f32x4_t* bp = (const f32x4_t*)(p.bqkv + u * C + head * HD + fq * 8);
+      bc[u][0] = bp[0]; bc[u][1] = bp[1];
+    }
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      bf16x8_t o[3];
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {
+        const f32x4_t v0 = acc[mi][2 * u] * 1.0f + bc[u][0], v1 = acc[mi][2 * u + 1] * 1.0f + bc[u][1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o[u][e] = (short)f32_to_bf16(v0[e]); o[u][4 + e] = (short)f32_to_bf16(v1[e]); }
+      }
+      qf[mi] = o[0]; kf8[mi] = o[1]; vf8[mi] = o[2];
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();                             // every wave is past its last fragment read: the stages are free
+  {
+    char* kimg = Kp + wn * QT_KIMG;
+    char* vimg = Vp + wn * QT_VIMG;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const int slot = (wm * MI + mi) * 16 + frow;
+      *(bf16x8_t*)(kimg + slot * HD * 2 + ((fq ^ ((frow >> 2) & 3)) << 4)) = kf8[mi];
+      *(bf16x8_t*)(vimg + slot * HD * 2 + (fq << 4)) = vf8[mi];
+    }
+    if (tid < 3 * 128) ((unsigned long long*)(Vp + (tid >> 7) * QT_VIMG + MAXN * HD * 2))[tid & 127] = 0ull;   // padding keys
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();                             // the three heads' K / V images and bias copies are complete
+
+  // ---- the v3 core on this wave's three query tiles
+  const float scale2 = p.g.scale * 1.4426950408889634f;
+  const float mask_acc = 100.0f / p.g.scale;
+  const int voff = ((4 * fq + (frow >> 2)) * HD + 4 * (frow & 3)) * 2;
+  int koffs[9];
+#pragma unroll
+  for (int kt = 0; kt < 9; ++kt) {
+    const int key0 = kt * 16 + fq * 4;
+    const int jy = key0 / 12, jx0 = key0 - jy * 12;
+    koffs[kt] = (jx0 - jy * 24) * 4;
+  }
+  auto bias_base = [&](int qn) -> int {
+    const int iy = qn / 12, ix = qn - iy * 12;
+    const int s = (11 - ix) & 3;
+    return (s * BS_COPY + (iy + 11) * 24 + 11 - ix - s) * 4;
+  };
+#pragma unroll
+  for (int qt = 0; qt < 3; ++qt) {
+    const int qn = (wm * 3 + qt) * 16 + frow;
+    const int orow = rows[qn];
+    int koff = (frow * HD + ((fq ^ ((frow >> 2) & 3)) * 8)) * 2, vo = voff, bb = bias_base(qn);
+    opaque_offsets(koff, vo, bb);
+    const char* kbase = Kp + wn * QT_KIMG + koff;
+    const char* vbase = Vp + wn * QT_VIMG + vo;
+    const char* bbase = Bp + wn * QT_BIMG + bb;
+    f32x4_t sc[9];
+    load_bias36(bbase, koffs, sc);
+    scores16<false>(kbase, qf[qt], sc);
+    if (masked) {
+      const unsigned my = rids[qn];
+#pragma unroll
+      for (int kt = 0; kt < 9; ++kt) {
+        const unsigned kr = *(const unsigned*)&rids[kt * 16 + fq * 4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (((kr >> (8 * j)) & 0xff) != my) sc[kt][j] -= mask_acc;
+      }
+    }
+    const float m = row_max36(sc);
+    const f32x2_t s2 = {scale2, scale2};
+    const f32x2_t c2 = {-m * scale2, -m * scale2};
+    f32x2_t lsum = {0.f, 0.f};
+    bf16x4_t pk[9];
+#pragma unroll
+    for (int kt = 0; kt < 9; ++kt) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x2_t a = f32x2_t{sc[kt][2 * h], sc[kt][2 * h + 1]} * s2 + c2;
+        const f32x2_t e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+        lsum += e;
+        pk[kt][2 * h] = (short)f32_to_bf16(e[0]);
+        pk[kt][2 * h + 1] = (short)f32_to_bf16(e[1]);
+      }
+    }
+    float l = lsum[0] + lsum[1];
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv_l = __builtin_amdgcn_rcpf(l);
+    f32x4_t oacc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int s5 = 0; s5 < 5; ++s5) {
+      const bf16x4_t lo4 = pk[2 * s5];
+      const bf16x4_t hi4 = s5 < 4 ? pk[2 * s5 + (s5 < 4)] : bf16x4_t{0, 0, 0, 0};
+      const bf16x8_t pf = bf16x8_t{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) v4s_t*)(vbase + (32 * s5) * HD * 2 + nt * 32));
+        const v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) v4s_t*)(vbase + (32 * s5 + 16) * HD * 2 + nt * 32));
+        const bf16x8_t vf = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        oacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[nt], 0, 0, 0);
+      }
+    }
+    store_o16<false>(p.out + (long)orow * C + head * HD + fq * 4, oacc, inv_l);
+  }
+}
+
+
+// =================================================================================================
 // Split-fp16 ("h2") flavour of the v3 kernel — the attention core of the near-exact fast mode (`precision='x3'`).
 // q, k, v arrive as hi + lo fp16 pairs (odic_common.h; a head's 32 channels are 128 bytes: [8 hi | 8 lo] x 4) and
 // both contractions run as three fp16 MFMAs each:  S = Kh·Qh + Kh·Ql + Kl·Qh,  O = Vh·Ph + Vh·Pl + Vl·Ph  with
@@ -1015,5 +1275,25 @@ extern "C" int odic_swin_qkv_attention(const float* x, int64_t ldx, const void* 
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM); done = true; }
   hipLaunchKernelGGL(k, dim3(B * p.g.nwin_side * p.g.nwin_side), dim3(576), SHMEM, (hipStream_t)stream, p);
+  return odic_launch_status();
+}
+
+/* qkv Linear → attention core of one Swin block in one launch for the wide stages (see swin_qkv_attention_tiled_kernel). */
+extern "C" int odic_swin_qkv_attention_tiled(const void* xn, const void* w_qkv, const float* b_qkv,
+                                             const float* bias_shifted_prescaled, void* out, int32_t B, int32_t res,
+                                             int32_t C, int32_t heads, int32_t ws, int32_t shift, float scale, void* stream) {
+  if (!xn || !w_qkv || !b_qkv || !bias_shifted_prescaled || !out) return ODIC_ENULL;
+  if (B <= 0 || res <= 0 || ws <= 0 || heads <= 0 || res % ws || shift < 0 || shift >= ws) return ODIC_EINVAL;
+  if (ws != 12 || heads * HD != C || heads % 3 || C % 64) return ODIC_EUNSUPPORTED;
+  if (((uintptr_t)xn & 15) || ((uintptr_t)w_qkv & 15) || ((uintptr_t)out & 7) || ((uintptr_t)bias_shifted_prescaled & 15) ||
+      ((uintptr_t)b_qkv & 15) || (long)B * res * res >= 2147483647L)
+    return ODIC_EINVAL;
+  TiledParams p = {(const bf16_raw*)xn, (const bf16_raw*)w_qkv, b_qkv, bias_shifted_prescaled, (bf16_raw*)out,
+                   {B, res, C, heads, ws, shift, res / ws, scale}, {}};
+  // one tile form, chosen by rule (legal inside a stream capture at a shape never run before): configuration 41's grid
+  const long M = (long)B * res * res;
+  const int max_rect = tile_grid(p.grid, (int)M, 3 * C, 144, 288, (double)M * C * 2.0, 3.0 * C * C * 2.0, 32);
+  tile_allow_lds<QT_SHMEM, swin_qkv_attention_tiled_kernel>();
+  hipLaunchKernelGGL(swin_qkv_attention_tiled_kernel, dim3(8 * max_rect), dim3(576), QT_SHMEM, (hipStream_t)stream, p);
   return odic_launch_status();
 }

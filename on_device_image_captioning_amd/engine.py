@@ -106,6 +106,11 @@ class SwinEngine:
         lr = os.environ.get("ODIC_FUSE_BACKBONE_LN_READ", "1")
         self.ln_read = (precision == "bf16" and lr != "0") or (precision == "x3" and lr == "x3")
         self.fuse_qkv_attn = precision == "bf16" and os.environ.get("ODIC_FUSE_QKV_ATTENTION", "1") == "1"
+        # bf16 mode, the wider stages: qkv → attention core as ONE launch on the LayerNorm output (odic_swin_qkv_attention_tiled,
+        # DESIGN.md §4.3): the qkv tensor is never written.  ODIC_FUSE_QKV_ATTENTION_TILED=0 keeps the two launches.
+        self.fuse_qkv_attn_tiled = precision == "bf16" and os.environ.get("ODIC_FUSE_QKV_ATTENTION_TILED", "1") == "1"
+        # (from width 768 up — Swin-L stages 2 and 3; ODIC_FUSE_QKV_ATTENTION_TILED_MIN_C=384 adds stage 1, measured in §4.3)
+        self.fuse_qkv_attn_tiled_min_c = int(os.environ.get("ODIC_FUSE_QKV_ATTENTION_TILED_MIN_C", "768"))
         # bf16 mode, width 192: norm2 → fc1 → GELU → fc2 + residual as ONE launch (odic_swin_mlp); it
         # uses the folded fc1 weights of the LayerNorm-while-reading form.  ODIC_FUSE_MLP=0 keeps the two launches.
         self.fuse_mlp = precision == "bf16" and os.environ.get("ODIC_FUSE_MLP", "1") == "1"
@@ -234,9 +239,16 @@ class SwinEngine:
                     xn = ops.layernorm(x, w["n1w"], w["n1b"], out_dtype=cdt)
                     if _amax is not None:
                         _amax[(s, bi, "ln1")] = float(xn.float().abs().max())
-                    qkv = ops.gemm(xn, w["qkv_w"], w["qkv_b"], alpha=w["qkv_a"])
-                    att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
-                                               bias_shifted_prescaled=w["dense"])
+                    if (self.fuse_qkv_attn_tiled and _amax is None and w["dense"] is not None and w["qkv_a"] == 1.0
+                            and C_ >= self.fuse_qkv_attn_tiled_min_c
+                            and ops.swin_qkv_attention_tiled_supported(x.shape[0], C_, heads, ws, res, cdt)):
+                        # qkv → attention core: one launch, q / k / v never leave the chip
+                        att = ops.swin_qkv_attention_tiled(xn, w["qkv_w"], w["qkv_b"], w["dense"], B, res, C_, heads, ws,
+                                                           w["shift"])
+                    else:
+                        qkv = ops.gemm(xn, w["qkv_w"], w["qkv_b"], alpha=w["qkv_a"])
+                        att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
+                                                   bias_shifted_prescaled=w["dense"])
                     ops.gemm(att, w["proj_w"], w["proj_b"], residual=x, out=x, alpha=w["proj_a"])
                     xn = ops.layernorm(x, w["n2w"], w["n2b"], out_dtype=cdt)
                     h = ops.gemm(xn, w["fc1_w"], w["fc1_b"], act=ops.ACT_GELU, alpha=w["fc1_a"])

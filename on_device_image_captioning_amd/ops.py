@@ -455,6 +455,34 @@ def swin_qkv_attention(x: torch.Tensor, w_folded: torch.Tensor, b_folded: torch.
     return out
 
 
+def swin_qkv_attention_tiled_supported(M: int, C_: int, heads: int, ws: int, res: int, dtype=torch.bfloat16) -> bool:
+    """Shapes odic_swin_qkv_attention_tiled takes: bf16, 12 x 12 windows, head dim 32, heads in threes, width a multiple
+    of 64, whole windows.  (One tile form, chosen by this rule and not by a timed run: the call is legal inside a stream
+    capture at a shape never run before.)"""
+    return (dtype == torch.bfloat16 and ws == 12 and heads > 0 and heads * 32 == C_ and heads % 3 == 0 and C_ % 64 == 0
+            and res > 0 and res % ws == 0 and M > 0 and M % (res * res) == 0)
+
+
+def swin_qkv_attention_tiled(xn: torch.Tensor, w_qkv: torch.Tensor, b_qkv: torch.Tensor, bias_shifted_prescaled: torch.Tensor,
+                             B: int, res: int, C_: int, heads: int, ws: int, shift: int, *,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qkv → attention core in one launch (odic_swin_qkv_attention_tiled; widths 384 / 768 / 1536, ws 12).  xn bf16
+    [B·res², C] contiguous (the norm1 output), w_qkv bf16 [3C, C] contiguous, b_qkv fp32 [3C] → bf16 [B·res², C]."""
+    _need_cuda(xn, w_qkv, b_qkv, bias_shifted_prescaled, out)
+    if (xn.dtype != torch.bfloat16 or w_qkv.dtype != torch.bfloat16 or not (xn.is_contiguous() and w_qkv.is_contiguous())
+            or xn.numel() != B * res * res * C_ or w_qkv.numel() != 3 * C_ * C_):
+        raise RuntimeError("swin_qkv_attention_tiled: contiguous bf16 rows [B·res², C] and a contiguous bf16 weight [3C, C]")
+    if out is None:
+        out = torch.empty(B * res * res, C_, dtype=torch.bfloat16, device=xn.device)
+    nwh = B * (res // ws) ** 2 * heads if ws > 0 else 0
+    with _timed("swin_qkv_attention", 2.0 * B * res * res * C_ * 3 * C_ + nwh * 2654208.0,
+                B * res * res * C_ * (2 + 2) + 3 * C_ * C_ * 2 + 3 * C_ * 4 + heads * 9216, f"res{res}h{heads}"):
+        _hip.check(_hip.load().odic_swin_qkv_attention_tiled(_p(xn), _p(w_qkv), _p(b_qkv), _p(bias_shifted_prescaled), _p(out),
+                                                            B, res, C_, heads, ws, shift, (C_ // heads) ** -0.5 if heads > 0 else 0.0,
+                                                            _stream()), "odic_swin_qkv_attention_tiled")
+    return out
+
+
 def swin_mlp_supported(M: int, C_: int, dtype=torch.bfloat16) -> bool:
     """Shapes odic_swin_mlp takes: bf16 weights, width 192, whole 128-row panels.  (One tile form, chosen by this rule
     and not by a timed run: the call is legal inside a stream capture at a shape never run before.)"""
