@@ -53,8 +53,9 @@ extern "C" {
 /* ABI version of this header; bumped on any signature change.
  *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step).
  *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale).
- *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)). */
-#define ODIC_ABI_VERSION 24
+ *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)).
+ *   25: odic_group_beam_step added (diverse beam search: groups with a Hamming penalty). */
+#define ODIC_ABI_VERSION 25
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -646,7 +647,8 @@ int odic_topk_rows(const float* logp, int64_t ldl, float* top_val, int32_t* top_
  *   done int32 scalar (set to 1 when every beam has stopped growing, :222).
  * All of these are compact arrays without leading dimensions.  The search-level test
  * test_pipeline_search_is_independent_of_the_previous_search pins that a search reads nothing a previous search left in them;
- * no guarded-buffer test covers the beam kernels' stores yet.
+ * tests/test_group_beam_gpu.py runs odic_group_beam_step (which shares the update
+ * half of odic_beam_step) with every array inside a guarded buffer.
  */
 typedef struct odic_beam_state {
   int64_t* tokens; float* logprobs; int32_t* anc;
@@ -668,6 +670,32 @@ typedef struct odic_embed_args {
 int odic_beam_step(const float* cand_val, const int32_t* cand_idx, const odic_beam_state* st,
                    const odic_embed_args* emb, int32_t n_img, int32_t beams, int32_t T, int64_t eos_idx,
                    void* stream);
+
+/* The step of diverse (group) beam search (Vijayakumar et al., "Diverse Beam Search"), the sibling of odic_beam_step
+ * on the same state: the R = groups·group_beams rows of an image are `groups` groups of `group_beams` beams, rows
+ * g·group_beams .. (g+1)·group_beams - 1 being group g, and a beam's parent is always a row of its own group.
+ *   cand_val / cand_idx [n_img·R, ncand], compact, as odic_logsoftmax_topk writes them with k = R (value descending, then
+ *   word ascending); ncand must equal R.
+ * Within one step the groups choose one after the other.  count[w] = the number of beams of groups 0..g-1 that
+ * appended word w at this step and had not finished before it.  A growing beam j of group g offers word w at
+ *   v = logp_j(w) - penalty·count[w],   total = cumul_j + v
+ * (three separately rounded fp32 operations); a finished beam offers its rank-0 candidate at 0 and the others at -999,
+ * never penalised, as in odic_beam_step.  The group keeps its group_beams best candidates: total descending, then beam
+ * in group ascending, then word ascending (at groups = 1 the rule of odic_beam_step; the call then leaves the state
+ * bitwise as odic_beam_step does).  At *pos == 0 group g draws from its own first row (all rows hold the same
+ * distribution) against the seeds of the groups before it.  The penalty only steers the choice: logprobs[.., pos+1] is
+ * the word's own log-prob and cumul the re-summed unpenalised prefix, so odic_beam_finalize scores the captions by the
+ * model alone.  R candidates per row suffice: the penalised top-group_beams of a row lies inside its unpenalised
+ * top-(group_beams + P), P <= g·group_beams <= R - group_beams being the number of penalised words.
+ * Everything else (permutation of prefixes / log-probs / ancestors, embedding tail, n_elem, has_eos, row_valid,
+ * next_tok, *pos, *done, the arrival counter) is odic_beam_step's, with its limits on T and n_img.
+ *   ODIC_EINVAL: groups < 1, group_beams < 1, R > 16, ncand != R, penalty negative or not finite, T / n_img outside
+ *   odic_beam_step's limits.  A refused call writes nothing.  All stores stay inside the compact state arrays and
+ *   columns [0, d) of the R·n_img rows of emb->y (tests/test_group_beam_gpu.py). */
+int odic_group_beam_step(const float* cand_val, const int32_t* cand_idx, int32_t ncand,
+                         const odic_beam_state* st, const odic_embed_args* emb,
+                         int32_t n_img, int32_t groups, int32_t group_beams, int32_t T,
+                         int64_t eos_idx, float penalty, void* stream);
 
 /* Initial state of a search (captioning_model.py:117-125): tokens[:, :, 0] = sos, logprobs[:, :, 0] = 0,
  * next_tok = sos, row_valid = 1, *pos = *done = *ctr = 0; with emb, also the input of position 0 (the embedded

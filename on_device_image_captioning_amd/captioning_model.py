@@ -42,6 +42,7 @@ class CaptioningModel(nn.Module):
         self.sampling_seed = 0              # Philox key of the device-side draws ('sample' / 'sampling' modes)
         self._sampling_calls = 0
         self._draw_log = None               # list → every sampled-beam-search draw is appended (tests)
+        self._cand_log = None               # list → every diverse-search step's (cand_val, cand_idx) is appended (tests)
 
     # ------------------------------------------------------------------ engine cache plumbing
     def check_required_attributes(self):
@@ -318,6 +319,13 @@ class CaptioningModel(nn.Module):
             return self.get_batch_multiple_sampled_prediction(
                 enc_x, enc_x_num_pads, num_outputs=kwargs.get("how_many_outputs", 1), sos_idx=sos_idx,
                 eos_idx=eos_idx, max_seq_len=kwargs.get("sample_max_seq_len", 20))
+        if mode == "diverse_beam_search":
+            return self.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
+                                            num_groups=kwargs.get("num_groups", 3),
+                                            group_size=kwargs.get("group_size", 3),
+                                            diversity_penalty=kwargs.get("diversity_penalty", 0.5),
+                                            how_many_outputs=kwargs.get("how_many_outputs", None),
+                                            max_seq_len=kwargs.get("beam_max_seq_len", 20))
         raise ValueError(f"unknown mode {mode!r}")
 
     def get_batch_multiple_sampled_prediction(self, enc_input, enc_input_num_pads, num_outputs, sos_idx, eos_idx,
@@ -428,6 +436,62 @@ class CaptioningModel(nn.Module):
         lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
         return res_tok, lp
 
+    def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
+                            diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20):
+        """Diverse (group) beam search (Vijayakumar et al.): `num_groups` groups of `group_size` beams per image.
+        Within a step the groups choose one after the other, and a group pays `diversity_penalty` for every earlier
+        group that appended the same word at this step (odic_group_beam_step).  The penalty only steers
+        the choice: the returned log-probs and the ranking (sum of log-probs / length) are the model's own.
+        Output j of an image is the best beam of group j (ties → the lower row), in group order — output 0 is what
+        beam_search(beam_size=group_size) returns, group 0 never being penalised.  `how_many_outputs` defaults to
+        num_groups and may not exceed it.  Returns what beam_search returns: a token list per image and output, and
+        the padded per-token log-probs [B, how_many_outputs, longest]."""
+        if how_many_outputs is None:
+            how_many_outputs = num_groups
+        if num_groups < 1 or group_size < 1 or num_groups * group_size > 16:
+            raise ValueError("diverse_beam_search needs num_groups >= 1, group_size >= 1 and num_groups·group_size <= 16")
+        if not 1 <= how_many_outputs <= num_groups:
+            raise ValueError("requested outputs per image must lie in [1, num_groups]: a group yields one caption")
+        penalty = float(diversity_penalty)
+        if not (0.0 <= penalty < float("inf")):
+            raise ValueError("diversity_penalty must be finite and >= 0")
+        mem = self.forward_enc(enc_input, enc_input_num_pads)
+        eng = self._captioner_engine()
+        dv = eng.device
+        B, S, _ = mem.shape
+        G, kg = int(num_groups), int(group_size)
+        R = G * kg
+        if R > eng.g.vocab_size:
+            raise ValueError(f"{R} beams per image exceed the vocabulary ({eng.g.vocab_size} words)")
+        steps = max(1, max_seq_len - 1)
+        T = steps + 1
+        st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
+        ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
+        for t in range(steps):
+            eng.group_beam_step(st, eos_idx, G, penalty)
+            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
+                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
+            if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(st.done.item()):
+                break
+        order = torch.empty(B, R, dtype=torch.int32, device=dv)
+        score = torch.empty(B, R, dtype=torch.float32, device=dv)
+        ops.beam_finalize(st.beam_state, order, score, B, R)
+        best = score.view(B, G, kg).cpu().argmax(dim=2)           # (first maximum: ties go to the lower row)
+        n_elem_h = st.n_elem.view(B, R).cpu()
+        tokens_h = st.tokens.cpu()
+        res_tok: List[List[List[int]]] = []
+        lp_rows = []
+        for b in range(B):
+            per = []
+            for j in range(how_many_outputs):
+                i = j * kg + int(best[b, j])
+                n = int(n_elem_h[b, i])
+                per.append(tokens_h[b, i, :n].tolist())
+                lp_rows.append(st.logprobs[b, i, :n])
+            res_tok.append(per)
+        lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
+        return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+
 
 def _as_list(pads, n: int) -> List[int]:
     if isinstance(pads, torch.Tensor):
@@ -476,6 +540,13 @@ class Captioner:
             return self.model.get_batch_multiple_sampled_prediction(
                 enc_x, enc_x_num_pads, num_outputs=a.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
                 max_seq_len=a.get("sample_max_seq_len", 20))
+        if mode == "diverse_beam_search":
+            self.apply_log_softmax = True
+            return self.model.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
+                                                  num_groups=a.get("num_groups", 3), group_size=a.get("group_size", 3),
+                                                  diversity_penalty=a.get("diversity_penalty", 0.5),
+                                                  how_many_outputs=a.get("how_many_outputs", None),
+                                                  max_seq_len=a.get("beam_max_seq_len", 20))
         raise ValueError(f"unknown mode {mode!r}")
 
     def forward_enc(self, enc_input, enc_input_num_pads):
@@ -487,6 +558,9 @@ class Captioner:
 
     def beam_search(self, *a, **k):
         return self.model.beam_search(*a, **k)
+
+    def diverse_beam_search(self, *a, **k):
+        return self.model.diverse_beam_search(*a, **k)
 
     def score_captions(self, *a, **k):
         return self.model.score_captions(*a, **k)

@@ -11,6 +11,7 @@
 //   cross_attn_step_kernel   MultiHeadAttention against per-image cached K/V (layers.py:266-295)
 //   logsoftmax_topk_kernel   log_softmax over the vocabulary + top-k (captioning_model.py:162-170)
 //   beam_step_kernel         candidate masking, k·k selection, prefix/ancestor re-gather (:172-223)
+//   group_beam_step_kernel   the same step for diverse (group) beam search: groups choose in turn, Hamming penalty
 //   beam_finalize_kernel     length-normalised ranking (:225-227)
 #include "odic_common.h"
 
@@ -695,9 +696,13 @@ struct BeamShared {
   int parent[MAX_K]; int word[MAX_K]; float lp[MAX_K]; float cumul[MAX_K];
 };
 
-// s.cv / s.ci hold the k x k candidates (written by this block; a barrier follows inside)
-__device__ __forceinline__ void beam_update(const BeamParams& p, const EmbedArgs& e, BeamShared& s, int b, int t) {
-  constexpr int NT = 256;                              // threads of beam_step_kernel
+constexpr int BEAM_NT = 256;                           // threads of beam_step_kernel / group_beam_step_kernel
+
+// The three parts of a step, shared by beam_step_kernel and group_beam_step_kernel: beam_load_rows (per-beam flags and
+// per-token log-probs of the image into LDS; ends with a barrier that also covers the caller's s.cv / s.ci),
+// a selection by wave 0 that fills s.parent (row within the image) / s.word / s.lp, and beam_apply (everything after).
+__device__ __forceinline__ void beam_load_rows(const BeamParams& p, BeamShared& s, int b, int t) {
+  constexpr int NT = BEAM_NT;
   const int tid = threadIdx.x, k = p.k, T = p.T;
   for (int r = tid; r < k; r += NT) {
     s.eos[r] = p.has_eos[b * k + r]; s.ne[r] = p.n_elem[b * k + r]; s.cu[r] = p.cumul[b * k + r];
@@ -707,7 +712,11 @@ __device__ __forceinline__ void beam_update(const BeamParams& p, const EmbedArgs
     s.lpm[r][j] = p.lp[((long)b * k + r) * T + j];
   }
   __syncthreads();
+}
 
+// the k best of the k x k candidates, the lowest flat index winning a tie (wave 0 only)
+__device__ __forceinline__ void beam_select(const BeamParams& p, BeamShared& s, int t) {
+  const int tid = threadIdx.x, k = p.k;
   if (tid < 64) {
     const int lane = tid;
     if (t == 0) {                       // seeding: the k best words of beam 0
@@ -744,6 +753,13 @@ __device__ __forceinline__ void beam_update(const BeamParams& p, const EmbedArgs
       }
     }
   }
+}
+
+// s.parent / s.word / s.lp of the k rows are chosen (by wave 0; the barrier is here): new cumulative scores, the in-place
+// permutation, the embedding tail, the per-beam outputs and the arrival counter
+__device__ __forceinline__ void beam_apply(const BeamParams& p, const EmbedArgs& e, BeamShared& s, int b, int t) {
+  constexpr int NT = BEAM_NT;
+  const int tid = threadIdx.x, k = p.k, T = p.T;
   __syncthreads();
   // cumulative score = re-summed per-token log-probs of the parent prefix + the new one (:213), in position order
   if (tid < k) {
@@ -824,7 +840,105 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p, EmbedArgs 
     s.cv[i] = p.cand_val[(long)b * k * k + i];
     s.ci[i] = p.cand_idx[(long)b * k * k + i];
   }
-  beam_update(p, e, s, b, t);            // (four waves: the k·d embedding rows and the prefix re-gather are the bulk)
+  beam_load_rows(p, s, b, t);
+  beam_select(p, s, t);
+  beam_apply(p, e, s, b, t);             // (four waves: the k·d embedding rows and the prefix re-gather are the bulk)
+}
+
+// ---------------------------------------------------------------------------------------------
+// Diverse (group) beam search step: the R = G·kg rows of an image are G groups of kg beams, rows g·kg .. g·kg+kg-1 being
+// group g.  Wave 0 walks the groups in order.  Group g ranks its kg·R candidates (beam j of the group x its R best
+// words; four per lane at most) by   total = cumul_j + (logp_j(w) - penalty·count[w])   where count[w] is the number
+// of picks of groups 0..g-1 at this step that appended w to a beam still growing; a finished beam keeps the rule of
+// beam_select (rank 0 worth 0, the others -999, never penalised).  Order: total descending, then beam in group
+// ascending, then word ascending — at G = 1 (count = 0, a row's candidates sorted by value, then word) the lowest flat
+// index of beam_select.  The three operations are rounded separately (__fmul_rn, __fsub_rn, __fadd_rn; the products go
+// through a small LDS table so that nothing can be contracted), so that a float32 host model reproduces the order bit
+// for bit.  The picks made so far ARE the penalty list: s.word[q]
+// and grow[q] for q < g·kg (at most 15 entries), read back by the next group after a fence.  What is stored (s.lp) is
+// the candidate's own, unpenalised value.  Seeding (t = 0): every row holds the same distribution; group g draws from
+// its first row, against the seeds of the groups before it.
+// R candidates per row are enough: the penalised top-kg of a row lies inside its unpenalised top-(kg + P), P <= g·kg <=
+// R - kg the number of penalised words.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void group_beam_select(const BeamParams& p, BeamShared& s, int* grow, const float* pen,
+                                                  int t, int G, int kg) {
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x, R = p.k;
+  constexpr int CPL = MAX_K * MAX_K / 64;              // candidates per lane (kg·R <= 256)
+  constexpr long long NO_KEY = 0x7fffffffffffffffLL;
+  const int nc = (t == 0 ? 1 : kg) * R;                // candidates of a group
+  for (int g = 0; g < G; ++g) {
+    const int row0 = g * kg;                           // first row of the group = number of earlier picks
+    float tot[CPL]; long long key[CPL];                // key: (beam in group, word); lower wins a tie on the total
+#pragma unroll
+    for (int u = 0; u < CPL; ++u) {
+      const int i = lane + 64 * u;
+      tot[u] = -INFINITY; key[u] = NO_KEY;
+      if (i < nc) {
+        const int j = i / R, c = i - j * R, row = row0 + j, fl = row * R + c;
+        const int w = s.ci[fl];
+        float v;
+        if (t > 0 && s.eos[row]) {
+          v = c == 0 ? 0.0f : -999.0f;
+        } else {
+          int cnt = 0;
+          for (int q = 0; q < row0; ++q) cnt += (grow[q] && s.word[q] == w) ? 1 : 0;
+          v = __fsub_rn(s.cv[fl], pen[cnt]);
+        }
+        tot[u] = t == 0 ? v : __fadd_rn(s.cu[row], v);
+        key[u] = ((long long)j << 32) | (long long)(unsigned)w;
+      }
+    }
+    for (int r = 0; r < kg; ++r) {
+      float best = tot[0]; long long bk = key[0]; int bu = 0;
+#pragma unroll
+      for (int u = 1; u < CPL; ++u)
+        if (tot[u] > best || (tot[u] == best && key[u] < bk)) { best = tot[u]; bk = key[u]; bu = u; }
+      int bi = lane + 64 * bu;                           // index into the group's candidates
+      if (!(best > -INFINITY)) { bk = NO_KEY; bi = 0x7fffffff; }     // nothing left in this lane
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const long long ok = __shfl_xor(bk, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && (ok < bk || (ok == bk && oi < bi)))) { best = ov; bk = ok; bi = oi; }
+      }
+#pragma unroll
+      for (int u = 0; u < CPL; ++u)
+        if (bi == lane + 64 * u) { tot[u] = -INFINITY; key[u] = NO_KEY; }
+      if (lane == 0) {
+        if (bi >= nc) bi = 0;                            // (fewer than kg finite candidates: the group's first one)
+        const int j = bi / R, c = bi - j * R, row = row0 + j;
+        const int fin = t > 0 && s.eos[row];
+        s.parent[row0 + r] = row; s.word[row0 + r] = s.ci[row * R + c];
+        s.lp[row0 + r] = fin ? (c == 0 ? 0.0f : -999.0f) : s.cv[row * R + c];
+        grow[row0 + r] = fin ? 0 : 1;
+      }
+    }
+    // lane 0's picks are read by every lane of this wave in the next group
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+}
+
+__global__ __launch_bounds__(256) void group_beam_step_kernel(BeamParams p, EmbedArgs e, int G, int kg, float penalty) {
+  __shared__ BeamShared s;
+  __shared__ int grow[MAX_K];           // pick q of this step extends a beam that was still growing
+  __shared__ float pen[MAX_K];          // penalty·count for count = 0 .. 15 (at most R - kg earlier picks)
+  const int b = blockIdx.x, R = p.k;
+  const int t = *p.pos;
+  if (t + 1 >= p.T) return;
+  // the product is rounded on its own here and only read back below: the build contracts a·b - c into one fma otherwise
+  if (threadIdx.x < MAX_K) pen[threadIdx.x] = __fmul_rn(penalty, (float)threadIdx.x);
+  for (int i = threadIdx.x; i < R * R; i += 256) {
+    s.cv[i] = p.cand_val[(long)b * R * R + i];
+    s.ci[i] = p.cand_idx[(long)b * R * R + i];
+  }
+  beam_load_rows(p, s, b, t);
+  group_beam_select(p, s, grow, pen, t, G, kg);
+  beam_apply(p, e, s, b, t);
 }
 
 __global__ void beam_finalize_kernel(const float* cumul, const int* n_elem, int* order, float* score, int n_img,
@@ -1029,6 +1143,24 @@ extern "C" int odic_beam_step(const float* cand_val, const int32_t* cand_idx, co
   if (rc != 0) return rc;
   p.cand_val = cand_val; p.cand_idx = cand_idx;
   hipLaunchKernelGGL(beam_step_kernel, dim3(n_img), dim3(256), 0, (hipStream_t)stream, p, e);
+  return odic_launch_status();
+}
+
+extern "C" int odic_group_beam_step(const float* cand_val, const int32_t* cand_idx, int32_t ncand,
+                                    const odic_beam_state* st, const odic_embed_args* emb, int32_t n_img,
+                                    int32_t groups, int32_t group_beams, int32_t T, int64_t eos_idx, float penalty,
+                                    void* stream) {
+  if (!cand_val || !cand_idx) return ODIC_ENULL;
+  if (groups < 1 || group_beams < 1 || groups > MAX_K || group_beams > MAX_K) return ODIC_EINVAL;
+  const int R = groups * group_beams;
+  if (R > MAX_K || ncand != R) return ODIC_EINVAL;
+  if (!(penalty >= 0.0f) || !(penalty <= 3.402823466e38f)) return ODIC_EINVAL;      // negative, infinite or NaN
+  BeamParams p; EmbedArgs e;
+  const int rc = beam_params(p, e, st, emb, n_img, R, T, eos_idx);
+  if (rc != 0) return rc;
+  p.cand_val = cand_val; p.cand_idx = cand_idx;
+  hipLaunchKernelGGL(group_beam_step_kernel, dim3(n_img), dim3(256), 0, (hipStream_t)stream, p, e, (int)groups,
+                     (int)group_beams, penalty);
   return odic_launch_status();
 }
 

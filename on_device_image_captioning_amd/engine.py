@@ -545,6 +545,18 @@ class CaptionerEngine:
         ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx, emb=st.emb)
 
+    def group_beam_step(self, st: DecodeState, eos_idx: int, groups: int, penalty: float) -> None:
+        """One full step of diverse beam search, the sibling of beam_step: all st.beams = groups·k' rows of an image go
+        through the decoder and the top-k launch together (k = st.beams candidates per row); only the selection walks
+        the groups in turn (odic_group_beam_step, one block per image)."""
+        if groups < 1 or st.beams % groups:
+            raise ValueError(f"{st.beams} rows per image do not split into {groups} groups")
+        self.step_logits(st, embed=False)
+        V = self.g.vocab_size
+        ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        ops.group_beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, groups, st.beams // groups, st.T, eos_idx,
+                            penalty, emb=st.emb)
+
     # ------------------------------------------------------------------------------------------
     # whole-sequence (teacher-forced) pass: every token is known, so the N·T rows go through each layer at once
     def vocab_row_chunk(self) -> int:

@@ -91,6 +91,10 @@ class EsembleCaptioningModel(CaptioningModel):
         raise NotImplementedError("an ensemble has no single set of attention maps: call word_attention on one of its "
                                   "member models (models_list[i])")
 
+    def diverse_beam_search(self, *a, **k):
+        raise NotImplementedError("diverse beam search runs on a single model: call it on one of the ensemble's member "
+                                  "models (models_list[i])")
+
     def ensemble_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                              max_seq_len=20, sample_or_max="max") -> Tuple[List[List[List[int]]], torch.Tensor]:
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"

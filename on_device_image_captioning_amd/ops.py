@@ -708,6 +708,17 @@ def beam_step(cand_val, cand_idx, state: "_hip.BeamState", n_img, beams, T, eos_
                                               T, eos_idx, _stream()), "odic_beam_step")
 
 
+def group_beam_step(cand_val, cand_idx, state: "_hip.BeamState", n_img, groups, group_beams, T, eos_idx, penalty,
+                    emb=None) -> None:
+    """The step of diverse beam search (odic_group_beam_step): `groups` groups of `group_beams` beams per image choose
+    in turn, each paying `penalty` per earlier group that took the same word.  cand_* are [n_img·R, R], R = groups·group_beams."""
+    beams = groups * group_beams
+    with _timed("beam_step", 0.0, n_img * beams * beams * 8.0 + _beam_bytes(n_img, beams, T, emb)):
+        _hip.check(_hip.load().odic_group_beam_step(_p(cand_val), _p(cand_idx), beams, C.byref(state), _emb_ref(emb), n_img,
+                                                    groups, group_beams, T, eos_idx, penalty, _stream()),
+                   "odic_group_beam_step")
+
+
 def beam_finalize(state: "_hip.BeamState", order, score, n_img, beams) -> None:
     with _timed("beam_finalize", 0.0, n_img * beams * 16.0):
         _hip.check(_hip.load().odic_beam_finalize(C.byref(state), _p(order), _p(score), n_img, beams, _stream()),

@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Per-step time of the decode chain (decoder → log-softmax / top-k → selection) for a search form, alone on the chip:
+FULL geometry, features-only model, 16 images, fp32, HIP events around the step loop of one search (19 steps, no `done`
+poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
+it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
+
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3
+
+A form this build does not have (diverse on a build before ABI 25) is reported as absent.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    import torch
+
+    import bench
+    from on_device_image_captioning_amd import ops
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--images", type=int, default=16)
+    ap.add_argument("--max-len", type=int, default=20)
+    ap.add_argument("--penalty", type=float, default=0.5)
+    ap.add_argument("--eager", action="store_true")
+    ap.add_argument("forms", nargs="+")
+    a = ap.parse_args()
+    torch.set_grad_enabled(False)
+    dev = torch.device("cuda", 0)
+    model, _, g = bench.build_model(dev, "fp32", "features48")
+    eng = model._captioner_engine()
+    feats = torch.randn(a.images, 144, g.final_swin_dim, device=dev, generator=torch.Generator(dev).manual_seed(1))
+    mem = model.forward_enc(feats, [0] * a.images)
+    kv = eng.project_kv(mem)
+    enc_len = model._enc_lens(a.images, mem.shape[1], [0] * a.images)
+    steps, T = a.max_len - 1, a.max_len
+    for form in a.forms:
+        kind, shape = form.split(":")
+        if kind == "diverse":
+            G, kg = (int(v) for v in shape.split("x"))
+            if not hasattr(eng, "group_beam_step"):
+                print(f"{form}: not in this build")
+                continue
+            R = G * kg
+            one = lambda st: eng.group_beam_step(st, bench.EOS, G, a.penalty)      # noqa: E731
+        else:
+            R = int(shape)
+            one = lambda st: eng.beam_step(st, bench.EOS)                          # noqa: E731
+        st = eng.new_state(a.images, R, T, kv, enc_len)
+        def search():
+            ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=st.emb)
+            for _ in range(steps):
+                one(st)
+
+        graph = None
+        if not a.eager:
+            side = torch.cuda.Stream(dev)
+            with torch.cuda.stream(side):
+                search()                                                           # warm-up outside the capture
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                search()
+        times = []
+        for run in range(a.runs + 2):                                              # two warm-up searches
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graph.replay() if graph is not None else search()
+            e1.record()
+            torch.cuda.synchronize()
+            if run >= 2:
+                times.append(e0.elapsed_time(e1) * 1000.0 / steps)
+        print(f"{form} ({'eager' if a.eager else 'graph'}): rows/image {R}, {steps} steps, per step median {statistics.median(times):.1f} us, "
+              f"min {min(times):.1f}, max {max(times):.1f} ({a.runs} runs)", flush=True)
+
+
+if __name__ == "__main__":
+    main()
