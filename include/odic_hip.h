@@ -54,8 +54,9 @@ extern "C" {
  *   19: the one-launch search step entry point removed (odic_logsoftmax_topk + odic_beam_step is the step).
  *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale).
  *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)).
- *   25: odic_group_beam_step added (diverse beam search: groups with a Hamming penalty). */
-#define ODIC_ABI_VERSION 25
+ *   25: odic_group_beam_step added (diverse beam search: groups with a Hamming penalty).
+ *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search). */
+#define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -635,6 +636,42 @@ int odic_ensemble_logprobs(const float* const* logits, int32_t M, int64_t ldl, f
  * logp columns [V, ldl) are not read (test_ensemble_logprobs_and_topk_rows_leading_dimensions, also for the one above). */
 int odic_topk_rows(const float* logp, int64_t ldl, float* top_val, int32_t* top_idx, int32_t N, int32_t V,
                    int32_t k, void* stream);
+
+/* Constrained word selection, the sibling of odic_topk_rows for a search that may not choose every word: the k best
+ * ADMISSIBLE entries of every row (value descending, ties → lower index), values taken as they are — the rows already hold
+ * log-probabilities (logp_out of odic_logsoftmax_topk, or the output of odic_ensemble_logprobs), so the log-probs of a
+ * constrained caption are bit for bit what the unconstrained kernels compute.  top_val fp32 [N,k], top_idx int32 [N,k],
+ * both compact; logp columns [V, ldl) are not read.  It runs between the top-k launch of a step and odic_beam_step /
+ * odic_group_beam_step, overwriting the candidates the former wrote.  Every pointer of the struct is a device pointer
+ * and the step is read on the device, so a step stays capturable.
+ *   Let p = tokens[n][0 .. *pos] (slot 0 = SOS; *pos is clamped to [0, T-1]).  For a growing row, word w is inadmissible if
+ *     - w is in `banned`, or
+ *     - w == eos_idx and *pos < min_words (the caption would end with *pos words), or
+ *     - no_repeat_ngram = g > 0 and some j in [0, *pos - g + 1] has p[j .. j+g-2] == p[*pos-g+2 .. *pos] and p[j+g-1] == w:
+ *       appending w would write a g-gram the prefix already holds (g = 1: every word of the prefix, SOS included; while
+ *       the prefix is shorter than g - 1 words plus one the range of j is empty).
+ *   Banned ids and prefix words outside [0, V) are ignored; nothing is stored out of range.  A finished row
+ *   (row_valid[n] == 0) gets exactly what odic_topk_rows gives it: the step kernels use only its rank-0 slot.
+ *   k admissible words always exist: a row loses at most n_banned + 1 + (T - 1) words, and a call with
+ *   n_banned + T + k > V is refused.  With no active constraint the output is odic_topk_rows', bit for bit.
+ *   ODIC_EINVAL, before any launch and with nothing written: n_banned + T + k > V, k outside [1, 16], no_repeat_ngram
+ *   outside [0, T], min_words < 0, T outside odic_beam_step's [2, 128], n_banned outside [0, 1024], V above 262144 (the
+ *   inadmissible set is a bitmap in 32 KB of LDS), N or V < 1, ldl < V, or a required pointer NULL (logp, c, top_val,
+ *   top_idx, tokens, pos; banned with n_banned > 0) — one refusal code for this entry point.
+ *   All stores stay inside top_val / top_idx (tests/test_search_constraints_gpu.py runs every operand in a guarded buffer). */
+typedef struct odic_search_constraints {
+  const int64_t* tokens;      /* [N, T] prefixes, row n = tokens + n*T (the beam state's `tokens`, viewed flat) */
+  const int32_t* pos;         /* device scalar: the step; row n's prefix is tokens[n][0 .. *pos], slot 0 = SOS */
+  const int32_t* row_valid;   /* [N] or NULL; a row with row_valid == 0 (finished beam) is selected UNCONSTRAINED */
+  const int32_t* banned;      /* [n_banned] word ids, or NULL with n_banned == 0 */
+  int32_t n_banned;
+  int32_t no_repeat_ngram;    /* 0 = off, else n >= 1 */
+  int32_t min_words;          /* eos is inadmissible while *pos < min_words (the caption would hold *pos words) */
+  int64_t eos_idx;
+  int32_t T;
+} odic_search_constraints;
+int odic_topk_rows_constrained(const float* logp, int64_t ldl, const odic_search_constraints* c,
+                               float* top_val, int32_t* top_idx, int32_t N, int32_t V, int32_t k, void* stream);
 
 /* Beam bookkeeping of one search step on device (captioning_model.py:172-223; the call with
  * *pos == 0 is the seeding of :126-140).  All arrays are device resident.

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libodic_hip.so")
 
 F32, BF16, FP8, F16, H2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _ERR = {-1: "ODIC_EINVAL (bad shape / alignment / enum)", -2: "ODIC_ENULL (required pointer is NULL)",
         -3: "ODIC_EUNSUPPORTED"}
@@ -46,6 +46,13 @@ class EmbedArgs(C.Structure):
     """odic_embed_args: the next position's input embedding as the tail of the launch that chooses the words."""
     _fields_ = [("embed", C.c_void_p), ("pos_table", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int64),
                 ("d", C.c_int32), ("scale", C.c_float), ("pos_rows", C.c_int32)]
+
+
+class SearchConstraints(C.Structure):
+    """odic_search_constraints: what the search may not choose (ops.search_constraints builds one)."""
+    _fields_ = [("tokens", C.c_void_p), ("pos", C.c_void_p), ("row_valid", C.c_void_p), ("banned", C.c_void_p),
+                ("n_banned", C.c_int32), ("no_repeat_ngram", C.c_int32), ("min_words", C.c_int32),
+                ("eos_idx", C.c_int64), ("T", C.c_int32)]
 
 
 class JpegBatch(C.Structure):
@@ -108,6 +115,7 @@ _SIGNATURES = {
     "odic_logsoftmax_sample": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, C.c_uint64, _P, _P]),
     "odic_ensemble_logprobs": (C.c_int, [C.POINTER(C.c_void_p), _I32, _I64, _P, _I64, _I32, _I32, _P]),
     "odic_topk_rows": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _P]),
+    "odic_topk_rows_constrained": (C.c_int, [_P, _I64, C.POINTER(SearchConstraints), _P, _P, _I32, _I32, _I32, _P]),
     "odic_beam_step": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),
     "odic_group_beam_step": (C.c_int, [_P, _P, _I32, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I32, _I64,
                                        _F, _P]),

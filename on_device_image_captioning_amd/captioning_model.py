@@ -42,7 +42,7 @@ class CaptioningModel(nn.Module):
         self.sampling_seed = 0              # Philox key of the device-side draws ('sample' / 'sampling' modes)
         self._sampling_calls = 0
         self._draw_log = None               # list → every sampled-beam-search draw is appended (tests)
-        self._cand_log = None               # list → every diverse-search step's (cand_val, cand_idx) is appended (tests)
+        self._cand_log = None               # list → every deterministic search step's (cand_val, cand_idx) is appended (tests)
 
     # ------------------------------------------------------------------ engine cache plumbing
     def check_required_attributes(self):
@@ -90,6 +90,33 @@ class CaptioningModel(nn.Module):
             raise RuntimeError("fp8_saturation_report needs set_precision('fp8')")
         swin = self._engines()[0]
         return swin.fp8_saturation(images.to(swin.device, torch.float32))
+
+    def _search_constraint_args(self, *, no_repeat_ngram_size=0, min_length=0, banned_words=None, sos_idx, eos_idx, max_seq_len,
+                                rows_per_image, sampling=False) -> Optional[dict]:
+        """The constraint keywords of the search methods, checked on the host before any device work: None when none is
+        active (the search then launches exactly what it always did), else the keywords of
+        CaptionerEngine.search_constraints."""
+        banned = [] if banned_words is None else sorted({int(w) for w in banned_words})
+        n, m = int(no_repeat_ngram_size), int(min_length)
+        if n < 0 or m < 0:
+            raise ValueError("no_repeat_ngram_size and min_length must be >= 0")
+        if n == 0 and m == 0 and not banned:
+            return None
+        if sampling:
+            raise ValueError("no_repeat_ngram_size / min_length / banned_words apply to the deterministic searches only: "
+                             "drawing under constraints (sample_or_max='sample', mode='sampling') is not supported")
+        T = max(1, max_seq_len - 1) + 1
+        if m > max_seq_len - 2:
+            raise ValueError(f"min_length {m} > max_seq_len - 2 = {max_seq_len - 2}: no caption could end")
+        if sos_idx in banned or eos_idx in banned:
+            raise ValueError("the SOS and EOS ids cannot be banned (min_length is the control over where a caption ends)")
+        V = self._vocab_size()
+        if len(banned) + T + rows_per_image > V:
+            raise ValueError(f"{len(banned)} banned words + {T} positions + {rows_per_image} candidates per row exceed the "
+                             f"vocabulary ({V} words): a row could run out of admissible words")
+        if len(banned) > 1024:
+            raise ValueError("at most 1024 banned words")
+        return dict(no_repeat_ngram=n, min_words=m, banned=banned)
 
     def _next_sampling_seed(self) -> int:
         """A fresh Philox key per sampling call (so repeated calls differ), reproducible from `sampling_seed`."""
@@ -314,8 +341,10 @@ class CaptioningModel(nn.Module):
                                     beam_size=kwargs.get("beam_size", 5),
                                     how_many_outputs=kwargs.get("how_many_outputs", 1),
                                     max_seq_len=kwargs.get("beam_max_seq_len", 20),
-                                    sample_or_max=kwargs.get("sample_or_max", "max"))
+                                    sample_or_max=kwargs.get("sample_or_max", "max"), **_constraint_kwargs(kwargs))
         if mode == "sampling":
+            self._search_constraint_args(**_constraint_kwargs(kwargs), sos_idx=sos_idx, eos_idx=eos_idx,
+                                         max_seq_len=kwargs.get("sample_max_seq_len", 20), rows_per_image=1, sampling=True)
             return self.get_batch_multiple_sampled_prediction(
                 enc_x, enc_x_num_pads, num_outputs=kwargs.get("how_many_outputs", 1), sos_idx=sos_idx,
                 eos_idx=eos_idx, max_seq_len=kwargs.get("sample_max_seq_len", 20))
@@ -325,7 +354,7 @@ class CaptioningModel(nn.Module):
                                             group_size=kwargs.get("group_size", 3),
                                             diversity_penalty=kwargs.get("diversity_penalty", 0.5),
                                             how_many_outputs=kwargs.get("how_many_outputs", None),
-                                            max_seq_len=kwargs.get("beam_max_seq_len", 20))
+                                            max_seq_len=kwargs.get("beam_max_seq_len", 20), **_constraint_kwargs(kwargs))
         raise ValueError(f"unknown mode {mode!r}")
 
     def get_batch_multiple_sampled_prediction(self, enc_input, enc_input_num_pads, num_outputs, sos_idx, eos_idx,
@@ -381,17 +410,26 @@ class CaptioningModel(nn.Module):
 
     # ------------------------------------------------------------------ search
     def beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
-                    max_seq_len=20, sample_or_max="max"):
+                    max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0, banned_words=None):
+        """The reference's beam search.  Keyword-only controls over what it may choose, applied on the
+        device inside the step: `no_repeat_ngram_size` = n > 0: no caption holds an n-gram twice; `min_length`: at least
+        that many words between SOS and EOS; `banned_words`: word ids that never appear.  With the defaults the search
+        launches exactly what it launches without them."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
+        cons = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                            banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
+                                            max_seq_len=max_seq_len, rows_per_image=beam_size,
+                                            sampling=(sample_or_max == "sample"))
         mem = self.forward_enc(enc_input, enc_input_num_pads)
         toks, lp = self._search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
-                                            max_seq_len, sample=(sample_or_max == "sample"))
+                                            max_seq_len, sample=(sample_or_max == "sample"), constraints=cons)
         return toks, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
     def _search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
-                            max_seq_len, sample: bool = False) -> Tuple[List[List[List[int]]], torch.Tensor]:
+                            max_seq_len, sample: bool = False, constraints: Optional[dict] = None
+                            ) -> Tuple[List[List[List[int]]], torch.Tensor]:
         eng = self._captioner_engine()
         dv = eng.device
         B, S, _ = mem.shape
@@ -404,6 +442,7 @@ class CaptioningModel(nn.Module):
         ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None if sample else st.emb)
         V = eng.g.vocab_size
         seed = self._next_sampling_seed() if sample else 0
+        cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
         for t in range(steps):
             if sample:
                 # 'sample' variant (captioning_model.py:128-131,166-168): the k candidates of every beam are
@@ -414,7 +453,9 @@ class CaptioningModel(nn.Module):
                     self._draw_log.append(st.cand_idx.cpu().clone())
                 ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx)
             else:
-                eng.beam_step(st, eos_idx)
+                eng.beam_step(st, eos_idx, constraints=cons)
+                if self._cand_log is not None:                    # test hook: the candidates, for replay in the model
+                    self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
             if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(st.done.item()):
                 break
         order = torch.empty(B, k, dtype=torch.int32, device=dv)
@@ -437,7 +478,8 @@ class CaptioningModel(nn.Module):
         return res_tok, lp
 
     def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
-                            diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20):
+                            diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20, *, no_repeat_ngram_size=0,
+                            min_length=0, banned_words=None):
         """Diverse (group) beam search (Vijayakumar et al.): `num_groups` groups of `group_size` beams per image.
         Within a step the groups choose one after the other, and a group pays `diversity_penalty` for every earlier
         group that appended the same word at this step (odic_group_beam_step).  The penalty only steers
@@ -445,7 +487,9 @@ class CaptioningModel(nn.Module):
         Output j of an image is the best beam of group j (ties → the lower row), in group order — output 0 is what
         beam_search(beam_size=group_size) returns, group 0 never being penalised.  `how_many_outputs` defaults to
         num_groups and may not exceed it.  Returns what beam_search returns: a token list per image and output, and
-        the padded per-token log-probs [B, how_many_outputs, longest]."""
+        the padded per-token log-probs [B, how_many_outputs, longest].
+        `no_repeat_ngram_size`, `min_length`, `banned_words`: as in beam_search; every group's caption keeps them (the
+        words are removed before the ranking the penalty works on)."""
         if how_many_outputs is None:
             how_many_outputs = num_groups
         if num_groups < 1 or group_size < 1 or num_groups * group_size > 16:
@@ -455,6 +499,9 @@ class CaptioningModel(nn.Module):
         penalty = float(diversity_penalty)
         if not (0.0 <= penalty < float("inf")):
             raise ValueError("diversity_penalty must be finite and >= 0")
+        constraints = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                                   banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
+                                                   max_seq_len=max_seq_len, rows_per_image=num_groups * group_size)
         mem = self.forward_enc(enc_input, enc_input_num_pads)
         eng = self._captioner_engine()
         dv = eng.device
@@ -467,8 +514,9 @@ class CaptioningModel(nn.Module):
         T = steps + 1
         st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
         ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
+        cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
         for t in range(steps):
-            eng.group_beam_step(st, eos_idx, G, penalty)
+            eng.group_beam_step(st, eos_idx, G, penalty, constraints=cons)
             if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
             if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(st.done.item()):
@@ -491,6 +539,14 @@ class CaptioningModel(nn.Module):
             res_tok.append(per)
         lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
         return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+
+
+_CONSTRAINT_KEYS = ("no_repeat_ngram_size", "min_length", "banned_words")
+
+
+def _constraint_kwargs(args) -> dict:
+    """The constraint keywords present in a forward(**kwargs) / beam_search_args mapping (absent = the default)."""
+    return {k: args[k] for k in _CONSTRAINT_KEYS if k in args}
 
 
 def _as_list(pads, n: int) -> List[int]:
@@ -534,9 +590,12 @@ class Captioner:
                                           beam_size=a.get("beam_size", 5),
                                           how_many_outputs=a.get("how_many_outputs", 1),
                                           max_seq_len=a.get("beam_max_seq_len", 20),
-                                          sample_or_max=a.get("sample_or_max", "max"))
+                                          sample_or_max=a.get("sample_or_max", "max"), **_constraint_kwargs(a))
         if mode == "sampling":
             self.apply_log_softmax = True
+            self.model._search_constraint_args(**_constraint_kwargs(a), sos_idx=sos_idx, eos_idx=eos_idx,
+                                               max_seq_len=a.get("sample_max_seq_len", 20), rows_per_image=1,
+                                               sampling=True)
             return self.model.get_batch_multiple_sampled_prediction(
                 enc_x, enc_x_num_pads, num_outputs=a.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
                 max_seq_len=a.get("sample_max_seq_len", 20))
@@ -546,7 +605,7 @@ class Captioner:
                                                   num_groups=a.get("num_groups", 3), group_size=a.get("group_size", 3),
                                                   diversity_penalty=a.get("diversity_penalty", 0.5),
                                                   how_many_outputs=a.get("how_many_outputs", None),
-                                                  max_seq_len=a.get("beam_max_seq_len", 20))
+                                                  max_seq_len=a.get("beam_max_seq_len", 20), **_constraint_kwargs(a))
         raise ValueError(f"unknown mode {mode!r}")
 
     def forward_enc(self, enc_input, enc_input_num_pads):

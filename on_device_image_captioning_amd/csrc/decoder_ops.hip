@@ -433,15 +433,6 @@ struct TopkShared {
   float bv[16]; int bi[16];
 };
 
-__device__ __forceinline__ void wave_argmax(float& best, int& besti) {        // every lane ends with the winner
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(besti, o, 64);
-    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-  }
-}
-
 template <int NTH, bool NORM>
 __device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x, float* __restrict__ logp,
                                                     float* top_val, int* top_idx, int V, int k, TopkShared& sh) {

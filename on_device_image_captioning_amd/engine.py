@@ -296,6 +296,8 @@ class DecodeState:
         self.cumul, self.n_elem, self.has_eos = f(N), i32(N), i32(N)
         self.cand_val, self.cand_idx = f(N, beams), i32(N, beams)
         self.logits = f(N, g.vocab_size)
+        self.logp = None            # [N, V] log-probs, allocated by the first constrained step (odic_topk_rows_constrained)
+        self.banned = None          # int32 word ids of the constraints built for this state (kept alive here)
         self.beam_state = _hip.BeamState(*(t.data_ptr() for t in (
             self.tokens, self.logprobs, self.anc, self.cumul, self.n_elem, self.has_eos, self.row_valid,
             self.next_tok, self.pos, self.done, self.ctr)))
@@ -535,17 +537,53 @@ class CaptionerEngine:
         else:
             ops.gemm(ops.layernorm(pre, self.drn_w, self.drn_b), self.voc_w, self.voc_b, out=st.logits)
 
-    def beam_step(self, st: DecodeState, eos_idx: int) -> None:
+    def search_constraints(self, st: DecodeState, eos_idx: int, *, no_repeat_ngram: int = 0, min_words: int = 0,
+                           banned=None) -> Optional["_hip.SearchConstraints"]:
+        """The constraints of a search on `st` for beam_step / group_beam_step, or None when none is
+        active: words that would repeat an n-gram of the row's prefix, EOS before `min_words` words, the word ids in
+        `banned`.  Everything the kernel reads is device resident (st.tokens, st.pos, st.row_valid, the uploaded ban list)."""
+        banned = sorted({int(w) for w in banned}) if banned is not None else []
+        if not banned and no_repeat_ngram == 0 and min_words == 0:
+            return None
+        V = self.g.vocab_size
+        if no_repeat_ngram < 0 or min_words < 0:
+            raise ValueError("no_repeat_ngram and min_words must be >= 0")
+        if len(banned) + st.T + st.beams > V:
+            raise ValueError(f"{len(banned)} banned words + {st.T} positions + {st.beams} candidates exceed the "
+                             f"vocabulary ({V} words): a row could run out of admissible words")
+        if len(banned) > 1024:
+            raise ValueError("at most 1024 banned words")
+        st.banned = torch.tensor(banned, dtype=torch.int32, device=self.device) if banned else None
+        return ops.search_constraints(st.tokens, st.pos, st.T, eos_idx, row_valid=st.row_valid, banned=st.banned,
+                                      no_repeat_ngram=min(int(no_repeat_ngram), st.T), min_words=int(min_words))
+
+    def constrained_candidates(self, st: DecodeState, constraints, logp: Optional[torch.Tensor] = None) -> None:
+        """st.cand_val / st.cand_idx = the st.beams best ADMISSIBLE words of every row.  The rows are the log-probs the
+        unconstrained launch writes (logp_out of odic_logsoftmax_topk into st.logp) or, given `logp`, rows that are
+        log-probs already (the ensemble's average); odic_topk_rows_constrained selects from them as they are."""
+        V = self.g.vocab_size
+        if logp is None:
+            if st.logp is None:
+                st.logp = torch.empty(st.N, V, dtype=torch.float32, device=self.device)
+            logp = st.logp
+            ops.logsoftmax_topk(st.logits, V, logp, V, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        ops.topk_rows_constrained(logp, constraints, st.cand_val, st.cand_idx, st.beams)
+
+    def beam_step(self, st: DecodeState, eos_idx: int, constraints=None) -> None:
         """One full search step: decoder → log-softmax / top-k (one block per row) → beam bookkeeping + the next
         position's input rows (one block per image).  The state must have been armed with
         ops.beam_reset(st.beam_state, ..., emb=st.emb).  (Both launches in one were slower, DESIGN.md §4.6: a block
-        per image then works through its k rows alone.)"""
+        per image then works through its k rows alone.)  `constraints` (search_constraints(st, ...)): the top-k launch
+        also writes the log-prob rows, and odic_topk_rows_constrained re-selects the candidates from them."""
         self.step_logits(st, embed=False)
         V = self.g.vocab_size
-        ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        if constraints is not None:
+            self.constrained_candidates(st, constraints)
+        else:
+            ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx, emb=st.emb)
 
-    def group_beam_step(self, st: DecodeState, eos_idx: int, groups: int, penalty: float) -> None:
+    def group_beam_step(self, st: DecodeState, eos_idx: int, groups: int, penalty: float, constraints=None) -> None:
         """One full step of diverse beam search, the sibling of beam_step: all st.beams = groups·k' rows of an image go
         through the decoder and the top-k launch together (k = st.beams candidates per row); only the selection walks
         the groups in turn (odic_group_beam_step, one block per image)."""
@@ -553,7 +591,10 @@ class CaptionerEngine:
             raise ValueError(f"{st.beams} rows per image do not split into {groups} groups")
         self.step_logits(st, embed=False)
         V = self.g.vocab_size
-        ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        if constraints is not None:
+            self.constrained_candidates(st, constraints)
+        else:
+            ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.group_beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, groups, st.beams // groups, st.T, eos_idx,
                             penalty, emb=st.emb)
 

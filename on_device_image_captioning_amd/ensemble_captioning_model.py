@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .captioning_model import CaptioningModel, _DONE_POLL
+from .captioning_model import CaptioningModel, _DONE_POLL, _constraint_kwargs
 
 
 class EsembleCaptioningModel(CaptioningModel):
@@ -37,7 +37,7 @@ class EsembleCaptioningModel(CaptioningModel):
                                          beam_size=kwargs.get("beam_size", 5),
                                          how_many_outputs=kwargs.get("how_many_outputs", 1),
                                          max_seq_len=kwargs.get("beam_max_seq_len", 20),
-                                         sample_or_max=kwargs.get("sample_or_max", "max"))
+                                         sample_or_max=kwargs.get("sample_or_max", "max"), **_constraint_kwargs(kwargs))
 
     def forward_enc(self, enc_input, enc_input_num_pads):
         return [m.forward_enc(enc_input, enc_input_num_pads) for m in self.models_list]
@@ -96,11 +96,17 @@ class EsembleCaptioningModel(CaptioningModel):
                                   "models (models_list[i])")
 
     def ensemble_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
-                             max_seq_len=20, sample_or_max="max") -> Tuple[List[List[List[int]]], torch.Tensor]:
+                             max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0,
+                             banned_words=None) -> Tuple[List[List[List[int]]], torch.Tensor]:
+        """`no_repeat_ngram_size`, `min_length`, `banned_words`: as in CaptioningModel.beam_search; the constrained
+        selection (odic_topk_rows_constrained) then replaces odic_topk_rows on the averaged log-probs."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
         sample = sample_or_max == "sample"
+        constraints = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                                   banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
+                                                   max_seq_len=max_seq_len, rows_per_image=beam_size, sampling=sample)
         # 'sample' (reference models/ensemble_captioning_model.py:123-130,174-183): the k candidates of every beam are drawn
         # without replacement from the averaged distribution — odic_logsoftmax_sample on rows that already are
         # log-probabilities (its normalisation is then the identity up to rounding), keyed by the lead member's seed
@@ -124,12 +130,15 @@ class EsembleCaptioningModel(CaptioningModel):
         lead.next_tok.fill_(sos_idx)
         V = engs[0].g.vocab_size
         avg = torch.empty(lead.N, V, dtype=torch.float32, device=dv)
+        cons = engs[0].search_constraints(lead, eos_idx, **constraints) if constraints else None
         for t in range(steps):
             for eng, st in zip(engs, states):
                 eng.step_logits(st)                              # reads the shared next_tok / pos / ancestor table
             ops.ensemble_logprobs([st.logits for st in states], avg)
             if sample:
                 ops.logsoftmax_sample(avg, V, None, 0, lead.cand_val, lead.cand_idx, lead.N, V, k, seed, lead.pos)
+            elif cons is not None:
+                engs[0].constrained_candidates(lead, cons, logp=avg)
             else:
                 ops.topk_rows(avg, lead.cand_val, lead.cand_idx, k)
             ops.beam_step(lead.cand_val, lead.cand_idx, lead.beam_state, lead.n_img, lead.beams, lead.T, eos_idx)

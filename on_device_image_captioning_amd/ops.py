@@ -685,6 +685,34 @@ def topk_rows(logp: torch.Tensor, top_val: torch.Tensor, top_idx: torch.Tensor, 
                    "odic_topk_rows")
 
 
+def search_constraints(tokens: torch.Tensor, pos: torch.Tensor, T: int, eos_idx: int, *, row_valid=None, banned=None,
+                       no_repeat_ngram: int = 0, min_words: int = 0) -> "_hip.SearchConstraints":
+    """odic_search_constraints for topk_rows_constrained (the caller keeps the tensors alive).  tokens: int64 prefixes,
+    N·T elements (the beam state's `tokens`); pos: the device int32 step counter; row_valid: int32 [N] or None;
+    banned: int32 device tensor of word ids or None."""
+    _need_cuda(tokens, pos, row_valid, banned)
+    if tokens.dtype != torch.int64 or pos.dtype != torch.int32 or not tokens.is_contiguous():
+        raise ValueError("search_constraints: tokens must be contiguous int64 and pos int32")
+    for name, t in (("row_valid", row_valid), ("banned", banned)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError(f"search_constraints: {name} must be a contiguous int32 tensor")
+    n_banned = 0 if banned is None else banned.numel()
+    return _hip.SearchConstraints(_p(tokens), _p(pos), _p(row_valid), _p(banned) if n_banned else None, n_banned,
+                                  int(no_repeat_ngram), int(min_words), int(eos_idx), int(T))
+
+
+def topk_rows_constrained(logp: torch.Tensor, constraints: "_hip.SearchConstraints", top_val: torch.Tensor,
+                          top_idx: torch.Tensor, k: int) -> None:
+    """The k best admissible words of every row of logp [N, V] (log-probs, taken as they are) under `constraints`
+    (odic_topk_rows_constrained): banned words, EOS before the minimum length, words that would repeat an n-gram."""
+    _need_cuda(logp, top_val, top_idx)
+    N, V = logp.shape
+    with _timed("logsoftmax_topk", 0.0, 4.0 * N * V):
+        _hip.check(_hip.load().odic_topk_rows_constrained(_p(logp), logp.stride(0), C.byref(constraints), _p(top_val),
+                                                          _p(top_idx), N, V, k, _stream()),
+                   "odic_topk_rows_constrained")
+
+
 def embed_args(embed, pos_table, y, ldy, d, scale) -> "_hip.EmbedArgs":
     """odic_embed_args for beam_step / beam_reset (the caller keeps the tensors alive)."""
     _need_cuda(embed, pos_table, y)

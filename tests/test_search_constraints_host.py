@@ -1,0 +1,242 @@
+"""Constrained search without a GPU: the numpy model of tests/search_constraints_model.py against a brute force that
+recomputes admissibility word by word from the definition; the ValueErrors of the public interface, raised before any
+device call; and the agreement of the header, the library and the ctypes binding on odic_topk_rows_constrained.
+"""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import search_constraints_model as SC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "odic_hip.h")
+F = np.float32
+SOS, EOS = 3, 2
+
+
+# ------------------------------------------------------------------------------------------------- model vs brute force
+def brute_admissible(w, p, pos, banned, g, min_words, eos):
+    """The definition, for ONE word: may a growing row whose prefix is p[0 .. pos] take w?"""
+    if w in banned:
+        return False
+    if w == eos and pos < min_words:
+        return False
+    if g > 0 and pos + 1 >= g - 1:
+        for j in range(0, pos - g + 2):
+            if all(p[j + u] == p[pos - g + 2 + u] for u in range(g - 1)) and p[j + g - 1] == w:
+                return False
+    return True
+
+
+def brute_topk(row, k, p, pos, banned, g, min_words, eos):
+    ok = [w for w in range(row.size) if brute_admissible(w, p, pos, banned, g, min_words, eos)]
+    ok.sort(key=lambda w: (-float(row[w]), w))
+    return ok[:k]
+
+
+def test_model_equals_the_word_by_word_brute_force():
+    rng = np.random.default_rng(2026)
+    cases = 0
+    hit = dict(banned=0, eos=0, ngram=0, finished=0, ties=0)
+    for V in range(8, 41):
+        for T in range(3, 10):
+            for pos in range(T):
+                for g in range(0, 5):
+                    N = 3
+                    # few distinct words, so that prefixes do repeat n-grams; one id outside [0, V)
+                    tokens = rng.integers(0, min(V, 4), size=(N, T)).astype(np.int64)
+                    tokens[:, 0] = SOS if SOS < V else 0
+                    if T > 3:
+                        tokens[0, int(rng.integers(1, T))] = V + 5
+                    n_banned = int(rng.integers(0, max(1, min(4, V - T - 4))))
+                    banned = [int(w) for w in rng.integers(-2, V + 3, size=n_banned)]
+                    k = int(rng.integers(1, max(2, V - len(banned) - T)))
+                    min_words = int(rng.integers(0, T))
+                    eos = EOS
+                    row_valid = np.array([1, 1, 0], np.int32)
+                    logp = (-np.round(rng.uniform(0.0, 2.0, size=(N, V)), 1)).astype(F)      # rounded to 0.1: ties
+                    val, idx = SC.topk_rows_constrained(logp, k, tokens, pos, row_valid, banned, g, min_words, eos)
+                    for n in range(N):
+                        if row_valid[n]:
+                            want = brute_topk(logp[n], k, [int(w) for w in tokens[n]], pos, set(banned), g, min_words, eos)
+                        else:
+                            want = sorted(range(V), key=lambda w: (-float(logp[n, w]), w))[:k]
+                            hit["finished"] += 1
+                        assert idx[n].tolist() == want, (V, T, pos, g, n)
+                        assert np.array_equal(val[n].view(np.int32), logp[n, want].view(np.int32))
+                        plain = sorted(range(V), key=lambda w: (-float(logp[n, w]), w))[:k]
+                        if row_valid[n] and want != plain:
+                            hit["banned"] += any(w in banned for w in plain)
+                            hit["eos"] += eos in plain and pos < min_words
+                            hit["ngram"] += g > 0
+                        hit["ties"] += len(set(val[n].tolist())) < k
+                    cases += 1
+    assert cases == 33 * sum(range(3, 10)) * 5
+    assert all(v > 50 for v in hit.values()), hit
+
+
+def test_hand_checked_prefixes():
+    V = 12
+    p = [3, 5, 6, 5, 6, 7, 5, 6]                       # SOS a b a b c a b
+    bad = SC.inadmissible(p, 7, V, no_repeat_ngram=3)   # last two words (5, 6) were followed by 5 and by 7
+    assert np.flatnonzero(bad).tolist() == [5, 7]
+    bad = SC.inadmissible(p, 7, V, no_repeat_ngram=2)   # last word 6 was followed by 5 and by 7
+    assert np.flatnonzero(bad).tolist() == [5, 7]
+    bad = SC.inadmissible(p, 7, V, no_repeat_ngram=1)
+    assert np.flatnonzero(bad).tolist() == [3, 5, 6, 7]
+    assert not SC.inadmissible(p, 1, V, no_repeat_ngram=4).any()           # pos + 1 < n - 1: nothing yet
+    assert not SC.inadmissible(p, 2, V, no_repeat_ngram=4).any()           # three words: no complete 4-gram to repeat
+    assert np.flatnonzero(SC.inadmissible(p, 3, V, min_words=4, eos=EOS)).tolist() == [EOS]
+    assert not SC.inadmissible(p, 4, V, min_words=4, eos=EOS).any()
+    assert np.flatnonzero(SC.inadmissible(p, 0, V, banned=[-1, 4, 12, 11])).tolist() == [4, 11]
+    assert SC.repeats_ngram([3, 5, 6, 5, 6, 2], 2) and not SC.repeats_ngram([3, 5, 6, 5, 7, 2], 2)
+    assert SC.repeats_ngram([3, 5, 6, 5, 2], 1) and not SC.repeats_ngram([3, 5, 6, 2], 1)
+
+
+# ------------------------------------------------------------------------------------------------- public interface
+@pytest.fixture(scope="module")
+def model():
+    from on_device_image_captioning_amd import weights as W
+    from on_device_image_captioning_amd.End_ExpansionNet_v2 import End_ExpansionNet_v2, make_drop_args
+    g = W.TINY
+    m = End_ExpansionNet_v2(**g.model_kwargs(), output_word2idx={i: i for i in range(g.vocab_size)},
+                            output_idx2word=list(range(g.vocab_size)), drop_args=make_drop_args(), rank="cpu")
+
+    def no_device(*a, **k):
+        raise AssertionError("the argument check must come before any device work")
+    m.forward_enc = no_device
+    m._captioner_engine = no_device
+    return m
+
+
+BAD = [dict(no_repeat_ngram_size=-1), dict(min_length=-1), dict(min_length=11),               # max_seq_len 12: 10 at most
+       dict(banned_words=range(10, 10 + 500 - 12 - 3 + 1)),                                  # len + T + k > V = 500
+       dict(banned_words=[7, EOS]), dict(banned_words=[SOS]),
+       dict(no_repeat_ngram_size=2, sample_or_max="sample"), dict(banned_words=[7], sample_or_max="sample"),
+       dict(min_length=3, sample_or_max="sample")]
+
+
+@pytest.mark.parametrize("kw", BAD, ids=[",".join(k) + str(i) for i, k in enumerate(BAD)])
+def test_beam_search_refuses_bad_constraints_before_any_device_call(model, kw):
+    from on_device_image_captioning_amd import weights as W
+    img = W.synth_images(1, W.TINY)
+    with pytest.raises(ValueError):
+        model.beam_search(img, [0], sos_idx=SOS, eos_idx=EOS, beam_size=3, max_seq_len=12, **kw)
+    if "sample_or_max" not in kw:
+        with pytest.raises(ValueError):
+            model.diverse_beam_search(img, [0], sos_idx=SOS, eos_idx=EOS, num_groups=3, group_size=1, max_seq_len=12, **kw)
+        with pytest.raises(ValueError):
+            model(enc_x=img, enc_x_num_pads=[0], mode="diverse_beam_search", sos_idx=SOS, eos_idx=EOS, num_groups=3,
+                  group_size=1, beam_max_seq_len=12, **kw)
+    with pytest.raises(ValueError):
+        model(enc_x=img, enc_x_num_pads=[0], mode="beam_search", sos_idx=SOS, eos_idx=EOS, beam_size=3,
+              beam_max_seq_len=12, **kw)
+
+
+def test_the_largest_admissible_ban_list_and_length_pass_the_check(model):
+    ok = model._search_constraint_args(no_repeat_ngram_size=0, min_length=10, banned_words=range(10, 10 + 500 - 12 - 3),
+                                       sos_idx=SOS, eos_idx=EOS, max_seq_len=12, rows_per_image=3)
+    assert ok["min_words"] == 10 and len(ok["banned"]) == 485 and ok["no_repeat_ngram"] == 0
+    assert model._search_constraint_args(no_repeat_ngram_size=0, min_length=0, banned_words=None, sos_idx=SOS,
+                                         eos_idx=EOS, max_seq_len=12, rows_per_image=3) is None
+    assert model._search_constraint_args(no_repeat_ngram_size=0, min_length=0, banned_words=[], sos_idx=SOS,
+                                         eos_idx=EOS, max_seq_len=12, rows_per_image=3, sampling=True) is None
+
+
+def test_sampling_modes_and_the_ensemble_refuse_constraints(model):
+    from on_device_image_captioning_amd import weights as W
+    from on_device_image_captioning_amd.captioning_model import Captioner
+    from on_device_image_captioning_amd.ensemble_captioning_model import EsembleCaptioningModel
+    img = W.synth_images(1, W.TINY)
+    for kw in (dict(no_repeat_ngram_size=2), dict(min_length=2), dict(banned_words=[9])):
+        with pytest.raises(ValueError, match="deterministic"):
+            model(enc_x=img, enc_x_num_pads=[0], mode="sampling", sos_idx=SOS, eos_idx=EOS, how_many_outputs=2,
+                  sample_max_seq_len=12, **kw)
+        cap = Captioner(dict(sos_idx=SOS, eos_idx=EOS, how_many_outputs=2, sample_max_seq_len=12, **kw), model=model)
+        with pytest.raises(ValueError, match="deterministic"):
+            cap(img, enc_x_num_pads=[0], mode="sampling")
+    cap = Captioner(dict(sos_idx=SOS, eos_idx=EOS, beam_size=3, beam_max_seq_len=12, min_length=11), model=model)
+    with pytest.raises(ValueError, match="min_length"):
+        cap(img, enc_x_num_pads=[0], mode="beam_search")
+    ens = EsembleCaptioningModel([model, model], rank="cpu")
+    ens.forward_enc = model.forward_enc
+    for kw in BAD:
+        with pytest.raises(ValueError):
+            ens.ensemble_beam_search(img, [0], sos_idx=SOS, eos_idx=EOS, beam_size=3, max_seq_len=12, **kw)
+    with pytest.raises(ValueError):
+        ens(enc_x=img, enc_x_num_pads=[0], mode="beam_search", sos_idx=SOS, eos_idx=EOS, beam_size=3,
+            beam_max_seq_len=12, banned_words=[EOS])
+
+
+def test_signatures_carry_the_keyword_only_arguments():
+    import inspect
+    from on_device_image_captioning_amd.captioning_model import CaptioningModel
+    from on_device_image_captioning_amd.ensemble_captioning_model import EsembleCaptioningModel
+    for fn in (CaptioningModel.beam_search, CaptioningModel.diverse_beam_search, EsembleCaptioningModel.ensemble_beam_search):
+        ps = inspect.signature(fn).parameters
+        for name, default in (("no_repeat_ngram_size", 0), ("min_length", 0), ("banned_words", None)):
+            assert ps[name].kind is inspect.Parameter.KEYWORD_ONLY and ps[name].default == default, (fn, name)
+
+
+# ------------------------------------------------------------------------------------------------- header / binding
+def header_struct_fields():
+    text = open(HEADER).read()
+    body = re.search(r"typedef struct odic_search_constraints \{(.*?)\} odic_search_constraints;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    out = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            ctype, name = decl.rsplit(None, 1)
+            if name.startswith("*"):
+                ctype, name = ctype + "*", name[1:]
+            out.append((name, ctype.replace("const ", "").replace(" ", "")))
+    return out
+
+
+def test_header_struct_and_binding_agree():
+    from on_device_image_captioning_amd import _hip
+    ctypes_of = {"int64_t*": ctypes.c_void_p, "int32_t*": ctypes.c_void_p, "int32_t": ctypes.c_int32,
+                 "int64_t": ctypes.c_int64}
+    want = [(n, ctypes_of[t]) for n, t in header_struct_fields()]
+    assert [n for n, _ in want] == ["tokens", "pos", "row_valid", "banned", "n_banned", "no_repeat_ngram", "min_words",
+                                    "eos_idx", "T"]
+    assert list(_hip.SearchConstraints._fields_) == want
+    # the layout a C compiler gives the struct: four pointers, three int32, padding, int64, int32, padding
+    S = _hip.SearchConstraints
+    assert (S.n_banned.offset, S.no_repeat_ngram.offset, S.min_words.offset, S.eos_idx.offset, S.T.offset) == \
+        (32, 36, 40, 48, 56) and ctypes.sizeof(S) == 64
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    proto = re.search(r"int odic_topk_rows_constrained\((.*?)\);", text, flags=re.S).group(1)
+    args = [a.strip() for a in proto.split(",")]
+    assert len(args) == 9 and args[2].startswith("const odic_search_constraints*")
+    res, argtypes = _hip._SIGNATURES["odic_topk_rows_constrained"]
+    assert res is ctypes.c_int and len(argtypes) == 9 and argtypes[2] is ctypes.POINTER(_hip.SearchConstraints)
+    assert _hip.ABI_VERSION == 26 and re.search(r"#define ODIC_ABI_VERSION 26\b", text)
+
+
+def test_the_library_refuses_bad_arguments_without_a_gpu():
+    from on_device_image_captioning_amd import _hip
+    if not os.path.exists(_hip.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    lib = _hip.load()
+    assert lib.odic_abi_version() == 26
+
+    def call(N=4, V=100, k=3, ldl=100, logp=16, tv=16, ti=16, cons=True, **kw):
+        f = dict(tokens=16, pos=16, row_valid=None, banned=None, n_banned=0, no_repeat_ngram=2, min_words=1, eos_idx=EOS,
+                 T=12)
+        f.update(kw)
+        c = _hip.SearchConstraints(**f)
+        return lib.odic_topk_rows_constrained(logp, ldl, ctypes.byref(c) if cons else None, tv, ti, N, V, k, None)
+
+    bad = [dict(V=12 + 3 - 1), dict(n_banned=86, banned=16), dict(k=0), dict(k=17), dict(no_repeat_ngram=-1),
+           dict(no_repeat_ngram=13), dict(min_words=-1), dict(T=1), dict(T=129), dict(n_banned=-1), dict(n_banned=1025, banned=16, V=4000, ldl=4000),
+           dict(V=262145, ldl=262145), dict(N=0), dict(ldl=99), dict(logp=None), dict(tv=None), dict(ti=None), dict(cons=False),
+           dict(tokens=None), dict(pos=None), dict(n_banned=2, banned=None)]
+    for kw in bad:
+        assert call(**kw) == -1, kw                                     # ODIC_EINVAL, before any launch

@@ -4,9 +4,11 @@ FULL geometry, features-only model, 16 images, fp32, HIP events around the step 
 poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
 it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
 
-    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9
 
-A form this build does not have (diverse on a build before ABI 25) is reported as absent.
+cbeam:K is beam:K under constraints: no_repeat_ngram_size=2, min_length=5 and 8 banned words; the step then
+holds one launch more (odic_topk_rows_constrained) and the top-k launch writes the log-prob rows.
+A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26) is reported as absent.
 """
 import argparse
 import os
@@ -52,7 +54,14 @@ def main():
         else:
             R = int(shape)
             one = lambda st: eng.beam_step(st, bench.EOS)                          # noqa: E731
+        if kind == "cbeam" and not hasattr(eng, "search_constraints"):
+            print(f"{form}: not in this build")
+            continue
         st = eng.new_state(a.images, R, T, kv, enc_len)
+        if kind == "cbeam":
+            cons = eng.search_constraints(st, bench.EOS, no_repeat_ngram=2, min_words=5,
+                                          banned=[w for w in range(100, 110) if w not in (bench.SOS, bench.EOS)][:8])
+            one = lambda st: eng.beam_step(st, bench.EOS, constraints=cons)        # noqa: E731
         def search():
             ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=st.emb)
             for _ in range(steps):
