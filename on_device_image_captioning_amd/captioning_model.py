@@ -23,8 +23,8 @@ from . import engine as _engine
 from . import ops
 from . import grounding as _grounding
 from . import scoring as _scoring
-
-_DONE_POLL = 4      # host looks at the device `done` flag every this many steps
+from . import search as _search
+from .search import _DONE_POLL      # noqa: F401  (the sampling loop below; importers of this module)
 
 
 class CaptioningModel(nn.Module):
@@ -96,27 +96,9 @@ class CaptioningModel(nn.Module):
         """The constraint keywords of the search methods, checked on the host before any device work: None when none is
         active (the search then launches exactly what it always did), else the keywords of
         CaptionerEngine.search_constraints."""
-        banned = [] if banned_words is None else sorted({int(w) for w in banned_words})
-        n, m = int(no_repeat_ngram_size), int(min_length)
-        if n < 0 or m < 0:
-            raise ValueError("no_repeat_ngram_size and min_length must be >= 0")
-        if n == 0 and m == 0 and not banned:
-            return None
-        if sampling:
-            raise ValueError("no_repeat_ngram_size / min_length / banned_words apply to the deterministic searches only: "
-                             "drawing under constraints (sample_or_max='sample', mode='sampling') is not supported")
-        T = max(1, max_seq_len - 1) + 1
-        if m > max_seq_len - 2:
-            raise ValueError(f"min_length {m} > max_seq_len - 2 = {max_seq_len - 2}: no caption could end")
-        if sos_idx in banned or eos_idx in banned:
-            raise ValueError("the SOS and EOS ids cannot be banned (min_length is the control over where a caption ends)")
-        V = self._vocab_size()
-        if len(banned) + T + rows_per_image > V:
-            raise ValueError(f"{len(banned)} banned words + {T} positions + {rows_per_image} candidates per row exceed the "
-                             f"vocabulary ({V} words): a row could run out of admissible words")
-        if len(banned) > 1024:
-            raise ValueError("at most 1024 banned words")
-        return dict(no_repeat_ngram=n, min_words=m, banned=banned)
+        return _search.check_constraints(no_repeat_ngram_size, min_length, banned_words, V=self._vocab_size,
+                                         max_seq_len=max_seq_len, rows_per_image=rows_per_image, sos_idx=sos_idx,
+                                         eos_idx=eos_idx, sampling=sampling)
 
     def _next_sampling_seed(self) -> int:
         """A fresh Philox key per sampling call (so repeated calls differ), reproducible from `sampling_seed`."""
@@ -208,6 +190,20 @@ class CaptioningModel(nn.Module):
     def _max_seq_len(self) -> int:
         return self.geometry.max_seq_len
 
+    def _packed_captions(self, n_img: int, captions, enc_x_num_pads, captions_per_image: int, pad_idx, dec_x_num_pads):
+        """The checked operands of score_captions / word_attention: (tokens int64 [N, Tm] SOS … EOS, the lengths, the
+        decoder lengths int32 [N] = length - 1, enc_x_num_pads with its default)."""
+        toks, lens = _scoring.pack_captions(captions, dec_x_num_pads, pad_idx=pad_idx, max_seq_len=self._max_seq_len())
+        N = toks.shape[0]
+        if captions_per_image < 1 or N != n_img * captions_per_image:
+            raise ValueError(f"{N} captions for {n_img} inputs x {captions_per_image} captions per image")
+        V = self._vocab_size()
+        if int(toks.min()) < 0 or int(toks.max()) >= V:
+            raise ValueError(f"token ids must lie in [0, {V})")
+        if enc_x_num_pads is None:
+            enc_x_num_pads = [0] * n_img
+        return toks, lens, torch.tensor([n - 1 for n in lens], dtype=torch.int32), enc_x_num_pads
+
     def score_captions(self, enc_x, captions, enc_x_num_pads=None, *, captions_per_image: int = 1, pad_idx=None,
                        dec_x_num_pads=None, row_chunk: Optional[int] = None) -> "_scoring.CaptionScores":
         """Log-probability of given captions under the model, in one whole-sequence decoder pass (what test.py:84-138
@@ -216,16 +212,9 @@ class CaptioningModel(nn.Module):
         are image-major — captions[i·R : (i+1)·R] belong to image i — and the encoder runs once per image.
         Returns scoring.CaptionScores: logprobs[n, t] = log p(token t+1 | tokens 0..t), 0 behind the caption's end."""
         n_img = enc_x.shape[0]
-        toks, lens = _scoring.pack_captions(captions, dec_x_num_pads, pad_idx=pad_idx, max_seq_len=self._max_seq_len())
-        N, Tm = toks.shape
-        if captions_per_image < 1 or N != n_img * captions_per_image:
-            raise ValueError(f"{N} captions for {n_img} inputs x {captions_per_image} captions per image")
-        V = self._vocab_size()
-        if int(toks.min()) < 0 or int(toks.max()) >= V:
-            raise ValueError(f"token ids must lie in [0, {V})")
-        if enc_x_num_pads is None:
-            enc_x_num_pads = [0] * n_img
-        dec_len = torch.tensor([n - 1 for n in lens], dtype=torch.int32)
+        toks, lens, dec_len, enc_x_num_pads = self._packed_captions(n_img, captions, enc_x_num_pads, captions_per_image,
+                                                                    pad_idx, dec_x_num_pads)
+        Tm = toks.shape[1]
         st = self._sequence_stats(enc_x, enc_x_num_pads, n_img, toks[:, :-1].contiguous(), dec_len,
                                   toks[:, 1:].contiguous(), row_chunk)
         dv = st["logp"].device
@@ -263,24 +252,17 @@ class CaptioningModel(nn.Module):
         a_layers, a_reduce = _grounding.parse_layers(layers, self.geometry.N_dec)
         a_heads = _grounding.parse_heads(heads)
         n_img = enc_x.shape[0]
-        if enc_x_num_pads is None:
-            enc_x_num_pads = [0] * n_img
         if captions is None:
             if sos_idx is None or eos_idx is None:
                 raise ValueError("word_attention without captions generates them and needs sos_idx and eos_idx")
             if captions_per_image != 1:
                 raise ValueError("word_attention without captions grounds one generated caption per input")
-            best, _ = self.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx, beam_size=beam_size,
-                                       how_many_outputs=1, max_seq_len=max_seq_len)
+            best, _ = self.beam_search(enc_x, [0] * n_img if enc_x_num_pads is None else enc_x_num_pads, sos_idx=sos_idx,
+                                       eos_idx=eos_idx, beam_size=beam_size, how_many_outputs=1, max_seq_len=max_seq_len)
             captions, pad_idx, dec_x_num_pads = [per[0] for per in best], None, None
-        toks, lens = _scoring.pack_captions(captions, dec_x_num_pads, pad_idx=pad_idx, max_seq_len=self._max_seq_len())
+        toks, lens, dec_len, enc_x_num_pads = self._packed_captions(n_img, captions, enc_x_num_pads, captions_per_image,
+                                                                    pad_idx, dec_x_num_pads)
         N, Tm = toks.shape
-        if captions_per_image < 1 or N != n_img * captions_per_image:
-            raise ValueError(f"{N} captions for {n_img} inputs x {captions_per_image} captions per image")
-        V = self._vocab_size()
-        if int(toks.min()) < 0 or int(toks.max()) >= V:
-            raise ValueError(f"token ids must lie in [0, {V})")
-        dec_len = torch.tensor([n - 1 for n in lens], dtype=torch.int32)
         eng = self._captioner_engine()
         dv = eng.device
         mem = self.forward_enc(enc_x, enc_x_num_pads)
@@ -334,28 +316,7 @@ class CaptioningModel(nn.Module):
             return y.to(enc_x.device) if isinstance(enc_x, torch.Tensor) else y
         assert ("sos_idx" in kwargs.keys() or "eos_idx" in kwargs.keys()), \
             "sos and eos must be provided in case of batch sampling or beam search"
-        sos_idx = kwargs.get("sos_idx", -999)
-        eos_idx = kwargs.get("eos_idx", -999)
-        if mode == "beam_search":
-            return self.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                    beam_size=kwargs.get("beam_size", 5),
-                                    how_many_outputs=kwargs.get("how_many_outputs", 1),
-                                    max_seq_len=kwargs.get("beam_max_seq_len", 20),
-                                    sample_or_max=kwargs.get("sample_or_max", "max"), **_constraint_kwargs(kwargs))
-        if mode == "sampling":
-            self._search_constraint_args(**_constraint_kwargs(kwargs), sos_idx=sos_idx, eos_idx=eos_idx,
-                                         max_seq_len=kwargs.get("sample_max_seq_len", 20), rows_per_image=1, sampling=True)
-            return self.get_batch_multiple_sampled_prediction(
-                enc_x, enc_x_num_pads, num_outputs=kwargs.get("how_many_outputs", 1), sos_idx=sos_idx,
-                eos_idx=eos_idx, max_seq_len=kwargs.get("sample_max_seq_len", 20))
-        if mode == "diverse_beam_search":
-            return self.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                            num_groups=kwargs.get("num_groups", 3),
-                                            group_size=kwargs.get("group_size", 3),
-                                            diversity_penalty=kwargs.get("diversity_penalty", 0.5),
-                                            how_many_outputs=kwargs.get("how_many_outputs", None),
-                                            max_seq_len=kwargs.get("beam_max_seq_len", 20), **_constraint_kwargs(kwargs))
-        raise ValueError(f"unknown mode {mode!r}")
+        return _search.dispatch(self, mode, kwargs, enc_x, enc_x_num_pads)
 
     def get_batch_multiple_sampled_prediction(self, enc_input, enc_input_num_pads, num_outputs, sos_idx, eos_idx,
                                               max_seq_len):
@@ -431,7 +392,6 @@ class CaptioningModel(nn.Module):
                             max_seq_len, sample: bool = False, constraints: Optional[dict] = None
                             ) -> Tuple[List[List[List[int]]], torch.Tensor]:
         eng = self._captioner_engine()
-        dv = eng.device
         B, S, _ = mem.shape
         k = beam_size
         steps = max(1, max_seq_len - 1)            # positions 0 .. steps-1 are fed; prefixes reach steps+1
@@ -443,39 +403,25 @@ class CaptioningModel(nn.Module):
         V = eng.g.vocab_size
         seed = self._next_sampling_seed() if sample else 0
         cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
-        for t in range(steps):
-            if sample:
-                # 'sample' variant (captioning_model.py:128-131,166-168): the k candidates of every beam are
-                # drawn without replacement from its distribution instead of being its top-k — on the device
-                eng.step_logits(st)
-                ops.logsoftmax_sample(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, k, seed, st.pos)
-                if self._draw_log is not None:                    # test hook: the draws, for replay in the oracle
-                    self._draw_log.append(st.cand_idx.cpu().clone())
-                ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx)
-            else:
-                eng.beam_step(st, eos_idx, constraints=cons)
-                if self._cand_log is not None:                    # test hook: the candidates, for replay in the model
-                    self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
-            if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(st.done.item()):
-                break
-        order = torch.empty(B, k, dtype=torch.int32, device=dv)
-        score = torch.empty(B, k, dtype=torch.float32, device=dv)
-        ops.beam_finalize(st.beam_state, order, score, B, k)
-        order_h = order.cpu()
-        n_elem_h = st.n_elem.view(B, k).cpu()
-        tokens_h = st.tokens.cpu()
-        res_tok: List[List[List[int]]] = []
-        lp_rows = []
-        for b in range(B):
-            per = []
-            for j in range(how_many_outputs):
-                i = int(order_h[b, j])
-                n = int(n_elem_h[b, i])
-                per.append(tokens_h[b, i, :n].tolist())
-                lp_rows.append(st.logprobs[b, i, :n])
-            res_tok.append(per)
-        lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
-        return res_tok, lp
+
+        def draw_step(t):
+            # 'sample' variant (captioning_model.py:128-131,166-168): the k candidates of every beam are drawn
+            # without replacement from its distribution instead of being its top-k — on the device
+            eng.step_logits(st)
+            ops.logsoftmax_sample(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, k, seed, st.pos)
+            if self._draw_log is not None:                        # test hook: the draws, for replay in the oracle
+                self._draw_log.append(st.cand_idx.cpu().clone())
+            ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx)
+
+        def step(t):
+            eng.beam_step(st, eos_idx, constraints=cons)
+            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
+                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
+
+        _search.run_steps(st, steps, draw_step if sample else step)
+        order, _ = _search.rank_beams(st)
+        # (the log-probs are on the engine's device; beam_search moves them to the input's)
+        return _search.read_captions(st, order.cpu()[:, :how_many_outputs], how_many_outputs)
 
     def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
                             diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20, *, no_repeat_ngram_size=0,
@@ -504,7 +450,6 @@ class CaptioningModel(nn.Module):
                                                    max_seq_len=max_seq_len, rows_per_image=num_groups * group_size)
         mem = self.forward_enc(enc_input, enc_input_num_pads)
         eng = self._captioner_engine()
-        dv = eng.device
         B, S, _ = mem.shape
         G, kg = int(num_groups), int(group_size)
         R = G * kg
@@ -515,38 +460,18 @@ class CaptioningModel(nn.Module):
         st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
         ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
         cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
-        for t in range(steps):
+
+        def step(t):
             eng.group_beam_step(st, eos_idx, G, penalty, constraints=cons)
             if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
-            if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(st.done.item()):
-                break
-        order = torch.empty(B, R, dtype=torch.int32, device=dv)
-        score = torch.empty(B, R, dtype=torch.float32, device=dv)
-        ops.beam_finalize(st.beam_state, order, score, B, R)
+
+        _search.run_steps(st, steps, step)
+        _, score = _search.rank_beams(st)
         best = score.view(B, G, kg).cpu().argmax(dim=2)           # (first maximum: ties go to the lower row)
-        n_elem_h = st.n_elem.view(B, R).cpu()
-        tokens_h = st.tokens.cpu()
-        res_tok: List[List[List[int]]] = []
-        lp_rows = []
-        for b in range(B):
-            per = []
-            for j in range(how_many_outputs):
-                i = j * kg + int(best[b, j])
-                n = int(n_elem_h[b, i])
-                per.append(tokens_h[b, i, :n].tolist())
-                lp_rows.append(st.logprobs[b, i, :n])
-            res_tok.append(per)
-        lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
+        rows = torch.arange(G)[None, :] * kg + best               # output j of an image: the best row of group j
+        res_tok, lp = _search.read_captions(st, rows[:, :how_many_outputs], how_many_outputs)
         return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
-
-
-_CONSTRAINT_KEYS = ("no_repeat_ngram_size", "min_length", "banned_words")
-
-
-def _constraint_kwargs(args) -> dict:
-    """The constraint keywords present in a forward(**kwargs) / beam_search_args mapping (absent = the default)."""
-    return {k: args[k] for k in _CONSTRAINT_KEYS if k in args}
 
 
 def _as_list(pads, n: int) -> List[int]:
@@ -581,32 +506,10 @@ class Captioner:
     def __call__(self, enc_x, dec_x=None, enc_x_num_pads=[0], dec_x_num_pads=[0], mode="beam_search"):
         assert ("sos_idx" in self.beam_search_args.keys() or "eos_idx" in self.beam_search_args.keys()), \
             "sos and eos must be provided in case of batch sampling or beam search"
-        sos_idx = self.beam_search_args["sos_idx"]
-        eos_idx = self.beam_search_args["eos_idx"]
         a = self.beam_search_args
-        if mode == "beam_search":
-            self.apply_log_softmax = True
-            return self.model.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                          beam_size=a.get("beam_size", 5),
-                                          how_many_outputs=a.get("how_many_outputs", 1),
-                                          max_seq_len=a.get("beam_max_seq_len", 20),
-                                          sample_or_max=a.get("sample_or_max", "max"), **_constraint_kwargs(a))
-        if mode == "sampling":
-            self.apply_log_softmax = True
-            self.model._search_constraint_args(**_constraint_kwargs(a), sos_idx=sos_idx, eos_idx=eos_idx,
-                                               max_seq_len=a.get("sample_max_seq_len", 20), rows_per_image=1,
-                                               sampling=True)
-            return self.model.get_batch_multiple_sampled_prediction(
-                enc_x, enc_x_num_pads, num_outputs=a.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
-                max_seq_len=a.get("sample_max_seq_len", 20))
-        if mode == "diverse_beam_search":
-            self.apply_log_softmax = True
-            return self.model.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                                  num_groups=a.get("num_groups", 3), group_size=a.get("group_size", 3),
-                                                  diversity_penalty=a.get("diversity_penalty", 0.5),
-                                                  how_many_outputs=a.get("how_many_outputs", None),
-                                                  max_seq_len=a.get("beam_max_seq_len", 20), **_constraint_kwargs(a))
-        raise ValueError(f"unknown mode {mode!r}")
+        self.apply_log_softmax = True
+        args = dict(a, sos_idx=a["sos_idx"], eos_idx=a["eos_idx"])      # (both required here, KeyError; forward() has -999)
+        return _search.dispatch(self.model, mode, args, enc_x, enc_x_num_pads)
 
     def forward_enc(self, enc_input, enc_input_num_pads):
         return self.model.forward_enc(enc_input, enc_input_num_pads)

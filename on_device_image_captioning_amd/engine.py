@@ -23,6 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _hip, ops
+from .search import check_constraints
 from .weights import Geometry
 
 SD = Dict[str, torch.Tensor]
@@ -541,21 +542,16 @@ class CaptionerEngine:
                            banned=None) -> Optional["_hip.SearchConstraints"]:
         """The constraints of a search on `st` for beam_step / group_beam_step, or None when none is
         active: words that would repeat an n-gram of the row's prefix, EOS before `min_words` words, the word ids in
-        `banned`.  Everything the kernel reads is device resident (st.tokens, st.pos, st.row_valid, the uploaded ban list)."""
-        banned = sorted({int(w) for w in banned}) if banned is not None else []
-        if not banned and no_repeat_ngram == 0 and min_words == 0:
+        `banned`.  The arguments pass search.check_constraints (as no_repeat_ngram_size, min_length, banned_words of a
+        caption of st.T positions).  Everything the kernel reads is device resident (st.tokens, st.pos, st.row_valid, the
+        uploaded ban list)."""
+        c = check_constraints(no_repeat_ngram, min_words, banned, V=self.g.vocab_size, max_seq_len=st.T,
+                              rows_per_image=st.beams, sos_idx=None, eos_idx=eos_idx)
+        if c is None:
             return None
-        V = self.g.vocab_size
-        if no_repeat_ngram < 0 or min_words < 0:
-            raise ValueError("no_repeat_ngram and min_words must be >= 0")
-        if len(banned) + st.T + st.beams > V:
-            raise ValueError(f"{len(banned)} banned words + {st.T} positions + {st.beams} candidates exceed the "
-                             f"vocabulary ({V} words): a row could run out of admissible words")
-        if len(banned) > 1024:
-            raise ValueError("at most 1024 banned words")
-        st.banned = torch.tensor(banned, dtype=torch.int32, device=self.device) if banned else None
+        st.banned = torch.tensor(c["banned"], dtype=torch.int32, device=self.device) if c["banned"] else None
         return ops.search_constraints(st.tokens, st.pos, st.T, eos_idx, row_valid=st.row_valid, banned=st.banned,
-                                      no_repeat_ngram=min(int(no_repeat_ngram), st.T), min_words=int(min_words))
+                                      no_repeat_ngram=min(c["no_repeat_ngram"], st.T), min_words=c["min_words"])
 
     def constrained_candidates(self, st: DecodeState, constraints, logp: Optional[torch.Tensor] = None) -> None:
         """st.cand_val / st.cand_idx = the st.beams best ADMISSIBLE words of every row.  The rows are the log-probs the
@@ -569,18 +565,22 @@ class CaptionerEngine:
             ops.logsoftmax_topk(st.logits, V, logp, V, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.topk_rows_constrained(logp, constraints, st.cand_val, st.cand_idx, st.beams)
 
+    def _candidates(self, st: DecodeState, constraints) -> None:
+        """The decoder pass of a step, then st.cand_val / st.cand_idx = the st.beams best (admissible) words of every row."""
+        self.step_logits(st, embed=False)
+        if constraints is not None:
+            self.constrained_candidates(st, constraints)
+        else:
+            V = self.g.vocab_size
+            ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+
     def beam_step(self, st: DecodeState, eos_idx: int, constraints=None) -> None:
         """One full search step: decoder → log-softmax / top-k (one block per row) → beam bookkeeping + the next
         position's input rows (one block per image).  The state must have been armed with
         ops.beam_reset(st.beam_state, ..., emb=st.emb).  (Both launches in one were slower, DESIGN.md §4.6: a block
         per image then works through its k rows alone.)  `constraints` (search_constraints(st, ...)): the top-k launch
         also writes the log-prob rows, and odic_topk_rows_constrained re-selects the candidates from them."""
-        self.step_logits(st, embed=False)
-        V = self.g.vocab_size
-        if constraints is not None:
-            self.constrained_candidates(st, constraints)
-        else:
-            ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        self._candidates(st, constraints)
         ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx, emb=st.emb)
 
     def group_beam_step(self, st: DecodeState, eos_idx: int, groups: int, penalty: float, constraints=None) -> None:
@@ -589,12 +589,7 @@ class CaptionerEngine:
         the groups in turn (odic_group_beam_step, one block per image)."""
         if groups < 1 or st.beams % groups:
             raise ValueError(f"{st.beams} rows per image do not split into {groups} groups")
-        self.step_logits(st, embed=False)
-        V = self.g.vocab_size
-        if constraints is not None:
-            self.constrained_candidates(st, constraints)
-        else:
-            ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        self._candidates(st, constraints)
         ops.group_beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, groups, st.beams // groups, st.T, eos_idx,
                             penalty, emb=st.emb)
 

@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .captioning_model import CaptioningModel, _DONE_POLL, _constraint_kwargs
+from . import search as _search
+from .captioning_model import CaptioningModel
 
 
 class EsembleCaptioningModel(CaptioningModel):
@@ -31,13 +32,7 @@ class EsembleCaptioningModel(CaptioningModel):
     def forward(self, enc_x, dec_x=None, enc_x_num_pads=[0], dec_x_num_pads=[0], apply_log_softmax=False,
                 mode="beam_search", **kwargs):
         assert mode == "beam_search", "this class supports only beam search."
-        sos_idx = kwargs.get("sos_idx", -999)
-        eos_idx = kwargs.get("eos_idx", -999)
-        return self.ensemble_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                         beam_size=kwargs.get("beam_size", 5),
-                                         how_many_outputs=kwargs.get("how_many_outputs", 1),
-                                         max_seq_len=kwargs.get("beam_max_seq_len", 20),
-                                         sample_or_max=kwargs.get("sample_or_max", "max"), **_constraint_kwargs(kwargs))
+        return _search.dispatch(self, mode, kwargs, enc_x, enc_x_num_pads)
 
     def forward_enc(self, enc_input, enc_input_num_pads):
         return [m.forward_enc(enc_input, enc_input_num_pads) for m in self.models_list]
@@ -110,53 +105,26 @@ class EsembleCaptioningModel(CaptioningModel):
         # 'sample' (reference models/ensemble_captioning_model.py:123-130,174-183): the k candidates of every beam are drawn
         # without replacement from the averaged distribution — odic_logsoftmax_sample on rows that already are
         # log-probabilities (its normalisation is then the identity up to rounding), keyed by the lead member's seed
-        seed = self.models_list[0]._next_sampling_seed() if sample else 0
+        seed = self.models_list[0]._next_sampling_seed() if sample else None
         mems = self.forward_enc(enc_input, enc_input_num_pads)
         engs = [m._captioner_engine() for m in self.models_list]
-        dv = engs[0].device
         B, S, _ = mems[0].shape
         k = beam_size
         steps = max(1, max_seq_len - 1)
         T = steps + 1
-        states = []
-        for m, eng, mem in zip(self.models_list, engs, mems):
-            st = eng.new_state(B, k, T, eng.project_kv(mem), m._enc_lens(B, S, enc_input_num_pads))
-            if states:                                           # one beam state for all members
-                lead = states[0]
-                st.anc, st.row_valid, st.next_tok, st.pos = lead.anc, lead.row_valid, lead.next_tok, lead.pos
-            states.append(st)
-        lead = states[0]
-        lead.tokens[:, :, 0] = sos_idx
-        lead.next_tok.fill_(sos_idx)
-        V = engs[0].g.vocab_size
-        avg = torch.empty(lead.N, V, dtype=torch.float32, device=dv)
+        states = [eng.new_state(B, k, T, eng.project_kv(mem), m._enc_lens(B, S, enc_input_num_pads))
+                  for m, eng, mem in zip(self.models_list, engs, mems)]
+        lead = _search.share_beam_state(states)
+        ops.beam_reset(lead.beam_state, B, k, T, sos_idx, emb=None)      # (the members embed for themselves in step_logits)
+        avg = torch.empty(lead.N, engs[0].g.vocab_size, dtype=torch.float32, device=engs[0].device)
         cons = engs[0].search_constraints(lead, eos_idx, **constraints) if constraints else None
-        for t in range(steps):
-            for eng, st in zip(engs, states):
-                eng.step_logits(st)                              # reads the shared next_tok / pos / ancestor table
-            ops.ensemble_logprobs([st.logits for st in states], avg)
-            if sample:
-                ops.logsoftmax_sample(avg, V, None, 0, lead.cand_val, lead.cand_idx, lead.N, V, k, seed, lead.pos)
-            elif cons is not None:
-                engs[0].constrained_candidates(lead, cons, logp=avg)
-            else:
-                ops.topk_rows(avg, lead.cand_val, lead.cand_idx, k)
-            ops.beam_step(lead.cand_val, lead.cand_idx, lead.beam_state, lead.n_img, lead.beams, lead.T, eos_idx)
-            if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(lead.done.item()):
-                break
-        order = torch.empty(B, k, dtype=torch.int32, device=dv)
-        score = torch.empty(B, k, dtype=torch.float32, device=dv)
-        ops.beam_finalize(lead.beam_state, order, score, B, k)
-        order_h, n_elem_h, tokens_h = order.cpu(), lead.n_elem.view(B, k).cpu(), lead.tokens.cpu()
-        res_tok: List[List[List[int]]] = []
-        lp_rows = []
-        for b in range(B):
-            per = []
-            for j in range(how_many_outputs):
-                i = int(order_h[b, j])
-                n = int(n_elem_h[b, i])
-                per.append(tokens_h[b, i, :n].tolist())
-                lp_rows.append(lead.logprobs[b, i, :n])
-            res_tok.append(per)
-        lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
-        return res_tok, lp
+        _search.run_steps(lead, steps, lambda t: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed,
+                                                                       constraints=cons))
+        order, _ = _search.rank_beams(lead)
+        # (the log-probs stay on the engine's device, unlike beam_search's, which go to the input's)
+        return _search.read_captions(lead, order.cpu()[:, :how_many_outputs], how_many_outputs)
+
+    def beam_search(self, *a, **k):
+        """ensemble_beam_search, with its arguments, under the name the mode dispatch (search.dispatch) calls; the
+        single-model beam_search this overrides could not run on a list of encoder memories."""
+        return self.ensemble_beam_search(*a, **k)

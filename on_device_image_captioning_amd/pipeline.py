@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import ops
+from . import search as _search
 from .captioning_model import CaptioningModel
 
 
@@ -95,8 +96,7 @@ class CaptionPipeline:
         for l in range(self.D):
             sts = [c.new_state(self.NB, beam_size, self.T, self.kv[l][mi], self.enc_len_grps[l])
                    for mi, (_, c) in enumerate(self.members)]
-            for st in sts[1:]:
-                st.anc, st.row_valid, st.next_tok, st.pos = sts[0].anc, sts[0].row_valid, sts[0].next_tok, sts[0].pos
+            _search.share_beam_state(sts)
             self.member_states.append(sts)
         self.states = [sts[0] for sts in self.member_states]
         self.avg_logp = [torch.empty(self.NB * beam_size, g.vocab_size, dtype=torch.float32, device=dv)
@@ -180,13 +180,7 @@ class CaptionPipeline:
         if self.M == 1:
             self.cap.beam_step(self.states[lane], self.eos)
             return
-        sts = self.member_states[lane]
-        lead = sts[0]
-        for (_, cap), st in zip(self.members, sts):
-            cap.step_logits(st)                                   # private caches, shared next_tok / pos / ancestors
-        ops.ensemble_logprobs([st.logits for st in sts], self.avg_logp[lane])
-        ops.topk_rows(self.avg_logp[lane], lead.cand_val, lead.cand_idx, lead.beams)
-        ops.beam_step(lead.cand_val, lead.cand_idx, lead.beam_state, lead.n_img, lead.beams, lead.T, self.eos)
+        _search.ensemble_step([cap for _, cap in self.members], self.member_states[lane], self.avg_logp[lane], self.eos)
 
     def replay_search(self, lane: int) -> None:
         """All steps of one search on the current stream, no polling (measurement tools)."""

@@ -1,0 +1,139 @@
+"""The host side of a search, once, for beam_search, diverse_beam_search, ensemble_beam_search and the ensemble step of
+CaptionPipeline: argument rules, mode dispatch, the step loop with its look at the device's
+`done` flag, the read-out of the chosen rows, and the members of an ensemble on one beam state.  Plain functions over a
+DecodeState (engine.py); the device side of a step is ops.beam_step / ops.group_beam_step.
+"""
+from __future__ import annotations
+
+from typing import Callable, List, Optional, Tuple
+
+import torch
+
+from . import ops
+
+_DONE_POLL = 4      # host looks at the device `done` flag every this many steps
+
+
+def _constraint_kwargs(args) -> dict:
+    """The constraint keywords present in a forward(**kwargs) / beam_search_args mapping (absent = the default)."""
+    return {k: args[k] for k in ("no_repeat_ngram_size", "min_length", "banned_words") if k in args}
+
+
+def check_constraints(n: int, m: int, banned, *, V, max_seq_len: int, rows_per_image: int, sos_idx, eos_idx,
+                      sampling: bool = False) -> Optional[dict]:
+    """The rules of a constrained search (no-repeat n-gram size `n`, `m` words at least, the `banned` word ids) for a
+    vocabulary of V words (an int, or a callable that is asked only when the rule is reached), captions of max_seq_len
+    positions and rows_per_image candidates per row.  None when no constraint is active, else the keywords of
+    CaptionerEngine.search_constraints; ValueError for what cannot work."""
+    banned = [] if banned is None else sorted({int(w) for w in banned})
+    n, m = int(n), int(m)
+    if n < 0 or m < 0:
+        raise ValueError("no_repeat_ngram_size and min_length must be >= 0")
+    if n == 0 and m == 0 and not banned:
+        return None
+    if sampling:
+        raise ValueError("no_repeat_ngram_size / min_length / banned_words apply to the deterministic searches only: "
+                         "drawing under constraints (sample_or_max='sample', mode='sampling') is not supported")
+    T = max(1, max_seq_len - 1) + 1
+    if m > max_seq_len - 2:
+        raise ValueError(f"min_length {m} > max_seq_len - 2 = {max_seq_len - 2}: no caption could end")
+    if sos_idx in banned or eos_idx in banned:
+        raise ValueError("the SOS and EOS ids cannot be banned (min_length is the control over where a caption ends)")
+    V = V() if callable(V) else V
+    if len(banned) + T + rows_per_image > V:
+        raise ValueError(f"{len(banned)} banned words + {T} positions + {rows_per_image} candidates per row exceed the "
+                         f"vocabulary ({V} words): a row could run out of admissible words")
+    if len(banned) > 1024:
+        raise ValueError("at most 1024 banned words")
+    return dict(no_repeat_ngram=n, min_words=m, banned=banned)
+
+
+def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
+    """mode='beam_search' | 'sampling' | 'diverse_beam_search' with the keys of `args` (a forward(**kwargs) or
+    beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
+    sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
+    if mode == "beam_search":
+        return model.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
+                                 beam_size=args.get("beam_size", 5), how_many_outputs=args.get("how_many_outputs", 1),
+                                 max_seq_len=args.get("beam_max_seq_len", 20),
+                                 sample_or_max=args.get("sample_or_max", "max"), **cons)
+    if mode == "sampling":
+        max_seq_len = args.get("sample_max_seq_len", 20)
+        model._search_constraint_args(**cons, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len, rows_per_image=1,
+                                      sampling=True)
+        return model.get_batch_multiple_sampled_prediction(
+            enc_x, enc_x_num_pads, num_outputs=args.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
+            max_seq_len=max_seq_len)
+    if mode == "diverse_beam_search":
+        return model.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
+                                         num_groups=args.get("num_groups", 3), group_size=args.get("group_size", 3),
+                                         diversity_penalty=args.get("diversity_penalty", 0.5),
+                                         how_many_outputs=args.get("how_many_outputs", None),
+                                         max_seq_len=args.get("beam_max_seq_len", 20), **cons)
+    raise ValueError(f"unknown mode {mode!r}")
+
+
+def run_steps(lead_state, steps: int, step_fn: Callable[[int], None]) -> None:
+    """Enqueue step_fn(0) .. step_fn(steps - 1); the host looks at the device's `done` flag after every _DONE_POLL-th
+    step (never after the last) and stops there once it is set.  All beams finished is a fixed point of the step, so the
+    steps run between two looks cannot change the result."""
+    for t in range(steps):
+        step_fn(t)
+        if t >= 1 and (t + 1) % _DONE_POLL == 0 and t + 1 < steps and int(lead_state.done.item()):
+            return
+
+
+def rank_beams(st) -> Tuple[torch.Tensor, torch.Tensor]:
+    """odic_beam_finalize: (order int32 [B, k] — the rows of every image, best first; score fp32 [B, k] by row)."""
+    order = torch.empty(st.n_img, st.beams, dtype=torch.int32, device=st.tokens.device)
+    score = torch.empty_like(order, dtype=torch.float32)
+    ops.beam_finalize(st.beam_state, order, score, st.n_img, st.beams)
+    return order, score
+
+
+def read_captions(state, rows: torch.Tensor, how_many_outputs: int) -> Tuple[List[List[List[int]]], torch.Tensor]:
+    """Rows `rows[b, j]` (host integers [B, how_many_outputs], row within image b) of the beam state → the token lists
+    per image and output, cut at the row's length, and their log-probs [B, how_many_outputs, longest chosen row],
+    zero-padded, on the state's device."""
+    B = state.n_img
+    n_elem_h = state.n_elem.view(B, state.beams).cpu()
+    tokens_h = state.tokens.cpu()
+    res_tok, lp_rows = [], []
+    for b in range(B):
+        per = []
+        for j in range(how_many_outputs):
+            i = int(rows[b, j])
+            n = int(n_elem_h[b, i])
+            per.append(tokens_h[b, i, :n].tolist())
+            lp_rows.append(state.logprobs[b, i, :n])
+        res_tok.append(per)
+    return res_tok, torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
+
+
+def share_beam_state(states):
+    """One beam state for all members of an ensemble: every state reads the lead's (states[0]) ancestor table, finished
+    flags, next words and position; only caches and logits stay private.  → the lead state."""
+    lead = states[0]
+    for st in states[1:]:
+        st.anc, st.row_valid, st.next_tok, st.pos = lead.anc, lead.row_valid, lead.next_tok, lead.pos
+    return lead
+
+
+def ensemble_step(engines, states, avg: torch.Tensor, eos_idx: int, *, sample_seed: Optional[int] = None,
+                  constraints=None) -> None:
+    """One search step of an ensemble on share_beam_state(states): a decoder pass per member, avg [N, V] =
+    log(mean_m softmax(logits_m)), the lead's k candidates per row from it — its top-k, under `constraints` the
+    admissible top-k, with `sample_seed` k draws without replacement (odic_logsoftmax_sample on rows that already are
+    log-probabilities: its normalisation is then the identity up to rounding) — and the beam bookkeeping."""
+    lead = states[0]
+    for eng, st in zip(engines, states):
+        eng.step_logits(st)                                      # private caches, shared next_tok / pos / ancestors
+    ops.ensemble_logprobs([st.logits for st in states], avg)
+    if sample_seed is not None:
+        V = avg.shape[1]
+        ops.logsoftmax_sample(avg, V, None, 0, lead.cand_val, lead.cand_idx, lead.N, V, lead.beams, sample_seed, lead.pos)
+    elif constraints is not None:
+        engines[0].constrained_candidates(lead, constraints, logp=avg)
+    else:
+        ops.topk_rows(avg, lead.cand_val, lead.cand_idx, lead.beams)
+    ops.beam_step(lead.cand_val, lead.cand_idx, lead.beam_state, lead.n_img, lead.beams, lead.T, eos_idx)
