@@ -18,6 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from dataclasses import dataclass, fields
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -55,13 +56,58 @@ def _dev(t: torch.Tensor, device, dtype=None) -> torch.Tensor:
 # =================================================================================================
 # Swin backbone  
 # =================================================================================================
+@dataclass
+class SwinFlags:
+    """The backbone's environment switches, parsed once per engine: what each selects and what it measured is DESIGN.md §5.
+    The fusions are bf16-only; a switch that does not apply to the engine's precision is off."""
+    ln_read: bool                       # ODIC_FUSE_BACKBONE_LN_READ: width 192, norm → qkv and norm → fc1 as one launch each
+    fuse_qkv_attn: bool                 # ODIC_FUSE_QKV_ATTENTION: width 192, norm1 → qkv → attention core as one launch
+    fuse_qkv_attn_tiled: bool           # ODIC_FUSE_QKV_ATTENTION_TILED: the wider stages, qkv → attention core as one launch
+    fuse_qkv_attn_tiled_min_c: int      # ODIC_FUSE_QKV_ATTENTION_TILED_MIN_C: the narrowest width that takes it (384 adds stage 1)
+    fuse_mlp: bool                      # ODIC_FUSE_MLP: width 192, norm2 → fc1 → GELU → fc2 + residual as one launch
+    stage_chunks: List[int]             # ODIC_SWIN_CHUNKS: image chunks a stage's blocks run over, per stage
+
+    @classmethod
+    def from_env(cls, precision: str) -> "SwinFlags":
+        env = os.environ
+        on = lambda name: precision == "bf16" and env.get(name, "1") == "1"        # noqa: E731
+        lr = env.get("ODIC_FUSE_BACKBONE_LN_READ", "1")                            # split fp16: opt-in, =x3
+        return cls(ln_read=(precision == "bf16" and lr != "0") or (precision == "x3" and lr == "x3"),
+                   fuse_qkv_attn=on("ODIC_FUSE_QKV_ATTENTION"), fuse_qkv_attn_tiled=on("ODIC_FUSE_QKV_ATTENTION_TILED"),
+                   fuse_qkv_attn_tiled_min_c=int(env.get("ODIC_FUSE_QKV_ATTENTION_TILED_MIN_C", "768")),
+                   fuse_mlp=on("ODIC_FUSE_MLP"), stage_chunks=[int(v) for v in env.get("ODIC_SWIN_CHUNKS", "1").split(",")])
+
+
+# The forms of a block's attention half (what runs in front of proj) and of its MLP half; their launches: DESIGN.md §5.
+ATTN_FP8, ATTN_FUSED, ATTN_LN_READ, ATTN_TILED, ATTN_PLAIN = "fp8", "fused", "ln_read", "tiled", "plain"
+MLP_FP8, MLP_FUSED, MLP_LN_READ, MLP_PLAIN = "fp8", "fused", "ln_read", "plain"
+
+
+def swin_block_plan(precision: str, flags: SwinFlags, C_: int, heads: int, ws: int, res: int, M: int, *, dense: bool,
+                    folded: bool, qkv_a_one: bool, calibrating: bool, fp8_ready: bool) -> Tuple[str, str]:
+    """(attention form, MLP form) of one Swin block over M rows: `dense` — it has the packed bias of the fast attention
+    kernels, `folded` — it has the `*_lnr` weights, `qkv_a_one` — its qkv operand carries no pack-time scale, `calibrating` —
+    the pass records operand ranges (`_amax`) and so needs the LayerNorm outputs and the hidden activations in memory."""
+    cdt = _CDT[precision]
+    if fp8_ready and not calibrating:
+        return ATTN_FP8, MLP_FP8
+    # The folded weights serve BOTH halves, and both hang on the predicate of the qkv product's shape (M x 3C x C) — the
+    # MLP forms too, whose own product is M x 4C x C.  Kept as it has always been (DESIGN.md §5).
+    if folded and not calibrating and ops.a_ln_supported(M, 3 * C_, C_, cdt):
+        return (ATTN_FUSED if flags.fuse_qkv_attn and ws == 12 and dense else ATTN_LN_READ,
+                MLP_FUSED if flags.fuse_mlp and ops.swin_mlp_supported(M, C_, cdt) else MLP_LN_READ)
+    tiled = (flags.fuse_qkv_attn_tiled and not calibrating and dense and qkv_a_one and C_ >= flags.fuse_qkv_attn_tiled_min_c
+             and ops.swin_qkv_attention_tiled_supported(M, C_, heads, ws, res, cdt))
+    return ATTN_TILED if tiled else ATTN_PLAIN, MLP_PLAIN
+
+
 class SwinEngine:
     def __init__(self, sd: SD, g: Geometry, device, precision: str = "fp32", calibration_images=None):
         if precision not in _CDT:
             raise ValueError(f"precision must be one of {list(_CDT)}")
         self.g, self.device, self.precision = g, device, precision
         self.cdt = _CDT[precision]
-        fp8 = precision == "fp8"
+        self.flags = SwinFlags.from_env(precision)
         fast_attn = precision in ("bf16", "fp8", "x3")
         P = "swin_transf"
         f32 = lambda k: _dev(sd[k], device, torch.float32)          # noqa: E731
@@ -76,18 +122,24 @@ class SwinEngine:
                 p = f"{P}.layers.{s}.blocks.{b}"
                 (qkv_w, qkv_a), (proj_w, proj_a) = cw(p + ".attn.qkv.weight"), cw(p + ".attn.proj.weight")
                 (fc1_w, fc1_a), (fc2_w, fc2_a) = cw(p + ".mlp.fc1.weight"), cw(p + ".mlp.fc2.weight")
-                blocks.append(dict(
+                table = f32(p + ".attn.relative_position_bias_table")
+                w = dict(
                     n1w=f32(p + ".norm1.weight"), n1b=f32(p + ".norm1.bias"),
-                    qkv_w=qkv_w, qkv_a=qkv_a, qkv_b=f32(p + ".attn.qkv.bias"),
-                    table=f32(p + ".attn.relative_position_bias_table"),
-                    dense=(ops.shifted_bias_prescaled(f32(p + ".attn.relative_position_bias_table"), g.stage_window(s),
-                                                      (g.stage_dim(s) // g.swin_num_heads[s]) ** -0.5)
+                    qkv_w=qkv_w, qkv_a=qkv_a, qkv_b=f32(p + ".attn.qkv.bias"), table=table,
+                    dense=(ops.shifted_bias_prescaled(table, g.stage_window(s), (g.stage_dim(s) // g.swin_num_heads[s]) ** -0.5)
                            if fast_attn and g.stage_window(s) == 12 else None),
                     proj_w=proj_w, proj_a=proj_a, proj_b=f32(p + ".attn.proj.bias"),
                     n2w=f32(p + ".norm2.weight"), n2b=f32(p + ".norm2.bias"),
                     fc1_w=fc1_w, fc1_a=fc1_a, fc1_b=f32(p + ".mlp.fc1.bias"),
                     fc2_w=fc2_w, fc2_a=fc2_a, fc2_b=f32(p + ".mlp.fc2.bias"),
-                    shift=g.stage_shift(s, b)))
+                    shift=g.stage_shift(s, b))
+                if self.flags.ln_read and g.stage_dim(s) == 192:
+                    # LayerNorm-while-reading: gamma / beta folded into the fp32 weight, which is then packed like every other
+                    for name, lin, norm in (("qkv", ".attn.qkv", "n1"), ("fc1", ".mlp.fc1", "n2")):
+                        Wg, b2, _ = ops.fold_layernorm(f32(p + lin + ".weight"), w[name + "_b"], w[norm + "w"], w[norm + "b"])
+                        op, alpha = pack_operand(Wg, self.cdt)
+                        w[name + "_lnr"] = (op, b2, alpha)
+                blocks.append(w)
             down = None
             if s < len(g.swin_depths) - 1:
                 p = f"{P}.layers.{s}.downsample"
@@ -95,43 +147,8 @@ class SwinEngine:
                 down = dict(nw=f32(p + ".norm.weight"), nb=f32(p + ".norm.bias"), red_w=red_w, red_a=red_a)
             self.stages.append((blocks, down))
         self.fn_w, self.fn_b = f32(f"{P}.norm.weight"), f32(f"{P}.norm.bias")
-        self.stage_chunks = [int(v) for v in os.environ.get("ODIC_SWIN_CHUNKS", "1").split(",")]
-        # bf16 mode, the stage of width 192 (Swin-L stage 0): norm1 → qkv and norm2 → fc1 are ONE launch each — the A-resident
-        # GEMM kernel normalises the fp32 rows while it reads them (odic_gemm_args.a_ln; gamma / beta folded into the
-        # weights): 96 → 85 and 130 → 105 µs per pair at B = 16.  Not at width 384: there the fused form needs the registers
-        # of a resident block and re-reads the fp32 rows once per column range — 95 against 62 µs (tools/ln_read_probe.py).
-        # ODIC_FUSE_BACKBONE_LN_READ=0 keeps the two launches.
-        # (split-fp16 mode: the same form exists — gemm_x3.hip tile configs 20 / 21 with a_ln — and is 1 % faster, but folding
-        #  gamma into the weights changes WHICH near-ties of the xavier checkpoint round the other way: 255 / 256 captions equal
-        #  to fp32 instead of 256 / 256 — the mode exists for that equality, so it is opt-in there: ODIC_FUSE_BACKBONE_LN_READ=x3)
-        lr = os.environ.get("ODIC_FUSE_BACKBONE_LN_READ", "1")
-        self.ln_read = (precision == "bf16" and lr != "0") or (precision == "x3" and lr == "x3")
-        self.fuse_qkv_attn = precision == "bf16" and os.environ.get("ODIC_FUSE_QKV_ATTENTION", "1") == "1"
-        # bf16 mode, the wider stages: qkv → attention core as ONE launch on the LayerNorm output (odic_swin_qkv_attention_tiled,
-        # DESIGN.md §4.3): the qkv tensor is never written.  ODIC_FUSE_QKV_ATTENTION_TILED=0 keeps the two launches.
-        self.fuse_qkv_attn_tiled = precision == "bf16" and os.environ.get("ODIC_FUSE_QKV_ATTENTION_TILED", "1") == "1"
-        # (from width 768 up — Swin-L stages 2 and 3; ODIC_FUSE_QKV_ATTENTION_TILED_MIN_C=384 adds stage 1, measured in §4.3)
-        self.fuse_qkv_attn_tiled_min_c = int(os.environ.get("ODIC_FUSE_QKV_ATTENTION_TILED_MIN_C", "768"))
-        # bf16 mode, width 192: norm2 → fc1 → GELU → fc2 + residual as ONE launch (odic_swin_mlp); it
-        # uses the folded fc1 weights of the LayerNorm-while-reading form.  ODIC_FUSE_MLP=0 keeps the two launches.
-        self.fuse_mlp = precision == "bf16" and os.environ.get("ODIC_FUSE_MLP", "1") == "1"
-        if self.ln_read:
-            for s, (blocks, _) in enumerate(self.stages):
-                if g.stage_dim(s) != 192:
-                    continue
-                for b, w in enumerate(blocks):
-                    p = f"{P}.layers.{s}.blocks.{b}"
-                    if precision == "bf16":
-                        w["qkv_lnr"] = ops.fold_layernorm_bf16(f32(p + ".attn.qkv.weight"), w["qkv_b"], w["n1w"], w["n1b"])[:2] + (1.0,)
-                        w["fc1_lnr"] = ops.fold_layernorm_bf16(f32(p + ".mlp.fc1.weight"), w["fc1_b"], w["n2w"], w["n2b"])[:2] + (1.0,)
-                    else:       # split fp16: the folded weight goes through the same power-of-two packing as every x3 weight
-                        for name, wk, bk, nw, nb in (("qkv_lnr", ".attn.qkv.weight", "qkv_b", "n1w", "n1b"),
-                                                     ("fc1_lnr", ".mlp.fc1.weight", "fc1_b", "n2w", "n2b")):
-                            Wg, b2, _ = ops.fold_layernorm(f32(p + wk), w[bk], w[nw], w[nb])
-                            op, alpha = pack_operand(Wg, self.cdt)
-                            w[name] = (op, b2, alpha)
         self.fp8_ready = False
-        if fp8:
+        if precision == "fp8":
             self._pack_fp8(sd, calibration_images)
 
     # ------------------------------------------------------------------------------------------ fp8 mode
@@ -190,7 +207,6 @@ class SwinEngine:
             raise RuntimeError("SwinEngine.forward wants an fp32 CUDA image batch")
         img = img.contiguous()
         B = img.shape[0]
-        fp8 = self.fp8_ready and _amax is None
         x = ops.patch_embed(img, self.pe_w, self.pe_b, self.pe_g, self.pe_beta, g.swin_patch_size)
         if taps is not None:
             taps["patch_embed"] = x.clone()
@@ -207,56 +223,47 @@ class SwinEngine:
             B = B_all // n_ch
             for ci, bi, w in ((ci, bi, w) for ci in range(n_ch) for bi, w in enumerate(blocks)):
                 x = x_all[ci * B * res * res:(ci + 1) * B * res * res]
-                if fp8:
-                    # LN → fp8 | qkv: fp8 MFMA → fp16 | attention fp16 | proj: fp16 MFMA + residual
+                attn, mlp = swin_block_plan(self.precision, self.flags, C_, heads, ws, res, x.shape[0],
+                                            dense=w["dense"] is not None, folded="qkv_lnr" in w, qkv_a_one=w["qkv_a"] == 1.0,
+                                            calibrating=_amax is not None, fp8_ready=self.fp8_ready)
+                # ---- attention half: x → att
+                if attn == ATTN_FP8:            # LN → fp8 | qkv: fp8 MFMA → fp16 | attention fp16 | proj: fp16 MFMA + residual
                     xn = ops.layernorm(x, w["n1w8"], w["n1b8"], out_dtype=ops.FP8_DTYPE)
                     qkv = ops.gemm(xn, w["qkv_w8"], w["qkv_b"], col_scale=w["qkv_cs"], out_dtype=torch.float16)
-                    att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
-                                               bias_shifted_prescaled=w["dense"])
-                    ops.gemm(att, w["proj_w16"], w["proj_b"], residual=x, out=x)
-                    # LN → fp8 | fc1: fp8 MFMA + GELU → fp8 | fc2: fp8 MFMA + residual
-                    xn = ops.layernorm(x, w["n2w8"], w["n2b8"], out_dtype=ops.FP8_DTYPE)
-                    h = ops.gemm(xn, w["fc1_w8"], w["fc1_b"], act=ops.ACT_GELU, col_scale=w["fc1_cs"],
-                                 out_scale=w["hid_inv"], out_dtype=ops.FP8_DTYPE)
-                    ops.gemm(h, w["fc2_w8"], w["fc2_b"], residual=x, out=x, col_scale=w["fc2_cs"])
-                elif "qkv_lnr" in w and _amax is None and ops.a_ln_supported(x.shape[0], 3 * C_, C_, cdt):
-                    if self.fuse_qkv_attn and ws == 12 and w["dense"] is not None:
-                        # norm1 → qkv → attention core: one launch, q / k / v never leave the chip
-                        att = ops.swin_qkv_attention(x, w["qkv_lnr"][0], w["qkv_lnr"][1], w["dense"], B, res, C_, heads,
-                                                     ws, w["shift"])
-                    else:
-                        qkv = ops.gemm(None, w["qkv_lnr"][0], w["qkv_lnr"][1], a_ln=x, out_dtype=cdt, alpha=w["qkv_lnr"][2])
-                        att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
-                                                   bias_shifted_prescaled=w["dense"])
-                    ops.gemm(att, w["proj_w"], w["proj_b"], residual=x, out=x, alpha=w["proj_a"])
-                    if self.fuse_mlp and ops.swin_mlp_supported(x.shape[0], C_, cdt):
-                        # norm2 → fc1 → GELU → fc2 + residual: one launch, the hidden activations never leave the chip
-                        ops.swin_mlp(x, w["fc1_lnr"][0], w["fc1_lnr"][1], w["fc2_w"], w["fc2_b"], w["fc2_a"], out=x)
-                    else:
-                        h = ops.gemm(None, w["fc1_lnr"][0], w["fc1_lnr"][1], a_ln=x, act=ops.ACT_GELU, out_dtype=cdt,
-                                     alpha=w["fc1_lnr"][2])
-                        ops.gemm(h, w["fc2_w"], w["fc2_b"], residual=x, out=x, alpha=w["fc2_a"])
+                elif attn == ATTN_FUSED:        # q / k / v never leave the chip
+                    att = ops.swin_qkv_attention(x, w["qkv_lnr"][0], w["qkv_lnr"][1], w["dense"], B, res, C_, heads, ws, w["shift"])
+                elif attn == ATTN_LN_READ:
+                    qkv = ops.gemm(None, w["qkv_lnr"][0], w["qkv_lnr"][1], a_ln=x, out_dtype=cdt, alpha=w["qkv_lnr"][2])
                 else:
                     xn = ops.layernorm(x, w["n1w"], w["n1b"], out_dtype=cdt)
                     if _amax is not None:
                         _amax[(s, bi, "ln1")] = float(xn.float().abs().max())
-                    if (self.fuse_qkv_attn_tiled and _amax is None and w["dense"] is not None and w["qkv_a"] == 1.0
-                            and C_ >= self.fuse_qkv_attn_tiled_min_c
-                            and ops.swin_qkv_attention_tiled_supported(x.shape[0], C_, heads, ws, res, cdt)):
-                        # qkv → attention core: one launch, q / k / v never leave the chip
-                        att = ops.swin_qkv_attention_tiled(xn, w["qkv_w"], w["qkv_b"], w["dense"], B, res, C_, heads, ws,
-                                                           w["shift"])
+                    if attn == ATTN_TILED:      # q / k / v never leave the chip
+                        att = ops.swin_qkv_attention_tiled(xn, w["qkv_w"], w["qkv_b"], w["dense"], B, res, C_, heads, ws, w["shift"])
                     else:
                         qkv = ops.gemm(xn, w["qkv_w"], w["qkv_b"], alpha=w["qkv_a"])
-                        att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"],
-                                                   bias_shifted_prescaled=w["dense"])
-                    ops.gemm(att, w["proj_w"], w["proj_b"], residual=x, out=x, alpha=w["proj_a"])
+                if attn not in (ATTN_FUSED, ATTN_TILED):
+                    att = ops.window_attention(qkv, w["table"], B, res, C_, heads, ws, w["shift"], bias_shifted_prescaled=w["dense"])
+                # ---- proj + residual (fp8 mode: the fp16 weight; its proj_a is 1)
+                ops.gemm(att, w["proj_w16" if attn == ATTN_FP8 else "proj_w"], w["proj_b"], residual=x, out=x, alpha=w["proj_a"])
+                # ---- MLP half: x += fc2(GELU(fc1(LN(x))))
+                if mlp == MLP_FP8:              # LN → fp8 | fc1: fp8 MFMA + GELU → fp8 | fc2: fp8 MFMA + residual
+                    xn = ops.layernorm(x, w["n2w8"], w["n2b8"], out_dtype=ops.FP8_DTYPE)
+                    h = ops.gemm(xn, w["fc1_w8"], w["fc1_b"], act=ops.ACT_GELU, col_scale=w["fc1_cs"], out_scale=w["hid_inv"],
+                                 out_dtype=ops.FP8_DTYPE)
+                elif mlp == MLP_FUSED:          # the hidden activations never leave the chip
+                    ops.swin_mlp(x, w["fc1_lnr"][0], w["fc1_lnr"][1], w["fc2_w"], w["fc2_b"], w["fc2_a"], out=x)
+                elif mlp == MLP_LN_READ:
+                    h = ops.gemm(None, w["fc1_lnr"][0], w["fc1_lnr"][1], a_ln=x, act=ops.ACT_GELU, out_dtype=cdt, alpha=w["fc1_lnr"][2])
+                else:
                     xn = ops.layernorm(x, w["n2w"], w["n2b"], out_dtype=cdt)
                     h = ops.gemm(xn, w["fc1_w"], w["fc1_b"], act=ops.ACT_GELU, alpha=w["fc1_a"])
                     if _amax is not None:
                         _amax[(s, bi, "ln2")] = float(xn.float().abs().max())
                         _amax[(s, bi, "hid")] = float(h.float().abs().max())
-                    ops.gemm(h, w["fc2_w"], w["fc2_b"], residual=x, out=x, alpha=w["fc2_a"])
+                if mlp != MLP_FUSED:            # (fp8 mode: the fp8 weight with its column scales; its fc2_a is 1)
+                    fc2_w, fc2_cs = (w["fc2_w8"], w["fc2_cs"]) if mlp == MLP_FP8 else (w["fc2_w"], None)
+                    ops.gemm(h, fc2_w, w["fc2_b"], residual=x, out=x, alpha=w["fc2_a"], col_scale=fc2_cs)
                 if taps is not None:
                     taps[f"s{s}b{bi}"] = x.view(B, res * res, C_).clone()
             x, B = x_all, B_all
@@ -268,6 +275,11 @@ class SwinEngine:
         res = g.stage_res(len(g.swin_depths) - 1)
         out = ops.layernorm(x, self.fn_w, self.fn_b, out_dtype=out_dtype)
         return out.view(B, res * res, -1)
+
+
+for _f in fields(SwinFlags):       # eng.fuse_mlp, eng.stage_chunks, ... read and write eng.flags (a test flips them on a live engine)
+    setattr(SwinEngine, _f.name, property(lambda self, _n=_f.name: getattr(self.flags, _n),
+                                          lambda self, v, _n=_f.name: setattr(self.flags, _n, v)))
 
 
 # =================================================================================================

@@ -141,6 +141,19 @@ _LOWP_CANDIDATES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9)   # gemm_lowp.hip tile configu
 _X3_CANDIDATES = tuple(int(c) for c in os.environ.get("ODIC_X3_TILE_CANDIDATES", "0,1,2,5,6,7,8").split(","))   # gemm_x3.hip
 
 
+def _tile_choice(key, tile_cfg: int) -> Optional[int]:
+    """The caller's explicit `tile_cfg`, else the choice this process remembers for `key`, else the one the ODIC_TILE_CACHE
+    file holds (remembered from then on); None when the shape has no choice yet."""
+    if tile_cfg >= 0:
+        return tile_cfg
+    cfg = _TILE_CHOICE.get(key)
+    if cfg is None and _TILE_CACHE:
+        cfg = _TILE_CACHE.get(_cache_key(key))
+        if cfg is not None:
+            _TILE_CHOICE[key] = cfg
+    return cfg
+
+
 def _tune_gemm(args: "_hip.GemmArgs", key, out: torch.Tensor, candidates=None) -> int:
     lib = _hip.load()
     scratch = torch.empty_like(out)
@@ -224,11 +237,7 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
                       _p(col_scale), float(out_scale), None, 0, None, None)
     if A.dtype in (torch.bfloat16, torch.float16, FP8_DTYPE, H2_DTYPE):
         key = (A.dtype, M, N, K, batch, out.dtype, act, residual is not None)
-        cfg = _TILE_CHOICE.get(key) if tile_cfg < 0 else tile_cfg
-        if cfg is None and tile_cfg < 0 and _TILE_CACHE:
-            cfg = _TILE_CACHE.get(_cache_key(key))
-            if cfg is not None:
-                _TILE_CHOICE[key] = cfg
+        cfg = _tile_choice(key, tile_cfg)
         if cfg is None and _TUNING and _PROFILE is None and ldc == N and batch == 1 \
                 and not torch.cuda.is_current_stream_capturing():
             cfg = _tune_gemm(a, key, out, None if A.dtype == torch.bfloat16 else
@@ -266,11 +275,7 @@ def _gemm_a_ln(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], o
                       dtype_code(W.dtype), dtype_code(out.dtype), tile_cfg, None, float(ln_eps), None, None, 1.0, None, 0, None, None,
                       _p(x), K)
     key = ("a_ln", W.dtype, M, N, K, out.dtype, act)
-    cfg = _TILE_CHOICE.get(key) if tile_cfg < 0 else tile_cfg
-    if cfg is None and _TILE_CACHE:
-        cfg = _TILE_CACHE.get(_cache_key(key))
-        if cfg is not None:
-            _TILE_CHOICE[key] = cfg
+    cfg = _tile_choice(key, tile_cfg)
     if cfg is None:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("gemm(a_ln=...): no tile choice for this shape yet — run it once outside graph capture")
