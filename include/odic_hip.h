@@ -740,6 +740,45 @@ int odic_group_beam_step(const float* cand_val, const int32_t* cand_idx, int32_t
 int odic_beam_reset(const odic_beam_state* st, const odic_embed_args* emb, int32_t n_img, int32_t beams, int32_t T,
                     int64_t sos_idx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Starting a search from a given prefix (csrc/decoder_prefill.hip): the whole-sequence pass over the
+ * prefix fills the step caches, and the reset below puts the beam state at position P.  Both are additions to ABI 26.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The per-position caches of odic_dynexp_step for positions 0..P-1 of n_seq known sequences, from the `lin` rows of the
+ * whole-sequence pass — what P calls of odic_dynexp_step on those rows would have cached, without computing any y.
+ *   lin fp32 [n_seq·P, >=5d] (ldlin), sequence-major as odic_dynexp_seq reads it (row = i·P + t); qexp fp32 [E, d].
+ *   Sequence i writes cache slot s = i·rows_per_image of caches laid out for N_cache sequences and T_cache positions
+ *   (cond_c, key_c, va_c, vb_c [T_cache, N_cache, d]; qk_c [T_cache, N_cache, E]; wfa_c, wfb_c [T_cache, N_cache, T_cache, E]):
+ *     cond/key/va/vb[t][s] = lin columns 0..4d of row i·P + t;   qk[t][s][e] = qexp[e]·key_t;
+ *     wfa[t][s][j][e] = relu(z)/(Σ_{j<=t} relu(z) + eps),  z = (qexp[e]·key_j + cond_t·key_j)/sqrt(d),  j <= t  (wfb: -z)
+ *   with the step kernel's expressions and summation order for the normaliser; the dot products are the 4 x 4 register
+ *   tiles of odic_dynexp_seq.  Entries with j > t, positions >= P and every other slot are not written
+ *   (tests/test_prefix_kernels_gpu.py runs every cache in a guarded, poisoned buffer).
+ *   1 <= P < T_cache <= 128, E in {4, 8, 16, 32}, d a multiple of 64, (n_seq-1)·rows_per_image < N_cache, ldlin a multiple
+ *   of 4 and >= 5d, lin / qexp 16-byte aligned: ODIC_EINVAL before any launch otherwise, with nothing written.
+ *   One 1024-thread block per sequence; (E + P)·P' + 2·P·E words of LDS, P' = P rounded up to 1 mod 4. */
+int odic_dynexp_fill_caches(const float* lin, int64_t ldlin, const float* qexp, float* cond_c, float* key_c, float* va_c,
+                            float* vb_c, float* wfa_c, float* wfb_c, float* qk_c, int32_t n_seq, int32_t P,
+                            int32_t rows_per_image, int32_t N_cache, int32_t T_cache, int32_t d, int32_t E, float eps,
+                            void* stream);
+
+/* The beam state of a search that starts behind a given prefix of P words (the sibling of odic_beam_reset):
+ *   prefix int64 [n_img, P] (ids inside the embedding table: the caller checks), prefix_logp fp32 [n_img, P] (the model's
+ *   log-prob of every prefix word given the ones before it).  For every row n = b·beams + r:
+ *     tokens[n][0] = sos, tokens[n][1..P] = prefix[b];  logprobs[n][0] = 0, logprobs[n][1..P] = prefix_logp[b];
+ *     anc[n][j] = b·beams for j < P (the slot odic_dynexp_fill_caches writes with rows_per_image = beams);
+ *     n_elem = P + 1, has_eos = 0, row_valid = 1, next_tok = prefix[b][P-1];
+ *     cumul = Σ_j logprobs[n][j] in position order when r % group_beams == 0, else -INFINITY;
+ *   *pos = P, *done = 0, *ctr = 0; with emb, y[n] = embed[prefix[b][P-1]]·scale + pos_table[P].
+ *   odic_beam_step (group_beams = beams) and odic_group_beam_step never rank a total of -inf, so the step at position P
+ *   chooses among the candidates of one row per group: the seeding of *pos == 0, from position P.
+ *   1 <= P <= T - 2, beams % group_beams == 0, emb->pos_rows > P, and odic_beam_step's limits on beams, T and n_img:
+ *   ODIC_EINVAL otherwise, before any launch.  All stores stay inside the compact state arrays and columns [0, d) of y. */
+int odic_beam_reset_prefix(const odic_beam_state* st, const odic_embed_args* emb, const int64_t* prefix,
+                           const float* prefix_logp, int32_t n_img, int32_t beams, int32_t group_beams, int32_t T,
+                           int32_t P, int64_t sos_idx, void* stream);
+
 /* Final selection (captioning_model.py:225-241): score = cumul / n_elem, descending order per
  * image → order int32 [n_img, beams], score fp32 [n_img, beams]. */
 int odic_beam_finalize(const odic_beam_state* st, int32_t* order, float* score, int32_t n_img,

@@ -122,6 +122,8 @@ _SIGNATURES = {
     "odic_beam_finalize": (C.c_int, [C.POINTER(BeamState), _P, _P, _I32, _I32, _P]),
     "odic_beam_finalize_best": (C.c_int, [C.POINTER(BeamState), _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "odic_beam_reset": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),
+    "odic_dynexp_fill_caches": (C.c_int, [_P, _I64, _P] + [_P] * 7 + [_I32] * 7 + [_F, _P]),
+    "odic_beam_reset_prefix": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _P, _P] + [_I32] * 5 + [_I64, _P]),
     "odic_jpeg_workspace_bytes": (C.c_size_t, [C.POINTER(JpegBatch)]),
     "odic_jpeg_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
     "odic_jpeg_progressive_workspace_bytes": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
@@ -148,7 +150,10 @@ def load() -> C.CDLL:
             "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repository root.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError here = header/library mismatch
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:       # header/library mismatch: a library built before the symbol existed
+            raise RuntimeError(f"libodic_hip.so has no symbol {name}: it is older than this binding; rebuild") from None
         fn.restype = res
         fn.argtypes = args
     got = lib.odic_abi_version()

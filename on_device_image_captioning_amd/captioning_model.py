@@ -100,6 +100,14 @@ class CaptioningModel(nn.Module):
                                          max_seq_len=max_seq_len, rows_per_image=rows_per_image, sos_idx=sos_idx,
                                          eos_idx=eos_idx, sampling=sampling)
 
+    def _search_prefix_arg(self, prefix, enc_input, *, sos_idx, eos_idx, max_seq_len, sampling=False):
+        """The `prefix` keyword of the search methods, checked on the host before any device work (search.check_prefix):
+        None for no prefix, else one id list per image."""
+        if prefix is None:
+            return None
+        return _search.check_prefix(prefix, len(enc_input), V=self._vocab_size, max_seq_len=max_seq_len, sos_idx=sos_idx,
+                                    eos_idx=eos_idx, sampling=sampling)
+
     def _next_sampling_seed(self) -> int:
         """A fresh Philox key per sampling call (so repeated calls differ), reproducible from `sampling_seed`."""
         self._sampling_calls += 1
@@ -371,11 +379,17 @@ class CaptioningModel(nn.Module):
 
     # ------------------------------------------------------------------ search
     def beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
-                    max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0, banned_words=None):
+                    max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0, banned_words=None,
+                    prefix=None):
         """The reference's beam search.  Keyword-only controls over what it may choose, applied on the
         device inside the step: `no_repeat_ngram_size` = n > 0: no caption holds an n-gram twice; `min_length`: at least
         that many words between SOS and EOS; `banned_words`: word ids that never appear.  With the defaults the search
-        launches exactly what it launches without them."""
+        launches exactly what it launches without them.
+        `prefix`: words every caption starts with — one list of word ids for all images, or one list per
+        image, all of one length P <= max_seq_len - 2.  The returned token lists are [sos, prefix…, continuation…] and the
+        log-probs include the prefix words' own, so a prefixed result agrees with score_captions like any other;
+        max_seq_len, min_length and the n-gram rule count the prefix words (a prefix may hold banned words).  One
+        whole-sequence decoder pass over the prefix replaces its P steps."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
@@ -383,14 +397,17 @@ class CaptioningModel(nn.Module):
                                             banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
                                             max_seq_len=max_seq_len, rows_per_image=beam_size,
                                             sampling=(sample_or_max == "sample"))
+        prefix = self._search_prefix_arg(prefix, enc_input, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
+                                         sampling=(sample_or_max == "sample"))
         mem = self.forward_enc(enc_input, enc_input_num_pads)
         toks, lp = self._search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
-                                            max_seq_len, sample=(sample_or_max == "sample"), constraints=cons)
+                                            max_seq_len, sample=(sample_or_max == "sample"), constraints=cons,
+                                            prefix=prefix)
         return toks, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
     def _search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
-                            max_seq_len, sample: bool = False, constraints: Optional[dict] = None
-                            ) -> Tuple[List[List[List[int]]], torch.Tensor]:
+                            max_seq_len, sample: bool = False, constraints: Optional[dict] = None,
+                            prefix: Optional[List[List[int]]] = None) -> Tuple[List[List[List[int]]], torch.Tensor]:
         eng = self._captioner_engine()
         B, S, _ = mem.shape
         k = beam_size
@@ -399,7 +416,11 @@ class CaptioningModel(nn.Module):
         enc_len = self._enc_lens(B, S, enc_input_num_pads)
         st = eng.new_state(B, k, T, eng.project_kv(mem), enc_len)
         # start state; for the deterministic search also the embedded start token as the input of position 0
-        ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None if sample else st.emb)
+        P = len(prefix[0]) if prefix else 0
+        if P:                                      # (check_prefix: never with `sample`)
+            eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx)
+        else:
+            ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None if sample else st.emb)
         V = eng.g.vocab_size
         seed = self._next_sampling_seed() if sample else 0
         cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
@@ -418,14 +439,14 @@ class CaptioningModel(nn.Module):
             if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
 
-        _search.run_steps(st, steps, draw_step if sample else step)
+        _search.run_steps(st, steps - P, draw_step if sample else step)
         order, _ = _search.rank_beams(st)
         # (the log-probs are on the engine's device; beam_search moves them to the input's)
         return _search.read_captions(st, order.cpu()[:, :how_many_outputs], how_many_outputs)
 
     def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
                             diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20, *, no_repeat_ngram_size=0,
-                            min_length=0, banned_words=None):
+                            min_length=0, banned_words=None, prefix=None):
         """Diverse (group) beam search (Vijayakumar et al.): `num_groups` groups of `group_size` beams per image.
         Within a step the groups choose one after the other, and a group pays `diversity_penalty` for every earlier
         group that appended the same word at this step (odic_group_beam_step).  The penalty only steers
@@ -435,7 +456,8 @@ class CaptioningModel(nn.Module):
         num_groups and may not exceed it.  Returns what beam_search returns: a token list per image and output, and
         the padded per-token log-probs [B, how_many_outputs, longest].
         `no_repeat_ngram_size`, `min_length`, `banned_words`: as in beam_search; every group's caption keeps them (the
-        words are removed before the ranking the penalty works on)."""
+        words are removed before the ranking the penalty works on).  `prefix`: as in beam_search; every group starts
+        behind it, and the groups part at the first free word as they part at the first word without it."""
         if how_many_outputs is None:
             how_many_outputs = num_groups
         if num_groups < 1 or group_size < 1 or num_groups * group_size > 16:
@@ -448,6 +470,7 @@ class CaptioningModel(nn.Module):
         constraints = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                                    banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
                                                    max_seq_len=max_seq_len, rows_per_image=num_groups * group_size)
+        prefix = self._search_prefix_arg(prefix, enc_input, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len)
         mem = self.forward_enc(enc_input, enc_input_num_pads)
         eng = self._captioner_engine()
         B, S, _ = mem.shape
@@ -458,7 +481,11 @@ class CaptioningModel(nn.Module):
         steps = max(1, max_seq_len - 1)
         T = steps + 1
         st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
-        ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
+        P = len(prefix[0]) if prefix else 0
+        if P:
+            eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx, group_beams=kg)
+        else:
+            ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
         cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
 
         def step(t):
@@ -466,7 +493,7 @@ class CaptioningModel(nn.Module):
             if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
 
-        _search.run_steps(st, steps, step)
+        _search.run_steps(st, steps - P, step)
         _, score = _search.rank_beams(st)
         best = score.view(B, G, kg).cpu().argmax(dim=2)           # (first maximum: ties go to the lower row)
         rows = torch.arange(G)[None, :] * kg + best               # output j of an image: the best row of group j

@@ -13,6 +13,7 @@
 //   cross_attn_probs_kernel  the softmax probabilities of the cross attention themselves (where the model looked for
 //                          each word): what cross_attn_step_kernel computes in LDS, uses for P·V and discards
 #include "odic_common.h"
+#include "dynexp_tiles.h"
 
 namespace {
 
@@ -96,50 +97,7 @@ __global__ __launch_bounds__(SEQ_NT) void dynexp_seq_kernel(DynSeqParams p) {
   if (L == 0) return;
 
   // ---- phase 1: rows a < L are cond_a, rows L..L+E-1 are qexp; columns are key_b
-  {
-    const int na = (L + E + 3) >> 2, nb = (L + 3) >> 2;
-    for (int it = tid; it < na * nb; it += SEQ_NT) {
-      const int a0 = (it / nb) * 4, b0 = (it % nb) * 4;
-      const float* ar[4]; const float* br[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int a = min(a0 + u, L + E - 1), b = min(b0 + u, L - 1);
-        ar[u] = a < L ? lin + (long)a * p.ldlin : p.qexp + (long)(a - L) * d;
-        br[u] = lin + (long)b * p.ldlin + d;
-      }
-      float acc[4][4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = 0.f;
-      for (int c = 0; c < d; c += 4) {
-        float4 av[4], bv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { av[u] = *(const float4*)(ar[u] + c); bv[u] = *(const float4*)(br[u] + c); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            float r = acc[u][v];
-            r = fmaf(av[u].x, bv[v].x, r); r = fmaf(av[u].y, bv[v].y, r);
-            r = fmaf(av[u].z, bv[v].z, r); r = fmaf(av[u].w, bv[v].w, r);
-            asm volatile("" : "+v"(r));     // scalar FMAs: hipcc's SLP pass pairs neighbouring accumulators into packed fp32
-                                            // ops with `op_sel` source selection otherwise (tests/test_isa_lint.py)
-            acc[u][v] = r;
-          }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int a = a0 + u, b = b0 + v;
-          if (a < L + E && b < L) {
-            if (a < L) CK[a * TS + b] = acc[u][v];
-            else QK[(a - L) * TS + b] = acc[u][v];
-          }
-        }
-    }
-  }
+  dynexp_qk_ck_tiles<SEQ_NT>(lin, p.ldlin, p.qexp, d, E, L, TS, QK, CK, tid);       // (dynexp_tiles.h)
   __syncthreads();
 
   // ---- normalisers.  forward: one thread per (e, j); backward: 16 lanes per t, fixed shuffle order

@@ -606,6 +606,33 @@ class CaptionerEngine:
                             penalty, emb=st.emb)
 
     # ------------------------------------------------------------------------------------------
+    # a search that starts behind a given prefix
+    def prefill(self, st: DecodeState, prefix: torch.Tensor, sos_idx: int, want_logits: bool = False):
+        """One whole-sequence pass over [sos, w_1 .. w_{P-1}] per image (n_img rows per position) that also fills the
+        step caches of `st` for positions 0..P-1, slot = the image's first row.  prefix int64 [n_img, P] on the device.
+        → the model's log-probs of the prefix words fp32 [n_img, P], or with want_logits the logits [n_img, P, V]."""
+        n_img, P = prefix.shape
+        if n_img != st.n_img or not 1 <= P <= st.T - 2:
+            raise ValueError(f"a prefix of {P} words for {n_img} images does not fit a state of {st.n_img} images and "
+                             f"{st.T} positions")
+        dec = torch.cat([torch.full((n_img, 1), int(sos_idx), dtype=torch.int64, device=self.device), prefix[:, :-1]], 1)
+        dec_len = torch.full((n_img,), P, dtype=torch.int32, device=self.device)
+        if want_logits:
+            return self.decode_sequence(dec, dec_len, st.kv, st.enc_len, n_img, want_logits=True, fill=(st, st.beams))
+        return self.decode_sequence(dec, dec_len, st.kv, st.enc_len, n_img, targets=prefix.contiguous(),
+                                    fill=(st, st.beams))["logp"]
+
+    def seed_prefix(self, st: DecodeState, prefix: torch.Tensor, sos_idx: int, group_beams: Optional[int] = None) -> None:
+        """Arm `st` for a search that continues `prefix` (int64 [n_img, P], the same P for every image): prefill, then
+        odic_beam_reset_prefix — every row holds [sos, prefix] with the prefix words' own log-probs, *pos = P, and only
+        the first row of every group of `group_beams` rows (default: all st.beams rows are one group) has a finite
+        cumulative score, so the next beam_step / group_beam_step seeds at position P as it seeds at position 0."""
+        prefix = prefix.to(self.device, torch.int64).contiguous()
+        logp = self.prefill(st, prefix, sos_idx)
+        ops.beam_reset_prefix(st.beam_state, prefix, logp.contiguous(), st.n_img, st.beams, group_beams or st.beams, st.T,
+                              sos_idx, emb=st.emb)
+
+    # ------------------------------------------------------------------------------------------
     # whole-sequence (teacher-forced) pass: every token is known, so the N·T rows go through each layer at once
     def vocab_row_chunk(self) -> int:
         """Rows per vocabulary product of decode_sequence: the logits workspace stays below 100 MB (2496 rows at
@@ -614,7 +641,7 @@ class CaptionerEngine:
 
     def decode_sequence(self, tokens: torch.Tensor, dec_len: torch.Tensor, kv: torch.Tensor, enc_len: torch.Tensor,
                         n_img: int, targets: Optional[torch.Tensor] = None, want_logits: bool = False,
-                        row_chunk: Optional[int] = None, attn: Optional[dict] = None):
+                        row_chunk: Optional[int] = None, attn: Optional[dict] = None, fill: Optional[tuple] = None):
         """Teacher-forced decoder over whole sequences (End_ExpansionNet_v2.py:103-138 in one pass).
         tokens int64 [N, T], rows image-major (N / n_img captions per image, sharing that image's K/V); dec_len int32 [N]
         real tokens per row; kv = project_kv(mem) [n_img, S, 2·N_dec·d]; enc_len int32 [n_img].
@@ -629,7 +656,11 @@ class CaptionerEngine:
         attention runs on; one more launch per listed layer): fp32 [N, T, S] with reduce_layers (the mean over the listed
         layers), [N, L', T, S] without, the mean over the heads either way; with per_head a heads axis in front of T.
         Padded rows hold the uniform 1/S of a masked row.  Without `attn` nothing is allocated or launched for it, and
-        every other result keeps its bits either way."""
+        every other result keeps its bits either way.
+        fill = (state, rows_per_image): every layer also writes the step caches of `state` (a DecodeState) for positions
+        0..T-1 of sequence i into slot i·rows_per_image, from the layer's `lin` rows (odic_dynexp_fill_caches; one more
+        launch per layer) — a search on `state` can then go on from position T (seed_prefix).  Without `fill` nothing is
+        allocated or launched for it, and every result keeps its bits either way."""
         g, dv = self.g, self.device
         d, L, V, E = g.d_model, g.N_dec, g.vocab_size, g.num_exp_dec
         N, T = tokens.shape
@@ -666,6 +697,9 @@ class CaptionerEngine:
             ops.layernorm(xin, w["n1w"], w["n1b"], M=M, C_=d, ldx=ld, out=xn)
             ops.gemm(xn, w["dyn_w"], w["dyn_b"], out=lin, tile_cfg=TC)                                   # [M,5d]
             ops.dynexp_seq(lin, 5 * d, w["qexp"], w["bexp"], dec_len, xin, ld, xo, ld, N, T, d, E)
+            if fill is not None:
+                ops.dynexp_fill_caches(lin, 5 * d, w["qexp"], fill[0].caches[i], N, T, int(fill[1]), fill[0].N, fill[0].T,
+                                       d, E)
             ops.layernorm(xo, w["n2w"], w["n2b"], M=M, C_=d, ldx=ld, out=xn)
             ops.gemm(xn, w["wq"], w["bq"], out=q, tile_cfg=TC)
             # the step kernel's row → image map is row / (rows / n_img): the sequence-major rows of an image are contiguous

@@ -92,9 +92,11 @@ class EsembleCaptioningModel(CaptioningModel):
 
     def ensemble_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                              max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0,
-                             banned_words=None) -> Tuple[List[List[List[int]]], torch.Tensor]:
+                             banned_words=None, prefix=None) -> Tuple[List[List[List[int]]], torch.Tensor]:
         """`no_repeat_ngram_size`, `min_length`, `banned_words`: as in CaptioningModel.beam_search; the constrained
-        selection (odic_topk_rows_constrained) then replaces odic_topk_rows on the averaged log-probs."""
+        selection (odic_topk_rows_constrained) then replaces odic_topk_rows on the averaged log-probs.
+        `prefix`: as in CaptioningModel.beam_search; every member fills its caches in one pass over the prefix and the
+        prefix words' log-probs are the averaged distribution's (search.ensemble_seed_prefix)."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
@@ -102,6 +104,8 @@ class EsembleCaptioningModel(CaptioningModel):
         constraints = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                                    banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
                                                    max_seq_len=max_seq_len, rows_per_image=beam_size, sampling=sample)
+        prefix = self._search_prefix_arg(prefix, enc_input, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
+                                         sampling=sample)
         # 'sample' (reference models/ensemble_captioning_model.py:123-130,174-183): the k candidates of every beam are drawn
         # without replacement from the averaged distribution — odic_logsoftmax_sample on rows that already are
         # log-probabilities (its normalisation is then the identity up to rounding), keyed by the lead member's seed
@@ -115,10 +119,14 @@ class EsembleCaptioningModel(CaptioningModel):
         states = [eng.new_state(B, k, T, eng.project_kv(mem), m._enc_lens(B, S, enc_input_num_pads))
                   for m, eng, mem in zip(self.models_list, engs, mems)]
         lead = _search.share_beam_state(states)
-        ops.beam_reset(lead.beam_state, B, k, T, sos_idx, emb=None)      # (the members embed for themselves in step_logits)
+        P = len(prefix[0]) if prefix else 0
+        if P:
+            _search.ensemble_seed_prefix(engs, states, _search.prefix_tensor(prefix, engs[0].device), sos_idx)
+        else:
+            ops.beam_reset(lead.beam_state, B, k, T, sos_idx, emb=None)  # (the members embed for themselves in step_logits)
         avg = torch.empty(lead.N, engs[0].g.vocab_size, dtype=torch.float32, device=engs[0].device)
         cons = engs[0].search_constraints(lead, eos_idx, **constraints) if constraints else None
-        _search.run_steps(lead, steps, lambda t: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed,
+        _search.run_steps(lead, steps - P, lambda t: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed,
                                                                        constraints=cons))
         order, _ = _search.rank_beams(lead)
         # (the log-probs stay on the engine's device, unlike beam_search's, which go to the input's)

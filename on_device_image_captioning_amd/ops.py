@@ -625,6 +625,19 @@ def dynexp_seq(lin, ldlin, qexp, bexp, dec_len, y_in, ldy_in, y, ldy, N, T, d, E
                                                _p(y), ldy, N, T, d, E, eps, _stream()), "odic_dynexp_seq")
 
 
+def dynexp_fill_caches(lin, ldlin, qexp, cache: dict, n_seq, P, rows_per_image, N_cache, T_cache, d, E, eps=1e-9) -> None:
+    """The step caches `cache` (one layer's dict of a DecodeState: cond, key, va, vb, wfa, wfb, qk) for positions 0..P-1 of
+    n_seq sequences, slot i·rows_per_image, from the lin rows of the whole-sequence pass (odic_dynexp_fill_caches)."""
+    c = cache
+    _need_cuda(lin, qexp, *(c[k] for k in ("cond", "key", "va", "vb", "wfa", "wfb", "qk")))
+    # lin rows in; the four row caches, qk and the P(P+1)/2·E forward weights (x2) out;  (P+E)·P dot products of length d
+    with _timed("dynexp_fill", n_seq * 2.0 * (P + E) * P * d, n_seq * (P * 9.0 * d + P * E + P * (P + 1.0) * E) * 4.0):
+        _hip.check(_hip.load().odic_dynexp_fill_caches(_p(lin), ldlin, _p(qexp), _p(c["cond"]), _p(c["key"]), _p(c["va"]),
+                                                       _p(c["vb"]), _p(c["wfa"]), _p(c["wfb"]), _p(c["qk"]), n_seq, P,
+                                                       rows_per_image, N_cache, T_cache, d, E, eps, _stream()),
+                   "odic_dynexp_fill_caches")
+
+
 def token_stats(logits, ldl, target, logp_target, sum_logp, argmax, max_logp, status, R, V) -> None:
     """Per logits row: log-prob of the target, Σ_v log-prob, arg-max (ties → lower index) and its log-prob."""
     _need_cuda(logits, target, logp_target, sum_logp, argmax, max_logp, status)
@@ -770,6 +783,20 @@ def beam_reset(state: "_hip.BeamState", n_img, beams, T, sos_idx, emb=None) -> N
     with _timed("beam_reset", 0.0, n_img * beams * (28.0 + (emb.d * 4.0 if emb is not None else 0.0))):
         _hip.check(_hip.load().odic_beam_reset(C.byref(state), _emb_ref(emb), n_img, beams, T, sos_idx, _stream()),
                    "odic_beam_reset")
+
+
+def beam_reset_prefix(state: "_hip.BeamState", prefix, prefix_logp, n_img, beams, group_beams, T, sos_idx, emb=None) -> None:
+    """The beam state behind a prefix (odic_beam_reset_prefix): prefix int64 [n_img, P], prefix_logp fp32 [n_img, P]."""
+    _need_cuda(prefix, prefix_logp)
+    if prefix.dtype != torch.int64 or prefix_logp.dtype != torch.float32 or prefix.dim() != 2 or \
+            tuple(prefix.shape) != tuple(prefix_logp.shape) or prefix.shape[0] != n_img or \
+            not prefix.is_contiguous() or not prefix_logp.is_contiguous():
+        raise ValueError("beam_reset_prefix: prefix int64 and prefix_logp fp32, both contiguous [n_img, P]")
+    P = prefix.shape[1]
+    with _timed("beam_reset", 0.0, n_img * (P * 12.0 + beams * ((P + 1) * 16.0 + 28.0 + (emb.d * 4.0 if emb is not None else 0.0)))):
+        _hip.check(_hip.load().odic_beam_reset_prefix(C.byref(state), _emb_ref(emb), _p(prefix), _p(prefix_logp), n_img,
+                                                      beams, group_beams, T, P, sos_idx, _stream()),
+                   "odic_beam_reset_prefix")
 
 
 def quantize_fp8_per_channel(w: torch.Tensor):

@@ -48,19 +48,61 @@ def check_constraints(n: int, m: int, banned, *, V, max_seq_len: int, rows_per_i
     return dict(no_repeat_ngram=n, min_words=m, banned=banned)
 
 
+def check_prefix(prefix, n_img: int, *, V, max_seq_len: int, sos_idx, eos_idx, sampling: bool = False
+                 ) -> Optional[List[List[int]]]:
+    """The rules of a search that starts behind given words.  `prefix`: one sequence of word ids used
+    for every image, or one sequence per image, all of the same length.  None for no prefix (None, or nothing but empty
+    sequences: the search then launches exactly what it launches without the keyword), else the n_img id lists;
+    ValueError, before any device work, for what cannot work."""
+    if prefix is None:
+        return None
+    if isinstance(prefix, torch.Tensor):
+        prefix = prefix.tolist()
+    prefix = list(prefix)
+    nested = bool(prefix) and all(isinstance(p, (list, tuple, torch.Tensor)) for p in prefix)
+    if nested:
+        rows = [[int(w) for w in (p.tolist() if isinstance(p, torch.Tensor) else p)] for p in prefix]
+        if len(rows) != n_img:
+            raise ValueError(f"{len(rows)} prefixes for {n_img} images: give one for all, or one per image")
+    else:
+        rows = [[int(w) for w in prefix]] * n_img
+    P = len(rows[0]) if rows else 0
+    if any(len(r) != P for r in rows):
+        raise ValueError("the prefixes of a batch must have one length (the position is one device scalar)")
+    if P == 0:
+        return None
+    if sampling:
+        raise ValueError("prefix applies to the deterministic searches only: drawing behind a prefix "
+                         "(sample_or_max='sample', mode='sampling') is not supported")
+    if P > max_seq_len - 2:
+        raise ValueError(f"a prefix of {P} words > max_seq_len - 2 = {max_seq_len - 2}: the caption could not go on and end")
+    V = V() if callable(V) else V
+    for r in rows:
+        for w in r:
+            if not 0 <= w < V:
+                raise ValueError(f"prefix word id {w} lies outside the vocabulary [0, {V})")
+            if w == sos_idx or w == eos_idx:
+                raise ValueError("the SOS and EOS ids cannot be part of a prefix")
+    return [list(r) for r in rows]
+
+
 def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
     """mode='beam_search' | 'sampling' | 'diverse_beam_search' with the keys of `args` (a forward(**kwargs) or
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
     sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
+    pre = {"prefix": args["prefix"]} if "prefix" in args else {}        # (absent = the default, as the constraints)
     if mode == "beam_search":
         return model.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
                                  beam_size=args.get("beam_size", 5), how_many_outputs=args.get("how_many_outputs", 1),
                                  max_seq_len=args.get("beam_max_seq_len", 20),
-                                 sample_or_max=args.get("sample_or_max", "max"), **cons)
+                                 sample_or_max=args.get("sample_or_max", "max"), **pre, **cons)
     if mode == "sampling":
         max_seq_len = args.get("sample_max_seq_len", 20)
         model._search_constraint_args(**cons, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len, rows_per_image=1,
                                       sampling=True)
+        if pre.get("prefix") is not None:
+            model._search_prefix_arg(pre["prefix"], enc_x, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
+                                     sampling=True)
         return model.get_batch_multiple_sampled_prediction(
             enc_x, enc_x_num_pads, num_outputs=args.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
             max_seq_len=max_seq_len)
@@ -69,7 +111,7 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
                                          num_groups=args.get("num_groups", 3), group_size=args.get("group_size", 3),
                                          diversity_penalty=args.get("diversity_penalty", 0.5),
                                          how_many_outputs=args.get("how_many_outputs", None),
-                                         max_seq_len=args.get("beam_max_seq_len", 20), **cons)
+                                         max_seq_len=args.get("beam_max_seq_len", 20), **pre, **cons)
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -117,6 +159,31 @@ def share_beam_state(states):
     for st in states[1:]:
         st.anc, st.row_valid, st.next_tok, st.pos = lead.anc, lead.row_valid, lead.next_tok, lead.pos
     return lead
+
+
+def prefix_tensor(prefix: List[List[int]], device) -> torch.Tensor:
+    """check_prefix's id lists → int64 [n_img, P] on the device."""
+    return torch.tensor(prefix, dtype=torch.int64, device=device)
+
+
+def ensemble_seed_prefix(engines, states, prefix: torch.Tensor, sos_idx: int) -> None:
+    """seed_prefix for an ensemble on share_beam_state(states): every member fills its own caches in a whole-sequence pass
+    over the prefix; the prefix words' log-probs are those of the averaged distribution (odic_ensemble_logprobs on the
+    members' logits rows, read by odic_token_stats as the ensemble's score_captions reads them); one
+    odic_beam_reset_prefix on the shared lead state (the members embed for themselves in step_logits)."""
+    lead = states[0]
+    n_img, P = prefix.shape
+    V = engines[0].g.vocab_size
+    dv = prefix.device
+    lg = [eng.prefill(st, prefix, sos_idx, want_logits=True).view(-1, V) for eng, st in zip(engines, states)]
+    avg = torch.empty(n_img * P, V, dtype=torch.float32, device=dv)
+    ops.ensemble_logprobs(lg, avg)
+    logp, sum_logp, max_logp = (torch.empty(n_img * P, dtype=torch.float32, device=dv) for _ in range(3))
+    argmax = torch.empty(n_img * P, dtype=torch.int32, device=dv)
+    status = torch.zeros(1, dtype=torch.int32, device=dv)
+    ops.token_stats(avg, V, prefix.contiguous().view(-1), logp, sum_logp, argmax, max_logp, status, n_img * P, V)
+    ops.beam_reset_prefix(lead.beam_state, prefix.contiguous(), logp.view(n_img, P), lead.n_img, lead.beams, lead.beams,
+                          lead.T, sos_idx, emb=None)
 
 
 def ensemble_step(engines, states, avg: torch.Tensor, eos_idx: int, *, sample_seed: Optional[int] = None,

@@ -4,11 +4,14 @@ FULL geometry, features-only model, 16 images, fp32, HIP events around the step 
 poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
 it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
 
-    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 pbeam:3:6
 
 cbeam:K is beam:K under constraints: no_repeat_ngram_size=2, min_length=5 and 8 banned words; the step then
 holds one launch more (odic_topk_rows_constrained) and the top-k launch writes the log-prob rows.
-A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26) is reported as absent.
+pbeam:K:P is beam:K behind a prefix of P words: one whole-sequence pass over the prefix that fills the step
+caches (CaptionerEngine.seed_prefix) and max_len - 1 - P steps; compare its time per SEARCH with beam:K's.
+A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix) is
+reported as absent.
 """
 import argparse
 import os
@@ -43,7 +46,14 @@ def main():
     enc_len = model._enc_lens(a.images, mem.shape[1], [0] * a.images)
     steps, T = a.max_len - 1, a.max_len
     for form in a.forms:
-        kind, shape = form.split(":")
+        kind, shape = form.split(":", 1)
+        P = 0
+        if kind == "pbeam":
+            shape, P = shape.split(":")
+            P = int(P)
+            if not hasattr(eng, "seed_prefix"):
+                print(f"{form}: not in this build")
+                continue
         if kind == "diverse":
             G, kg = (int(v) for v in shape.split("x"))
             if not hasattr(eng, "group_beam_step"):
@@ -62,9 +72,14 @@ def main():
             cons = eng.search_constraints(st, bench.EOS, no_repeat_ngram=2, min_words=5,
                                           banned=[w for w in range(100, 110) if w not in (bench.SOS, bench.EOS)][:8])
             one = lambda st: eng.beam_step(st, bench.EOS, constraints=cons)        # noqa: E731
+        prefix = torch.arange(200, 200 + P, device=dev).repeat(a.images, 1) if P else None
+
         def search():
-            ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=st.emb)
-            for _ in range(steps):
+            if P:
+                eng.seed_prefix(st, prefix, bench.SOS)
+            else:
+                ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=st.emb)
+            for _ in range(steps - P):
                 one(st)
 
         graph = None
@@ -85,8 +100,9 @@ def main():
             torch.cuda.synchronize()
             if run >= 2:
                 times.append(e0.elapsed_time(e1) * 1000.0 / steps)
-        print(f"{form} ({'eager' if a.eager else 'graph'}): rows/image {R}, {steps} steps, per step median {statistics.median(times):.1f} us, "
-              f"min {min(times):.1f}, max {max(times):.1f} ({a.runs} runs)", flush=True)
+        print(f"{form} ({'eager' if a.eager else 'graph'}): rows/image {R}, {steps - P} steps, per step median {statistics.median(times):.1f} us, "
+              f"min {min(times):.1f}, max {max(times):.1f} ({a.runs} runs); per search median "
+              f"{statistics.median(times) * steps:.0f} us", flush=True)
 
 
 if __name__ == "__main__":
