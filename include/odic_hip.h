@@ -167,8 +167,9 @@ int odic_patch_merge_layernorm(const float* x, const float* gamma, const float* 
 
 /* PatchEmbed: Conv2d(in_chans→C, k=s=patch) + flatten + LayerNorm(C)
  * (swin_transformer_mod.py:511-519).  img fp32 [B,in_chans,H,W]; w fp32 [C,in_chans*patch*patch];
- * out fp32 [B,(H/patch)*(W/patch),C].  patch == 4, C in {64,96,128,192,256}, in_chans*16 <= 64.  `out` is compact: exactly
- * that many elements are written (test_patch_embed_compact_output). */
+ * out fp32 [B,(H/patch)*(W/patch),C].  patch == 4, C in {64,96,128,192,256}, in_chans*16 <= 64; H and W any multiples of patch
+ * (images of fewer than 64 tokens included: test_patch_embed_shapes); anything else is refused and nothing is written.  `out`
+ * is compact: exactly that many elements are written (test_patch_embed_compact_output). */
 int odic_patch_embed(const float* img, const float* w, const float* b, const float* gamma,
                      const float* beta, float* out, int32_t B, int32_t in_chans, int32_t H,
                      int32_t W, int32_t patch, int32_t C, float eps, void* stream);

@@ -167,8 +167,8 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
     const int t = i & 63, sgm = i >> 6;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (t < nvalid) {
-      int r = r0 + t, b = b0;
-      if (r >= per_img) { r -= per_img; ++b; }           // a 64-token block spans at most two images
+      const int over = (r0 + t) / per_img;               // a 64-token block spans 64 images when an image is one token
+      const int r = r0 + t - over * per_img, b = b0 + over;
       const int ph = r / gw, pw = r - ph * gw;
       const int c = sgm / patch, kh = sgm - c * patch;
       v = *(const float4*)(img + (((long)b * in_chans + c) * H + ph * patch + kh) * W + pw * patch);
