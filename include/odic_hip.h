@@ -55,7 +55,9 @@ extern "C" {
  *   21: odic_jpeg_decode_scaled and odic_jpeg_decode_progressive_scaled added (decode at 1/2, 1/4, 1/8 scale).
  *   22: odic_resize_boxes_normalize added (batched box resize, PIL's resize(..., box=)).
  *   25: odic_group_beam_step added (diverse beam search: groups with a Hamming penalty).
- *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search). */
+ *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
+ *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
+ *       odic_beam_reset_prefix, odic_require_beam_step. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -734,6 +736,44 @@ int odic_group_beam_step(const float* cand_val, const int32_t* cand_idx, int32_t
                          const odic_beam_state* st, const odic_embed_args* emb,
                          int32_t n_img, int32_t groups, int32_t group_beams, int32_t T,
                          int64_t eos_idx, float penalty, void* stream);
+
+/* The step of a beam search whose captions must CONTAIN given words (Anderson et al., "Guided Open Vocabulary Image
+ * Captioning with Constrained Beam Search"), the sibling of odic_beam_step on the same state.  An addition
+ * to ABI 26.
+ *   required int64 [n_img, n_required], device resident: the word ids image b must mention, -1 in unused slots (an id
+ *   outside [0, V) counts as -1; the ids of an image are distinct: the caller checks).  C = n_required <= 4.
+ *   The R = 2^C·bank_beams rows of an image are 2^C banks of bank_beams rows, bank m (a bit mask over the C slots) being
+ *   rows m·bank_beams .. (m+1)·bank_beams - 1.  A row lives in bank m when its caption holds exactly the required words
+ *   whose bits are set in m; the accepting bank of an image is the mask of its used slots.
+ *   cand_val / cand_idx [n_img·R, ncand] as for odic_group_beam_step (ncand must equal R); logp fp32 [n_img·R, V] (ldl):
+ *   the log-prob rows the candidates were taken from (logp_out of odic_logsoftmax_topk); columns [V, ldl) are not read.
+ * At *pos = t the live rows are those with cumul > -inf.  Target bank m keeps the bank_beams best of
+ *   stay:  from every live row j of bank m — a finished row (has_eos) its rank-0 candidate at 0 and nothing else; a
+ *          growing row each of its ncand candidates whose word is neither a required word of the image whose bit is
+ *          clear in m, nor EOS unless m is the accepting bank;
+ *   enter: for every slot c set in m with required[b][c] >= 0 and every live, growing row j of bank m ^ (1 << c): the
+ *          word required[b][c] at v = logp[row j][required[b][c]] (it need not be among the row's candidates);
+ * total = cumul_j + v (one rounded fp32 addition); at t = 0 only row 0 of the image offers anything, and total = v.
+ * Order: total descending, then source row (within the image) ascending, then word ascending.  A (row, word) pair leads to
+ * exactly one bank.  A bank with fewer than bank_beams finite totals fills its remaining slots as EMPTY rows: parent =
+ * the slot's own row (row 0 at t = 0), word = EOS, stored log-prob -inf — after the update such a row has cumul = -inf and
+ * has_eos = 1, never offers anything again, and odic_beam_finalize scores it -inf.  Banks that carry the bit of an unused
+ * slot stay empty.  A caption cannot take EOS before it holds every required word.
+ * Everything after the choice (permutation of prefixes / log-probs / ancestors, embedding tail, n_elem, has_eos,
+ * row_valid, next_tok, *pos, *done, the arrival counter) is odic_beam_step's: logprobs[.., pos+1] is the word's own
+ * log-prob and cumul the re-summed prefix.  With n_required = 0 (logp and required may be NULL) the call leaves the state
+ * bitwise as odic_beam_step with beams = bank_beams does, as long as every image has bank_beams finite totals (where
+ * odic_beam_step would take a finished row's -999 fillers, this step writes empty rows).
+ * A row loses at most C + 1 of its R candidates (the unmet required words and EOS) and must still offer bank_beams.
+ *   ODIC_EINVAL, before any launch and with nothing written: n_required outside [0, 4], bank_beams < 1, R > 16,
+ *   ncand != R, R < bank_beams + n_required + 1 with n_required > 0 (only C = 1 with one beam), ldl < V, V < 1, eos_idx
+ *   outside [0, V) (it is the word of an empty row), logp or required NULL with n_required > 0, T / n_img outside
+ *   odic_beam_step's limits.  All stores stay inside the compact state arrays and columns [0, d) of the R·n_img rows of
+ *   emb->y (tests/test_require_beam_step_gpu.py). */
+int odic_require_beam_step(const float* cand_val, const int32_t* cand_idx, int32_t ncand,
+                           const float* logp, int64_t ldl, const int64_t* required, int32_t n_required,
+                           const odic_beam_state* st, const odic_embed_args* emb,
+                           int32_t n_img, int32_t bank_beams, int32_t T, int64_t eos_idx, int32_t V, void* stream);
 
 /* Initial state of a search (captioning_model.py:117-125): tokens[:, :, 0] = sos, logprobs[:, :, 0] = 0,
  * next_tok = sos, row_valid = 1, *pos = *done = *ctr = 0; with emb, also the input of position 0 (the embedded

@@ -119,6 +119,8 @@ _SIGNATURES = {
     "odic_beam_step": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),
     "odic_group_beam_step": (C.c_int, [_P, _P, _I32, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I32, _I64,
                                        _F, _P]),
+    "odic_require_beam_step": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I32, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32,
+                                         _I32, _I32, _I64, _I32, _P]),
     "odic_beam_finalize": (C.c_int, [C.POINTER(BeamState), _P, _P, _I32, _I32, _P]),
     "odic_beam_finalize_best": (C.c_int, [C.POINTER(BeamState), _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "odic_beam_reset": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),

@@ -43,6 +43,7 @@ class CaptioningModel(nn.Module):
         self._sampling_calls = 0
         self._draw_log = None               # list → every sampled-beam-search draw is appended (tests)
         self._cand_log = None               # list → every deterministic search step's (cand_val, cand_idx) is appended (tests)
+        self.last_required_satisfied = None  # after a beam_search with required_words: per image, does output 0 hold them all
 
     # ------------------------------------------------------------------ engine cache plumbing
     def check_required_attributes(self):
@@ -107,6 +108,16 @@ class CaptioningModel(nn.Module):
             return None
         return _search.check_prefix(prefix, len(enc_input), V=self._vocab_size, max_seq_len=max_seq_len, sos_idx=sos_idx,
                                     eos_idx=eos_idx, sampling=sampling)
+
+    def _search_required_arg(self, required_words, enc_input, *, beam_size, banned_words, sos_idx, eos_idx, max_seq_len,
+                             sampling=False):
+        """The `required_words` keyword of beam_search, checked on the host before any device work
+        (search.check_required_words): None for nothing required, else one padded id list per image."""
+        if required_words is None:
+            return None
+        return _search.check_required_words(required_words, len(enc_input), V=self._vocab_size, beam_size=beam_size,
+                                            banned=banned_words, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
+                                            sampling=sampling)
 
     def _next_sampling_seed(self) -> int:
         """A fresh Philox key per sampling call (so repeated calls differ), reproducible from `sampling_seed`."""
@@ -380,7 +391,7 @@ class CaptioningModel(nn.Module):
     # ------------------------------------------------------------------ search
     def beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                     max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0, banned_words=None,
-                    prefix=None):
+                    prefix=None, required_words=None):
         """The reference's beam search.  Keyword-only controls over what it may choose, applied on the
         device inside the step: `no_repeat_ngram_size` = n > 0: no caption holds an n-gram twice; `min_length`: at least
         that many words between SOS and EOS; `banned_words`: word ids that never appear.  With the defaults the search
@@ -389,21 +400,65 @@ class CaptioningModel(nn.Module):
         image, all of one length P <= max_seq_len - 2.  The returned token lists are [sos, prefix…, continuation…] and the
         log-probs include the prefix words' own, so a prefixed result agrees with score_captions like any other;
         max_seq_len, min_length and the n-gram rule count the prefix words (a prefix may hold banned words).  One
-        whole-sequence decoder pass over the prefix replaces its P steps."""
+        whole-sequence decoder pass over the prefix replaces its P steps.
+        `required_words`: word ids every caption must contain — one list for all images, or one list per
+        image (ragged lists allowed), C <= 4 words at most.  The search then keeps `beam_size` beams PER BANK, a bank for
+        every subset of the C words (2^C·beam_size <= 16 rows per image), and a caption may take EOS only once it holds all
+        its words (odic_require_beam_step).  Output j of an image is the j-th best caption that holds them all;
+        `self.last_required_satisfied` says per image whether there was one (else the outputs are the best captions the
+        search still had).  Composes with the three controls above; not with `prefix` or sample_or_max='sample'.  None, [] or
+        nothing but empty lists: exactly the search without the keyword."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
+        sampling = sample_or_max == "sample"
+        self.last_required_satisfied = None
+        required = self._search_required_arg(required_words, enc_input, beam_size=beam_size, banned_words=banned_words,
+                                             sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len, sampling=sampling)
+        rows_per_image = beam_size << len(required[0]) if required else beam_size
         cons = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                             banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
-                                            max_seq_len=max_seq_len, rows_per_image=beam_size,
-                                            sampling=(sample_or_max == "sample"))
+                                            max_seq_len=max_seq_len, rows_per_image=rows_per_image, sampling=sampling)
         prefix = self._search_prefix_arg(prefix, enc_input, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
-                                         sampling=(sample_or_max == "sample"))
+                                         sampling=sampling)
+        if required and prefix:
+            raise ValueError("required_words together with prefix is not supported")
+        if required and rows_per_image > self._vocab_size():
+            raise ValueError(f"{rows_per_image} rows per image exceed the vocabulary ({self._vocab_size()} words)")
         mem = self.forward_enc(enc_input, enc_input_num_pads)
-        toks, lp = self._search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
-                                            max_seq_len, sample=(sample_or_max == "sample"), constraints=cons,
-                                            prefix=prefix)
+        if required:
+            toks, lp = self._required_search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size,
+                                                         how_many_outputs, max_seq_len, required, cons)
+        else:
+            toks, lp = self._search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
+                                                max_seq_len, sample=sampling, constraints=cons, prefix=prefix)
         return toks, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+
+    def _required_search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, bank_beams, how_many_outputs,
+                                     max_seq_len, required: List[List[int]], constraints: Optional[dict]):
+        """beam_search with required words (check_required_words' lists): 2^C banks of bank_beams rows per image."""
+        eng = self._captioner_engine()
+        B, S, _ = mem.shape
+        R = bank_beams << len(required[0])
+        steps = max(1, max_seq_len - 1)
+        T = steps + 1
+        st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
+        ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
+        req = torch.tensor(required, dtype=torch.int64, device=eng.device)
+        cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
+
+        def step(t):
+            eng.require_beam_step(st, eos_idx, req, bank_beams, constraints=cons)
+            if self._cand_log is not None:       # test hook: the candidates and the required words' log-probs per row
+                logp_h, req_h = st.logp.cpu(), req.cpu().repeat_interleave(R, dim=0)
+                req_logp = torch.where(req_h >= 0, logp_h.gather(1, req_h.clamp(min=0)), torch.tensor(float("-inf")))
+                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone(), req_logp))
+
+        _search.run_steps(st, steps, step)
+        order, _ = _search.rank_beams(st)
+        rows, self.last_required_satisfied = _search.required_outputs(order.cpu().tolist(), st.cumul.view(B, R).cpu().tolist(),
+                                                                      required, bank_beams, how_many_outputs)
+        return _search.read_captions(st, rows, how_many_outputs)
 
     def _search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
                             max_seq_len, sample: bool = False, constraints: Optional[dict] = None,
@@ -446,7 +501,7 @@ class CaptioningModel(nn.Module):
 
     def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
                             diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20, *, no_repeat_ngram_size=0,
-                            min_length=0, banned_words=None, prefix=None):
+                            min_length=0, banned_words=None, prefix=None, required_words=None):
         """Diverse (group) beam search (Vijayakumar et al.): `num_groups` groups of `group_size` beams per image.
         Within a step the groups choose one after the other, and a group pays `diversity_penalty` for every earlier
         group that appended the same word at this step (odic_group_beam_step).  The penalty only steers
@@ -457,9 +512,11 @@ class CaptioningModel(nn.Module):
         the padded per-token log-probs [B, how_many_outputs, longest].
         `no_repeat_ngram_size`, `min_length`, `banned_words`: as in beam_search; every group's caption keeps them (the
         words are removed before the ranking the penalty works on).  `prefix`: as in beam_search; every group starts
-        behind it, and the groups part at the first free word as they part at the first word without it."""
+        behind it, and the groups part at the first free word as they part at the first word without it.
+        `required_words`: beam_search's; anything but nothing required is refused here."""
         if how_many_outputs is None:
             how_many_outputs = num_groups
+        _search.refuse_required_words(required_words, "in diverse_beam_search")
         if num_groups < 1 or group_size < 1 or num_groups * group_size > 16:
             raise ValueError("diverse_beam_search needs num_groups >= 1, group_size >= 1 and num_groups·group_size <= 16")
         if not 1 <= how_many_outputs <= num_groups:

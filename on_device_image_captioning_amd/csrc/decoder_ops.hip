@@ -12,6 +12,7 @@
 //   logsoftmax_topk_kernel   log_softmax over the vocabulary + top-k (captioning_model.py:162-170)
 //   beam_step_kernel         candidate masking, k·k selection, prefix/ancestor re-gather (:172-223)
 //   group_beam_step_kernel   the same step for diverse (group) beam search: groups choose in turn, Hamming penalty
+//   require_beam_step_kernel the same step for required words: 2^C banks of beams, one per set of words mentioned so far
 //   beam_finalize_kernel     length-normalised ranking (:225-227)
 #include "odic_common.h"
 
@@ -932,6 +933,118 @@ __global__ __launch_bounds__(256) void group_beam_step_kernel(BeamParams p, Embe
   beam_apply(p, e, s, b, t);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Required words (lexically constrained beam search): an image has C <= 4 required word ids (-1 = unused
+// slot), and its R = 2^C·kb rows are 2^C banks of kb rows, bank m (a bit mask over the slots) being rows m·kb .. m·kb+kb-1:
+// a row lives in bank m when its caption holds exactly the required words whose bits are set in m.  Wave 0 walks the
+// target banks in order.  Bank m ranks kb·(R + C) candidates, four per lane at most:
+//   stay   row j of bank m x its R best words, without the required words whose bit is clear in m (they lead elsewhere)
+//          and without EOS unless m is the accepting bank (every used slot set); a finished row keeps the rule of
+//          beam_select's rank 0 (worth 0) and offers nothing else;
+//   enter  for every slot c set in m, row j of bank m ^ (1 << c) x the word required[c], at the value gathered from the
+//          row's log-probs (rlp) — the word need not be among the row's R best.
+// Only rows with cumul > -inf offer anything (t = 0: row 0 alone, total = v).  Order: total descending, then source row
+// ascending, then word ascending; (row, word) is unique within a target bank, so the key decides every tie.  A slot for
+// which no finite total is left becomes an EMPTY row: parent = the slot itself (row 0 at t = 0), word = EOS, stored
+// log-prob -inf — beam_apply then leaves it with cumul = -inf and has_eos = 1, and it never offers anything again.
+// The banks read only the state of before the step, so nothing is handed from one bank to the next (no fence as between
+// the groups of group_beam_select).  total is one __fadd_rn, as in the group kernel.
+// ---------------------------------------------------------------------------------------------
+constexpr int MAX_REQ = 4;
+struct RequireArgs { const float* logp; long ldl; const long long* required; int C, kb, V; };
+
+__device__ __forceinline__ void require_beam_select(const BeamParams& p, BeamShared& s, const int* req,
+                                                    const float (*rlp)[MAX_REQ], int t, int C, int kb) {
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x, R = p.k, eos = (int)p.eos;
+  constexpr int CPL = MAX_K * MAX_K / 64;              // candidates per lane (kb·(R + C) <= 256)
+  constexpr long long NO_KEY = 0x7fffffffffffffffLL;
+  int accept = 0;
+  for (int c = 0; c < C; ++c) accept |= req[c] >= 0 ? 1 << c : 0;
+  const int n_stay = kb * R, nc = n_stay + C * kb;
+  for (int m = 0; m < (1 << C); ++m) {
+    float tot[CPL], val[CPL]; long long key[CPL];      // key: (source row, word); lower wins a tie on the total
+#pragma unroll
+    for (int u = 0; u < CPL; ++u) {
+      const int i = lane + 64 * u;
+      tot[u] = -INFINITY; val[u] = 0.f; key[u] = NO_KEY;
+      if (i < nc) {
+        int row, w; bool ok; float v = 0.f;
+        if (i < n_stay) {
+          const int j = i / R, c = i - j * R;
+          row = m * kb + j;
+          w = s.ci[row * R + c];
+          if (t > 0 && s.eos[row]) {
+            ok = c == 0;
+          } else {
+            v = s.cv[row * R + c];
+            ok = !(w == eos && m != accept);
+            for (int q = 0; q < C; ++q) ok = ok && !(w == req[q] && !((m >> q) & 1));
+          }
+        } else {
+          const int en = i - n_stay, q = en / kb, j = en - q * kb;
+          row = (m ^ (1 << q)) * kb + j;                 // (< R whatever the bit)
+          w = req[q];
+          ok = ((m >> q) & 1) && w >= 0 && !(t > 0 && s.eos[row]);
+          if (ok) v = rlp[row][q];
+        }
+        ok = ok && (t == 0 ? row == 0 : s.cu[row] > -INFINITY);
+        if (ok) {
+          tot[u] = t == 0 ? v : __fadd_rn(s.cu[row], v);
+          val[u] = v;
+          key[u] = ((long long)row << 32) | (long long)(unsigned)w;
+        }
+      }
+    }
+    for (int r = 0; r < kb; ++r) {
+      float best = tot[0], bval = val[0]; long long bk = key[0];
+#pragma unroll
+      for (int u = 1; u < CPL; ++u)
+        if (tot[u] > best || (tot[u] == best && key[u] < bk)) { best = tot[u]; bval = val[u]; bk = key[u]; }
+      if (!(best > -INFINITY)) bk = NO_KEY;              // nothing left in this lane
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64), ol = __shfl_xor(bval, o, 64);
+        const long long ok = __shfl_xor(bk, o, 64);
+        if (ov > best || (ov == best && ok < bk)) { best = ov; bval = ol; bk = ok; }
+      }
+      const bool found = best > -INFINITY;
+#pragma unroll
+      for (int u = 0; u < CPL; ++u)
+        if (found && key[u] == bk) { tot[u] = -INFINITY; key[u] = NO_KEY; }
+      if (lane == 0) {
+        const int slot = m * kb + r;
+        s.parent[slot] = found ? (int)(bk >> 32) : (t == 0 ? 0 : slot);
+        s.word[slot] = found ? (int)(bk & 0xffffffffLL) : eos;
+        s.lp[slot] = found ? bval : -INFINITY;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void require_beam_step_kernel(BeamParams p, EmbedArgs e, RequireArgs a) {
+  __shared__ BeamShared s;
+  __shared__ int req[MAX_REQ];          // the image's required ids; -1: unused slot, or an id outside the vocabulary
+  __shared__ float rlp[MAX_K][MAX_REQ]; // log-prob of required word c in row r
+  const int b = blockIdx.x, R = p.k, C = a.C;
+  const int t = *p.pos;
+  if (t + 1 >= p.T) return;
+  for (int i = threadIdx.x; i < R * R; i += 256) {
+    s.cv[i] = p.cand_val[(long)b * R * R + i];
+    s.ci[i] = p.cand_idx[(long)b * R * R + i];
+  }
+  for (int i = threadIdx.x; i < R * C; i += 256) {
+    const int row = i / C, c = i - row * C;
+    const long long w = a.required[(long)b * C + c];
+    const bool used = w >= 0 && w < a.V;
+    if (row == 0) req[c] = used ? (int)w : -1;
+    rlp[row][c] = used ? a.logp[((long)b * R + row) * a.ldl + w] : -INFINITY;
+  }
+  beam_load_rows(p, s, b, t);
+  require_beam_select(p, s, req, rlp, t, C, a.kb);
+  beam_apply(p, e, s, b, t);
+}
+
 __global__ void beam_finalize_kernel(const float* cumul, const int* n_elem, int* order, float* score, int n_img,
                                      int k) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1152,6 +1265,28 @@ extern "C" int odic_group_beam_step(const float* cand_val, const int32_t* cand_i
   p.cand_val = cand_val; p.cand_idx = cand_idx;
   hipLaunchKernelGGL(group_beam_step_kernel, dim3(n_img), dim3(256), 0, (hipStream_t)stream, p, e, (int)groups,
                      (int)group_beams, penalty);
+  return odic_launch_status();
+}
+
+extern "C" int odic_require_beam_step(const float* cand_val, const int32_t* cand_idx, int32_t ncand, const float* logp,
+                                      int64_t ldl, const int64_t* required, int32_t n_required,
+                                      const odic_beam_state* st, const odic_embed_args* emb, int32_t n_img,
+                                      int32_t bank_beams, int32_t T, int64_t eos_idx, int32_t V, void* stream) {
+  if (!cand_val || !cand_idx) return ODIC_ENULL;
+  if (n_required < 0 || n_required > MAX_REQ || bank_beams < 1 || bank_beams > MAX_K) return ODIC_EINVAL;
+  const int R = bank_beams << n_required;
+  if (R > MAX_K || ncand != R) return ODIC_EINVAL;
+  if (n_required > 0 && R < bank_beams + n_required + 1) return ODIC_EINVAL;
+  // eos: the word of an empty row, embedded like any other
+  if (V < 1 || ldl < V || eos_idx < 0 || eos_idx >= V) return ODIC_EINVAL;
+  if (n_required > 0 && (!logp || !required)) return ODIC_EINVAL;
+  BeamParams p; EmbedArgs e;
+  const int rc = beam_params(p, e, st, emb, n_img, R, T, eos_idx);
+  if (rc != 0) return rc;
+  p.cand_val = cand_val; p.cand_idx = cand_idx;
+  RequireArgs a;
+  a.logp = logp; a.ldl = (long)ldl; a.required = (const long long*)required; a.C = n_required; a.kb = bank_beams; a.V = V;
+  hipLaunchKernelGGL(require_beam_step_kernel, dim3(n_img), dim3(256), 0, (hipStream_t)stream, p, e, a);
   return odic_launch_status();
 }
 

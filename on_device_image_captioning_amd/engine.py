@@ -605,6 +605,26 @@ class CaptionerEngine:
         ops.group_beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, groups, st.beams // groups, st.T, eos_idx,
                             penalty, emb=st.emb)
 
+    def require_beam_step(self, st: DecodeState, eos_idx: int, required: torch.Tensor, bank_beams: int,
+                          constraints=None) -> None:
+        """One full step of a search whose captions must contain given words, the sibling of beam_step:
+        `required` int64 [n_img, C] on the device (-1 = unused slot), st.beams = 2^C·bank_beams rows per image.  The top-k
+        launch always writes the log-prob rows (st.logp, k = st.beams): a required word need not be among a row's
+        candidates, so odic_require_beam_step reads its log-prob there.  `constraints`: as in beam_step."""
+        C = int(required.shape[1])
+        if bank_beams < 1 or st.beams != bank_beams << C:
+            raise ValueError(f"{st.beams} rows per image are not 2^{C} banks of {bank_beams} beams")
+        self.step_logits(st, embed=False)
+        if constraints is not None:
+            self.constrained_candidates(st, constraints)
+        else:
+            V = self.g.vocab_size
+            if st.logp is None:
+                st.logp = torch.empty(st.N, V, dtype=torch.float32, device=self.device)
+            ops.logsoftmax_topk(st.logits, V, st.logp, V, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        ops.require_beam_step(st.cand_val, st.cand_idx, st.logp, required, st.beam_state, st.n_img, bank_beams, st.T,
+                              eos_idx, emb=st.emb)
+
     # ------------------------------------------------------------------------------------------
     # a search that starts behind a given prefix (DESIGN.md §4.15)
     def prefill(self, st: DecodeState, prefix: torch.Tensor, sos_idx: int, want_logits: bool = False):

@@ -765,6 +765,27 @@ def group_beam_step(cand_val, cand_idx, state: "_hip.BeamState", n_img, groups, 
                    "odic_group_beam_step")
 
 
+def require_beam_step(cand_val, cand_idx, logp, required, state: "_hip.BeamState", n_img, bank_beams, T, eos_idx,
+                      emb=None) -> None:
+    """The step of a search for captions that contain given words (odic_require_beam_step).  required: int64 [n_img, C]
+    on the device (-1 = unused slot) or None for C = 0; the image's R = 2^C·bank_beams rows are 2^C banks of bank_beams
+    beams.  cand_* are [n_img·R, R]; logp fp32 [n_img·R, V] (row stride >= V): the log-prob rows the candidates came from."""
+    C_ = 0 if required is None else int(required.shape[1])
+    if C_:
+        _need_cuda(logp, required)
+        if required.dtype != torch.int64 or required.dim() != 2 or required.shape[0] != n_img or not required.is_contiguous():
+            raise ValueError("require_beam_step: required must be a contiguous int64 [n_img, C] tensor")
+        if logp.dtype != torch.float32 or logp.dim() != 2 or logp.stride(1) != 1:
+            raise ValueError("require_beam_step: logp must be fp32 [N, V] with unit column stride")
+    beams = bank_beams << C_ if 0 <= C_ <= 4 else 0
+    V = int(logp.shape[1]) if logp is not None else int(eos_idx) + 1
+    ldl = int(logp.stride(0)) if logp is not None else V
+    with _timed("beam_step", 0.0, n_img * beams * (beams * 8.0 + C_ * 12.0) + _beam_bytes(n_img, beams, T, emb)):
+        _hip.check(_hip.load().odic_require_beam_step(_p(cand_val), _p(cand_idx), beams, _p(logp), ldl, _p(required) if C_ else None, C_, C.byref(state), _emb_ref(emb),
+                                                      n_img, bank_beams, T, eos_idx, V, _stream()),
+                   "odic_require_beam_step")
+
+
 def beam_finalize(state: "_hip.BeamState", order, score, n_img, beams) -> None:
     with _timed("beam_finalize", 0.0, n_img * beams * 16.0):
         _hip.check(_hip.load().odic_beam_finalize(C.byref(state), _p(order), _p(score), n_img, beams, _stream()),

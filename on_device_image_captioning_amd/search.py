@@ -1,7 +1,8 @@
 """The host side of a search, once, for beam_search, diverse_beam_search, ensemble_beam_search and the ensemble step of
-CaptionPipeline (DESIGN.md §4.13-§4.14): argument rules, mode dispatch, the step loop with its look at the device's
+CaptionPipeline (DESIGN.md §4.13-§4.16): argument rules, mode dispatch, the step loop with its look at the device's
 `done` flag, the read-out of the chosen rows, and the members of an ensemble on one beam state.  Plain functions over a
-DecodeState (engine.py); the device side of a step is ops.beam_step / ops.group_beam_step.
+DecodeState (engine.py); the device side of a step is ops.beam_step / ops.group_beam_step /
+ops.require_beam_step.
 """
 from __future__ import annotations
 
@@ -86,11 +87,96 @@ def check_prefix(prefix, n_img: int, *, V, max_seq_len: int, sos_idx, eos_idx, s
     return [list(r) for r in rows]
 
 
+MAX_REQUIRED = 4    # required words per image (odic_require_beam_step: 2^C banks of beams, 16 rows per image at most)
+
+
+def check_required_words(required, n_img: int, *, V, beam_size: int, banned, sos_idx, eos_idx, max_seq_len: int,
+                         sampling: bool = False) -> Optional[List[List[int]]]:
+    """The rules of a search whose captions must contain given words.  `required`: one sequence of word
+    ids for all images, or one sequence per image (ragged lists allowed).  None for nothing required (None, or nothing
+    but empty sequences: the search then launches exactly what it launches without the keyword), else n_img lists of C ids,
+    C the longest list, the shorter ones padded with -1; ValueError, before any device work, for what cannot work.
+    `beam_size` is the beams per bank: an image searches 2^C·beam_size rows."""
+    if required is None:
+        return None
+    if isinstance(required, torch.Tensor):
+        required = required.tolist()
+    required = list(required)
+    nested = bool(required) and all(isinstance(r, (list, tuple, torch.Tensor)) for r in required)
+    if nested:
+        rows = [[int(w) for w in (r.tolist() if isinstance(r, torch.Tensor) else r)] for r in required]
+        if len(rows) != n_img:
+            raise ValueError(f"{len(rows)} lists of required words for {n_img} images: give one for all, or one per image")
+    else:
+        rows = [[int(w) for w in required] for _ in range(n_img)]
+    C = max((len(r) for r in rows), default=0)
+    if C == 0:
+        return None
+    if sampling:
+        raise ValueError("required_words applies to the deterministic beam search only: drawing under it "
+                         "(sample_or_max='sample', mode='sampling') is not supported")
+    if C > MAX_REQUIRED:
+        raise ValueError(f"{C} required words for one image: at most {MAX_REQUIRED}")
+    if (1 << C) * beam_size > 16:
+        raise ValueError(f"{C} required words take 2^{C} banks of beam_size = {beam_size} beams, more than 16 rows per "
+                         f"image: beam_size may be {16 >> C} at most")
+    if C == 1 and beam_size == 1:
+        raise ValueError("one required word needs beam_size >= 2: a row must keep a candidate besides that word and EOS")
+    if C > max_seq_len - 2:
+        raise ValueError(f"{C} required words > max_seq_len - 2 = {max_seq_len - 2}: no caption could hold them and end")
+    V = V() if callable(V) else V
+    banned = set() if banned is None else {int(w) for w in banned}
+    for r in rows:
+        if len(set(r)) != len(r):
+            raise ValueError(f"required words {r}: an image's words must be distinct")
+        for w in r:
+            if not 0 <= w < V:
+                raise ValueError(f"required word id {w} lies outside the vocabulary [0, {V})")
+            if w == sos_idx or w == eos_idx:
+                raise ValueError("the SOS and EOS ids cannot be required words")
+            if w in banned:
+                raise ValueError(f"word id {w} is both required and banned")
+    return [list(r) + [-1] * (C - len(r)) for r in rows]
+
+
+def refuse_required_words(required, where: str) -> None:
+    """For the searches that do not take required words: ValueError unless `required` is None or holds no word."""
+    if required is None:
+        return
+    if isinstance(required, torch.Tensor):
+        required = required.tolist()
+    flat = [w for r in required for w in (r if isinstance(r, (list, tuple)) else r.tolist() if isinstance(r, torch.Tensor)
+                                          else [r])]
+    if flat:
+        raise ValueError(f"required_words is not supported {where}: use beam_search on one model, without a prefix")
+
+
+def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, how_many_outputs: int):
+    """The rows a required-words search returns.  order: odic_beam_finalize's [B, R] (host integers), cumul [B, R] (host
+    floats), required: check_required_words' lists.  Output j of an image is the j-th live row (cumul > -inf) of its
+    accepting bank in finalize order; an image whose accepting bank holds no live row falls back to the finalize order
+    over all its live rows.  Fewer live rows than outputs: the remaining outputs go on with the image's other live rows,
+    then repeat the last.  → (rows [B, how_many_outputs] int64, satisfied: a bool per image)."""
+    rows, satisfied = [], []
+    for b, req in enumerate(required):
+        accept = sum(1 << c for c, w in enumerate(req) if w >= 0)
+        live = []
+        for i in (int(v) for v in order[b]):
+            if i not in live and float(cumul[b][i]) > float("-inf"):
+                live.append(i)
+        inside = [i for i in live if i // bank_beams == accept]
+        satisfied.append(bool(inside))
+        pick = (inside + [i for i in live if i not in inside]) if inside else live
+        pick = (pick or [0])[:how_many_outputs]
+        rows.append(pick + [pick[-1]] * (how_many_outputs - len(pick)))
+    return torch.tensor(rows, dtype=torch.int64), satisfied
+
+
 def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
     """mode='beam_search' | 'sampling' | 'diverse_beam_search' with the keys of `args` (a forward(**kwargs) or
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
     sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
-    pre = {"prefix": args["prefix"]} if "prefix" in args else {}        # (absent = the default, as the constraints)
+    pre = {k: args[k] for k in ("prefix", "required_words") if k in args}       # (absent = the default, as the constraints)
     if mode == "beam_search":
         return model.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
                                  beam_size=args.get("beam_size", 5), how_many_outputs=args.get("how_many_outputs", 1),
@@ -103,6 +189,9 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
         if pre.get("prefix") is not None:
             model._search_prefix_arg(pre["prefix"], enc_x, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
                                      sampling=True)
+        if pre.get("required_words") is not None:
+            model._search_required_arg(pre["required_words"], enc_x, beam_size=1, banned_words=None, sos_idx=sos_idx,
+                                       eos_idx=eos_idx, max_seq_len=max_seq_len, sampling=True)
         return model.get_batch_multiple_sampled_prediction(
             enc_x, enc_x_num_pads, num_outputs=args.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
             max_seq_len=max_seq_len)

@@ -4,14 +4,17 @@ FULL geometry, features-only model, 16 images, fp32, HIP events around the step 
 poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
 it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
 
-    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 pbeam:3:6
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 pbeam:3:6 rbeam:3:2
 
 cbeam:K is beam:K under constraints: no_repeat_ngram_size=2, min_length=5 and 8 banned words; the step then
 holds one launch more (odic_topk_rows_constrained) and the top-k launch writes the log-prob rows.
 pbeam:K:P is beam:K behind a prefix of P words: one whole-sequence pass over the prefix that fills the step
 caches (CaptionerEngine.seed_prefix) and max_len - 1 - P steps; compare its time per SEARCH with beam:K's.
-A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix) is
-reported as absent.
+rbeam:K:C is the search for captions that contain C required words: 2^C banks of K beams per image (words
+300 .. 300+C-1 for every image); the top-k launch writes the log-prob rows and the selection is odic_require_beam_step.  Compare
+it with diverse:GxK' at the same number of rows per image.
+A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix, rbeam
+before odic_require_beam_step) is reported as absent.
 """
 import argparse
 import os
@@ -54,7 +57,16 @@ def main():
             if not hasattr(eng, "seed_prefix"):
                 print(f"{form}: not in this build")
                 continue
-        if kind == "diverse":
+        if kind == "rbeam":
+            shape, C = shape.split(":")
+            kb, C = int(shape), int(C)
+            if not hasattr(eng, "require_beam_step"):
+                print(f"{form}: not in this build")
+                continue
+            R = kb << C
+            req = torch.arange(300, 300 + C, device=dev).repeat(a.images, 1)
+            one = lambda st: eng.require_beam_step(st, bench.EOS, req, kb)         # noqa: E731
+        elif kind == "diverse":
             G, kg = (int(v) for v in shape.split("x"))
             if not hasattr(eng, "group_beam_step"):
                 print(f"{form}: not in this build")
