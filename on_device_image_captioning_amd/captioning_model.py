@@ -443,22 +443,22 @@ class CaptioningModel(nn.Module):
         steps = max(1, max_seq_len - 1)
         T = steps + 1
         st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
-        ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
         req = torch.tensor(required, dtype=torch.int64, device=eng.device)
-        cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
 
-        def step(t):
+        def step(cons):
             eng.require_beam_step(st, eos_idx, req, bank_beams, constraints=cons)
             if self._cand_log is not None:       # test hook: the candidates and the required words' log-probs per row
                 logp_h, req_h = st.logp.cpu(), req.cpu().repeat_interleave(R, dim=0)
                 req_logp = torch.where(req_h >= 0, logp_h.gather(1, req_h.clamp(min=0)), torch.tensor(float("-inf")))
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone(), req_logp))
 
-        _search.run_steps(st, steps, step)
-        order, _ = _search.rank_beams(st)
-        rows, self.last_required_satisfied = _search.required_outputs(order.cpu().tolist(), st.cumul.view(B, R).cpu().tolist(),
-                                                                      required, bank_beams, how_many_outputs)
-        return _search.read_captions(st, rows, how_many_outputs)
+        def pick(order, score):
+            rows, self.last_required_satisfied = _search.required_outputs(
+                order.cpu().tolist(), st.cumul.view(B, R).cpu().tolist(), required, bank_beams, how_many_outputs)
+            return rows
+
+        return _search.run_search(eng, st, eos_idx, steps, how_many_outputs, constraints=constraints, step=step, pick=pick,
+                                  arm=lambda: ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb))
 
     def _search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
                             max_seq_len, sample: bool = False, constraints: Optional[dict] = None,
@@ -468,19 +468,18 @@ class CaptioningModel(nn.Module):
         k = beam_size
         steps = max(1, max_seq_len - 1)            # positions 0 .. steps-1 are fed; prefixes reach steps+1
         T = steps + 1
-        enc_len = self._enc_lens(B, S, enc_input_num_pads)
-        st = eng.new_state(B, k, T, eng.project_kv(mem), enc_len)
-        # start state; for the deterministic search also the embedded start token as the input of position 0
+        st = eng.new_state(B, k, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
         P = len(prefix[0]) if prefix else 0
-        if P:                                      # (check_prefix: never with `sample`)
-            eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx)
-        else:
-            ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None if sample else st.emb)
         V = eng.g.vocab_size
         seed = self._next_sampling_seed() if sample else 0
-        cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
 
-        def draw_step(t):
+        def arm():       # start state; for the deterministic search also the embedded start token as the input of position 0
+            if P:                                  # (check_prefix: never with `sample`)
+                eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx)
+            else:
+                ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None if sample else st.emb)
+
+        def draw_step(cons):
             # 'sample' variant (captioning_model.py:128-131,166-168): the k candidates of every beam are drawn
             # without replacement from its distribution instead of being its top-k — on the device
             eng.step_logits(st)
@@ -489,15 +488,14 @@ class CaptioningModel(nn.Module):
                 self._draw_log.append(st.cand_idx.cpu().clone())
             ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx)
 
-        def step(t):
+        def step(cons):
             eng.beam_step(st, eos_idx, constraints=cons)
             if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
 
-        _search.run_steps(st, steps - P, draw_step if sample else step)
-        order, _ = _search.rank_beams(st)
         # (the log-probs are on the engine's device; beam_search moves them to the input's)
-        return _search.read_captions(st, order.cpu()[:, :how_many_outputs], how_many_outputs)
+        return _search.run_search(eng, st, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
+                                  step=draw_step if sample else step)
 
     def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
                             diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20, *, no_repeat_ngram_size=0,
@@ -539,22 +537,24 @@ class CaptioningModel(nn.Module):
         T = steps + 1
         st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
         P = len(prefix[0]) if prefix else 0
-        if P:
-            eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx, group_beams=kg)
-        else:
-            ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
-        cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
 
-        def step(t):
+        def arm():
+            if P:
+                eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx, group_beams=kg)
+            else:
+                ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
+
+        def step(cons):
             eng.group_beam_step(st, eos_idx, G, penalty, constraints=cons)
             if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
                 self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
 
-        _search.run_steps(st, steps - P, step)
-        _, score = _search.rank_beams(st)
-        best = score.view(B, G, kg).cpu().argmax(dim=2)           # (first maximum: ties go to the lower row)
-        rows = torch.arange(G)[None, :] * kg + best               # output j of an image: the best row of group j
-        res_tok, lp = _search.read_captions(st, rows[:, :how_many_outputs], how_many_outputs)
+        def pick(order, score):                                   # output j of an image: the best row of group j
+            best = score.view(B, G, kg).cpu().argmax(dim=2)       # (first maximum: ties go to the lower row)
+            return (torch.arange(G)[None, :] * kg + best)[:, :how_many_outputs]
+
+        res_tok, lp = _search.run_search(eng, st, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
+                                         step=step, pick=pick)
         return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
 

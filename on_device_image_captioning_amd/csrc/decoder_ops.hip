@@ -664,8 +664,8 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
 
 // ---------------------------------------------------------------------------------------------
 // Beam bookkeeping: one block per image (captioning_model.py:172-223).  Wave 0 does the k·k selection — one lane per
-// candidate (four at k = 16), k rounds of a wave arg-max in which the lowest flat index wins a tie (the scan order
-// of the reference's topk over the flattened k x k scores) — then all threads permute the prefix / log-prob /
+// candidate (four at k = 16), k rounds of wave_extract_best (below) in which the lowest flat index wins a tie (the scan
+// order of the reference's topk over the flattened k x k scores) — then all threads permute the prefix / log-prob /
 // ancestor rows IN PLACE (a thread owns whole columns j: it reads the k parent values of its column first, then
 // writes the k new rows) and, when asked to, write the embedding of the chosen words for the next position
 // (EmbeddingLayer, layers.py:118-121: what odic_dec_embed would do in its own launch).  The block that arrives last
@@ -679,8 +679,6 @@ struct BeamParams {
   int* pos; int* done; int* ctr;
   int n_img, k, T; long long eos;
 };
-struct EmbedArgs { const float* embed; const float* pos_table; float* y; long ldy; int d; float scale; int pos_rows; };
-
 struct BeamShared {
   float cv[MAX_K * MAX_K]; int ci[MAX_K * MAX_K];      // candidates: log-prob, word  [beam][rank]
   int eos[MAX_K]; int ne[MAX_K]; float cu[MAX_K];
@@ -690,12 +688,16 @@ struct BeamShared {
 
 constexpr int BEAM_NT = 256;                           // threads of beam_step_kernel / group_beam_step_kernel
 
-// The three parts of a step, shared by beam_step_kernel and group_beam_step_kernel: beam_load_rows (per-beam flags and
-// per-token log-probs of the image into LDS; ends with a barrier that also covers the caller's s.cv / s.ci),
-// a selection by wave 0 that fills s.parent (row within the image) / s.word / s.lp, and beam_apply (everything after).
+// The three parts of a step, shared by the three step kernels: beam_load_rows (the image's k x k candidates, per-beam
+// flags and per-token log-probs into LDS; ends with a barrier that also covers the caller's own prologue), a selection
+// by wave 0 that fills s.parent (row within the image) / s.word / s.lp, and beam_apply (everything after).
 __device__ __forceinline__ void beam_load_rows(const BeamParams& p, BeamShared& s, int b, int t) {
   constexpr int NT = BEAM_NT;
   const int tid = threadIdx.x, k = p.k, T = p.T;
+  for (int i = tid; i < k * k; i += NT) {
+    s.cv[i] = p.cand_val[(long)b * k * k + i];
+    s.ci[i] = p.cand_idx[(long)b * k * k + i];
+  }
   for (int r = tid; r < k; r += NT) {
     s.eos[r] = p.has_eos[b * k + r]; s.ne[r] = p.n_elem[b * k + r]; s.cu[r] = p.cumul[b * k + r];
   }
@@ -706,44 +708,67 @@ __device__ __forceinline__ void beam_load_rows(const BeamParams& p, BeamShared& 
   __syncthreads();
 }
 
-// the k best of the k x k candidates, the lowest flat index winning a tie (wave 0 only)
+// The extraction all three selections repeat (wave 0 only, all 64 lanes).  A lane holds BEAM_CPL candidates in registers:
+// tot (what is ranked; -inf = none), key (unique among the live candidates) and val (the payload: what s.lp will hold).
+// One call takes out the largest total, a tie going to the smaller key: every lane returns with the winner's key and
+// payload and found = (its total > -inf; else bk = NO_KEY<K>), and the lane that owns the winner has retired it — by
+// comparing every register slot with the winning key: a runtime index would send the arrays to scratch.  A selection =
+// fill tot / key / val, extract n times, lane 0 decodes each key.
+constexpr int BEAM_CPL = MAX_K * MAX_K / 64;           // candidates per lane: every selection ranks 256 at most
+template <typename K> constexpr K NO_KEY = (K)(0x7fffffffffffffffLL >> (64 - 8 * (int)sizeof(K)));
+
+template <typename K>
+__device__ __forceinline__ bool wave_extract_best(float (&tot)[BEAM_CPL], K (&key)[BEAM_CPL], const float (&val)[BEAM_CPL],
+                                                  K& bk, float& bval) {
+  // (conditions joined with | and & on purpose: the short-circuit forms compile to a branch per candidate)
+  float best = tot[0]; bval = val[0]; bk = key[0];
+#pragma unroll
+  for (int u = 1; u < BEAM_CPL; ++u) {
+    const bool take = (tot[u] > best) | ((tot[u] == best) & (key[u] < bk));
+    best = take ? tot[u] : best; bval = take ? val[u] : bval; bk = take ? key[u] : bk;
+  }
+  if (!(best > -INFINITY)) bk = NO_KEY<K>;             // nothing left in this lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64), ol = __shfl_xor(bval, o, 64);
+    const K ok = __shfl_xor(bk, o, 64);
+    const bool take = (ov > best) | ((ov == best) & (ok < bk));
+    best = take ? ov : best; bval = take ? ol : bval; bk = take ? ok : bk;
+  }
+  const bool found = best > -INFINITY;
+#pragma unroll
+  for (int u = 0; u < BEAM_CPL; ++u) {
+    const bool hit = found & (key[u] == bk);
+    tot[u] = hit ? -INFINITY : tot[u]; key[u] = hit ? NO_KEY<K> : key[u];
+  }
+  return found;
+}
+
+// the k best of the k x k candidates.  Key: the flat candidate index beam·k + rank (the scan order of the reference's
+// topk over the flattened scores; drawn candidates are not sorted by word, and a finished row's rule is positional)
 __device__ __forceinline__ void beam_select(const BeamParams& p, BeamShared& s, int t) {
-  const int tid = threadIdx.x, k = p.k;
-  if (tid < 64) {
-    const int lane = tid;
-    if (t == 0) {                       // seeding: the k best words of beam 0
-      if (lane < k) { s.parent[lane] = 0; s.word[lane] = s.ci[lane]; s.lp[lane] = s.cv[lane]; }
-    } else {
-      constexpr int CPL = MAX_K * MAX_K / 64;        // candidates per lane
-      float tot[CPL], val[CPL];
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x, k = p.k;
+  if (t == 0) {                         // seeding: the k best words of beam 0
+    if (lane < k) { s.parent[lane] = 0; s.word[lane] = s.ci[lane]; s.lp[lane] = s.cv[lane]; }
+    return;
+  }
+  float tot[BEAM_CPL], val[BEAM_CPL]; int key[BEAM_CPL];
 #pragma unroll
-      for (int u = 0; u < CPL; ++u) {
-        const int i = lane + 64 * u;
-        tot[u] = -INFINITY; val[u] = 0.f;
-        if (i < k * k) {
-          const int j = i / k, c = i - j * k;
-          val[u] = s.eos[j] ? (c == 0 ? 0.0f : -999.0f) : s.cv[i];
-          tot[u] = s.cu[j] + val[u];
-        }
-      }
-      for (int r = 0; r < k; ++r) {
-        float best = tot[0], bval = val[0]; int bi = lane;
-#pragma unroll
-        for (int u = 1; u < CPL; ++u)
-          if (tot[u] > best) { best = tot[u]; bval = val[u]; bi = lane + 64 * u; }
-        if (!(best > -INFINITY)) bi = 0x7fffffff;               // nothing left in this lane
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const float ov = __shfl_xor(best, o, 64), ol = __shfl_xor(bval, o, 64);
-          const int oi = __shfl_xor(bi, o, 64);
-          if (ov > best || (ov == best && oi < bi)) { best = ov; bval = ol; bi = oi; }
-        }
-#pragma unroll
-        for (int u = 0; u < CPL; ++u)
-          if (bi == lane + 64 * u) tot[u] = -INFINITY;
-        if (lane == 0) { s.parent[r] = bi / k; s.word[r] = s.ci[bi]; s.lp[r] = bval; }
-      }
+  for (int u = 0; u < BEAM_CPL; ++u) {
+    const int i = lane + 64 * u;
+    tot[u] = -INFINITY; val[u] = 0.f; key[u] = NO_KEY<int>;
+    if (i < k * k) {
+      const int j = i / k, c = i - j * k;
+      val[u] = s.eos[j] ? (c == 0 ? 0.0f : -999.0f) : s.cv[i];
+      tot[u] = s.cu[j] + val[u];
+      key[u] = i;
     }
+  }
+  for (int r = 0; r < k; ++r) {
+    int bi; float bval;
+    wave_extract_best(tot, key, val, bi, bval);
+    if (lane == 0) { s.parent[r] = bi / k; s.word[r] = s.ci[bi]; s.lp[r] = bval; }
   }
 }
 
@@ -825,13 +850,9 @@ __device__ __forceinline__ void beam_apply(const BeamParams& p, const EmbedArgs&
 
 __global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p, EmbedArgs e) {
   __shared__ BeamShared s;
-  const int b = blockIdx.x, k = p.k;
+  const int b = blockIdx.x;
   const int t = *p.pos;                 // position just processed; prefix length is t+1
   if (t + 1 >= p.T) return;             // the prefix is full: a replay past the last step changes nothing
-  for (int i = threadIdx.x; i < k * k; i += 256) {
-    s.cv[i] = p.cand_val[(long)b * k * k + i];
-    s.ci[i] = p.cand_idx[(long)b * k * k + i];
-  }
   beam_load_rows(p, s, b, t);
   beam_select(p, s, t);
   beam_apply(p, e, s, b, t);             // (four waves: the k·d embedding rows and the prefix re-gather are the bulk)
@@ -842,14 +863,14 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p, EmbedArgs 
 // group g.  Wave 0 walks the groups in order.  Group g ranks its kg·R candidates (beam j of the group x its R best
 // words; four per lane at most) by   total = cumul_j + (logp_j(w) - penalty·count[w])   where count[w] is the number
 // of picks of groups 0..g-1 at this step that appended w to a beam still growing; a finished beam keeps the rule of
-// beam_select (rank 0 worth 0, the others -999, never penalised).  Order: total descending, then beam in group
-// ascending, then word ascending — at G = 1 (count = 0, a row's candidates sorted by value, then word) the lowest flat
-// index of beam_select.  The three operations are rounded separately (__fmul_rn, __fsub_rn, __fadd_rn; the products go
+// beam_select (rank 0 worth 0, the others -999, never penalised).  wave_extract_best with the key (beam in group, word)
+// — unique within a group, a row's k words being distinct; at G = 1 (count = 0, a row's candidates sorted by value, then
+// word) the order of beam_select's flat index — and the candidate's own, unpenalised value as the payload: that is what
+// is stored (s.lp).  The three operations are rounded separately (__fmul_rn, __fsub_rn, __fadd_rn; the products go
 // through a small LDS table so that nothing can be contracted), so that a float32 host model reproduces the order bit
-// for bit.  The picks made so far ARE the penalty list: s.word[q]
-// and grow[q] for q < g·kg (at most 15 entries), read back by the next group after a fence.  What is stored (s.lp) is
-// the candidate's own, unpenalised value.  Seeding (t = 0): every row holds the same distribution; group g draws from
-// its first row, against the seeds of the groups before it.
+// for bit.  The picks made so far ARE the penalty list: s.word[q] and grow[q] for q < g·kg (at most 15 entries), read
+// back by the next group after a fence.  Seeding (t = 0): every row holds the same distribution; group g draws from its
+// first row, against the seeds of the groups before it.
 // R candidates per row are enough: the penalised top-kg of a row lies inside its unpenalised top-(kg + P), P <= g·kg <=
 // R - kg the number of penalised words.
 // ---------------------------------------------------------------------------------------------
@@ -857,54 +878,38 @@ __device__ __forceinline__ void group_beam_select(const BeamParams& p, BeamShare
                                                   int t, int G, int kg) {
   if (threadIdx.x >= 64) return;
   const int lane = threadIdx.x, R = p.k;
-  constexpr int CPL = MAX_K * MAX_K / 64;              // candidates per lane (kg·R <= 256)
-  constexpr long long NO_KEY = 0x7fffffffffffffffLL;
-  const int nc = (t == 0 ? 1 : kg) * R;                // candidates of a group
+  const int nc = (t == 0 ? 1 : kg) * R;                // candidates of a group (kg·R <= 256)
   for (int g = 0; g < G; ++g) {
     const int row0 = g * kg;                           // first row of the group = number of earlier picks
-    float tot[CPL]; long long key[CPL];                // key: (beam in group, word); lower wins a tie on the total
+    float tot[BEAM_CPL], val[BEAM_CPL]; long long key[BEAM_CPL];
 #pragma unroll
-    for (int u = 0; u < CPL; ++u) {
+    for (int u = 0; u < BEAM_CPL; ++u) {
       const int i = lane + 64 * u;
-      tot[u] = -INFINITY; key[u] = NO_KEY;
+      tot[u] = -INFINITY; val[u] = 0.f; key[u] = NO_KEY<long long>;
       if (i < nc) {
         const int j = i / R, c = i - j * R, row = row0 + j, fl = row * R + c;
         const int w = s.ci[fl];
         float v;
         if (t > 0 && s.eos[row]) {
-          v = c == 0 ? 0.0f : -999.0f;
+          v = val[u] = c == 0 ? 0.0f : -999.0f;
         } else {
           int cnt = 0;
           for (int q = 0; q < row0; ++q) cnt += (grow[q] && s.word[q] == w) ? 1 : 0;
-          v = __fsub_rn(s.cv[fl], pen[cnt]);
+          val[u] = s.cv[fl];
+          v = __fsub_rn(val[u], pen[cnt]);
         }
         tot[u] = t == 0 ? v : __fadd_rn(s.cu[row], v);
         key[u] = ((long long)j << 32) | (long long)(unsigned)w;
       }
     }
     for (int r = 0; r < kg; ++r) {
-      float best = tot[0]; long long bk = key[0]; int bu = 0;
-#pragma unroll
-      for (int u = 1; u < CPL; ++u)
-        if (tot[u] > best || (tot[u] == best && key[u] < bk)) { best = tot[u]; bk = key[u]; bu = u; }
-      int bi = lane + 64 * bu;                           // index into the group's candidates
-      if (!(best > -INFINITY)) { bk = NO_KEY; bi = 0x7fffffff; }     // nothing left in this lane
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const long long ok = __shfl_xor(bk, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && (ok < bk || (ok == bk && oi < bi)))) { best = ov; bk = ok; bi = oi; }
-      }
-#pragma unroll
-      for (int u = 0; u < CPL; ++u)
-        if (bi == lane + 64 * u) { tot[u] = -INFINITY; key[u] = NO_KEY; }
-      if (lane == 0) {
-        if (bi >= nc) bi = 0;                            // (fewer than kg finite candidates: the group's first one)
-        const int j = bi / R, c = bi - j * R, row = row0 + j;
+      long long bk; float bval;
+      const bool found = wave_extract_best(tot, key, val, bk, bval);
+      if (lane == 0) {                                   // (fewer than kg finite candidates: the group's first one)
+        const int row = found ? row0 + (int)(bk >> 32) : row0;
         const int fin = t > 0 && s.eos[row];
-        s.parent[row0 + r] = row; s.word[row0 + r] = s.ci[row * R + c];
-        s.lp[row0 + r] = fin ? (c == 0 ? 0.0f : -999.0f) : s.cv[row * R + c];
+        s.parent[row0 + r] = row; s.word[row0 + r] = found ? (int)(bk & 0xffffffffLL) : s.ci[row0 * R];
+        s.lp[row0 + r] = found ? bval : fin ? 0.0f : s.cv[row0 * R];
         grow[row0 + r] = fin ? 0 : 1;
       }
     }
@@ -919,15 +924,11 @@ __global__ __launch_bounds__(256) void group_beam_step_kernel(BeamParams p, Embe
   __shared__ BeamShared s;
   __shared__ int grow[MAX_K];           // pick q of this step extends a beam that was still growing
   __shared__ float pen[MAX_K];          // penalty·count for count = 0 .. 15 (at most R - kg earlier picks)
-  const int b = blockIdx.x, R = p.k;
+  const int b = blockIdx.x;
   const int t = *p.pos;
   if (t + 1 >= p.T) return;
   // the product is rounded on its own here and only read back below: the build contracts a·b - c into one fma otherwise
   if (threadIdx.x < MAX_K) pen[threadIdx.x] = __fmul_rn(penalty, (float)threadIdx.x);
-  for (int i = threadIdx.x; i < R * R; i += 256) {
-    s.cv[i] = p.cand_val[(long)b * R * R + i];
-    s.ci[i] = p.cand_idx[(long)b * R * R + i];
-  }
   beam_load_rows(p, s, b, t);
   group_beam_select(p, s, grow, pen, t, G, kg);
   beam_apply(p, e, s, b, t);
@@ -943,10 +944,10 @@ __global__ __launch_bounds__(256) void group_beam_step_kernel(BeamParams p, Embe
 //          beam_select's rank 0 (worth 0) and offers nothing else;
 //   enter  for every slot c set in m, row j of bank m ^ (1 << c) x the word required[c], at the value gathered from the
 //          row's log-probs (rlp) — the word need not be among the row's R best.
-// Only rows with cumul > -inf offer anything (t = 0: row 0 alone, total = v).  Order: total descending, then source row
-// ascending, then word ascending; (row, word) is unique within a target bank, so the key decides every tie.  A slot for
-// which no finite total is left becomes an EMPTY row: parent = the slot itself (row 0 at t = 0), word = EOS, stored
-// log-prob -inf — beam_apply then leaves it with cumul = -inf and has_eos = 1, and it never offers anything again.
+// Only rows with cumul > -inf offer anything (t = 0: row 0 alone, total = v).  wave_extract_best with the key (source
+// row, word), unique within a target bank, and the candidate's value as the payload.  A slot for which no finite total
+// is left (not found) becomes an EMPTY row: parent = the slot itself (row 0 at t = 0), word = EOS, stored log-prob -inf —
+// beam_apply then leaves it with cumul = -inf and has_eos = 1, and it never offers anything again.
 // The banks read only the state of before the step, so nothing is handed from one bank to the next (no fence as between
 // the groups of group_beam_select).  total is one __fadd_rn, as in the group kernel.
 // ---------------------------------------------------------------------------------------------
@@ -957,17 +958,15 @@ __device__ __forceinline__ void require_beam_select(const BeamParams& p, BeamSha
                                                     const float (*rlp)[MAX_REQ], int t, int C, int kb) {
   if (threadIdx.x >= 64) return;
   const int lane = threadIdx.x, R = p.k, eos = (int)p.eos;
-  constexpr int CPL = MAX_K * MAX_K / 64;              // candidates per lane (kb·(R + C) <= 256)
-  constexpr long long NO_KEY = 0x7fffffffffffffffLL;
   int accept = 0;
   for (int c = 0; c < C; ++c) accept |= req[c] >= 0 ? 1 << c : 0;
-  const int n_stay = kb * R, nc = n_stay + C * kb;
+  const int n_stay = kb * R, nc = n_stay + C * kb;     // (kb·(R + C) <= 256)
   for (int m = 0; m < (1 << C); ++m) {
-    float tot[CPL], val[CPL]; long long key[CPL];      // key: (source row, word); lower wins a tie on the total
+    float tot[BEAM_CPL], val[BEAM_CPL]; long long key[BEAM_CPL];
 #pragma unroll
-    for (int u = 0; u < CPL; ++u) {
+    for (int u = 0; u < BEAM_CPL; ++u) {
       const int i = lane + 64 * u;
-      tot[u] = -INFINITY; val[u] = 0.f; key[u] = NO_KEY;
+      tot[u] = -INFINITY; val[u] = 0.f; key[u] = NO_KEY<long long>;
       if (i < nc) {
         int row, w; bool ok; float v = 0.f;
         if (i < n_stay) {
@@ -997,21 +996,8 @@ __device__ __forceinline__ void require_beam_select(const BeamParams& p, BeamSha
       }
     }
     for (int r = 0; r < kb; ++r) {
-      float best = tot[0], bval = val[0]; long long bk = key[0];
-#pragma unroll
-      for (int u = 1; u < CPL; ++u)
-        if (tot[u] > best || (tot[u] == best && key[u] < bk)) { best = tot[u]; bval = val[u]; bk = key[u]; }
-      if (!(best > -INFINITY)) bk = NO_KEY;              // nothing left in this lane
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64), ol = __shfl_xor(bval, o, 64);
-        const long long ok = __shfl_xor(bk, o, 64);
-        if (ov > best || (ov == best && ok < bk)) { best = ov; bval = ol; bk = ok; }
-      }
-      const bool found = best > -INFINITY;
-#pragma unroll
-      for (int u = 0; u < CPL; ++u)
-        if (found && key[u] == bk) { tot[u] = -INFINITY; key[u] = NO_KEY; }
+      long long bk; float bval;
+      const bool found = wave_extract_best(tot, key, val, bk, bval);
       if (lane == 0) {
         const int slot = m * kb + r;
         s.parent[slot] = found ? (int)(bk >> 32) : (t == 0 ? 0 : slot);
@@ -1029,10 +1015,6 @@ __global__ __launch_bounds__(256) void require_beam_step_kernel(BeamParams p, Em
   const int b = blockIdx.x, R = p.k, C = a.C;
   const int t = *p.pos;
   if (t + 1 >= p.T) return;
-  for (int i = threadIdx.x; i < R * R; i += 256) {
-    s.cv[i] = p.cand_val[(long)b * R * R + i];
-    s.ci[i] = p.cand_idx[(long)b * R * R + i];
-  }
   for (int i = threadIdx.x; i < R * C; i += 256) {
     const int row = i / C, c = i - row * C;
     const long long w = a.required[(long)b * C + c];
@@ -1228,14 +1210,7 @@ static int beam_params(BeamParams& p, EmbedArgs& e, const odic_beam_state* st, c
   p.cumul = st->cumul; p.n_elem = st->n_elem; p.has_eos = st->has_eos; p.row_valid = st->row_valid;
   p.next_tok = (long long*)st->next_tok; p.pos = st->pos; p.done = st->done; p.ctr = st->ctr;
   p.n_img = n_img; p.k = beams; p.T = T; p.eos = eos_idx;
-  e.embed = nullptr; e.pos_table = nullptr; e.y = nullptr; e.ldy = 0; e.d = 0; e.scale = 0.f; e.pos_rows = 0;
-  if (emb) {
-    if (!emb->embed || !emb->pos_table || !emb->y) return ODIC_ENULL;
-    if (emb->d <= 0 || emb->pos_rows <= 0) return ODIC_EINVAL;
-    e.embed = emb->embed; e.pos_table = emb->pos_table; e.y = emb->y; e.ldy = emb->ldy; e.d = emb->d; e.scale = emb->scale;
-    e.pos_rows = emb->pos_rows;
-  }
-  return 0;
+  return odic_embed_args_from(e, emb);
 }
 
 extern "C" int odic_beam_step(const float* cand_val, const int32_t* cand_idx, const odic_beam_state* st,
@@ -1313,13 +1288,9 @@ extern "C" int odic_beam_finalize_best(const odic_beam_state* st, int32_t* order
 extern "C" int odic_beam_reset(const odic_beam_state* st, const odic_embed_args* emb, int32_t n_img, int32_t beams,
                                int32_t T, int64_t sos_idx, void* stream) {
   if (!st) return ODIC_ENULL;
-  EmbedArgs e; e.embed = nullptr; e.pos_table = nullptr; e.y = nullptr; e.ldy = 0; e.d = 0; e.scale = 0.f; e.pos_rows = 0;
-  if (emb) {
-    if (!emb->embed || !emb->pos_table || !emb->y) return ODIC_ENULL;
-    if (emb->d <= 0 || emb->pos_rows <= 0) return ODIC_EINVAL;
-    e.embed = emb->embed; e.pos_table = emb->pos_table; e.y = emb->y; e.ldy = emb->ldy; e.d = emb->d; e.scale = emb->scale;
-    e.pos_rows = emb->pos_rows;
-  }
+  EmbedArgs e;
+  const int rc = odic_embed_args_from(e, emb);
+  if (rc != 0) return rc;
   if (!st->tokens || !st->logprobs || !st->row_valid || !st->next_tok || !st->pos || !st->done || !st->ctr)
     return ODIC_ENULL;
   if (n_img <= 0 || beams <= 0 || beams > MAX_K || T <= 0) return ODIC_EINVAL;

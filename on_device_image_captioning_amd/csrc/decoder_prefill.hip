@@ -102,7 +102,7 @@ struct ResetPrefixParams {
   long long* tok; float* lp; int* anc; float* cumul; int* n_elem; int* has_eos; int* row_valid; long long* next_tok;
   int* pos; int* done; int* ctr;
   const long long* prefix; const float* prefix_logp;
-  const float* embed; const float* pos_table; float* y; long ldy; int d; float scale;
+  EmbedArgs e;
   int k, kg, T, P; long long sos;
 };
 
@@ -127,12 +127,13 @@ __global__ __launch_bounds__(256) void beam_reset_prefix_kernel(ResetPrefixParam
     p.cumul[n] = cs; p.n_elem[n] = P + 1; p.has_eos[n] = 0; p.row_valid[n] = 1; p.next_tok[n] = pre[P - 1];
   }
   if (b == 0 && tid == 0) { *p.pos = P; *p.done = 0; *p.ctr = 0; }
-  if (p.embed) {                                  // input of position P: the last prefix word
-    const float* er = p.embed + pre[P - 1] * (long)p.d;
-    const float* prow = p.pos_table + (long)P * p.d;
-    for (int i = tid; i < k * p.d; i += 256) {
-      const int r = i / p.d, c = i - r * p.d;
-      p.y[((long)b * k + r) * p.ldy + c] = er[c] * p.scale + prow[c];
+  const EmbedArgs& e = p.e;
+  if (e.embed) {                                  // input of position P: the last prefix word
+    const float* er = e.embed + pre[P - 1] * (long)e.d;
+    const float* prow = e.pos_table + (long)P * e.d;
+    for (int i = tid; i < k * e.d; i += 256) {
+      const int r = i / e.d, c = i - r * e.d;
+      e.y[((long)b * k + r) * e.ldy + c] = er[c] * e.scale + prow[c];
     }
   }
 }
@@ -179,12 +180,9 @@ extern "C" int odic_beam_reset_prefix(const odic_beam_state* st, const odic_embe
   p.has_eos = st->has_eos; p.row_valid = st->row_valid; p.next_tok = (long long*)st->next_tok;
   p.pos = st->pos; p.done = st->done; p.ctr = st->ctr;
   p.prefix = (const long long*)prefix; p.prefix_logp = prefix_logp;
-  p.embed = nullptr; p.pos_table = nullptr; p.y = nullptr; p.ldy = 0; p.d = 0; p.scale = 0.f;
-  if (emb) {
-    if (!emb->embed || !emb->pos_table || !emb->y) return ODIC_ENULL;
-    if (emb->d <= 0 || emb->pos_rows <= P || emb->ldy < emb->d) return ODIC_EINVAL;     // pos_table row P is read
-    p.embed = emb->embed; p.pos_table = emb->pos_table; p.y = emb->y; p.ldy = emb->ldy; p.d = emb->d; p.scale = emb->scale;
-  }
+  const int rc = odic_embed_args_from(p.e, emb);
+  if (rc != 0) return rc;
+  if (emb && (p.e.pos_rows <= P || p.e.ldy < p.e.d)) return ODIC_EINVAL;               // pos_table row P is read
   p.k = beams; p.kg = group_beams; p.T = T; p.P = P; p.sos = sos_idx;
   hipLaunchKernelGGL(beam_reset_prefix_kernel, dim3(n_img), dim3(256), 0, (hipStream_t)stream, p);
   return odic_launch_status();

@@ -181,3 +181,17 @@ static inline int odic_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
+
+// The embedding tail of the beam kernels (decoder_ops.hip, decoder_prefill.hip) as a kernel argument, and its one
+// translation from the C ABI's nullable odic_embed_args: no `emb` = all zero (embed == nullptr: the tail is skipped).
+struct EmbedArgs { const float* embed; const float* pos_table; float* y; long ldy; int d; float scale; int pos_rows; };
+
+static inline int odic_embed_args_from(EmbedArgs& e, const odic_embed_args* emb) {
+  e.embed = nullptr; e.pos_table = nullptr; e.y = nullptr; e.ldy = 0; e.d = 0; e.scale = 0.f; e.pos_rows = 0;
+  if (!emb) return 0;
+  if (!emb->embed || !emb->pos_table || !emb->y) return ODIC_ENULL;
+  if (emb->d <= 0 || emb->pos_rows <= 0) return ODIC_EINVAL;
+  e.embed = emb->embed; e.pos_table = emb->pos_table; e.y = emb->y; e.ldy = emb->ldy; e.d = emb->d; e.scale = emb->scale;
+  e.pos_rows = emb->pos_rows;
+  return 0;
+}

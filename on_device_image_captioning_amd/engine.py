@@ -577,14 +577,18 @@ class CaptionerEngine:
             ops.logsoftmax_topk(st.logits, V, logp, V, st.cand_val, st.cand_idx, st.N, V, st.beams)
         ops.topk_rows_constrained(logp, constraints, st.cand_val, st.cand_idx, st.beams)
 
-    def _candidates(self, st: DecodeState, constraints) -> None:
-        """The decoder pass of a step, then st.cand_val / st.cand_idx = the st.beams best (admissible) words of every row."""
+    def _candidates(self, st: DecodeState, constraints, want_logp: bool = False) -> None:
+        """The decoder pass of a step, then st.cand_val / st.cand_idx = the st.beams best (admissible) words of every row.
+        `want_logp`: the top-k launch also writes the log-prob rows (st.logp), as it does under constraints anyway."""
         self.step_logits(st, embed=False)
         if constraints is not None:
             self.constrained_candidates(st, constraints)
-        else:
-            V = self.g.vocab_size
-            ops.logsoftmax_topk(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, st.beams)
+            return
+        V = self.g.vocab_size
+        if want_logp and st.logp is None:
+            st.logp = torch.empty(st.N, V, dtype=torch.float32, device=self.device)
+        logp, ldp = (st.logp, V) if want_logp else (None, 0)
+        ops.logsoftmax_topk(st.logits, V, logp, ldp, st.cand_val, st.cand_idx, st.N, V, st.beams)
 
     def beam_step(self, st: DecodeState, eos_idx: int, constraints=None) -> None:
         """One full search step: decoder → log-softmax / top-k (one block per row) → beam bookkeeping + the next
@@ -614,14 +618,7 @@ class CaptionerEngine:
         C = int(required.shape[1])
         if bank_beams < 1 or st.beams != bank_beams << C:
             raise ValueError(f"{st.beams} rows per image are not 2^{C} banks of {bank_beams} beams")
-        self.step_logits(st, embed=False)
-        if constraints is not None:
-            self.constrained_candidates(st, constraints)
-        else:
-            V = self.g.vocab_size
-            if st.logp is None:
-                st.logp = torch.empty(st.N, V, dtype=torch.float32, device=self.device)
-            ops.logsoftmax_topk(st.logits, V, st.logp, V, st.cand_val, st.cand_idx, st.N, V, st.beams)
+        self._candidates(st, constraints, want_logp=True)
         ops.require_beam_step(st.cand_val, st.cand_idx, st.logp, required, st.beam_state, st.n_img, bank_beams, st.T,
                               eos_idx, emb=st.emb)
 

@@ -123,17 +123,18 @@ class EsembleCaptioningModel(CaptioningModel):
                   for m, eng, mem in zip(self.models_list, engs, mems)]
         lead = _search.share_beam_state(states)
         P = len(prefix[0]) if prefix else 0
-        if P:
-            _search.ensemble_seed_prefix(engs, states, _search.prefix_tensor(prefix, engs[0].device), sos_idx)
-        else:
-            ops.beam_reset(lead.beam_state, B, k, T, sos_idx, emb=None)  # (the members embed for themselves in step_logits)
         avg = torch.empty(lead.N, engs[0].g.vocab_size, dtype=torch.float32, device=engs[0].device)
-        cons = engs[0].search_constraints(lead, eos_idx, **constraints) if constraints else None
-        _search.run_steps(lead, steps - P, lambda t: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed,
-                                                                       constraints=cons))
-        order, _ = _search.rank_beams(lead)
+
+        def arm():
+            if P:
+                _search.ensemble_seed_prefix(engs, states, _search.prefix_tensor(prefix, engs[0].device), sos_idx)
+            else:
+                ops.beam_reset(lead.beam_state, B, k, T, sos_idx, emb=None)  # (the members embed for themselves in step_logits)
+
         # (the log-probs stay on the engine's device, unlike beam_search's, which go to the input's)
-        return _search.read_captions(lead, order.cpu()[:, :how_many_outputs], how_many_outputs)
+        return _search.run_search(
+            engs[0], lead, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
+            step=lambda cons: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed, constraints=cons))
 
     def beam_search(self, *a, **k):
         """ensemble_beam_search, with its arguments, under the name the mode dispatch (search.dispatch) calls; the

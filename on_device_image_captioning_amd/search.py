@@ -1,8 +1,9 @@
 """The host side of a search, once, for beam_search, diverse_beam_search, ensemble_beam_search and the ensemble step of
-CaptionPipeline: argument rules, mode dispatch, the step loop with its look at the device's
-`done` flag, the read-out of the chosen rows, and the members of an ensemble on one beam state.  Plain functions over a
-DecodeState (engine.py); the device side of a step is ops.beam_step / ops.group_beam_step /
-ops.require_beam_step.
+CaptionPipeline: argument rules, mode dispatch, the members of an ensemble on one beam state, and
+run_search — arm, constraints, the step loop with its look at the device's `done` flag, ranking, row pick, read-out — which
+every search method calls with its own way to arm, its step and its rows.  Plain functions over a DecodeState (engine.py);
+the device side of a step is ops.beam_step / ops.group_beam_step / ops.require_beam_step, three rules on one extraction
+(wave_extract_best, csrc/decoder_ops.hip).
 """
 from __future__ import annotations
 
@@ -239,6 +240,20 @@ def read_captions(state, rows: torch.Tensor, how_many_outputs: int) -> Tuple[Lis
             lp_rows.append(state.logprobs[b, i, :n])
         res_tok.append(per)
     return res_tok, torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
+
+
+def run_search(eng, st, eos_idx: int, steps: int, how_many_outputs: int, *, arm: Callable[[], None],
+               step: Callable[[object], None], pick: Optional[Callable] = None, constraints: Optional[dict] = None):
+    """A whole search on the built (lead) state `st`, once for every search: arm() brings the state to its first position
+    (beam_reset, seed_prefix, ensemble_seed_prefix); `constraints` (check_constraints' keywords, or None) become the
+    device's on `eng`; step(cons) enqueues one step under them and feeds the caller's log hook, `steps` times at most
+    (run_steps); pick(order, score) takes rank_beams' device tensors to the output rows [B, how_many_outputs] (host
+    integers; default: the first of the finalize order).  → read_captions: the log-probs are on the state's device."""
+    arm()
+    cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
+    run_steps(st, steps, lambda t: step(cons))
+    order, score = rank_beams(st)
+    return read_captions(st, pick(order, score) if pick else order.cpu()[:, :how_many_outputs], how_many_outputs)
 
 
 def share_beam_state(states):

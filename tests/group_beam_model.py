@@ -79,10 +79,11 @@ def select_image(cv, ci, cumul, has_eos, t: int, G: int, kg: int, lam: float):
     return parent, word, lp, grow, ev
 
 
-def step(st: dict, cand_val, cand_idx, G: int, kg: int, lam: float, eos: int, emb: dict | None = None):
+def step(st: dict, cand_val, cand_idx, G: int, kg: int, lam: float, eos: int, emb: dict | None = None, select=None):
     """One step on every image.  st: the arrays of STATE_KEYS; cand_val / cand_idx: [n_img·R, C].  emb: None or
     dict(embed [V, d], pos_table [rows, d], scale, y [n_img·R, d]) — y is updated in place as the embedding tail does.
-    Returns (new state, per-image event dicts)."""
+    `select(cv, ci, cumul, has_eos, t) -> (parent, word, lp)`: another selection in place of select_image (G = 1), for
+    the state update alone.  Returns (new state, per-image event dicts)."""
     n_img, R, T = st["tokens"].shape
     assert R == G * kg
     t = int(st["pos"][0])
@@ -92,8 +93,13 @@ def step(st: dict, cand_val, cand_idx, G: int, kg: int, lam: float, eos: int, em
     events, alive_any = [], False
     for b in range(n_img):
         rows = slice(b * R, (b + 1) * R)
-        parent, word, lp, grow, ev = select_image(np.asarray(cand_val)[rows], np.asarray(cand_idx)[rows],
-                                                  st["cumul"][rows], st["has_eos"][rows], t, G, kg, lam)
+        if select is None:
+            parent, word, lp, grow, ev = select_image(np.asarray(cand_val)[rows], np.asarray(cand_idx)[rows],
+                                                      st["cumul"][rows], st["has_eos"][rows], t, G, kg, lam)
+        else:
+            parent, word, lp = select(np.asarray(cand_val)[rows], np.asarray(cand_idx)[rows], st["cumul"][rows],
+                                      st["has_eos"][rows], t)
+            grow, ev = [0 if t > 0 and st["has_eos"][b * R + int(q)] else 1 for q in parent], {}
         ev = dict(ev, parent=parent, word=word, grow=grow)
         for r in range(R):
             par = int(parent[r])
