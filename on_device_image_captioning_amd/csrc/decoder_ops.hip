@@ -9,39 +9,21 @@
 //   dec_embed_kernel         y = embed[tok]·sqrt(d) + pos_table[pos]
 //   dynexp_step_kernel       DynamicExpansionBlock for the newest row (layers.py:152-204)
 //   cross_attn_step_kernel   MultiHeadAttention against per-image cached K/V (layers.py:266-295)
-//   logsoftmax_topk_kernel   log_softmax over the vocabulary + top-k (captioning_model.py:162-170)
+//   logsoftmax_topk_kernel   log_softmax over the vocabulary + top-k (captioning_model.py:162-170); <false>: top-k alone
+//   logsoftmax_sample_kernel log_softmax + k draws without replacement (Gumbel top-k)
+//   ensemble_logprob_kernel  log of the mean of the models' softmaxes
 //   beam_step_kernel         candidate masking, k·k selection, prefix/ancestor re-gather (:172-223)
 //   group_beam_step_kernel   the same step for diverse (group) beam search: groups choose in turn, Hamming penalty
 //   require_beam_step_kernel the same step for required words: 2^C banks of beams, one per set of words mentioned so far
 //   beam_finalize_kernel     length-normalised ranking (:225-227)
-#include "odic_common.h"
+// The row kernels (the three above that work on vocabulary rows) rank and reduce with row_select.h.
+#include "row_select.h"
 
 namespace {
 
 constexpr int MAX_T = 128;     // max decode positions supported by the LDS scratch below
 constexpr int MAX_E = 32;      // max expansion vectors per position
 constexpr int MAX_K = 16;      // max beam size
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < nw; ++i) t += red[i];
-  return t;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float t = red[0];
-  for (int i = 1; i < nw; ++i) t = fmaxf(t, red[i]);
-  return t;
-}
 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dec_embed_kernel(const long long* __restrict__ tokens,
@@ -420,18 +402,14 @@ __global__ __launch_bounds__(256) void cross_attn_step_kernel(const float* __res
 //   3. in the Σexp pass every element >= tau (k .. a dozen of them) is appended to a candidate list in LDS;
 //   4. wave 0 picks the k best of the candidates: k rounds of a wave arg-max over (value, lower index).
 // That is ~60 VALU operations per thread and k+1 shuffle chains, against ~1000 for per-thread sorted lists.  A row
-// whose candidate list would overflow (k > 8 wave maxima, or hundreds of equal values) takes k rounds of a block-wide
-// arg-max instead — exact, just slower.
+// whose candidate list would overflow (k > 8 wave maxima, or hundreds of equal values) takes block_ranked_topk
+// (row_select.h) over a streaming scan instead — exact, just slower.
 // `top_val` / `top_idx` ([k]); logp (optional): the full log-prob row.
-// The three one-trip `for (once …)` loops and the first and last barrier do no work.  They are what is left of the
-// multi-row form this kernel was measured in (commit d9f7de9): with them hipcc emits that commit's instruction stream
-// for both instantiations; without a loop it lays the blocks out differently (a few instructions, one SGPR), without
-// the barriers the stream is shorter.  Take them out together with an end-to-end measurement of the search step.
 // ---------------------------------------------------------------------------------------------
 constexpr int TOPK_CAP = 128;          // candidates (two per lane of the selecting wave)
 struct TopkShared {
   float red[16]; float red2[16]; int cnt; float cv[TOPK_CAP]; int ci[TOPK_CAP];
-  float bv[16]; int bi[16];
+  ArgmaxSlots<8> win;                    // (512 threads)
 };
 
 template <int NTH, bool NORM>
@@ -439,6 +417,7 @@ __device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x,
                                                     float* top_val, int* top_idx, int V, int k, TopkShared& sh) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NPT = 10240 / NTH, NWV = NTH / 64;
+  static_assert(NWV == 8, "TopkShared::win");
   const bool small = V <= NPT * NTH;
   float xv[NPT];
   float tm = -INFINITY;
@@ -446,19 +425,14 @@ __device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x,
 #pragma unroll
     for (int u = 0; u < NPT; ++u) { const int i = tid + u * NTH; xv[u] = i < V ? x[i] : -INFINITY; }
   }
-  for (int once = 0; once < 1; ++once) {             // (pins hipcc's block layout, see above)
-    if (small) {
+  if (small) {
 #pragma unroll
-      for (int u = 0; u < NPT; ++u) tm = fmaxf(tm, xv[u]);
-    } else {
-      for (int i = tid; i < V; i += NTH) tm = fmaxf(tm, x[i]);
-    }
+    for (int u = 0; u < NPT; ++u) tm = fmaxf(tm, xv[u]);
+  } else {
+    for (int i = tid; i < V; i += NTH) tm = fmaxf(tm, x[i]);
   }
-  __syncthreads();                                   // (no work: see above)
-  for (int once = 0; once < 1; ++once) {             // (pins hipcc's block layout)
-    const float m = wave_max(tm);
-    if (lane == 0) sh.red[wave] = m;
-  }
+  tm = wave_max(tm);
+  if (lane == 0) sh.red[wave] = tm;
   if (tid == 0) sh.cnt = 0;
   __syncthreads();
   float wm[NWV];
@@ -473,7 +447,7 @@ __device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x,
     for (int i = 0; i < NWV; ++i) {                  // the element with exactly k-1 others ranked above it
       int above = 0;
 #pragma unroll
-      for (int j = 0; j < NWV; ++j) above += (wm[j] > wm[i] || (wm[j] == wm[i] && j < i)) ? 1 : 0;
+      for (int j = 0; j < NWV; ++j) above += ranks_before(wm[j], j, wm[i], i) ? 1 : 0;
       if (above == k - 1) tau = wm[i];
     }
   }
@@ -519,7 +493,7 @@ __device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x,
       if (lane < n) { c0 = sh.cv[lane]; i0 = sh.ci[lane]; }
       if (lane + 64 < n) { c1 = sh.cv[lane + 64]; i1 = sh.ci[lane + 64]; }
       for (int rd = 0; rd < k; ++rd) {
-        const bool first = c0 > c1 || (c0 == c1 && i0 < i1);
+        const bool first = ranks_before(c0, i0, c1, i1);
         float best = first ? c0 : c1; int besti = first ? i0 : i1;
         wave_argmax(best, besti);
         if (lane == 0) { top_val[rd] = best - lse; top_idx[rd] = besti; }
@@ -528,28 +502,16 @@ __device__ __forceinline__ void row_logsoftmax_topk(const float* __restrict__ x,
       }
     }
   }
-  // overflowed row (block-uniform): k rounds of a block-wide arg-max over the elements ranked below the last winner
-  for (int once = 0; once < 1; ++once) if (sh.cnt > TOPK_CAP) {            // (loop: pins hipcc's block layout)
-    float pv = INFINITY; int pi = -1;                // last winner: later rounds take (value, index) ranked after it
-    for (int rd = 0; rd < k; ++rd) {
-      float best = -INFINITY; int besti = 0x7fffffff;
+  // overflowed row (block-uniform)
+  if (sh.cnt > TOPK_CAP) {
+    block_ranked_topk<NTH>([&](float pv, int pi, float& best, int& besti) {
       for (int i = tid; i < V; i += NTH) {
         const float v = x[i];
-        const bool after = v < pv || (v == pv && i > pi);
-        if (after && (v > best || (v == best && i < besti))) { best = v; besti = i; }
+        const bool after = ranks_after(v, i, pv, pi), before = ranks_before(v, i, best, besti);
+        if (after & before) { best = v; besti = i; }
       }
-      wave_argmax(best, besti);
-      __syncthreads();
-      if (lane == 0) { sh.bv[wave] = best; sh.bi[wave] = besti; }
-      __syncthreads();
-      best = sh.bv[0]; besti = sh.bi[0];
-      for (int w = 1; w < NWV; ++w)
-        if (sh.bv[w] > best || (sh.bv[w] == best && sh.bi[w] < besti)) { best = sh.bv[w]; besti = sh.bi[w]; }
-      if (tid == 0) { top_val[rd] = best - lse; top_idx[rd] = besti; }
-      pv = best; pi = besti;
-    }
+    }, k, lse, top_val, top_idx, sh.win);
   }
-  __syncthreads();                                   // (no work: see above)
 }
 
 template <bool NORM = true>
@@ -598,10 +560,8 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
                                                                  int V, int k, unsigned long long seed,
                                                                  const int* __restrict__ pos) {
   __shared__ float red[16];
-  __shared__ float bv[16];
-  __shared__ int bi[16];
-  __shared__ int winner;
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ ArgmaxSlots<16> win;
+  const int n = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (long)n * ldl;
   const unsigned step = pos ? (unsigned)*pos : 0u;
   float tv[KM]; int ti[KM];
@@ -637,24 +597,12 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
     for (int i = tid; i < V; i += 1024) logp_out[(long)n * ldp + i] = x[i] - lse;
   for (int r = 0; r < k; ++r) {
     float best = tv[0]; int besti = ti[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(besti, o, 64);
-      if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
-    if (lane == 0) { bv[wave] = best; bi[wave] = besti; }
-    __syncthreads();
+    block_argmax<16>(best, besti, win, r);
     if (tid == 0) {
-      float b = bv[0]; int ix = bi[0];
-      for (int w = 1; w < 16; ++w)
-        if (bv[w] > b || (bv[w] == b && bi[w] < ix)) { b = bv[w]; ix = bi[w]; }
-      winner = ix;
-      top_val[(long)n * k + r] = x[ix] - lse;            // the word's log-probability, not its perturbed score
-      top_idx[(long)n * k + r] = ix;
+      top_val[(long)n * k + r] = x[besti] - lse;         // the word's log-probability, not its perturbed score
+      top_idx[(long)n * k + r] = besti;
     }
-    __syncthreads();
-    if (ti[0] == winner) {
+    if (ti[0] == besti) {
 #pragma unroll
       for (int q = 0; q + 1 < KM; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
       tv[KM - 1] = -INFINITY; ti[KM - 1] = 0x7fffffff;

@@ -9,10 +9,11 @@
 //   dynexp_seq_kernel      DynamicExpansionBlock (layers.py:152-204) for all positions of a sequence, nothing cached
 //                          in global memory
 //   token_stats_kernel     the scoring tail: per logits row the target's log-prob, Σ_v log-prob, arg-max and its
-//                          log-prob — one number per quantity instead of an [R, V] log-prob tensor
+//                          log-prob — one number per quantity instead of an [R, V] log-prob tensor (ranking
+//                          and block reductions: row_select.h)
 //   cross_attn_probs_kernel  the softmax probabilities of the cross attention themselves (where the model looked for
 //                          each word): what cross_attn_step_kernel computes in LDS, uses for P·V and discards
-#include "odic_common.h"
+#include "row_select.h"
 #include "dynexp_tiles.h"
 
 namespace {
@@ -227,42 +228,26 @@ __global__ __launch_bounds__(TS_NT) void token_stats_kernel(const float* __restr
                                                             float* __restrict__ logp_target, float* __restrict__ sum_logp,
                                                             int* __restrict__ argmax, float* __restrict__ max_logp,
                                                             int* __restrict__ status, int V) {
-  __shared__ float s_v[TS_NT / 64];
-  __shared__ int s_i[TS_NT / 64];
+  __shared__ ArgmaxSlots<TS_NT / 64> s_m;
+  __shared__ float s_e[TS_NT / 64];
   __shared__ double s_d[TS_NT / 64];
   const long row = blockIdx.x;
   const float* x = logits + row * ldl;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   float m = -INFINITY; int mi = 0x7fffffff;
   for (int i = tid; i < V; i += TS_NT) {
     const float v = x[i];
-    if (v > m || mi == 0x7fffffff) { m = v; mi = i; }
+    if (v > m || mi == 0x7fffffff) { m = v; mi = i; }   // (a thread's first element always: an all -inf or NaN row)
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(m, o, 64); const int oi = __shfl_xor(mi, o, 64);
-    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-  }
-  if (lane == 0) { s_v[wave] = m; s_i[wave] = mi; }
-  __syncthreads();
-  m = s_v[0]; mi = s_i[0];
-#pragma unroll
-  for (int w = 1; w < TS_NT / 64; ++w)
-    if (s_v[w] > m || (s_v[w] == m && s_i[w] < mi)) { m = s_v[w]; mi = s_i[w]; }
-  __syncthreads();
+  block_argmax<TS_NT / 64>(m, mi, s_m, 0);
   float se = 0.f; double sx = 0.0;
   for (int i = tid; i < V; i += TS_NT) {
     const float dv = x[i] - m;
     se += expf(dv); sx += (double)dv;
   }
-  se = wave_sum(se);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
-  if (lane == 0) { s_v[wave] = se; s_d[wave] = sx; }
-  __syncthreads();
+  const float e = block_sum(se, s_e);
+  const double dsum = block_sum(sx, s_d);     // wave 0 first, ascending: sum_logp keeps its bits
   if (tid == 0) {
-    float e = 0.f; double dsum = 0.0;
-    for (int w = 0; w < TS_NT / 64; ++w) { e += s_v[w]; dsum += s_d[w]; }
     const float lg = logf(e);                 // logsumexp = m + lg
     sum_logp[row] = (float)(dsum - (double)V * (double)lg);
     argmax[row] = mi;

@@ -118,16 +118,6 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-// arg-max of (value, index) over a wave, ties to the lower index: the order of every top-k in this library
-// (decoder_ops.hip, search_constraints.hip)
-__device__ __forceinline__ void wave_argmax(float& best, int& besti) {        // every lane ends with the winner
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(besti, o, 64);
-    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-  }
-}
 
 // exact-erf GELU (fp32 path) and a 1.5e-7-abs-error erf (Abramowitz–Stegun 7.1.26) for the bf16
 // path, where the result is rounded to 8 bits of mantissa anyway.

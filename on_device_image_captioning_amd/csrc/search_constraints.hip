@@ -7,16 +7,15 @@
 //      list, the EOS rule and the start positions j of the no-repeat rule, each setting bits with atomicOr;
 //   2. a thread keeps its 20-value slice of the row and the admissibility bit of each value in registers (V <= 10240;
 //      longer rows stream from memory and look the bitmap up again in every round);
-//   3. k rounds of a block-wide arg-max over the admissible elements ranked after the last winner — (value descending,
-//      word ascending), wave_argmax's rule — as the overflow path of row_logsoftmax_topk does.  There is no candidate
-//      list, so any number of ties is exact for every k <= 16.
+//   3. block_ranked_topk (row_select.h), the routine the overflow path of row_logsoftmax_topk calls too: k rounds of a
+//      block-wide arg-max over the elements ranked after the last winner, here with a scan that skips the inadmissible
+//      ones.  There is no candidate list, so any number of ties is exact for every k <= 16.
 // A finished row (row_valid == 0) builds no bitmap and gets what odic_topk_rows gives it.
-#include "odic_common.h"
+#include "row_select.h"
 
 namespace {
 
 constexpr int SC_NTH = 512;
-constexpr int SC_NWV = SC_NTH / 64;
 constexpr int SC_NPT = 10240 / SC_NTH;              // values a thread keeps in registers
 constexpr int SC_MAX_V = 32768 * 8;                 // the bitmap may take 32 KB of LDS
 constexpr int SC_MAX_K = 16;                        // odic_beam_step's limits
@@ -37,9 +36,8 @@ __global__ __launch_bounds__(SC_NTH) void topk_rows_constrained_kernel(const flo
                                                                        ConstraintParams c, float* __restrict__ top_val,
                                                                        int* __restrict__ top_idx, int V, int k) {
   extern __shared__ unsigned bm[];                  // bit w set: word w is inadmissible
-  __shared__ float bv[2][SC_NWV];
-  __shared__ int bi[2][SC_NWV];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ ArgmaxSlots<SC_NTH / 64> win;
+  const int tid = threadIdx.x;
   const int n = blockIdx.x;
   const float* x = logp + (long)n * ldl;
   const int nw = (V + 31) >> 5;
@@ -73,36 +71,23 @@ __global__ __launch_bounds__(SC_NTH) void topk_rows_constrained_kernel(const flo
       if (in && !((bm[i >> 5] >> (i & 31)) & 1u)) adm |= 1u << u;
     }
   }
-  float pv = INFINITY; int pi = -1;                 // last winner: a round takes (value, index) ranked after it
-  for (int rd = 0; rd < k; ++rd) {
-    float best = -INFINITY; int besti = 0x7fffffff;
+  // one call of scan: the thread's best admissible element ranked after the last winner (pv, pi)
+  block_ranked_topk<SC_NTH>([&](float pv, int pi, float& best, int& besti) {
     if (small) {
 #pragma unroll
       for (int u = 0; u < SC_NPT; ++u) {
         const float v = xv[u];
         const int i = tid + u * SC_NTH;
-        const bool after = v < pv || (v == pv && i > pi);
-        if (((adm >> u) & 1u) && after && (v > best || (v == best && i < besti))) { best = v; besti = i; }
+        const bool after = ranks_after(v, i, pv, pi), before = ranks_before(v, i, best, besti);
+        if (((adm >> u) & 1u) & after & before) { best = v; besti = i; }
       }
     } else {
       for (int i = tid; i < V; i += SC_NTH) {
         const float v = x[i];
-        const bool after = v < pv || (v == pv && i > pi);
-        if (after && !((bm[i >> 5] >> (i & 31)) & 1u) && (v > best || (v == best && i < besti))) { best = v; besti = i; }
+        if (ranks_after(v, i, pv, pi) && !((bm[i >> 5] >> (i & 31)) & 1u) && ranks_before(v, i, best, besti)) { best = v; besti = i; }
       }
     }
-    wave_argmax(best, besti);
-    if (lane == 0) { bv[rd & 1][wave] = best; bi[rd & 1][wave] = besti; }
-    __syncthreads();                                // (two buffers: round rd+1 writes while a slow wave still reads rd)
-    best = bv[rd & 1][0]; besti = bi[rd & 1][0];
-#pragma unroll
-    for (int w = 1; w < SC_NWV; ++w) {
-      const float ov = bv[rd & 1][w]; const int oi = bi[rd & 1][w];
-      if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
-    if (tid == 0) { top_val[(long)n * k + rd] = best; top_idx[(long)n * k + rd] = besti; }
-    pv = best; pi = besti;
-  }
+  }, k, 0.f, top_val + (long)n * k, top_idx + (long)n * k, win);
 }
 
 }  // namespace

@@ -295,7 +295,8 @@ def test_logsoftmax_topk(ops):
     assert_close(tv, wv, 2e-6, "topk values")
 
 
-@pytest.mark.parametrize("V,k", [(10000, 3), (10000, 8), (10000, 12), (37, 5), (12000, 4), (513, 16)])
+@pytest.mark.parametrize("V,k", [(10000, 3), (10000, 8), (10000, 12), (37, 5), (12000, 4), (513, 16),
+                                 (10241, 9), (10241, 16)])
 def test_logsoftmax_topk_threshold_selection_edge_cases(ops, V, k):
     """The top-k is chosen among the elements >= the k-th largest wave maximum (decoder_ops.hip); rows on which that
     candidate list overflows — all-equal rows, hundreds of exact ties at the top, k above the wave count — and rows

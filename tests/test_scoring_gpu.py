@@ -119,6 +119,7 @@ def test_token_stats(ops):
     x = rnd(R_, V, seed=1, scale=3.0)
     x[2, 17] = x[2, 4000] = x[2].max() + 1.0              # an exact tie: the lower index wins
     x[5] = 0.25                                           # an all-equal row → index 0
+    x[6, 0] = x[6, V // 2] = x[6, V - 1] = x[6].max() + 1.0     # the maximum three times: first, middle, last index
     tgt = torch.randint(0, V, (R_,), generator=torch.Generator().manual_seed(2))
     tgt[3], tgt[7] = V, -1                                # outside the vocabulary: flagged, log-prob 0
     want = torch.log_softmax(x.double(), -1)
@@ -135,7 +136,7 @@ def test_token_stats(ops):
     assert float((sl.cpu().double() - want.sum(-1)).abs().max()) <= 2e-6 * want.sum(-1).abs().max().item()
     assert float((ml.cpu().double() - want.max(-1).values).abs().max()) <= 2e-6 * scale
     order = torch.argsort(x.double(), dim=-1, descending=True, stable=True)[:, 0]
-    assert torch.equal(am.cpu().long(), order) and int(am[2]) == 17 and int(am[5]) == 0
+    assert torch.equal(am.cpu().long(), order) and int(am[2]) == 17 and int(am[5]) == 0 and int(am[6]) == 0
     # without targets: no status, the same statistics
     sl2, ml2 = f(), f()
     am2 = torch.empty_like(am)
@@ -145,6 +146,24 @@ def test_token_stats(ops):
     tgt[3], tgt[7] = 0, 1
     ops.token_stats(x.to(DEV), V, tgt.to(DEV), lp, sl, am, ml, status, R_, V)
     assert int(status) == 0
+    # a row barely longer than the 256-thread block, its maximum at the first index (thread 0, wave 0), a middle one
+    # (150: wave 2) and the last (299: thread 43, wave 0 again, the thread's second element)
+    R_, V = 3, 300
+    x = rnd(R_, V, seed=4, scale=3.0)
+    x[1, 0] = x[1, 150] = x[1, V - 1] = x[1].max() + 1.0
+    tgt = torch.tensor([7, V - 1, 150])
+    want = torch.log_softmax(x.double(), -1)
+    lp, sl, ml = f()[:R_], f()[:R_], f()[:R_]
+    am = torch.empty(R_, dtype=torch.int32, device=DEV)
+    status.zero_()
+    ops.token_stats(x.to(DEV), V, tgt.to(DEV), lp, sl, am, ml, status, R_, V)
+    scale = want.abs().max().item()
+    assert int(status) == 0
+    assert float((lp.cpu().double() - want[torch.arange(R_), tgt]).abs().max()) <= 2e-6 * scale
+    assert float((sl.cpu().double() - want.sum(-1)).abs().max()) <= 2e-6 * want.sum(-1).abs().max().item()
+    assert float((ml.cpu().double() - want.max(-1).values).abs().max()) <= 2e-6 * scale
+    order = torch.argsort(x.double(), dim=-1, descending=True, stable=True)[:, 0]
+    assert torch.equal(am.cpu().long(), order) and int(am[1]) == 0
 
 
 def test_dec_embed_seq(ops):

@@ -184,6 +184,33 @@ def test_every_constraint_equals_the_numpy_model_exactly_in_guarded_buffers(ops,
         assert np.array_equal(gi[rows], want_plain[1][rows]) and np.array_equal(bits(gv[rows]), bits(want_plain[0][rows])), what
 
 
+@pytest.mark.parametrize("V", (37, 513, 10241))
+@pytest.mark.parametrize("k", (1, 9, 16))
+def test_tied_rows_equal_the_numpy_model_exactly(ops, V, k):
+    """An all-equal row (every round a V-way tie: indices ascending, the inadmissible ones skipped) and rows on a coarse
+    grid (randn().round(): ties at every rank), with and without constraints.  V = 37 is shorter than the block, at
+    V = 513 most register slots of a thread are empty, V = 10241 streams the row and looks the bitmap up per round."""
+    _, tokens, _, banned = inputs(V)
+    tokens = tokens[:3]                                               # row 2: the prefix whose bigrams repeat
+    banned = np.concatenate([banned, np.array([0, 1, V - 1], np.int32)])      # the first two and the last word
+    assert banned.size + T + k <= V
+    g = torch.Generator().manual_seed(V)
+    grid = lambda: torch.randn(V, generator=g).round().numpy().astype(F)      # noqa: E731
+    logp = np.stack([np.full(V, -0.25, F), grid(), grid()])
+    d = lambda a: torch.from_numpy(a).to(DEV)                         # noqa: E731
+    tok, bn = d(tokens), d(banned)
+    pos = torch.full((1,), POS, dtype=torch.int32, device=DEV)
+    tv = torch.empty(3, k, dtype=torch.float32, device=DEV)
+    ti = torch.empty(3, k, dtype=torch.int32, device=DEV)
+    for what, kw in (("none", {}), ("all", dict(banned=bn, no_repeat_ngram=2, min_words=MINW))):
+        ops.topk_rows_constrained(d(logp), ops.search_constraints(tok, pos, T, EOS, **kw), tv, ti, k)
+        wv, wi = SC.topk_rows_constrained(logp, k, tokens, POS, None, banned.tolist() if kw else [],
+                                          kw.get("no_repeat_ngram", 0), kw.get("min_words", 0), EOS)
+        assert np.array_equal(ti.cpu().numpy(), wi), f"V={V} k={k} {what}: indices\n{ti.cpu().numpy()}\n{wi}"
+        assert np.array_equal(bits(tv.cpu().numpy()), bits(wv)), f"V={V} k={k} {what}: values"
+    assert wi[0, 0] == 3 and (np.diff(wi[0]) > 0).all()               # all equal: words 0, 1 banned, 2 = EOS too early
+
+
 def test_the_inputs_reach_every_case_the_selection_has():
     """From the model alone: what the comparison above covers."""
     seen = dict(top1_banned=0, eos_removed_and_back=0, two_words_by_two_starts=0, prefix_too_short=0, ties_over_128=0,
