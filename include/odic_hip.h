@@ -111,6 +111,15 @@ typedef struct odic_gemm_args {
    *     out = act(rstd[m]·(alpha·A·W'ᵀ − mean[m]·ln_colsum) + bias') + residual
    *         = act(LayerNorm(A; gamma, beta, ln_eps)·Wᵀ + bias) + residual
    * with mean/rstd the moments of row m of the RAW fp32 A, accumulated from the operand fragments.
+   * Neither Σa² − (Σa)²/K nor A·W'ᵀ − mean·ln_colsum is formed as written: every K-slice of a row is
+   * centred on a mean of its own elements before the product, the slices' moments are merged
+   * pairwise, and the column sums the centring needs are taken per slice from the W' fragments.
+   * So ln_colsum is NOT the operand of a subtraction any more.  It is (1) the flag that selects the
+   * fold (non-NULL) and (2) with alpha != 1 only, the factor of the term (alpha − 1)·mean[m]·ln_colsum[n]
+   * that makes the result the formula above for any alpha; with alpha = 1 (every caller in this
+   * project) its N values are not read.  Accuracy on offset rows (randn ± 30), constant,
+   * zero, single-outlier and near-eps rows is pinned by tests/test_decoder_hard_rows_gpu.py: every
+   * such row within 3e-5 of the output scale against fp64, at every tile_cfg.
    * Replaces the separate norm_1/2/3 + dec_reduce_norm launches of the decoder step
    * (layers.py:225,228,232; End_ExpansionNet_v2.py:135).  NULL = plain GEMM. */
   const float* ln_colsum; float ln_eps;

@@ -142,11 +142,21 @@ __global__ __launch_bounds__(256) void gemm_f32_nt_kernel(Params p) {
 // K-order inside an MFMA is permuted (slot (kq, s) <-> k = k0 + 4·kq + s) identically on both
 // operands, which only changes the summation order.
 //
-// Folded LayerNorm (FOLD): with W' = W·diag(gamma), colsum[n] = Σ_k W'[n][k] and
-// bias' = bias + W·beta prepared by the caller,
-//     LayerNorm(a)·Wᵀ + bias = rstd·(a·W'ᵀ − mean·colsum) + bias'
-// so the product runs on the RAW rows and only the epilogue needs the row moments — which every
-// wave accumulates for free from the A fragments it loads anyway (Σa, Σa² over its K-slice).
+// Folded LayerNorm (FOLD): with W' = W·diag(gamma) and bias' = bias + W·beta prepared by the caller,
+//     LayerNorm(a)·Wᵀ + bias = rstd·((a − mean)·W'ᵀ) + bias'
+// and only the epilogue knows the row's mean.  Neither Σa² − (Σa)²/K nor a·W'ᵀ − mean·colsum is formed: both cancel
+// in fp32 (a row of randn + 30 loses three digits in the first, a constant row shows the second magnified by
+// rstd = 1/sqrt(eps)).  Instead every wave centres its K-slice s of the row on c_s, the mean of the first round of
+// loads it holds in registers anyway (the whole slice when the slice is one round; two shuffles), runs the MFMAs on
+// a − c_s, and accumulates Σ(a − c_s), Σ(a − c_s)² and the slice's column sums cs_s[n] = Σ_{k in s} W'[n][k] from the
+// same fragments.  The epilogue merges the slices' (count, mean, M2) with the pairwise update of Chan et al. and adds
+// what the centring left out:
+//     (a − mean)·W'ᵀ[n] = Σ_s ( P_s[n] + (c_s − mean)·cs_s[n] ),   P_s = the slice's partial product on a − c_s.
+// c_s − mean is of the size of the row's spread, never of its offset, so nothing large is subtracted anywhere; a
+// constant row gives a − c_s = 0 and c_s = mean exactly, hence bias' exactly.  (c_s is a mean of min(16·UN, slice)
+// elements — 16 at the least, 32 or 64 wherever the slice is that long — not a pivot element: a single outlier cannot
+// turn a well-conditioned row into an ill-conditioned one.  A centre taken from a separate float4 load of the slice's
+// first four elements, which needs no shuffle in front of the first MFMA, was measured and is slower: DESIGN.md §4.2.)
 // ---------------------------------------------------------------------------------------------
 //
 // Decomposition (launch_skinny): grid = (N/16 column tiles) x (row blocks); a block owns MT row tiles starting at
@@ -161,7 +171,7 @@ __global__ __launch_bounds__(256) void gemm_f32_nt_kernel(Params p) {
 // what lets two or three of the 512-thread blocks of decomposition 2 share a CU.
 template <int MTW, int UN, bool FOLD, typename OutT, int MAXT, bool ONE>
 __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int kslice, int KS, int MT) {
-  extern __shared__ float red[];                   // [KS][MT][4][64] partial tiles (+ [KS][MT*16][2] row sums if FOLD)
+  extern __shared__ float red[];                   // [KS][MT][4][64] partial tiles; FOLD: see the pointers behind the K loop
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ks = wave % KS, ms = wave / KS;
@@ -175,9 +185,9 @@ __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int ksl
   const int tb = blockIdx.y * MT;                   // first row tile of this block
 
   f32x4_t acc[MTW];
-  float sx[MTW], sxx[MTW];
+  float ctr[MTW], sd[MTW], sdd[MTW], sw = 0.f;     // FOLD: slice centre, Σ(a − ctr), Σ(a − ctr)², Σ of this lane's W'
 #pragma unroll
-  for (int i = 0; i < MTW; ++i) { acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; sx[i] = 0.f; sxx[i] = 0.f; }
+  for (int i = 0; i < MTW; ++i) { acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; ctr[i] = 0.f; sd[i] = 0.f; sdd[i] = 0.f; }
 
   const bool wn_ok = (n0 + fr) < p.N;
   const float* wrow = W + (long)min(n0 + fr, p.N - 1) * p.ldw + 4 * fq;
@@ -190,6 +200,7 @@ __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int ksl
     arow[i] = A + (long)min(m, p.M - 1) * p.lda + 4 * fq;
   }
   constexpr int NBUF = ONE ? 1 : 2;
+  constexpr int STEP = 16 * UN;
   float4 w4[NBUF][UN], a4[NBUF][UN][MTW];
   auto load_round = [&](int buf, int k) {            // addresses clamped, values masked in compute()
 #pragma unroll
@@ -200,19 +211,40 @@ __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int ksl
       for (int i = 0; i < MTW; ++i) a4[buf][u][i] = *(const float4*)(arow[i] + kk);
     }
   };
+  // reciprocals of the first round's and the slice's element counts: wave-uniform, formed while the loads are in flight
+  const float inv_first = 1.0f / (float)max(min(STEP, k_end - k_begin), 1), inv_nw = 1.0f / (float)max(k_end - k_begin, 1);
+  auto centre = [&](int k) {                         // FOLD: ctr = mean of the slice's first round (buffer 0), per row
+#pragma unroll
+    for (int i = 0; i < MTW; ++i) {
+      float s = 0.f;
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        const float4 a = a4[0][u][i];
+        if (k + 16 * u < k_end) s += (a.x + a.y) + (a.z + a.w);
+      }
+      s += __shfl_xor(s, 16, 64); s += __shfl_xor(s, 32, 64);
+      float c = am_ok[i] ? s * inv_first : 0.f;
+      asm volatile("" : "+v"(c));          // (its own register: two row tiles' centres in one register pair make the packed
+      ctr[i] = c;                          //  a − ctr take its HIGH half, the `op_sel` form — tests/test_isa_lint.py)
+    }
+  };
   auto compute = [&](int buf, int k) {
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const bool live = k + 16 * u < k_end;
       float4 w = w4[buf][u];
       if (!live || !wn_ok) w = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (FOLD) { if (ms == 0) sw += (w.x + w.y) + (w.z + w.w); }
 #pragma unroll
       for (int i = 0; i < MTW; ++i) {
         float4 a = a4[buf][u][i];
+        if constexpr (FOLD) { a.x -= ctr[i]; a.y -= ctr[i]; a.z -= ctr[i]; a.w -= ctr[i]; }
         if (!live || !am_ok[i]) a = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (FOLD) {
-          sx[i] += (a.x + a.y) + (a.z + a.w);
-          sxx[i] += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+          sd[i] += (a.x + a.y) + (a.z + a.w);
+          // (an fma chain, not a sum of products: hipcc's SLP pass turns x·x + y·y of a centred pair into a packed add with
+          //  `op_sel` source selection — tests/test_isa_lint.py)
+          sdd[i] = fmaf(a.x, a.x, fmaf(a.y, a.y, fmaf(a.z, a.z, fmaf(a.w, a.w, sdd[i]))));
         }
         acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc[i], 0, 0, 0);
         acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc[i], 0, 0, 0);
@@ -221,13 +253,17 @@ __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int ksl
       }
     }
   };
-  constexpr int STEP = 16 * UN;
   if constexpr (ONE) {
-    if (t0 < MT && k_begin < k_end) { load_round(0, k_begin); compute(0, k_begin); }
+    if (t0 < MT && k_begin < k_end) {
+      load_round(0, k_begin);
+      if constexpr (FOLD) centre(k_begin);
+      compute(0, k_begin);
+    }
   } else if (t0 < MT && k_begin < k_end) {
     load_round(0, k_begin);
     for (int k = k_begin; k < k_end; k += 2 * STEP) {
       if (k + STEP < k_end) load_round(NBUF - 1, k + STEP);
+      if constexpr (FOLD) { if (k == k_begin) centre(k); }
       compute(0, k);
       if (k + STEP < k_end) {
         if (k + 2 * STEP < k_end) load_round(0, k + 2 * STEP);
@@ -242,17 +278,25 @@ __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int ksl
       for (int j = 0; j < 4; ++j) red[((ks * MT + t0 + i) * 4 + j) * 64 + lane] = acc[i][j];
     }
   }
-  float* rsum = red + KS * MT * 256;               // [KS][MT*16][2]
+  float* rsum = red + KS * MT * 256;               // [KS][MT*16][3] per slice and row: centre, mean, M2 about that mean
+  float* csl = rsum + KS * MT * 48;                // [KS][16]       per slice and column: Σ_k W'
+  float* mom = csl + KS * 16;                      // [MT*16][2]     per row: mean, rstd
   if constexpr (FOLD) {
 #pragma unroll
     for (int i = 0; i < MTW; ++i) {
-      float a = sx[i], b = sxx[i];
+      float a = sd[i], b = sdd[i];
       a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
       b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
       if (fq == 0 && t0 + i < MT) {
-        rsum[((ks * MT + t0 + i) * 16 + fr) * 2 + 0] = a;
-        rsum[((ks * MT + t0 + i) * 16 + fr) * 2 + 1] = b;
+        float* r = rsum + ((ks * MT + t0 + i) * 16 + fr) * 3;
+        r[0] = ctr[i];
+        r[1] = ctr[i] + a * inv_nw;
+        r[2] = fmaxf(b - a * a * inv_nw, 0.f);
       }
+    }
+    if (ms == 0) {                                   // (the waves of the other row tiles hold the same W' fragments)
+      sw += __shfl_xor(sw, 16, 64); sw += __shfl_xor(sw, 32, 64);
+      if (fq == 0) csl[ks * 16 + fr] = sw;
     }
   }
   __syncthreads();
@@ -260,30 +304,48 @@ __global__ __launch_bounds__(MAXT) void gemm_f32_skinny_kernel(Params p, int ksl
   const float* bias = p.bias ? p.bias + bz * p.strideBias : nullptr;
   const float* resid = p.residual ? p.residual + bz * p.strideR : nullptr;
   OutT* out = (OutT*)p.out + bz * p.strideC;
-  if constexpr (FOLD) {                              // row moments: combine the K-slices once per row, not per element
-    const float inv_k = 1.0f / (float)p.K;
-    float mean = 0.f, rstd = 0.f;
+  if constexpr (FOLD) {                              // row moments: merge the K-slices once per row, not per element
     if (tid < MT * 16) {
-      float s1 = 0.f, s2 = 0.f;
-      for (int w = 0; w < KS; ++w) { s1 += rsum[(w * MT * 16 + tid) * 2]; s2 += rsum[(w * MT * 16 + tid) * 2 + 1]; }
-      mean = s1 * inv_k;
-      rstd = rsqrtf(fmaxf(s2 * inv_k - mean * mean, 0.f) + p.ln_eps);
+      // the pairwise update over all slices at once, free of divisions: mean = m_0 + Σ n_w·(m_w − m_0) / K (differences
+      // of slice means, so a constant row keeps mean = m_w exactly), M2 = Σ (M2_w + n_w·(m_w − mean)²)
+      const float inv_k = 1.0f / (float)p.K, m0 = rsum[tid * 3 + 1];
+      float s = 0.f, m2 = 0.f;
+      for (int w = 1; w < KS; ++w) {
+        const int cnt = min(p.K, (w + 1) * kslice) - w * kslice;
+        if (cnt > 0) s += (float)cnt * (rsum[(w * MT * 16 + tid) * 3 + 1] - m0);      // (an empty slice holds zeros)
+      }
+      const float mean = m0 + s * inv_k;
+      for (int w = 0; w < KS; ++w) {
+        const int cnt = min(p.K, (w + 1) * kslice) - w * kslice;
+        float* r = rsum + (w * MT * 16 + tid) * 3;
+        const float dm = r[1] - mean;
+        if (cnt > 0) m2 += r[2] + (float)cnt * dm * dm;
+        r[0] -= mean;                                // what the slice's centring left out, per unit of its column sums
+      }
+      mom[tid * 2] = mean;
+      mom[tid * 2 + 1] = rsqrtf(m2 * inv_k + p.ln_eps);
     }
-    __syncthreads();
-    if (tid < MT * 16) { rsum[tid * 2] = mean; rsum[tid * 2 + 1] = rstd; }
     __syncthreads();
   }
   for (int e = tid; e < MT * 256; e += blockDim.x) {
     const int i = e >> 8, j = (e >> 6) & 3, l = e & 63;
-    float v = 0.f;
-    for (int w = 0; w < KS; ++w) v += red[((w * MT + i) * 4 + j) * 64 + l];
     const int r16 = (l >> 4) * 4 + j;
+    float v = 0.f;
+    if constexpr (FOLD) {                            // partial products and what the centring left out, one pass over the slices
+      for (int w = 0; w < KS; ++w)                   // (every row and column of a tile has its rsum / csl entry, live or not)
+        v += red[((w * MT + i) * 4 + j) * 64 + l] + rsum[((w * MT + i) * 16 + r16) * 3] * csl[w * 16 + (l & 15)];
+    } else {
+      for (int w = 0; w < KS; ++w) v += red[((w * MT + i) * 4 + j) * 64 + l];
+    }
     const int row = (tb + i) * 16 + r16, col = n0 + (l & 15);
     if (row < p.M && col < p.N) {
-      v *= p.alpha;
       if constexpr (FOLD) {
-        const float mean = rsum[(i * 16 + r16) * 2], rstd = rsum[(i * 16 + r16) * 2 + 1];
-        v = (v - mean * p.ln_colsum[col]) * rstd;
+        const float mean = mom[(i * 16 + r16) * 2], rstd = mom[(i * 16 + r16) * 2 + 1];
+        v *= p.alpha;                                // alpha·a·W'ᵀ − mean·colsum = alpha·(a − mean)·W'ᵀ + (alpha − 1)·mean·colsum:
+        if (p.alpha != 1.0f) v += (p.alpha - 1.0f) * mean * p.ln_colsum[col];      // the header's formula for any alpha
+        v *= rstd;
+      } else {
+        v *= p.alpha;
       }
       if (bias) v += p.bias_axis ? bias[row] : bias[col];
       v = apply_act<false>(v, p.act);
@@ -305,8 +367,8 @@ static void launch_skinny(const Params& p, int out_dtype, int batch, hipStream_t
   if (KS < 1) KS = 1;
   const int kslice = ((p.K + KS - 1) / KS + 15) / 16 * 16;
   dim3 grid((p.N + 15) / 16, (MT_all + MT - 1) / MT, batch), block(64 * KS * MS);
-  const size_t shmem = (size_t)(KS * MT * 256 + KS * MT * 32) * sizeof(float);
   const bool fold = p.ln_colsum != nullptr;
+  const size_t shmem = (size_t)(KS * MT * 256 + KS * MT * 32 + (fold ? KS * MT * 16 + KS * 16 + MT * 32 : 0)) * sizeof(float);
   constexpr int MAXT = 64 * MAXW;
   const bool one = kslice <= 16 * UN;
 #define ODIC_SKINNY_GO(FOLD_, OUT_, ONE_)                                                                          \
