@@ -577,7 +577,11 @@ int odic_dynexp_seq(const float* lin, int64_t ldlin, const float* qexp, const fl
  *   argmax     int32 [R]  (ties → lower index, as odic_logsoftmax_topk);  max_logp fp32 [R] its log-probability
  *   status     int32 scalar, required with target: bit 0 is OR-ed in when some target lies outside [0, V); that row's
  *              logp_target is 0 and nothing is read out of bounds.  The caller clears it.
- * All outputs are compact; logits columns [V, ldl) are not read. */
+ * All outputs are compact; logits columns [V, ldl) are not read.
+ * Log-probs are formed as (x − max) − log Σ exp(x − max), as torch forms them: the error does not grow with |logsumexp|
+ * (odic_logsoftmax_topk's does).  A masked word (logit -inf) has log-prob exactly -inf, as a target too; a row with one
+ * has sum_logp exactly -inf; argmax / max_logp ignore it.  A row without a finite logit, or with a NaN, is outside the
+ * contract. */
 int odic_token_stats(const float* logits, int64_t ldl, const int64_t* target, float* logp_target, float* sum_logp,
                      int32_t* argmax, float* max_logp, int32_t* status, int32_t R, int32_t V, void* stream);
 
@@ -622,7 +626,13 @@ int odic_cross_attn_probs(const float* q, int64_t ldq, const float* kv, int64_t 
 /* log_softmax over V + top-k (captioning_model.py:126-127,162-170).  logits fp32 [N, V] (ldl);
  * writes logp_out fp32 [N, V] (ldp) if non-NULL, top_val fp32 [N,k] / top_idx int32 [N,k] sorted
  * descending (ties: lower index first).  k <= 16.  logp_out columns [V, ldp) are left untouched, top_val / top_idx are compact,
- * logits columns [V, ldl) are not read (test_logsoftmax_topk_leading_dimensions). */
+ * logits columns [V, ldl) are not read (test_logsoftmax_topk_leading_dimensions).
+ * Log-probs are formed as x − (max + log Σ exp(x − max)): one rounding of the log-sum-exp is shared by the whole row, so
+ * the error is bounded by 6e-6 + 2^-23·(|logsumexp| + |log-prob|) and grows with the offset of the logits
+ * (odic_token_stats uses the other form; tests/vocab_rows_refs.py derives both bounds).
+ * A masked word (logit -inf) has log-prob exactly -inf and ranks behind every finite word; a row with fewer than k finite
+ * words fills the remaining slots with masked words by ascending index, top_val -inf.  A row without a finite logit, or
+ * with a NaN, is outside the contract (every entry point below says the same of its rows). */
 int odic_logsoftmax_topk(const float* logits, int64_t ldl, float* logp_out, int64_t ldp,
                          float* top_val, int32_t* top_idx, int32_t N, int32_t V, int32_t k,
                          void* stream);
@@ -633,19 +643,30 @@ int odic_logsoftmax_topk(const float* logits, int64_t ldl, float* logp_out, int6
  * their log-probabilities; logp_out as in odic_logsoftmax_topk.  Noise = Philox4x32-10(seed; row, word/4,
  * *pos): `pos` (device int32 scalar, may be NULL = 0) separates the steps of a captured graph.  Padding as for
  * odic_logsoftmax_topk: logp_out columns [V, ldp) left untouched, top_val / top_idx compact
- * (test_logsoftmax_sample_leading_dimensions). */
+ * (test_logsoftmax_sample_leading_dimensions).  Log-probs in odic_logsoftmax_topk's form, with its bound.
+ * A masked word (logit -inf) has probability 0 and is never drawn while a word of non-zero probability is left.  A row
+ * with m < k finite words gives those m words in draw order, then the masked words with the lowest indices in ascending
+ * order, each with top_val -inf: every top_idx lies in [0, V) and nothing outside the row is read.  Rows with at least k
+ * finite words are not affected by that rule.  A row without a finite logit, or with a NaN, is outside the contract. */
 int odic_logsoftmax_sample(const float* logits, int64_t ldl, float* logp_out, int64_t ldp, float* top_val,
                            int32_t* top_idx, int32_t N, int32_t V, int32_t k, uint64_t seed,
                            const int32_t* pos, void* stream);
 
 /* Ensemble step distribution (ensemble_captioning_model.py:66-83): `logits` is a HOST array of M (<= 8)
  * device pointers to fp32 [N, V] logits (row pitch ldl); out[n][v] = log(mean_m softmax(logits_m[n])[v]).  out columns
- * [V, ldo) are left untouched, logits columns [V, ldl) are not read. */
+ * [V, ldo) are left untouched, logits columns [V, ldl) are not read.
+ * The probabilities are averaged in fp32: out is exactly -inf where every member masks the word (logit -inf) AND where
+ * every member's probability underflows (below about 2^-150, i.e. a word some 104 below each member's maximum); between
+ * 2^-126 and that the result carries the absolute spacing of fp32 denormals.  A word masked by some members only is
+ * finite.  Within 6e-6 + 2^-23·(max_m |x_m − max_m| + |out|) while the mean probability is a normal number.  A member
+ * row without a finite logit, or with a NaN, is outside the contract. */
 int odic_ensemble_logprobs(const float* const* logits, int32_t M, int64_t ldl, float* out, int64_t ldo,
                            int32_t N, int32_t V, void* stream);
 /* k largest entries of every row (ties → lower index), values taken as they are (rows already hold
  * log-probabilities, e.g. the output of odic_ensemble_logprobs): top_val fp32 [N,k], top_idx int32 [N,k], both compact;
- * logp columns [V, ldl) are not read (test_ensemble_logprobs_and_topk_rows_leading_dimensions, also for the one above). */
+ * logp columns [V, ldl) are not read (test_ensemble_logprobs_and_topk_rows_leading_dimensions, also for the one above).
+ * Values are copied, never recomputed.  -inf entries rank behind every finite one; with fewer than k finite entries the
+ * remaining slots hold -inf entries by ascending index.  NaN entries are outside the contract. */
 int odic_topk_rows(const float* logp, int64_t ldl, float* top_val, int32_t* top_idx, int32_t N, int32_t V,
                    int32_t k, void* stream);
 
@@ -665,7 +686,8 @@ int odic_topk_rows(const float* logp, int64_t ldl, float* top_val, int32_t* top_
  *   Banned ids and prefix words outside [0, V) are ignored; nothing is stored out of range.  A finished row
  *   (row_valid[n] == 0) gets exactly what odic_topk_rows gives it: the step kernels use only its rank-0 slot.
  *   k admissible words always exist: a row loses at most n_banned + 1 + (T - 1) words, and a call with
- *   n_banned + T + k > V is refused.  With no active constraint the output is odic_topk_rows', bit for bit.
+ *   n_banned + T + k > V is refused.  With no active constraint the output is odic_topk_rows', bit for bit, -inf entries
+ *   included: they rank behind every finite admissible word and fill the last slots by ascending index.
  *   ODIC_EINVAL, before any launch and with nothing written: n_banned + T + k > V, k outside [1, 16], no_repeat_ngram
  *   outside [0, T], min_words < 0, T outside odic_beam_step's [2, 128], n_banned outside [0, 1024], V above 262144 (the
  *   inadmissible set is a bitmap in 32 KB of LDS), N or V < 1, ldl < V, or a required pointer NULL (logp, c, top_val,

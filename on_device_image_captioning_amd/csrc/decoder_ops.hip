@@ -598,6 +598,21 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
   for (int r = 0; r < k; ++r) {
     float best = tv[0]; int besti = ti[0];
     block_argmax<16>(best, besti, win, r);
+    if (besti == 0x7fffffff) {                           // (block-uniform) every list is empty: a short row
+      // Fewer than k words have a non-zero probability.  No list ever overflowed (one that did holds KM >= k words), so
+      // the words drawn so far are ALL the words above -inf; slots r .. k-1 take the others by ascending index with
+      // log-prob -inf.  V >= k, so there are enough of them: no index outside [0, V) is formed and x[] is not read there.
+      int pi = -1;
+      for (int rr = r; rr < k; ++rr) {
+        float fv = -INFINITY; int fi = 0x7fffffff;
+        for (int i = tid; i < V; i += 1024)
+          if (i > pi && !(x[i] > -INFINITY)) { fi = i; break; }
+        block_argmax<16>(fv, fi, win, rr + 1);            // equal values: the lowest index wins
+        if (tid == 0) { top_val[(long)n * k + rr] = -INFINITY; top_idx[(long)n * k + rr] = fi; }
+        pi = fi;
+      }
+      break;
+    }
     if (tid == 0) {
       top_val[(long)n * k + r] = x[besti] - lse;         // the word's log-probability, not its perturbed score
       top_idx[(long)n * k + r] = besti;

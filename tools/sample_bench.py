@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Time of one odic_logsoftmax_sample launch at the bench shape (V = 10000, k = 5, 48 rows = 16 images x 3 rows), alone on
+the chip: 32 launches captured into one hipGraph, 5 replays between HIP events, median of --runs such figures.
+
+    python3 tools/sample_bench.py [--lib path/to/another/libodic_hip.so] [--runs 9] [--rows 48] [-V 10000] [-k 5]
+
+--lib times another build of the library (the parent commit's) with this tree's binding."""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from on_device_image_captioning_amd import _hip, ops
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib")
+    ap.add_argument("--runs", type=int, default=9)
+    ap.add_argument("--rows", type=int, default=48)
+    ap.add_argument("-V", type=int, default=10000)
+    ap.add_argument("-k", type=int, default=5)
+    a = ap.parse_args()
+    if a.lib:
+        _hip.LIB_PATH = os.path.abspath(a.lib)
+    _hip.load()
+    N, V, k = a.rows, a.V, a.k
+    x = torch.randn(N, V, device="cuda", generator=torch.Generator("cuda").manual_seed(1)) * 3
+    lp, tv = torch.empty(N, V, device="cuda"), torch.empty(N, k, device="cuda")
+    ti = torch.empty(N, k, dtype=torch.int32, device="cuda")
+    pos = torch.zeros(1, dtype=torch.int32, device="cuda")
+    s = torch.cuda.Stream()
+    for name, out in (("top-k only", None), ("with log-prob rows", lp)):
+        fn = lambda: ops.logsoftmax_sample(x, V, out, V if out is not None else 0, tv, ti, N, V, k, 7, pos)   # noqa: E731
+        with torch.cuda.stream(s):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for _ in range(32):
+                fn()
+        times = []
+        for run in range(a.runs + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(s):
+                e0.record()
+                for _ in range(5):
+                    g.replay()
+                e1.record()
+            torch.cuda.synchronize()
+            if run >= 2:
+                times.append(e0.elapsed_time(e1) * 1e3 / 160)
+        print(f"logsoftmax_sample V={V} k={k} rows={N} {name}: median {statistics.median(times):.2f} us, "
+              f"min {min(times):.2f}, max {max(times):.2f} ({a.runs} runs)", flush=True)
+
+
+if __name__ == "__main__":
+    main()
