@@ -652,6 +652,45 @@ int odic_logsoftmax_sample(const float* logits, int64_t ldl, float* logp_out, in
                            int32_t* top_idx, int32_t N, int32_t V, int32_t k, uint64_t seed,
                            const int32_t* pos, void* stream);
 
+/* Sampling controls: odic_logsoftmax_sample's draws from a temperature-scaled top-k / nucleus (top-p) subset of the row. */
+typedef struct odic_sample_filter {
+  float   inv_temperature; /* 1/temperature, rounded once to fp32 by the caller; finite, > 0 */
+  int32_t top_k;           /* 0 = off, else keep the top_k best-ranked words */
+  float   top_p;           /* in (0, 1]; 1 = off */
+} odic_sample_filter;
+
+/* odic_logsoftmax_sample with a filter; logits, logp_out, top_val, top_idx, seed and pos are its arguments.  One block
+ * handles one row.
+ *   Scaled logits: z[v] = x[v]·inv_temperature, one fp32 multiply; ranking, filtering and drawing happen on z.  Rank:
+ *     larger z first, ties to the lower index (-0 = +0); a masked word (x = -inf) has zero mass and ranks last.
+ *   Top-k set K: the first top_k words in rank order; all V words when top_k == 0 or top_k >= V.
+ *   Nucleus: q = softmax(z) renormalised over K, c(v) = the mass of the words of K ranked strictly before v; v is in the
+ *     nucleus iff c(v) < top_p — the smallest rank-prefix whose mass reaches top_p, never empty; equal values at the
+ *     boundary are split by index.  top_p == 1 is OFF: every word of K is in the nucleus, masked ones and those whose
+ *     mass underflows included (their c(v) is 1, or rounds to it).
+ *   kept int32 [N] (may be NULL): m = the number of words in top-k ∩ nucleus, before the extension below.
+ *   Draw set S: the first max(m, k) words in rank order — the filter never leaves fewer candidates than are drawn (a
+ *     min_tokens_to_keep of k), so a beam search with k = beam_size keeps beam_size finite candidates whenever the row
+ *     has that many finite words.
+ *   Draws: the k words of S with the largest z[v] + Gumbel(v), in draw order; the noise is odic_logsoftmax_sample's,
+ *     Philox counter (row, v/4, *pos, 0) under the same key.
+ *   Reported values: top_val and logp_out are the MODEL'S OWN log-probs x[v] − logsumexp(x), unscaled and unfiltered, in
+ *     odic_logsoftmax_sample's form, summation order and bound: a sampled caption's log-probs are its teacher-forced ones.
+ *   Short rows: a row with fewer than k finite words follows odic_logsoftmax_sample's rule.
+ *   Filter off (inv_temperature == 1, top_k == 0, top_p == 1): top_idx, top_val and logp_out are bit for bit those of
+ *     odic_logsoftmax_sample for the same seed and *pos.
+ *   Boundary band: with c(v) in exact arithmetic from the fp32 z, a word with c(v) < top_p·(1 − 1e-5) is kept, one with
+ *     c(v) > top_p·(1 + 1e-5) is dropped, in between either (expf is good to about 2^-22 per term; the masses are summed in
+ *     double, so the summation order adds nothing visible).
+ *   ODIC_EINVAL before any launch, nothing written: inv_temperature not finite or <= 0; top_k < 0; top_p outside (0, 1] or
+ *     NaN; k outside [1, 16]; V < k, V < 1 or V > 262144; N < 1; ldl < V, or ldp < V with logp_out given; f, logits,
+ *     top_val or top_idx NULL.
+ *   All stores stay inside top_val, top_idx, kept and columns [0, V) of logp_out; logits columns [V, ldl) are not read.
+ *   A row without a finite logit, or with a NaN, is outside the contract. */
+int odic_logsoftmax_sample_filtered(const float* logits, int64_t ldl, float* logp_out, int64_t ldp, float* top_val,
+                                    int32_t* top_idx, int32_t* kept /* [N] or NULL */, int32_t N, int32_t V, int32_t k,
+                                    const odic_sample_filter* f, uint64_t seed, const int32_t* pos, void* stream);
+
 /* Ensemble step distribution (ensemble_captioning_model.py:66-83): `logits` is a HOST array of M (<= 8)
  * device pointers to fp32 [N, V] logits (row pitch ldl); out[n][v] = log(mean_m softmax(logits_m[n])[v]).  out columns
  * [V, ldo) are left untouched, logits columns [V, ldl) are not read.

@@ -55,6 +55,11 @@ class SearchConstraints(C.Structure):
                 ("eos_idx", C.c_int64), ("T", C.c_int32)]
 
 
+class SampleFilter(C.Structure):
+    """odic_sample_filter: temperature, top-k and nucleus of a filtered draw (ops.logsoftmax_sample_filtered)."""
+    _fields_ = [("inv_temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 class JpegBatch(C.Structure):
     """odic_jpeg_batch: one batched JPEG decode (headers from on_device_image_captioning_amd.jpeg.pack_headers)."""
     _fields_ = [("headers", C.c_void_p), ("data", C.c_void_p), ("out", C.c_void_p), ("status", C.c_void_p),
@@ -113,6 +118,8 @@ _SIGNATURES = {
     "odic_cross_attn_probs": (C.c_int, [_P, _I64, _P, _I64, _I32, _P, _P, _P, _I64] + [_I32] * 7 + [_F, _P]),
     "odic_logsoftmax_topk": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _P]),
     "odic_logsoftmax_sample": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, C.c_uint64, _P, _P]),
+    "odic_logsoftmax_sample_filtered": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _I32, _I32, _I32, C.POINTER(SampleFilter),
+                                                  C.c_uint64, _P, _P]),
     "odic_ensemble_logprobs": (C.c_int, [C.POINTER(C.c_void_p), _I32, _I64, _P, _I64, _I32, _I32, _P]),
     "odic_topk_rows": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _P]),
     "odic_topk_rows_constrained": (C.c_int, [_P, _I64, C.POINTER(SearchConstraints), _P, _P, _I32, _I32, _I32, _P]),

@@ -338,13 +338,18 @@ class CaptioningModel(nn.Module):
         return _search.dispatch(self, mode, kwargs, enc_x, enc_x_num_pads)
 
     def get_batch_multiple_sampled_prediction(self, enc_input, enc_input_num_pads, num_outputs, sos_idx, eos_idx,
-                                              max_seq_len):
+                                              max_seq_len, *, temperature=1.0, top_k=0, top_p=1.0):
         """mode='sampling' (legacy_models/captioning_model.py:59-109): `num_outputs` ancestral samples per
         image.  Each step runs the incremental decoder and ONE kernel that normalises the row and draws the
         next word on the device (odic_logsoftmax_sample, Philox noise keyed by `self.sampling_seed`, the row and
         the position) — no host round trip, no ATen launch.  The draws cannot be those of the reference's CPU
         generator; what IS checkable — and tested — is that every reported log-prob equals the teacher-forced
-        log-prob of the returned sequence, and that the draw frequencies follow the distribution."""
+        log-prob of the returned sequence, and that the draw frequencies follow the distribution.
+        `temperature`, `top_k`, `top_p`: the draws come from softmax(logits / temperature), cut to its
+        top_k best words (0 = all) and to the nucleus of mass top_p (1 = all) on the device
+        (odic_logsoftmax_sample_filtered); the returned log-probs stay the model's own.  With the defaults the call
+        launches exactly what it launches without them."""
+        flt = _search.check_sampling_filter(temperature, top_k, top_p)
         eng = self._captioner_engine()
         dv = eng.device
         mem = self.forward_enc(enc_input, enc_input_num_pads)
@@ -367,7 +372,7 @@ class CaptioningModel(nn.Module):
         while t < max_seq_len:
             st.pos.fill_(t)
             eng.step_logits(st)
-            ops.logsoftmax_sample(st.logits, V, None, 0, draw_val, draw_idx, N, V, 1, seed, st.pos)
+            _search.draw_candidates(st.logits, draw_val, draw_idx, N, V, 1, seed, st.pos, flt)
             nxt = draw_idx[:, 0].long()
             toks[:, t + 1] = nxt
             lps[:, t + 1] = draw_val[:, 0]
@@ -391,7 +396,7 @@ class CaptioningModel(nn.Module):
     # ------------------------------------------------------------------ search
     def beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                     max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0, banned_words=None,
-                    prefix=None, required_words=None):
+                    prefix=None, required_words=None, temperature=1.0, top_k=0, top_p=1.0):
         """The reference's beam search.  Keyword-only controls over what it may choose, applied on the
         device inside the step: `no_repeat_ngram_size` = n > 0: no caption holds an n-gram twice; `min_length`: at least
         that many words between SOS and EOS; `banned_words`: word ids that never appear.  With the defaults the search
@@ -407,11 +412,15 @@ class CaptioningModel(nn.Module):
         its words (odic_require_beam_step).  Output j of an image is the j-th best caption that holds them all;
         `self.last_required_satisfied` says per image whether there was one (else the outputs are the best captions the
         search still had).  Composes with the three controls above; not with `prefix` or sample_or_max='sample'.  None, [] or
-        nothing but empty lists: exactly the search without the keyword."""
+        nothing but empty lists: exactly the search without the keyword.
+        `temperature`, `top_k`, `top_p`, with sample_or_max='sample' only: every beam's candidates are
+        drawn from softmax(logits / temperature) cut to its top_k best words (0 = all) and to the nucleus of mass top_p
+        (1 = all), never fewer than beam_size words; the log-probs and the ranking stay the model's own."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
         sampling = sample_or_max == "sample"
+        flt = _search.check_sampling_filter(temperature, top_k, top_p, sampling=sampling)
         self.last_required_satisfied = None
         required = self._search_required_arg(required_words, enc_input, beam_size=beam_size, banned_words=banned_words,
                                              sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len, sampling=sampling)
@@ -431,7 +440,8 @@ class CaptioningModel(nn.Module):
                                                          how_many_outputs, max_seq_len, required, cons)
         else:
             toks, lp = self._search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
-                                                max_seq_len, sample=sampling, constraints=cons, prefix=prefix)
+                                                max_seq_len, sample=sampling, constraints=cons, prefix=prefix,
+                                                sample_filter=flt)
         return toks, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
     def _required_search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, bank_beams, how_many_outputs,
@@ -462,7 +472,8 @@ class CaptioningModel(nn.Module):
 
     def _search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
                             max_seq_len, sample: bool = False, constraints: Optional[dict] = None,
-                            prefix: Optional[List[List[int]]] = None) -> Tuple[List[List[List[int]]], torch.Tensor]:
+                            prefix: Optional[List[List[int]]] = None, sample_filter=None
+                            ) -> Tuple[List[List[List[int]]], torch.Tensor]:
         eng = self._captioner_engine()
         B, S, _ = mem.shape
         k = beam_size
@@ -483,7 +494,7 @@ class CaptioningModel(nn.Module):
             # 'sample' variant (captioning_model.py:128-131,166-168): the k candidates of every beam are drawn
             # without replacement from its distribution instead of being its top-k — on the device
             eng.step_logits(st)
-            ops.logsoftmax_sample(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, k, seed, st.pos)
+            _search.draw_candidates(st.logits, st.cand_val, st.cand_idx, st.N, V, k, seed, st.pos, sample_filter)
             if self._draw_log is not None:                        # test hook: the draws, for replay in the oracle
                 self._draw_log.append(st.cand_idx.cpu().clone())
             ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx)

@@ -17,7 +17,7 @@
 //   require_beam_step_kernel the same step for required words: 2^C banks of beams, one per set of words mentioned so far
 //   beam_finalize_kernel     length-normalised ranking (:225-227)
 // The row kernels (the three above that work on vocabulary rows) rank and reduce with row_select.h.
-#include "row_select.h"
+#include "row_sample.h"
 
 namespace {
 
@@ -536,23 +536,6 @@ __global__ __launch_bounds__(512) void logsoftmax_topk_kernel(const float* __res
 // captured step graph draw fresh numbers at every replay.  Outputs: the chosen words in draw order (descending
 // perturbed score) and their log-probabilities x[v] − logsumexp(x); optionally the full log-prob row.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ float gumbel_from_bits(unsigned b) {
-  const float u = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);       // (0,1), 24 bits
-  return -logf(-logf(u));
-}
-
 template <int KM>
 __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __restrict__ logits, long ldl,
                                                                  float* __restrict__ logp_out, long ldp,
@@ -564,9 +547,8 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
   const int n = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (long)n * ldl;
   const unsigned step = pos ? (unsigned)*pos : 0u;
-  float tv[KM]; int ti[KM];
-#pragma unroll
-  for (int q = 0; q < KM; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
+  DrawList<KM> l;
+  l.clear();
   float mx = -INFINITY;
   // a thread owns groups of 4 consecutive words: one Philox call per group
   for (int g4 = tid; g4 * 4 < V; g4 += 1024) {
@@ -574,17 +556,11 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
     philox4x32_10((unsigned)n, (unsigned)g4, step, 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int vi0 = g4 * 4 + e;
-      if (vi0 < V) {
-        const float xv = x[vi0];
+      const int vi = g4 * 4 + e;
+      if (vi < V) {
+        const float xv = x[vi];
         mx = fmaxf(mx, xv);
-        float v = xv + gumbel_from_bits(r[e]); int vi = vi0;
-        if (v > tv[KM - 1]) {
-#pragma unroll
-          for (int q = 0; q < KM; ++q) {
-            if (v > tv[q]) { const float fv = tv[q]; const int fi = ti[q]; tv[q] = v; ti[q] = vi; v = fv; vi = fi; }
-          }
-        }
+        l.offer(xv + gumbel_from_bits(r[e]), vi);
       }
     }
   }
@@ -595,34 +571,7 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
   const float lse = m + logf(s);
   if (logp_out)
     for (int i = tid; i < V; i += 1024) logp_out[(long)n * ldp + i] = x[i] - lse;
-  for (int r = 0; r < k; ++r) {
-    float best = tv[0]; int besti = ti[0];
-    block_argmax<16>(best, besti, win, r);
-    if (besti == 0x7fffffff) {                           // (block-uniform) every list is empty: a short row
-      // Fewer than k words have a non-zero probability.  No list ever overflowed (one that did holds KM >= k words), so
-      // the words drawn so far are ALL the words above -inf; slots r .. k-1 take the others by ascending index with
-      // log-prob -inf.  V >= k, so there are enough of them: no index outside [0, V) is formed and x[] is not read there.
-      int pi = -1;
-      for (int rr = r; rr < k; ++rr) {
-        float fv = -INFINITY; int fi = 0x7fffffff;
-        for (int i = tid; i < V; i += 1024)
-          if (i > pi && !(x[i] > -INFINITY)) { fi = i; break; }
-        block_argmax<16>(fv, fi, win, rr + 1);            // equal values: the lowest index wins
-        if (tid == 0) { top_val[(long)n * k + rr] = -INFINITY; top_idx[(long)n * k + rr] = fi; }
-        pi = fi;
-      }
-      break;
-    }
-    if (tid == 0) {
-      top_val[(long)n * k + r] = x[besti] - lse;         // the word's log-probability, not its perturbed score
-      top_idx[(long)n * k + r] = besti;
-    }
-    if (ti[0] == besti) {
-#pragma unroll
-      for (int q = 0; q + 1 < KM; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
-      tv[KM - 1] = -INFINITY; ti[KM - 1] = 0x7fffffff;
-    }
-  }
+  block_draw_rounds<KM>(l, x, V, k, lse, top_val + (long)n * k, top_idx + (long)n * k, win);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -92,17 +92,19 @@ class EsembleCaptioningModel(CaptioningModel):
 
     def ensemble_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                              max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0,
-                             banned_words=None, prefix=None, required_words=None
+                             banned_words=None, prefix=None, required_words=None, temperature=1.0, top_k=0, top_p=1.0
                              ) -> Tuple[List[List[List[int]]], torch.Tensor]:
         """`no_repeat_ngram_size`, `min_length`, `banned_words`: as in CaptioningModel.beam_search; the constrained
         selection (odic_topk_rows_constrained) then replaces odic_topk_rows on the averaged log-probs.
         `prefix`: as in CaptioningModel.beam_search; every member fills its caches in one pass over the prefix and the
         prefix words' log-probs are the averaged distribution's (search.ensemble_seed_prefix).
-        `required_words`: CaptioningModel.beam_search's; anything but nothing required is refused here."""
+        `required_words`: CaptioningModel.beam_search's; anything but nothing required is refused here.
+        `temperature`, `top_k`, `top_p`: as in CaptioningModel.beam_search, on the averaged distribution."""
         assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
         assert (sample_or_max == "max" or sample_or_max == "sample"), \
             "argument must be chosen between 'max' and 'sample'"
         sample = sample_or_max == "sample"
+        flt = _search.check_sampling_filter(temperature, top_k, top_p, sampling=sample)
         _search.refuse_required_words(required_words, "in ensemble_beam_search")
         constraints = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                                    banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
@@ -134,7 +136,8 @@ class EsembleCaptioningModel(CaptioningModel):
         # (the log-probs stay on the engine's device, unlike beam_search's, which go to the input's)
         return _search.run_search(
             engs[0], lead, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
-            step=lambda cons: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed, constraints=cons))
+            step=lambda cons: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed, constraints=cons,
+                                                    sample_filter=flt))
 
     def beam_search(self, *a, **k):
         """ensemble_beam_search, with its arguments, under the name the mode dispatch (search.dispatch) calls; the

@@ -684,6 +684,25 @@ def logsoftmax_sample(logits, ldl, logp_out, ldp, top_val, top_idx, N, V, k, see
                    "odic_logsoftmax_sample")
 
 
+def sample_filter(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> "_hip.SampleFilter":
+    """odic_sample_filter of the three controls; 1/temperature is formed in double and rounded once to fp32."""
+    return _hip.SampleFilter(1.0 / float(temperature), int(top_k), float(top_p))
+
+
+def logsoftmax_sample_filtered(logits, ldl, logp_out, ldp, top_val, top_idx, kept, N, V, k, flt, seed: int, pos=None) -> None:
+    """logsoftmax_sample's draws from the temperature-scaled top-k / nucleus set of `flt` (sample_filter(...)); top_val and
+    logp_out stay the model's own log-probs.  kept: int32 [N] for the size of every row's filtered set, or None."""
+    _need_cuda(logits, logp_out, top_val, top_idx, kept, pos)
+    # the plain draw's work plus the passes of the threshold search over the row: 32 bisection rounds per active control
+    rounds = 32 * ((0 < flt.top_k < V) + (flt.top_p < 1.0))
+    with _timed("logsoftmax_sample_filtered", (14.0 + 3.0 * rounds) * N * V,
+                N * V * 4.0 * (2 if logp_out is not None else 1) + N * k * 8.0):
+        _hip.check(_hip.load().odic_logsoftmax_sample_filtered(_p(logits), ldl, _p(logp_out), ldp, _p(top_val), _p(top_idx),
+                                                               _p(kept), N, V, k, C.byref(flt),
+                                                               seed & 0xFFFFFFFFFFFFFFFF, _p(pos), _stream()),
+                   "odic_logsoftmax_sample_filtered")
+
+
 def ensemble_logprobs(logits_list, out: torch.Tensor) -> None:
     """out[n] = log(mean_m softmax(logits_m[n])) — ensemble_captioning_model.py:66-83."""
     _need_cuda(out, *logits_list)

@@ -88,6 +88,49 @@ def check_prefix(prefix, n_img: int, *, V, max_seq_len: int, sos_idx, eos_idx, s
     return [list(r) for r in rows]
 
 
+def _filter_kwargs(args) -> dict:
+    """The sampling-control keywords present in a forward(**kwargs) / beam_search_args mapping (absent = the default)."""
+    return {k: args[k] for k in ("temperature", "top_k", "top_p") if k in args}
+
+
+def check_sampling_filter(temperature=1.0, top_k=0, top_p=1.0, *, sampling: bool = True, where: str = "sample_or_max='max'"):
+    """The rules of the sampling controls: the draws come from softmax(logits / temperature) cut to its
+    `top_k` best words (0 = all) and to the nucleus of mass `top_p` (1 = all).  None when all three are at their defaults
+    (the search then launches exactly what it launches without them: odic_logsoftmax_sample), else the odic_sample_filter of
+    odic_logsoftmax_sample_filtered; ValueError for what cannot work.  `sampling`: whether the search draws at all; one
+    that does not (`where` names it) takes the defaults only."""
+    t, p = float(temperature), float(top_p)
+    if isinstance(top_k, bool) or int(top_k) != top_k:
+        raise ValueError(f"top_k must be an integer, not {top_k!r}")
+    k = int(top_k)
+    if not (0.0 < t < float("inf")):
+        raise ValueError(f"temperature must be finite and > 0, not {temperature!r}")
+    if k < 0:
+        raise ValueError(f"top_k must be >= 0 (0 = off), not {top_k!r}")
+    if not (0.0 < p <= 1.0):
+        raise ValueError(f"top_p must lie in (0, 1] (1 = off), not {top_p!r}")
+    flt = ops.sample_filter(t, k, p)
+    if t == 1.0 and k == 0 and p == 1.0:
+        return None
+    if not (0.0 < flt.inv_temperature < float("inf")):
+        raise ValueError(f"temperature {temperature!r}: its reciprocal is not a positive finite fp32 number")
+    if not (0.0 < flt.top_p <= 1.0):
+        raise ValueError(f"top_p {top_p!r} is not a positive fp32 number")
+    if not sampling:
+        raise ValueError(f"temperature / top_k / top_p shape the draws of the sampling searches (sample_or_max='sample', "
+                         f"mode='sampling'): {where} draws nothing")
+    return flt
+
+
+def draw_candidates(logits, cand_val, cand_idx, N: int, V: int, k: int, seed: int, pos, flt=None) -> None:
+    """k draws without replacement per logits row into cand_val / cand_idx: odic_logsoftmax_sample, or under `flt`
+    (check_sampling_filter's) odic_logsoftmax_sample_filtered."""
+    if flt is None:
+        ops.logsoftmax_sample(logits, V, None, 0, cand_val, cand_idx, N, V, k, seed, pos)
+    else:
+        ops.logsoftmax_sample_filtered(logits, V, None, 0, cand_val, cand_idx, None, N, V, k, flt, seed, pos)
+
+
 MAX_REQUIRED = 4    # required words per image (odic_require_beam_step: 2^C banks of beams, 16 rows per image at most)
 
 
@@ -178,11 +221,12 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
     sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
     pre = {k: args[k] for k in ("prefix", "required_words") if k in args}       # (absent = the default, as the constraints)
+    flt = _filter_kwargs(args)
     if mode == "beam_search":
         return model.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
                                  beam_size=args.get("beam_size", 5), how_many_outputs=args.get("how_many_outputs", 1),
                                  max_seq_len=args.get("beam_max_seq_len", 20),
-                                 sample_or_max=args.get("sample_or_max", "max"), **pre, **cons)
+                                 sample_or_max=args.get("sample_or_max", "max"), **pre, **cons, **flt)
     if mode == "sampling":
         max_seq_len = args.get("sample_max_seq_len", 20)
         model._search_constraint_args(**cons, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len, rows_per_image=1,
@@ -195,8 +239,9 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
                                        eos_idx=eos_idx, max_seq_len=max_seq_len, sampling=True)
         return model.get_batch_multiple_sampled_prediction(
             enc_x, enc_x_num_pads, num_outputs=args.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
-            max_seq_len=max_seq_len)
+            max_seq_len=max_seq_len, **flt)
     if mode == "diverse_beam_search":
+        check_sampling_filter(**flt, sampling=False, where="diverse_beam_search")
         return model.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
                                          num_groups=args.get("num_groups", 3), group_size=args.get("group_size", 3),
                                          diversity_penalty=args.get("diversity_penalty", 0.5),
@@ -291,18 +336,19 @@ def ensemble_seed_prefix(engines, states, prefix: torch.Tensor, sos_idx: int) ->
 
 
 def ensemble_step(engines, states, avg: torch.Tensor, eos_idx: int, *, sample_seed: Optional[int] = None,
-                  constraints=None) -> None:
+                  constraints=None, sample_filter=None) -> None:
     """One search step of an ensemble on share_beam_state(states): a decoder pass per member, avg [N, V] =
     log(mean_m softmax(logits_m)), the lead's k candidates per row from it — its top-k, under `constraints` the
     admissible top-k, with `sample_seed` k draws without replacement (odic_logsoftmax_sample on rows that already are
-    log-probabilities: its normalisation is then the identity up to rounding) — and the beam bookkeeping."""
+    log-probabilities: its normalisation is then the identity up to rounding; under `sample_filter`, check_sampling_filter's,
+    the filtered draws) — and the beam bookkeeping."""
     lead = states[0]
     for eng, st in zip(engines, states):
         eng.step_logits(st)                                      # private caches, shared next_tok / pos / ancestors
     ops.ensemble_logprobs([st.logits for st in states], avg)
     if sample_seed is not None:
-        V = avg.shape[1]
-        ops.logsoftmax_sample(avg, V, None, 0, lead.cand_val, lead.cand_idx, lead.N, V, lead.beams, sample_seed, lead.pos)
+        draw_candidates(avg, lead.cand_val, lead.cand_idx, lead.N, avg.shape[1], lead.beams, sample_seed, lead.pos,
+                        sample_filter)
     elif constraints is not None:
         engines[0].constrained_candidates(lead, constraints, logp=avg)
     else:

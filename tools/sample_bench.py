@@ -3,8 +3,10 @@
 the chip: 32 launches captured into one hipGraph, 5 replays between HIP events, median of --runs such figures.
 
     python3 tools/sample_bench.py [--lib path/to/another/libodic_hip.so] [--runs 9] [--rows 48] [-V 10000] [-k 5]
+                                  [--filter topk:topp:temp ...]
 
---lib times another build of the library (the parent commit's) with this tree's binding."""
+--lib times another build of the library (the parent commit's) with this tree's binding.
+--filter times odic_logsoftmax_sample_filtered under those controls as well, e.g. --filter 20:0.9:0.8."""
 import argparse
 import os
 import statistics
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--rows", type=int, default=48)
     ap.add_argument("-V", type=int, default=10000)
     ap.add_argument("-k", type=int, default=5)
+    ap.add_argument("--filter", nargs="*", default=[])
     a = ap.parse_args()
     if a.lib:
         _hip.LIB_PATH = os.path.abspath(a.lib)
@@ -33,8 +36,15 @@ def main():
     ti = torch.empty(N, k, dtype=torch.int32, device="cuda")
     pos = torch.zeros(1, dtype=torch.int32, device="cuda")
     s = torch.cuda.Stream()
-    for name, out in (("top-k only", None), ("with log-prob rows", lp)):
-        fn = lambda: ops.logsoftmax_sample(x, V, out, V if out is not None else 0, tv, ti, N, V, k, 7, pos)   # noqa: E731
+    cases = [("top-k only", None, None), ("with log-prob rows", lp, None)]
+    for spec in a.filter:
+        tk, tp, t = spec.split(":")
+        cases.append((f"filtered top_k={tk} top_p={tp} temperature={t}", None, ops.sample_filter(float(t), int(tk), float(tp))))
+    for name, out, flt in cases:
+        if flt is None:
+            fn = lambda: ops.logsoftmax_sample(x, V, out, V if out is not None else 0, tv, ti, N, V, k, 7, pos)   # noqa: E731
+        else:
+            fn = lambda: ops.logsoftmax_sample_filtered(x, V, None, 0, tv, ti, None, N, V, k, flt, 7, pos)       # noqa: E731
         with torch.cuda.stream(s):
             fn()
         torch.cuda.synchronize()

@@ -4,7 +4,7 @@ FULL geometry, features-only model, 16 images, fp32, HIP events around the step 
 poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
 it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
 
-    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 pbeam:3:6 rbeam:3:2
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 pbeam:3:6 rbeam:3:2 sample:3 sample:3:20:0.9:0.8
 
 cbeam:K is beam:K under constraints: no_repeat_ngram_size=2, min_length=5 and 8 banned words; the step then
 holds one launch more (odic_topk_rows_constrained) and the top-k launch writes the log-prob rows.
@@ -13,6 +13,9 @@ caches (CaptionerEngine.seed_prefix) and max_len - 1 - P steps; compare its time
 rbeam:K:C is the search for captions that contain C required words: 2^C banks of K beams per image (words
 300 .. 300+C-1 for every image); the top-k launch writes the log-prob rows and the selection is odic_require_beam_step.  Compare
 it with diverse:GxK' at the same number of rows per image.
+sample:K[:topk:topp:temp] is the step of beam_search(sample_or_max='sample') with K beams: the decoder, the k draws per row
+and the beam bookkeeping.  sample:K draws with odic_logsoftmax_sample; with the three controls given, e.g.
+sample:3:20:0.9:0.8, with odic_logsoftmax_sample_filtered: the difference of the two is the cost of the filter per step.
 A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix, rbeam
 before odic_require_beam_step) is reported as absent.
 """
@@ -57,7 +60,25 @@ def main():
             if not hasattr(eng, "seed_prefix"):
                 print(f"{form}: not in this build")
                 continue
-        if kind == "rbeam":
+        if kind == "sample":
+            shape, *ctl = shape.split(":")
+            R, flt = int(shape), None
+            if ctl:
+                if len(ctl) != 3 or not hasattr(ops, "logsoftmax_sample_filtered"):
+                    print(f"{form}: not in this build" if len(ctl) == 3 else f"{form}: give topk:topp:temp, or none of them")
+                    continue
+                flt = ops.sample_filter(float(ctl[2]), int(ctl[0]), float(ctl[1]))
+            V = eng.g.vocab_size
+
+            def one(st, flt=flt, V=V, R=R):
+                eng.step_logits(st)
+                if flt is None:
+                    ops.logsoftmax_sample(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.N, V, R, 7, st.pos)
+                else:
+                    ops.logsoftmax_sample_filtered(st.logits, V, None, 0, st.cand_val, st.cand_idx, None, st.N, V, R, flt, 7,
+                                                   st.pos)
+                ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, bench.EOS)
+        elif kind == "rbeam":
             shape, C = shape.split(":")
             kb, C = int(shape), int(C)
             if not hasattr(eng, "require_beam_step"):
@@ -90,7 +111,7 @@ def main():
             if P:
                 eng.seed_prefix(st, prefix, bench.SOS)
             else:
-                ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=st.emb)
+                ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=None if kind == "sample" else st.emb)
             for _ in range(steps - P):
                 one(st)
 
