@@ -298,6 +298,11 @@ class DecodeState:
         f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dv)      # noqa: E731
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dv)      # noqa: E731
         self.ycat = f(N, L * d)
+        # what step_logits would otherwise build again for every token: each layer's (input, output) column slices of
+        # ycat (layer 0 works in place), and the integers ops.gemm_dims derives at each of its call sites — the operand
+        # shapes and strides of a site are the same at every step of this state
+        self.layer_io = [(self.ycat[:, max(i - 1, 0) * d:max(i, 1) * d], self.ycat[:, i * d:(i + 1) * d]) for i in range(L)]
+        self.gemm_dims: dict = {}
         self.caches = [dict(cond=f(T, N, d), key=f(T, N, d), va=f(T, N, d), vb=f(T, N, d),
                             wfa=f(T, N, T, E), wfb=f(T, N, T, E), qk=f(T, N, E)) for _ in range(L)]
         self.anc = i32(N, T)
@@ -328,6 +333,7 @@ class CaptionerEngine:
         # decoder LayerNorms folded into the consuming skinny GEMM (10 fewer launches per step; see
         # odic_gemm_args.ln_colsum).  ODIC_FOLD_LN=0 keeps the separate odic_layernorm launches.
         self.fuse_ln = os.environ.get("ODIC_FOLD_LN", "1") == "1"
+        self._pad_ws = {}           # encode's zero-padded GEMM outputs, kept per (B, S, stream)
         d = g.d_model
         f32 = lambda k: _dev(sd[k], device, torch.float32)          # noqa: E731
         cat = lambda ks: torch.cat([f32(k) for k in ks], 0).contiguous()   # noqa: E731
@@ -388,14 +394,14 @@ class CaptionerEngine:
         self.embed, self.pos_table = f32("out_embedder.embed.weight"), f32("pos_encoder.weight")
 
     # ------------------------------------------------------------------------------------------
-    def _as_operand(self, x: torch.Tensor, M: int, C_: int, ldx: int) -> torch.Tensor:
+    def _as_operand(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 activations → the encoder GEMM operand dtype (identity view in fp32 mode)."""
         if x.dtype == self.cdt:
             return x
         if self.cdt == torch.bfloat16 and x.dtype == torch.float32:
-            return ops.cast_bf16(x, M=M, C_=C_, ldx=ldx)
+            return ops.cast_bf16(x)
         if self.cdt == ops.H2_DTYPE and x.dtype == torch.float32:
-            return ops.cast_h2(x, M=M, C_=C_, ldx=ldx)
+            return ops.cast_h2(x)
         raise RuntimeError(f"cannot feed {x.dtype} to a {self.cdt} encoder")
 
     def encode(self, feats: torch.Tensor, enc_len: torch.Tensor, want_bf16_mem: bool = False):
@@ -412,10 +418,7 @@ class CaptionerEngine:
         Sp, nqp = -(-S // pad) * pad, -(-nq // pad) * pad
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dv)      # noqa: E731
         zc = lambda *s: torch.zeros(*s, dtype=cdt, device=dv)               # noqa: E731  (K padding must be finite)
-        feats2 = feats.reshape(M, F)
-        if not feats2.is_contiguous():
-            feats2 = feats2.contiguous()
-        x0 = ops.gemm(self._as_operand(feats2, M, F, F), self.in_w, self.in_b, out_dtype=torch.float32,
+        x0 = ops.gemm(self._as_operand(feats.contiguous().view(M, F)), self.in_w, self.in_b, out_dtype=torch.float32,
                       alpha=self.in_a)                                                                   # [M,d]
         xcat = f(M, L * d)
         z = f(B, nq, S)
@@ -430,49 +433,38 @@ class CaptionerEngine:
         pb, nb = ec(B, S, nqp), ec(B, S, nqp)
         colsum = f(B * len(g.num_exp_enc_list) * 2 * S)
         key = (B, S, torch.cuda.current_stream(dv).cuda_stream)
-        pads = self._pad_ws.get(key) if hasattr(self, "_pad_ws") else None
+        pads = self._pad_ws.get(key)
         if pads is None:
-            if torch.cuda.is_current_stream_capturing():      # (a first call under capture: plain per-call buffers)
-                pads = (zc(B, d, nqp), zc(B, d, nqp), zc(B, 2 * d, Sp))
-            else:
-                if not hasattr(self, "_pad_ws"):
-                    self._pad_ws = {}
-                pads = self._pad_ws[key] = (zc(B, d, nqp), zc(B, d, nqp), zc(B, 2 * d, Sp))
+            pads = (zc(B, d, nqp), zc(B, d, nqp), zc(B, 2 * d, Sp))
+            if not torch.cuda.is_current_stream_capturing():  # (a first call under capture: plain per-call buffers)
+                self._pad_ws[key] = pads
         AT, BT, vabT = pads
         A2, B2 = f(B, S, d), f(B, S, d)
         key = torch.empty(M, d, dtype=cdt, device=dv)
-        ld = L * d
         for i, w in enumerate(self.enc):
-            xin, ldin = (x0, d) if i == 0 else (xcat[:, (i - 1) * d:], ld)
-            xo = xcat[:, i * d:]
-            x2 = ops.layernorm(xin, w["n1w"], w["n1b"], M=M, C_=d, ldx=ldin, out_dtype=cdt)
+            xin = x0 if i == 0 else xcat[:, (i - 1) * d:i * d]
+            xo = xcat[:, i * d:(i + 1) * d]
+            x2 = ops.layernorm(xin, w["n1w"], w["n1b"], out_dtype=cdt)
             ops.gemm(x2, w["key_w"], w["key_b"], out=key, alpha=w["key_a"])
             sel = ops.gemm(x2, w["sel_w"], w["sel_b"], out_dtype=torch.float32, alpha=w["sel_a"])
             # (class_a | class_b) projections, produced transposed: [B, 2d, S] = W·x2ᵀ + b(row)
-            ops.gemm(w["ab_w"], x2, w["ab_b"], out=vabT, bias_axis=1, M=2 * d, N=S, K=d, lda=d, ldw=d, ldc=Sp,
-                     batch=B, strideA=0, strideW=S * d, strideC=2 * d * Sp, alpha=w["ab_a"])
+            ops.gemm(w["ab_w"], x2.view(B, S, d), w["ab_b"], out=vabT, bias_axis=1, batch=B, alpha=w["ab_a"])
             # z = Q·Kᵀ/sqrt(d)
-            ops.gemm(w["q"], key, out=z, alpha=w["q_a"] / math.sqrt(d), M=nq, N=S, K=d, lda=d, ldw=d, ldc=S,
-                     batch=B, strideA=0, strideW=S * d, strideC=nq * S)
+            ops.gemm(w["q"], key.view(B, S, d), out=z, batch=B, alpha=w["q_a"] / math.sqrt(d))
             ops.stcexp_normalize(z, enc_len, self.group_meta, len(g.num_exp_enc_list), pf, nf, pb, nb, colsum,
                                  scale_fw=fw_sc, scale_bw=bw_sc)
             # class_aᵀ [d,nq] = Vaᵀ·pos_fwᵀ + Bvᵀ    (layers.py:63-64, transposed)
-            ops.gemm(vabT, pf, residual=w["bvT"], out=AT, M=d, N=nq, K=Sp, lda=Sp, ldw=Sp, ldr=nq, ldc=nqp, batch=B,
-                     strideA=2 * d * Sp, strideW=nq * Sp, strideR=0, strideC=d * nqp, alpha=1.0 / fw_sc)
-            ops.gemm(vabT[:, d:], nf, residual=w["bvT"], out=BT, M=d, N=nq, K=Sp, lda=Sp, ldw=Sp, ldr=nq, ldc=nqp,
-                     batch=B, strideA=2 * d * Sp, strideW=nq * Sp, strideR=0, strideC=d * nqp, alpha=1.0 / fw_sc)
+            ops.gemm(vabT[:, :d], pf, residual=w["bvT"], out=AT, batch=B, alpha=1.0 / fw_sc)
+            ops.gemm(vabT[:, d:], nf, residual=w["bvT"], out=BT, batch=B, alpha=1.0 / fw_sc)
             # backward: [S,nq]·[nq,d]
-            ops.gemm(pb, AT, out=A2, M=S, N=d, K=nqp, lda=nqp, ldw=nqp, ldc=d, batch=B, strideA=S * nqp,
-                     strideW=d * nqp, strideC=S * d, alpha=1.0 / bw_sc)
-            ops.gemm(nb, BT, out=B2, M=S, N=d, K=nqp, lda=nqp, ldw=nqp, ldc=d, batch=B, strideA=S * nqp,
-                     strideW=d * nqp, strideC=S * d, alpha=1.0 / bw_sc)
-            ops.selector_mix(xin, ldin, sel, d, A2, d, B2, d, xo, ld, M, d)
-            x2 = ops.layernorm(xo, w["n2w"], w["n2b"], M=M, C_=d, ldx=ld, out_dtype=cdt)
+            ops.gemm(pb, AT, out=A2, batch=B, alpha=1.0 / bw_sc)
+            ops.gemm(nb, BT, out=B2, batch=B, alpha=1.0 / bw_sc)
+            ops.selector_mix(xin, xin.stride(0), sel, d, A2, d, B2, d, xo, xo.stride(0), M, d)
+            x2 = ops.layernorm(xo, w["n2w"], w["n2b"], out_dtype=cdt)
             h = ops.gemm(x2, w["f1w"], w["f1b"], act=ops.ACT_RELU, alpha=w["f1a"])
-            ops.gemm(h, w["f2w"], w["f2b"], residual=xo, out=xo, M=M, N=d, K=g.ff, lda=g.ff, ldw=g.ff, ldr=ld,
-                     ldc=ld, alpha=w["f2a"])
-        pre = ops.gemm(self._as_operand(xcat, M, ld, ld), self.er_w, self.er_b, residual=xcat[:, (L - 1) * d:], M=M,
-                       N=d, K=ld, lda=ld, ldw=ld, ldr=ld, ldc=d, out=f(M, d), alpha=self.er_a)
+            ops.gemm(h, w["f2w"], w["f2b"], residual=xo, out=xo, alpha=w["f2a"])
+        pre = ops.gemm(self._as_operand(xcat), self.er_w, self.er_b, residual=xcat[:, (L - 1) * d:], out=f(M, d),
+                       alpha=self.er_a)
         mem = ops.layernorm(pre, self.ern_w, self.ern_b).view(B, S, d)
         if want_bf16_mem and cdt != torch.float32:                 # the K/V projection's operand, rounded once
             return mem, ops.layernorm(pre, self.ern_w, self.ern_b, out_dtype=cdt).view(B, S, d)
@@ -485,15 +477,10 @@ class CaptionerEngine:
         n = self.kv_w.shape[0]
         if out is None:
             out = torch.empty(B, S, n, dtype=torch.float32, device=self.device)
-        a = mem.reshape(B * S, d)
-        if not a.is_contiguous():
-            a = a.contiguous()
         # bf16 mode: the product runs on the bf16 MFMA GEMM whatever dtype the caller holds the memory in, so
         # the direct beam_search call and CaptionPipeline (which feeds the bf16 LayerNorm output) see
         # bit-identical K/V: round-to-nearest-even of the same fp32 values either way.
-        if a.dtype != self.kv_w.dtype:
-            a = self._as_operand(a, B * S, d, d)
-        ops.gemm(a, self.kv_w, self.kv_b, out=out, M=B * S, N=n, K=d, lda=d, ldw=d, ldc=n, alpha=self.kv_a)
+        ops.gemm(self._as_operand(mem.contiguous().view(B * S, d)), self.kv_w, self.kv_b, out=out, alpha=self.kv_a)
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -509,46 +496,51 @@ class CaptionerEngine:
         this position is already in st.ycat (written by the launch that chose the word: beam_reset / beam_step
         with st.emb)."""
         g = self.g
-        d, L, N = g.d_model, g.N_dec, st.N
-        ld = L * d
+        d, N = g.d_model, st.N
         if embed:
-            ops.dec_embed(st.next_tok, self.embed, self.pos_table, st.pos, st.ycat, ld, N, d, math.sqrt(d))
+            ops.dec_embed(st.next_tok, self.embed, self.pos_table, st.pos, st.ycat, st.ycat.stride(0), N, d, math.sqrt(d))
         # the folded-LayerNorm form lives in the skinny-M kernel (M <= 192 rows, gemm_f32.hip); wider
         # searches (batch 64 x beam 5, decode groups) take the LayerNorm + GEMM pair
         fuse = self.fuse_ln and N <= 192
         eps = 1e-5
 
-        def ln_gemm(x, ldx, nw, nb, W, b, folded, **kw):
+        dims = st.gemm_dims.setdefault(fuse, {})
+
+        def gemm(site, A, W, b, residual=None, out=None, **kw):
+            """ops.gemm with the integers of this call site derived once per state (DecodeState.gemm_dims)."""
+            dm = dims.get(site)
+            if dm is None:
+                dm = dims[site] = ops.gemm_dims(A, W, residual, out)
+            return ops.gemm(A, W, b, residual, out, dims=dm, **kw)
+
+        def ln_gemm(site, x, nw, nb, W, b, folded, **kw):
             """LayerNorm(x)·Wᵀ + b: one launch (LayerNorm folded into the product) or two."""
             if fuse:
                 Wf, bf, cs = folded
-                return ops.gemm(x, Wf, bf, M=N, N=Wf.shape[0], K=d, lda=ldx, ldw=d, ldc=Wf.shape[0], ln_fold=(cs, eps), **kw)
-            return ops.gemm(ops.layernorm(x, nw, nb, M=N, C_=d, ldx=ldx), W, b, **kw)
+                return gemm(site, x, Wf, bf, ln_fold=(cs, eps), **kw)
+            return gemm(site, ops.layernorm(x, nw, nb), W, b, **kw)
 
         for i, w in enumerate(self.dec):
             c = st.caches[i]
-            xin = st.ycat if i == 0 else st.ycat[:, (i - 1) * d:]
-            xo = st.ycat[:, i * d:]
-            lin = ln_gemm(xin, ld, w["n1w"], w["n1b"], w["dyn_w"], w["dyn_b"], w["dyn_f"])               # [N,5d]
-            ops.dynexp_step(lin, 5 * d, w["qexp"], w["bexp"], c["cond"], c["key"], c["va"], c["vb"], c["wfa"],
+            xin, xo = st.layer_io[i]
+            ld = xo.stride(0)
+            lin = ln_gemm((i, "dyn"), xin, w["n1w"], w["n1b"], w["dyn_w"], w["dyn_b"], w["dyn_f"])       # [N,5d]
+            ops.dynexp_step(lin, lin.stride(0), w["qexp"], w["bexp"], c["cond"], c["key"], c["va"], c["vb"], c["wfa"],
                             c["wfb"], c["qk"], st.anc, st.row_valid, st.pos, xin, ld, xo, ld, N, st.T, d,
                             g.num_exp_dec)
-            q = ln_gemm(xo, ld, w["n2w"], w["n2b"], w["wq"], w["bq"], w["wq_f"])
+            q = ln_gemm((i, "wq"), xo, w["n2w"], w["n2b"], w["wq"], w["bq"], w["wq_f"])
             att = torch.empty(N, d, dtype=torch.float32, device=self.device)
             ops.cross_attn_step(q, d, st.kv, st.kv.shape[2], 2 * i * d, (2 * i + 1) * d, st.enc_len,
                                 st.row_valid, att, d, N, st.n_img, st.S, d, g.num_heads)
-            ops.gemm(att, w["wo"], w["bo"], residual=xo, out=xo, M=N, N=d, K=d, lda=d, ldw=d, ldr=ld, ldc=ld)
-            h = ln_gemm(xo, ld, w["n3w"], w["n3b"], w["f1w"], w["f1b"], w["f1_f"], act=ops.ACT_RELU)
-            ops.gemm(h, w["f2w"], w["f2b"], residual=xo, out=xo, M=N, N=d, K=g.ff, lda=g.ff, ldw=g.ff, ldr=ld,
-                     ldc=ld)
+            gemm((i, "wo"), att, w["wo"], w["bo"], xo, xo)
+            h = ln_gemm((i, "f1"), xo, w["n3w"], w["n3b"], w["f1w"], w["f1b"], w["f1_f"], act=ops.ACT_RELU)
+            gemm((i, "f2"), h, w["f2w"], w["f2b"], xo, xo)
         pre = torch.empty(N, d, dtype=torch.float32, device=self.device)
-        ops.gemm(st.ycat, self.dr_w, self.dr_b, residual=st.ycat[:, (L - 1) * d:], out=pre, M=N, N=d, K=ld, lda=ld,
-                 ldw=ld, ldr=ld, ldc=d)
+        gemm("reduce", st.ycat, self.dr_w, self.dr_b, st.layer_io[-1][1], pre)
         if fuse:
-            ops.gemm(pre, self.voc_f[0], self.voc_f[1], out=st.logits, M=N, N=g.vocab_size, K=d, lda=d, ldw=d,
-                     ldc=g.vocab_size, ln_fold=(self.voc_f[2], eps))
+            gemm("vocab", pre, self.voc_f[0], self.voc_f[1], out=st.logits, ln_fold=(self.voc_f[2], eps))
         else:
-            ops.gemm(ops.layernorm(pre, self.drn_w, self.drn_b), self.voc_w, self.voc_b, out=st.logits)
+            gemm("vocab", ops.layernorm(pre, self.drn_w, self.drn_b), self.voc_w, self.voc_b, out=st.logits)
 
     def search_constraints(self, st: DecodeState, eos_idx: int, *, no_repeat_ngram: int = 0, min_words: int = 0,
                            banned=None) -> Optional["_hip.SearchConstraints"]:
@@ -690,10 +682,11 @@ class CaptionerEngine:
         if tokens.dtype != torch.int64 or dec_len.dtype != torch.int32 or enc_len.dtype != torch.int32:
             raise RuntimeError("decode_sequence wants int64 tokens and int32 lengths")
         tokens = tokens.contiguous()
-        M, ld, S = N * T, L * d, kv.shape[1]
+        M, S = N * T, kv.shape[1]
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dv)      # noqa: E731
         TC = 3                                   # odic_gemm tile_cfg: the 64 x 64 tile kernel whatever M is
-        ycat, row_valid = f(M, ld), torch.empty(M, dtype=torch.int32, device=dv)
+        ycat, row_valid = f(M, L * d), torch.empty(M, dtype=torch.int32, device=dv)
+        ld = ycat.stride(0)
         ops.dec_embed_seq(tokens, self.embed, self.pos_table, ycat, ld, N, T, d, math.sqrt(d), dec_len, row_valid)
         xn, lin, q, att, h = f(M, d), f(M, 5 * d), f(M, d), f(M, d), f(M, g.ff)
         amap = None
@@ -709,15 +702,15 @@ class CaptionerEngine:
             amap = f(1 if a_reduce else len(a_layers), M, a_w)
             a_scale = (1.0 if a_heads else 1.0 / H) / (len(a_layers) if a_reduce else 1)
         for i, w in enumerate(self.dec):
-            xin = ycat if i == 0 else ycat[:, (i - 1) * d:]
-            xo = ycat[:, i * d:]
-            ops.layernorm(xin, w["n1w"], w["n1b"], M=M, C_=d, ldx=ld, out=xn)
+            xo = ycat[:, i * d:(i + 1) * d]
+            xin = xo if i == 0 else ycat[:, (i - 1) * d:i * d]             # (layer 0 works in place)
+            ops.layernorm(xin, w["n1w"], w["n1b"], out=xn)
             ops.gemm(xn, w["dyn_w"], w["dyn_b"], out=lin, tile_cfg=TC)                                   # [M,5d]
-            ops.dynexp_seq(lin, 5 * d, w["qexp"], w["bexp"], dec_len, xin, ld, xo, ld, N, T, d, E)
+            ops.dynexp_seq(lin, lin.stride(0), w["qexp"], w["bexp"], dec_len, xin, ld, xo, ld, N, T, d, E)
             if fill is not None:
-                ops.dynexp_fill_caches(lin, 5 * d, w["qexp"], fill[0].caches[i], N, T, int(fill[1]), fill[0].N, fill[0].T,
+                ops.dynexp_fill_caches(lin, lin.stride(0), w["qexp"], fill[0].caches[i], N, T, int(fill[1]), fill[0].N, fill[0].T,
                                        d, E)
-            ops.layernorm(xo, w["n2w"], w["n2b"], M=M, C_=d, ldx=ld, out=xn)
+            ops.layernorm(xo, w["n2w"], w["n2b"], out=xn)
             ops.gemm(xn, w["wq"], w["bq"], out=q, tile_cfg=TC)
             # the step kernel's row → image map is row / (rows / n_img): the sequence-major rows of an image are contiguous
             ops.cross_attn_step(q, d, kv, kv.shape[2], 2 * i * d, (2 * i + 1) * d, enc_len, row_valid, att, d, M,
@@ -727,15 +720,12 @@ class CaptionerEngine:
                 ops.cross_attn_probs(q, d, kv, kv.shape[2], 2 * i * d, enc_len, row_valid, amap[0 if a_reduce else j], a_w,
                                      M, n_img, S, d, g.num_heads, per_head=a_heads, accumulate=a_reduce and i != min(a_layers),
                                      scale=a_scale)
-            ops.gemm(att, w["wo"], w["bo"], residual=xo, out=xo, M=M, N=d, K=d, lda=d, ldw=d, ldr=ld, ldc=ld,
-                     tile_cfg=TC)
-            ops.layernorm(xo, w["n3w"], w["n3b"], M=M, C_=d, ldx=ld, out=xn)
+            ops.gemm(att, w["wo"], w["bo"], residual=xo, out=xo, tile_cfg=TC)
+            ops.layernorm(xo, w["n3w"], w["n3b"], out=xn)
             ops.gemm(xn, w["f1w"], w["f1b"], out=h, act=ops.ACT_RELU, tile_cfg=TC)
-            ops.gemm(h, w["f2w"], w["f2b"], residual=xo, out=xo, M=M, N=d, K=g.ff, lda=g.ff, ldw=g.ff, ldr=ld,
-                     ldc=ld, tile_cfg=TC)
+            ops.gemm(h, w["f2w"], w["f2b"], residual=xo, out=xo, tile_cfg=TC)
         pre = f(M, d)
-        ops.gemm(ycat, self.dr_w, self.dr_b, residual=ycat[:, (L - 1) * d:], out=pre, M=M, N=d, K=ld, lda=ld,
-                 ldw=ld, ldr=ld, ldc=d, tile_cfg=TC)
+        ops.gemm(ycat, self.dr_w, self.dr_b, residual=ycat[:, (L - 1) * d:], out=pre, tile_cfg=TC)
         ops.layernorm(pre, self.drn_w, self.drn_b, out=xn)
         rc = int(row_chunk) if row_chunk else self.vocab_row_chunk()
         if rc <= 0:

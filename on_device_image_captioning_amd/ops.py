@@ -186,6 +186,61 @@ def _tune_gemm(args: "_hip.GemmArgs", key, out: torch.Tensor, candidates=None) -
     return best
 
 
+def row_view(t: torch.Tensor, what: str, batch: int = 1) -> tuple:
+    """(rows, width, leading dimension, batch stride) of one operand view, from its shape and strides alone.
+    A 2-D view with unit column stride keeps its row stride; any other tensor must be contiguous and is flattened to
+    [numel / width, width].  batch > 1: a 3-D view [batch, rows, width] carries its own batch stride, a 2-D view is
+    shared by all batches (batch stride 0)."""
+    shape, stride = t.shape, t.stride()         # (read once: this runs for every operand of every decoder-step product)
+    nd, bs = len(shape), 0
+    if batch > 1 and nd != 2:
+        if nd != 3 or shape[0] != batch:
+            raise RuntimeError(f"{what}: a batched operand is [batch={batch}, rows, cols] or a shared 2-D view, "
+                               f"got {tuple(shape)}")
+        nd, bs = 2, stride[0]
+    width = shape[-1]
+    if nd == 2:
+        ld = stride[-2]
+        if stride[-1] == 1 and ld >= width:
+            return shape[-2], width, ld, bs
+        if batch > 1 or not t.is_contiguous():
+            raise RuntimeError(f"{what}: column stride {stride[-1]} (must be 1)" if stride[-1] != 1 else
+                               f"{what}: row stride {ld} is smaller than the row width {width}")
+    elif not t.is_contiguous():
+        raise RuntimeError(f"{what}: a view of {nd} dimensions must be contiguous")
+    return t.numel() // width, width, width, 0
+
+
+def gemm_dims(A: torch.Tensor, W: torch.Tensor, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, batch: int = 1) -> tuple:
+    """(M, N, K, lda, ldw, ldr, ldc, batch, strideA, strideW, strideR, strideC) of out = A·Wᵀ (+ residual), read off the
+    views: every operand has unit column stride, A is [M, K] and W [N, K]; `out` and `residual` have at least N columns
+    (only the first N are the product's, the row stride is the leading dimension).  batch == 1: 2-D row-strided views,
+    or contiguous tensors of any rank flattened to rows.  batch > 1: 3-D views [batch, rows, cols] and shared 2-D views,
+    `out` always 3-D.  Reads shapes and strides only (CPU tensors do); raises RuntimeError on what a view cannot say."""
+    M, K, lda, sA = row_view(A, "gemm A", batch)
+    N, Kw, ldw, sW = row_view(W, "gemm W", batch)
+    if Kw != K:
+        raise RuntimeError(f"gemm: A has K = {K} columns, W has {Kw}")
+    ldr = sR = sC = 0
+    ldc = N
+    if out is not None:
+        if batch > 1 and out.dim() != 3:
+            raise RuntimeError("gemm: the `out` of a batched product is [batch, rows, cols]")
+        Mo, No, ldc, sC = row_view(out, "gemm out", batch)
+        if No < N or Mo < M:
+            raise RuntimeError(f"gemm: out [{Mo}, {No}] does not hold the [{M}, {N}] product")
+    elif batch > 1:
+        raise RuntimeError("gemm: a batched product with implicit shapes needs `out`")
+    if residual is not None and residual is out:        # in place on a residual stream: read once
+        ldr, sR = ldc, sC
+    elif residual is not None:
+        Mr, Nr, ldr, sR = row_view(residual, "gemm residual", batch)
+        if Nr < N or Mr < M:
+            raise RuntimeError(f"gemm: residual [{Mr}, {Nr}] does not hold the [{M}, {N}] product")
+    return M, N, K, lda, ldw, ldr, ldc, batch, sA, sW, sR, sC
+
+
 def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
          residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *, act: int = ACT_NONE,
          alpha: float = 1.0, bias_axis: int = 0, out_dtype: Optional[torch.dtype] = None,
@@ -194,10 +249,14 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
          ldc: Optional[int] = None, batch: int = 1, strideA: int = 0, strideW: int = 0, strideBias: int = 0,
          strideR: int = 0, strideC: int = 0, ln_fold: Optional[tuple] = None, tile_cfg: int = -1,
          col_scale: Optional[torch.Tensor] = None, out_scale: float = 1.0,
-         a_ln: Optional[torch.Tensor] = None, ln_eps: float = 1e-5) -> torch.Tensor:
-    """out = act(alpha·A·Wᵀ + bias) + residual.  With no explicit dims, A is [..., K] (flattened to
-    [M,K]) and W is [N,K], both contiguous.  Explicit dims / leading dimensions / batch strides allow
-    strided sub-matrices (elements).  ln_fold = (colsum, eps): W and bias come from fold_layernorm() and
+         a_ln: Optional[torch.Tensor] = None, ln_eps: float = 1e-5, dims: Optional[tuple] = None) -> torch.Tensor:
+    """out = act(alpha·A·Wᵀ + bias) + residual.  With no explicit M, every dimension, leading dimension and batch
+    stride is read off the views (gemm_dims): unit column stride, A [M,K] and W [N,K] of exactly the operand's width,
+    `out` / `residual` possibly wider than N (a slice of a wider buffer); contiguous tensors of any rank are flattened
+    to rows; with `batch` > 1 the operands are [batch, rows, cols] views or shared 2-D ones.  `dims`: what gemm_dims
+    returned for operands of these shapes and strides, kept by a call site that runs every decoder step.  Explicit
+    dims / leading dimensions / batch strides (elements) are taken as given instead, and only together with M.
+    ln_fold = (colsum, eps): W and bias come from fold_layernorm() and
     the rows of A are LayerNorm-ed inside the product (fp32 skinny-M path only).  fp8 / fp16 operands (the
     low-precision backbone mode): `col_scale` fp32 [N] multiplies column n of A·Wᵀ (activation scale x weight channel
     scale) and `out_scale` the result before an fp8 / fp16 output cast.
@@ -205,16 +264,15 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
     A-resident kernels normalise each row in registers — one launch for norm → linear (K = 192 / 384, whole tiles)."""
     if a_ln is not None:
         return _gemm_a_ln(a_ln, W, bias, out, act=act, alpha=alpha, out_dtype=out_dtype, ln_eps=ln_eps, tile_cfg=tile_cfg)
+    if M is None and (not (N is K is lda is ldw is ldr is ldc is None) or strideA or strideW or strideR or strideC):
+        raise RuntimeError("gemm: N / K / leading dimensions / batch strides are explicit only together with M")
     _need_cuda(A, W, bias, residual, out, col_scale)
     if A.dtype != W.dtype:
         raise RuntimeError("A and W must share a dtype")
-    if M is None:
-        K = A.shape[-1]
-        M = A.numel() // K
-        N = W.shape[0]
-        lda, ldw = K, W.shape[-1]
-        if not (A.is_contiguous() and W.is_contiguous()):
-            raise RuntimeError("gemm: implicit-shape operands must be contiguous")
+    if dims is not None:
+        M, N, K, lda, ldw, ldr, ldc, batch, strideA, strideW, strideR, strideC = dims
+    elif M is None:
+        M, N, K, lda, ldw, ldr, ldc, batch, strideA, strideW, strideR, strideC = gemm_dims(A, W, residual, out, batch)
     odt = out_dtype or (out.dtype if out is not None else A.dtype)
     if out is None:
         out = torch.empty((batch, M, N) if batch > 1 else (*A.shape[:-1], N), dtype=odt, device=A.device)
@@ -319,11 +377,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: 
               M: Optional[int] = None, C_: Optional[int] = None, ldx: Optional[int] = None) -> torch.Tensor:
     _need_cuda(x, gamma, beta, out)
     if M is None:
-        C_ = x.shape[-1]
-        M = x.numel() // C_
-        ldx = C_
-        if not x.is_contiguous():
-            raise RuntimeError("layernorm: implicit-shape input must be contiguous")
+        M, C_, ldx, _ = row_view(x, "layernorm input")
     if out is None:
         out = torch.empty((M, C_) if x.dim() < 2 or ldx != C_ else x.shape, dtype=out_dtype, device=x.device)
     with _timed("layernorm", 8.0 * M * C_, M * C_ * (4 + out.element_size())):
@@ -332,32 +386,29 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: 
     return out
 
 
+def _cast(x: torch.Tensor, M: Optional[int], C_: Optional[int], ldx: Optional[int], dtype: torch.dtype, to: str,
+          nbytes: float) -> torch.Tensor:
+    """fp32 [M,C] (row stride ldx; with no explicit M: a 2-D row-strided view or a contiguous tensor) → contiguous [M,C]."""
+    _need_cuda(x)
+    if M is None:
+        M, C_, ldx, _ = row_view(x, "cast_" + to + " input")
+    out = torch.empty((M, C_), dtype=dtype, device=x.device)
+    with _timed("cast_" + to, 0.0, M * C_ * nbytes):
+        _hip.check(getattr(_hip.load(), "odic_cast_f32_to_" + to)(_p(x), ldx, _p(out), C_, M, C_, _stream()),
+                   "odic_cast_f32_to_" + to)
+    return out
+
+
 def cast_bf16(x: torch.Tensor, *, M: Optional[int] = None, C_: Optional[int] = None, ldx: Optional[int] = None
               ) -> torch.Tensor:
     """fp32 [M,C] (row stride ldx) → contiguous bf16 [M,C]."""
-    _need_cuda(x)
-    if M is None:
-        C_ = x.shape[-1]
-        M = x.numel() // C_
-        ldx = C_
-    out = torch.empty((M, C_), dtype=torch.bfloat16, device=x.device)
-    with _timed("cast_bf16", 0.0, M * C_ * 6.0):
-        _hip.check(_hip.load().odic_cast_f32_to_bf16(_p(x), ldx, _p(out), C_, M, C_, _stream()), "odic_cast_f32_to_bf16")
-    return out
+    return _cast(x, M, C_, ldx, torch.bfloat16, "bf16", 6.0)
 
 
 def cast_h2(x: torch.Tensor, *, M: Optional[int] = None, C_: Optional[int] = None, ldx: Optional[int] = None
             ) -> torch.Tensor:
     """fp32 [M,C] (row stride ldx) → contiguous split-fp16 [M,C] (an int32 tensor, see H2_DTYPE)."""
-    _need_cuda(x)
-    if M is None:
-        C_ = x.shape[-1]
-        M = x.numel() // C_
-        ldx = C_
-    out = torch.empty((M, C_), dtype=H2_DTYPE, device=x.device)
-    with _timed("cast_h2", 0.0, M * C_ * 8.0):
-        _hip.check(_hip.load().odic_cast_f32_to_h2(_p(x), ldx, _p(out), C_, M, C_, _stream()), "odic_cast_f32_to_h2")
-    return out
+    return _cast(x, M, C_, ldx, H2_DTYPE, "h2", 8.0)
 
 
 def h2_from_f32(x: torch.Tensor) -> torch.Tensor:
