@@ -24,6 +24,17 @@
  *     strides (in ELEMENTS) are those of the fp32 tensor it replaces; inside a row, every group of 8 consecutive
  *     elements is 32 bytes: [8 x hi | 8 x lo].  Rows start on 32-byte boundaries (base 32-byte aligned, ld % 8 == 0).
  *     All-zero bytes are the value 0, so zero-filled K padding is valid.  |x| saturates at 65504.
+ *   - OUTPUT CASTS: wherever a kernel narrows an fp32 result to `out_dtype` (every odic_gemm epilogue and store path,
+ *     odic_layernorm, odic_patch_merge_layernorm, the two casts), one rule per format, pinned bitwise at ties, subnormals,
+ *     the range limit, ±inf and NaN by tests/test_output_casts_gpu.py:
+ *       rounding   to nearest, ties to even, in every format (subnormal results included; nothing is flushed);
+ *       ODIC_FP8   finite values past the range and ±inf SATURATE to ±448; NaN stays NaN (0x7F / 0xFF);
+ *       ODIC_H2    finite values past the range and ±inf SATURATE to ±65504 (hi = ±65504, lo = 0); NaN stays NaN
+ *                  (hi and lo both NaN);
+ *       ODIC_BF16, ODIC_F16   as IEEE 754 and torch do: values that round past the largest finite one (bf16: from
+ *                  0x7F7F8000; fp16: from 65520) and ±inf give ±inf; NaN stays NaN.  NO saturation: a caller that cannot
+ *                  take an fp16 inf keeps its values in range (DESIGN.md "Output casts").
+ *     A NaN in an input therefore always reaches the output as a NaN, never as a plausible finite value.
  */
 #ifndef ODIC_HIP_H
 #define ODIC_HIP_H
@@ -76,6 +87,9 @@ const char* odic_build_info(void);
  *   >= M / >= N, residual columns [N, ldr), or past the N (M) entries of bias / col_scale / ln_colsum
  *   (test_gemm_f32_folded_layernorm_reads_exactly_n_column_sums): those bytes may hold anything, NaN included.  A refused
  *   launch writes nothing.
+ *   Output cast (OUTPUT CASTS above; the same in the vector, whole-line, scalar-tail and A-resident stores of every family):
+ *   nearest-even; an ODIC_FP8 out saturates at ±448 and an ODIC_H2 out at ±65504; an ODIC_BF16 / ODIC_F16 out overflows to
+ *   ±inf; NaN stays NaN.  The residual is added in fp32 in front of the cast.
  * Replaces every nn.Linear on the path: swin_transformer_mod.py:190,212 (qkv/proj), :94-97
  * (Mlp fc1/fc2), :396 (PatchMerging.reduction), layers.py:49-51,99,154-161,274-276,293,306-307,
  * End_ExpansionNet_v2.py:82,97,134,137.
@@ -149,6 +163,8 @@ int odic_gemm(const odic_gemm_args* args, void* stream);
  *   quantisation scale is folded into gamma / beta by the caller).   C % 4 == 0 (ODIC_H2: % 8), C <= 8192.
  *   `out` has no leading dimension: exactly M·C elements are written, nothing in front or behind; x columns [C, ldx) are
  *   not read (test_layernorm_reads_ldx_and_writes_compact_rows).
+ *   Output cast (OUTPUT CASTS above; the same for odic_patch_merge_layernorm): nearest-even; ODIC_FP8 saturates at ±448,
+ *   ODIC_H2 at ±65504, ODIC_BF16 overflows to ±inf; NaN stays NaN.
  * Replaces swin_transformer_mod.py:309,338 (norm1/norm2), :639 (final norm), layers.py:119,121,
  * 225,228,232 and the reduce norms End_ExpansionNet_v2.py:99,135.
  * ------------------------------------------------------------------------------------------- */
@@ -162,10 +178,12 @@ int odic_copy(const void* src, void* dst, int64_t nbytes, void* stream);
 
 /* Row-strided fp32 → bf16 conversion (feeds fp32 residual streams / caller tensors to the bf16 MFMA
  * GEMM).  x fp32 [M,C] (ldx) → out bf16 [M,C] (ldo); C, ldx, ldo multiples of 4.  out columns [C, ldo) are left untouched,
- * x columns [C, ldx) are not read (test_casts_respect_ldx_and_ldo; the same for the split-fp16 form below). */
+ * x columns [C, ldx) are not read (test_casts_respect_ldx_and_ldo; the same for the split-fp16 form below).
+ * Nearest-even; values from 0x7F7F8000 up and ±inf give ±inf; NaN stays NaN (OUTPUT CASTS above). */
 int odic_cast_f32_to_bf16(const float* x, int64_t ldx, void* out, int64_t ldo, int32_t M, int32_t C,
                           void* stream);
-/* The same into split fp16 (ODIC_H2): C % 8 == 0, ldo % 8 == 0 (elements of 4 bytes), out 32-byte aligned. */
+/* The same into split fp16 (ODIC_H2): C % 8 == 0, ldo % 8 == 0 (elements of 4 bytes), out 32-byte aligned.
+ * hi = fp16(x), lo = fp16(x - hi), both nearest-even; |x| > 65504 and ±inf saturate to ±65504; NaN stays NaN. */
 int odic_cast_f32_to_h2(const float* x, int64_t ldx, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 
 /* PatchMerging gather + LayerNorm(4C)  (swin_transformer_mod.py:386-395):

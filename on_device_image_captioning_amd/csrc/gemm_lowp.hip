@@ -10,6 +10,13 @@
 //                       dequantisation is ONE per-column factor col_scale[n] = sa·sw[n] in the epilogue.
 //   in_dtype ODIC_F16   the attention-output projection (A = fp16 attention output, W fp16); v_mfma_f32_16x16x32_f16.
 //
+// out_cast (include/odic_hip.h "OUTPUT CASTS"; tests/test_output_casts_gpu.py runs every store path below at the edges):
+//   fp8 out   f32x4_to_fp8: nearest-even, saturating at ±448, NaN kept;
+//   fp16 out  the plain (_Float16) conversion in all four store paths — nearest-even, and from 65520 up it gives inf, ON
+//             PURPOSE: that is what IEEE and torch's .half() do, and the mode's references are written with .half().  The
+//             fp16 consumers (window attention reading qkv) do not survive an inf — the caller's scales keep the values in
+//             range (DESIGN.md "Output casts").
+//
 // Same one-block-per-tile structure as gemm_bf16.hip (its header describes it).  The swizzle, the W row permutation,
 // the tile grid and the host's launch helpers are gemm_tile.h's, shared with gemm_bf16.hip and gemm_x3.hip; what differs:
 //   * an LDS row is ROWB = 128 bytes = 128 fp8 K-elements (or 64 fp16): half the staging bytes per FLOP of bf16 —

@@ -29,11 +29,19 @@ __device__ __forceinline__ bf16_raw f32_to_bf16(float f) {
   return __builtin_bit_cast(bf16_raw, b);
 }
 
-// four floats → four OCP e4m3 bytes, saturating at ±448 (the converter alone returns NaN past the range)
+// x limited to [-lim, lim], a NaN kept: fminf / fmaxf and v_med3_f32 all return the OTHER operand for a NaN, which alone
+// would turn a NaN into -lim, a plausible finite value
+__device__ __forceinline__ float clamp_keep_nan(float x, float lim) {
+  const float c = __builtin_amdgcn_fmed3f(x, -lim, lim);
+  return x != x ? x : c;
+}
+
+// four floats → four OCP e4m3 bytes, round to nearest even; finite values past the range and ±inf saturate at ±448 (the
+// converter alone returns NaN past the range), NaN stays NaN (0x7F / 0xFF)
 __device__ __forceinline__ unsigned f32x4_to_fp8(float a, float b, float c, float d) {
   const float lim = 448.0f;
-  a = fminf(fmaxf(a, -lim), lim); b = fminf(fmaxf(b, -lim), lim);
-  c = fminf(fmaxf(c, -lim), lim); d = fminf(fmaxf(d, -lim), lim);
+  a = clamp_keep_nan(a, lim); b = clamp_keep_nan(b, lim);
+  c = clamp_keep_nan(c, lim); d = clamp_keep_nan(d, lim);
   int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
   v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
   return (unsigned)v;
@@ -54,7 +62,7 @@ typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
 struct h2_t { unsigned v; };                    // tag type: one h2 element slot (4 bytes)
 
 __device__ __forceinline__ void h2_split(float x, f16_t& hi, f16_t& lo) {
-  x = __builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f);       // saturate instead of producing inf (inf − inf = NaN)
+  x = clamp_keep_nan(x, 65504.0f);       // saturate instead of producing inf (inf − inf = NaN); a NaN leaves as hi = lo = NaN
   hi = (f16_t)x;
   lo = (f16_t)(x - (float)hi);
 }

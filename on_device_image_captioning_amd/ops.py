@@ -413,10 +413,11 @@ def cast_h2(x: torch.Tensor, *, M: Optional[int] = None, C_: Optional[int] = Non
 
 def h2_from_f32(x: torch.Tensor) -> torch.Tensor:
     """Weight-pack-time split of an fp32 tensor [..., K] (K % 8 == 0) into the h2 layout, on the tensor's device with
-    plain torch ops (exact: two round-to-nearest-even fp16 conversions)."""
+    plain torch ops (exact: two round-to-nearest-even fp16 conversions).  The bits the device writes, NaN payloads aside
+    (csrc/odic_common.h::h2_split): |x| > 65504 and ±inf saturate to ±65504, a NaN leaves as hi = lo = NaN."""
     if x.shape[-1] % 8:
         raise RuntimeError("h2 rows are whole groups of 8 elements")
-    x = x.detach().float().clamp(-65504.0, 65504.0)
+    x = x.detach().float().clamp(-65504.0, 65504.0)         # (torch.clamp keeps a NaN)
     hi = x.to(torch.float16)
     lo = (x - hi.float()).to(torch.float16)
     g = torch.stack([hi.reshape(*x.shape[:-1], -1, 8), lo.reshape(*x.shape[:-1], -1, 8)], dim=-2)   # [..., K/8, 2, 8]
