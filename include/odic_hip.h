@@ -540,7 +540,7 @@ int odic_dec_embed(const int64_t* tokens, const float* embed, const float* pos_t
  *                                            qk_c [T, N, E]   (query_exp[e]·key of that position)
  *   anc int32 [N, T]: for sequence n and position j < pos, the slot (sequence index) whose cache
  *        entry at j belongs to n's history (beam re-ordering without copying caches); position
- *        `pos` itself is always slot n.
+ *        `pos` itself is always slot n.  Entries at positions j >= pos are not read: they may hold anything.
  *   row_valid int32 [N]: 0 → padded row (finished beam): the block contributes 0 (masked rows of
  *        utils/masking.py:37-47), caches are still written.
  *   y_in fp32 [N,d] (ldy_in) → y fp32 [N,d] (ldy):  y = y_in + sel·A' + (1-sel)·B'  (may alias).
@@ -548,7 +548,8 @@ int odic_dec_embed(const int64_t* tokens, const float* embed, const float* pos_t
  *   A launch with *pos outside [0, T) changes nothing (the caches hold T positions; checked on the device).
  *   y columns [d, ldy) are left untouched; lin columns beyond 5d and y_in columns beyond d are not read; the caches are
  *   compact, written only at position *pos, and no entry is read that an earlier position did not write — they need no
- *   clearing (test_dynexp_step_leading_dimensions_and_caches).
+ *   clearing (test_dynexp_step_leading_dimensions_and_caches): cache rows at positions > *pos, rows of slots outside the
+ *   history and forward weights [j][slot][i > j] may hold NaN (tests/test_dynexp_hard_rows_gpu.py).
  */
 int odic_dynexp_step(const float* lin, int64_t ldlin, const float* qexp, const float* bexp,
                      float* cond_c, float* key_c, float* va_c, float* vb_c, float* wfa_c,
@@ -577,7 +578,8 @@ int odic_dec_embed_seq(const int64_t* tokens, const float* embed, const float* p
  *        odic_dynexp_step reads; qexp, bexp fp32 [E, d]; dec_len int32 [N] (clamped to [0, T]).
  *   y_in fp32 [N·T, d] (ldy_in) → y fp32 [N·T, d] (ldy):  y = y_in + sel·A' + (1-sel)·B'  (may alias).
  *   Masking as the reference: causal in position, rows and columns at t >= dec_len[n] masked.  A padded row gets
- *   y = y_in (its weights are 0/(0+eps)), exactly what the step kernel gives with row_valid = 0.
+ *   y = y_in (its weights are 0/(0+eps)), exactly what the step kernel gives with row_valid = 0.  The masks are loop
+ *   bounds: lin rows at positions t >= dec_len[n] are not read and may hold NaN (y_in rows there are read: they are copied).
  *   z[(i,e), j] = (qexp[e]·key_j + cond_i·key_j)/sqrt(d) splits into an E x T and a T x T product per sequence; both,
  *   the normalisers of the forward and backward weights and 16 rows at a time of the re-associated backward sum
  *   (odic_dynexp_step above) stay in LDS; fp32 accumulation throughout.  One 1024-thread block per sequence.
@@ -877,6 +879,8 @@ int odic_beam_reset(const odic_beam_state* st, const odic_embed_args* emb, int32
 /* The per-position caches of odic_dynexp_step for positions 0..P-1 of n_seq known sequences, from the `lin` rows of the
  * whole-sequence pass — what P calls of odic_dynexp_step on those rows would have cached, without computing any y.
  *   lin fp32 [n_seq·P, >=5d] (ldlin), sequence-major as odic_dynexp_seq reads it (row = i·P + t); qexp fp32 [E, d].
+ *   There is no dec_len: every sequence has P valid positions (a shorter prefix is a smaller P), all n_seq·P rows are read
+ *   and nothing behind the last of them is.
  *   Sequence i writes cache slot s = i·rows_per_image of caches laid out for N_cache sequences and T_cache positions
  *   (cond_c, key_c, va_c, vb_c [T_cache, N_cache, d]; qk_c [T_cache, N_cache, E]; wfa_c, wfb_c [T_cache, N_cache, T_cache, E]):
  *     cond/key/va/vb[t][s] = lin columns 0..4d of row i·P + t;   qk[t][s][e] = qexp[e]·key_t;
