@@ -68,7 +68,7 @@ extern "C" {
  *   25: odic_group_beam_step added (diverse beam search: groups with a Hamming penalty).
  *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
- *       odic_beam_reset_prefix, odic_require_beam_step. */
+ *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -924,6 +924,50 @@ int odic_beam_finalize(const odic_beam_state* st, int32_t* order, float* score, 
 int odic_beam_finalize_best(const odic_beam_state* st, int32_t* order, float* score, int32_t* out_tok,
                             int32_t* out_len, int32_t n_img, int32_t beams, int32_t T, int32_t pad_idx,
                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * CIDEr-D on word ids (csrc/cider.hip): the self-critical reward and consensus reranking.
+ *   N-gram key: the n-gram (id_0 … id_{k-1}), k = 1..4, is the uint64 Σ_j (id_j + 1) << (16·j); unused high fields are 0,
+ *   so the order is the index of the highest non-zero field and keys of different orders never collide.  ids lie in
+ *   [0, ODIC_CIDER_MAX_ID].  Keys are compared and sorted as UNSIGNED values (an id >= 32767 in field 3 sets bit 63).
+ *   Workspace: one row of ODIC_CIDER_ROW_WORDS 8-byte words per caption, row pitch ldw words:
+ *     words [0, 512)      uint64  the caption's unique keys, ascending; entries [0, count) are written
+ *     words [512, 1024)   fp64    w = tf·idf of the key at the same index; entries [0, count) are written
+ *     words [1024, 1028)  fp64    per-order norms sqrt(Σ w²), orders 1..4
+ *     word  1028          int32 count, int32 length — `length` is what the Gaussian penalty compares: the number of
+ *                         BIGRAM tokens of the caption, max(L − 1, 0) (the reference's quirk, cider.py's docstring)
+ * --------------------------------------------------------------------------------------------- */
+#define ODIC_CIDER_MAX_LEN 128      /* words per caption: the decoder's position limit */
+#define ODIC_CIDER_MAX_KEYS 512     /* >= 128 + 127 + 126 + 125 = 506 n-grams */
+#define ODIC_CIDER_MAX_ID 65533
+#define ODIC_CIDER_ROW_WORDS 1029
+#define ODIC_CIDER_SIGMA 6.0
+
+/* R captions → their workspace rows, one block per caption: the n-grams of orders 1..4 are sorted in LDS, run-length
+ * encoded into unique keys with their term frequency, and weighted with the IDF of the table.
+ *   tokens int32 [R, ld], lengths int32 [R]: caption r is tokens[r][0 .. L), L = lengths[r] clamped into [0, max_len]; an
+ *   id in the device data is clamped into [0, max_id] — neither is trusted.
+ *   Table: df_keys uint64 [n_table] ascending, df_idf fp64 [n_table], the IDF of each key as the host computed it (the
+ *   kernel takes no logarithm).  A key outside the table gets default_idf; n_table == 0: every key does.
+ *   ODIC_ENULL: tokens, lengths or ws NULL, or n_table > 0 with a table pointer NULL.  ODIC_EINVAL: R <= 0, n_table < 0,
+ *   max_len outside [0, 128], ld < max_len, max_id outside [0, 65533], ldw < ODIC_CIDER_ROW_WORDS, default_idf NaN.  Both
+ *   before any launch.  All stores stay inside words [0, ODIC_CIDER_ROW_WORDS) of the R rows. */
+int odic_cider_vectorize(const int32_t* tokens, int64_t ld, const int32_t* lengths, int32_t R, int32_t max_len,
+                         int32_t max_id, const uint64_t* df_keys, const double* df_idf, int32_t n_table,
+                         double default_idf, uint64_t* ws, int64_t ldw, void* stream);
+
+/* Clipped cosine similarities of vectorised rows, one wave per (hypothesis, reference slot).  Hypothesis h is workspace row
+ * h (the hypotheses are the first H rows); its references are the rows [ref_begin[h], ref_end[h]).  For slot s < max_refs,
+ * with j = ref_begin[h] + s:
+ *   sim[h][s] = 10 · ¼ Σ_{order} ( Σ_g min(w_h[g], w_j[g])·w_j[g] / (norm_h·norm_j) ) · exp(−Δ² / (2σ²))
+ *   over the hypothesis's keys g, the division only where both norms are non-zero, Δ = length_h − length_j, σ = 6;
+ *   sim[h][s] = 0 where j >= ref_end[h] or j lies outside [0, R) (a reference count above max_refs is cut at max_refs).
+ * sim fp64 [H, lds]: every column [0, max_refs) of every row is written, nothing else.  Fixed reduction tree, no atomics:
+ * two runs give the same bits.
+ *   ODIC_ENULL for a NULL pointer; ODIC_EINVAL for R <= 0, H <= 0, H > R, max_refs <= 0, ldw < ODIC_CIDER_ROW_WORDS or
+ *   lds < max_refs.  Both before any launch. */
+int odic_cider_pairs(const uint64_t* ws, int64_t ldw, int32_t R, const int32_t* ref_begin, const int32_t* ref_end,
+                     int32_t H, int32_t max_refs, double* sim, int64_t lds, void* stream);
 
 #ifdef __cplusplus
 }

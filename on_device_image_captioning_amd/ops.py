@@ -755,6 +755,56 @@ def logsoftmax_sample_filtered(logits, ldl, logp_out, ldp, top_val, top_idx, kep
                    "odic_logsoftmax_sample_filtered")
 
 
+def cider_workspace(R: int, device) -> torch.Tensor:
+    """int64 [R, CIDER_ROW_WORDS]: one odic_cider_vectorize row per caption (cider_row_views names its parts)."""
+    return torch.empty(R, _hip.CIDER_ROW_WORDS, dtype=torch.int64, device=device)
+
+
+def cider_row_views(ws: torch.Tensor):
+    """→ (keys int64 [R, 512] — the uint64 bits, weights fp64 [R, 512], norms fp64 [R, 4], meta int32 [R, 2] = count, length)."""
+    nk = _hip.CIDER_MAX_KEYS
+    return (ws[:, :nk], ws[:, nk:2 * nk].view(torch.float64), ws[:, 2 * nk:2 * nk + 4].view(torch.float64),
+            ws[:, 2 * nk + 4:2 * nk + 5].view(torch.int32))
+
+
+def cider_vectorize(tokens: torch.Tensor, lengths: torch.Tensor, ws: torch.Tensor, *, max_id: int = _hip.CIDER_MAX_ID,
+                    df_keys=None, df_idf=None, default_idf: float = 1.0) -> None:
+    """Captions (int32 tokens [R, ld], lengths [R]) → their TF-IDF n-gram rows in `ws` (odic_cider_vectorize).  df_keys: the
+    sorted uint64 keys of the document-frequency table as int64 bits, df_idf their fp64 IDF; without a table every n-gram
+    weighs default_idf."""
+    _need_cuda(tokens, lengths, ws, df_keys, df_idf)
+    if tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or ws.dtype != torch.int64:
+        raise ValueError("cider_vectorize takes int32 tokens and lengths and an int64 workspace")
+    if tokens.dim() != 2 or tokens.stride(1) != 1 or ws.dim() != 2 or ws.stride(1) != 1 or not lengths.is_contiguous():
+        raise ValueError("cider_vectorize takes row-major operands")
+    R, T = tokens.shape
+    if T > _hip.CIDER_MAX_LEN:
+        raise ValueError(f"captions of {T} tokens exceed the limit of {_hip.CIDER_MAX_LEN}")
+    if not 0 <= max_id <= _hip.CIDER_MAX_ID:
+        raise ValueError(f"word ids up to {max_id} exceed the n-gram key's limit of {_hip.CIDER_MAX_ID}")
+    if lengths.numel() != R or ws.shape[0] < R or ws.shape[1] < _hip.CIDER_ROW_WORDS:
+        raise ValueError("cider_vectorize: lengths or workspace do not cover the captions")
+    n_table = 0 if df_keys is None else df_keys.numel()
+    with _timed("cider_vectorize", 0.0, R * (T * 4.0 + 16.0 * _hip.CIDER_MAX_KEYS)):
+        _hip.check(_hip.load().odic_cider_vectorize(_p(tokens), tokens.stride(0), _p(lengths), R, T, max_id, _p(df_keys),
+                                                    _p(df_idf), n_table, float(default_idf), _p(ws), ws.stride(0),
+                                                    _stream()), "odic_cider_vectorize")
+
+
+def cider_pairs(ws: torch.Tensor, ref_begin: torch.Tensor, ref_end: torch.Tensor, sim: torch.Tensor) -> None:
+    """sim fp64 [H, max_refs]: CIDEr-D of hypothesis h (row h of `ws`) against each of the rows [ref_begin[h], ref_end[h]);
+    unused slots are written as 0 (odic_cider_pairs)."""
+    _need_cuda(ws, ref_begin, ref_end, sim)
+    if ref_begin.dtype != torch.int32 or ref_end.dtype != torch.int32 or sim.dtype != torch.float64:
+        raise ValueError("cider_pairs takes int32 row ranges and an fp64 output")
+    H, max_refs = sim.shape
+    if ref_begin.numel() != H or ref_end.numel() != H or sim.stride(1) != 1:
+        raise ValueError("cider_pairs: one row range per hypothesis, a row-major output")
+    with _timed("cider_pairs", 0.0, 16.0 * _hip.CIDER_MAX_KEYS * H * (1 + max_refs)):
+        _hip.check(_hip.load().odic_cider_pairs(_p(ws), ws.stride(0), ws.shape[0], _p(ref_begin), _p(ref_end), H, max_refs,
+                                                _p(sim), sim.stride(0), _stream()), "odic_cider_pairs")
+
+
 def ensemble_logprobs(logits_list, out: torch.Tensor) -> None:
     """out[n] = log(mean_m softmax(logits_m[n])) — ensemble_captioning_model.py:66-83."""
     _need_cuda(out, *logits_list)
