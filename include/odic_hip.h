@@ -68,7 +68,8 @@ extern "C" {
  *   25: odic_group_beam_step added (diverse beam search: groups with a Hamming penalty).
  *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
- *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs. */
+ *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
+ *       odic_lcs_pairs. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -968,6 +969,52 @@ int odic_cider_vectorize(const int32_t* tokens, int64_t ld, const int32_t* lengt
  *   lds < max_refs.  Both before any launch. */
 int odic_cider_pairs(const uint64_t* ws, int64_t ldw, int32_t R, const int32_t* ref_begin, const int32_t* ref_end,
                      int32_t H, int32_t max_refs, double* sim, int64_t lds, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BLEU-1..4 and ROUGE-L on word ids (csrc/caption_metrics.hip): the integer parts of both metrics; the
+ * scores are a few fp64 operations on them (metrics.py).  Both kernels reduce integers in a fixed tree, without atomics:
+ * two runs give the same bits.
+ * --------------------------------------------------------------------------------------------- */
+#define ODIC_BLEU_STAT_WORDS 12
+
+/* The BLEU components of Q queries, one wave per query.  Query q is (hyp_row[q], ref_begin[q], ref_end[q]): workspace row
+ * hyp_row[q] is the hypothesis, the rows [ref_begin[q], ref_end[q]) are its references.  Any row may be the hypothesis of
+ * any number of queries (one query per image for evaluation, N·N single-reference queries per image for pairwise scores).
+ *   REQUIRED MODE of the workspace: the rows odic_cider_vectorize writes with n_table = 0 and default_idf = 1.0.  The stored
+ *   weight is then the term frequency, an exact small integer in fp64, and is read as one.  With any other weights the
+ *   counts are meaningless (nothing is read or written out of bounds).
+ *   lengths int32 [R]: the captions' lengths again (the row records only the bigram count), clamped into [0, max_len] as
+ *   vectorize clamps them; pass the max_len the rows were vectorised with.
+ *   stats int32 [Q, lds], words [0, ODIC_BLEU_STAT_WORDS) of every row are written, nothing else.  With L the hypothesis
+ *   length:
+ *     [0..3]  correct_k, k = 1..4: Σ over the hypothesis's unique k-grams of min(tf_hyp, max over the references of tf_ref)
+ *             — clipped against the MAXIMUM over the references, not their sum
+ *     [4..7]  guess_k = max(0, L − k + 1)
+ *     [8]     testlen = L
+ *     [9]     the closest reference length: the l that minimises (|l − L|, l), a tie going to the shorter reference
+ *     [10]    the shortest reference length        [11]  the sum of the reference lengths (modulo 2^32)
+ *   A reference index outside [0, R) is skipped, never dereferenced.  An empty range (or one that lies outside [0, R))
+ *   gives 0 in [0..3] and [9..11].  A hyp_row outside [0, R) gives a row of twelve zeros.
+ *   ODIC_ENULL for a NULL pointer; ODIC_EINVAL for Q <= 0, R <= 0, ldw < ODIC_CIDER_ROW_WORDS, lds < ODIC_BLEU_STAT_WORDS
+ *   or max_len outside [0, 128].  Both before any launch. */
+int odic_bleu_stats(const uint64_t* ws, int64_t ldw, const int32_t* lengths, int32_t R, int32_t max_len,
+                    const int32_t* hyp_row, const int32_t* ref_begin, const int32_t* ref_end, int32_t Q, int32_t* stats,
+                    int64_t lds, void* stream);
+
+/* Longest-common-subsequence lengths straight from token rows, one wave per (hypothesis, reference slot), bit-parallel
+ * (Hyyrö's bit-vector recurrence on 128 bits, the match masks from two ballots per hypothesis token).
+ *   tokens int32 [R, ld], lengths int32 [R]: caption r is tokens[r][0 .. L), L = lengths[r] clamped into [0, max_len].  The
+ *   ids may be ANY int32: words are only compared, there is no key and no id limit.
+ *   Rows [0, H) are the hypotheses; the references of hypothesis h are the rows [ref_begin[h], ref_end[h]) — the convention
+ *   of odic_cider_pairs.  For slot s < max_refs, with j = ref_begin[h] + s:
+ *     lcs[h][s] = the LCS length of rows h and j; 0 where either is empty;
+ *     lcs[h][s] = 0 where j >= ref_end[h] or j lies outside [0, R) (a reference count above max_refs is cut at max_refs).
+ *   lcs int32 [H, ldl]: every column [0, max_refs) of every row is written, nothing else.
+ *   ODIC_ENULL for a NULL pointer; ODIC_EINVAL for R <= 0, H <= 0, H > R, max_refs <= 0, ldl < max_refs, max_len outside
+ *   [0, 128] or ld < max_len.  Both before any launch. */
+int odic_lcs_pairs(const int32_t* tokens, int64_t ld, const int32_t* lengths, int32_t R, int32_t max_len,
+                   const int32_t* ref_begin, const int32_t* ref_end, int32_t H, int32_t max_refs, int32_t* lcs, int64_t ldl,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -142,9 +142,12 @@ _SIGNATURES = {
     "odic_jpeg_decode_progressive_scaled": (C.c_int, [C.POINTER(JpegProgBatch), _P, _P, C.c_size_t, _P]),
     "odic_cider_vectorize": (C.c_int, [_P, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, C.c_double, _P, _I64, _P]),
     "odic_cider_pairs": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _I32, _P, _I64, _P]),
+    "odic_bleu_stats": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P]),
+    "odic_lcs_pairs": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _I64, _P]),
 }
 
 CIDER_MAX_LEN, CIDER_MAX_KEYS, CIDER_MAX_ID, CIDER_ROW_WORDS = 128, 512, 65533, 1029      # ODIC_CIDER_*
+BLEU_STAT_WORDS = 12                                                                      # ODIC_BLEU_STAT_WORDS
 
 #: every symbol include/odic_hip.h declares
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

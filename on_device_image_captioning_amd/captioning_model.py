@@ -569,14 +569,15 @@ class CaptioningModel(nn.Module):
         return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, num_candidates, source="sampling", sos_idx, eos_idx,
-                          max_seq_len=20, corpus=None, **search_args):
+                          max_seq_len=20, corpus=None, metric="cider", **search_args):
         """One caption per image by consensus: draw `num_candidates` candidates, score each against the
         others under CIDEr-D on the device (reward.consensus_rerank) and return the one that agrees most with the rest.
         source='sampling': get_batch_multiple_sampled_prediction(num_outputs=num_candidates, **search_args) — temperature,
         top_k, top_p; source='diverse': diverse_beam_search(num_groups=num_candidates, **search_args) — group_size (default
         1), diversity_penalty and the search controls.  `corpus`: a reward.CiderCorpus whose IDF table weighs the n-grams
-        (default: every n-gram counts 1).  → (captions: one token list per image, scores fp64 [B]: its mean CIDEr-D against
-        the other candidates).  `self.last_consensus` keeps (candidates, best_index [B], scores [B, N])."""
+        (default: every n-gram counts 1).  `metric`: 'cider', or 'bleu4' / 'rouge_l' for the pairwise sentence BLEU-4 or
+        ROUGE-L F as the utility (§4.20; no corpus with them).  → (captions: one token list per image, scores fp64 [B]: its
+        mean utility against the other candidates).  `self.last_consensus` keeps (candidates, best_index [B], scores [B, N])."""
         from . import reward as _reward
         if num_candidates < 1:
             raise ValueError("consensus_caption needs num_candidates >= 1")
@@ -589,7 +590,7 @@ class CaptioningModel(nn.Module):
                                                 max_seq_len=max_seq_len, **search_args)
         else:
             raise ValueError("source must be 'sampling' or 'diverse'")
-        index, scores = _reward.consensus_rerank(cands, corpus=corpus, eos_idx=eos_idx)
+        index, scores = _reward.consensus_rerank(cands, corpus=corpus, eos_idx=eos_idx, metric=metric)
         self.last_consensus = (cands, index, scores)
         best = index.tolist()
         return [cands[b][best[b]] for b in range(len(cands))], scores.gather(1, index[:, None])[:, 0]
@@ -645,9 +646,10 @@ class Captioner:
     def diverse_beam_search(self, *a, **k):
         return self.model.diverse_beam_search(*a, **k)
 
-    def consensus_caption(self, enc_x, enc_x_num_pads=[0], **k):
+    def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, metric="cider", **k):
         """CaptioningModel.consensus_caption with this object's `beam_search_args` (sos_idx, eos_idx, beam_max_seq_len)
         unless the call names its own."""
+        k["metric"] = metric
         b = self.beam_search_args
         for arg, key in (("sos_idx", "sos_idx"), ("eos_idx", "eos_idx"), ("max_seq_len", "beam_max_seq_len")):
             if key in b:

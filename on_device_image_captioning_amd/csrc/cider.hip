@@ -2,40 +2,18 @@
 // every caption into its sorted TF-IDF n-gram vector, one block per caption with the caption's 512 key slots in LDS for
 // the whole sort; odic_cider_pairs takes the clipped cosine of a hypothesis and one reference per wave.  Integer keys,
 // fp64 weights, fixed reduction trees, no atomics: two runs give the same bits.
-#include "odic_common.h"
+#include "cider_row.h"
 
 namespace {
 
-constexpr int NK = ODIC_CIDER_MAX_KEYS;        // key slots per caption: 128 + 127 + 126 + 125 = 506 n-grams at most
-constexpr int MAXLEN = ODIC_CIDER_MAX_LEN;
-constexpr int ROW = ODIC_CIDER_ROW_WORDS;
 constexpr int VT = NK / 2, VW = VT / 64;       // vectorize: one thread per compare-exchange of the bitonic network
 constexpr int PW = 4;                          // pairs: waves (= pairs) per block
 constexpr unsigned long long NOKEY = ~0ull;    // sorts behind every key (a field holds id + 1 <= 65534, never 0xFFFF)
-
-// a workspace row, in 8-byte words: [keys NK | weights NK | norms 4 | {count, length}]
-struct Row {
-  unsigned long long* keys; double* w; double* norms; int* meta;
-  __device__ __forceinline__ Row(unsigned long long* base) : keys(base), w((double*)(base + NK)),
-      norms((double*)(base + 2 * NK)), meta((int*)(base + 2 * NK + 4)) {}
-};
-
-__device__ __forceinline__ int key_order(unsigned long long k) { return (k >> 48) ? 3 : (k >> 32) ? 2 : (k >> 16) ? 1 : 0; }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// index of `key` in the ascending array a[0, n), or -1
-__device__ __forceinline__ int find_key(const unsigned long long* __restrict__ a, int n, unsigned long long key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && a[lo] == key) ? lo : -1;
 }
 
 __global__ __launch_bounds__(VT) void cider_vectorize_kernel(const int* __restrict__ tokens, long ld,

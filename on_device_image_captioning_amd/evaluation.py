@@ -7,7 +7,8 @@ model: that is 100 x the scorer's `compute_score` output (≈1.404 on Karpathy t
     README units = 100 x CiderD.compute_score(...)[0]        (a caption identical to its only
                                                                reference scores 10.0 → 1000 README units)
 
-and "±0.1 CIDEr-D" means ±0.001 of `compute_score`.  Host-side, not on the GPU hot path.
+and "±0.1 CIDEr-D" means ±0.001 of `compute_score`.  Host-side, not on the GPU hot path — except `coco_scores`, whose BLEU
+and ROUGE-L rows come from the device (metrics.py).
 """
 from __future__ import annotations
 
@@ -65,3 +66,22 @@ def caption_agreement(candidates: Sequence[Sequence[int]], reference_captions: S
             "cider_d_delta": round(self_score - score, 3), "unit": "README units = 100 x compute_score",
             "images": len(candidates), "identical": round(same / max(1, len(candidates)), 4),
             "mean_prefix": round(pref / max(1, tot), 4)}
+
+
+def coco_scores(candidates: Sequence[Sequence[int]], references: Sequence[Sequence[Sequence[int]]],
+                idx2word: Optional[Sequence] = None) -> Dict[str, float]:
+    """The part of COCOEvalCap's table (test.py:230-257) that needs no Java, for one candidate caption per image against
+    that image's references, all token-id lists incl. SOS/EOS (stripped as prediction_words strips them):
+    {"Bleu_1" … "Bleu_4", "ROUGE_L", "CIDEr"}, each in its scorer's `compute_score` units.  BLEU and ROUGE-L are computed
+    on the device (metrics.py; a GPU is required), CIDEr by the host CiderD as in cider_d_readme."""
+    from . import metrics
+    if len(candidates) != len(references):
+        raise ValueError("one candidate per image")
+    cand = [list(c)[1:-1] for c in candidates]
+    refs = [[list(r)[1:-1] for r in per] for per in references]
+    bleu, _ = metrics.bleu(cand, refs)
+    rouge, _ = metrics.rouge_l(cand, refs)
+    out = {f"Bleu_{k + 1}": bleu[k] for k in range(4)}
+    out["ROUGE_L"] = rouge
+    out["CIDEr"] = cider_d_readme(candidates, references, idx2word) / README_SCALE
+    return out

@@ -805,6 +805,47 @@ def cider_pairs(ws: torch.Tensor, ref_begin: torch.Tensor, ref_end: torch.Tensor
                                                 _p(sim), sim.stride(0), _stream()), "odic_cider_pairs")
 
 
+def bleu_stats(ws: torch.Tensor, lengths: torch.Tensor, max_len: int, hyp_row: torch.Tensor, ref_begin: torch.Tensor,
+               ref_end: torch.Tensor, stats: torch.Tensor) -> None:
+    """stats int32 [Q, >= 12]: the BLEU components of query q = (hypothesis row hyp_row[q], reference rows [ref_begin[q],
+    ref_end[q])) of the workspace `ws` (odic_bleu_stats).  `ws` must hold the rows cider_vectorize writes WITHOUT a table
+    and with default_idf = 1.0; `lengths` and `max_len` are the ones it was given."""
+    _need_cuda(ws, lengths, hyp_row, ref_begin, ref_end, stats)
+    if any(t.dtype != torch.int32 for t in (lengths, hyp_row, ref_begin, ref_end, stats)) or ws.dtype != torch.int64:
+        raise ValueError("bleu_stats takes an int64 workspace and int32 lengths, queries and output")
+    if ws.dim() != 2 or ws.stride(1) != 1 or stats.dim() != 2 or stats.stride(1) != 1 or not lengths.is_contiguous():
+        raise ValueError("bleu_stats takes row-major operands")
+    R, Q = ws.shape[0], stats.shape[0]
+    if lengths.numel() != R or ws.shape[1] < _hip.CIDER_ROW_WORDS or stats.shape[1] < _hip.BLEU_STAT_WORDS:
+        raise ValueError("bleu_stats: lengths, workspace or output rows are too short")
+    if any(t.numel() != Q or not t.is_contiguous() for t in (hyp_row, ref_begin, ref_end)):
+        raise ValueError("bleu_stats: one hypothesis row and one row range per query")
+    with _timed("bleu_stats", 0.0, 16.0 * _hip.CIDER_MAX_KEYS * 2 * Q):
+        _hip.check(_hip.load().odic_bleu_stats(_p(ws), ws.stride(0), _p(lengths), R, int(max_len), _p(hyp_row),
+                                               _p(ref_begin), _p(ref_end), Q, _p(stats), stats.stride(0), _stream()),
+                   "odic_bleu_stats")
+
+
+def lcs_pairs(tokens: torch.Tensor, lengths: torch.Tensor, ref_begin: torch.Tensor, ref_end: torch.Tensor,
+              lcs: torch.Tensor) -> None:
+    """lcs int32 [H, max_refs]: the longest-common-subsequence length of caption h (row h of int32 tokens [R, ld], lengths
+    [R]) with each of the rows [ref_begin[h], ref_end[h]); unused slots are written as 0 (odic_lcs_pairs)."""
+    _need_cuda(tokens, lengths, ref_begin, ref_end, lcs)
+    if any(t.dtype != torch.int32 for t in (tokens, lengths, ref_begin, ref_end, lcs)):
+        raise ValueError("lcs_pairs takes int32 operands")
+    if tokens.dim() != 2 or tokens.stride(1) != 1 or lcs.dim() != 2 or lcs.stride(1) != 1 or not lengths.is_contiguous():
+        raise ValueError("lcs_pairs takes row-major operands")
+    R, T = tokens.shape
+    H, max_refs = lcs.shape
+    if T > _hip.CIDER_MAX_LEN:
+        raise ValueError(f"captions of {T} tokens exceed the limit of {_hip.CIDER_MAX_LEN}")
+    if lengths.numel() != R or any(t.numel() != H or not t.is_contiguous() for t in (ref_begin, ref_end)):
+        raise ValueError("lcs_pairs: one length per caption, one row range per hypothesis")
+    with _timed("lcs_pairs", 0.0, 8.0 * T * H * max_refs):
+        _hip.check(_hip.load().odic_lcs_pairs(_p(tokens), tokens.stride(0), _p(lengths), R, T, _p(ref_begin), _p(ref_end), H,
+                                              max_refs, _p(lcs), lcs.stride(0), _stream()), "odic_lcs_pairs")
+
+
 def ensemble_logprobs(logits_list, out: torch.Tensor) -> None:
     """out[n] = log(mean_m softmax(logits_m[n])) — ensemble_captioning_model.py:66-83."""
     _need_cuda(out, *logits_list)

@@ -233,13 +233,20 @@ class ReinforceCiderReward:
         return loss, reward, reward_base
 
 
-def consensus_rerank(captions, *, corpus: Optional[CiderCorpus] = None, eos_idx: int):
+def consensus_rerank(captions, *, corpus: Optional[CiderCorpus] = None, eos_idx: int, metric: str = "cider"):
     """Minimum-Bayes-risk selection under CIDEr-D: of the N candidates of every image, the one that agrees most with the
     other N − 1.  captions: list[B][N] of id lists as the sampler and the searches return them (SOS first); a candidate is
     scored as caption[1:], with EOS appended where the search was cut before it.  Without a corpus every n-gram has IDF 1 (a
     clipped term-frequency cosine; a corpus of this one image would give every n-gram IDF 0); with one, its table weighs
     them.  → (best_index int64 [B], scores fp64 [B, N]) on the device; ties go to the lower index, N = 1 gives index 0 and
-    score 0, duplicate candidates are legal."""
+    score 0, duplicate candidates are legal.
+    metric 'bleu4' or 'rouge_l' takes the pairwise sentence BLEU-4, or the pairwise ROUGE-L F, of candidate i against
+    candidate j as its single reference in place of CIDEr-D (metrics.pairwise); neither has an IDF, so a
+    corpus with them is refused."""
+    if metric not in ("cider", "bleu4", "rouge_l"):
+        raise ValueError("metric must be 'cider', 'bleu4' or 'rouge_l'")
+    if metric != "cider" and corpus is not None:
+        raise ValueError(f"metric {metric!r} has no IDF: it takes no corpus")
     B = len(captions)
     N = len(captions[0]) if B else 0
     if B == 0 or N == 0 or any(len(c) != N for c in captions):
@@ -251,15 +258,19 @@ def consensus_rerank(captions, *, corpus: Optional[CiderCorpus] = None, eos_idx:
     H = B * N
     if N == 1:
         return torch.zeros(B, dtype=torch.int64, device=dv), torch.zeros(B, 1, dtype=torch.float64, device=dv)
-    ws = ops.cider_workspace(H, dv)
-    if corpus is not None:
-        ops.cider_vectorize(tok, lens, ws, df_keys=corpus.df_keys, df_idf=corpus.df_idf, default_idf=corpus.log_images)
+    if metric != "cider":
+        from . import metrics
+        sim = metrics.pairwise(tok, lens, B, N, metric)
     else:
-        ops.cider_vectorize(tok, lens, ws, default_idf=1.0)
-    begin = (torch.arange(B, device=dv, dtype=torch.int32) * N).repeat_interleave(N)
-    sim = torch.empty(H, N, dtype=torch.float64, device=dv)
-    ops.cider_pairs(ws, begin, begin + N, sim)
-    sim = sim.view(B, N, N)
+        ws = ops.cider_workspace(H, dv)
+        if corpus is not None:
+            ops.cider_vectorize(tok, lens, ws, df_keys=corpus.df_keys, df_idf=corpus.df_idf, default_idf=corpus.log_images)
+        else:
+            ops.cider_vectorize(tok, lens, ws, default_idf=1.0)
+        begin = (torch.arange(B, device=dv, dtype=torch.int32) * N).repeat_interleave(N)
+        sim = torch.empty(H, N, dtype=torch.float64, device=dv)
+        ops.cider_pairs(ws, begin, begin + N, sim)
+        sim = sim.view(B, N, N)
     off_diagonal = ~torch.eye(N, dtype=torch.bool, device=dv)
     # summed in ascending order (the similarities are >= 0, the dropped diagonal sorts first): candidates that are equal
     # get scores equal to the bit wherever they stand, so their tie is a tie
