@@ -856,7 +856,9 @@ __device__ __forceinline__ unsigned char clamp255(int v) { return (unsigned char
 // One output pixel.  kScaled = false is the full-size decode (lg = 0).  At scale 1 / 2^lg the output is
 // ceil(W / 2^lg) × ceil(H / 2^lg) and the planes hold the transform sizes of scaled_sizes(): 4:4:4 and, for lg > 0,
 // 4:2:0 read chroma on the luma grid; 4:2:2 upsamples horizontally (jdsample.c): fancy while the chroma transform is
-// larger than 1x1 and the component's downsampled width ceil(W·nc / 16) is above 2, else by replication.
+// larger than 1x1 and the component's downsampled width ceil(W·nc / 16) is above 2, else by replication.  The width
+// rule holds at full size too, for 4:2:2 and 4:2:0 alike: chroma at most two samples wide (a frame at most 4 pixels
+// wide) is replicated in both directions, without the triangle filter.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int img, int lg,
                                             unsigned char* __restrict__ out, int* __restrict__ status) {
@@ -884,15 +886,14 @@ __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int i
     const int dw = kScaled ? (h.width * nc + 15) >> 4 : (W + 1) >> 1;      // the same number at lg = 0
     const int c = x >> 1, odd = x & 1;
     const int cn = odd ? min(c + 1, dw - 1) : max(c - 1, 0);
-    if (sampling == 1) {
+    if (dw <= 2 || (kScaled && nc == 1)) {                  // jdsample.c: h2v1_upsample / h2v2_upsample, no filter in
+      const long r = (long)(sampling == 2 ? y >> 1 : y) * cw;   // either direction (a frame at most 4 pixels wide)
+      cb = Cb[r + c];
+      cr = Cr[r + c];
+    } else if (sampling == 1) {
       const long r = (long)y * cw;
-      if (kScaled && lg > 0 && (nc == 1 || dw <= 2)) {
-        cb = Cb[r + c];
-        cr = Cr[r + c];
-      } else {
-        cb = (3 * Cb[r + c] + Cb[r + cn] + 1 + odd) >> 2;
-        cr = (3 * Cr[r + c] + Cr[r + cn] + 1 + odd) >> 2;
-      }
+      cb = (3 * Cb[r + c] + Cb[r + cn] + 1 + odd) >> 2;
+      cr = (3 * Cr[r + c] + Cr[r + cn] + 1 + odd) >> 2;
     } else {
       const int dh = (H + 1) >> 1;
       const int rr = y >> 1;

@@ -345,6 +345,8 @@ def model_rgb(blob):
         if hy == 1:
             return P[:H, :W]
         c = x >> 1
+        if dw <= 2:                                       # jdsample.c: a component at most two samples wide is
+            return P[(y >> 1) if vy == 2 else y][:, c]    # replicated (h2v1_upsample / h2v2_upsample), not filtered
         cn = np.where(x & 1, np.minimum(c + 1, dw - 1), np.maximum(c - 1, 0))
         if vy == 1:                                       # h2v1_fancy_upsample
             a, b = P[:H][:, c], P[:H][:, cn]
