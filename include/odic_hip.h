@@ -673,6 +673,21 @@ int odic_logsoftmax_sample(const float* logits, int64_t ldl, float* logp_out, in
                            int32_t* top_idx, int32_t N, int32_t V, int32_t k, uint64_t seed,
                            const int32_t* pos, void* stream);
 
+/* odic_logsoftmax_sample that also reports the PERTURBED scores its draws were ranked by — what stochastic beam search
+ * (odic_stochastic_beam_step below) ranks whole captions by.  An addition to ABI 26.
+ *   top_pert fp32 [N, k], compact: top_pert[n][r] = (x[v_r] + Gumbel(v_r)) − logsumexp(x), v_r = top_idx[n][r]: the fp32 sum
+ *   the draw order was decided on, minus the row's one shared log-sum-exp.  Non-increasing along r.  Within
+ *   2e-6 + 2^-23·(|x| + |logsumexp| + |Gumbel|) of the exact value for the same noise bits.
+ *   top_idx, top_val and logp_out are bit for bit odic_logsoftmax_sample's for the same seed and *pos (one kernel serves
+ *   both; odic_logsoftmax_sample is the call with top_pert not stored).
+ *   A slot filled by the short-row rule (a masked word, top_val -inf) has top_pert -inf.
+ * Refusals (before any launch, nothing written), padding and containment are odic_logsoftmax_sample's: ODIC_ENULL for a
+ * NULL logits, top_val, top_idx or top_pert; ODIC_EINVAL for N, V or k < 1, k > 16 or k > V.  All stores stay inside
+ * top_val, top_idx, top_pert and columns [0, V) of logp_out; logits columns [V, ldl) are not read. */
+int odic_logsoftmax_sample_scored(const float* logits, int64_t ldl, float* logp_out, int64_t ldp, float* top_val,
+                                  int32_t* top_idx, float* top_pert, int32_t N, int32_t V, int32_t k, uint64_t seed,
+                                  const int32_t* pos, void* stream);
+
 /* Sampling controls: odic_logsoftmax_sample's draws from a temperature-scaled top-k / nucleus (top-p) subset of the row. */
 typedef struct odic_sample_filter {
   float   inv_temperature; /* 1/temperature, rounded once to fp32 by the caller; finite, > 0 */
@@ -865,6 +880,42 @@ int odic_require_beam_step(const float* cand_val, const int32_t* cand_idx, int32
                            const float* logp, int64_t ldl, const int64_t* required, int32_t n_required,
                            const odic_beam_state* st, const odic_embed_args* emb,
                            int32_t n_img, int32_t bank_beams, int32_t T, int64_t eos_idx, int32_t V, void* stream);
+
+/* The step of STOCHASTIC beam search (Kool, van Hoof & Welling, "Stochastic Beams and Where to Find Them", ICML 2019;
+ * DESIGN.md §4.21), the sibling of odic_beam_step on the same state: after the last step the `beams` rows of an image are
+ * `beams` DISTINCT captions sampled from the model without replacement, row 0 an exact sample.  An addition to ABI 26; the
+ * state struct is unchanged, the rows' perturbed scores travel in an argument of their own.
+ *   cand_val / cand_idx / cand_pert [n_img·beams, beams], compact: as odic_logsoftmax_sample_scored writes them with
+ *   k = beams (cand_pert[.][0] the row's largest).  gscore fp32 [n_img·beams], compact, in and out: the perturbed score
+ *   G of every row; it need not be initialised before the call with *pos == 0.
+ * Let row j of an image have phi_j = cumul[j] and G_j = gscore[j].
+ *   Offers.  A live row is one with cumul > -inf.  A live growing row offers each of its candidates r with
+ *   cand_val > -inf.  A live finished row (has_eos) offers exactly one candidate, itself: the word of its rank-0 slot at
+ *   log-prob 0, as odic_beam_step keeps a finished row, with G~ = G_j.  At *pos == 0 only row 0 offers, with phi = G = 0.
+ *   Perturbed score of candidate r of a growing row, G~_r = -log(e^-G_j − e^-Z + e^-g_r) (Z the row's largest g), in fp32 as
+ *     d = cand_pert[r] − cand_pert[0]                         (<= 0; phi_j cancels)
+ *     d == 0:  G~_r = G_j exactly                             (rank 0, and any exact tie with it)
+ *     else     u = (G_j − phi_j) − cand_pert[r];  v = u + log1mexp(d);  G~_r = G_j − max(v, 0) − log1p(exp(−|v|))
+ *     with log1mexp(d) = d > −ln 2 ? log(−expm1(d)) : log1p(−exp(d)): neither e^-G nor e^-Z is ever formed.
+ *   Selection.  The `beams` best offers of the image: G~ descending, then source row ascending, then rank ascending.  New
+ *   row i takes the parent, the word and the word's OWN log-prob cand_val (cumul is re-summed as in odic_beam_step), and
+ *   gscore[i] = G~.  Rows leave every step sorted by G~; every child's G~ <= its parent's G, the best child of a row
+ *   inherits it bit for bit, and the live rows of an image hold different prefixes.  With fewer offers than beams the
+ *   remaining slots become EMPTY rows by odic_require_beam_step's convention (parent = the slot itself, row 0 at *pos == 0;
+ *   word = EOS; stored log-prob -inf, so cumul = -inf and has_eos = 1) with gscore -inf.
+ * Everything after the choice (permutation of prefixes / log-probs / ancestors, embedding tail, n_elem, has_eos,
+ * row_valid, next_tok, *pos, *done, the arrival counter, the no-op at *pos == T − 1) is odic_beam_step's, with its limits.
+ * The inclusion probability of a caption of log-prob phi in the sample, given the threshold kappa = the G of the first
+ * caption NOT returned, is 1 − exp(−exp(phi − kappa)) (Kool et al., eq. 15 ff.); this library reports G and leaves that to
+ * the caller.
+ *   ODIC_EINVAL — one refusal code for this entry point — before any launch and with nothing written: beams outside
+ *   [1, 16], T outside [2, 128], n_img outside [1, 32767], eos_idx < 0 (it is the word of an empty row, embedded like any
+ *   other: the caller keeps it inside the embedding table), cand_val, cand_idx, cand_pert, gscore, st or one of its arrays
+ *   NULL, an emb with a NULL table or d / pos_rows < 1.  All stores stay inside the compact state arrays, gscore and
+ *   columns [0, d) of the beams·n_img rows of emb->y (tests/test_stochastic_beam_step_gpu.py). */
+int odic_stochastic_beam_step(const float* cand_val, const int32_t* cand_idx, const float* cand_pert, float* gscore,
+                              const odic_beam_state* st, const odic_embed_args* emb, int32_t n_img, int32_t beams,
+                              int32_t T, int64_t eos_idx, void* stream);
 
 /* Initial state of a search (captioning_model.py:117-125): tokens[:, :, 0] = sos, logprobs[:, :, 0] = 0,
  * next_tok = sos, row_valid = 1, *pos = *done = *ctr = 0; with emb, also the input of position 0 (the embedded

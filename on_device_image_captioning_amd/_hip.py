@@ -118,6 +118,7 @@ _SIGNATURES = {
     "odic_cross_attn_probs": (C.c_int, [_P, _I64, _P, _I64, _I32, _P, _P, _P, _I64] + [_I32] * 7 + [_F, _P]),
     "odic_logsoftmax_topk": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _P]),
     "odic_logsoftmax_sample": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, C.c_uint64, _P, _P]),
+    "odic_logsoftmax_sample_scored": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _I32, _I32, _I32, C.c_uint64, _P, _P]),
     "odic_logsoftmax_sample_filtered": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _I32, _I32, _I32, C.POINTER(SampleFilter),
                                                   C.c_uint64, _P, _P]),
     "odic_ensemble_logprobs": (C.c_int, [C.POINTER(C.c_void_p), _I32, _I64, _P, _I64, _I32, _I32, _P]),
@@ -128,6 +129,8 @@ _SIGNATURES = {
                                        _F, _P]),
     "odic_require_beam_step": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I32, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32,
                                          _I32, _I32, _I64, _I32, _P]),
+    "odic_stochastic_beam_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64,
+                                            _P]),
     "odic_beam_finalize": (C.c_int, [C.POINTER(BeamState), _P, _P, _I32, _I32, _P]),
     "odic_beam_finalize_best": (C.c_int, [C.POINTER(BeamState), _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "odic_beam_reset": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),

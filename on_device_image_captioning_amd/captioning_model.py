@@ -43,6 +43,7 @@ class CaptioningModel(nn.Module):
         self._sampling_calls = 0
         self._draw_log = None               # list → every sampled-beam-search draw is appended (tests)
         self._cand_log = None               # list → every deterministic search step's (cand_val, cand_idx) is appended (tests)
+        self.last_stochastic_beam = None    # after stochastic_beam_search: the samples' perturbed scores, kappa and log-probs
         self.last_required_satisfied = None  # after a beam_search with required_words: per image, does output 0 hold them all
 
     # ------------------------------------------------------------------ engine cache plumbing
@@ -568,13 +569,64 @@ class CaptioningModel(nn.Module):
                                          step=step, pick=pick)
         return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
+    def stochastic_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_samples=5, max_seq_len=20,
+                               seed=None, *, prefix=None, required_words=None, no_repeat_ngram_size=0, min_length=0,
+                               banned_words=None, temperature=1.0, top_k=0, top_p=1.0):
+        """Stochastic beam search (Kool, van Hoof & Welling, ICML 2019): `num_samples` captions per image
+        sampled from the model WITHOUT replacement — always distinct, the first an exact sample from the model, the set a
+        Plackett-Luce sample over whole captions.  Every step is the decoder, one launch that draws every row's words with
+        their Gumbel-perturbed scores (odic_logsoftmax_sample_scored) and one that keeps the rows with the largest
+        perturbed scores (odic_stochastic_beam_step).  Returns what beam_search(how_many_outputs=num_samples) returns;
+        output j is row j, in sampling order (descending perturbed score), and the log-probs are the model's own.
+        The search runs num_samples + 1 rows, so 1 <= num_samples <= 15.  It sets
+          self.last_stochastic_beam = {"gumbel": fp32 [B, num_samples], "kappa": fp32 [B], "sum_logprob": fp32 [B, num_samples]}
+        on the device: the samples' perturbed scores, the perturbed score of the extra row (-inf when the image had no
+        further caption to offer) and the samples' log-probs phi.  Given kappa, sample s was included with probability
+        1 − exp(−exp(phi_s − kappa)): what a without-replacement REINFORCE estimator weighs it by (not computed here).
+        `seed`: the Philox key of the noise; None draws one from torch's default generator (torch.manual_seed governs it),
+        and leaves `sampling_seed`'s call counter alone.
+        prefix, required_words, no_repeat_ngram_size, min_length, banned_words, temperature / top_k / top_p: accepted so
+        that a call that names them fails loudly — anything but their defaults raises ValueError: they change the
+        distribution that is sampled."""
+        n = _search.check_stochastic_beam(num_samples, prefix=prefix, required_words=required_words,
+                                          no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                          banned_words=banned_words, temperature=temperature, top_k=top_k, top_p=top_p)
+        R = n + 1
+        if R > self._vocab_size():
+            raise ValueError(f"{R} rows per image exceed the vocabulary ({self._vocab_size()} words)")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        mem = self.forward_enc(enc_input, enc_input_num_pads)
+        eng = self._captioner_engine()
+        B, S, _ = mem.shape
+        steps = max(1, max_seq_len - 1)
+        T = steps + 1
+        st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
+
+        def step(cons):
+            eng.stochastic_beam_step(st, eos_idx, seed)
+            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
+                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone(), st.cand_pert.cpu().clone()))
+
+        def pick(order, score):                                   # the rows are in sampling order already
+            return torch.arange(n)[None, :].expand(B, n)
+
+        res_tok, lp = _search.run_search(eng, st, eos_idx, steps, n, step=step, pick=pick,
+                                         arm=lambda: ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb))
+        g = st.gscore.view(B, R)
+        self.last_stochastic_beam = {"gumbel": g[:, :n].clone(), "kappa": g[:, n].clone(),
+                                     "sum_logprob": st.cumul.view(B, R)[:, :n].clone()}
+        return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, num_candidates, source="sampling", sos_idx, eos_idx,
                           max_seq_len=20, corpus=None, metric="cider", **search_args):
         """One caption per image by consensus: draw `num_candidates` candidates, score each against the
         others under CIDEr-D on the device (reward.consensus_rerank) and return the one that agrees most with the rest.
         source='sampling': get_batch_multiple_sampled_prediction(num_outputs=num_candidates, **search_args) — temperature,
         top_k, top_p; source='diverse': diverse_beam_search(num_groups=num_candidates, **search_args) — group_size (default
-        1), diversity_penalty and the search controls.  `corpus`: a reward.CiderCorpus whose IDF table weighs the n-grams
+        1), diversity_penalty and the search controls; source='stochastic_beam': stochastic_beam_search(num_samples=
+        num_candidates, **search_args) — `seed`; the candidates are distinct, so no pair is scored twice.  `corpus`: a reward.CiderCorpus whose IDF table weighs the n-grams
         (default: every n-gram counts 1).  `metric`: 'cider', or 'bleu4' / 'rouge_l' for the pairwise sentence BLEU-4 or
         ROUGE-L F as the utility (§4.20; no corpus with them).  → (captions: one token list per image, scores fp64 [B]: its
         mean utility against the other candidates).  `self.last_consensus` keeps (candidates, best_index [B], scores [B, N])."""
@@ -588,8 +640,11 @@ class CaptioningModel(nn.Module):
             search_args.setdefault("group_size", 1)
             cands, _ = self.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx, eos_idx, num_groups=num_candidates,
                                                 max_seq_len=max_seq_len, **search_args)
+        elif source == "stochastic_beam":
+            cands, _ = self.stochastic_beam_search(enc_x, enc_x_num_pads, sos_idx, eos_idx, num_samples=num_candidates,
+                                                   max_seq_len=max_seq_len, **search_args)
         else:
-            raise ValueError("source must be 'sampling' or 'diverse'")
+            raise ValueError("source must be 'sampling', 'diverse' or 'stochastic_beam'")
         index, scores = _reward.consensus_rerank(cands, corpus=corpus, eos_idx=eos_idx, metric=metric)
         self.last_consensus = (cands, index, scores)
         best = index.tolist()
@@ -645,6 +700,9 @@ class Captioner:
 
     def diverse_beam_search(self, *a, **k):
         return self.model.diverse_beam_search(*a, **k)
+
+    def stochastic_beam_search(self, *a, **k):
+        return self.model.stochastic_beam_search(*a, **k)
 
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, metric="cider", **k):
         """CaptioningModel.consensus_caption with this object's `beam_search_args` (sos_idx, eos_idx, beam_max_seq_len)

@@ -46,11 +46,12 @@ template <int KM> struct DrawList {
 };
 
 // The k draws of row x (V words, log-sum-exp lse) from the threads' lists: round r takes the block's best head, thread 0
-// stores its word and the word's log-probability x[v] - lse, not its perturbed score.
+// stores its word and the word's log-probability x[v] - lse; its perturbed score (x[v] + noise) - lse goes to top_pert
+// where the caller wants it (nullptr: not stored) — stochastic beam search ranks whole captions by it.
 template <int KM>
 __device__ __forceinline__ void block_draw_rounds(DrawList<KM>& l, const float* __restrict__ x, int V, int k, float lse,
                                                   float* __restrict__ top_val, int* __restrict__ top_idx,
-                                                  ArgmaxSlots<16>& win) {
+                                                  float* __restrict__ top_pert, ArgmaxSlots<16>& win) {
   const int tid = threadIdx.x;
   for (int r = 0; r < k; ++r) {
     float best = l.v[0]; int besti = l.i[0];
@@ -65,12 +66,12 @@ __device__ __forceinline__ void block_draw_rounds(DrawList<KM>& l, const float* 
         for (int i = tid; i < V; i += 1024)
           if (i > pi && !(x[i] > -INFINITY)) { fi = i; break; }
         block_argmax<16>(fv, fi, win, rr + 1);            // equal values: the lowest index wins
-        if (tid == 0) { top_val[rr] = -INFINITY; top_idx[rr] = fi; }
+        if (tid == 0) { top_val[rr] = -INFINITY; top_idx[rr] = fi; if (top_pert) top_pert[rr] = -INFINITY; }
         pi = fi;
       }
       break;
     }
-    if (tid == 0) { top_val[r] = x[besti] - lse; top_idx[r] = besti; }
+    if (tid == 0) { top_val[r] = x[besti] - lse; top_idx[r] = besti; if (top_pert) top_pert[r] = best - lse; }
     if (l.i[0] == besti) l.pop();
   }
 }

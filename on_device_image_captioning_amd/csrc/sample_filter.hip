@@ -210,7 +210,7 @@ __global__ __launch_bounds__(NTH) void sample_filter_kernel(const float* __restr
       }
     }
   }
-  block_draw_rounds<KM>(l, x, V, k, lse, top_val + (long)n * k, top_idx + (long)n * k, win);
+  block_draw_rounds<KM>(l, x, V, k, lse, top_val + (long)n * k, top_idx + (long)n * k, nullptr, win);
 }
 
 template <int KM>

@@ -315,6 +315,8 @@ class DecodeState:
         self.cand_val, self.cand_idx = f(N, beams), i32(N, beams)
         self.logits = f(N, g.vocab_size)
         self.logp = None            # [N, V] log-probs, allocated by the first constrained step (odic_topk_rows_constrained)
+        self.cand_pert = None       # [N, beams] perturbed scores of the candidates, and
+        self.gscore = None          # [N] of the rows: allocated by the first stochastic beam step
         self.banned = None          # int32 word ids of the constraints built for this state (kept alive here)
         self.beam_state = _hip.BeamState(*(t.data_ptr() for t in (
             self.tokens, self.logprobs, self.anc, self.cumul, self.n_elem, self.has_eos, self.row_valid,
@@ -613,6 +615,22 @@ class CaptionerEngine:
         self._candidates(st, constraints, want_logp=True)
         ops.require_beam_step(st.cand_val, st.cand_idx, st.logp, required, st.beam_state, st.n_img, bank_beams, st.T,
                               eos_idx, emb=st.emb)
+
+    def stochastic_beam_step(self, st: DecodeState, eos_idx: int, seed: int) -> None:
+        """One full step of stochastic beam search, the sibling of beam_step with the same two launches
+        behind the decoder: st.beams draws without replacement per row WITH their perturbed scores
+        (odic_logsoftmax_sample_scored, noise keyed by `seed`, the row, the word and *st.pos) into st.cand_val / cand_idx /
+        cand_pert, then odic_stochastic_beam_step, which keeps the st.beams best perturbed continuations of every image and
+        carries their scores in st.gscore.  The state must have been armed like beam_step's."""
+        if st.cand_pert is None:
+            st.cand_pert = torch.empty(st.N, st.beams, dtype=torch.float32, device=self.device)
+            st.gscore = torch.empty(st.N, dtype=torch.float32, device=self.device)
+        V = self.g.vocab_size
+        self.step_logits(st, embed=False)
+        ops.logsoftmax_sample_scored(st.logits, V, None, 0, st.cand_val, st.cand_idx, st.cand_pert, st.N, V, st.beams, seed,
+                                     st.pos)
+        ops.stochastic_beam_step(st.cand_val, st.cand_idx, st.cand_pert, st.gscore, st.beam_state, st.n_img, st.beams,
+                                 st.T, eos_idx, emb=st.emb)
 
     # ------------------------------------------------------------------------------------------
     # a search that starts behind a given prefix (DESIGN.md §4.15)

@@ -736,6 +736,17 @@ def logsoftmax_sample(logits, ldl, logp_out, ldp, top_val, top_idx, N, V, k, see
                    "odic_logsoftmax_sample")
 
 
+def logsoftmax_sample_scored(logits, ldl, logp_out, ldp, top_val, top_idx, top_pert, N, V, k, seed: int, pos=None) -> None:
+    """logsoftmax_sample that also writes the perturbed scores of its draws, top_pert fp32 [N, k] = log-prob + Gumbel noise
+    (odic_logsoftmax_sample_scored): what stochastic_beam_step ranks captions by.  Words and log-probs are those of
+    logsoftmax_sample for the same seed and *pos, bit for bit."""
+    _need_cuda(logits, logp_out, top_val, top_idx, top_pert, pos)
+    with _timed("logsoftmax_topk", 14.0 * N * V, N * V * 4.0 * (2 if logp_out is not None else 1) + N * k * 12.0):
+        _hip.check(_hip.load().odic_logsoftmax_sample_scored(_p(logits), ldl, _p(logp_out), ldp, _p(top_val), _p(top_idx),
+                                                             _p(top_pert), N, V, k, seed & 0xFFFFFFFFFFFFFFFF, _p(pos),
+                                                             _stream()), "odic_logsoftmax_sample_scored")
+
+
 def sample_filter(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> "_hip.SampleFilter":
     """odic_sample_filter of the three controls; 1/temperature is formed in double and rounded once to fp32."""
     return _hip.SampleFilter(1.0 / float(temperature), int(top_k), float(top_p))
@@ -946,6 +957,19 @@ def require_beam_step(cand_val, cand_idx, logp, required, state: "_hip.BeamState
         _hip.check(_hip.load().odic_require_beam_step(_p(cand_val), _p(cand_idx), beams, _p(logp), ldl, _p(required) if C_ else None, C_, C.byref(state), _emb_ref(emb),
                                                       n_img, bank_beams, T, eos_idx, V, _stream()),
                    "odic_require_beam_step")
+
+
+def stochastic_beam_step(cand_val, cand_idx, cand_pert, gscore, state: "_hip.BeamState", n_img, beams, T, eos_idx,
+                         emb=None) -> None:
+    """The step of stochastic beam search (odic_stochastic_beam_step; Kool et al. 2019): the `beams` rows of an image
+    become its `beams` continuations with the largest perturbed scores — captions sampled without replacement.  cand_*
+    are [n_img·beams, beams] as logsoftmax_sample_scored writes them with k = beams; gscore fp32 [n_img·beams] carries the
+    rows' perturbed scores from step to step (read from *pos = 1 on, written at every step)."""
+    _need_cuda(cand_val, cand_idx, cand_pert, gscore)
+    with _timed("beam_step", 0.0, n_img * beams * (beams * 12.0 + 8.0) + _beam_bytes(n_img, beams, T, emb)):
+        _hip.check(_hip.load().odic_stochastic_beam_step(_p(cand_val), _p(cand_idx), _p(cand_pert), _p(gscore),
+                                                         C.byref(state), _emb_ref(emb), n_img, beams, T, eos_idx,
+                                                         _stream()), "odic_stochastic_beam_step")
 
 
 def beam_finalize(state: "_hip.BeamState", order, score, n_img, beams) -> None:

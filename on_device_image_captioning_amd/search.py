@@ -2,8 +2,8 @@
 CaptionPipeline: argument rules, mode dispatch, the members of an ensemble on one beam state, and
 run_search — arm, constraints, the step loop with its look at the device's `done` flag, ranking, row pick, read-out — which
 every search method calls with its own way to arm, its step and its rows.  Plain functions over a DecodeState (engine.py);
-the device side of a step is ops.beam_step / ops.group_beam_step / ops.require_beam_step, three rules on one extraction
-(wave_extract_best, csrc/decoder_ops.hip).
+the device side of a step is ops.beam_step / ops.group_beam_step / ops.require_beam_step / ops.stochastic_beam_step, four
+rules on one extraction (wave_extract_best, csrc/beam_step.h).
 """
 from __future__ import annotations
 
@@ -195,6 +195,35 @@ def refuse_required_words(required, where: str) -> None:
         raise ValueError(f"required_words is not supported {where}: use beam_search on one model, without a prefix")
 
 
+MAX_STOCHASTIC_SAMPLES = 15     # stochastic_beam_search runs num_samples + 1 rows per image, 16 at most
+
+
+def check_stochastic_beam(num_samples, *, prefix=None, required_words=None, no_repeat_ngram_size=0, min_length=0,
+                          banned_words=None, temperature=1.0, top_k=0, top_p=1.0) -> int:
+    """The rules of stochastic_beam_search → num_samples as an int.  Everything that would change the
+    distribution the captions are sampled from is refused, in the wording of refuse_required_words: the samples, their
+    perturbed scores and the inclusion probabilities derived from them are those of the model itself."""
+    where = "in stochastic_beam_search"
+    if isinstance(num_samples, bool) or int(num_samples) != num_samples or not 1 <= int(num_samples) <= MAX_STOCHASTIC_SAMPLES:
+        raise ValueError(f"num_samples must be an integer in [1, {MAX_STOCHASTIC_SAMPLES}] (the search runs num_samples + 1 "
+                         f"rows per image, 16 at most), not {num_samples!r}")
+    refuse_required_words(required_words, where)
+    tail = "it samples captions from the model's own distribution"
+    if isinstance(prefix, torch.Tensor):
+        prefix = prefix.tolist()
+    if prefix is not None and any(len(p) if isinstance(p, (list, tuple, torch.Tensor)) else 1 for p in prefix):
+        raise ValueError(f"prefix is not supported {where}: {tail}")
+    if int(no_repeat_ngram_size) != 0:
+        raise ValueError(f"no_repeat_ngram_size is not supported {where}: {tail}")
+    if int(min_length) != 0:
+        raise ValueError(f"min_length is not supported {where}: {tail}")
+    if banned_words is not None and len(list(banned_words)):
+        raise ValueError(f"banned_words is not supported {where}: {tail}")
+    if float(temperature) != 1.0 or top_k != 0 or float(top_p) != 1.0:
+        raise ValueError(f"temperature / top_k / top_p are not supported {where}: {tail}")
+    return int(num_samples)
+
+
 def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, how_many_outputs: int):
     """The rows a required-words search returns.  order: odic_beam_finalize's [B, R] (host integers), cumul [B, R] (host
     floats), required: check_required_words' lists.  Output j of an image is the j-th live row (cumul > -inf) of its
@@ -217,7 +246,7 @@ def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, h
 
 
 def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
-    """mode='beam_search' | 'sampling' | 'diverse_beam_search' with the keys of `args` (a forward(**kwargs) or
+    """mode='beam_search' | 'sampling' | 'diverse_beam_search' | 'stochastic_beam_search' with the keys of `args` (a forward(**kwargs) or
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
     sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
     pre = {k: args[k] for k in ("prefix", "required_words") if k in args}       # (absent = the default, as the constraints)
@@ -247,6 +276,11 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
                                          diversity_penalty=args.get("diversity_penalty", 0.5),
                                          how_many_outputs=args.get("how_many_outputs", None),
                                          max_seq_len=args.get("beam_max_seq_len", 20), **pre, **cons)
+    if mode == "stochastic_beam_search":
+        return model.stochastic_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
+                                            num_samples=args.get("num_samples", 5),
+                                            max_seq_len=args.get("beam_max_seq_len", 20), seed=args.get("seed", None),
+                                            **pre, **cons, **flt)
     raise ValueError(f"unknown mode {mode!r}")
 
 

@@ -16,8 +16,10 @@ it with diverse:GxK' at the same number of rows per image.
 sample:K[:topk:topp:temp] is the step of beam_search(sample_or_max='sample') with K beams: the decoder, the k draws per row
 and the beam bookkeeping.  sample:K draws with odic_logsoftmax_sample; with the three controls given, e.g.
 sample:3:20:0.9:0.8, with odic_logsoftmax_sample_filtered: the difference of the two is the cost of the filter per step.
+sbeam:K is the step of stochastic_beam_search(num_samples=K): K + 1 rows per image, the decoder, the scored
+draws (odic_logsoftmax_sample_scored) and odic_stochastic_beam_step.  Compare it with beam:K+1, the same rows per image.
 A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix, rbeam
-before odic_require_beam_step) is reported as absent.
+before odic_require_beam_step, sbeam before odic_stochastic_beam_step) is reported as absent.
 """
 import argparse
 import os
@@ -87,6 +89,12 @@ def main():
             R = kb << C
             req = torch.arange(300, 300 + C, device=dev).repeat(a.images, 1)
             one = lambda st: eng.require_beam_step(st, bench.EOS, req, kb)         # noqa: E731
+        elif kind == "sbeam":
+            if not hasattr(eng, "stochastic_beam_step"):
+                print(f"{form}: not in this build")
+                continue
+            R = int(shape) + 1
+            one = lambda st: eng.stochastic_beam_step(st, bench.EOS, 7)            # noqa: E731
         elif kind == "diverse":
             G, kg = (int(v) for v in shape.split("x"))
             if not hasattr(eng, "group_beam_step"):
