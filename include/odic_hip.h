@@ -782,6 +782,50 @@ typedef struct odic_search_constraints {
 int odic_topk_rows_constrained(const float* logp, int64_t ldl, const odic_search_constraints* c,
                                float* top_val, int32_t* top_idx, int32_t N, int32_t V, int32_t k, void* stream);
 
+/* The candidates of a CONTRASTIVE search step (the emitter–suppressor beam search of Vedantam et al., "Context-aware
+ * captions from context-agnostic supervision", CVPR 2017, with the plausibility cut of contrastive decoding, Li et al.
+ * 2022): a word is ranked by its log-prob under the target image minus a weighted log-prob under up to
+ * seven distractor images, among the words the target itself finds plausible.  An addition to ABI 26.  One block per row. */
+typedef struct odic_contrast_args {
+  float   weight;     /* w >= 0, finite: how strongly the suppressor counts (Vedantam's 1 − λ); 0 = off */
+  float   log_alpha;  /* <= 0 or -inf: a word is plausible iff x_t[v] − max(x_t) >= log_alpha (one fp32 subtract); -inf = off */
+  float   floor;      /* finite, <= 0: the suppressor log-prob is clamped from below to this */
+  int32_t min_keep;   /* >= k: the cut never leaves fewer than this many candidates */
+} odic_contrast_args;
+/*   logits: a HOST array of M = 1 + D (<= 8) device pointers to fp32 [N, V] rows of one pitch ldl, [0] the target's;
+ *   count int32 [N] on the device: row n uses distractors 1 .. c, c = count[n] clamped to [0, D] (NULL only with M == 1).
+ *   For row n:
+ *   1. Log-probs lp_t, lp_1 .. lp_c as odic_logsoftmax_topk forms them, x − (max + log Σ exp(x − max)), in its summation
+ *      order, with its bound.
+ *   2. Suppressor: c == 1: s[v] = lp_1[v] exactly.  c > 1: s[v] = (m + logf(Σ_d expf(lp_d[v] − m))) − logf(c), m = max_d
+ *      lp_d[v], the sum in ascending d: the log of the mean probability, formed in the log domain, so it does not
+ *      underflow where odic_ensemble_logprobs does.  s'[v] = max(s[v], floor); a word every active distractor masks
+ *      (-inf) has s' = floor.
+ *   3. Score: out[v] = lp_t[v] − w·s'[v], a rounded product and a rounded difference (no FMA).  With c == 0 or w == 0,
+ *      out[v] = lp_t[v] and no distractor row is read.  A word the target masks has out = -inf.  Scores may be POSITIVE.
+ *   4. Plausibility: the words are ranked by x_t (larger first, ties to the lower index, -0 = +0); m = the number of
+ *      plausible words; the admissible words are the first max(m, min_keep) in that order (the rule by which
+ *      odic_logsoftmax_sample_filtered never leaves fewer candidates than are drawn); every other word has out = -inf.
+ *      kept[n] = m (kept may be NULL).  log_alpha == -inf: every word is admissible, m = V.
+ *   5. top_val / top_idx [N, k], compact: the k best out values, ties to the lower index; -inf entries come last by
+ *      ascending index (odic_topk_rows' short-row rule).  top_val[n][r] is out[top_idx[n][r]] bit for bit.  score_out
+ *      fp32 [N, V] (lds), when given, takes the whole row: what odic_topk_rows_constrained re-selects from.
+ *   6. Off: with w == 0 or count[n] == 0, and log_alpha == -inf, top_val, top_idx and score_out are bit for bit
+ *      odic_logsoftmax_topk's top_val, top_idx and logp_out.  (A row with w == 0 or count[n] == 0 is ranked by x_t under
+ *      any log_alpha, as that kernel ranks: where two different logits round to one log-prob, the larger logit comes
+ *      first, not the lower index.)
+ *   ODIC_EINVAL / ODIC_ENULL before any launch, nothing written: M outside [1, 8]; k outside [1, 16], k > V, V > 262144,
+ *     N < 1; ldl < V, or lds < V with score_out given; min_keep < k or > V; weight negative or not finite; log_alpha > 0 or
+ *     NaN; floor not finite or > 0; logits, one of its M pointers, a, top_val or top_idx NULL; count NULL with M > 1.
+ *   All stores stay inside top_val, top_idx, kept and columns [0, V) of score_out; logits columns [V, ldl) and the
+ *   distractor rows beyond count[n] are never read (tests/test_contrast_rows_gpu.py runs every operand in a guarded
+ *   buffer, the unused distractor rows filled with NaN).  A target row, or an active distractor row, without a finite
+ *   logit or with a NaN is outside the contract.  Rows above 10240 words recompute a word's score in every one of the k
+ *   selection rounds: exact, slower. */
+int odic_contrast_topk(const float* const* logits, int32_t M, int64_t ldl, const int32_t* count,
+                       const odic_contrast_args* a, float* score_out, int64_t lds, float* top_val, int32_t* top_idx,
+                       int32_t* kept /* [N] or NULL */, int32_t N, int32_t V, int32_t k, void* stream);
+
 /* Beam bookkeeping of one search step on device (captioning_model.py:172-223; the call with
  * *pos == 0 is the seeding of :126-140).  All arrays are device resident.
  *   cand_val/cand_idx [n_img*beams, beams]: per-sequence top-k log-probs / words

@@ -60,6 +60,11 @@ class SampleFilter(C.Structure):
     _fields_ = [("inv_temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
 
 
+class ContrastArgs(C.Structure):
+    """odic_contrast_args: weight, plausibility cut, suppressor floor and minimum candidates (ops.contrast_args)."""
+    _fields_ = [("weight", C.c_float), ("log_alpha", C.c_float), ("floor", C.c_float), ("min_keep", C.c_int32)]
+
+
 class JpegBatch(C.Structure):
     """odic_jpeg_batch: one batched JPEG decode (headers from on_device_image_captioning_amd.jpeg.pack_headers)."""
     _fields_ = [("headers", C.c_void_p), ("data", C.c_void_p), ("out", C.c_void_p), ("status", C.c_void_p),
@@ -124,6 +129,8 @@ _SIGNATURES = {
     "odic_ensemble_logprobs": (C.c_int, [C.POINTER(C.c_void_p), _I32, _I64, _P, _I64, _I32, _I32, _P]),
     "odic_topk_rows": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _P]),
     "odic_topk_rows_constrained": (C.c_int, [_P, _I64, C.POINTER(SearchConstraints), _P, _P, _I32, _I32, _I32, _P]),
+    "odic_contrast_topk": (C.c_int, [C.POINTER(C.c_void_p), _I32, _I64, _P, C.POINTER(ContrastArgs), _P, _I64, _P, _P, _P, _I32,
+                                     _I32, _I32, _P]),
     "odic_beam_step": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),
     "odic_group_beam_step": (C.c_int, [_P, _P, _I32, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I32, _I64,
                                        _F, _P]),

@@ -619,6 +619,62 @@ class CaptioningModel(nn.Module):
                                      "sum_logprob": st.cumul.view(B, R)[:, :n].clone()}
         return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
 
+    def contrastive_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, distractors, beam_size=3,
+                                how_many_outputs=1, max_seq_len=20, *, contrast=0.5, plausibility=0.1,
+                                suppressor_floor=-20.0, no_repeat_ngram_size=0, min_length=0, banned_words=None,
+                                prefix=None, required_words=None, sample_or_max="max"):
+        """Distinctive captions: the emitter–suppressor beam search of Vedantam et al. (CVPR 2017) with
+        the plausibility cut of contrastive decoding (Li et al. 2022).  `distractors`: for every image a sequence of
+        0..7 distinct indices of OTHER images of this batch (ragged lists allowed), or 'others' for all of them
+        (B - 1 <= 7).  At every step a word of an image's beam is ranked by
+            log p(word | image) − contrast · max(log mean_d p(word | distractor d), suppressor_floor)
+        among the words whose probability under the image itself is at least `plausibility` times its best word's (0 = no
+        cut; never fewer than the words the step needs), so the caption says what tells the image apart from its
+        distractors without leaving what the model finds sayable.  The encoder and the K/V projection run once per
+        batch; a distractor is the same beam prefix decoded against another image's memory, so a step costs about
+        1 + D decoder passes, D the longest distractor list, and one launch for the scores (odic_contrast_topk).
+        An image without distractors, and every image at contrast = 0 with plausibility = 0, gets beam_search's captions.
+        Returns what beam_search returns; the per-word values are the CONTRASTIVE scores the search ranked by (they can
+        be positive), not log-probs: score_captions gives the model's own log-probs of the returned captions.
+        `no_repeat_ngram_size`, `min_length`, `banned_words`: as in beam_search.  prefix, required_words and
+        sample_or_max='sample' are accepted so that a call that names them fails loudly: ValueError."""
+        assert (how_many_outputs <= beam_size), "requested output per sequence must be lower than beam width"
+        B = enc_input.shape[0]
+        c = _search.check_contrast(distractors, B, contrast=contrast, plausibility=plausibility,
+                                   suppressor_floor=suppressor_floor, prefix=prefix, required_words=required_words,
+                                   sample_or_max=sample_or_max)
+        cons = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                            banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
+                                            max_seq_len=max_seq_len, rows_per_image=beam_size)
+        if beam_size > self._vocab_size():
+            raise ValueError(f"{beam_size} beams per image exceed the vocabulary ({self._vocab_size()} words)")
+        mem = self.forward_enc(enc_input, enc_input_num_pads)
+        eng = self._captioner_engine()
+        dv = eng.device
+        S = mem.shape[1]
+        k, D = int(beam_size), c["D"]
+        steps = max(1, max_seq_len - 1)
+        T = steps + 1
+        kv, enc_len = eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads)
+        states = [eng.new_state(B, k, T, kv, enc_len)]
+        for d in range(D):           # distractor d of every image: its memory rows (an unused slot: the image's own; count masks it)
+            idx = torch.tensor([r[d] if d < len(r) else i for i, r in enumerate(c["lists"])], dtype=torch.int64, device=dv)
+            states.append(eng.new_state(B, k, T, kv.index_select(0, idx).contiguous(), enc_len.index_select(0, idx)))
+        st = _search.share_beam_state(states)
+        count = torch.tensor([len(r) for r in c["lists"]], dtype=torch.int32, device=dv).repeat_interleave(k).contiguous()
+        # under constraints a row can lose n_banned + T words (odic_topk_rows_constrained): beam_size finite ones remain
+        min_keep = k + (len(cons["banned"]) + T if cons else 0)
+        args = ops.contrast_args(c["contrast"], c["plausibility"], c["suppressor_floor"], min_keep)
+
+        def step(dev_cons):
+            eng.contrast_beam_step(states, count, args, eos_idx, constraints=dev_cons)
+            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
+                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
+
+        res_tok, lp = _search.run_search(eng, st, eos_idx, steps, how_many_outputs, constraints=cons, step=step,
+                                         arm=lambda: ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None))
+        return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, num_candidates, source="sampling", sos_idx, eos_idx,
                           max_seq_len=20, corpus=None, metric="cider", **search_args):
         """One caption per image by consensus: draw `num_candidates` candidates, score each against the
@@ -704,6 +760,9 @@ class Captioner:
     def stochastic_beam_search(self, *a, **k):
         return self.model.stochastic_beam_search(*a, **k)
 
+    def contrastive_beam_search(self, *a, **k):
+        return self.model.contrastive_beam_search(*a, **k)
+
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, metric="cider", **k):
         """CaptioningModel.consensus_caption with this object's `beam_search_args` (sos_idx, eos_idx, beam_max_seq_len)
         unless the call names its own."""
@@ -730,19 +789,37 @@ class Captioner:
                 k.setdefault(arg, b[key])
         return self.model.word_attention(enc_x, captions, *a, **k)
 
-    def caption_regions(self, preprocessor, images, regions):
+    def caption_regions(self, preprocessor, images, regions, distinctive=False, **contrast_args):
         """Captions of parts of pictures that live on the device: `preprocessor.resize_regions(images, regions)` (a
         DevicePreprocessor of the model's input size; images: uint8 (H,W,3) device tensors as its `decode_jpeg` returns
         them; regions: sequence of (image index, (l, t, r, b)), the box as PIL's `resize(..., box=)` takes it), then
         this object's encode and search on that batch (`__call__`).  Returns one list per input image,
         holding a grounding.RegionCaption for each of its regions in the order they were given; an image without a
-        region gets an empty list."""
+        region gets an empty list.
+        `distinctive=True`: the search is contrastive_beam_search with, for every region, the OTHER
+        regions of the same source image as its distractors, so sibling crops stop sharing one caption; `contrast_args`
+        (contrast, plausibility, suppressor_floor) go to it, the rest comes from `beam_search_args` as in `__call__`
+        with mode='contrastive_beam_search'.  A region without siblings gets beam_search's caption; more than 7 siblings is
+        a ValueError.  The RegionCaption's `logprobs` are then the contrastive scores."""
         regions = [(int(i), tuple(float(v) for v in box)) for i, box in regions]
         per_image = [[] for _ in images]
         if not regions:
             return per_image
+        if not distinctive and contrast_args:
+            raise ValueError(f"{sorted(contrast_args)} apply to distinctive=True only")
+        if distinctive:
+            siblings = [[m for m, (j, _) in enumerate(regions) if j == i and m != n] for n, (i, _) in enumerate(regions)]
+            most = max(len(r) for r in siblings)
+            if most > _search.MAX_DISTRACTORS:
+                raise ValueError(f"a region with {most} sibling regions: distinctive captions take at most "
+                                 f"{_search.MAX_DISTRACTORS} distractors per region")
         batch = preprocessor.resize_regions(images, regions)
-        toks, lps = self(batch, enc_x_num_pads=[0] * len(regions))
+        if distinctive:
+            a = self.beam_search_args
+            args = dict(a, sos_idx=a["sos_idx"], eos_idx=a["eos_idx"], distractors=siblings, **contrast_args)
+            toks, lps = _search.dispatch(self.model, "contrastive_beam_search", args, batch, [0] * len(regions))
+        else:
+            toks, lps = self(batch, enc_x_num_pads=[0] * len(regions))
         for n, (i, box) in enumerate(regions):
             per_image[i].append(_grounding.RegionCaption(region=n, box=box, tokens=toks[n], logprobs=lps[n]))
         return per_image

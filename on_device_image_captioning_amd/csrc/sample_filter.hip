@@ -2,55 +2,16 @@
 // scaled top-k / nucleus set, one block of 1024 threads per row (include/odic_hip.h has the contract, DESIGN.md §4.17 the
 // reasoning).  No sort: the set is the rank-prefix up to one threshold word (value, index), found by bisection on the
 // order-preserving integer key of z = x·inv_temperature — 32 rounds of a block-wide count (top-k) or mass sum (nucleus) —
-// and, where the threshold value is shared by several words, a bisection on the index among them.  The model's own
-// log-sum-exp, the noise and the draw rounds are odic_logsoftmax_sample's (row_sample.h), in its order of operations.
+// and, where the threshold value is shared by several words, a bisection on the index among them (the key, the block
+// count and the bisection: row_bisect.h).  The model's own log-sum-exp, the noise and the draw rounds are
+// odic_logsoftmax_sample's (row_sample.h), in its order of operations.
 #include "row_sample.h"
+#include "row_bisect.h"
 
 namespace {
 
 constexpr int NTH = 1024, NWV = NTH / 64;
 constexpr int NPT = 16;                        // words a thread holds in registers: rows up to NPT·NTH = 16384 words
-
-// float → unsigned, order-preserving (a < b ⇔ key(a) < key(b), -0 = +0); every non-NaN float has a key > 0
-__device__ __forceinline__ unsigned rank_key(float z) {
-  unsigned b = __float_as_uint(z);
-  if ((b << 1) == 0) b = 0;
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned key) {
-  return __uint_as_float(key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-// Block sums of a count and (MASS) a mass, every thread ends with both.  One barrier per call: call number rd writes
-// slot set rd & 1 (block_argmax's scheme, row_select.h); the waves are combined in ascending order.
-struct CountMassSlots { double m[2][NWV]; int c[2][NWV]; };
-
-template <bool MASS>
-__device__ __forceinline__ void block_count_mass(int& c, double& m, CountMassSlots& s, int& rd) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if constexpr (MASS) m = wave_sum(m);
-  const int p = rd++ & 1;
-  if ((threadIdx.x & 63) == 0) {
-    s.c[p][threadIdx.x >> 6] = c;
-    if constexpr (MASS) s.m[p][threadIdx.x >> 6] = m;
-  }
-  __syncthreads();
-  int tc = 0; double tm = 0.0;
-#pragma unroll
-  for (int w = 0; w < NWV; ++w) { tc += s.c[p][w]; if constexpr (MASS) tm += s.m[p][w]; }
-  c = tc; m = tm;
-}
-
-// the largest t of `bits` bits with pred(t), for a block-uniform pred that holds at 0 and, once false, stays false
-template <typename Pred> __device__ __forceinline__ unsigned bisect_max(int bits, Pred pred) {
-  unsigned t = 0;
-  for (int b = bits - 1; b >= 0; --b) {
-    const unsigned c = t | (1u << b);
-    if (pred(c)) t = c;
-  }
-  return t;
-}
 
 // #{ j in [0, cap) : before + j·w < P }: how many of `cap` equal words, each of mass w, start below P
 __device__ __forceinline__ int ties_below(double before, double w, double P, int cap) {
@@ -71,7 +32,7 @@ __global__ __launch_bounds__(NTH) void sample_filter_kernel(const float* __restr
                                                             const int* __restrict__ pos) {
   __shared__ float red[NWV];
   __shared__ ArgmaxSlots<NWV> win;
-  __shared__ CountMassSlots cms;
+  __shared__ CountMassSlots<NWV> cms;
   const int n = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (long)n * ldl;
   const unsigned step = pos ? (unsigned)*pos : 0u;

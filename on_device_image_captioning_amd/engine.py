@@ -632,6 +632,29 @@ class CaptionerEngine:
         ops.stochastic_beam_step(st.cand_val, st.cand_idx, st.cand_pert, st.gscore, st.beam_state, st.n_img, st.beams,
                                  st.T, eos_idx, emb=st.emb)
 
+    def contrast_beam_step(self, states, count: torch.Tensor, args: "_hip.ContrastArgs", eos_idx: int,
+                           constraints=None) -> None:
+        """One full step of contrastive beam search, the sibling of beam_step: states[0] decodes the
+        target images, the others the distractor images (the same rows against other encoder memories), all on
+        search.share_beam_state(states) and embedding for themselves like the members of an ensemble.  A decoder pass per
+        state, then ONE launch that turns the 1 + D logits rows of every beam into contrastive scores and their st.beams
+        best (odic_contrast_topk; count int32 [N]: the distractors row n uses), then the unchanged odic_beam_step.
+        `constraints`: the launch also writes the score rows (lead.logp) and odic_topk_rows_constrained re-selects the
+        candidates from them; args.min_keep then covers what a row can lose."""
+        lead = states[0]
+        for st in states:
+            self.step_logits(st)                                     # private caches, shared next_tok / pos / ancestors
+        score = None
+        if constraints is not None:
+            if lead.logp is None:
+                lead.logp = torch.empty(lead.N, self.g.vocab_size, dtype=torch.float32, device=self.device)
+            score = lead.logp
+        ops.contrast_topk([st.logits for st in states], count, args, lead.cand_val, lead.cand_idx, lead.beams,
+                          score_out=score)
+        if constraints is not None:
+            ops.topk_rows_constrained(score, constraints, lead.cand_val, lead.cand_idx, lead.beams)
+        ops.beam_step(lead.cand_val, lead.cand_idx, lead.beam_state, lead.n_img, lead.beams, lead.T, eos_idx)
+
     # ------------------------------------------------------------------------------------------
     # a search that starts behind a given prefix (DESIGN.md §4.15)
     def prefill(self, st: DecodeState, prefix: torch.Tensor, sos_idx: int, want_logits: bool = False):

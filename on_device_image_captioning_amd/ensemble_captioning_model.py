@@ -94,6 +94,10 @@ class EsembleCaptioningModel(CaptioningModel):
         raise NotImplementedError("stochastic beam search runs on a single model: call it on one of the ensemble's member "
                                   "models (models_list[i])")
 
+    def contrastive_beam_search(self, *a, **k):
+        raise NotImplementedError("contrastive beam search runs on a single model: call it on one of the ensemble's member "
+                                  "models (models_list[i])")
+
     def ensemble_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
                              max_seq_len=20, sample_or_max="max", *, no_repeat_ngram_size=0, min_length=0,
                              banned_words=None, prefix=None, required_words=None, temperature=1.0, top_k=0, top_p=1.0

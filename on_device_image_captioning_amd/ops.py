@@ -7,6 +7,7 @@ falls back — a non-CUDA tensor or a missing library raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -902,6 +903,35 @@ def topk_rows_constrained(logp: torch.Tensor, constraints: "_hip.SearchConstrain
         _hip.check(_hip.load().odic_topk_rows_constrained(_p(logp), logp.stride(0), C.byref(constraints), _p(top_val),
                                                           _p(top_idx), N, V, k, _stream()),
                    "odic_topk_rows_constrained")
+
+
+def contrast_args(weight: float, plausibility: float, floor: float, min_keep: int) -> "_hip.ContrastArgs":
+    """odic_contrast_args: the suppressor's weight, log(plausibility) rounded once to fp32 (-inf for 0 = no cut), the
+    suppressor floor and the least number of candidates the cut leaves."""
+    log_alpha = math.log(plausibility) if plausibility > 0.0 else float("-inf")
+    return _hip.ContrastArgs(float(weight), log_alpha, float(floor), int(min_keep))
+
+
+def contrast_topk(logits_list, count: Optional[torch.Tensor], args: "_hip.ContrastArgs", top_val: torch.Tensor,
+                  top_idx: torch.Tensor, k: int, *, score_out: Optional[torch.Tensor] = None,
+                  kept: Optional[torch.Tensor] = None) -> None:
+    """The k best contrastive scores of every row (odic_contrast_topk): logits_list[0] the target's logits [N, V], the
+    others the distractors' (one row pitch); count int32 [N]: how many of them row n uses (None with the target alone).
+    score_out [N, V]: the whole score row, for topk_rows_constrained; kept int32 [N]: the plausible words per row."""
+    _need_cuda(count, top_val, top_idx, score_out, kept, *logits_list)
+    M = len(logits_list)
+    N, V = logits_list[0].shape
+    ldl = logits_list[0].stride(0)
+    if any(t.shape != (N, V) or t.stride(0) != ldl or t.stride(1) != 1 or t.dtype != torch.float32 for t in logits_list):
+        raise ValueError("contrast_topk: the logits must be fp32 [N, V] tensors of one shape and row pitch")
+    if count is not None and (count.dtype != torch.int32 or count.numel() != N or not count.is_contiguous()):
+        raise ValueError("contrast_topk: count must be a contiguous int32 [N] tensor")
+    arr = (C.c_void_p * M)(*[t.data_ptr() for t in logits_list])
+    with _timed("contrast_topk", (4.0 + 6.0 * (M - 1)) * N * V,
+                4.0 * N * V * (M + (1 if score_out is not None else 0)) + N * k * 8.0):
+        _hip.check(_hip.load().odic_contrast_topk(arr, M, ldl, _p(count), C.byref(args), _p(score_out),
+                                                  score_out.stride(0) if score_out is not None else 0, _p(top_val),
+                                                  _p(top_idx), _p(kept), N, V, k, _stream()), "odic_contrast_topk")
 
 
 def embed_args(embed, pos_table, y, ldy, d, scale) -> "_hip.EmbedArgs":

@@ -3,7 +3,8 @@ CaptionPipeline: argument rules, mode dispatch, the me
 run_search — arm, constraints, the step loop with its look at the device's `done` flag, ranking, row pick, read-out — which
 every search method calls with its own way to arm, its step and its rows.  Plain functions over a DecodeState (engine.py);
 the device side of a step is ops.beam_step / ops.group_beam_step / ops.require_beam_step / ops.stochastic_beam_step, four
-rules on one extraction (wave_extract_best, csrc/beam_step.h).
+rules on one extraction (wave_extract_best, csrc/beam_step.h); contrastive_beam_search changes what
+ops.beam_step is fed, not the step (ops.contrast_topk).
 """
 from __future__ import annotations
 
@@ -224,6 +225,66 @@ def check_stochastic_beam(num_samples, *, prefix=None, required_words=None, no_r
     return int(num_samples)
 
 
+MAX_DISTRACTORS = 7             # odic_contrast_topk takes the target's row and seven more
+
+
+def check_contrast(distractors, n_img: int, *, contrast=0.5, plausibility=0.1, suppressor_floor=-20.0, prefix=None,
+                   required_words=None, sample_or_max="max") -> dict:
+    """The rules of contrastive_beam_search.  `distractors`: one sequence per image of 0..7 distinct
+    indices into the same batch, never the image itself (ragged lists allowed), or 'others' for every other image
+    (n_img - 1 <= 7), or None for none.  → dict(lists: n_img lists of ints, D: the longest list, contrast, plausibility,
+    suppressor_floor as floats); ValueError, before any device work, for what cannot work.  prefix, required_words and
+    sample_or_max='sample' are refused, in the wording of check_stochastic_beam."""
+    where = "in contrastive_beam_search"
+    refuse_required_words(required_words, where)
+    tail = "it ranks the words of one deterministic beam search by a contrast between images"
+    if isinstance(prefix, torch.Tensor):
+        prefix = prefix.tolist()
+    if prefix is not None and any(len(p) if isinstance(p, (list, tuple, torch.Tensor)) else 1 for p in prefix):
+        raise ValueError(f"prefix is not supported {where}: {tail}")
+    if sample_or_max != "max":
+        raise ValueError(f"sample_or_max={sample_or_max!r} is not supported {where}: {tail}")
+    w, a, fl = float(contrast), float(plausibility), float(suppressor_floor)
+    if not (0.0 <= w <= 3.0e38):
+        raise ValueError(f"contrast must be finite and >= 0 (0 = off), not {contrast!r}")
+    if not (0.0 <= a <= 1.0):
+        raise ValueError(f"plausibility must lie in [0, 1] (0 = off), not {plausibility!r}")
+    if not (-3.0e38 <= fl <= 0.0):
+        raise ValueError(f"suppressor_floor must be finite and <= 0, not {suppressor_floor!r}")
+    if distractors is None:
+        lists = [[] for _ in range(n_img)]
+    elif isinstance(distractors, str):
+        if distractors != "others":
+            raise ValueError(f"distractors must be 'others' or one sequence of image indices per image, not {distractors!r}")
+        if n_img - 1 > MAX_DISTRACTORS:
+            raise ValueError(f"distractors='others' with {n_img} images: an image takes at most {MAX_DISTRACTORS} distractors")
+        lists = [[j for j in range(n_img) if j != i] for i in range(n_img)]
+    else:
+        if isinstance(distractors, torch.Tensor):
+            distractors = distractors.tolist()
+        lists = []
+        for r in distractors:
+            r = r.tolist() if isinstance(r, torch.Tensor) else r
+            if not isinstance(r, (list, tuple)):
+                raise ValueError("distractors must hold one sequence of image indices per image")
+            if any(isinstance(j, bool) or int(j) != j for j in r):
+                raise ValueError(f"distractors {list(r)}: the indices must be integers")
+            lists.append([int(j) for j in r])
+        if len(lists) != n_img:
+            raise ValueError(f"{len(lists)} lists of distractors for {n_img} images: give one per image")
+    for i, r in enumerate(lists):
+        if len(r) > MAX_DISTRACTORS:
+            raise ValueError(f"{len(r)} distractors for image {i}: at most {MAX_DISTRACTORS}")
+        if len(set(r)) != len(r):
+            raise ValueError(f"distractors {r} of image {i}: an image's distractors must be distinct")
+        for j in r:
+            if not 0 <= j < n_img:
+                raise ValueError(f"distractor index {j} of image {i} lies outside the batch [0, {n_img})")
+            if j == i:
+                raise ValueError(f"image {i} cannot be its own distractor")
+    return dict(lists=lists, D=max((len(r) for r in lists), default=0), contrast=w, plausibility=a, suppressor_floor=fl)
+
+
 def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, how_many_outputs: int):
     """The rows a required-words search returns.  order: odic_beam_finalize's [B, R] (host integers), cumul [B, R] (host
     floats), required: check_required_words' lists.  Output j of an image is the j-th live row (cumul > -inf) of its
@@ -246,7 +307,7 @@ def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, h
 
 
 def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
-    """mode='beam_search' | 'sampling' | 'diverse_beam_search' | 'stochastic_beam_search' with the keys of `args` (a forward(**kwargs) or
+    """mode='beam_search' | 'sampling' | 'diverse_beam_search' | 'stochastic_beam_search' | 'contrastive_beam_search' with the keys of `args` (a forward(**kwargs) or
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
     sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
     pre = {k: args[k] for k in ("prefix", "required_words") if k in args}       # (absent = the default, as the constraints)
@@ -281,6 +342,15 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
                                             num_samples=args.get("num_samples", 5),
                                             max_seq_len=args.get("beam_max_seq_len", 20), seed=args.get("seed", None),
                                             **pre, **cons, **flt)
+    if mode == "contrastive_beam_search":
+        check_sampling_filter(**flt, sampling=False, where="contrastive_beam_search")
+        knobs = {k: args[k] for k in ("contrast", "plausibility", "suppressor_floor") if k in args}
+        return model.contrastive_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
+                                             distractors=args.get("distractors", "others"),
+                                             beam_size=args.get("beam_size", 5),
+                                             how_many_outputs=args.get("how_many_outputs", 1),
+                                             max_seq_len=args.get("beam_max_seq_len", 20),
+                                             sample_or_max=args.get("sample_or_max", "max"), **knobs, **pre, **cons)
     raise ValueError(f"unknown mode {mode!r}")
 
 

@@ -4,7 +4,7 @@ FULL geometry, features-only model, 16 images, fp32, HIP events around the step 
 poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
 it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
 
-    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 pbeam:3:6 rbeam:3:2 sample:3 sample:3:20:0.9:0.8
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 cbeam:3:1 pbeam:3:6 rbeam:3:2 sample:3 sample:3:20:0.9:0.8
 
 cbeam:K is beam:K under constraints: no_repeat_ngram_size=2, min_length=5 and 8 banned words; the step then
 holds one launch more (odic_topk_rows_constrained) and the top-k launch writes the log-prob rows.
@@ -18,10 +18,16 @@ and the beam bookkeeping.  sample:K draws with odic_logsoftmax_sample; with the 
 sample:3:20:0.9:0.8, with odic_logsoftmax_sample_filtered: the difference of the two is the cost of the filter per step.
 sbeam:K is the step of stochastic_beam_search(num_samples=K): K + 1 rows per image, the decoder, the scored
 draws (odic_logsoftmax_sample_scored) and odic_stochastic_beam_step.  Compare it with beam:K+1, the same rows per image.
+cbeam:K:D (two numbers) is the step of contrastive_beam_search with K beams and D distractor images per image
+(image i against images i+1 .. i+D of the batch): 1 + D decoder passes on one shared beam state, one odic_contrast_topk launch
+and odic_beam_step.  Compare it with beam:K.  A second line times the row launch alone against the composition the library
+could already form — 1 + D odic_logsoftmax_topk launches that write their log-prob rows, an elementwise combine (torch) and
+odic_topk_rows — on the same logits, alternating the two, HIP events around 200 launches each.
 A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix, rbeam
 before odic_require_beam_step, sbeam before odic_stochastic_beam_step) is reported as absent.
 """
 import argparse
+import math
 import os
 import statistics
 import sys
@@ -95,6 +101,13 @@ def main():
                 continue
             R = int(shape) + 1
             one = lambda st: eng.stochastic_beam_step(st, bench.EOS, 7)            # noqa: E731
+        elif kind == "cbeam" and ":" in shape:
+            shape, D = shape.split(":")
+            R, D = int(shape), int(D)
+            if not hasattr(eng, "contrast_beam_step") or not 0 <= D <= 7 or D >= a.images:
+                print(f"{form}: not in this build" if not hasattr(eng, "contrast_beam_step") else f"{form}: D must lie in [0, 7] and below --images")
+                continue
+            kind = "contrast"
         elif kind == "diverse":
             G, kg = (int(v) for v in shape.split("x"))
             if not hasattr(eng, "group_beam_step"):
@@ -113,13 +126,23 @@ def main():
             cons = eng.search_constraints(st, bench.EOS, no_repeat_ngram=2, min_words=5,
                                           banned=[w for w in range(100, 110) if w not in (bench.SOS, bench.EOS)][:8])
             one = lambda st: eng.beam_step(st, bench.EOS, constraints=cons)        # noqa: E731
+        if kind == "contrast":
+            from on_device_image_captioning_amd import search as _search
+            states = [st]
+            for d in range(D):
+                idx = (torch.arange(a.images, device=dev) + 1 + d) % a.images
+                states.append(eng.new_state(a.images, R, T, kv.index_select(0, idx).contiguous(), enc_len.index_select(0, idx)))
+            _search.share_beam_state(states)
+            count = torch.full((st.N,), D, dtype=torch.int32, device=dev)
+            cargs = ops.contrast_args(0.5, 0.1, -20.0, R)
+            one = lambda st: eng.contrast_beam_step(states, count, cargs, bench.EOS)   # noqa: E731
         prefix = torch.arange(200, 200 + P, device=dev).repeat(a.images, 1) if P else None
 
         def search():
             if P:
                 eng.seed_prefix(st, prefix, bench.SOS)
             else:
-                ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=None if kind == "sample" else st.emb)
+                ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=None if kind in ("sample", "contrast") else st.emb)
             for _ in range(steps - P):
                 one(st)
 
@@ -144,6 +167,54 @@ def main():
         print(f"{form} ({'eager' if a.eager else 'graph'}): rows/image {R}, {steps - P} steps, per step median {statistics.median(times):.1f} us, "
               f"min {min(times):.1f}, max {max(times):.1f} ({a.runs} runs); per search median "
               f"{statistics.median(times) * steps:.0f} us", flush=True)
+        if kind == "contrast":
+            rows_alone(ops, states, count, cargs, R, form)
+
+
+def rows_alone(ops, states, count, cargs, k, form, reps=200, rounds=5):
+    """The fused row launch against (1 + D) odic_logsoftmax_topk + combine + odic_topk_rows on the states' last logits."""
+    import torch
+    lg = [s.logits for s in states]
+    N, V = lg[0].shape
+    D = len(lg) - 1
+    tv, ti = states[0].cand_val, states[0].cand_idx
+    lp = [torch.empty_like(x) for x in lg]
+    w, floor, la = cargs.weight, cargs.floor, cargs.log_alpha
+
+    def fused():
+        ops.contrast_topk(lg, count, cargs, tv, ti, k)
+
+    def composed():
+        for x, o in zip(lg, lp):
+            ops.logsoftmax_topk(x, V, o, V, tv, ti, N, V, k)
+        if D:
+            s = lp[1] if D == 1 else torch.logsumexp(torch.stack(lp[1:]), 0) - math.log(D)
+            out = lp[0] - w * s.clamp_(min=floor)
+        else:
+            out = lp[0]
+        out = out.masked_fill(lg[0] - lg[0].max(-1, keepdim=True).values < la, float("-inf"))
+        ops.topk_rows(out, tv, ti, k)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1000.0 / reps
+
+    for fn in (fused, composed):
+        timed(fn)                                                                  # warm-up
+    tf, tc = [], []
+    for _ in range(rounds):
+        tf.append(timed(fused))
+        tc.append(timed(composed))
+    byt = 4.0 * (1 + D) * N * V
+    print(f"{form} rows alone (eager, {N} rows x {V} words, {1 + D} logits rows each): fused median {statistics.median(tf):.1f} us "
+          f"(min {min(tf):.1f}, max {max(tf):.1f}; {byt / statistics.median(tf) / 1e3:.1f} GB/s of logits read), composed "
+          f"{statistics.median(tc):.1f} us (min {min(tc):.1f}, max {max(tc):.1f}; {2 + D + (3 if D else 1) + (2 if D > 1 else 0)}+ launches)",
+          flush=True)
 
 
 if __name__ == "__main__":
