@@ -34,6 +34,9 @@
 // coefficients and then the scaled forms of the last two: reduced 4x4 / 2x2 / 1x1 inverse transforms per component
 // (idct_blocks) and a colour pass over ceil(W / s) × ceil(H / s) pixels (color_pixel), s = 1, 2, 4, 8 per image.
 //
+// One-component (grayscale) frames, sampling = 3, take the same launches in the same batch: one block per MCU in
+// block-raster order, tables 0 / 3, one plane, and a colour pass that writes R = G = B = Y (Pillow's L → RGB).
+//
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
 // whose coefficients leave the range where libjpeg-turbo's SIMD and C IDCTs agree (kIdctLimit), gets status 1:
@@ -139,8 +142,18 @@ bool batch_dims_ok(const Batch& b) {
          b.total_blocks > 0 && b.total_plane_bytes > 0;
 }
 
-__device__ __forceinline__ int blocks_per_mcu(int sampling) { return sampling == 0 ? 3 : (sampling == 1 ? 4 : 6); }
-__device__ __forceinline__ int luma_blocks(int sampling) { return sampling == 0 ? 1 : (sampling == 1 ? 2 : 4); }
+// sampling 3 is a one-component (grayscale) frame: one 8x8 block per MCU in block-raster order, Huffman tables 0 (DC)
+// and 3 (AC), quantisation table 0, a single plane and no colour conversion.
+constexpr int kGray = 3;
+__device__ __forceinline__ int blocks_per_mcu(int sampling) {
+  return sampling == kGray ? 1 : (sampling == 0 ? 3 : (sampling == 1 ? 4 : 6));
+}
+__device__ __forceinline__ int luma_blocks(int sampling) {
+  return sampling == 0 || sampling == kGray ? 1 : (sampling == 1 ? 2 : 4);
+}
+// luma blocks of an MCU across and down
+__device__ __forceinline__ int luma_h(int sampling) { return sampling == 0 || sampling == kGray ? 1 : 2; }
+__device__ __forceinline__ int luma_v(int sampling) { return sampling == 2 ? 2 : 1; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // segment: one workgroup of 256 lanes per image, 16 bytes per lane per 4 KiB tile
@@ -631,7 +644,7 @@ __global__ __launch_bounds__(64) void jpeg_serial_kernel(const odic_jpeg_header*
 __global__ __launch_bounds__(256) void jpeg_dc_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
   const odic_jpeg_header& h = hdrs[blockIdx.x];
   const int t = threadIdx.x;
-  const int nY = luma_blocks(h.sampling), bpm = nY + 2;
+  const int nY = luma_blocks(h.sampling), bpm = blocks_per_mcu(h.sampling);   // gray: one predictor, j < nY throughout
   const int nmcu = h.mcus_x * h.mcus_y, R = h.restart;
   short* coef = ws.coef + h.coef_off * 64;
   __shared__ int sv[3][256];
@@ -752,7 +765,7 @@ __device__ __forceinline__ bool idct_reads(int n, int i) {
 // only the input and the result).  libjpeg-turbo's SIMD 4x4 / 2x2 keep the same 16-bit intermediates as its 8x8.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int img, int lg, int (*ws8)[8][9]) {
-  const int nY = luma_blocks(h.sampling), bpm = nY + 2;
+  const int nY = luma_blocks(h.sampling), bpm = blocks_per_mcu(h.sampling);   // gray: every block is component 0
   const long nblocks = (long)h.mcus_x * h.mcus_y * bpm;
   const long b = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
   const int lane = threadIdx.x & 7, slot = threadIdx.x >> 3;
@@ -802,7 +815,7 @@ __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int i
   if (lane >= n) return;
   const long mcu = b / bpm;
   const int mx = (int)(mcu % h.mcus_x), my = (int)(mcu / h.mcus_x);
-  const int hy = h.sampling == 0 ? 1 : 2, vy = h.sampling == 2 ? 2 : 1;
+  const int hy = luma_h(h.sampling), vy = luma_v(h.sampling);
   int bx = mx, by = my, pw = h.mcus_x * nc;
   unsigned char* plane = ws.planes + h.plane_off;
   const long ysz = (long)h.mcus_x * ny * hy * h.mcus_y * ny * vy, csz = (long)h.mcus_x * nc * h.mcus_y * nc;
@@ -870,7 +883,7 @@ __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int i
   const int round = (1 << lg) - 1;
   const int W = kScaled ? (h.width + round) >> lg : h.width, H = kScaled ? (h.height + round) >> lg : h.height;
   if (x >= W || y >= H) return;
-  const int sampling = h.sampling, hy = sampling == 0 ? 1 : 2, vy = sampling == 2 ? 2 : 1;
+  const int sampling = h.sampling, hy = luma_h(sampling), vy = luma_v(sampling);
   int ny = 8, nc = 8;
   if (kScaled) scaled_sizes(sampling, lg, ny, nc);
   const int yw = h.mcus_x * ny * hy, cw = h.mcus_x * nc;
@@ -878,6 +891,11 @@ __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int i
   const unsigned char* Cb = Y + (long)yw * h.mcus_y * ny * vy;
   const unsigned char* Cr = Cb + (long)cw * h.mcus_y * nc;
   const int yv = Y[(long)y * yw + x];
+  unsigned char* o = out + h.out_off + ((long)y * W + x) * 3;
+  if (sampling == kGray) {                                    // the one plane is the image: Pillow's L → RGB
+    o[0] = o[1] = o[2] = (unsigned char)yv;
+    return;
+  }
   int cb, cr;
   if (sampling == 0 || (kScaled && sampling == 2 && lg > 0)) {
     cb = Cb[(long)y * cw + x];
@@ -907,7 +925,6 @@ __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int i
   }
   cb -= 128;
   cr -= 128;
-  unsigned char* o = out + h.out_off + ((long)y * W + x) * 3;
   o[0] = clamp255(yv + ((kCrR * cr + 32768) >> 16));
   o[1] = clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
   o[2] = clamp255(yv + ((kCbB * cb + 32768) >> 16));
@@ -1215,7 +1232,8 @@ __global__ __launch_bounds__(64) void jpeg_prog_decode_kernel(const odic_jpeg_pr
   const bool dc = sc.ss == 0, first_pass = sc.ah == 0;
   const int ntab = dc ? (first_pass ? __popc(sc.comp_mask & 7) : 0) : 1;
   bool ok = sc.restart > 0 && sc.n_units > 0 && (sc.comp_mask & 7) != 0 && sc.ss >= 0 && sc.ss <= sc.se &&
-            sc.se <= 63 && sc.al >= 0 && sc.al <= 13 && (dc || ((sc.comp_mask & (sc.comp_mask - 1)) == 0 && sc.blocks_w > 0));
+            sc.se <= 63 && sc.al >= 0 && sc.al <= 13 && (dc || ((sc.comp_mask & (sc.comp_mask - 1)) == 0 && sc.blocks_w > 0)) &&
+            (h.sampling != kGray || ((sc.comp_mask & 7) == 1 && sc.blocks_w > 0));   // gray: component 0 alone, every scan
   for (int q = 0; q < ntab && ok; ++q) {
     if ((unsigned)sc.table[q] >= (unsigned)n_tables) ok = false;
     else load_ptab(tables[sc.table[q]], T[q]);
@@ -1227,11 +1245,11 @@ __global__ __launch_bounds__(64) void jpeg_prog_decode_kernel(const odic_jpeg_pr
     x.w = (const unsigned*)(ws.scan + sc.scan_off);
     x.coef = ws.coef + h.coef_off * 64;
     x.nY = luma_blocks(h.sampling);
-    x.bpm = x.nY + 2;
+    x.bpm = blocks_per_mcu(h.sampling);                  // gray: the MCU order is the component's block raster
     x.nblocks = (long)h.mcus_x * h.mcus_y * x.bpm;
     x.mcus_x = h.mcus_x;
-    x.hy = h.sampling == 0 ? 1 : 2;
-    x.vy = h.sampling == 2 ? 2 : 1;
+    x.hy = luma_h(h.sampling);
+    x.vy = luma_v(h.sampling);
     x.u0 = k * sc.restart;
     x.nu = min(sc.restart, sc.n_units - x.u0);
     x.pos = ib[k];

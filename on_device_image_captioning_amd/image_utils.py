@@ -39,7 +39,9 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # `from_files(..., decode="device")`.  Files the device decoder does not take (arithmetic coding, non-JPEG, ...)
 # and images whose entropy data fails to decode are decoded by PIL in the same call, so the result and the
 # exceptions are those of the host path.  With a draft request (`draft=`) the files are decoded at 1/2, 1/4 or 1/8 scale
-# in the DCT domain, as `PIL.Image.draft` does, on either path and bit-exact between them.
+# in the DCT domain, as `PIL.Image.draft` does, on either path and bit-exact between them.  Non-RGB files are a black
+# canvas as in the reference, or with `non_rgb="convert"` what `convert("RGB")` makes of them: grayscale JPEGs on the
+# device, the other modes by PIL.
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -220,24 +222,30 @@ class DevicePreprocessor:
         torch.cuda.current_stream().wait_stream(self.stream)
         return out
 
-    def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None) -> torch.Tensor:
+    def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None,
+                   non_rgb: str = "black") -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
         the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
+        non_rgb="convert": a file of any other mode (L, LA, P, RGBA, I;16, CMYK, ...) is read as
+        `Image.open(f).convert("RGB")` instead of the black canvas, after the draft if there is one; with
+        decode="device" baseline grayscale JPEGs are decoded on the device, everything else non-RGB by PIL.
         draft=True: JPEGs are decoded at the scale `Image.draft("RGB", (S, S))` picks (1/2, 1/4 or 1/8 while both sides
         stay at least S) and resized from there; the tensor differs slightly from the undrafted one, identically for
         both values of `decode`.
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` instead
         of the whole-image batch, for either value of `decode` (torch.equal between them); with draft=True the boxes
         are in the coordinates of the drafted image."""
+        from .jpeg import check_non_rgb
+        check_non_rgb(non_rgb)
         if decode == "device":
             blobs = []
             for p in paths:
                 with open(p, "rb") as f:
                     blobs.append(f.read())
-            return self.from_jpeg_bytes(blobs, draft=draft, regions=regions)
+            return self.from_jpeg_bytes(blobs, draft=draft, regions=regions, non_rgb=non_rgb)
         if decode != "host":
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
-        arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None) for p in paths]
+        arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None, non_rgb) for p in paths]
         if regions is None:
             return self(arrays)
         for a in arrays:
@@ -245,22 +253,22 @@ class DevicePreprocessor:
         return self.resize_regions([torch.from_numpy(a.copy()).to(self.device) for a in arrays], regions)
 
     @staticmethod
-    def _pil_rgb(pil, draft=None) -> np.ndarray:
-        """The host decode of one opened file: the draft request if there is one, a black canvas for non-RGB modes
-        (of the size the draft left) → uint8 (H,W,3) array."""
+    def _pil_rgb(pil, draft=None, non_rgb="black") -> np.ndarray:
+        """The host decode of one opened file: the draft request if there is one, then for non-RGB modes a black canvas
+        (of the size the draft left) or, with non_rgb="convert", PIL's `convert("RGB")` → uint8 (H,W,3) array."""
         if draft is not None:
             pil.draft("RGB", draft)
         if pil.mode != "RGB":
-            pil = Image.new("RGB", pil.size)
+            pil = pil.convert("RGB") if non_rgb == "convert" else Image.new("RGB", pil.size)
         return np.asarray(pil, dtype=np.uint8)
 
     # ---------------------------------------------------------------------------------------------------------
     # device JPEG decode
     # ---------------------------------------------------------------------------------------------------------
-    def _host_rgb(self, blob, draft=None) -> np.ndarray:
+    def _host_rgb(self, blob, draft=None, non_rgb="black") -> np.ndarray:
         """The host path for one file: PIL decode, after `im.draft("RGB", draft)` if there is a draft request (black
-        canvas for non-RGB modes, of the drafted size) → uint8 (H,W,3) array."""
-        return self._pil_rgb(Image.open(io.BytesIO(blob)), draft)
+        canvas for non-RGB modes, of the drafted size, or their `convert("RGB")`) → uint8 (H,W,3) array."""
+        return self._pil_rgb(Image.open(io.BytesIO(blob)), draft, non_rgb)
 
     @staticmethod
     def _grow(buf, nbytes, **kw):
@@ -284,9 +292,12 @@ class DevicePreprocessor:
         return tuple(self._jpeg_routes)
 
     def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host",
-                    draft=None):
+                    draft=None, non_rgb: str = "black"):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
-        np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path).  Baseline JPEGs are
+        np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path; with
+        non_rgb="convert" each equals np.asarray(PIL.Image.open(f).convert("RGB")) instead: one-component JPEGs take the
+        device routes below like three-component ones, four-component JPEGs and every other non-RGB file go to PIL, and
+        no route is "black").  Baseline JPEGs are
         decoded by odic_jpeg_decode and, with progressive="device", progressive ones by odic_jpeg_decode_progressive
         (the default "host" sends them to PIL until the device route is measured faster), each kind in one batched call, with one host-to-device copy and one status read-back
         for both; the rest, and images the device rejects, by PIL.  Exceptions are the host path's, in its order: PIL's,
@@ -298,16 +309,18 @@ class DevicePreprocessor:
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
+        J.check_non_rgb(non_rgb)
+        opt = () if non_rgb == "black" else (non_rgb,)                   # the default's calls stay as they are
         if draft is not None:
             draft = (int(draft[0]), int(draft[1]))
             if draft[0] <= 0 or draft[1] <= 0:
                 raise ValueError(f"draft wants a positive (width, height), not {draft!r}")
         blobs = [bytes(b) for b in blobs]
-        hdrs = [J.parse(b) for b in blobs]
+        hdrs = [J.parse(b, *opt) for b in blobs]
         if progressive == "device":
             for i, h in enumerate(hdrs):
                 if h.kind == J.HOST and h.reason == "SOF2":
-                    ph = J.parse_progressive(blobs[i])
+                    ph = J.parse_progressive(blobs[i], *opt)
                     if ph.kind == J.DEVICE:
                         hdrs[i] = ph
         out = [None] * len(blobs)
@@ -336,7 +349,7 @@ class DevicePreprocessor:
         self._jpeg_routes = routes
         for i, h in enumerate(hdrs):                                     # input order, as the host path
             if h.kind != J.BLACK and out[i] is None:
-                out[i] = self._host_rgb(blobs[i], draft)
+                out[i] = self._host_rgb(blobs[i], draft, *opt)
         for i, h in enumerate(hdrs):
             if h.kind == J.BLACK:
                 self._check_size(sizes[i][1], sizes[i][0])
@@ -413,13 +426,15 @@ class DevicePreprocessor:
         return self._jpeg_ws[lo:hi].view(torch.int16).view(-1, 64).clone()
 
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
-                        progressive: str = "host", draft: bool = False, regions=None) -> torch.Tensor:
+                        progressive: str = "host", draft: bool = False, regions=None,
+                        non_rgb: str = "black") -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
-        torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`).
+        torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`,
+        and the same `non_rgb`).
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` on the
         decoded images instead; with draft=True the boxes are in the coordinates of the drafted image."""
         imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
-                                draft=(self.S, self.S) if draft else None)
+                                draft=(self.S, self.S) if draft else None, non_rgb=non_rgb)
         if regions is not None:
             return self.resize_regions(imgs, regions)
         S = self.S

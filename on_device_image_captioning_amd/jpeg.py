@@ -18,6 +18,12 @@ parser does not fully understand goes to PIL, which then raises or decodes exact
     host    everything else (progressive, arithmetic, 12-bit, lossless, Adobe RGB, multi-scan, DNL,
             non-JPEG data, malformed or truncated headers, more than MAX_SCAN_BYTES after SOS)
 
+That is the default, non_rgb="black".  Under non_rgb="convert" every file is to equal
+`np.asarray(PIL.Image.open(f).convert("RGB"))` and nothing is `black`: a one-component frame (baseline here, SOF2 in
+`parse_progressive`) is a `device` kind with sampling GRAY — one 8x8 block per MCU in block-raster order, whatever
+sampling factors and component id the SOF declares, which libjpeg ignores for a single component — and a four-component
+frame is `host`, where PIL converts it.
+
 `parse` keeps that sorting.  For the files it turns away with reason "SOF2", `parse_progressive` (below) reads the whole
 scan script, locating every scan's end in the file, and packs the records odic_jpeg_decode_progressive reads.
 """
@@ -38,7 +44,15 @@ NATURAL_ORDER = np.array([
 MAX_SCAN_BYTES = 1 << 27           # kMaxScanBytes of csrc/jpeg_decode.hip: bit positions stay int32
 LUT_BITS = 9                       # codes up to this length decode with one table lookup on the device
 SAMPLING = {(1, 1): 0, (2, 1): 1, (2, 2): 2}          # luma (h, v) → 0: 4:4:4, 1: 4:2:2 (h2v1), 2: 4:2:0 (h2v2)
-BLOCKS_PER_MCU = (3, 4, 6)
+GRAY = 3                                              # `sampling` of a one-component frame: one 8x8 block per MCU
+BLOCKS_PER_MCU = (3, 4, 6, 1)
+NON_RGB = ("black", "convert")                        # what a file that is not three-component RGB / YCbCr becomes
+
+
+def check_non_rgb(non_rgb):
+    if non_rgb not in NON_RGB:
+        raise ValueError(f"non_rgb must be 'black' or 'convert', not {non_rgb!r}")
+    return non_rgb
 
 # odic_jpeg_header (include/odic_hip.h), field for field
 HEADER_DTYPE = np.dtype([
@@ -92,10 +106,13 @@ def _u16(b, i):
     return (b[i] << 8) | b[i + 1]
 
 
-def parse(blob) -> JpegHeader:
-    """Walk the markers of one file up to SOS → JpegHeader with its kind; never raises."""
+def parse(blob, non_rgb: str = "black") -> JpegHeader:
+    """Walk the markers of one file up to SOS → JpegHeader with its kind; never raises on a file's content.
+    non_rgb="convert": a one-component frame is a device kind (sampling GRAY) and a four-component one goes to the
+    host, where PIL converts it; the default "black" sorts both as BLACK."""
+    check_non_rgb(non_rgb)
     try:
-        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob)
+        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob, non_rgb)
     except _Bad as e:
         return JpegHeader(HOST, reason=str(e))
     except (IndexError, ValueError) as e:
@@ -215,7 +232,7 @@ class _Walker:
                 raise _Bad(f"marker {m:02X}")
 
 
-def _frame(w, header, sof_kinds, distinct_ids):
+def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black"):
     """What the frame admits, by libjpeg's rules, at the first SOS → header(BLACK) or header(DEVICE) with the frame
     fields; anything else raises.  sof_kinds: {C0, C1} for `parse`, {C2} for `parse_progressive`."""
     if w.sof is None:
@@ -225,15 +242,24 @@ def _frame(w, header, sof_kinds, distinct_ids):
         raise _Bad(f"{prec}-bit")
     if nc not in (1, 3, 4):
         raise _Bad(f"{nc} components")
-    if nc in (1, 4) and m in (0xC0, 0xC1, 0xC2):
+    if nc in (1, 4) and m in (0xC0, 0xC1, 0xC2) and non_rgb == "black":
         # PIL opens these as mode L / CMYK and the host path substitutes a black RGB canvas without decoding
         if width == 0 or height == 0:
             raise _Bad("empty frame")
         return header(BLACK, width=width, height=height, ncomp=nc)
+    if nc == 4 and m in (0xC0, 0xC1, 0xC2):           # non_rgb="convert": Adobe inversion, YCCK and PIL's CMYK → RGB are
+        raise _Bad("4 components (CMYK / YCCK)")      # the host's, whichever parser asks
     if m not in sof_kinds:
         raise _Bad(f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
         raise _Bad("DNL / empty frame")
+    if nc == 1:
+        # libjpeg decodes a one-component frame as one block per MCU in block-raster order whatever sampling factors
+        # and component id the SOF declares, and no colour-space latch applies: the header says (1, 1) for all of them
+        if comps[0][3] not in w.qt:
+            raise _Bad("missing DQT")
+        return header(DEVICE, width=width, height=height, ncomp=1, sampling=GRAY, comp_ids=[comps[0][0]],
+                      comp_hv=[(1, 1)], qtables=[w.qt[comps[0][3]]])
     ids = [c[0] for c in comps]
     if w.jfif:
         ycc = True
@@ -255,20 +281,20 @@ def _frame(w, header, sof_kinds, distinct_ids):
                   qtables=[w.qt[c[3]] for c in comps])
 
 
-def _parse(b) -> JpegHeader:
+def _parse(b, non_rgb="black") -> JpegHeader:
     w = _Walker(b)
     s = next(w.scans(script=False))                   # the first SOS; whatever keeps the walk from it raises
-    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False)
+    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False, non_rgb=non_rgb)
     if hd.kind != DEVICE:
         return hd
-    # SOS: one interleaved baseline scan of all three components, in frame order
+    # SOS: one baseline scan of all the frame's components (three interleaved, or the one of a gray frame), in frame order
     ns = s[0] if len(s) >= 1 else 0
-    if ns != 3 or len(s) != 1 + 2 * ns + 3:
+    if ns != hd.ncomp or len(s) != 1 + 2 * ns + 3:
         raise _Bad("not one interleaved scan")
-    sel = [(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(3)]
+    sel = [(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(ns)]
     if [x[0] for x in sel] != hd.comp_ids:
         raise _Bad("scan component order")
-    ss, se, ah_al = s[7], s[8], s[9]
+    ss, se, ah_al = s[1 + 2 * ns], s[2 + 2 * ns], s[3 + 2 * ns]
     if ss != 0 or se != 63 or ah_al != 0:
         raise _Bad("bad spectral selection")
     for _, td, ta in sel:
@@ -354,7 +380,7 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
     r["width"], r["height"], r["sampling"] = h.width, h.height, h.sampling
     r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
-    for c in range(3):
+    for c in range(h.ncomp):                          # a gray frame: qt[0], the rest stays zero
         r["qt"][c] = h.qtables[c]
     out_offs.append(out_bytes)
     tot["total_blocks"] += blocks
@@ -385,7 +411,7 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None):
         r["int_off"], r["unit_off"] = tot["total_intervals"], tot["total_units"]
         r["restart"] = h.restart_interval or nmcu
         r["n_intervals"], r["n_units"] = nint, units
-        for c in range(3):
+        for c in range(h.ncomp):                      # a gray frame: DC table 0, AC table 3, the rest stays zero
             for t, tab in ((c, h.dc_tables[c]), (3 + c, h.ac_tables[c])):
                 lut, mc, vo, hv = device_tables(tab)
                 r["lut"][t], r["maxcode"][t], r["valoff"][t], r["huffval"][t] = lut, mc, vo, hv
@@ -408,7 +434,8 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None):
 # device  8-bit SOF2 Huffman, three YCbCr components under the rules of `parse`, any scan script libjpeg accepts
 #         without a warning and that leaves every coefficient of every component at full precision by EOI
 #         (libjpeg's inter-block smoothing only runs for incomplete scripts), DHT / DRI redefined between scans,
-#         at most MAX_SCANS scans
+#         at most MAX_SCANS scans; under non_rgb="convert" also one component (sampling GRAY), whose scans, the DC scans
+#         included, are all non-interleaved over the block raster
 # host    everything else: bogus progressions, AC before DC, an incomplete script, DQT or any other marker
 #         between scans, DNL, a scan cut short or a missing EOI, more than MAX_SCANS scans
 # ---------------------------------------------------------------------------------------------------------------
@@ -470,26 +497,28 @@ def marker_positions(blob) -> np.ndarray:
     return ff[(nx != 0) & (nx != 0xFF) & ((nx & 0xF8) != 0xD0)]
 
 
-def parse_progressive(blob) -> ProgHeader:
+def parse_progressive(blob, non_rgb: str = "black") -> ProgHeader:
     """The whole scan script of a progressive file → ProgHeader of kind DEVICE, or HOST with a reason (BLACK for
-    one and four components, as `parse`); never raises."""
+    one and four components, as `parse`; under non_rgb="convert" a one-component frame is a device kind whose scans
+    are all non-interleaved, and a four-component one is HOST); never raises on a file's content."""
+    check_non_rgb(non_rgb)
     try:
-        return _parse_progressive(bytes(blob))
+        return _parse_progressive(bytes(blob), non_rgb)
     except _Bad as e:
         return ProgHeader(HOST, reason=str(e))
     except (IndexError, ValueError) as e:
         return ProgHeader(HOST, reason=f"malformed: {e}")
 
 
-def _parse_progressive(b) -> ProgHeader:
+def _parse_progressive(b, non_rgb="black") -> ProgHeader:
     w = _Walker(b)
     hd = coef_bits = marks = None                  # set at the first SOS; coef_bits: [3][64] current Al of every
     for s in w.scans(script=True):                 # coefficient, -1: not yet sent (lists)
         if hd is None:
-            hd = _frame(w, ProgHeader, (0xC2,), distinct_ids=True)
+            hd = _frame(w, ProgHeader, (0xC2,), distinct_ids=True, non_rgb=non_rgb)
             if hd.kind != DEVICE:
                 return hd
-            coef_bits = [[-1] * 64 for _ in range(3)]
+            coef_bits = [[-1] * 64 for _ in range(hd.ncomp)]
             marks = marker_positions(b)
         if len(hd.scans) >= MAX_SCANS:
             raise _Bad(f"more than {MAX_SCANS} scans")

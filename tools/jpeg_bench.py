@@ -15,6 +15,11 @@ size; the two results are checked torch.equal first.  One JSON line per batch si
 path is what every progressive file took before odic_jpeg_decode_progressive; then tatin.jpg itself (1280x960), alone
 and as a batch of copies; and the cost of jpeg.parse_progressive per file.
 
+--gray: the same crops saved as mode L (one component), decoded under non_rgb="convert": the device path against the
+host's `Image.open(f).convert("RGB")`; with --progressive, their progressive re-saves.
+
+    python tools/jpeg_bench.py --gray --batches 16 64 --iters 20 --out profiles/r12_jpeg_gray_bench.json
+
 --draft: what decoding at the scale `Image.draft("RGB", (S, S))` picks saves.  Seeded synthetic JPEGs,
 3456x4608 (drafts at 1/8) and 640x480 (drafts at 1/1: the control), 4:2:0 and 4:4:4, baseline and progressive; per
 case `decode_jpeg` alone and `from_jpeg_bytes` (decode + resize), draft off and on alternating in the same process,
@@ -42,7 +47,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def make_inputs(n: int, seed: int = 0, progressive: bool = False):
+def make_inputs(n: int, seed: int = 0, progressive: bool = False, gray: bool = False):
     from PIL import Image
     src = Image.open(os.path.join(ROOT, "tests", "golden", "demo_material", "micheal.jpg")).convert("RGB")
     rng = np.random.default_rng(seed)
@@ -55,7 +60,10 @@ def make_inputs(n: int, seed: int = 0, progressive: bool = False):
         if rng.integers(2):
             im = im.transpose(Image.FLIP_LEFT_RIGHT)
         buf = io.BytesIO()
-        im.save(buf, format="JPEG", quality=90, subsampling=2, progressive=progressive)
+        if gray:
+            im.convert("L").save(buf, format="JPEG", quality=90, progressive=progressive)
+        else:
+            im.save(buf, format="JPEG", quality=90, subsampling=2, progressive=progressive)
         out.append(buf.getvalue())
     return out
 
@@ -149,6 +157,7 @@ def main():
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--sweep", action="store_true", help="also time the device path at other subseq_bits / passes")
     ap.add_argument("--progressive", action="store_true", help="progressive re-saves of the crops, and tatin.jpg")
+    ap.add_argument("--gray", action="store_true", help="the crops as one-component files, non_rgb='convert'")
     ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
     ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
     ap.add_argument("--out", default=None)
@@ -161,7 +170,8 @@ def main():
     from on_device_image_captioning_amd.image_utils import DevicePreprocessor
     assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
     pre = DevicePreprocessor(args.size, "cuda:0")
-    blobs_all = make_inputs(max(args.batches), progressive=args.progressive)
+    blobs_all = make_inputs(max(args.batches), progressive=args.progressive, gray=args.gray)
+    non_rgb = "convert" if args.gray else "black"
     want_route = "device-progressive" if args.progressive else "device"
     inputs = [(B, blobs_all[:B], (640, 480)) for B in args.batches]
     parse_us = None
@@ -169,19 +179,22 @@ def main():
         from on_device_image_captioning_amd import jpeg as J
         with open(os.path.join(ROOT, "tests", "golden", "demo_material", "tatin.jpg"), "rb") as f:
             tatin = f.read()
-        inputs += [(1, [tatin], (1280, 960)), (16, [tatin] * 16, (1280, 960))]
+        if not args.gray:                                # tatin.jpg is a colour file
+            inputs += [(1, [tatin], (1280, 960)), (16, [tatin] * 16, (1280, 960))]
         t0 = time.perf_counter()
         for _ in range(5):
             for b in blobs_all:
-                J.parse(b)
-                J.parse_progressive(b)
+                J.parse(b, non_rgb)
+                J.parse_progressive(b, non_rgb)
         parse_us = 1e6 * (time.perf_counter() - t0) / (5 * len(blobs_all))
 
     def host(blobs):
+        if args.gray:
+            return pre([np.asarray(Image.open(io.BytesIO(b)).convert("RGB")) for b in blobs])
         return pre([np.asarray(Image.open(io.BytesIO(b))) for b in blobs])
 
     def device(blobs):
-        return pre.from_jpeg_bytes(blobs, progressive="device" if args.progressive else "host")
+        return pre.from_jpeg_bytes(blobs, progressive="device" if args.progressive else "host", non_rgb=non_rgb)
 
     lines = []
     for B, blobs, (width, height) in inputs:
@@ -208,7 +221,8 @@ def main():
         if args.sweep:
             for bits in (1024, 2048, 4096):
                 for passes in (2, 4, 8):
-                    fn = lambda b, bits=bits, passes=passes: pre.from_jpeg_bytes(b, bits, passes)   # noqa: E731
+                    fn = lambda b, bits=bits, passes=passes: pre.from_jpeg_bytes(   # noqa: E731
+                        b, bits, passes, non_rgb=non_rgb)
                     for _ in range(2):
                         fn(blobs)
                     torch.cuda.synchronize()
@@ -219,8 +233,8 @@ def main():
                         torch.cuda.synchronize()
                         ts.append(time.perf_counter() - t0)
                     sweep[f"bits{bits}_passes{passes}"] = B / float(np.median(ts))
-        line = {"batch": B, "width": width, "height": height, "quality": 90, "subsampling": "4:2:0",
-                "progressive": args.progressive,
+        line = {"batch": B, "width": width, "height": height, "quality": 90,
+                "subsampling": "gray" if args.gray else "4:2:0", "progressive": args.progressive,
                 "mean_jpeg_bytes": int(np.mean([len(b) for b in blobs])),
                 "host_images_per_s": B / med["host"], "device_images_per_s": B / med["device"],
                 "speedup": med["host"] / med["device"],
