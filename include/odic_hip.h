@@ -861,7 +861,17 @@ typedef struct odic_embed_args {
 } odic_embed_args;
 /*   Limits: beams <= 16, 2 <= T <= 128 (per-token log-probs are staged in LDS), n_img <= 32767 (the
  *   arrival counter packs {arrivals, still-growing images} into one int32): ODIC_EINVAL otherwise.
- *   A call with *pos == T - 1 (the prefix is full) changes nothing.  emb: NULL or the embedding tail above. */
+ *   A call with *pos == T - 1 (the prefix is full) changes nothing.  emb: NULL or the embedding tail above.
+ *   Dead rows (one convention for the four step entry points).  At *pos >= 1 a total of -inf is never ranked: a row with
+ *   cumul = -inf offers nothing, nor does a candidate of value -inf (the short-row rule of the top-k kernels); a finished
+ *   row offers its rank-0 candidate at 0 and the others at -999.  The `beams` largest totals above -inf are taken, the
+ *   lowest flat index row·beams + rank winning a tie.  With fewer than `beams` of them, every remaining slot becomes an
+ *   EMPTY row: parent = the slot's own row, word = eos_idx (embedded like any other word: the caller keeps it inside the
+ *   table), stored log-prob -inf — after the update it has cumul = -inf and has_eos = 1, offers nothing again, counts as
+ *   finished for *done from the next step on, and odic_beam_finalize scores it -inf.  Every index the kernel forms from a
+ *   selection lies inside the image's rows and candidates, whatever the candidate values are
+ *   (tests/test_beam_dead_rows_gpu.py).  The seeding call (*pos == 0) takes the candidates of row 0 as they come.  Rows
+ *   with a NaN stay outside the contract (a NaN total is never ranked either). */
 int odic_beam_step(const float* cand_val, const int32_t* cand_idx, const odic_beam_state* st,
                    const odic_embed_args* emb, int32_t n_img, int32_t beams, int32_t T, int64_t eos_idx,
                    void* stream);
@@ -876,8 +886,12 @@ int odic_beam_step(const float* cand_val, const int32_t* cand_idx, const odic_be
  *   v = logp_j(w) - penalty·count[w],   total = cumul_j + v
  * (three separately rounded fp32 operations); a finished beam offers its rank-0 candidate at 0 and the others at -999,
  * never penalised, as in odic_beam_step.  The group keeps its group_beams best candidates: total descending, then beam
- * in group ascending, then word ascending (at groups = 1 the rule of odic_beam_step; the call then leaves the state
- * bitwise as odic_beam_step does).  At *pos == 0 group g draws from its own first row (all rows hold the same
+ * in group ascending, then word ascending — among the -999 fillers of one finished beam, rank ascending (at groups = 1 the
+ * rule of odic_beam_step; the call then leaves the state bitwise as odic_beam_step does, EMPTY rows included, at every
+ * *pos >= 1, and at *pos == 0 while row 0 holds `beams` candidates above -inf).  Dead rows follow odic_beam_step's
+ * convention, group by group: a total of -inf is never ranked, and a slot for which the group has no total above -inf left
+ * becomes an EMPTY row (parent = the slot's own row, word = eos_idx, stored log-prob -inf) that no later group counts in
+ * count[w] — a group never holds one live caption twice.  At *pos == 0 group g draws from its own first row (all rows hold the same
  * distribution) against the seeds of the groups before it.  The penalty only steers the choice: logprobs[.., pos+1] is
  * the word's own log-prob and cumul the re-summed unpenalised prefix, so odic_beam_finalize scores the captions by the
  * model alone.  R candidates per row suffice: the penalised top-group_beams of a row lies inside its unpenalised
@@ -1014,7 +1028,10 @@ int odic_beam_reset_prefix(const odic_beam_state* st, const odic_embed_args* emb
                            int32_t P, int64_t sos_idx, void* stream);
 
 /* Final selection (captioning_model.py:225-241): score = cumul / n_elem, descending order per
- * image → order int32 [n_img, beams], score fp32 [n_img, beams]. */
+ * image → order int32 [n_img, beams], score fp32 [n_img, beams].
+ * order[b] is always a permutation of 0 .. beams-1: score descending, a tie to the lower row, and -inf against -inf is a
+ * tie — dead and EMPTY rows (score -inf) come last, in row order.  odic_beam_finalize_best emits row order[b][0], which
+ * is row 0 when every row of the image is dead. */
 int odic_beam_finalize(const odic_beam_state* st, int32_t* order, float* score, int32_t n_img,
                        int32_t beams, void* stream);
 

@@ -587,7 +587,12 @@ __global__ __launch_bounds__(1024) void logsoftmax_sample_kernel(const float* __
 // (beam_apply) live in beam_step.h, which stochastic_beam.hip shares.
 // ---------------------------------------------------------------------------------------------
 // the k best of the k x k candidates.  Key: the flat candidate index beam·k + rank (the scan order of the reference's
-// topk over the flattened scores; drawn candidates are not sorted by word, and a finished row's rule is positional)
+// topk over the flattened scores; drawn candidates are not sorted by word, and a finished row's rule is positional).
+// A total of -inf is never ranked (a dead row, cumul = -inf; a candidate of value -inf; a NaN total compares false and
+// goes the same way).  A slot for which no total above -inf is left (not found) becomes the EMPTY row of
+// require_beam_select: parent = the slot itself, word = EOS, stored log-prob -inf.  A found key is a flat index that was
+// put in below, so every index formed from a selection lies in [0, k) (s.parent) and [0, k·k) (s.ci), whatever the
+// candidate values are.
 __device__ __forceinline__ void beam_select(const BeamParams& p, BeamShared& s, int t) {
   if (threadIdx.x >= 64) return;
   const int lane = threadIdx.x, k = p.k;
@@ -609,8 +614,11 @@ __device__ __forceinline__ void beam_select(const BeamParams& p, BeamShared& s, 
   }
   for (int r = 0; r < k; ++r) {
     int bi; float bval;
-    wave_extract_best(tot, key, val, bi, bval);
-    if (lane == 0) { s.parent[r] = bi / k; s.word[r] = s.ci[bi]; s.lp[r] = bval; }
+    const bool found = wave_extract_best(tot, key, val, bi, bval);
+    if (lane == 0) {
+      if (found) { s.parent[r] = bi / k; s.word[r] = s.ci[bi]; s.lp[r] = bval; }
+      else { s.parent[r] = r; s.word[r] = (int)p.eos; s.lp[r] = -INFINITY; }
+    }
   }
 }
 
@@ -637,6 +645,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p, EmbedArgs 
 // for bit.  The picks made so far ARE the penalty list: s.word[q] and grow[q] for q < g·kg (at most 15 entries), read
 // back by the next group after a fence.  Seeding (t = 0): every row holds the same distribution; group g draws from its
 // first row, against the seeds of the groups before it.
+// A finished beam's candidates carry their rank in place of the word in the key (its -999 fillers tie, and beam_select
+// takes them by flat index; lane 0 reads the word back from s.ci).  A slot for which no total above -inf is left becomes
+// the EMPTY row of beam_select (parent = the slot's own row, word = EOS, stored log-prob -inf, grow = 0: never counted
+// by a later group), so a group never holds one live caption twice.
 // R candidates per row are enough: the penalised top-kg of a row lies inside its unpenalised top-(kg + P), P <= g·kg <=
 // R - kg the number of penalised words.
 // ---------------------------------------------------------------------------------------------
@@ -655,9 +667,11 @@ __device__ __forceinline__ void group_beam_select(const BeamParams& p, BeamShare
       if (i < nc) {
         const int j = i / R, c = i - j * R, row = row0 + j, fl = row * R + c;
         const int w = s.ci[fl];
+        int low = w;
         float v;
         if (t > 0 && s.eos[row]) {
           v = val[u] = c == 0 ? 0.0f : -999.0f;
+          low = c;                                       // the -999 fillers of a row tie: by rank, as in beam_select
         } else {
           int cnt = 0;
           for (int q = 0; q < row0; ++q) cnt += (grow[q] && s.word[q] == w) ? 1 : 0;
@@ -665,18 +679,21 @@ __device__ __forceinline__ void group_beam_select(const BeamParams& p, BeamShare
           v = __fsub_rn(val[u], pen[cnt]);
         }
         tot[u] = t == 0 ? v : __fadd_rn(s.cu[row], v);
-        key[u] = ((long long)j << 32) | (long long)(unsigned)w;
+        key[u] = ((long long)j << 32) | (long long)(unsigned)low;
       }
     }
     for (int r = 0; r < kg; ++r) {
       long long bk; float bval;
       const bool found = wave_extract_best(tot, key, val, bk, bval);
-      if (lane == 0) {                                   // (fewer than kg finite candidates: the group's first one)
-        const int row = found ? row0 + (int)(bk >> 32) : row0;
-        const int fin = t > 0 && s.eos[row];
-        s.parent[row0 + r] = row; s.word[row0 + r] = found ? (int)(bk & 0xffffffffLL) : s.ci[row0 * R];
-        s.lp[row0 + r] = found ? bval : fin ? 0.0f : s.cv[row0 * R];
-        grow[row0 + r] = fin ? 0 : 1;
+      if (lane == 0) {
+        const int q = row0 + r;
+        if (found) {                                     // (a found key was put in above: row in the group, low < 2^31)
+          const int row = row0 + (int)(bk >> 32), low = (int)(bk & 0xffffffffLL);
+          const int fin = t > 0 && s.eos[row];
+          s.parent[q] = row; s.word[q] = fin ? s.ci[row * R + low] : low; s.lp[q] = bval; grow[q] = fin ? 0 : 1;
+        } else {                                         // no total above -inf is left: the EMPTY row of beam_select
+          s.parent[q] = q; s.word[q] = (int)p.eos; s.lp[q] = -INFINITY; grow[q] = 0;
+        }
       }
     }
     // lane 0's picks are read by every lane of this wave in the next group
@@ -793,18 +810,32 @@ __global__ __launch_bounds__(256) void require_beam_step_kernel(BeamParams p, Em
   beam_apply(p, e, s, b, t);
 }
 
+// score = cumul / n_elem of the k rows of image b, and their order: score descending, a tie (-inf against -inf included)
+// to the lower row.  The rows already listed are remembered in a bit mask, their scores left alone, and every round takes
+// the first row not yet listed unless a later one is strictly better: order is a permutation of 0..k-1 whatever the
+// scores are (dead rows, score -inf, come last in row order).  Returns order[0].
+__device__ __forceinline__ int beam_rank_rows(const float* cumul, const int* n_elem, int* order, float* score, int b,
+                                              int k) {
+  float sc[MAX_K];
+  for (int j = 0; j < k; ++j) { sc[j] = cumul[b * k + j] / (float)n_elem[b * k + j]; score[b * k + j] = sc[j]; }
+  unsigned taken = 0;
+  int first = 0;
+  for (int r = 0; r < k; ++r) {
+    int bi = -1; float bv = 0.f;
+    for (int j = 0; j < k; ++j)
+      if (!((taken >> j) & 1u) && (bi < 0 || sc[j] > bv)) { bv = sc[j]; bi = j; }
+    taken |= 1u << bi;
+    order[b * k + r] = bi;
+    if (r == 0) first = bi;
+  }
+  return first;
+}
+
 __global__ void beam_finalize_kernel(const float* cumul, const int* n_elem, int* order, float* score, int n_img,
                                      int k) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n_img) return;
-  float sc[MAX_K];
-  for (int j = 0; j < k; ++j) { sc[j] = cumul[b * k + j] / (float)n_elem[b * k + j]; score[b * k + j] = sc[j]; }
-  for (int r = 0; r < k; ++r) {
-    int bi = 0; float bv = -INFINITY;
-    for (int j = 0; j < k; ++j) if (sc[j] > bv) { bv = sc[j]; bi = j; }
-    sc[bi] = -INFINITY;
-    order[b * k + r] = bi;
-  }
+  beam_rank_rows(cumul, n_elem, order, score, b, k);
 }
 
 // odic_beam_finalize + emission of the best caption (EOS-padded int32 row + length): one 64-lane block per image
@@ -813,17 +844,7 @@ __global__ __launch_bounds__(64) void beam_finalize_best_kernel(const float* cum
                                                                 int* out_tok, int* out_len, int k, int T, int pad) {
   __shared__ int s_best;
   const int b = blockIdx.x, lane = threadIdx.x;
-  if (lane == 0) {
-    float sc[MAX_K];
-    for (int j = 0; j < k; ++j) { sc[j] = cumul[b * k + j] / (float)n_elem[b * k + j]; score[b * k + j] = sc[j]; }
-    for (int r = 0; r < k; ++r) {
-      int bi = 0; float bv = -INFINITY;
-      for (int j = 0; j < k; ++j) if (sc[j] > bv) { bv = sc[j]; bi = j; }
-      sc[bi] = -INFINITY;
-      order[b * k + r] = bi;
-      if (r == 0) s_best = bi;
-    }
-  }
+  if (lane == 0) s_best = beam_rank_rows(cumul, n_elem, order, score, b, k);   // (row 0 when every row is dead)
   __syncthreads();
   const int best = s_best;
   const int len = n_elem[b * k + best];

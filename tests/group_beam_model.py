@@ -6,7 +6,11 @@ Written from the semantics in include/odic_hip.h (odic_group_beam_step) and DESI
   * count[w] = number of picks of earlier groups AT THIS STEP that appended w to a beam that had not finished before;
   * a growing beam j offers word w at v = logp_j(w) - penalty·count[w], total = cumul_j + v (three float32 operations);
   * a finished beam offers its rank-0 candidate at 0 and every other one at -999, never penalised;
-  * a group keeps its kg best: total descending, then beam in group ascending, then word ascending;
+  * a total of -inf is never ranked (a dead beam, cumul = -inf, offers nothing; nor does a candidate of value -inf);
+  * a group keeps its kg best: total descending, then beam in group ascending, then word ascending — among the -999
+    fillers of one finished beam, rank ascending (the flat index of odic_beam_step);
+  * a slot for which no total above -inf is left becomes an EMPTY row: parent = the slot's own row, word = EOS, stored
+    value -inf, not growing (it is never counted by a later group);
   * at t = 0 group g draws from its own first row, total = v;
   * what is stored is the candidate's own value; cumul is the float32 sum, in position order, of the parent's per-token
     log-probs plus the new one.
@@ -33,9 +37,10 @@ def new_state(n_img: int, R: int, T: int, sos: int, fill: int = 0) -> dict:
     return st
 
 
-def select_image(cv, ci, cumul, has_eos, t: int, G: int, kg: int, lam: float):
+def select_image(cv, ci, cumul, has_eos, t: int, G: int, kg: int, lam: float, eos: int | None = None):
     """The selection of one image.  cv / ci: [R, C] candidates of its R = G·kg rows, every row sorted by value descending,
     then word ascending (C = R for the kernel; any C >= 1 here, the whole vocabulary included).  cumul / has_eos: [R].
+    eos: the word of an EMPTY row (needed only where a group runs out of totals above -inf).
     Returns parent (row within the image), word, lp (the stored value), grow — each [R] — and a dict of the events met."""
     R = G * kg
     lam = F(lam)
@@ -44,7 +49,7 @@ def select_image(cv, ci, cumul, has_eos, t: int, G: int, kg: int, lam: float):
     ev = dict(same_word_wanted=False, tie_across_beams=False, tie_within_beam_after_penalty=False)
     for g in range(G):
         rows = [g * kg] if t == 0 else list(range(g * kg, g * kg + kg))
-        cands = []                                   # (total, beam in group, word, stored value, row, count, plain total)
+        cands = []                    # (total, beam in group, word, stored value, row, count, plain total, tie key)
         for j, row in enumerate(rows):
             fin = t > 0 and bool(has_eos[row])
             for c in range(cv.shape[1]):
@@ -57,12 +62,18 @@ def select_image(cv, ci, cumul, has_eos, t: int, G: int, kg: int, lam: float):
                     v, stored = F(F(cv[row, c]) - pen), F(cv[row, c])
                 total = v if t == 0 else F(F(cumul[row]) + v)
                 plain = stored if t == 0 else F(F(cumul[row]) + stored)
-                cands.append((float(total), j, w, stored, row, cnt, float(plain)))
+                if total > -np.inf:                                    # (a NaN is not ranked either)
+                    cands.append((float(total), j, w, stored, row, cnt, float(plain), c if fin else w))
         by_plain = sorted(cands, key=lambda x: (-x[6], x[1], x[2]))[:kg]
         if any(x[5] > 0 for x in by_plain):
             ev["same_word_wanted"] = True
-        left = sorted(cands, key=lambda x: (-x[0], x[1], x[2]))
+        left = sorted(cands, key=lambda x: (-x[0], x[1], x[7]))
         for r in range(kg):
+            q = g * kg + r
+            if not left:
+                assert eos is not None, "fewer finite totals than beams: the EMPTY row needs eos"
+                parent[q], word[q], lp[q], grow[q] = q, eos, F(-np.inf), 0
+                continue
             best = left[0]
             tied = [x for x in left[1:] if x[0] == best[0]]
             if any(x[1] != best[1] for x in tied):
@@ -70,7 +81,6 @@ def select_image(cv, ci, cumul, has_eos, t: int, G: int, kg: int, lam: float):
             if any(x[1] == best[1] and (x[5] > 0 or best[5] > 0) for x in tied):
                 ev["tie_within_beam_after_penalty"] = True
             left = left[1:]
-            q = g * kg + r
             fin = t > 0 and bool(has_eos[best[4]])
             parent[q], word[q], lp[q], grow[q] = best[4], best[2], best[3], 0 if fin else 1
         for q in range(g * kg, g * kg + kg):
@@ -95,7 +105,7 @@ def step(st: dict, cand_val, cand_idx, G: int, kg: int, lam: float, eos: int, em
         rows = slice(b * R, (b + 1) * R)
         if select is None:
             parent, word, lp, grow, ev = select_image(np.asarray(cand_val)[rows], np.asarray(cand_idx)[rows],
-                                                      st["cumul"][rows], st["has_eos"][rows], t, G, kg, lam)
+                                                      st["cumul"][rows], st["has_eos"][rows], t, G, kg, lam, eos)
         else:
             parent, word, lp = select(np.asarray(cand_val)[rows], np.asarray(cand_idx)[rows], st["cumul"][rows],
                                       st["has_eos"][rows], t)
