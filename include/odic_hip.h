@@ -69,7 +69,7 @@ extern "C" {
  *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
  *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
- *       odic_lcs_pairs. */
+ *       odic_lcs_pairs, odic_orient_rgb8. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -257,6 +257,32 @@ int odic_resize_boxes_normalize(const odic_resize_job* jobs, int32_t n_jobs, con
                                 const int32_t* bounds_pool, const int32_t* coef_pool, uint8_t* tmp, size_t tmp_bytes,
                                 float* dst, int32_t out_size, int32_t max_rows, const float* mean3, const float* std3,
                                 void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * EXIF orientation (tag 0x0112) applied to packed RGB8 images on the device: one job per image, a pure permutation of
+ * its pixels, bit for bit Pillow's Image.transpose with the method ImageOps.exif_transpose picks:
+ *     2 FLIP_LEFT_RIGHT   3 ROTATE_180   4 FLIP_TOP_BOTTOM   5 TRANSPOSE   6 ROTATE_270   7 TRANSVERSE   8 ROTATE_90
+ *   src_off            byte offset of the source image (its pixel (0, 0)) from src_base; any value, odd ones included
+ *   dst_off            byte offset of the output image from dst_base; any value
+ *   src_stride_bytes   bytes from one source row to the next (>= 3 W); any value, odd ones included
+ *   H, W               size of the SOURCE image
+ *   orientation        2..8
+ * The output rows are packed: H rows of 3·W bytes for orientations 2..4, W rows of 3·H bytes for 5..8; exactly those
+ * 3·H·W bytes from dst_off on are written (test_orient_kernel_gpu.py).  Source and destination must NOT overlap, within a
+ * job or between jobs: tiles are read and written in no particular order.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct odic_orient_job {
+  int64_t src_off, dst_off, src_stride_bytes;
+  int32_t H, W, orientation;
+} odic_orient_job;
+
+/* jobs is a HOST pointer (the records are checked here and travel as kernel arguments); src_base and dst_base are DEVICE
+ * pointers.  One launch per 64 jobs, on `stream`, no allocation, no host synchronisation, capturable: the grid walks
+ * the 64 x 64 pixel tiles of all jobs of the launch.  n_jobs == 0 succeeds and launches nothing.  ODIC_EINVAL, before any
+ * launch and with nothing written: n_jobs < 0; jobs, src_base or dst_base NULL while n_jobs > 0; a job with an orientation
+ * outside 2..8, H <= 0, W <= 0, src_stride_bytes < 3·W, or more than 2^31 - 1 tiles. */
+int odic_orient_rgb8(const odic_orient_job* jobs, int32_t n_jobs, const uint8_t* src_base, uint8_t* dst_base,
+                     void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched JPEG decode on the device, baseline files here and progressive ones below (utils/image_utils.py:7, PIL_Image.open), bit-exact with

@@ -106,6 +106,7 @@ _SIGNATURES = {
                                                  C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
     "odic_resize_boxes_normalize": (C.c_int, [_P, _I32, _P, _P, _P, _P, C.c_size_t, _P, _I32, _I32,
                                               C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
+    "odic_orient_rgb8": (C.c_int, [_P, _I32, _P, _P, _P]),
     "odic_window_attention": (C.c_int, [_P, _P, _P, _P] + [_I32] * 6 + [_F, _I32, _P]),
     "odic_swin_qkv_attention": (C.c_int, [_P, _I64, _P, _P, _P, _P] + [_I32] * 6 + [_F, _F, _P]),
     "odic_swin_qkv_attention_tiled": (C.c_int, [_P] * 5 + [_I32] * 6 + [_F, _P]),

@@ -41,7 +41,8 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # exceptions are those of the host path.  With a draft request (`draft=`) the files are decoded at 1/2, 1/4 or 1/8 scale
 # in the DCT domain, as `PIL.Image.draft` does, on either path and bit-exact between them.  Non-RGB files are a black
 # canvas as in the reference, or with `non_rgb="convert"` what `convert("RGB")` makes of them: grayscale JPEGs on the
-# device, the other modes by PIL.
+# device, the other modes by PIL.  With `orientation="exif"` every image is turned upright as `ImageOps.exif_transpose`
+# does: device-decoded files by one odic_orient_rgb8 launch (csrc/orient.hip), PIL-decoded ones by PIL.
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -91,6 +92,9 @@ RESIZE_JOB_DTYPE = np.dtype([("src_off", "<i8"), ("src_pitch", "<i8"), ("tmp_off
                              ("row_first", "<i4"), ("n_rows", "<i4"), ("bounds_x", "<i4"), ("coef_x", "<i4"),
                              ("bounds_y", "<i4"), ("coef_y", "<i4"), ("ksize_x", "<i4"), ("ksize_y", "<i4")])
 MAX_RESIZE_JOBS = 65535                                       # one grid z index per job
+#: odic_orient_job (include/odic_hip.h), field for field; the C struct's trailing padding included
+ORIENT_JOB_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("src_stride_bytes", "<i8"), ("H", "<i4"),
+                             ("W", "<i4"), ("orientation", "<i4")], align=True)
 
 
 def pack_resize_jobs(jobs, out_size: int):
@@ -170,6 +174,7 @@ class DevicePreprocessor:
         self._jpeg_pinned = self._jpeg_dev = self._jpeg_ws = self._jpeg_status = None
         self._jpeg_tmp = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._jpeg_routes, self._jpeg_prog_coef = [], None
+        self._jpeg_orientations = []
         # region resize: grow-only gather buffer for images that do not share one storage, and the horizontal pass's rows
         self._region_src = self._region_tmp = None
         self._mean = (ctypes.c_float * 3)(*_MEAN)
@@ -223,7 +228,7 @@ class DevicePreprocessor:
         return out
 
     def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None,
-                   non_rgb: str = "black") -> torch.Tensor:
+                   non_rgb: str = "black", orientation: str = "ignore") -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
         the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
         non_rgb="convert": a file of any other mode (L, LA, P, RGBA, I;16, CMYK, ...) is read as
@@ -234,18 +239,24 @@ class DevicePreprocessor:
         both values of `decode`.
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` instead
         of the whole-image batch, for either value of `decode` (torch.equal between them); with draft=True the boxes
-        are in the coordinates of the drafted image."""
-        from .jpeg import check_non_rgb
+        are in the coordinates of the drafted image.
+        orientation="exif": every file, of any format, is turned upright by its EXIF Orientation tag as
+        `ImageOps.exif_transpose` does, after the draft and the non-RGB rule (the black canvas has the transposed size),
+        for either value of `decode` (torch.equal between them); region boxes are in oriented coordinates.  The default
+        "ignore" reads the stored pixel grid, as the reference does."""
+        from .jpeg import check_non_rgb, check_orientation
         check_non_rgb(non_rgb)
+        check_orientation(orientation)
+        exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's calls stay as they are
         if decode == "device":
             blobs = []
             for p in paths:
                 with open(p, "rb") as f:
                     blobs.append(f.read())
-            return self.from_jpeg_bytes(blobs, draft=draft, regions=regions, non_rgb=non_rgb)
+            return self.from_jpeg_bytes(blobs, draft=draft, regions=regions, non_rgb=non_rgb, **exif)
         if decode != "host":
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
-        arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None, non_rgb) for p in paths]
+        arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None, non_rgb, **exif) for p in paths]
         if regions is None:
             return self(arrays)
         for a in arrays:
@@ -253,22 +264,31 @@ class DevicePreprocessor:
         return self.resize_regions([torch.from_numpy(a.copy()).to(self.device) for a in arrays], regions)
 
     @staticmethod
-    def _pil_rgb(pil, draft=None, non_rgb="black") -> np.ndarray:
+    def _pil_rgb(pil, draft=None, non_rgb="black", orientation="ignore") -> np.ndarray:
         """The host decode of one opened file: the draft request if there is one, then for non-RGB modes a black canvas
-        (of the size the draft left) or, with non_rgb="convert", PIL's `convert("RGB")` → uint8 (H,W,3) array."""
+        (of the size the draft left) or, with non_rgb="convert", PIL's `convert("RGB")`, then with orientation="exif"
+        the transposition `ImageOps.exif_transpose` picks for the file → uint8 (H,W,3) array."""
         if draft is not None:
             pil.draft("RGB", draft)
+        turn = 1
+        if orientation != "ignore":
+            from .jpeg import pil_orientation
+            turn = pil_orientation(pil)                                  # of the file: a converted image may lose its tag
         if pil.mode != "RGB":
             pil = pil.convert("RGB") if non_rgb == "convert" else Image.new("RGB", pil.size)
+        if turn != 1:
+            from .jpeg import transpose_method
+            pil = pil.transpose(transpose_method(turn))
         return np.asarray(pil, dtype=np.uint8)
 
     # ---------------------------------------------------------------------------------------------------------
     # device JPEG decode
     # ---------------------------------------------------------------------------------------------------------
-    def _host_rgb(self, blob, draft=None, non_rgb="black") -> np.ndarray:
+    def _host_rgb(self, blob, draft=None, non_rgb="black", orientation="ignore") -> np.ndarray:
         """The host path for one file: PIL decode, after `im.draft("RGB", draft)` if there is a draft request (black
-        canvas for non-RGB modes, of the drafted size, or their `convert("RGB")`) → uint8 (H,W,3) array."""
-        return self._pil_rgb(Image.open(io.BytesIO(blob)), draft, non_rgb)
+        canvas for non-RGB modes, of the drafted size, or their `convert("RGB")`), turned upright with
+        orientation="exif" → uint8 (H,W,3) array."""
+        return self._pil_rgb(Image.open(io.BytesIO(blob)), draft, non_rgb, orientation)
 
     @staticmethod
     def _grow(buf, nbytes, **kw):
@@ -291,8 +311,14 @@ class DevicePreprocessor:
         take), "host-after-status" (the device reported status 1 and PIL decoded the file again) or "black"."""
         return tuple(self._jpeg_routes)
 
+    @property
+    def last_orientations(self):
+        """The EXIF orientation applied to each file of the last `decode_jpeg` / `from_jpeg_bytes` call, in input order:
+        2..8, or 1 for none (no tag, a value Pillow does not transpose by, or orientation="ignore")."""
+        return tuple(self._jpeg_orientations)
+
     def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host",
-                    draft=None, non_rgb: str = "black"):
+                    draft=None, non_rgb: str = "black", orientation: str = "ignore"):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
         np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path; with
         non_rgb="convert" each equals np.asarray(PIL.Image.open(f).convert("RGB")) instead: one-component JPEGs take the
@@ -305,11 +331,17 @@ class DevicePreprocessor:
         draft=(width, height): every file is decoded as after `im.draft("RGB", draft)`, at 1/2, 1/4 or 1/8 of its size
         while both sides stay at least the requested ones (`jpeg.draft_scale`), by odic_jpeg_decode_scaled /
         odic_jpeg_decode_progressive_scaled or by PIL with the same request; sizes, black canvases and the size check
-        are those of the drafted image."""
+        are those of the drafted image.
+        orientation="exif": every image is returned upright, equal to `np.asarray(ImageOps.exif_transpose(im))` of the
+        image the rules above describe (after the draft and the non-RGB rule: a black canvas has the transposed size),
+        in the oriented shape.  Files decoded on the device are permuted there by one odic_orient_rgb8 launch into one
+        new buffer, files PIL decodes by PIL; the routes are the same as without it.  `last_orientations` reports the
+        value applied to each file (`jpeg.exif_orientation`)."""
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
         J.check_non_rgb(non_rgb)
+        J.check_orientation(orientation)
         opt = () if non_rgb == "black" else (non_rgb,)                   # the default's calls stay as they are
         if draft is not None:
             draft = (int(draft[0]), int(draft[1]))
@@ -317,6 +349,9 @@ class DevicePreprocessor:
                 raise ValueError(f"draft wants a positive (width, height), not {draft!r}")
         blobs = [bytes(b) for b in blobs]
         hdrs = [J.parse(b, *opt) for b in blobs]
+        exif = orientation != "ignore"
+        turns = [J.header_orientation(h, b) if exif else 1 for h, b in zip(hdrs, blobs)]
+        host_kw = {"orientation": orientation} if exif else {}           # the default's calls stay as they are
         if progressive == "device":
             for i, h in enumerate(hdrs):
                 if h.kind == J.HOST and h.reason == "SOF2":
@@ -340,25 +375,52 @@ class DevicePreprocessor:
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
                                                            [hdrs[i] for i in prog], [blobs[i] for i in prog],
                                                            subseq_bits, max_sync_passes, [scales[i] for i in order])
+            turned = []                                                  # (image, its offset in rgb): to be permuted
             for k, i in enumerate(order):
-                if status[k] == 0:
+                if status[k] != 0:
+                    routes[i] = "host-after-status"
+                elif turns[i] != 1:
+                    turned.append((i, out_offs[k]))
+                else:
                     w, h = sizes[i]
                     out[i] = rgb[out_offs[k]:out_offs[k] + w * h * 3].view(h, w, 3)
-                else:
-                    routes[i] = "host-after-status"
-        self._jpeg_routes = routes
+            if turned:
+                self._orient_on_device(rgb, turned, sizes, turns, out)
+        self._jpeg_routes, self._jpeg_orientations = routes, turns
         for i, h in enumerate(hdrs):                                     # input order, as the host path
             if h.kind != J.BLACK and out[i] is None:
-                out[i] = self._host_rgb(blobs[i], draft, *opt)
+                out[i] = self._host_rgb(blobs[i], draft, *opt, **host_kw)
         for i, h in enumerate(hdrs):
             if h.kind == J.BLACK:
-                self._check_size(sizes[i][1], sizes[i][0])
-                out[i] = torch.zeros(sizes[i][1], sizes[i][0], 3, dtype=torch.uint8, device=self.device)
+                w, hh = J.oriented_size(sizes[i], turns[i])
+                self._check_size(hh, w)
+                out[i] = torch.zeros(hh, w, 3, dtype=torch.uint8, device=self.device)
             else:
                 self._check_size(out[i].shape[0], out[i].shape[1])
                 if isinstance(out[i], np.ndarray):
                     out[i] = torch.from_numpy(out[i].copy()).to(self.device)
         return out
+
+    def _orient_on_device(self, rgb, turned, sizes, turns, out) -> None:
+        """One odic_orient_rgb8 call on self.stream, behind the decode launches: the images `turned` [(index, byte offset
+        in rgb)] of (width, height) sizes[index], from the shared decode buffer into one new buffer, 256-aligned slots;
+        out[index] becomes the oriented (H,W,3) view."""
+        from .jpeg import oriented_size
+        rec = np.zeros(len(turned), ORIENT_JOB_DTYPE)
+        pos = 0
+        for r, (i, off) in zip(rec, turned):
+            w, h = sizes[i]
+            r["src_off"], r["dst_off"], r["src_stride_bytes"] = off, pos, 3 * w
+            r["H"], r["W"], r["orientation"] = h, w, turns[i]
+            pos += _pad256(w * h * 3)
+        dst = torch.empty(pos, dtype=torch.uint8, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream())
+        self._hip.check(self.lib.odic_orient_rgb8(rec.ctypes.data, len(rec), rgb.data_ptr(), dst.data_ptr(),
+                                                  self.stream.cuda_stream), "odic_orient_rgb8")
+        torch.cuda.current_stream().wait_stream(self.stream)
+        for r, (i, _) in zip(rec, turned):
+            w, h = oriented_size(sizes[i], turns[i])
+            out[i] = dst[int(r["dst_off"]):int(r["dst_off"]) + w * h * 3].view(h, w, 3)
 
     def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales):
         """One odic_jpeg_decode call for the baseline files and one odic_jpeg_decode_progressive call for the progressive
@@ -427,14 +489,16 @@ class DevicePreprocessor:
 
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
                         progressive: str = "host", draft: bool = False, regions=None,
-                        non_rgb: str = "black") -> torch.Tensor:
+                        non_rgb: str = "black", orientation: str = "ignore") -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
         torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`,
-        and the same `non_rgb`).
+        the same `non_rgb` and the same `orientation`).
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` on the
-        decoded images instead; with draft=True the boxes are in the coordinates of the drafted image."""
+        decoded images instead; with draft=True the boxes are in the coordinates of the drafted image, with
+        orientation="exif" in those of the upright one."""
+        exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's call stays as it is
         imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
-                                draft=(self.S, self.S) if draft else None, non_rgb=non_rgb)
+                                draft=(self.S, self.S) if draft else None, non_rgb=non_rgb, **exif)
         if regions is not None:
             return self.resize_regions(imgs, regions)
         S = self.S

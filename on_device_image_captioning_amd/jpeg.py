@@ -86,6 +86,8 @@ class JpegHeader:
     restart_interval: int = 0                            # DRI value (0: none)
     data_offset: int = 0                                 # first byte of the entropy-coded data
     reason: str = ""
+    app1: list = field(default=None, compare=False, repr=False)     # APP1 payloads ahead of the first SOS, where the
+                                                                     # walk got that far (`header_orientation`)
 
     @property
     def mcus_x(self):
@@ -172,6 +174,7 @@ class _Walker:
         self.dri, self.sof = 0, None                  # sof: (marker, precision, height, width, nc, [(id, h, v, tq)])
         self.jfif = self.adobe = False
         self.adobe_transform = None
+        self.app1 = []                                # payload of every APP1 ahead of the first SOS (`exif_orientation`)
 
     def scans(self, script):
         """Generator of the payload of every SOS segment, self.i behind it.  script=False (`parse`): the caller
@@ -206,10 +209,13 @@ class _Walker:
                     raise _Bad("bad DRI")
                 self.dri = (s[0] << 8) | s[1]
             elif 0xE0 <= m <= 0xEF or m == 0xFE:      # APPn / COM: skipped, but for libjpeg's two colour-space latches
+                                                      # and the APP1 payloads, kept for `exif_orientation`
                 if before and m == 0xE0 and len(s) >= 14 and s[:5] == b"JFIF\x00":        # APP0_DATA_LEN
                     self.jfif = True
                 elif before and m == 0xEE and len(s) >= 12 and s[:5] == b"Adobe":         # APP14_DATA_LEN
                     self.adobe, self.adobe_transform = True, s[11]
+                elif before and m == 0xE1:
+                    self.app1.append(s)
             elif m == 0xDA:
                 before, self.i = False, i
                 yield s
@@ -285,6 +291,7 @@ def _parse(b, non_rgb="black") -> JpegHeader:
     w = _Walker(b)
     s = next(w.scans(script=False))                   # the first SOS; whatever keeps the walk from it raises
     hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False, non_rgb=non_rgb)
+    hd.app1 = w.app1
     if hd.kind != DEVICE:
         return hd
     # SOS: one baseline scan of all the frame's components (three interleaved, or the one of a gray frame), in frame order
@@ -308,6 +315,150 @@ def _parse(b, non_rgb="black") -> JpegHeader:
         raise _Bad("scan longer than the device decoder's bit positions allow")
     hd.restart_interval, hd.data_offset = w.dri, w.i
     return hd
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# EXIF orientation (tag 0x0112): what `ImageOps.exif_transpose` would do to the file.  The rule of this file applies:
+# own code reads the plain form only — exactly one `Exif\0\0` APP1 ahead of the first SOS, a TIFF header `II` / `MM`
+# with magic 42, IFD0 walked to its end, one entry 0x0112 of type SHORT or LONG with count 1 — and everything else
+# (several Exif APP1s, which Pillow concatenates; another entry type or count; an Exif block that cannot be walked; no
+# Orientation in Exif but an XMP packet that names tiff:Orientation; a file the walker turns away) is Pillow's to
+# decide: `Image.open(...).getexif().get(0x0112)` reads headers and decodes no pixels.  Asking Pillow changes where the
+# number comes from, never the decode route.
+# ---------------------------------------------------------------------------------------------------------------
+ORIENTATIONS = ("ignore", "exif")
+_EXIF, _XMP = b"Exif\x00\x00", b"http://ns.adobe.com/xap/1.0/\x00"
+#: orientation → (mirror x, mirror y, swap the axes): source pixel (y, x) of an H x W image lands at (u, v) with
+#: u = H-1-y if mirror y else y and v = W-1-x if mirror x else x, or at (v, u) when the axes swap (csrc/orient.hip)
+ORIENT_OPS = {1: (False, False, False), 2: (True, False, False), 3: (True, True, False), 4: (False, True, False),
+              5: (False, False, True), 6: (False, True, True), 7: (True, True, True), 8: (True, False, True)}
+
+
+def check_orientation(orientation):
+    if orientation not in ORIENTATIONS:
+        raise ValueError(f"orientation must be 'ignore' or 'exif', not {orientation!r}")
+    return orientation
+
+
+def transpose_method(orientation: int):
+    """The `Image.Transpose` method `ImageOps.exif_transpose` applies for an orientation 2..8."""
+    from PIL import Image
+    t = Image.Transpose
+    return {2: t.FLIP_LEFT_RIGHT, 3: t.ROTATE_180, 4: t.FLIP_TOP_BOTTOM, 5: t.TRANSPOSE, 6: t.ROTATE_270,
+            7: t.TRANSVERSE, 8: t.ROTATE_90}[orientation]
+
+
+def effective_orientation(tag) -> int:
+    """Pillow's tag value → the orientation `exif_transpose` acts on: an int 2..8, else 1 (absent, 0, 9, the ASCII
+    "6" and the BYTE b"\x06" that Pillow reports but does not transpose by)."""
+    return tag if isinstance(tag, int) and not isinstance(tag, bool) and 2 <= tag <= 8 else 1
+
+
+def pil_orientation(im) -> int:
+    """The effective orientation of an opened PIL image, any format."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return effective_orientation(im.getexif().get(0x0112))
+
+
+def _plain_orientation(app1):
+    """The APP1 payloads ahead of the first SOS → the raw tag value of the plain form (1: no tag anywhere), or None:
+    ask Pillow."""
+    import struct
+    exif = [s for s in app1 if s.startswith(_EXIF)]
+    xmp = any(s.startswith(_XMP) and b"tiff:Orientation" in s for s in app1)
+    if len(exif) > 1:
+        return None
+    if exif:
+        t = exif[0][6:]
+        if t[:4] == b"II\x2a\x00":
+            e = "<"
+        elif t[:4] == b"MM\x00\x2a":
+            e = ">"
+        else:
+            return None
+        if len(t) < 8:
+            return None
+        off = struct.unpack_from(e + "I", t, 4)[0]
+        if off + 2 > len(t):
+            return None
+        n = struct.unpack_from(e + "H", t, off)[0]
+        if off + 2 + 12 * n + 4 > len(t):             # the entries and the offset of the next IFD behind them
+            return None
+        found = []
+        for k in range(n):
+            tag, typ, cnt = struct.unpack_from(e + "HHI", t, off + 2 + 12 * k)
+            if tag == 0x0112:
+                if typ not in (3, 4) or cnt != 1:
+                    return None
+                found.append(struct.unpack_from(e + ("H" if typ == 3 else "I"), t, off + 2 + 12 * k + 8)[0])
+        if len(found) > 1:
+            return None
+        if found:
+            return found[0]
+    return None if xmp else 1
+
+
+def exif_orientation(blob) -> int:
+    """The orientation 1..8 `ImageOps.exif_transpose(Image.open(f))` acts on: 1 wherever Pillow does not transpose
+    (no tag, a value outside 2..8, a tag Pillow reads as something other than an int, a file Pillow cannot open).
+    Looks at the segments ahead of the first SOS only, as Pillow's `_open` does; never raises on a file's content."""
+    b = blob if isinstance(blob, bytes) else bytes(blob)
+    try:
+        w = _Walker(b)
+        next(w.scans(script=False))
+        tag = _plain_orientation(w.app1)
+    except (_Bad, IndexError, ValueError, StopIteration):
+        tag = None
+    return _pillow_orientation(b) if tag is None else effective_orientation(tag)
+
+
+def _pillow_orientation(b) -> int:
+    import io
+    import warnings
+    from PIL import Image
+    try:
+        with warnings.catch_warnings():                  # a corrupt Exif block: Pillow warns and reports no tag
+            warnings.simplefilter("ignore")
+            with Image.open(io.BytesIO(b)) as im:
+                return pil_orientation(im)
+    except Exception:                                    # not an image Pillow opens: the decode route says so
+        return 1
+
+
+def header_orientation(hd, blob) -> int:
+    """`exif_orientation(blob)` for a file `parse` / `parse_progressive` has walked already: from the APP1 payloads the
+    header kept, without a second walk; a header without them (the walk ended early) reads the file."""
+    if hd.app1 is None:
+        return exif_orientation(blob)
+    tag = _plain_orientation(hd.app1)
+    return _pillow_orientation(blob) if tag is None else effective_orientation(tag)
+
+
+def oriented_size(size, orientation: int):
+    """(width, height) of an image of `size` after the orientation is applied."""
+    return (size[1], size[0]) if ORIENT_OPS[orientation][2] else (size[0], size[1])
+
+
+def orient_box(box, size, orientation: int, inverse: bool = False):
+    """An (l, t, r, b) box between the stored pixel grid and the oriented one.  size: (width, height) of the image AS
+    STORED, for both directions.  inverse=False: a box on the stored grid → the same pixels on the oriented grid;
+    inverse=True: a box on the oriented grid (e.g. `grounding.source_box` of an image decoded with
+    orientation="exif") → the box on the file as stored."""
+    if orientation not in ORIENT_OPS:
+        raise ValueError(f"orientation must lie in 1..8, not {orientation!r}")
+    fx, fy, swap = ORIENT_OPS[orientation]
+    W, H = size
+    l, t, r, b = box
+    if not inverse:
+        v0, v1 = (W - r, W - l) if fx else (l, r)
+        u0, u1 = (H - b, H - t) if fy else (t, b)
+        return (u0, v0, u1, v1) if swap else (v0, u0, v1, u1)
+    (u0, u1), (v0, v1) = ((l, r), (t, b)) if swap else ((t, b), (l, r))
+    x0, x1 = (W - v1, W - v0) if fx else (v0, v1)
+    y0, y1 = (H - u1, H - u0) if fy else (u0, u1)
+    return (x0, y0, x1, y1)
 
 
 _TABLE_CACHE: dict = {}
@@ -516,6 +667,7 @@ def _parse_progressive(b, non_rgb="black") -> ProgHeader:
     for s in w.scans(script=True):                 # coefficient, -1: not yet sent (lists)
         if hd is None:
             hd = _frame(w, ProgHeader, (0xC2,), distinct_ids=True, non_rgb=non_rgb)
+            hd.app1 = w.app1
             if hd.kind != DEVICE:
                 return hd
             coef_bits = [[-1] * 64 for _ in range(hd.ncomp)]

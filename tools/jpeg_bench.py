@@ -30,6 +30,15 @@ kernel), in which the scaled kernels carry their own names; profiles/r11_jpeg_dr
     python tools/jpeg_bench.py --draft --iters 15 --warmup 3 --out profiles/r11_jpeg_draft_bench.json
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/jpeg_bench.py --draft --device-only --draft-cases large \
         --iters 4 --warmup 1
+
+--orient: EXIF orientation.  First odic_orient_rgb8 alone, device events around a run of launches, for
+each of the seven orientations at 4032x3024 and 640x480 (one image, and the batch of 16 the end-to-end case launches),
+next to `torch.Tensor.copy_` of the same bytes between two uint8 device buffers: the copy moves each byte once in and
+once out, as the kernel does.  Then a batch of 16 640x480 files tagged orientation 6, three ways, alternating:
+`from_files(decode="host", orientation="exif")`, `from_jpeg_bytes(orientation="exif")` and
+`from_jpeg_bytes()` (orientation ignored) on the same files.
+
+    python tools/jpeg_bench.py --orient --iters 20 --out profiles/r22_jpeg_orient_bench.json
 """
 from __future__ import annotations
 
@@ -148,6 +157,112 @@ def draft_bench(args):
                 f.write(json.dumps(line) + "\n")
 
 
+def with_orientation(blob: bytes, orientation: int) -> bytes:
+    """The file with an Exif APP1 that holds the Orientation tag alone, behind its JFIF APP0."""
+    from PIL import Image
+    exif = Image.Exif()
+    exif[0x0112] = orientation
+    payload = exif.tobytes()
+    pos = 2
+    if blob[2:4] == b"\xff\xe0":
+        pos = 4 + int.from_bytes(blob[4:6], "big")
+    return blob[:pos] + b"\xff\xe1" + (len(payload) + 2).to_bytes(2, "big") + payload + blob[pos:]
+
+
+def _quartiles(ts):
+    q1, med, q3 = (float(x) for x in np.percentile(ts, [25, 50, 75]))
+    return {"median": med, "q1": q1, "q3": q3, "min": float(min(ts))}
+
+
+def orient_bench(args):
+    """The orient launch against a device-to-device copy, then orientation="exif" end to end."""
+    import tempfile
+    import torch
+    from on_device_image_captioning_amd import _hip
+    from on_device_image_captioning_amd.image_utils import ORIENT_JOB_DTYPE, DevicePreprocessor
+    assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
+    lib = _hip.load()
+    lines = []
+
+    def event_us(fn, reps):
+        """Median / quartiles / min of the time per call over args.iters windows of `reps` calls each."""
+        for _ in range(args.warmup * reps):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(args.iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            ts.append(1e3 * a.elapsed_time(b) / reps)
+        return _quartiles(ts)
+
+    for (W, H), n, reps in (((4032, 3024), 1, 50), ((640, 480), 1, 500), ((640, 480), 16, 200)):
+        nbytes = 3 * W * H
+        slot = (nbytes + 255) // 256 * 256
+        src = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device="cuda:0")
+        dst = torch.empty_like(src)
+        stream = torch.cuda.current_stream().cuda_stream
+        line = {"kernel": "odic_orient_rgb8", "width": W, "height": H, "images": n, "bytes_each_way": n * nbytes,
+                "launches_per_window": reps, "iters": args.iters, "gpu": torch.cuda.get_device_name(0)}
+        copy = event_us(lambda: dst.copy_(src), reps)
+        line["copy_us"] = copy
+        for o in range(2, 9):
+            rec = np.zeros(n, ORIENT_JOB_DTYPE)
+            rec["src_off"] = rec["dst_off"] = np.arange(n) * slot
+            rec["src_stride_bytes"], rec["H"], rec["W"], rec["orientation"] = 3 * W, H, W, o
+            t = event_us(lambda: _hip.check(lib.odic_orient_rgb8(rec.ctypes.data, n, src.data_ptr(), dst.data_ptr(),
+                                                                 stream), "odic_orient_rgb8"), reps)
+            line[f"orient_{o}_us"] = t
+            line[f"orient_{o}_over_copy"] = t["median"] / copy["median"]
+            line[f"orient_{o}_GBps"] = 2 * n * nbytes / t["median"] / 1e3
+        line["copy_GBps"] = 2 * n * nbytes / copy["median"] / 1e3
+        line["copy_again_us"] = event_us(lambda: dst.copy_(src), reps)       # the spread of the yardstick itself
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+
+    pre = DevicePreprocessor(args.size, "cuda:0")
+    B = 16
+    blobs = [with_orientation(b, 6) for b in make_inputs(B)]
+    with tempfile.TemporaryDirectory() as d:
+        paths = []
+        for k, b in enumerate(blobs):
+            paths.append(os.path.join(d, f"{k}.jpg"))
+            with open(paths[-1], "wb") as f:
+                f.write(b)
+        fns = {"host_exif": lambda: pre.from_files(paths, decode="host", orientation="exif"),
+               "device_exif": lambda: pre.from_jpeg_bytes(blobs, orientation="exif"),
+               "device_ignore": lambda: pre.from_jpeg_bytes(blobs)}
+        assert torch.equal(fns["host_exif"](), fns["device_exif"]()), "host and device paths differ"
+        assert pre.last_routes == ("device",) * B and pre.last_orientations == (6,) * B
+        for _ in range(args.warmup):
+            for fn in fns.values():
+                fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in fns}
+        for _ in range(args.iters):
+            for name, fn in fns.items():
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                t[name].append(1e3 * (time.perf_counter() - t0))
+    line = {"end_to_end": "16 files 640x480 q90 4:2:0, orientation 6", "iters": args.iters, "size": args.size,
+            "gpu": torch.cuda.get_device_name(0)}
+    for k, v in t.items():
+        line[f"{k}_ms"] = _quartiles(v)
+    line["host_over_device_exif"] = line["host_exif_ms"]["median"] / line["device_exif_ms"]["median"]
+    line["exif_minus_ignore_ms"] = _quartiles([a - b for a, b in zip(t["device_exif"], t["device_ignore"])])
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 64])
@@ -160,10 +275,13 @@ def main():
     ap.add_argument("--gray", action="store_true", help="the crops as one-component files, non_rgb='convert'")
     ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
     ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
+    ap.add_argument("--orient", action="store_true", help="odic_orient_rgb8 against a copy; orientation='exif' end to end")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.draft:
         return draft_bench(args)
+    if args.orient:
+        return orient_bench(args)
 
     import torch
     from PIL import Image
