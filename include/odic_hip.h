@@ -600,7 +600,10 @@ int odic_dynexp_step(const float* lin, int64_t ldlin, const float* qexp, const f
  *   tokens int64 [N, T] compact; embed fp32 [vocab, d]; pos_table fp32 [pos_rows, d]; T <= pos_rows (ODIC_EINVAL otherwise,
  *   checked on the host).  A token outside [0, vocab) embeds as the zero vector: nothing is read out of bounds.
  *   row_valid (optional, with dec_len int32 [N]): int32 [N·T] receives 1 where t < dec_len[n], else 0 — the row mask
- *   odic_cross_attn_step takes.  y columns [d, ldy) are left untouched; row_valid is compact. */
+ *   odic_cross_attn_step takes.  y columns [d, ldy) are left untouched; row_valid is compact.
+ *   Any int64 is a legal token: an id outside the table (vocab, -1, INT64_MIN, 2^40) is compared before an address is
+ *   formed and gives exactly pos_table[t] (embed row 0 is read in its place and multiplied by 0); dec_len[n] <= 0 marks no row, >= T every row; without row_valid nothing is
+ *   written but y.  ldy < d or N·T > 2^31 - 1: ODIC_EINVAL; row_valid without dec_len: ODIC_ENULL; nothing is written. */
 int odic_dec_embed_seq(const int64_t* tokens, const float* embed, const float* pos_table, const int32_t* dec_len,
                        int32_t* row_valid, float* y, int64_t ldy, int32_t N, int32_t T, int32_t d, int32_t vocab,
                        int32_t pos_rows, float scale, void* stream);
@@ -633,7 +636,17 @@ int odic_dynexp_seq(const float* lin, int64_t ldlin, const float* qexp, const fl
  * Log-probs are formed as (x − max) − log Σ exp(x − max), as torch forms them: the error does not grow with |logsumexp|
  * (odic_logsoftmax_topk's does).  A masked word (logit -inf) has log-prob exactly -inf, as a target too; a row with one
  * has sum_logp exactly -inf; argmax / max_logp ignore it.  A row without a finite logit, or with a NaN, is outside the
- * contract. */
+ * contract.  What such a row gets today (tests/token_stats_model.py, pinned by tests/test_token_stats_gpu.py):
+ *   ties       the lowest index of the maximum, wherever in the block the tied words sit (an all-equal row: 0);
+ *   status     only ever OR-ed (4 on entry and a flagged row: 5; no flagged row: unchanged); the flagged row's three
+ *              other outputs are those of an unflagged row;
+ *   +inf, or no finite word (all -inf): logp_target, sum_logp and max_logp are NaN (inf - inf, as torch.log_softmax),
+ *              argmax is the lowest index of the maximum (all -inf: 0);
+ *   a NaN      logp_target, sum_logp and max_logp are NaN; argmax is the arg-max of the other words when the NaN sits at
+ *              an index >= 256, 0 when it sits at index 0, and otherwise that of the words the NaN's lane does not hide
+ *              (it is NOT the NaN's index, which is what torch.argmax would give).
+ *   R <= 0, V <= 0 or ldl < V: ODIC_EINVAL; a NULL logits / sum_logp / argmax / max_logp, or target without logp_target
+ *   and status: ODIC_ENULL; nothing is written either way. */
 int odic_token_stats(const float* logits, int64_t ldl, const int64_t* target, float* logp_target, float* sum_logp,
                      int32_t* argmax, float* max_logp, int32_t* status, int32_t R, int32_t V, void* stream);
 

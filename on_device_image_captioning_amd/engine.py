@@ -768,7 +768,7 @@ class CaptionerEngine:
         pre = f(M, d)
         ops.gemm(ycat, self.dr_w, self.dr_b, residual=ycat[:, (L - 1) * d:], out=pre, tile_cfg=TC)
         ops.layernorm(pre, self.drn_w, self.drn_b, out=xn)
-        rc = int(row_chunk) if row_chunk else self.vocab_row_chunk()
+        rc = int(row_chunk) if row_chunk is not None else self.vocab_row_chunk()      # (0 is an error, not "the default")
         if rc <= 0:
             raise ValueError("row_chunk must be positive")
         if want_logits:

@@ -327,6 +327,54 @@ def test_scoring_invariances_are_exact():
     assert torch.equal(a, b)
 
 
+def test_decode_sequence_row_chunks_score_every_row_from_its_own_logits():
+    """decode_sequence walks the M = N·T rows through the vocabulary product and token_stats `row_chunk` rows at a time,
+    in ONE [rc, V] workspace: a chunking error is a row scored from the previous chunk's logits.  M = 27 is no multiple of
+    7, 26 or 28; ragged dec_len (a padded sequence end inside a chunk); every result has the single-chunk call's bits."""
+    g = W.TINY
+    m = build_model("TINY", "eos")
+    eng = m._captioner_engine()
+    N, T = 3, 9
+    M = N * T
+    img = W.synth_images(N, g).to(DEV)
+    rng = np.random.Generator(np.random.Philox(key=27))
+    dec = torch.from_numpy(rng.integers(4, g.vocab_size, size=(N, T))).long().to(DEV)
+    tgt = torch.from_numpy(rng.integers(0, g.vocab_size, size=(N, T))).long().to(DEV)
+    dec_len = torch.tensor([9, 2, 5], dtype=torch.int32, device=DEV)
+    mem = m.forward_enc(img, [0] * N)
+    kv, enc_len = eng.project_kv(mem), m._enc_lens(N, mem.shape[1], None)
+    run = lambda **kw: eng.decode_sequence(dec, dec_len, kv, enc_len, N, **kw)      # noqa: E731
+    fields = ("logp", "sum_logp", "argmax", "max_logp", "status")
+    base = run(targets=tgt, row_chunk=M)
+    base_lg = run(want_logits=True, row_chunk=M)
+    assert int(base["status"]) == 0 and bool(torch.isfinite(base["logp"]).all()) and bool((base["logp"] < 0).all())
+    assert len(torch.unique(base["sum_logp"])) > M // 2         # rows differ: a row scored from another row's logits shows
+    for rc in (1, 7, M - 1, M, M + 1):
+        got = run(targets=tgt, row_chunk=rc)
+        for f in fields:
+            assert torch.equal(got[f], base[f]), (rc, f)
+        assert torch.equal(run(want_logits=True, row_chunk=rc), base_lg), rc
+    # without targets: the same three statistics, no log-prob
+    got = run(row_chunk=7)
+    assert "logp" not in got and all(torch.equal(got[f], base[f]) for f in fields[1:])
+    for kw in (dict(targets=tgt), dict(want_logits=True)):
+        with pytest.raises(ValueError):
+            run(row_chunk=0, **kw)
+    # one target outside the vocabulary in the LAST row of a middle chunk (rows 7..13 at row_chunk = 7)
+    bad_row = 13
+    tgt2 = tgt.clone()
+    tgt2.view(-1)[bad_row] = g.vocab_size
+    for rc in (7, M):
+        got = run(targets=tgt2, row_chunk=rc)
+        assert int(got["status"]) == 1, rc
+        lp = got["logp"].view(-1)
+        assert float(lp[bad_row]) == 0.0 and int((lp == 0).sum()) == 1                # only that row's log-prob is 0
+        keep = torch.arange(M, device=DEV) != bad_row
+        assert torch.equal(lp[keep], base["logp"].view(-1)[keep])
+        for f in fields[1:4]:
+            assert torch.equal(got[f], base[f]), (rc, f)
+
+
 def test_launch_count_does_not_depend_on_the_length(ops):
     m = build_model("TINY", "eos")
     img = W.synth_images(2, W.TINY).to(DEV)
