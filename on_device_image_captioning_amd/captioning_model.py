@@ -120,6 +120,20 @@ class CaptioningModel(nn.Module):
                                             banned=banned_words, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
                                             sampling=sampling)
 
+    def _check_rows_fit(self, rows: int, what: str = "rows") -> None:
+        """A search of `rows` rows per image takes that many distinct words of a row: ValueError past the vocabulary."""
+        if rows > self._vocab_size():
+            raise ValueError(f"{rows} {what} per image exceed the vocabulary ({self._vocab_size()} words)")
+
+    def _open_search(self, mem, enc_input_num_pads, rows: int, max_seq_len: int):
+        """A search of `rows` rows per image on the encoder memory `mem` → (the engine, the DecodeState still to be
+        armed, steps): positions 0 .. steps-1 are fed, the state holds steps + 1 (a prefix reaches that far)."""
+        eng = self._captioner_engine()
+        B, S, _ = mem.shape
+        steps = max(1, max_seq_len - 1)
+        st = eng.new_state(B, rows, steps + 1, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
+        return eng, st, steps
+
     def _next_sampling_seed(self) -> int:
         """A fresh Philox key per sampling call (so repeated calls differ), reproducible from `sampling_seed`."""
         self._sampling_calls += 1
@@ -326,14 +340,14 @@ class CaptioningModel(nn.Module):
         st = self._sequence_stats(enc_x, enc_x_num_pads, N, dec, dec_len, tgt.masked_fill(ignored, 0))
         loss = _scoring.label_smoothing_loss(st["logp"].cpu(), st["sum_logp"].cpu(), ignored, V, smoothing,
                                              divide_by_non_zeros)
-        return loss.to(enc_x.device) if isinstance(enc_x, torch.Tensor) else loss
+        return _to_input_device(loss, enc_x)
 
     def forward(self, enc_x, dec_x=None, enc_x_num_pads=[0], dec_x_num_pads=[0], apply_log_softmax=False,
                 mode="forward", **kwargs):
         if mode == "forward":
             x = self.forward_enc(enc_x, enc_x_num_pads)
             y = self.forward_dec(x, enc_x_num_pads, dec_x, dec_x_num_pads, apply_log_softmax)
-            return y.to(enc_x.device) if isinstance(enc_x, torch.Tensor) else y
+            return _to_input_device(y, enc_x)
         assert ("sos_idx" in kwargs.keys() or "eos_idx" in kwargs.keys()), \
             "sos and eos must be provided in case of batch sampling or beam search"
         return _search.dispatch(self, mode, kwargs, enc_x, enc_x_num_pads)
@@ -392,7 +406,7 @@ class CaptioningModel(nn.Module):
         width = int(eos_h.max()) + 1
         ar = torch.arange(width, device=dv)[None, :]
         probs = lps[:, :width].masked_fill(ar > where_eos[:, None], 0.0).reshape(bs, num_outputs, -1)
-        return res, probs.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else probs
+        return res, _to_input_device(probs, enc_input)
 
     # ------------------------------------------------------------------ search
     def beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
@@ -433,8 +447,8 @@ class CaptioningModel(nn.Module):
                                          sampling=sampling)
         if required and prefix:
             raise ValueError("required_words together with prefix is not supported")
-        if required and rows_per_image > self._vocab_size():
-            raise ValueError(f"{rows_per_image} rows per image exceed the vocabulary ({self._vocab_size()} words)")
+        if required:
+            self._check_rows_fit(rows_per_image)
         mem = self.forward_enc(enc_input, enc_input_num_pads)
         if required:
             toks, lp = self._required_search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size,
@@ -443,71 +457,51 @@ class CaptioningModel(nn.Module):
             toks, lp = self._search_from_memory(mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
                                                 max_seq_len, sample=sampling, constraints=cons, prefix=prefix,
                                                 sample_filter=flt)
-        return toks, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+        return toks, _to_input_device(lp, enc_input)
 
     def _required_search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, bank_beams, how_many_outputs,
                                      max_seq_len, required: List[List[int]], constraints: Optional[dict]):
         """beam_search with required words (check_required_words' lists): 2^C banks of bank_beams rows per image."""
-        eng = self._captioner_engine()
-        B, S, _ = mem.shape
         R = bank_beams << len(required[0])
-        steps = max(1, max_seq_len - 1)
-        T = steps + 1
-        st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
+        eng, st, steps = self._open_search(mem, enc_input_num_pads, R, max_seq_len)
         req = torch.tensor(required, dtype=torch.int64, device=eng.device)
 
-        def step(cons):
-            eng.require_beam_step(st, eos_idx, req, bank_beams, constraints=cons)
-            if self._cand_log is not None:       # test hook: the candidates and the required words' log-probs per row
-                logp_h, req_h = st.logp.cpu(), req.cpu().repeat_interleave(R, dim=0)
-                req_logp = torch.where(req_h >= 0, logp_h.gather(1, req_h.clamp(min=0)), torch.tensor(float("-inf")))
-                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone(), req_logp))
+        def req_logp():                          # the log: the candidates and the required words' log-probs per row
+            logp_h, req_h = st.logp.cpu(), req.cpu().repeat_interleave(R, dim=0)
+            return torch.where(req_h >= 0, logp_h.gather(1, req_h.clamp(min=0)), torch.tensor(float("-inf")))
 
         def pick(order, score):
             rows, self.last_required_satisfied = _search.required_outputs(
-                order.cpu().tolist(), st.cumul.view(B, R).cpu().tolist(), required, bank_beams, how_many_outputs)
+                order.cpu().tolist(), st.cumul.view(st.n_img, R).cpu().tolist(), required, bank_beams, how_many_outputs)
             return rows
 
-        return _search.run_search(eng, st, eos_idx, steps, how_many_outputs, constraints=constraints, step=step, pick=pick,
-                                  arm=lambda: ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb))
+        step = lambda cons: eng.require_beam_step(st, eos_idx, req, bank_beams, constraints=cons)      # noqa: E731
+        return _search.run_search(eng, st, eos_idx, steps, how_many_outputs, constraints=constraints, pick=pick,
+                                  step=_search.logged(step, st, self._cand_log, req_logp),
+                                  arm=lambda: _search.arm_state(eng, st, sos_idx, emb=st.emb))
 
     def _search_from_memory(self, mem, enc_input_num_pads, sos_idx, eos_idx, beam_size, how_many_outputs,
                             max_seq_len, sample: bool = False, constraints: Optional[dict] = None,
                             prefix: Optional[List[List[int]]] = None, sample_filter=None
                             ) -> Tuple[List[List[List[int]]], torch.Tensor]:
-        eng = self._captioner_engine()
-        B, S, _ = mem.shape
-        k = beam_size
-        steps = max(1, max_seq_len - 1)            # positions 0 .. steps-1 are fed; prefixes reach steps+1
-        T = steps + 1
-        st = eng.new_state(B, k, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
-        P = len(prefix[0]) if prefix else 0
-        V = eng.g.vocab_size
+        eng, st, steps = self._open_search(mem, enc_input_num_pads, beam_size, max_seq_len)
         seed = self._next_sampling_seed() if sample else 0
-
-        def arm():       # start state; for the deterministic search also the embedded start token as the input of position 0
-            if P:                                  # (check_prefix: never with `sample`)
-                eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx)
-            else:
-                ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None if sample else st.emb)
 
         def draw_step(cons):
             # 'sample' variant (captioning_model.py:128-131,166-168): the k candidates of every beam are drawn
             # without replacement from its distribution instead of being its top-k — on the device
             eng.step_logits(st)
-            _search.draw_candidates(st.logits, st.cand_val, st.cand_idx, st.N, V, k, seed, st.pos, sample_filter)
+            _search.draw_candidates(st.logits, st.cand_val, st.cand_idx, st.N, eng.g.vocab_size, beam_size, seed, st.pos,
+                                    sample_filter)
             if self._draw_log is not None:                        # test hook: the draws, for replay in the oracle
                 self._draw_log.append(st.cand_idx.cpu().clone())
             ops.beam_step(st.cand_val, st.cand_idx, st.beam_state, st.n_img, st.beams, st.T, eos_idx)
 
-        def step(cons):
-            eng.beam_step(st, eos_idx, constraints=cons)
-            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
-                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
-
-        # (the log-probs are on the engine's device; beam_search moves them to the input's)
-        return _search.run_search(eng, st, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
-                                  step=draw_step if sample else step)
+        step = _search.logged(lambda cons: eng.beam_step(st, eos_idx, constraints=cons), st, self._cand_log)
+        # (a prefix never comes with `sample`: check_prefix; the log-probs are on the engine's device, beam_search moves them)
+        return _search.run_search(eng, st, eos_idx, steps - (len(prefix[0]) if prefix else 0), how_many_outputs,
+                                  constraints=constraints, step=draw_step if sample else step,
+                                  arm=lambda: _search.arm_state(eng, st, sos_idx, prefix, emb=None if sample else st.emb))
 
     def diverse_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_groups=3, group_size=3,
                             diversity_penalty=0.5, how_many_outputs=None, max_seq_len=20, *, no_repeat_ngram_size=0,
@@ -539,35 +533,19 @@ class CaptioningModel(nn.Module):
                                                    max_seq_len=max_seq_len, rows_per_image=num_groups * group_size)
         prefix = self._search_prefix_arg(prefix, enc_input, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len)
         mem = self.forward_enc(enc_input, enc_input_num_pads)
-        eng = self._captioner_engine()
-        B, S, _ = mem.shape
         G, kg = int(num_groups), int(group_size)
-        R = G * kg
-        if R > eng.g.vocab_size:
-            raise ValueError(f"{R} beams per image exceed the vocabulary ({eng.g.vocab_size} words)")
-        steps = max(1, max_seq_len - 1)
-        T = steps + 1
-        st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
-        P = len(prefix[0]) if prefix else 0
-
-        def arm():
-            if P:
-                eng.seed_prefix(st, _search.prefix_tensor(prefix, eng.device), sos_idx, group_beams=kg)
-            else:
-                ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb)
-
-        def step(cons):
-            eng.group_beam_step(st, eos_idx, G, penalty, constraints=cons)
-            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
-                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
+        self._check_rows_fit(G * kg, "beams")
+        eng, st, steps = self._open_search(mem, enc_input_num_pads, G * kg, max_seq_len)
 
         def pick(order, score):                                   # output j of an image: the best row of group j
-            best = score.view(B, G, kg).cpu().argmax(dim=2)       # (first maximum: ties go to the lower row)
+            best = score.view(st.n_img, G, kg).cpu().argmax(dim=2)     # (first maximum: ties go to the lower row)
             return (torch.arange(G)[None, :] * kg + best)[:, :how_many_outputs]
 
-        res_tok, lp = _search.run_search(eng, st, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
-                                         step=step, pick=pick)
-        return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+        step = lambda cons: eng.group_beam_step(st, eos_idx, G, penalty, constraints=cons)              # noqa: E731
+        res_tok, lp = _search.run_search(eng, st, eos_idx, steps - (len(prefix[0]) if prefix else 0), how_many_outputs,
+                                         constraints=constraints, step=_search.logged(step, st, self._cand_log), pick=pick,
+                                         arm=lambda: _search.arm_state(eng, st, sos_idx, prefix, emb=st.emb, group_beams=kg))
+        return res_tok, _to_input_device(lp, enc_input)
 
     def stochastic_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, num_samples=5, max_seq_len=20,
                                seed=None, *, prefix=None, required_words=None, no_repeat_ngram_size=0, min_length=0,
@@ -592,32 +570,25 @@ class CaptioningModel(nn.Module):
                                           no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                           banned_words=banned_words, temperature=temperature, top_k=top_k, top_p=top_p)
         R = n + 1
-        if R > self._vocab_size():
-            raise ValueError(f"{R} rows per image exceed the vocabulary ({self._vocab_size()} words)")
+        self._check_rows_fit(R)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         mem = self.forward_enc(enc_input, enc_input_num_pads)
-        eng = self._captioner_engine()
-        B, S, _ = mem.shape
-        steps = max(1, max_seq_len - 1)
-        T = steps + 1
-        st = eng.new_state(B, R, T, eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads))
-
-        def step(cons):
-            eng.stochastic_beam_step(st, eos_idx, seed)
-            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
-                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone(), st.cand_pert.cpu().clone()))
+        eng, st, steps = self._open_search(mem, enc_input_num_pads, R, max_seq_len)
+        B = st.n_img
 
         def pick(order, score):                                   # the rows are in sampling order already
             return torch.arange(n)[None, :].expand(B, n)
 
+        step = _search.logged(lambda cons: eng.stochastic_beam_step(st, eos_idx, seed), st, self._cand_log,
+                              lambda: st.cand_pert.cpu().clone())
         res_tok, lp = _search.run_search(eng, st, eos_idx, steps, n, step=step, pick=pick,
-                                         arm=lambda: ops.beam_reset(st.beam_state, B, R, T, sos_idx, emb=st.emb))
+                                         arm=lambda: _search.arm_state(eng, st, sos_idx, emb=st.emb))
         g = st.gscore.view(B, R)
         self.last_stochastic_beam = {"gumbel": g[:, :n].clone(), "kappa": g[:, n].clone(),
                                      "sum_logprob": st.cumul.view(B, R)[:, :n].clone()}
-        return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+        return res_tok, _to_input_device(lp, enc_input)
 
     def contrastive_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, distractors, beam_size=3,
                                 how_many_outputs=1, max_seq_len=20, *, contrast=0.5, plausibility=0.1,
@@ -646,34 +617,25 @@ class CaptioningModel(nn.Module):
         cons = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                             banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
                                             max_seq_len=max_seq_len, rows_per_image=beam_size)
-        if beam_size > self._vocab_size():
-            raise ValueError(f"{beam_size} beams per image exceed the vocabulary ({self._vocab_size()} words)")
+        self._check_rows_fit(beam_size, "beams")
         mem = self.forward_enc(enc_input, enc_input_num_pads)
-        eng = self._captioner_engine()
+        k = int(beam_size)
+        eng, st, steps = self._open_search(mem, enc_input_num_pads, k, max_seq_len)
         dv = eng.device
-        S = mem.shape[1]
-        k, D = int(beam_size), c["D"]
-        steps = max(1, max_seq_len - 1)
-        T = steps + 1
-        kv, enc_len = eng.project_kv(mem), self._enc_lens(B, S, enc_input_num_pads)
-        states = [eng.new_state(B, k, T, kv, enc_len)]
-        for d in range(D):           # distractor d of every image: its memory rows (an unused slot: the image's own; count masks it)
+        states = [st]
+        for d in range(c["D"]):      # distractor d of every image: its memory rows (an unused slot: the image's own; count masks it)
             idx = torch.tensor([r[d] if d < len(r) else i for i, r in enumerate(c["lists"])], dtype=torch.int64, device=dv)
-            states.append(eng.new_state(B, k, T, kv.index_select(0, idx).contiguous(), enc_len.index_select(0, idx)))
-        st = _search.share_beam_state(states)
+            states.append(eng.new_state(B, k, st.T, st.kv.index_select(0, idx).contiguous(), st.enc_len.index_select(0, idx)))
+        _search.share_beam_state(states)
         count = torch.tensor([len(r) for r in c["lists"]], dtype=torch.int32, device=dv).repeat_interleave(k).contiguous()
         # under constraints a row can lose n_banned + T words (odic_topk_rows_constrained): beam_size finite ones remain
-        min_keep = k + (len(cons["banned"]) + T if cons else 0)
+        min_keep = k + (len(cons["banned"]) + st.T if cons else 0)
         args = ops.contrast_args(c["contrast"], c["plausibility"], c["suppressor_floor"], min_keep)
-
-        def step(dev_cons):
-            eng.contrast_beam_step(states, count, args, eos_idx, constraints=dev_cons)
-            if self._cand_log is not None:                        # test hook: the candidates, for replay in the model
-                self._cand_log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()))
-
-        res_tok, lp = _search.run_search(eng, st, eos_idx, steps, how_many_outputs, constraints=cons, step=step,
-                                         arm=lambda: ops.beam_reset(st.beam_state, B, k, T, sos_idx, emb=None))
-        return res_tok, (lp.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else lp)
+        step = lambda dev_cons: eng.contrast_beam_step(states, count, args, eos_idx, constraints=dev_cons)     # noqa: E731
+        res_tok, lp = _search.run_search(eng, st, eos_idx, steps, how_many_outputs, constraints=cons,
+                                         step=_search.logged(step, st, self._cand_log),
+                                         arm=lambda: _search.arm_state(eng, st, sos_idx, emb=None))
+        return res_tok, _to_input_device(lp, enc_input)
 
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, num_candidates, source="sampling", sos_idx, eos_idx,
                           max_seq_len=20, corpus=None, metric="cider", **search_args):
@@ -716,6 +678,11 @@ def _as_list(pads, n: int) -> List[int]:
     return [int(p) for p in pads]
 
 
+def _to_input_device(x: torch.Tensor, enc_input) -> torch.Tensor:
+    """A result goes back on the device its input came from; an input that is no tensor leaves it on the engine's."""
+    return x.to(enc_input.device) if isinstance(enc_input, torch.Tensor) else x
+
+
 # =================================================================================================
 # refactored API  (models/captioning_model.py:40-110, models/End_ExpansionNet_v2.py:311-354)
 # =================================================================================================
@@ -739,10 +706,22 @@ class Captioner:
     def __call__(self, enc_x, dec_x=None, enc_x_num_pads=[0], dec_x_num_pads=[0], mode="beam_search"):
         assert ("sos_idx" in self.beam_search_args.keys() or "eos_idx" in self.beam_search_args.keys()), \
             "sos and eos must be provided in case of batch sampling or beam search"
-        a = self.beam_search_args
         self.apply_log_softmax = True
-        args = dict(a, sos_idx=a["sos_idx"], eos_idx=a["eos_idx"])      # (both required here, KeyError; forward() has -999)
-        return _search.dispatch(self.model, mode, args, enc_x, enc_x_num_pads)
+        return _search.dispatch(self.model, mode, self._dispatch_args(), enc_x, enc_x_num_pads)
+
+    def _dispatch_args(self, **more) -> dict:
+        """`beam_search_args` (and `more`) as search.dispatch takes them; sos_idx and eos_idx are required here (KeyError;
+        forward() has -999)."""
+        a = self.beam_search_args
+        return dict(a, sos_idx=a["sos_idx"], eos_idx=a["eos_idx"], **more)
+
+    def _fill_search_defaults(self, k: dict, *names) -> None:
+        """Every keyword of `names` the call left out takes its value from `beam_search_args`, where that has one
+        (max_seq_len is its beam_max_seq_len)."""
+        for name in names:
+            key = "beam_max_seq_len" if name == "max_seq_len" else name
+            if key in self.beam_search_args:
+                k.setdefault(name, self.beam_search_args[key])
 
     def forward_enc(self, enc_input, enc_input_num_pads):
         return self.model.forward_enc(enc_input, enc_input_num_pads)
@@ -767,10 +746,7 @@ class Captioner:
         """CaptioningModel.consensus_caption with this object's `beam_search_args` (sos_idx, eos_idx, beam_max_seq_len)
         unless the call names its own."""
         k["metric"] = metric
-        b = self.beam_search_args
-        for arg, key in (("sos_idx", "sos_idx"), ("eos_idx", "eos_idx"), ("max_seq_len", "beam_max_seq_len")):
-            if key in b:
-                k.setdefault(arg, b[key])
+        self._fill_search_defaults(k, "sos_idx", "eos_idx", "max_seq_len")
         return self.model.consensus_caption(enc_x, enc_x_num_pads, **k)
 
     def score_captions(self, *a, **k):
@@ -782,11 +758,7 @@ class Captioner:
     def word_attention(self, enc_x, captions=None, *a, **k):
         """CaptioningModel.word_attention; the generated-caption form (`captions=None`) searches with this object's
         `beam_search_args` (sos_idx, eos_idx, beam_size, beam_max_seq_len) unless the call names its own."""
-        b = self.beam_search_args
-        for arg, key in (("sos_idx", "sos_idx"), ("eos_idx", "eos_idx"), ("beam_size", "beam_size"),
-                         ("max_seq_len", "beam_max_seq_len")):
-            if key in b:
-                k.setdefault(arg, b[key])
+        self._fill_search_defaults(k, "sos_idx", "eos_idx", "beam_size", "max_seq_len")
         return self.model.word_attention(enc_x, captions, *a, **k)
 
     def caption_regions(self, preprocessor, images, regions, distinctive=False, **contrast_args):
@@ -815,9 +787,8 @@ class Captioner:
                                  f"{_search.MAX_DISTRACTORS} distractors per region")
         batch = preprocessor.resize_regions(images, regions)
         if distinctive:
-            a = self.beam_search_args
-            args = dict(a, sos_idx=a["sos_idx"], eos_idx=a["eos_idx"], distractors=siblings, **contrast_args)
-            toks, lps = _search.dispatch(self.model, "contrastive_beam_search", args, batch, [0] * len(regions))
+            toks, lps = _search.dispatch(self.model, "contrastive_beam_search",
+                                         self._dispatch_args(distractors=siblings, **contrast_args), batch, [0] * len(regions))
         else:
             toks, lps = self(batch, enc_x_num_pads=[0] * len(regions))
         for n, (i, box) in enumerate(regions):

@@ -124,26 +124,19 @@ class EsembleCaptioningModel(CaptioningModel):
         # log-probabilities (its normalisation is then the identity up to rounding), keyed by the lead member's seed
         seed = self.models_list[0]._next_sampling_seed() if sample else None
         mems = self.forward_enc(enc_input, enc_input_num_pads)
-        engs = [m._captioner_engine() for m in self.models_list]
-        B, S, _ = mems[0].shape
-        k = beam_size
-        steps = max(1, max_seq_len - 1)
-        T = steps + 1
-        states = [eng.new_state(B, k, T, eng.project_kv(mem), m._enc_lens(B, S, enc_input_num_pads))
-                  for m, eng, mem in zip(self.models_list, engs, mems)]
+        engs, states = [], []
+        for m, mem in zip(self.models_list, mems):
+            eng, st, steps = m._open_search(mem, enc_input_num_pads, beam_size, max_seq_len)
+            engs.append(eng)
+            states.append(st)
         lead = _search.share_beam_state(states)
-        P = len(prefix[0]) if prefix else 0
         avg = torch.empty(lead.N, engs[0].g.vocab_size, dtype=torch.float32, device=engs[0].device)
-
-        def arm():
-            if P:
-                _search.ensemble_seed_prefix(engs, states, _search.prefix_tensor(prefix, engs[0].device), sos_idx)
-            else:
-                ops.beam_reset(lead.beam_state, B, k, T, sos_idx, emb=None)  # (the members embed for themselves in step_logits)
-
         # (the log-probs stay on the engine's device, unlike beam_search's, which go to the input's)
         return _search.run_search(
-            engs[0], lead, eos_idx, steps - P, how_many_outputs, arm=arm, constraints=constraints,
+            engs[0], lead, eos_idx, steps - (len(prefix[0]) if prefix else 0), how_many_outputs, constraints=constraints,
+            arm=lambda: _search.arm_state(     # (emb: the members embed for themselves in step_logits)
+                engs[0], lead, sos_idx, prefix, emb=None,
+                seed_prefix=lambda p: _search.ensemble_seed_prefix(engs, states, p, sos_idx)),
             step=lambda cons: _search.ensemble_step(engs, states, avg, eos_idx, sample_seed=seed, constraints=cons,
                                                     sample_filter=flt))
 

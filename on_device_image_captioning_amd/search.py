@@ -51,24 +51,36 @@ def check_constraints(n: int, m: int, banned, *, V, max_seq_len: int, rows_per_i
     return dict(no_repeat_ngram=n, min_words=m, banned=banned)
 
 
+def per_image_word_lists(value, n_img: int, noun: str) -> Optional[List[List[int]]]:
+    """"One word list for all images, or one per image", read once for `prefix` and `required_words`.  `value`: None, a
+    1-D or 2-D tensor, a flat sequence of word ids (one list for all images), or a sequence whose elements are all lists,
+    tuples or tensors (one per image; `noun` names them in the count error).  → None for None, else n_img lists of ints."""
+    if value is None:
+        return None
+    value = list(value.tolist() if isinstance(value, torch.Tensor) else value)
+    if not value or not all(isinstance(r, (list, tuple, torch.Tensor)) for r in value):
+        return [[int(w) for w in value] for _ in range(n_img)]
+    rows = [[int(w) for w in (r.tolist() if isinstance(r, torch.Tensor) else r)] for r in value]
+    if len(rows) != n_img:
+        raise ValueError(f"{len(rows)} {noun} for {n_img} images: give one for all, or one per image")
+    return rows
+
+
+def names_a_word(value) -> bool:
+    """Does a `prefix` / `required_words` value the caller will refuse hold any word (per_image_word_lists' forms, read
+    without the image count)."""
+    if isinstance(value, torch.Tensor):
+        value = value.tolist()
+    return value is not None and any(len(p) if isinstance(p, (list, tuple, torch.Tensor)) else 1 for p in value)
+
+
 def check_prefix(prefix, n_img: int, *, V, max_seq_len: int, sos_idx, eos_idx, sampling: bool = False
                  ) -> Optional[List[List[int]]]:
     """The rules of a search that starts behind given words.  `prefix`: one sequence of word ids used
     for every image, or one sequence per image, all of the same length.  None for no prefix (None, or nothing but empty
     sequences: the search then launches exactly what it launches without the keyword), else the n_img id lists;
     ValueError, before any device work, for what cannot work."""
-    if prefix is None:
-        return None
-    if isinstance(prefix, torch.Tensor):
-        prefix = prefix.tolist()
-    prefix = list(prefix)
-    nested = bool(prefix) and all(isinstance(p, (list, tuple, torch.Tensor)) for p in prefix)
-    if nested:
-        rows = [[int(w) for w in (p.tolist() if isinstance(p, torch.Tensor) else p)] for p in prefix]
-        if len(rows) != n_img:
-            raise ValueError(f"{len(rows)} prefixes for {n_img} images: give one for all, or one per image")
-    else:
-        rows = [[int(w) for w in prefix]] * n_img
+    rows = per_image_word_lists(prefix, n_img, "prefixes") or []
     P = len(rows[0]) if rows else 0
     if any(len(r) != P for r in rows):
         raise ValueError("the prefixes of a batch must have one length (the position is one device scalar)")
@@ -86,7 +98,7 @@ def check_prefix(prefix, n_img: int, *, V, max_seq_len: int, sos_idx, eos_idx, s
                 raise ValueError(f"prefix word id {w} lies outside the vocabulary [0, {V})")
             if w == sos_idx or w == eos_idx:
                 raise ValueError("the SOS and EOS ids cannot be part of a prefix")
-    return [list(r) for r in rows]
+    return rows
 
 
 def _filter_kwargs(args) -> dict:
@@ -142,18 +154,7 @@ def check_required_words(required, n_img: int, *, V, beam_size: int, banned, sos
     but empty sequences: the search then launches exactly what it launches without the keyword), else n_img lists of C ids,
     C the longest list, the shorter ones padded with -1; ValueError, before any device work, for what cannot work.
     `beam_size` is the beams per bank: an image searches 2^C·beam_size rows."""
-    if required is None:
-        return None
-    if isinstance(required, torch.Tensor):
-        required = required.tolist()
-    required = list(required)
-    nested = bool(required) and all(isinstance(r, (list, tuple, torch.Tensor)) for r in required)
-    if nested:
-        rows = [[int(w) for w in (r.tolist() if isinstance(r, torch.Tensor) else r)] for r in required]
-        if len(rows) != n_img:
-            raise ValueError(f"{len(rows)} lists of required words for {n_img} images: give one for all, or one per image")
-    else:
-        rows = [[int(w) for w in required] for _ in range(n_img)]
+    rows = per_image_word_lists(required, n_img, "lists of required words") or []
     C = max((len(r) for r in rows), default=0)
     if C == 0:
         return None
@@ -181,11 +182,13 @@ def check_required_words(required, n_img: int, *, V, beam_size: int, banned, sos
                 raise ValueError("the SOS and EOS ids cannot be required words")
             if w in banned:
                 raise ValueError(f"word id {w} is both required and banned")
-    return [list(r) + [-1] * (C - len(r)) for r in rows]
+    return [r + [-1] * (C - len(r)) for r in rows]
 
 
 def refuse_required_words(required, where: str) -> None:
-    """For the searches that do not take required words: ValueError unless `required` is None or holds no word."""
+    """For the searches that do not take required words: ValueError unless `required` is None or holds no word.
+    (Not names_a_word: this reader unpacks every element before it looks, that one stops at the first word, so where a
+    0-d tensor stands for a list of ids the two raise differently — [5, tensor(6)]: TypeError here, a word there.)"""
     if required is None:
         return
     if isinstance(required, torch.Tensor):
@@ -210,9 +213,7 @@ def check_stochastic_beam(num_samples, *, prefix=None, required_words=None, no_r
                          f"rows per image, 16 at most), not {num_samples!r}")
     refuse_required_words(required_words, where)
     tail = "it samples captions from the model's own distribution"
-    if isinstance(prefix, torch.Tensor):
-        prefix = prefix.tolist()
-    if prefix is not None and any(len(p) if isinstance(p, (list, tuple, torch.Tensor)) else 1 for p in prefix):
+    if names_a_word(prefix):
         raise ValueError(f"prefix is not supported {where}: {tail}")
     if int(no_repeat_ngram_size) != 0:
         raise ValueError(f"no_repeat_ngram_size is not supported {where}: {tail}")
@@ -238,9 +239,7 @@ def check_contrast(distractors, n_img: int, *, contrast=0.5, plausibility=0.1, s
     where = "in contrastive_beam_search"
     refuse_required_words(required_words, where)
     tail = "it ranks the words of one deterministic beam search by a contrast between images"
-    if isinstance(prefix, torch.Tensor):
-        prefix = prefix.tolist()
-    if prefix is not None and any(len(p) if isinstance(p, (list, tuple, torch.Tensor)) else 1 for p in prefix):
+    if names_a_word(prefix):
         raise ValueError(f"prefix is not supported {where}: {tail}")
     if sample_or_max != "max":
         raise ValueError(f"sample_or_max={sample_or_max!r} is not supported {where}: {tail}")
@@ -309,48 +308,38 @@ def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, h
 def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
     """mode='beam_search' | 'sampling' | 'diverse_beam_search' | 'stochastic_beam_search' | 'contrastive_beam_search' with the keys of `args` (a forward(**kwargs) or
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
-    sos_idx, eos_idx, cons = args.get("sos_idx", -999), args.get("eos_idx", -999), _constraint_kwargs(args)
+    ends = dict(sos_idx=args.get("sos_idx", -999), eos_idx=args.get("eos_idx", -999))
+    cons, flt = _constraint_kwargs(args), _filter_kwargs(args)
     pre = {k: args[k] for k in ("prefix", "required_words") if k in args}       # (absent = the default, as the constraints)
-    flt = _filter_kwargs(args)
-    if mode == "beam_search":
-        return model.beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                 beam_size=args.get("beam_size", 5), how_many_outputs=args.get("how_many_outputs", 1),
-                                 max_seq_len=args.get("beam_max_seq_len", 20),
-                                 sample_or_max=args.get("sample_or_max", "max"), **pre, **cons, **flt)
     if mode == "sampling":
-        max_seq_len = args.get("sample_max_seq_len", 20)
-        model._search_constraint_args(**cons, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len, rows_per_image=1,
-                                      sampling=True)
+        ends["max_seq_len"] = args.get("sample_max_seq_len", 20)
+        model._search_constraint_args(**cons, **ends, rows_per_image=1, sampling=True)
         if pre.get("prefix") is not None:
-            model._search_prefix_arg(pre["prefix"], enc_x, sos_idx=sos_idx, eos_idx=eos_idx, max_seq_len=max_seq_len,
-                                     sampling=True)
+            model._search_prefix_arg(pre["prefix"], enc_x, **ends, sampling=True)
         if pre.get("required_words") is not None:
-            model._search_required_arg(pre["required_words"], enc_x, beam_size=1, banned_words=None, sos_idx=sos_idx,
-                                       eos_idx=eos_idx, max_seq_len=max_seq_len, sampling=True)
-        return model.get_batch_multiple_sampled_prediction(
-            enc_x, enc_x_num_pads, num_outputs=args.get("how_many_outputs", 1), sos_idx=sos_idx, eos_idx=eos_idx,
-            max_seq_len=max_seq_len, **flt)
+            model._search_required_arg(pre["required_words"], enc_x, beam_size=1, banned_words=None, **ends, sampling=True)
+        return model.get_batch_multiple_sampled_prediction(enc_x, enc_x_num_pads, num_outputs=args.get("how_many_outputs", 1),
+                                                           **ends, **flt)
+    # the deterministic searches: the ends and the length, the prefix / required words and the constraints go to all four
+    common = dict(ends, max_seq_len=args.get("beam_max_seq_len", 20), **pre, **cons)
+    beam = dict(beam_size=args.get("beam_size", 5), how_many_outputs=args.get("how_many_outputs", 1),
+                sample_or_max=args.get("sample_or_max", "max"))
+    if mode == "beam_search":
+        return model.beam_search(enc_x, enc_x_num_pads, **beam, **common, **flt)
     if mode == "diverse_beam_search":
         check_sampling_filter(**flt, sampling=False, where="diverse_beam_search")
-        return model.diverse_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                         num_groups=args.get("num_groups", 3), group_size=args.get("group_size", 3),
+        return model.diverse_beam_search(enc_x, enc_x_num_pads, num_groups=args.get("num_groups", 3),
+                                         group_size=args.get("group_size", 3),
                                          diversity_penalty=args.get("diversity_penalty", 0.5),
-                                         how_many_outputs=args.get("how_many_outputs", None),
-                                         max_seq_len=args.get("beam_max_seq_len", 20), **pre, **cons)
+                                         how_many_outputs=args.get("how_many_outputs", None), **common)
     if mode == "stochastic_beam_search":
-        return model.stochastic_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                            num_samples=args.get("num_samples", 5),
-                                            max_seq_len=args.get("beam_max_seq_len", 20), seed=args.get("seed", None),
-                                            **pre, **cons, **flt)
+        return model.stochastic_beam_search(enc_x, enc_x_num_pads, num_samples=args.get("num_samples", 5),
+                                            seed=args.get("seed", None), **common, **flt)
     if mode == "contrastive_beam_search":
         check_sampling_filter(**flt, sampling=False, where="contrastive_beam_search")
         knobs = {k: args[k] for k in ("contrast", "plausibility", "suppressor_floor") if k in args}
-        return model.contrastive_beam_search(enc_x, enc_x_num_pads, sos_idx=sos_idx, eos_idx=eos_idx,
-                                             distractors=args.get("distractors", "others"),
-                                             beam_size=args.get("beam_size", 5),
-                                             how_many_outputs=args.get("how_many_outputs", 1),
-                                             max_seq_len=args.get("beam_max_seq_len", 20),
-                                             sample_or_max=args.get("sample_or_max", "max"), **knobs, **pre, **cons)
+        return model.contrastive_beam_search(enc_x, enc_x_num_pads, distractors=args.get("distractors", "others"), **beam,
+                                             **knobs, **common)
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -389,6 +378,32 @@ def read_captions(state, rows: torch.Tensor, how_many_outputs: int) -> Tuple[Lis
             lp_rows.append(state.logprobs[b, i, :n])
         res_tok.append(per)
     return res_tok, torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
+
+
+def arm_state(eng, st, sos_idx: int, prefix: Optional[List[List[int]]] = None, *, emb, group_beams: Optional[int] = None,
+              seed_prefix: Optional[Callable[[torch.Tensor], None]] = None) -> None:
+    """Bring the built (lead) state to its first position, the arm() of every search.  Behind `prefix` (check_prefix's
+    lists): eng.seed_prefix on `st`, the rows in groups of `group_beams` — or seed_prefix(prefix tensor), the ensemble's
+    way (ensemble_seed_prefix).  Without one: odic_beam_reset, which with `emb` (st.emb) also embeds the start token as
+    the input of position 0; None where the step embeds for itself (step_logits: the draws, the contrast, the ensemble)."""
+    if prefix:
+        p = prefix_tensor(prefix, eng.device)
+        seed_prefix(p) if seed_prefix else eng.seed_prefix(st, p, sos_idx, group_beams=group_beams)
+    else:
+        ops.beam_reset(st.beam_state, st.n_img, st.beams, st.T, sos_idx, emb=emb)
+
+
+def logged(step: Callable[[object], None], st, log: Optional[list], extra: Optional[Callable[[], torch.Tensor]] = None):
+    """The test hook of the deterministic searches, once: `step` itself when `log` (a model's _cand_log) is None, else
+    step followed by log.append((cand_val, cand_idx[, extra()])) — host copies of what the step chose from, for replay in
+    the tests' models."""
+    if log is None:
+        return step
+
+    def logged_step(cons):
+        step(cons)
+        log.append((st.cand_val.cpu().clone(), st.cand_idx.cpu().clone()) + ((extra(),) if extra else ()))
+    return logged_step
 
 
 def run_search(eng, st, eos_idx: int, steps: int, how_many_outputs: int, *, arm: Callable[[], None],
