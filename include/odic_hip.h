@@ -1019,6 +1019,63 @@ int odic_stochastic_beam_step(const float* cand_val, const int32_t* cand_idx, co
                               const odic_beam_state* st, const odic_embed_args* emb, int32_t n_img, int32_t beams,
                               int32_t T, int64_t eos_idx, void* stream);
 
+/* POOLED beam search (csrc/pool_beam.hip), on the same beam state: a hypothesis that takes EOS leaves the
+ * beam for a per-image pool of at most P = beams finished hypotheses scored by sum / len^alpha, the `beams` rows stay live,
+ * and an image closes once its pool cannot be improved.  Additions to ABI 26.
+ *   The pool, all device resident and compact: tokens int64 / logprobs fp32 [n_img, P, T]; len int32, sum fp32, score fp32,
+ *   serial int32 [n_img, P]; count int32 [n_img] (entries [0, count) of an image are hypotheses); closed int32 [n_img]
+ *   (0 = open; bit 0: closed by a step; bit 1: finalized).  odic_pool_reset zeroes count and closed — nothing else of the
+ *   pool is read before it is written.  scale fp32 [T + 1]: scale[L] = (fp32)((double)L ** alpha), built by the host, so
+ *   that the device never calls powf and score = __fdiv_rn(sum, scale[len]) can be reproduced bit for bit; len counts SOS
+ *   and EOS like n_elem (alpha = 1: odic_beam_finalize's score of the same row).
+ *   cand_val / cand_idx [n_img·beams, beams]: every row's `beams` best admissible words OTHER than eos_idx (the caller
+ *   selects them with EOS inadmissible: odic_topk_rows_constrained with min_words >= T); logp fp32 [n_img·beams, V] (ldl):
+ *   the log-prob rows they came from — the step reads logp[row][eos_idx] and nothing else of them.
+ * One step at *pos = t for an open image:
+ *   1. Every live row j (cumul > -inf; t = 0: row 0 alone, its cumul taken as 0) offers candidate c < beams at cand_val as
+ *      slot c, and EOS at logp[j][eos_idx] as slot `beams` — the latter only when t >= min_words.
+ *   2. The candidates are ranked by total = cumul_j + value (one rounded addition; t = 0: the value), descending, a tie
+ *      to the lower key j·(beams + 1) + slot; a total of -inf or NaN is never ranked.
+ *   3. The ranking is walked from the best, 2·beams extractions at most: a word becomes the next live row until `beams`
+ *      are chosen; an EOS met while fewer than `beams` candidates were extracted before it is offered to the pool, a later
+ *      one dropped.  A slot for which nothing is left becomes the EMPTY row of odic_beam_step (parent = the slot itself,
+ *      row 0 at t = 0; word = eos_idx; stored log-prob -inf).
+ *   4. A pool offer: sum = the parent's per-token log-probs re-summed in position order, + value (odic_beam_step's order
+ *      for cumul); len = n_elem(parent) + 1; score as above (len clamped to [0, T] for the table).  While count < P it is
+ *      appended; else it replaces the worst entry (lowest score, a tie to the highest serial) if its score is STRICTLY
+ *      greater.  An accepted hypothesis takes serial = 1 + the largest serial in the pool (0 in an empty pool), the
+ *      parent's tokens / log-probs [0..t] as they stand before this step permutes the rows, eos_idx / value at t + 1 and
+ *      zeros behind.  The offers of one step are applied one after the other in walk order.
+ *   5. The image closes if count == P and (early_stopping != 0 or worst score >= __fdiv_rn(best new cumul, scale[T])), best
+ *      new cumul the largest cumul of the rows chosen in 3 (-inf when there is none).  Its rows are written as by any step
+ *      but with row_valid = 0, they do not count as growing for *done, and closed = 1.
+ *   Everything else (permutation, embedding tail, n_elem, has_eos, next_tok, *pos, *done, the counter, the no-op at
+ *   *pos == T - 1) is odic_beam_step's.  For a closed image a step changes nothing (its block only arrives at the counter).
+ * odic_pool_beam_finalize, once after the last step, one block per image: an image still open (closed == 0) offers its rows
+ *   with cumul > -inf and has_eos == 0 in row order, sum = cumul, len = n_elem, tokens / log-probs [0, len) and zeros behind
+ *   (no EOS), by the rule of 4.  Then order int32 [n_img, P]: the pool slots by score descending, a tie to the lower serial,
+ *   -1 behind the count; score fp32 [n_img, P]: the scores in that order, -inf behind the count; closed |= 2.
+ *   ODIC_EINVAL — one refusal code — before any launch and with nothing written: beams outside [1, 15] (beams·(beams + 1)
+ *   candidates are ranked 256 at a time), T / n_img outside odic_beam_step's limits, V < 1, ldl < V, eos_idx outside
+ *   [0, V), min_words < 0, a NULL pointer (cand_val, cand_idx, logp, order, score, pool or one of its arrays, st or one of
+ *   its arrays), an emb with a NULL table.  All stores stay inside the compact state and pool arrays, order, score and
+ *   columns [0, d) of emb->y (the pool and state arrays run in guarded buffers in
+ *   tests/test_pool_beam_kernels_gpu.py; the embedding tail is odic_beam_step's). */
+typedef struct odic_pool_args {
+  int64_t* tokens; float* logprobs;
+  int32_t* len; float* sum; float* score; int32_t* serial;
+  int32_t* count; int32_t* closed;
+  const float* scale;
+  int32_t min_words;        /* EOS is offered only at *pos >= min_words (the caption would hold *pos words) */
+  int32_t early_stopping;   /* != 0: an image closes as soon as its pool is full */
+} odic_pool_args;
+int odic_pool_reset(const odic_pool_args* pool, int32_t n_img, void* stream);
+int odic_pool_beam_step(const float* cand_val, const int32_t* cand_idx, const float* logp, int64_t ldl,
+                        const odic_pool_args* pool, const odic_beam_state* st, const odic_embed_args* emb,
+                        int32_t n_img, int32_t beams, int32_t T, int64_t eos_idx, int32_t V, void* stream);
+int odic_pool_beam_finalize(const odic_pool_args* pool, const odic_beam_state* st, int32_t* order, float* score,
+                            int32_t n_img, int32_t beams, int32_t T, void* stream);
+
 /* Initial state of a search (captioning_model.py:117-125): tokens[:, :, 0] = sos, logprobs[:, :, 0] = 0,
  * next_tok = sos, row_valid = 1, *pos = *done = *ctr = 0; with emb, also the input of position 0 (the embedded
  * start token).  One launch instead of six fills on the latency-bound decode stream. */

@@ -65,6 +65,12 @@ class ContrastArgs(C.Structure):
     _fields_ = [("weight", C.c_float), ("log_alpha", C.c_float), ("floor", C.c_float), ("min_keep", C.c_int32)]
 
 
+class PoolArgs(C.Structure):
+    """odic_pool_args: the pool of finished hypotheses of a pooled beam search (ops.pool_args builds one)."""
+    _fields_ = [(n, C.c_void_p) for n in ("tokens", "logprobs", "len", "sum", "score", "serial", "count", "closed", "scale")] + \
+               [("min_words", C.c_int32), ("early_stopping", C.c_int32)]
+
+
 class JpegBatch(C.Structure):
     """odic_jpeg_batch: one batched JPEG decode (headers from on_device_image_captioning_amd.jpeg.pack_headers)."""
     _fields_ = [("headers", C.c_void_p), ("data", C.c_void_p), ("out", C.c_void_p), ("status", C.c_void_p),
@@ -139,6 +145,10 @@ _SIGNATURES = {
                                          _I32, _I32, _I64, _I32, _P]),
     "odic_stochastic_beam_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64,
                                             _P]),
+    "odic_pool_reset": (C.c_int, [C.POINTER(PoolArgs), _I32, _P]),
+    "odic_pool_beam_step": (C.c_int, [_P, _P, _P, _I64, C.POINTER(PoolArgs), C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32,
+                                      _I32, _I32, _I64, _I32, _P]),
+    "odic_pool_beam_finalize": (C.c_int, [C.POINTER(PoolArgs), C.POINTER(BeamState), _P, _P, _I32, _I32, _I32, _P]),
     "odic_beam_finalize": (C.c_int, [C.POINTER(BeamState), _P, _P, _I32, _I32, _P]),
     "odic_beam_finalize_best": (C.c_int, [C.POINTER(BeamState), _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "odic_beam_reset": (C.c_int, [C.POINTER(BeamState), C.POINTER(EmbedArgs), _I32, _I32, _I32, _I64, _P]),

@@ -45,6 +45,9 @@ class CaptioningModel(nn.Module):
         self._cand_log = None               # list → every deterministic search step's (cand_val, cand_idx) is appended (tests)
         self.last_stochastic_beam = None    # after stochastic_beam_search: the samples' perturbed scores, kappa and log-probs
         self.last_required_satisfied = None  # after a beam_search with required_words: per image, does output 0 hold them all
+        self.last_pool_scores = None        # after pool_beam_search: the outputs' scores sum / len^alpha, fp32 [B, how_many_outputs],
+        self.last_pool_counts = None        # the hypotheses every image's pool held, int32 [B], and
+        self.last_pool_closed = None        # whether the image closed before the steps ran out, bool [B] (all on the host)
 
     # ------------------------------------------------------------------ engine cache plumbing
     def check_required_attributes(self):
@@ -590,6 +593,53 @@ class CaptioningModel(nn.Module):
                                      "sum_logprob": st.cumul.view(B, R)[:, :n].clone()}
         return res_tok, _to_input_device(lp, enc_input)
 
+    def pool_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, beam_size=3, how_many_outputs=1,
+                         max_seq_len=20, length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=0, min_length=0,
+                         banned_words=None, *, prefix=None, required_words=None, sample_or_max="max"):
+        """Beam search with a pool of finished captions: a beam that takes EOS leaves the beam for a
+        per-image pool of at most `beam_size` finished captions scored by (sum of log-probs) / length^`length_penalty`
+        (length counts SOS and EOS; 1.0 is the final ranking of beam_search, 0 ranks by the raw sum, larger values favour
+        longer captions), so all `beam_size` rows keep exploring, and an image stops once its pool is full and no live
+        row can still beat the pool's worst entry — or, with `early_stopping`, as soon as the pool is full.  Rows still
+        unfinished when the steps run out join the pool as they are.  Every step is the decoder, the constrained row
+        selection with EOS inadmissible and odic_pool_beam_step.
+        Returns what beam_search returns: output j of an image is the j-th best caption of its pool, with the model's own
+        per-token log-probs.  `self.last_pool_scores` (fp32 [B, how_many_outputs]) holds their scores,
+        `self.last_pool_counts` (int32 [B]) the captions each pool held and `self.last_pool_closed` (bool [B]) whether the
+        image closed before the steps ran out (every caption of such an image ends in EOS).  A pool holds fewer than
+        how_many_outputs captions only when every candidate of the image died (-inf rows): the missing outputs are then
+        the EMPTY caption [sos, eos] with log-probs [0, -inf] and score -inf.
+        how_many_outputs <= beam_size <= 15.  `no_repeat_ngram_size`, `min_length`, `banned_words`: as in beam_search.
+        prefix, required_words and sample_or_max='sample' are accepted so that a call that names them fails loudly:
+        ValueError, like length_penalty < 0 or not finite."""
+        alpha = _search.check_pool_beam(beam_size, how_many_outputs, length_penalty, prefix=prefix,
+                                        required_words=required_words, sample_or_max=sample_or_max)
+        k, n_out = int(beam_size), int(how_many_outputs)
+        cons = self._search_constraint_args(no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                            banned_words=banned_words, sos_idx=sos_idx, eos_idx=eos_idx,
+                                            max_seq_len=max_seq_len, rows_per_image=k) or {}
+        self._check_rows_fit(k + 1, "beams and EOS")
+        mem = self.forward_enc(enc_input, enc_input_num_pads)
+        eng, st, steps = self._open_search(mem, enc_input_num_pads, k, max_seq_len)
+        pool = ops.Pool(st.n_img, k, st.T, alpha, cons.get("min_words", 0), bool(early_stopping), eng.device)
+        dev_cons = eng.pool_constraints(st, eos_idx, no_repeat_ngram=cons.get("no_repeat_ngram", 0),
+                                        banned=cons.get("banned"))
+
+        def arm():
+            _search.arm_state(eng, st, sos_idx, emb=st.emb)
+            ops.pool_reset(pool.args, st.n_img)
+
+        def finish():
+            closed = pool.closed.cpu() != 0                       # (before the finalize marks every image)
+            toks, lp, self.last_pool_scores, self.last_pool_counts = _search.read_pool(st, pool, n_out, sos_idx, eos_idx)
+            self.last_pool_closed = closed
+            return toks, lp
+
+        step = _search.logged(lambda _: eng.pool_beam_step(st, pool, eos_idx, dev_cons), st, self._cand_log,
+                              lambda: st.logp[:, eos_idx].cpu().clone())
+        res_tok, lp = _search.run_search(eng, st, eos_idx, steps, n_out, arm=arm, step=step, finish=finish)
+        return res_tok, _to_input_device(lp, enc_input)
+
     def contrastive_beam_search(self, enc_input, enc_input_num_pads, sos_idx, eos_idx, distractors, beam_size=3,
                                 how_many_outputs=1, max_seq_len=20, *, contrast=0.5, plausibility=0.1,
                                 suppressor_floor=-20.0, no_repeat_ngram_size=0, min_length=0, banned_words=None,
@@ -741,6 +791,9 @@ class Captioner:
 
     def contrastive_beam_search(self, *a, **k):
         return self.model.contrastive_beam_search(*a, **k)
+
+    def pool_beam_search(self, *a, **k):
+        return self.model.pool_beam_search(*a, **k)
 
     def consensus_caption(self, enc_x, enc_x_num_pads=[0], *, metric="cider", **k):
         """CaptioningModel.consensus_caption with this object's `beam_search_args` (sos_idx, eos_idx, beam_max_seq_len)

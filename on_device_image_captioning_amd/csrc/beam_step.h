@@ -82,9 +82,24 @@ __device__ __forceinline__ bool wave_extract_best(float (&tot)[BEAM_CPL], K (&ke
   return found;
 }
 
+// The arrival of one image's block (one thread): the block that arrives last advances *pos, raises *done when no image
+// has a row still growing, and re-arms the counter.
+__device__ __forceinline__ void beam_arrive(const BeamParams& p, int alive_any, int t) {
+  const int prev = atomicAdd(p.ctr, 1 + (alive_any << 16));
+  if ((prev & 0xffff) == p.n_img - 1) {                 // every block has read *pos before arriving here
+    const int al = (prev >> 16) + alive_any;
+    if (!al) *p.done = 1;
+    *p.pos = t + 1;
+    *p.ctr = 0;
+  }
+}
+
 // s.parent / s.word / s.lp of the k rows are chosen (by wave 0; the barrier is here): new cumulative scores, the in-place
-// permutation, the embedding tail, the per-beam outputs and the arrival counter
-__device__ __forceinline__ void beam_apply(const BeamParams& p, const EmbedArgs& e, BeamShared& s, int b, int t) {
+// permutation, the embedding tail, the per-beam outputs and the arrival counter.  `closing` (pool_beam.hip alone; block
+// uniform): the image ends its search with this step — its rows are written as always but leave with row_valid = 0 and
+// do not count as growing.
+__device__ __forceinline__ void beam_apply(const BeamParams& p, const EmbedArgs& e, BeamShared& s, int b, int t,
+                                           bool closing = false) {
   constexpr int NT = BEAM_NT;
   const int tid = threadIdx.x, k = p.k, T = p.T;
   __syncthreads();
@@ -140,21 +155,13 @@ __device__ __forceinline__ void beam_apply(const BeamParams& p, const EmbedArgs&
     p.cumul[b * k + r] = s.cumul[r];
     p.n_elem[b * k + r] = ne + (pe ? 0 : 1);
     p.has_eos[b * k + r] = (pe || ((long long)s.word[r] == p.eos)) ? 1 : 0;
-    p.row_valid[b * k + r] = pe ? 0 : 1;
+    p.row_valid[b * k + r] = (pe || closing) ? 0 : 1;
     p.next_tok[b * k + r] = (long long)s.word[r];
-    alive = pe ? 0 : 1;
+    alive = (pe || closing) ? 0 : 1;
   }
   if (tid < 64) {
     const int alive_any = __any(alive) ? 1 : 0;         // (k <= 16 lanes of wave 0 carry the flags)
-    if (tid == 0) {
-      const int prev = atomicAdd(p.ctr, 1 + (alive_any << 16));
-      if ((prev & 0xffff) == p.n_img - 1) {             // every block has read *pos before arriving here
-        const int al = (prev >> 16) + alive_any;
-        if (!al) *p.done = 1;
-        *p.pos = t + 1;
-        *p.ctr = 0;
-      }
-    }
+    if (tid == 0) beam_arrive(p, alive_any, t);
   }
 }
 

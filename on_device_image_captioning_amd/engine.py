@@ -632,6 +632,29 @@ class CaptionerEngine:
         ops.stochastic_beam_step(st.cand_val, st.cand_idx, st.cand_pert, st.gscore, st.beam_state, st.n_img, st.beams,
                                  st.T, eos_idx, emb=st.emb)
 
+    def pool_constraints(self, st: DecodeState, eos_idx: int, *, no_repeat_ngram: int = 0, banned=None
+                         ) -> "_hip.SearchConstraints":
+        """The constraints every pooled step selects its candidates under: the search's own n-gram rule
+        and ban list, and EOS inadmissible at every position (min_words = st.T: odic_pool_beam_step offers EOS itself, from
+        the log-prob rows, and applies min_length there) — so a row's candidates are its st.beams best words other than
+        EOS, exactly."""
+        banned = sorted({int(w) for w in (banned or [])})
+        if len(banned) + st.T + st.beams > self.g.vocab_size:
+            raise ValueError(f"{len(banned)} banned words + {st.T} positions + {st.beams} candidates per row exceed the "
+                             f"vocabulary ({self.g.vocab_size} words): a row could run out of admissible words")
+        st.banned = torch.tensor(banned, dtype=torch.int32, device=self.device) if banned else None
+        return ops.search_constraints(st.tokens, st.pos, st.T, eos_idx, row_valid=st.row_valid, banned=st.banned,
+                                      no_repeat_ngram=min(int(no_repeat_ngram), st.T), min_words=st.T)
+
+    def pool_beam_step(self, st: DecodeState, pool: "ops.Pool", eos_idx: int, constraints) -> None:
+        """One full step of pooled beam search, the sibling of beam_step under constraints with the same
+        launches behind the decoder: the top-k launch that writes the log-prob rows, odic_topk_rows_constrained under
+        `constraints` (pool_constraints: never EOS), then odic_pool_beam_step, which offers every row's EOS from the
+        log-prob rows, moves the hypotheses that end to `pool` and keeps st.beams live rows."""
+        self._candidates(st, constraints)
+        ops.pool_beam_step(st.cand_val, st.cand_idx, st.logp, pool.args, st.beam_state, st.n_img, st.beams, st.T, eos_idx,
+                           emb=st.emb)
+
     def contrast_beam_step(self, states, count: torch.Tensor, args: "_hip.ContrastArgs", eos_idx: int,
                            constraints=None) -> None:
         """One full step of contrastive beam search, the sibling of beam_step: states[0] decodes the

@@ -94,6 +94,10 @@ class EsembleCaptioningModel(CaptioningModel):
         raise NotImplementedError("stochastic beam search runs on a single model: call it on one of the ensemble's member "
                                   "models (models_list[i])")
 
+    def pool_beam_search(self, *a, beam_size=3, how_many_outputs=1, length_penalty=1.0, **k):
+        """Refused (search.check_pool_beam): the pooled search runs on a single model."""
+        _search.check_pool_beam(beam_size, how_many_outputs, length_penalty, ensemble=True)
+
     def contrastive_beam_search(self, *a, **k):
         raise NotImplementedError("contrastive beam search runs on a single model: call it on one of the ensemble's member "
                                   "models (models_list[i])")

@@ -1002,6 +1002,70 @@ def stochastic_beam_step(cand_val, cand_idx, cand_pert, gscore, state: "_hip.Bea
                                                          _stream()), "odic_stochastic_beam_step")
 
 
+def pool_scale(T: int, length_penalty: float) -> torch.Tensor:
+    """scale[L] = float32(float64(L) ** length_penalty), L = 0 .. T: the table odic_pool_beam_step divides a hypothesis's sum
+    by (host tensor; the power in float64, then one rounding — the device never calls powf)."""
+    return torch.tensor([float(L) ** float(length_penalty) for L in range(T + 1)], dtype=torch.float64).to(torch.float32)
+
+
+class Pool:
+    """The pool of finished hypotheses of a pooled beam search (odic_pool_args) for n_img images, P = beams slots each and
+    T positions, with its tensors: tokens, logprobs [n_img, P, T]; len, sum, score, serial [n_img, P]; count, closed
+    [n_img]; scale [T + 1]."""
+
+    def __init__(self, n_img: int, beams: int, T: int, length_penalty: float, min_words: int, early_stopping: bool, device):
+        z = lambda dt, *s: torch.zeros(*s, dtype=dt, device=device)      # noqa: E731
+        self.tokens, self.logprobs = z(torch.int64, n_img, beams, T), z(torch.float32, n_img, beams, T)
+        self.len, self.serial = z(torch.int32, n_img, beams), z(torch.int32, n_img, beams)
+        self.sum, self.score = z(torch.float32, n_img, beams), z(torch.float32, n_img, beams)
+        self.count, self.closed = z(torch.int32, n_img), z(torch.int32, n_img)
+        self.scale = pool_scale(T, length_penalty).to(device)
+        self.args = pool_args(self.tokens, self.logprobs, self.len, self.sum, self.score, self.serial, self.count,
+                              self.closed, self.scale, min_words, early_stopping)
+
+
+def pool_args(tokens, logprobs, len_, sum_, score, serial, count, closed, scale, min_words: int,
+              early_stopping: bool) -> "_hip.PoolArgs":
+    """odic_pool_args (the caller keeps the tensors alive)."""
+    _need_cuda(tokens, logprobs, len_, sum_, score, serial, count, closed, scale)
+    for name, t, dt in (("tokens", tokens, torch.int64), ("logprobs", logprobs, torch.float32), ("len", len_, torch.int32),
+                        ("sum", sum_, torch.float32), ("score", score, torch.float32), ("serial", serial, torch.int32),
+                        ("count", count, torch.int32), ("closed", closed, torch.int32), ("scale", scale, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"pool_args: {name} must be a contiguous {dt} tensor")
+    return _hip.PoolArgs(*(_p(t) for t in (tokens, logprobs, len_, sum_, score, serial, count, closed, scale)),
+                         int(min_words), 1 if early_stopping else 0)
+
+
+def pool_reset(pool: "_hip.PoolArgs", n_img: int) -> None:
+    """An empty pool and every image open (odic_pool_reset: count = closed = 0)."""
+    with _timed("beam_reset", 0.0, n_img * 8.0):
+        _hip.check(_hip.load().odic_pool_reset(C.byref(pool), n_img, _stream()), "odic_pool_reset")
+
+
+def pool_beam_step(cand_val, cand_idx, logp, pool: "_hip.PoolArgs", state: "_hip.BeamState", n_img, beams, T, eos_idx,
+                   emb=None) -> None:
+    """The step of pooled beam search (odic_pool_beam_step): cand_* [n_img·beams, beams] hold every row's best words other
+    than EOS, logp fp32 [n_img·beams, V] the log-prob rows they came from (EOS's log-prob is read there); a hypothesis
+    that takes EOS goes to the pool, the rows stay live, an image whose pool cannot be improved closes."""
+    _need_cuda(cand_val, cand_idx, logp)
+    if logp.dtype != torch.float32 or logp.dim() != 2 or logp.stride(1) != 1:
+        raise ValueError("pool_beam_step: logp must be fp32 [N, V] with unit column stride")
+    with _timed("beam_step", 0.0, n_img * beams * (beams * 8.0 + 4.0 + 2 * T * 12.0) + _beam_bytes(n_img, beams, T, emb)):
+        _hip.check(_hip.load().odic_pool_beam_step(_p(cand_val), _p(cand_idx), _p(logp), int(logp.stride(0)), C.byref(pool),
+                                                   C.byref(state), _emb_ref(emb), n_img, beams, T, eos_idx,
+                                                   int(logp.shape[1]), _stream()), "odic_pool_beam_step")
+
+
+def pool_beam_finalize(pool: "_hip.PoolArgs", state: "_hip.BeamState", order, score, n_img, beams, T) -> None:
+    """odic_pool_beam_finalize: the rows an open image still grows join its pool; order int32 / score fp32 [n_img, beams]:
+    the pool's slots best first (-1 / -inf behind the image's count)."""
+    _need_cuda(order, score)
+    with _timed("beam_finalize", 0.0, n_img * beams * (32.0 + 2 * T * 12.0)):
+        _hip.check(_hip.load().odic_pool_beam_finalize(C.byref(pool), C.byref(state), _p(order), _p(score), n_img, beams, T,
+                                                       _stream()), "odic_pool_beam_finalize")
+
+
 def beam_finalize(state: "_hip.BeamState", order, score, n_img, beams) -> None:
     with _timed("beam_finalize", 0.0, n_img * beams * 16.0):
         _hip.check(_hip.load().odic_beam_finalize(C.byref(state), _p(order), _p(score), n_img, beams, _stream()),

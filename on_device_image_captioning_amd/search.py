@@ -2,8 +2,8 @@
 CaptionPipeline: argument rules, mode dispatch, the members of an ensemble on one beam state, and
 run_search — arm, constraints, the step loop with its look at the device's `done` flag, ranking, row pick, read-out — which
 every search method calls with its own way to arm, its step and its rows.  Plain functions over a DecodeState (engine.py);
-the device side of a step is ops.beam_step / ops.group_beam_step / ops.require_beam_step / ops.stochastic_beam_step, four
-rules on one extraction (wave_extract_best, csrc/beam_step.h); contrastive_beam_search changes what
+the device side of a step is ops.beam_step / ops.group_beam_step / ops.require_beam_step / ops.stochastic_beam_step /
+ops.pool_beam_step, five rules on one extraction (wave_extract_best, csrc/beam_step.h); contrastive_beam_search changes what
 ops.beam_step is fed, not the step (ops.contrast_topk).
 """
 from __future__ import annotations
@@ -226,6 +226,35 @@ def check_stochastic_beam(num_samples, *, prefix=None, required_words=None, no_r
     return int(num_samples)
 
 
+MAX_POOL_BEAMS = 15             # odic_pool_beam_step ranks beam_size·(beam_size + 1) candidates, 256 at most
+
+
+def check_pool_beam(beam_size, how_many_outputs, length_penalty, *, prefix=None, required_words=None, sample_or_max="max",
+                    ensemble: bool = False) -> float:
+    """The rules of pool_beam_search → length_penalty as a float.  What the pooled rule has no form for is
+    refused, in the wording of check_stochastic_beam."""
+    where = "in pool_beam_search"
+    tail = "it keeps one pool of finished captions per image beside one deterministic beam of one model"
+    if ensemble:
+        raise ValueError(f"an ensemble is not supported {where}: {tail}")
+    if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= int(beam_size) <= MAX_POOL_BEAMS:
+        raise ValueError(f"beam_size must be an integer in [1, {MAX_POOL_BEAMS}] (the step ranks beam_size·(beam_size + 1) "
+                         f"candidates, 256 at most), not {beam_size!r}")
+    if isinstance(how_many_outputs, bool) or int(how_many_outputs) != how_many_outputs or \
+            not 1 <= int(how_many_outputs) <= int(beam_size):
+        raise ValueError(f"how_many_outputs must be an integer in [1, beam_size] (the pool holds beam_size captions), not "
+                         f"{how_many_outputs!r}")
+    refuse_required_words(required_words, where)
+    if names_a_word(prefix):
+        raise ValueError(f"prefix is not supported {where}: {tail}")
+    if sample_or_max != "max":
+        raise ValueError(f"sample_or_max={sample_or_max!r} is not supported {where}: {tail}")
+    a = float(length_penalty)
+    if not (0.0 <= a < float("inf")):
+        raise ValueError(f"length_penalty must be finite and >= 0 (0 = rank by the sum of log-probs), not {length_penalty!r}")
+    return a
+
+
 MAX_DISTRACTORS = 7             # odic_contrast_topk takes the target's row and seven more
 
 
@@ -306,7 +335,8 @@ def required_outputs(order, cumul, required: List[List[int]], bank_beams: int, h
 
 
 def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
-    """mode='beam_search' | 'sampling' | 'diverse_beam_search' | 'stochastic_beam_search' | 'contrastive_beam_search' with the keys of `args` (a forward(**kwargs) or
+    """mode='beam_search' | 'sampling' | 'diverse_beam_search' | 'stochastic_beam_search' | 'contrastive_beam_search' |
+    'pool_beam_search' with the keys of `args` (a forward(**kwargs) or
     beam_search_args mapping; an absent key takes the reference's default) → the call of the model's method."""
     ends = dict(sos_idx=args.get("sos_idx", -999), eos_idx=args.get("eos_idx", -999))
     cons, flt = _constraint_kwargs(args), _filter_kwargs(args)
@@ -340,6 +370,10 @@ def dispatch(model, mode: str, args, enc_x, enc_x_num_pads):
         knobs = {k: args[k] for k in ("contrast", "plausibility", "suppressor_floor") if k in args}
         return model.contrastive_beam_search(enc_x, enc_x_num_pads, distractors=args.get("distractors", "others"), **beam,
                                              **knobs, **common)
+    if mode == "pool_beam_search":
+        check_sampling_filter(**flt, sampling=False, where="pool_beam_search")
+        knobs = {k: args[k] for k in ("length_penalty", "early_stopping") if k in args}
+        return model.pool_beam_search(enc_x, enc_x_num_pads, **beam, **knobs, **common)
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -380,6 +414,35 @@ def read_captions(state, rows: torch.Tensor, how_many_outputs: int) -> Tuple[Lis
     return res_tok, torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
 
 
+def read_pool(st, pool, how_many_outputs: int, sos_idx: int, eos_idx: int):
+    """odic_pool_beam_finalize on the pool of the search on `st`, then its best hypotheses → (token lists per image and
+    output, log-probs [B, how_many_outputs, longest] zero-padded on the state's device, scores fp32 [B, how_many_outputs],
+    counts int32 [B] — both on the host).  Output j of an image is the j-th best hypothesis of its pool; an image with
+    fewer than how_many_outputs hypotheses (every candidate died) fills the rest with the EMPTY caption [sos, eos], log-probs
+    [0, -inf], score -inf."""
+    B, P, dv = st.n_img, st.beams, st.tokens.device
+    order = torch.empty(B, P, dtype=torch.int32, device=dv)
+    score = torch.empty(B, P, dtype=torch.float32, device=dv)
+    ops.pool_beam_finalize(pool.args, st.beam_state, order, score, B, P, st.T)
+    order_h, len_h, tok_h = order.cpu(), pool.len.cpu(), pool.tokens.cpu()
+    empty_lp = torch.tensor([0.0, float("-inf")], dtype=torch.float32, device=dv)
+    res_tok, lp_rows = [], []
+    for b in range(B):
+        per = []
+        for j in range(how_many_outputs):
+            i = int(order_h[b, j])
+            if i < 0:
+                per.append([int(sos_idx), int(eos_idx)])
+                lp_rows.append(empty_lp)
+                continue
+            n = int(len_h[b, i])
+            per.append(tok_h[b, i, :n].tolist())
+            lp_rows.append(pool.logprobs[b, i, :n])
+        res_tok.append(per)
+    lp = torch.nn.utils.rnn.pad_sequence(lp_rows, batch_first=True).view(B, how_many_outputs, -1)
+    return res_tok, lp, score[:, :how_many_outputs].cpu(), pool.count.cpu()
+
+
 def arm_state(eng, st, sos_idx: int, prefix: Optional[List[List[int]]] = None, *, emb, group_beams: Optional[int] = None,
               seed_prefix: Optional[Callable[[torch.Tensor], None]] = None) -> None:
     """Bring the built (lead) state to its first position, the arm() of every search.  Behind `prefix` (check_prefix's
@@ -407,15 +470,20 @@ def logged(step: Callable[[object], None], st, log: Optional[list], extra: Optio
 
 
 def run_search(eng, st, eos_idx: int, steps: int, how_many_outputs: int, *, arm: Callable[[], None],
-               step: Callable[[object], None], pick: Optional[Callable] = None, constraints: Optional[dict] = None):
+               step: Callable[[object], None], pick: Optional[Callable] = None, constraints: Optional[dict] = None,
+               finish: Optional[Callable[[], tuple]] = None):
     """A whole search on the built (lead) state `st`, once for every search: arm() brings the state to its first position
     (beam_reset, seed_prefix, ensemble_seed_prefix); `constraints` (check_constraints' keywords, or None) become the
     device's on `eng`; step(cons) enqueues one step under them and feeds the caller's log hook, `steps` times at most
     (run_steps); pick(order, score) takes rank_beams' device tensors to the output rows [B, how_many_outputs] (host
-    integers; default: the first of the finalize order).  → read_captions: the log-probs are on the state's device."""
+    integers; default: the first of the finalize order).  → read_captions: the log-probs are on the state's device.
+    `finish` (the pooled search, whose captions do not lie in the beam state): called in place of the ranking and the
+    read-out, → what run_search returns."""
     arm()
     cons = eng.search_constraints(st, eos_idx, **constraints) if constraints else None
     run_steps(st, steps, lambda t: step(cons))
+    if finish is not None:
+        return finish()
     order, score = rank_beams(st)
     return read_captions(st, pick(order, score) if pick else order.cpu()[:, :how_many_outputs], how_many_outputs)
 

@@ -4,7 +4,7 @@ FULL geometry, features-only model, 16 images, fp32, HIP events around the step 
 poll), median and spread over the runs.  The loop is captured into one hipGraph and replayed (as CaptionPipeline runs
 it: the figure is the device's, free of host launch jitter); --eager times the plain enqueue loop instead.
 
-    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 cbeam:3:1 pbeam:3:6 rbeam:3:2 sample:3 sample:3:20:0.9:0.8
+    python3 tools/search_step_bench.py [--runs 7] [--images 16] [--eager] beam:3 beam:9 diverse:3x3 cbeam:3 cbeam:9 cbeam:3:1 pbeam:3:6 rbeam:3:2 sample:3 sample:3:20:0.9:0.8 poolbeam:3
 
 cbeam:K is beam:K under constraints: no_repeat_ngram_size=2, min_length=5 and 8 banned words; the step then
 holds one launch more (odic_topk_rows_constrained) and the top-k launch writes the log-prob rows.
@@ -23,8 +23,14 @@ cbeam:K:D (two numbers) is the step of contrastive_beam_search (DESIGN.md §4.22
 and odic_beam_step.  Compare it with beam:K.  A second line times the row launch alone against the composition the library
 could already form — 1 + D odic_logsoftmax_topk launches that write their log-prob rows, an elementwise combine (torch) and
 odic_topk_rows — on the same logits, alternating the two, HIP events around 200 launches each.
+poolbeam:K is the step of pool_beam_search(beam_size=K): the decoder, the top-k launch that writes the log-prob
+rows, odic_topk_rows_constrained with EOS inadmissible and odic_pool_beam_step, length_penalty 1, no early stopping (the graph
+holds all 19 steps; a closed image's block only arrives).  Compare it with cbeam:K, the same launches with odic_beam_step.  A
+second line counts the steps an eager search runs until the device raises `done` (looked at after every step), with
+early_stopping off and on.
 A form this build does not have (diverse on a build before ABI 25, cbeam before ABI 26, pbeam before seed_prefix, rbeam
-before odic_require_beam_step, sbeam before odic_stochastic_beam_step) is reported as absent.
+before odic_require_beam_step, sbeam before odic_stochastic_beam_step, poolbeam before odic_pool_beam_step) is reported as
+absent.
 """
 import argparse
 import math
@@ -101,6 +107,11 @@ def main():
                 continue
             R = int(shape) + 1
             one = lambda st: eng.stochastic_beam_step(st, bench.EOS, 7)            # noqa: E731
+        elif kind == "poolbeam":
+            if not hasattr(eng, "pool_beam_step"):
+                print(f"{form}: not in this build")
+                continue
+            R = int(shape)
         elif kind == "cbeam" and ":" in shape:
             shape, D = shape.split(":")
             R, D = int(shape), int(D)
@@ -126,6 +137,11 @@ def main():
             cons = eng.search_constraints(st, bench.EOS, no_repeat_ngram=2, min_words=5,
                                           banned=[w for w in range(100, 110) if w not in (bench.SOS, bench.EOS)][:8])
             one = lambda st: eng.beam_step(st, bench.EOS, constraints=cons)        # noqa: E731
+        pool = None
+        if kind == "poolbeam":
+            pool = ops.Pool(a.images, R, T, 1.0, 0, False, dev)
+            pcons = eng.pool_constraints(st, bench.EOS)
+            one = lambda st: eng.pool_beam_step(st, pool, bench.EOS, pcons)        # noqa: E731
         if kind == "contrast":
             from on_device_image_captioning_amd import search as _search
             states = [st]
@@ -143,6 +159,8 @@ def main():
                 eng.seed_prefix(st, prefix, bench.SOS)
             else:
                 ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=None if kind in ("sample", "contrast") else st.emb)
+            if pool is not None:
+                ops.pool_reset(pool.args, a.images)
             for _ in range(steps - P):
                 one(st)
 
@@ -169,6 +187,19 @@ def main():
               f"{statistics.median(times) * steps:.0f} us", flush=True)
         if kind == "contrast":
             rows_alone(ops, states, count, cargs, R, form)
+        if kind == "poolbeam":
+            ran = {}
+            for early in (False, True):
+                pool = ops.Pool(a.images, R, T, 1.0, 0, early, dev)
+                ops.beam_reset(st.beam_state, a.images, R, T, bench.SOS, emb=st.emb)
+                ops.pool_reset(pool.args, a.images)
+                n = 0
+                while n < steps and not int(st.done.item()):
+                    one(st)
+                    n += 1
+                ran[early] = (n, int((pool.closed != 0).sum().item()))
+            print(f"{form} steps until done (eager, of {steps}): early_stopping off {ran[False][0]} ({ran[False][1]} of {a.images} images "
+                  f"closed), on {ran[True][0]} ({ran[True][1]} closed)", flush=True)
 
 
 def rows_alone(ops, states, count, cargs, k, form, reps=200, rounds=5):
