@@ -69,7 +69,7 @@ extern "C" {
  *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
  *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
- *       odic_lcs_pairs, odic_orient_rgb8. */
+ *       odic_lcs_pairs, odic_orient_rgb8, odic_jpeg4_workspace_bytes, odic_jpeg4_decode, odic_cmyk_to_rgb8. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -359,6 +359,51 @@ int odic_jpeg_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_by
  * containment are those of odic_jpeg_decode.  ODIC_ENULL for a null scale_log2. */
 int odic_jpeg_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace, size_t ws_bytes,
                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Four-component baseline files (CMYK and YCCK: print workflows, Photoshop), bit-exact with
+ * np.asarray(PIL.Image.open(f).convert("RGB")).  jpeg.parse(..., "convert", cmyk="device") admits 8-bit SOF0/SOF1 Huffman
+ * frames with one interleaved scan of the four components in frame order, component 0 at 1x1, 2x1 or 2x2, each of
+ * components 1..3 at 1x1 or at component 0's sampling, and at most 10 blocks per MCU (libjpeg's limit).  The record has
+ * odic_jpeg_header's offset and size fields with the same meaning (mcus_x = ceil(W / (8 h[0])), mcus_y =
+ * ceil(H / (8 v[0])); restart in MCUs), and instead of `sampling`:
+ *   h / v        sampling factors of each component.  An MCU holds h[c]·v[c] blocks of component c, row by row, in
+ *                component order; the planes follow each other in component order from plane_off, plane c being
+ *                mcus_x·8·h[c] wide and mcus_y·8·v[c] high (64 bytes per block in all)
+ *   ycck         1: Adobe transform 2, components 0..2 are YCbCr of the complemented C, M, Y (libjpeg's
+ *                ycck_cmyk_convert); 0: the components are C, M, Y, K as stored (transform 0 or no Adobe marker)
+ *   qt           quantisation table of each component, natural order
+ *   lut/maxcode/valoff/huffval  tables 0-3: DC of components 0-3, 4-7: their AC, in odic_jpeg_header's form
+ * Every sub-sampled component, K included, is upsampled with libjpeg's fancy h2v1 / h2v2 filters; every sample is then
+ * complemented (Pillow reads all four-layer JPEGs as "CMYK;I") and the pixel goes through Pillow's CMYK → RGB.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct odic_jpeg_header4 {
+  int64_t data_off, data_end, out_off, scan_off, coef_off, plane_off;
+  int32_t int_off, unit_off, width, height;
+  int32_t ycck;
+  int32_t mcus_x, mcus_y, restart, n_intervals, n_units;
+  int32_t h[4], v[4];
+  uint16_t qt[4][64];
+  uint16_t lut[8][512];
+  int32_t maxcode[8][18];
+  int32_t valoff[8][18];
+  uint8_t huffval[8][256];
+} odic_jpeg_header4;                /* 12024 bytes */
+
+/* odic_jpeg_workspace_bytes / odic_jpeg_decode for a batch whose `headers` are odic_jpeg_header4 [n_images]: the same
+ * descriptor, launches, workspace layout, status rule and contract (all launches on `stream`, no allocation, no host
+ * synchronisation; at most the queried workspace bytes are touched, and exactly the images' H·W·3 bytes of `out` and
+ * n_images entries of `status` are written — test_jpeg4_decode_stays_inside_its_workspace).  An out_off that is a
+ * multiple of 4 lets the colour kernel store whole words. */
+size_t odic_jpeg4_workspace_bytes(const odic_jpeg_batch* batch);
+int odic_jpeg4_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
+
+/* The last stage of that decode on its own: n_pixels interleaved C, M, Y, K bytes (DEVICE pointers) → interleaved RGB,
+ * as Pillow's convert("RGB") of a CMYK image: per channel x with nk = 255 - K, t = x·nk + 128,
+ * out = clip(nk - (((t >> 8) + t) >> 8), 0, 255).  invert != 0: every input sample is first replaced by 255 - x (the
+ * "CMYK;I" unpacking of a JPEG).  n_pixels == 0 launches nothing.  ODIC_ENULL for a null pointer, ODIC_EINVAL for a
+ * negative n_pixels. */
+int odic_cmyk_to_rgb8(const uint8_t* cmyk, uint8_t* rgb, int64_t n_pixels, int invert, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Progressive files (8-bit SOF2 Huffman, 3 YCbCr components, the samplings above — sampling 3 included: one component,

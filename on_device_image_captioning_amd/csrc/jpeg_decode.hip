@@ -37,15 +37,26 @@
 // One-component (grayscale) frames, sampling = 3, take the same launches in the same batch: one block per MCU in
 // block-raster order, tables 0 / 3, one plane, and a colour pass that writes R = G = B = Y (Pillow's L → RGB).
 //
+// Four-component frames (CMYK / YCCK, odic_jpeg4_decode) have a record of their own, odic_jpeg_header4: every
+// component with its own sampling, four quantisation and eight Huffman tables.  The launches up to the coefficients are
+// the same kernels, templates over the header type (Frame<Header>: blocks per MCU and the component of each block); the
+// IDCT writes four planes and jpeg_color4_kernel upsamples each, then applies YCCK → CMYK, Pillow's inversion and
+// Pillow's CMYK → RGB: np.asarray(PIL.Image.open(f).convert("RGB")).  Full size only.
+//
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
 // whose coefficients leave the range where libjpeg-turbo's SIMD and C IDCTs agree (kIdctLimit), gets status 1:
 // the caller decodes it again on the host.  Entropy data that does decode yields libjpeg's coefficients exactly.
+#include <type_traits>
+
 #include "odic_common.h"
 
 static_assert(sizeof(odic_jpeg_header) == 9016 && offsetof(odic_jpeg_header, qt) == 88 &&
                   offsetof(odic_jpeg_header, huffval) == 7480,
               "odic_jpeg_header layout is mirrored by jpeg.HEADER_DTYPE");
+static_assert(sizeof(odic_jpeg_header4) == 12024 && offsetof(odic_jpeg_header4, h) == 88 &&
+                  offsetof(odic_jpeg_header4, qt) == 120 && offsetof(odic_jpeg_header4, huffval) == 9976,
+              "odic_jpeg_header4 layout is mirrored by jpeg.HEADER4_DTYPE");
 
 namespace {
 
@@ -155,6 +166,38 @@ __device__ __forceinline__ int luma_blocks(int sampling) {
 __device__ __forceinline__ int luma_h(int sampling) { return sampling == 0 || sampling == kGray ? 1 : 2; }
 __device__ __forceinline__ int luma_v(int sampling) { return sampling == 2 ? 2 : 1; }
 
+// What the entropy kernels need of a frame: the blocks of an MCU and the component of each, which is also its Huffman
+// table pair (DC table c, AC table kComps + c) and its DC predictor.  Three-component and gray frames derive both from
+// `sampling`; a four-component frame (odic_jpeg_header4) carries the sampling of every component, and the map from a
+// block of the MCU to its component is packed from the record, two bits per block (at most 10 blocks).
+constexpr int kMaxMcuBlocks4 = 10;                 // libjpeg's D_MAX_BLOCKS_IN_MCU
+template <typename Header>
+struct Frame;
+template <>
+struct Frame<odic_jpeg_header> {
+  static constexpr int kComps = 3;
+  int nY, bpm;
+  __device__ explicit Frame(const odic_jpeg_header& h)
+      : nY(luma_blocks(h.sampling)), bpm(blocks_per_mcu(h.sampling)) {}
+  __device__ __forceinline__ int comp(int blk) const { return blk < nY ? 0 : blk - nY + 1; }
+};
+template <>
+struct Frame<odic_jpeg_header4> {
+  static constexpr int kComps = 4;
+  unsigned map;
+  int bpm;
+  __device__ explicit Frame(const odic_jpeg_header4& h) : map(0), bpm(0) {
+    for (int c = 0; c < 4; ++c) {                    // the parser admits h, v in 1..2 and at most 10 blocks; the clamps
+      const int n = min(max(h.h[c] * h.v[c], 1), 4);  // only keep a record that breaks the rule inside the map
+      for (int j = 0; j < n && bpm < kMaxMcuBlocks4; ++j) map |= (unsigned)c << (2 * bpm++);
+    }
+  }
+  __device__ __forceinline__ int comp(int blk) const { return (map >> (2 * blk)) & 3; }
+};
+__device__ __forceinline__ int mcu_blocks(const odic_jpeg_header4& h) { return Frame<odic_jpeg_header4>(h).bpm; }
+template <typename Header>
+__device__ __forceinline__ int mcu_blocks(const Header& h) { return blocks_per_mcu(h.sampling); }
+
 // ---------------------------------------------------------------------------------------------------------------
 // segment: one workgroup of 256 lanes per image, 16 bytes per lane per 4 KiB tile
 // ---------------------------------------------------------------------------------------------------------------
@@ -255,10 +298,11 @@ __device__ int segment_bytes(const unsigned char* __restrict__ src, const long l
   return err;
 }
 
-__global__ __launch_bounds__(256) void jpeg_segment_kernel(const odic_jpeg_header* __restrict__ hdrs,
+template <typename Header>                                      // odic_jpeg_header or odic_jpeg_header4
+__global__ __launch_bounds__(256) void jpeg_segment_kernel(const Header* __restrict__ hdrs,
                                                            const unsigned char* __restrict__ data, Ws ws,
                                                            int subseq_bits) {
-  const odic_jpeg_header& h = hdrs[blockIdx.x];
+  const Header& h = hdrs[blockIdx.x];
   const int t = threadIdx.x;
   int* ib = ws.int_bits + h.int_off;
   int* us = ws.unit_start + h.int_off;
@@ -290,17 +334,20 @@ __global__ __launch_bounds__(256) void jpeg_segment_kernel(const odic_jpeg_heade
 // ---------------------------------------------------------------------------------------------------------------
 // Huffman decoding, shared by the speculative, sync, write-out and serial kernels
 // ---------------------------------------------------------------------------------------------------------------
+template <int kTables>             // 6 (three components: DC 0..2, AC 3..5) or 8 (four: DC 0..3, AC 4..7)
 struct Tabs {
-  unsigned short lut[6 * 512];
-  int lim[6 * 8];                  // [l - 9]: one past the last code of length <= l, left-justified to 16 bits
-  int maxcode[6 * 18];
-  int valoff[6 * 18];
-  unsigned char huffval[6 * 256];
+  unsigned short lut[kTables * 512];
+  int lim[kTables * 8];            // [l - 9]: one past the last code of length <= l, left-justified to 16 bits
+  int maxcode[kTables * 18];
+  int valoff[kTables * 18];
+  unsigned char huffval[kTables * 256];
   unsigned char natural[64];
 };
+template <typename Header>
+using TabsOf = Tabs<2 * Frame<Header>::kComps>;
 
 // canonical codes: the codes of length l, left-justified, end where those of l + 1 begin → lim[] of table `tab` (Tabs:
-// one of six; PTab: tab = 0)
+// one of six or eight; PTab: tab = 0)
 __device__ __forceinline__ void fill_lim(const int* maxcode, int* lim, int tab) {
   int last = 0;
   for (int l = 1; l <= 16; ++l) {
@@ -310,16 +357,17 @@ __device__ __forceinline__ void fill_lim(const int* maxcode, int* lim, int tab) 
   }
 }
 
-__device__ void load_tabs(const odic_jpeg_header& h, Tabs& T) {
+template <typename Header, int kTables>
+__device__ void load_tabs(const Header& h, Tabs<kTables>& T) {
   const int t = threadIdx.x;
-  for (int i = t; i < 6 * 512; i += blockDim.x) T.lut[i] = (&h.lut[0][0])[i];
-  for (int i = t; i < 6 * 18; i += blockDim.x) {
+  for (int i = t; i < kTables * 512; i += blockDim.x) T.lut[i] = (&h.lut[0][0])[i];
+  for (int i = t; i < kTables * 18; i += blockDim.x) {
     T.maxcode[i] = (&h.maxcode[0][0])[i];
     T.valoff[i] = (&h.valoff[0][0])[i];
   }
-  for (int i = t; i < 6 * 256; i += blockDim.x) T.huffval[i] = (&h.huffval[0][0])[i];
+  for (int i = t; i < kTables * 256; i += blockDim.x) T.huffval[i] = (&h.huffval[0][0])[i];
   for (int i = t; i < 64; i += blockDim.x) T.natural[i] = kNatural[i];
-  if (t < 6) fill_lim(&h.maxcode[0][0], T.lim, t);
+  if (t < kTables) fill_lim(&h.maxcode[0][0], T.lim, t);
   __syncthreads();
 }
 
@@ -359,7 +407,7 @@ __device__ __forceinline__ unsigned bits_peek(Bits& b, int pos) {      // the 32
   return (unsigned)(x >> (32 - (pos & 31)));
 }
 
-template <typename Tab>          // Tabs: six tables, `tab` picks one; PTab (the progressive path): one table, tab = 0
+template <typename Tab>          // Tabs: six or eight tables, `tab` picks one; PTab (the progressive path): one table, tab = 0
 __device__ __forceinline__ int huff(const Tab& T, int tab, unsigned win, int& len) {
   const unsigned e = T.lut[tab * 512 + (win >> (32 - kLutBits))];
   if (e) {
@@ -382,9 +430,10 @@ __device__ __forceinline__ int extend(unsigned bits, int s) {    // HUFF_EXTEND
 }
 
 // One symbol at s.pos.  zz = zig-zag index written (-1: none), val its value.  Returns false on an invalid code.
-__device__ __forceinline__ bool step(const Tabs& T, Bits& br, St& s, int nY, int bpm, int& zz, int& val) {
+template <typename F>            // F: the Frame of the header type
+__device__ __forceinline__ bool step(const Tabs<2 * F::kComps>& T, Bits& br, St& s, const F& f, int& zz, int& val) {
   const unsigned win = bits_peek(br, s.pos);
-  const int comp = s.blk < nY ? 0 : s.blk - nY + 1;
+  const int comp = f.comp(s.blk);
   int len;
   if (s.k == 0) {
     const int cat = huff(T, comp, win, len);
@@ -395,7 +444,7 @@ __device__ __forceinline__ bool step(const Tabs& T, Bits& br, St& s, int nY, int
     s.k = 1;
     return true;
   }
-  const int rs = huff(T, 3 + comp, win, len);
+  const int rs = huff(T, F::kComps + comp, win, len);
   if (rs < 0) return false;
   const int r = rs >> 4, c = rs & 15;
   if (c) {
@@ -411,20 +460,22 @@ __device__ __forceinline__ bool step(const Tabs& T, Bits& br, St& s, int nY, int
   }
   if (s.k >= 64) {
     s.k = 0;
-    s.blk = s.blk + 1 == bpm ? 0 : s.blk + 1;
+    s.blk = s.blk + 1 == f.bpm ? 0 : s.blk + 1;
   }
   return true;
 }
 
 // decode [s.pos, end) counting the blocks begun; an invalid code ends the span with pos = kInvalidPos
-__device__ int4 decode_span(const Tabs& T, const unsigned* __restrict__ w, int off, St s, int end, int nY, int bpm) {
+template <typename F>
+__device__ int4 decode_span(const Tabs<2 * F::kComps>& T, const unsigned* __restrict__ w, int off, St s, int end,
+                            const F& f) {
   int count = 0;
   Bits br{w, off};
   if (s.pos < end) bits_seek(br, s.pos);
   while (s.pos < end) {
     count += s.k == 0;
     int zz, val;
-    if (!step(T, br, s, nY, bpm, zz, val)) {
+    if (!step(T, br, s, f, zz, val)) {
       s = St{kInvalidPos, 0, 0};
       break;
     }
@@ -484,12 +535,13 @@ __device__ int stage_units(const unsigned* __restrict__ gw, unsigned* sdata, boo
   return w_lo;
 }
 
-__global__ __launch_bounds__(kUnitLanes) void jpeg_sync_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws, int S,
+template <typename Header>
+__global__ __launch_bounds__(kUnitLanes) void jpeg_sync_kernel(const Header* __restrict__ hdrs, Ws ws, int S,
                                                         int pass) {
   if (pass >= 2 && ws.flags[pass] == 0) return;                // pass - 1 changed nothing: converged
-  __shared__ Tabs T;
+  __shared__ TabsOf<Header> T;
   const int img = blockIdx.y;
-  const odic_jpeg_header& h = hdrs[img];
+  const Header& h = hdrs[img];
   if (blockIdx.x * kUnitLanes >= h.n_units) return;
   if (pass >= 1 && threadIdx.x == 0) atomicMax(&ws.flags[0], pass);
   load_tabs(h, T);
@@ -500,14 +552,14 @@ __global__ __launch_bounds__(kUnitLanes) void jpeg_sync_kernel(const odic_jpeg_h
   extern __shared__ unsigned sdata[];
   const int off = stage_units((const unsigned*)(ws.scan + h.scan_off), sdata, valid, U.start, U.end);
   if (!valid) return;
-  const int sampling = h.sampling, nY = luma_blocks(sampling), bpm = blocks_per_mcu(sampling);
+  const Frame<Header> f(h);
   int4* out = ws.est[pass & 1] + h.unit_off;
   St s{U.start, 0, 0};
   if (pass >= 1 && U.u != U.first) {
     const int4 p = ws.est[(pass - 1) & 1][h.unit_off + U.u - 1];
     s = St{p.x, p.y, p.z};
   }
-  const int4 e = decode_span(T, sdata, off, s, U.end, nY, bpm);
+  const int4 e = decode_span(T, sdata, off, s, U.end, f);
   if (pass >= 1) {
     const int4 old = ws.est[(pass - 1) & 1][h.unit_off + U.u];
     if (old.x != e.x || old.y != e.y || old.z != e.z || old.w != e.w) {
@@ -519,14 +571,16 @@ __global__ __launch_bounds__(kUnitLanes) void jpeg_sync_kernel(const odic_jpeg_h
 }
 
 // an interval's end states are exact once a pass changed none of them, or after jpeg_serial_kernel walked it (-1)
-__device__ __forceinline__ bool converged(const Ws& ws, const odic_jpeg_header& h, int k) {
+template <typename Header>
+__device__ __forceinline__ bool converged(const Ws& ws, const Header& h, int k) {
   const int ran = ws.flags[0], last = ws.last_change[h.int_off + k];
   return last < 0 || (ran >= 1 && last < ran);
 }
 
 // per image: exclusive prefix of the blocks begun per unit (final pass buffer)
-__global__ __launch_bounds__(256) void jpeg_block_scan_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
-  const odic_jpeg_header& h = hdrs[blockIdx.x];
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_block_scan_kernel(const Header* __restrict__ hdrs, Ws ws) {
+  const Header& h = hdrs[blockIdx.x];
   __shared__ int sh[256];
   const int n = ws.unit_start[h.int_off + h.n_intervals];
   const int4* e = ws.est[ws.flags[0] & 1] + h.unit_off;
@@ -542,15 +596,16 @@ __global__ __launch_bounds__(256) void jpeg_block_scan_kernel(const odic_jpeg_he
 }
 
 // decode from s to `end` (or the interval's last block) writing coefficients; bcur = block in progress (local)
-__device__ void write_span(const Tabs& T, const unsigned* __restrict__ w, int off, St s, int bcur, int end,
-                           int int_end, int nblk, short* __restrict__ coef, int nY, int bpm, int* state) {
+template <typename F>
+__device__ void write_span(const Tabs<2 * F::kComps>& T, const unsigned* __restrict__ w, int off, St s, int bcur, int end,
+                           int int_end, int nblk, short* __restrict__ coef, const F& f, int* state) {
   Bits br{w, off};
   if (s.pos < end) bits_seek(br, s.pos);
   while (s.pos < end) {
     const int nb = s.k == 0 ? bcur + 1 : bcur;
     if (nb >= nblk) return;                                   // past the interval's last block: padding
     int zz, val;
-    if (nb < 0 || !step(T, br, s, nY, bpm, zz, val) || zz > 63) {   // zz > 63: libjpeg would clobber coef 63
+    if (nb < 0 || !step(T, br, s, f, zz, val) || zz > 63) {   // zz > 63: libjpeg would clobber coef 63
       atomicOr(&state[0], kErrDecode);
       return;
     }
@@ -565,15 +620,17 @@ __device__ void write_span(const Tabs& T, const unsigned* __restrict__ w, int of
   // the unit's bits are used up; the interval's completion is counted by the unit that finishes it
 }
 
-__device__ __forceinline__ int interval_blocks(const odic_jpeg_header& h, int k, int bpm) {
+template <typename Header>
+__device__ __forceinline__ int interval_blocks(const Header& h, int k, int bpm) {
   const int nmcu = h.mcus_x * h.mcus_y;
   return min(h.restart, nmcu - k * h.restart) * bpm;
 }
 
-__global__ __launch_bounds__(kUnitLanes) void jpeg_writeout_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws, int S) {
-  __shared__ Tabs T;
+template <typename Header>
+__global__ __launch_bounds__(kUnitLanes) void jpeg_writeout_kernel(const Header* __restrict__ hdrs, Ws ws, int S) {
+  __shared__ TabsOf<Header> T;
   const int img = blockIdx.y;
-  const odic_jpeg_header& h = hdrs[img];
+  const Header& h = hdrs[img];
   if (blockIdx.x * kUnitLanes >= h.n_units) return;
   load_tabs(h, T);
   const int* us = ws.unit_start + h.int_off;
@@ -583,7 +640,8 @@ __global__ __launch_bounds__(kUnitLanes) void jpeg_writeout_kernel(const odic_jp
   extern __shared__ unsigned sdata[];
   const int off = stage_units((const unsigned*)(ws.scan + h.scan_off), sdata, valid, U.start, U.end);
   if (!valid) return;
-  const int sampling = h.sampling, nY = luma_blocks(sampling), bpm = blocks_per_mcu(sampling);
+  const Frame<Header> f(h);
+  const int bpm = f.bpm;
   St s{U.start, 0, 0};
   if (U.u != U.first) {
     const int4 p = ws.est[ws.flags[0] & 1][h.unit_off + U.u - 1];
@@ -592,7 +650,7 @@ __global__ __launch_bounds__(kUnitLanes) void jpeg_writeout_kernel(const odic_jp
   const int* uf = ws.unit_first + h.unit_off;
   const int bcur = uf[U.u] - uf[U.first] - 1;
   short* coef = ws.coef + (h.coef_off + (long)U.k * h.restart * bpm) * 64;
-  write_span(T, sdata, off, s, bcur, U.end, U.int_end, interval_blocks(h, U.k, bpm), coef, nY, bpm,
+  write_span(T, sdata, off, s, bcur, U.end, U.int_end, interval_blocks(h, U.k, bpm), coef, f,
              ws.state + kStateWords * img);
 }
 
@@ -600,10 +658,11 @@ __global__ __launch_bounds__(kUnitLanes) void jpeg_writeout_kernel(const odic_jp
 // start state in the last pass equals the walker's state kept a correct end state and is stepped over; any other unit
 // is decoded again from the walker's state.  The wave loads 64 units' states at a time and broadcasts them; all lanes
 // decode redundantly (same state, same addresses).  With max_sync_passes = 0 this is a serial decode of each interval.
-__global__ __launch_bounds__(64) void jpeg_serial_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws, int S) {
-  __shared__ Tabs T;
+template <typename Header>
+__global__ __launch_bounds__(64) void jpeg_serial_kernel(const Header* __restrict__ hdrs, Ws ws, int S) {
+  __shared__ TabsOf<Header> T;
   const int img = blockIdx.y, k = blockIdx.x;
-  const odic_jpeg_header& h = hdrs[img];
+  const Header& h = hdrs[img];
   if (k >= h.n_intervals || converged(ws, h, k)) return;
   load_tabs(h, T);
   const int* ib = ws.int_bits + h.int_off;
@@ -612,7 +671,7 @@ __global__ __launch_bounds__(64) void jpeg_serial_kernel(const odic_jpeg_header*
   int4* cur = ws.est[ran & 1] + h.unit_off;
   const int4* prev = ws.est[(ran - 1) & 1] + h.unit_off;
   const unsigned* w = (const unsigned*)(ws.scan + h.scan_off);
-  const int sampling = h.sampling, nY = luma_blocks(sampling), bpm = blocks_per_mcu(sampling);
+  const Frame<Header> f(h);
   const int lane = threadIdx.x, u_end = us[k + 1];
   St s{ib[k], 0, 0};
   for (int u0 = us[k]; u0 < u_end; u0 += 64) {
@@ -629,7 +688,7 @@ __global__ __launch_bounds__(64) void jpeg_serial_kernel(const odic_jpeg_header*
         s = St{ep, eb, ek};
       } else {
         const int start = ib[k] + (u0 + j - us[k]) * S;
-        const int4 d = decode_span(T, w, 0, s, min(start + S, ib[k + 1]), nY, bpm);
+        const int4 d = decode_span(T, w, 0, s, min(start + S, ib[k + 1]), f);
         if (lane == 0) cur[u0 + j] = d;
         s = St{d.x, d.y, d.z};
       }
@@ -639,50 +698,53 @@ __global__ __launch_bounds__(64) void jpeg_serial_kernel(const odic_jpeg_header*
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// DC prediction: per image, one lane per MCU, a segmented scan of the three components' differences
+// DC prediction: per image, one lane per MCU, a segmented scan of the components' differences (three or four)
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void jpeg_dc_kernel(const odic_jpeg_header* __restrict__ hdrs, Ws ws) {
-  const odic_jpeg_header& h = hdrs[blockIdx.x];
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_dc_kernel(const Header* __restrict__ hdrs, Ws ws) {
+  const Header& h = hdrs[blockIdx.x];
   const int t = threadIdx.x;
-  const int nY = luma_blocks(h.sampling), bpm = blocks_per_mcu(h.sampling);   // gray: one predictor, j < nY throughout
+  constexpr int kC = Frame<Header>::kComps;
+  const Frame<Header> fr(h);                                 // gray: one predictor, every block is component 0
+  const int bpm = fr.bpm;
   const int nmcu = h.mcus_x * h.mcus_y, R = h.restart;
   short* coef = ws.coef + h.coef_off * 64;
-  __shared__ int sv[3][256];
+  __shared__ int sv[kC][256];
   __shared__ int sf[256];
-  int carry[3] = {0, 0, 0};
+  int carry[kC] = {};
   for (int m0 = 0; m0 < nmcu; m0 += 256) {
     const int m = m0 + t;
-    int own[3] = {0, 0, 0};
+    int own[kC] = {};
     if (m < nmcu) {
-      for (int j = 0; j < bpm; ++j) own[j < nY ? 0 : j - nY + 1] += coef[((long)m * bpm + j) * 64];
+      for (int j = 0; j < bpm; ++j) own[fr.comp(j)] += coef[((long)m * bpm + j) * 64];
     }
     int f = m % R == 0;
-    int v[3];
-    for (int c = 0; c < 3; ++c) v[c] = own[c] + (t == 0 && !f ? carry[c] : 0);
+    int v[kC];
+    for (int c = 0; c < kC; ++c) v[c] = own[c] + (t == 0 && !f ? carry[c] : 0);
     for (int off = 1; off < 256; off <<= 1) {
-      for (int c = 0; c < 3; ++c) sv[c][t] = v[c];
+      for (int c = 0; c < kC; ++c) sv[c][t] = v[c];
       sf[t] = f;
       __syncthreads();
       if (t >= off && !f) {
-        for (int c = 0; c < 3; ++c) v[c] += sv[c][t - off];
+        for (int c = 0; c < kC; ++c) v[c] += sv[c][t - off];
         f = sf[t - off];
       }
       __syncthreads();
     }
     if (m < nmcu) {
-      int run[3];
-      for (int c = 0; c < 3; ++c) run[c] = v[c] - own[c];
+      int run[kC];
+      for (int c = 0; c < kC; ++c) run[c] = v[c] - own[c];
       for (int j = 0; j < bpm; ++j) {
-        const int c = j < nY ? 0 : j - nY + 1;
+        const int c = fr.comp(j);
         short* p = &coef[((long)m * bpm + j) * 64];
         run[c] += *p;
         if (run[c] < -32768 || run[c] > 32767) atomicOr(&ws.state[kStateWords * blockIdx.x], kErrRange);
         *p = (short)run[c];                                  // JCOEF is a short
       }
     }
-    for (int c = 0; c < 3; ++c) sv[c][t] = v[c];
+    for (int c = 0; c < kC; ++c) sv[c][t] = v[c];
     __syncthreads();
-    for (int c = 0; c < 3; ++c) carry[c] = sv[c][255];
+    for (int c = 0; c < kC; ++c) carry[c] = sv[c][255];
     __syncthreads();
   }
 }
@@ -758,6 +820,45 @@ __device__ __forceinline__ bool idct_reads(int n, int i) {
   return n == 8 || (n == 4 ? i != 4 : (n == 2 ? (i < 2 || (i & 1)) : i == 0));
 }
 
+// Where block j of an MCU goes: its component, the transform size n, the component's blocks per MCU across and down
+// (hc, vc), the block's place among them (jx, jy) and the byte offset of the component's plane.  Every plane is
+// mcus_x·n·hc wide and mcus_y·n·vc high, padded to whole MCUs.
+struct BlockGeo {
+  int comp, n, hc, vc, jx, jy;
+  long plane;
+};
+// three components or gray: component 0 at the luma sampling with transform size ny, the others 1x1 with size nc
+template <typename Header>
+__device__ __forceinline__ BlockGeo block_geo(const Header& h, int j, int ny, int nc) {
+  const int nY = luma_blocks(h.sampling), hy = luma_h(h.sampling), vy = luma_v(h.sampling);
+  BlockGeo g;
+  g.comp = j < nY ? 0 : j - nY + 1;
+  if (g.comp == 0) {
+    g.n = ny; g.hc = hy; g.vc = vy; g.jx = j % hy; g.jy = j / hy; g.plane = 0;
+  } else {
+    const long ysz = (long)h.mcus_x * ny * hy * h.mcus_y * ny * vy, csz = (long)h.mcus_x * nc * h.mcus_y * nc;
+    g.n = nc; g.hc = 1; g.vc = 1; g.jx = 0; g.jy = 0; g.plane = ysz + (g.comp - 1) * csz;
+  }
+  return g;
+}
+// four components, each with its own sampling, full size only: the planes follow each other in component order
+__device__ __forceinline__ long plane_bytes4(const odic_jpeg_header4& h, int c) {
+  return (long)h.mcus_x * 8 * h.h[c] * h.mcus_y * 8 * h.v[c];
+}
+__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j, int, int) {
+  BlockGeo g{3, 8, h.h[3], h.v[3], 0, 0, 0};
+  for (int c = 0; c < 4; ++c) {
+    const int nb = h.h[c] * h.v[c];
+    if (j < nb || c == 3) {
+      g.comp = c; g.hc = h.h[c]; g.vc = h.v[c]; g.jx = j % g.hc; g.jy = min(j / g.hc, g.vc - 1);
+      break;
+    }
+    j -= nb;
+    g.plane += plane_bytes4(h, c);
+  }
+  return g;
+}
+
 // One block per 8 lanes: column pass → LDS → row pass, n×n samples into the component's plane.  kScaled = false is
 // the full-size decode (lg = 0, n = 8 throughout, the branches below fold away).  A scaled image's planes keep the
 // full-size order (Y, Cb, Cr from plane_off) with every block n wide and high.  The range rule of kIdctLimit holds for
@@ -765,17 +866,17 @@ __device__ __forceinline__ bool idct_reads(int n, int i) {
 // only the input and the result).  libjpeg-turbo's SIMD 4x4 / 2x2 keep the same 16-bit intermediates as its 8x8.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int img, int lg, int (*ws8)[8][9]) {
-  const int nY = luma_blocks(h.sampling), bpm = blocks_per_mcu(h.sampling);   // gray: every block is component 0
+  const int bpm = mcu_blocks(h);                              // gray: every block is component 0
   const long nblocks = (long)h.mcus_x * h.mcus_y * bpm;
   const long b = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
   const int lane = threadIdx.x & 7, slot = threadIdx.x >> 3;
   if ((long)blockIdx.x * 32 >= nblocks) return;
   const bool live = b < nblocks;
   const int j = (int)(live ? b % bpm : 0);
-  const int comp = j < nY ? 0 : j - nY + 1;
   int ny = 8, nc = 8;
-  if (kScaled) scaled_sizes(h.sampling, lg, ny, nc);
-  const int n = comp == 0 ? ny : nc;
+  if constexpr (kScaled) scaled_sizes(h.sampling, lg, ny, nc);
+  const BlockGeo g = block_geo(h, j, ny, nc);
+  const int comp = g.comp, n = g.n;
   bool outside = false;                                       // a value where libjpeg-turbo's SIMD and C IDCTs part
   if (live && idct_reads(n, lane)) {                          // column `lane`
     const short* c = ws.coef + (h.coef_off + b) * 64;
@@ -815,17 +916,8 @@ __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int i
   if (lane >= n) return;
   const long mcu = b / bpm;
   const int mx = (int)(mcu % h.mcus_x), my = (int)(mcu / h.mcus_x);
-  const int hy = luma_h(h.sampling), vy = luma_v(h.sampling);
-  int bx = mx, by = my, pw = h.mcus_x * nc;
-  unsigned char* plane = ws.planes + h.plane_off;
-  const long ysz = (long)h.mcus_x * ny * hy * h.mcus_y * ny * vy, csz = (long)h.mcus_x * nc * h.mcus_y * nc;
-  if (comp == 0) {
-    bx = mx * hy + j % hy;
-    by = my * vy + j / hy;
-    pw = h.mcus_x * ny * hy;
-  } else {
-    plane += ysz + (comp - 1) * csz;
-  }
+  const int bx = mx * g.hc + g.jx, by = my * g.vc + g.jy, pw = h.mcus_x * n * g.hc;
+  unsigned char* plane = ws.planes + h.plane_off + g.plane;
   unsigned char* row = plane + (long)(by * n + lane) * pw + bx * n;
   if (n == 8) {
     uint2 v;
@@ -866,6 +958,25 @@ constexpr int kCrR = 91881, kCbB = 116130, kCrG = 46802, kCbG = 22554;   // FIX(
 
 __device__ __forceinline__ unsigned char clamp255(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
+// jdsample.c: one sample of a plane with half the output's width (and, v2, half its height) at output pixel (x, y).
+// dw, dh: the plane's own width and height in samples (the clamp at the image's edges); plain: replication in both
+// directions instead of the triangle filters h2v1_fancy_upsample / h2v2_fancy_upsample.
+__device__ __forceinline__ int upsampled(const unsigned char* __restrict__ P, int cw, int x, int y, bool v2, bool plain,
+                                         int dw, int dh) {
+  const int c = x >> 1, odd = x & 1;
+  const int cn = odd ? min(c + 1, dw - 1) : max(c - 1, 0);
+  if (plain) return P[(long)(v2 ? y >> 1 : y) * cw + c];
+  if (!v2) {
+    const long r = (long)y * cw;
+    return (3 * P[r + c] + P[r + cn] + 1 + odd) >> 2;
+  }
+  const int rr = y >> 1;
+  const int rn = (y & 1) ? min(rr + 1, dh - 1) : max(rr - 1, 0);
+  const long r0 = (long)rr * cw, r1 = (long)rn * cw;
+  const int s0 = 3 * P[r0 + c] + P[r1 + c], s1 = 3 * P[r0 + cn] + P[r1 + cn];
+  return (3 * s0 + s1 + 8 - odd) >> 4;
+}
+
 // One output pixel.  kScaled = false is the full-size decode (lg = 0).  At scale 1 / 2^lg the output is
 // ceil(W / 2^lg) × ceil(H / 2^lg) and the planes hold the transform sizes of scaled_sizes(): 4:4:4 and, for lg > 0,
 // 4:2:0 read chroma on the luma grid; 4:2:2 upsamples horizontally (jdsample.c): fancy while the chroma transform is
@@ -902,26 +1013,11 @@ __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int i
     cr = Cr[(long)y * cw + x];
   } else {
     const int dw = kScaled ? (h.width * nc + 15) >> 4 : (W + 1) >> 1;      // the same number at lg = 0
-    const int c = x >> 1, odd = x & 1;
-    const int cn = odd ? min(c + 1, dw - 1) : max(c - 1, 0);
-    if (dw <= 2 || (kScaled && nc == 1)) {                  // jdsample.c: h2v1_upsample / h2v2_upsample, no filter in
-      const long r = (long)(sampling == 2 ? y >> 1 : y) * cw;   // either direction (a frame at most 4 pixels wide)
-      cb = Cb[r + c];
-      cr = Cr[r + c];
-    } else if (sampling == 1) {
-      const long r = (long)y * cw;
-      cb = (3 * Cb[r + c] + Cb[r + cn] + 1 + odd) >> 2;
-      cr = (3 * Cr[r + c] + Cr[r + cn] + 1 + odd) >> 2;
-    } else {
-      const int dh = (H + 1) >> 1;
-      const int rr = y >> 1;
-      const int rn = (y & 1) ? min(rr + 1, dh - 1) : max(rr - 1, 0);
-      const long r0 = (long)rr * cw, r1 = (long)rn * cw;
-      const int cbs0 = 3 * Cb[r0 + c] + Cb[r1 + c], cbs1 = 3 * Cb[r0 + cn] + Cb[r1 + cn];
-      const int crs0 = 3 * Cr[r0 + c] + Cr[r1 + c], crs1 = 3 * Cr[r0 + cn] + Cr[r1 + cn];
-      cb = (3 * cbs0 + cbs1 + 8 - odd) >> 4;
-      cr = (3 * crs0 + crs1 + 8 - odd) >> 4;
-    }
+    // jdsample.c: h2v1_upsample / h2v2_upsample, no filter in either direction, for chroma at most two samples wide
+    // (a frame at most 4 pixels wide) or a 1x1 chroma transform
+    const bool plain = dw <= 2 || (kScaled && nc == 1);
+    cb = upsampled(Cb, cw, x, y, sampling == 2, plain, dw, (H + 1) >> 1);
+    cr = upsampled(Cr, cw, x, y, sampling == 2, plain, dw, (H + 1) >> 1);
   }
   cb -= 128;
   cr -= 128;
@@ -947,6 +1043,102 @@ __global__ __launch_bounds__(256) void jpeg_color_scaled_kernel(const Header* __
     return;
   }
   color_pixel<true>(hdrs[img], ws, img, lg, out, status);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Four-component frames (odic_jpeg_header4): what Image.open(f).convert("RGB") makes of a CMYK / YCCK file.
+//   jdcolor.c ycck_cmyk_convert (Adobe transform 2): C, M, Y = 255 - (R, G, B) of the table-driven YCbCr→RGB above,
+//       K as stored; other files hold C, M, Y, K as stored
+//   Pillow's unpacker "CMYK;I", which JpegImagePlugin picks for every four-layer file: each sample becomes 255 - x
+//   Pillow's Convert.c cmyk2rgb: per channel x with nk = 255 - K, t = x·nk + 128, out = clip(nk - (((t >> 8) + t) >> 8))
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cmyk_pixel_rgb(int c, int m, int y, int k, int invert, unsigned char* __restrict__ o) {
+  if (invert) {
+    c = 255 - c; m = 255 - m; y = 255 - y; k = 255 - k;
+  }
+  const int nk = 255 - k;
+  const int v[3] = {c, m, y};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int t = v[i] * nk + 128;
+    o[i] = clamp255(nk - (((t >> 8) + t) >> 8));
+  }
+}
+
+// n <= 4 pixels (3 n bytes) to o: three 32-bit stores where there are four pixels and o is 4-aligned, else bytes
+__device__ __forceinline__ void store_rgb4(unsigned char* __restrict__ o, const unsigned char* px, int n) {
+  if (n == 4 && ((size_t)o & 3) == 0) {
+    unsigned* q = (unsigned*)o;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) q[i] = px[4 * i] | px[4 * i + 1] << 8 | px[4 * i + 2] << 16 | (unsigned)px[4 * i + 3] << 24;
+  } else {
+    for (int i = 0; i < 3 * n; ++i) o[i] = px[i];
+  }
+}
+
+constexpr int kColor4Pixels = 4;                   // pixels per lane of the two kernels below
+
+__global__ __launch_bounds__(256) void cmyk_to_rgb8_kernel(const unsigned char* __restrict__ cmyk,
+                                                           unsigned char* __restrict__ rgb, long n_pixels, int invert) {
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
+  if (p0 >= n_pixels) return;
+  const int n = (int)min((long)kColor4Pixels, n_pixels - p0);
+  unsigned char in[4 * kColor4Pixels], px[3 * kColor4Pixels];
+  const unsigned char* src = cmyk + 4 * p0;
+  if (n == kColor4Pixels && ((size_t)src & 15) == 0) {
+    *(uint4*)in = *(const uint4*)src;
+  } else {
+    for (int i = 0; i < 4 * n; ++i) in[i] = src[i];
+  }
+  for (int i = 0; i < n; ++i) cmyk_pixel_rgb(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3], invert, px + 3 * i);
+  store_rgb4(rgb + 3 * p0, px, n);
+}
+
+// Four consecutive pixels of the image's H·W per lane: every component is read at its own sampling (a component at
+// component 0's sampling lies on the output grid, a 1x1 one under 2x1 / 2x2 is upsampled as chroma is above, K
+// included), then the chain of the comment above; plus the per-image status.
+__global__ __launch_bounds__(256) void jpeg_color4_kernel(const odic_jpeg_header4* __restrict__ hdrs, Ws ws,
+                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
+  const int img = blockIdx.y;
+  const odic_jpeg_header4& h = hdrs[img];
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
+  if (p0 == 0) {
+    const int* st = ws.state + kStateWords * img;
+    status[img] = (st[0] == 0 && st[1] == h.n_intervals) ? 0 : 1;
+  }
+  const int W = h.width, H = h.height;
+  const long npix = (long)W * H;
+  if (p0 >= npix) return;
+  const int n = (int)min((long)kColor4Pixels, npix - p0);
+  const unsigned char* P[4];
+  int pw[4];
+  bool full[4];
+  const unsigned char* base = ws.planes + h.plane_off;
+  for (int c = 0; c < 4; ++c) {
+    P[c] = base;
+    pw[c] = h.mcus_x * 8 * h.h[c];
+    full[c] = h.h[c] == h.h[0] && h.v[c] == h.v[0];
+    base += plane_bytes4(h, c);
+  }
+  const bool v2 = h.v[0] == 2;
+  const int dw = (W + 1) >> 1, dh = (H + 1) >> 1;
+  unsigned char px[3 * kColor4Pixels];
+  for (int i = 0; i < n; ++i) {
+    const long p = p0 + i;
+    const int y = (int)(p / W), x = (int)(p - (long)y * W);
+    int s[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      s[c] = full[c] ? P[c][(long)y * pw[c] + x] : upsampled(P[c], pw[c], x, y, v2, dw <= 2, dw, dh);
+    if (h.ycck) {
+      const int cb = s[1] - 128, cr = s[2] - 128, yv = s[0];
+      s[0] = 255 - clamp255(yv + ((kCrR * cr + 32768) >> 16));
+      s[1] = 255 - clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
+      s[2] = 255 - clamp255(yv + ((kCbB * cb + 32768) >> 16));
+    }
+    cmyk_pixel_rgb(s[0], s[1], s[2], s[3], 1, px + 3 * i);
+  }
+  store_rgb4(out + h.out_off + 3 * p0, px, n);
 }
 
 
@@ -1308,6 +1500,8 @@ void launch_idct_color(const Batch* b, const Header* hdrs, const Ws& ws, const i
   }
 }
 
+// Header: odic_jpeg_header (three components or gray) or odic_jpeg_header4 (four; full size only)
+template <typename Header>
 int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream,
                     const int32_t* scale_log2) {
   if (!b || !b->headers || !b->data || !b->out || !b->status || !workspace) return ODIC_ENULL;
@@ -1320,21 +1514,29 @@ int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, 
   const Layout L = layout(*b);
   const Ws ws = bind(workspace, L);
   hipStream_t s = (hipStream_t)stream;
-  const auto* hdrs = (const odic_jpeg_header*)b->headers;
+  const auto* hdrs = (const Header*)b->headers;
   const int n = b->n_images, S = b->subseq_bits;
   hipError_t e = hipMemsetAsync(workspace, 0, L.scan, s);                 // state, flags, last_change
   if (e == hipSuccess) e = hipMemsetAsync(ws.coef, 0, L.planes - L.coef, s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(jpeg_segment_kernel, dim3(n), dim3(256), 0, s, hdrs, b->data, ws, S);
+  hipLaunchKernelGGL(jpeg_segment_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, b->data, ws, S);
   const dim3 ugrid((b->max_units + kUnitLanes - 1) / kUnitLanes, n);
   const size_t lds = sizeof(unsigned) * stage_words(S);
   for (int p = 0; p <= b->max_sync_passes; ++p)                          // pass 0: speculative
-    hipLaunchKernelGGL(jpeg_sync_kernel, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S, p);
-  hipLaunchKernelGGL(jpeg_serial_kernel, dim3(b->max_intervals, n), dim3(64), 0, s, hdrs, ws, S);
-  hipLaunchKernelGGL(jpeg_block_scan_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
-  hipLaunchKernelGGL(jpeg_writeout_kernel, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
-  hipLaunchKernelGGL(jpeg_dc_kernel, dim3(n), dim3(256), 0, s, hdrs, ws);
-  launch_idct_color(b, hdrs, ws, scale_log2, s);
+    hipLaunchKernelGGL(jpeg_sync_kernel<Header>, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S, p);
+  hipLaunchKernelGGL(jpeg_serial_kernel<Header>, dim3(b->max_intervals, n), dim3(64), 0, s, hdrs, ws, S);
+  hipLaunchKernelGGL(jpeg_block_scan_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
+  hipLaunchKernelGGL(jpeg_writeout_kernel<Header>, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
+  hipLaunchKernelGGL(jpeg_dc_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
+  if constexpr (std::is_same<Header, odic_jpeg_header4>::value) {
+    const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
+    hipLaunchKernelGGL(jpeg_idct_kernel<Header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs,
+                       ws);
+    hipLaunchKernelGGL(jpeg_color4_kernel, dim3((unsigned)((lanes + 255) / 256), n), dim3(256), 0, s, hdrs, ws, b->out,
+                       b->status);
+  } else {
+    launch_idct_color(b, hdrs, ws, scale_log2, s);
+  }
   return odic_launch_status();
 }
 
@@ -1365,13 +1567,29 @@ int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws
 }  // namespace
 
 extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
-  return decode_baseline(b, workspace, ws_bytes, stream, nullptr);
+  return decode_baseline<odic_jpeg_header>(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" size_t odic_jpeg4_workspace_bytes(const odic_jpeg_batch* b) { return odic_jpeg_workspace_bytes(b); }
+
+extern "C" int odic_jpeg4_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
+  return decode_baseline<odic_jpeg_header4>(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" int odic_cmyk_to_rgb8(const uint8_t* cmyk, uint8_t* rgb, int64_t n_pixels, int invert, void* stream) {
+  if (!cmyk || !rgb) return ODIC_ENULL;
+  const int64_t blocks = (n_pixels + 256 * kColor4Pixels - 1) / (256 * kColor4Pixels);
+  if (n_pixels < 0 || blocks > 0x7fffffffL) return ODIC_EINVAL;
+  if (n_pixels == 0) return 0;
+  hipLaunchKernelGGL(cmyk_to_rgb8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, cmyk, rgb,
+                     (long)n_pixels, invert);
+  return odic_launch_status();
 }
 
 extern "C" int odic_jpeg_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
                                        size_t ws_bytes, void* stream) {
   if (!scale_log2) return ODIC_ENULL;
-  return decode_baseline(b, workspace, ws_bytes, stream, scale_log2);
+  return decode_baseline<odic_jpeg_header>(b, workspace, ws_bytes, stream, scale_log2);
 }
 
 extern "C" size_t odic_jpeg_progressive_workspace_bytes(const odic_jpeg_prog_batch* b) {

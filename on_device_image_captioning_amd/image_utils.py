@@ -42,7 +42,9 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # in the DCT domain, as `PIL.Image.draft` does, on either path and bit-exact between them.  Non-RGB files are a black
 # canvas as in the reference, or with `non_rgb="convert"` what `convert("RGB")` makes of them: grayscale JPEGs on the
 # device, the other modes by PIL.  With `orientation="exif"` every image is turned upright as `ImageOps.exif_transpose`
-# does: device-decoded files by one odic_orient_rgb8 launch (csrc/orient.hip), PIL-decoded ones by PIL.
+# does: device-decoded files by one odic_orient_rgb8 launch (csrc/orient.hip), PIL-decoded ones by PIL.  With
+# `cmyk="device"` (and `non_rgb="convert"`) baseline CMYK / YCCK JPEGs are decoded and converted on the device too
+# (odic_jpeg4_decode) instead of leaving the batch for PIL.
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -228,7 +230,7 @@ class DevicePreprocessor:
         return out
 
     def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None,
-                   non_rgb: str = "black", orientation: str = "ignore") -> torch.Tensor:
+                   non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host") -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
         the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
         non_rgb="convert": a file of any other mode (L, LA, P, RGBA, I;16, CMYK, ...) is read as
@@ -243,11 +245,17 @@ class DevicePreprocessor:
         orientation="exif": every file, of any format, is turned upright by its EXIF Orientation tag as
         `ImageOps.exif_transpose` does, after the draft and the non-RGB rule (the black canvas has the transposed size),
         for either value of `decode` (torch.equal between them); region boxes are in oriented coordinates.  The default
-        "ignore" reads the stored pixel grid, as the reference does."""
-        from .jpeg import check_non_rgb, check_orientation
+        "ignore" reads the stored pixel grid, as the reference does.
+        cmyk="device" (needs non_rgb="convert"): with decode="device" it is passed on to `from_jpeg_bytes`, where
+        baseline CMYK / YCCK JPEGs are decoded on the device (not under a draft request: there are no draft scales for
+        four components); decode="host" ignores it.  The tensor is the same either way."""
+        from .jpeg import check_cmyk, check_non_rgb, check_orientation
         check_non_rgb(non_rgb)
         check_orientation(orientation)
+        check_cmyk(cmyk, non_rgb)
         exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's calls stay as they are
+        if cmyk != "host":
+            exif["cmyk"] = cmyk
         if decode == "device":
             blobs = []
             for p in paths:
@@ -256,6 +264,7 @@ class DevicePreprocessor:
             return self.from_jpeg_bytes(blobs, draft=draft, regions=regions, non_rgb=non_rgb, **exif)
         if decode != "host":
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
+        exif.pop("cmyk", None)
         arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None, non_rgb, **exif) for p in paths]
         if regions is None:
             return self(arrays)
@@ -307,7 +316,8 @@ class DevicePreprocessor:
     @property
     def last_routes(self):
         """How each file of the last `decode_jpeg` / `from_jpeg_bytes` call was decoded, in input order: "device" (baseline,
-        odic_jpeg_decode), "device-progressive" (odic_jpeg_decode_progressive), "host" (PIL: a kind the device does not
+        odic_jpeg_decode), "device-progressive" (odic_jpeg_decode_progressive), "device-cmyk" (four components,
+        odic_jpeg4_decode), "host" (PIL: a kind the device does not
         take), "host-after-status" (the device reported status 1 and PIL decoded the file again) or "black"."""
         return tuple(self._jpeg_routes)
 
@@ -318,7 +328,7 @@ class DevicePreprocessor:
         return tuple(self._jpeg_orientations)
 
     def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host",
-                    draft=None, non_rgb: str = "black", orientation: str = "ignore"):
+                    draft=None, non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host"):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
         np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path; with
         non_rgb="convert" each equals np.asarray(PIL.Image.open(f).convert("RGB")) instead: one-component JPEGs take the
@@ -336,19 +346,26 @@ class DevicePreprocessor:
         image the rules above describe (after the draft and the non-RGB rule: a black canvas has the transposed size),
         in the oriented shape.  Files decoded on the device are permuted there by one odic_orient_rgb8 launch into one
         new buffer, files PIL decodes by PIL; the routes are the same as without it.  `last_orientations` reports the
-        value applied to each file (`jpeg.exif_orientation`)."""
+        value applied to each file (`jpeg.exif_orientation`).
+        cmyk="device" (needs non_rgb="convert"; the default "host" leaves them to PIL until the device route is
+        measured): baseline four-component JPEGs — CMYK, or YCCK by Adobe transform 2 — that
+        `jpeg.parse` admits are decoded by one odic_jpeg4_decode call in the same upload and status read-back, route
+        "device-cmyk", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  Progressive four-component files
+        stay with PIL, and so do all of them under a draft request: there are no draft scales for this layout."""
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
         J.check_non_rgb(non_rgb)
         J.check_orientation(orientation)
+        J.check_cmyk(cmyk, non_rgb)
         opt = () if non_rgb == "black" else (non_rgb,)                   # the default's calls stay as they are
+        copt = {"cmyk": cmyk} if cmyk != "host" and draft is None else {}
         if draft is not None:
             draft = (int(draft[0]), int(draft[1]))
             if draft[0] <= 0 or draft[1] <= 0:
                 raise ValueError(f"draft wants a positive (width, height), not {draft!r}")
         blobs = [bytes(b) for b in blobs]
-        hdrs = [J.parse(b, *opt) for b in blobs]
+        hdrs = [J.parse(b, *opt, **copt) for b in blobs]
         exif = orientation != "ignore"
         turns = [J.header_orientation(h, b) if exif else 1 for h, b in zip(hdrs, blobs)]
         host_kw = {"orientation": orientation} if exif else {}           # the default's calls stay as they are
@@ -365,16 +382,21 @@ class DevicePreprocessor:
         # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
         dev = [i for i, h in enumerate(hdrs)
                if h.kind == J.DEVICE and sizes[i][0] * sizes[i][1] * 3 <= self.max_bytes]
-        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader)]
+        four = [i for i in dev if hdrs[i].ncomp == 4]
+        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader) and hdrs[i].ncomp != 4]
         prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader)]
         routes = ["host" if h.kind == J.DEVICE else h.kind for h in hdrs]        # a device kind left so is oversized
         for i in dev:
             routes[i] = "device-progressive" if isinstance(hdrs[i], J.ProgHeader) else "device"
+        for i in four:
+            routes[i] = "device-cmyk"
         if dev:
-            order = base + prog
+            order = base + prog + four
+            group4 = ([hdrs[i] for i in four], [blobs[i] for i in four]) if four else ()   # without: today's call
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
                                                            [hdrs[i] for i in prog], [blobs[i] for i in prog],
-                                                           subseq_bits, max_sync_passes, [scales[i] for i in order])
+                                                           subseq_bits, max_sync_passes,
+                                                           [scales[i] for i in base + prog], *group4)
             turned = []                                                  # (image, its offset in rgb): to be permuted
             for k, i in enumerate(order):
                 if status[k] != 0:
@@ -422,22 +444,31 @@ class DevicePreprocessor:
             w, h = oriented_size(sizes[i], turns[i])
             out[i] = dst[int(r["dst_off"]):int(r["dst_off"]) + w * h * 3].view(h, w, 3)
 
-    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales):
-        """One odic_jpeg_decode call for the baseline files and one odic_jpeg_decode_progressive call for the progressive
-        ones, sharing one upload, one output buffer, one workspace and one status read-back → (status numpy int32 —
-        baseline files first —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
+    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales, chdrs=(), cblobs=()):
+        """One odic_jpeg_decode call for the baseline files, one odic_jpeg_decode_progressive call for the progressive
+        ones and one odic_jpeg4_decode call for the four-component ones (chdrs, cblobs), sharing one upload, one output
+        buffer, one workspace and one status read-back → (status numpy int32 — baseline files first, four-component
+        last —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
         baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales uploaded
         beside the headers.  This is the GPU half: `jpeg.plan_device_batch` lays the upload and the output out."""
         from . import jpeg as J
-        nb, npg = len(hdrs), len(phdrs)
-        plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales)
+        nb, npg, ncm = len(hdrs), len(phdrs), len(chdrs)
+        group4 = (chdrs, cblobs) if ncm else ()
+        plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, *group4)
+        n_all = nb + npg + ncm
         self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
         self._jpeg_pinned = self._grow(self._jpeg_pinned, plan.total, pin_memory=True)
-        self._jpeg_status = self._grow(self._jpeg_status, 4 * (nb + npg), pin_memory=True)
+        self._jpeg_status = self._grow(self._jpeg_status, 4 * n_all, pin_memory=True)
         plan.fill(self._jpeg_pinned.numpy())
-        rgb = torch.empty(max(plan.out_bytes + plan.pout_bytes, 1), dtype=torch.uint8, device=self.device)
-        status = torch.empty(nb + npg, dtype=torch.int32, device=self.device)
-        need_b = need_p = 0
+        out_total = plan.cout_off + plan.cout_bytes if ncm else plan.out_bytes + plan.pout_bytes
+        rgb = torch.empty(max(out_total, 1), dtype=torch.uint8, device=self.device)
+        status = torch.empty(n_all, dtype=torch.int32, device=self.device)
+        need_b = need_p = need_c = 0
+        if ncm:
+            cb = self._hip.JpegBatch()
+            cb.n_images, cb.subseq_bits, cb.max_sync_passes = ncm, subseq_bits, max_sync_passes
+            self._set_fields(cb, plan.ctot)
+            need_c = self.lib.odic_jpeg4_workspace_bytes(ctypes.byref(cb))
         if nb:
             b = self._hip.JpegBatch()
             b.n_images, b.subseq_bits, b.max_sync_passes = nb, subseq_bits, max_sync_passes
@@ -453,7 +484,7 @@ class DevicePreprocessor:
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             self._jpeg_dev = self._grow(self._jpeg_dev, plan.total, device=self.device)
-            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p), device=self.device)
+            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p, need_c), device=self.device)
             self._jpeg_dev[:plan.total].copy_(self._jpeg_pinned[:plan.total], non_blocking=True)
             self._jpeg_ev.record(self.stream)
             base = self._jpeg_dev.data_ptr()
@@ -468,13 +499,18 @@ class DevicePreprocessor:
             if nb:
                 b.headers, b.data, b.out, b.status = base, base + plan.data_off, rgb.data_ptr(), status.data_ptr()
                 decode("odic_jpeg_decode", b, need_b, 0)
-            if npg:                                                      # second: its coefficients stay in the workspace
+            if ncm:
+                cb.headers, cb.data = base + plan.cmyk_off, base + plan.data_off
+                cb.out, cb.status = rgb.data_ptr() + plan.cout_off, status.data_ptr() + 4 * (nb + npg)
+                self._hip.check(self.lib.odic_jpeg4_decode(ctypes.byref(cb), self._jpeg_ws.data_ptr(), need_c,
+                                                           self.stream.cuda_stream), "odic_jpeg4_decode")
+            if npg:                                                      # last: its coefficients stay in the workspace
                 pb.headers, pb.scans, pb.tables = (base + o for o in plan.prog_off)
                 pb.data, pb.out = base + plan.data_off, rgb.data_ptr() + plan.out_bytes
                 pb.status = status.data_ptr() + 4 * nb
                 decode("odic_jpeg_decode_progressive", pb, need_p, nb)
                 self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(pb)), plan.coef_off)
-            st = self._jpeg_status[:4 * (nb + npg)].view(torch.int32)
+            st = self._jpeg_status[:4 * n_all].view(torch.int32)
             st.copy_(status, non_blocking=True)
         self.stream.synchronize()                                        # the one host synchronisation
         torch.cuda.current_stream().wait_stream(self.stream)
@@ -489,14 +525,17 @@ class DevicePreprocessor:
 
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
                         progressive: str = "host", draft: bool = False, regions=None,
-                        non_rgb: str = "black", orientation: str = "ignore") -> torch.Tensor:
+                        non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host") -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
         torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`,
         the same `non_rgb` and the same `orientation`).
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` on the
         decoded images instead; with draft=True the boxes are in the coordinates of the drafted image, with
-        orientation="exif" in those of the upright one."""
+        orientation="exif" in those of the upright one.  cmyk: as `decode_jpeg` (with draft=True four-component files
+        stay on the host route)."""
         exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's call stays as it is
+        if cmyk != "host":
+            exif["cmyk"] = cmyk
         imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
                                 draft=(self.S, self.S) if draft else None, non_rgb=non_rgb, **exif)
         if regions is not None:

@@ -22,7 +22,10 @@ That is the default, non_rgb="black".  Under non_rgb="convert" every file is to 
 `np.asarray(PIL.Image.open(f).convert("RGB"))` and nothing is `black`: a one-component frame (baseline here, SOF2 in
 `parse_progressive`) is a `device` kind with sampling GRAY — one 8x8 block per MCU in block-raster order, whatever
 sampling factors and component id the SOF declares, which libjpeg ignores for a single component — and a four-component
-frame is `host`, where PIL converts it.
+frame is `host`, where PIL converts it — unless the caller also passes cmyk="device": then a baseline four-component frame
+(CMYK, or YCCK by Adobe transform 2) that `_frame4` admits is a `device` kind with ncomp 4, the sampling of every
+component in comp_hv and the `ycck` flag; odic_jpeg4_decode reads its records (`HEADER4_DTYPE`).  Progressive
+four-component files, and all of them under a draft request, stay `host`.
 
 `parse` keeps that sorting.  For the files it turns away with reason "SOF2", `parse_progressive` (below) reads the whole
 scan script, locating every scan's end in the file, and packs the records odic_jpeg_decode_progressive reads.
@@ -54,6 +57,19 @@ def check_non_rgb(non_rgb):
         raise ValueError(f"non_rgb must be 'black' or 'convert', not {non_rgb!r}")
     return non_rgb
 
+
+CMYK = ("host", "device")                             # who decodes a four-component JPEG under non_rgb="convert"
+MAX_MCU_BLOCKS = 10                                   # libjpeg's D_MAX_BLOCKS_IN_MCU
+
+
+def check_cmyk(cmyk, non_rgb):
+    if cmyk not in CMYK:
+        raise ValueError(f"cmyk must be 'host' or 'device', not {cmyk!r}")
+    if cmyk == "device" and non_rgb != "convert":
+        raise ValueError("cmyk='device' decodes four-component files to their RGB conversion: it needs "
+                         "non_rgb='convert' (under non_rgb='black' they are black canvases)")
+    return cmyk
+
 # odic_jpeg_header (include/odic_hip.h), field for field
 HEADER_DTYPE = np.dtype([
     ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
@@ -62,6 +78,16 @@ HEADER_DTYPE = np.dtype([
     ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart", "<i4"), ("n_intervals", "<i4"), ("n_units", "<i4"),
     ("qt", "<u2", (3, 64)), ("lut", "<u2", (6, 512)), ("maxcode", "<i4", (6, 18)), ("valoff", "<i4", (6, 18)),
     ("huffval", "u1", (6, 256)),
+], align=True)
+# odic_jpeg_header4 (include/odic_hip.h), field for field: four components, each with its own sampling
+HEADER4_DTYPE = np.dtype([
+    ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
+    ("plane_off", "<i8"),
+    ("int_off", "<i4"), ("unit_off", "<i4"), ("width", "<i4"), ("height", "<i4"), ("ycck", "<i4"),
+    ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart", "<i4"), ("n_intervals", "<i4"), ("n_units", "<i4"),
+    ("h", "<i4", (4,)), ("v", "<i4", (4,)),
+    ("qt", "<u2", (4, 64)), ("lut", "<u2", (8, 512)), ("maxcode", "<i4", (8, 18)), ("valoff", "<i4", (8, 18)),
+    ("huffval", "u1", (8, 256)),
 ], align=True)
 
 
@@ -86,6 +112,7 @@ class JpegHeader:
     restart_interval: int = 0                            # DRI value (0: none)
     data_offset: int = 0                                 # first byte of the entropy-coded data
     reason: str = ""
+    ycck: bool = False                                   # four components: Adobe transform 2 (YCCK), else CMYK as stored
     app1: list = field(default=None, compare=False, repr=False)     # APP1 payloads ahead of the first SOS, where the
                                                                      # walk got that far (`header_orientation`)
 
@@ -108,13 +135,17 @@ def _u16(b, i):
     return (b[i] << 8) | b[i + 1]
 
 
-def parse(blob, non_rgb: str = "black") -> JpegHeader:
+def parse(blob, non_rgb: str = "black", cmyk: str = "host") -> JpegHeader:
     """Walk the markers of one file up to SOS → JpegHeader with its kind; never raises on a file's content.
     non_rgb="convert": a one-component frame is a device kind (sampling GRAY) and a four-component one goes to the
-    host, where PIL converts it; the default "black" sorts both as BLACK."""
+    host, where PIL converts it; the default "black" sorts both as BLACK.
+    cmyk="device" (with non_rgb="convert" only): a baseline four-component frame that `_frame4` admits is a device
+    kind with ncomp 4, comp_hv and `ycck`; progressive four-component files stay HOST, with a reason of their own.
+    Draft scales do not exist for this layout: a caller with a draft request leaves cmyk at "host"."""
     check_non_rgb(non_rgb)
+    check_cmyk(cmyk, non_rgb)
     try:
-        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob, non_rgb)
+        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob, non_rgb, cmyk)
     except _Bad as e:
         return JpegHeader(HOST, reason=str(e))
     except (IndexError, ValueError) as e:
@@ -238,7 +269,36 @@ class _Walker:
                 raise _Bad(f"marker {m:02X}")
 
 
-def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black"):
+def _frame4(w, header):
+    """The four-component half of `_frame` for cmyk="device", by libjpeg's rules (jdapimin.c default_decompress_parms,
+    jdinput.c): the colour space comes from the Adobe marker alone — transform 2 is YCCK, transform 0 and no Adobe
+    marker (a JFIF marker does not matter) are CMYK; any other transform makes libjpeg warn and guess, which is the
+    host's.  Component 0 carries the MCU's size; every other component is 1x1 or shares it."""
+    m, _, height, width, _, comps = w.sof
+    if m == 0xC2:
+        raise _Bad("4 components, progressive (SOF2)")
+    if width == 0 or height == 0:
+        raise _Bad("DNL / empty frame")
+    t = w.adobe_transform if w.adobe else 0
+    if t not in (0, 2):
+        raise _Bad(f"4 components with Adobe transform {t}")
+    ids = [c[0] for c in comps]
+    if len(set(ids)) != 4:
+        raise _Bad("duplicate component ids")
+    hv = [(c[1], c[2]) for c in comps]
+    if hv[0] not in SAMPLING or any(x != (1, 1) and x != hv[0] for x in hv[1:]):
+        raise _Bad(f"sampling {hv}")
+    blocks = sum(h * v for h, v in hv)
+    if blocks > MAX_MCU_BLOCKS:
+        raise _Bad(f"{blocks} blocks per MCU")
+    for c in comps:
+        if c[3] not in w.qt:
+            raise _Bad("missing DQT")
+    return header(DEVICE, width=width, height=height, ncomp=4, comp_ids=ids, comp_hv=hv,
+                  qtables=[w.qt[c[3]] for c in comps], ycck=t == 2)
+
+
+def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black", cmyk="host"):
     """What the frame admits, by libjpeg's rules, at the first SOS → header(BLACK) or header(DEVICE) with the frame
     fields; anything else raises.  sof_kinds: {C0, C1} for `parse`, {C2} for `parse_progressive`."""
     if w.sof is None:
@@ -254,7 +314,9 @@ def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black"):
             raise _Bad("empty frame")
         return header(BLACK, width=width, height=height, ncomp=nc)
     if nc == 4 and m in (0xC0, 0xC1, 0xC2):           # non_rgb="convert": Adobe inversion, YCCK and PIL's CMYK → RGB are
-        raise _Bad("4 components (CMYK / YCCK)")      # the host's, whichever parser asks
+        if cmyk == "device":                          # the host's, whichever parser asks, unless `parse` was told
+            return _frame4(w, header)                 # cmyk="device"
+        raise _Bad("4 components (CMYK / YCCK)")
     if m not in sof_kinds:
         raise _Bad(f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
@@ -287,14 +349,15 @@ def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black"):
                   qtables=[w.qt[c[3]] for c in comps])
 
 
-def _parse(b, non_rgb="black") -> JpegHeader:
+def _parse(b, non_rgb="black", cmyk="host") -> JpegHeader:
     w = _Walker(b)
     s = next(w.scans(script=False))                   # the first SOS; whatever keeps the walk from it raises
-    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False, non_rgb=non_rgb)
+    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False, non_rgb=non_rgb, cmyk=cmyk)
     hd.app1 = w.app1
     if hd.kind != DEVICE:
         return hd
-    # SOS: one baseline scan of all the frame's components (three interleaved, or the one of a gray frame), in frame order
+    # SOS: one baseline scan of all the frame's components (three or four interleaved, or the one of a gray frame), in
+    # frame order
     ns = s[0] if len(s) >= 1 else 0
     if ns != hd.ncomp or len(s) != 1 + 2 * ns + 3:
         raise _Bad("not one interleaved scan")
@@ -527,9 +590,14 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
         raise ValueError(f"scale must be 1, 2, 4 or 8, not {scale!r}")
     width, height = scaled_size((h.width, h.height), scale)
     nmcu = h.mcus_x * h.mcus_y
-    blocks = nmcu * BLOCKS_PER_MCU[h.sampling]
+    four = h.ncomp == 4                               # r is a HEADER4_DTYPE record: h, v and ycck instead of sampling
+    blocks = nmcu * (sum(a * b for a, b in h.comp_hv) if four else BLOCKS_PER_MCU[h.sampling])
     r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
-    r["width"], r["height"], r["sampling"] = h.width, h.height, h.sampling
+    r["width"], r["height"] = h.width, h.height
+    if four:
+        r["h"], r["v"], r["ycck"] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv], int(h.ycck)
+    else:
+        r["sampling"] = h.sampling
     r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
     for c in range(h.ncomp):                          # a gray frame: qt[0], the rest stays zero
         r["qt"][c] = h.qtables[c]
@@ -542,13 +610,17 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     return nmcu, out_bytes + width * height * 3
 
 
-def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None):
+def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None, dtype=HEADER_DTYPE):
     """Header records + workspace totals for a batch of device-kind headers.
+    dtype=HEADER4_DTYPE: the four-component headers of one odic_jpeg4_decode call (no scales); their output offsets
+    are rounded up to multiples of 4, which lets the colour kernel store whole words.
     data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
     buffer.  scales: 1, 2, 4 or 8 per image (None: all 1), the draft scale its output is placed for.
-    → (np array HEADER_DTYPE [n], dict of batch totals / maxima, list of output byte offsets, output bytes)."""
+    → (np array of `dtype` [n], dict of batch totals / maxima, list of output byte offsets, output bytes)."""
     n = len(hdrs)
-    rec = np.zeros(n, HEADER_DTYPE)
+    rec = np.zeros(n, dtype)
+    four = dtype is HEADER4_DTYPE
+    ndc = 4 if four else 3                            # DC tables 0 .. ndc - 1, AC tables behind them
     tot = dict(total_scan_bytes=0, total_intervals=0, total_units=0, total_blocks=0, total_plane_bytes=0,
                max_units=1, max_intervals=1, max_width=1, max_height=1, max_blocks=1, max_scan_bytes=1)
     out_offs, out_bytes = [], 0
@@ -557,13 +629,15 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None):
         scan = data_ends[k] - data_offs[k]
         nint = n_intervals(h)
         units = -(-scan * 8 // subseq_bits) + nint
+        if four:
+            out_bytes = (out_bytes + 3) // 4 * 4
         nmcu, out_bytes = _place_image(r, h, tot, out_offs, out_bytes, scales[k] if scales else 1)
         r["data_off"], r["data_end"], r["scan_off"] = data_offs[k], data_ends[k], tot["total_scan_bytes"]
         r["int_off"], r["unit_off"] = tot["total_intervals"], tot["total_units"]
         r["restart"] = h.restart_interval or nmcu
         r["n_intervals"], r["n_units"] = nint, units
         for c in range(h.ncomp):                      # a gray frame: DC table 0, AC table 3, the rest stays zero
-            for t, tab in ((c, h.dc_tables[c]), (3 + c, h.ac_tables[c])):
+            for t, tab in ((c, h.dc_tables[c]), (ndc + c, h.ac_tables[c])):
                 lut, mc, vo, hv = device_tables(tab)
                 r["lut"][t], r["maxcode"][t], r["valoff"][t], r["huffval"][t] = lut, mc, vo, hv
         tot["total_scan_bytes"] += (scan + 3) // 4 * 4 + 16
@@ -817,7 +891,8 @@ def pad256(n: int) -> int:
 @dataclass
 class BatchPlan:
     """One decode batch in the staging buffer that is uploaded in one copy (256-aligned record sections in the order
-    baseline headers, progressive headers / scans / tables, scales; then the files, baseline first) and in the output."""
+    baseline headers, progressive headers / scans / tables, scales, four-component headers; then the files, baseline
+    first, four-component last) and in the output."""
     sections: list                 # [(staging offset, record array)], by offset
     data_off: int                  # the data area: what the records' data_off / data_end count from
     blobs: list                    # [(staging offset, uint8 array)] of every file, baseline first
@@ -830,6 +905,10 @@ class BatchPlan:
     out_bytes: int                 # RGB bytes of the baseline files: the progressive output starts here
     pout_bytes: int                # RGB bytes of the progressive files
     coef_off: list                 # first coefficient block of every progressive file, then their total
+    ctot: dict = None              # odic_jpeg_batch totals of the four-component files (`pack_headers`); None without them
+    cmyk_off: int = None           # staging offset of their HEADER4_DTYPE records; None without them
+    cout_off: int = 0              # where their part of the RGB output starts (256-aligned) ...
+    cout_bytes: int = 0            # ... and its bytes
 
     def fill(self, host):
         """Write the sections and the files into the uint8 array `host` of at least `total` bytes."""
@@ -837,11 +916,15 @@ class BatchPlan:
             host[o:o + a.nbytes] = a.view(np.uint8)
 
 
-def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales) -> BatchPlan:
+def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(), cblobs=()) -> BatchPlan:
     """The layout of one device decode of the baseline files (hdrs, blobs: DEVICE-kind `parse` results and their bytes)
     and the progressive ones (phdrs, pblobs: `parse_progressive`).  scales: the draft scale of every image, baseline
-    first.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload."""
-    nb, npg = len(hdrs), len(phdrs)
+    first.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
+    chdrs, cblobs: the four-component files (`parse(..., "convert", cmyk="device")`, ncomp 4), one more group behind the
+    others: its records behind the scales, its files behind the progressive ones, its output behind theirs from the
+    next multiple of 256.  They have no scales.  Without them the plan is what it is without these arguments."""
+    nb, npg, ncm = len(hdrs), len(phdrs), len(chdrs)
+    scales = list(scales)[:nb + npg]
     sections, pos = [], pad256(nb * HEADER_DTYPE.itemsize)
     ptot = prog_off = scale_off = None
     if npg:                                              # sizes only, for now: the files' offsets follow from them
@@ -853,19 +936,34 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales) -> BatchP
         scale_off = pos
         sections.append((pos, np.asarray([s.bit_length() - 1 for s in scales], np.int32)))
         pos += pad256(4 * (nb + npg))
+    cmyk_off = None
+    if ncm:
+        cmyk_off = pos
+        pos += pad256(ncm * HEADER4_DTYPE.itemsize)
     data_off = pos
-    starts = np.cumsum([0] + [len(b) for b in list(blobs) + list(pblobs)]).tolist()     # inside the data area
+    every = list(blobs) + list(pblobs) + list(cblobs)
+    starts = np.cumsum([0] + [len(b) for b in every]).tolist()                          # inside the data area
     tot, out_offs, out_bytes = None, [], 0
     if nb:
         rec, tot, out_offs, out_bytes = pack_headers(hdrs, [o + h.data_offset for o, h in zip(starts, hdrs)],
                                                      starts[1:nb + 1], subseq_bits, scales[:nb])
         sections.insert(0, (0, rec))
     if npg:
-        shift = np.asarray(starts[nb:-1], np.int64)[srec["image"]]
+        shift = np.asarray(starts[nb:nb + npg], np.int64)[srec["image"]]
         srec["data_off"] += shift
         srec["data_end"] += shift
         out_offs = out_offs + [out_bytes + o for o in pout_offs]
-    files = [(data_off + o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, list(blobs) + list(pblobs))]
+    extra = {}
+    if ncm:
+        first = nb + npg
+        crec, ctot, cout_offs, cout_bytes = pack_headers(
+            chdrs, [o + h.data_offset for o, h in zip(starts[first:], chdrs)], starts[first + 1:], subseq_bits,
+            dtype=HEADER4_DTYPE)
+        sections.append((cmyk_off, crec))
+        cout_off = pad256(out_bytes + (pout_bytes if npg else 0))
+        out_offs = out_offs + [cout_off + o for o in cout_offs]
+        extra = dict(ctot=ctot, cmyk_off=cmyk_off, cout_off=cout_off, cout_bytes=cout_bytes)
+    files = [(data_off + o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, every)]
     coef_off = [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])] if npg else []
     return BatchPlan(sections, data_off, files, data_off + starts[-1], tot, ptot, prog_off, scale_off, out_offs,
-                     out_bytes, pout_bytes if npg else 0, coef_off)
+                     out_bytes, pout_bytes if npg else 0, coef_off, **extra)

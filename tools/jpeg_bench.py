@@ -20,6 +20,13 @@ host's `Image.open(f).convert("RGB")`; with --progressive, their progressive re-
 
     python tools/jpeg_bench.py --gray --batches 16 64 --iters 20 --out profiles/r12_jpeg_gray_bench.json
 
+--cmyk: the same crops saved as mode CMYK (four components; Pillow writes Adobe transform 0 with component 0 at 2x2 for
+subsampling=2), decoded under non_rgb="convert": the device path with cmyk="device" (odic_jpeg4_decode) against the
+host's `Image.open(f).convert("RGB")`.  This is the line that decides whether cmyk="device" becomes the default
+(DESIGN §4.25).
+
+    python tools/jpeg_bench.py --cmyk --batches 16 64 --iters 20 --out profiles/jpeg_cmyk_bench.json
+
 --draft: what decoding at the scale `Image.draft("RGB", (S, S))` picks saves.  Seeded synthetic JPEGs,
 3456x4608 (drafts at 1/8) and 640x480 (drafts at 1/1: the control), 4:2:0 and 4:4:4, baseline and progressive; per
 case `decode_jpeg` alone and `from_jpeg_bytes` (decode + resize), draft off and on alternating in the same process,
@@ -56,7 +63,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def make_inputs(n: int, seed: int = 0, progressive: bool = False, gray: bool = False):
+def make_inputs(n: int, seed: int = 0, progressive: bool = False, gray: bool = False, cmyk: bool = False):
     from PIL import Image
     src = Image.open(os.path.join(ROOT, "tests", "golden", "demo_material", "micheal.jpg")).convert("RGB")
     rng = np.random.default_rng(seed)
@@ -71,6 +78,8 @@ def make_inputs(n: int, seed: int = 0, progressive: bool = False, gray: bool = F
         buf = io.BytesIO()
         if gray:
             im.convert("L").save(buf, format="JPEG", quality=90, progressive=progressive)
+        elif cmyk:
+            im.convert("CMYK").save(buf, format="JPEG", quality=90, subsampling=2)
         else:
             im.save(buf, format="JPEG", quality=90, subsampling=2, progressive=progressive)
         out.append(buf.getvalue())
@@ -273,6 +282,7 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="also time the device path at other subseq_bits / passes")
     ap.add_argument("--progressive", action="store_true", help="progressive re-saves of the crops, and tatin.jpg")
     ap.add_argument("--gray", action="store_true", help="the crops as one-component files, non_rgb='convert'")
+    ap.add_argument("--cmyk", action="store_true", help="the crops as four-component files, non_rgb='convert', cmyk='device'")
     ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
     ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
     ap.add_argument("--orient", action="store_true", help="odic_orient_rgb8 against a copy; orientation='exif' end to end")
@@ -288,9 +298,12 @@ def main():
     from on_device_image_captioning_amd.image_utils import DevicePreprocessor
     assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
     pre = DevicePreprocessor(args.size, "cuda:0")
-    blobs_all = make_inputs(max(args.batches), progressive=args.progressive, gray=args.gray)
-    non_rgb = "convert" if args.gray else "black"
-    want_route = "device-progressive" if args.progressive else "device"
+    if args.cmyk and (args.gray or args.progressive):
+        ap.error("--cmyk goes alone: the four-component route is baseline only")
+    blobs_all = make_inputs(max(args.batches), progressive=args.progressive, gray=args.gray, cmyk=args.cmyk)
+    non_rgb = "convert" if args.gray or args.cmyk else "black"
+    route_kw = {"cmyk": "device"} if args.cmyk else {}
+    want_route = "device-cmyk" if args.cmyk else "device-progressive" if args.progressive else "device"
     inputs = [(B, blobs_all[:B], (640, 480)) for B in args.batches]
     parse_us = None
     if args.progressive:
@@ -307,12 +320,13 @@ def main():
         parse_us = 1e6 * (time.perf_counter() - t0) / (5 * len(blobs_all))
 
     def host(blobs):
-        if args.gray:
+        if args.gray or args.cmyk:
             return pre([np.asarray(Image.open(io.BytesIO(b)).convert("RGB")) for b in blobs])
         return pre([np.asarray(Image.open(io.BytesIO(b))) for b in blobs])
 
     def device(blobs):
-        return pre.from_jpeg_bytes(blobs, progressive="device" if args.progressive else "host", non_rgb=non_rgb)
+        return pre.from_jpeg_bytes(blobs, progressive="device" if args.progressive else "host", non_rgb=non_rgb,
+                                   **route_kw)
 
     lines = []
     for B, blobs, (width, height) in inputs:
@@ -340,7 +354,7 @@ def main():
             for bits in (1024, 2048, 4096):
                 for passes in (2, 4, 8):
                     fn = lambda b, bits=bits, passes=passes: pre.from_jpeg_bytes(   # noqa: E731
-                        b, bits, passes, non_rgb=non_rgb)
+                        b, bits, passes, non_rgb=non_rgb, **route_kw)
                     for _ in range(2):
                         fn(blobs)
                     torch.cuda.synchronize()
@@ -352,7 +366,8 @@ def main():
                         ts.append(time.perf_counter() - t0)
                     sweep[f"bits{bits}_passes{passes}"] = B / float(np.median(ts))
         line = {"batch": B, "width": width, "height": height, "quality": 90,
-                "subsampling": "gray" if args.gray else "4:2:0", "progressive": args.progressive,
+                "subsampling": "gray" if args.gray else "cmyk 2x2,1x1,1x1,1x1" if args.cmyk else "4:2:0",
+                "progressive": args.progressive,
                 "mean_jpeg_bytes": int(np.mean([len(b) for b in blobs])),
                 "host_images_per_s": B / med["host"], "device_images_per_s": B / med["device"],
                 "speedup": med["host"] / med["device"],
