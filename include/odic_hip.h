@@ -69,7 +69,8 @@ extern "C" {
  *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
  *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
- *       odic_lcs_pairs, odic_orient_rgb8, odic_jpeg4_workspace_bytes, odic_jpeg4_decode, odic_cmyk_to_rgb8. */
+ *       odic_lcs_pairs, odic_orient_rgb8, odic_jpeg4_workspace_bytes, odic_jpeg4_decode, odic_cmyk_to_rgb8,
+ *       odic_jpeg3_any_workspace_bytes, odic_jpeg3_any_decode. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -404,6 +405,40 @@ int odic_jpeg4_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_b
  * "CMYK;I" unpacking of a JPEG).  n_pixels == 0 launches nothing.  ODIC_ENULL for a null pointer, ODIC_EINVAL for a
  * negative n_pixels. */
 int odic_cmyk_to_rgb8(const uint8_t* cmyk, uint8_t* rgb, int64_t n_pixels, int invert, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Three-component baseline files at every other sampling layout libjpeg decodes, and RGB-stored ones, bit-exact with
+ * np.asarray(PIL.Image.open(f).convert("RGB")).  jpeg.parse(..., layouts="all") admits 8-bit SOF0/SOF1 Huffman frames
+ * with one interleaved scan of the three components in frame order that odic_jpeg_header cannot describe: sampling
+ * factors in 1..4, every factor a divisor of the largest in its direction, at most 10 blocks per MCU.  The record has
+ * odic_jpeg_header4's fields with the same meaning, for three components, except that the MCU spans the LARGEST
+ * factors (mcus_x = ceil(W / (8 max h)), mcus_y = ceil(H / (8 max v))), and instead of `ycck`:
+ *   rgb          1: the components are R, G, B as stored (Adobe transform 0, or ids 'R', 'G', 'B' with neither a JFIF
+ *                nor an Adobe marker); 0: Y, Cb, Cr (libjpeg's ycc_rgb_convert)
+ *   lut/maxcode/valoff/huffval  tables 0-2: DC of components 0-2, 3-5: their AC
+ * Every component, component 0 included, is brought to the output grid by libjpeg's rule for its ratios (rh, rv) =
+ * (max h / h[c], max v / v[c]): (1,1) as it is; (2,1) / (2,2) the fancy triangle filters, or replication where the
+ * component is at most two samples wide; (1,2) h1v2_fancy_upsample at every width; any other ratio replication.
+ * A record that breaks the rules above is not decoded: its status is 1 and none of its pixels are written.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct odic_jpeg_header3 {
+  int64_t data_off, data_end, out_off, scan_off, coef_off, plane_off;
+  int32_t int_off, unit_off, width, height;
+  int32_t rgb;
+  int32_t mcus_x, mcus_y, restart, n_intervals, n_units;
+  int32_t h[3], v[3];
+  uint16_t qt[3][64];
+  uint16_t lut[6][512];
+  int32_t maxcode[6][18];
+  int32_t valoff[6][18];
+  uint8_t huffval[6][256];
+} odic_jpeg_header3;                /* 9040 bytes */
+
+/* odic_jpeg_workspace_bytes / odic_jpeg_decode for a batch whose `headers` are odic_jpeg_header3 [n_images]: the same
+ * descriptor, launches, workspace layout, status rule and contract as odic_jpeg4_decode
+ * (test_layout_decode_stays_inside_its_workspace). */
+size_t odic_jpeg3_any_workspace_bytes(const odic_jpeg_batch* batch);
+int odic_jpeg3_any_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Progressive files (8-bit SOF2 Huffman, 3 YCbCr components, the samplings above — sampling 3 included: one component,

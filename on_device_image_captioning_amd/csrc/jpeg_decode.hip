@@ -43,6 +43,12 @@
 // IDCT writes four planes and jpeg_color4_kernel upsamples each, then applies YCCK → CMYK, Pillow's inversion and
 // Pillow's CMYK → RGB: np.asarray(PIL.Image.open(f).convert("RGB")).  Full size only.
 //
+// Three-component frames at any other sampling layout libjpeg decodes (4:4:0, 4:1:1, 4:1:0, chroma sub-sampled one way
+// under a 2x2 luma, a component 0 that is not the largest), stored as YCbCr or as RGB (odic_jpeg3_any_decode), have the
+// record odic_jpeg_header3: per-component sampling and a colour flag, three quantisation and six Huffman tables.  The
+// same templates again up to the IDCT, which writes three planes; jpeg_color3_kernel reads every component through
+// upsampled_by() — copy, h2v1 / h2v2 / h1v2 fancy, or replication by an integral ratio — and converts or copies.
+//
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
 // whose coefficients leave the range where libjpeg-turbo's SIMD and C IDCTs agree (kIdctLimit), gets status 1:
@@ -57,6 +63,9 @@ static_assert(sizeof(odic_jpeg_header) == 9016 && offsetof(odic_jpeg_header, qt)
 static_assert(sizeof(odic_jpeg_header4) == 12024 && offsetof(odic_jpeg_header4, h) == 88 &&
                   offsetof(odic_jpeg_header4, qt) == 120 && offsetof(odic_jpeg_header4, huffval) == 9976,
               "odic_jpeg_header4 layout is mirrored by jpeg.HEADER4_DTYPE");
+static_assert(sizeof(odic_jpeg_header3) == 9040 && offsetof(odic_jpeg_header3, h) == 88 &&
+                  offsetof(odic_jpeg_header3, qt) == 112 && offsetof(odic_jpeg_header3, huffval) == 7504,
+              "odic_jpeg_header3 layout is mirrored by jpeg.HEADER3_DTYPE");
 
 namespace {
 
@@ -194,7 +203,40 @@ struct Frame<odic_jpeg_header4> {
   }
   __device__ __forceinline__ int comp(int blk) const { return (map >> (2 * blk)) & 3; }
 };
+// Three components, each with its own sampling (odic_jpeg_header3).  layout_ok() is libjpeg's rule set, which the host
+// parser applies before it packs a record: factors in 1..4, at most 10 blocks, every factor a divisor of the largest.
+// A record that breaks it is a frame of one block of component 0 to the entropy kernels, which stay inside whatever
+// the record's offsets span; the IDCT and the colour pass write nothing for it and the image gets status 1.
+__device__ __forceinline__ bool layout_ok(const odic_jpeg_header3& h) {
+  int hm = 1, vm = 1, n = 0;
+  for (int c = 0; c < 3; ++c) {
+    if ((unsigned)(h.h[c] - 1) > 3u || (unsigned)(h.v[c] - 1) > 3u) return false;
+    hm = max(hm, h.h[c]);
+    vm = max(vm, h.v[c]);
+    n += h.h[c] * h.v[c];
+  }
+  if (n > kMaxMcuBlocks4) return false;
+  for (int c = 0; c < 3; ++c)
+    if (hm % h.h[c] || vm % h.v[c]) return false;
+  return true;
+}
+template <>
+struct Frame<odic_jpeg_header3> {
+  static constexpr int kComps = 3;
+  unsigned map;
+  int bpm;
+  __device__ explicit Frame(const odic_jpeg_header3& h) : map(0), bpm(0) {
+    if (!layout_ok(h)) {
+      bpm = 1;
+      return;
+    }
+    for (int c = 0; c < 3; ++c)
+      for (int j = 0; j < h.h[c] * h.v[c]; ++j) map |= (unsigned)c << (2 * bpm++);
+  }
+  __device__ __forceinline__ int comp(int blk) const { return (map >> (2 * blk)) & 3; }
+};
 __device__ __forceinline__ int mcu_blocks(const odic_jpeg_header4& h) { return Frame<odic_jpeg_header4>(h).bpm; }
+__device__ __forceinline__ int mcu_blocks(const odic_jpeg_header3& h) { return Frame<odic_jpeg_header3>(h).bpm; }
 template <typename Header>
 __device__ __forceinline__ int mcu_blocks(const Header& h) { return blocks_per_mcu(h.sampling); }
 
@@ -841,15 +883,18 @@ __device__ __forceinline__ BlockGeo block_geo(const Header& h, int j, int ny, in
   }
   return g;
 }
-// four components, each with its own sampling, full size only: the planes follow each other in component order
-__device__ __forceinline__ long plane_bytes4(const odic_jpeg_header4& h, int c) {
+// every component with its own sampling (odic_jpeg_header4: kC = 4, odic_jpeg_header3: kC = 3), full size only: the
+// planes follow each other in component order
+template <typename Header>
+__device__ __forceinline__ long plane_bytes4(const Header& h, int c) {
   return (long)h.mcus_x * 8 * h.h[c] * h.mcus_y * 8 * h.v[c];
 }
-__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j, int, int) {
-  BlockGeo g{3, 8, h.h[3], h.v[3], 0, 0, 0};
-  for (int c = 0; c < 4; ++c) {
+template <int kC, typename Header>
+__device__ __forceinline__ BlockGeo block_geo_own(const Header& h, int j) {
+  BlockGeo g{kC - 1, 8, h.h[kC - 1], h.v[kC - 1], 0, 0, 0};
+  for (int c = 0; c < kC; ++c) {
     const int nb = h.h[c] * h.v[c];
-    if (j < nb || c == 3) {
+    if (j < nb || c == kC - 1) {
       g.comp = c; g.hc = h.h[c]; g.vc = h.v[c]; g.jx = j % g.hc; g.jy = min(j / g.hc, g.vc - 1);
       break;
     }
@@ -858,6 +903,8 @@ __device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j,
   }
   return g;
 }
+__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j, int, int) { return block_geo_own<4>(h, j); }
+__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header3& h, int j, int, int) { return block_geo_own<3>(h, j); }
 
 // One block per 8 lanes: column pass → LDS → row pass, n×n samples into the component's plane.  kScaled = false is
 // the full-size decode (lg = 0, n = 8 throughout, the branches below fold away).  A scaled image's planes keep the
@@ -866,6 +913,9 @@ __device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j,
 // only the input and the result).  libjpeg-turbo's SIMD 4x4 / 2x2 keep the same 16-bit intermediates as its 8x8.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int img, int lg, int (*ws8)[8][9]) {
+  if constexpr (std::is_same<Header, odic_jpeg_header3>::value) {
+    if (!layout_ok(h)) return;                                // the whole workgroup: one image per blockIdx.y
+  }
   const int bpm = mcu_blocks(h);                              // gray: every block is component 0
   const long nblocks = (long)h.mcus_x * h.mcus_y * bpm;
   const long b = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
@@ -977,6 +1027,32 @@ __device__ __forceinline__ int upsampled(const unsigned char* __restrict__ P, in
   return (3 * s0 + s1 + 8 - odd) >> 4;
 }
 
+// jdcolor.c ycc_rgb_convert on one pixel, cb and cr as stored
+__device__ __forceinline__ void ycc_rgb_pixel(int yv, int cb, int cr, unsigned char* __restrict__ o) {
+  cb -= 128;
+  cr -= 128;
+  o[0] = clamp255(yv + ((kCrR * cr + 32768) >> 16));
+  o[1] = clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
+  o[2] = clamp255(yv + ((kCbB * cb + 32768) >> 16));
+}
+
+// jdsample.c jinit_upsampler for any component: one sample at output pixel (x, y) of a plane with 1 / rh of the
+// output's width and 1 / rv of its height, dw x dh real samples.  (1, 1) is the plane itself; (2, 1) and (2, 2) are
+// upsampled() above, fancy unless the plane is at most two samples wide; (1, 2) is h1v2_fancy_upsample at every width:
+// three parts of the nearer row and one of the farther, the row above for an upper output row (bias 1) and below for a
+// lower one (bias 2), the plane's first and last real rows standing in for the rows outside it; every other integral
+// ratio is int_upsample: replication.
+__device__ __forceinline__ int upsampled_by(const unsigned char* __restrict__ P, int cw, int x, int y, int rh, int rv,
+                                            int dw, int dh) {
+  if (rh == 2 && rv <= 2) return upsampled(P, cw, x, y, rv == 2, dw <= 2, dw, dh);
+  if (rh == 1 && rv == 2) {
+    const int r = y >> 1, odd = y & 1;
+    const int rn = odd ? min(r + 1, dh - 1) : max(r - 1, 0);
+    return (3 * P[(long)r * cw + x] + P[(long)rn * cw + x] + 1 + odd) >> 2;
+  }
+  return P[(long)(y / rv) * cw + x / rh];
+}
+
 // One output pixel.  kScaled = false is the full-size decode (lg = 0).  At scale 1 / 2^lg the output is
 // ceil(W / 2^lg) × ceil(H / 2^lg) and the planes hold the transform sizes of scaled_sizes(): 4:4:4 and, for lg > 0,
 // 4:2:0 read chroma on the luma grid; 4:2:2 upsamples horizontally (jdsample.c): fancy while the chroma transform is
@@ -1019,11 +1095,7 @@ __device__ __forceinline__ void color_pixel(const Header& h, const Ws& ws, int i
     cb = upsampled(Cb, cw, x, y, sampling == 2, plain, dw, (H + 1) >> 1);
     cr = upsampled(Cr, cw, x, y, sampling == 2, plain, dw, (H + 1) >> 1);
   }
-  cb -= 128;
-  cr -= 128;
-  o[0] = clamp255(yv + ((kCrR * cr + 32768) >> 16));
-  o[1] = clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
-  o[2] = clamp255(yv + ((kCbB * cb + 32768) >> 16));
+  ycc_rgb_pixel(yv, cb, cr, o);
 }
 
 template <typename Header>
@@ -1137,6 +1209,53 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(const odic_jpeg_header
       s[2] = 255 - clamp255(yv + ((kCbB * cb + 32768) >> 16));
     }
     cmyk_pixel_rgb(s[0], s[1], s[2], s[3], 1, px + 3 * i);
+  }
+  store_rgb4(out + h.out_off + 3 * p0, px, n);
+}
+
+// odic_jpeg_header3, in jpeg_color4_kernel's form: four consecutive pixels of the image's H·W per lane, every component
+// through upsampled_by() at its own ratio to the largest sampling — component 0 too, where it is not the largest —
+// then ycc_rgb_convert, or the three samples as they are for an RGB file; plus the per-image status.  A record that
+// layout_ok() refuses has status 1 and no pixels.
+__global__ __launch_bounds__(256) void jpeg_color3_kernel(const odic_jpeg_header3* __restrict__ hdrs, Ws ws,
+                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
+  const int img = blockIdx.y;
+  const odic_jpeg_header3& h = hdrs[img];
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
+  const bool ok = layout_ok(h);
+  if (p0 == 0) {
+    const int* st = ws.state + kStateWords * img;
+    status[img] = (ok && st[0] == 0 && st[1] == h.n_intervals) ? 0 : 1;
+  }
+  const int W = h.width, H = h.height;
+  const long npix = (long)W * H;
+  if (!ok || p0 >= npix) return;
+  const int n = (int)min((long)kColor4Pixels, npix - p0);
+  const int hm = max(h.h[0], max(h.h[1], h.h[2])), vm = max(h.v[0], max(h.v[1], h.v[2]));
+  const unsigned char* P[3];
+  int pw[3], rh[3], rv[3], dw[3], dh[3];
+  const unsigned char* base = ws.planes + h.plane_off;
+  for (int c = 0; c < 3; ++c) {
+    P[c] = base;
+    pw[c] = h.mcus_x * 8 * h.h[c];
+    rh[c] = hm / h.h[c];
+    rv[c] = vm / h.v[c];
+    dw[c] = (int)(((long)W * h.h[c] + hm - 1) / hm);         // jdinput.c: the component's downsampled size
+    dh[c] = (int)(((long)H * h.v[c] + vm - 1) / vm);
+    base += plane_bytes4(h, c);
+  }
+  unsigned char px[3 * kColor4Pixels];
+  for (int i = 0; i < n; ++i) {
+    const long p = p0 + i;
+    const int y = (int)(p / W), x = (int)(p - (long)y * W);
+    int s[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s[c] = upsampled_by(P[c], pw[c], x, y, rh[c], rv[c], dw[c], dh[c]);
+    if (h.rgb) {
+      for (int c = 0; c < 3; ++c) px[3 * i + c] = (unsigned char)s[c];
+    } else {
+      ycc_rgb_pixel(s[0], s[1], s[2], px + 3 * i);
+    }
   }
   store_rgb4(out + h.out_off + 3 * p0, px, n);
 }
@@ -1500,7 +1619,8 @@ void launch_idct_color(const Batch* b, const Header* hdrs, const Ws& ws, const i
   }
 }
 
-// Header: odic_jpeg_header (three components or gray) or odic_jpeg_header4 (four; full size only)
+// Header: odic_jpeg_header (three components or gray), odic_jpeg_header4 (four; full size only) or odic_jpeg_header3
+// (three at any sampling layout; full size only)
 template <typename Header>
 int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream,
                     const int32_t* scale_log2) {
@@ -1528,12 +1648,15 @@ int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, 
   hipLaunchKernelGGL(jpeg_block_scan_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
   hipLaunchKernelGGL(jpeg_writeout_kernel<Header>, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
   hipLaunchKernelGGL(jpeg_dc_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
-  if constexpr (std::is_same<Header, odic_jpeg_header4>::value) {
+  if constexpr (!std::is_same<Header, odic_jpeg_header>::value) {       // per-component sampling: full size only
     const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
+    const dim3 cgrid((unsigned)((lanes + 255) / 256), n);
     hipLaunchKernelGGL(jpeg_idct_kernel<Header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs,
                        ws);
-    hipLaunchKernelGGL(jpeg_color4_kernel, dim3((unsigned)((lanes + 255) / 256), n), dim3(256), 0, s, hdrs, ws, b->out,
-                       b->status);
+    if constexpr (std::is_same<Header, odic_jpeg_header4>::value)
+      hipLaunchKernelGGL(jpeg_color4_kernel, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+    else
+      hipLaunchKernelGGL(jpeg_color3_kernel, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
   } else {
     launch_idct_color(b, hdrs, ws, scale_log2, s);
   }
@@ -1574,6 +1697,12 @@ extern "C" size_t odic_jpeg4_workspace_bytes(const odic_jpeg_batch* b) { return 
 
 extern "C" int odic_jpeg4_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
   return decode_baseline<odic_jpeg_header4>(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" size_t odic_jpeg3_any_workspace_bytes(const odic_jpeg_batch* b) { return odic_jpeg_workspace_bytes(b); }
+
+extern "C" int odic_jpeg3_any_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
+  return decode_baseline<odic_jpeg_header3>(b, workspace, ws_bytes, stream, nullptr);
 }
 
 extern "C" int odic_cmyk_to_rgb8(const uint8_t* cmyk, uint8_t* rgb, int64_t n_pixels, int invert, void* stream) {

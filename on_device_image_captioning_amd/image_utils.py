@@ -44,7 +44,9 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # device, the other modes by PIL.  With `orientation="exif"` every image is turned upright as `ImageOps.exif_transpose`
 # does: device-decoded files by one odic_orient_rgb8 launch (csrc/orient.hip), PIL-decoded ones by PIL.  With
 # `cmyk="device"` (and `non_rgb="convert"`) baseline CMYK / YCCK JPEGs are decoded and converted on the device too
-# (odic_jpeg4_decode) instead of leaving the batch for PIL.
+# (odic_jpeg4_decode) instead of leaving the batch for PIL.  With `layouts="all"` so are baseline three-component
+# JPEGs at the sampling layouts and colour spaces the common decode turns away (odic_jpeg3_any_decode: 4:4:0, 4:1:1,
+# 4:1:0, RGB-stored files, ...).
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -230,7 +232,8 @@ class DevicePreprocessor:
         return out
 
     def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None,
-                   non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host") -> torch.Tensor:
+                   non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host",
+                   layouts: str = "common") -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
         the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
         non_rgb="convert": a file of any other mode (L, LA, P, RGBA, I;16, CMYK, ...) is read as
@@ -248,14 +251,20 @@ class DevicePreprocessor:
         "ignore" reads the stored pixel grid, as the reference does.
         cmyk="device" (needs non_rgb="convert"): with decode="device" it is passed on to `from_jpeg_bytes`, where
         baseline CMYK / YCCK JPEGs are decoded on the device (not under a draft request: there are no draft scales for
-        four components); decode="host" ignores it.  The tensor is the same either way."""
-        from .jpeg import check_cmyk, check_non_rgb, check_orientation
+        four components); decode="host" ignores it.  The tensor is the same either way.
+        layouts="all": likewise passed on to `from_jpeg_bytes` with decode="device", where baseline three-component
+        JPEGs at any sampling layout libjpeg decodes, and RGB-stored ones, are decoded on the device (not under a draft
+        request); decode="host" ignores it.  The tensor is the same either way."""
+        from .jpeg import check_cmyk, check_layouts, check_non_rgb, check_orientation
         check_non_rgb(non_rgb)
         check_orientation(orientation)
         check_cmyk(cmyk, non_rgb)
+        check_layouts(layouts)
         exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's calls stay as they are
         if cmyk != "host":
             exif["cmyk"] = cmyk
+        if layouts != "common":
+            exif["layouts"] = layouts
         if decode == "device":
             blobs = []
             for p in paths:
@@ -265,6 +274,7 @@ class DevicePreprocessor:
         if decode != "host":
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
         exif.pop("cmyk", None)
+        exif.pop("layouts", None)
         arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None, non_rgb, **exif) for p in paths]
         if regions is None:
             return self(arrays)
@@ -317,7 +327,8 @@ class DevicePreprocessor:
     def last_routes(self):
         """How each file of the last `decode_jpeg` / `from_jpeg_bytes` call was decoded, in input order: "device" (baseline,
         odic_jpeg_decode), "device-progressive" (odic_jpeg_decode_progressive), "device-cmyk" (four components,
-        odic_jpeg4_decode), "host" (PIL: a kind the device does not
+        odic_jpeg4_decode), "device-layout" (three components at a layout of layouts="all", odic_jpeg3_any_decode), "host"
+        (PIL: a kind the device does not
         take), "host-after-status" (the device reported status 1 and PIL decoded the file again) or "black"."""
         return tuple(self._jpeg_routes)
 
@@ -328,7 +339,8 @@ class DevicePreprocessor:
         return tuple(self._jpeg_orientations)
 
     def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host",
-                    draft=None, non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host"):
+                    draft=None, non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host",
+                    layouts: str = "common"):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
         np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path; with
         non_rgb="convert" each equals np.asarray(PIL.Image.open(f).convert("RGB")) instead: one-component JPEGs take the
@@ -351,7 +363,13 @@ class DevicePreprocessor:
         measured): baseline four-component JPEGs — CMYK, or YCCK by Adobe transform 2 — that
         `jpeg.parse` admits are decoded by one odic_jpeg4_decode call in the same upload and status read-back, route
         "device-cmyk", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  Progressive four-component files
-        stay with PIL, and so do all of them under a draft request: there are no draft scales for this layout."""
+        stay with PIL, and so do all of them under a draft request: there are no draft scales for this layout.
+        layouts="all" (the default "common" leaves them to PIL until the device route is measured):
+        baseline three-component JPEGs that only `jpeg.parse(f, layouts="all")` admits — luma at 1x2 (4:4:0), 4x1
+        (4:1:1), 4x2 (4:1:0), chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest, files
+        stored as RGB — are decoded by one odic_jpeg3_any_decode call in the same upload and status read-back, route
+        "device-layout", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  A file the common rules admit keeps
+        its route.  Progressive files with these layouts stay with PIL, and so do all of them under a draft request."""
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
@@ -359,7 +377,10 @@ class DevicePreprocessor:
         J.check_orientation(orientation)
         J.check_cmyk(cmyk, non_rgb)
         opt = () if non_rgb == "black" else (non_rgb,)                   # the default's calls stay as they are
+        J.check_layouts(layouts)
         copt = {"cmyk": cmyk} if cmyk != "host" and draft is None else {}
+        if layouts != "common" and draft is None:
+            copt["layouts"] = layouts
         if draft is not None:
             draft = (int(draft[0]), int(draft[1]))
             if draft[0] <= 0 or draft[1] <= 0:
@@ -383,16 +404,22 @@ class DevicePreprocessor:
         dev = [i for i, h in enumerate(hdrs)
                if h.kind == J.DEVICE and sizes[i][0] * sizes[i][1] * 3 <= self.max_bytes]
         four = [i for i in dev if hdrs[i].ncomp == 4]
-        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader) and hdrs[i].ncomp != 4]
+        lay = [i for i in dev if getattr(hdrs[i], "layout", False)]
+        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader) and hdrs[i].ncomp != 4
+                and not getattr(hdrs[i], "layout", False)]
         prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader)]
         routes = ["host" if h.kind == J.DEVICE else h.kind for h in hdrs]        # a device kind left so is oversized
         for i in dev:
             routes[i] = "device-progressive" if isinstance(hdrs[i], J.ProgHeader) else "device"
         for i in four:
             routes[i] = "device-cmyk"
+        for i in lay:
+            routes[i] = "device-layout"
         if dev:
-            order = base + prog + four
-            group4 = ([hdrs[i] for i in four], [blobs[i] for i in four]) if four else ()   # without: today's call
+            order = base + prog + four + lay
+            group4 = ([hdrs[i] for i in four], [blobs[i] for i in four]) if four or lay else ()   # without: today's call
+            if lay:
+                group4 += ([hdrs[i] for i in lay], [blobs[i] for i in lay])
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
                                                            [hdrs[i] for i in prog], [blobs[i] for i in prog],
                                                            subseq_bits, max_sync_passes,
@@ -444,26 +471,37 @@ class DevicePreprocessor:
             w, h = oriented_size(sizes[i], turns[i])
             out[i] = dst[int(r["dst_off"]):int(r["dst_off"]) + w * h * 3].view(h, w, 3)
 
-    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales, chdrs=(), cblobs=()):
+    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales, chdrs=(), cblobs=(),
+                          lhdrs=(), lblobs=()):
         """One odic_jpeg_decode call for the baseline files, one odic_jpeg_decode_progressive call for the progressive
-        ones and one odic_jpeg4_decode call for the four-component ones (chdrs, cblobs), sharing one upload, one output
-        buffer, one workspace and one status read-back → (status numpy int32 — baseline files first, four-component
-        last —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
+        ones, one odic_jpeg4_decode call for the four-component ones (chdrs, cblobs) and one odic_jpeg3_any_decode call
+        for the `layout` ones (lhdrs, lblobs), sharing one upload, one output
+        buffer, one workspace and one status read-back → (status numpy int32 — baseline files first, then progressive,
+        four-component, `layout` —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
         baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales uploaded
         beside the headers.  This is the GPU half: `jpeg.plan_device_batch` lays the upload and the output out."""
         from . import jpeg as J
-        nb, npg, ncm = len(hdrs), len(phdrs), len(chdrs)
-        group4 = (chdrs, cblobs) if ncm else ()
+        nb, npg, ncm, nly = len(hdrs), len(phdrs), len(chdrs), len(lhdrs)
+        group4 = (chdrs, cblobs) if ncm or nly else ()
+        if nly:
+            group4 += (lhdrs, lblobs)
         plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, *group4)
-        n_all = nb + npg + ncm
+        n_all = nb + npg + ncm + nly
         self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
         self._jpeg_pinned = self._grow(self._jpeg_pinned, plan.total, pin_memory=True)
         self._jpeg_status = self._grow(self._jpeg_status, 4 * n_all, pin_memory=True)
         plan.fill(self._jpeg_pinned.numpy())
         out_total = plan.cout_off + plan.cout_bytes if ncm else plan.out_bytes + plan.pout_bytes
+        if nly:
+            out_total = plan.lout_off + plan.lout_bytes
         rgb = torch.empty(max(out_total, 1), dtype=torch.uint8, device=self.device)
         status = torch.empty(n_all, dtype=torch.int32, device=self.device)
-        need_b = need_p = need_c = 0
+        need_b = need_p = need_c = need_l = 0
+        if nly:
+            lb = self._hip.JpegBatch()
+            lb.n_images, lb.subseq_bits, lb.max_sync_passes = nly, subseq_bits, max_sync_passes
+            self._set_fields(lb, plan.ltot)
+            need_l = self.lib.odic_jpeg3_any_workspace_bytes(ctypes.byref(lb))
         if ncm:
             cb = self._hip.JpegBatch()
             cb.n_images, cb.subseq_bits, cb.max_sync_passes = ncm, subseq_bits, max_sync_passes
@@ -484,7 +522,7 @@ class DevicePreprocessor:
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             self._jpeg_dev = self._grow(self._jpeg_dev, plan.total, device=self.device)
-            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p, need_c), device=self.device)
+            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p, need_c, need_l), device=self.device)
             self._jpeg_dev[:plan.total].copy_(self._jpeg_pinned[:plan.total], non_blocking=True)
             self._jpeg_ev.record(self.stream)
             base = self._jpeg_dev.data_ptr()
@@ -504,6 +542,11 @@ class DevicePreprocessor:
                 cb.out, cb.status = rgb.data_ptr() + plan.cout_off, status.data_ptr() + 4 * (nb + npg)
                 self._hip.check(self.lib.odic_jpeg4_decode(ctypes.byref(cb), self._jpeg_ws.data_ptr(), need_c,
                                                            self.stream.cuda_stream), "odic_jpeg4_decode")
+            if nly:
+                lb.headers, lb.data = base + plan.layout_off, base + plan.data_off
+                lb.out, lb.status = rgb.data_ptr() + plan.lout_off, status.data_ptr() + 4 * (nb + npg + ncm)
+                self._hip.check(self.lib.odic_jpeg3_any_decode(ctypes.byref(lb), self._jpeg_ws.data_ptr(), need_l,
+                                                               self.stream.cuda_stream), "odic_jpeg3_any_decode")
             if npg:                                                      # last: its coefficients stay in the workspace
                 pb.headers, pb.scans, pb.tables = (base + o for o in plan.prog_off)
                 pb.data, pb.out = base + plan.data_off, rgb.data_ptr() + plan.out_bytes
@@ -525,17 +568,20 @@ class DevicePreprocessor:
 
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
                         progressive: str = "host", draft: bool = False, regions=None,
-                        non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host") -> torch.Tensor:
+                        non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host",
+                        layouts: str = "common") -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
         torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`,
         the same `non_rgb` and the same `orientation`).
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` on the
         decoded images instead; with draft=True the boxes are in the coordinates of the drafted image, with
         orientation="exif" in those of the upright one.  cmyk: as `decode_jpeg` (with draft=True four-component files
-        stay on the host route)."""
+        stay on the host route); layouts: as `decode_jpeg` (likewise)."""
         exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's call stays as it is
         if cmyk != "host":
             exif["cmyk"] = cmyk
+        if layouts != "common":
+            exif["layouts"] = layouts
         imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
                                 draft=(self.S, self.S) if draft else None, non_rgb=non_rgb, **exif)
         if regions is not None:

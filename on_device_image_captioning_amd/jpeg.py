@@ -27,6 +27,18 @@ frame is `host`, where PIL converts it — unless the caller also passes cmyk="d
 component in comp_hv and the `ycck` flag; odic_jpeg4_decode reads its records (`HEADER4_DTYPE`).  Progressive
 four-component files, and all of them under a draft request, stay `host`.
 
+Under layouts="all" (`parse` only; the default "common" is everything above) a baseline three-component frame that the
+rules above turn away for its sampling or its colour space is a `device` kind too where `_frame3_any` admits it: every
+component at its own (h, v) in 1..4 with integral ratios to the largest and at most MAX_MCU_BLOCKS blocks per MCU —
+4:4:0, 4:1:1, 4:1:0, chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest — stored as
+YCbCr or as RGB (Adobe transform 0, or ids R, G, B with neither marker).  The header has `layout` set, comp_hv, the
+`rgb` flag and MCU counts from the largest factors; odic_jpeg3_any_decode reads its records (`HEADER3_DTYPE`).  What
+still goes to the host after that:
+
+    host    fractional sampling ratios; more than 10 blocks per MCU; progressive files, and draft requests, with these
+            layouts; non-interleaved multi-scan baseline files; arithmetic coding; 12-bit; three components with an
+            Adobe transform other than 0 and 1, or with duplicate ids
+
 `parse` keeps that sorting.  For the files it turns away with reason "SOF2", `parse_progressive` (below) reads the whole
 scan script, locating every scan's end in the file, and packs the records odic_jpeg_decode_progressive reads.
 """
@@ -70,6 +82,17 @@ def check_cmyk(cmyk, non_rgb):
                          "non_rgb='convert' (under non_rgb='black' they are black canvases)")
     return cmyk
 
+
+
+LAYOUTS = ("common", "all")                           # which three-component baseline layouts are a device kind
+
+
+def check_layouts(layouts):
+    if layouts not in LAYOUTS:
+        raise ValueError(f"layouts must be 'common' or 'all', not {layouts!r}")
+    return layouts
+
+
 # odic_jpeg_header (include/odic_hip.h), field for field
 HEADER_DTYPE = np.dtype([
     ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
@@ -88,6 +111,16 @@ HEADER4_DTYPE = np.dtype([
     ("h", "<i4", (4,)), ("v", "<i4", (4,)),
     ("qt", "<u2", (4, 64)), ("lut", "<u2", (8, 512)), ("maxcode", "<i4", (8, 18)), ("valoff", "<i4", (8, 18)),
     ("huffval", "u1", (8, 256)),
+], align=True)
+# odic_jpeg_header3 (include/odic_hip.h), field for field: three components, each with its own sampling, YCbCr or RGB
+HEADER3_DTYPE = np.dtype([
+    ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
+    ("plane_off", "<i8"),
+    ("int_off", "<i4"), ("unit_off", "<i4"), ("width", "<i4"), ("height", "<i4"), ("rgb", "<i4"),
+    ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart", "<i4"), ("n_intervals", "<i4"), ("n_units", "<i4"),
+    ("h", "<i4", (3,)), ("v", "<i4", (3,)),
+    ("qt", "<u2", (3, 64)), ("lut", "<u2", (6, 512)), ("maxcode", "<i4", (6, 18)), ("valoff", "<i4", (6, 18)),
+    ("huffval", "u1", (6, 256)),
 ], align=True)
 
 
@@ -113,16 +146,18 @@ class JpegHeader:
     data_offset: int = 0                                 # first byte of the entropy-coded data
     reason: str = ""
     ycck: bool = False                                   # four components: Adobe transform 2 (YCCK), else CMYK as stored
+    layout: bool = False                                 # three components admitted by `_frame3_any` (layouts="all")
+    rgb: bool = False                                    # ... stored as RGB (no colour conversion), else YCbCr
     app1: list = field(default=None, compare=False, repr=False)     # APP1 payloads ahead of the first SOS, where the
                                                                      # walk got that far (`header_orientation`)
 
     @property
-    def mcus_x(self):
-        return -(-self.width // (8 * self.comp_hv[0][0]))
+    def mcus_x(self):                                    # the MCU spans the largest factors: component 0's in every
+        return -(-self.width // (8 * max(h for h, _ in self.comp_hv)))      # frame but a `layout` one
 
     @property
     def mcus_y(self):
-        return -(-self.height // (8 * self.comp_hv[0][1]))
+        return -(-self.height // (8 * max(v for _, v in self.comp_hv)))
 
 
 class _Bad(Exception):
@@ -135,17 +170,22 @@ def _u16(b, i):
     return (b[i] << 8) | b[i + 1]
 
 
-def parse(blob, non_rgb: str = "black", cmyk: str = "host") -> JpegHeader:
+def parse(blob, non_rgb: str = "black", cmyk: str = "host", layouts: str = "common") -> JpegHeader:
     """Walk the markers of one file up to SOS → JpegHeader with its kind; never raises on a file's content.
     non_rgb="convert": a one-component frame is a device kind (sampling GRAY) and a four-component one goes to the
     host, where PIL converts it; the default "black" sorts both as BLACK.
     cmyk="device" (with non_rgb="convert" only): a baseline four-component frame that `_frame4` admits is a device
     kind with ncomp 4, comp_hv and `ycck`; progressive four-component files stay HOST, with a reason of their own.
-    Draft scales do not exist for this layout: a caller with a draft request leaves cmyk at "host"."""
+    Draft scales do not exist for this layout: a caller with a draft request leaves cmyk at "host".
+    layouts="all": a baseline three-component frame that the common rules turn away for its sampling or colour space
+    and `_frame3_any` admits is a device kind with `layout` set, comp_hv and `rgb`; progressive ones stay HOST, with a
+    reason of their own.  A file the common rules admit parses as it does without the keyword.  No draft scales either:
+    a caller with a draft request leaves layouts at "common"."""
     check_non_rgb(non_rgb)
     check_cmyk(cmyk, non_rgb)
+    check_layouts(layouts)
     try:
-        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob, non_rgb, cmyk)
+        return _parse(memoryview(blob).cast("B") if not isinstance(blob, bytes) else blob, non_rgb, cmyk, layouts)
     except _Bad as e:
         return JpegHeader(HOST, reason=str(e))
     except (IndexError, ValueError) as e:
@@ -298,7 +338,54 @@ def _frame4(w, header):
                   qtables=[w.qt[c[3]] for c in comps], ycck=t == 2)
 
 
-def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black", cmyk="host"):
+def _frame3_any(w, header):
+    """The three-component frames of layouts="all" that the common rules turn away, by libjpeg's rules.
+    jdapimin.c default_decompress_parms: a JFIF marker means YCbCr; else Adobe transform 0 is RGB and 1 is YCbCr (any
+    other makes libjpeg warn and guess: the host's); with neither marker ids 1, 2, 3 are YCbCr, R, G, B are RGB and
+    anything else is taken for YCbCr.  jdinput.c initial_setup / per_scan_setup: factors in 1..4, at most
+    MAX_MCU_BLOCKS blocks per MCU, the MCU spans the largest factors.  jdsample.c jinit_upsampler: the ratio of the
+    largest factor to each component's has to be integral ("fractional sampling not implemented")."""
+    m, _, height, width, _, comps = w.sof
+    hv = [(c[1], c[2]) for c in comps]
+    if m == 0xC2:
+        raise _Bad(f"3 components, progressive (SOF2), outside the common layouts: {hv}")
+    if width == 0 or height == 0:
+        raise _Bad("DNL / empty frame")
+    ids = [c[0] for c in comps]
+    if w.jfif:
+        rgb = False
+    elif w.adobe:
+        if w.adobe_transform not in (0, 1):
+            raise _Bad(f"3 components with Adobe transform {w.adobe_transform}")
+        rgb = w.adobe_transform == 0
+    else:
+        rgb = ids == [0x52, 0x47, 0x42]
+    if len(set(ids)) != 3:
+        raise _Bad("duplicate component ids")
+    if any(not (1 <= h <= 4 and 1 <= v <= 4) for h, v in hv):
+        raise _Bad(f"sampling {hv}")
+    hmax, vmax = max(h for h, _ in hv), max(v for _, v in hv)
+    if any(hmax % h or vmax % v for h, v in hv):
+        raise _Bad(f"fractional sampling {hv}")
+    blocks = sum(h * v for h, v in hv)
+    if blocks > MAX_MCU_BLOCKS:
+        raise _Bad(f"{blocks} blocks per MCU")
+    for c in comps:
+        if c[3] not in w.qt:
+            raise _Bad("missing DQT")
+    return header(DEVICE, width=width, height=height, ncomp=3, comp_ids=ids, comp_hv=hv,
+                  qtables=[w.qt[c[3]] for c in comps], layout=True, rgb=rgb)
+
+
+def _common3(w):
+    """Whether the common rules of `_frame` admit this three-component frame's colour space and sampling."""
+    comps = w.sof[5]
+    ycc = w.jfif or (w.adobe_transform == 1 if w.adobe else [c[0] for c in comps] == [1, 2, 3])
+    hv = [(c[1], c[2]) for c in comps]
+    return ycc and hv[1] == (1, 1) and hv[2] == (1, 1) and hv[0] in SAMPLING
+
+
+def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black", cmyk="host", layouts="common"):
     """What the frame admits, by libjpeg's rules, at the first SOS → header(BLACK) or header(DEVICE) with the frame
     fields; anything else raises.  sof_kinds: {C0, C1} for `parse`, {C2} for `parse_progressive`."""
     if w.sof is None:
@@ -317,6 +404,8 @@ def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black", cmyk="host"):
         if cmyk == "device":                          # the host's, whichever parser asks, unless `parse` was told
             return _frame4(w, header)                 # cmyk="device"
         raise _Bad("4 components (CMYK / YCCK)")
+    if layouts == "all" and nc == 3 and m in (0xC0, 0xC1, 0xC2) and not _common3(w):
+        return _frame3_any(w, header)
     if m not in sof_kinds:
         raise _Bad(f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
@@ -349,10 +438,10 @@ def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black", cmyk="host"):
                   qtables=[w.qt[c[3]] for c in comps])
 
 
-def _parse(b, non_rgb="black", cmyk="host") -> JpegHeader:
+def _parse(b, non_rgb="black", cmyk="host", layouts="common") -> JpegHeader:
     w = _Walker(b)
     s = next(w.scans(script=False))                   # the first SOS; whatever keeps the walk from it raises
-    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False, non_rgb=non_rgb, cmyk=cmyk)
+    hd = _frame(w, JpegHeader, (0xC0, 0xC1), distinct_ids=False, non_rgb=non_rgb, cmyk=cmyk, layouts=layouts)
     hd.app1 = w.app1
     if hd.kind != DEVICE:
         return hd
@@ -591,11 +680,13 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     width, height = scaled_size((h.width, h.height), scale)
     nmcu = h.mcus_x * h.mcus_y
     four = h.ncomp == 4                               # r is a HEADER4_DTYPE record: h, v and ycck instead of sampling
-    blocks = nmcu * (sum(a * b for a, b in h.comp_hv) if four else BLOCKS_PER_MCU[h.sampling])
+    own = four or h.layout                            # ... or a HEADER3_DTYPE one: h, v and rgb
+    blocks = nmcu * (sum(a * b for a, b in h.comp_hv) if own else BLOCKS_PER_MCU[h.sampling])
     r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
     r["width"], r["height"] = h.width, h.height
-    if four:
-        r["h"], r["v"], r["ycck"] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv], int(h.ycck)
+    if own:
+        r["h"], r["v"] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv]
+        r["ycck" if four else "rgb"] = int(h.ycck if four else h.rgb)
     else:
         r["sampling"] = h.sampling
     r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
@@ -613,13 +704,15 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
 def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None, dtype=HEADER_DTYPE):
     """Header records + workspace totals for a batch of device-kind headers.
     dtype=HEADER4_DTYPE: the four-component headers of one odic_jpeg4_decode call (no scales); their output offsets
-    are rounded up to multiples of 4, which lets the colour kernel store whole words.
+    are rounded up to multiples of 4, which lets the colour kernel store whole words.  dtype=HEADER3_DTYPE: the
+    `layout` headers of one odic_jpeg3_any_decode call, placed the same way.
     data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
     buffer.  scales: 1, 2, 4 or 8 per image (None: all 1), the draft scale its output is placed for.
     → (np array of `dtype` [n], dict of batch totals / maxima, list of output byte offsets, output bytes)."""
     n = len(hdrs)
     rec = np.zeros(n, dtype)
     four = dtype is HEADER4_DTYPE
+    words = four or dtype is HEADER3_DTYPE
     ndc = 4 if four else 3                            # DC tables 0 .. ndc - 1, AC tables behind them
     tot = dict(total_scan_bytes=0, total_intervals=0, total_units=0, total_blocks=0, total_plane_bytes=0,
                max_units=1, max_intervals=1, max_width=1, max_height=1, max_blocks=1, max_scan_bytes=1)
@@ -629,7 +722,7 @@ def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None, dtype=HEA
         scan = data_ends[k] - data_offs[k]
         nint = n_intervals(h)
         units = -(-scan * 8 // subseq_bits) + nint
-        if four:
+        if words:
             out_bytes = (out_bytes + 3) // 4 * 4
         nmcu, out_bytes = _place_image(r, h, tot, out_offs, out_bytes, scales[k] if scales else 1)
         r["data_off"], r["data_end"], r["scan_off"] = data_offs[k], data_ends[k], tot["total_scan_bytes"]
@@ -909,6 +1002,10 @@ class BatchPlan:
     cmyk_off: int = None           # staging offset of their HEADER4_DTYPE records; None without them
     cout_off: int = 0              # where their part of the RGB output starts (256-aligned) ...
     cout_bytes: int = 0            # ... and its bytes
+    ltot: dict = None              # the same four for the `layout` files (`parse(..., layouts="all")`, HEADER3_DTYPE), the
+    layout_off: int = None         # last group of all
+    lout_off: int = 0
+    lout_bytes: int = 0
 
     def fill(self, host):
         """Write the sections and the files into the uint8 array `host` of at least `total` bytes."""
@@ -916,14 +1013,17 @@ class BatchPlan:
             host[o:o + a.nbytes] = a.view(np.uint8)
 
 
-def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(), cblobs=()) -> BatchPlan:
+def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(), cblobs=(), lhdrs=(),
+                      lblobs=()) -> BatchPlan:
     """The layout of one device decode of the baseline files (hdrs, blobs: DEVICE-kind `parse` results and their bytes)
     and the progressive ones (phdrs, pblobs: `parse_progressive`).  scales: the draft scale of every image, baseline
     first.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
     chdrs, cblobs: the four-component files (`parse(..., "convert", cmyk="device")`, ncomp 4), one more group behind the
     others: its records behind the scales, its files behind the progressive ones, its output behind theirs from the
-    next multiple of 256.  They have no scales.  Without them the plan is what it is without these arguments."""
-    nb, npg, ncm = len(hdrs), len(phdrs), len(chdrs)
+    next multiple of 256.  They have no scales.  Without them the plan is what it is without these arguments.
+    lhdrs, lblobs: the `layout` files (`parse(..., layouts="all")`), the last group, placed by the same rule behind the
+    four-component one."""
+    nb, npg, ncm, nly = len(hdrs), len(phdrs), len(chdrs), len(lhdrs)
     scales = list(scales)[:nb + npg]
     sections, pos = [], pad256(nb * HEADER_DTYPE.itemsize)
     ptot = prog_off = scale_off = None
@@ -940,8 +1040,12 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     if ncm:
         cmyk_off = pos
         pos += pad256(ncm * HEADER4_DTYPE.itemsize)
+    layout_off = None
+    if nly:
+        layout_off = pos
+        pos += pad256(nly * HEADER3_DTYPE.itemsize)
     data_off = pos
-    every = list(blobs) + list(pblobs) + list(cblobs)
+    every = list(blobs) + list(pblobs) + list(cblobs) + list(lblobs)
     starts = np.cumsum([0] + [len(b) for b in every]).tolist()                          # inside the data area
     tot, out_offs, out_bytes = None, [], 0
     if nb:
@@ -957,12 +1061,22 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     if ncm:
         first = nb + npg
         crec, ctot, cout_offs, cout_bytes = pack_headers(
-            chdrs, [o + h.data_offset for o, h in zip(starts[first:], chdrs)], starts[first + 1:], subseq_bits,
-            dtype=HEADER4_DTYPE)
+            chdrs, [o + h.data_offset for o, h in zip(starts[first:], chdrs)], starts[first + 1:first + ncm + 1],
+            subseq_bits, dtype=HEADER4_DTYPE)
         sections.append((cmyk_off, crec))
         cout_off = pad256(out_bytes + (pout_bytes if npg else 0))
         out_offs = out_offs + [cout_off + o for o in cout_offs]
         extra = dict(ctot=ctot, cmyk_off=cmyk_off, cout_off=cout_off, cout_bytes=cout_bytes)
+    if nly:
+        first = nb + npg + ncm
+        lrec, ltot, lout_offs, lout_bytes = pack_headers(
+            lhdrs, [o + h.data_offset for o, h in zip(starts[first:], lhdrs)], starts[first + 1:], subseq_bits,
+            dtype=HEADER3_DTYPE)
+        sections.append((layout_off, lrec))
+        before = cout_off + cout_bytes if ncm else out_bytes + (pout_bytes if npg else 0)
+        lout_off = pad256(before)
+        out_offs = out_offs + [lout_off + o for o in lout_offs]
+        extra.update(ltot=ltot, layout_off=layout_off, lout_off=lout_off, lout_bytes=lout_bytes)
     files = [(data_off + o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, every)]
     coef_off = [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])] if npg else []
     return BatchPlan(sections, data_off, files, data_off + starts[-1], tot, ptot, prog_off, scale_off, out_offs,

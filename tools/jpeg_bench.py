@@ -27,6 +27,12 @@ host's `Image.open(f).convert("RGB")`.  This is the line that decides whether cm
 
     python tools/jpeg_bench.py --cmyk --batches 16 64 --iters 20 --out profiles/jpeg_cmyk_bench.json
 
+--layouts: 640x480 gradient-plus-noise pictures written at 4:4:0 and 4:1:1 by the tests' writer (Pillow's encoder cannot),
+eight distinct files per layout repeated to the batch size: the device path with layouts="all" (odic_jpeg3_any_decode)
+against the host's `Image.open(f).convert("RGB")` on one thread.  One line per layout and batch.
+
+    python tools/jpeg_bench.py --layouts --batches 16 64 --iters 20 --out profiles/jpeg_layouts_bench.json
+
 --draft: what decoding at the scale `Image.draft("RGB", (S, S))` picks saves.  Seeded synthetic JPEGs,
 3456x4608 (drafts at 1/8) and 640x480 (drafts at 1/1: the control), 4:2:0 and 4:4:4, baseline and progressive; per
 case `decode_jpeg` alone and `from_jpeg_bytes` (decode + resize), draft off and on alternating in the same process,
@@ -87,6 +93,16 @@ def make_inputs(n: int, seed: int = 0, progressive: bool = False, gray: bool = F
 
 
 @functools.lru_cache(maxsize=None)
+def layout_inputs(layout: str, n: int, distinct: int = 8):
+    """n files of 640x480 at `layout` (a key of tests/jpeg_layout_cases.LAYOUTS): `distinct` pictures, repeated."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from jpeg_layout_cases import LAYOUTS, picture
+    from jpeg_layout_writer import write_jpeg3
+    hv, style = LAYOUTS[layout]
+    files = [write_jpeg3(picture(480, 640, seed=k, noise=True), hv, style) for k in range(min(n, distinct))]
+    return [files[k % len(files)] for k in range(n)]
+
+
 def synthetic_rgb(h: int, w: int, seed: int) -> np.ndarray:
     """A seeded image with a photograph's spectrum, roughly: smooth fields at three scales plus sensor-like noise."""
     from PIL import Image
@@ -283,6 +299,7 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="progressive re-saves of the crops, and tatin.jpg")
     ap.add_argument("--gray", action="store_true", help="the crops as one-component files, non_rgb='convert'")
     ap.add_argument("--cmyk", action="store_true", help="the crops as four-component files, non_rgb='convert', cmyk='device'")
+    ap.add_argument("--layouts", action="store_true", help="4:4:0 and 4:1:1 files from the tests' writer, layouts='all'")
     ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
     ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
     ap.add_argument("--orient", action="store_true", help="odic_orient_rgb8 against a copy; orientation='exif' end to end")
@@ -300,11 +317,23 @@ def main():
     pre = DevicePreprocessor(args.size, "cuda:0")
     if args.cmyk and (args.gray or args.progressive):
         ap.error("--cmyk goes alone: the four-component route is baseline only")
-    blobs_all = make_inputs(max(args.batches), progressive=args.progressive, gray=args.gray, cmyk=args.cmyk)
+    if args.layouts and (args.gray or args.progressive or args.cmyk):
+        ap.error("--layouts goes alone: the route is baseline three-component files only")
     non_rgb = "convert" if args.gray or args.cmyk else "black"
-    route_kw = {"cmyk": "device"} if args.cmyk else {}
-    want_route = "device-cmyk" if args.cmyk else "device-progressive" if args.progressive else "device"
-    inputs = [(B, blobs_all[:B], (640, 480)) for B in args.batches]
+    route_kw = {"cmyk": "device"} if args.cmyk else {"layouts": "all"} if args.layouts else {}
+    want_route = ("device-cmyk" if args.cmyk else "device-layout" if args.layouts else
+                  "device-progressive" if args.progressive else "device")
+    names = {}                                           # id of a batch's list → its layout
+    if args.layouts:
+        inputs = []
+        for layout in ("440", "411"):
+            blobs_all = layout_inputs(layout, max(args.batches))
+            for B in args.batches:
+                inputs.append((B, blobs_all[:B], (640, 480)))
+                names[id(inputs[-1][1])] = layout
+    else:
+        blobs_all = make_inputs(max(args.batches), progressive=args.progressive, gray=args.gray, cmyk=args.cmyk)
+        inputs = [(B, blobs_all[:B], (640, 480)) for B in args.batches]
     parse_us = None
     if args.progressive:
         from on_device_image_captioning_amd import jpeg as J
@@ -320,7 +349,7 @@ def main():
         parse_us = 1e6 * (time.perf_counter() - t0) / (5 * len(blobs_all))
 
     def host(blobs):
-        if args.gray or args.cmyk:
+        if args.gray or args.cmyk or args.layouts:
             return pre([np.asarray(Image.open(io.BytesIO(b)).convert("RGB")) for b in blobs])
         return pre([np.asarray(Image.open(io.BytesIO(b))) for b in blobs])
 
@@ -366,7 +395,8 @@ def main():
                         ts.append(time.perf_counter() - t0)
                     sweep[f"bits{bits}_passes{passes}"] = B / float(np.median(ts))
         line = {"batch": B, "width": width, "height": height, "quality": 90,
-                "subsampling": "gray" if args.gray else "cmyk 2x2,1x1,1x1,1x1" if args.cmyk else "4:2:0",
+                "subsampling": "gray" if args.gray else "cmyk 2x2,1x1,1x1,1x1" if args.cmyk else
+                {"440": "4:4:0", "411": "4:1:1"}[names[id(blobs)]] if args.layouts else "4:2:0",
                 "progressive": args.progressive,
                 "mean_jpeg_bytes": int(np.mean([len(b) for b in blobs])),
                 "host_images_per_s": B / med["host"], "device_images_per_s": B / med["device"],
