@@ -70,7 +70,8 @@ extern "C" {
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
  *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
  *       odic_lcs_pairs, odic_orient_rgb8, odic_jpeg4_workspace_bytes, odic_jpeg4_decode, odic_cmyk_to_rgb8,
- *       odic_jpeg3_any_workspace_bytes, odic_jpeg3_any_decode. */
+ *       odic_jpeg3_any_workspace_bytes, odic_jpeg3_any_decode, odic_jpeg_progressive_any_workspace_bytes,
+ *       odic_jpeg_decode_progressive_any. */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -479,7 +480,8 @@ typedef struct odic_jpeg_scan {
   int64_t data_off, data_end, scan_off;
   int32_t image, int_off, n_intervals, restart, n_units, blocks_w, comp_mask, ss, se, ah, al, level;
   int32_t table[3];
-  int32_t pad;
+  int32_t pad;                   /* odic_jpeg_decode_progressive_any: the fourth DC table index of an interleaved first DC
+                                    scan of four components, else -1; the other entry points never read it */
 } odic_jpeg_scan;
 
 typedef struct odic_jpeg_prog_batch {
@@ -513,6 +515,42 @@ int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* batch, void* worksp
 /* odic_jpeg_decode_scaled for progressive files: scale_log2 as there, everything else as odic_jpeg_decode_progressive. */
 int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* batch, const int32_t* scale_log2, void* workspace,
                                         size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Progressive files with per-component sampling: four components (CMYK / YCCK) and three components at the layouts of
+ * odic_jpeg_header3, YCbCr or RGB, bit-exact with np.asarray(PIL.Image.open(f).convert("RGB")).
+ * jpeg.parse_progressive(..., cmyk="device") / (..., layouts="all") admits them.  The record starts with
+ * odic_jpeg_prog_header's fields (`color` in the place of `sampling`) and goes on with the frame:
+ *   color        three components: 1 the components are R, G, B as stored, 0 Y, Cb, Cr (odic_jpeg_header3's `rgb`);
+ *                four components: 1 YCCK, 0 CMYK as stored (odic_jpeg_header4's `ycck`)
+ *   ncomp        3 or 4
+ *   h / v        sampling factors of each component (entries from ncomp on are not read).  mcus_x = ceil(W / (8 max h)),
+ *                mcus_y = ceil(H / (8 max v)); coefficient blocks MCU by MCU and planes as odic_jpeg_header4 has them
+ *   qt           quantisation table of each component, natural order
+ * Frame rules, checked on the device: ncomp 3 or 4; factors in 1..4, every factor a divisor of the largest in its
+ * direction, at most 10 blocks per MCU; four components: component 0 at 1x1, 2x1 or 2x2 and every other one at 1x1 or at
+ * component 0's sampling.  Scans are odic_jpeg_scan records under the rules above with comp_mask four bits wide and, for
+ * an interleaved first DC scan of four components, the fourth table index in `pad`; an interleaved scan walks the
+ * frame's MCUs (largest factors) whichever components it names, a single-component scan the component's own raster.
+ * A record that breaks the frame rules, or a scan of it whose mask names a component the frame lacks, is not decoded.
+ * An image with status 1 — by these rules or by those of odic_jpeg_decode_progressive — has none of its pixels written.
+ * Upsampling and colour are odic_jpeg3_any_decode's (three components) and odic_jpeg4_decode's (four).  Full size only.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct odic_jpeg_prog_header_any {
+  int64_t out_off, coef_off, plane_off;
+  int32_t width, height, color, mcus_x, mcus_y, n_intervals;
+  int32_t ncomp, pad;
+  int32_t h[4], v[4];
+  uint16_t qt[4][64];
+} odic_jpeg_prog_header_any;        /* 600 bytes */
+
+/* odic_jpeg_progressive_workspace_bytes / odic_jpeg_decode_progressive for a batch whose `headers` are
+ * odic_jpeg_prog_header_any [n_images]: the same descriptor, workspace layout, per-level launches and contract (all
+ * launches on `stream`, no allocation, no host synchronisation; only `workspace`, `out` and `status` are written —
+ * test_progressive_any_decode_stays_inside_its_workspace).  An out_off that is a multiple of 4 lets the colour kernels
+ * store whole words. */
+size_t odic_jpeg_progressive_any_workspace_bytes(const odic_jpeg_prog_batch* batch);
+int odic_jpeg_decode_progressive_any(const odic_jpeg_prog_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core  (WindowAttention.forward swin_transformer_mod.py:193-211

@@ -49,6 +49,10 @@
 // same templates again up to the IDCT, which writes three planes; jpeg_color3_kernel reads every component through
 // upsampled_by() — copy, h2v1 / h2v2 / h1v2 fancy, or replication by an integral ratio — and converts or copies.
 //
+// Progressive files of those two kinds (odic_jpeg_decode_progressive_any) have the record odic_jpeg_prog_header_any:
+// the progressive decode kernel and its coding procedures instantiated for per-component block geometry (ProgGeo), then
+// the same per-component IDCT and the two colour kernels above.
+//
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
 // whose coefficients leave the range where libjpeg-turbo's SIMD and C IDCTs agree (kIdctLimit), gets status 1:
@@ -207,17 +211,32 @@ struct Frame<odic_jpeg_header4> {
 // parser applies before it packs a record: factors in 1..4, at most 10 blocks, every factor a divisor of the largest.
 // A record that breaks it is a frame of one block of component 0 to the entropy kernels, which stay inside whatever
 // the record's offsets span; the IDCT and the colour pass write nothing for it and the image gets status 1.
-__device__ __forceinline__ bool layout_ok(const odic_jpeg_header3& h) {
+__device__ __forceinline__ bool factors_ok(const int* h, const int* v, int ncomp) {
   int hm = 1, vm = 1, n = 0;
-  for (int c = 0; c < 3; ++c) {
-    if ((unsigned)(h.h[c] - 1) > 3u || (unsigned)(h.v[c] - 1) > 3u) return false;
-    hm = max(hm, h.h[c]);
-    vm = max(vm, h.v[c]);
-    n += h.h[c] * h.v[c];
+  for (int c = 0; c < ncomp; ++c) {
+    if ((unsigned)(h[c] - 1) > 3u || (unsigned)(v[c] - 1) > 3u) return false;
+    hm = max(hm, h[c]);
+    vm = max(vm, v[c]);
+    n += h[c] * v[c];
   }
   if (n > kMaxMcuBlocks4) return false;
-  for (int c = 0; c < 3; ++c)
-    if (hm % h.h[c] || vm % h.v[c]) return false;
+  for (int c = 0; c < ncomp; ++c)
+    if (hm % h[c] || vm % v[c]) return false;
+  return true;
+}
+__device__ __forceinline__ bool layout_ok(const odic_jpeg_header3& h) { return factors_ok(h.h, h.v, 3); }
+__device__ __forceinline__ bool layout_ok(const odic_jpeg_header4&) { return true; }   // the parser's rules, not checked here
+// The progressive record with per-component sampling: three components under the rules above, or four under those the
+// parser applies to odic_jpeg_header4, which jpeg_color4_kernel's plane addressing relies on: component 0 at 1x1, 2x1
+// or 2x2, every other component at 1x1 or at component 0's sampling.
+__device__ __forceinline__ bool layout_ok(const odic_jpeg_prog_header_any& h) {
+  if (h.ncomp != 3 && h.ncomp != 4) return false;
+  if (!factors_ok(h.h, h.v, h.ncomp)) return false;
+  if (h.ncomp == 4) {
+    if (h.h[0] > 2 || h.v[0] > h.h[0]) return false;
+    for (int c = 1; c < 4; ++c)
+      if ((h.h[c] != 1 || h.v[c] != 1) && (h.h[c] != h.h[0] || h.v[c] != h.v[0])) return false;
+  }
   return true;
 }
 template <>
@@ -237,6 +256,11 @@ struct Frame<odic_jpeg_header3> {
 };
 __device__ __forceinline__ int mcu_blocks(const odic_jpeg_header4& h) { return Frame<odic_jpeg_header4>(h).bpm; }
 __device__ __forceinline__ int mcu_blocks(const odic_jpeg_header3& h) { return Frame<odic_jpeg_header3>(h).bpm; }
+__device__ __forceinline__ int mcu_blocks(const odic_jpeg_prog_header_any& h) {   // of a record layout_ok() admits
+  int n = 0;
+  for (int c = 0; c < h.ncomp; ++c) n += h.h[c] * h.v[c];
+  return n;
+}
 template <typename Header>
 __device__ __forceinline__ int mcu_blocks(const Header& h) { return blocks_per_mcu(h.sampling); }
 
@@ -905,6 +929,13 @@ __device__ __forceinline__ BlockGeo block_geo_own(const Header& h, int j) {
 }
 __device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j, int, int) { return block_geo_own<4>(h, j); }
 __device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header3& h, int j, int, int) { return block_geo_own<3>(h, j); }
+__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_prog_header_any& h, int j, int, int) {
+  return h.ncomp == 4 ? block_geo_own<4>(h, j) : block_geo_own<3>(h, j);
+}
+// the records whose frame rules are checked on the device (layout_ok): an image that breaks them is not decoded
+template <typename Header>
+constexpr bool kHasFrameRules =
+    std::is_same<Header, odic_jpeg_header3>::value || std::is_same<Header, odic_jpeg_prog_header_any>::value;
 
 // One block per 8 lanes: column pass → LDS → row pass, n×n samples into the component's plane.  kScaled = false is
 // the full-size decode (lg = 0, n = 8 throughout, the branches below fold away).  A scaled image's planes keep the
@@ -913,7 +944,7 @@ __device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header3& h, int j,
 // only the input and the result).  libjpeg-turbo's SIMD 4x4 / 2x2 keep the same 16-bit intermediates as its 8x8.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int img, int lg, int (*ws8)[8][9]) {
-  if constexpr (std::is_same<Header, odic_jpeg_header3>::value) {
+  if constexpr (kHasFrameRules<Header>) {
     if (!layout_ok(h)) return;                                // the whole workgroup: one image per blockIdx.y
   }
   const int bpm = mcu_blocks(h);                              // gray: every block is component 0
@@ -1150,6 +1181,26 @@ __device__ __forceinline__ void store_rgb4(unsigned char* __restrict__ o, const 
 
 constexpr int kColor4Pixels = 4;                   // pixels per lane of the two kernels below
 
+// What the two per-component colour kernels read of their records.  odic_jpeg_prog_header_any serves both: an image
+// of four components is jpeg_color4_kernel's, every other one jpeg_color3_kernel's (where layout_ok() refuses a count
+// that is not 3), and its pixels are written only where the whole decode succeeded — the state words are final by then,
+// every kernel that sets them lies ahead of the colour kernels on the stream.
+__device__ __forceinline__ int colour_comps(const odic_jpeg_header4&) { return 4; }
+__device__ __forceinline__ int colour_comps(const odic_jpeg_header3&) { return 3; }
+__device__ __forceinline__ int colour_comps(const odic_jpeg_prog_header_any& h) { return h.ncomp == 4 ? 4 : 3; }
+__device__ __forceinline__ int colour_flag(const odic_jpeg_header4& h) { return h.ycck; }
+__device__ __forceinline__ int colour_flag(const odic_jpeg_header3& h) { return h.rgb; }
+__device__ __forceinline__ int colour_flag(const odic_jpeg_prog_header_any& h) { return h.color; }
+template <typename Header>
+__device__ __forceinline__ bool image_status_ok(const Header& h, const int* st) {
+  return layout_ok(h) && st[0] == 0 && st[1] == h.n_intervals;
+}
+template <typename Header>
+__device__ __forceinline__ bool pixels_wanted(const Header& h, const int* st) {
+  if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) return image_status_ok(h, st);
+  else return layout_ok(h);
+}
+
 __global__ __launch_bounds__(256) void cmyk_to_rgb8_kernel(const unsigned char* __restrict__ cmyk,
                                                            unsigned char* __restrict__ rgb, long n_pixels, int invert) {
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
@@ -1169,18 +1220,18 @@ __global__ __launch_bounds__(256) void cmyk_to_rgb8_kernel(const unsigned char* 
 // Four consecutive pixels of the image's H·W per lane: every component is read at its own sampling (a component at
 // component 0's sampling lies on the output grid, a 1x1 one under 2x1 / 2x2 is upsampled as chroma is above, K
 // included), then the chain of the comment above; plus the per-image status.
-__global__ __launch_bounds__(256) void jpeg_color4_kernel(const odic_jpeg_header4* __restrict__ hdrs, Ws ws,
+template <typename Header>                                      // odic_jpeg_header4 or odic_jpeg_prog_header_any
+__global__ __launch_bounds__(256) void jpeg_color4_kernel(const Header* __restrict__ hdrs, Ws ws,
                                                           unsigned char* __restrict__ out, int* __restrict__ status) {
   const int img = blockIdx.y;
-  const odic_jpeg_header4& h = hdrs[img];
+  const Header& h = hdrs[img];
+  if (colour_comps(h) != 4) return;
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
-  if (p0 == 0) {
-    const int* st = ws.state + kStateWords * img;
-    status[img] = (st[0] == 0 && st[1] == h.n_intervals) ? 0 : 1;
-  }
+  const int* st = ws.state + kStateWords * img;
+  if (p0 == 0) status[img] = image_status_ok(h, st) ? 0 : 1;
   const int W = h.width, H = h.height;
   const long npix = (long)W * H;
-  if (p0 >= npix) return;
+  if (!pixels_wanted(h, st) || p0 >= npix) return;
   const int n = (int)min((long)kColor4Pixels, npix - p0);
   const unsigned char* P[4];
   int pw[4];
@@ -1202,7 +1253,7 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(const odic_jpeg_header
 #pragma unroll
     for (int c = 0; c < 4; ++c)
       s[c] = full[c] ? P[c][(long)y * pw[c] + x] : upsampled(P[c], pw[c], x, y, v2, dw <= 2, dw, dh);
-    if (h.ycck) {
+    if (colour_flag(h)) {
       const int cb = s[1] - 128, cr = s[2] - 128, yv = s[0];
       s[0] = 255 - clamp255(yv + ((kCrR * cr + 32768) >> 16));
       s[1] = 255 - clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
@@ -1217,19 +1268,18 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(const odic_jpeg_header
 // through upsampled_by() at its own ratio to the largest sampling — component 0 too, where it is not the largest —
 // then ycc_rgb_convert, or the three samples as they are for an RGB file; plus the per-image status.  A record that
 // layout_ok() refuses has status 1 and no pixels.
-__global__ __launch_bounds__(256) void jpeg_color3_kernel(const odic_jpeg_header3* __restrict__ hdrs, Ws ws,
+template <typename Header>                                      // odic_jpeg_header3 or odic_jpeg_prog_header_any
+__global__ __launch_bounds__(256) void jpeg_color3_kernel(const Header* __restrict__ hdrs, Ws ws,
                                                           unsigned char* __restrict__ out, int* __restrict__ status) {
   const int img = blockIdx.y;
-  const odic_jpeg_header3& h = hdrs[img];
+  const Header& h = hdrs[img];
+  if (colour_comps(h) != 3) return;
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
-  const bool ok = layout_ok(h);
-  if (p0 == 0) {
-    const int* st = ws.state + kStateWords * img;
-    status[img] = (ok && st[0] == 0 && st[1] == h.n_intervals) ? 0 : 1;
-  }
+  const int* st = ws.state + kStateWords * img;
+  if (p0 == 0) status[img] = image_status_ok(h, st) ? 0 : 1;
   const int W = h.width, H = h.height;
   const long npix = (long)W * H;
-  if (!ok || p0 >= npix) return;
+  if (!pixels_wanted(h, st) || p0 >= npix) return;
   const int n = (int)min((long)kColor4Pixels, npix - p0);
   const int hm = max(h.h[0], max(h.h[1], h.h[2])), vm = max(h.v[0], max(h.v[1], h.v[2]));
   const unsigned char* P[3];
@@ -1251,7 +1301,7 @@ __global__ __launch_bounds__(256) void jpeg_color3_kernel(const odic_jpeg_header
     int s[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) s[c] = upsampled_by(P[c], pw[c], x, y, rh[c], rv[c], dw[c], dh[c]);
-    if (h.rgb) {
+    if (colour_flag(h)) {
       for (int c = 0; c < 3; ++c) px[3 * i + c] = (unsigned char)s[c];
     } else {
       ycc_rgb_pixel(s[0], s[1], s[2], px + 3 * i);
@@ -1285,11 +1335,38 @@ __global__ __launch_bounds__(256) void jpeg_color3_kernel(const odic_jpeg_header
 // index is checked against the image's block count; a zig-zag index is checked against Se <= 63 before it is used;
 // the bit reader only advances while pos <= the interval's end, which keeps its look-ahead inside the 16 bytes reserved
 // behind every compacted scan, and correction bits are fetched only after pos <= end was checked for the whole block.
+//
+// Frames with per-component sampling (odic_jpeg_prog_header_any: four components, or three at any layout; entry point
+// odic_jpeg_decode_progressive_any) run the same segment kernel and the same decode kernel and coding procedures,
+// instantiated for that record: what differs is ProgGeo, the frame as the scans see it.  An interleaved scan walks the
+// frame's MCUs, which span the largest factors whichever components the scan names, and writes the named components'
+// blocks of each; a single-component scan walks the component's own raster, so the padding blocks outside it keep what
+// the interleaved scans gave them (zero where there was none).  Then jpeg_idct_kernel for the record (block_geo_own)
+// and both per-component colour kernels, each of which takes the images of its component count.
+//
+// The bounds argument for that record.  The geometry is built only from a record layout_ok() admits: ncomp 3 or 4,
+// factors in 1..4 that divide the largest, at most 10 blocks per MCU, so hh, vv in 1..4 and first + nb <= bpm <= 10 fit
+// ProgGeo's four-bit fields; a scan whose mask names a component >= ncomp is refused before anything is read, so hh / vv
+// of a named component are the record's own and never 0.  Every block index, from raster_block() (single-component
+// scans; bw is the scan's own and only has to be positive) or from u · bpm + first + j (interleaved scans, j < nb), is
+// compared with nblocks = mcus_x · mcus_y · bpm before the coefficient array is touched, and the host sizes that array
+// (coef_off, total_blocks) by the same product; the zig-zag index and bit reader rules are those above, unchanged.
+// The IDCT reads block b < nblocks and writes plane bytes below 64 · nblocks from plane_off (block_geo_own places
+// block j of MCU m at a row and column inside plane c's mcus_x·8·h[c] by mcus_y·8·v[c] samples); it returns at once
+// for a record layout_ok() refuses.  The colour kernels return before reading a plane, and write status 1 and no
+// pixel, for such a record and for any image whose state words report an error or a missing interval; otherwise
+// they read sample (y / rv, x / rh) and its neighbours clamped to the component's dw x dh real samples, which lie
+// inside its plane because W <= mcus_x · 8 · hmax and H <= mcus_y · 8 · vmax.
 // ---------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(odic_jpeg_prog_header) == 432 && offsetof(odic_jpeg_prog_header, qt) == 48 &&
                   sizeof(odic_jpeg_scan) == 88 && offsetof(odic_jpeg_scan, table) == 72 &&
                   sizeof(odic_jpeg_table) == 1424 && offsetof(odic_jpeg_table, huffval) == 1168,
               "the progressive records are mirrored by jpeg.PROG_HEADER_DTYPE / SCAN_DTYPE / TABLE_DTYPE");
+static_assert(sizeof(odic_jpeg_prog_header_any) == 600 && offsetof(odic_jpeg_prog_header_any, ncomp) == 48 &&
+                  offsetof(odic_jpeg_prog_header_any, h) == 56 && offsetof(odic_jpeg_prog_header_any, qt) == 88 &&
+                  offsetof(odic_jpeg_prog_header_any, n_intervals) == offsetof(odic_jpeg_prog_header, n_intervals) &&
+                  offsetof(odic_jpeg_scan, pad) == 84,
+              "odic_jpeg_prog_header_any is mirrored by jpeg.PROG_HEADER_ANY_DTYPE; it shares odic_jpeg_prog_header's prefix");
 
 struct PTab {                      // one Huffman table in LDS
   unsigned short lut[512];
@@ -1306,11 +1383,66 @@ __device__ void load_ptab(const odic_jpeg_table& g, PTab& T) {          // one w
   if (t == 0) fill_lim(g.maxcode, T.lim, 0);
 }
 
+// The frame as the scans see it: the blocks of an MCU, and for component c its blocks per MCU across and down
+// (hh, vv), their number (nb) and the place of the first of them in the MCU (first) — the inverse of the map from a
+// block of the MCU to its component that the IDCT follows (block_geo / block_geo_own).  set() is false for a frame or
+// a scan mask the kernel does not decode; the geometry is then that of one 1x1 block, which nothing reads.
+template <typename Header>
+struct ProgGeo;
+// three components or gray: component 0 carries the only sub-sampling
+template <>
+struct ProgGeo<odic_jpeg_prog_header> {
+  static constexpr int kComps = 3;
+  int nY, bpm, hy, vy;
+  __device__ __forceinline__ bool set(const odic_jpeg_prog_header& h, int mask, int blocks_w) {
+    nY = luma_blocks(h.sampling);
+    bpm = blocks_per_mcu(h.sampling);                    // gray: the MCU order is the component's block raster
+    hy = luma_h(h.sampling);
+    vy = luma_v(h.sampling);
+    return h.sampling != kGray || (mask == 1 && blocks_w > 0);   // gray: component 0 alone, every scan
+  }
+  __device__ __forceinline__ int hh(int c) const { return c == 0 ? hy : 1; }
+  __device__ __forceinline__ int vv(int c) const { return c == 0 ? vy : 1; }
+  __device__ __forceinline__ int nb(int c) const { return c == 0 ? nY : 1; }
+  __device__ __forceinline__ int first(int c) const { return c == 0 ? 0 : nY + c - 1; }
+};
+// three or four components, each with its own sampling (layout_ok: factors in 1..4, at most 10 blocks), four bits per
+// component and field: block_geo_own's order, component after component, each row by row
+template <>
+struct ProgGeo<odic_jpeg_prog_header_any> {
+  static constexpr int kComps = 4;
+  unsigned hp, vp, fp;
+  int bpm;
+  __device__ __forceinline__ bool set(const odic_jpeg_prog_header_any& h, int mask, int) {
+    hp = vp = 0x1111u;
+    fp = 0;
+    bpm = 1;
+    if (!layout_ok(h) || (mask >> h.ncomp) != 0) return false;   // the mask names a component the frame lacks
+    hp = vp = 0;
+    bpm = 0;
+    for (int c = 0; c < 4; ++c) {
+      const bool have = c < h.ncomp;
+      hp |= (unsigned)(have ? h.h[c] : 1) << (4 * c);
+      vp |= (unsigned)(have ? h.v[c] : 1) << (4 * c);
+      fp |= (unsigned)bpm << (4 * c);
+      if (have) bpm += h.h[c] * h.v[c];
+    }
+    return true;
+  }
+  __device__ __forceinline__ int hh(int c) const { return (hp >> (4 * c)) & 15; }
+  __device__ __forceinline__ int vv(int c) const { return (vp >> (4 * c)) & 15; }
+  __device__ __forceinline__ int nb(int c) const { return hh(c) * vv(c); }
+  __device__ __forceinline__ int first(int c) const { return (fp >> (4 * c)) & 15; }
+};
+
+template <typename Header>
 struct ScanCtx {
+  static constexpr int kComps = ProgGeo<Header>::kComps;
   const unsigned* w;               // the scan's compacted words
   short* coef;                     // the image's coefficient blocks
   long nblocks;                    // ... and how many there are
-  int mcus_x, nY, bpm, hy, vy;
+  int mcus_x;
+  ProgGeo<Header> g;
   int u0, nu;                      // the interval's units (MCUs of an interleaved scan, else blocks of the component)
   int pos, end;                    // its bit range
   int mask, ss, se, al, bw;
@@ -1318,11 +1450,12 @@ struct ScanCtx {
 };
 
 // block `n` of component c's own raster (bw blocks per row) → its block index in the MCU-ordered coefficient array
-__device__ __forceinline__ long raster_block(const ScanCtx& x, int c, int n) {
+template <typename X>
+__device__ __forceinline__ long raster_block(const X& x, int c, int n) {
   const int bx = n % x.bw, by = n / x.bw;
-  const int hh = c == 0 ? x.hy : 1, vv = c == 0 ? x.vy : 1;
+  const int hh = x.g.hh(c), vv = x.g.vv(c);
   const long mcu = (long)(by / vv) * x.mcus_x + bx / hh;
-  return mcu * x.bpm + (c == 0 ? 0 : x.nY + c - 1) + (by % vv) * hh + bx % hh;
+  return mcu * x.g.bpm + x.g.first(c) + (by % vv) * hh + bx % hh;
 }
 
 __device__ __forceinline__ unsigned bit_at(const unsigned* __restrict__ w, int pos) {
@@ -1330,17 +1463,18 @@ __device__ __forceinline__ unsigned bit_at(const unsigned* __restrict__ w, int p
 }
 
 // DC, first pass (G.1.2.1): difference coding, prediction reset at the interval's start, value << Al
-__device__ bool prog_dc_first(ScanCtx& x, const PTab* T) {
-  int pred[3] = {0, 0, 0};
+template <typename X>
+__device__ bool prog_dc_first(X& x, const PTab* T) {
+  int pred[X::kComps] = {};
   Bits br{x.w, 0};
   bits_seek(br, x.pos);
   const bool single = (x.mask & (x.mask - 1)) == 0;
   for (int u = x.u0; u < x.u0 + x.nu; ++u) {
     int q = 0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < X::kComps; ++c) {
       if (!((x.mask >> c) & 1)) continue;
-      const int nb = (c == 0 && !single) ? x.nY : 1;
+      const int nb = single ? 1 : x.g.nb(c);
       for (int j = 0; j < nb; ++j) {
         if (x.pos > x.end) return false;
         const unsigned win = bits_peek(br, x.pos);
@@ -1352,7 +1486,7 @@ __device__ bool prog_dc_first(ScanCtx& x, const PTab* T) {
         pred[c] += diff;
         const int v = pred[c] * (1 << x.al);
         if (v < -32768 || v > 32767) atomicOr(&x.state[0], kErrRange);
-        const long b = single ? raster_block(x, c, u) : (long)u * x.bpm + (c == 0 ? 0 : x.nY + c - 1) + j;
+        const long b = single ? raster_block(x, c, u) : (long)u * x.g.bpm + x.g.first(c) + j;
         if (b < 0 || b >= x.nblocks) return false;
         if (threadIdx.x == 0) x.coef[b * 64] = (short)v;
       }
@@ -1363,9 +1497,12 @@ __device__ bool prog_dc_first(ScanCtx& x, const PTab* T) {
 }
 
 // DC, refinement (G.1.2.1): one raw bit per block, 64 blocks per step
-__device__ bool prog_dc_refine(ScanCtx& x) {
+template <typename X>
+__device__ bool prog_dc_refine(X& x) {
   const bool single = (x.mask & (x.mask - 1)) == 0;
-  const int bps = single ? 1 : ((x.mask & 1) ? x.nY : 0) + ((x.mask >> 1) & 1) + ((x.mask >> 2) & 1);
+  int bps = 0;                                          // blocks per MCU of this scan
+  for (int c = 0; c < X::kComps; ++c) bps += ((x.mask >> c) & 1) ? x.g.nb(c) : 0;
+  if (single) bps = 1;
   const long nb = (long)x.nu * bps;
   if (x.pos + nb > x.end) return false;
   bool ok = true;
@@ -1375,16 +1512,16 @@ __device__ bool prog_dc_refine(ScanCtx& x) {
       b = raster_block(x, __builtin_ctz(x.mask), x.u0 + (int)i);
     } else {
       int idx = (int)(i % bps), j = 0;
-      for (int c = 0; c < 3; ++c) {
+      for (int c = 0; c < X::kComps; ++c) {
         if (!((x.mask >> c) & 1)) continue;
-        const int n = c == 0 ? x.nY : 1;
+        const int n = x.g.nb(c);
         if (idx < n) {
-          j = (c == 0 ? 0 : x.nY + c - 1) + idx;
+          j = x.g.first(c) + idx;
           break;
         }
         idx -= n;
       }
-      b = (long)(x.u0 + i / bps) * x.bpm + j;
+      b = (long)(x.u0 + i / bps) * x.g.bpm + j;
     }
     if (b < 0 || b >= x.nblocks) {
       ok = false;
@@ -1397,7 +1534,8 @@ __device__ bool prog_dc_refine(ScanCtx& x) {
 }
 
 // AC, first pass (G.1.2.2): run/size symbols, ZRL, EOB runs carried across blocks (reset at the interval's start)
-__device__ bool prog_ac_first(ScanCtx& x, const PTab& T) {
+template <typename X>
+__device__ bool prog_ac_first(X& x, const PTab& T) {
   const int c = __builtin_ctz(x.mask);
   Bits br{x.w, 0};
   bits_seek(br, x.pos);
@@ -1441,7 +1579,8 @@ __device__ bool prog_ac_first(ScanCtx& x, const PTab& T) {
 }
 
 // AC, refinement (G.1.2.3).  Lane i holds zig-zag coefficient i of the block.
-__device__ bool prog_ac_refine(ScanCtx& x, const PTab& T) {
+template <typename X>
+__device__ bool prog_ac_refine(X& x, const PTab& T) {
   const int c = __builtin_ctz(x.mask);
   const int lane = threadIdx.x;
   const int nat = kNatural[lane];
@@ -1530,42 +1669,41 @@ __global__ __launch_bounds__(256) void jpeg_prog_segment_kernel(const odic_jpeg_
   if (threadIdx.x == 0 && err) atomicOr(&ws.state[kStateWords * sc.image], kErrSegment);
 }
 
-__global__ __launch_bounds__(64) void jpeg_prog_decode_kernel(const odic_jpeg_prog_header* __restrict__ hdrs,
+template <typename Header>                                      // odic_jpeg_prog_header or odic_jpeg_prog_header_any
+__global__ __launch_bounds__(64) void jpeg_prog_decode_kernel(const Header* __restrict__ hdrs,
                                                               const odic_jpeg_scan* __restrict__ scans,
                                                               const odic_jpeg_table* __restrict__ tables, Ws ws,
                                                               int first, int n_images, int n_tables) {
   const odic_jpeg_scan& sc = scans[first + blockIdx.y];
   const int k = blockIdx.x;
   if (k >= sc.n_intervals || (unsigned)sc.image >= (unsigned)n_images) return;
-  const odic_jpeg_prog_header& h = hdrs[sc.image];
+  const Header& h = hdrs[sc.image];
   int* state = ws.state + kStateWords * sc.image;
-  __shared__ PTab T[3];
+  constexpr int kC = ProgGeo<Header>::kComps, kMask = (1 << kC) - 1;
+  __shared__ PTab T[kC];
   const bool dc = sc.ss == 0, first_pass = sc.ah == 0;
-  const int ntab = dc ? (first_pass ? __popc(sc.comp_mask & 7) : 0) : 1;
-  bool ok = sc.restart > 0 && sc.n_units > 0 && (sc.comp_mask & 7) != 0 && sc.ss >= 0 && sc.ss <= sc.se &&
-            sc.se <= 63 && sc.al >= 0 && sc.al <= 13 && (dc || ((sc.comp_mask & (sc.comp_mask - 1)) == 0 && sc.blocks_w > 0)) &&
-            (h.sampling != kGray || ((sc.comp_mask & 7) == 1 && sc.blocks_w > 0));   // gray: component 0 alone, every scan
+  const int ntab = dc ? (first_pass ? __popc(sc.comp_mask & kMask) : 0) : 1;
+  ScanCtx<Header> x;
+  bool ok = sc.restart > 0 && sc.n_units > 0 && (sc.comp_mask & kMask) != 0 && sc.ss >= 0 && sc.ss <= sc.se &&
+            sc.se <= 63 && sc.al >= 0 && sc.al <= 13 && (dc || ((sc.comp_mask & (sc.comp_mask - 1)) == 0 && sc.blocks_w > 0));
+  ok = x.g.set(h, sc.comp_mask & kMask, sc.blocks_w) && ok;
   for (int q = 0; q < ntab && ok; ++q) {
-    if ((unsigned)sc.table[q] >= (unsigned)n_tables) ok = false;
-    else load_ptab(tables[sc.table[q]], T[q]);
+    const int ti = q < 3 ? sc.table[q] : sc.pad;        // the fourth index: four components only (kC = 4)
+    if ((unsigned)ti >= (unsigned)n_tables) ok = false;
+    else load_ptab(tables[ti], T[q]);
   }
   __syncthreads();
   if (ok) {
     const int* ib = ws.int_bits + sc.int_off;
-    ScanCtx x;
     x.w = (const unsigned*)(ws.scan + sc.scan_off);
     x.coef = ws.coef + h.coef_off * 64;
-    x.nY = luma_blocks(h.sampling);
-    x.bpm = blocks_per_mcu(h.sampling);                  // gray: the MCU order is the component's block raster
-    x.nblocks = (long)h.mcus_x * h.mcus_y * x.bpm;
+    x.nblocks = (long)h.mcus_x * h.mcus_y * x.g.bpm;
     x.mcus_x = h.mcus_x;
-    x.hy = luma_h(h.sampling);
-    x.vy = luma_v(h.sampling);
     x.u0 = k * sc.restart;
     x.nu = min(sc.restart, sc.n_units - x.u0);
     x.pos = ib[k];
     x.end = ib[k + 1];
-    x.mask = sc.comp_mask & 7;
+    x.mask = sc.comp_mask & kMask;
     x.ss = sc.ss;
     x.se = sc.se;
     x.al = sc.al;
@@ -1654,15 +1792,18 @@ int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, 
     hipLaunchKernelGGL(jpeg_idct_kernel<Header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs,
                        ws);
     if constexpr (std::is_same<Header, odic_jpeg_header4>::value)
-      hipLaunchKernelGGL(jpeg_color4_kernel, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+      hipLaunchKernelGGL(jpeg_color4_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
     else
-      hipLaunchKernelGGL(jpeg_color3_kernel, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+      hipLaunchKernelGGL(jpeg_color3_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
   } else {
     launch_idct_color(b, hdrs, ws, scale_log2, s);
   }
   return odic_launch_status();
 }
 
+// Header: odic_jpeg_prog_header (three components at the common samplings, or gray) or odic_jpeg_prog_header_any
+// (per-component sampling, three or four components; full size only)
+template <typename Header>
 int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes, void* stream,
                        const int32_t* scale_log2) {
   if (!b || !b->headers || !b->scans || !b->tables || !b->data || !b->out || !b->status || !workspace)
@@ -1672,7 +1813,7 @@ int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws
   if (ws_bytes < L.total) return ODIC_EINVAL;
   const Ws ws = bind(workspace, L);
   hipStream_t s = (hipStream_t)stream;
-  const auto* hdrs = (const odic_jpeg_prog_header*)b->headers;
+  const auto* hdrs = (const Header*)b->headers;
   const auto* scans = (const odic_jpeg_scan*)b->scans;
   const auto* tables = (const odic_jpeg_table*)b->tables;
   const int n = b->n_images;
@@ -1681,9 +1822,19 @@ int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(jpeg_prog_segment_kernel, dim3(b->n_scans), dim3(256), 0, s, scans, b->data, ws, n);
   for (int l = 0; l < b->n_levels; ++l)
-    hipLaunchKernelGGL(jpeg_prog_decode_kernel, dim3(b->level_intervals[l], b->level_first[l + 1] - b->level_first[l]),
-                       dim3(64), 0, s, hdrs, scans, tables, ws, b->level_first[l], n, b->n_tables);
-  launch_idct_color(b, hdrs, ws, scale_log2, s);
+    hipLaunchKernelGGL(jpeg_prog_decode_kernel<Header>,
+                       dim3(b->level_intervals[l], b->level_first[l + 1] - b->level_first[l]), dim3(64), 0, s, hdrs, scans,
+                       tables, ws, b->level_first[l], n, b->n_tables);
+  if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) {
+    const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
+    const dim3 cgrid((unsigned)((lanes + 255) / 256), n);
+    hipLaunchKernelGGL(jpeg_idct_kernel<Header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs,
+                       ws);
+    hipLaunchKernelGGL(jpeg_color3_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+    hipLaunchKernelGGL(jpeg_color4_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+  } else {
+    launch_idct_color(b, hdrs, ws, scale_log2, s);
+  }
   return odic_launch_status();
 }
 
@@ -1733,11 +1884,20 @@ extern "C" size_t odic_jpeg_progressive_coef_offset(const odic_jpeg_prog_batch* 
 
 extern "C" int odic_jpeg_decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
                                             void* stream) {
-  return decode_progressive(b, workspace, ws_bytes, stream, nullptr);
+  return decode_progressive<odic_jpeg_prog_header>(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" size_t odic_jpeg_progressive_any_workspace_bytes(const odic_jpeg_prog_batch* b) {
+  return odic_jpeg_progressive_workspace_bytes(b);
+}
+
+extern "C" int odic_jpeg_decode_progressive_any(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
+                                                void* stream) {
+  return decode_progressive<odic_jpeg_prog_header_any>(b, workspace, ws_bytes, stream, nullptr);
 }
 
 extern "C" int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* b, const int32_t* scale_log2,
                                                    void* workspace, size_t ws_bytes, void* stream) {
   if (!scale_log2) return ODIC_ENULL;
-  return decode_progressive(b, workspace, ws_bytes, stream, scale_log2);
+  return decode_progressive<odic_jpeg_prog_header>(b, workspace, ws_bytes, stream, scale_log2);
 }

@@ -46,7 +46,8 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # `cmyk="device"` (and `non_rgb="convert"`) baseline CMYK / YCCK JPEGs are decoded and converted on the device too
 # (odic_jpeg4_decode) instead of leaving the batch for PIL.  With `layouts="all"` so are baseline three-component
 # JPEGs at the sampling layouts and colour spaces the common decode turns away (odic_jpeg3_any_decode: 4:4:0, 4:1:1,
-# 4:1:0, RGB-stored files, ...).
+# 4:1:0, RGB-stored files, ...).  With `progressive="device"` beside either keyword the progressive files of that kind are
+# decoded on the device as well (odic_jpeg_decode_progressive_any).
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -327,7 +328,9 @@ class DevicePreprocessor:
     def last_routes(self):
         """How each file of the last `decode_jpeg` / `from_jpeg_bytes` call was decoded, in input order: "device" (baseline,
         odic_jpeg_decode), "device-progressive" (odic_jpeg_decode_progressive), "device-cmyk" (four components,
-        odic_jpeg4_decode), "device-layout" (three components at a layout of layouts="all", odic_jpeg3_any_decode), "host"
+        odic_jpeg4_decode), "device-layout" (three components at a layout of layouts="all", odic_jpeg3_any_decode),
+        "device-progressive-cmyk" / "device-progressive-layout" (the progressive files of those two kinds,
+        odic_jpeg_decode_progressive_any), "host"
         (PIL: a kind the device does not
         take), "host-after-status" (the device reported status 1 and PIL decoded the file again) or "black"."""
         return tuple(self._jpeg_routes)
@@ -363,13 +366,22 @@ class DevicePreprocessor:
         measured): baseline four-component JPEGs — CMYK, or YCCK by Adobe transform 2 — that
         `jpeg.parse` admits are decoded by one odic_jpeg4_decode call in the same upload and status read-back, route
         "device-cmyk", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  Progressive four-component files
-        stay with PIL, and so do all of them under a draft request: there are no draft scales for this layout.
+        stay with PIL unless progressive="device" is given too (below), and so do all of them under a draft request:
+        there are no draft scales for this layout.
         layouts="all" (the default "common" leaves them to PIL until the device route is measured):
         baseline three-component JPEGs that only `jpeg.parse(f, layouts="all")` admits — luma at 1x2 (4:4:0), 4x1
         (4:1:1), 4x2 (4:1:0), chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest, files
         stored as RGB — are decoded by one odic_jpeg3_any_decode call in the same upload and status read-back, route
         "device-layout", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  A file the common rules admit keeps
-        its route.  Progressive files with these layouts stay with PIL, and so do all of them under a draft request."""
+        its route.  Progressive files with these layouts stay with PIL unless progressive="device" is given too, and
+        so do all of them under a draft request.
+        progressive="device" together with cmyk="device", or together with layouts="all" (both opt-ins; any other
+        combination of keywords does exactly what it did): the progressive files of that kind — SOF2 frames of four
+        components, or of three at a layout only layouts="all" admits — that `jpeg.parse_progressive(f, non_rgb,
+        cmyk=, layouts=)` admits are decoded by one odic_jpeg_decode_progressive_any call in the same upload and
+        status read-back, routes "device-progressive-cmyk" / "device-progressive-layout" (DESIGN §4.27), each equal to
+        np.asarray(PIL.Image.open(f).convert("RGB")).  Under a draft request they stay with PIL, as their baseline
+        siblings do."""
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
@@ -396,6 +408,10 @@ class DevicePreprocessor:
                     ph = J.parse_progressive(blobs[i], *opt)
                     if ph.kind == J.DEVICE:
                         hdrs[i] = ph
+                elif h.kind == J.HOST and (h.reason == J.PROG_CMYK_REASON or h.reason.startswith(J.PROG_LAYOUT_REASON)):
+                    ph = J.parse_progressive(blobs[i], *opt, **copt)     # `parse` gives these reasons under copt only
+                    if ph.kind == J.DEVICE:
+                        hdrs[i] = ph
         out = [None] * len(blobs)
         scales = [J.draft_scale((h.width, h.height), draft) if draft is not None and h.kind != J.HOST else 1
                   for h in hdrs]
@@ -403,11 +419,12 @@ class DevicePreprocessor:
         # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
         dev = [i for i, h in enumerate(hdrs)
                if h.kind == J.DEVICE and sizes[i][0] * sizes[i][1] * 3 <= self.max_bytes]
-        four = [i for i in dev if hdrs[i].ncomp == 4]
-        lay = [i for i in dev if getattr(hdrs[i], "layout", False)]
-        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader) and hdrs[i].ncomp != 4
-                and not getattr(hdrs[i], "layout", False)]
-        prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader)]
+        own = lambda h: h.ncomp == 4 or getattr(h, "layout", False)      # every component with its own sampling
+        pany = [i for i in dev if isinstance(hdrs[i], J.ProgHeader) and own(hdrs[i])]
+        four = [i for i in dev if hdrs[i].ncomp == 4 and i not in pany]
+        lay = [i for i in dev if getattr(hdrs[i], "layout", False) and i not in pany]
+        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader) and not own(hdrs[i])]
+        prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader) and i not in pany]
         routes = ["host" if h.kind == J.DEVICE else h.kind for h in hdrs]        # a device kind left so is oversized
         for i in dev:
             routes[i] = "device-progressive" if isinstance(hdrs[i], J.ProgHeader) else "device"
@@ -415,15 +432,19 @@ class DevicePreprocessor:
             routes[i] = "device-cmyk"
         for i in lay:
             routes[i] = "device-layout"
+        for i in pany:
+            routes[i] = "device-progressive-cmyk" if hdrs[i].ncomp == 4 else "device-progressive-layout"
         if dev:
-            order = base + prog + four + lay
+            order = base + prog + four + lay + pany
             group4 = ([hdrs[i] for i in four], [blobs[i] for i in four]) if four or lay else ()   # without: today's call
             if lay:
                 group4 += ([hdrs[i] for i in lay], [blobs[i] for i in lay])
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
                                                            [hdrs[i] for i in prog], [blobs[i] for i in prog],
                                                            subseq_bits, max_sync_passes,
-                                                           [scales[i] for i in base + prog], *group4)
+                                                           [scales[i] for i in base + prog], *group4,
+                                                           **({"ahdrs": [hdrs[i] for i in pany],
+                                                               "ablobs": [blobs[i] for i in pany]} if pany else {}))
             turned = []                                                  # (image, its offset in rgb): to be permuted
             for k, i in enumerate(order):
                 if status[k] != 0:
@@ -472,12 +493,13 @@ class DevicePreprocessor:
             out[i] = dst[int(r["dst_off"]):int(r["dst_off"]) + w * h * 3].view(h, w, 3)
 
     def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales, chdrs=(), cblobs=(),
-                          lhdrs=(), lblobs=()):
+                          lhdrs=(), lblobs=(), ahdrs=(), ablobs=()):
         """One odic_jpeg_decode call for the baseline files, one odic_jpeg_decode_progressive call for the progressive
         ones, one odic_jpeg4_decode call for the four-component ones (chdrs, cblobs) and one odic_jpeg3_any_decode call
-        for the `layout` ones (lhdrs, lblobs), sharing one upload, one output
+        for the `layout` ones (lhdrs, lblobs) and one odic_jpeg_decode_progressive_any call for the progressive files
+        with per-component sampling (ahdrs, ablobs), sharing one upload, one output
         buffer, one workspace and one status read-back → (status numpy int32 — baseline files first, then progressive,
-        four-component, `layout` —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
+        four-component, `layout`, progressive with per-component sampling —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
         baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales uploaded
         beside the headers.  This is the GPU half: `jpeg.plan_device_batch` lays the upload and the output out."""
         from . import jpeg as J
@@ -485,8 +507,10 @@ class DevicePreprocessor:
         group4 = (chdrs, cblobs) if ncm or nly else ()
         if nly:
             group4 += (lhdrs, lblobs)
-        plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, *group4)
-        n_all = nb + npg + ncm + nly
+        npa = len(ahdrs)
+        group_any = {"ahdrs": ahdrs, "ablobs": ablobs} if npa else {}    # without: today's call
+        plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, *group4, **group_any)
+        n_all = nb + npg + ncm + nly + npa
         self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
         self._jpeg_pinned = self._grow(self._jpeg_pinned, plan.total, pin_memory=True)
         self._jpeg_status = self._grow(self._jpeg_status, 4 * n_all, pin_memory=True)
@@ -494,9 +518,18 @@ class DevicePreprocessor:
         out_total = plan.cout_off + plan.cout_bytes if ncm else plan.out_bytes + plan.pout_bytes
         if nly:
             out_total = plan.lout_off + plan.lout_bytes
+        if npa:
+            out_total = plan.aout_off + plan.aout_bytes
         rgb = torch.empty(max(out_total, 1), dtype=torch.uint8, device=self.device)
         status = torch.empty(n_all, dtype=torch.int32, device=self.device)
-        need_b = need_p = need_c = need_l = 0
+        need_b = need_p = need_c = need_l = need_a = 0
+        if npa:
+            ab = self._hip.JpegProgBatch()
+            ab.n_images = npa
+            self._set_fields(ab, plan.atot)
+            need_a = self.lib.odic_jpeg_progressive_any_workspace_bytes(ctypes.byref(ab))
+            if need_a == 0:
+                raise RuntimeError("JPEG batch too large for one progressive decode call")
         if nly:
             lb = self._hip.JpegBatch()
             lb.n_images, lb.subseq_bits, lb.max_sync_passes = nly, subseq_bits, max_sync_passes
@@ -522,7 +555,7 @@ class DevicePreprocessor:
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             self._jpeg_dev = self._grow(self._jpeg_dev, plan.total, device=self.device)
-            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p, need_c, need_l), device=self.device)
+            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p, need_c, need_l, need_a), device=self.device)
             self._jpeg_dev[:plan.total].copy_(self._jpeg_pinned[:plan.total], non_blocking=True)
             self._jpeg_ev.record(self.stream)
             base = self._jpeg_dev.data_ptr()
@@ -547,6 +580,13 @@ class DevicePreprocessor:
                 lb.out, lb.status = rgb.data_ptr() + plan.lout_off, status.data_ptr() + 4 * (nb + npg + ncm)
                 self._hip.check(self.lib.odic_jpeg3_any_decode(ctypes.byref(lb), self._jpeg_ws.data_ptr(), need_l,
                                                                self.stream.cuda_stream), "odic_jpeg3_any_decode")
+            if npa:
+                ab.headers, ab.scans, ab.tables = (base + o for o in plan.any_off)
+                ab.data, ab.out = base + plan.data_off, rgb.data_ptr() + plan.aout_off
+                ab.status = status.data_ptr() + 4 * (nb + npg + ncm + nly)
+                self._hip.check(self.lib.odic_jpeg_decode_progressive_any(ctypes.byref(ab), self._jpeg_ws.data_ptr(),
+                                                                          need_a, self.stream.cuda_stream),
+                                "odic_jpeg_decode_progressive_any")
             if npg:                                                      # last: its coefficients stay in the workspace
                 pb.headers, pb.scans, pb.tables = (base + o for o in plan.prog_off)
                 pb.data, pb.out = base + plan.data_off, rgb.data_ptr() + plan.out_bytes

@@ -24,8 +24,8 @@ That is the default, non_rgb="black".  Under non_rgb="convert" every file is to 
 sampling factors and component id the SOF declares, which libjpeg ignores for a single component — and a four-component
 frame is `host`, where PIL converts it — unless the caller also passes cmyk="device": then a baseline four-component frame
 (CMYK, or YCCK by Adobe transform 2) that `_frame4` admits is a `device` kind with ncomp 4, the sampling of every
-component in comp_hv and the `ycck` flag; odic_jpeg4_decode reads its records (`HEADER4_DTYPE`).  Progressive
-four-component files, and all of them under a draft request, stay `host`.
+component in comp_hv and the `ycck` flag; odic_jpeg4_decode reads its records (`HEADER4_DTYPE`).  To `parse`
+progressive four-component files stay `host` (`PROG_CMYK_REASON`), and so do all of them under a draft request.
 
 Under layouts="all" (`parse` only; the default "common" is everything above) a baseline three-component frame that the
 rules above turn away for its sampling or its colour space is a `device` kind too where `_frame3_any` admits it: every
@@ -35,12 +35,15 @@ YCbCr or as RGB (Adobe transform 0, or ids R, G, B with neither marker).  The he
 `rgb` flag and MCU counts from the largest factors; odic_jpeg3_any_decode reads its records (`HEADER3_DTYPE`).  What
 still goes to the host after that:
 
-    host    fractional sampling ratios; more than 10 blocks per MCU; progressive files, and draft requests, with these
-            layouts; non-interleaved multi-scan baseline files; arithmetic coding; 12-bit; three components with an
-            Adobe transform other than 0 and 1, or with duplicate ids
+    host    fractional sampling ratios; more than 10 blocks per MCU; progressive files (`PROG_LAYOUT_REASON`), and draft
+            requests, with these layouts; non-interleaved multi-scan baseline files; arithmetic coding; 12-bit; three
+            components with an Adobe transform other than 0 and 1, or with duplicate ids
 
 `parse` keeps that sorting.  For the files it turns away with reason "SOF2", `parse_progressive` (below) reads the whole
-scan script, locating every scan's end in the file, and packs the records odic_jpeg_decode_progressive reads.
+scan script, locating every scan's end in the file, and packs the records odic_jpeg_decode_progressive reads.  Given
+the same cmyk="device" / layouts="all" it also admits the SOF2 frames `parse` turned away with the two reasons named
+above — four components, or three at a layout of `_frame3_any` — under the same frame rules and the same scan-script
+rules; odic_jpeg_decode_progressive_any reads their records (`PROG_HEADER_ANY_DTYPE`).
 """
 from __future__ import annotations
 
@@ -309,14 +312,19 @@ class _Walker:
                 raise _Bad(f"marker {m:02X}")
 
 
-def _frame4(w, header):
+PROG_CMYK_REASON = "4 components, progressive (SOF2)"
+PROG_LAYOUT_REASON = "3 components, progressive (SOF2), outside the common layouts"
+
+
+def _frame4(w, header, sof_kinds=(0xC0, 0xC1)):
     """The four-component half of `_frame` for cmyk="device", by libjpeg's rules (jdapimin.c default_decompress_parms,
     jdinput.c): the colour space comes from the Adobe marker alone — transform 2 is YCCK, transform 0 and no Adobe
     marker (a JFIF marker does not matter) are CMYK; any other transform makes libjpeg warn and guess, which is the
-    host's.  Component 0 carries the MCU's size; every other component is 1x1 or shares it."""
+    host's.  Component 0 carries the MCU's size; every other component is 1x1 or shares it.  sof_kinds: the frame
+    markers of the parser that asks; the other parser's get that parser's reason."""
     m, _, height, width, _, comps = w.sof
-    if m == 0xC2:
-        raise _Bad("4 components, progressive (SOF2)")
+    if m not in sof_kinds:
+        raise _Bad(PROG_CMYK_REASON if m == 0xC2 else f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
         raise _Bad("DNL / empty frame")
     t = w.adobe_transform if w.adobe else 0
@@ -338,7 +346,7 @@ def _frame4(w, header):
                   qtables=[w.qt[c[3]] for c in comps], ycck=t == 2)
 
 
-def _frame3_any(w, header):
+def _frame3_any(w, header, sof_kinds=(0xC0, 0xC1)):
     """The three-component frames of layouts="all" that the common rules turn away, by libjpeg's rules.
     jdapimin.c default_decompress_parms: a JFIF marker means YCbCr; else Adobe transform 0 is RGB and 1 is YCbCr (any
     other makes libjpeg warn and guess: the host's); with neither marker ids 1, 2, 3 are YCbCr, R, G, B are RGB and
@@ -347,8 +355,8 @@ def _frame3_any(w, header):
     largest factor to each component's has to be integral ("fractional sampling not implemented")."""
     m, _, height, width, _, comps = w.sof
     hv = [(c[1], c[2]) for c in comps]
-    if m == 0xC2:
-        raise _Bad(f"3 components, progressive (SOF2), outside the common layouts: {hv}")
+    if m not in sof_kinds:
+        raise _Bad(f"{PROG_LAYOUT_REASON}: {hv}" if m == 0xC2 else f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
         raise _Bad("DNL / empty frame")
     ids = [c[0] for c in comps]
@@ -402,10 +410,10 @@ def _frame(w, header, sof_kinds, distinct_ids, non_rgb="black", cmyk="host", lay
         return header(BLACK, width=width, height=height, ncomp=nc)
     if nc == 4 and m in (0xC0, 0xC1, 0xC2):           # non_rgb="convert": Adobe inversion, YCCK and PIL's CMYK → RGB are
         if cmyk == "device":                          # the host's, whichever parser asks, unless `parse` was told
-            return _frame4(w, header)                 # cmyk="device"
+            return _frame4(w, header, sof_kinds)      # cmyk="device"
         raise _Bad("4 components (CMYK / YCCK)")
     if layouts == "all" and nc == 3 and m in (0xC0, 0xC1, 0xC2) and not _common3(w):
-        return _frame3_any(w, header)
+        return _frame3_any(w, header, sof_kinds)
     if m not in sof_kinds:
         raise _Bad(f"SOF{m - 0xC0}")
     if width == 0 or height == 0:
@@ -684,7 +692,10 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     blocks = nmcu * (sum(a * b for a, b in h.comp_hv) if own else BLOCKS_PER_MCU[h.sampling])
     r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
     r["width"], r["height"] = h.width, h.height
-    if own:
+    if own and "ncomp" in r.dtype.names:              # a PROG_HEADER_ANY_DTYPE record: both kinds, told apart by ncomp
+        r["ncomp"], r["color"] = h.ncomp, int(h.ycck if four else h.rgb)
+        r["h"][:h.ncomp], r["v"][:h.ncomp] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv]
+    elif own:
         r["h"], r["v"] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv]
         r["ycck" if four else "rgb"] = int(h.ycck if four else h.rgb)
     else:
@@ -765,6 +776,13 @@ PROG_HEADER_DTYPE = np.dtype([
     ("width", "<i4"), ("height", "<i4"), ("sampling", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"),
     ("n_intervals", "<i4"), ("qt", "<u2", (3, 64)),
 ], align=True)
+# odic_jpeg_prog_header_any: odic_jpeg_prog_header's prefix with `color` where `sampling` is, then the frame
+PROG_HEADER_ANY_DTYPE = np.dtype([
+    ("out_off", "<i8"), ("coef_off", "<i8"), ("plane_off", "<i8"),
+    ("width", "<i4"), ("height", "<i4"), ("color", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"),
+    ("n_intervals", "<i4"), ("ncomp", "<i4"), ("pad", "<i4"), ("h", "<i4", (4,)), ("v", "<i4", (4,)),
+    ("qt", "<u2", (4, 64)),
+], align=True)
 SCAN_DTYPE = np.dtype([
     ("data_off", "<i8"), ("data_end", "<i8"), ("scan_off", "<i8"),
     ("image", "<i4"), ("int_off", "<i4"), ("n_intervals", "<i4"), ("restart", "<i4"), ("n_units", "<i4"),
@@ -815,25 +833,34 @@ def marker_positions(blob) -> np.ndarray:
     return ff[(nx != 0) & (nx != 0xFF) & ((nx & 0xF8) != 0xD0)]
 
 
-def parse_progressive(blob, non_rgb: str = "black") -> ProgHeader:
+def parse_progressive(blob, non_rgb: str = "black", cmyk: str = "host", layouts: str = "common") -> ProgHeader:
     """The whole scan script of a progressive file → ProgHeader of kind DEVICE, or HOST with a reason (BLACK for
     one and four components, as `parse`; under non_rgb="convert" a one-component frame is a device kind whose scans
-    are all non-interleaved, and a four-component one is HOST); never raises on a file's content."""
+    are all non-interleaved, and a four-component one is HOST); never raises on a file's content.
+    cmyk="device" (with non_rgb="convert" only): a four-component SOF2 frame under `_frame4`'s rules is a device kind
+    with ncomp 4, comp_hv and `ycck`.  layouts="all": a three-component SOF2 frame that the common rules turn away for
+    its sampling or colour space and `_frame3_any` admits is one with `layout` set, comp_hv and `rgb`.  Both are read
+    by odic_jpeg_decode_progressive_any (`pack_progressive(..., dtype=PROG_HEADER_ANY_DTYPE)`); the scan-script rules
+    are the same, for up to four components.  A frame with more than MAX_MCU_BLOCKS blocks per MCU stays HOST even
+    where none of its interleaved scans exceeds libjpeg's limit.  With the defaults the result is what it is without
+    the keywords."""
     check_non_rgb(non_rgb)
+    check_cmyk(cmyk, non_rgb)
+    check_layouts(layouts)
     try:
-        return _parse_progressive(bytes(blob), non_rgb)
+        return _parse_progressive(bytes(blob), non_rgb, cmyk, layouts)
     except _Bad as e:
         return ProgHeader(HOST, reason=str(e))
     except (IndexError, ValueError) as e:
         return ProgHeader(HOST, reason=f"malformed: {e}")
 
 
-def _parse_progressive(b, non_rgb="black") -> ProgHeader:
+def _parse_progressive(b, non_rgb="black", cmyk="host", layouts="common") -> ProgHeader:
     w = _Walker(b)
     hd = coef_bits = marks = None                  # set at the first SOS; coef_bits: [3][64] current Al of every
     for s in w.scans(script=True):                 # coefficient, -1: not yet sent (lists)
         if hd is None:
-            hd = _frame(w, ProgHeader, (0xC2,), distinct_ids=True, non_rgb=non_rgb)
+            hd = _frame(w, ProgHeader, (0xC2,), distinct_ids=True, non_rgb=non_rgb, cmyk=cmyk, layouts=layouts)
             hd.app1 = w.app1
             if hd.kind != DEVICE:
                 return hd
@@ -860,7 +887,7 @@ def _progressive_scan(hd, s, dht, dri, coef_bits) -> ProgScan:
     """One SOS header under libjpeg's rules (jdmarker.c get_sos, jdphuff.c start_pass_phuff_decoder): whatever
     makes libjpeg warn goes to the host."""
     ns = s[0] if len(s) >= 1 else 0
-    if ns < 1 or ns > 3 or len(s) != 1 + 2 * ns + 3:
+    if ns < 1 or ns > (4 if hd.ncomp == 4 else 3) or len(s) != 1 + 2 * ns + 3:
         raise _Bad("bad SOS")
     sel = [(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(ns)]
     try:
@@ -899,7 +926,7 @@ def _progressive_scan(hd, s, dht, dri, coef_bits) -> ProgScan:
         sc.n_units = hd.mcus_x * hd.mcus_y
     else:
         h, v = hd.comp_hv[comps[0]]
-        hmax, vmax = hd.comp_hv[0]
+        hmax, vmax = max(a for a, _ in hd.comp_hv), max(b for _, b in hd.comp_hv)
         sc.blocks_w = -(-(-(-hd.width * h // hmax)) // 8)
         sc.n_units = sc.blocks_w * -(-(-(-hd.height * v // vmax)) // 8)
     return sc
@@ -919,13 +946,17 @@ def _dependency_levels(scans):
         sc.level = lvl + 1
 
 
-def pack_progressive(hdrs, blob_offs, scales=None):
+def pack_progressive(hdrs, blob_offs, scales=None, dtype=PROG_HEADER_DTYPE):
     """Header, scan and table records + batch totals for progressive headers whose files start at blob_offs inside
     the batch's data buffer.  Scans are sorted by level (stable), which is how odic_jpeg_decode_progressive walks
-    them.  scales: as `pack_headers`.  → (headers PROG_HEADER_DTYPE [n], scans SCAN_DTYPE [m], tables TABLE_DTYPE [t], totals dict with
+    them.  scales: as `pack_headers`.  dtype=PROG_HEADER_ANY_DTYPE: the headers of one odic_jpeg_decode_progressive_any
+    call (`parse_progressive` with cmyk="device" / layouts="all"; no scales): output offsets rounded up to multiples of
+    4 as `pack_headers` does for its word-storing kinds, and the fourth DC table index of a scan in its `pad` word.
+    → (headers `dtype` [n], scans SCAN_DTYPE [m], tables TABLE_DTYPE [t], totals dict with
     level_first / level_intervals lists, output byte offsets, output bytes)."""
     n = len(hdrs)
-    rec = np.zeros(n, PROG_HEADER_DTYPE)
+    rec = np.zeros(n, dtype)
+    own = dtype is PROG_HEADER_ANY_DTYPE
     tot = dict(total_scan_bytes=0, total_intervals=0, total_blocks=0, total_plane_bytes=0, max_width=1, max_height=1,
                max_blocks=1)
     tables, table_ix, flat = [], {}, []
@@ -939,6 +970,8 @@ def pack_progressive(hdrs, blob_offs, scales=None):
         return table_ix[key]
 
     for k, h in enumerate(hdrs):
+        if own:
+            out_bytes = (out_bytes + 3) // 4 * 4
         _, out_bytes = _place_image(rec[k], h, tot, out_offs, out_bytes, scales[k] if scales else 1)
         rec[k]["n_intervals"] = sum(s.n_intervals for s in h.scans)
         flat += [(s.level, k, s) for s in h.scans]
@@ -956,8 +989,12 @@ def pack_progressive(hdrs, blob_offs, scales=None):
         r["comp_mask"] = sum(1 << c for c in s.comps)
         r["ss"], r["se"], r["ah"], r["al"], r["level"] = s.ss, s.se, s.ah, s.al, lvl
         r["table"] = -1
+        if own:
+            r["pad"] = -1
         for q, t in enumerate(s.dc_tables):
-            if t is not None:
+            if t is not None and q == 3:
+                r["pad"] = table(t)
+            elif t is not None:
                 r["table"][q] = table(t)
         if s.ac_table is not None:
             r["table"][0] = table(s.ac_table)
@@ -1006,6 +1043,10 @@ class BatchPlan:
     layout_off: int = None         # last group of all
     lout_off: int = 0
     lout_bytes: int = 0
+    atot: dict = None              # the progressive files with per-component sampling (`parse_progressive` with
+    any_off: tuple = None          # cmyk="device" / layouts="all", PROG_HEADER_ANY_DTYPE): odic_jpeg_prog_batch totals,
+    aout_off: int = 0              # staging offsets of their headers, scans, tables, and their part of the output;
+    aout_bytes: int = 0            # behind every other group
 
     def fill(self, host):
         """Write the sections and the files into the uint8 array `host` of at least `total` bytes."""
@@ -1014,7 +1055,7 @@ class BatchPlan:
 
 
 def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(), cblobs=(), lhdrs=(),
-                      lblobs=()) -> BatchPlan:
+                      lblobs=(), ahdrs=(), ablobs=()) -> BatchPlan:
     """The layout of one device decode of the baseline files (hdrs, blobs: DEVICE-kind `parse` results and their bytes)
     and the progressive ones (phdrs, pblobs: `parse_progressive`).  scales: the draft scale of every image, baseline
     first.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
@@ -1022,8 +1063,12 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     others: its records behind the scales, its files behind the progressive ones, its output behind theirs from the
     next multiple of 256.  They have no scales.  Without them the plan is what it is without these arguments.
     lhdrs, lblobs: the `layout` files (`parse(..., layouts="all")`), the last group, placed by the same rule behind the
-    four-component one."""
-    nb, npg, ncm, nly = len(hdrs), len(phdrs), len(chdrs), len(lhdrs)
+    four-component one.
+    ahdrs, ablobs: the progressive files with per-component sampling (`parse_progressive(..., cmyk="device")` /
+    `(..., layouts="all")`), placed by the same rule behind the `layout` group: header, scan and table records behind
+    the others', files behind the others', output from the next multiple of 256.  Without them the plan is what it is
+    without these arguments."""
+    nb, npg, ncm, nly, npa = len(hdrs), len(phdrs), len(chdrs), len(lhdrs), len(ahdrs)
     scales = list(scales)[:nb + npg]
     sections, pos = [], pad256(nb * HEADER_DTYPE.itemsize)
     ptot = prog_off = scale_off = None
@@ -1044,8 +1089,14 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     if nly:
         layout_off = pos
         pos += pad256(nly * HEADER3_DTYPE.itemsize)
+    any_off = None
+    if npa:                                              # sizes only, as for the progressive group above
+        arec, asrec, atrec, atot, aout_offs, aout_bytes = pack_progressive(ahdrs, [0] * npa,
+                                                                           dtype=PROG_HEADER_ANY_DTYPE)
+        any_off = (pos, pos + pad256(arec.nbytes), pos + pad256(arec.nbytes) + pad256(asrec.nbytes))
+        pos = any_off[2] + pad256(atrec.nbytes)
     data_off = pos
-    every = list(blobs) + list(pblobs) + list(cblobs) + list(lblobs)
+    every = list(blobs) + list(pblobs) + list(cblobs) + list(lblobs) + list(ablobs)
     starts = np.cumsum([0] + [len(b) for b in every]).tolist()                          # inside the data area
     tot, out_offs, out_bytes = None, [], 0
     if nb:
@@ -1070,13 +1121,24 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     if nly:
         first = nb + npg + ncm
         lrec, ltot, lout_offs, lout_bytes = pack_headers(
-            lhdrs, [o + h.data_offset for o, h in zip(starts[first:], lhdrs)], starts[first + 1:], subseq_bits,
-            dtype=HEADER3_DTYPE)
+            lhdrs, [o + h.data_offset for o, h in zip(starts[first:], lhdrs)], starts[first + 1:first + nly + 1],
+            subseq_bits, dtype=HEADER3_DTYPE)
         sections.append((layout_off, lrec))
         before = cout_off + cout_bytes if ncm else out_bytes + (pout_bytes if npg else 0)
         lout_off = pad256(before)
         out_offs = out_offs + [lout_off + o for o in lout_offs]
         extra.update(ltot=ltot, layout_off=layout_off, lout_off=lout_off, lout_bytes=lout_bytes)
+    if npa:
+        first = nb + npg + ncm + nly
+        shift = np.asarray(starts[first:first + npa], np.int64)[asrec["image"]]
+        asrec["data_off"] += shift
+        asrec["data_end"] += shift
+        sections += list(zip(any_off, (arec, asrec, atrec)))
+        before = (lout_off + lout_bytes if nly else cout_off + cout_bytes if ncm
+                  else out_bytes + (pout_bytes if npg else 0))
+        aout_off = pad256(before)
+        out_offs = out_offs + [aout_off + o for o in aout_offs]
+        extra.update(atot=atot, any_off=any_off, aout_off=aout_off, aout_bytes=aout_bytes)
     files = [(data_off + o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, every)]
     coef_off = [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])] if npg else []
     return BatchPlan(sections, data_off, files, data_off + starts[-1], tot, ptot, prog_off, scale_off, out_offs,

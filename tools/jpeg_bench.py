@@ -33,6 +33,13 @@ against the host's `Image.open(f).convert("RGB")` on one thread.  One line per l
 
     python tools/jpeg_bench.py --layouts --batches 16 64 --iters 20 --out profiles/jpeg_layouts_bench.json
 
+--progressive-layouts: the two progressive routes with per-component sampling: 640x480 pictures written
+as progressive 4:4:0 by the tests' writer (four distinct files, repeated) and the crops saved by Pillow as progressive
+CMYK; the device path with progressive="device", cmyk="device", layouts="all" (odic_jpeg_decode_progressive_any)
+against the host's `Image.open(f).convert("RGB")` on one thread.  One line per kind and batch.
+
+    python tools/jpeg_bench.py --progressive-layouts --batches 16 64 --iters 20
+
 --draft: what decoding at the scale `Image.draft("RGB", (S, S))` picks saves.  Seeded synthetic JPEGs,
 3456x4608 (drafts at 1/8) and 640x480 (drafts at 1/1: the control), 4:2:0 and 4:4:4, baseline and progressive; per
 case `decode_jpeg` alone and `from_jpeg_bytes` (decode + resize), draft off and on alternating in the same process,
@@ -85,7 +92,7 @@ def make_inputs(n: int, seed: int = 0, progressive: bool = False, gray: bool = F
         if gray:
             im.convert("L").save(buf, format="JPEG", quality=90, progressive=progressive)
         elif cmyk:
-            im.convert("CMYK").save(buf, format="JPEG", quality=90, subsampling=2)
+            im.convert("CMYK").save(buf, format="JPEG", quality=90, subsampling=2, progressive=progressive)
         else:
             im.save(buf, format="JPEG", quality=90, subsampling=2, progressive=progressive)
         out.append(buf.getvalue())
@@ -100,6 +107,21 @@ def layout_inputs(layout: str, n: int, distinct: int = 8):
     from jpeg_layout_writer import write_jpeg3
     hv, style = LAYOUTS[layout]
     files = [write_jpeg3(picture(480, 640, seed=k, noise=True), hv, style) for k in range(min(n, distinct))]
+    return [files[k % len(files)] for k in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def progressive_layout_inputs(layout: str, n: int, distinct: int = 4):
+    """n progressive files of 640x480 at `layout` (a key of tests/jpeg_prog_layout_cases.LAYOUTS) under libjpeg's
+    standard script: `distinct` pictures, repeated."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from jpeg_prog_layout_cases import LAYOUTS, source
+    from jpeg_prog_layout_writer import standard_script, write_progressive_any, zigzag_coefficients
+    hv, style = LAYOUTS[layout]
+    files = []
+    for k in range(min(n, distinct)):
+        zz, _, _ = zigzag_coefficients(source(len(hv), 480, 640, seed=k, noise=True), hv, 6)
+        files.append(write_progressive_any(640, 480, hv, zz, 6, standard_script(len(hv)), style))
     return [files[k % len(files)] for k in range(n)]
 
 
@@ -300,6 +322,8 @@ def main():
     ap.add_argument("--gray", action="store_true", help="the crops as one-component files, non_rgb='convert'")
     ap.add_argument("--cmyk", action="store_true", help="the crops as four-component files, non_rgb='convert', cmyk='device'")
     ap.add_argument("--layouts", action="store_true", help="4:4:0 and 4:1:1 files from the tests' writer, layouts='all'")
+    ap.add_argument("--progressive-layouts", action="store_true",
+                    help="progressive 4:4:0 from the tests' writer and Pillow's progressive CMYK, every opt-in")
     ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
     ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
     ap.add_argument("--orient", action="store_true", help="odic_orient_rgb8 against a copy; orientation='exif' end to end")
@@ -319,12 +343,23 @@ def main():
         ap.error("--cmyk goes alone: the four-component route is baseline only")
     if args.layouts and (args.gray or args.progressive or args.cmyk):
         ap.error("--layouts goes alone: the route is baseline three-component files only")
-    non_rgb = "convert" if args.gray or args.cmyk else "black"
+    both = args.progressive_layouts
+    if both and (args.gray or args.progressive or args.cmyk or args.layouts):
+        ap.error("--progressive-layouts goes alone: it sets every opt-in itself")
+    non_rgb = "convert" if args.gray or args.cmyk or both else "black"
     route_kw = {"cmyk": "device"} if args.cmyk else {"layouts": "all"} if args.layouts else {}
     want_route = ("device-cmyk" if args.cmyk else "device-layout" if args.layouts else
                   "device-progressive" if args.progressive else "device")
     names = {}                                           # id of a batch's list → its layout
-    if args.layouts:
+    if both:
+        route_kw = {"cmyk": "device", "layouts": "all"}
+        inputs = []
+        for kind, blobs_all in (("440", progressive_layout_inputs("440", max(args.batches))),
+                                ("cmyk", make_inputs(max(args.batches), progressive=True, cmyk=True))):
+            for B in args.batches:
+                inputs.append((B, blobs_all[:B], (640, 480)))
+                names[id(inputs[-1][1])] = kind
+    elif args.layouts:
         inputs = []
         for layout in ("440", "411"):
             blobs_all = layout_inputs(layout, max(args.batches))
@@ -349,12 +384,12 @@ def main():
         parse_us = 1e6 * (time.perf_counter() - t0) / (5 * len(blobs_all))
 
     def host(blobs):
-        if args.gray or args.cmyk or args.layouts:
+        if args.gray or args.cmyk or args.layouts or both:
             return pre([np.asarray(Image.open(io.BytesIO(b)).convert("RGB")) for b in blobs])
         return pre([np.asarray(Image.open(io.BytesIO(b))) for b in blobs])
 
     def device(blobs):
-        return pre.from_jpeg_bytes(blobs, progressive="device" if args.progressive else "host", non_rgb=non_rgb,
+        return pre.from_jpeg_bytes(blobs, progressive="device" if args.progressive or both else "host", non_rgb=non_rgb,
                                    **route_kw)
 
     lines = []
@@ -365,6 +400,8 @@ def main():
             torch.cuda.synchronize()
             continue
         assert torch.equal(host(blobs), device(blobs)), "host and device paths differ"
+        if both:
+            want_route = {"440": "device-progressive-layout", "cmyk": "device-progressive-cmyk"}[names[id(blobs)]]
         assert set(pre.last_routes) == {want_route}, pre.last_routes
         for _ in range(args.warmup):
             host(blobs)
@@ -396,8 +433,9 @@ def main():
                     sweep[f"bits{bits}_passes{passes}"] = B / float(np.median(ts))
         line = {"batch": B, "width": width, "height": height, "quality": 90,
                 "subsampling": "gray" if args.gray else "cmyk 2x2,1x1,1x1,1x1" if args.cmyk else
-                {"440": "4:4:0", "411": "4:1:1"}[names[id(blobs)]] if args.layouts else "4:2:0",
-                "progressive": args.progressive,
+                {"440": "4:4:0", "411": "4:1:1", "cmyk": "cmyk 2x2,1x1,1x1,1x1"}[names[id(blobs)]]
+                if args.layouts or both else "4:2:0",
+                "progressive": args.progressive or both,
                 "mean_jpeg_bytes": int(np.mean([len(b) for b in blobs])),
                 "host_images_per_s": B / med["host"], "device_images_per_s": B / med["device"],
                 "speedup": med["host"] / med["device"],
