@@ -71,7 +71,8 @@ extern "C" {
  *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
  *       odic_lcs_pairs, odic_orient_rgb8, odic_jpeg4_workspace_bytes, odic_jpeg4_decode, odic_cmyk_to_rgb8,
  *       odic_jpeg3_any_workspace_bytes, odic_jpeg3_any_decode, odic_jpeg_progressive_any_workspace_bytes,
- *       odic_jpeg_decode_progressive_any. */
+ *       odic_jpeg_decode_progressive_any, odic_jpeg4_decode_scaled, odic_jpeg3_any_decode_scaled,
+ *       odic_jpeg_decode_progressive_any_scaled (the per-component records at 1/2, 1/4, 1/8 scale). */
 #define ODIC_ABI_VERSION 26
 int odic_abi_version(void);
 
@@ -400,6 +401,18 @@ typedef struct odic_jpeg_header4 {
 size_t odic_jpeg4_workspace_bytes(const odic_jpeg_batch* batch);
 int odic_jpeg4_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
+/* odic_jpeg_decode_scaled for odic_jpeg_header4 records: scale_log2 (DEVICE int32 [n_images], each 0..3), out_off,
+ * max_width / max_height and the output sizes as there; ODIC_ENULL for a null scale_log2; a value outside 0..3 leaves the
+ * image undecoded with status 1 and nothing of it written.  Every component takes libjpeg's own transform size n at the
+ * scale (jdmaster.c; jpeg.scaled_components): it starts at 8 / s and doubles while it is below 8 and 2 n·h[c] still
+ * divides (8 / s)·max h, and the same down.  Plane c is mcus_x·n·h[c] wide and mcus_y·n·v[c] high; the planes follow each
+ * other from plane_off, each rounded up to a multiple of 16 bytes (at full size that is the layout above).  The
+ * upsampling that remains, by ((8 / s)·max h) / (n·h[c]) across and the same down, is odic_jpeg3_any_decode's, with the
+ * triangle filters only while 8 / s > 1 (at 1/8 every ratio is replication).  Workspace query, status rule and
+ * containment are odic_jpeg4_decode's (test_scaled_decodes_stay_inside_their_buffers). */
+int odic_jpeg4_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace, size_t ws_bytes,
+                             void* stream);
+
 /* The last stage of that decode on its own: n_pixels interleaved C, M, Y, K bytes (DEVICE pointers) → interleaved RGB,
  * as Pillow's convert("RGB") of a CMYK image: per channel x with nk = 255 - K, t = x·nk + 128,
  * out = clip(nk - (((t >> 8) + t) >> 8), 0, 255).  invert != 0: every input sample is first replaced by 255 - x (the
@@ -440,6 +453,10 @@ typedef struct odic_jpeg_header3 {
  * (test_layout_decode_stays_inside_its_workspace). */
 size_t odic_jpeg3_any_workspace_bytes(const odic_jpeg_batch* batch);
 int odic_jpeg3_any_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
+
+/* odic_jpeg4_decode_scaled for odic_jpeg_header3 records: the same scale_log2, transform sizes, planes and contract. */
+int odic_jpeg3_any_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace,
+                                 size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Progressive files (8-bit SOF2 Huffman, 3 YCbCr components, the samplings above — sampling 3 included: one component,
@@ -534,7 +551,8 @@ int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* batch, const
  * frame's MCUs (largest factors) whichever components it names, a single-component scan the component's own raster.
  * A record that breaks the frame rules, or a scan of it whose mask names a component the frame lacks, is not decoded.
  * An image with status 1 — by these rules or by those of odic_jpeg_decode_progressive — has none of its pixels written.
- * Upsampling and colour are odic_jpeg3_any_decode's (three components) and odic_jpeg4_decode's (four).  Full size only.
+ * Upsampling and colour are odic_jpeg3_any_decode's (three components) and odic_jpeg4_decode's (four); at a reduced
+ * scale (odic_jpeg_decode_progressive_any_scaled) those of their _scaled forms.
  * ------------------------------------------------------------------------------------------- */
 typedef struct odic_jpeg_prog_header_any {
   int64_t out_off, coef_off, plane_off;
@@ -551,6 +569,11 @@ typedef struct odic_jpeg_prog_header_any {
  * store whole words. */
 size_t odic_jpeg_progressive_any_workspace_bytes(const odic_jpeg_prog_batch* batch);
 int odic_jpeg_decode_progressive_any(const odic_jpeg_prog_batch* batch, void* workspace, size_t ws_bytes, void* stream);
+
+/* odic_jpeg4_decode_scaled / odic_jpeg3_any_decode_scaled for odic_jpeg_prog_header_any records: the scans decode as at
+ * full size, the inverse transforms, planes, upsampling and output follow scale_log2 as there. */
+int odic_jpeg_decode_progressive_any_scaled(const odic_jpeg_prog_batch* batch, const int32_t* scale_log2,
+                                            void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Swin (shifted-)window attention core  (WindowAttention.forward swin_transformer_mod.py:193-211

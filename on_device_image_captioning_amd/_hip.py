@@ -168,6 +168,9 @@ _SIGNATURES = {
     "odic_jpeg3_any_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
     "odic_jpeg_progressive_any_workspace_bytes": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
     "odic_jpeg_decode_progressive_any": (C.c_int, [C.POINTER(JpegProgBatch), _P, C.c_size_t, _P]),
+    "odic_jpeg4_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
+    "odic_jpeg3_any_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
+    "odic_jpeg_decode_progressive_any_scaled": (C.c_int, [C.POINTER(JpegProgBatch), _P, _P, C.c_size_t, _P]),
     "odic_cider_vectorize": (C.c_int, [_P, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, C.c_double, _P, _I64, _P]),
     "odic_cider_pairs": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _I32, _P, _I64, _P]),
     "odic_bleu_stats": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P]),

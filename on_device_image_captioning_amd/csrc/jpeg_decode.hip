@@ -41,7 +41,7 @@
 // component with its own sampling, four quantisation and eight Huffman tables.  The launches up to the coefficients are
 // the same kernels, templates over the header type (Frame<Header>: blocks per MCU and the component of each block); the
 // IDCT writes four planes and jpeg_color4_kernel upsamples each, then applies YCCK → CMYK, Pillow's inversion and
-// Pillow's CMYK → RGB: np.asarray(PIL.Image.open(f).convert("RGB")).  Full size only.
+// Pillow's CMYK → RGB: np.asarray(PIL.Image.open(f).convert("RGB")).
 //
 // Three-component frames at any other sampling layout libjpeg decodes (4:4:0, 4:1:1, 4:1:0, chroma sub-sampled one way
 // under a 2x2 luma, a component 0 that is not the largest), stored as YCbCr or as RGB (odic_jpeg3_any_decode), have the
@@ -52,6 +52,11 @@
 // Progressive files of those two kinds (odic_jpeg_decode_progressive_any) have the record odic_jpeg_prog_header_any:
 // the progressive decode kernel and its coding procedures instantiated for per-component block geometry (ProgGeo), then
 // the same per-component IDCT and the two colour kernels above.
+//
+// These three records decode at 1 / 2, 1 / 4, 1 / 8 as well (odic_jpeg4_decode_scaled, odic_jpeg3_any_decode_scaled,
+// odic_jpeg_decode_progressive_any_scaled): every component at libjpeg's own transform size for the scale
+// (scaled_size_own), planes at those sizes (plane_bytes_own), and the upsampling that remains through upsampled_by(),
+// with the triangle filters while the smallest transform is above 1x1.
 //
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
@@ -881,6 +886,18 @@ __device__ __forceinline__ void scaled_sizes(int sampling, int lg, int& ny, int&
   nc = (sampling == 2 && lg > 0) ? 2 * ny : ny;
 }
 
+// The same rule for a component of a frame with per-component sampling (hc, vc; hm, vm: the frame's largest factors):
+// doubling must keep the block on the largest component's grid in both directions.  4:2:0 chroma at 1/2 reaches 8,
+// 4:2:2 chroma stays, 4:1:1 chroma never doubles; lg = 0 gives 8.  The factors are clamped to 1..4, which changes
+// nothing for a record the parser made and keeps one that breaks its rules away from a zero divisor.
+__device__ __forceinline__ int factor14(int f) { return min(max(f, 1), 4); }
+__device__ __forceinline__ int scaled_size_own(int hc, int vc, int hm, int vm, int lg) {
+  const int mn = 8 >> lg;
+  int n = mn;
+  while (n < 8 && (hm * mn) % (hc * n * 2) == 0 && (vm * mn) % (vc * n * 2) == 0) n *= 2;
+  return n;
+}
+
 // row / column i is an input of the n-point transform
 __device__ __forceinline__ bool idct_reads(int n, int i) {
   return n == 8 || (n == 4 ? i != 4 : (n == 2 ? (i < 2 || (i & 1)) : i == 0));
@@ -893,44 +910,64 @@ struct BlockGeo {
   int comp, n, hc, vc, jx, jy;
   long plane;
 };
-// three components or gray: component 0 at the luma sampling with transform size ny, the others 1x1 with size nc
+// every component with its own sampling (odic_jpeg_header4: kC = 4, odic_jpeg_header3: kC = 3): the planes follow
+// each other in component order, plane c at the component's transform size n (8 at full size), each rounded up to a
+// multiple of 16 bytes, which a plane of 8x8 blocks is anyway and which keeps the n-aligned row stores of the IDCT
+// aligned behind a plane of 1x1 or 2x2 blocks
 template <typename Header>
-__device__ __forceinline__ BlockGeo block_geo(const Header& h, int j, int ny, int nc) {
-  const int nY = luma_blocks(h.sampling), hy = luma_h(h.sampling), vy = luma_v(h.sampling);
-  BlockGeo g;
-  g.comp = j < nY ? 0 : j - nY + 1;
-  if (g.comp == 0) {
-    g.n = ny; g.hc = hy; g.vc = vy; g.jx = j % hy; g.jy = j / hy; g.plane = 0;
-  } else {
-    const long ysz = (long)h.mcus_x * ny * hy * h.mcus_y * ny * vy, csz = (long)h.mcus_x * nc * h.mcus_y * nc;
-    g.n = nc; g.hc = 1; g.vc = 1; g.jx = 0; g.jy = 0; g.plane = ysz + (g.comp - 1) * csz;
-  }
-  return g;
+__device__ __forceinline__ long plane_bytes_own(const Header& h, int c, int n) {
+  return ((long)h.mcus_x * n * h.h[c] * h.mcus_y * n * h.v[c] + 15) & ~15L;
 }
-// every component with its own sampling (odic_jpeg_header4: kC = 4, odic_jpeg_header3: kC = 3), full size only: the
-// planes follow each other in component order
-template <typename Header>
-__device__ __forceinline__ long plane_bytes4(const Header& h, int c) {
-  return (long)h.mcus_x * 8 * h.h[c] * h.mcus_y * 8 * h.v[c];
+// the largest factors of the record's first kC components, each clamped to 1..4
+template <int kC, typename Header>
+__device__ __forceinline__ void largest_factors(const Header& h, int& hm, int& vm) {
+  hm = vm = 1;
+  for (int c = 0; c < kC; ++c) {
+    hm = max(hm, factor14(h.h[c]));
+    vm = max(vm, factor14(h.v[c]));
+  }
 }
 template <int kC, typename Header>
-__device__ __forceinline__ BlockGeo block_geo_own(const Header& h, int j) {
+__device__ __forceinline__ BlockGeo block_geo_own(const Header& h, int j, int lg) {
+  int hm = 1, vm = 1;
+  if (lg) largest_factors<kC>(h, hm, vm);
   BlockGeo g{kC - 1, 8, h.h[kC - 1], h.v[kC - 1], 0, 0, 0};
   for (int c = 0; c < kC; ++c) {
+    const int n = lg ? scaled_size_own(factor14(h.h[c]), factor14(h.v[c]), hm, vm, lg) : 8;
     const int nb = h.h[c] * h.v[c];
     if (j < nb || c == kC - 1) {
-      g.comp = c; g.hc = h.h[c]; g.vc = h.v[c]; g.jx = j % g.hc; g.jy = min(j / g.hc, g.vc - 1);
+      g.comp = c; g.n = n; g.hc = h.h[c]; g.vc = h.v[c]; g.jx = j % g.hc; g.jy = min(j / g.hc, g.vc - 1);
       break;
     }
     j -= nb;
-    g.plane += plane_bytes4(h, c);
+    g.plane += plane_bytes_own(h, c, n);
   }
   return g;
 }
-__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header4& h, int j, int, int) { return block_geo_own<4>(h, j); }
-__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_header3& h, int j, int, int) { return block_geo_own<3>(h, j); }
-__device__ __forceinline__ BlockGeo block_geo(const odic_jpeg_prog_header_any& h, int j, int, int) {
-  return h.ncomp == 4 ? block_geo_own<4>(h, j) : block_geo_own<3>(h, j);
+// Block j of an MCU of any record at scale 1 / 2^lg (kScaled = false: lg = 0).  Three components or gray at the common
+// samplings: component 0 at the luma sampling with transform size ny, the others 1x1 with size nc.
+template <bool kScaled, typename Header>
+__device__ __forceinline__ BlockGeo block_geo(const Header& h, int j, int lg) {
+  if constexpr (std::is_same<Header, odic_jpeg_header4>::value) {
+    return block_geo_own<4>(h, j, kScaled ? lg : 0);
+  } else if constexpr (std::is_same<Header, odic_jpeg_header3>::value) {
+    return block_geo_own<3>(h, j, kScaled ? lg : 0);
+  } else if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) {
+    return h.ncomp == 4 ? block_geo_own<4>(h, j, kScaled ? lg : 0) : block_geo_own<3>(h, j, kScaled ? lg : 0);
+  } else {
+    int ny = 8, nc = 8;
+    if constexpr (kScaled) scaled_sizes(h.sampling, lg, ny, nc);
+    const int nY = luma_blocks(h.sampling), hy = luma_h(h.sampling), vy = luma_v(h.sampling);
+    BlockGeo g;
+    g.comp = j < nY ? 0 : j - nY + 1;
+    if (g.comp == 0) {
+      g.n = ny; g.hc = hy; g.vc = vy; g.jx = j % hy; g.jy = j / hy; g.plane = 0;
+    } else {
+      const long ysz = (long)h.mcus_x * ny * hy * h.mcus_y * ny * vy, csz = (long)h.mcus_x * nc * h.mcus_y * nc;
+      g.n = nc; g.hc = 1; g.vc = 1; g.jx = 0; g.jy = 0; g.plane = ysz + (g.comp - 1) * csz;
+    }
+    return g;
+  }
 }
 // the records whose frame rules are checked on the device (layout_ok): an image that breaks them is not decoded
 template <typename Header>
@@ -954,9 +991,7 @@ __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int i
   if ((long)blockIdx.x * 32 >= nblocks) return;
   const bool live = b < nblocks;
   const int j = (int)(live ? b % bpm : 0);
-  int ny = 8, nc = 8;
-  if constexpr (kScaled) scaled_sizes(h.sampling, lg, ny, nc);
-  const BlockGeo g = block_geo(h, j, ny, nc);
+  const BlockGeo g = block_geo<kScaled>(h, j, lg);
   const int comp = g.comp, n = g.n;
   bool outside = false;                                       // a value where libjpeg-turbo's SIMD and C IDCTs part
   if (live && idct_reads(n, lane)) {                          // column `lane`
@@ -1072,11 +1107,12 @@ __device__ __forceinline__ void ycc_rgb_pixel(int yv, int cb, int cr, unsigned c
 // upsampled() above, fancy unless the plane is at most two samples wide; (1, 2) is h1v2_fancy_upsample at every width:
 // three parts of the nearer row and one of the farther, the row above for an upper output row (bias 1) and below for a
 // lower one (bias 2), the plane's first and last real rows standing in for the rows outside it; every other integral
-// ratio is int_upsample: replication.
+// ratio is int_upsample: replication.  fancy = false (a scaled decode whose smallest transform is 1x1, where jdsample.c
+// drops the triangle filters): replication at every ratio.
 __device__ __forceinline__ int upsampled_by(const unsigned char* __restrict__ P, int cw, int x, int y, int rh, int rv,
-                                            int dw, int dh) {
-  if (rh == 2 && rv <= 2) return upsampled(P, cw, x, y, rv == 2, dw <= 2, dw, dh);
-  if (rh == 1 && rv == 2) {
+                                            int dw, int dh, bool fancy = true) {
+  if (rh == 2 && rv <= 2) return upsampled(P, cw, x, y, rv == 2, dw <= 2 || !fancy, dw, dh);
+  if (rh == 1 && rv == 2 && fancy) {
     const int r = y >> 1, odd = y & 1;
     const int rn = odd ? min(r + 1, dh - 1) : max(r - 1, 0);
     return (3 * P[(long)r * cw + x] + P[(long)rn * cw + x] + 1 + odd) >> 2;
@@ -1217,34 +1253,54 @@ __global__ __launch_bounds__(256) void cmyk_to_rgb8_kernel(const unsigned char* 
   store_rgb4(rgb + 3 * p0, px, n);
 }
 
-// Four consecutive pixels of the image's H·W per lane: every component is read at its own sampling (a component at
-// component 0's sampling lies on the output grid, a 1x1 one under 2x1 / 2x2 is upsampled as chroma is above, K
-// included), then the chain of the comment above; plus the per-image status.
-template <typename Header>                                      // odic_jpeg_header4 or odic_jpeg_prog_header_any
-__global__ __launch_bounds__(256) void jpeg_color4_kernel(const Header* __restrict__ hdrs, Ws ws,
-                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
-  const int img = blockIdx.y;
-  const Header& h = hdrs[img];
+// One component as the two per-component colour kernels read it at scale 1 / 2^lg: its plane (pw samples a row) at
+// the transform size of scaled_size_own(), the integral ratios (rh, rv) of the output grid to it, and its real samples
+// dw x dh (jdmaster.c: the component's downsampled size, ceil(W·h·n / (8 hmax)) across).  At lg = 0 these are the
+// full-size planes, the ratios of the sampling factors and ceil(W·h / hmax).
+struct CompPlane {
+  const unsigned char* P;
+  int pw, rh, rv, dw, dh;
+};
+template <int kC, typename Header>
+__device__ __forceinline__ void comp_planes(const Header& h, const Ws& ws, int lg, CompPlane* cp) {
+  int hm, vm;
+  largest_factors<kC>(h, hm, vm);
+  const int mn = 8 >> lg;
+  const unsigned char* base = ws.planes + h.plane_off;
+  for (int c = 0; c < kC; ++c) {
+    const int hc = factor14(h.h[c]), vc = factor14(h.v[c]);
+    const int n = lg ? scaled_size_own(hc, vc, hm, vm, lg) : 8;
+    cp[c].P = base;
+    cp[c].pw = h.mcus_x * n * h.h[c];
+    cp[c].rh = max(hm * mn / (hc * n), 1);
+    cp[c].rv = max(vm * mn / (vc * n), 1);
+    cp[c].dw = (int)(((long)h.width * hc * n + hm * 8 - 1) / (hm * 8));
+    cp[c].dh = (int)(((long)h.height * vc * n + vm * 8 - 1) / (vm * 8));
+    base += plane_bytes_own(h, c, n);
+  }
+}
+
+// Four consecutive pixels of the image's H·W per lane (of ceil(W / s) · ceil(H / s) at scale 1 / s = 1 / 2^lg; kScaled =
+// false is the full-size decode, lg = 0): every component is read at its own sampling through upsampled_by() (a
+// component at component 0's sampling lies on the output grid, a 1x1 one under 2x1 / 2x2 is upsampled as chroma is
+// above, K included; at a reduced scale by the ratios that libjpeg's transform sizes leave), then the chain of the
+// comment above; plus the per-image status.
+template <bool kScaled, typename Header>                        // odic_jpeg_header4 or odic_jpeg_prog_header_any
+__device__ __forceinline__ void color4_pixels(const Header& h, const Ws& ws, int img, int lg_in,
+                                              unsigned char* __restrict__ out, int* __restrict__ status) {
   if (colour_comps(h) != 4) return;
+  const int lg = kScaled ? lg_in : 0;
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
   const int* st = ws.state + kStateWords * img;
   if (p0 == 0) status[img] = image_status_ok(h, st) ? 0 : 1;
-  const int W = h.width, H = h.height;
+  const int round = (1 << lg) - 1;
+  const int W = (h.width + round) >> lg, H = (h.height + round) >> lg;
   const long npix = (long)W * H;
   if (!pixels_wanted(h, st) || p0 >= npix) return;
   const int n = (int)min((long)kColor4Pixels, npix - p0);
-  const unsigned char* P[4];
-  int pw[4];
-  bool full[4];
-  const unsigned char* base = ws.planes + h.plane_off;
-  for (int c = 0; c < 4; ++c) {
-    P[c] = base;
-    pw[c] = h.mcus_x * 8 * h.h[c];
-    full[c] = h.h[c] == h.h[0] && h.v[c] == h.v[0];
-    base += plane_bytes4(h, c);
-  }
-  const bool v2 = h.v[0] == 2;
-  const int dw = (W + 1) >> 1, dh = (H + 1) >> 1;
+  CompPlane cp[4];
+  comp_planes<4>(h, ws, lg, cp);
+  const bool fancy = lg < 3;
   unsigned char px[3 * kColor4Pixels];
   for (int i = 0; i < n; ++i) {
     const long p = p0 + i;
@@ -1252,7 +1308,7 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(const Header* __restri
     int s[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      s[c] = full[c] ? P[c][(long)y * pw[c] + x] : upsampled(P[c], pw[c], x, y, v2, dw <= 2, dw, dh);
+      s[c] = upsampled_by(cp[c].P, cp[c].pw, x, y, cp[c].rh, cp[c].rv, cp[c].dw, cp[c].dh, fancy);
     if (colour_flag(h)) {
       const int cb = s[1] - 128, cr = s[2] - 128, yv = s[0];
       s[0] = 255 - clamp255(yv + ((kCrR * cr + 32768) >> 16));
@@ -1264,43 +1320,34 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(const Header* __restri
   store_rgb4(out + h.out_off + 3 * p0, px, n);
 }
 
-// odic_jpeg_header3, in jpeg_color4_kernel's form: four consecutive pixels of the image's H·W per lane, every component
-// through upsampled_by() at its own ratio to the largest sampling — component 0 too, where it is not the largest —
-// then ycc_rgb_convert, or the three samples as they are for an RGB file; plus the per-image status.  A record that
-// layout_ok() refuses has status 1 and no pixels.
-template <typename Header>                                      // odic_jpeg_header3 or odic_jpeg_prog_header_any
-__global__ __launch_bounds__(256) void jpeg_color3_kernel(const Header* __restrict__ hdrs, Ws ws,
-                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
-  const int img = blockIdx.y;
-  const Header& h = hdrs[img];
+// odic_jpeg_header3, in color4_pixels' form: four consecutive pixels per lane, every component through upsampled_by()
+// at its own ratio to the largest sampling — component 0 too, where it is not the largest — then ycc_rgb_convert, or the
+// three samples as they are for an RGB file; plus the per-image status.  A record that layout_ok() refuses has status 1
+// and no pixels.
+template <bool kScaled, typename Header>                        // odic_jpeg_header3 or odic_jpeg_prog_header_any
+__device__ __forceinline__ void color3_pixels(const Header& h, const Ws& ws, int img, int lg_in,
+                                              unsigned char* __restrict__ out, int* __restrict__ status) {
   if (colour_comps(h) != 3) return;
+  const int lg = kScaled ? lg_in : 0;
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
   const int* st = ws.state + kStateWords * img;
   if (p0 == 0) status[img] = image_status_ok(h, st) ? 0 : 1;
-  const int W = h.width, H = h.height;
+  const int round = (1 << lg) - 1;
+  const int W = (h.width + round) >> lg, H = (h.height + round) >> lg;
   const long npix = (long)W * H;
   if (!pixels_wanted(h, st) || p0 >= npix) return;
   const int n = (int)min((long)kColor4Pixels, npix - p0);
-  const int hm = max(h.h[0], max(h.h[1], h.h[2])), vm = max(h.v[0], max(h.v[1], h.v[2]));
-  const unsigned char* P[3];
-  int pw[3], rh[3], rv[3], dw[3], dh[3];
-  const unsigned char* base = ws.planes + h.plane_off;
-  for (int c = 0; c < 3; ++c) {
-    P[c] = base;
-    pw[c] = h.mcus_x * 8 * h.h[c];
-    rh[c] = hm / h.h[c];
-    rv[c] = vm / h.v[c];
-    dw[c] = (int)(((long)W * h.h[c] + hm - 1) / hm);         // jdinput.c: the component's downsampled size
-    dh[c] = (int)(((long)H * h.v[c] + vm - 1) / vm);
-    base += plane_bytes4(h, c);
-  }
+  CompPlane cp[3];
+  comp_planes<3>(h, ws, lg, cp);
+  const bool fancy = lg < 3;
   unsigned char px[3 * kColor4Pixels];
   for (int i = 0; i < n; ++i) {
     const long p = p0 + i;
     const int y = (int)(p / W), x = (int)(p - (long)y * W);
     int s[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s[c] = upsampled_by(P[c], pw[c], x, y, rh[c], rv[c], dw[c], dh[c]);
+    for (int c = 0; c < 3; ++c)
+      s[c] = upsampled_by(cp[c].P, cp[c].pw, x, y, cp[c].rh, cp[c].rv, cp[c].dw, cp[c].dh, fancy);
     if (colour_flag(h)) {
       for (int c = 0; c < 3; ++c) px[3 * i + c] = (unsigned char)s[c];
     } else {
@@ -1308,6 +1355,35 @@ __global__ __launch_bounds__(256) void jpeg_color3_kernel(const Header* __restri
     }
   }
   store_rgb4(out + h.out_off + 3 * p0, px, n);
+}
+
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_color4_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
+  color4_pixels<false>(hdrs[blockIdx.y], ws, blockIdx.y, 0, out, status);
+}
+
+template <typename Header>
+__global__ __launch_bounds__(256) void jpeg_color3_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
+  color3_pixels<false>(hdrs[blockIdx.y], ws, blockIdx.y, 0, out, status);
+}
+
+// The two at scale_log2[image] = 0..3.  Not a scale: nothing was decoded (jpeg_idct_scaled_kernel), nothing is written,
+// and the kernel of the image's component count reports status 1.
+template <int kC, typename Header>
+__global__ __launch_bounds__(256) void jpeg_color_own_scaled_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                                    const int* __restrict__ scale_log2,
+                                                                    unsigned char* __restrict__ out,
+                                                                    int* __restrict__ status) {
+  const int img = blockIdx.y, lg = scale_log2[img];
+  const Header& h = hdrs[img];
+  if ((unsigned)lg > 3u) {
+    if (colour_comps(h) == kC && blockIdx.x == 0 && threadIdx.x == 0) status[img] = 1;
+    return;
+  }
+  if constexpr (kC == 4) color4_pixels<true>(h, ws, img, lg, out, status);
+  else color3_pixels<true>(h, ws, img, lg, out, status);
 }
 
 
@@ -1757,8 +1833,33 @@ void launch_idct_color(const Batch* b, const Header* hdrs, const Ws& ws, const i
   }
 }
 
-// Header: odic_jpeg_header (three components or gray), odic_jpeg_header4 (four; full size only) or odic_jpeg_header3
-// (three at any sampling layout; full size only)
+// The same for the records with per-component sampling: the per-component IDCT and the colour kernel of the record's
+// component count (both for odic_jpeg_prog_header_any, each of which takes the images of its count), four pixels per
+// lane; max_width / max_height are those of the scaled sizes.
+template <typename Header, typename Batch>
+void launch_idct_color_own(const Batch* b, const Header* hdrs, const Ws& ws, const int32_t* scale_log2, hipStream_t s) {
+  constexpr bool k3 = !std::is_same<Header, odic_jpeg_header4>::value;
+  constexpr bool k4 = !std::is_same<Header, odic_jpeg_header3>::value;
+  const int n = b->n_images;
+  const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
+  const dim3 igrid((unsigned)((b->max_blocks + 31) / 32), n), cgrid((unsigned)((lanes + 255) / 256), n);
+  if (scale_log2) {
+    hipLaunchKernelGGL(jpeg_idct_scaled_kernel<Header>, igrid, dim3(256), 0, s, hdrs, ws, scale_log2);
+    if constexpr (k3)
+      hipLaunchKernelGGL((jpeg_color_own_scaled_kernel<3, Header>), cgrid, dim3(256), 0, s, hdrs, ws, scale_log2, b->out,
+                         b->status);
+    if constexpr (k4)
+      hipLaunchKernelGGL((jpeg_color_own_scaled_kernel<4, Header>), cgrid, dim3(256), 0, s, hdrs, ws, scale_log2, b->out,
+                         b->status);
+  } else {
+    hipLaunchKernelGGL(jpeg_idct_kernel<Header>, igrid, dim3(256), 0, s, hdrs, ws);
+    if constexpr (k3) hipLaunchKernelGGL(jpeg_color3_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+    if constexpr (k4) hipLaunchKernelGGL(jpeg_color4_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+  }
+}
+
+// Header: odic_jpeg_header (three components or gray), odic_jpeg_header4 (four) or odic_jpeg_header3 (three at any
+// sampling layout)
 template <typename Header>
 int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream,
                     const int32_t* scale_log2) {
@@ -1786,15 +1887,8 @@ int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, 
   hipLaunchKernelGGL(jpeg_block_scan_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
   hipLaunchKernelGGL(jpeg_writeout_kernel<Header>, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
   hipLaunchKernelGGL(jpeg_dc_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
-  if constexpr (!std::is_same<Header, odic_jpeg_header>::value) {       // per-component sampling: full size only
-    const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
-    const dim3 cgrid((unsigned)((lanes + 255) / 256), n);
-    hipLaunchKernelGGL(jpeg_idct_kernel<Header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs,
-                       ws);
-    if constexpr (std::is_same<Header, odic_jpeg_header4>::value)
-      hipLaunchKernelGGL(jpeg_color4_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
-    else
-      hipLaunchKernelGGL(jpeg_color3_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+  if constexpr (!std::is_same<Header, odic_jpeg_header>::value) {       // per-component sampling
+    launch_idct_color_own(b, hdrs, ws, scale_log2, s);
   } else {
     launch_idct_color(b, hdrs, ws, scale_log2, s);
   }
@@ -1802,7 +1896,7 @@ int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, 
 }
 
 // Header: odic_jpeg_prog_header (three components at the common samplings, or gray) or odic_jpeg_prog_header_any
-// (per-component sampling, three or four components; full size only)
+// (per-component sampling, three or four components)
 template <typename Header>
 int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes, void* stream,
                        const int32_t* scale_log2) {
@@ -1826,12 +1920,7 @@ int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws
                        dim3(b->level_intervals[l], b->level_first[l + 1] - b->level_first[l]), dim3(64), 0, s, hdrs, scans,
                        tables, ws, b->level_first[l], n, b->n_tables);
   if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) {
-    const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
-    const dim3 cgrid((unsigned)((lanes + 255) / 256), n);
-    hipLaunchKernelGGL(jpeg_idct_kernel<Header>, dim3((unsigned)((b->max_blocks + 31) / 32), n), dim3(256), 0, s, hdrs,
-                       ws);
-    hipLaunchKernelGGL(jpeg_color3_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
-    hipLaunchKernelGGL(jpeg_color4_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+    launch_idct_color_own(b, hdrs, ws, scale_log2, s);
   } else {
     launch_idct_color(b, hdrs, ws, scale_log2, s);
   }
@@ -1894,6 +1983,24 @@ extern "C" size_t odic_jpeg_progressive_any_workspace_bytes(const odic_jpeg_prog
 extern "C" int odic_jpeg_decode_progressive_any(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes,
                                                 void* stream) {
   return decode_progressive<odic_jpeg_prog_header_any>(b, workspace, ws_bytes, stream, nullptr);
+}
+
+extern "C" int odic_jpeg4_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
+                                        size_t ws_bytes, void* stream) {
+  if (!scale_log2) return ODIC_ENULL;
+  return decode_baseline<odic_jpeg_header4>(b, workspace, ws_bytes, stream, scale_log2);
+}
+
+extern "C" int odic_jpeg3_any_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
+                                            size_t ws_bytes, void* stream) {
+  if (!scale_log2) return ODIC_ENULL;
+  return decode_baseline<odic_jpeg_header3>(b, workspace, ws_bytes, stream, scale_log2);
+}
+
+extern "C" int odic_jpeg_decode_progressive_any_scaled(const odic_jpeg_prog_batch* b, const int32_t* scale_log2,
+                                                       void* workspace, size_t ws_bytes, void* stream) {
+  if (!scale_log2) return ODIC_ENULL;
+  return decode_progressive<odic_jpeg_prog_header_any>(b, workspace, ws_bytes, stream, scale_log2);
 }
 
 extern "C" int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* b, const int32_t* scale_log2,

@@ -47,7 +47,8 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # (odic_jpeg4_decode) instead of leaving the batch for PIL.  With `layouts="all"` so are baseline three-component
 # JPEGs at the sampling layouts and colour spaces the common decode turns away (odic_jpeg3_any_decode: 4:4:0, 4:1:1,
 # 4:1:0, RGB-stored files, ...).  With `progressive="device"` beside either keyword the progressive files of that kind are
-# decoded on the device as well (odic_jpeg_decode_progressive_any).
+# decoded on the device as well (odic_jpeg_decode_progressive_any).  Under a draft request those four kinds go to PIL
+# unless `draft_layouts="all"`, which decodes them at the draft scale on the device (the three _scaled entry points).
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -234,7 +235,7 @@ class DevicePreprocessor:
 
     def from_files(self, paths, decode: str = "host", draft: bool = False, regions=None,
                    non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host",
-                   layouts: str = "common") -> torch.Tensor:
+                   layouts: str = "common", draft_layouts: str = "common") -> torch.Tensor:
         """JPEG/PNG files → fp32 [B,3,S,S].  decode="host": PIL decode (non-RGB files become a black canvas as in
         the reference) + device pipeline; decode="device": the file bytes go to `from_jpeg_bytes` (same result).
         non_rgb="convert": a file of any other mode (L, LA, P, RGBA, I;16, CMYK, ...) is read as
@@ -251,21 +252,27 @@ class DevicePreprocessor:
         for either value of `decode` (torch.equal between them); region boxes are in oriented coordinates.  The default
         "ignore" reads the stored pixel grid, as the reference does.
         cmyk="device" (needs non_rgb="convert"): with decode="device" it is passed on to `from_jpeg_bytes`, where
-        baseline CMYK / YCCK JPEGs are decoded on the device (not under a draft request: there are no draft scales for
-        four components); decode="host" ignores it.  The tensor is the same either way.
+        baseline CMYK / YCCK JPEGs are decoded on the device (under a draft request only with draft_layouts="all");
+        decode="host" ignores it.  The tensor is the same either way.
         layouts="all": likewise passed on to `from_jpeg_bytes` with decode="device", where baseline three-component
-        JPEGs at any sampling layout libjpeg decodes, and RGB-stored ones, are decoded on the device (not under a draft
-        request); decode="host" ignores it.  The tensor is the same either way."""
-        from .jpeg import check_cmyk, check_layouts, check_non_rgb, check_orientation
+        JPEGs at any sampling layout libjpeg decodes, and RGB-stored ones, are decoded on the device (under a draft
+        request only with draft_layouts="all"); decode="host" ignores it.  The tensor is the same either way.
+        draft_layouts="all": with decode="device" and draft=True the files of cmyk= and layouts= are decoded on the
+        device at the draft scale instead of going to PIL (`decode_jpeg`); decode="host" ignores it, and so does a call
+        without a draft.  The tensor is the same either way."""
+        from .jpeg import check_cmyk, check_draft_layouts, check_layouts, check_non_rgb, check_orientation
         check_non_rgb(non_rgb)
         check_orientation(orientation)
         check_cmyk(cmyk, non_rgb)
         check_layouts(layouts)
+        check_draft_layouts(draft_layouts)
         exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's calls stay as they are
         if cmyk != "host":
             exif["cmyk"] = cmyk
         if layouts != "common":
             exif["layouts"] = layouts
+        if draft_layouts != "common":
+            exif["draft_layouts"] = draft_layouts
         if decode == "device":
             blobs = []
             for p in paths:
@@ -276,6 +283,7 @@ class DevicePreprocessor:
             raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
         exif.pop("cmyk", None)
         exif.pop("layouts", None)
+        exif.pop("draft_layouts", None)
         arrays = [self._pil_rgb(Image.open(p), (self.S, self.S) if draft else None, non_rgb, **exif) for p in paths]
         if regions is None:
             return self(arrays)
@@ -343,7 +351,7 @@ class DevicePreprocessor:
 
     def decode_jpeg(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4, progressive: str = "host",
                     draft=None, non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host",
-                    layouts: str = "common"):
+                    layouts: str = "common", draft_layouts: str = "common"):
         """Compressed files (bytes) → list of uint8 (H,W,3) RGB tensors on the device, each equal to
         np.asarray(PIL.Image.open(f)) (an all-black canvas for non-RGB files, as the host path; with
         non_rgb="convert" each equals np.asarray(PIL.Image.open(f).convert("RGB")) instead: one-component JPEGs take the
@@ -366,22 +374,28 @@ class DevicePreprocessor:
         measured): baseline four-component JPEGs — CMYK, or YCCK by Adobe transform 2 — that
         `jpeg.parse` admits are decoded by one odic_jpeg4_decode call in the same upload and status read-back, route
         "device-cmyk", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  Progressive four-component files
-        stay with PIL unless progressive="device" is given too (below), and so do all of them under a draft request:
-        there are no draft scales for this layout.
+        stay with PIL unless progressive="device" is given too (below), and so do all of them under a draft request
+        unless draft_layouts="all" (below).
         layouts="all" (the default "common" leaves them to PIL until the device route is measured):
         baseline three-component JPEGs that only `jpeg.parse(f, layouts="all")` admits — luma at 1x2 (4:4:0), 4x1
         (4:1:1), 4x2 (4:1:0), chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest, files
         stored as RGB — are decoded by one odic_jpeg3_any_decode call in the same upload and status read-back, route
         "device-layout", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  A file the common rules admit keeps
         its route.  Progressive files with these layouts stay with PIL unless progressive="device" is given too, and
-        so do all of them under a draft request.
+        so do all of them under a draft request unless draft_layouts="all".
         progressive="device" together with cmyk="device", or together with layouts="all" (both opt-ins; any other
         combination of keywords does exactly what it did): the progressive files of that kind — SOF2 frames of four
         components, or of three at a layout only layouts="all" admits — that `jpeg.parse_progressive(f, non_rgb,
         cmyk=, layouts=)` admits are decoded by one odic_jpeg_decode_progressive_any call in the same upload and
         status read-back, routes "device-progressive-cmyk" / "device-progressive-layout" (DESIGN §4.27), each equal to
         np.asarray(PIL.Image.open(f).convert("RGB")).  Under a draft request they stay with PIL, as their baseline
-        siblings do."""
+        siblings do, unless draft_layouts="all".
+        draft_layouts="all" (the default "common" withholds cmyk= and layouts= from the parsers under a draft request,
+        so that their files go to PIL with the same request): the files those two keywords admit keep their four routes
+        under a draft and are decoded at the draft scale by odic_jpeg4_decode_scaled, odic_jpeg3_any_decode_scaled and
+        odic_jpeg_decode_progressive_any_scaled, every component at libjpeg's own transform size for that scale
+        (`jpeg.scaled_components`), each equal to what PIL makes of the file after `im.draft("RGB", draft)`
+        and `convert("RGB")`.  Without a draft request it changes nothing."""
         from . import jpeg as J
         if progressive not in ("device", "host"):
             raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
@@ -390,59 +404,29 @@ class DevicePreprocessor:
         J.check_cmyk(cmyk, non_rgb)
         opt = () if non_rgb == "black" else (non_rgb,)                   # the default's calls stay as they are
         J.check_layouts(layouts)
-        copt = {"cmyk": cmyk} if cmyk != "host" and draft is None else {}
-        if layouts != "common" and draft is None:
-            copt["layouts"] = layouts
+        J.check_draft_layouts(draft_layouts)
         if draft is not None:
             draft = (int(draft[0]), int(draft[1]))
             if draft[0] <= 0 or draft[1] <= 0:
                 raise ValueError(f"draft wants a positive (width, height), not {draft!r}")
         blobs = [bytes(b) for b in blobs]
-        hdrs = [J.parse(b, *opt, **copt) for b in blobs]
+        rp = J.plan_routes(blobs, progressive, draft, non_rgb, cmyk, layouts, draft_layouts, self.max_bytes)
+        hdrs, scales, sizes, routes = rp.hdrs, rp.scales, rp.sizes, rp.routes
+        base, prog, four, lay, pany = rp.base, rp.prog, rp.four, rp.lay, rp.pany
+        dev = rp.order
         exif = orientation != "ignore"
         turns = [J.header_orientation(h, b) if exif else 1 for h, b in zip(hdrs, blobs)]
         host_kw = {"orientation": orientation} if exif else {}           # the default's calls stay as they are
-        if progressive == "device":
-            for i, h in enumerate(hdrs):
-                if h.kind == J.HOST and h.reason == "SOF2":
-                    ph = J.parse_progressive(blobs[i], *opt)
-                    if ph.kind == J.DEVICE:
-                        hdrs[i] = ph
-                elif h.kind == J.HOST and (h.reason == J.PROG_CMYK_REASON or h.reason.startswith(J.PROG_LAYOUT_REASON)):
-                    ph = J.parse_progressive(blobs[i], *opt, **copt)     # `parse` gives these reasons under copt only
-                    if ph.kind == J.DEVICE:
-                        hdrs[i] = ph
         out = [None] * len(blobs)
-        scales = [J.draft_scale((h.width, h.height), draft) if draft is not None and h.kind != J.HOST else 1
-                  for h in hdrs]
-        sizes = [J.scaled_size((h.width, h.height), s) for h, s in zip(hdrs, scales)]        # (width, height)
-        # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
-        dev = [i for i, h in enumerate(hdrs)
-               if h.kind == J.DEVICE and sizes[i][0] * sizes[i][1] * 3 <= self.max_bytes]
-        own = lambda h: h.ncomp == 4 or getattr(h, "layout", False)      # every component with its own sampling
-        pany = [i for i in dev if isinstance(hdrs[i], J.ProgHeader) and own(hdrs[i])]
-        four = [i for i in dev if hdrs[i].ncomp == 4 and i not in pany]
-        lay = [i for i in dev if getattr(hdrs[i], "layout", False) and i not in pany]
-        base = [i for i in dev if not isinstance(hdrs[i], J.ProgHeader) and not own(hdrs[i])]
-        prog = [i for i in dev if isinstance(hdrs[i], J.ProgHeader) and i not in pany]
-        routes = ["host" if h.kind == J.DEVICE else h.kind for h in hdrs]        # a device kind left so is oversized
-        for i in dev:
-            routes[i] = "device-progressive" if isinstance(hdrs[i], J.ProgHeader) else "device"
-        for i in four:
-            routes[i] = "device-cmyk"
-        for i in lay:
-            routes[i] = "device-layout"
-        for i in pany:
-            routes[i] = "device-progressive-cmyk" if hdrs[i].ncomp == 4 else "device-progressive-layout"
         if dev:
-            order = base + prog + four + lay + pany
+            order = dev
             group4 = ([hdrs[i] for i in four], [blobs[i] for i in four]) if four or lay else ()   # without: today's call
             if lay:
                 group4 += ([hdrs[i] for i in lay], [blobs[i] for i in lay])
             status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
                                                            [hdrs[i] for i in prog], [blobs[i] for i in prog],
                                                            subseq_bits, max_sync_passes,
-                                                           [scales[i] for i in base + prog], *group4,
+                                                           [scales[i] for i in order], *group4,
                                                            **({"ahdrs": [hdrs[i] for i in pany],
                                                                "ablobs": [blobs[i] for i in pany]} if pany else {}))
             turned = []                                                  # (image, its offset in rgb): to be permuted
@@ -573,20 +557,16 @@ class DevicePreprocessor:
             if ncm:
                 cb.headers, cb.data = base + plan.cmyk_off, base + plan.data_off
                 cb.out, cb.status = rgb.data_ptr() + plan.cout_off, status.data_ptr() + 4 * (nb + npg)
-                self._hip.check(self.lib.odic_jpeg4_decode(ctypes.byref(cb), self._jpeg_ws.data_ptr(), need_c,
-                                                           self.stream.cuda_stream), "odic_jpeg4_decode")
+                decode("odic_jpeg4_decode", cb, need_c, nb + npg)
             if nly:
                 lb.headers, lb.data = base + plan.layout_off, base + plan.data_off
                 lb.out, lb.status = rgb.data_ptr() + plan.lout_off, status.data_ptr() + 4 * (nb + npg + ncm)
-                self._hip.check(self.lib.odic_jpeg3_any_decode(ctypes.byref(lb), self._jpeg_ws.data_ptr(), need_l,
-                                                               self.stream.cuda_stream), "odic_jpeg3_any_decode")
+                decode("odic_jpeg3_any_decode", lb, need_l, nb + npg + ncm)
             if npa:
                 ab.headers, ab.scans, ab.tables = (base + o for o in plan.any_off)
                 ab.data, ab.out = base + plan.data_off, rgb.data_ptr() + plan.aout_off
                 ab.status = status.data_ptr() + 4 * (nb + npg + ncm + nly)
-                self._hip.check(self.lib.odic_jpeg_decode_progressive_any(ctypes.byref(ab), self._jpeg_ws.data_ptr(),
-                                                                          need_a, self.stream.cuda_stream),
-                                "odic_jpeg_decode_progressive_any")
+                decode("odic_jpeg_decode_progressive_any", ab, need_a, nb + npg + ncm + nly)
             if npg:                                                      # last: its coefficients stay in the workspace
                 pb.headers, pb.scans, pb.tables = (base + o for o in plan.prog_off)
                 pb.data, pb.out = base + plan.data_off, rgb.data_ptr() + plan.out_bytes
@@ -609,19 +589,22 @@ class DevicePreprocessor:
     def from_jpeg_bytes(self, blobs, subseq_bits: int = 2048, max_sync_passes: int = 4,
                         progressive: str = "host", draft: bool = False, regions=None,
                         non_rgb: str = "black", orientation: str = "ignore", cmyk: str = "host",
-                        layouts: str = "common") -> torch.Tensor:
+                        layouts: str = "common", draft_layouts: str = "common") -> torch.Tensor:
         """Compressed files (bytes) → normalised fp32 [B,3,S,S]: `decode_jpeg` + the resize / normalise kernel,
         torch.equal to `from_files` on the same files (with the same `draft`: True requests (S, S) of `decode_jpeg`,
         the same `non_rgb` and the same `orientation`).
         regions: a sequence of (file index, (l, t, r, b)) → the region batch fp32 [N,3,S,S] of `resize_regions` on the
         decoded images instead; with draft=True the boxes are in the coordinates of the drafted image, with
         orientation="exif" in those of the upright one.  cmyk: as `decode_jpeg` (with draft=True four-component files
-        stay on the host route); layouts: as `decode_jpeg` (likewise)."""
+        stay on the host route unless draft_layouts="all"); layouts: as `decode_jpeg` (likewise); draft_layouts: as
+        `decode_jpeg`."""
         exif = {} if orientation == "ignore" else {"orientation": orientation}   # the default's call stays as it is
         if cmyk != "host":
             exif["cmyk"] = cmyk
         if layouts != "common":
             exif["layouts"] = layouts
+        if draft_layouts != "common":
+            exif["draft_layouts"] = draft_layouts
         imgs = self.decode_jpeg(blobs, subseq_bits, max_sync_passes, progressive,
                                 draft=(self.S, self.S) if draft else None, non_rgb=non_rgb, **exif)
         if regions is not None:

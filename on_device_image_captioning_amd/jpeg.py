@@ -25,7 +25,8 @@ sampling factors and component id the SOF declares, which libjpeg ignores for a 
 frame is `host`, where PIL converts it — unless the caller also passes cmyk="device": then a baseline four-component frame
 (CMYK, or YCCK by Adobe transform 2) that `_frame4` admits is a `device` kind with ncomp 4, the sampling of every
 component in comp_hv and the `ycck` flag; odic_jpeg4_decode reads its records (`HEADER4_DTYPE`).  To `parse`
-progressive four-component files stay `host` (`PROG_CMYK_REASON`), and so do all of them under a draft request.
+progressive four-component files stay `host` (`PROG_CMYK_REASON`); under a draft request `plan_routes` withholds the
+keyword unless draft_layouts="all", which decodes them at the draft scale (`scaled_components`).
 
 Under layouts="all" (`parse` only; the default "common" is everything above) a baseline three-component frame that the
 rules above turn away for its sampling or its colour space is a `device` kind too where `_frame3_any` admits it: every
@@ -36,7 +37,7 @@ YCbCr or as RGB (Adobe transform 0, or ids R, G, B with neither marker).  The he
 still goes to the host after that:
 
     host    fractional sampling ratios; more than 10 blocks per MCU; progressive files (`PROG_LAYOUT_REASON`), and draft
-            requests, with these layouts; non-interleaved multi-scan baseline files; arithmetic coding; 12-bit; three
+            requests unless draft_layouts="all", with these layouts; non-interleaved multi-scan baseline files; arithmetic coding; 12-bit; three
             components with an Adobe transform other than 0 and 1, or with duplicate ids
 
 `parse` keeps that sorting.  For the files it turns away with reason "SOF2", `parse_progressive` (below) reads the whole
@@ -94,6 +95,16 @@ def check_layouts(layouts):
     if layouts not in LAYOUTS:
         raise ValueError(f"layouts must be 'common' or 'all', not {layouts!r}")
     return layouts
+
+
+DRAFT_LAYOUTS = ("common", "all")                     # which layouts a draft request leaves to the device
+                                                      # ("all": also the kinds of cmyk="device" / layouts="all")
+
+
+def check_draft_layouts(draft_layouts):
+    if draft_layouts not in DRAFT_LAYOUTS:
+        raise ValueError(f"draft_layouts must be 'common' or 'all', not {draft_layouts!r}")
+    return draft_layouts
 
 
 # odic_jpeg_header (include/odic_hip.h), field for field
@@ -179,11 +190,12 @@ def parse(blob, non_rgb: str = "black", cmyk: str = "host", layouts: str = "comm
     host, where PIL converts it; the default "black" sorts both as BLACK.
     cmyk="device" (with non_rgb="convert" only): a baseline four-component frame that `_frame4` admits is a device
     kind with ncomp 4, comp_hv and `ycck`; progressive four-component files stay HOST, with a reason of their own.
-    Draft scales do not exist for this layout: a caller with a draft request leaves cmyk at "host".
+    A caller with a draft request leaves cmyk at "host" unless it decodes these files at the draft scale
+    (`plan_routes` with draft_layouts="all").
     layouts="all": a baseline three-component frame that the common rules turn away for its sampling or colour space
     and `_frame3_any` admits is a device kind with `layout` set, comp_hv and `rgb`; progressive ones stay HOST, with a
-    reason of their own.  A file the common rules admit parses as it does without the keyword.  No draft scales either:
-    a caller with a draft request leaves layouts at "common"."""
+    reason of their own.  A file the common rules admit parses as it does without the keyword.  A caller with a draft
+    request leaves layouts at "common" likewise, unless draft_layouts="all"."""
     check_non_rgb(non_rgb)
     check_cmyk(cmyk, non_rgb)
     check_layouts(layouts)
@@ -621,6 +633,78 @@ def orient_box(box, size, orientation: int, inverse: bool = False):
     return (x0, y0, x1, y1)
 
 
+@dataclass
+class RoutePlan:
+    """Who decodes each file of one `decode_jpeg` call (`plan_routes`)."""
+    hdrs: list                     # JpegHeader / ProgHeader per file
+    scales: list                   # the draft scale of each (1 without a draft request, and for a HOST kind)
+    sizes: list                    # (width, height) each decodes to
+    routes: list                   # "device", "device-progressive", "device-cmyk", "device-layout",
+                                   # "device-progressive-cmyk", "device-progressive-layout", "host" or "black"
+    base: list                     # indices of the files of each device group, in input order: odic_jpeg_decode,
+    prog: list                     # odic_jpeg_decode_progressive,
+    four: list                     # odic_jpeg4_decode,
+    lay: list                      # odic_jpeg3_any_decode,
+    pany: list                     # odic_jpeg_decode_progressive_any
+
+    @property
+    def order(self):
+        return self.base + self.prog + self.four + self.lay + self.pany
+
+
+def plan_routes(blobs, progressive="host", draft=None, non_rgb="black", cmyk="host", layouts="common",
+                draft_layouts="common", max_bytes=None) -> RoutePlan:
+    """Parse every file and sort it into its decode route: the host half of `DevicePreprocessor.decode_jpeg`, whose
+    keywords these are.  draft: None or a positive (width, height).  Under a draft request cmyk= and layouts= are
+    withheld from the parsers — their files are HOST kinds, decoded by PIL with the same request — unless
+    draft_layouts="all", which passes them through: the files keep their four route names and their scale is the one
+    `draft_scale` picks.  Without a draft request draft_layouts changes nothing.  max_bytes: a device kind whose
+    decoded image is larger goes to PIL like a HOST kind (route "host")."""
+    if progressive not in ("device", "host"):
+        raise ValueError(f"progressive must be 'device' or 'host', not {progressive!r}")
+    check_non_rgb(non_rgb)
+    check_cmyk(cmyk, non_rgb)
+    check_layouts(layouts)
+    check_draft_layouts(draft_layouts)
+    opt = () if non_rgb == "black" else (non_rgb,)                   # the default's calls stay as they are
+    own_kinds = draft is None or draft_layouts == "all"
+    copt = {"cmyk": cmyk} if cmyk != "host" and own_kinds else {}
+    if layouts != "common" and own_kinds:
+        copt["layouts"] = layouts
+    hdrs = [parse(b, *opt, **copt) for b in blobs]
+    if progressive == "device":
+        for i, h in enumerate(hdrs):
+            if h.kind == HOST and h.reason == "SOF2":
+                ph = parse_progressive(blobs[i], *opt)
+                if ph.kind == DEVICE:
+                    hdrs[i] = ph
+            elif h.kind == HOST and (h.reason == PROG_CMYK_REASON or h.reason.startswith(PROG_LAYOUT_REASON)):
+                ph = parse_progressive(blobs[i], *opt, **copt)       # `parse` gives these reasons under copt only
+                if ph.kind == DEVICE:
+                    hdrs[i] = ph
+    scales = [draft_scale((h.width, h.height), draft) if draft is not None and h.kind != HOST else 1 for h in hdrs]
+    sizes = [scaled_size((h.width, h.height), s) for h, s in zip(hdrs, scales)]          # (width, height)
+    # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
+    dev = [i for i, h in enumerate(hdrs)
+           if h.kind == DEVICE and (max_bytes is None or sizes[i][0] * sizes[i][1] * 3 <= max_bytes)]
+    own = lambda h: h.ncomp == 4 or getattr(h, "layout", False)      # every component with its own sampling
+    pany = [i for i in dev if isinstance(hdrs[i], ProgHeader) and own(hdrs[i])]
+    four = [i for i in dev if hdrs[i].ncomp == 4 and i not in pany]
+    lay = [i for i in dev if getattr(hdrs[i], "layout", False) and i not in pany]
+    base = [i for i in dev if not isinstance(hdrs[i], ProgHeader) and not own(hdrs[i])]
+    prog = [i for i in dev if isinstance(hdrs[i], ProgHeader) and i not in pany]
+    routes = ["host" if h.kind == DEVICE else h.kind for h in hdrs]          # a device kind left so is oversized
+    for i in dev:
+        routes[i] = "device-progressive" if isinstance(hdrs[i], ProgHeader) else "device"
+    for i in four:
+        routes[i] = "device-cmyk"
+    for i in lay:
+        routes[i] = "device-layout"
+    for i in pany:
+        routes[i] = "device-progressive-cmyk" if hdrs[i].ncomp == 4 else "device-progressive-layout"
+    return RoutePlan(hdrs, scales, sizes, routes, base, prog, four, lay, pany)
+
+
 _TABLE_CACHE: dict = {}
 
 
@@ -678,11 +762,41 @@ def scaled_size(size, scale):
     return (size[0] + scale - 1) // scale, (size[1] + scale - 1) // scale
 
 
+def scaled_components(comp_hv, scale):
+    """libjpeg's per-component geometry of a frame decoded at 1 / scale (scale 1, 2, 4 or 8) → [(n, rh, rv)] per
+    component: the side n in {1, 2, 4, 8} of the block its inverse transform produces and the integral upsampling
+    factors that remain across and down.  jdmaster.c: every component starts at 8 / scale and doubles while it is below
+    8 and the doubled block still divides the largest component's extent in both directions; jdsample.c then upsamples
+    by (hmax · min) / (h · n) and (vmax · min) / (v · n).  4:2:0 chroma at 1/2 is transformed at 8 and not upsampled,
+    4:2:2 chroma stays at 4 (h2v1), 4:1:1 chroma never doubles.  The triangle filters apply only while 8 / scale > 1."""
+    if scale not in (1, 2, 4, 8):
+        raise ValueError(f"scale must be 1, 2, 4 or 8, not {scale!r}")
+    mn = 8 // scale
+    hmax, vmax = max(h for h, _ in comp_hv), max(v for _, v in comp_hv)
+    out = []
+    for h, v in comp_hv:
+        n = mn
+        while n < 8 and (hmax * mn) % (h * n * 2) == 0 and (vmax * mn) % (v * n * 2) == 0:
+            n *= 2
+        out.append((n, hmax * mn // (h * n), vmax * mn // (v * n)))
+    return out
+
+
+def scaled_plane_bytes(h, scale=1):
+    """Bytes of every component's sample plane of a per-component-sampling header decoded at 1 / scale: mcus_x · n · h
+    by mcus_y · n · v samples at the component's own n (`scaled_components`), each plane rounded up to a multiple of 16
+    bytes so that the next one starts where the IDCT's n-aligned row stores need it."""
+    nmcu = h.mcus_x * h.mcus_y
+    return [(nmcu * a * b * n * n + 15) // 16 * 16
+            for (a, b), (n, _, _) in zip(h.comp_hv, scaled_components(h.comp_hv, scale))]
+
+
 def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     """The per-image part of both packers: geometry, quantisation tables and the output / coefficient / plane offsets
     into record r, the running totals and maxima into tot → (MCUs, output bytes after this image).  The record keeps
     the frame's own geometry, which the entropy decoders need; the output bytes and the maxima that size the colour
-    launch are those of the frame decoded at 1 / scale (odic_jpeg_decode_scaled)."""
+    launch are those of the frame decoded at 1 / scale (odic_jpeg_decode_scaled).  A record with per-component sampling
+    reserves its planes at the per-component transform sizes of that scale (`scaled_plane_bytes`)."""
     if scale not in (1, 2, 4, 8):
         raise ValueError(f"scale must be 1, 2, 4 or 8, not {scale!r}")
     width, height = scaled_size((h.width, h.height), scale)
@@ -705,7 +819,7 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
         r["qt"][c] = h.qtables[c]
     out_offs.append(out_bytes)
     tot["total_blocks"] += blocks
-    tot["total_plane_bytes"] += (blocks * 64 + 15) // 16 * 16
+    tot["total_plane_bytes"] += sum(scaled_plane_bytes(h, scale)) if own else (blocks * 64 + 15) // 16 * 16
     tot["max_width"] = max(tot["max_width"], width)
     tot["max_height"] = max(tot["max_height"], height)
     tot["max_blocks"] = max(tot["max_blocks"], blocks)
@@ -714,9 +828,10 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
 
 def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None, dtype=HEADER_DTYPE):
     """Header records + workspace totals for a batch of device-kind headers.
-    dtype=HEADER4_DTYPE: the four-component headers of one odic_jpeg4_decode call (no scales); their output offsets
-    are rounded up to multiples of 4, which lets the colour kernel store whole words.  dtype=HEADER3_DTYPE: the
-    `layout` headers of one odic_jpeg3_any_decode call, placed the same way.
+    dtype=HEADER4_DTYPE: the four-component headers of one odic_jpeg4_decode / odic_jpeg4_decode_scaled call; their
+    output offsets are rounded up to multiples of 4, which lets the colour kernel store whole words.
+    dtype=HEADER3_DTYPE: the `layout` headers of one odic_jpeg3_any_decode / odic_jpeg3_any_decode_scaled call, placed
+    the same way.  With scales these two place the output by `scaled_size` and the planes by `scaled_plane_bytes`.
     data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
     buffer.  scales: 1, 2, 4 or 8 per image (None: all 1), the draft scale its output is placed for.
     → (np array of `dtype` [n], dict of batch totals / maxima, list of output byte offsets, output bytes)."""
@@ -950,8 +1065,9 @@ def pack_progressive(hdrs, blob_offs, scales=None, dtype=PROG_HEADER_DTYPE):
     """Header, scan and table records + batch totals for progressive headers whose files start at blob_offs inside
     the batch's data buffer.  Scans are sorted by level (stable), which is how odic_jpeg_decode_progressive walks
     them.  scales: as `pack_headers`.  dtype=PROG_HEADER_ANY_DTYPE: the headers of one odic_jpeg_decode_progressive_any
-    call (`parse_progressive` with cmyk="device" / layouts="all"; no scales): output offsets rounded up to multiples of
-    4 as `pack_headers` does for its word-storing kinds, and the fourth DC table index of a scan in its `pad` word.
+    / odic_jpeg_decode_progressive_any_scaled call (`parse_progressive` with cmyk="device" / layouts="all"): output
+    offsets rounded up to multiples of 4 and planes placed as `pack_headers` does for its word-storing kinds, and the
+    fourth DC table index of a scan in its `pad` word.
     → (headers `dtype` [n], scans SCAN_DTYPE [m], tables TABLE_DTYPE [t], totals dict with
     level_first / level_intervals lists, output byte offsets, output bytes)."""
     n = len(hdrs)
@@ -1058,10 +1174,13 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
                       lblobs=(), ahdrs=(), ablobs=()) -> BatchPlan:
     """The layout of one device decode of the baseline files (hdrs, blobs: DEVICE-kind `parse` results and their bytes)
     and the progressive ones (phdrs, pblobs: `parse_progressive`).  scales: the draft scale of every image, baseline
-    first.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
+    first, then progressive and the groups below in their order; a list that ends early means scale 1 for the rest.
+    The int32 scale_log2 section holds the first two groups, or, where a later group has a scale above 1, every image:
+    group g's entries start at 4 · (images before it).
+    Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
     chdrs, cblobs: the four-component files (`parse(..., "convert", cmyk="device")`, ncomp 4), one more group behind the
     others: its records behind the scales, its files behind the progressive ones, its output behind theirs from the
-    next multiple of 256.  They have no scales.  Without them the plan is what it is without these arguments.
+    next multiple of 256.  Without them the plan is what it is without these arguments.
     lhdrs, lblobs: the `layout` files (`parse(..., layouts="all")`), the last group, placed by the same rule behind the
     four-component one.
     ahdrs, ablobs: the progressive files with per-component sampling (`parse_progressive(..., cmyk="device")` /
@@ -1069,7 +1188,14 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     the others', files behind the others', output from the next multiple of 256.  Without them the plan is what it is
     without these arguments."""
     nb, npg, ncm, nly, npa = len(hdrs), len(phdrs), len(chdrs), len(lhdrs), len(ahdrs)
-    scales = list(scales)[:nb + npg]
+    n_all = nb + npg + ncm + nly + npa
+    scales = list(scales)[:n_all]
+    scales += [1] * (n_all - len(scales))                # a caller that names only the first two groups: full size
+    if all(s == 1 for s in scales[nb + npg:]):           # the section then holds the first two groups, as without them
+        scales = scales[:nb + npg]
+    cscales = scales[nb + npg:nb + npg + ncm] or None
+    lscales = scales[nb + npg + ncm:nb + npg + ncm + nly] or None
+    ascales = scales[nb + npg + ncm + nly:] or None
     sections, pos = [], pad256(nb * HEADER_DTYPE.itemsize)
     ptot = prog_off = scale_off = None
     if npg:                                              # sizes only, for now: the files' offsets follow from them
@@ -1080,7 +1206,7 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
     if any(s > 1 for s in scales):
         scale_off = pos
         sections.append((pos, np.asarray([s.bit_length() - 1 for s in scales], np.int32)))
-        pos += pad256(4 * (nb + npg))
+        pos += pad256(4 * len(scales))
     cmyk_off = None
     if ncm:
         cmyk_off = pos
@@ -1091,7 +1217,7 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
         pos += pad256(nly * HEADER3_DTYPE.itemsize)
     any_off = None
     if npa:                                              # sizes only, as for the progressive group above
-        arec, asrec, atrec, atot, aout_offs, aout_bytes = pack_progressive(ahdrs, [0] * npa,
+        arec, asrec, atrec, atot, aout_offs, aout_bytes = pack_progressive(ahdrs, [0] * npa, ascales,
                                                                            dtype=PROG_HEADER_ANY_DTYPE)
         any_off = (pos, pos + pad256(arec.nbytes), pos + pad256(arec.nbytes) + pad256(asrec.nbytes))
         pos = any_off[2] + pad256(atrec.nbytes)
@@ -1113,7 +1239,7 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
         first = nb + npg
         crec, ctot, cout_offs, cout_bytes = pack_headers(
             chdrs, [o + h.data_offset for o, h in zip(starts[first:], chdrs)], starts[first + 1:first + ncm + 1],
-            subseq_bits, dtype=HEADER4_DTYPE)
+            subseq_bits, cscales, dtype=HEADER4_DTYPE)
         sections.append((cmyk_off, crec))
         cout_off = pad256(out_bytes + (pout_bytes if npg else 0))
         out_offs = out_offs + [cout_off + o for o in cout_offs]
@@ -1122,7 +1248,7 @@ def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(),
         first = nb + npg + ncm
         lrec, ltot, lout_offs, lout_bytes = pack_headers(
             lhdrs, [o + h.data_offset for o, h in zip(starts[first:], lhdrs)], starts[first + 1:first + nly + 1],
-            subseq_bits, dtype=HEADER3_DTYPE)
+            subseq_bits, lscales, dtype=HEADER3_DTYPE)
         sections.append((layout_off, lrec))
         before = cout_off + cout_bytes if ncm else out_bytes + (pout_bytes if npg else 0)
         lout_off = pad256(before)

@@ -51,6 +51,14 @@ kernel), in which the scaled kernels carry their own names; profiles/r11_jpeg_dr
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/jpeg_bench.py --draft --device-only --draft-cases large \
         --iters 4 --warmup 1
 
+--draft-layouts: the draft request on the files of cmyk="device" / layouts="all" (DESIGN §4.28): a batch of four
+3456x4608 CMYK files from Pillow's encoder (drafts at 1/8) and a batch of four 2048x1536 4:4:0 files from the tests'
+writer (two distinct pictures; drafts at 1/4), each decoded by `decode_jpeg(draft=(S, S))` and by `from_jpeg_bytes(draft=
+True)` with draft_layouts="common" (PIL decodes them, one thread) and draft_layouts="all" (the _scaled entry points),
+alternating in the same process; the two results are checked torch.equal first.
+
+    python tools/jpeg_bench.py --draft-layouts --iters 10 --warmup 2 --out profiles/jpeg_draft_layouts_bench.json
+
 --orient: EXIF orientation.  First odic_orient_rgb8 alone, device events around a run of launches, for
 each of the seven orientations at 4032x3024 and 640x480 (one image, and the batch of 16 the end-to-end case launches),
 next to `torch.Tensor.copy_` of the same bytes between two uint8 device buffers: the copy moves each byte once in and
@@ -204,6 +212,66 @@ def draft_bench(args):
                 f.write(json.dumps(line) + "\n")
 
 
+def draft_layouts_bench(args):
+    """draft_layouts="common" against "all" under a draft request: the same build, the same files, alternating."""
+    import torch
+    from PIL import Image
+    from on_device_image_captioning_amd import jpeg as J
+    from on_device_image_captioning_amd.image_utils import DevicePreprocessor
+    assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from jpeg_layout_cases import LAYOUTS, picture
+    from jpeg_layout_writer import write_jpeg3
+    S = args.size
+    pre = DevicePreprocessor(S, "cuda:0")
+    kw = dict(non_rgb="convert", cmyk="device", layouts="all")
+    cmyk = []
+    for k in range(4):
+        buf = io.BytesIO()
+        Image.fromarray(synthetic_rgb(4608, 3456, seed=k)).convert("CMYK").save(buf, format="JPEG", quality=90,
+                                                                               subsampling=2)
+        cmyk.append(buf.getvalue())
+    two = [write_jpeg3(picture(1536, 2048, seed=k, noise=True), *LAYOUTS["440"], q=12) for k in range(2)]
+    cases = [("cmyk 4:2:0-style (component 0 at 2x2)", "device-cmyk", (3456, 4608), cmyk),
+             ("4:4:0", "device-layout", (2048, 1536), [two[k % 2] for k in range(4)])]
+    lines = []
+    for name, route, (w, h), blobs in cases:
+        fns = {"decode": lambda dl: pre.decode_jpeg(blobs, draft=(S, S), draft_layouts=dl, **kw),
+               "decode_resize": lambda dl: pre.from_jpeg_bytes(blobs, draft=True, draft_layouts=dl, **kw)}
+        dev = fns["decode"]("all")
+        assert pre.last_routes == (route,) * len(blobs), pre.last_routes
+        host = fns["decode"]("common")
+        assert pre.last_routes == ("host",) * len(blobs), pre.last_routes
+        assert all(torch.equal(a, b) for a, b in zip(dev, host)), "the device's drafted pixels differ from Pillow's"
+        scale = J.draft_scale((w, h), (S, S))
+        line = {"kind": name, "route": route, "width": w, "height": h, "batch": len(blobs), "draft_scale": scale,
+                "drafted_size": list(J.scaled_size((w, h), scale)),
+                "mean_jpeg_bytes": int(np.mean([len(b) for b in blobs])), "iters": args.iters,
+                "gpu": torch.cuda.get_device_name(0)}
+        for fname, fn in fns.items():
+            for _ in range(args.warmup):
+                fn("common")
+                fn("all")
+            torch.cuda.synchronize()
+            t = {"common": [], "all": []}
+            for _ in range(args.iters):
+                for dl in ("common", "all"):
+                    t0 = time.perf_counter()
+                    fn(dl)
+                    torch.cuda.synchronize()
+                    t[dl].append(1e3 * (time.perf_counter() - t0))
+            for dl in ("common", "all"):
+                q1, med, q3 = (float(x) for x in np.percentile(t[dl], [25, 50, 75]))
+                line[f"{fname}_{dl}_ms"] = {"median": med, "q1": q1, "q3": q3, "min": float(min(t[dl]))}
+            line[f"{fname}_common_over_all"] = line[f"{fname}_common_ms"]["median"] / line[f"{fname}_all_ms"]["median"]
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.out and lines:
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def with_orientation(blob: bytes, orientation: int) -> bytes:
     """The file with an Exif APP1 that holds the Orientation tag alone, behind its JFIF APP0."""
     from PIL import Image
@@ -326,11 +394,15 @@ def main():
                     help="progressive 4:4:0 from the tests' writer and Pillow's progressive CMYK, every opt-in")
     ap.add_argument("--draft", action="store_true", help="draft off against draft on, large and small synthetic files")
     ap.add_argument("--draft-cases", choices=["all", "large"], default="all")
+    ap.add_argument("--draft-layouts", action="store_true",
+                    help="large CMYK and 4:4:0 files under a draft, draft_layouts='common' against 'all'")
     ap.add_argument("--orient", action="store_true", help="odic_orient_rgb8 against a copy; orientation='exif' end to end")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.draft:
         return draft_bench(args)
+    if args.draft_layouts:
+        return draft_layouts_bench(args)
     if args.orient:
         return orient_bench(args)
 
