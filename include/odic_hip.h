@@ -69,11 +69,12 @@ extern "C" {
  *   26: odic_topk_rows_constrained added (no-repeat n-grams, minimum length, banned words in the search).
  *       Pure additions since, the number unchanged (detect them by the symbol): odic_dynexp_fill_caches,
  *       odic_beam_reset_prefix, odic_require_beam_step, odic_cider_vectorize, odic_cider_pairs, odic_bleu_stats,
- *       odic_lcs_pairs, odic_orient_rgb8, odic_jpeg4_workspace_bytes, odic_jpeg4_decode, odic_cmyk_to_rgb8,
- *       odic_jpeg3_any_workspace_bytes, odic_jpeg3_any_decode, odic_jpeg_progressive_any_workspace_bytes,
- *       odic_jpeg_decode_progressive_any, odic_jpeg4_decode_scaled, odic_jpeg3_any_decode_scaled,
- *       odic_jpeg_decode_progressive_any_scaled (the per-component records at 1/2, 1/4, 1/8 scale). */
-#define ODIC_ABI_VERSION 26
+ *       odic_lcs_pairs, odic_orient_rgb8, odic_cmyk_to_rgb8, odic_jpeg_progressive_any_workspace_bytes,
+ *       odic_jpeg_decode_progressive_any, odic_jpeg_decode_progressive_any_scaled.
+ *   27: the two baseline per-component records and their six entry points (four components; three at any layout) removed:
+ *       odic_jpeg_header_any with odic_jpeg_any_workspace_bytes, odic_jpeg_any_decode and odic_jpeg_any_decode_scaled
+ *       decodes both kinds, in one call. */
+#define ODIC_ABI_VERSION 27
 int odic_abi_version(void);
 
 /* Human-readable build string ("gfx950 hipcc ..."), static storage. */
@@ -364,99 +365,73 @@ int odic_jpeg_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_l
                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Four-component baseline files (CMYK and YCCK: print workflows, Photoshop), bit-exact with
- * np.asarray(PIL.Image.open(f).convert("RGB")).  jpeg.parse(..., "convert", cmyk="device") admits 8-bit SOF0/SOF1 Huffman
- * frames with one interleaved scan of the four components in frame order, component 0 at 1x1, 2x1 or 2x2, each of
- * components 1..3 at 1x1 or at component 0's sampling, and at most 10 blocks per MCU (libjpeg's limit).  The record has
- * odic_jpeg_header's offset and size fields with the same meaning (mcus_x = ceil(W / (8 h[0])), mcus_y =
- * ceil(H / (8 v[0])); restart in MCUs), and instead of `sampling`:
- *   h / v        sampling factors of each component.  An MCU holds h[c]·v[c] blocks of component c, row by row, in
- *                component order; the planes follow each other in component order from plane_off, plane c being
- *                mcus_x·8·h[c] wide and mcus_y·8·v[c] high (64 bytes per block in all)
- *   ycck         1: Adobe transform 2, components 0..2 are YCbCr of the complemented C, M, Y (libjpeg's
- *                ycck_cmyk_convert); 0: the components are C, M, Y, K as stored (transform 0 or no Adobe marker)
+ * Baseline files with per-component sampling, bit-exact with np.asarray(PIL.Image.open(f).convert("RGB")): four
+ * components (CMYK and YCCK: print workflows, Photoshop; jpeg.parse(..., "convert", cmyk="device")) and three components
+ * at every sampling layout libjpeg decodes that odic_jpeg_header cannot describe, stored as YCbCr or as RGB
+ * (jpeg.parse(..., layouts="all")).  Both are 8-bit SOF0/SOF1 Huffman frames with one interleaved scan of all components
+ * in frame order; one batch may mix them.  The record has odic_jpeg_header's offset and size fields with the same
+ * meaning (mcus_x = ceil(W / (8 max h)), mcus_y = ceil(H / (8 max v)); restart in MCUs), and instead of `sampling`:
+ *   color        three components: 1 the components are R, G, B as stored (Adobe transform 0, or ids 'R', 'G', 'B' with
+ *                neither a JFIF nor an Adobe marker), 0 Y, Cb, Cr (libjpeg's ycc_rgb_convert); four components: 1 Adobe
+ *                transform 2, components 0..2 are YCbCr of the complemented C, M, Y (libjpeg's ycck_cmyk_convert), 0 the
+ *                components are C, M, Y, K as stored.  odic_jpeg_prog_header_any's `color`
+ *   h / v        sampling factors of each component (entries from ncomp on are not read).  An MCU holds h[c]·v[c] blocks
+ *                of component c, row by row, in component order; the planes follow each other in component order from
+ *                plane_off, plane c being mcus_x·8·h[c] wide and mcus_y·8·v[c] high (64 bytes per block in all)
+ *   ncomp        3 or 4
  *   qt           quantisation table of each component, natural order
- *   lut/maxcode/valoff/huffval  tables 0-3: DC of components 0-3, 4-7: their AC, in odic_jpeg_header's form
- * Every sub-sampled component, K included, is upsampled with libjpeg's fancy h2v1 / h2v2 filters; every sample is then
- * complemented (Pillow reads all four-layer JPEGs as "CMYK;I") and the pixel goes through Pillow's CMYK → RGB.
+ *   lut/maxcode/valoff/huffval  tables 0-3: DC of components 0-3, 4-7: their AC, in odic_jpeg_header's form; the slots
+ *                of a component the frame lacks stay zero
+ * Frame rules, checked on the device, those of odic_jpeg_prog_header_any: ncomp 3 or 4; factors in 1..4, every factor a
+ * divisor of the largest in its direction, at most 10 blocks per MCU (libjpeg's limit); four components: component 0 at
+ * 1x1, 2x1 or 2x2 and every other one at 1x1 or at component 0's sampling.  A record that breaks them is not decoded:
+ * its status is 1 and none of its pixels are written.
+ * Every component, component 0 and K included, is brought to the output grid by libjpeg's rule for its ratios (rh, rv) =
+ * (max h / h[c], max v / v[c]): (1,1) as it is; (2,1) / (2,2) the fancy triangle filters, or replication where the
+ * component is at most two samples wide; (1,2) h1v2_fancy_upsample at every width; any other ratio replication.  Three
+ * components are then converted or copied by `color`; of four, every sample is complemented (Pillow reads all four-layer
+ * JPEGs as "CMYK;I") after the YCCK step and the pixel goes through Pillow's CMYK → RGB.
  * ------------------------------------------------------------------------------------------- */
-typedef struct odic_jpeg_header4 {
+typedef struct odic_jpeg_header_any {
   int64_t data_off, data_end, out_off, scan_off, coef_off, plane_off;
   int32_t int_off, unit_off, width, height;
-  int32_t ycck;
+  int32_t color;
   int32_t mcus_x, mcus_y, restart, n_intervals, n_units;
   int32_t h[4], v[4];
+  int32_t ncomp, pad;
   uint16_t qt[4][64];
   uint16_t lut[8][512];
   int32_t maxcode[8][18];
   int32_t valoff[8][18];
   uint8_t huffval[8][256];
-} odic_jpeg_header4;                /* 12024 bytes */
+} odic_jpeg_header_any;             /* 12032 bytes */
 
-/* odic_jpeg_workspace_bytes / odic_jpeg_decode for a batch whose `headers` are odic_jpeg_header4 [n_images]: the same
+/* odic_jpeg_workspace_bytes / odic_jpeg_decode for a batch whose `headers` are odic_jpeg_header_any [n_images]: the same
  * descriptor, launches, workspace layout, status rule and contract (all launches on `stream`, no allocation, no host
  * synchronisation; at most the queried workspace bytes are touched, and exactly the images' H·W·3 bytes of `out` and
- * n_images entries of `status` are written — test_jpeg4_decode_stays_inside_its_workspace).  An out_off that is a
+ * n_images entries of `status` are written — test_jpeg_any_decode_stays_inside_its_buffers).  An out_off that is a
  * multiple of 4 lets the colour kernel store whole words. */
-size_t odic_jpeg4_workspace_bytes(const odic_jpeg_batch* batch);
-int odic_jpeg4_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
+size_t odic_jpeg_any_workspace_bytes(const odic_jpeg_batch* batch);
+int odic_jpeg_any_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
-/* odic_jpeg_decode_scaled for odic_jpeg_header4 records: scale_log2 (DEVICE int32 [n_images], each 0..3), out_off,
+/* odic_jpeg_decode_scaled for odic_jpeg_header_any records: scale_log2 (DEVICE int32 [n_images], each 0..3), out_off,
  * max_width / max_height and the output sizes as there; ODIC_ENULL for a null scale_log2; a value outside 0..3 leaves the
  * image undecoded with status 1 and nothing of it written.  Every component takes libjpeg's own transform size n at the
  * scale (jdmaster.c; jpeg.scaled_components): it starts at 8 / s and doubles while it is below 8 and 2 n·h[c] still
  * divides (8 / s)·max h, and the same down.  Plane c is mcus_x·n·h[c] wide and mcus_y·n·v[c] high; the planes follow each
  * other from plane_off, each rounded up to a multiple of 16 bytes (at full size that is the layout above).  The
- * upsampling that remains, by ((8 / s)·max h) / (n·h[c]) across and the same down, is odic_jpeg3_any_decode's, with the
+ * upsampling that remains, by ((8 / s)·max h) / (n·h[c]) across and the same down, follows the rule above, with the
  * triangle filters only while 8 / s > 1 (at 1/8 every ratio is replication).  Workspace query, status rule and
- * containment are odic_jpeg4_decode's (test_scaled_decodes_stay_inside_their_buffers). */
-int odic_jpeg4_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace, size_t ws_bytes,
-                             void* stream);
+ * containment are odic_jpeg_any_decode's (test_scaled_decodes_stay_inside_their_buffers). */
+int odic_jpeg_any_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace, size_t ws_bytes,
+                                void* stream);
 
-/* The last stage of that decode on its own: n_pixels interleaved C, M, Y, K bytes (DEVICE pointers) → interleaved RGB,
- * as Pillow's convert("RGB") of a CMYK image: per channel x with nk = 255 - K, t = x·nk + 128,
+/* The last stage of the four-component decode on its own: n_pixels interleaved C, M, Y, K bytes (DEVICE pointers) →
+ * interleaved RGB, as Pillow's convert("RGB") of a CMYK image: per channel x with nk = 255 - K, t = x·nk + 128,
  * out = clip(nk - (((t >> 8) + t) >> 8), 0, 255).  invert != 0: every input sample is first replaced by 255 - x (the
  * "CMYK;I" unpacking of a JPEG).  n_pixels == 0 launches nothing.  ODIC_ENULL for a null pointer, ODIC_EINVAL for a
  * negative n_pixels. */
 int odic_cmyk_to_rgb8(const uint8_t* cmyk, uint8_t* rgb, int64_t n_pixels, int invert, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * Three-component baseline files at every other sampling layout libjpeg decodes, and RGB-stored ones, bit-exact with
- * np.asarray(PIL.Image.open(f).convert("RGB")).  jpeg.parse(..., layouts="all") admits 8-bit SOF0/SOF1 Huffman frames
- * with one interleaved scan of the three components in frame order that odic_jpeg_header cannot describe: sampling
- * factors in 1..4, every factor a divisor of the largest in its direction, at most 10 blocks per MCU.  The record has
- * odic_jpeg_header4's fields with the same meaning, for three components, except that the MCU spans the LARGEST
- * factors (mcus_x = ceil(W / (8 max h)), mcus_y = ceil(H / (8 max v))), and instead of `ycck`:
- *   rgb          1: the components are R, G, B as stored (Adobe transform 0, or ids 'R', 'G', 'B' with neither a JFIF
- *                nor an Adobe marker); 0: Y, Cb, Cr (libjpeg's ycc_rgb_convert)
- *   lut/maxcode/valoff/huffval  tables 0-2: DC of components 0-2, 3-5: their AC
- * Every component, component 0 included, is brought to the output grid by libjpeg's rule for its ratios (rh, rv) =
- * (max h / h[c], max v / v[c]): (1,1) as it is; (2,1) / (2,2) the fancy triangle filters, or replication where the
- * component is at most two samples wide; (1,2) h1v2_fancy_upsample at every width; any other ratio replication.
- * A record that breaks the rules above is not decoded: its status is 1 and none of its pixels are written.
- * ------------------------------------------------------------------------------------------- */
-typedef struct odic_jpeg_header3 {
-  int64_t data_off, data_end, out_off, scan_off, coef_off, plane_off;
-  int32_t int_off, unit_off, width, height;
-  int32_t rgb;
-  int32_t mcus_x, mcus_y, restart, n_intervals, n_units;
-  int32_t h[3], v[3];
-  uint16_t qt[3][64];
-  uint16_t lut[6][512];
-  int32_t maxcode[6][18];
-  int32_t valoff[6][18];
-  uint8_t huffval[6][256];
-} odic_jpeg_header3;                /* 9040 bytes */
-
-/* odic_jpeg_workspace_bytes / odic_jpeg_decode for a batch whose `headers` are odic_jpeg_header3 [n_images]: the same
- * descriptor, launches, workspace layout, status rule and contract as odic_jpeg4_decode
- * (test_layout_decode_stays_inside_its_workspace). */
-size_t odic_jpeg3_any_workspace_bytes(const odic_jpeg_batch* batch);
-int odic_jpeg3_any_decode(const odic_jpeg_batch* batch, void* workspace, size_t ws_bytes, void* stream);
-
-/* odic_jpeg4_decode_scaled for odic_jpeg_header3 records: the same scale_log2, transform sizes, planes and contract. */
-int odic_jpeg3_any_decode_scaled(const odic_jpeg_batch* batch, const int32_t* scale_log2, void* workspace,
-                                 size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Progressive files (8-bit SOF2 Huffman, 3 YCbCr components, the samplings above — sampling 3 included: one component,
@@ -535,14 +510,14 @@ int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* batch, const
 
 /* ---------------------------------------------------------------------------------------------
  * Progressive files with per-component sampling: four components (CMYK / YCCK) and three components at the layouts of
- * odic_jpeg_header3, YCbCr or RGB, bit-exact with np.asarray(PIL.Image.open(f).convert("RGB")).
+ * odic_jpeg_header_any, YCbCr or RGB, bit-exact with np.asarray(PIL.Image.open(f).convert("RGB")).
  * jpeg.parse_progressive(..., cmyk="device") / (..., layouts="all") admits them.  The record starts with
  * odic_jpeg_prog_header's fields (`color` in the place of `sampling`) and goes on with the frame:
- *   color        three components: 1 the components are R, G, B as stored, 0 Y, Cb, Cr (odic_jpeg_header3's `rgb`);
- *                four components: 1 YCCK, 0 CMYK as stored (odic_jpeg_header4's `ycck`)
+ *   color        three components: 1 the components are R, G, B as stored, 0 Y, Cb, Cr;
+ *                four components: 1 YCCK, 0 CMYK as stored (odic_jpeg_header_any's `color`)
  *   ncomp        3 or 4
  *   h / v        sampling factors of each component (entries from ncomp on are not read).  mcus_x = ceil(W / (8 max h)),
- *                mcus_y = ceil(H / (8 max v)); coefficient blocks MCU by MCU and planes as odic_jpeg_header4 has them
+ *                mcus_y = ceil(H / (8 max v)); coefficient blocks MCU by MCU and planes as odic_jpeg_header_any has them
  *   qt           quantisation table of each component, natural order
  * Frame rules, checked on the device: ncomp 3 or 4; factors in 1..4, every factor a divisor of the largest in its
  * direction, at most 10 blocks per MCU; four components: component 0 at 1x1, 2x1 or 2x2 and every other one at 1x1 or at
@@ -551,8 +526,8 @@ int odic_jpeg_decode_progressive_scaled(const odic_jpeg_prog_batch* batch, const
  * frame's MCUs (largest factors) whichever components it names, a single-component scan the component's own raster.
  * A record that breaks the frame rules, or a scan of it whose mask names a component the frame lacks, is not decoded.
  * An image with status 1 — by these rules or by those of odic_jpeg_decode_progressive — has none of its pixels written.
- * Upsampling and colour are odic_jpeg3_any_decode's (three components) and odic_jpeg4_decode's (four); at a reduced
- * scale (odic_jpeg_decode_progressive_any_scaled) those of their _scaled forms.
+ * Upsampling and colour are odic_jpeg_any_decode's; at a reduced scale (odic_jpeg_decode_progressive_any_scaled)
+ * those of odic_jpeg_any_decode_scaled.
  * ------------------------------------------------------------------------------------------- */
 typedef struct odic_jpeg_prog_header_any {
   int64_t out_off, coef_off, plane_off;
@@ -570,7 +545,7 @@ typedef struct odic_jpeg_prog_header_any {
 size_t odic_jpeg_progressive_any_workspace_bytes(const odic_jpeg_prog_batch* batch);
 int odic_jpeg_decode_progressive_any(const odic_jpeg_prog_batch* batch, void* workspace, size_t ws_bytes, void* stream);
 
-/* odic_jpeg4_decode_scaled / odic_jpeg3_any_decode_scaled for odic_jpeg_prog_header_any records: the scans decode as at
+/* odic_jpeg_any_decode_scaled for odic_jpeg_prog_header_any records: the scans decode as at
  * full size, the inverse transforms, planes, upsampling and output follow scale_log2 as there. */
 int odic_jpeg_decode_progressive_any_scaled(const odic_jpeg_prog_batch* batch, const int32_t* scale_log2,
                                             void* workspace, size_t ws_bytes, void* stream);

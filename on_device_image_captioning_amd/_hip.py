@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libodic_hip.so")
 
 F32, BF16, FP8, F16, H2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _ERR = {-1: "ODIC_EINVAL (bad shape / alignment / enum)", -2: "ODIC_ENULL (required pointer is NULL)",
         -3: "ODIC_EUNSUPPORTED"}
@@ -161,15 +161,12 @@ _SIGNATURES = {
     "odic_jpeg_decode_progressive": (C.c_int, [C.POINTER(JpegProgBatch), _P, C.c_size_t, _P]),
     "odic_jpeg_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
     "odic_jpeg_decode_progressive_scaled": (C.c_int, [C.POINTER(JpegProgBatch), _P, _P, C.c_size_t, _P]),
-    "odic_jpeg4_workspace_bytes": (C.c_size_t, [C.POINTER(JpegBatch)]),
-    "odic_jpeg4_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
+    "odic_jpeg_any_workspace_bytes": (C.c_size_t, [C.POINTER(JpegBatch)]),
+    "odic_jpeg_any_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
+    "odic_jpeg_any_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
     "odic_cmyk_to_rgb8": (C.c_int, [_P, _P, _I64, _I32, _P]),
-    "odic_jpeg3_any_workspace_bytes": (C.c_size_t, [C.POINTER(JpegBatch)]),
-    "odic_jpeg3_any_decode": (C.c_int, [C.POINTER(JpegBatch), _P, C.c_size_t, _P]),
     "odic_jpeg_progressive_any_workspace_bytes": (C.c_size_t, [C.POINTER(JpegProgBatch)]),
     "odic_jpeg_decode_progressive_any": (C.c_int, [C.POINTER(JpegProgBatch), _P, C.c_size_t, _P]),
-    "odic_jpeg4_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
-    "odic_jpeg3_any_decode_scaled": (C.c_int, [C.POINTER(JpegBatch), _P, _P, C.c_size_t, _P]),
     "odic_jpeg_decode_progressive_any_scaled": (C.c_int, [C.POINTER(JpegProgBatch), _P, _P, C.c_size_t, _P]),
     "odic_cider_vectorize": (C.c_int, [_P, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, C.c_double, _P, _I64, _P]),
     "odic_cider_pairs": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _I32, _P, _I64, _P]),

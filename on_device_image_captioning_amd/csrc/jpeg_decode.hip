@@ -37,26 +37,23 @@
 // One-component (grayscale) frames, sampling = 3, take the same launches in the same batch: one block per MCU in
 // block-raster order, tables 0 / 3, one plane, and a colour pass that writes R = G = B = Y (Pillow's L → RGB).
 //
-// Four-component frames (CMYK / YCCK, odic_jpeg4_decode) have a record of their own, odic_jpeg_header4: every
-// component with its own sampling, four quantisation and eight Huffman tables.  The launches up to the coefficients are
-// the same kernels, templates over the header type (Frame<Header>: blocks per MCU and the component of each block); the
-// IDCT writes four planes and jpeg_color4_kernel upsamples each, then applies YCCK → CMYK, Pillow's inversion and
-// Pillow's CMYK → RGB: np.asarray(PIL.Image.open(f).convert("RGB")).
+// All of the above is the COMMON record family: odic_jpeg_header (baseline) and odic_jpeg_prog_header (progressive),
+// whose frame is one `sampling` word.  Every kernel is a template over the header type, and the second family goes
+// through the same launches:
 //
-// Three-component frames at any other sampling layout libjpeg decodes (4:4:0, 4:1:1, 4:1:0, chroma sub-sampled one way
-// under a 2x2 luma, a component 0 that is not the largest), stored as YCbCr or as RGB (odic_jpeg3_any_decode), have the
-// record odic_jpeg_header3: per-component sampling and a colour flag, three quantisation and six Huffman tables.  The
-// same templates again up to the IDCT, which writes three planes; jpeg_color3_kernel reads every component through
-// upsampled_by() — copy, h2v1 / h2v2 / h1v2 fancy, or replication by an integral ratio — and converts or copies.
-//
-// Progressive files of those two kinds (odic_jpeg_decode_progressive_any) have the record odic_jpeg_prog_header_any:
-// the progressive decode kernel and its coding procedures instantiated for per-component block geometry (ProgGeo), then
-// the same per-component IDCT and the two colour kernels above.
-//
-// These three records decode at 1 / 2, 1 / 4, 1 / 8 as well (odic_jpeg4_decode_scaled, odic_jpeg3_any_decode_scaled,
-// odic_jpeg_decode_progressive_any_scaled): every component at libjpeg's own transform size for the scale
-// (scaled_size_own), planes at those sizes (plane_bytes_own), and the upsampling that remains through upsampled_by(),
-// with the triangle filters while the smallest transform is above 1x1.
+// The PER-COMPONENT family — odic_jpeg_header_any (odic_jpeg_any_decode) and odic_jpeg_prog_header_any
+// (odic_jpeg_decode_progressive_any) — carries ncomp = 3 or 4, the sampling of every component in h[] / v[], a `color`
+// flag, four quantisation tables and, in the baseline record, eight Huffman tables.  It holds four-component frames (CMYK,
+// or YCCK with color = 1) and three-component frames at any other sampling layout libjpeg decodes (4:4:0, 4:1:1, 4:1:0,
+// chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest), stored as YCbCr or, with
+// color = 1, as RGB; one batch may mix the counts.  One rule set admits a frame (layout_ok); Frame<Header> gives the
+// entropy kernels the blocks per MCU and the component of each, ProgGeo the same to the progressive coding procedures;
+// the IDCT writes ncomp planes (block_geo_own), and one colour kernel (color_own_pixels) reads every component through
+// upsampled_by() — copy, h2v1 / h2v2 / h1v2 fancy, or replication by an integral ratio — and then converts: YCbCr → RGB
+// or a copy for three components; YCCK → CMYK, Pillow's inversion and Pillow's CMYK → RGB for four:
+// np.asarray(PIL.Image.open(f).convert("RGB")).  The _scaled entry points of this family take every component at
+// libjpeg's own transform size for the scale (scaled_size_own), planes at those sizes (plane_bytes_own), and the
+// upsampling that remains, with the triangle filters while the smallest transform is above 1x1.
 //
 // An image whose entropy data does not decode (invalid code, unexpected marker, RST out of sequence, too few
 // or too many intervals, an interval whose MCUs need bits past its end, a run past coefficient 63, no EOI), or
@@ -69,12 +66,10 @@
 static_assert(sizeof(odic_jpeg_header) == 9016 && offsetof(odic_jpeg_header, qt) == 88 &&
                   offsetof(odic_jpeg_header, huffval) == 7480,
               "odic_jpeg_header layout is mirrored by jpeg.HEADER_DTYPE");
-static_assert(sizeof(odic_jpeg_header4) == 12024 && offsetof(odic_jpeg_header4, h) == 88 &&
-                  offsetof(odic_jpeg_header4, qt) == 120 && offsetof(odic_jpeg_header4, huffval) == 9976,
-              "odic_jpeg_header4 layout is mirrored by jpeg.HEADER4_DTYPE");
-static_assert(sizeof(odic_jpeg_header3) == 9040 && offsetof(odic_jpeg_header3, h) == 88 &&
-                  offsetof(odic_jpeg_header3, qt) == 112 && offsetof(odic_jpeg_header3, huffval) == 7504,
-              "odic_jpeg_header3 layout is mirrored by jpeg.HEADER3_DTYPE");
+static_assert(sizeof(odic_jpeg_header_any) == 12032 && offsetof(odic_jpeg_header_any, h) == 88 &&
+                  offsetof(odic_jpeg_header_any, ncomp) == 120 && offsetof(odic_jpeg_header_any, qt) == 128 &&
+                  offsetof(odic_jpeg_header_any, huffval) == 9984,
+              "odic_jpeg_header_any layout is mirrored by jpeg.HEADER_ANY_DTYPE");
 
 namespace {
 
@@ -185,10 +180,60 @@ __device__ __forceinline__ int luma_h(int sampling) { return sampling == 0 || sa
 __device__ __forceinline__ int luma_v(int sampling) { return sampling == 2 ? 2 : 1; }
 
 // What the entropy kernels need of a frame: the blocks of an MCU and the component of each, which is also its Huffman
-// table pair (DC table c, AC table kComps + c) and its DC predictor.  Three-component and gray frames derive both from
-// `sampling`; a four-component frame (odic_jpeg_header4) carries the sampling of every component, and the map from a
-// block of the MCU to its component is packed from the record, two bits per block (at most 10 blocks).
-constexpr int kMaxMcuBlocks4 = 10;                 // libjpeg's D_MAX_BLOCKS_IN_MCU
+// table pair (DC table c, AC table kComps + c) and its DC predictor.  A common record derives both from `sampling`; a
+// per-component one carries the sampling of every component, and the map from a block of the MCU to its component is
+// packed from the record, two bits per block (at most 10 blocks).
+constexpr int kMaxMcuBlocks = 10;                  // libjpeg's D_MAX_BLOCKS_IN_MCU
+
+// The two record families: per-component records have ncomp, h[] and v[]; common ones have `sampling`.
+template <typename Header, typename = void>
+constexpr bool kPerComponent = false;
+template <typename Header>
+constexpr bool kPerComponent<Header, std::void_t<decltype(Header::ncomp)>> = true;
+// When the colour pass writes an image's pixels.  A baseline record's are written whenever its frame rules hold (an
+// image whose entropy data failed gets status 1 beside whatever its coefficients gave, as in the common family); a
+// progressive per-component record's only when the whole decode succeeded — its state words are final by then, every
+// kernel that sets them lies ahead of the colour kernel on the stream.
+template <typename Header>
+constexpr bool kPixelsOnlyWhenDecoded = std::is_same<Header, odic_jpeg_prog_header_any>::value;
+
+// The frame rules of the per-component family, libjpeg's and the host parser's: three or four components; factors in
+// 1..4, every factor a divisor of the largest in its direction, at most 10 blocks per MCU; four components: component 0
+// at 1x1, 2x1 or 2x2 and every other one at 1x1 or at component 0's sampling, which the colour pass's plane addressing
+// relies on.  A record that breaks them is a frame of one block of component 0 to the entropy kernels, which stay inside
+// whatever the record's offsets span; the IDCT and the colour pass write nothing for it and the image gets status 1.
+template <typename Header>
+__device__ __forceinline__ bool layout_ok(const Header& h) {
+  if (h.ncomp != 3 && h.ncomp != 4) return false;
+  int hm = 1, vm = 1, n = 0;
+  for (int c = 0; c < h.ncomp; ++c) {
+    if ((unsigned)(h.h[c] - 1) > 3u || (unsigned)(h.v[c] - 1) > 3u) return false;
+    hm = max(hm, h.h[c]);
+    vm = max(vm, h.v[c]);
+    n += h.h[c] * h.v[c];
+  }
+  if (n > kMaxMcuBlocks) return false;
+  for (int c = 0; c < h.ncomp; ++c)
+    if (hm % h.h[c] || vm % h.v[c]) return false;
+  if (h.ncomp == 4) {
+    if (h.h[0] > 2 || h.v[0] > h.h[0]) return false;
+    for (int c = 1; c < 4; ++c)
+      if ((h.h[c] != 1 || h.v[c] != 1) && (h.h[c] != h.h[0] || h.v[c] != h.v[0])) return false;
+  }
+  return true;
+}
+// blocks of an MCU; of a per-component record that layout_ok() admits
+template <typename Header>
+__device__ __forceinline__ int mcu_blocks(const Header& h) {
+  if constexpr (kPerComponent<Header>) {
+    int n = 0;
+    for (int c = 0; c < h.ncomp; ++c) n += h.h[c] * h.v[c];
+    return n;
+  } else {
+    return blocks_per_mcu(h.sampling);
+  }
+}
+
 template <typename Header>
 struct Frame;
 template <>
@@ -200,74 +245,20 @@ struct Frame<odic_jpeg_header> {
   __device__ __forceinline__ int comp(int blk) const { return blk < nY ? 0 : blk - nY + 1; }
 };
 template <>
-struct Frame<odic_jpeg_header4> {
-  static constexpr int kComps = 4;
+struct Frame<odic_jpeg_header_any> {
+  static constexpr int kComps = 4;                   // table and predictor slots; a three-component file uses three
   unsigned map;
   int bpm;
-  __device__ explicit Frame(const odic_jpeg_header4& h) : map(0), bpm(0) {
-    for (int c = 0; c < 4; ++c) {                    // the parser admits h, v in 1..2 and at most 10 blocks; the clamps
-      const int n = min(max(h.h[c] * h.v[c], 1), 4);  // only keep a record that breaks the rule inside the map
-      for (int j = 0; j < n && bpm < kMaxMcuBlocks4; ++j) map |= (unsigned)c << (2 * bpm++);
-    }
-  }
-  __device__ __forceinline__ int comp(int blk) const { return (map >> (2 * blk)) & 3; }
-};
-// Three components, each with its own sampling (odic_jpeg_header3).  layout_ok() is libjpeg's rule set, which the host
-// parser applies before it packs a record: factors in 1..4, at most 10 blocks, every factor a divisor of the largest.
-// A record that breaks it is a frame of one block of component 0 to the entropy kernels, which stay inside whatever
-// the record's offsets span; the IDCT and the colour pass write nothing for it and the image gets status 1.
-__device__ __forceinline__ bool factors_ok(const int* h, const int* v, int ncomp) {
-  int hm = 1, vm = 1, n = 0;
-  for (int c = 0; c < ncomp; ++c) {
-    if ((unsigned)(h[c] - 1) > 3u || (unsigned)(v[c] - 1) > 3u) return false;
-    hm = max(hm, h[c]);
-    vm = max(vm, v[c]);
-    n += h[c] * v[c];
-  }
-  if (n > kMaxMcuBlocks4) return false;
-  for (int c = 0; c < ncomp; ++c)
-    if (hm % h[c] || vm % v[c]) return false;
-  return true;
-}
-__device__ __forceinline__ bool layout_ok(const odic_jpeg_header3& h) { return factors_ok(h.h, h.v, 3); }
-__device__ __forceinline__ bool layout_ok(const odic_jpeg_header4&) { return true; }   // the parser's rules, not checked here
-// The progressive record with per-component sampling: three components under the rules above, or four under those the
-// parser applies to odic_jpeg_header4, which jpeg_color4_kernel's plane addressing relies on: component 0 at 1x1, 2x1
-// or 2x2, every other component at 1x1 or at component 0's sampling.
-__device__ __forceinline__ bool layout_ok(const odic_jpeg_prog_header_any& h) {
-  if (h.ncomp != 3 && h.ncomp != 4) return false;
-  if (!factors_ok(h.h, h.v, h.ncomp)) return false;
-  if (h.ncomp == 4) {
-    if (h.h[0] > 2 || h.v[0] > h.h[0]) return false;
-    for (int c = 1; c < 4; ++c)
-      if ((h.h[c] != 1 || h.v[c] != 1) && (h.h[c] != h.h[0] || h.v[c] != h.v[0])) return false;
-  }
-  return true;
-}
-template <>
-struct Frame<odic_jpeg_header3> {
-  static constexpr int kComps = 3;
-  unsigned map;
-  int bpm;
-  __device__ explicit Frame(const odic_jpeg_header3& h) : map(0), bpm(0) {
+  __device__ explicit Frame(const odic_jpeg_header_any& h) : map(0), bpm(0) {
     if (!layout_ok(h)) {
       bpm = 1;
       return;
     }
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < h.ncomp; ++c)
       for (int j = 0; j < h.h[c] * h.v[c]; ++j) map |= (unsigned)c << (2 * bpm++);
   }
   __device__ __forceinline__ int comp(int blk) const { return (map >> (2 * blk)) & 3; }
 };
-__device__ __forceinline__ int mcu_blocks(const odic_jpeg_header4& h) { return Frame<odic_jpeg_header4>(h).bpm; }
-__device__ __forceinline__ int mcu_blocks(const odic_jpeg_header3& h) { return Frame<odic_jpeg_header3>(h).bpm; }
-__device__ __forceinline__ int mcu_blocks(const odic_jpeg_prog_header_any& h) {   // of a record layout_ok() admits
-  int n = 0;
-  for (int c = 0; c < h.ncomp; ++c) n += h.h[c] * h.v[c];
-  return n;
-}
-template <typename Header>
-__device__ __forceinline__ int mcu_blocks(const Header& h) { return blocks_per_mcu(h.sampling); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // segment: one workgroup of 256 lanes per image, 16 bytes per lane per 4 KiB tile
@@ -369,7 +360,7 @@ __device__ int segment_bytes(const unsigned char* __restrict__ src, const long l
   return err;
 }
 
-template <typename Header>                                      // odic_jpeg_header or odic_jpeg_header4
+template <typename Header>                                      // odic_jpeg_header or odic_jpeg_header_any
 __global__ __launch_bounds__(256) void jpeg_segment_kernel(const Header* __restrict__ hdrs,
                                                            const unsigned char* __restrict__ data, Ws ws,
                                                            int subseq_bits) {
@@ -405,7 +396,7 @@ __global__ __launch_bounds__(256) void jpeg_segment_kernel(const Header* __restr
 // ---------------------------------------------------------------------------------------------------------------
 // Huffman decoding, shared by the speculative, sync, write-out and serial kernels
 // ---------------------------------------------------------------------------------------------------------------
-template <int kTables>             // 6 (three components: DC 0..2, AC 3..5) or 8 (four: DC 0..3, AC 4..7)
+template <int kTables>             // 6 (common records: DC 0..2, AC 3..5) or 8 (per-component ones: DC 0..3, AC 4..7)
 struct Tabs {
   unsigned short lut[kTables * 512];
   int lim[kTables * 8];            // [l - 9]: one past the last code of length <= l, left-justified to 16 bits
@@ -428,15 +419,24 @@ __device__ __forceinline__ void fill_lim(const int* maxcode, int* lim, int tab) 
   }
 }
 
+// The tables of the frame's components: all of a common record's; of a per-component record the pairs of components
+// below ncomp, so a three-component file does not pay for the fourth pair.  The slots left out are never indexed:
+// Frame::comp() is below ncomp for a frame layout_ok() admits and 0 for one it refuses.
 template <typename Header, int kTables>
 __device__ void load_tabs(const Header& h, Tabs<kTables>& T) {
+  constexpr int kC = kTables / 2;
   const int t = threadIdx.x;
-  for (int i = t; i < kTables * 512; i += blockDim.x) T.lut[i] = (&h.lut[0][0])[i];
+  constexpr bool kAll = !kPerComponent<Header>;
+  int nc = kC;
+  if constexpr (!kAll) nc = min(max(h.ncomp, 1), kC);
+  for (int i = t; i < kTables * 512; i += blockDim.x)
+    if (kAll || (i >> 9) % kC < nc) T.lut[i] = (&h.lut[0][0])[i];
   for (int i = t; i < kTables * 18; i += blockDim.x) {
     T.maxcode[i] = (&h.maxcode[0][0])[i];
     T.valoff[i] = (&h.valoff[0][0])[i];
   }
-  for (int i = t; i < kTables * 256; i += blockDim.x) T.huffval[i] = (&h.huffval[0][0])[i];
+  for (int i = t; i < kTables * 256; i += blockDim.x)
+    if (kAll || (i >> 8) % kC < nc) T.huffval[i] = (&h.huffval[0][0])[i];
   for (int i = t; i < 64; i += blockDim.x) T.natural[i] = kNatural[i];
   if (t < kTables) fill_lim(&h.maxcode[0][0], T.lim, t);
   __syncthreads();
@@ -910,7 +910,7 @@ struct BlockGeo {
   int comp, n, hc, vc, jx, jy;
   long plane;
 };
-// every component with its own sampling (odic_jpeg_header4: kC = 4, odic_jpeg_header3: kC = 3): the planes follow
+// every component with its own sampling (the per-component records, kC = ncomp): the planes follow
 // each other in component order, plane c at the component's transform size n (8 at full size), each rounded up to a
 // multiple of 16 bytes, which a plane of 8x8 blocks is anyway and which keeps the n-aligned row stores of the IDCT
 // aligned behind a plane of 1x1 or 2x2 blocks
@@ -944,15 +944,11 @@ __device__ __forceinline__ BlockGeo block_geo_own(const Header& h, int j, int lg
   }
   return g;
 }
-// Block j of an MCU of any record at scale 1 / 2^lg (kScaled = false: lg = 0).  Three components or gray at the common
-// samplings: component 0 at the luma sampling with transform size ny, the others 1x1 with size nc.
+// Block j of an MCU of any record at scale 1 / 2^lg (kScaled = false: lg = 0).  A common record: component 0 at the
+// luma sampling with transform size ny, the others 1x1 with size nc.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ BlockGeo block_geo(const Header& h, int j, int lg) {
-  if constexpr (std::is_same<Header, odic_jpeg_header4>::value) {
-    return block_geo_own<4>(h, j, kScaled ? lg : 0);
-  } else if constexpr (std::is_same<Header, odic_jpeg_header3>::value) {
-    return block_geo_own<3>(h, j, kScaled ? lg : 0);
-  } else if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) {
+  if constexpr (kPerComponent<Header>) {
     return h.ncomp == 4 ? block_geo_own<4>(h, j, kScaled ? lg : 0) : block_geo_own<3>(h, j, kScaled ? lg : 0);
   } else {
     int ny = 8, nc = 8;
@@ -969,11 +965,6 @@ __device__ __forceinline__ BlockGeo block_geo(const Header& h, int j, int lg) {
     return g;
   }
 }
-// the records whose frame rules are checked on the device (layout_ok): an image that breaks them is not decoded
-template <typename Header>
-constexpr bool kHasFrameRules =
-    std::is_same<Header, odic_jpeg_header3>::value || std::is_same<Header, odic_jpeg_prog_header_any>::value;
-
 // One block per 8 lanes: column pass → LDS → row pass, n×n samples into the component's plane.  kScaled = false is
 // the full-size decode (lg = 0, n = 8 throughout, the branches below fold away).  A scaled image's planes keep the
 // full-size order (Y, Cb, Cr from plane_off) with every block n wide and high.  The range rule of kIdctLimit holds for
@@ -981,7 +972,7 @@ constexpr bool kHasFrameRules =
 // only the input and the result).  libjpeg-turbo's SIMD 4x4 / 2x2 keep the same 16-bit intermediates as its 8x8.
 template <bool kScaled, typename Header>
 __device__ __forceinline__ void idct_blocks(const Header& h, const Ws& ws, int img, int lg, int (*ws8)[8][9]) {
-  if constexpr (kHasFrameRules<Header>) {
+  if constexpr (kPerComponent<Header>) {
     if (!layout_ok(h)) return;                                // the whole workgroup: one image per blockIdx.y
   }
   const int bpm = mcu_blocks(h);                              // gray: every block is component 0
@@ -1185,7 +1176,8 @@ __global__ __launch_bounds__(256) void jpeg_color_scaled_kernel(const Header* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Four-component frames (odic_jpeg_header4): what Image.open(f).convert("RGB") makes of a CMYK / YCCK file.
+// The colour pass of the per-component records.  Four components: what Image.open(f).convert("RGB") makes of a CMYK /
+// YCCK file.
 //   jdcolor.c ycck_cmyk_convert (Adobe transform 2): C, M, Y = 255 - (R, G, B) of the table-driven YCbCr→RGB above,
 //       K as stored; other files hold C, M, Y, K as stored
 //   Pillow's unpacker "CMYK;I", which JpegImagePlugin picks for every four-layer file: each sample becomes 255 - x
@@ -1215,27 +1207,7 @@ __device__ __forceinline__ void store_rgb4(unsigned char* __restrict__ o, const 
   }
 }
 
-constexpr int kColor4Pixels = 4;                   // pixels per lane of the two kernels below
-
-// What the two per-component colour kernels read of their records.  odic_jpeg_prog_header_any serves both: an image
-// of four components is jpeg_color4_kernel's, every other one jpeg_color3_kernel's (where layout_ok() refuses a count
-// that is not 3), and its pixels are written only where the whole decode succeeded — the state words are final by then,
-// every kernel that sets them lies ahead of the colour kernels on the stream.
-__device__ __forceinline__ int colour_comps(const odic_jpeg_header4&) { return 4; }
-__device__ __forceinline__ int colour_comps(const odic_jpeg_header3&) { return 3; }
-__device__ __forceinline__ int colour_comps(const odic_jpeg_prog_header_any& h) { return h.ncomp == 4 ? 4 : 3; }
-__device__ __forceinline__ int colour_flag(const odic_jpeg_header4& h) { return h.ycck; }
-__device__ __forceinline__ int colour_flag(const odic_jpeg_header3& h) { return h.rgb; }
-__device__ __forceinline__ int colour_flag(const odic_jpeg_prog_header_any& h) { return h.color; }
-template <typename Header>
-__device__ __forceinline__ bool image_status_ok(const Header& h, const int* st) {
-  return layout_ok(h) && st[0] == 0 && st[1] == h.n_intervals;
-}
-template <typename Header>
-__device__ __forceinline__ bool pixels_wanted(const Header& h, const int* st) {
-  if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) return image_status_ok(h, st);
-  else return layout_ok(h);
-}
+constexpr int kColor4Pixels = 4;                   // pixels per lane of the kernels below
 
 __global__ __launch_bounds__(256) void cmyk_to_rgb8_kernel(const unsigned char* __restrict__ cmyk,
                                                            unsigned char* __restrict__ rgb, long n_pixels, int invert) {
@@ -1253,7 +1225,7 @@ __global__ __launch_bounds__(256) void cmyk_to_rgb8_kernel(const unsigned char* 
   store_rgb4(rgb + 3 * p0, px, n);
 }
 
-// One component as the two per-component colour kernels read it at scale 1 / 2^lg: its plane (pw samples a row) at
+// One component as the per-component colour pass reads it at scale 1 / 2^lg: its plane (pw samples a row) at
 // the transform size of scaled_size_own(), the integral ratios (rh, rv) of the output grid to it, and its real samples
 // dw x dh (jdmaster.c: the component's downsampled size, ceil(W·h·n / (8 hmax)) across).  At lg = 0 these are the
 // full-size planes, the ratios of the sampling factors and ceil(W·h / hmax).
@@ -1281,74 +1253,44 @@ __device__ __forceinline__ void comp_planes(const Header& h, const Ws& ws, int l
 }
 
 // Four consecutive pixels of the image's H·W per lane (of ceil(W / s) · ceil(H / s) at scale 1 / s = 1 / 2^lg; kScaled =
-// false is the full-size decode, lg = 0): every component is read at its own sampling through upsampled_by() (a
-// component at component 0's sampling lies on the output grid, a 1x1 one under 2x1 / 2x2 is upsampled as chroma is
-// above, K included; at a reduced scale by the ratios that libjpeg's transform sizes leave), then the chain of the
-// comment above; plus the per-image status.
-template <bool kScaled, typename Header>                        // odic_jpeg_header4 or odic_jpeg_prog_header_any
-__device__ __forceinline__ void color4_pixels(const Header& h, const Ws& ws, int img, int lg_in,
-                                              unsigned char* __restrict__ out, int* __restrict__ status) {
-  if (colour_comps(h) != 4) return;
+// false is the full-size decode, lg = 0): every one of the kC components is read at its own sampling through
+// upsampled_by() at its ratio to the largest sampling — component 0 too, where it is not the largest, and K like any
+// other; at a reduced scale by the ratios that libjpeg's transform sizes leave.  Then, three components: ycc_rgb_convert,
+// or the samples as they are for an RGB file (color = 1); four: the YCCK step (color = 1) and the chain of the comment
+// above.  Plus the per-image status.  A record that layout_ok() refuses has status 1 and no pixels.
+template <bool kScaled, int kC, typename Header>
+__device__ __forceinline__ void color_own_pixels(const Header& h, const Ws& ws, int img, int lg_in,
+                                                 unsigned char* __restrict__ out, int* __restrict__ status) {
   const int lg = kScaled ? lg_in : 0;
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
   const int* st = ws.state + kStateWords * img;
-  if (p0 == 0) status[img] = image_status_ok(h, st) ? 0 : 1;
+  const bool framed = layout_ok(h), decoded = framed && st[0] == 0 && st[1] == h.n_intervals;
+  if (p0 == 0) status[img] = decoded ? 0 : 1;
   const int round = (1 << lg) - 1;
   const int W = (h.width + round) >> lg, H = (h.height + round) >> lg;
   const long npix = (long)W * H;
-  if (!pixels_wanted(h, st) || p0 >= npix) return;
+  if (!(kPixelsOnlyWhenDecoded<Header> ? decoded : framed) || p0 >= npix) return;
   const int n = (int)min((long)kColor4Pixels, npix - p0);
-  CompPlane cp[4];
-  comp_planes<4>(h, ws, lg, cp);
+  CompPlane cp[kC];
+  comp_planes<kC>(h, ws, lg, cp);
   const bool fancy = lg < 3;
   unsigned char px[3 * kColor4Pixels];
   for (int i = 0; i < n; ++i) {
     const long p = p0 + i;
     const int y = (int)(p / W), x = (int)(p - (long)y * W);
-    int s[4];
+    int s[kC];
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
+    for (int c = 0; c < kC; ++c)
       s[c] = upsampled_by(cp[c].P, cp[c].pw, x, y, cp[c].rh, cp[c].rv, cp[c].dw, cp[c].dh, fancy);
-    if (colour_flag(h)) {
-      const int cb = s[1] - 128, cr = s[2] - 128, yv = s[0];
-      s[0] = 255 - clamp255(yv + ((kCrR * cr + 32768) >> 16));
-      s[1] = 255 - clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
-      s[2] = 255 - clamp255(yv + ((kCbB * cb + 32768) >> 16));
-    }
-    cmyk_pixel_rgb(s[0], s[1], s[2], s[3], 1, px + 3 * i);
-  }
-  store_rgb4(out + h.out_off + 3 * p0, px, n);
-}
-
-// odic_jpeg_header3, in color4_pixels' form: four consecutive pixels per lane, every component through upsampled_by()
-// at its own ratio to the largest sampling — component 0 too, where it is not the largest — then ycc_rgb_convert, or the
-// three samples as they are for an RGB file; plus the per-image status.  A record that layout_ok() refuses has status 1
-// and no pixels.
-template <bool kScaled, typename Header>                        // odic_jpeg_header3 or odic_jpeg_prog_header_any
-__device__ __forceinline__ void color3_pixels(const Header& h, const Ws& ws, int img, int lg_in,
-                                              unsigned char* __restrict__ out, int* __restrict__ status) {
-  if (colour_comps(h) != 3) return;
-  const int lg = kScaled ? lg_in : 0;
-  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kColor4Pixels;
-  const int* st = ws.state + kStateWords * img;
-  if (p0 == 0) status[img] = image_status_ok(h, st) ? 0 : 1;
-  const int round = (1 << lg) - 1;
-  const int W = (h.width + round) >> lg, H = (h.height + round) >> lg;
-  const long npix = (long)W * H;
-  if (!pixels_wanted(h, st) || p0 >= npix) return;
-  const int n = (int)min((long)kColor4Pixels, npix - p0);
-  CompPlane cp[3];
-  comp_planes<3>(h, ws, lg, cp);
-  const bool fancy = lg < 3;
-  unsigned char px[3 * kColor4Pixels];
-  for (int i = 0; i < n; ++i) {
-    const long p = p0 + i;
-    const int y = (int)(p / W), x = (int)(p - (long)y * W);
-    int s[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      s[c] = upsampled_by(cp[c].P, cp[c].pw, x, y, cp[c].rh, cp[c].rv, cp[c].dw, cp[c].dh, fancy);
-    if (colour_flag(h)) {
+    if constexpr (kC == 4) {
+      if (h.color) {
+        const int cb = s[1] - 128, cr = s[2] - 128, yv = s[0];
+        s[0] = 255 - clamp255(yv + ((kCrR * cr + 32768) >> 16));
+        s[1] = 255 - clamp255(yv + ((-kCbG * cb + 32768 - kCrG * cr) >> 16));
+        s[2] = 255 - clamp255(yv + ((kCbB * cb + 32768) >> 16));
+      }
+      cmyk_pixel_rgb(s[0], s[1], s[2], s[3], 1, px + 3 * i);
+    } else if (h.color) {
       for (int c = 0; c < 3; ++c) px[3 * i + c] = (unsigned char)s[c];
     } else {
       ycc_rgb_pixel(s[0], s[1], s[2], px + 3 * i);
@@ -1357,21 +1299,20 @@ __device__ __forceinline__ void color3_pixels(const Header& h, const Ws& ws, int
   store_rgb4(out + h.out_off + 3 * p0, px, n);
 }
 
+// One launch for a batch of either per-component record: each image takes the body of its component count (a count
+// that is neither, which layout_ok() refuses, the one for three: status 1, no pixels).
 template <typename Header>
-__global__ __launch_bounds__(256) void jpeg_color4_kernel(const Header* __restrict__ hdrs, Ws ws,
-                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
-  color4_pixels<false>(hdrs[blockIdx.y], ws, blockIdx.y, 0, out, status);
+__global__ __launch_bounds__(256) void jpeg_color_own_kernel(const Header* __restrict__ hdrs, Ws ws,
+                                                             unsigned char* __restrict__ out,
+                                                             int* __restrict__ status) {
+  const Header& h = hdrs[blockIdx.y];
+  if (h.ncomp == 4) color_own_pixels<false, 4>(h, ws, blockIdx.y, 0, out, status);
+  else color_own_pixels<false, 3>(h, ws, blockIdx.y, 0, out, status);
 }
 
+// The same at scale_log2[image] = 0..3.  Not a scale: nothing was decoded (jpeg_idct_scaled_kernel), nothing is written,
+// and the image gets status 1.
 template <typename Header>
-__global__ __launch_bounds__(256) void jpeg_color3_kernel(const Header* __restrict__ hdrs, Ws ws,
-                                                          unsigned char* __restrict__ out, int* __restrict__ status) {
-  color3_pixels<false>(hdrs[blockIdx.y], ws, blockIdx.y, 0, out, status);
-}
-
-// The two at scale_log2[image] = 0..3.  Not a scale: nothing was decoded (jpeg_idct_scaled_kernel), nothing is written,
-// and the kernel of the image's component count reports status 1.
-template <int kC, typename Header>
 __global__ __launch_bounds__(256) void jpeg_color_own_scaled_kernel(const Header* __restrict__ hdrs, Ws ws,
                                                                     const int* __restrict__ scale_log2,
                                                                     unsigned char* __restrict__ out,
@@ -1379,11 +1320,11 @@ __global__ __launch_bounds__(256) void jpeg_color_own_scaled_kernel(const Header
   const int img = blockIdx.y, lg = scale_log2[img];
   const Header& h = hdrs[img];
   if ((unsigned)lg > 3u) {
-    if (colour_comps(h) == kC && blockIdx.x == 0 && threadIdx.x == 0) status[img] = 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[img] = 1;
     return;
   }
-  if constexpr (kC == 4) color4_pixels<true>(h, ws, img, lg, out, status);
-  else color3_pixels<true>(h, ws, img, lg, out, status);
+  if (h.ncomp == 4) color_own_pixels<true, 4>(h, ws, img, lg, out, status);
+  else color_own_pixels<true, 3>(h, ws, img, lg, out, status);
 }
 
 
@@ -1412,27 +1353,32 @@ __global__ __launch_bounds__(256) void jpeg_color_own_scaled_kernel(const Header
 // the bit reader only advances while pos <= the interval's end, which keeps its look-ahead inside the 16 bytes reserved
 // behind every compacted scan, and correction bits are fetched only after pos <= end was checked for the whole block.
 //
-// Frames with per-component sampling (odic_jpeg_prog_header_any: four components, or three at any layout; entry point
-// odic_jpeg_decode_progressive_any) run the same segment kernel and the same decode kernel and coding procedures,
-// instantiated for that record: what differs is ProgGeo, the frame as the scans see it.  An interleaved scan walks the
-// frame's MCUs, which span the largest factors whichever components the scan names, and writes the named components'
-// blocks of each; a single-component scan walks the component's own raster, so the padding blocks outside it keep what
-// the interleaved scans gave them (zero where there was none).  Then jpeg_idct_kernel for the record (block_geo_own)
-// and both per-component colour kernels, each of which takes the images of its component count.
+// The per-component record (odic_jpeg_prog_header_any, entry point odic_jpeg_decode_progressive_any) runs the same
+// segment kernel and the same decode kernel and coding procedures, instantiated for it: what differs is ProgGeo, the
+// frame as the scans see it.  An interleaved scan walks the frame's MCUs, which span the largest factors whichever
+// components the scan names, and writes the named components' blocks of each; a single-component scan walks the
+// component's own raster, so the padding blocks outside it keep what the interleaved scans gave them (zero where there
+// was none).  Then the per-component IDCT (block_geo_own) and colour kernel, as for odic_jpeg_header_any.
 //
-// The bounds argument for that record.  The geometry is built only from a record layout_ok() admits: ncomp 3 or 4,
-// factors in 1..4 that divide the largest, at most 10 blocks per MCU, so hh, vv in 1..4 and first + nb <= bpm <= 10 fit
-// ProgGeo's four-bit fields; a scan whose mask names a component >= ncomp is refused before anything is read, so hh / vv
-// of a named component are the record's own and never 0.  Every block index, from raster_block() (single-component
+// The bounds argument, by record family.  A COMMON record's geometry is a function of `sampling` alone, which every
+// helper maps to one of four fixed shapes (blocks_per_mcu, luma_h / luma_v), so a block index is below mcus_x · mcus_y ·
+// bpm and a plane byte below 64 times that, the products the host sizes the coefficient array and the planes by.  A
+// PER-COMPONENT record's geometry is built only from a record layout_ok() admits: ncomp 3 or 4, factors in 1..4 that
+// divide the largest, at most 10 blocks per MCU — so the block-to-component map fits Frame's two bits per block, and hh,
+// vv in 1..4 and first + nb <= bpm <= 10 fit ProgGeo's four-bit fields.  For a record it refuses, the baseline entropy
+// kernels decode a frame of one block of component 0 into the record's own coefficient slice (interval_blocks() bounds
+// every block index by the MCU count, write_span() by the interval's), and the progressive decode kernel reads nothing;
+// a progressive scan whose mask names a component >= ncomp is refused before anything is read, so hh / vv of a named
+// component are the record's own and never 0.  Every progressive block index, from raster_block() (single-component
 // scans; bw is the scan's own and only has to be positive) or from u · bpm + first + j (interleaved scans, j < nb), is
 // compared with nblocks = mcus_x · mcus_y · bpm before the coefficient array is touched, and the host sizes that array
 // (coef_off, total_blocks) by the same product; the zig-zag index and bit reader rules are those above, unchanged.
 // The IDCT reads block b < nblocks and writes plane bytes below 64 · nblocks from plane_off (block_geo_own places
 // block j of MCU m at a row and column inside plane c's mcus_x·8·h[c] by mcus_y·8·v[c] samples); it returns at once
-// for a record layout_ok() refuses.  The colour kernels return before reading a plane, and write status 1 and no
-// pixel, for such a record and for any image whose state words report an error or a missing interval; otherwise
-// they read sample (y / rv, x / rh) and its neighbours clamped to the component's dw x dh real samples, which lie
-// inside its plane because W <= mcus_x · 8 · hmax and H <= mcus_y · 8 · vmax.
+// for a record layout_ok() refuses.  The colour kernel returns before reading a plane, and writes status 1 and no
+// pixel, for such a record (and, kPixelsOnlyWhenDecoded, for a progressive image whose state words report an error or
+// a missing interval); otherwise it reads sample (y / rv, x / rh) and its neighbours clamped to the component's dw x dh
+// real samples, which lie inside its plane because W <= mcus_x · 8 · hmax and H <= mcus_y · 8 · vmax.
 // ---------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(odic_jpeg_prog_header) == 432 && offsetof(odic_jpeg_prog_header, qt) == 48 &&
                   sizeof(odic_jpeg_scan) == 88 && offsetof(odic_jpeg_scan, table) == 72 &&
@@ -1833,33 +1779,24 @@ void launch_idct_color(const Batch* b, const Header* hdrs, const Ws& ws, const i
   }
 }
 
-// The same for the records with per-component sampling: the per-component IDCT and the colour kernel of the record's
-// component count (both for odic_jpeg_prog_header_any, each of which takes the images of its count), four pixels per
-// lane; max_width / max_height are those of the scaled sizes.
+// The same for the per-component records: the per-component IDCT and the one colour kernel, four pixels per lane;
+// max_width / max_height are those of the scaled sizes.
 template <typename Header, typename Batch>
 void launch_idct_color_own(const Batch* b, const Header* hdrs, const Ws& ws, const int32_t* scale_log2, hipStream_t s) {
-  constexpr bool k3 = !std::is_same<Header, odic_jpeg_header4>::value;
-  constexpr bool k4 = !std::is_same<Header, odic_jpeg_header3>::value;
   const int n = b->n_images;
   const long lanes = ((long)b->max_width * b->max_height + kColor4Pixels - 1) / kColor4Pixels;
   const dim3 igrid((unsigned)((b->max_blocks + 31) / 32), n), cgrid((unsigned)((lanes + 255) / 256), n);
   if (scale_log2) {
     hipLaunchKernelGGL(jpeg_idct_scaled_kernel<Header>, igrid, dim3(256), 0, s, hdrs, ws, scale_log2);
-    if constexpr (k3)
-      hipLaunchKernelGGL((jpeg_color_own_scaled_kernel<3, Header>), cgrid, dim3(256), 0, s, hdrs, ws, scale_log2, b->out,
-                         b->status);
-    if constexpr (k4)
-      hipLaunchKernelGGL((jpeg_color_own_scaled_kernel<4, Header>), cgrid, dim3(256), 0, s, hdrs, ws, scale_log2, b->out,
-                         b->status);
+    hipLaunchKernelGGL(jpeg_color_own_scaled_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, scale_log2, b->out,
+                       b->status);
   } else {
     hipLaunchKernelGGL(jpeg_idct_kernel<Header>, igrid, dim3(256), 0, s, hdrs, ws);
-    if constexpr (k3) hipLaunchKernelGGL(jpeg_color3_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
-    if constexpr (k4) hipLaunchKernelGGL(jpeg_color4_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
+    hipLaunchKernelGGL(jpeg_color_own_kernel<Header>, cgrid, dim3(256), 0, s, hdrs, ws, b->out, b->status);
   }
 }
 
-// Header: odic_jpeg_header (three components or gray), odic_jpeg_header4 (four) or odic_jpeg_header3 (three at any
-// sampling layout)
+// Header: odic_jpeg_header (common) or odic_jpeg_header_any (per-component)
 template <typename Header>
 int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream,
                     const int32_t* scale_log2) {
@@ -1887,16 +1824,12 @@ int decode_baseline(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, 
   hipLaunchKernelGGL(jpeg_block_scan_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
   hipLaunchKernelGGL(jpeg_writeout_kernel<Header>, ugrid, dim3(kUnitLanes), lds, s, hdrs, ws, S);
   hipLaunchKernelGGL(jpeg_dc_kernel<Header>, dim3(n), dim3(256), 0, s, hdrs, ws);
-  if constexpr (!std::is_same<Header, odic_jpeg_header>::value) {       // per-component sampling
-    launch_idct_color_own(b, hdrs, ws, scale_log2, s);
-  } else {
-    launch_idct_color(b, hdrs, ws, scale_log2, s);
-  }
+  if constexpr (kPerComponent<Header>) launch_idct_color_own(b, hdrs, ws, scale_log2, s);
+  else launch_idct_color(b, hdrs, ws, scale_log2, s);
   return odic_launch_status();
 }
 
-// Header: odic_jpeg_prog_header (three components at the common samplings, or gray) or odic_jpeg_prog_header_any
-// (per-component sampling, three or four components)
+// Header: odic_jpeg_prog_header (common) or odic_jpeg_prog_header_any (per-component)
 template <typename Header>
 int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws_bytes, void* stream,
                        const int32_t* scale_log2) {
@@ -1919,11 +1852,8 @@ int decode_progressive(const odic_jpeg_prog_batch* b, void* workspace, size_t ws
     hipLaunchKernelGGL(jpeg_prog_decode_kernel<Header>,
                        dim3(b->level_intervals[l], b->level_first[l + 1] - b->level_first[l]), dim3(64), 0, s, hdrs, scans,
                        tables, ws, b->level_first[l], n, b->n_tables);
-  if constexpr (std::is_same<Header, odic_jpeg_prog_header_any>::value) {
-    launch_idct_color_own(b, hdrs, ws, scale_log2, s);
-  } else {
-    launch_idct_color(b, hdrs, ws, scale_log2, s);
-  }
+  if constexpr (kPerComponent<Header>) launch_idct_color_own(b, hdrs, ws, scale_log2, s);
+  else launch_idct_color(b, hdrs, ws, scale_log2, s);
   return odic_launch_status();
 }
 
@@ -1933,16 +1863,10 @@ extern "C" int odic_jpeg_decode(const odic_jpeg_batch* b, void* workspace, size_
   return decode_baseline<odic_jpeg_header>(b, workspace, ws_bytes, stream, nullptr);
 }
 
-extern "C" size_t odic_jpeg4_workspace_bytes(const odic_jpeg_batch* b) { return odic_jpeg_workspace_bytes(b); }
+extern "C" size_t odic_jpeg_any_workspace_bytes(const odic_jpeg_batch* b) { return odic_jpeg_workspace_bytes(b); }
 
-extern "C" int odic_jpeg4_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
-  return decode_baseline<odic_jpeg_header4>(b, workspace, ws_bytes, stream, nullptr);
-}
-
-extern "C" size_t odic_jpeg3_any_workspace_bytes(const odic_jpeg_batch* b) { return odic_jpeg_workspace_bytes(b); }
-
-extern "C" int odic_jpeg3_any_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
-  return decode_baseline<odic_jpeg_header3>(b, workspace, ws_bytes, stream, nullptr);
+extern "C" int odic_jpeg_any_decode(const odic_jpeg_batch* b, void* workspace, size_t ws_bytes, void* stream) {
+  return decode_baseline<odic_jpeg_header_any>(b, workspace, ws_bytes, stream, nullptr);
 }
 
 extern "C" int odic_cmyk_to_rgb8(const uint8_t* cmyk, uint8_t* rgb, int64_t n_pixels, int invert, void* stream) {
@@ -1985,16 +1909,10 @@ extern "C" int odic_jpeg_decode_progressive_any(const odic_jpeg_prog_batch* b, v
   return decode_progressive<odic_jpeg_prog_header_any>(b, workspace, ws_bytes, stream, nullptr);
 }
 
-extern "C" int odic_jpeg4_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
-                                        size_t ws_bytes, void* stream) {
+extern "C" int odic_jpeg_any_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
+                                           size_t ws_bytes, void* stream) {
   if (!scale_log2) return ODIC_ENULL;
-  return decode_baseline<odic_jpeg_header4>(b, workspace, ws_bytes, stream, scale_log2);
-}
-
-extern "C" int odic_jpeg3_any_decode_scaled(const odic_jpeg_batch* b, const int32_t* scale_log2, void* workspace,
-                                            size_t ws_bytes, void* stream) {
-  if (!scale_log2) return ODIC_ENULL;
-  return decode_baseline<odic_jpeg_header3>(b, workspace, ws_bytes, stream, scale_log2);
+  return decode_baseline<odic_jpeg_header_any>(b, workspace, ws_bytes, stream, scale_log2);
 }
 
 extern "C" int odic_jpeg_decode_progressive_any_scaled(const odic_jpeg_prog_batch* b, const int32_t* scale_log2,

@@ -44,11 +44,11 @@ def preprocess_image(image_path: str, img_size: int) -> torch.Tensor:
 # device, the other modes by PIL.  With `orientation="exif"` every image is turned upright as `ImageOps.exif_transpose`
 # does: device-decoded files by one odic_orient_rgb8 launch (csrc/orient.hip), PIL-decoded ones by PIL.  With
 # `cmyk="device"` (and `non_rgb="convert"`) baseline CMYK / YCCK JPEGs are decoded and converted on the device too
-# (odic_jpeg4_decode) instead of leaving the batch for PIL.  With `layouts="all"` so are baseline three-component
-# JPEGs at the sampling layouts and colour spaces the common decode turns away (odic_jpeg3_any_decode: 4:4:0, 4:1:1,
+# (odic_jpeg_any_decode) instead of leaving the batch for PIL.  With `layouts="all"` so are baseline three-component
+# JPEGs at the sampling layouts and colour spaces the common decode turns away (the same call: 4:4:0, 4:1:1,
 # 4:1:0, RGB-stored files, ...).  With `progressive="device"` beside either keyword the progressive files of that kind are
 # decoded on the device as well (odic_jpeg_decode_progressive_any).  Under a draft request those four kinds go to PIL
-# unless `draft_layouts="all"`, which decodes them at the draft scale on the device (the three _scaled entry points).
+# unless `draft_layouts="all"`, which decodes them at the draft scale on the device (the two _scaled entry points).
 # =================================================================================================
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -336,7 +336,7 @@ class DevicePreprocessor:
     def last_routes(self):
         """How each file of the last `decode_jpeg` / `from_jpeg_bytes` call was decoded, in input order: "device" (baseline,
         odic_jpeg_decode), "device-progressive" (odic_jpeg_decode_progressive), "device-cmyk" (four components,
-        odic_jpeg4_decode), "device-layout" (three components at a layout of layouts="all", odic_jpeg3_any_decode),
+        odic_jpeg_any_decode), "device-layout" (three components at a layout of layouts="all", the same call),
         "device-progressive-cmyk" / "device-progressive-layout" (the progressive files of those two kinds,
         odic_jpeg_decode_progressive_any), "host"
         (PIL: a kind the device does not
@@ -372,14 +372,14 @@ class DevicePreprocessor:
         value applied to each file (`jpeg.exif_orientation`).
         cmyk="device" (needs non_rgb="convert"; the default "host" leaves them to PIL until the device route is
         measured): baseline four-component JPEGs — CMYK, or YCCK by Adobe transform 2 — that
-        `jpeg.parse` admits are decoded by one odic_jpeg4_decode call in the same upload and status read-back, route
+        `jpeg.parse` admits are decoded by one odic_jpeg_any_decode call in the same upload and status read-back, route
         "device-cmyk", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  Progressive four-component files
         stay with PIL unless progressive="device" is given too (below), and so do all of them under a draft request
         unless draft_layouts="all" (below).
         layouts="all" (the default "common" leaves them to PIL until the device route is measured):
         baseline three-component JPEGs that only `jpeg.parse(f, layouts="all")` admits — luma at 1x2 (4:4:0), 4x1
         (4:1:1), 4x2 (4:1:0), chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest, files
-        stored as RGB — are decoded by one odic_jpeg3_any_decode call in the same upload and status read-back, route
+        stored as RGB — are decoded by that odic_jpeg_any_decode call too (one call for both kinds), route
         "device-layout", each equal to np.asarray(PIL.Image.open(f).convert("RGB")).  A file the common rules admit keeps
         its route.  Progressive files with these layouts stay with PIL unless progressive="device" is given too, and
         so do all of them under a draft request unless draft_layouts="all".
@@ -392,7 +392,7 @@ class DevicePreprocessor:
         siblings do, unless draft_layouts="all".
         draft_layouts="all" (the default "common" withholds cmyk= and layouts= from the parsers under a draft request,
         so that their files go to PIL with the same request): the files those two keywords admit keep their four routes
-        under a draft and are decoded at the draft scale by odic_jpeg4_decode_scaled, odic_jpeg3_any_decode_scaled and
+        under a draft and are decoded at the draft scale by odic_jpeg_any_decode_scaled and
         odic_jpeg_decode_progressive_any_scaled, every component at libjpeg's own transform size for that scale
         (`jpeg.scaled_components`), each equal to what PIL makes of the file after `im.draft("RGB", draft)`
         and `convert("RGB")`.  Without a draft request it changes nothing."""
@@ -412,23 +412,15 @@ class DevicePreprocessor:
         blobs = [bytes(b) for b in blobs]
         rp = J.plan_routes(blobs, progressive, draft, non_rgb, cmyk, layouts, draft_layouts, self.max_bytes)
         hdrs, scales, sizes, routes = rp.hdrs, rp.scales, rp.sizes, rp.routes
-        base, prog, four, lay, pany = rp.base, rp.prog, rp.four, rp.lay, rp.pany
-        dev = rp.order
+        order = rp.order
         exif = orientation != "ignore"
         turns = [J.header_orientation(h, b) if exif else 1 for h, b in zip(hdrs, blobs)]
         host_kw = {"orientation": orientation} if exif else {}           # the default's calls stay as they are
         out = [None] * len(blobs)
-        if dev:
-            order = dev
-            group4 = ([hdrs[i] for i in four], [blobs[i] for i in four]) if four or lay else ()   # without: today's call
-            if lay:
-                group4 += ([hdrs[i] for i in lay], [blobs[i] for i in lay])
-            status, rgb, out_offs = self._decode_on_device([hdrs[i] for i in base], [blobs[i] for i in base],
-                                                           [hdrs[i] for i in prog], [blobs[i] for i in prog],
-                                                           subseq_bits, max_sync_passes,
-                                                           [scales[i] for i in order], *group4,
-                                                           **({"ahdrs": [hdrs[i] for i in pany],
-                                                               "ablobs": [blobs[i] for i in pany]} if pany else {}))
+        if order:
+            groups = [(kind, [hdrs[i] for i in idx], [blobs[i] for i in idx]) for kind, idx in rp.groups]
+            status, rgb, out_offs = self._decode_on_device(groups, subseq_bits, max_sync_passes,
+                                                           [scales[i] for i in order])
             turned = []                                                  # (image, its offset in rgb): to be permuted
             for k, i in enumerate(order):
                 if status[k] != 0:
@@ -476,103 +468,63 @@ class DevicePreprocessor:
             w, h = oriented_size(sizes[i], turns[i])
             out[i] = dst[int(r["dst_off"]):int(r["dst_off"]) + w * h * 3].view(h, w, 3)
 
-    def _decode_on_device(self, hdrs, blobs, phdrs, pblobs, subseq_bits, max_sync_passes, scales, chdrs=(), cblobs=(),
-                          lhdrs=(), lblobs=(), ahdrs=(), ablobs=()):
-        """One odic_jpeg_decode call for the baseline files, one odic_jpeg_decode_progressive call for the progressive
-        ones, one odic_jpeg4_decode call for the four-component ones (chdrs, cblobs) and one odic_jpeg3_any_decode call
-        for the `layout` ones (lhdrs, lblobs) and one odic_jpeg_decode_progressive_any call for the progressive files
-        with per-component sampling (ahdrs, ablobs), sharing one upload, one output
-        buffer, one workspace and one status read-back → (status numpy int32 — baseline files first, then progressive,
-        four-component, `layout`, progressive with per-component sampling —, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image,
-        baseline files first; a kind with a scale above 1 goes through its _scaled entry point, with the scales uploaded
-        beside the headers.  This is the GPU half: `jpeg.plan_device_batch` lays the upload and the output out."""
+    #: group kind (jpeg.GROUP_KINDS) → (batch struct of _hip, workspace query, entry point; `_scaled` for a draft scale)
+    _JPEG_CALLS = {
+        "base": ("JpegBatch", "odic_jpeg_workspace_bytes", "odic_jpeg_decode"),
+        "prog": ("JpegProgBatch", "odic_jpeg_progressive_workspace_bytes", "odic_jpeg_decode_progressive"),
+        "own": ("JpegBatch", "odic_jpeg_any_workspace_bytes", "odic_jpeg_any_decode"),
+        "pany": ("JpegProgBatch", "odic_jpeg_progressive_any_workspace_bytes", "odic_jpeg_decode_progressive_any"),
+    }
+
+    def _decode_on_device(self, groups, subseq_bits, max_sync_passes, scales):
+        """One decode call per group of `groups` ([(kind, headers, files)] as `jpeg.plan_device_batch` takes them):
+        odic_jpeg_decode, odic_jpeg_decode_progressive, odic_jpeg_any_decode or odic_jpeg_decode_progressive_any
+        (`_JPEG_CALLS`), sharing one upload, one output buffer, one workspace and one status read-back → (status numpy
+        int32 in group order, uint8 RGB buffer, byte offset per image).  scales: the draft scale of every image in group
+        order; a group with a scale above 1 goes through its _scaled entry point, with the scales uploaded beside the
+        headers.  This is the GPU half: `jpeg.plan_device_batch` lays the upload and the output out."""
         from . import jpeg as J
-        nb, npg, ncm, nly = len(hdrs), len(phdrs), len(chdrs), len(lhdrs)
-        group4 = (chdrs, cblobs) if ncm or nly else ()
-        if nly:
-            group4 += (lhdrs, lblobs)
-        npa = len(ahdrs)
-        group_any = {"ahdrs": ahdrs, "ablobs": ablobs} if npa else {}    # without: today's call
-        plan = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, *group4, **group_any)
-        n_all = nb + npg + ncm + nly + npa
+        plan = J.plan_device_batch(groups, subseq_bits, scales)
+        n_all = len(plan.out_offs)
         self._jpeg_ev.synchronize()                                      # the previous batch's upload is done
         self._jpeg_pinned = self._grow(self._jpeg_pinned, plan.total, pin_memory=True)
         self._jpeg_status = self._grow(self._jpeg_status, 4 * n_all, pin_memory=True)
         plan.fill(self._jpeg_pinned.numpy())
-        out_total = plan.cout_off + plan.cout_bytes if ncm else plan.out_bytes + plan.pout_bytes
-        if nly:
-            out_total = plan.lout_off + plan.lout_bytes
-        if npa:
-            out_total = plan.aout_off + plan.aout_bytes
-        rgb = torch.empty(max(out_total, 1), dtype=torch.uint8, device=self.device)
+        rgb = torch.empty(max(plan.groups[-1].out_off + plan.groups[-1].out_bytes, 1), dtype=torch.uint8,
+                          device=self.device)
         status = torch.empty(n_all, dtype=torch.int32, device=self.device)
-        need_b = need_p = need_c = need_l = need_a = 0
-        if npa:
-            ab = self._hip.JpegProgBatch()
-            ab.n_images = npa
-            self._set_fields(ab, plan.atot)
-            need_a = self.lib.odic_jpeg_progressive_any_workspace_bytes(ctypes.byref(ab))
-            if need_a == 0:
+        calls = []                                                       # (group, batch struct, workspace bytes, entry)
+        for g in sorted(plan.groups, key=lambda g: g.kind == "prog"):    # "prog" last: its coefficients stay in the
+            struct, query, entry = self._JPEG_CALLS[g.kind]              # workspace (`progressive_coefficients`)
+            b = getattr(self._hip, struct)()
+            b.n_images = g.n
+            if struct == "JpegBatch":
+                b.subseq_bits, b.max_sync_passes = subseq_bits, max_sync_passes
+            self._set_fields(b, g.tot)
+            need = getattr(self.lib, query)(ctypes.byref(b))
+            if need == 0 and struct == "JpegProgBatch":
                 raise RuntimeError("JPEG batch too large for one progressive decode call")
-        if nly:
-            lb = self._hip.JpegBatch()
-            lb.n_images, lb.subseq_bits, lb.max_sync_passes = nly, subseq_bits, max_sync_passes
-            self._set_fields(lb, plan.ltot)
-            need_l = self.lib.odic_jpeg3_any_workspace_bytes(ctypes.byref(lb))
-        if ncm:
-            cb = self._hip.JpegBatch()
-            cb.n_images, cb.subseq_bits, cb.max_sync_passes = ncm, subseq_bits, max_sync_passes
-            self._set_fields(cb, plan.ctot)
-            need_c = self.lib.odic_jpeg4_workspace_bytes(ctypes.byref(cb))
-        if nb:
-            b = self._hip.JpegBatch()
-            b.n_images, b.subseq_bits, b.max_sync_passes = nb, subseq_bits, max_sync_passes
-            self._set_fields(b, plan.tot)
-            need_b = self.lib.odic_jpeg_workspace_bytes(ctypes.byref(b))
-        if npg:
-            pb = self._hip.JpegProgBatch()
-            pb.n_images = npg
-            self._set_fields(pb, plan.ptot)
-            need_p = self.lib.odic_jpeg_progressive_workspace_bytes(ctypes.byref(pb))
-            if need_p == 0:
-                raise RuntimeError("JPEG batch too large for one progressive decode call")
+            calls.append((g, b, need, entry))
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             self._jpeg_dev = self._grow(self._jpeg_dev, plan.total, device=self.device)
-            self._jpeg_ws = self._grow(self._jpeg_ws, max(need_b, need_p, need_c, need_l, need_a), device=self.device)
+            self._jpeg_ws = self._grow(self._jpeg_ws, max(need for _, _, need, _ in calls), device=self.device)
             self._jpeg_dev[:plan.total].copy_(self._jpeg_pinned[:plan.total], non_blocking=True)
             self._jpeg_ev.record(self.stream)
             base = self._jpeg_dev.data_ptr()
-
-            def decode(name, batch, need, first):                        # `first`: the kind's first image in `scales`
-                args = [ctypes.byref(batch), self._jpeg_ws.data_ptr(), need, self.stream.cuda_stream]
-                if any(s > 1 for s in scales[first:first + batch.n_images]):
-                    name += "_scaled"
-                    args.insert(1, base + plan.scale_off + 4 * first)
-                self._hip.check(getattr(self.lib, name)(*args), name)
-
-            if nb:
-                b.headers, b.data, b.out, b.status = base, base + plan.data_off, rgb.data_ptr(), status.data_ptr()
-                decode("odic_jpeg_decode", b, need_b, 0)
-            if ncm:
-                cb.headers, cb.data = base + plan.cmyk_off, base + plan.data_off
-                cb.out, cb.status = rgb.data_ptr() + plan.cout_off, status.data_ptr() + 4 * (nb + npg)
-                decode("odic_jpeg4_decode", cb, need_c, nb + npg)
-            if nly:
-                lb.headers, lb.data = base + plan.layout_off, base + plan.data_off
-                lb.out, lb.status = rgb.data_ptr() + plan.lout_off, status.data_ptr() + 4 * (nb + npg + ncm)
-                decode("odic_jpeg3_any_decode", lb, need_l, nb + npg + ncm)
-            if npa:
-                ab.headers, ab.scans, ab.tables = (base + o for o in plan.any_off)
-                ab.data, ab.out = base + plan.data_off, rgb.data_ptr() + plan.aout_off
-                ab.status = status.data_ptr() + 4 * (nb + npg + ncm + nly)
-                decode("odic_jpeg_decode_progressive_any", ab, need_a, nb + npg + ncm + nly)
-            if npg:                                                      # last: its coefficients stay in the workspace
-                pb.headers, pb.scans, pb.tables = (base + o for o in plan.prog_off)
-                pb.data, pb.out = base + plan.data_off, rgb.data_ptr() + plan.out_bytes
-                pb.status = status.data_ptr() + 4 * nb
-                decode("odic_jpeg_decode_progressive", pb, need_p, nb)
-                self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(pb)), plan.coef_off)
+            for g, b, need, entry in calls:
+                b.headers = base + g.offs[0]
+                if len(g.offs) == 3:
+                    b.scans, b.tables = base + g.offs[1], base + g.offs[2]
+                b.data, b.out = base + plan.data_off, rgb.data_ptr() + g.out_off
+                b.status = status.data_ptr() + 4 * g.first
+                args = [ctypes.byref(b), self._jpeg_ws.data_ptr(), need, self.stream.cuda_stream]
+                if any(s > 1 for s in scales[g.first:g.first + g.n]):
+                    entry += "_scaled"
+                    args.insert(1, base + plan.scale_off + 4 * g.first)
+                self._hip.check(getattr(self.lib, entry)(*args), entry)
+                if g.kind == "prog":
+                    self._jpeg_prog_coef = (self.lib.odic_jpeg_progressive_coef_offset(ctypes.byref(b)), plan.coef_off)
             st = self._jpeg_status[:4 * n_all].view(torch.int32)
             st.copy_(status, non_blocking=True)
         self.stream.synchronize()                                        # the one host synchronisation

@@ -24,7 +24,7 @@ That is the default, non_rgb="black".  Under non_rgb="convert" every file is to 
 sampling factors and component id the SOF declares, which libjpeg ignores for a single component — and a four-component
 frame is `host`, where PIL converts it — unless the caller also passes cmyk="device": then a baseline four-component frame
 (CMYK, or YCCK by Adobe transform 2) that `_frame4` admits is a `device` kind with ncomp 4, the sampling of every
-component in comp_hv and the `ycck` flag; odic_jpeg4_decode reads its records (`HEADER4_DTYPE`).  To `parse`
+component in comp_hv and the `ycck` flag; odic_jpeg_any_decode reads its records (`HEADER_ANY_DTYPE`).  To `parse`
 progressive four-component files stay `host` (`PROG_CMYK_REASON`); under a draft request `plan_routes` withholds the
 keyword unless draft_layouts="all", which decodes them at the draft scale (`scaled_components`).
 
@@ -33,7 +33,7 @@ rules above turn away for its sampling or its colour space is a `device` kind to
 component at its own (h, v) in 1..4 with integral ratios to the largest and at most MAX_MCU_BLOCKS blocks per MCU —
 4:4:0, 4:1:1, 4:1:0, chroma sub-sampled one way under a 2x2 luma, a component 0 that is not the largest — stored as
 YCbCr or as RGB (Adobe transform 0, or ids R, G, B with neither marker).  The header has `layout` set, comp_hv, the
-`rgb` flag and MCU counts from the largest factors; odic_jpeg3_any_decode reads its records (`HEADER3_DTYPE`).  What
+`rgb` flag and MCU counts from the largest factors; the same call reads its records, of the same dtype.  What
 still goes to the host after that:
 
     host    fractional sampling ratios; more than 10 blocks per MCU; progressive files (`PROG_LAYOUT_REASON`), and draft
@@ -116,25 +116,16 @@ HEADER_DTYPE = np.dtype([
     ("qt", "<u2", (3, 64)), ("lut", "<u2", (6, 512)), ("maxcode", "<i4", (6, 18)), ("valoff", "<i4", (6, 18)),
     ("huffval", "u1", (6, 256)),
 ], align=True)
-# odic_jpeg_header4 (include/odic_hip.h), field for field: four components, each with its own sampling
-HEADER4_DTYPE = np.dtype([
+# odic_jpeg_header_any (include/odic_hip.h), field for field: three or four components, each with its own sampling;
+# `color` as in PROG_HEADER_ANY_DTYPE (three components: stored as RGB; four: YCCK)
+HEADER_ANY_DTYPE = np.dtype([
     ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
     ("plane_off", "<i8"),
-    ("int_off", "<i4"), ("unit_off", "<i4"), ("width", "<i4"), ("height", "<i4"), ("ycck", "<i4"),
+    ("int_off", "<i4"), ("unit_off", "<i4"), ("width", "<i4"), ("height", "<i4"), ("color", "<i4"),
     ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart", "<i4"), ("n_intervals", "<i4"), ("n_units", "<i4"),
-    ("h", "<i4", (4,)), ("v", "<i4", (4,)),
+    ("h", "<i4", (4,)), ("v", "<i4", (4,)), ("ncomp", "<i4"), ("pad", "<i4"),
     ("qt", "<u2", (4, 64)), ("lut", "<u2", (8, 512)), ("maxcode", "<i4", (8, 18)), ("valoff", "<i4", (8, 18)),
     ("huffval", "u1", (8, 256)),
-], align=True)
-# odic_jpeg_header3 (include/odic_hip.h), field for field: three components, each with its own sampling, YCbCr or RGB
-HEADER3_DTYPE = np.dtype([
-    ("data_off", "<i8"), ("data_end", "<i8"), ("out_off", "<i8"), ("scan_off", "<i8"), ("coef_off", "<i8"),
-    ("plane_off", "<i8"),
-    ("int_off", "<i4"), ("unit_off", "<i4"), ("width", "<i4"), ("height", "<i4"), ("rgb", "<i4"),
-    ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart", "<i4"), ("n_intervals", "<i4"), ("n_units", "<i4"),
-    ("h", "<i4", (3,)), ("v", "<i4", (3,)),
-    ("qt", "<u2", (3, 64)), ("lut", "<u2", (6, 512)), ("maxcode", "<i4", (6, 18)), ("valoff", "<i4", (6, 18)),
-    ("huffval", "u1", (6, 256)),
 ], align=True)
 
 
@@ -641,15 +632,19 @@ class RoutePlan:
     sizes: list                    # (width, height) each decodes to
     routes: list                   # "device", "device-progressive", "device-cmyk", "device-layout",
                                    # "device-progressive-cmyk", "device-progressive-layout", "host" or "black"
-    base: list                     # indices of the files of each device group, in input order: odic_jpeg_decode,
-    prog: list                     # odic_jpeg_decode_progressive,
-    four: list                     # odic_jpeg4_decode,
-    lay: list                      # odic_jpeg3_any_decode,
+    base: list                     # indices of the files of each device group (GROUP_KINDS), in input order:
+    prog: list                     # odic_jpeg_decode, odic_jpeg_decode_progressive,
+    own: list                      # odic_jpeg_any_decode (per-component sampling: three and four components together),
     pany: list                     # odic_jpeg_decode_progressive_any
 
     @property
+    def groups(self):
+        """[(kind, file indices)] of the device groups in GROUP_KINDS order, empty ones included."""
+        return [(kind, getattr(self, kind)) for kind in GROUP_KINDS]
+
+    @property
     def order(self):
-        return self.base + self.prog + self.four + self.lay + self.pany
+        return [i for _, idx in self.groups for i in idx]
 
 
 def plan_routes(blobs, progressive="host", draft=None, non_rgb="black", cmyk="host", layouts="common",
@@ -685,24 +680,17 @@ def plan_routes(blobs, progressive="host", draft=None, non_rgb="black", cmyk="ho
     scales = [draft_scale((h.width, h.height), draft) if draft is not None and h.kind != HOST else 1 for h in hdrs]
     sizes = [scaled_size((h.width, h.height), s) for h, s in zip(hdrs, scales)]          # (width, height)
     # an oversized file goes to PIL like a host-kind one: the host path decodes it before its size check fails
-    dev = [i for i, h in enumerate(hdrs)
-           if h.kind == DEVICE and (max_bytes is None or sizes[i][0] * sizes[i][1] * 3 <= max_bytes)]
-    own = lambda h: h.ncomp == 4 or getattr(h, "layout", False)      # every component with its own sampling
-    pany = [i for i in dev if isinstance(hdrs[i], ProgHeader) and own(hdrs[i])]
-    four = [i for i in dev if hdrs[i].ncomp == 4 and i not in pany]
-    lay = [i for i in dev if getattr(hdrs[i], "layout", False) and i not in pany]
-    base = [i for i in dev if not isinstance(hdrs[i], ProgHeader) and not own(hdrs[i])]
-    prog = [i for i in dev if isinstance(hdrs[i], ProgHeader) and i not in pany]
     routes = ["host" if h.kind == DEVICE else h.kind for h in hdrs]          # a device kind left so is oversized
-    for i in dev:
-        routes[i] = "device-progressive" if isinstance(hdrs[i], ProgHeader) else "device"
-    for i in four:
-        routes[i] = "device-cmyk"
-    for i in lay:
-        routes[i] = "device-layout"
-    for i in pany:
-        routes[i] = "device-progressive-cmyk" if hdrs[i].ncomp == 4 else "device-progressive-layout"
-    return RoutePlan(hdrs, scales, sizes, routes, base, prog, four, lay, pany)
+    groups = {kind: [] for kind in GROUP_KINDS}
+    for i, h in enumerate(hdrs):
+        if h.kind != DEVICE or (max_bytes is not None and sizes[i][0] * sizes[i][1] * 3 > max_bytes):
+            continue
+        prog = isinstance(h, ProgHeader)
+        own = h.ncomp == 4 or h.layout                               # every component with its own sampling
+        groups[("pany" if prog else "own") if own else ("prog" if prog else "base")].append(i)
+        routes[i] = ("device" + ("-progressive" if prog else "")
+                     + (("-cmyk" if h.ncomp == 4 else "-layout") if own else ""))
+    return RoutePlan(hdrs, scales, sizes, routes, **groups)
 
 
 _TABLE_CACHE: dict = {}
@@ -791,6 +779,13 @@ def scaled_plane_bytes(h, scale=1):
             for (a, b), (n, _, _) in zip(h.comp_hv, scaled_components(h.comp_hv, scale))]
 
 
+def _per_component(dtype) -> bool:
+    """The record family of a header dtype: per-component (`h` / `v` per component, `ncomp`, `color`; planes at each
+    component's own size, output offsets rounded up to whole words for the colour pass's 32-bit stores) against common
+    (one `sampling` word)."""
+    return "h" in dtype.names
+
+
 def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
     """The per-image part of both packers: geometry, quantisation tables and the output / coefficient / plane offsets
     into record r, the running totals and maxima into tot → (MCUs, output bytes after this image).  The record keeps
@@ -801,17 +796,13 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
         raise ValueError(f"scale must be 1, 2, 4 or 8, not {scale!r}")
     width, height = scaled_size((h.width, h.height), scale)
     nmcu = h.mcus_x * h.mcus_y
-    four = h.ncomp == 4                               # r is a HEADER4_DTYPE record: h, v and ycck instead of sampling
-    own = four or h.layout                            # ... or a HEADER3_DTYPE one: h, v and rgb
+    own = _per_component(r.dtype)
     blocks = nmcu * (sum(a * b for a, b in h.comp_hv) if own else BLOCKS_PER_MCU[h.sampling])
     r["out_off"], r["coef_off"], r["plane_off"] = out_bytes, tot["total_blocks"], tot["total_plane_bytes"]
     r["width"], r["height"] = h.width, h.height
-    if own and "ncomp" in r.dtype.names:              # a PROG_HEADER_ANY_DTYPE record: both kinds, told apart by ncomp
-        r["ncomp"], r["color"] = h.ncomp, int(h.ycck if four else h.rgb)
+    if own:                                           # three or four components, told apart by ncomp
+        r["ncomp"], r["color"] = h.ncomp, int(h.ycck if h.ncomp == 4 else h.rgb)
         r["h"][:h.ncomp], r["v"][:h.ncomp] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv]
-    elif own:
-        r["h"], r["v"] = [a for a, _ in h.comp_hv], [b for _, b in h.comp_hv]
-        r["ycck" if four else "rgb"] = int(h.ycck if four else h.rgb)
     else:
         r["sampling"] = h.sampling
     r["mcus_x"], r["mcus_y"] = h.mcus_x, h.mcus_y
@@ -828,18 +819,17 @@ def _place_image(r, h, tot, out_offs, out_bytes, scale=1):
 
 def pack_headers(hdrs, data_offs, data_ends, subseq_bits, scales=None, dtype=HEADER_DTYPE):
     """Header records + workspace totals for a batch of device-kind headers.
-    dtype=HEADER4_DTYPE: the four-component headers of one odic_jpeg4_decode / odic_jpeg4_decode_scaled call; their
-    output offsets are rounded up to multiples of 4, which lets the colour kernel store whole words.
-    dtype=HEADER3_DTYPE: the `layout` headers of one odic_jpeg3_any_decode / odic_jpeg3_any_decode_scaled call, placed
-    the same way.  With scales these two place the output by `scaled_size` and the planes by `scaled_plane_bytes`.
+    dtype=HEADER_ANY_DTYPE: the four-component and `layout` headers of one odic_jpeg_any_decode /
+    odic_jpeg_any_decode_scaled call; their output offsets are rounded up to multiples of 4, which lets the colour
+    kernel store whole words, and with scales the output is placed by `scaled_size` and the planes by
+    `scaled_plane_bytes`.  The table count, the rounding and the planes follow from the dtype's fields.
     data_offs / data_ends: byte range of each image's entropy data (SOS end .. blob end) inside the batch's data
     buffer.  scales: 1, 2, 4 or 8 per image (None: all 1), the draft scale its output is placed for.
     → (np array of `dtype` [n], dict of batch totals / maxima, list of output byte offsets, output bytes)."""
     n = len(hdrs)
     rec = np.zeros(n, dtype)
-    four = dtype is HEADER4_DTYPE
-    words = four or dtype is HEADER3_DTYPE
-    ndc = 4 if four else 3                            # DC tables 0 .. ndc - 1, AC tables behind them
+    words = _per_component(dtype)
+    ndc = dtype["lut"].shape[0] // 2                  # DC tables 0 .. ndc - 1, AC tables behind them
     tot = dict(total_scan_bytes=0, total_intervals=0, total_units=0, total_blocks=0, total_plane_bytes=0,
                max_units=1, max_intervals=1, max_width=1, max_height=1, max_blocks=1, max_scan_bytes=1)
     out_offs, out_bytes = [], 0
@@ -1072,7 +1062,7 @@ def pack_progressive(hdrs, blob_offs, scales=None, dtype=PROG_HEADER_DTYPE):
     level_first / level_intervals lists, output byte offsets, output bytes)."""
     n = len(hdrs)
     rec = np.zeros(n, dtype)
-    own = dtype is PROG_HEADER_ANY_DTYPE
+    own = _per_component(dtype)
     tot = dict(total_scan_bytes=0, total_intervals=0, total_blocks=0, total_plane_bytes=0, max_width=1, max_height=1,
                max_blocks=1)
     tables, table_ix, flat = [], {}, []
@@ -1134,35 +1124,50 @@ def pad256(n: int) -> int:
     return (n + 255) // 256 * 256
 
 
+#: The device groups of one decode, in the order they are laid out: kind → (header dtype, packed by `pack_progressive`).
+#: "base" / "prog": the common record family (`parse` / `parse_progressive`); "own" / "pany": the per-component one
+#: (cmyk="device" / layouts="all"), three- and four-component files together in input order.
+GROUP_KINDS = {"base": (HEADER_DTYPE, False), "prog": (PROG_HEADER_DTYPE, True),
+               "own": (HEADER_ANY_DTYPE, False), "pany": (PROG_HEADER_ANY_DTYPE, True)}
+COMMON_KINDS = ("base", "prog")
+
+
+@dataclass
+class GroupPlan:
+    """One device group of a `BatchPlan`: the files of one decode call."""
+    kind: str                      # a key of GROUP_KINDS
+    n: int                         # images
+    first: int                     # index of its first image in the plan's image order (scales, out_offs, status)
+    tot: dict                      # the batch totals of `pack_headers` / `pack_progressive`
+    offs: tuple                    # staging offsets of its record sections: (headers,) or (headers, scans, tables)
+    out_off: int                   # where its part of the RGB output starts ...
+    out_bytes: int                 # ... and its bytes
+
+
 @dataclass
 class BatchPlan:
     """One decode batch in the staging buffer that is uploaded in one copy (256-aligned record sections in the order
-    baseline headers, progressive headers / scans / tables, scales, four-component headers; then the files, baseline
-    first, four-component last) and in the output."""
+    baseline headers, progressive headers / scans / tables, scales, then the records of every later group; then the
+    files in group order) and in the output."""
     sections: list                 # [(staging offset, record array)], by offset
     data_off: int                  # the data area: what the records' data_off / data_end count from
-    blobs: list                    # [(staging offset, uint8 array)] of every file, baseline first
+    blobs: list                    # [(staging offset, uint8 array)] of every file, in group order
     total: int                     # staging bytes
-    tot: dict                      # odic_jpeg_batch totals (`pack_headers`); None without baseline files
-    ptot: dict                     # odic_jpeg_prog_batch totals (`pack_progressive`); None without progressive files
-    prog_off: tuple                # staging offsets of the progressive headers, scans, tables; None without them
+    groups: list                   # GroupPlan of every group that has files, in GROUP_KINDS order
     scale_off: int                 # staging offset of int32 scale_log2 [images]; None when every scale is 1
-    out_offs: list                 # byte offset of every image in the RGB output, baseline first
-    out_bytes: int                 # RGB bytes of the baseline files: the progressive output starts here
-    pout_bytes: int                # RGB bytes of the progressive files
-    coef_off: list                 # first coefficient block of every progressive file, then their total
-    ctot: dict = None              # odic_jpeg_batch totals of the four-component files (`pack_headers`); None without them
-    cmyk_off: int = None           # staging offset of their HEADER4_DTYPE records; None without them
-    cout_off: int = 0              # where their part of the RGB output starts (256-aligned) ...
-    cout_bytes: int = 0            # ... and its bytes
-    ltot: dict = None              # the same four for the `layout` files (`parse(..., layouts="all")`, HEADER3_DTYPE), the
-    layout_off: int = None         # last group of all
-    lout_off: int = 0
-    lout_bytes: int = 0
-    atot: dict = None              # the progressive files with per-component sampling (`parse_progressive` with
-    any_off: tuple = None          # cmyk="device" / layouts="all", PROG_HEADER_ANY_DTYPE): odic_jpeg_prog_batch totals,
-    aout_off: int = 0              # staging offsets of their headers, scans, tables, and their part of the output;
-    aout_bytes: int = 0            # behind every other group
+    out_offs: list                 # byte offset of every image in the RGB output, in group order
+    coef_off: list                 # first coefficient block of every "prog" file, then their total
+
+    def group(self, kind):
+        return next((g for g in self.groups if g.kind == kind), None)
+
+    # the two common groups by their earlier names: totals (None without files), the progressive record offsets, and the
+    # bytes of the contiguous output they share (the progressive part starts at out_bytes)
+    tot = property(lambda self: getattr(self.group("base"), "tot", None))
+    ptot = property(lambda self: getattr(self.group("prog"), "tot", None))
+    prog_off = property(lambda self: getattr(self.group("prog"), "offs", None))
+    out_bytes = property(lambda self: getattr(self.group("base"), "out_bytes", 0))
+    pout_bytes = property(lambda self: getattr(self.group("prog"), "out_bytes", 0))
 
     def fill(self, host):
         """Write the sections and the files into the uint8 array `host` of at least `total` bytes."""
@@ -1170,102 +1175,58 @@ class BatchPlan:
             host[o:o + a.nbytes] = a.view(np.uint8)
 
 
-def plan_device_batch(hdrs, blobs, phdrs, pblobs, subseq_bits, scales, chdrs=(), cblobs=(), lhdrs=(),
-                      lblobs=(), ahdrs=(), ablobs=()) -> BatchPlan:
-    """The layout of one device decode of the baseline files (hdrs, blobs: DEVICE-kind `parse` results and their bytes)
-    and the progressive ones (phdrs, pblobs: `parse_progressive`).  scales: the draft scale of every image, baseline
-    first, then progressive and the groups below in their order; a list that ends early means scale 1 for the rest.
-    The int32 scale_log2 section holds the first two groups, or, where a later group has a scale above 1, every image:
-    group g's entries start at 4 · (images before it).
-    Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
-    chdrs, cblobs: the four-component files (`parse(..., "convert", cmyk="device")`, ncomp 4), one more group behind the
-    others: its records behind the scales, its files behind the progressive ones, its output behind theirs from the
-    next multiple of 256.  Without them the plan is what it is without these arguments.
-    lhdrs, lblobs: the `layout` files (`parse(..., layouts="all")`), the last group, placed by the same rule behind the
-    four-component one.
-    ahdrs, ablobs: the progressive files with per-component sampling (`parse_progressive(..., cmyk="device")` /
-    `(..., layouts="all")`), placed by the same rule behind the `layout` group: header, scan and table records behind
-    the others', files behind the others', output from the next multiple of 256.  Without them the plan is what it is
-    without these arguments."""
-    nb, npg, ncm, nly, npa = len(hdrs), len(phdrs), len(chdrs), len(lhdrs), len(ahdrs)
-    n_all = nb + npg + ncm + nly + npa
+def plan_device_batch(groups, subseq_bits, scales) -> BatchPlan:
+    """The layout of one device decode.  groups: [(kind, headers, files as bytes)] in GROUP_KINDS order, each the
+    DEVICE-kind results of `parse` / `parse_progressive` that `plan_routes` sorted into that kind; a group without files
+    may be left out or be empty.  scales: the draft scale of every image in group order; a list that ends early means
+    scale 1 for the rest.  Host arithmetic only: this is what keeps every offset the kernels follow inside the upload.
+    Every group is placed by one rule: its record sections (256-aligned) behind those of the groups before it, its files
+    behind theirs in the data area, its output behind theirs — the two common groups share one contiguous output,
+    every later group starts at the next multiple of 256.  The int32 scale_log2 section lies behind the common groups'
+    records and holds those two groups, or, where a later group has a scale above 1, every image: group g's entries
+    start at 4 · g.first.  A plan of common groups alone does not depend on there being other kinds."""
+    groups = [(kind, list(hdrs), list(blobs)) for kind, hdrs, blobs in groups if len(hdrs)]
+    kinds = [kind for kind, _, _ in groups]
+    if kinds != [kind for kind in GROUP_KINDS if kind in kinds]:
+        raise ValueError(f"groups must be distinct kinds in the order {tuple(GROUP_KINDS)}, not {kinds}")
+    n_all = sum(len(hdrs) for _, hdrs, _ in groups)
+    n_common = sum(len(hdrs) for kind, hdrs, _ in groups if kind in COMMON_KINDS)
     scales = list(scales)[:n_all]
-    scales += [1] * (n_all - len(scales))                # a caller that names only the first two groups: full size
-    if all(s == 1 for s in scales[nb + npg:]):           # the section then holds the first two groups, as without them
-        scales = scales[:nb + npg]
-    cscales = scales[nb + npg:nb + npg + ncm] or None
-    lscales = scales[nb + npg + ncm:nb + npg + ncm + nly] or None
-    ascales = scales[nb + npg + ncm + nly:] or None
-    sections, pos = [], pad256(nb * HEADER_DTYPE.itemsize)
-    ptot = prog_off = scale_off = None
-    if npg:                                              # sizes only, for now: the files' offsets follow from them
-        prec, srec, trec, ptot, pout_offs, pout_bytes = pack_progressive(phdrs, [0] * npg, scales[nb:])
-        prog_off = (pos, pos + pad256(prec.nbytes), pos + pad256(prec.nbytes) + pad256(srec.nbytes))
-        sections = list(zip(prog_off, (prec, srec, trec)))
-        pos = prog_off[2] + pad256(trec.nbytes)
-    if any(s > 1 for s in scales):
-        scale_off = pos
-        sections.append((pos, np.asarray([s.bit_length() - 1 for s in scales], np.int32)))
-        pos += pad256(4 * len(scales))
-    cmyk_off = None
-    if ncm:
-        cmyk_off = pos
-        pos += pad256(ncm * HEADER4_DTYPE.itemsize)
-    layout_off = None
-    if nly:
-        layout_off = pos
-        pos += pad256(nly * HEADER3_DTYPE.itemsize)
-    any_off = None
-    if npa:                                              # sizes only, as for the progressive group above
-        arec, asrec, atrec, atot, aout_offs, aout_bytes = pack_progressive(ahdrs, [0] * npa, ascales,
-                                                                           dtype=PROG_HEADER_ANY_DTYPE)
-        any_off = (pos, pos + pad256(arec.nbytes), pos + pad256(arec.nbytes) + pad256(asrec.nbytes))
-        pos = any_off[2] + pad256(atrec.nbytes)
-    data_off = pos
-    every = list(blobs) + list(pblobs) + list(cblobs) + list(lblobs) + list(ablobs)
-    starts = np.cumsum([0] + [len(b) for b in every]).tolist()                          # inside the data area
-    tot, out_offs, out_bytes = None, [], 0
-    if nb:
-        rec, tot, out_offs, out_bytes = pack_headers(hdrs, [o + h.data_offset for o, h in zip(starts, hdrs)],
-                                                     starts[1:nb + 1], subseq_bits, scales[:nb])
-        sections.insert(0, (0, rec))
-    if npg:
-        shift = np.asarray(starts[nb:nb + npg], np.int64)[srec["image"]]
-        srec["data_off"] += shift
-        srec["data_end"] += shift
-        out_offs = out_offs + [out_bytes + o for o in pout_offs]
-    extra = {}
-    if ncm:
-        first = nb + npg
-        crec, ctot, cout_offs, cout_bytes = pack_headers(
-            chdrs, [o + h.data_offset for o, h in zip(starts[first:], chdrs)], starts[first + 1:first + ncm + 1],
-            subseq_bits, cscales, dtype=HEADER4_DTYPE)
-        sections.append((cmyk_off, crec))
-        cout_off = pad256(out_bytes + (pout_bytes if npg else 0))
-        out_offs = out_offs + [cout_off + o for o in cout_offs]
-        extra = dict(ctot=ctot, cmyk_off=cmyk_off, cout_off=cout_off, cout_bytes=cout_bytes)
-    if nly:
-        first = nb + npg + ncm
-        lrec, ltot, lout_offs, lout_bytes = pack_headers(
-            lhdrs, [o + h.data_offset for o, h in zip(starts[first:], lhdrs)], starts[first + 1:first + nly + 1],
-            subseq_bits, lscales, dtype=HEADER3_DTYPE)
-        sections.append((layout_off, lrec))
-        before = cout_off + cout_bytes if ncm else out_bytes + (pout_bytes if npg else 0)
-        lout_off = pad256(before)
-        out_offs = out_offs + [lout_off + o for o in lout_offs]
-        extra.update(ltot=ltot, layout_off=layout_off, lout_off=lout_off, lout_bytes=lout_bytes)
-    if npa:
-        first = nb + npg + ncm + nly
-        shift = np.asarray(starts[first:first + npa], np.int64)[asrec["image"]]
-        asrec["data_off"] += shift
-        asrec["data_end"] += shift
-        sections += list(zip(any_off, (arec, asrec, atrec)))
-        before = (lout_off + lout_bytes if nly else cout_off + cout_bytes if ncm
-                  else out_bytes + (pout_bytes if npg else 0))
-        aout_off = pad256(before)
-        out_offs = out_offs + [aout_off + o for o in aout_offs]
-        extra.update(atot=atot, any_off=any_off, aout_off=aout_off, aout_bytes=aout_bytes)
-    files = [(data_off + o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, every)]
-    coef_off = [int(x) for x in prec["coef_off"]] + [int(ptot["total_blocks"])] if npg else []
-    return BatchPlan(sections, data_off, files, data_off + starts[-1], tot, ptot, prog_off, scale_off, out_offs,
-                     out_bytes, pout_bytes if npg else 0, coef_off, **extra)
+    scales += [1] * (n_all - len(scales))
+    if all(s == 1 for s in scales[n_common:]):           # the section then holds the common groups, as without the rest
+        scales = scales[:n_common]
+    log2 = np.asarray([s.bit_length() - 1 for s in scales], np.int32) if any(s > 1 for s in scales) else None
+    sections, plans, files, out_offs, coef_off = [], [], [], [], []
+    pos = first = data_end = out_end = 0
+    scale_off = None
+
+    def section(a):
+        nonlocal pos
+        sections.append((pos, a))
+        pos += pad256(a.nbytes)
+        return sections[-1][0]
+
+    for kind, hdrs, blobs in groups:
+        dtype, progressive = GROUP_KINDS[kind]
+        common = kind in COMMON_KINDS
+        if not common and log2 is not None and scale_off is None:
+            scale_off = section(log2)
+        n = len(hdrs)
+        starts = np.cumsum([data_end] + [len(b) for b in blobs]).tolist()               # inside the data area
+        group_scales = scales[first:first + n] or None
+        if progressive:
+            *recs, tot, offs, nbytes = pack_progressive(hdrs, starts[:-1], group_scales, dtype)
+        else:
+            *recs, tot, offs, nbytes = pack_headers(hdrs, [o + h.data_offset for o, h in zip(starts, hdrs)],
+                                                    starts[1:], subseq_bits, group_scales, dtype)
+        out_off = out_end if common else pad256(out_end)
+        plans.append(GroupPlan(kind, n, first, tot, tuple(section(a) for a in recs), out_off, nbytes))
+        out_offs += [out_off + o for o in offs]
+        files += [(o, np.frombuffer(b, np.uint8)) for o, b in zip(starts, blobs)]
+        if kind == "prog":
+            coef_off = [int(x) for x in recs[0]["coef_off"]] + [int(tot["total_blocks"])]
+        first, data_end, out_end = first + n, starts[-1], out_off + nbytes
+    if log2 is not None and scale_off is None:
+        scale_off = section(log2)
+    return BatchPlan(sections, pos, [(pos + o, a) for o, a in files], pos + data_end, plans, scale_off, out_offs,
+                     coef_off)

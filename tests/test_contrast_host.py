@@ -149,7 +149,7 @@ def test_header_declares_and_the_binding_binds_the_entry_point():
                                                       ("int32_t", "min_keep")]
     assert [(n, t) for n, t in _hip.ContrastArgs._fields_] == [("weight", ctypes.c_float), ("log_alpha", ctypes.c_float),
                                                               ("floor", ctypes.c_float), ("min_keep", I32)]
-    assert _hip.ABI_VERSION == 26 and re.search(r"#define ODIC_ABI_VERSION 26\b", text)   # a pure addition
+    assert _hip.ABI_VERSION == 27 and re.search(r"#define ODIC_ABI_VERSION 27\b", text)   # a pure addition
     a = ops.contrast_args(0.5, 0.1, -20.0, 5)
     assert (a.weight, a.floor, a.min_keep) == (0.5, -20.0, 5) and a.log_alpha == float(np.float32(math.log(0.1)))
     assert ops.contrast_args(0.5, 0.0, -20.0, 5).log_alpha == float("-inf") and ops.contrast_args(1, 1.0, 0, 1).log_alpha == 0.0

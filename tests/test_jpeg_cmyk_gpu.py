@@ -1,6 +1,6 @@
 """Four-component (CMYK / YCCK) JPEGs on the device: `decode_jpeg(..., non_rgb="convert", cmyk="device")` against
 `np.asarray(Image.open(f).convert("RGB"))` bit for bit, the conversion stage on its own over every (x, K) pair, a mixed
-batch, the status fallback, EXIF orientation, and the containment of odic_jpeg4_decode."""
+batch, the status fallback, EXIF orientation, and the containment of odic_jpeg_any_decode."""
 import io
 
 import numpy as np
@@ -130,7 +130,7 @@ def test_orientation_tag_6(pre):
 
 
 def test_jpeg4_decode_stays_inside_its_workspace(pre, monkeypatch):
-    """odic_jpeg4_decode on a two-image batch with the workspace, the compressed-data copy, the RGB output and `status` each
+    """odic_jpeg_any_decode on a two-image batch with the workspace, the compressed-data copy, the RGB output and `status` each
     exactly as large as asked for inside a poisoned allocation: nothing outside them is written, nor are the bytes of the
     output that lie between the images (the second image's offset is rounded up to a multiple of 4)."""
     from on_device_image_captioning_amd import image_utils

@@ -1,6 +1,6 @@
 """CPU side of the four-component (CMYK / YCCK) device JPEG route: what `jpeg.parse(..., "convert", cmyk="device")`
-admits and refuses, that the defaults stay what they were, the HEADER4_DTYPE record against a ctypes mirror of
-odic_jpeg_header4, the new symbols, a numpy model of the colour chain against Pillow, and the batch plan's extra group."""
+admits and refuses, that the defaults stay what they were, the HEADER_ANY_DTYPE record against a ctypes mirror of
+odic_jpeg_header_any, the symbols, a numpy model of the colour chain against Pillow, and the batch plan's extra group."""
 import ctypes
 import io
 
@@ -61,43 +61,61 @@ def test_bad_combinations_raise():
             J.parse(blob, "convert", cmyk=bad)
 
 
-class Header4(ctypes.Structure):
-    """odic_jpeg_header4 as include/odic_hip.h declares it."""
+class HeaderAny(ctypes.Structure):
+    """odic_jpeg_header_any as include/odic_hip.h declares it."""
     _fields_ = [(n, ctypes.c_int64) for n in ("data_off", "data_end", "out_off", "scan_off", "coef_off", "plane_off")] + \
-               [(n, ctypes.c_int32) for n in ("int_off", "unit_off", "width", "height", "ycck", "mcus_x", "mcus_y", "restart",
+               [(n, ctypes.c_int32) for n in ("int_off", "unit_off", "width", "height", "color", "mcus_x", "mcus_y", "restart",
                                              "n_intervals", "n_units")] + \
-               [("h", ctypes.c_int32 * 4), ("v", ctypes.c_int32 * 4), ("qt", ctypes.c_uint16 * 64 * 4),
-                ("lut", ctypes.c_uint16 * 512 * 8), ("maxcode", ctypes.c_int32 * 18 * 8), ("valoff", ctypes.c_int32 * 18 * 8),
-                ("huffval", ctypes.c_uint8 * 256 * 8)]
+               [("h", ctypes.c_int32 * 4), ("v", ctypes.c_int32 * 4), ("ncomp", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("qt", ctypes.c_uint16 * 64 * 4), ("lut", ctypes.c_uint16 * 512 * 8), ("maxcode", ctypes.c_int32 * 18 * 8),
+                ("valoff", ctypes.c_int32 * 18 * 8), ("huffval", ctypes.c_uint8 * 256 * 8)]
 
 
-def test_header4_record_matches_the_c_struct():
-    assert J.HEADER4_DTYPE.itemsize == ctypes.sizeof(Header4) == 12024     # the static_assert in csrc/jpeg_decode.hip
-    assert list(J.HEADER4_DTYPE.names) == [n for n, _ in Header4._fields_]
-    for name, _ in Header4._fields_:
-        dt, off = J.HEADER4_DTYPE.fields[name][:2]
-        f = getattr(Header4, name)
+def test_header_any_record_matches_the_c_struct():
+    """The one per-component baseline record (it replaces the four- and the three-component records and their two tests):
+    field names, offsets and size against the ctypes mirror, the numbers of the static_assert in csrc/jpeg_decode.hip,
+    and the shared prefix at HEADER_DTYPE's offsets."""
+    D = J.HEADER_ANY_DTYPE
+    assert D.itemsize == ctypes.sizeof(HeaderAny) == 12032               # the static_assert in csrc/jpeg_decode.hip
+    assert list(D.names) == [n for n, _ in HeaderAny._fields_]
+    for name, _ in HeaderAny._fields_:
+        dt, off = D.fields[name][:2]
+        f = getattr(HeaderAny, name)
         assert (off, dt.itemsize) == (f.offset, f.size), name
-    # the fields both records have sit at the same offsets up to `sampling` / `ycck`, so the templated kernels read alike
-    for name in J.HEADER_DTYPE.names[:10]:
-        assert J.HEADER4_DTYPE.fields[name][1] == J.HEADER_DTYPE.fields[name][1]
+    assert (D.fields["h"][1], D.fields["ncomp"][1], D.fields["qt"][1], D.fields["huffval"][1]) == (88, 120, 128, 9984)
+    # the fields both records have sit at the same offsets up to `sampling` / `color`, and the five behind it too, so the
+    # templated kernels read alike
+    for name in J.HEADER_DTYPE.names[:10] + J.HEADER_DTYPE.names[11:16]:
+        assert D.fields[name][1] == J.HEADER_DTYPE.fields[name][1]
+    assert D.names[10] == "color" and D.fields["color"][1] == J.HEADER_DTYPE.fields["sampling"][1]
     assert J.HEADER_DTYPE.itemsize == 9016
+    # one rule for the word and the frame in both per-component records
+    P = J.PROG_HEADER_ANY_DTYPE
+    assert all(D.fields[n][0] == P.fields[n][0] for n in ("color", "ncomp", "h", "v", "qt"))
+    assert D.fields["v"][1] - D.fields["h"][1] == 16 == D.fields["ncomp"][1] - D.fields["v"][1]
+
+
+REMOVED = ("odic_jpeg4_workspace_bytes", "odic_jpeg4_decode", "odic_jpeg4_decode_scaled", "odic_jpeg3_any_workspace_bytes",
+           "odic_jpeg3_any_decode", "odic_jpeg3_any_decode_scaled")
 
 
 def test_abi_version_and_new_symbols():
     from on_device_image_captioning_amd import _hip
     lib = _hip.load()
-    assert lib.odic_abi_version() == 26 == _hip.ABI_VERSION
-    for name in ("odic_jpeg4_workspace_bytes", "odic_jpeg4_decode", "odic_cmyk_to_rgb8"):
+    assert lib.odic_abi_version() == 27 == _hip.ABI_VERSION
+    for name in ("odic_jpeg_any_workspace_bytes", "odic_jpeg_any_decode", "odic_cmyk_to_rgb8"):
         assert name in _hip.EXPORTED_SYMBOLS and getattr(lib, name).argtypes is not None
-    assert lib.odic_jpeg4_decode(None, None, 0, None) == -2
-    assert lib.odic_jpeg4_workspace_bytes(None) == 0
+    assert lib.odic_jpeg_any_decode(None, None, 0, None) == -2
+    assert lib.odic_jpeg_any_workspace_bytes(None) == 0
     assert lib.odic_cmyk_to_rgb8(None, None, 4, 1, None) == -2
     assert lib.odic_cmyk_to_rgb8(16, 16, -1, 1, None) == -1
     assert lib.odic_cmyk_to_rgb8(16, 16, 0, 1, None) == 0                  # nothing to do, nothing launched
     with open(_hip.LIB_PATH.replace("on_device_image_captioning_amd/libodic_hip.so", "include/odic_hip.h")) as f:
         header = f.read()
-    assert "#define ODIC_ABI_VERSION 26" in header and "} odic_jpeg_header4;" in header
+    assert "#define ODIC_ABI_VERSION 27" in header and "} odic_jpeg_header_any;" in header
+    raw = ctypes.CDLL(_hip.LIB_PATH)
+    for name in REMOVED:                                                  # gone from the library, the table and the header
+        assert name not in _hip.EXPORTED_SYMBOLS and not hasattr(raw, name) and name + "(" not in header
 
 
 def test_cmyk_to_rgb_model_is_pillows_on_every_pair():
@@ -137,9 +155,9 @@ def test_batch_plan_lists_the_group_only_when_a_file_is_there():
     names = ["cmyk-sub2-17x33", "photoshop-ycck-2x2-7x9"]
     cblobs = [K.CASES[n][0] for n in names]
     chdrs = [J.parse(b, "convert", cmyk="device") for b in cblobs]
-    plain = J.plan_device_batch(hdrs, BASE, [], [], 2048, [1])
-    same = J.plan_device_batch(hdrs, BASE, [], [], 2048, [1], [], [])
-    assert plain.ctot is None and plain.cmyk_off is None and plain.cout_bytes == 0
+    plain = J.plan_device_batch([("base", hdrs, BASE)], 2048, [1])
+    same = J.plan_device_batch([("base", hdrs, BASE), ("prog", [], []), ("own", [], []), ("pany", [], [])], 2048, [1])
+    assert plain.group("own") is None and [g.kind for g in plain.groups] == ["base"] == [g.kind for g in same.groups]
     assert [a.dtype for _, a in plain.sections] == [J.HEADER_DTYPE]
     host_a, host_b = np.zeros(plain.total, np.uint8), np.zeros(same.total, np.uint8)
     plain.fill(host_a)
@@ -147,28 +165,30 @@ def test_batch_plan_lists_the_group_only_when_a_file_is_there():
     assert plain.total == same.total and np.array_equal(host_a, host_b) and plain.out_offs == same.out_offs
 
     for base_h, base_b in ((hdrs, BASE), ([], [])):
-        p = J.plan_device_batch(base_h, base_b, [], [], 2048, [1] * len(base_h), chdrs, cblobs)
-        assert [a.dtype for _, a in p.sections] == [J.HEADER_DTYPE] * len(base_h) + [J.HEADER4_DTYPE]
+        p = J.plan_device_batch([("base", base_h, base_b), ("own", chdrs, cblobs)], 2048, [1] * len(base_h))
+        g = p.group("own")
+        assert (g.n, g.first) == (2, len(base_h))
+        assert [a.dtype for _, a in p.sections] == [J.HEADER_DTYPE] * len(base_h) + [J.HEADER_ANY_DTYPE]
         spans = [(o, o + a.nbytes) for o, a in p.sections] + [(p.data_off, p.total)]
         assert all(lo % 256 == 0 for lo, _ in spans) and spans == sorted(spans)
         assert all(a_hi <= b_lo for (_, a_hi), (b_lo, _) in zip(spans, spans[1:]))
-        assert p.sections[-1][0] == p.cmyk_off
+        assert (p.sections[-1][0],) == g.offs
         host = np.full(p.total + 16, 0xA5, np.uint8)
         p.fill(host)
         assert (host[p.total:] == 0xA5).all()
-        rec = host[p.cmyk_off:p.cmyk_off + 2 * J.HEADER4_DTYPE.itemsize].view(J.HEADER4_DTYPE)
+        rec = host[g.offs[0]:g.offs[0] + 2 * J.HEADER_ANY_DTYPE.itemsize].view(J.HEADER_ANY_DTYPE)
         nb = len(base_h)
         for r, h, (o, _), blob in zip(rec, chdrs, p.blobs[nb:], cblobs):
             lo, hi = p.data_off + int(r["data_off"]), p.data_off + int(r["data_end"])
             assert (lo, hi) == (o + h.data_offset, o + len(blob)) and host[lo:hi].tobytes() == blob[h.data_offset:]
-            assert list(zip(r["h"], r["v"])) == h.comp_hv and bool(r["ycck"]) == h.ycck
+            assert list(zip(r["h"], r["v"])) == h.comp_hv and bool(r["color"]) == h.ycck and r["ncomp"] == 4
             assert int(r["out_off"]) % 4 == 0
         # the output: the group starts on a multiple of 256 behind the others' bytes, images do not overlap
-        assert p.cout_off % 256 == 0 and p.cout_off >= p.out_bytes + p.pout_bytes
-        assert p.out_offs[nb:] == [p.cout_off + int(o) for o in rec["out_off"]]
+        assert g.out_off % 256 == 0 and g.out_off >= p.out_bytes + p.pout_bytes
+        assert p.out_offs[nb:] == [g.out_off + int(o) for o in rec["out_off"]]
         ends = [o + h.width * h.height * 3 for o, h in zip(p.out_offs[nb:], chdrs)]
-        assert all(e <= o for e, o in zip(ends, p.out_offs[nb + 1:])) and ends[-1] == p.cout_off + p.cout_bytes
+        assert all(e <= o for e, o in zip(ends, p.out_offs[nb + 1:])) and ends[-1] == g.out_off + g.out_bytes
         # workspace totals: 64 plane bytes and one coefficient block per block of every component
         blocks = [h.mcus_x * h.mcus_y * sum(a * b for a, b in h.comp_hv) for h in chdrs]
-        assert p.ctot["total_blocks"] == sum(blocks) and p.ctot["total_plane_bytes"] == 64 * sum(blocks)
-        assert p.ctot["max_blocks"] == max(blocks)
+        assert g.tot["total_blocks"] == sum(blocks) and g.tot["total_plane_bytes"] == 64 * sum(blocks)
+        assert g.tot["max_blocks"] == max(blocks)

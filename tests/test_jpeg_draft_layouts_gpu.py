@@ -1,7 +1,7 @@
 """Draft-scale decode of CMYK / YCCK and any-layout JPEGs on the device: `decode_jpeg(..., draft=, draft_layouts="all")`
 against the host route and against Pillow's drafted `convert("RGB")` bit for bit — a mixed batch that holds scales 1, 2, 4
 and 8 at once, the full case list of jpeg_draft_layout_model (baseline and progressive, with and without restart
-intervals), regions and EXIF orientation on the drafted image, the three _scaled entry points' treatment of a null or
+intervals), regions and EXIF orientation on the drafted image, the two _scaled entry points' treatment of a null or
 invalid scale, and the default's routes."""
 import ctypes
 import io
@@ -226,9 +226,8 @@ def test_a_null_scale_array_is_refused(pre):
     b.max_units = b.max_intervals = b.max_width = b.max_height = 1
     b.max_blocks = b.max_scan_bytes = b.total_scan_bytes = b.total_intervals = b.total_units = 1
     b.total_blocks = b.total_plane_bytes = 1
-    need = lib.odic_jpeg4_workspace_bytes(ctypes.byref(b))
-    assert lib.odic_jpeg4_decode_scaled(ctypes.byref(b), None, 16, need, None) == -2
-    assert lib.odic_jpeg3_any_decode_scaled(ctypes.byref(b), None, 16, need, None) == -2
+    need = lib.odic_jpeg_any_workspace_bytes(ctypes.byref(b))
+    assert need > 0 and lib.odic_jpeg_any_decode_scaled(ctypes.byref(b), None, 16, need, None) == -2
     p = hip.JpegProgBatch()
     p.headers = p.scans = p.tables = p.data = p.out = p.status = 16
     assert lib.odic_jpeg_decode_progressive_any_scaled(ctypes.byref(p), None, 16, 1 << 20, None) == -2

@@ -116,7 +116,7 @@ def _ranges(hdrs, blobs):
 
 @pytest.mark.parametrize("kind", ["layout", "cmyk"])
 def test_baseline_packers_place_a_mixed_scale_batch(kind):
-    names, dtype = (PACK, J.HEADER3_DTYPE) if kind == "layout" else (PACK4, J.HEADER4_DTYPE)
+    names, dtype = (PACK if kind == "layout" else PACK4), J.HEADER_ANY_DTYPE
     cases = [M.CASES[n] for n, _ in names]
     scales = [s for _, s in names]
     blobs = [c.baseline() for c in cases]
@@ -155,7 +155,9 @@ def test_plan_carries_the_scales_of_every_group():
     ch, lh = ([J.parse(b, **k) for b, k in zip(g, kw)] for g, kw in zip(groups[:2], kws[:2]))
     ah = [J.parse_progressive(b, **k) for b, k in zip(groups[2], kws[2])]
     scales = [2, 4, 8, 1]
-    p = J.plan_device_batch([], [], [], [], 2048, scales, ch, groups[0], lh, groups[1], ahdrs=ah, ablobs=groups[2])
+    own_pany = [("own", ch + lh, groups[0] + groups[1]), ("pany", ah, groups[2])]
+    p = J.plan_device_batch(own_pany, 2048, scales)
+    own, pany = p.group("own"), p.group("pany")
     assert p.scale_off is not None and p.scale_off % 256 == 0
     sec = dict(p.sections)
     assert list(sec[p.scale_off]) == [1, 2, 3, 0]
@@ -164,13 +166,15 @@ def test_plan_carries_the_scales_of_every_group():
     every = ch + lh + ah
     sizes = [J.scaled_size((h.width, h.height), s) for h, s in zip(every, scales)]
     assert all(o % 4 == 0 for o in p.out_offs)
-    for (w, h), a, b in zip(sizes, p.out_offs, p.out_offs[1:] + [p.aout_off + p.aout_bytes]):
+    for (w, h), a, b in zip(sizes, p.out_offs, p.out_offs[1:] + [pany.out_off + pany.out_bytes]):
         assert a + w * h * 3 <= b
-    assert (p.cout_bytes, p.lout_bytes) == tuple(w * h * 3 for w, h in sizes[:2])
-    assert (p.ctot["max_width"], p.ctot["max_height"]) == sizes[0] and (p.ltot["max_width"], p.ltot["max_height"]) == sizes[1]
+    first, second = (w * h * 3 for w, h in sizes[:2])      # one group now: the second image on the next whole word
+    assert own.out_bytes == (first + 3) // 4 * 4 + second and p.out_offs[:2] == [own.out_off, own.out_off + (first + 3) // 4 * 4]
+    assert (own.tot["max_width"], own.tot["max_height"]) == tuple(max(a, b) for a, b in zip(sizes[0], sizes[1]))
+    assert pany.out_off == J.pad256(own.out_off + own.out_bytes) and (own.first, pany.first) == (0, 2)
     # full size: the plan of the call without scales, with no scale section
-    q = J.plan_device_batch([], [], [], [], 2048, [], ch, groups[0], lh, groups[1], ahdrs=ah, ablobs=groups[2])
-    one = J.plan_device_batch([], [], [], [], 2048, [1] * 4, ch, groups[0], lh, groups[1], ahdrs=ah, ablobs=groups[2])
+    q = J.plan_device_batch(own_pany, 2048, [])
+    one = J.plan_device_batch(own_pany, 2048, [1] * 4)
     assert q.scale_off is None and one.scale_off is None and q.total == one.total and q.out_offs == one.out_offs
 
 
@@ -224,15 +228,14 @@ def test_all_plans_them_as_their_device_routes_at_the_draft_scale():
         assert rp.routes == ["device"] + OWN_ROUTES
         assert rp.scales == [J.draft_scale((93, 67), req)] * 5 == [s] * 5
         assert rp.sizes == [J.scaled_size((93, 67), s)] * 5
-        assert (rp.base, rp.lay, rp.four, rp.pany, rp.prog) == ([0], [1], [2], [3, 4], [])
+        assert (rp.base, rp.own, rp.pany, rp.prog) == ([0], [1, 2], [3, 4], [])
+        assert [rp.hdrs[i].ncomp for i in rp.own] == [3, 4]              # the layout and the cmyk file, in input order
         order = rp.order
-        plan = J.plan_device_batch([rp.hdrs[i] for i in rp.base], [blobs[i] for i in rp.base], [], [], 2048,
-                                   [rp.scales[i] for i in order],
-                                   [rp.hdrs[i] for i in rp.four], [blobs[i] for i in rp.four],
-                                   [rp.hdrs[i] for i in rp.lay], [blobs[i] for i in rp.lay],
-                                   ahdrs=[rp.hdrs[i] for i in rp.pany], ablobs=[blobs[i] for i in rp.pany])
+        plan = J.plan_device_batch([(kind, [rp.hdrs[i] for i in idx], [blobs[i] for i in idx]) for kind, idx in rp.groups],
+                                   2048, [rp.scales[i] for i in order])
         w, h = rp.sizes[0]
-        assert (plan.cout_bytes, plan.lout_bytes, plan.aout_bytes) == (w * h * 3, w * h * 3, (w * h * 3 + 3) // 4 * 4 + w * h * 3)
+        two = (w * h * 3 + 3) // 4 * 4 + w * h * 3
+        assert (plan.group("own").out_bytes, plan.group("pany").out_bytes) == (two, two)
         if s > 1:
             assert list(dict(plan.sections)[plan.scale_off]) == [s.bit_length() - 1] * 5
         else:
@@ -259,7 +262,7 @@ def lib():
 def test_scaled_entry_points_are_exported_and_reject_null_arguments(lib):
     from on_device_image_captioning_amd import _hip
     header = open(os.path.join(H.ROOT, "include", "odic_hip.h")).read()
-    names = ("odic_jpeg4_decode_scaled", "odic_jpeg3_any_decode_scaled", "odic_jpeg_decode_progressive_any_scaled")
+    names = ("odic_jpeg_any_decode_scaled", "odic_jpeg_decode_progressive_any_scaled")
     for name in names:
         assert name in _hip.EXPORTED_SYMBOLS and len(getattr(lib, name).argtypes) == 5
         assert f"int {name}(" in header and header.index(name) < header.index("#define ODIC_ABI_VERSION")   # history line
@@ -270,8 +273,7 @@ def test_scaled_entry_points_are_exported_and_reject_null_arguments(lib):
     b.max_units = b.max_intervals = b.max_width = b.max_height = 1
     b.max_blocks = b.max_scan_bytes = b.total_scan_bytes = b.total_intervals = b.total_units = 1
     b.total_blocks = b.total_plane_bytes = 1
-    for name, query in (("odic_jpeg4_decode_scaled", lib.odic_jpeg4_workspace_bytes),
-                        ("odic_jpeg3_any_decode_scaled", lib.odic_jpeg3_any_workspace_bytes)):
+    for name, query in (("odic_jpeg_any_decode_scaled", lib.odic_jpeg_any_workspace_bytes),):
         fn, need = getattr(lib, name), query(ctypes.byref(b))
         assert need > 0
         assert fn(ctypes.byref(b), None, 16, need, None) == -2         # null scale_log2

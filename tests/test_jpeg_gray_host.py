@@ -173,7 +173,7 @@ def test_plan_of_a_batch_mixing_gray_and_colour(scales):
     hdrs = [J.parse(b, "convert") for b in blobs]
     phdrs = [J.parse_progressive(b, "convert") for b in pblobs]
     assert [h.sampling for h in hdrs + phdrs] == [3, 2, 3, 3, 0]
-    p = J.plan_device_batch(hdrs, blobs, phdrs, pblobs, 2048, scales)
+    p = J.plan_device_batch([("base", hdrs, blobs), ("prog", phdrs, pblobs)], 2048, scales)
     rec = p.sections[0][1]
     prec = dict(p.sections)[p.prog_off[0]]
     assert rec.dtype == J.HEADER_DTYPE and prec.dtype == J.PROG_HEADER_DTYPE

@@ -1,5 +1,5 @@
 """CPU side of the layouts="all" device JPEG route: what `jpeg.parse(f, layouts="all")` admits and refuses, that the default
-stays what it was, the HEADER3_DTYPE record against a ctypes mirror of odic_jpeg_header3, the new symbols, a numpy model
+stays what it was, the symbols (the HEADER_ANY_DTYPE record is checked in test_jpeg_cmyk_host), a numpy model
 of the whole tail (IDCT planes from the writer's coefficients, libjpeg's upsampling rule per component, colour) against
 Pillow on every case, and the batch plan's extra group."""
 import ctypes
@@ -76,38 +76,17 @@ def test_check_layouts():
             J.parse(L.CASES["440-7x9"].blob, layouts=bad)
 
 
-class Header3(ctypes.Structure):
-    """odic_jpeg_header3 as include/odic_hip.h declares it."""
-    _fields_ = [(n, ctypes.c_int64) for n in ("data_off", "data_end", "out_off", "scan_off", "coef_off", "plane_off")] + \
-               [(n, ctypes.c_int32) for n in ("int_off", "unit_off", "width", "height", "rgb", "mcus_x", "mcus_y", "restart",
-                                             "n_intervals", "n_units")] + \
-               [("h", ctypes.c_int32 * 3), ("v", ctypes.c_int32 * 3), ("qt", ctypes.c_uint16 * 64 * 3),
-                ("lut", ctypes.c_uint16 * 512 * 6), ("maxcode", ctypes.c_int32 * 18 * 6), ("valoff", ctypes.c_int32 * 18 * 6),
-                ("huffval", ctypes.c_uint8 * 256 * 6)]
-
-
-def test_header3_record_matches_the_c_struct():
-    assert J.HEADER3_DTYPE.itemsize == ctypes.sizeof(Header3) == 9040      # the static_assert in csrc/jpeg_decode.hip
-    assert list(J.HEADER3_DTYPE.names) == [n for n, _ in Header3._fields_]
-    for name, _ in Header3._fields_:
-        dt, off = J.HEADER3_DTYPE.fields[name][:2]
-        f = getattr(Header3, name)
-        assert (off, dt.itemsize) == (f.offset, f.size), name
-    for name in J.HEADER_DTYPE.names[:10]:                 # the common prefix the templated kernels read
-        assert J.HEADER3_DTYPE.fields[name][1] == J.HEADER_DTYPE.fields[name][1]
-    for name in ("mcus_x", "mcus_y", "restart", "n_intervals", "n_units", "h"):
-        assert J.HEADER3_DTYPE.fields[name][1] == J.HEADER4_DTYPE.fields[name][1]
-    assert J.HEADER_DTYPE.itemsize == 9016 and J.HEADER4_DTYPE.itemsize == 12024
-
-
 def test_abi_version_and_new_symbols():
     from on_device_image_captioning_amd import _hip
+    from test_jpeg_cmyk_host import REMOVED
     lib = _hip.load()
-    assert lib.odic_abi_version() == 26 == _hip.ABI_VERSION
-    for name in ("odic_jpeg3_any_workspace_bytes", "odic_jpeg3_any_decode"):
+    assert lib.odic_abi_version() == 27 == _hip.ABI_VERSION
+    for name in ("odic_jpeg_any_workspace_bytes", "odic_jpeg_any_decode", "odic_jpeg_any_decode_scaled"):
         assert name in _hip.EXPORTED_SYMBOLS and getattr(lib, name).argtypes is not None
-    assert lib.odic_jpeg3_any_decode(None, None, 0, None) == -2
-    assert lib.odic_jpeg3_any_workspace_bytes(None) == 0
+    assert lib.odic_jpeg_any_decode(None, None, 0, None) == -2
+    assert lib.odic_jpeg_any_workspace_bytes(None) == 0
+    raw = ctypes.CDLL(_hip.LIB_PATH)
+    assert not any(name in _hip.EXPORTED_SYMBOLS or hasattr(raw, name) for name in REMOVED)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -180,9 +159,9 @@ BASE = [encode(smooth_rgb(16, 16, seed=1), quality=90, subsampling=0)]
 def test_batch_plan_lists_the_group_only_when_a_file_is_there():
     hdrs = [J.parse(b, layouts="all") for b in BASE]
     assert all(same(a, J.parse(b)) for a, b in zip(hdrs, BASE))
-    plain = J.plan_device_batch(hdrs, BASE, [], [], 2048, [1])
-    empty = J.plan_device_batch(hdrs, BASE, [], [], 2048, [1], [], [], [], [])
-    assert plain.ltot is None and plain.layout_off is None and plain.lout_bytes == 0
+    plain = J.plan_device_batch([("base", hdrs, BASE)], 2048, [1])
+    empty = J.plan_device_batch([("base", hdrs, BASE), ("prog", [], []), ("own", [], [])], 2048, [1])
+    assert plain.group("own") is None and empty.group("own") is None and len(empty.groups) == 1
     assert [a.dtype for _, a in plain.sections] == [J.HEADER_DTYPE]
     host_a, host_b = np.zeros(plain.total, np.uint8), np.zeros(empty.total, np.uint8)
     plain.fill(host_a)
@@ -193,50 +172,70 @@ def test_batch_plan_lists_the_group_only_when_a_file_is_there():
     lblobs = [L.CASES[n].blob for n in names]
     lhdrs = [J.parse(b, layouts="all") for b in lblobs]
     for base_h, base_b in ((hdrs, BASE), ([], [])):
-        p = J.plan_device_batch(base_h, base_b, [], [], 2048, [1] * len(base_h), [], [], lhdrs, lblobs)
-        assert [a.dtype for _, a in p.sections] == [J.HEADER_DTYPE] * len(base_h) + [J.HEADER3_DTYPE]
+        p = J.plan_device_batch([("base", base_h, base_b), ("own", lhdrs, lblobs)], 2048, [1] * len(base_h))
+        g = p.group("own")
+        assert (g.n, g.first) == (3, len(base_h))
+        assert [a.dtype for _, a in p.sections] == [J.HEADER_DTYPE] * len(base_h) + [J.HEADER_ANY_DTYPE]
         spans = [(o, o + a.nbytes) for o, a in p.sections] + [(p.data_off, p.total)]
         assert all(lo % 256 == 0 for lo, _ in spans) and spans == sorted(spans)
         assert all(a_hi <= b_lo for (_, a_hi), (b_lo, _) in zip(spans, spans[1:]))
-        assert p.sections[-1][0] == p.layout_off and p.cmyk_off is None
+        assert (p.sections[-1][0],) == g.offs
         host = np.full(p.total + 16, 0xA5, np.uint8)
         p.fill(host)
         assert (host[p.total:] == 0xA5).all()
-        rec = host[p.layout_off:p.layout_off + 3 * J.HEADER3_DTYPE.itemsize].view(J.HEADER3_DTYPE)
+        rec = host[g.offs[0]:g.offs[0] + 3 * J.HEADER_ANY_DTYPE.itemsize].view(J.HEADER_ANY_DTYPE)
         nb = len(base_h)
         for r, h, (o, _), blob in zip(rec, lhdrs, p.blobs[nb:], lblobs):
             lo, hi = p.data_off + int(r["data_off"]), p.data_off + int(r["data_end"])
             assert (lo, hi) == (o + h.data_offset, o + len(blob)) and host[lo:hi].tobytes() == blob[h.data_offset:]
-            assert list(zip(r["h"], r["v"])) == h.comp_hv and bool(r["rgb"]) == h.rgb
+            assert list(zip(r["h"][:3], r["v"][:3])) == h.comp_hv and bool(r["color"]) == h.rgb and r["ncomp"] == 3
+            assert (r["h"][3], r["v"][3]) == (0, 0) and not r["lut"][3].any() and not r["lut"][7].any()
             assert (int(r["mcus_x"]), int(r["mcus_y"])) == (h.mcus_x, h.mcus_y)
             assert int(r["out_off"]) % 4 == 0
-        assert p.lout_off % 256 == 0 and p.lout_off >= p.out_bytes + p.pout_bytes
-        assert p.out_offs[nb:] == [p.lout_off + int(o) for o in rec["out_off"]]
+        assert g.out_off % 256 == 0 and g.out_off >= p.out_bytes + p.pout_bytes
+        assert p.out_offs[nb:] == [g.out_off + int(o) for o in rec["out_off"]]
         ends = [o + h.width * h.height * 3 for o, h in zip(p.out_offs[nb:], lhdrs)]
-        assert all(e <= o for e, o in zip(ends, p.out_offs[nb + 1:])) and ends[-1] == p.lout_off + p.lout_bytes
+        assert all(e <= o for e, o in zip(ends, p.out_offs[nb + 1:])) and ends[-1] == g.out_off + g.out_bytes
         blocks = [h.mcus_x * h.mcus_y * sum(a * b for a, b in h.comp_hv) for h in lhdrs]
-        assert p.ltot["total_blocks"] == sum(blocks) and p.ltot["total_plane_bytes"] == 64 * sum(blocks)
-        assert p.ltot["max_blocks"] == max(blocks)
+        assert g.tot["total_blocks"] == sum(blocks) and g.tot["total_plane_bytes"] == 64 * sum(blocks)
+        assert g.tot["max_blocks"] == max(blocks)
 
 
-def test_batch_plan_places_the_group_behind_the_four_component_one():
+def test_batch_plan_holds_both_kinds_in_the_one_own_group():
+    """A four-component and a `layout` file are one "own" group (they were two groups, the second placed behind the
+    first): the first file's placement does not depend on the second, the two lie side by side in one record section and
+    one stretch of the output, and the group's totals are the sums and maxima over both."""
     import jpeg_cmyk_cases as K
     cblobs = [K.CASES["cmyk-sub2-17x33"][0]]
     chdrs = [J.parse(b, "convert", cmyk="device", layouts="all") for b in cblobs]
     lblobs = [L.CASES["411-17x33"].blob]
     lhdrs = [J.parse(b, "convert", cmyk="device", layouts="all") for b in lblobs]
     hdrs = [J.parse(b) for b in BASE]
-    only = J.plan_device_batch(hdrs, BASE, [], [], 2048, [1], chdrs, cblobs)
-    p = J.plan_device_batch(hdrs, BASE, [], [], 2048, [1], chdrs, cblobs, lhdrs, lblobs)
-    assert [a.dtype for _, a in p.sections] == [J.HEADER_DTYPE, J.HEADER4_DTYPE, J.HEADER3_DTYPE]
-    assert (p.cmyk_off, p.cout_off, p.cout_bytes, p.out_offs[:2]) == (only.cmyk_off, only.cout_off, only.cout_bytes,
-                                                                      only.out_offs)
-    assert p.layout_off == p.cmyk_off + J.pad256(J.HEADER4_DTYPE.itemsize)
-    assert p.lout_off == J.pad256(p.cout_off + p.cout_bytes) and p.out_offs[2] == p.lout_off
+    only = J.plan_device_batch([("base", hdrs, BASE), ("own", chdrs, cblobs)], 2048, [1])
+    p = J.plan_device_batch([("base", hdrs, BASE), ("own", chdrs + lhdrs, cblobs + lblobs)], 2048, [1])
+    g, og = p.group("own"), only.group("own")
+    assert [a.dtype for _, a in p.sections] == [J.HEADER_DTYPE, J.HEADER_ANY_DTYPE] and [x.kind for x in p.groups] == ["base", "own"]
+    assert (g.offs, g.out_off, g.first, p.out_offs[:2]) == (og.offs, og.out_off, og.first, only.out_offs)
+    assert g.offs[0] % 256 == 0 and g.out_off == J.pad256(p.out_bytes) and (g.n, og.n) == (2, 1)
+    # the second image behind the first, on a whole word, inside the group's bytes; nothing overlaps
+    assert p.out_offs[2] == g.out_off + (og.out_bytes + 3) // 4 * 4 and p.out_offs[2] % 4 == 0
+    assert p.out_offs[2] >= p.out_offs[1] + chdrs[0].width * chdrs[0].height * 3
+    assert p.out_offs[2] + lhdrs[0].width * lhdrs[0].height * 3 == g.out_off + g.out_bytes
     host = np.zeros(p.total, np.uint8)
     p.fill(host)
-    c4 = host[p.cmyk_off:p.cmyk_off + J.HEADER4_DTYPE.itemsize].view(J.HEADER4_DTYPE)[0]
-    l3 = host[p.layout_off:p.layout_off + J.HEADER3_DTYPE.itemsize].view(J.HEADER3_DTYPE)[0]
-    for r, h, blob in ((c4, chdrs[0], cblobs[0]), (l3, lhdrs[0], lblobs[0])):
+    rec = host[g.offs[0]:g.offs[0] + 2 * J.HEADER_ANY_DTYPE.itemsize].view(J.HEADER_ANY_DTYPE)
+    assert g.offs[0] + rec.nbytes <= p.data_off and list(rec["ncomp"]) == [4, 3]
+    spans = []
+    for r, h, blob in zip(rec, chdrs + lhdrs, cblobs + lblobs):
         lo, hi = p.data_off + int(r["data_off"]), p.data_off + int(r["data_end"])
         assert host[lo:hi].tobytes() == blob[h.data_offset:]
+        assert list(zip(r["h"][:h.ncomp], r["v"][:h.ncomp])) == h.comp_hv
+        spans.append((lo, hi))
+    assert spans[0][1] <= spans[1][0] and spans[1][1] == p.total
+    # coefficient blocks and planes of the second image start where the first one's end
+    blocks = [h.mcus_x * h.mcus_y * sum(a * b for a, b in h.comp_hv) for h in chdrs + lhdrs]
+    assert list(rec["coef_off"]) == [0, blocks[0]] and list(rec["plane_off"]) == [0, 64 * blocks[0]]
+    assert g.tot["total_blocks"] == sum(blocks) == og.tot["total_blocks"] + blocks[1]
+    assert g.tot["total_plane_bytes"] == 64 * sum(blocks) and g.tot["max_blocks"] == max(blocks)
+    assert g.tot["max_width"] == max(h.width for h in chdrs + lhdrs)
+    assert g.tot["max_height"] == max(h.height for h in chdrs + lhdrs)

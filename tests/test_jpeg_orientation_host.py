@@ -186,7 +186,7 @@ def lib():
 def test_abi_stays_26_and_header_and_binding_agree(lib):
     from on_device_image_captioning_amd import _hip
     text = open(HEADER).read()
-    assert _hip.ABI_VERSION == 26 == lib.odic_abi_version() and re.search(r"#define ODIC_ABI_VERSION 26\b", text)
+    assert _hip.ABI_VERSION == 27 == lib.odic_abi_version() and re.search(r"#define ODIC_ABI_VERSION 27\b", text)
     assert "odic_orient_rgb8" in _hip.EXPORTED_SYMBOLS and hasattr(ctypes.CDLL(_hip.LIB_PATH), "odic_orient_rgb8")
     bare = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     proto = re.search(r"int odic_orient_rgb8\((.*?)\);", bare, flags=re.S).group(1)

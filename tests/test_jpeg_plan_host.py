@@ -28,7 +28,7 @@ def plan_of(blobs, pblobs, scales):
     hdrs, phdrs = [J.parse(b) for b in blobs], [J.parse_progressive(b) for b in pblobs]
     assert all(h.kind == J.DEVICE for h in hdrs + phdrs)
     assert all(not isinstance(h, J.ProgHeader) for h in hdrs) and all(h.scans for h in phdrs)
-    return hdrs, phdrs, J.plan_device_batch(hdrs, blobs, phdrs, pblobs, 2048, scales)
+    return hdrs, phdrs, J.plan_device_batch([("base", hdrs, blobs), ("prog", phdrs, pblobs)], 2048, scales)
 
 
 def test_the_test_files_are_what_they_should_be():

@@ -168,9 +168,9 @@ def filled(p):
 
 def test_plan_without_the_new_files_is_unchanged():
     hdrs, phdrs = [J.parse(b) for b in BASE], [J.parse_progressive(b) for b in PROG]
-    a = J.plan_device_batch(hdrs, BASE, phdrs, PROG, 2048, [1, 1])
-    b = J.plan_device_batch(hdrs, BASE, phdrs, PROG, 2048, [1, 1], ahdrs=[], ablobs=[])
-    assert (a.atot, a.any_off, a.aout_off, a.aout_bytes) == (None, None, 0, 0) == (b.atot, b.any_off, b.aout_off, b.aout_bytes)
+    a = J.plan_device_batch([("base", hdrs, BASE), ("prog", phdrs, PROG)], 2048, [1, 1])
+    b = J.plan_device_batch([("base", hdrs, BASE), ("prog", phdrs, PROG), ("pany", [], [])], 2048, [1, 1])
+    assert a.group("pany") is None and b.group("pany") is None and [g.kind for g in b.groups] == ["base", "prog"]
     assert a.total == b.total and a.out_offs == b.out_offs and np.array_equal(filled(a), filled(b))
     assert [o for o, _ in a.sections] == [o for o, _ in b.sections] and len(a.sections) == 4
 
@@ -180,13 +180,15 @@ def test_plan_with_the_new_group():
     hdrs, phdrs = [J.parse(b) for b in BASE], [J.parse_progressive(b) for b in PROG]
     lay = P.CASES["440-17x33"].baseline()
     lhdrs = [J.parse(lay, layouts="all")]
-    without = J.plan_device_batch(hdrs, BASE, phdrs, PROG, 2048, [1, 1], (), (), lhdrs, [lay])
-    p = J.plan_device_batch(hdrs, BASE, phdrs, PROG, 2048, [1, 1], (), (), lhdrs, [lay], ahdrs, ablobs)
+    three = [("base", hdrs, BASE), ("prog", phdrs, PROG), ("own", lhdrs, [lay])]
+    without = J.plan_device_batch(three, 2048, [1, 1])
+    p = J.plan_device_batch(three + [("pany", ahdrs, ablobs)], 2048, [1, 1])
+    own, pany = p.group("own"), p.group("pany")
     # the other groups' records lie where they lay, and their output too; the new records follow the others'
     assert [o for o, _ in p.sections[:len(without.sections)]] == [o for o, _ in without.sections]
-    assert p.out_offs[:3] == without.out_offs and p.lout_off == without.lout_off
+    assert p.out_offs[:3] == without.out_offs and own.out_off == without.group("own").out_off
     assert [a.dtype for _, a in p.sections[-3:]] == [J.PROG_HEADER_ANY_DTYPE, J.SCAN_DTYPE, J.TABLE_DTYPE]
-    assert list(p.any_off) == [o for o, _ in p.sections[-3:]] and p.any_off[0] >= without.data_off
+    assert list(pany.offs) == [o for o, _ in p.sections[-3:]] and pany.offs[0] >= without.data_off
     spans = [(o, o + a.nbytes) for o, a in p.sections] + [(p.data_off, p.total)]
     assert all(lo % 256 == 0 for lo, _ in spans) and spans == sorted(spans)
     assert all(a_hi <= b_lo for (_, a_hi), (b_lo, _) in zip(spans, spans[1:]))
@@ -195,23 +197,23 @@ def test_plan_with_the_new_group():
     assert (host[p.total:] == 0xA5).all() and len(p.blobs) == 3 + len(ablobs)
     for (o, a), blob in zip(p.blobs[3:], ablobs):
         assert host[o:o + len(blob)].tobytes() == blob
-    srec = dict(p.sections)[p.any_off[1]]
+    srec = dict(p.sections)[pany.offs[1]]
     for r in srec:
         o, blob = p.blobs[3 + int(r["image"])][0], ablobs[int(r["image"])]
         assert o <= p.data_off + int(r["data_off"]) <= p.data_off + int(r["data_end"]) <= o + len(blob)
     # output: behind the layout group from the next multiple of 256, images disjoint
-    assert p.aout_off == J.pad256(p.lout_off + p.lout_bytes) and p.aout_off % 256 == 0
+    assert pany.out_off == J.pad256(own.out_off + own.out_bytes) and pany.out_off % 256 == 0
     mine = p.out_offs[3:]
     sizes = [h.width * h.height * 3 for h in ahdrs]
-    assert mine[0] == p.aout_off and all(a + n <= b for a, n, b in zip(mine, sizes, mine[1:]))
-    assert mine[-1] + sizes[-1] == p.aout_off + p.aout_bytes
-    assert [p.aout_off + int(o) for o in dict(p.sections)[p.any_off[0]]["out_off"]] == mine
+    assert mine[0] == pany.out_off and all(a + n <= b for a, n, b in zip(mine, sizes, mine[1:]))
+    assert mine[-1] + sizes[-1] == pany.out_off + pany.out_bytes
+    assert [pany.out_off + int(o) for o in dict(p.sections)[pany.offs[0]]["out_off"]] == mine
 
 
 def test_binding_and_abi():
     from on_device_image_captioning_amd import _hip
     lib = _hip.load()
-    assert _hip.ABI_VERSION == 26 == lib.odic_abi_version()
+    assert _hip.ABI_VERSION == 27 == lib.odic_abi_version()
     for name in ("odic_jpeg_progressive_any_workspace_bytes", "odic_jpeg_decode_progressive_any"):
         assert name in _hip.EXPORTED_SYMBOLS and getattr(lib, name)
     assert lib.odic_jpeg_decode_progressive_any(None, None, 0, None) == -2

@@ -1,5 +1,5 @@
 """Search behind a given prefix, the parts that need no GPU: the argument rules (raised before any
-device work), header / binding agreement of the two entry points with the ABI still 26, the built library refusing bad
+device work), header / binding agreement of the two entry points with the ABI number of the header, the built library refusing bad
 arguments, and the reason the reset works: tests/prefix_model.py's reset state fed to the step model of
 tests/group_beam_model.py chooses at position P exactly what a seeding at position 0 chooses from the same candidates."""
 import ctypes
@@ -118,7 +118,7 @@ def test_header_and_binding_agree_and_the_abi_is_still_26():
     res, argtypes = _hip._SIGNATURES["odic_beam_reset_prefix"]
     want = [ctypes.POINTER(_hip.BeamState), ctypes.POINTER(_hip.EmbedArgs)] + [ctype(a) for a in args[2:]]
     assert res is ctypes.c_int and list(argtypes) == want
-    assert _hip.ABI_VERSION == 26 and re.search(r"#define ODIC_ABI_VERSION 26\b", text)
+    assert _hip.ABI_VERSION == 27 and re.search(r"#define ODIC_ABI_VERSION 27\b", text)
 
 
 def test_a_library_without_a_symbol_is_reported_as_stale(monkeypatch):
@@ -138,7 +138,7 @@ def test_the_library_refuses_bad_arguments_without_a_gpu():
         import __graft_entry__ as ge
         ge.build()
     lib = _hip.load()
-    assert lib.odic_abi_version() == 26
+    assert lib.odic_abi_version() == 27
 
     def fill(lin=16, ldlin=320, qexp=16, c=16, n_seq=2, P=5, rpi=3, N=6, T=12, d=64, E=16, **kw):
         ptr = dict(cond=c, key=c, va=c, vb=c, wfa=c, wfb=c, qk=c)

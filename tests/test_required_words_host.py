@@ -213,7 +213,7 @@ def test_header_declares_and_the_binding_binds_the_entry_point():
     assert list(argtypes) == [P, P, I32, P, I64, P, I32, ctypes.POINTER(_hip.BeamState), ctypes.POINTER(_hip.EmbedArgs),
                               I32, I32, I32, I64, I32, P]
     assert "odic_require_beam_step" in _hip.EXPORTED_SYMBOLS
-    assert _hip.ABI_VERSION == 26 and re.search(r"#define ODIC_ABI_VERSION 26\b", text)   # a pure addition
+    assert _hip.ABI_VERSION == 27 and re.search(r"#define ODIC_ABI_VERSION 27\b", text)   # a pure addition
 
 
 def test_the_library_refuses_bad_arguments_without_a_gpu():

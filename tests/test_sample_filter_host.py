@@ -214,7 +214,7 @@ def lib():
 
 def test_abi_version_is_unchanged(lib):
     from on_device_image_captioning_amd import _hip
-    assert _hip.ABI_VERSION == 26 and lib.odic_abi_version() == 26
+    assert _hip.ABI_VERSION == 27 and lib.odic_abi_version() == 27
 
 
 def test_refusals_need_no_gpu(lib):

@@ -216,7 +216,7 @@ def test_header_struct_and_binding_agree():
     assert len(args) == 9 and args[2].startswith("const odic_search_constraints*")
     res, argtypes = _hip._SIGNATURES["odic_topk_rows_constrained"]
     assert res is ctypes.c_int and len(argtypes) == 9 and argtypes[2] is ctypes.POINTER(_hip.SearchConstraints)
-    assert _hip.ABI_VERSION == 26 and re.search(r"#define ODIC_ABI_VERSION 26\b", text)
+    assert _hip.ABI_VERSION == 27 and re.search(r"#define ODIC_ABI_VERSION 27\b", text)
 
 
 def test_the_library_refuses_bad_arguments_without_a_gpu():
@@ -225,7 +225,7 @@ def test_the_library_refuses_bad_arguments_without_a_gpu():
         import __graft_entry__ as ge
         ge.build()
     lib = _hip.load()
-    assert lib.odic_abi_version() == 26
+    assert lib.odic_abi_version() == 27
 
     def call(N=4, V=100, k=3, ldl=100, logp=16, tv=16, ti=16, cons=True, **kw):
         f = dict(tokens=16, pos=16, row_valid=None, banned=None, n_banned=0, no_repeat_ngram=2, min_words=1, eos_idx=EOS,

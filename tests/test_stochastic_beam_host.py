@@ -115,7 +115,7 @@ def test_header_declares_and_the_binding_binds_the_entry_points():
     for name in ("odic_stochastic_beam_step", "odic_logsoftmax_sample_scored"):
         assert name in _hip.EXPORTED_SYMBOLS
     assert hasattr(ops, "stochastic_beam_step") and hasattr(ops, "logsoftmax_sample_scored")
-    assert _hip.ABI_VERSION == 26 and re.search(r"#define ODIC_ABI_VERSION 26\b", text)   # a pure addition
+    assert _hip.ABI_VERSION == 27 and re.search(r"#define ODIC_ABI_VERSION 27\b", text)   # a pure addition
     # the state struct is what it was: eleven pointers
     assert [n for n, _ in _hip.BeamState._fields_] == ["tokens", "logprobs", "anc", "cumul", "n_elem", "has_eos", "row_valid",
                                                        "next_tok", "pos", "done", "ctr"]
@@ -127,7 +127,7 @@ def test_the_library_refuses_bad_arguments_without_a_gpu():
         import __graft_entry__ as ge
         ge.build()
     lib = _hip.load()
-    assert lib.odic_abi_version() == 26
+    assert lib.odic_abi_version() == 27
     st = _hip.BeamState(*([16] * 11))
 
     def step(cv=16, ci=16, cp=16, g=16, state=st, emb=None, n_img=3, k=5, T=8, eos=EOS):

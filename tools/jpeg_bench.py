@@ -21,14 +21,14 @@ host's `Image.open(f).convert("RGB")`; with --progressive, their progressive re-
     python tools/jpeg_bench.py --gray --batches 16 64 --iters 20 --out profiles/r12_jpeg_gray_bench.json
 
 --cmyk: the same crops saved as mode CMYK (four components; Pillow writes Adobe transform 0 with component 0 at 2x2 for
-subsampling=2), decoded under non_rgb="convert": the device path with cmyk="device" (odic_jpeg4_decode) against the
+subsampling=2), decoded under non_rgb="convert": the device path with cmyk="device" (odic_jpeg_any_decode) against the
 host's `Image.open(f).convert("RGB")`.  This is the line that decides whether cmyk="device" becomes the default
 (DESIGN §4.25).
 
     python tools/jpeg_bench.py --cmyk --batches 16 64 --iters 20 --out profiles/jpeg_cmyk_bench.json
 
 --layouts: 640x480 gradient-plus-noise pictures written at 4:4:0 and 4:1:1 by the tests' writer (Pillow's encoder cannot),
-eight distinct files per layout repeated to the batch size: the device path with layouts="all" (odic_jpeg3_any_decode)
+eight distinct files per layout repeated to the batch size: the device path with layouts="all" (odic_jpeg_any_decode)
 against the host's `Image.open(f).convert("RGB")` on one thread.  One line per layout and batch.
 
     python tools/jpeg_bench.py --layouts --batches 16 64 --iters 20 --out profiles/jpeg_layouts_bench.json
